@@ -77,7 +77,14 @@ def parse_args(argv=None):
                          "host memory over gloo (RCCL refuses two ranks on one device)")
     ap.add_argument("--tiny", action="store_true", help="N=2 d_model=64 d_ff=128 h=4 latent=16 (launcher tests)")
     ap.add_argument("--selftest-cpu", action="store_true", help="launcher/step-loop self-test on CPU (see docstring)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, logits, mu, logvar, "
+                         "property predictions, a fixed sample of the updated parameters and of the gradients) as "
+                         "DIR/<name>.npy, float32 / float64, at most 64 MB (rank 0); e.g. DIR = bench_outputs/")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 # ---------------------------------------------------------------------------------- launcher
@@ -184,8 +191,10 @@ def selftest_workload(a, dev, world, rank):
     def fwd_loss(batch):
         logits = model(batch["src"], batch["trg"][:, :-1])
         ys = batch["trg"][:, 1:].reshape(-1)
-        return nn.functional.cross_entropy(logits.reshape(-1, vt), ys, ignore_index=synthetic.PAD_ID,
-                                           reduction="sum")
+        loss = nn.functional.cross_entropy(logits.reshape(-1, vt), ys, ignore_index=synthetic.PAD_ID, reduction="sum")
+        if a.dump_outputs:
+            fwd_loss.outputs = {"batch": batch, "loss": loss, "logits": logits}
+        return loss
     fwd_loss.model = model
     return inner, opt, fwd_loss
 
@@ -223,6 +232,9 @@ def hip_workload(a, dev, world, rank, mtype=None):
         ys = batch["trg"][:, 1:].contiguous().view(-1)
         ys_cond = batch["dconds"].unsqueeze(2).contiguous().view(-1, nc, 1) if nc else None
         loss, _, _, _ = loss_function(beta, prop, mol, ys_cond, ys, mu, lv, False, pad_id)
+        if a.dump_outputs:                # --dump-outputs: the last step's outputs are written after the timed region
+            fwd_loss.outputs = {"batch": batch, "loss": loss, "logits": mol, "mu": mu, "logvar": lv,
+                                "prop": prop if nc else None}
         return loss
     fwd_loss.model = model            # the data-parallel wrapper at N > 1 (what a trainer calls), else the model itself
 
@@ -548,6 +560,53 @@ def replay_switch_children(rows=512, budget_s=200.0):
     return out
 
 
+# ------------------------------------------------------------------------------- output dump
+DUMP_MAX_VALUES = 1 << 21         # per array (8 MiB in float32): the at most seven arrays stay under 64 MB
+
+
+def _dump_sample(t, seed):
+    """t itself while it has at most DUMP_MAX_VALUES elements, else a fixed sample of them (1-D): positions drawn
+    from a CPU generator seeded with `seed`, sorted, so the same positions for the same size on every run."""
+    import torch
+    if t.numel() <= DUMP_MAX_VALUES:
+        return t.detach()
+    flat = t.detach().reshape(-1)
+    idx = torch.randint(flat.numel(), (DUMP_MAX_VALUES,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(out_dir, outs, inner, skipped_rows):
+    """--dump-outputs: what the last timed step handed its caller, as out_dir/<name>.npy.  The loss in float64, the
+    rest in float32.  With the trainer's row skipping (skipped_rows) the logits of rows whose target is <pad> are not
+    computed (their values are unspecified) and are written as zeros.  Parameters and gradients are concatenated in
+    named_parameters() order (a parameter without a gradient contributes zeros) and sampled like any other large
+    array.  Returns {name: shape} of what was written."""
+    import numpy as np
+    import torch
+    from gct_plus_amd import synthetic
+    arrays = {"loss": outs["loss"].detach().reshape(()).double()}
+    logits = outs["logits"].detach()
+    if skipped_rows:
+        live = outs["batch"]["trg"][:, 1:] != synthetic.PAD_ID
+        logits = logits.reshape(live.shape[0], live.shape[1], -1) * live.unsqueeze(-1).to(logits.dtype)
+    arrays["logits"] = _dump_sample(logits, 1)
+    for i, name in enumerate(("mu", "logvar", "prop")):
+        if outs.get(name) is not None:
+            arrays[name] = _dump_sample(outs[name], 2 + i)
+    with torch.no_grad():
+        params = list(inner.parameters())
+        arrays["parameters"] = _dump_sample(torch.cat([p.reshape(-1) for p in params]), 5)
+        arrays["gradients"] = _dump_sample(torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1)
+                                                      for p in params]), 6)
+    host = {n: v.cpu().numpy().astype(np.float64 if n == "loss" else np.float32) for n, v in arrays.items()}
+    total = sum(v.nbytes for v in host.values())
+    assert total <= 64 * 2 ** 20, f"--dump-outputs would write {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for n, v in host.items():
+        np.save(os.path.join(out_dir, n + ".npy"), v)
+    return {n: list(v.shape) for n, v in host.items()}
+
+
 # ------------------------------------------------------------------------------------ worker
 def worker(a):
     import torch
@@ -665,6 +724,9 @@ def worker(a):
         # kinds cost ~2 % of the step in event overhead); --all-kernel-timing restores the rest
         ops.PROFILE_KINDS = None if a.all_kernel_timing else {"gemm_fwd"}
     dt, last = region(a.warmup, a.steps)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = dump_outputs(a.dump_outputs, fwd_loss.outputs, inner, skipped_rows=not cpu and not a.dense_decoder)
     host_main = {"ms_per_step": round(host["s"] / max(host["n"], 1) * 1e3, 3),
                  "blocked_in_readback_ms_per_step": round(ops.HOST_BLOCKED_S[0] / max(host["n"], 1) * 1e3, 3) if ops else None,
                  "note": "wall time this rank's Python spent inside the timed steps (ctypes launches, autograd, allocator) and "
@@ -779,6 +841,8 @@ def worker(a):
                               "seq_len": S, "parallelism": f"dp{world}"},
                    "ranks": world, "backend": backend, "launcher": launcher,
                    "final_loss_per_sample": round(final_loss, 4)}
+            if dumped is not None:
+                out["dumped_outputs"] = dumped
             if multi is not None:
                 out["multi_rank"] = multi
             print(json.dumps(out), flush=True)
@@ -808,6 +872,8 @@ def worker(a):
                 "roofline": roof,
                 "host": host_main,
             }
+            if dumped is not None:
+                out["dumped_outputs"] = dumped
             try:                                       # which box is this: the matrix rate it sustains (diagnostics library)
                 from gct_plus_amd import graphdiag
                 out["box"] = graphdiag.mfma_probe()

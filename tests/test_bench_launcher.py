@@ -66,6 +66,45 @@ def test_dead_rank_fails_the_launch():
     assert r.returncode == 3 and not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
+def _load_dump(d):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d)) if f.endswith(".npy")}
+
+
+def test_dump_outputs_cpu_selftest_is_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's outputs, float32 / float64 only; the same arguments give the same
+    inputs, so two runs write the same arrays, and the loss written is the one the line reports for the last step."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        out = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8", "--selftest-cpu", "--dump-outputs", d])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+        dumps.append(_load_dump(d))
+        assert sorted(out["dumped_outputs"]) == sorted(dumps[-1])
+    a, b = dumps
+    assert {"loss", "logits", "parameters", "gradients"} <= set(a) and a.keys() == b.keys()
+    for n in a:
+        assert a[n].dtype in (np.float32, np.float64) and np.isfinite(a[n]).all(), n
+        assert np.array_equal(a[n], b[n]), n
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+    assert abs(float(a["loss"]) / 8 - out["final_loss_per_sample"]) < 1e-3
+
+
+@pytest.mark.gpu
+def test_dump_outputs_real_model(tmp_path):
+    import numpy as np
+    d = str(tmp_path / "dump")
+    out = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8", "--model-type", "pvaetf", "--tiny",
+                "--no-alt-mode", "--no-fixed-len-leg", "--dump-outputs", d], timeout=900)
+    got = _load_dump(d)
+    assert set(got) == {"loss", "logits", "mu", "logvar", "prop", "parameters", "gradients"}
+    for n, v in got.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), n
+    assert got["logits"].ndim == 3 and got["logits"].shape[0] == 8 and np.abs(got["gradients"]).max() > 0
+    assert abs(float(got["loss"]) / 8 - out["final_loss_per_sample"]) < 1e-3 * abs(out["final_loss_per_sample"]) + 1e-4
+
+
 @pytest.mark.gpu
 def test_plain_gpus2_real_model_shared_gpu():
     out = _run(["--gpus", "2", "--steps", "3", "--warmup", "2", "--batch", "8", "--model-type", "scavaetf",

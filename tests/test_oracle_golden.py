@@ -31,6 +31,19 @@ def cfg_from(fx):
                       use_cond2lat=c["use_cond2lat"])
 
 
+def assert_grad_matches(P, name, ref_grads):
+    g, e = P[name].grad, ref_grads[name]
+    if name.endswith("k_linear.bias"):
+        # the scores of a row are shifted alike by the key bias and softmax ignores the shift: in exact arithmetic
+        # this gradient is zero, and the reference's stored value and ours are fp32 rounding residue whose digits
+        # follow the host CPU's summation order.  Both must be residue on the scale of the key weights' gradient.
+        scale = float(ref_grads[name[:-len("bias")] + "weight"].abs().max())
+        assert float(e.abs().max()) <= 1e-6 * scale, name
+        assert float(g.abs().max()) <= 1e-6 * scale, name
+        return
+    assert torch.allclose(g, e, atol=1e-5 * float(e.abs().max()) + 1e-7, rtol=1e-4), name
+
+
 def test_known_answers(golden_dir):
     g1 = json.load(open(os.path.join(golden_dir, "g1_known_answers.json")))
     y = O.norm(torch.tensor([[1.0, 2.0, 3.0, 4.0]]), torch.ones(4), torch.zeros(4))
@@ -88,8 +101,7 @@ def test_forward_loss_grads(golden_dir, mtype):
         if name in fx["no_grad_params"]:
             assert P[name].grad is None, name
             continue
-        g, e = P[name].grad, fx["grads"][name]
-        assert torch.allclose(g, e, atol=1e-5 * float(e.abs().max()) + 1e-7, rtol=1e-4), name
+        assert_grad_matches(P, name, fx["grads"])
     if mtype == "vaetf":   # dead encoder.fc_* (SURVEY 2.3 caveat)
         assert set(fx["no_grad_params"]) == {"encoder.fc_mu.weight", "encoder.fc_mu.bias",
                                              "encoder.fc_log_var.weight", "encoder.fc_log_var.bias"}
@@ -157,8 +169,8 @@ def test_cond2dec_path(golden_dir):
     for got, key in ((loss, "loss"), (rce, "rce"), (rce_prop, "rce_prop"), (kld, "kld")):
         assert abs(got.item() - fx[key]) <= 1e-5 * abs(fx[key]), key
     loss.backward()
-    for name, e in fx["grads"].items():
-        assert torch.allclose(P[name].grad, e, atol=1e-5 * float(e.abs().max()) + 1e-7, rtol=1e-4), name
+    for name in fx["grads"]:
+        assert_grad_matches(P, name, fx["grads"])
 
 
 # ------------------------------------------------------------------ G6: reference-written checkpoints
