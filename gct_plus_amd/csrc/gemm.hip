@@ -63,7 +63,6 @@ struct GemmArgs {
   uint32_t thr;
   GctRng rng;
   float* bias_slab;  // wgrad fast path: per-split column sums of dY, [nsplit][M] (nullptr: off)
-  int stagger;       // s_sleep(127) repeats for the second resident workgroup of each CU
   int64_t row_base;  // rows in front of this launch's row 0 (a launch on a row range keeps the dropout coordinates)
   const int32_t* quad_map;  // rows are a quad compaction (csrc/liverows.hip): dropout coordinates of compact quad q are
                             // those of original quad quad_map[q] (nullptr: identity)
@@ -451,17 +450,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GemmArgs g) {
 // =====================================================================================
 // epilogue stores: 16 B per lane, non-temporal -- the outputs (84-336 MB) are far larger than the L2
 // and are not re-read by this kernel, so they should not evict the operand panels (A/B: +3-7 % on the
-// K = 512 shapes, +1 % on the step; -DGCT_EPI_PLAIN restores ordinary stores)
+// K = 512 shapes, +1 % on the step, against ordinary stores)
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void epi_store4(float* p, const float (&x)[4]) {
 #ifdef GCT_LAB_NO_EPI_STORE   // tools/gemm_lab.hip: arithmetic kept alive, (almost) nothing stored
   if (x[0] != 123456.789f) return;
 #endif
-#ifdef GCT_EPI_PLAIN
-  *reinterpret_cast<float4*>(p) = make_float4(x[0], x[1], x[2], x[3]);
-#else
   __builtin_nontemporal_store(f32x4_t{x[0], x[1], x[2], x[3]}, reinterpret_cast<f32x4_t*>(p));
-#endif
 }
 
 struct FastEpi {
@@ -630,13 +625,6 @@ gemm_f32_fast_kernel(const GemmArgs g) {
   __shared__ __attribute__((aligned(16))) float lds[4 * TILE_FLOATS];  // A0 B0 A1 B1 : 64 KB
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-  // Two workgroups share a CU and, started together, stay in lockstep: their prologues and
-  // epilogues coincide and the MFMA pipe idles.  Delaying the second resident workgroup of the
-  // first dispatch round by about half a tile de-phases them for the rest of the launch (tiles
-  // have equal duration, so the offset persists).  Placement is a speed guess only.
-  if (g.stagger > 0 && ((blockIdx.x >> 8) & 1)) {
-    for (int i = 0; i < g.stagger; ++i) __builtin_amdgcn_s_sleep(127);
-  }
 
   const unsigned tiles_n = (unsigned)((g.N + BN - 1) / BN);
   const unsigned tiles_m = (unsigned)((g.M + BM - 1) / BM);
@@ -857,21 +845,6 @@ gemm_f32_fast_kernel(const GemmArgs g) {
 
 int64_t g_x6_kernel_launches = 0;   // gemm_x6_kernel launches (a tail-balanced call makes two)
 #include "gemm_x6.inc"
-#ifdef GCT_LAB_X6P
-// tools/gemm_lab.hip only: the persistent stream-K form of the forward / dgrad kernels (round-4 experiment, measured and
-// not adopted: profiles/r04_gemm_experiment_persistent_*.log).  Nothing of it is compiled into the library.
-#include "../../tools/gemm_x6p.inc"
-#include "../../tools/gemm_x6w.inc"      // one wave per SIMD (round-4 experiment, forward only): g_x6p_on == 2
-#include "../../tools/gemm_x6h.inc"      // two 4-wave workgroups per CU, 128 x 128 tiles (round-4 experiment, forward only): g_x6p_on == 4
-constexpr int X6P_SYNC_SLOTS = 32;
-int g_x6p_on = 0;
-int* g_x6p_counters = nullptr;
-unsigned g_x6p_seq = 0;
-inline int* x6p_counter_slot() {
-  if (!g_x6p_counters) return nullptr;
-  return g_x6p_counters + (size_t)((g_x6p_seq++) % X6P_SYNC_SLOTS) * 256;
-}
-#endif
 
 // =====================================================================================
 // SKINNY-M forward kernel (KV-cached decode: M = batch rows per step = 512): 64x64 tiles, 4 waves
@@ -1175,9 +1148,8 @@ inline int gemm_mode() {
 // single source of truth for "this launch takes gemm_f32_fast_kernel"
 template <bool A_KC, bool B_KC>
 bool fast_ok(const GemmArgs& g, bool vec) {
-  static const bool no_fast = getenv("GCT_GEMM_NO_FAST") != nullptr;   // A/B switch for benchmarks
   auto seg_ok = [](int64_t nper, int64_t extent, int64_t gran) { return nper >= extent || nper % gran == 0; };
-  return vec && !no_fast && g.K % BK == 0 && g.ksplit % BK == 0 && g.M >= 4 && g.N >= 4 &&
+  return vec && g.K % BK == 0 && g.ksplit % BK == 0 && g.M >= 4 && g.N >= 4 &&
          (A_KC ? seg_ok(g.a_nper, g.K, BK) : (seg_ok(g.a_nper, g.M, BM) && g.M % 4 == 0)) &&
          (B_KC ? seg_ok(g.b_nper, g.N, BN) : (seg_ok(g.b_nper, g.K, BK) && g.N % 4 == 0)) &&
          g.N % 4 == 0 && g.ldc % 4 == 0 && gct_aligned16(g.c0) && g.c_d1 % 4 == 0 && g.c_d2 % 4 == 0 &&
@@ -1185,6 +1157,26 @@ bool fast_ok(const GemmArgs& g, bool vec) {
          (!g.bias0 || (gct_aligned16(g.bias0) && g.bias_d1 % 4 == 0 && g.bias_d2 % 4 == 0)) &&
          (!g.resid || gct_aligned16(g.resid)) && (!g.pre || gct_aligned16(g.pre)) &&
          (!g.pre_in || gct_aligned16(g.pre_in)) && 130 * g.lda < (1ll << 31) && 130 * g.ldb < (1ll << 31);
+}
+
+// ---- split rules: each slab count is computed here once, for the launch and for the workspace queries alike
+
+// bytes of s fp32 slabs of [rows][cols]; 0 when s <= 1 (no split, no slabs)
+inline int64_t slab_bytes(int64_t s, int64_t rows, int64_t cols) {
+  return s > 1 ? s * rows * cols * (int64_t)sizeof(float) : 0;
+}
+
+// skinny M (decode steps): 64x64 tiles when the 128x128 grid would leave most CUs idle
+// (192: with more tiles the bf16x6 kernel wins even on half the CUs -- decode at n >= 6144 lost 5-8 % with 384)
+inline bool skinny_m(int64_t M, int64_t N) { return ((M + BM - 1) / BM) * ((N + BN - 1) / BN) < 192; }
+
+// K-splits of the skinny fp32 route (gemm_f32_small_kernel; 1 = none): ~768 workgroups, >= 4 K-tiles per split
+int skinny_splits(int64_t M, int64_t N, int64_t K) {
+  const int64_t tiles = ((M + 63) / 64) * ((N + 63) / 64);
+  if (tiles <= 0) return 1;
+  int64_t ns = 768 / tiles;
+  if (ns > K / BK / 4) ns = K / BK / 4;
+  return ns < 1 ? 1 : (int)ns;
 }
 
 // Tail balancing for the bf16x6 forward / dgrad launches (one 128x256 workgroup per CU, 256 CUs): when the
@@ -1196,10 +1188,9 @@ bool fast_ok(const GemmArgs& g, bool vec) {
 // K-splits (1 = no) and the first tail row
 int x6_tail_plan(int64_t M, int64_t N, int64_t K, int64_t* m1_out) {
   constexpr int64_t CUS = 256;
-  static const bool off = getenv("GCT_X6_NO_TAIL_SPLIT") != nullptr;
   const int64_t tm = (M + XBM - 1) / XBM, tn = (N + XBN - 1) / XBN, tiles = tm * tn;
   const int64_t rem = tiles % CUS;
-  if (off || tiles <= CUS || rem == 0 || rem % tn != 0 || K % XBK != 0) return 1;
+  if (tiles <= CUS || rem == 0 || rem % tn != 0 || K % XBK != 0) return 1;
   const int64_t nkt = K / XBK;
   int best = 1;
   double cost = 1.0;                                   // duration of the last round, in rounds
@@ -1215,6 +1206,70 @@ int x6_tail_plan(int64_t M, int64_t N, int64_t K, int64_t* m1_out) {
   return best;
 }
 
+// Few 128x256 tiles but a long reduction (FFN-2 of a 1 024 .. 8 192-row decode step: 32-64 tiles, K = 2 048): the bf16x6
+// kernel with K split s ways into fp32 slabs + the fix-up kernel fills the chip where the plain launch would use a
+// quarter of it and the skinny fp32 kernel would run at the fp32 pipe's rate.
+// number of K-splits of that route (1 = not taken)
+int x6_splitk_all_plan(int64_t M, int64_t N, int64_t K) {
+  constexpr int64_t CUS = 256;
+  const int64_t tiles = ((M + XBM - 1) / XBM) * ((N + XBN - 1) / XBN), nkt = K / XBK;
+  // K = 1024 (the folded cross-attention output projection of a decode step) pays only from 2 048 rows on: with fewer
+  // the panel kernel is faster (+7 % per step at n = 1 024, measured both ways at 1 024 ... 8 192)
+  if (tiles > CUS / 2 || K % XBK != 0 || nkt < 32 || M < 1024 || (nkt < 64 && M < 2048)) return 1;
+  int64_t sp = CUS / tiles;
+  if (sp > nkt / 8) sp = nkt / 8;                      // >= 8 K-tiles per split
+  if (sp > 8) sp = 8;
+  return sp < 2 ? 1 : (int)sp;
+}
+
+// ---- route thresholds (measured; each one moves launches between kernels)
+
+// 64 x 128 tiles of the bf16x6 small-tile kernel
+inline int64_t x6s_tiles(int64_t M, int64_t N) { return ((M + SBM - 1) / SBM) * ((N + SBN - 1) / SBN); }
+
+// few 128 x 256 tiles but enough 64 x 128 ones: the small-tile bf16x6 kernel (forward and dgrad; decode steps of
+// 2 000-4 000 rows, training at small batches).  Measured (tools/kernel_bench.py --suite decgemm, rows 1 024 ... 5 184):
+// a 64 x 128 tile takes 0.75 us per K-tile alone on its CU and 1.45 us when two share it, a 128 x 256 tile 2.8 us;
+// from K = 2 048 on the large kernel's K-split routes fill the chip and win, at K = 1 024 only while every small tile
+// has a CU to itself
+inline bool x6s_shape(const GemmArgs& g) {
+  const int64_t big = ((g.M + XBM - 1) / XBM) * ((g.N + XBN - 1) / XBN), small = x6s_tiles(g.M, g.N), nkt = g.K / XBK;
+  return big <= 160 && small >= 96 && small <= (nkt <= 16 ? 512 : 256) && nkt <= 32;
+}
+
+// K <= 1 024 and a short tail: the tail rows of a tail-balanced bf16x6 launch on 64 x 128 tiles (gemm_x6s_kernel, up
+// to two per CU) finish with their own epilogue -- no slabs, no fix-up launch (48.6 -> 48.2 ms per step with the
+// forward launches alone) -- while they are at most this many tiles
+constexpr int64_t X6_TAIL_SMALL_MAX = 512;
+
+// skinny fp32 forwards: the panel kernel while it has at most this many 32 x 32 (resp. 32 x 64) tiles; 4096: +9 % / +3 %
+// per decode step at n = 1024 / 4096 over 384
+constexpr int64_t PANEL32_MAX_TILES = 4096, PANEL64_MAX_TILES = 768;
+
+// ---- slab routes: K split into fp32 slabs at ws, then splitk_epilogue_kernel applies g's epilogue to their sum
+
+// the split-K form of g: raw partial sums of `splits` K ranges (whole 32-wide K-tiles) into dense [M][N] slabs at ws
+static_assert(BK == XBK, "the fp32 and bf16x6 kernels split K at the same granularity");
+GemmArgs slab_args(const GemmArgs& g, int splits, float* ws) {
+  const int64_t nkt = g.K / BK;
+  GemmArgs p = g;
+  p.ksplit = ((nkt + splits - 1) / splits) * BK;
+  p.nsplit = (int)((g.K + p.ksplit - 1) / p.ksplit);
+  p.epi = EPI_SLAB; p.c0 = ws; p.ldc = g.N; p.slab_stride = g.M * g.N;
+  p.c_d1 = p.c_d2 = 0; p.c_nper = INT64_MAX / 4; p.bias0 = nullptr; p.resid = nullptr; p.pre = nullptr; p.pre_in = nullptr;
+  return p;
+}
+
+int launch_fixup(const GemmArgs& g, const GemmArgs& slabs, hipStream_t st, const char* name) {
+  const int64_t patches = ((g.M + 3) / 4) * (g.N / 4);
+  hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((patches + 255) / 256)), dim3(256), 0, st, g,
+                     (const float*)slabs.c0, slabs.nsplit, slabs.slab_stride);
+  GCT_LAUNCH_CHECK(name);
+  return GCT_OK;
+}
+
+// executor of the bf16x6 route: plain, or tail-balanced (x6_tail_plan) with the tail rows on the small-tile kernel
+// or K-split into slabs.  Not in the planner: it depends on whether the stream is being captured.
 template <int MODE>
 int launch_x6_tail_split(const GemmArgs& g, hipStream_t st, float* ws, int64_t ws_bytes) {
   if (MODE == X6_WGRAD || g.nsplit != 1 || !ws || !gct_aligned16(ws)) return launch_x6<MODE>(g, st);
@@ -1222,7 +1277,7 @@ int launch_x6_tail_split(const GemmArgs& g, hipStream_t st, float* ws, int64_t w
   const int best = x6_tail_plan(g.M, g.N, g.K, &m1);
   const int64_t m2 = g.M - m1, nkt = g.K / XBK;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;   // keep captured graphs to one kernel per GEMM
-  if (best == 1 || (int64_t)best * m2 * g.N * (int64_t)sizeof(float) > ws_bytes ||
+  if (best == 1 || slab_bytes(best, m2, g.N) > ws_bytes ||
       hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
     return launch_x6<MODE>(g, st);
   GemmArgs head = g;
@@ -1237,224 +1292,132 @@ int launch_x6_tail_split(const GemmArgs& g, hipStream_t st, float* ws, int64_t w
   if (e.pre) e.pre += m1 * g.ldc;
   // pre_in read through the quad map keeps the forward's row space: the tail finds its rows through row_base
   if (e.pre_in && !(g.pre_rows > 0 && g.quad_map)) e.pre_in += m1 * g.ldc;
-  {
-    // K <= 1 024 and a short tail: the tail rows on 64 x 128 tiles (gemm_x6s_kernel, up to two per CU) finish with
-    // their own epilogue -- no slabs, no fix-up launch (48.6 -> 48.2 ms per step with the forward launches alone)
-    static const int small_cap = getenv("GCT_X6_TAIL_SMALL") ? atoi(getenv("GCT_X6_TAIL_SMALL")) : 512;  // A/B switch: 0 = off
-    static const int small_dg = getenv("GCT_X6_TAIL_SMALL_DGRAD") ? atoi(getenv("GCT_X6_TAIL_SMALL_DGRAD")) : 1;
-    const int64_t small = ((m2 + SBM - 1) / SBM) * ((g.N + SBN - 1) / SBN);
-    if (nkt <= 32 && small <= small_cap) {
-      if (MODE == X6_FWD && x6s_ok(e, true)) return launch_x6s<X6_FWD>(e, st);
-      if (MODE == X6_DGRAD && small_dg && x6s_dgrad_ok(e, true)) return launch_x6s<X6_DGRAD>(e, st);
-    }
+  if (nkt <= 32 && x6s_tiles(m2, g.N) <= X6_TAIL_SMALL_MAX) {
+    if (MODE == X6_FWD && x6s_ok(e, true)) return launch_x6s<X6_FWD>(e, st);
+    if (MODE == X6_DGRAD && x6s_dgrad_ok(e, true)) return launch_x6s<X6_DGRAD>(e, st);
   }
-  GemmArgs p = e;
-  p.nsplit = best;
-  p.ksplit = ((nkt + best - 1) / best) * XBK;
-  p.nsplit = (int)((g.K + p.ksplit - 1) / p.ksplit);
-  p.epi = EPI_SLAB; p.c0 = ws; p.ldc = g.N; p.slab_stride = m2 * g.N;
-  p.c_d1 = p.c_d2 = 0; p.c_nper = INT64_MAX / 4; p.bias0 = nullptr; p.resid = nullptr; p.pre = nullptr; p.pre_in = nullptr;
+  const GemmArgs p = slab_args(e, best, ws);
   rc = launch_x6<MODE>(p, st);
   if (rc) return rc;
-  const int64_t patches = ((m2 + 3) / 4) * (g.N / 4);
-  hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((patches + 255) / 256)), dim3(256), 0, st, e,
-                     (const float*)ws, p.nsplit, p.slab_stride);
-  GCT_LAUNCH_CHECK("x6 tail fix-up");
-  return GCT_OK;
+  return launch_fixup(e, p, st, "x6 tail fix-up");
 }
 
-// Few 128x256 tiles but a long reduction (FFN-2 of a 1 024 .. 8 192-row decode step: 32-64 tiles, K = 2 048): the bf16x6
-// kernel with K split s ways into fp32 slabs + the fix-up kernel fills the chip where the plain launch would use a
-// quarter of it and the skinny fp32 kernel would run at the fp32 pipe's rate.  Returns 1 if it took the launch.
-// number of K-splits of that route (1 = not taken); shared with gct_linear_fwd_ws_bytes
-int x6_splitk_all_plan(int64_t M, int64_t N, int64_t K) {
-  constexpr int64_t CUS = 256;
-  const int64_t tiles = ((M + XBM - 1) / XBM) * ((N + XBN - 1) / XBN), nkt = K / XBK;
-  // K = 1024 (the folded cross-attention output projection of a decode step) pays only from 2 048 rows on: with fewer
-  // the panel kernel is faster (+7 % per step at n = 1 024, measured both ways at 1 024 ... 8 192)
-  if (tiles > CUS / 2 || K % XBK != 0 || nkt < 32 || M < 1024 || (nkt < 64 && M < 2048)) return 1;
-  int64_t sp = CUS / tiles;
-  if (sp > nkt / 8) sp = nkt / 8;                      // >= 8 K-tiles per split
-  if (sp > 8) sp = 8;
-  return sp < 2 ? 1 : (int)sp;
-}
-template <int MODE>
-int launch_x6_splitk_all(const GemmArgs& g, hipStream_t st, float* ws, int64_t ws_bytes, int* taken) {
-  *taken = 0;
-  if ((MODE != X6_FWD && MODE != X6_DGRAD) || g.nsplit != 1 || !ws || !gct_aligned16(ws)) return GCT_OK;
-  const int64_t sp = x6_splitk_all_plan(g.M, g.N, g.K), nkt = g.K / XBK;
-  if (sp < 2 || sp * g.M * g.N * (int64_t)sizeof(float) > ws_bytes) return GCT_OK;
-  GemmArgs p = g;
-  p.ksplit = ((nkt + sp - 1) / sp) * XBK;
-  p.nsplit = (int)((g.K + p.ksplit - 1) / p.ksplit);
-  p.epi = EPI_SLAB; p.c0 = ws; p.ldc = g.N; p.slab_stride = g.M * g.N;
-  p.c_d1 = p.c_d2 = 0; p.c_nper = INT64_MAX / 4; p.bias0 = nullptr; p.resid = nullptr; p.pre = nullptr; p.pre_in = nullptr;
-  int rc = launch_x6<MODE>(p, st);
-  if (rc) return rc;
-  const int64_t patches = ((g.M + 3) / 4) * (g.N / 4);
-  hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((patches + 255) / 256)), dim3(256), 0, st, g,
-                     (const float*)ws, p.nsplit, p.slab_stride);
-  GCT_LAUNCH_CHECK("x6 split-K fix-up");
-  *taken = 1;
-  return GCT_OK;
+// ---- the route of one GEMM call: plan_gemm decides, launch() executes
+struct GemmRoute {
+  enum Kind {
+    X6S,            // gemm_x6s_kernel: 64 x 128 bf16x6 tiles over the whole problem
+    X6_SPLITK_ALL,  // gemm_x6_kernel with K split `splits` ways into slabs + fix-up
+    PANEL_THIN,     // gemm_f32_panel_kernel<32, RAGGED>: N <= 32
+    PANEL32,        // gemm_f32_panel_kernel<32>: the whole reduction in one workgroup per 32 x 32 tile
+    PANEL64,        // gemm_f32_panel_kernel<64>
+    F32_SMALL,      // gemm_f32_small_kernel: 64 x 64 fp32 tiles, K split `splits` ways into slabs + fix-up when > 1
+    X6,             // gemm_x6_kernel: 128 x 256 bf16x6 tiles, tail-balanced by launch_x6_tail_split
+    F32_FAST,       // gemm_f32_fast_kernel
+    F32_VEC,        // gemm_f32_kernel<VEC = true>
+    F32,            // gemm_f32_kernel<VEC = false>
+  } kind;
+  int splits;
+};
+
+// The first row whose shape condition holds wins.  Pure: no launches, no environment; `mode` is the arithmetic mode,
+// ws / ws_bytes the caller's workspace (a slab route is taken only where its slabs fit).
+template <bool A_KC, bool B_KC>
+GemmRoute plan_gemm(const GemmArgs& g, bool vec, int mode, const float* ws, int64_t ws_bytes) {
+  constexpr bool FWD = A_KC && B_KC, DGRAD = A_KC && !B_KC;
+  constexpr int MODE = A_KC ? (B_KC ? X6_FWD : X6_DGRAD) : X6_WGRAD;
+  const bool x6 = mode == GCT_GEMM_BF16X6;
+  const bool x6_fwd = x6 && FWD && g.epi < EPI_D0, x6_dgrad = x6 && DGRAD && g.epi >= EPI_D0 && g.epi < EPI_SLAB;
+  const bool ws_ok = ws && gct_aligned16(ws);
+  if (x6_fwd || x6_dgrad) {
+    const bool x6s = x6_fwd ? x6s_ok(g, vec) : x6s_dgrad_ok(g, vec);
+    if (x6s && x6s_shape(g)) return {GemmRoute::X6S, 1};
+    // weight segments of 128 rows (the sampler's mu | log_var, N = 2 x 128): not a whole number of 256-row tiles per
+    // segment, so the large kernel cannot take them -- the small-tile kernel for the whole problem instead of fp32 MFMA
+    if (x6_fwd && x6s && !x6_ok<X6_FWD>(g, vec) && x6s_tiles(g.M, g.N) >= 96) return {GemmRoute::X6S, 1};
+    // few tiles, long reduction (decode FFN-2; dgrad with K' = 1 536 / 2 048 at batch 64): K split over the whole problem
+    const int sp = x6_splitk_all_plan(g.M, g.N, g.K);
+    if (x6_ok<MODE>(g, vec) && g.nsplit == 1 && ws_ok && sp > 1 && slab_bytes(sp, g.M, g.N) <= ws_bytes)
+      return {GemmRoute::X6_SPLITK_ALL, sp};
+  }
+  // narrow outputs (the vocabulary head, N = 28-31): the ragged panel kernel, exact fp32 MFMA, M / 32 workgroups
+  if (FWD && vec && g.N <= 32 && g.K % 256 == 0 && g.epi == GCT_EPI_BIAS && g.nsplit == 1 && g.b_nper >= g.N &&
+      g.c_nper >= g.N && g.M >= 1 && g.lda * 4 * 33 < (1ll << 31) && g.ldb * 4 * 33 < (1ll << 31) && g.M < (1ll << 36))
+    return {GemmRoute::PANEL_THIN, 1};
+  const bool fast = fast_ok<A_KC, B_KC>(g, vec);
+  if (FWD && fast && g.nsplit == 1 && skinny_m(g.M, g.N) && g.epi < EPI_D0 && (g.b_nper >= g.N || g.b_nper % 64 == 0)) {
+    // ... the panel kernel (whole reduction in one workgroup, one launch) when even 64 x 64 tiles are few
+    if (g.K % 256 == 0 && g.lda * 4 * 33 < (1ll << 31) && g.ldb * 4 * 65 < (1ll << 31) &&
+        (g.c_nper >= g.N || g.c_nper % 64 == 0)) {
+      const int64_t tm32 = (g.M + 31) / 32;
+      if (g.N % 32 == 0 && (g.b_nper >= g.N || g.b_nper % 32 == 0) && tm32 * (g.N / 32) <= PANEL32_MAX_TILES)
+        return {GemmRoute::PANEL32, 1};
+      if (g.N % 64 == 0 && tm32 * (g.N / 64) <= PANEL64_MAX_TILES) return {GemmRoute::PANEL64, 1};
+    }
+    int64_t ns = 1;
+    if (ws_ok) {
+      // never more slabs than the caller's workspace holds (fewer splits, same result up to summation order)
+      const int64_t slab = g.M * g.N * (int64_t)sizeof(float);
+      ns = skinny_splits(g.M, g.N, g.K);
+      if (ns * slab > ws_bytes) ns = ws_bytes / slab;
+      if (ns < 1) ns = 1;
+    }
+    return {GemmRoute::F32_SMALL, (int)ns};
+  }
+  if (x6 && (A_KC || !B_KC) && x6_ok<MODE>(g, vec)) return {GemmRoute::X6, 1};
+  return {fast ? GemmRoute::F32_FAST : (vec ? GemmRoute::F32_VEC : GemmRoute::F32), 1};
 }
 
 template <bool A_KC, bool B_KC>
-int launch(const GemmArgs& g, bool vec, hipStream_t st, float* skinny_ws = nullptr, int64_t ws_bytes = 0) {
+int launch(const GemmArgs& g, bool vec, hipStream_t st, float* ws = nullptr, int64_t ws_bytes = 0) {
+  constexpr int MODE = A_KC ? (B_KC ? X6_FWD : X6_DGRAD) : X6_WGRAD;
   const int64_t tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN) * g.nsplit;
   if (tiles <= 0) return GCT_OK;
   if (tiles > INT_MAX) {
     gct_set_error("gemm: grid too large");
     return GCT_ERR_ARG;
   }
-  dim3 grid((unsigned)tiles), block(256);
-  const bool fast = fast_ok<A_KC, B_KC>(g, vec);
-  static const int stagger_env = getenv("GCT_GEMM_STAGGER") ? atoi(getenv("GCT_GEMM_STAGGER")) : -1;
-  if (A_KC && B_KC && gemm_mode() == GCT_GEMM_BF16X6 && g.epi < EPI_D0) {
-    // few 128 x 256 tiles but enough 64 x 128 ones: the small-tile bf16x6 kernel (decode steps of 2 000-4 000 rows,
-    // training at small batches)
-    static const int x6s_on = getenv("GCT_X6S") ? atoi(getenv("GCT_X6S")) : 1;          // A/B switch
-    const int64_t big = ((g.M + XBM - 1) / XBM) * ((g.N + XBN - 1) / XBN);
-    const int64_t small = ((g.M + SBM - 1) / SBM) * ((g.N + SBN - 1) / SBN);
-    // measured (tools/kernel_bench.py --suite decgemm, rows 1 024 ... 5 184): a 64 x 128 tile takes 0.75 us per K-tile
-    // alone on its CU and 1.45 us when two share it, a 128 x 256 tile 2.8 us; from K = 2 048 on the large kernel's
-    // K-split routes fill the chip and win, at K = 1 024 only while every small tile has a CU to itself
-    const int64_t nkt_ = g.K / XBK;
-    if (x6s_on && big <= 160 && small >= 96 && small <= (nkt_ <= 16 ? 512 : 256) && nkt_ <= 32 && x6s_ok(g, vec)) {
+  const GemmRoute r = plan_gemm<A_KC, B_KC>(g, vec, gemm_mode(), ws, ws_bytes);
+  switch (r.kind) {
+    case GemmRoute::X6S:
       ++g_gemm_launches[1];
-      return launch_x6s(g, st);
+      return launch_x6s<B_KC ? X6_FWD : X6_DGRAD>(g, st);
+    case GemmRoute::X6_SPLITK_ALL: {
+      const GemmArgs p = slab_args(g, r.splits, ws);
+      int rc = launch_x6<MODE>(p, st);
+      if (!rc) rc = launch_fixup(g, p, st, "x6 split-K fix-up");
+      if (!rc) ++g_gemm_launches[1];
+      return rc;
     }
-    // weight segments of 128 rows (the sampler's mu | log_var, N = 2 x 128): not a whole number of 256-row tiles per
-    // segment, so the large kernel cannot take them -- the small-tile kernel for the whole problem instead of fp32 MFMA
-    if (x6s_on && !x6_ok<X6_FWD>(g, vec) && small >= 96 && x6s_ok(g, vec)) {
-      ++g_gemm_launches[1];
-      return launch_x6s(g, st);
-    }
-    if (x6_ok<X6_FWD>(g, vec)) {
-      int taken = 0;
-      const int rc = launch_x6_splitk_all<X6_FWD>(g, st, skinny_ws, ws_bytes, &taken);
-      if (rc || taken) {
-        if (taken) ++g_gemm_launches[1];
-        return rc;
-      }
-    }
-  }
-  if (A_KC && !B_KC && gemm_mode() == GCT_GEMM_BF16X6 && g.epi >= EPI_D0 && g.epi < EPI_SLAB) {
-    // the same for dgrad launches (training at small batches): few 128 x 256 tiles, enough 64 x 128 ones
-    static const int x6s_dg = getenv("GCT_X6S_DGRAD") ? atoi(getenv("GCT_X6S_DGRAD")) : 1;              // A/B switch
-    const int64_t big = ((g.M + XBM - 1) / XBM) * ((g.N + XBN - 1) / XBN);
-    const int64_t small = ((g.M + SBM - 1) / SBM) * ((g.N + SBN - 1) / SBN);
-    const int64_t nkt_ = g.K / XBK;
-    if (x6s_dg && big <= 160 && small >= 96 && small <= (nkt_ <= 16 ? 512 : 256) && nkt_ <= 32 && x6s_dgrad_ok(g, vec)) {
-      ++g_gemm_launches[1];
-      return launch_x6s<X6_DGRAD>(g, st);
-    }
-    // ... and a long reduction over few tiles (K' = 1 536 / 2 048 at batch 64): K split over the whole problem + fix-up
-    static const int dg_splitk = getenv("GCT_X6_DGRAD_SPLITK") ? atoi(getenv("GCT_X6_DGRAD_SPLITK")) : 1;  // A/B switch
-    if (dg_splitk && x6_ok<X6_DGRAD>(g, vec)) {
-      int taken = 0;
-      const int rc = launch_x6_splitk_all<X6_DGRAD>(g, st, skinny_ws, ws_bytes, &taken);
-      if (rc || taken) {
-        if (taken) ++g_gemm_launches[1];
-        return rc;
-      }
-    }
-  }
-  // narrow outputs (the vocabulary head, N = 28-31): the ragged panel kernel, exact fp32 MFMA, M / 32 workgroups
-  if (A_KC && B_KC && vec && g.N <= 32 && g.K % 256 == 0 && g.epi == GCT_EPI_BIAS && g.nsplit == 1 && g.b_nper >= g.N &&
-      g.c_nper >= g.N && g.M >= 1 && g.lda * 4 * 33 < (1ll << 31) && g.ldb * 4 * 33 < (1ll << 31) && g.M < (1ll << 36)) {
-    static const bool no_thin = getenv("GCT_GEMM_NO_THIN") != nullptr;     // A/B switch
-    if (!no_thin) {
+    case GemmRoute::PANEL_THIN:
       ++g_gemm_launches[0];
       return launch_panel<32, true>(g, st);
+    case GemmRoute::PANEL32:
+      return launch_panel<32>(g, st);
+    case GemmRoute::PANEL64:
+      return launch_panel<64>(g, st);
+    case GemmRoute::F32_SMALL: {
+      const int64_t tiles64 = ((g.M + 63) / 64) * ((g.N + 63) / 64);
+      if (r.splits == 1) {
+        hipLaunchKernelGGL(gemm_f32_small_kernel, dim3((unsigned)tiles64), dim3(256), 0, st, g);
+        GCT_LAUNCH_CHECK("gemm_f32_small");
+        return GCT_OK;
+      }
+      const GemmArgs p = slab_args(g, r.splits, ws);
+      hipLaunchKernelGGL(gemm_f32_small_kernel, dim3((unsigned)(tiles64 * p.nsplit)), dim3(256), 0, st, p);
+      GCT_LAUNCH_CHECK("gemm_f32_small(split-K)");
+      return launch_fixup(g, p, st, "splitk_epilogue");
     }
-  }
-  // skinny M (decode steps): 64x64 tiles when the 128x128 grid would leave most CUs idle
-  // (192: with more tiles the bf16x6 kernel wins even on half the CUs -- decode at n >= 6144 lost 5-8 % with 384)
-  if (fast && A_KC && B_KC && g.nsplit == 1 && tiles < 192 && g.epi < EPI_D0 &&
-      (g.b_nper >= g.N || g.b_nper % 64 == 0)) {
-    // ... and the panel kernel (whole reduction in one workgroup, one launch) when even those are few
-    static const bool no_panel = getenv("GCT_GEMM_NO_PANEL") != nullptr;   // A/B switch for benchmarks
-    if (!no_panel && g.K % 256 == 0 && g.lda * 4 * 33 < (1ll << 31) && g.ldb * 4 * 65 < (1ll << 31) &&
-        (g.c_nper >= g.N || g.c_nper % 64 == 0)) {
-      const int64_t tm32 = (g.M + 31) / 32;
-      static const int64_t cap32 = getenv("GCT_PANEL_MAX32") ? atoll(getenv("GCT_PANEL_MAX32")) : 4096;  // knobs; 4096: +9 % / +3 % per decode step at n = 1024 / 4096 over 384
-      static const int64_t cap64 = getenv("GCT_PANEL_MAX64") ? atoll(getenv("GCT_PANEL_MAX64")) : 768;
-      if (g.N % 32 == 0 && (g.b_nper >= g.N || g.b_nper % 32 == 0) && tm32 * (g.N / 32) <= cap32)
-        return launch_panel<32>(g, st);
-      if (g.N % 64 == 0 && tm32 * (g.N / 64) <= cap64) return launch_panel<64>(g, st);
-    }
-    const int64_t st_ = ((g.M + 63) / 64) * ((g.N + 63) / 64);
-    const int64_t nkt = g.K / BK;
-    int64_t ns = 1;
-    if (skinny_ws && gct_aligned16(skinny_ws)) {      // split-K: >= 4 K-tiles per split, ~768 blocks
-      ns = 768 / st_;
-      if (ns > nkt / 4) ns = nkt / 4;
-      static const int ns_cap = getenv("GCT_SKINNY_SPLIT_MAX") ? atoi(getenv("GCT_SKINNY_SPLIT_MAX")) : 1 << 30;
-      if (ns > ns_cap) ns = ns_cap;
-      // never more slabs than the caller's workspace holds (fewer splits, same result up to summation order)
-      const int64_t slab_b = g.M * g.N * (int64_t)sizeof(float);
-      if (slab_b > 0 && ns * slab_b > ws_bytes) ns = ws_bytes / slab_b;
-      if (ns < 1) ns = 1;
-    }
-    if (ns <= 1) {
-      hipLaunchKernelGGL(gemm_f32_small_kernel, dim3((unsigned)st_), dim3(256), 0, st, g);
-      GCT_LAUNCH_CHECK("gemm_f32_small");
-      return GCT_OK;
-    }
-    GemmArgs p = g;                                   // pass 1: raw partial sums into slabs
-    p.ksplit = ((nkt + ns - 1) / ns) * BK;
-    p.nsplit = (int)((g.K + p.ksplit - 1) / p.ksplit);
-    p.epi = EPI_SLAB;
-    p.c0 = skinny_ws;
-    p.slab_stride = g.M * g.N;
-    hipLaunchKernelGGL(gemm_f32_small_kernel, dim3((unsigned)(st_ * p.nsplit)), dim3(256), 0, st, p);
-    GCT_LAUNCH_CHECK("gemm_f32_small(split-K)");
-    const int64_t patches = ((g.M + 3) / 4) * (g.N / 4);
-    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((patches + 255) / 256)), dim3(256), 0, st,
-                       g, (const float*)skinny_ws, p.nsplit, p.slab_stride);
-    GCT_LAUNCH_CHECK("splitk_epilogue");
-    return GCT_OK;
-  }
-  if (gemm_mode() == GCT_GEMM_BF16X6) {
-    constexpr int MODE = A_KC ? (B_KC ? X6_FWD : X6_DGRAD) : X6_WGRAD;
-    if ((A_KC || !B_KC) && x6_ok<MODE>(g, vec)) {
+    case GemmRoute::X6:
       ++g_gemm_launches[1];
-#ifdef GCT_LAB_X6P
-      if constexpr (MODE == X6_FWD) {
-        if (g_x6p_on == 2 && g.nsplit == 1 && g.epi < EPI_D0 && g.a_nper >= g.K) return launch_x6w<X6_FWD>(g, st);
-      }
-      if constexpr (MODE == X6_FWD) {          // lab variant 3: the 64 x 128-tile kernel (two workgroups per CU) for the whole problem
-        if (g_x6p_on == 3 && x6s_ok(g, vec)) return launch_x6s<X6_FWD>(g, st);
-        if (g_x6p_on == 4 && x6s_ok(g, vec)) return launch_x6h<X6_FWD>(g, st);
-      }
-      if constexpr (MODE == X6_DGRAD) {
-        if (g_x6p_on == 3 && x6s_dgrad_ok(g, vec)) return launch_x6s<X6_DGRAD>(g, st);
-      }
-      if constexpr (MODE != X6_WGRAD) {
-        if (g_x6p_on == 1 && x6p_ok<MODE>(g, vec)) {
-          int taken = 0;
-          const int rc = launch_x6p<MODE>(g, st, skinny_ws, ws_bytes, x6p_counter_slot(), &taken);
-          if (rc || taken) return rc;
-        }
-      }
-#endif
-      return launch_x6_tail_split<MODE>(g, st, skinny_ws, ws_bytes);
-    }
+      return launch_x6_tail_split<MODE>(g, st, ws, ws_bytes);
+    default:
+      break;
   }
   ++g_gemm_launches[0];
-  if (fast) {
-    GemmArgs gs = g;
-    // half of one tile's main loop: nkt K-tiles x ~4.5k cycles / 2, in units of s_sleep(127) ~ 8.1k cycles
-    const int64_t nkt = (g.ksplit < g.K ? g.ksplit : g.K) / BK;
-    // measured (tools/kernel_bench.py, GCT_GEMM_STAGGER=0/2/4/8): within +-2 % on every shape, so the
-    // stagger is OFF unless requested -- kept as an experiment knob
-    (void)nkt;
-    gs.stagger = stagger_env > 0 ? stagger_env : 0;
-    if (tiles <= 512) gs.stagger = 0;      // a single round: nothing to de-phase
-    hipLaunchKernelGGL((gemm_f32_fast_kernel<A_KC, B_KC>), grid, block, 0, st, gs);
-  }
-  else if (vec)
+  const dim3 grid((unsigned)tiles), block(256);
+  if (r.kind == GemmRoute::F32_FAST)
+    hipLaunchKernelGGL((gemm_f32_fast_kernel<A_KC, B_KC>), grid, block, 0, st, g);
+  else if (r.kind == GemmRoute::F32_VEC)
     hipLaunchKernelGGL((gemm_f32_kernel<A_KC, B_KC, true>), grid, block, 0, st, g);
   else
     hipLaunchKernelGGL((gemm_f32_kernel<A_KC, B_KC, false>), grid, block, 0, st, g);
@@ -1577,18 +1540,6 @@ extern "C" int gct_gemm_set_mode(int mode) {
   return GCT_OK;
 }
 extern "C" int gct_gemm_get_mode(void) { return gemm_mode(); }
-#ifdef GCT_LAB_X6P
-extern "C" int gct_gemm_set_persistent(int on) {
-  g_x6p_on = on;
-  return GCT_OK;
-}
-extern "C" int gct_gemm_set_sync_buffer(int32_t* buf, int64_t bytes) {
-  GCT_CHECK_ARG(!buf || bytes >= (int64_t)X6P_SYNC_SLOTS * 256 * 4, "gemm_set_sync_buffer: need %d bytes, zero-initialised",
-                X6P_SYNC_SLOTS * 256 * 4);
-  g_x6p_counters = buf;
-  return GCT_OK;
-}
-#endif
 extern "C" int64_t gct_gemm_x6_kernel_launches(void) { return g_x6_kernel_launches; }
 extern "C" int gct_gemm_launch_counts(int64_t* out2) {
   GCT_CHECK_ARG(out2, "gemm_launch_counts: null");
@@ -1609,29 +1560,25 @@ extern "C" int gct_split_planes(const float* src, int64_t numel, uint16_t* plane
   return GCT_OK;
 }
 
+// Workspace queries: the slabs of every route a call of this shape can take, from the routes' own split rules (an upper
+// bound: alignment and the epilogue are not known here).
 extern "C" int64_t gct_linear_fwd_ws_bytes(int64_t M, int K, int Ntot) {
-  const int64_t tiles = ((M + BM - 1) / BM) * (((int64_t)Ntot + BN - 1) / BN);
-  int64_t need = 0;
-  if (tiles < 192) {
-    // skinny M: worst case K/128 slabs of [M][Ntot]
-    const int64_t ns = K / (4 * BK) > 0 ? K / (4 * BK) : 1;
-    need = ns * M * Ntot * (int64_t)sizeof(float);
+  int64_t need = 0, m1 = 0;
+  if (skinny_m(M, Ntot)) {
+    need = slab_bytes(skinny_splits(M, Ntot, K), M, Ntot);
   } else {
-    int64_t m1 = 0;                                  // bf16x6 tail balancing: s slabs of the tail rows
-    const int s = x6_tail_plan(M, Ntot, K, &m1);
-    if (s > 1) need = (int64_t)s * (M - m1) * Ntot * (int64_t)sizeof(float);
+    const int s = x6_tail_plan(M, Ntot, K, &m1);      // bf16x6 tail balancing: s slabs of the tail rows
+    need = slab_bytes(s, M - m1, Ntot);
   }
-  const int64_t sp = x6_splitk_all_plan(M, Ntot, K);   // bf16x6 split-K over the whole problem (few tiles, long K)
-  if (sp > 1 && sp * M * Ntot * (int64_t)sizeof(float) > need) need = sp * M * Ntot * (int64_t)sizeof(float);
-  return need + 256;
+  const int64_t all = slab_bytes(x6_splitk_all_plan(M, Ntot, K), M, Ntot);
+  return (need > all ? need : all) + 256;
 }
 
 extern "C" int64_t gct_linear_dgrad_ws_bytes(int64_t M, int Ntot, int K) {
   int64_t m1 = 0;
   const int s = x6_tail_plan(M, K, Ntot, &m1);       // dx is [M][K], reduced over Ntot
-  const int64_t tail = s > 1 ? (int64_t)s * (M - m1) * K * (int64_t)sizeof(float) : 0;
-  const int64_t sp = x6_splitk_all_plan(M, K, Ntot);  // few tiles, long reduction: K split over the whole problem
-  const int64_t all = sp > 1 ? sp * M * K * (int64_t)sizeof(float) : 0;
+  const int64_t tail = slab_bytes(s, M - m1, K);
+  const int64_t all = slab_bytes(x6_splitk_all_plan(M, K, Ntot), M, K);
   return (tail > all ? tail : all) + 256;
 }
 

@@ -5,12 +5,10 @@
 // -DGCT_LAB_NO_EPI_MATH  : the fused epilogues store the raw accumulators (no bias / GELU / Philox / residual reads)
 // -DGCT_LAB_NO_EPI_STORE : epilogue arithmetic kept, stores dropped
 // -DGCT_LAB_NO_EPI       : the whole per-wave epilogue dropped
-#define GCT_LAB_X6P 1
 #include "../gct_plus_amd/csrc/capi.hip"
 #include "../gct_plus_amd/csrc/gemm.hip"
 #include "../gct_plus_amd/csrc/reduce.hip"
 #include <algorithm>
-#include <math.h>
 #include <string>
 #include <vector>
 
@@ -43,31 +41,10 @@ static double timeit(F fn, int reps) {
   return ts[ts.size() / 2] * 1e3;
 }
 
-// A/B: alternate the two variants launch by launch, median of each
-template <class F>
-static void timeab(F fn, int reps, double* out2) {
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-  for (int v = 0; v < 2; ++v) { fn(v); fn(v); }
-  (void)hipDeviceSynchronize();
-  std::vector<float> ts[2];
-  for (int r = 0; r < reps; ++r)
-    for (int v = 0; v < 2; ++v) {
-      (void)hipEventRecord(e0, 0);
-      fn(v);
-      (void)hipEventRecord(e1, 0);
-      (void)hipEventSynchronize(e1);
-      float ms; (void)hipEventElapsedTime(&ms, e0, e1);
-      ts[v].push_back(ms);
-    }
-  for (int v = 0; v < 2; ++v) { std::sort(ts[v].begin(), ts[v].end()); out2[v] = ts[v][ts[v].size() / 2] * 1e3; }
-}
-
 int main(int argc, char** argv) {
   const int64_t M = argc > 1 ? atoll(argv[1]) : 40960;
   const int reps = argc > 2 ? atoi(argv[2]) : 9;
   const std::string filt = argc > 3 ? argv[3] : "";
-  const int variant = argc > 4 ? atoi(argv[4]) : 1;      // 1: persistent stream-K launch, 2: one wave per SIMD (forward only)
   struct Shape { const char* name; int K, nper, nseg; };
   const Shape shapes[] = {{"qkv", 512, 512, 3}, {"out", 512, 512, 1}, {"ffn1", 512, 2048, 1}, {"ffn2", 2048, 512, 1}};
   const size_t maxn = (size_t)M * 2048;
@@ -83,20 +60,6 @@ int main(int argc, char** argv) {
   uint16_t* wp; (void)hipMalloc(&wp, (size_t)3 * 2048 * 512 * 3 * 2);
   const int64_t wsb = 1ll << 30;
   float* ws; (void)hipMalloc(&ws, wsb);
-  int32_t* sync; (void)hipMalloc(&sync, 32 * 256 * 4); (void)hipMemset(sync, 0, 32 * 256 * 4);
-  gct_gemm_set_sync_buffer(sync, 32 * 256 * 4);
-  float* yref = dalloc(maxn, 0.f, 11);
-  float* pre_ref = dalloc(maxn, 0.f, 12);
-  // max |a - b| over n floats (host side; small enough at these sizes)
-  auto maxdiff = [&](const float* a, const float* bb, size_t n) {
-    std::vector<float> ha(n), hb(n);
-    (void)hipMemcpy(ha.data(), a, n * 4, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(hb.data(), bb, n * 4, hipMemcpyDeviceToHost);
-    double m = 0; size_t bad = 0;
-    for (size_t i = 0; i < n; ++i) { const double d = fabs((double)ha[i] - hb[i]); if (d > m) m = d; if (!(d <= 1e-3)) ++bad; }
-    if (bad) printf("      !!! %zu elements differ by more than 1e-3\n", bad);
-    return m;
-  };
   printf("rows %ld, median of %d, mode %s\n", (long)M, reps, gct_gemm_get_mode() == GCT_GEMM_BF16X6 ? "bf16x6" : "f32");
   for (const Shape& s : shapes) {
     if (!filt.empty() && filt.find(s.name) == std::string::npos) continue;
@@ -114,35 +77,22 @@ int main(int argc, char** argv) {
     const Case fc[] = {{"bias", GCT_EPI_BIAS, 0.f}, {"gelu_drop.1", GCT_EPI_GELU_DROP, 0.1f}, {"drop_resid.1", GCT_EPI_DROP_RESID, 0.1f}};
     for (const Case& c : fc) {
       if (c.epi != GCT_EPI_BIAS && nseg > 1) continue;
-      double tt[2];
-      (void)hipMemset(y, 0xff, (size_t)M * N * 4); (void)hipMemset(yref, 0xff, (size_t)M * N * 4);
-      timeab([&](int pers) {
-        gct_gemm_set_persistent(pers ? variant : 0);
-        float* yy = pers ? y : yref; float* pp = pers ? pre : pre_ref;
-        float* yy1 = nseg > 1 ? yy + nper : nullptr; float* yy2 = nseg > 2 ? yy + 2 * nper : nullptr;
-        int rc = gct_linear_fwd_p(x, K, M, K, w, w1, w2, K, wp, pstride, b, b1, b2, nseg, nper, yy, yy1, yy2, N, c.epi, resid, pp, c.p,
+      const double t = timeit([&] {
+        int rc = gct_linear_fwd_p(x, K, M, K, w, w1, w2, K, wp, pstride, b, b1, b2, nseg, nper, y, y1, y2, N, c.epi, resid, pre, c.p,
                                   3, 1, ws, wsb, nullptr, nullptr);
         if (rc) { printf("fwd failed: %s\n", gct_last_error()); exit(1); }
-      }, reps, tt);
-      const double md = maxdiff(y, yref, (size_t)M * N);
-      printf("%-5s fwd   %-13s M=%ld K=%d N=%d: %8.1f us %6.1f TF | persistent %8.1f us %6.1f TF (%+5.1f %%) maxdiff %.2e\n", s.name, c.nm,
-             (long)M, K, N, tt[0], fl / tt[0] / 1e6, tt[1], fl / tt[1] / 1e6, 100 * (tt[1] / tt[0] - 1), md);
+      }, reps);
+      printf("%-5s fwd   %-13s M=%ld K=%d N=%d: %8.1f us %6.1f TF\n", s.name, c.nm, (long)M, K, N, t, fl / t / 1e6);
     }
     const Case dc[] = {{"store", GCT_DEPI_STORE, 0.f}, {"gelu_bwd.1", GCT_DEPI_GELU_BWD, 0.1f}};
     for (const Case& c : dc) {
       if (c.epi != GCT_DEPI_STORE && nseg > 1) continue;
-      double tt[2];
-      (void)hipMemset(dx, 0xff, (size_t)M * K * 4); (void)hipMemset(yref, 0xff, (size_t)M * K * 4);
-      timeab([&](int pers) {
-        gct_gemm_set_persistent(pers ? variant : 0);
-        float* dd = pers ? dx : yref;
+      const double t = timeit([&] {
         int rc = gct_linear_dgrad_p(resid, nseg > 1 ? resid + nper : nullptr, nseg > 2 ? resid + 2 * nper : nullptr, N, M, nseg, nper, w, w1, w2,
-                                    K, wp, pstride, K, dd, K, c.epi, pre_ref, c.p, 3, 1, ws, wsb, nullptr, 0, nullptr);
+                                    K, wp, pstride, K, dx, K, c.epi, pre, c.p, 3, 1, ws, wsb, nullptr, 0, nullptr);
         if (rc) { printf("dgrad failed: %s\n", gct_last_error()); exit(1); }
-      }, reps, tt);
-      const double md = maxdiff(dx, yref, (size_t)M * K);
-      printf("%-5s dgrad %-13s M=%ld K'=%d N'=%d: %8.1f us %6.1f TF | persistent %8.1f us %6.1f TF (%+5.1f %%) maxdiff %.2e\n", s.name, c.nm,
-             (long)M, N, K, tt[0], fl / tt[0] / 1e6, tt[1], fl / tt[1] / 1e6, 100 * (tt[1] / tt[0] - 1), md);
+      }, reps);
+      printf("%-5s dgrad %-13s M=%ld K'=%d N'=%d: %8.1f us %6.1f TF\n", s.name, c.nm, (long)M, N, K, t, fl / t / 1e6);
     }
     {
       float* dw1 = nseg > 1 ? dw + (size_t)nper * K : nullptr;
