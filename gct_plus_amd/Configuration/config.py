@@ -52,3 +52,6 @@ def train_opts(parser):
     parser.add_argument('-print_every', type=int, default=1)
     parser.add_argument('-eps_mode', type=str, default='device', choices=['device', 'cpu'],
                         help="'cpu' draws the VAE eps from the CPU torch generator (parity runs)")
+    parser.add_argument('-matmul_precision', type=str, default='highest', choices=['highest', 'high'],
+                        help="nn.Linear GEMM arithmetic: 'highest' = the process default (bf16x6, fp32-class); "
+                             "'high' = opt-in bf16x3, < 3.02 * 2^-16 |a*b| dropped per product, faster")

@@ -843,7 +843,8 @@ gemm_f32_fast_kernel(const GemmArgs g) {
 }
 
 
-int64_t g_x6_kernel_launches = 0;   // gemm_x6_kernel launches (a tail-balanced call makes two)
+int64_t g_x6_kernel_launches = 0;   // gemm_x6_kernel / gemm_x6s_kernel launches, 3 pieces (a tail-balanced call makes two)
+int64_t g_x3_kernel_launches = 0;   // the same kernels with 2 pieces (bf16x3 mode)
 #include "gemm_x6.inc"
 
 // =====================================================================================
@@ -1133,10 +1134,12 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const GemmArgs g, 
 }
 
 // GEMM arithmetic: GCT_GEMM_F32 = v_mfma_f32_32x32x2_f32 everywhere; GCT_GEMM_BF16X6 = exact 3-way bf16
-// split with six partial products (gemm_x6.inc) wherever a launch qualifies.  Process-wide; the
+// split with six partial products (gemm_x6.inc) wherever a launch qualifies; GCT_GEMM_BF16X3 (opt-in, set only
+// through gct_gemm_set_mode) = the same routes and kernels with two pieces and three products.  Process-wide; the
 // default comes from GCT_GEMM_MODE=f32|x6 (x6 when unset).
 int g_gemm_mode = -1;
-int64_t g_gemm_launches[2] = {0, 0};   // GEMM calls served by [fp32-MFMA kernels, bf16x6 kernels] (tests / diagnostics)
+int64_t g_gemm_launches[2] = {0, 0};   // GEMM calls served by [fp32-MFMA kernels, bf16x6 kernels] (tests / diagnostics;
+                                       // bf16x3 calls count in g_x3_kernel_launches only)
 inline int gemm_mode() {
   if (g_gemm_mode < 0) {
     const char* e = getenv("GCT_GEMM_MODE");
@@ -1269,20 +1272,21 @@ int launch_fixup(const GemmArgs& g, const GemmArgs& slabs, hipStream_t st, const
 }
 
 // executor of the bf16x6 route: plain, or tail-balanced (x6_tail_plan) with the tail rows on the small-tile kernel
-// or K-split into slabs.  Not in the planner: it depends on whether the stream is being captured.
-template <int MODE>
+// or K-split into slabs.  Not in the planner: it depends on whether the stream is being captured.  NP: pieces
+// (3: bf16x6, 2: bf16x3).
+template <int MODE, int NP>
 int launch_x6_tail_split(const GemmArgs& g, hipStream_t st, float* ws, int64_t ws_bytes) {
-  if (MODE == X6_WGRAD || g.nsplit != 1 || !ws || !gct_aligned16(ws)) return launch_x6<MODE>(g, st);
+  if (MODE == X6_WGRAD || g.nsplit != 1 || !ws || !gct_aligned16(ws)) return launch_x6<MODE, NP>(g, st);
   int64_t m1 = 0;
   const int best = x6_tail_plan(g.M, g.N, g.K, &m1);
   const int64_t m2 = g.M - m1, nkt = g.K / XBK;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;   // keep captured graphs to one kernel per GEMM
   if (best == 1 || slab_bytes(best, m2, g.N) > ws_bytes ||
       hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
-    return launch_x6<MODE>(g, st);
+    return launch_x6<MODE, NP>(g, st);
   GemmArgs head = g;
   head.M = m1;
-  int rc = launch_x6<MODE>(head, st);
+  int rc = launch_x6<MODE, NP>(head, st);
   if (rc) return rc;
   GemmArgs e = g;                                      // the tail rows as their own problem
   e.M = m2; e.row_base = g.row_base + m1;
@@ -1293,11 +1297,11 @@ int launch_x6_tail_split(const GemmArgs& g, hipStream_t st, float* ws, int64_t w
   // pre_in read through the quad map keeps the forward's row space: the tail finds its rows through row_base
   if (e.pre_in && !(g.pre_rows > 0 && g.quad_map)) e.pre_in += m1 * g.ldc;
   if (nkt <= 32 && x6s_tiles(m2, g.N) <= X6_TAIL_SMALL_MAX) {
-    if (MODE == X6_FWD && x6s_ok(e, true)) return launch_x6s<X6_FWD>(e, st);
-    if (MODE == X6_DGRAD && x6s_dgrad_ok(e, true)) return launch_x6s<X6_DGRAD>(e, st);
+    if (MODE == X6_FWD && x6s_ok(e, true)) return launch_x6s<X6_FWD, NP>(e, st);
+    if (MODE == X6_DGRAD && x6s_dgrad_ok(e, true)) return launch_x6s<X6_DGRAD, NP>(e, st);
   }
   const GemmArgs p = slab_args(e, best, ws);
-  rc = launch_x6<MODE>(p, st);
+  rc = launch_x6<MODE, NP>(p, st);
   if (rc) return rc;
   return launch_fixup(e, p, st, "x6 tail fix-up");
 }
@@ -1319,13 +1323,14 @@ struct GemmRoute {
   int splits;
 };
 
-// The first row whose shape condition holds wins.  Pure: no launches, no environment; `mode` is the arithmetic mode,
-// ws / ws_bytes the caller's workspace (a slab route is taken only where its slabs fit).
+// The first row whose shape condition holds wins.  Pure: no launches, no environment; `mode` is the arithmetic mode
+// (bf16x6 and bf16x3 plan alike: the X6* routes then run the 3- resp. 2-piece kernels), ws / ws_bytes the caller's
+// workspace (a slab route is taken only where its slabs fit).
 template <bool A_KC, bool B_KC>
 GemmRoute plan_gemm(const GemmArgs& g, bool vec, int mode, const float* ws, int64_t ws_bytes) {
   constexpr bool FWD = A_KC && B_KC, DGRAD = A_KC && !B_KC;
   constexpr int MODE = A_KC ? (B_KC ? X6_FWD : X6_DGRAD) : X6_WGRAD;
-  const bool x6 = mode == GCT_GEMM_BF16X6;
+  const bool x6 = mode == GCT_GEMM_BF16X6 || mode == GCT_GEMM_BF16X3;
   const bool x6_fwd = x6 && FWD && g.epi < EPI_D0, x6_dgrad = x6 && DGRAD && g.epi >= EPI_D0 && g.epi < EPI_SLAB;
   const bool ws_ok = ws && gct_aligned16(ws);
   if (x6_fwd || x6_dgrad) {
@@ -1376,16 +1381,19 @@ int launch(const GemmArgs& g, bool vec, hipStream_t st, float* ws = nullptr, int
     gct_set_error("gemm: grid too large");
     return GCT_ERR_ARG;
   }
-  const GemmRoute r = plan_gemm<A_KC, B_KC>(g, vec, gemm_mode(), ws, ws_bytes);
+  const int mode = gemm_mode();
+  const bool x3 = mode == GCT_GEMM_BF16X3;
+  const GemmRoute r = plan_gemm<A_KC, B_KC>(g, vec, mode, ws, ws_bytes);
   switch (r.kind) {
     case GemmRoute::X6S:
+      if (x3) return launch_x6s<B_KC ? X6_FWD : X6_DGRAD, 2>(g, st);
       ++g_gemm_launches[1];
-      return launch_x6s<B_KC ? X6_FWD : X6_DGRAD>(g, st);
+      return launch_x6s<B_KC ? X6_FWD : X6_DGRAD, 3>(g, st);
     case GemmRoute::X6_SPLITK_ALL: {
       const GemmArgs p = slab_args(g, r.splits, ws);
-      int rc = launch_x6<MODE>(p, st);
+      int rc = x3 ? launch_x6<MODE, 2>(p, st) : launch_x6<MODE, 3>(p, st);
       if (!rc) rc = launch_fixup(g, p, st, "x6 split-K fix-up");
-      if (!rc) ++g_gemm_launches[1];
+      if (!rc && !x3) ++g_gemm_launches[1];
       return rc;
     }
     case GemmRoute::PANEL_THIN:
@@ -1408,8 +1416,9 @@ int launch(const GemmArgs& g, bool vec, hipStream_t st, float* ws = nullptr, int
       return launch_fixup(g, p, st, "splitk_epilogue");
     }
     case GemmRoute::X6:
+      if (x3) return launch_x6_tail_split<MODE, 2>(g, st, ws, ws_bytes);
       ++g_gemm_launches[1];
-      return launch_x6_tail_split<MODE>(g, st, ws, ws_bytes);
+      return launch_x6_tail_split<MODE, 3>(g, st, ws, ws_bytes);
     default:
       break;
   }
@@ -1535,12 +1544,14 @@ extern "C" int gct_linear_fwd_p(const float* x, int64_t ldx, int64_t M, int K, c
 }
 
 extern "C" int gct_gemm_set_mode(int mode) {
-  GCT_CHECK_ARG(mode == GCT_GEMM_F32 || mode == GCT_GEMM_BF16X6, "gemm_set_mode: unknown mode %d", mode);
+  GCT_CHECK_ARG(mode == GCT_GEMM_F32 || mode == GCT_GEMM_BF16X6 || mode == GCT_GEMM_BF16X3,
+                "gemm_set_mode: unknown mode %d", mode);
   g_gemm_mode = mode;
   return GCT_OK;
 }
 extern "C" int gct_gemm_get_mode(void) { return gemm_mode(); }
 extern "C" int64_t gct_gemm_x6_kernel_launches(void) { return g_x6_kernel_launches; }
+extern "C" int64_t gct_gemm_x3_launches(void) { return g_x3_kernel_launches; }
 extern "C" int gct_gemm_launch_counts(int64_t* out2) {
   GCT_CHECK_ARG(out2, "gemm_launch_counts: null");
   out2[0] = g_gemm_launches[0]; out2[1] = g_gemm_launches[1];
@@ -1653,7 +1664,7 @@ static int linear_wgrad_impl(const float* dy0, const float* dy1, const float* dy
   g.c0 = ws; g.ldc = K; g.c_nper = INT64_MAX / 4;
   g.slab_stride = Ntot * K;
   g.ksplit = BK; g.nsplit = 1; g.epi = EPI_SLAB;
-  const bool use_x6 = gemm_mode() == GCT_GEMM_BF16X6 && x6_ok<X6_WGRAD>(g, vec);
+  const bool use_x6 = gemm_mode() != GCT_GEMM_F32 && x6_ok<X6_WGRAD>(g, vec);   // bf16x6 or bf16x3: same route
   if (use_x6 && kt_list && kt_count) { g.kt_list = kt_list; g.kt_count = kt_count; }   // other kernels reduce over every row
   const int splits = wgrad_splits(M, Ntot, K, use_x6);
   int64_t ks = (M + splits - 1) / splits;

@@ -21,6 +21,16 @@
 // 32x32x16 block instead of 8 x 64.  The 16x16x32 shape is used because the chip sustains a higher
 // clock on it: the same loop ran 20-29 % faster than with 32x32x16 (tools/gemm_x6_proto.hip).
 //
+// bf16x3 (opt-in, GCT_GEMM_BF16X3; the same kernels instantiated with NP = 2 pieces): x is split as x ~ h + m, the
+// first two pieces of the same exact split, and a*b is accumulated as the three leading products am*bh + ah*bm + ah*bh.
+// Bound of what is dropped, from the same piece bounds (|x - h| <= u|x|, so |m| <= u|x|, |l| <= u^2|x|, and
+// |h| <= (1 + u)|x|): am*bm + ah*bl + al*bh + am*bl + al*bm + al*bl  <=  (u^2 + 2(1 + u)u^2 + 2u^3 + u^4)|a*b|
+// = (3u^2 + 4u^3 + u^4)|a*b| < 3.02 * 2^-16 |a*b| per product -- about 16 good bits instead of 24 (TF32 rounds each
+// product by about 2^-10).  Summed over k: <= 3.02 * 2^-16 sum|a_k b_k| on top of the shared fp32 accumulation term.
+// tests/test_gemm_x3_gpu.py asserts |err| <= (3.02 * 2^-16 + 1.5 r32) sum|a_k b_k| (+ the flush floor) on the same
+// adversarial data as the bf16x6 test.  The weight planes are those of bf16x6 (planes 0 and 1 are read), so a mode
+// switch needs no re-split.
+//
 // Range notes: an infinite operand (or one that rounds to +-inf in bf16, |x| > 3.39e38) turns its residual
 // into NaN, so inf inputs give NaN where fp32 arithmetic could give inf; pieces below the bf16 normal range
 // (|x| < 2^-110 or so) are flushed, an absolute error under 1e-38.  Neither occurs in this model.
@@ -80,6 +90,22 @@ __device__ __forceinline__ void x6_split4(const float4 v, x6_u32x2& h, x6_u32x2&
   x6_split2(v.z, v.w, h1, m1, l1);
   h = x6_u32x2{h0, h1}; m = x6_u32x2{m0, m1}; l = x6_u32x2{l0, l1};
 }
+// the first NP pieces (NP = 3: h, m, l; NP = 2: h, m -- the last residual is not formed) of four fp32 values
+template <int NP>
+__device__ __forceinline__ void x6_split4n(const float4 v, x6_u32x2 (&pc)[NP]) {
+  if constexpr (NP == 3) {
+    x6_split4(v, pc[0], pc[1], pc[2]);
+  } else {
+    static_assert(NP == 2, "bf16x6 (3 pieces) or bf16x3 (2 pieces)");
+    unsigned h0, h1;
+    h0 = x6_pk(v.x, v.y);
+    h1 = x6_pk(v.z, v.w);
+    const float r0 = x6_sub(v.x, __uint_as_float(h0 << 16)), r1 = x6_sub(v.y, __uint_as_float(h0 & 0xffff0000u));
+    const float r2 = x6_sub(v.z, __uint_as_float(h1 << 16)), r3 = x6_sub(v.w, __uint_as_float(h1 & 0xffff0000u));
+    pc[0] = x6_u32x2{h0, h1};
+    pc[1] = x6_u32x2{x6_pk(r0, r1), x6_pk(r2, r3)};
+  }
+}
 
 // row image: [rows][32 k] bf16 = 64-B rows; 16-B chunk c (8 k-values) of row r.  A 16x16x32 fragment read
 // takes row (lane & 15), chunk (lane >> 4); the per-4-rows permutation {0,2,3,1} keeps every 16-lane group
@@ -111,12 +137,15 @@ typedef float x6_f32x4 __attribute__((ext_vector_type(4)));
 // FWD   x  [M][K]   K-contiguous, row reads       W planes [N][K]   K-contiguous, row reads
 // DGRAD dY [M][K']  K'-contiguous (segmented)     W planes [K'][N]  natural, transposed reads
 // WGRAD dY [K'][M]  natural, transposed reads     X fp32 [K'][N]    natural, split on the fly, transposed reads
-template <int MODE>
+// NP = pieces per operand element: 3 (bf16x6, six products) or 2 (bf16x3, three products; the LDS layout and the
+// stage size stay those of NP = 3, the third plane slots are left unused)
+template <int MODE, int NP = 3>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 gemm_x6_kernel(const GemmArgs g) {
+  static_assert(NP == 2 || NP == 3, "bf16x3 or bf16x6");
   extern __shared__ __attribute__((aligned(16))) unsigned char xlds[];
   constexpr bool A_TR = MODE == X6_WGRAD, B_TR = MODE != X6_FWD, B_PL = MODE != X6_WGRAD;
-  constexpr int NB = B_PL ? 2 : 4;  // B loads per thread (x 3 planes when pre-split)
+  constexpr int NB = B_PL ? 2 : 4;  // B loads per thread (x NP planes when pre-split)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = (wave >> 2) * 64, wn = (wave & 3) * 64;
 
@@ -203,7 +232,7 @@ gemm_x6_kernel(const GemmArgs g) {
     for (int j = 0; j < 4; ++j) acc[i][j] = x6_f32x4{0.f, 0.f, 0.f, 0.f};
 
   float4 pa[2];
-  x6_u32x4 pbp[3][2];   // B_PL
+  x6_u32x4 pbp[NP][2];  // B_PL
   float4 pbf[4];        // !B_PL
 #define X6_GLOAD(k0_)                                                                          \
   do {                                                                                         \
@@ -212,7 +241,7 @@ gemm_x6_kernel(const GemmArgs g) {
     _Pragma("unroll") for (int j = 0; j < 2; ++j)                                              \
         pa[j] = *reinterpret_cast<const float4*>(ab__ + offa[j]);                              \
     if (B_PL) {                                                                                \
-      _Pragma("unroll") for (int p = 0; p < 3; ++p)                                            \
+      _Pragma("unroll") for (int p = 0; p < NP; ++p)                                           \
       _Pragma("unroll") for (int j = 0; j < 2; ++j)                                            \
           pbp[p][j] = *reinterpret_cast<const x6_u32x4*>(g.bp0 + p * g.bp_stride + bo__ + offb[j]); \
     } else {                                                                                   \
@@ -224,23 +253,21 @@ gemm_x6_kernel(const GemmArgs g) {
   do {                                                                                         \
     unsigned char* s__ = (st_);                                                                \
     _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                            \
-      x6_u32x2 h__, m__, l__;                                                                  \
-      x6_split4(pa[j], h__, m__, l__);                                                         \
-      *reinterpret_cast<x6_u32x2*>(s__ + 0 * X_APL + sta[j]) = h__;                            \
-      *reinterpret_cast<x6_u32x2*>(s__ + 1 * X_APL + sta[j]) = m__;                            \
-      *reinterpret_cast<x6_u32x2*>(s__ + 2 * X_APL + sta[j]) = l__;                            \
+      x6_u32x2 pc__[NP];                                                                       \
+      x6_split4n<NP>(pa[j], pc__);                                                             \
+      _Pragma("unroll") for (int p = 0; p < NP; ++p)                                           \
+          *reinterpret_cast<x6_u32x2*>(s__ + p * X_APL + sta[j]) = pc__[p];                    \
     }                                                                                          \
     if (B_PL) {                                                                                \
-      _Pragma("unroll") for (int p = 0; p < 3; ++p)                                            \
+      _Pragma("unroll") for (int p = 0; p < NP; ++p)                                           \
       _Pragma("unroll") for (int j = 0; j < 2; ++j)                                            \
           *reinterpret_cast<x6_u32x4*>(s__ + 3 * X_APL + p * X_BPL + stb[j]) = pbp[p][j];      \
     } else {                                                                                   \
       _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                          \
-        x6_u32x2 h__, m__, l__;                                                                \
-        x6_split4(pbf[j], h__, m__, l__);                                                      \
-        *reinterpret_cast<x6_u32x2*>(s__ + 3 * X_APL + 0 * X_BPL + stb[j]) = h__;              \
-        *reinterpret_cast<x6_u32x2*>(s__ + 3 * X_APL + 1 * X_BPL + stb[j]) = m__;              \
-        *reinterpret_cast<x6_u32x2*>(s__ + 3 * X_APL + 2 * X_BPL + stb[j]) = l__;              \
+        x6_u32x2 pc__[NP];                                                                     \
+        x6_split4n<NP>(pbf[j], pc__);                                                          \
+        _Pragma("unroll") for (int p = 0; p < NP; ++p)                                         \
+            *reinterpret_cast<x6_u32x2*>(s__ + 3 * X_APL + p * X_BPL + stb[j]) = pc__[p];      \
       }                                                                                        \
     }                                                                                          \
   } while (0)
@@ -250,7 +277,7 @@ gemm_x6_kernel(const GemmArgs g) {
   // (first half: LDS writes + B loads; second half: split VALU + A loads).  Stamps before: 2127 / 1643
   // cycles per half against 1536 of MFMAs.
   constexpr bool BAL = B_PL;
-  x6_u32x2 pk[2][3];    // packed pieces of the A tile (BAL)
+  x6_u32x2 pk[2][NP];   // packed pieces of the A tile (BAL)
 #define X6_GLOAD_A(k0_)                                                                        \
   do {                                                                                         \
     const float* ab__ = abase(k0_);                                                            \
@@ -260,19 +287,19 @@ gemm_x6_kernel(const GemmArgs g) {
 #define X6_GLOAD_B(k0_)                                                                        \
   do {                                                                                         \
     const int64_t bo__ = boff(k0_);                                                            \
-    _Pragma("unroll") for (int p = 0; p < 3; ++p)                                              \
+    _Pragma("unroll") for (int p = 0; p < NP; ++p)                                             \
     _Pragma("unroll") for (int j = 0; j < 2; ++j)                                              \
         pbp[p][j] = *reinterpret_cast<const x6_u32x4*>(g.bp0 + p * g.bp_stride + bo__ + offb[j]); \
   } while (0)
 #define X6_SPLIT_A()                                                                           \
-  _Pragma("unroll") for (int j = 0; j < 2; ++j) x6_split4(pa[j], pk[j][0], pk[j][1], pk[j][2]);
+  _Pragma("unroll") for (int j = 0; j < 2; ++j) x6_split4n<NP>(pa[j], pk[j]);
 #define X6_LSTORE_PK(st_)                                                                      \
   do {                                                                                         \
     unsigned char* s__ = (st_);                                                                \
     _Pragma("unroll") for (int j = 0; j < 2; ++j)                                              \
-    _Pragma("unroll") for (int p = 0; p < 3; ++p)                                              \
+    _Pragma("unroll") for (int p = 0; p < NP; ++p)                                             \
         *reinterpret_cast<x6_u32x2*>(s__ + p * X_APL + sta[j]) = pk[j][p];                     \
-    _Pragma("unroll") for (int p = 0; p < 3; ++p)                                              \
+    _Pragma("unroll") for (int p = 0; p < NP; ++p)                                             \
     _Pragma("unroll") for (int j = 0; j < 2; ++j)                                              \
         *reinterpret_cast<x6_u32x4*>(s__ + 3 * X_APL + p * X_BPL + stb[j]) = pbp[p][j];        \
   } while (0)
@@ -290,27 +317,29 @@ gemm_x6_kernel(const GemmArgs g) {
   }
   // four fragment sets of two tiles each; quarter-phase order (A01,B01) (A23,B01) | (A01,B23) (A23,B23):
   // every set is reloaded while the MFMAs of another phase run, 96 fragment VGPRs in all
-  x6_bf16x8 fA01[2][3], fA23[2][3], fB01[2][3], fB23[2][3];
+  x6_bf16x8 fA01[2][NP], fA23[2][NP], fB01[2][NP], fB23[2][NP];   // NP = 2: 64 fragment VGPRs
 #define X6_LD_A(dst_, st_, i0_)                                                                \
   _Pragma("unroll") for (int ii = 0; ii < 2; ++ii)                                             \
-  _Pragma("unroll") for (int p = 0; p < 3; ++p) {                                              \
+  _Pragma("unroll") for (int p = 0; p < NP; ++p) {                                             \
     if (A_TR) dst_[ii][p] = x6_tr_frag((st_) + p * X_APL + fao[(i0_) + ii], 256);              \
     else dst_[ii][p] = *reinterpret_cast<const x6_bf16x8*>((st_) + p * X_APL + fao[0] + ((i0_) + ii) * 1024); \
   }
 #define X6_LD_B(dst_, st_, j0_)                                                                \
   _Pragma("unroll") for (int jj = 0; jj < 2; ++jj)                                             \
-  _Pragma("unroll") for (int p = 0; p < 3; ++p) {                                              \
+  _Pragma("unroll") for (int p = 0; p < NP; ++p) {                                             \
     if (B_TR) dst_[jj][p] = x6_tr_frag((st_) + p * X_BPL + fbo[(j0_) + jj], 512);              \
     else dst_[jj][p] = *reinterpret_cast<const x6_bf16x8*>((st_) + p * X_BPL + fbo[0] + ((j0_) + jj) * 1024); \
   }
-// 2 x 2 tiles x 6 partial products, the six MFMAs of one accumulator back to back (chained MFMAs on one
-// accumulator issue fastest; interleaving accumulators cost 26 %)
+// 2 x 2 tiles x 6 (NP = 3) or 3 (NP = 2) partial products, smallest first, the MFMAs of one accumulator back to back
+// (chained MFMAs on one accumulator issue fastest; interleaving accumulators cost 26 %)
 #define X6_MM(a_, b_, i0_, j0_)                                                                \
   _Pragma("unroll") for (int ii = 0; ii < 2; ++ii)                                             \
   _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) {                                           \
-    X6_MFMA(a_[ii][2], b_[jj][0], acc[(i0_) + ii][(j0_) + jj]);                                \
-    X6_MFMA(a_[ii][0], b_[jj][2], acc[(i0_) + ii][(j0_) + jj]);                                \
-    X6_MFMA(a_[ii][1], b_[jj][1], acc[(i0_) + ii][(j0_) + jj]);                                \
+    if constexpr (NP == 3) {                                                                   \
+      X6_MFMA(a_[ii][NP - 1], b_[jj][0], acc[(i0_) + ii][(j0_) + jj]);                         \
+      X6_MFMA(a_[ii][0], b_[jj][NP - 1], acc[(i0_) + ii][(j0_) + jj]);                         \
+      X6_MFMA(a_[ii][1], b_[jj][1], acc[(i0_) + ii][(j0_) + jj]);                              \
+    }                                                                                          \
     X6_MFMA(a_[ii][1], b_[jj][0], acc[(i0_) + ii][(j0_) + jj]);                                \
     X6_MFMA(a_[ii][0], b_[jj][1], acc[(i0_) + ii][(j0_) + jj]);                                \
     X6_MFMA(a_[ii][0], b_[jj][0], acc[(i0_) + ii][(j0_) + jj]);                                \
@@ -379,8 +408,12 @@ gemm_x6_kernel(const GemmArgs g) {
     X6_LD_B(fB01, xlds, 0)
   }
   STAMP(0);
-  constexpr int RA = A_TR ? 12 : 6, RB = B_TR ? 12 : 6;   // LDS reads per two-tile fragment set
-  constexpr int NWR = B_PL ? 12 : 18;                     // LDS stores per K-tile
+  constexpr int RA = 2 * NP * (A_TR ? 2 : 1), RB = 2 * NP * (B_TR ? 2 : 1);   // LDS reads per two-tile fragment set
+  constexpr int NWR = B_PL ? 4 * NP : 6 * NP;             // LDS stores per K-tile
+  // issue-order hints below: the NP = 3 counts are the tuned ones; NP = 2 has half the MFMAs and about half the
+  // split VALU work per K-tile, and its groups are scaled to match (not retuned)
+  constexpr int NG = 2 * NP;                              // MFMA / LDS-read groups per fragment-set load
+  constexpr int MPW = NP == 3 ? 2 : 1;                    // MFMAs per LDS store (BAL, first half)
   int64_t k2n = nkt > 0 ? ktile(2) : 0;   // K index of tile t+2, looked up one iteration ahead: the scalar load
                                           // of a tile-list entry never sits in front of the loads that use it
   for (int64_t kt = 0; kt < nkt; ++kt) {
@@ -405,26 +438,26 @@ gemm_x6_kernel(const GemmArgs g) {
     X6_MM(fA01, fB01, 0, 0)
     X6_MM(fA23, fB01, 2, 0)
 #pragma unroll
-    for (int q = 0; q < 6; ++q) {
+    for (int q = 0; q < NG; ++q) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, (RA + RB) / 6, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, (RA + RB) / NG, 0);
     }
     if (BAL) {
 #pragma unroll
-      for (int q = 0; q < 12; ++q) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      for (int q = 0; q < NWR; ++q) {
+        __builtin_amdgcn_sched_group_barrier(0x008, MPW, 0);
         __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
       }
 #pragma unroll
-      for (int q = 0; q < 6; ++q) {
+      for (int q = 0; q < 2 * NP; ++q) {
         __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
     } else {
 #pragma unroll
-      for (int q = 0; q < 21; ++q) {
+      for (int q = 0; q < (NP == 3 ? 21 : 8); ++q) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, NP == 3 ? 6 : 9, 0);
       }
 #pragma unroll
       for (int q = 0; q < NWR; ++q) {
@@ -446,21 +479,21 @@ gemm_x6_kernel(const GemmArgs g) {
     }
     X6_MM(fA01, fB23, 0, 2)
 #pragma unroll
-    for (int q = 0; q < 6; ++q) {
+    for (int q = 0; q < NG; ++q) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, RB / 6, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, RB / NG, 0);
     }
     if (BAL) {
 #pragma unroll
-      for (int q = 0; q < 14; ++q) {
+      for (int q = 0; q < (NP == 3 ? 14 : 6); ++q) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, NP == 3 ? 3 : 4, 0);
       }
       __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
       __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
     } else {
 #pragma unroll
-      for (int q = 0; q < 8; ++q) {
+      for (int q = 0; q < (NP == 3 ? 8 : 4); ++q) {
         __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
@@ -469,9 +502,9 @@ gemm_x6_kernel(const GemmArgs g) {
     X6_LD_A(fA01, stn, 0)
     X6_MM(fA23, fB23, 2, 2)
 #pragma unroll
-    for (int q = 0; q < 6; ++q) {
+    for (int q = 0; q < NG; ++q) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, RA / 6, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, RA / NG, 0);
     }
     __builtin_amdgcn_sched_barrier(0);
     STAMP(3);
@@ -548,7 +581,7 @@ bool x6_ok(const GemmArgs& g, bool vec, int fwd_bn = XBN) {     // fwd_bn: weigh
   return seg_ok(g.a_nper, g.M, XBM) && g.M % 4 == 0;
 }
 
-template <int MODE>
+template <int MODE, int NP>
 int launch_x6(const GemmArgs& g, hipStream_t st) {
   const int64_t tiles = ((g.M + XBM - 1) / XBM) * ((g.N + XBN - 1) / XBN) * g.nsplit;
   if (tiles <= 0) return GCT_OK;
@@ -558,7 +591,7 @@ int launch_x6(const GemmArgs& g, hipStream_t st) {
   }
   static bool attr_set = false;   // per instantiation
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_x6_kernel<MODE>,
+    hipError_t e = hipFuncSetAttribute((const void*)gemm_x6_kernel<MODE, NP>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, X_LDS_BYTES);
     if (e != hipSuccess) {
       gct_set_error("gemm_x6: cannot reserve %d bytes of LDS: %s", X_LDS_BYTES, hipGetErrorString(e));
@@ -566,8 +599,8 @@ int launch_x6(const GemmArgs& g, hipStream_t st) {
     }
     attr_set = true;
   }
-  hipLaunchKernelGGL((gemm_x6_kernel<MODE>), dim3((unsigned)tiles), dim3(512), X_LDS_BYTES, st, g);
-  ++g_x6_kernel_launches;
+  hipLaunchKernelGGL((gemm_x6_kernel<MODE, NP>), dim3((unsigned)tiles), dim3(512), X_LDS_BYTES, st, g);
+  ++(NP == 3 ? g_x6_kernel_launches : g_x3_kernel_launches);
   GCT_LAUNCH_CHECK("gemm_x6");
   return GCT_OK;
 }
@@ -586,9 +619,11 @@ constexpr int XS_APL = SBM * 64, XS_BPL = SBN * 64, XS_STAGE = 3 * XS_APL + 3 * 
 constexpr int XS_LDS_BYTES = 2 * XS_STAGE;
 
 // MODE = X6_FWD: B = W planes [N][K] (row reads); X6_DGRAD: A = dY [M][K'] (K' segmented), B = W planes [K'][N] natural,
-// transposed reads -- the tail rows of a tail-balanced dgrad launch (gemm.hip launch_x6_tail_split).
-template <int MODE>
+// transposed reads -- the tail rows of a tail-balanced dgrad launch (gemm.hip launch_x6_tail_split).  NP as for
+// gemm_x6_kernel (3: bf16x6, 2: bf16x3; same LDS layout).
+template <int MODE, int NP = 3>
 __global__ __launch_bounds__(512) void gemm_x6s_kernel(const GemmArgs g) {
+  static_assert(NP == 2 || NP == 3, "bf16x3 or bf16x6");
   extern __shared__ __attribute__((aligned(16))) unsigned char xlds[];
   constexpr bool B_TR = MODE == X6_DGRAD;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -630,22 +665,21 @@ __global__ __launch_bounds__(512) void gemm_x6s_kernel(const GemmArgs g) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[i][j] = x6_f32x4{0.f, 0.f, 0.f, 0.f};
   float4 pa;
-  x6_u32x4 pb[3];
+  x6_u32x4 pb[NP];
   auto gload = [&](int64_t k0) {
     int64_t ao, bko;
     koff(k0, ao, bko);
     pa = *reinterpret_cast<const float4*>(ap + ao);
 #pragma unroll
-    for (int p = 0; p < 3; ++p) pb[p] = *reinterpret_cast<const x6_u32x4*>(bp + p * g.bp_stride + bko);
+    for (int p = 0; p < NP; ++p) pb[p] = *reinterpret_cast<const x6_u32x4*>(bp + p * g.bp_stride + bko);
   };
   auto lstore = [&](unsigned char* st) {
-    x6_u32x2 h, m, l;
-    x6_split4(pa, h, m, l);
-    *reinterpret_cast<x6_u32x2*>(st + 0 * XS_APL + sta) = h;
-    *reinterpret_cast<x6_u32x2*>(st + 1 * XS_APL + sta) = m;
-    *reinterpret_cast<x6_u32x2*>(st + 2 * XS_APL + sta) = l;
+    x6_u32x2 pc[NP];
+    x6_split4n<NP>(pa, pc);
 #pragma unroll
-    for (int p = 0; p < 3; ++p) *reinterpret_cast<x6_u32x4*>(st + 3 * XS_APL + p * XS_BPL + stb) = pb[p];
+    for (int p = 0; p < NP; ++p) *reinterpret_cast<x6_u32x2*>(st + p * XS_APL + sta) = pc[p];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) *reinterpret_cast<x6_u32x4*>(st + 3 * XS_APL + p * XS_BPL + stb) = pb[p];
   };
   const int fr = lane & 15, fc = lane >> 4;
   const int tq = (lane & 15) >> 2, tp = lane & 3;
@@ -662,11 +696,11 @@ __global__ __launch_bounds__(512) void gemm_x6s_kernel(const GemmArgs g) {
   __syncthreads();
   for (int64_t kt = 0; kt < nkt; ++kt) {
     const unsigned char* st = xlds + (kt & 1) * XS_STAGE;
-    x6_bf16x8 fa[2][3], fb[2][3];
+    x6_bf16x8 fa[2][NP], fb[2][NP];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) {
+      for (int p = 0; p < NP; ++p) {
         fa[i][p] = *reinterpret_cast<const x6_bf16x8*>(st + p * XS_APL + fao + i * 1024);
         if (B_TR) fb[i][p] = x6_tr_frag(st + p * XS_BPL + fbo[i], 256);
         else fb[i][p] = *reinterpret_cast<const x6_bf16x8*>(st + p * XS_BPL + fbo[i]);
@@ -677,38 +711,41 @@ __global__ __launch_bounds__(512) void gemm_x6s_kernel(const GemmArgs g) {
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        X6_MFMA(fa[i][2], fb[j][0], acc[i][j]);
-        X6_MFMA(fa[i][0], fb[j][2], acc[i][j]);
-        X6_MFMA(fa[i][1], fb[j][1], acc[i][j]);
+        if constexpr (NP == 3) {
+          X6_MFMA(fa[i][NP - 1], fb[j][0], acc[i][j]);
+          X6_MFMA(fa[i][0], fb[j][NP - 1], acc[i][j]);
+          X6_MFMA(fa[i][1], fb[j][1], acc[i][j]);
+        }
         X6_MFMA(fa[i][1], fb[j][0], acc[i][j]);
         X6_MFMA(fa[i][0], fb[j][1], acc[i][j]);
         X6_MFMA(fa[i][0], fb[j][0], acc[i][j]);
       }
 #ifndef GCT_X6S_PLAIN
     // issue order: the MFMAs of the first row tile start as soon as its fragments are in; the second row tile's
-    // fragments, the split of tile t+1, its LDS stores and the loads of tile t+2 go between the MFMAs
-    __builtin_amdgcn_sched_group_barrier(0x100, B_TR ? 15 : 9, 0);
+    // fragments, the split of tile t+1, its LDS stores and the loads of tile t+2 go between the MFMAs (NP = 2: 12
+    // MFMAs, 8 / 12 reads, 4 stores, 3 loads per K-tile -- the same order with scaled counts, not retuned)
+    __builtin_amdgcn_sched_group_barrier(0x100, NP == 3 ? (B_TR ? 15 : 9) : (B_TR ? 10 : 6), 0);
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+    for (int q = 0; q < (NP == 3 ? 3 : 2); ++q) {
+      __builtin_amdgcn_sched_group_barrier(0x008, NP == 3 ? 2 : 1, 0);
       __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
     }
 #pragma unroll
-    for (int q = 0; q < 6; ++q) {
+    for (int q = 0; q < (NP == 3 ? 6 : 3); ++q) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);
+      __builtin_amdgcn_sched_group_barrier(0x002, NP == 3 ? 5 : 4, 0);
     }
 #pragma unroll
-    for (int q = 0; q < 6; ++q) {
+    for (int q = 0; q < 2 * NP; ++q) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
     }
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < NP + 1; ++q) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
     }
-    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+    if constexpr (NP == 3) __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
 #endif
     __syncthreads();
   }
@@ -751,21 +788,21 @@ inline bool x6s_dgrad_ok(const GemmArgs& g, bool vec) {
          70 * g.lda < (1ll << 31) && 40 * g.ldb < (1ll << 31);
 }
 
-template <int MODE = X6_FWD>
+template <int MODE, int NP>
 inline int launch_x6s(const GemmArgs& g, hipStream_t st) {
   const int64_t tiles = ((g.M + SBM - 1) / SBM) * ((g.N + SBN - 1) / SBN);
   if (tiles <= 0) return GCT_OK;
   static bool attr_set = false;        // per instantiation
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_x6s_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, XS_LDS_BYTES);
+    hipError_t e = hipFuncSetAttribute((const void*)gemm_x6s_kernel<MODE, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, XS_LDS_BYTES);
     if (e != hipSuccess) {
       gct_set_error("gemm_x6s: cannot reserve %d bytes of LDS: %s", XS_LDS_BYTES, hipGetErrorString(e));
       return GCT_ERR_HIP;
     }
     attr_set = true;
   }
-  hipLaunchKernelGGL(gemm_x6s_kernel<MODE>, dim3((unsigned)tiles), dim3(512), XS_LDS_BYTES, st, g);
-  ++g_x6_kernel_launches;
+  hipLaunchKernelGGL((gemm_x6s_kernel<MODE, NP>), dim3((unsigned)tiles), dim3(512), XS_LDS_BYTES, st, g);
+  ++(NP == 3 ? g_x6_kernel_launches : g_x3_kernel_launches);
   GCT_LAUNCH_CHECK("gemm_x6s");
   return GCT_OK;
 }

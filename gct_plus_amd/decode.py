@@ -226,7 +226,7 @@ class KVDecoder:
                 qw[:off].copy_(a.q_linear.weight)
                 self.zq_b[li][:off].copy_(a.q_linear.bias)
                 ow[:, :off].copy_(a.out.weight)
-        if ops.gemm_get_mode() == ops.GEMM_BF16X6:
+        if ops.gemm_get_mode() != ops.GEMM_F32:          # bf16x6 / bf16x3
             self.zplanes = ops.split_planes(self.zflat, self.zplanes)
             ops.register_planes(self.zflat, self.zplanes)
 

@@ -90,7 +90,7 @@ class FlatModelMixin:
         if f is None or not f["params"].is_cuda:
             return
         from . import ops
-        if ops.gemm_get_mode() != ops.GEMM_BF16X6:
+        if ops.gemm_get_mode() == ops.GEMM_F32:          # bf16x6 and bf16x3 share the planes
             if "planes" in f:
                 ops.unregister_planes(f["params"])
                 del f["planes"]

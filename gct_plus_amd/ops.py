@@ -281,6 +281,7 @@ def _seg3(ts: Sequence[Optional[torch.Tensor]]):
 
 # ---- bf16x6 GEMM mode: pre-split weight planes --------------------------------------------------
 GEMM_F32, GEMM_BF16X6 = 0, 1
+GEMM_BF16X3 = 2   # opt-in: two bf16 pieces, three products, < 3.02 * 2^-16 |a*b| dropped per product (gemm_x6.inc)
 _PLANES = []     # [(base_ptr, end_ptr, planes tensor (int16 [3, numel]), numel)]
 
 
@@ -290,6 +291,11 @@ def gemm_set_mode(mode: int):
 
 def gemm_get_mode() -> int:
     return _L().gct_gemm_get_mode()
+
+
+def gemm_x3_launches() -> int:
+    """Launches of the bf16x3 (2-piece) GEMM kernels since load."""
+    return int(_L().gct_gemm_x3_launches())
 
 
 def gemm_launch_counts():

@@ -116,6 +116,10 @@ def main(rank, world_size, argv=None):
     os.makedirs(args.model_folder, exist_ok=True)
     LOG = get_logger("train", os.path.join(args.model_folder, "records.log"))
     LOG.info("random seed: %s", args.seed)
+    if args.matmul_precision == "high":          # process-wide, so set in every rank's own process
+        from . import ops
+        ops.gemm_set_mode(ops.GEMM_BF16X3)
+        LOG.info("matmul precision: high (bf16x3 GEMMs, opt-in)")
     if rank == 0:
         LOG.info(args)
         LOG.info(f"world size: {world_size}")

@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 13
+#define GCT_ABI_VERSION 14
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -131,22 +131,35 @@ int gct_linear_wgrad(const float* dy0, const float* dy1, const float* dy2, int64
                      float* db0, float* db1, float* db2, float* ws, void* stream);
 
 /* ---- GEMM arithmetic mode and pre-split weights ------------------------------------------
- * The nn.Linear GEMMs (Model/sublayers.py:54-59,64-66,70,81-88) run in one of two modes, both with
+ * The nn.Linear GEMMs (Model/sublayers.py:54-59,64-66,70,81-88) run in one of two modes with
  * fp32 operands, fp32 results and fp32-class error:
  *   GCT_GEMM_F32    : v_mfma_f32_32x32x2_f32 (fp32 fma chains);
  *   GCT_GEMM_BF16X6 : every operand element is split EXACTLY into three bf16 values (8+8+8
  *                     significand bits) and the six leading partial products are accumulated in
  *                     fp32 by v_mfma_f32_16x16x32_bf16; launches that do not qualify (odd shapes,
  *                     skinny M, no planes for fwd/dgrad) use the fp32 kernels.
- * Process-wide; default from the environment (GCT_GEMM_MODE=f32|x6, x6 when unset). */
+ * and one opt-in lower-precision mode (PyTorch's "high" float32 matmul precision tier):
+ *   GCT_GEMM_BF16X3 : the bf16x6 routes and kernels with two pieces per element, x ~ h + m (the
+ *                     first two pieces of the same split, so the same weight planes serve), and
+ *                     the three leading products am*bh + ah*bm + ah*bh.  Dropped per product:
+ *                     <= (3u^2 + 4u^3 + u^4)|a*b| < 3.02 * 2^-16 |a*b| (u = 2^-8), i.e. about 16
+ *                     good bits instead of 24, plus the fp32 accumulation error all modes share.
+ *                     Launches that take the fp32 kernels in bf16x6 mode take them here too.
+ * Process-wide; default from the environment (GCT_GEMM_MODE=f32|x6, x6 when unset); bf16x3 only
+ * through gct_gemm_set_mode. */
 #define GCT_GEMM_F32 0
 #define GCT_GEMM_BF16X6 1
+#define GCT_GEMM_BF16X3 2
 int gct_gemm_set_mode(int mode);
 int gct_gemm_get_mode(void);
-/* diagnostics: out2[0] = launches of the fp32-MFMA tile kernels so far, out2[1] = of the bf16x6 kernels */
+/* diagnostics: out2[0] = launches of the fp32-MFMA tile kernels so far, out2[1] = of the bf16x6 kernels
+ * (bf16x3 calls are counted by neither) */
 int gct_gemm_launch_counts(int64_t* out2);
-/* diagnostics: gemm_x6_kernel launches so far (a tail-balanced forward / dgrad call launches it twice) */
+/* diagnostics: bf16x6 (3-piece) gemm_x6 / gemm_x6s kernel launches so far (a tail-balanced forward / dgrad
+ * call launches two) */
 int64_t gct_gemm_x6_kernel_launches(void);
+/* diagnostics: bf16x3 (2-piece) launches of the same kernels so far, counted the same way */
+int64_t gct_gemm_x3_launches(void);
 
 /* planes[p*plane_stride + i] = p-th bf16 piece (p = 0 high, 1 middle, 2 low) of src[i], i < numel.
  * numel % 4 == 0, plane_stride % 4 == 0, plane_stride >= numel; src 16-B aligned.  Run it over the

@@ -1,21 +1,28 @@
-"""Randomised parity sweep of the nn.Linear kernels (forward / dgrad / wgrad, all fused epilogues, both arithmetic modes)
-against fp64 on the GPU.  Shapes are drawn around the places where the host side changes route: tile counts next to
+"""Randomised parity sweep of the nn.Linear kernels (forward / dgrad / wgrad, all fused epilogues, the three arithmetic
+modes) against fp64 on the GPU.  Shapes are drawn around the places where the host side changes route: tile counts next to
 multiples of the 256 CUs (tail balancing), few tiles (skinny split-K, panel kernel, split-K over the whole problem),
 ragged M / N, K from 32 to 4096, 1-3 weight segments, quad-mapped GELU-backward, weight gradients over a tile list.
   python tools/gemm_fuzz.py --cases 80 [--seed 1]
-Prints one line per case; exit code 1 when a case is outside the tolerance (the tolerances of tests/test_kernels_gpu.py)."""
+Prints one line per case; exit code 1 when a case is outside the tolerance (the tolerances of tests/test_kernels_gpu.py;
+bf16x3 on top of them its own bound, X3_REL * sum_k |a_k b_k| per output, gemm_x6.inc)."""
 import argparse, math, sys, types, torch
 sys.path.insert(0, ".")
 from gct_plus_amd import ops
 DEV = "cuda"
+MODES = (ops.GEMM_F32, ops.GEMM_BF16X6, ops.GEMM_BF16X3)
+X3_REL = 3.02 * 2.0 ** -16     # bf16x3: what the dropped partial products may add, per unit of sum_k |a_k b_k|
+X3_GAIN = 1.2                  # epilogue slope on top (GELU' <= 1.13) and the rounding of the result
 
 
-def _err(a, ref, atol, rtol):
-    """max over elements of |a - ref| / (atol + rtol |ref|): <= 1 passes"""
+def _err(a, ref, atol, rtol, extra=None):
+    """max over elements of |a - ref| / (atol + rtol |ref| + extra): <= 1 passes"""
     a, ref = a.double(), ref.double()
     if not torch.isfinite(a).all():
         return float("inf")
-    return float(((a - ref).abs() / (atol + rtol * ref.abs())).max()) if a.numel() else 0.0
+    den = atol + rtol * ref.abs()
+    if extra is not None:
+        den = den + extra
+    return float(((a - ref).abs() / den).max()) if a.numel() else 0.0
 
 
 def _shape(ri):
@@ -42,7 +49,7 @@ def _shape(ri):
     return max(M, 1), max(N, 1), K
 
 
-def sweep(cases=60, seed=1, verbose=True):
+def sweep(cases=60, seed=1, verbose=True, modes=MODES):
     g = torch.Generator().manual_seed(seed)
     ri = lambda lo, hi: int(torch.randint(lo, hi + 1, (1,), generator=g))          # noqa: E731
     gd = torch.Generator(device=DEV).manual_seed(seed)
@@ -88,10 +95,16 @@ def sweep(cases=60, seed=1, verbose=True):
             nq_full = M // 4 + ri(1, 400)
             quads = torch.randperm(nq_full, generator=g)[:M // 4].sort().values.to(torch.int32).to(DEV)
         errs, res = {}, {}
-        k0 = ops._L().gct_gemm_x6_kernel_launches()
+        k0, k3 = ops._L().gct_gemm_x6_kernel_launches(), ops.gemm_x3_launches()
+        if ops.GEMM_BF16X3 in modes:        # sum_k |a_k b_k| of every output: the scale of the bf16x3 bound
+            Wa = W.abs()
+            s_fwd, s_dg = x.double().abs() @ Wa.t(), dy.double().abs() @ Wa
+            s_wg = dy.double().abs().t() @ x.double().abs()
         try:
-            for mode in (ops.GEMM_F32, ops.GEMM_BF16X6):
+            for mode in modes:
                 ops.gemm_set_mode(mode)
+                x3 = mode == ops.GEMM_BF16X3
+                ex = (lambda s: X3_REL * X3_GAIN * s) if x3 else (lambda s: None)      # noqa: E731
                 y, pre = torch.empty(M, N, device=DEV), torch.empty(M, N, device=DEV)
                 if fwd_epi == 0:
                     ops.linear_fwd(x, wv, bs, dys(y), N)
@@ -125,15 +138,17 @@ def sweep(cases=60, seed=1, verbose=True):
                 # references
                 e = {}
                 if fwd_epi == 0:
-                    e["fwd"] = _err(y, ref_y, 2e-5, 2e-5)
+                    e["fwd"] = _err(y, ref_y, 2e-5, 2e-5, ex(s_fwd) if x3 else None)
                 elif fwd_epi == 1:
                     keep = (y != 0) | (ref_y == 0)
-                    e["fwd"] = _err(torch.where(keep, y.double() * (1 - p), ref_y), ref_y, 3e-5, 3e-5)
-                    e["pre"] = _err(pre, u, 2e-5, 2e-5)
+                    e["fwd"] = _err(torch.where(keep, y.double() * (1 - p), ref_y), ref_y, 3e-5, 3e-5,
+                                    ex(s_fwd) if x3 else None)
+                    e["pre"] = _err(pre, u, 2e-5, 2e-5, ex(s_fwd) if x3 else None)
                     e["rate"] = abs(float(keep.double().mean()) - (1 - p)) / (0.02 + 3.0 / math.sqrt(M * N)) if p else 0.0
                 else:
                     kept = (y != resid)
-                    e["fwd"] = _err(torch.where(kept, (y.double() - resid.double()) * (1 - p), u), u, 3e-5, 3e-5)
+                    e["fwd"] = _err(torch.where(kept, (y.double() - resid.double()) * (1 - p), u), u, 3e-5, 3e-5,
+                                    ex(s_fwd) if x3 else None)
                     e["rate"] = abs(float(kept.double().mean()) - (1 - p)) / (0.02 + 3.0 / math.sqrt(M * N)) if p else 0.0
                 gx = dy.double() @ W
                 if dg_epi == 1:
@@ -142,19 +157,21 @@ def sweep(cases=60, seed=1, verbose=True):
                     pd = pre_in.double().requires_grad_()
                     (torch.nn.functional.gelu(pd) * gx).sum().backward()
                     gx = pd.grad
-                e["dgrad"] = _err(dx, gx, 5e-5, 1e-4)
+                e["dgrad"] = _err(dx, gx, 5e-5, 1e-4, ex(s_dg) if x3 else None)
                 tw = 1.5e-4 * math.sqrt(M / 100 + 1)      # max over up to 1e7 outputs of an fp32 chain of M terms
-                e["wgrad"] = _err(res[mode][3], dy.double().t() @ x.double(), tw, 1e-4)
+                e["wgrad"] = _err(res[mode][3], dy.double().t() @ x.double(), tw, 1e-4, ex(s_wg) if x3 else None)
                 e["dbias"] = _err(res[mode][4], dy.double().sum(0), tw, 1e-4)
                 errs[mode] = e
-            # same dropout mask in both modes
-            a, c = res[ops.GEMM_F32], res[ops.GEMM_BF16X6]
+            # same dropout mask in every mode
+            a = res[modes[0]]
             same_mask = True
             # (an element whose kept value is below the rounding of what it is added to cannot be told from a dropped one)
-            if p and fwd_epi == 1:
-                same_mask = not bool((((a[0] == 0) != (c[0] == 0)) & (ref_y.abs() > 1e-4)).any())
-            if p and fwd_epi == 2:
-                same_mask = not bool((((a[0] == resid) != (c[0] == resid)) & (u.abs() > 1e-4)).any())
+            for mode in modes[1:]:
+                c = res[mode]
+                if p and fwd_epi == 1:
+                    same_mask &= not bool((((a[0] == 0) != (c[0] == 0)) & (ref_y.abs() > 1e-4)).any())
+                if p and fwd_epi == 2:
+                    same_mask &= not bool((((a[0] == resid) != (c[0] == resid)) & (u.abs() > 1e-4)).any())
         finally:
             ops.gemm_set_mode(ops.GEMM_BF16X6)
             if use_planes:
@@ -163,7 +180,8 @@ def sweep(cases=60, seed=1, verbose=True):
         ok = w_case <= 1.0 and same_mask
         worst = max(worst, w_case)
         line = (f"case {case:3d} M={M:6d} K={K:5d} N={N:5d} nseg={nseg} fwd_epi={fwd_epi} dgrad_epi={dg_epi} p={p} "
-                f"planes={int(use_planes)} qmap={int(quads is not None)} x6_launches={ops._L().gct_gemm_x6_kernel_launches() - k0} worst={w_case:.3f} mask_equal={same_mask}")
+                f"planes={int(use_planes)} qmap={int(quads is not None)} x6_launches={ops._L().gct_gemm_x6_kernel_launches() - k0} "
+                f"x3_launches={ops.gemm_x3_launches() - k3} worst={w_case:.3f} mask_equal={same_mask}")
         if verbose or not ok:
             print(line + ("" if ok else "   <-- FAIL " + repr(errs)), flush=True)
         if not ok:
@@ -176,6 +194,8 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", type=int, default=60)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--modes", default="f32,x6,x3", help="comma-separated subset of f32, x6, x3")
     a = ap.parse_args()
-    worst, bad = sweep(a.cases, a.seed)
+    names = {"f32": ops.GEMM_F32, "x6": ops.GEMM_BF16X6, "x3": ops.GEMM_BF16X3}
+    worst, bad = sweep(a.cases, a.seed, modes=tuple(names[m] for m in a.modes.split(",")))
     sys.exit(1 if bad else 0)

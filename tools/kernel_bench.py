@@ -28,7 +28,12 @@ def timeit(fn, reps=10, warm=3):
     return ts[len(ts) // 2], ts[0]
 
 
-def gemm_suite(reps, only=None):
+GEMM_MODES = {"f32": ops.GEMM_F32, "x6": ops.GEMM_BF16X6, "x3": ops.GEMM_BF16X3}
+
+
+def gemm_suite(reps, only=None, modes=None, rounds=3):
+    """modes: names of GEMM_MODES to time (None: the process mode).  With several, every call is timed in each mode in
+    `rounds` interleaved rounds (median of `reps` per round) and the line gives the median over rounds and their spread."""
     dev = "cuda"
     shapes = [("qkv", 40960, 512, 512, 3), ("out", 40960, 512, 512, 1), ("ffn1", 40960, 512, 2048, 1),
               ("ffn2", 40960, 2048, 512, 1), ("kv", 40960, 512, 512, 2), ("mulv", 40960, 512, 128, 2),
@@ -40,8 +45,7 @@ def gemm_suite(reps, only=None):
         x = torch.randn(M, K, device=dev)
         wflat = torch.randn(nseg * nper * K, device=dev) * K ** -0.5      # one buffer, as flat.py lays weights out
         ws = [wflat[s * nper * K:(s + 1) * nper * K].view(nper, K) for s in range(nseg)]
-        if ops.gemm_get_mode() == ops.GEMM_BF16X6:
-            ops.register_planes(wflat, ops.split_planes(wflat))
+        ops.register_planes(wflat, ops.split_planes(wflat))   # read in the bf16 modes only (both use the same planes)
         bs = [torch.randn(nper, device=dev) for _ in range(nseg)]
         y = torch.empty(M, N, device=dev)
         outs = [y[:, s * nper:] for s in range(nseg)]
@@ -54,9 +58,27 @@ def gemm_suite(reps, only=None):
         for kind, fn in (("fwd", lambda: ops.linear_fwd(x, ws, bs, outs, N)),
                          ("dgrad", lambda: ops.linear_dgrad(dys, N, M, ws, dx)),
                          ("wgrad", lambda: ops.linear_wgrad(dys, N, x, dws, dbs))):
-            med, best = timeit(fn, reps)
-            print(f"gemm {name:5s} {kind:5s} M={M} K={K} N={N}: {med*1e6:8.1f} us  {fl/med/1e12:6.1f} TF  (best {fl/best/1e12:6.1f})",
-                  flush=True)
+            if not modes:
+                med, best = timeit(fn, reps)
+                print(f"gemm {name:5s} {kind:5s} M={M} K={K} N={N}: {med*1e6:8.1f} us  {fl/med/1e12:6.1f} TF  (best {fl/best/1e12:6.1f})",
+                      flush=True)
+                continue
+            keep = ops.gemm_get_mode()
+            per = {m: [] for m in modes}
+            for _ in range(rounds):
+                for m in modes:
+                    ops.gemm_set_mode(GEMM_MODES[m])
+                    per[m].append(timeit(fn, reps)[0])
+            ops.gemm_set_mode(keep)
+            for m in modes:
+                ts = sorted(per[m])
+                med = ts[len(ts) // 2]
+                print(f"gemm {name:5s} {kind:5s} {m:3s} M={M} K={K} N={N}: {med*1e6:8.1f} us  {fl/med/1e12:6.1f} TF  "
+                      f"(rounds {ts[0]*1e6:.1f}..{ts[-1]*1e6:.1f} us)", flush=True)
+            if len(modes) > 1:
+                meds = {m: sorted(per[m])[rounds // 2] for m in modes}
+                print(f"gemm {name:5s} {kind:5s} " + "  ".join(f"{m}/{modes[0]} {meds[m] / meds[modes[0]]:.3f}"
+                                                              for m in modes[1:]), flush=True)
 
 
 def decgemm_suite(reps):
@@ -67,7 +89,7 @@ def decgemm_suite(reps):
                            ("ffn1", 512, 2048), ("ffn2", 2048, 512)):
             x = torch.randn(M, K, device=dev)
             w = torch.randn(N * K, device=dev) * K ** -0.5
-            if ops.gemm_get_mode() == ops.GEMM_BF16X6:
+            if ops.gemm_get_mode() != ops.GEMM_F32:
                 ops.register_planes(w, ops.split_planes(w))
             b, y = torch.randn(N, device=dev), torch.empty(M, N, device=dev)
             wsb = torch.empty(int(ops._L().gct_linear_fwd_ws_bytes(M, K, N)) // 4 + 64, device=dev)
@@ -84,7 +106,7 @@ def epi_suite(reps):
     for name, K, N in (("out", 512, 512), ("ffn1", 512, 2048), ("ffn2", 2048, 512)):
         x = torch.randn(M, K, device=dev)
         w = torch.randn(N * K, device=dev) * K ** -0.5
-        if ops.gemm_get_mode() == ops.GEMM_BF16X6:
+        if ops.gemm_get_mode() != ops.GEMM_F32:
             ops.register_planes(w, ops.split_planes(w))
         W = w.view(N, K)
         b, y = torch.randn(N, device=dev), torch.empty(M, N, device=dev)
@@ -169,9 +191,16 @@ if __name__ == "__main__":
     ap.add_argument("--suite", default="gemm,attn,bw")
     ap.add_argument("--only", default="")
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--gemm-mode", default="",
+                    help="gemm suite: comma-separated modes to time, interleaved (f32, x6, x3; e.g. x6,x3). "
+                         "Default: the process mode")
     a = ap.parse_args()
+    gmodes = [m for m in a.gemm_mode.split(",") if m]
+    for m in gmodes:
+        if m not in GEMM_MODES:
+            ap.error(f"--gemm-mode: unknown mode {m!r} (f32, x6, x3)")
     if "gemm" in a.suite.split(","):
-        gemm_suite(a.reps, a.only.split(",") if a.only else None)
+        gemm_suite(a.reps, a.only.split(",") if a.only else None, gmodes or None)
     if "decgemm" in a.suite:
         decgemm_suite(a.reps)
     if "epi" in a.suite.split(","):
