@@ -18,17 +18,18 @@
 //    when everything is masked) stay exact.  Dropout keep bits: one Philox call per (query, 8 keys) in
 //    the lane that owns them, only for tiles that are computed.
 //  * The backward recomputes probabilities from the saved log-sum-exp (no [B,H,L,L] tensor).
-// Two kernel families:
-//  * L_k <= 96 (every shipped configuration): BARRIER-FREE kernels, one wave per work item, no workgroup
-//    cooperation, a non-persistent grid the dispatcher balances: attn_fwd_direct_kernel (item = pair x query
+// Two kernel families; plan_attn_fwd / plan_attn_bwd (below) choose from the shape alone:
+//  * L_k <= GCT_ATTN_DIRECT_MAX_KEYS = 96 (every shipped configuration): BARRIER-FREE kernels, one wave per work item,
+//    no workgroup cooperation, a non-persistent grid the dispatcher balances: attn_fwd_direct_kernel (item = pair x query
 //    tile), attn_bwd_dq_kernel (pair x query tile -> dQ + per-row scalars / keep bits / visited tiles in a
 //    workspace), attn_bwd_dkv_kernel (pair x key tile -> dK, dV).  Operands reach a wave coalesced and are turned
 //    into the row-per-lane MFMA fragments in wave-private LDS tiles (WaveTile); a pair's K / V are re-read by its
 //    query tiles from L2, not HBM (measured HBM traffic = algorithmic bytes +1 %).  Register use is kept low on
 //    purpose (71 / 118 / 120 VGPRs): what hides the memory latency here is the number of resident waves.
-//  * 96 < L <= 208: the LDS kernels attn_fwd_kernel / attn_bwd_kernel -- one (batch, head) pair at a time in a
+//  * 96 < L_k <= 208: the LDS kernels attn_fwd_kernel / attn_bwd_kernel -- one (batch, head) pair at a time in a
 //    persistent 6-wave workgroup's LDS (K and V [L][dk+4] fp32, software-pipelined over the pairs; the backward in
-//    two phases that reuse one LDS region).  GCT_ATTN_FWD_LDS=1 / GCT_ATTN_BWD_LDS=1 select them for any length.
+//    two phases that reuse one LDS region).  The direct backward keeps its per-row records in a caller-owned workspace
+//    (gct_attn_bwd_ws_bytes), which it requires.
 // Roofline: HBM-bound on q,k,v,o (+ gradients): 0.57 / 0.51 of it fwd / bwd at B=512;
 // 4.L.d flop/token ~ 3 % of the step's flops.
 #include "common.h"
@@ -40,6 +41,11 @@ namespace {
 constexpr int ATT_THREADS = 384;       // 6 waves: one per query / key tile at L <= 96
 constexpr int MASK_W = 8;              // packed mask: 8 x 32 bits per query row
 constexpr int L_MAX = 208;             // 13 tiles of 16: covers the reference's 200-row positional table + 3 conditions
+constexpr int DIRECT_NT = GCT_ATTN_DIRECT_MAX_KEYS / 16;   // key tiles of the direct kernels
+// packed mask words (and dropout keep words) per query row of a kernel instantiated for NT key tiles of 16
+constexpr int mask_words(int nt) { return (nt + 1) / 2; }
+static_assert(GCT_ATTN_DIRECT_MAX_KEYS % 32 == 0 && mask_words(DIRECT_NT) == GCT_ATTN_DIRECT_MAX_KEYS / 32,
+              "the direct kernels' rows are whole mask words");
 
 struct AttnArgs {
   // strides are 32-bit (checked on the host): 64-bit strides cost SGPRs this kernel does not have to spare -- they
@@ -86,7 +92,7 @@ struct AttnArgs {
 #endif
 };
 
-// Diagnostic build only (tools/attn_stamps.hip, -DGCT_STAMPS): s_memtime at the pipeline's seams, summed per wave.
+// Diagnostic build only (tools/attn_stamps.hip, -DGCT_STAMPS): s_memtime at the direct kernels' seams, summed per wave.
 #ifdef GCT_STAMPS
 #define ASTAMP_DECL unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev; \
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev)::"memory")
@@ -99,10 +105,7 @@ struct AttnArgs {
     seg[i] += t__ - tprev;                                                             \
     tprev = t__;                                                                       \
   } while (0)
-#define ASTAMP_OUT                                                                     \
-  if (a.stamps && (threadIdx.x & 63) == 0 && blockIdx.x < 64)                          \
-    for (int i = 0; i < 8; ++i) a.stamps[((size_t)blockIdx.x * (ATT_THREADS / 64) + (threadIdx.x >> 6)) * 8 + i] = seg[i]
-// direct kernels: one record per wave (= item), items [GCT_STAMP_ITEM0, GCT_STAMP_ITEM0 + 4096)
+// one record per wave (= item), items [GCT_STAMP_ITEM0, GCT_STAMP_ITEM0 + 4096)
 #define GCT_STAMP_ITEM0 8192
 #define DSTAMP_OUT_AT(item, rec0)                                                      \
   if (a.stamps && (threadIdx.x & 63) == 0 && (item) >= GCT_STAMP_ITEM0 && (item) < GCT_STAMP_ITEM0 + 4096)  \
@@ -111,7 +114,6 @@ struct AttnArgs {
 #else
 #define ASTAMP_DECL
 #define ASTAMP(i)
-#define ASTAMP_OUT
 #define DSTAMP_OUT(item)
 #define DSTAMP_OUT_AT(item, rec0)
 #endif
@@ -292,9 +294,9 @@ __device__ __forceinline__ float score_of(float s, bool in_range, bool visible, 
 // mask words of this lane's query row.
 template <int NDT, int NT, bool PROBS, typename AfterS>
 __device__ __forceinline__ void fwd_unit(const AttnArgs& a, int b, int h, int u, float4 (&bq)[NDT],
-                                         const uint32_t (&mw)[(NT + 1) / 2], const float* Ks, const float* Vs, int nkt,
+                                         const uint32_t (&mw)[mask_words(NT)], const float* Ks, const float* Vs, int nkt,
                                          int lane, AfterS after_s) {
-  constexpr int DK = 16 * NDT, SD = DK + 4, MW = (NT + 1) / 2;
+  constexpr int DK = 16 * NDT, SD = DK + 4, MW = mask_words(NT);
   const int g = lane >> 4, c16 = lane & 15;
   const int q = 16 * u + c16;
   const uint32_t use = tiles_for_q<MW>(mw, q, a.Lq, a.Lk, nkt);
@@ -386,9 +388,10 @@ __device__ __forceinline__ void fwd_unit(const AttnArgs& a, int b, int h, int u,
   }
 }
 
-template <int NDT, int NT, bool PIPE, int OCC>
-__global__ __launch_bounds__(ATT_THREADS, OCC) void attn_fwd_kernel(const AttnArgs a) {
-  constexpr int DK = 16 * NDT, SD = DK + 4, NW = ATT_THREADS / 64, MW = (NT + 1) / 2;
+template <int NDT, int NT>
+__global__ __launch_bounds__(ATT_THREADS, (NT <= 8 ? 3 : 2)) void attn_fwd_kernel(const AttnArgs a) {
+  constexpr int DK = 16 * NDT, SD = DK + 4, NW = ATT_THREADS / 64, MW = mask_words(NT);
+  constexpr bool PIPE = NT <= 8;         // next pair's K / V / Q requested during this pair's MFMAs (NT 13: after them)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c16 = lane & 15;
   const int LQP = (a.Lq + 15) & ~15, LKP = (a.Lk + 15) & ~15, nkt = LKP / 16, nqt = LQP / 16;
@@ -409,18 +412,14 @@ __global__ __launch_bounds__(ATT_THREADS, OCC) void attn_fwd_kernel(const AttnAr
     row_frag_global<NDT>(bq, a.q, a.ldq, b, h, a.Lq, 16 * wave + c16, g);
     if (a.mbits) mask_row_raw<MW>(mraw, a, b, 16 * wave + c16);
   }
-  ASTAMP_DECL;
   for (;;) {
     const int b = pair / a.H, h = pair - b * a.H;
-    ASTAMP(0);                           // loop seam
     const int Lk_in = a.klen ? a.klen[b] : a.Lk;          // keys that exist as rows (the others are masked: zero rows)
     sk.store(Ks, Lk_in, LKP, tid);
     sv.store(Vs, Lk_in, LKP, tid);
     uint32_t mw[MW];
     mask_row_use<MW>(mw, mraw, a, 16 * wave + c16);
-    ASTAMP(1);                           // wait for the staged K / V + LDS stores
     __syncthreads();
-    ASTAMP(2);                           // barrier 1
     const int next = pair + (int)gridDim.x;
     const bool more = next < a.npairs;
     const int nb = more ? next / a.H : b, nh = more ? next - nb * a.H : h;
@@ -432,7 +431,6 @@ __global__ __launch_bounds__(ATT_THREADS, OCC) void attn_fwd_kernel(const AttnAr
       sv.load_rows(a.v, a.ldv, nkr0, nh, kvo);
       if (a.mbits) mask_row_raw<MW>(mraw, a, nb, 16 * wave + c16);
     }
-    ASTAMP(3);                           // prefetch issue
     for (int u = wave; u < nqt; u += NW) {
       if (u != wave) {                   // only when there are more query tiles than waves (L > 96)
         row_frag_global<NDT>(bq, a.q, a.ldq, b, h, a.Lq, 16 * u + c16, g);
@@ -447,10 +445,8 @@ __global__ __launch_bounds__(ATT_THREADS, OCC) void attn_fwd_kernel(const AttnAr
       });
     }
     if (PIPE && more && wave >= nqt) row_frag_global<NDT>(bq, a.q, a.ldq, nb, nh, a.Lq, 16 * wave + c16, g);
-    ASTAMP(4);                           // compute
     if (!more) break;
     __syncthreads();                     // every wave is done reading Ks / Vs
-    ASTAMP(5);                           // barrier 2
     if (!PIPE) {
       sk.load_rows(a.k, a.ldk, nkr0, nh, kvo);
       sv.load_rows(a.v, a.ldv, nkr0, nh, kvo);
@@ -459,7 +455,6 @@ __global__ __launch_bounds__(ATT_THREADS, OCC) void attn_fwd_kernel(const AttnAr
     }
     pair = next;
   }
-  ASTAMP_OUT;
 }
 
 // ------------------------------------------------------------------------------ forward, direct
@@ -467,7 +462,7 @@ __global__ __launch_bounds__(ATT_THREADS, OCC) void attn_fwd_kernel(const AttnAr
 // come straight from L2 (a pair's K, V are 2 x L x 256 B and are read by its 5-6 query tiles within microseconds of each
 // other), so a wave never waits for another wave and the hardware dispatcher balances the SIMDs -- the LDS kernel
 // above puts 5-6 query tiles on the 4 SIMDs of a CU the same way for every pair and ends every pair on a barrier.
-// Same arithmetic, same order of operations, same dropout bits as fwd_unit; used for L_k <= 96.
+// Same arithmetic, same order of operations, same dropout bits as fwd_unit; used for L_k <= GCT_ATTN_DIRECT_MAX_KEYS.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 // NDT consecutive floats as a NATIVE vector (HIP's float4 is a struct: its copies are memcpy calls that keep whole
 // operand arrays in scratch memory when they sit under a condition)
@@ -514,13 +509,9 @@ __device__ __forceinline__ void tile_load(typename VecN<NDT>::T (&v)[4], const c
   }
 }
 
-#ifndef GCT_FWD_NH          // A/B knobs: -DGCT_FWD_NH=2 -DGCT_FWD_OCC=5, -DGCT_FWD_NH=3 -DGCT_FWD_OCC=4
-#define GCT_FWD_NH 1
-#define GCT_FWD_OCC 6
-#endif
 template <int NDT, int NT>
-__global__ __launch_bounds__(256, GCT_FWD_OCC) void attn_fwd_direct_kernel(const AttnArgs a) {
-  constexpr int DK = 16 * NDT, MW = (NT + 1) / 2;
+__global__ __launch_bounds__(256, 6) void attn_fwd_direct_kernel(const AttnArgs a) {
+  constexpr int DK = 16 * NDT, MW = mask_words(NT);
   typedef typename VecN<NDT>::T VT;
   const int lane = threadIdx.x & 63, g = lane >> 4, c16 = lane & 15;
   const int nqt = (a.Lq + 15) >> 4, nkt = (a.Lk + 15) >> 4;
@@ -550,26 +541,21 @@ __global__ __launch_bounds__(256, GCT_FWD_OCC) void attn_fwd_direct_kernel(const
   uint4 mraw[(MW + 3) / 4] = {};
   if (a.mbits) mask_row_raw<MW>(mraw, a, b, q);
   const char* kbase = reinterpret_cast<const char*>(a.k + kr0 * a.ldk + h * DK);                  // wave-uniform
-  VT tk[NT][4];
+  // K / V tiles are requested one at a time into one set of registers: 71 VGPRs, 6-7 waves per SIMD.  Requesting two,
+  // three or all six tiles ahead measured +1-3 %, +5 %, +12 % slower (87 / 103 / 150 VGPRs, 5 / 4 / 3 waves) -- what
+  // hides the L2 latency here is the other waves, not the depth of one wave's request queue
+  VT tk[4];
   // with the precomputed tile word (a scalar load) the K requests go out before the mask rows are back
   uint32_t use = 0;
-  // K / V tiles are requested in batches of NH that reuse one set of registers.  NH = 1: 71 VGPRs, 6-7 waves per SIMD;
-  // NH = 2: 87 VGPRs / 5 waves, +1-3 %; NH = 3: 103 / 4, +5 %; all six tiles at once: 150 VGPRs / 3 waves, +12 % --
-  // what hides the L2 latency here is the other waves, not the depth of one wave's request queue
-  constexpr int NH = GCT_FWD_NH;
   if (a.tbits) {
     use = __builtin_amdgcn_readfirstlane(a.tbits[(int64_t)b * a.tb_sb + u * a.tb_su]);
-#pragma unroll
-    for (int t = 0; t < NH; ++t)
-      if ((use >> t) & 1u) tile_load<NDT>(tk[t], kbase, a.ldk, 16 * t, klast, g, c16);
+    if (use & 1u) tile_load<NDT>(tk, kbase, a.ldk, 0, klast, g, c16);
   }
   uint32_t mw[MW];
   mask_row_use<MW>(mw, mraw, a, q);
   if (!a.tbits) {
     use = tiles_for_q<MW>(mw, q, a.Lq, a.Lk, nkt);
-#pragma unroll
-    for (int t = 0; t < NH; ++t)
-      if ((use >> t) & 1u) tile_load<NDT>(tk[t], kbase, a.ldk, 16 * t, klast, g, c16);
+    if (use & 1u) tile_load<NDT>(tk, kbase, a.ldk, 0, klast, g, c16);
   }
   ASTAMP(0);                           // Q / mask / K requests, mask arrival (visible tiles when not precomputed)
   uint32_t rowvis = 0;
@@ -584,18 +570,15 @@ __global__ __launch_bounds__(256, GCT_FWD_OCC) void attn_fwd_direct_kernel(const
   for (int t = 0; t < NT; ++t) sacc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
-    if (t >= NH && t % NH == 0) {      // next batch of K tiles, into the registers the previous one has left
-#pragma unroll
-      for (int t2 = t; t2 < t + NH && t2 < NT; ++t2)
-        if ((use >> t2) & 1u) tile_load<NDT>(tk[t2], kbase, a.ldk, 16 * t2, klast, g, c16);
-    }
+    if (t > 0 && ((use >> t) & 1u))    // next K tile, into the registers the previous one has left
+      tile_load<NDT>(tk, kbase, a.ldk, 16 * t, klast, g, c16);
     if ((use >> t) & 1u) {
       float4 ak[NDT];
       if (t & 1) {                     // alternate: tile t+1 is written while tile t is read
-        T1.put(tk[t], g, c16);
+        T1.put(tk, g, c16);
         T1.get(ak, g, c16);
       } else {
-        T0.put(tk[t], g, c16);
+        T0.put(tk, g, c16);
         T0.get(ak, g, c16);
       }
       sacc[t] = dot_frag<NDT>(ak, bq, sacc[t]);
@@ -605,10 +588,8 @@ __global__ __launch_bounds__(256, GCT_FWD_OCC) void attn_fwd_direct_kernel(const
   // V fragments, requested now and consumed after the softmax: lane (c16, g) holds V[16t + 4g + r][NDT c16 .. + NDT)
   // -- output tile dt of the P.V product covers the head columns {NDT m + dt}
   const char* vbase = reinterpret_cast<const char*>(a.v + kr0 * a.ldv + h * DK);                  // wave-uniform
-  VT av[NT][4];
-#pragma unroll
-  for (int t = 0; t < NH; ++t)
-    if ((use >> t) & 1u) tile_load<NDT>(av[t], vbase, a.ldv, 16 * t, klast, g, c16);
+  VT av[4];
+  if (use & 1u) tile_load<NDT>(av, vbase, a.ldv, 0, klast, g, c16);
   ASTAMP(3);                           // V requests
   // scale + mask + softmax (as fwd_unit)
   float m = -INFINITY;
@@ -670,16 +651,13 @@ __global__ __launch_bounds__(256, GCT_FWD_OCC) void attn_fwd_direct_kernel(const
   for (int dt = 0; dt < NDT; ++dt) oacc[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
-    if (t >= NH && t % NH == 0) {      // next batch of V tiles
-#pragma unroll
-      for (int t2 = t; t2 < t + NH && t2 < NT; ++t2)
-        if ((use >> t2) & 1u) tile_load<NDT>(av[t2], vbase, a.ldv, 16 * t2, klast, g, c16);
-    }
+    if (t > 0 && ((use >> t) & 1u))    // next V tile
+      tile_load<NDT>(av, vbase, a.ldv, 16 * t, klast, g, c16);
     if ((use >> t) & 1u) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
 #pragma unroll
-        for (int dt = 0; dt < NDT; ++dt) oacc[dt] = mfma16(vec_at<NDT>(av[t][r], dt), sacc[t][r], oacc[dt]);
+        for (int dt = 0; dt < NDT; ++dt) oacc[dt] = mfma16(vec_at<NDT>(av[r], dt), sacc[t][r], oacc[dt]);
       }
     }
   }
@@ -704,7 +682,7 @@ __global__ __launch_bounds__(256, GCT_FWD_OCC) void attn_fwd_direct_kernel(const
 // ----------------------------------------------------------------------------- backward
 template <int NDT, int NT>
 __global__ __launch_bounds__(ATT_THREADS, (NT <= 8 ? 3 : 2)) void attn_bwd_kernel(const AttnArgs a) {
-  constexpr int DK = 16 * NDT, SD = DK + 4, NW = ATT_THREADS / 64, MW = (NT + 1) / 2;
+  constexpr int DK = 16 * NDT, SD = DK + 4, NW = ATT_THREADS / 64, MW = mask_words(NT);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c16 = lane & 15;
   const int LQP = (a.Lq + 15) & ~15, LKP = (a.Lk + 15) & ~15, nkt = LKP / 16, nqt = LQP / 16;
@@ -721,9 +699,7 @@ __global__ __launch_bounds__(ATT_THREADS, (NT <= 8 ? 3 : 2)) void attn_bwd_kerne
   uint8_t* rowlive = rowok + LQP;                                 // [LQP] dO row has a non-zero element
   StageOff<DK, NT> kvo;                  // ldk == ldv (checked on the host)
   kvo.init(a.ldk, a.Lk, tid);
-  ASTAMP_DECL;
   for (int pair = blockIdx.x; pair < a.npairs; pair += (int)gridDim.x) {
-    ASTAMP(0);                           // loop seam
     const int b = pair / a.H, h = pair - b * a.H;
     const int64_t lrow0 = ((int64_t)b * a.H + h) * a.Lq;
     const int Lq_e = a.nlive ? a.nlive[b] : a.Lq;                               // query rows that exist in dout / dq
@@ -762,9 +738,7 @@ __global__ __launch_bounds__(ATT_THREADS, (NT <= 8 ? 3 : 2)) void attn_bwd_kerne
       sk.store(R0, Lk_in, LKP, tid);
       sv.store(R1, Lk_in, LKP, tid);
     }
-    ASTAMP(1);                           // loads issued, mask rows, wait for K / V, LDS stores
     __syncthreads();
-    ASTAMP(2);                           // barrier 1
     float4 bk[NDT], bv[NDT];
     bool tile_live = false;
     for (int u = wave; u < nqt; u += NW) {
@@ -873,7 +847,6 @@ __global__ __launch_bounds__(ATT_THREADS, (NT <= 8 ? 3 : 2)) void attn_bwd_kerne
               make_float4(qacc[dt][0] * a.scale, qacc[dt][1] * a.scale, qacc[dt][2] * a.scale, qacc[dt][3] * a.scale);
       }
     }
-    ASTAMP(3);                           // phase A
     constexpr bool FRAG_STAGE = NT <= NW;   // one query tile and one key tile per wave: stage through registers
     if (FRAG_STAGE) {
       // this wave's key tile of phase B: K / V rows are still in LDS
@@ -881,7 +854,6 @@ __global__ __launch_bounds__(ATT_THREADS, (NT <= 8 ? 3 : 2)) void attn_bwd_kerne
       row_frag<NDT>(bv, R1, 16 * wave + c16, g);
     }
     __syncthreads();      // K, V no longer needed; del_s / lse_s / rowlive / keep bits complete
-    ASTAMP(4);                           // own K / V rows from LDS + barrier 2
     // ---------------------------------------------------------------- phase B: Q, dO in LDS -> dK, dV
     if (FRAG_STAGE) {
       // Q and dO cross HBM once: every wave still holds the rows of its query tile as fragments, in exactly the
@@ -907,9 +879,7 @@ __global__ __launch_bounds__(ATT_THREADS, (NT <= 8 ? 3 : 2)) void attn_bwd_kerne
       sq.store(R0, Lq_e, LQP, tid);
       sd.store(R1, Lq_e, LQP, tid);
     }
-    ASTAMP(5);                           // Q / dO fragments -> LDS
     __syncthreads();
-    ASTAMP(6);                           // barrier 3
     for (int t = wave; t < nkt; t += NW) {
       const int k = 16 * t + c16;
       if (16 * t >= Lk_e) continue;        // compact self-attention: dead keys have no row (and no gradient)
@@ -980,10 +950,8 @@ __global__ __launch_bounds__(ATT_THREADS, (NT <= 8 ? 3 : 2)) void attn_bwd_kerne
         }
       }
     }
-    ASTAMP(7);                           // phase B
     __syncthreads();      // before the next pair's staging overwrites the region
   }
-  ASTAMP_OUT;
 }
 
 // ------------------------------------------------------------------------------ backward, direct
@@ -999,7 +967,7 @@ struct DqBuf {                         // one key tile's operands of the dQ kern
 
 template <int NDT, int NT>
 __global__ __launch_bounds__(256, 4) void attn_bwd_dq_kernel(const AttnArgs a) {
-  constexpr int DK = 16 * NDT, MW = (NT + 1) / 2;
+  constexpr int DK = 16 * NDT, MW = mask_words(NT);
   const int lane = threadIdx.x & 63, g = lane >> 4, c16 = lane & 15;
   const int nqt = (a.Lq + 15) >> 4, nkt = (a.Lk + 15) >> 4, LQP = 16 * nqt;
   const int item = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
@@ -1168,7 +1136,7 @@ struct DkvBuf {                        // one query tile's operands of the dK / 
 
 template <int NDT, int NT>
 __global__ __launch_bounds__(256, 4) void attn_bwd_dkv_kernel(const AttnArgs a) {
-  constexpr int DK = 16 * NDT, MW = (NT + 1) / 2;
+  constexpr int DK = 16 * NDT, MW = mask_words(NT);
   const int lane = threadIdx.x & 63, g = lane >> 4, c16 = lane & 15;
   const int nqt = (a.Lq + 15) >> 4, nkt = (a.Lk + 15) >> 4, LQP = 16 * nqt;
   const int item = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
@@ -1440,46 +1408,95 @@ int check_common(const char* who, const float* q, int64_t ldq, const float* k, i
   return GCT_OK;
 }
 
-template <int NDT, int NT>
-int launch_fwd(const AttnArgs& a, size_t lds, hipStream_t st) {
-  static const bool lds_kernel = getenv("GCT_ATTN_FWD_LDS") != nullptr;     // A/B switch for benchmarks
-  if constexpr (NT <= 6) {
-    if (!lds_kernel) {
-      const int64_t items = (int64_t)a.npairs * ((a.Lq + 15) / 16);
-      hipLaunchKernelGGL((attn_fwd_direct_kernel<NDT, NT>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, a);
-      return GCT_OK;
-    }
-  }
+// ---- the route of one attention call: plan_attn_fwd / plan_attn_bwd decide, launch() executes
+struct AttnRoute {
+  enum Kind {
+    DIRECT,  // L_k <= GCT_ATTN_DIRECT_MAX_KEYS: the barrier-free kernels <NDT, DIRECT_NT>, `grid` workgroups of 4 waves
+             // (backward: dQ over the query tiles, then `grid_kv` workgroups for dK / dV over the key tiles)
+    LDS8,    // the LDS kernel <NDT, 8> (L <= 128): `grid` persistent workgroups of ATT_THREADS with `lds` bytes
+    LDS13,   // the LDS kernel <NDT, 13> (L <= L_MAX)
+  } kind;
+  int64_t grid, grid_kv;
+  size_t lds;
+};
+
+// dynamic LDS of the LDS kernels: K, V [LKP][dk + 4] (forward); two [LMX][dk + 4] regions, lse / delta [LQP], mask
+// and keep words [LQP][MW], two row flags [LQP] (backward: the layout at the top of attn_bwd_kernel)
+constexpr size_t fwd_lds_bytes(int LKP, int dk) { return (size_t)(2 * LKP) * (dk + 4) * 4; }
+constexpr size_t bwd_lds_bytes(int LQP, int LMX, int dk, int MW) {
+  return (size_t)(2 * LMX) * (dk + 4) * 4 + (size_t)LQP * 8 + (size_t)LQP * MW * 8 + (size_t)LQP * 2;
+}
+static_assert(fwd_lds_bytes(L_MAX, 64) <= 160 * 1024 && bwd_lds_bytes(L_MAX, L_MAX, 64, mask_words(13)) <= 160 * 1024,
+              "every admitted shape fits the 160 KB of LDS a workgroup can opt in to");
+
+// Pure: no launches, no environment.  cus = compute units of the device (the persistent grids of the LDS kernels).
+AttnRoute plan_attn_fwd(int Lq, int Lk, int dk, int64_t npairs, int cus) {
+  if (Lk <= GCT_ATTN_DIRECT_MAX_KEYS)                       // one wave per (pair, query tile)
+    return {AttnRoute::DIRECT, (npairs * ((Lq + 15) / 16) + 3) / 4, 0, 0};
   // persistent workgroups: as many as are resident together (2 per CU: 6 waves at <= 168 VGPRs)
-  const int per_cu = NT > 8 ? 1 : 2;
-  const int64_t want = (int64_t)num_cus() * per_cu;
-  const unsigned grid = (unsigned)(a.npairs < want ? a.npairs : want);
-  if constexpr (NT > 8) {
-    int rc = ensure_lds(attn_fwd_kernel<NDT, NT, false, 2>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((attn_fwd_kernel<NDT, NT, false, 2>), dim3(grid), dim3(ATT_THREADS), lds, st, a);
-  } else {
-    int rc = ensure_lds(attn_fwd_kernel<NDT, NT, true, 3>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((attn_fwd_kernel<NDT, NT, true, 3>), dim3(grid), dim3(ATT_THREADS), lds, st, a);
-  }
-  return GCT_OK;
+  const int LKP = (Lk + 15) & ~15;
+  const bool nt8 = LKP <= 8 * 16;
+  const int64_t want = (int64_t)cus * (nt8 ? 2 : 1);
+  return {nt8 ? AttnRoute::LDS8 : AttnRoute::LDS13, npairs < want ? npairs : want, 0, fwd_lds_bytes(LKP, dk)};
 }
-template <int NDT, int NT>
-int launch_bwd(const AttnArgs& a, size_t lds, unsigned grid, hipStream_t st) {
-  int rc = ensure_lds(attn_bwd_kernel<NDT, NT>, lds);
+
+AttnRoute plan_attn_bwd(int Lq, int Lk, int dk, int64_t npairs, int cus) {
+  const int LQP = (Lq + 15) & ~15, LKP = (Lk + 15) & ~15;
+  if (Lk <= GCT_ATTN_DIRECT_MAX_KEYS)                       // one wave per (pair, query tile), then per (pair, key tile)
+    return {AttnRoute::DIRECT, (npairs * (LQP / 16) + 3) / 4, (npairs * (LKP / 16) + 3) / 4, 0};
+  const int LMX = LQP > LKP ? LQP : LKP;
+  const bool nt8 = LMX <= 8 * 16;
+  const size_t lds = bwd_lds_bytes(LQP, LMX, dk, mask_words(nt8 ? 8 : 13));
+  const int per_cu = lds <= 50 * 1024 ? 3 : lds <= 76 * 1024 ? 2 : 1;
+  const int64_t want = (int64_t)cus * per_cu * 2;           // a few pairs per workgroup keep the tail short
+  return {nt8 ? AttnRoute::LDS8 : AttnRoute::LDS13, npairs < want ? npairs : want, 0, lds};
+}
+
+// Workspace of the direct backward (byte offsets): per (pair, padded query row) a float4 {lse, delta, masked score,
+// dO row live} and the row's dropout keep words, then per (pair, query tile) one word of visited key tiles
+struct BwdWs {
+  int64_t keep, use, bytes;
+};
+BwdWs bwd_ws_layout(int B, int H, int Lq) {
+  const int64_t LQP = (Lq + 15) & ~15, rows = (int64_t)B * H * LQP;
+  const int64_t keep = rows * 16, use = keep + rows * mask_words(DIRECT_NT) * 4;
+  return {keep, use, use + (((int64_t)B * H * (LQP / 16) * 4 + 15) & ~(int64_t)15)};
+}
+
+template <typename K>
+int launch_lds(K kernel, const AttnRoute& r, const AttnArgs& a, hipStream_t st) {
+  int rc = ensure_lds(kernel, r.lds);
   if (rc) return rc;
-  hipLaunchKernelGGL((attn_bwd_kernel<NDT, NT>), dim3(grid), dim3(ATT_THREADS), lds, st, a);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)r.grid), dim3(ATT_THREADS), r.lds, st, a);
   return GCT_OK;
 }
-template <int NT>
-int launch_fwd_dk(int dk, const AttnArgs& a, size_t lds, hipStream_t st) {
-  return dk == 64 ? launch_fwd<4, NT>(a, lds, st) : dk == 32 ? launch_fwd<2, NT>(a, lds, st) : launch_fwd<1, NT>(a, lds, st);
+
+template <bool BWD, int NDT>
+int launch_route(const AttnRoute& r, const AttnArgs& a, hipStream_t st) {
+  switch (r.kind) {
+    case AttnRoute::DIRECT:
+      if constexpr (BWD) {
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<NDT, DIRECT_NT>), dim3((unsigned)r.grid), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<NDT, DIRECT_NT>), dim3((unsigned)r.grid_kv), dim3(256), 0, st, a);
+      } else {
+        hipLaunchKernelGGL((attn_fwd_direct_kernel<NDT, DIRECT_NT>), dim3((unsigned)r.grid), dim3(256), 0, st, a);
+      }
+      return GCT_OK;
+    case AttnRoute::LDS8:
+      return BWD ? launch_lds(attn_bwd_kernel<NDT, 8>, r, a, st) : launch_lds(attn_fwd_kernel<NDT, 8>, r, a, st);
+    default:
+      return BWD ? launch_lds(attn_bwd_kernel<NDT, 13>, r, a, st) : launch_lds(attn_fwd_kernel<NDT, 13>, r, a, st);
+  }
 }
-template <int NT>
-int launch_bwd_dk(int dk, const AttnArgs& a, size_t lds, unsigned grid, hipStream_t st) {
-  return dk == 64 ? launch_bwd<4, NT>(a, lds, grid, st) : dk == 32 ? launch_bwd<2, NT>(a, lds, grid, st)
-                                                                   : launch_bwd<1, NT>(a, lds, grid, st);
+
+// the one switch over the head dim (check_common admits 16 / 32 / 64)
+template <bool BWD>
+int launch(int dk, const AttnRoute& r, const AttnArgs& a, hipStream_t st) {
+  switch (dk) {
+    case 64: return launch_route<BWD, 4>(r, a, st);
+    case 32: return launch_route<BWD, 2>(r, a, st);
+    default: return launch_route<BWD, 1>(r, a, st);
+  }
 }
 
 }  // namespace
@@ -1537,29 +1554,22 @@ extern "C" int gct_attn_fwd(const float* q, int64_t ldq, const float* k, int64_t
   GCT_CHECK_ARG((kstart == nullptr) == (klen == nullptr), "attn_fwd: kstart / klen go together");
   a.kstart = kstart; a.klen = klen;
   GCT_CHECK_ARG((qstart == nullptr) == (qlen == nullptr), "attn_fwd: qstart / qlen go together");
-  GCT_CHECK_ARG(!qstart || (Lk <= 96 && !probs && getenv("GCT_ATTN_FWD_LDS") == nullptr),
-                "attn_fwd: compact query rows need the direct kernel (Lk <= 96) and no probs output");
+  GCT_CHECK_ARG(!qstart || (Lk <= GCT_ATTN_DIRECT_MAX_KEYS && !probs),
+                "attn_fwd: compact query rows need the direct kernel (Lk <= %d) and no probs output",
+                GCT_ATTN_DIRECT_MAX_KEYS);
   a.cstart = qstart; a.nlive = qlen; a.qo_compact = qstart ? 1 : 0;
   a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.npairs = B * H; a.scale = scale;
   a.thr = gct_drop_threshold(p); a.keep_scale = 1.0f / (1.0f - p); a.rng = gct_rng_make(seed, site);
-  const int LKP = (Lk + 15) & ~15, SD = dk + 4;
-  const int nt = LKP / 16;                      // query tiles beyond the wave count are looped
-  const size_t lds = (size_t)(2 * LKP) * SD * 4;
-  GCT_CHECK_ARG(lds <= 160 * 1024, "attn_fwd: needs %zu B of LDS", lds);
-  hipStream_t st = (hipStream_t)stream;
-  rc = nt <= 6 ? launch_fwd_dk<6>(dk, a, lds, st) : nt <= 8 ? launch_fwd_dk<8>(dk, a, lds, st)
-                                                            : launch_fwd_dk<13>(dk, a, lds, st);
+  rc = launch<false>(dk, plan_attn_fwd(Lq, Lk, dk, a.npairs, num_cus()), a, (hipStream_t)stream);
   if (rc) return rc;
   GCT_LAUNCH_CHECK("attn_fwd");
   return GCT_OK;
 }
 
-// workspace of the direct backward kernels (L_k <= 96): per (pair, padded query row) a float4 record and 3 keep words,
-// per (pair, query tile) one word; without it (or beyond 96 keys) gct_attn_bwd runs the LDS kernel
+// the workspace the direct backward needs (bwd_ws_layout); 0 beyond GCT_ATTN_DIRECT_MAX_KEYS (the LDS kernel needs none)
 extern "C" int64_t gct_attn_bwd_ws_bytes(int B, int H, int Lq, int Lk) {
-  if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || Lk > 96) return 0;
-  const int64_t LQP = (Lq + 15) & ~15, rows = (int64_t)B * H * LQP;
-  return rows * 16 + rows * 3 * 4 + (((int64_t)B * H * (LQP / 16) * 4 + 15) & ~(int64_t)15);
+  if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || Lk > GCT_ATTN_DIRECT_MAX_KEYS) return 0;
+  return bwd_ws_layout(B, H, Lq).bytes;
 }
 
 extern "C" int gct_attn_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk,
@@ -1601,46 +1611,23 @@ extern "C" int gct_attn_bwd(const float* q, int64_t ldq, const float* k, int64_t
   GCT_CHECK_ARG((kstart == nullptr) == (klen == nullptr) && !(kstart && kv_compact),
                 "attn_bwd: kstart / klen go together and exclude kv_compact");
   a.kstart = kstart; a.klen = klen;
+  GCT_CHECK_ARG(!qo_compact || Lk <= GCT_ATTN_DIRECT_MAX_KEYS,
+                "attn_bwd: compact q / o rows need the direct kernels (Lk <= %d)", GCT_ATTN_DIRECT_MAX_KEYS);
+  const int64_t ws_need = gct_attn_bwd_ws_bytes(B, H, Lq, Lk);
+  GCT_CHECK_ARG(ws_need == 0 || (ws && gct_aligned16(ws) && ws_bytes >= ws_need),
+                "attn_bwd: Lk <= %d needs a 16-B aligned workspace of %lld B (gct_attn_bwd_ws_bytes); got %lld B at %p",
+                GCT_ATTN_DIRECT_MAX_KEYS, (long long)ws_need, (long long)ws_bytes, ws);
   a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.npairs = B * H; a.scale = scale;
   a.thr = gct_drop_threshold(p); a.keep_scale = 1.0f / (1.0f - p); a.rng = gct_rng_make(seed, site);
-  const int LQP = (Lq + 15) & ~15, LKP = (Lk + 15) & ~15, SD = dk + 4;
-  const int LMX = LQP > LKP ? LQP : LKP, nt = LMX / 16;
-  const int MW = nt <= 6 ? 3 : nt <= 8 ? 4 : 7;
-  hipStream_t st = (hipStream_t)stream;
-  static const bool lds_kernel = getenv("GCT_ATTN_BWD_LDS") != nullptr;       // A/B switch for benchmarks
-  if (LKP <= 96 && ws && !lds_kernel && gct_aligned16(ws) && ws_bytes >= gct_attn_bwd_ws_bytes(B, H, Lq, Lk)) {
-    // direct kernels: one wave per (pair, query tile), then one wave per (pair, key tile)
-    const int64_t rows = (int64_t)a.npairs * LQP;
+  const AttnRoute r = plan_attn_bwd(Lq, Lk, dk, a.npairs, num_cus());
+  GCT_CHECK_ARG(r.grid <= INT32_MAX && r.grid_kv <= INT32_MAX, "attn_bwd: grid too large");
+  if (r.kind == AttnRoute::DIRECT) {
+    const BwdWs w = bwd_ws_layout(B, H, Lq);
     a.ws_meta = reinterpret_cast<float4*>(ws);
-    a.ws_keep = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ws) + rows * 16);
-    a.ws_use = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ws) + rows * 16 + rows * 3 * 4);
-    const int64_t items_q = (int64_t)a.npairs * (LQP / 16), items_k = (int64_t)a.npairs * (LKP / 16);
-    GCT_CHECK_ARG((items_q + 3) / 4 <= INT32_MAX && (items_k + 3) / 4 <= INT32_MAX, "attn_bwd: grid too large");
-    const dim3 gq((unsigned)((items_q + 3) / 4)), gk((unsigned)((items_k + 3) / 4));
-    if (dk == 64) {
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<4, 6>), gq, dim3(256), 0, st, a);
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<4, 6>), gk, dim3(256), 0, st, a);
-    } else if (dk == 32) {
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<2, 6>), gq, dim3(256), 0, st, a);
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<2, 6>), gk, dim3(256), 0, st, a);
-    } else {
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<1, 6>), gq, dim3(256), 0, st, a);
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<1, 6>), gk, dim3(256), 0, st, a);
-    }
-    GCT_LAUNCH_CHECK("attn_bwd (direct)");
-    return GCT_OK;
+    a.ws_keep = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + w.keep);
+    a.ws_use = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + w.use);
   }
-  if (qo_compact) {
-    gct_set_error("attn_bwd: compact q / o rows need the direct kernels (Lk <= 96 and a workspace)");
-    return GCT_ERR_ARG;
-  }
-  const size_t lds = (size_t)(2 * LMX) * SD * 4 + (size_t)LQP * 8 + (size_t)LQP * MW * 8 + (size_t)LQP * 2;
-  GCT_CHECK_ARG(lds <= 160 * 1024, "attn_bwd: needs %zu B of LDS", lds);
-  const int per_cu = lds <= 50 * 1024 ? 3 : lds <= 76 * 1024 ? 2 : 1;
-  const int64_t want = (int64_t)num_cus() * per_cu * 2;            // a few pairs per workgroup keep the tail short
-  const unsigned grid = (unsigned)(a.npairs < want ? a.npairs : want);
-  rc = nt <= 6 ? launch_bwd_dk<6>(dk, a, lds, grid, st) : nt <= 8 ? launch_bwd_dk<8>(dk, a, lds, grid, st)
-                                                                  : launch_bwd_dk<13>(dk, a, lds, grid, st);
+  rc = launch<true>(dk, r, a, (hipStream_t)stream);
   if (rc) return rc;
   GCT_LAUNCH_CHECK("attn_bwd");
   return GCT_OK;

@@ -109,8 +109,8 @@ class RowPlan:
             else:
                 dk = ops.KeyRows(sm, B, Le)
         lr = None
-        if (COMPACT_FWD and loss_rows is not None and trg_mask_u8 is not None and T <= 96 and Le + nc_lat <= 96
-                and n_layers_dec > 0):
+        if (COMPACT_FWD and loss_rows is not None and trg_mask_u8 is not None and T <= ops.ATTN_DIRECT_MAX_KEYS
+                and Le + nc_lat <= ops.ATTN_DIRECT_MAX_KEYS and n_layers_dec > 0):
             lr = ops.LiveRows.from_rows(loss_rows.reshape(B, T), B, T, trg_mask_u8)
         return _PendingPlan(ek, dk, lr, ops.PendingReadBack(ek, dk, lr),   # ONE read-back for all three
                             B * Le, B * (Le + nc_lat), B * T)
@@ -530,8 +530,8 @@ def decoder_trunk_fwd(dec, run: Run, trg, z, src_mask_u8, trg_mask_u8, dconds, w
     #         projections are never used and their dK / dV are zero, so the six K|V GEMMs, their weight gradients and
     #         the gradient w.r.t. the memory run on the visible rows only (quad-compacted, ops.KeyRows).
     live, keys = None, None
-    fwd_ok = (not c2d and not want_probs and T <= 96 and Lk <= 96 and len(dec.layers) > 0 and not capturing
-              and trg_mask_u8 is not None)
+    fwd_ok = (not c2d and not want_probs and T <= ops.ATTN_DIRECT_MAX_KEYS and Lk <= ops.ATTN_DIRECT_MAX_KEYS
+              and len(dec.layers) > 0 and not capturing and trg_mask_u8 is not None)
     if plan is not None:
         live = plan.live if fwd_ok else None
         keys = plan.dec_keys if (src_mask_u8 is not None and src_mask_u8.numel() == B * Lk) else None

@@ -672,6 +672,11 @@ def dropout_bwd(dout2d, p, seed, site, out=None, live=None):
 
 
 # ------------------------------------------------------------------------------ attention
+# GCT_ATTN_DIRECT_MAX_KEYS of include/gctplus_hip.h: up to this many keys the barrier-free kernels run (the backward
+# then needs its workspace); the forward over compact query rows (`live`) exists only there
+ATTN_DIRECT_MAX_KEYS = 96
+
+
 class MaskBits:
     """An attention mask packed for the kernels (gct_attn_mask_pack): one bit per key, 8 words per query row.
     Built once per trunk call from the reference's bool / int64 mask and shared by every layer, head and the

@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 14
+#define GCT_ABI_VERSION 15
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -271,7 +271,9 @@ int gct_dropout_bwd(const float* dout, float* dy, int64_t rows, int cols, float 
  * o: [B][Lq][H*dk] (heads merged, ready for the out projection); lse: [B][H][Lq].
  * probs (nullable): pre-dropout probabilities [B][H][Lq][Lk] (get_attn path).
  * dk in {16, 32, 64}; Lq, Lk <= 208 (the reference's positional table ends at 200: Model/modules.py:117; + 3
- * condition tokens).  Lk <= 96 runs the barrier-free kernels (one wave per query / key tile), longer rows the LDS kernels. */
+ * condition tokens).  Lk <= GCT_ATTN_DIRECT_MAX_KEYS runs the barrier-free kernels (one wave per query / key tile),
+ * longer rows the LDS kernels. */
+#define GCT_ATTN_DIRECT_MAX_KEYS 96
 /* mask: uint8, element (b,q,k) at mask[b*mask_sb + q*mask_sq + k] (0 = masked); mask_sq == 0: key-padding mask
  * [B][Lk] -> bits [B][8]; else bits [B][Lq][8]. */
 /* tiles (nullable): one word per (batch, 16-row query tile) -- [B][1] for a key-padding mask, [B][ceil(Lq/16)]
@@ -295,7 +297,7 @@ int gct_attn_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const
  * the rows of sample b start at kstart[b] and there are klen[b] of them (keys klen[b]..Lk-1 are masked by mbits).
  * qstart / qlen (nullable, together; gct_live_rows): q and o hold only the first qlen[b] query rows of sample b, at rows
  * qstart[b].. (the decoder forward over the rows that reach the loss); lse keeps its [B][H][Lq] layout, entries of rows
- * that do not exist are not written.  Needs the direct kernels (Lk <= 96, probs == NULL). */
+ * that do not exist are not written.  Needs the direct kernels (Lk <= GCT_ATTN_DIRECT_MAX_KEYS, probs == NULL). */
 /* dq/dk/dv written (overwrite) with the same layout as q/k/v.
  * cstart / nlive (nullable, together): dout and dq are quad-compacted (gct_live_rows): the rows of sample b start at
  * cstart[b] and only its first nlive[b] query rows exist; kv_compact bit 0 (self-attention, Lq == Lk): dk / dv live
@@ -311,9 +313,10 @@ int gct_attn_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const
                  const int32_t* kstart, const int32_t* klen, const uint32_t* tbits, int64_t tb_sb, int64_t tb_su,
                  void* ws, int64_t ws_bytes, void* stream);
 /* kstart / klen as in gct_attn_fwd: k, v AND dk, dv hold the visible keys only (excludes kv_compact).
- * ws (nullable, caller-owned, 16-B aligned, >= gct_attn_bwd_ws_bytes): scratch of the two-launch backward used for
- * Lk <= 96 (one wave per query tile -> dq, then one wave per key tile -> dk, dv; no LDS); without it, or beyond 96
- * keys, the single-launch LDS kernel runs.  Same results either way (same arithmetic, same dropout bits). */
+ * ws / ws_bytes: caller-owned scratch (16-B aligned, ws_bytes >= gct_attn_bwd_ws_bytes) of the two-launch backward that
+ * runs for Lk <= GCT_ATTN_DIRECT_MAX_KEYS (one wave per query tile -> dq, then one wave per key tile -> dk, dv; no LDS).
+ * Required whenever gct_attn_bwd_ws_bytes > 0: a null, short or misaligned ws is GCT_ERR_ARG.  Longer rows run the
+ * single-launch LDS kernel and need none (gct_attn_bwd_ws_bytes == 0, ws may be NULL). */
 int64_t gct_attn_bwd_ws_bytes(int B, int H, int Lq, int Lk);
 
 /* ------------------------------------------------- K6: reparameterisation + KL */

@@ -33,6 +33,23 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(dl, name), name
 
 
+def test_attention_direct_key_limit_has_one_owner():
+    """GCT_ATTN_DIRECT_MAX_KEYS (header) is ops.ATTN_DIRECT_MAX_KEYS, and the direct backward's workspace exists up to
+    it only: positive at the limit (per padded query row a 16-B record and limit / 32 keep words, per query tile one
+    word rounded up to 16 B), 0 one key above it (the LDS kernel needs none)."""
+    from gct_plus_amd import ops
+    hdr = open(os.path.join(ROOT, "include", "gctplus_hip.h")).read()
+    limit = int(re.search(r"#define GCT_ATTN_DIRECT_MAX_KEYS (\d+)", hdr).group(1))
+    assert limit == ops.ATTN_DIRECT_MAX_KEYS
+    lib = _lib.load()
+    B, H, Lq = 3, 8, 100
+    rows, tiles = B * H * 112, B * H * 7
+    assert lib.gct_attn_bwd_ws_bytes(B, H, Lq, limit) == rows * (16 + 4 * limit // 32) + (tiles * 4 + 15) // 16 * 16
+    assert lib.gct_attn_bwd_ws_bytes(B, H, Lq, 1) == lib.gct_attn_bwd_ws_bytes(B, H, Lq, limit)
+    assert lib.gct_attn_bwd_ws_bytes(B, H, Lq, limit + 1) == 0
+    assert lib.gct_attn_bwd_ws_bytes(0, H, Lq, limit) == 0
+
+
 def test_ops_refuse_cpu_tensors():
     from gct_plus_amd import ops
     with pytest.raises(_lib.GctError):

@@ -236,6 +236,43 @@ def test_attention_many_pairs_per_workgroup(ops):
     close(un(dqkv[:, 2 * d:]), vd.grad, 2e-5, 1e-4, "dv (many pairs)")
 
 
+def test_attention_bwd_requires_its_workspace(ops):
+    """Up to ops.ATTN_DIRECT_MAX_KEYS keys the backward runs the direct kernels, whose workspace is required: a null,
+    short or misaligned one is an argument error naming the size, before anything is launched (every other buffer is
+    real and correctly sized, and a short / misaligned ws still lies inside a large enough allocation).  With the
+    workspace, the raw entry point matches ops.attn_bwd bit for bit."""
+    from gct_plus_amd import _lib
+    lib = _lib.load()
+    B, H, L, dk = 2, 4, ops.ATTN_DIRECT_MAX_KEYS, 16
+    d = H * dk
+    qkv = rnd(B * L, 3 * d, seed=21).to(DEV)
+    q, k, v = qkv, qkv[:, d:], qkv[:, 2 * d:]
+    o, lse, _ = ops.attn_fwd(q, k, v, 3 * d, 3 * d, 3 * d, None, B, H, L, L, dk, 0.1, 3, 4)
+    do = rnd(B * L, d, seed=22).to(DEV)
+    need = lib.gct_attn_bwd_ws_bytes(B, H, L, L)
+    assert need > 0
+    buf = torch.zeros(need + 16, dtype=torch.uint8, device=DEV)
+    dqkv = torch.zeros(B * L, 3 * d, device=DEV)
+
+    def call(ws, nbytes):
+        p = lambda t: t.data_ptr()                                                                   # noqa: E731
+        return lib.gct_attn_bwd(p(q), 3 * d, p(k), 3 * d, p(v), 3 * d, None, 0, 0, p(o), p(do), d, p(lse),
+                                p(dqkv), 3 * d, p(dqkv[:, d:]), 3 * d, p(dqkv[:, 2 * d:]), 3 * d, B, H, L, L, dk,
+                                1.0 / math.sqrt(dk), 0.1, 3, 4, None, None, 0, None, None, None, 0, 0, ws, nbytes,
+                                torch.cuda.current_stream().cuda_stream)
+
+    for ws, nbytes in [(None, 0), (None, need), (buf.data_ptr(), need - 16), (buf.data_ptr() + 8, need)]:
+        with pytest.raises(_lib.GctError, match=f"workspace of {need} B"):
+            _lib.check(call(ws, nbytes), "gct_attn_bwd")
+    torch.cuda.synchronize()
+    assert not dqkv.any(), "a refused call wrote its outputs"
+    _lib.check(call(buf.data_ptr(), need), "gct_attn_bwd")
+    ref = torch.empty_like(dqkv)
+    ops.attn_bwd(q, k, v, 3 * d, 3 * d, 3 * d, None, o, do, lse, ref, ref[:, d:], ref[:, 2 * d:], 3 * d, 3 * d, 3 * d,
+                 B, H, L, L, dk, 0.1, 3, 4)
+    assert torch.equal(dqkv, ref)
+
+
 @pytest.mark.parametrize("L", [48, 170])
 def test_attention_dropout(ops, L):
     """One-hot V blocks recover the dropped probabilities => the keep mask the FORWARD used (64 keys per run, same

@@ -1,8 +1,8 @@
-"""Randomised parity sweep of the attention kernels against fp64 (dropout 0) and, with --dump / --compare, between the
-two kernel families with dropout on (same Philox bits => same results to fp32 rounding):
+"""Randomised parity sweep of the attention kernels against fp64 (dropout 0) and, with --dump / --compare, between two
+builds of the library with dropout on (same Philox bits => same results to fp32 rounding):
   python tools/attn_fuzz.py --cases 80
-  GCT_ATTN_FWD_LDS=1 GCT_ATTN_BWD_LDS=1 python tools/attn_fuzz.py --cases 40 --dropout 0.1 --dump /tmp/lds.pt
-  python tools/attn_fuzz.py --cases 40 --dropout 0.1 --compare /tmp/lds.pt"""
+  python tools/attn_fuzz.py --cases 40 --dropout 0.1 --dump /tmp/before.pt      # one build
+  python tools/attn_fuzz.py --cases 40 --dropout 0.1 --compare /tmp/before.pt   # the other"""
 import argparse, math, sys, torch
 sys.path.insert(0, ".")
 from gct_plus_amd import ops
