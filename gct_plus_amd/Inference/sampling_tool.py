@@ -8,7 +8,10 @@ Deliberate deviations, none in the arithmetic:
   * vocabularies are gct_plus_amd.data.Vocab objects (no torchtext Field);
   * `id_to_smi` appends each token once (the reference appends it twice, sampling_tool.py:55-63);
   * token lengths are drawn from the same histogram-with-jitter distribution as
-    Inference/toklen_sampling.py:19-36, with numpy's Generator instead of the global RNG.
+    Inference/toklen_sampling.py:19-36, with numpy's Generator instead of the global RNG;
+  * decode_algo="beam" (the reference's -decode_algo choice, whose Inference/generate_mols.py code does not run) is
+    beam search with frozen finished beams and a length-normalised final ranking (gct_plus_amd.decode): `decode`
+    returns the best beam, `decode_beams` all of them.
 """
 from __future__ import annotations
 
@@ -19,7 +22,7 @@ import torch
 
 from ..Model.modules import get_src_mask
 from ..data import Vocab, tokenize
-from ..decode import KVDecoder
+from ..decode import BEAM_ALPHA, KVDecoder, check_beam_size
 
 
 def sample_token_lengths(data: Sequence[int], size: int, rng: np.random.Generator) -> np.ndarray:
@@ -40,7 +43,11 @@ def sample_token_lengths(data: Sequence[int], size: int, rng: np.random.Generato
 class Sampling:
     def __init__(self, model, SRC: Vocab, TRG: Vocab, latent_dim: int, max_strlen: int = 80,
                  cond_dim: int = 0, decode_algo: str = "greedy", toklen_data: Optional[Sequence[int]] = None,
-                 scaler=None, device="cuda", seed: int = 0, use_graphs: bool = False):
+                 scaler=None, device="cuda", seed: int = 0, use_graphs: bool = False, beam_size: int = 4,
+                 beam_alpha: float = BEAM_ALPHA):
+        if decode_algo == "beam":
+            check_beam_size(beam_size, model.out.weight.shape[0])
+        self.beam_size, self.beam_alpha = beam_size, float(beam_alpha)
         self.model, self.SRC, self.TRG = model.eval(), SRC, TRG
         self.pad_id, self.sos_id, self.eos_id = SRC.stoi["<pad>"], TRG.stoi["<sos>"], TRG.stoi["<eos>"]
         self.sep_id = TRG.stoi.get("<sep>")
@@ -92,6 +99,9 @@ class Sampling:
     # ---- decode: KV-cached equivalent of Sampling.decode (sampling_tool.py:140-184) ----------
     @torch.no_grad()
     def decode(self, zs, ys, src_mask, dconds=None):
+        """ids [n, L] (prefix included); with decode_algo="beam" the best beam of each sample."""
+        if self.decode_algo == "beam":
+            return self.decode_beams(zs, ys, src_mask, dconds)[0][:, 0]
         self.seed += 1
         zs, ys, src_mask = zs.to(self.device), ys.to(self.device), src_mask.to(self.device)
         dconds = None if dconds is None else dconds.to(self.device)
@@ -100,6 +110,19 @@ class Sampling:
         self.kv.start(zs, src_mask, dconds, max_total_len=min(200 - self.kv.off, total))
         return self.kv.generate(ys, self.max_strlen, algo=self.decode_algo, seed=self.seed,
                                 use_graphs=self.use_graphs)
+
+    @torch.no_grad()
+    def decode_beams(self, zs, ys, src_mask, dconds=None, beam_size=None, alpha=None):
+        """Beam search: (ids [n, k, L], scores [n, k] sums of log-probabilities, lengths [n, k]), beams sorted by
+        score / length**alpha (KVDecoder.generate_beam).  beam_size / alpha default to the constructor's."""
+        k = self.beam_size if beam_size is None else beam_size
+        check_beam_size(k, self.model.out.weight.shape[0])
+        zs, ys, src_mask = zs.to(self.device), ys.to(self.device), src_mask.to(self.device)
+        dconds = None if dconds is None else dconds.to(self.device)
+        total = ys.size(1) + self.max_strlen
+        self.kv.start(zs, src_mask, dconds, max_total_len=min(200 - self.kv.off, total), beams=k)
+        return self.kv.generate_beam(ys, k, self.max_strlen, alpha=self.beam_alpha if alpha is None else alpha,
+                                     use_graphs=self.use_graphs)
 
     def _latent_setup(self, n, zs, toklen, extra=0):
         if zs is not None:

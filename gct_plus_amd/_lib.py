@@ -73,6 +73,9 @@ SIGNATURES = {
     "gct_decode_embed": (I32, [P, I64, P, I32, P, I32, P, P, I32, I32, F32, P]),
     "gct_decode_advance": (I32, [P, P]),
     "gct_select_token": (I32, [P, I32, P, I64, I32, P, I64, P, P, I32, I32, I64, I64, U64, P, I32, P, P]),
+    "gct_attn_decode_beam": (I32, [P, I64, P, P, I64, I64, P, I64, P, I64, I32, I32, I32, I32, F32, P, I32, P, P, I64,
+                                   P, I64, P]),
+    "gct_beam_select": (I32, [P, I32, I32, I32, P, P, P, P, P, I64, P, I64, I32, P, I64, I32, P, P, I64, I64, P]),
     "gct_smiles_tokenize": (I32, [C.c_char_p, I32, P, P, I32]),
     "gct_smiles_encode_batch": (I32, [P, I32, I32, P, I32, I64, I64, I64, I64, P, I64, P]),
     "gct_adam_step": (I32, [P, P, P, P, I64, F32, F32, F32, F32, I64, F32, P]),
@@ -88,7 +91,7 @@ SIGNATURES = {
     "gct_add": (I32, [P, P, P, I64, P]),
 }
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 _lib = None
 
 

@@ -3,8 +3,12 @@
 //   gct_attn_decode  : one query row per (sample, head) against cached keys/values
 //   gct_select_token : softmax over the vocabulary + greedy / multinomial choice, appends the
 //                      token, updates the key-valid flags and the per-sample finished mask
+//   gct_attn_decode_beam / gct_beam_select : the same two for beam search, with the self-attention caches
+//                      shared by ancestry through a per-row map (kv_src) instead of copied
 // Both are tiny and HBM/latency-bound; they exist so a whole decode step is a fixed kernel
 // chain with no host round trip (graph-capturable).
+#include <climits>
+
 #include "common.h"
 
 namespace {
@@ -13,14 +17,18 @@ namespace {
 // pos (nullable): DEVICE-side step counter -- the cache holds Lc = cache_off + *pos keys, and the step's own key /
 // value (knew / vnew, row b of a [n][ldn] step buffer) are the last key: they are appended to the caches here
 // (row Lc) and scored from registers, so ONE captured graph serves every step of the decode loop.
-template <int DK>
+// MAPPED (beam search, pos required): key / value j of row b and the valid flag masking it live in physical row
+// kv_src[b][j] (Lc_host = cache rows, the bound of every map entry's position); the step's own key still goes to row b.
+template <int DK, bool MAPPED>
 __global__ __launch_bounds__(256) void attn_decode_kernel(
     const float* __restrict__ q, int64_t ldq, float* __restrict__ k, float* __restrict__ v,
     int64_t kv_row, int64_t kv_batch, const uint8_t* __restrict__ valid, int64_t valid_sb,
     float* __restrict__ o, int64_t ldo, int n, int H, int Lc_host, float scale,
     const int32_t* __restrict__ pos, int cache_off, const float* __restrict__ knew,
-    const float* __restrict__ vnew, int64_t ldn, const int32_t* __restrict__ klen) {
+    const float* __restrict__ vnew, int64_t ldn, const int32_t* __restrict__ klen,
+    const int32_t* __restrict__ kv_src, int64_t ld_src) {
   __shared__ float sc[4][256];
+  __shared__ int32_t rs[4][256];     // MAPPED: physical row of key j
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t pair = (int64_t)blockIdx.x * 4 + wave;
   if (pair >= (int64_t)n * H) return;
@@ -38,6 +46,16 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
   constexpr int KPP = 64 / LPK;      // keys per pass
   const int sub = lane % LPK, kslot = lane / LPK;
   const float4 qv = *reinterpret_cast<const float4*>(qp + sub * 4);
+  if constexpr (MAPPED) {
+    if (Lold >= Lc_host) return;                  // no room for this step's key (the host sizes the caches)
+    const int32_t* sr = kv_src + (int64_t)b * ld_src;
+    for (int j = lane; j < Lold; j += 64) {
+      const int r = sr[j];
+      rs[wave][j] = r < 0 ? 0 : (r >= n ? n - 1 : r);
+    }
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_wave_barrier();
+  }
   float vlast = 0.f;
   if (pos) {
     // this step's key: score it from the step buffer and append key / value to the caches
@@ -64,14 +82,21 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
     const int j = j0 + kslot;
     float s = 0.f;
     if (j < Lold) {
-      const float4 kv4 = *reinterpret_cast<const float4*>(kp + (int64_t)j * kv_row + sub * 4);
+      const float* kj;
+      if constexpr (MAPPED) kj = k + (int64_t)rs[wave][j] * kv_batch + h * DK + (int64_t)j * kv_row;
+      else kj = kp + (int64_t)j * kv_row;
+      const float4 kv4 = *reinterpret_cast<const float4*>(kj + sub * 4);
       s = (qv.x * kv4.x + qv.y * kv4.y) + (qv.z * kv4.z + qv.w * kv4.w);
     }
 #pragma unroll
     for (int off = LPK / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
     if (j < Lold && sub == 0) {
       s *= scale;
-      if (vl && vl[j] == 0) s = -1e9f;            // masked_fill(mask == 0, -1e9)
+      if constexpr (MAPPED) {
+        if (valid && valid[(int64_t)rs[wave][j] * valid_sb + j] == 0) s = -1e9f;
+      } else {
+        if (vl && vl[j] == 0) s = -1e9f;            // masked_fill(mask == 0, -1e9)
+      }
       sc[wave][j] = s;
     }
   }
@@ -91,7 +116,13 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
   __builtin_amdgcn_wave_barrier();
   if (lane < DK) {
     float acc = 0.f;
-    for (int j = 0; j < Lold; ++j) acc = fmaf(sc[wave][j] * inv, vp[(int64_t)j * kv_row + lane], acc);
+    if constexpr (MAPPED) {
+      const float* vh = v + h * DK + lane;
+      for (int j = 0; j < Lold; ++j)
+        acc = fmaf(sc[wave][j] * inv, vh[(int64_t)rs[wave][j] * kv_batch + (int64_t)j * kv_row], acc);
+    } else {
+      for (int j = 0; j < Lold; ++j) acc = fmaf(sc[wave][j] * inv, vp[(int64_t)j * kv_row + lane], acc);
+    }
     if (pos) acc = fmaf(sc[wave][Lold] * inv, vlast, acc);
     o[(int64_t)b * ldo + h * DK + lane] = acc;
   }
@@ -289,6 +320,159 @@ __global__ __launch_bounds__(256) void select_token_kernel(const float* __restri
   }
 }
 
+// ---------------------------------------------------------------------------------------------- beam search
+// Candidate order of the selection: higher score first, then the lower flat index beam * V + token.
+__device__ __forceinline__ bool beam_better(float av, int ai, float bv, int bi) {
+  return av > bv || (av == bv && ai < bi);
+}
+
+// One thread's KM best candidates, sorted; the new one enters at the tail and bubbles up (constant indices: registers).
+template <int KM>
+__device__ __forceinline__ void beam_insert(float (&cv)[KM], int (&ci)[KM], float v, int i) {
+  if (!beam_better(v, i, cv[KM - 1], ci[KM - 1])) return;
+  cv[KM - 1] = v;
+  ci[KM - 1] = i;
+#pragma unroll
+  for (int t = KM - 1; t > 0; --t) {
+    if (beam_better(cv[t], ci[t], cv[t - 1], ci[t - 1])) {
+      const float tv = cv[t]; cv[t] = cv[t - 1]; cv[t - 1] = tv;
+      const int ti = ci[t]; ci[t] = ci[t - 1]; ci[t - 1] = ti;
+    }
+  }
+}
+
+// One workgroup per sample s, whose K beams are rows s*K .. s*K+K-1 (semantics: decode.py beam_step_reference).
+//   1. beam state and the group's kv_src rows -> LDS;
+//   2. per live beam (one wave each): m = max logit, ls = log sum exp(x - m); a candidate scores
+//      score_b + ((x - m) - ls); a finished beam offers only (score_b, token pad); beams at -inf offer nothing;
+//   3. each thread keeps its KM best candidates, then K rounds of a workgroup argmax pop the winners in order;
+//   4. child c of parent b: score, finished = fin_b || token == eos, length = len_b + !fin_b, the token at
+//      ys[row][p] / valid[row][valid_off + p], and the parent's kv_src row with entry valid_off + p = the child's row.
+// p = *pos_dev + 1 (device counter, as select_token_kernel): no host round trip, one captured graph for every step.
+template <int KM>
+__global__ __launch_bounds__(256) void beam_select_kernel(
+    const float* __restrict__ logits, int V, int K, float* __restrict__ scores, uint8_t* __restrict__ finished,
+    int32_t* __restrict__ lengths, int32_t* __restrict__ parent_out, int64_t* __restrict__ ys, int64_t ld_ys,
+    uint8_t* __restrict__ valid, int64_t valid_sb, int valid_off, int32_t* __restrict__ kv_src, int64_t ld_src, int T,
+    uint8_t* __restrict__ done, const int32_t* __restrict__ pos_dev, int64_t pad_id, int64_t eos_id) {
+  __shared__ float s_score[KM], s_m[KM], s_ls[KM], s_winv[KM], s_wv[2][4];
+  __shared__ int32_t s_len[KM], s_win[KM], s_par[KM], s_wi[2][4];
+  __shared__ uint8_t s_fin[KM], s_cfin[KM];
+  __shared__ int32_t s_map[KM][256];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int p = *pos_dev + 1;                               // index of the token chosen now
+  const int slot = valid_off + p;
+  if (p < 0 || slot >= T) return;                          // no room (the host sizes the caches)
+  const int64_t row0 = (int64_t)blockIdx.x * K;
+  if (tid < K) {
+    s_score[tid] = scores[row0 + tid];
+    s_fin[tid] = finished[row0 + tid];
+    s_len[tid] = lengths[row0 + tid];
+  }
+  for (int i = tid; i < K * T; i += 256) {
+    const int b = i / T, j = i - b * T;
+    s_map[b][j] = kv_src[(row0 + b) * ld_src + j];
+  }
+  __syncthreads();
+  for (int b = wave; b < K; b += 4) {                       // log-softmax statistics, one wave per live beam
+    if (s_fin[b] || s_score[b] == -INFINITY) continue;
+    const float* lr = logits + (row0 + b) * V;
+    float m = -INFINITY;
+    for (int c = lane; c < V; c += 64) m = fmaxf(m, lr[c]);
+    m = gct_wave_max(m);
+    float se = 0.f;
+    for (int c = lane; c < V; c += 64) se += expf(lr[c] - m);
+    se = gct_wave_sum(se);
+    if (lane == 0) {
+      s_m[b] = m;
+      s_ls[b] = logf(se);
+    }
+  }
+  __syncthreads();
+  float cv[KM];
+  int ci[KM];
+#pragma unroll
+  for (int t = 0; t < KM; ++t) {
+    cv[t] = -INFINITY;
+    ci[t] = INT_MAX;
+  }
+  for (int b = 0; b < K; ++b) {                             // ascending flat index per thread
+    const float sb = s_score[b];
+    if (sb == -INFINITY) continue;
+    if (s_fin[b]) {
+      if (tid == 0) beam_insert<KM>(cv, ci, sb, b * V + (int)pad_id);
+      continue;
+    }
+    const float m = s_m[b], ls = s_ls[b];
+    const float* lr = logits + (row0 + b) * V;
+    for (int c = tid; c < V; c += 256) beam_insert<KM>(cv, ci, sb + ((lr[c] - m) - ls), b * V + c);
+  }
+  for (int r = 0; r < K; ++r) {                             // K rounds: workgroup argmax of the threads' heads
+    float bv = cv[0];
+    int bi = ci[0];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float ov = __shfl_xor(bv, off, 64);
+      const int oi = __shfl_xor(bi, off, 64);
+      if (beam_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) {
+      s_wv[r & 1][wave] = bv;
+      s_wi[r & 1][wave] = bi;
+    }
+    __syncthreads();                                        // (double buffer: round r+1 writes the other slot)
+    float wv = s_wv[r & 1][0];
+    int wi = s_wi[r & 1][0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w)
+      if (beam_better(s_wv[r & 1][w], s_wi[r & 1][w], wv, wi)) { wv = s_wv[r & 1][w]; wi = s_wi[r & 1][w]; }
+    if (ci[0] == wi && wi != INT_MAX) {                     // the owner pops its head
+#pragma unroll
+      for (int t = 0; t < KM - 1; ++t) {
+        cv[t] = cv[t + 1];
+        ci[t] = ci[t + 1];
+      }
+      cv[KM - 1] = -INFINITY;
+      ci[KM - 1] = INT_MAX;
+    }
+    if (tid == 0) {
+      s_win[r] = wi;
+      s_winv[r] = wv;
+    }
+  }
+  __syncthreads();
+  if (tid < K) {
+    const int f = s_win[tid];
+    const int64_t row = row0 + tid;
+    int b, tok;
+    float sc;
+    if (f == INT_MAX) {                                     // fewer than K candidates (cannot happen with K <= V)
+      b = tid; tok = (int)pad_id; sc = -INFINITY;
+    } else {
+      b = f / V; tok = f - b * V; sc = s_winv[tid];
+    }
+    const bool fin = f == INT_MAX || s_fin[b] || tok == eos_id;
+    scores[row] = sc;
+    finished[row] = fin ? 1 : 0;
+    lengths[row] = s_len[b] + (s_fin[b] ? 0 : 1);
+    if (parent_out) parent_out[row] = b;
+    ys[row * ld_ys + p] = tok;
+    valid[row * valid_sb + slot] = tok != pad_id ? 1 : 0;
+    s_par[tid] = b;
+    s_cfin[tid] = fin ? 1 : 0;
+  }
+  __syncthreads();
+  for (int i = tid; i < K * T; i += 256) {                 // child row = parent's map row, plus its own new slot
+    const int c = i / T, j = i - c * T;
+    kv_src[(row0 + c) * ld_src + j] = j == slot ? (int32_t)(row0 + c) : s_map[s_par[c]][j];
+  }
+  if (tid == 0) {
+    uint8_t all = 1;
+    for (int c = 0; c < K; ++c) all &= s_cfin[c];
+    done[blockIdx.x] = all;
+  }
+}
+
 }  // namespace
 
 extern "C" int gct_attn_decode(const float* q, int64_t ldq, float* k, float* v,
@@ -309,9 +493,9 @@ extern "C" int gct_attn_decode(const float* q, int64_t ldq, float* k, float* v,
   const int64_t pairs = (int64_t)n * H;
   dim3 grid((unsigned)((pairs + 3) / 4)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (dk == 64) hipLaunchKernelGGL(attn_decode_kernel<64>, grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, klen);
-  else if (dk == 32) hipLaunchKernelGGL(attn_decode_kernel<32>, grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, klen);
-  else hipLaunchKernelGGL(attn_decode_kernel<16>, grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, klen);
+  if (dk == 64) hipLaunchKernelGGL((attn_decode_kernel<64, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, klen, nullptr, 0);
+  else if (dk == 32) hipLaunchKernelGGL((attn_decode_kernel<32, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, klen, nullptr, 0);
+  else hipLaunchKernelGGL((attn_decode_kernel<16, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, klen, nullptr, 0);
   GCT_LAUNCH_CHECK("attn_decode");
   return GCT_OK;
 }
@@ -376,5 +560,52 @@ extern "C" int gct_select_token(const float* logits, int V, int64_t* ys, int64_t
                      (hipStream_t)stream, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out,
                      n, mode, pad_id, eos_id, gct_rng_make(seed, 0xDEC0DEu), pos_dev, valid_off, seed_dev);
   GCT_LAUNCH_CHECK("select_token");
+  return GCT_OK;
+}
+
+extern "C" int gct_attn_decode_beam(const float* q, int64_t ldq, float* k, float* v, int64_t kv_row, int64_t kv_batch,
+                                    const uint8_t* valid, int64_t valid_sb, float* o, int64_t ldo, int n, int H, int T,
+                                    int dk, float scale, const int32_t* pos, int cache_off, const float* knew,
+                                    const float* vnew, int64_t ldn, const int32_t* kv_src, int64_t ld_src,
+                                    void* stream) {
+  GCT_CHECK_ARG(q && k && v && o && pos && kv_src && n >= 0 && H > 0 && T > 0 && T <= 256 && ld_src >= T &&
+                    cache_off >= 0,
+                "attn_decode_beam: bad args");
+  GCT_CHECK_ARG(knew && vnew && ldn % 4 == 0 && gct_aligned16(knew) && gct_aligned16(vnew),
+                "attn_decode_beam: needs this step's key / value rows");
+  GCT_CHECK_ARG(dk == 16 || dk == 32 || dk == 64, "attn_decode_beam: head dim %d unsupported", dk);
+  GCT_CHECK_ARG(ldq % 4 == 0 && kv_row % 4 == 0 && kv_batch % 4 == 0 && gct_aligned16(q) && gct_aligned16(k) &&
+                    gct_aligned16(v),
+                "attn_decode_beam: operands must be 16-B aligned");
+  if (n == 0) return GCT_OK;
+  const int64_t pairs = (int64_t)n * H;
+  dim3 grid((unsigned)((pairs + 3) / 4)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (dk == 64) hipLaunchKernelGGL((attn_decode_kernel<64, true>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, T, scale, pos, cache_off, knew, vnew, ldn, nullptr, kv_src, ld_src);
+  else if (dk == 32) hipLaunchKernelGGL((attn_decode_kernel<32, true>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, T, scale, pos, cache_off, knew, vnew, ldn, nullptr, kv_src, ld_src);
+  else hipLaunchKernelGGL((attn_decode_kernel<16, true>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, T, scale, pos, cache_off, knew, vnew, ldn, nullptr, kv_src, ld_src);
+  GCT_LAUNCH_CHECK("attn_decode_beam");
+  return GCT_OK;
+}
+
+extern "C" int gct_beam_select(const float* logits, int V, int n, int k, float* scores, uint8_t* finished,
+                               int32_t* lengths, int32_t* parent, int64_t* ys, int64_t ld_ys, uint8_t* valid,
+                               int64_t valid_sb, int valid_off, int32_t* kv_src, int64_t ld_src, int T, uint8_t* done,
+                               const int32_t* pos_dev, int64_t pad_id, int64_t eos_id, void* stream) {
+  GCT_CHECK_ARG(logits && scores && finished && lengths && ys && valid && kv_src && done && pos_dev && n >= 0,
+                "beam_select: bad args");
+  GCT_CHECK_ARG(k >= 1 && k <= GCT_BEAM_MAX_K && V >= k && V <= GCT_BEAM_MAX_VOCAB,
+                "beam_select: beam size %d / vocabulary %d unsupported", k, V);
+  GCT_CHECK_ARG(T > 0 && T <= 256 && valid_off >= 0 && valid_off < T && ld_src >= T && valid_sb >= T &&
+                    ld_ys >= T - valid_off,
+                "beam_select: cache rows %d / map %lld / valid %lld / ys %lld", T, (long long)ld_src,
+                (long long)valid_sb, (long long)ld_ys);
+  GCT_CHECK_ARG(pad_id >= 0 && pad_id < V, "beam_select: pad id %lld outside the vocabulary", (long long)pad_id);
+  if (n == 0) return GCT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (k <= 4) hipLaunchKernelGGL(beam_select_kernel<4>, dim3((unsigned)n), dim3(256), 0, st, logits, V, k, scores, finished, lengths, parent, ys, ld_ys, valid, valid_sb, valid_off, kv_src, ld_src, T, done, pos_dev, pad_id, eos_id);
+  else if (k <= 8) hipLaunchKernelGGL(beam_select_kernel<8>, dim3((unsigned)n), dim3(256), 0, st, logits, V, k, scores, finished, lengths, parent, ys, ld_ys, valid, valid_sb, valid_off, kv_src, ld_src, T, done, pos_dev, pad_id, eos_id);
+  else hipLaunchKernelGGL(beam_select_kernel<16>, dim3((unsigned)n), dim3(256), 0, st, logits, V, k, scores, finished, lengths, parent, ys, ld_ys, valid, valid_sb, valid_off, kv_src, ld_src, T, done, pos_dev, pad_id, eos_id);
+  GCT_LAUNCH_CHECK("beam_select");
   return GCT_OK;
 }

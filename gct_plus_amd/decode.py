@@ -19,6 +19,12 @@ same token ids come out of
 The step reads its position from a DEVICE-side counter (csrc/decode.hip), so one captured graph serves every step
 (`use_graphs=True`): no host round trip, no per-position capture.  Work per generated token drops from O(T) decoder
 passes to O(1).
+
+Beam search (`start(..., beams=k)` + `generate_beam`): sample s owns rows s*k .. s*k+k-1.  The rules are stated once,
+in `beam_step_reference` / `beam_finalize`; gct_beam_select implements the step on the device.  The self-attention
+caches, ys and valid stay PHYSICAL slots, each written once by the row that owns it, and an int32 map kv_src [n*k, T]
+says where beam r's logical position j lives (row kv_src[r, j]): a selection copies the parent's map row instead of the
+parent's caches (gct_attn_decode_beam reads through it).  Final ids: token t of beam b is ys[kv_src[b, off + t], t].
 """
 from __future__ import annotations
 
@@ -43,6 +49,74 @@ ZATTN = os.environ.get("GCT_DECODE_ZATTN", "1") != "0"
 # eager launches of the same step on this box; `GCT_DECODE_GRAPH_GUARD=0` switches the guard off (always replay)
 REPLAY_GUARD = os.environ.get("GCT_DECODE_GRAPH_GUARD", "1") != "0"
 REPLAY_SLOW_FACTOR = 1.3
+# beam search: length penalty exponent of the final ranking score / length**alpha (reference generate_mols.py:182-185)
+BEAM_ALPHA = 0.7
+BEAM = "beam"                                       # selection mode key of the beam step (self.graphs, _advance)
+
+
+# ------------------------------------------------------------------------------------- beam-search semantics
+def check_beam_size(beam_size, vocab):
+    """1 <= beam_size <= ops.BEAM_MAX_K and beam_size <= vocab (gct_beam_select's limits); ValueError otherwise."""
+    if isinstance(beam_size, bool) or not isinstance(beam_size, int):
+        raise ValueError(f"beam_size must be an int, got {beam_size!r}")
+    if not 1 <= beam_size <= ops.BEAM_MAX_K:
+        raise ValueError(f"beam_size {beam_size} outside [1, {ops.BEAM_MAX_K}]")
+    if beam_size > vocab:
+        raise ValueError(f"beam_size {beam_size} exceeds the vocabulary ({vocab} tokens)")
+    if vocab > ops.BEAM_MAX_VOCAB:
+        raise ValueError(f"beam search supports vocabularies up to {ops.BEAM_MAX_VOCAB} tokens, not {vocab}")
+
+
+def beam_init(n, k, device=None):
+    """State after the prefill: scores [n, k] = [0, -inf, ...] (the first expansion uses beam 0 only: every beam holds
+    the same prefix), finished [n, k] False, lengths [n, k] 0 (generated tokens, <eos> included)."""
+    scores = torch.full((n, k), -math.inf, dtype=torch.float32, device=device)
+    scores[:, 0] = 0.0
+    return scores, torch.zeros(n, k, dtype=torch.bool, device=device), torch.zeros(n, k, dtype=torch.int64, device=device)
+
+
+def beam_log_softmax(logits):
+    """fp32 log-softmax of the step's logits, x - m - log sum exp(x - m)."""
+    y = logits.float() - logits.float().max(-1, keepdim=True).values
+    return y - torch.log(torch.exp(y).sum(-1, keepdim=True))
+
+
+def beam_candidates(scores, finished, logp, k, pad_id):
+    """[n, k*V] candidate scores at flat index beam * V + token (-inf: not offered); see beam_step_reference."""
+    n = scores.shape[0]
+    V = logp.shape[-1]
+    cand = scores.float().unsqueeze(-1) + logp.reshape(n, k, V).float()
+    frozen = torch.full_like(cand, -math.inf)
+    frozen[:, :, pad_id] = scores.float()
+    return torch.where(finished.unsqueeze(-1), frozen, cand).reshape(n, k * V)
+
+
+def beam_step_reference(scores, finished, lengths, logp, k, pad_id, eos_id):
+    """One beam-search step, THE statement of the rules (gct_beam_select implements them on the device).
+    scores [n, k] fp32, finished [n, k] bool, lengths [n, k] int, logp [n*k, V] (beam_log_softmax of the step's logits).
+      * a live beam b offers score_b + logp_b(v) for every token v;
+      * a finished beam offers exactly one candidate, itself with token pad_id and its score unchanged (frozen);
+      * the k best candidates by score become the children, ties to the lower flat index b*V + token;
+      * child: finished = parent.finished or token == eos_id; length = parent's + 1 while the parent was live.
+    Returns (parent [n, k], token [n, k], scores, finished, lengths) of the children, best first."""
+    V = logp.shape[-1]
+    cand = beam_candidates(scores, finished, logp, k, pad_id)
+    order = torch.sort(cand, dim=1, descending=True, stable=True).indices[:, :k]
+    parent, token = order // V, order % V
+    pfin = finished.gather(1, parent)
+    return (parent, token, cand.gather(1, order), pfin | (token == eos_id),
+            lengths.gather(1, parent) + (~pfin).to(lengths.dtype))
+
+
+def beam_finalize(ys, scores, lengths, t0, alpha=BEAM_ALPHA):
+    """Final ranking: beams sorted by score / length**alpha (ties to the lower beam), also when the length limit ended
+    the search.  ys [n, k, L] (prefix of t0 tokens, pad after each beam's end) is cut to t0 + the longest beam.
+    Returns (ys, scores, lengths) in that order."""
+    norm = scores / lengths.clamp(min=1).to(scores.dtype) ** alpha
+    order = torch.sort(norm, dim=1, descending=True, stable=True).indices
+    ys = ys.gather(1, order.unsqueeze(-1).expand_as(ys))
+    lengths = lengths.gather(1, order)
+    return ys[:, :, :t0 + int(lengths.max())].contiguous(), scores.gather(1, order), lengths
 
 
 class KVDecoder:
@@ -63,9 +137,10 @@ class KVDecoder:
 
     # -------------------------------------------------------------------------------------
     @torch.no_grad()
-    def start(self, z, src_mask, dconds=None, max_total_len=208, refold=False):
+    def start(self, z, src_mask, dconds=None, max_total_len=208, refold=False, beams=1):
         """z [n, L_e, latent]; src_mask bool [n,1,L_e] (as the reference builds it); max_total_len = longest
         token sequence (prefix + generated) this call may reach.
+        beams=k > 1 (for generate_beam): latent, masks and dconds are replicated per beam, the decode runs n*k rows.
         refold=True recomputes the folded cross-attention projections even if `model.weights_token()` has not changed:
         the token follows torch in-place operations on the parameters / the flat buffer and FusedAdam's kernel, but NOT
         writes through `p.data` (p.data.copy_ / mul_: a separate version counter) or raw kernels of the caller's own --
@@ -73,6 +148,11 @@ class KVDecoder:
         if refold:
             self._fold_key = None
         dec, d = self.dec, self.d
+        beams = int(beams)
+        if beams != 1:
+            check_beam_size(beams, self.model.out.weight.shape[0])
+            z, src_mask = z.repeat_interleave(beams, 0), src_mask.repeat_interleave(beams, 0)
+            dconds = None if dconds is None else dconds.repeat_interleave(beams, 0)
         dev = z.device
         n, Le, lat = z.shape
         if hasattr(self.model, "refresh_weight_planes"):
@@ -104,7 +184,7 @@ class KVDecoder:
             # the positional table has pe_rows rows (Model/modules.py:116-144: 200); the reference fails loudly past it
             raise ValueError(f"decode: {max_total_len} tokens + {self.off} condition rows exceed the {pe_rows}-row "
                              "positional table")
-        shape = (n, Lk, T, str(dev), self.zattn, lat)
+        shape = (n, Lk, T, str(dev), self.zattn, lat, beams)
         if shape != self._shape:
             # new geometry: new buffers, and the graphs captured against the old ones are dropped with them
             # (they hold raw pointers: replaying them after a reallocation would write freed memory)
@@ -138,6 +218,14 @@ class KVDecoder:
             self.src_klen = torch.empty(n, dtype=torch.int32, device=dev)  # leading memory rows the cross-attention reads
             self.pos = torch.zeros(1, dtype=torch.int32, device=dev)       # token index the next step consumes
             self.seed = torch.zeros(1, dtype=torch.int64, device=dev)      # multinomial seed of this generate()
+            # beam search state (generate_beam), per row: score, finished, length, parent; the ancestry map; done [n/k]
+            self.beams = beams
+            self.bscores = torch.zeros(n, device=dev)
+            self.bfin = torch.zeros(n, dtype=torch.uint8, device=dev)
+            self.blen = torch.zeros(n, dtype=torch.int32, device=dev)
+            self.bparent = torch.zeros(n, dtype=torch.int32, device=dev)
+            self.kv_src = torch.zeros(n, T, dtype=torch.int32, device=dev)
+            self.bdone = torch.zeros(n // beams, dtype=torch.uint8, device=dev)
             dff = dec.layers[0].ff.linear_1.weight.shape[0]
             V = self.model.out.weight.shape[0]
             need = ops._L().gct_linear_fwd_ws_bytes
@@ -262,8 +350,9 @@ class KVDecoder:
 
     # -------------------------------------------------------------------------------------
     @torch.no_grad()
-    def step(self):
-        """Consume token ys[:, p] with p = *pos + 1 ... see _chain: ONE generated token, position on the device."""
+    def step(self, beam=False):
+        """Consume token ys[:, p] with p = *pos + 1 ... see _chain: ONE generated token, position on the device.
+        beam=True: the self-attention reads the caches through the ancestry map kv_src (gct_attn_decode_beam)."""
         dec, d, n, T, B = self.dec, self.d, self.n, self.T, self.buf
         L = ops._L()
         st = ops._st()
@@ -279,9 +368,14 @@ class KVDecoder:
             ops.linear_fwd(B["x2"], [a1.q_linear.weight, a1.k_linear.weight, a1.v_linear.weight],
                            [a1.q_linear.bias, a1.k_linear.bias, a1.v_linear.bias],
                            [qkv, qkv[:, d:], qkv[:, 2 * d:]], 3 * d, **self.gemm_kw)
-            ops.attn_decode(qkv, 3 * d, self.kc[li], self.vc[li], d, T * d, self.valid, T, B["o"], n,
-                            self.H, 0, self.dk, pos=self.pos, cache_off=self.off, knew=qkv[:, d:],
-                            vnew=qkv[:, 2 * d:], ldn=3 * d)
+            if beam:
+                ops.attn_decode_beam(qkv, 3 * d, self.kc[li], self.vc[li], d, T * d, self.valid, T, B["o"], n,
+                                     self.H, T, self.dk, self.pos, self.off, qkv[:, d:], qkv[:, 2 * d:], 3 * d,
+                                     self.kv_src)
+            else:
+                ops.attn_decode(qkv, 3 * d, self.kc[li], self.vc[li], d, T * d, self.valid, T, B["o"], n,
+                                self.H, 0, self.dk, pos=self.pos, cache_off=self.off, knew=qkv[:, d:],
+                                vnew=qkv[:, 2 * d:], ldn=3 * d)
             ops.linear_fwd(B["o"], [a1.out.weight], [a1.out.bias], [B["xa"]], d,
                            epi=ops.EPI_DROP_RESID, resid=x, **self.gemm_kw)
             ops.norm_fwd(B["xa"], layer.norm_2.alpha, layer.norm_2.bias, layer.norm_2.eps, out=B["x2"])
@@ -312,9 +406,20 @@ class KVDecoder:
         return B["logits"]
 
     def _select(self, mode):
-        """softmax + choice of the next token from buf['logits']; written at ys[:, *pos + 1] (device position)."""
+        """softmax + choice of the next token from buf['logits']; written at ys[:, *pos + 1] (device position).
+        mode BEAM: gct_beam_select (beam state, the kv_src map and bdone in place)."""
+        if mode == BEAM:
+            ops.beam_select(self.buf["logits"], self.beams, self.bscores, self.bfin, self.blen, self.ys, self.valid,
+                            self.off, self.kv_src, self.bdone, self.pos, self.pad_id, self.eos_id,
+                            parent_i32=self.bparent)
+            return
         ops.select_token(self.buf["logits"], self.ys, 0, self.valid, self.done, mode, self.pad_id, self.eos_id,
                          pos_dev=self.pos, valid_off=self.off, seed_dev=self.seed)
+
+    def _advance(self, mode):
+        """One step and its selection: the unit a graph captures."""
+        self.step(beam=mode == BEAM)
+        self._select(mode)
 
     # -------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -344,15 +449,49 @@ class KVDecoder:
             ys = ys[:, :t0 + int(first.max().item()) + 1]
         return ys.clone()
 
+    @torch.no_grad()
+    def generate_beam(self, ys0, beam_size, max_strlen=80, alpha=BEAM_ALPHA, check_every=8, use_graphs=False):
+        """Beam search from the prefix ys0 [n, t0] after start(..., beams=beam_size): up to max_strlen-1 tokens, stops
+        early once every beam of every sample has produced <eos> (checked every `check_every` steps).
+        Returns (ys [n, k, L] int64, scores [n, k] fp32 sums of log-probabilities, lengths [n, k] int64), beams sorted
+        by score / length**alpha (beam_finalize); pad after each beam's end, L = t0 + the longest beam."""
+        k = int(beam_size)
+        if k != self.beams:
+            raise ValueError(f"generate_beam: beam_size {k}, but start() prepared {self.beams} beam(s) per sample")
+        ns, t0 = ys0.shape
+        if ns * k != self.n:
+            raise ValueError(f"generate_beam: {ns} prefixes x {k} beams != the {self.n} rows start() prepared")
+        steps = max_strlen - 1
+        if steps < 1:
+            raise ValueError("generate_beam: max_strlen must be at least 2")
+        if self.off + t0 + steps > self.T:
+            raise ValueError(f"prefix {t0} + {steps} steps exceeds the cache length {self.T - self.off}")
+        dev = self.ys.device
+        self.prefill(ys0.to(dev).repeat_interleave(k, 0))
+        scores, _, _ = beam_init(ns, k, dev)
+        self.bscores.copy_(scores.view(-1))
+        self.bfin.zero_()
+        self.blen.zero_()
+        self.bdone.zero_()
+        self.kv_src.copy_(torch.arange(self.n, dtype=torch.int32, device=dev).view(-1, 1).expand(-1, self.T))
+        self._select(BEAM)                                         # token t0 from the prefill's last position
+        last = t0 + steps
+        for i in range(1, steps):
+            self._run_step(BEAM, use_graphs)                       # consumes token t0+i-1, writes token t0+i
+            if check_every and (i + 1) % check_every == 0 and bool(self.bdone.all()):
+                last = t0 + i + 1
+                break
+        ys = torch.gather(self.ys[:, :last], 0, self.kv_src[:, self.off:self.off + last].long())
+        return beam_finalize(ys.view(ns, k, last), self.bscores.view(ns, k).clone(),
+                             self.blen.view(ns, k).to(torch.int64), t0, alpha)
+
     def _run_step(self, mode, use_graphs):
         if not use_graphs:
-            self.step()
-            self._select(mode)
+            self._advance(mode)
             return
         g = self.graphs.get(mode)
         if g is False:                                  # no usable graph for these buffers (capture failed, or replay is
-            self.step()                                 # the slower launch mode on this box): same kernels, eagerly
-            self._select(mode)
+            self._advance(mode)                         # the slower launch mode on this box): same kernels, eagerly
             return
         if g is None:
             g = self._capture(mode)
@@ -361,10 +500,16 @@ class KVDecoder:
         g.replay()
 
     def _state(self):
-        return (self.pos.clone(), self.ys.clone(), self.valid.clone(), self.done.clone())
+        return tuple(t.clone() for t in self._state_tensors())
 
     def _restore(self, keep):
-        self.pos.copy_(keep[0]); self.ys.copy_(keep[1]); self.valid.copy_(keep[2]); self.done.copy_(keep[3])
+        for t, k in zip(self._state_tensors(), keep):
+            t.copy_(k)
+
+    def _state_tensors(self):
+        """Everything a step + selection writes besides the caches' next row (the beam state included)."""
+        return (self.pos, self.ys, self.valid, self.done, self.bscores, self.bfin, self.blen, self.bparent,
+                self.kv_src, self.bdone)
 
     def _capture(self, mode):
         """Capture step + select into one graph; returns it, or None after running the step eagerly (capture failed, or
@@ -376,8 +521,7 @@ class KVDecoder:
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            self.step()
-            self._select(mode)
+            self._advance(mode)
         torch.cuda.current_stream().wait_stream(s)
         # (the key / value row the warm-up appended is rewritten with the same values by the replay below)
         self._restore(keep)
@@ -389,8 +533,7 @@ class KVDecoder:
             # thread_local: another thread's runtime calls (the RCCL watchdog of a data-parallel job queries
             # events) must not invalidate this thread's capture
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self.step()
-                self._select(mode)
+                self._advance(mode)
         except RuntimeError as exc:                     # no graph for these buffers: same kernels, launched eagerly
             import warnings
             warnings.warn(f"KVDecoder: graph capture failed ({exc}); decoding without graph replay")
@@ -398,15 +541,13 @@ class KVDecoder:
             self._restore(keep)
             self.graphs[mode] = False
             self.graph_replay = False
-            self.step()
-            self._select(mode)
+            self._advance(mode)
             return None
         self.graphs[mode] = g
         if REPLAY_GUARD and not self._replay_is_fast(mode, g, keep):
             self.graphs[mode] = False
             self.graph_replay = False
-            self.step()
-            self._select(mode)
+            self._advance(mode)
             return None
         return g
 
@@ -431,8 +572,7 @@ class KVDecoder:
             return e0.elapsed_time(e1) / k
 
         def eager():
-            self.step()
-            self._select(mode)
+            self._advance(mode)
 
         g.replay()                                                       # first replay (instantiation, upload): untimed
         self._restore(keep)
@@ -471,3 +611,33 @@ def reference_style_decode(model, z, src_mask, dconds, ys0, pad_id, eos_id, max_
         if bool(done.all()):
             break
     return ys
+
+
+@torch.no_grad()
+def reference_style_beam_decode(model, z, src_mask, dconds, ys0, pad_id, eos_id, beam_size, max_strlen=80,
+                                alpha=BEAM_ALPHA, trace=None):
+    """Beam search on the un-cached model.decode over [n*k, t] every step (the reference's loop shape,
+    sampling_tool.py:140-184, with beam_step_reference as the selection): the baseline generate_beam must match.
+    use_cond2dec: the block mask and the logits of the token rows only, as the cached decoder sees them.
+    trace (a list): receives the k+1 best candidate scores [n, k+1] of every step (near-tie diagnostics)."""
+    from .Model.modules import get_trg_mask
+    dec = model.decoder
+    c2d = bool(dec.use_cond2dec and dec.nconds > 0)
+    nc = dec.nconds if c2d else 0
+    n, t0 = ys0.shape
+    k = int(beam_size)
+    rep = lambda x: None if x is None else x.repeat_interleave(k, 0)       # noqa: E731
+    z, src_mask, dconds, ys = rep(z), rep(src_mask), rep(dconds), rep(ys0)
+    scores, finished, lengths = beam_init(n, k, ys.device)
+    base = torch.arange(n, device=ys.device).view(n, 1) * k
+    for _ in range(max_strlen - 1):
+        logits = model.decode(ys, z, src_mask, get_trg_mask(ys, pad_id, c2d, dconds), dconds)[:, nc:]
+        logp = beam_log_softmax(logits[:, -1])
+        if trace is not None:
+            cand = beam_candidates(scores, finished, logp, k, pad_id)
+            trace.append(cand.topk(min(k + 1, cand.shape[1]), dim=1).values.cpu())
+        parent, tok, scores, finished, lengths = beam_step_reference(scores, finished, lengths, logp, k, pad_id, eos_id)
+        ys = torch.cat([ys[(base + parent).view(-1)], tok.view(-1, 1)], dim=1)
+        if bool(finished.all()):
+            break
+    return beam_finalize(ys.view(n, k, -1), scores, lengths, t0, alpha)

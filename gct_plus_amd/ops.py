@@ -929,3 +929,28 @@ def select_token(logits2d, ys, pos, valid_u8, done_u8, mode, pad_id, eos_id, see
                                 valid_u8.stride(0) if valid_u8 is not None else 0, _p(done_u8),
                                 _p(probs_out), n, mode, pad_id, eos_id, seed, _p(pos_dev), valid_off, _p(seed_dev),
                                 _st()), "gct_select_token")
+
+
+BEAM_MAX_K, BEAM_MAX_VOCAB = 16, 65536          # GCT_BEAM_MAX_K / GCT_BEAM_MAX_VOCAB (include/gctplus_hip.h)
+
+
+def attn_decode_beam(q, ldq, k, v, kv_row, kv_batch, valid_u8, valid_sb, out, n, H, T, dk, pos, cache_off, knew, vnew,
+                     ldn, kv_src):
+    """gct_attn_decode_beam: the device-position attn_decode whose key / value / valid flag j of row b come from physical
+    row kv_src[b, j] (int32 [n, >= T]); this step's key / value are appended to row b."""
+    check(_L().gct_attn_decode_beam(_p(q), ldq, _p(k), _p(v), kv_row, kv_batch, _p(valid_u8), valid_sb, _p(out),
+                                    out.stride(0), n, H, T, dk, 1.0 / math.sqrt(dk), _p(pos), cache_off, _p(knew),
+                                    _p(vnew), ldn, _p(kv_src), kv_src.stride(0), _st()), "gct_attn_decode_beam")
+
+
+def beam_select(logits2d, beam_size, scores, finished_u8, lengths_i32, ys, valid_u8, valid_off, kv_src, done_u8,
+                pos_dev, pad_id, eos_id, parent_i32=None):
+    """gct_beam_select over logits [n*k, V]: the k best children of each sample (decode.beam_step_reference), written
+    in place to the beam state, ys[:, *pos_dev + 1], valid, the kv_src map and done [n]."""
+    rows, V = logits2d.shape
+    k = int(beam_size)
+    T = kv_src.shape[1]
+    check(_L().gct_beam_select(_p(logits2d), V, rows // k, k, _p(scores), _p(finished_u8), _p(lengths_i32),
+                               _p(parent_i32), _p(ys), ys.stride(0), _p(valid_u8), valid_u8.stride(0), valid_off,
+                               _p(kv_src), kv_src.stride(0), T, _p(done_u8), _p(pos_dev), pad_id, eos_id, _st()),
+          "gct_beam_select")

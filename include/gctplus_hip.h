@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 15
+#define GCT_ABI_VERSION 16
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -405,6 +405,32 @@ int gct_select_token(const float* logits, int V, int64_t* ys, int64_t ld_ys, int
                      int64_t valid_sb, uint8_t* done, float* probs_out, int n, int mode,
                      int64_t pad_id, int64_t eos_id, uint64_t seed, const int32_t* pos_dev, int valid_off,
                      const uint64_t* seed_dev, void* stream);
+
+/* Beam search (gct_plus_amd/decode.py beam_step_reference states the rules).  Sample s owns the k rows
+ * s*k .. s*k+k-1 of an n*k-row decode.  The self-attention caches, ys and valid are PHYSICAL slots, each written once:
+ * row r writes cache slot cache_off + p in the step that consumes token p, and ys[r][p] / valid[r][cache_off + p] when
+ * that token is chosen.  kv_src int32 [n*k][ld_src] maps beam r's logical position j to the physical row kv_src[r][j].
+ * gct_attn_decode_beam: the device-position form of gct_attn_decode (pos required, no klen) where key / value j of row
+ *   b and valid[.][j] are read from row kv_src[b][j] (clamped to [0, n)); this step's key / value are appended to row b.
+ *   T = cache rows (<= 256, <= ld_src).
+ * gct_beam_select: one workgroup per sample; p = *pos_dev + 1.  Candidates: live beam b offers scores[b] + logp_b(v)
+ *   for every token v (logp = fp32 log-softmax of logits row b, x - m - log sum exp(x - m)); a finished beam offers
+ *   itself once, token pad_id, score unchanged; a beam at -inf offers nothing.  The k best by score, ties to the lower
+ *   beam * V + token, become the children in order: scores / finished (parent's or token == eos_id) / lengths (parent's
+ *   + 1 while the parent was live) / parent (nullable, int32 [n*k]) per row; ys[row][p] = token,
+ *   valid[row][valid_off + p] = token != pad_id; kv_src[row][0, T) = the parent's row before this call, with entry
+ *   valid_off + p = row; done[s] = all k children finished.  1 <= k <= GCT_BEAM_MAX_K, k <= V <= GCT_BEAM_MAX_VOCAB,
+ *   0 <= pad_id < V, T <= 256, ld_src >= T, valid_sb >= T, ld_ys >= T - valid_off; otherwise GCT_ERR_ARG. */
+#define GCT_BEAM_MAX_K 16
+#define GCT_BEAM_MAX_VOCAB 65536
+int gct_attn_decode_beam(const float* q, int64_t ldq, float* k, float* v, int64_t kv_row, int64_t kv_batch,
+                         const uint8_t* valid, int64_t valid_sb, float* o, int64_t ldo, int n, int H, int T, int dk,
+                         float scale, const int32_t* pos, int cache_off, const float* knew, const float* vnew,
+                         int64_t ldn, const int32_t* kv_src, int64_t ld_src, void* stream);
+int gct_beam_select(const float* logits, int V, int n, int k, float* scores, uint8_t* finished, int32_t* lengths,
+                    int32_t* parent, int64_t* ys, int64_t ld_ys, uint8_t* valid, int64_t valid_sb, int valid_off,
+                    int32_t* kv_src, int64_t ld_src, int T, uint8_t* done, const int32_t* pos_dev, int64_t pad_id,
+                    int64_t eos_id, void* stream);
 
 /* ------------------------------------------------ host side: SMILES tokeniser + collate */
 /* Utils/field.py:8-33 moltokenize (the atom-wise regex, findall semantics) as a scanner.

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Decoded SMILES/s (BASELINE config 5 shape: pscavaetf-style decode, batch 512, max_strlen 80):
-KV-cached decode (eager and graph replay) vs the reference-style full re-run loop."""
+KV-cached decode (eager and graph replay) vs the reference-style full re-run loop.
+--beam K: beam search of n samples x K beams against greedy decode of the same n*K rows (ms per token step, SMILES/s),
+ids checked against reference_style_beam_decode on the first --ref-n samples."""
 import argparse
 import os
 import sys
@@ -11,7 +13,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gct_plus_amd import synthetic  # noqa: E402
 from gct_plus_amd.Model import model_dict  # noqa: E402
-from gct_plus_amd.decode import KVDecoder, reference_style_decode  # noqa: E402
+from gct_plus_amd.decode import KVDecoder, reference_style_beam_decode, reference_style_decode  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=512)
@@ -19,6 +21,7 @@ ap.add_argument("--model-type", default="vaetf")
 ap.add_argument("--ref-n", type=int, default=64, help="batch for the (slow) reference-style loop")
 ap.add_argument("--ragged", action="store_true", help="latent length 80 with MOSES-like valid lengths N(35,8) (padded "
                 "memory, as Inference/*_sampling.py batches it) instead of 40 fully valid positions")
+ap.add_argument("--beam", type=int, default=0, help="beam search with K beams per sample (see the docstring)")
 a = ap.parse_args()
 mtype = a.model_type
 vs, vt = synthetic.vocab_sizes(mtype)
@@ -34,6 +37,43 @@ if a.ragged:
     lens = (torch.randn(n, device="cuda") * 8 + 35).round().clamp(15, 80).long() + nc
     src_mask = (torch.arange(Le, device="cuda")[None, :] < lens[:, None]).unsqueeze(1)
 ys0 = torch.full((n, 1), synthetic.SOS_ID, dtype=torch.long, device="cuda")
+
+
+def timed(run):
+    run()                                                                  # warm-up / capture
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = run()
+    torch.cuda.synchronize()
+    return out, time.perf_counter() - t0
+
+
+if a.beam:
+    k = a.beam
+    rep = lambda x: None if x is None else x.repeat_interleave(k, 0)     # noqa: E731
+    kg = KVDecoder(model, synthetic.PAD_ID, synthetic.SOS_ID, eos_id=-1)   # never stop early: worst case
+    kb = KVDecoder(model, synthetic.PAD_ID, synthetic.SOS_ID, eos_id=-1)
+    for graphs in (False, True):
+        def greedy():
+            kg.start(rep(z), rep(src_mask), rep(dconds), max_total_len=96)
+            return kg.generate(rep(ys0), 80, use_graphs=graphs, check_every=0)
+
+        def beam():
+            kb.start(z, src_mask, dconds, max_total_len=96, beams=k)
+            return kb.generate_beam(ys0, k, 80, use_graphs=graphs, check_every=0)
+        _, tg = timed(greedy)
+        (ys, scores, _), tb = timed(beam)
+        print(f"graphs={graphs}: greedy n={n * k} rows {tg / 79 * 1e3:.3f} ms/step ({n * k / tg:.0f} SMILES/s) | "
+              f"beam {n} x {k} {tb / 79 * 1e3:.3f} ms/step ({n / tb:.0f} SMILES/s) | beam/greedy {tb / tg:.3f}",
+              flush=True)
+    m = min(a.ref_n, n)
+    if m:
+        ref, rsc, _ = reference_style_beam_decode(model, z[:m], src_mask[:m], None if dconds is None else dconds[:m],
+                                                  ys0[:m], synthetic.PAD_ID, -1, k, 80)
+        print("beam token ids equal:", bool(torch.equal(ref, ys[:m])),
+              f"max score diff {float((rsc - scores[:m]).abs().max()):.2e}")
+    sys.exit(0)
+
 kd = KVDecoder(model, synthetic.PAD_ID, synthetic.SOS_ID, eos_id=-1)       # never stop early: worst case
 for graphs in (False, True):
     kd.start(z, src_mask, dconds, max_total_len=96)
