@@ -12,6 +12,12 @@ Deliberate deviations, none in the arithmetic:
   * decode_algo="beam" (the reference's -decode_algo choice, whose Inference/generate_mols.py code does not run) is
     beam search with frozen finished beams and a length-normalised final ranking (gct_plus_amd.decode): `decode`
     returns the best beam, `decode_beams` all of them.
+
+`sample_multiple_smiles` (scaffold models) is the reference's commented-out PscavaetfSampling.sample_multiple_smiles,
+one scaffold per row: the prefixes <sos> scaffold <sep> of different lengths are right-padded into ONE batch and decoded
+with per-row positions (KVDecoder.generate(prefix_lens=)), so each row gives exactly what `sample_smiles` gives for its
+scaffold alone (no left-padding, which would shift the positional encodings).  Beam search has no mixed-length kernels:
+it runs one decode per prefix length and restores the input order.
 """
 from __future__ import annotations
 
@@ -22,7 +28,7 @@ import torch
 
 from ..Model.modules import get_src_mask
 from ..data import Vocab, tokenize
-from ..decode import BEAM_ALPHA, KVDecoder, check_beam_size
+from ..decode import BEAM_ALPHA, KVDecoder, check_beam_size, generated_tokens
 
 
 def sample_token_lengths(data: Sequence[int], size: int, rng: np.random.Generator) -> np.ndarray:
@@ -38,6 +44,53 @@ def sample_token_lengths(data: Sequence[int], size: int, rng: np.random.Generato
     u = rng.uniform(0, 1, size)
     idx = np.clip(np.argmax(cdf[None, :] >= u[:, None], axis=1) - 1, 0, nbins - 1)
     return np.rint(centres[idx] + dx * rng.normal(size=size) / 2).astype(int)
+
+
+def pack_prefixes(rows: Sequence[Sequence[int]], pad_id: int):
+    """Token-id rows of different lengths -> (ys0 [n, t0_max] int64 right-padded with pad_id, lens [n] int64)."""
+    lens = [len(r) for r in rows]
+    if not rows or min(lens) < 1:
+        raise ValueError("pack_prefixes: every row needs at least one token")
+    ys0 = torch.full((len(rows), max(lens)), pad_id, dtype=torch.long)
+    for i, r in enumerate(rows):
+        ys0[i, :len(r)] = torch.as_tensor(list(r), dtype=torch.long)
+    return ys0, torch.as_tensor(lens, dtype=torch.long)
+
+
+def group_by_length(lens):
+    """Row indices grouped by prefix length, shortest first, input order within a group: [(length, idx int64)]."""
+    lens = torch.as_tensor(lens).long().view(-1)
+    return [(int(v), (lens == v).nonzero().view(-1)) for v in torch.unique(lens).tolist()]
+
+
+def latent_setup_rows(extras, zs, toklen, latent_dim, sample_toklen, sample_z):
+    """Per-row latent geometry of a mixed-scaffold batch: row r uses extras[r] + toklen[r] latent rows (its scaffold,
+    <sep>, then the molecule), L_e = the maximum, src_mask [n, 1, L_e] marks each row's own rows.  zs (optional)
+    [n, >= L_e, latent]; with zs and no toklen, toklen[r] = zs.size(1) - extras[r] (sample_smiles' rule per row).
+    Returns (zs [n, L_e, latent], toklen list, src_mask)."""
+    n = len(extras)
+    if zs is not None:
+        if zs.dim() != 3 or zs.size(0) != n:
+            raise ValueError(f"zs must be [{n}, L_e, {latent_dim}], got {list(zs.shape)}")
+        if toklen is None:
+            toklen = [zs.size(1) - e for e in extras]
+    elif toklen is None:
+        toklen = list(sample_toklen(n))
+    toklen = [int(t) for t in toklen]
+    if len(toklen) != n:
+        raise ValueError(f"toklen has {len(toklen)} entries for {n} rows")
+    stop = torch.as_tensor(toklen, dtype=torch.long) + torch.as_tensor(list(extras), dtype=torch.long)
+    if int(stop.min()) < 1:
+        raise ValueError("every row needs at least one latent row")
+    lat = int(stop.max())
+    if zs is None:
+        zs = sample_z(lat, n)
+    elif zs.size(1) < lat:
+        raise ValueError(f"zs has {zs.size(1)} latent rows, a row needs {lat}")
+    else:
+        zs = zs[:, :lat]
+    src_mask = torch.arange(lat).expand(n, 1, lat) < stop.view(n, 1, 1)
+    return zs, toklen, src_mask
 
 
 class Sampling:
@@ -98,9 +151,12 @@ class Sampling:
 
     # ---- decode: KV-cached equivalent of Sampling.decode (sampling_tool.py:140-184) ----------
     @torch.no_grad()
-    def decode(self, zs, ys, src_mask, dconds=None):
-        """ids [n, L] (prefix included); with decode_algo="beam" the best beam of each sample."""
+    def decode(self, zs, ys, src_mask, dconds=None, prefix_lens=None):
+        """ids [n, L] (prefix included); with decode_algo="beam" the best beam of each sample.
+        prefix_lens (ints [n], optional): row r's prefix is ys[r, :t0_r] (KVDecoder.generate); not with beam search."""
         if self.decode_algo == "beam":
+            if prefix_lens is not None:
+                raise ValueError("decode: beam search takes prefixes of one length (see sample_multiple_smiles)")
             return self.decode_beams(zs, ys, src_mask, dconds)[0][:, 0]
         self.seed += 1
         zs, ys, src_mask = zs.to(self.device), ys.to(self.device), src_mask.to(self.device)
@@ -109,7 +165,7 @@ class Sampling:
         # the positional table has 200 rows, of which use_cond2dec spends n_c on the condition tokens
         self.kv.start(zs, src_mask, dconds, max_total_len=min(200 - self.kv.off, total))
         return self.kv.generate(ys, self.max_strlen, algo=self.decode_algo, seed=self.seed,
-                                use_graphs=self.use_graphs)
+                                use_graphs=self.use_graphs, prefix_lens=prefix_lens)
 
     @torch.no_grad()
     def decode_beams(self, zs, ys, src_mask, dconds=None, beam_size=None, alpha=None):
@@ -137,6 +193,35 @@ class Sampling:
         stop = torch.as_tensor(toklen, dtype=torch.long).view(n, 1, 1) + extra
         src_mask = torch.arange(lat).expand(n, 1, lat) < stop
         return zs, toklen, src_mask
+
+    def _scaffold_prefixes(self, scaffolds):
+        """<sos> scaffold <sep> per row -> (ys0 [n, t0_max], lens [n], extras: scaffold tokens + 1 per row)."""
+        sca = [self.smi_to_id(s) for s in scaffolds]
+        ys0, lens = pack_prefixes([[self.sos_id] + ids + [self.sep_id] for ids in sca], self.pad_id)
+        return ys0, lens, [len(ids) + 1 for ids in sca]
+
+    @torch.no_grad()
+    def _sample_multiple(self, scaffolds, zs, toklen, dconds):
+        """One scaffold per row (sample_multiple_smiles): a single mixed-prefix decode, or for beam search one decode
+        per prefix length; (smiles, toklen, toklen_gen) in input order."""
+        scaffolds = list(scaffolds)
+        if not scaffolds:
+            raise ValueError("sample_multiple_smiles: no scaffolds")
+        ys0, lens, extras = self._scaffold_prefixes(scaffolds)
+        zs, toklen, src_mask = latent_setup_rows(extras, zs, toklen, self.latent_dim, self.sample_toklen,
+                                                 self.sample_z)
+        n = len(scaffolds)
+        if self.decode_algo == "beam":
+            gens = [None] * n
+            for t0, idx in group_by_length(lens):
+                outs = self.decode(zs[idx], ys0[idx, :t0], src_mask[idx], None if dconds is None else dconds[idx])
+                for i, row in zip(idx.tolist(), outs[:, t0:].cpu()):
+                    gens[i] = row
+        else:
+            outs = self.decode(zs, ys0, src_mask, dconds, prefix_lens=lens)
+            gens = list(generated_tokens(outs, lens).cpu())
+        smiles = [self.id_to_smi(g.numpy()) for g in gens]
+        return smiles, toklen, [len(tokenize(s, self.add_sep)) for s in smiles]
 
     def _finish(self, outs, toklen, skip=0):
         outs = outs.cpu().numpy()
@@ -182,6 +267,11 @@ class ScaVaeSampling(Sampling):
         outs = self.decode(zs, self.init_y(n, True, sca_ids, True), src_mask)
         return self._finish(outs, toklen, skip=1 + len(sca_ids) + 1)
 
+    def sample_multiple_smiles(self, scaffolds, zs=None, toklen=None):
+        """One molecule per scaffold, all rows in one batch: row r decodes as sample_smiles(1, scaffolds[r]) with z
+        row zs[r] and token length toklen[r] would (latent rows len(scaffold tokens) + 1 + toklen[r])."""
+        return self._sample_multiple(scaffolds, zs, toklen, None)
+
 
 class PscavaetfSampling(Sampling):
     def encode_smiles(self, smiles_list, scaffold_list, econds, transform=True):
@@ -197,6 +287,15 @@ class PscavaetfSampling(Sampling):
         zs, toklen, src_mask = self._latent_setup(n, zs, toklen, extra=len(sca_ids) + 1)
         outs = self.decode(zs, self.init_y(n, True, sca_ids, True), src_mask, dconds)
         return self._finish(outs, toklen, skip=1 + len(sca_ids) + 1)
+
+    def sample_multiple_smiles(self, dconds, scaffolds, zs=None, toklen=None, transform=True):
+        """The reference's intended sample_multiple_smiles (sampling_tool.py, commented out there): row r has the
+        properties dconds[r] and the scaffold scaffolds[r]; all rows are one batch and row r decodes as
+        sample_smiles(dconds[r:r+1], scaffolds[r]) would."""
+        if len(dconds) != len(scaffolds):
+            raise ValueError(f"{len(dconds)} property rows for {len(scaffolds)} scaffolds")
+        dconds = self.transform(dconds) if transform else torch.as_tensor(dconds, dtype=torch.float32)
+        return self._sample_multiple(scaffolds, zs, toklen, dconds)
 
 
 sampling_tool_dict = {

@@ -19,14 +19,17 @@ namespace {
 // (row Lc) and scored from registers, so ONE captured graph serves every step of the decode loop.
 // MAPPED (beam search, pos required): key / value j of row b and the valid flag masking it live in physical row
 // kv_src[b][j] (Lc_host = cache rows, the bound of every map entry's position); the step's own key still goes to row b.
-template <int DK, bool MAPPED>
+// RAGGED (pos required, not MAPPED): row b's own position is *pos - row_off[b] (a batch of prefixes of different lengths
+// that share one device counter): Lold = cache_off + *pos - row_off[b], and the step's key is appended at that row.
+template <int DK, bool MAPPED, bool RAGGED>
 __global__ __launch_bounds__(256) void attn_decode_kernel(
     const float* __restrict__ q, int64_t ldq, float* __restrict__ k, float* __restrict__ v,
     int64_t kv_row, int64_t kv_batch, const uint8_t* __restrict__ valid, int64_t valid_sb,
     float* __restrict__ o, int64_t ldo, int n, int H, int Lc_host, float scale,
     const int32_t* __restrict__ pos, int cache_off, const float* __restrict__ knew,
     const float* __restrict__ vnew, int64_t ldn, const int32_t* __restrict__ klen,
-    const int32_t* __restrict__ kv_src, int64_t ld_src) {
+    const int32_t* __restrict__ kv_src, int64_t ld_src, const int32_t* __restrict__ row_off) {
+  static_assert(!(MAPPED && RAGGED), "ragged rows are not supported by the beam (mapped) form");
   __shared__ float sc[4][256];
   __shared__ int32_t rs[4][256];     // MAPPED: physical row of key j
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -36,7 +39,9 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
   // klen (nullable, without pos): the keys of sample b beyond klen[b] are masked (`valid` says so too) and b sees at
   // least one key, so they weigh exactly 0: their cache rows are never read (the padded latent positions of the
   // cross-attention memory are most of it at MOSES-like lengths)
-  const int Lold = pos ? cache_off + *pos : (klen ? klen[b] : Lc_host);          // keys already in the cache
+  int Lold;                                                                        // keys already in the cache
+  if constexpr (RAGGED) Lold = cache_off + *pos - row_off[b];                      // uniform over the wave
+  else Lold = pos ? cache_off + *pos : (klen ? klen[b] : Lc_host);
   const int Lc = pos ? Lold + 1 : Lold;
   const float* qp = q + (int64_t)b * ldq + h * DK;
   float* kp = k + (int64_t)b * kv_batch + h * DK;
@@ -225,15 +230,20 @@ __global__ __launch_bounds__(256) void attn_decode_z_kernel(
 }
 
 // x[b][:] = table[ys[b][*pos]] * scale + pe[pe_off + *pos][:]   (Embeddings + PositionalEncoding of ONE position)
+// RAGGED: row b's position is *pos - row_off[b] (one load per thread; consecutive threads still store consecutive float4)
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void decode_embed_kernel(const int64_t* __restrict__ ys, int64_t ld_ys,
                                                            const int32_t* __restrict__ pos, int pe_off,
                                                            const float* __restrict__ table, int vocab,
                                                            const float* __restrict__ pe, float* __restrict__ out,
-                                                           int n, int d, float scale) {
-  const int p = *pos;
+                                                           int n, int d, float scale,
+                                                           const int32_t* __restrict__ row_off) {
+  const int p0 = *pos;
   const int64_t total = (int64_t)n * (d / 4);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int b = (int)(i / (d / 4)), c = (int)(i - (int64_t)b * (d / 4));
+    int p = p0;
+    if constexpr (RAGGED) p -= row_off[b];
     int64_t tok = ys[(int64_t)b * ld_ys + p];
     tok = tok < 0 ? 0 : (tok >= vocab ? vocab - 1 : tok);
     const float4 e = *reinterpret_cast<const float4*>(table + tok * d + c * 4);
@@ -248,19 +258,24 @@ __global__ void decode_advance_kernel(int32_t* pos) { *pos += 1; }
 __device__ __forceinline__ float u01_open(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
 // one wave per sample row.  pos_dev (nullable): device-side step counter -- the token is written at ys[.., *pos_dev + 1]
-// and valid[.., valid_off + *pos_dev + 1]; seed_dev (nullable) replaces the by-value seed of the multinomial draw
+// and valid[.., valid_off + *pos_dev + 1]; seed_dev (nullable) replaces the by-value seed of the multinomial draw.
+// RAGGED (pos_dev required): row r's position is *pos_dev - row_off[r] + 1 (uniform over the wave; the Philox key stays
+// (row, token position))
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void select_token_kernel(const float* __restrict__ logits, int V,
                                                            int64_t* ys, int64_t ld_ys, int pos_host,
                                                            uint8_t* valid, int64_t valid_sb,
                                                            uint8_t* done, float* probs_out, int n,
                                                            int mode, int64_t pad_id, int64_t eos_id,
                                                            GctRng rng, const int32_t* __restrict__ pos_dev,
-                                                           int valid_off, const uint64_t* __restrict__ seed_dev) {
-  const int pos = pos_dev ? *pos_dev + 1 : pos_host;
+                                                           int valid_off, const uint64_t* __restrict__ seed_dev,
+                                                           const int32_t* __restrict__ row_off) {
+  int pos = pos_dev ? *pos_dev + 1 : pos_host;
   if (seed_dev) rng = gct_rng_make(*seed_dev, 0xDEC0DEu);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = blockIdx.x * 4 + wave;
   if (row >= n) return;
+  if constexpr (RAGGED) pos -= row_off[row];
   const float* lr = logits + (int64_t)row * V;
   float mx = -INFINITY;
   for (int c = lane; c < V; c += 64) mx = fmaxf(mx, lr[c]);
@@ -479,8 +494,10 @@ extern "C" int gct_attn_decode(const float* q, int64_t ldq, float* k, float* v,
                                int64_t kv_row, int64_t kv_batch, const uint8_t* valid,
                                int64_t valid_sb, float* o, int64_t ldo, int n, int H, int Lc, int dk,
                                float scale, const int32_t* pos, int cache_off, const float* knew,
-                               const float* vnew, int64_t ldn, const int32_t* klen, void* stream) {
+                               const float* vnew, int64_t ldn, const int32_t* klen, const int32_t* row_off,
+                               void* stream) {
   GCT_CHECK_ARG(q && k && v && o && n >= 0 && H > 0 && Lc >= 0 && Lc <= 256, "attn_decode: bad args");
+  GCT_CHECK_ARG(!row_off || pos, "attn_decode: row_off needs the device-position form");
   GCT_CHECK_ARG(!(klen && pos), "attn_decode: klen is for a fixed cache (cross-attention), not the device-position form");
   GCT_CHECK_ARG(pos || Lc > 0, "attn_decode: no keys");
   GCT_CHECK_ARG(!pos || (knew && vnew && ldn % 4 == 0 && gct_aligned16(knew) && gct_aligned16(vnew) && cache_off >= 0),
@@ -493,9 +510,16 @@ extern "C" int gct_attn_decode(const float* q, int64_t ldq, float* k, float* v,
   const int64_t pairs = (int64_t)n * H;
   dim3 grid((unsigned)((pairs + 3) / 4)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (dk == 64) hipLaunchKernelGGL((attn_decode_kernel<64, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, klen, nullptr, 0);
-  else if (dk == 32) hipLaunchKernelGGL((attn_decode_kernel<32, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, klen, nullptr, 0);
-  else hipLaunchKernelGGL((attn_decode_kernel<16, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, klen, nullptr, 0);
+  if (row_off) {
+    if (dk == 64) hipLaunchKernelGGL((attn_decode_kernel<64, false, true>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, nullptr, nullptr, 0, row_off);
+    else if (dk == 32) hipLaunchKernelGGL((attn_decode_kernel<32, false, true>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, nullptr, nullptr, 0, row_off);
+    else hipLaunchKernelGGL((attn_decode_kernel<16, false, true>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, nullptr, nullptr, 0, row_off);
+    GCT_LAUNCH_CHECK("attn_decode");
+    return GCT_OK;
+  }
+  if (dk == 64) hipLaunchKernelGGL((attn_decode_kernel<64, false, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, klen, nullptr, 0, nullptr);
+  else if (dk == 32) hipLaunchKernelGGL((attn_decode_kernel<32, false, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, klen, nullptr, 0, nullptr);
+  else hipLaunchKernelGGL((attn_decode_kernel<16, false, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, klen, nullptr, 0, nullptr);
   GCT_LAUNCH_CHECK("attn_decode");
   return GCT_OK;
 }
@@ -530,14 +554,20 @@ extern "C" int gct_attn_decode_z(const float* q, int64_t ldq, int qoff, const fl
 }
 
 extern "C" int gct_decode_embed(const int64_t* ys, int64_t ld_ys, const int32_t* pos, int pe_off, const float* table,
-                                int vocab, const float* pe, float* out, int n, int d, float scale, void* stream) {
+                                int vocab, const float* pe, float* out, int n, int d, float scale,
+                                const int32_t* row_off, void* stream) {
   GCT_CHECK_ARG(ys && pos && table && pe && out && n >= 0 && d > 0 && d % 4 == 0 && vocab > 0 && pe_off >= 0 &&
                     gct_aligned16(table) && gct_aligned16(pe) && gct_aligned16(out),
                 "decode_embed: bad args");
   if (n == 0) return GCT_OK;
   const int64_t work = (int64_t)n * (d / 4);
-  hipLaunchKernelGGL(decode_embed_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ys,
-                     ld_ys, pos, pe_off, table, vocab, pe, out, n, d, scale);
+  const dim3 grid((unsigned)((work + 255) / 256));
+  if (row_off)
+    hipLaunchKernelGGL(decode_embed_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, ys, ld_ys, pos, pe_off, table,
+                       vocab, pe, out, n, d, scale, row_off);
+  else
+    hipLaunchKernelGGL(decode_embed_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, ys, ld_ys, pos, pe_off, table,
+                       vocab, pe, out, n, d, scale, nullptr);
   GCT_LAUNCH_CHECK("decode_embed");
   return GCT_OK;
 }
@@ -552,13 +582,20 @@ extern "C" int gct_decode_advance(int32_t* pos, void* stream) {
 extern "C" int gct_select_token(const float* logits, int V, int64_t* ys, int64_t ld_ys, int pos,
                                 uint8_t* valid, int64_t valid_sb, uint8_t* done, float* probs_out,
                                 int n, int mode, int64_t pad_id, int64_t eos_id, uint64_t seed,
-                                const int32_t* pos_dev, int valid_off, const uint64_t* seed_dev, void* stream) {
+                                const int32_t* pos_dev, int valid_off, const uint64_t* seed_dev,
+                                const int32_t* row_off, void* stream) {
   GCT_CHECK_ARG(logits && ys && V > 0 && n >= 0 && pos >= 0 && (mode == 0 || mode == 1) && valid_off >= 0,
                 "select_token: bad args");
+  GCT_CHECK_ARG(!row_off || pos_dev, "select_token: row_off needs the device position");
   if (n == 0) return GCT_OK;
-  hipLaunchKernelGGL(select_token_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0,
-                     (hipStream_t)stream, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out,
-                     n, mode, pad_id, eos_id, gct_rng_make(seed, 0xDEC0DEu), pos_dev, valid_off, seed_dev);
+  if (row_off)
+    hipLaunchKernelGGL(select_token_kernel<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0,
+                       (hipStream_t)stream, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out,
+                       n, mode, pad_id, eos_id, gct_rng_make(seed, 0xDEC0DEu), pos_dev, valid_off, seed_dev, row_off);
+  else
+    hipLaunchKernelGGL(select_token_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0,
+                       (hipStream_t)stream, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out,
+                       n, mode, pad_id, eos_id, gct_rng_make(seed, 0xDEC0DEu), pos_dev, valid_off, seed_dev, nullptr);
   GCT_LAUNCH_CHECK("select_token");
   return GCT_OK;
 }
@@ -581,9 +618,9 @@ extern "C" int gct_attn_decode_beam(const float* q, int64_t ldq, float* k, float
   const int64_t pairs = (int64_t)n * H;
   dim3 grid((unsigned)((pairs + 3) / 4)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (dk == 64) hipLaunchKernelGGL((attn_decode_kernel<64, true>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, T, scale, pos, cache_off, knew, vnew, ldn, nullptr, kv_src, ld_src);
-  else if (dk == 32) hipLaunchKernelGGL((attn_decode_kernel<32, true>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, T, scale, pos, cache_off, knew, vnew, ldn, nullptr, kv_src, ld_src);
-  else hipLaunchKernelGGL((attn_decode_kernel<16, true>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, T, scale, pos, cache_off, knew, vnew, ldn, nullptr, kv_src, ld_src);
+  if (dk == 64) hipLaunchKernelGGL((attn_decode_kernel<64, true, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, T, scale, pos, cache_off, knew, vnew, ldn, nullptr, kv_src, ld_src, nullptr);
+  else if (dk == 32) hipLaunchKernelGGL((attn_decode_kernel<32, true, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, T, scale, pos, cache_off, knew, vnew, ldn, nullptr, kv_src, ld_src, nullptr);
+  else hipLaunchKernelGGL((attn_decode_kernel<16, true, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, T, scale, pos, cache_off, knew, vnew, ldn, nullptr, kv_src, ld_src, nullptr);
   GCT_LAUNCH_CHECK("attn_decode_beam");
   return GCT_OK;
 }

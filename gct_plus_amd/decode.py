@@ -25,6 +25,12 @@ in `beam_step_reference` / `beam_finalize`; gct_beam_select implements the step 
 caches, ys and valid stay PHYSICAL slots, each written once by the row that owns it, and an int32 map kv_src [n*k, T]
 says where beam r's logical position j lives (row kv_src[r, j]): a selection copies the parent's map row instead of the
 parent's caches (gct_attn_decode_beam reads through it).  Final ids: token t of beam b is ys[kv_src[b, off + t], t].
+
+Mixed prefix lengths (`generate(..., prefix_lens=)`, e.g. one batch of many scaffolds): row r's prefix is ys0[r, :t0_r],
+right-padded to t0_max.  The device counter stays shared (the token index of the longest prefix) and row r reads it
+through its offset row_off[r] = t0_max - t0_r (gct_decode_embed / gct_attn_decode / gct_select_token), so each row keeps
+its own token positions, positional rows, cache slots and multinomial keys (row, token position): it decodes exactly
+what it would decode alone.  Row r's generated tokens start at column t0_r of the output (`generated_tokens`).
 """
 from __future__ import annotations
 
@@ -65,6 +71,32 @@ def check_beam_size(beam_size, vocab):
         raise ValueError(f"beam_size {beam_size} exceeds the vocabulary ({vocab} tokens)")
     if vocab > ops.BEAM_MAX_VOCAB:
         raise ValueError(f"beam search supports vocabularies up to {ops.BEAM_MAX_VOCAB} tokens, not {vocab}")
+
+
+# --------------------------------------------------------------------------------- mixed prefix lengths
+def check_prefix_lens(prefix_lens, n, width):
+    """prefix_lens (ints [n], 1 <= t0_r <= width) as an int64 CPU tensor, or None when every row uses the full width
+    (the uniform path); ValueError otherwise."""
+    if prefix_lens is None:
+        return None
+    lens = torch.as_tensor(prefix_lens)
+    if lens.dtype.is_floating_point or lens.dtype.is_complex or lens.dtype == torch.bool:
+        raise ValueError(f"prefix_lens must hold integers, got {lens.dtype}")
+    lens = lens.to("cpu", torch.int64)
+    if lens.dim() != 1 or lens.numel() != n:
+        raise ValueError(f"prefix_lens must have shape [{n}], got {list(lens.shape)}")
+    if n and (int(lens.min()) < 1 or int(lens.max()) > width):
+        raise ValueError(f"prefix_lens must lie in [1, {width}] (the prefix width), got [{int(lens.min())}, "
+                         f"{int(lens.max())}]")
+    return None if bool((lens == width).all()) else lens
+
+
+def generated_tokens(ys, prefix_lens):
+    """The generated part of a mixed-prefix output ys [n, t0_max + G]: [n, G], row r = ys[r, t0_r : t0_r + G] (pad
+    after the row's last step).  prefix_lens=None: ys[:, t0:] is the caller's slice."""
+    lens = torch.as_tensor(prefix_lens, device=ys.device).long().view(-1, 1)
+    g = ys.shape[1] - int(lens.max())
+    return ys.gather(1, lens + torch.arange(g, device=ys.device).view(1, -1))
 
 
 def beam_init(n, k, device=None):
@@ -217,6 +249,8 @@ class KVDecoder:
             self.src_valid = torch.empty(n, Lk, dtype=torch.uint8, device=dev)
             self.src_klen = torch.empty(n, dtype=torch.int32, device=dev)  # leading memory rows the cross-attention reads
             self.pos = torch.zeros(1, dtype=torch.int32, device=dev)       # token index the next step consumes
+            self.row_off = torch.zeros(n, dtype=torch.int32, device=dev)   # mixed prefixes: row r is at pos - row_off[r]
+            self.ragged = False                                            # this decode passes row_off to the kernels
             self.seed = torch.zeros(1, dtype=torch.int64, device=dev)      # multinomial seed of this generate()
             # beam search state (generate_beam), per row: score, finished, length, parent; the ancestry map; done [n/k]
             self.beams = beams
@@ -320,13 +354,22 @@ class KVDecoder:
 
     # -------------------------------------------------------------------------------------
     @torch.no_grad()
-    def prefill(self, ys0):
+    def prefill(self, ys0, prefix_lens=None):
         """The prefix ys0 [n, t0] (and, with use_cond2dec, the condition tokens in front of it) through one decoder
-        forward; fills the caches for positions < off + t0 and returns the logits of the last prefix position."""
+        forward; fills the caches for positions < off + t0 and returns the logits of the last prefix position.
+        prefix_lens (int64 [n], from check_prefix_lens; None = all t0): row r's prefix is ys0[r, :t0_r]; the columns
+        behind it become pad (invalid cache slots until generation overwrites them), the returned logits are those of
+        position t0_r - 1, and the steps run with row offsets t0 - t0_r."""
         from .Model.modules import get_trg_mask
         dec, d, n = self.dec, self.d, self.n
         t0 = ys0.shape[1]
         ys0 = ys0.to(self.ys.device)
+        self.ragged = prefix_lens is not None
+        if self.ragged:
+            lens = prefix_lens.to(self.ys.device, torch.int64)
+            cols = torch.arange(t0, device=ys0.device).view(1, -1)
+            ys0 = torch.where(cols < lens.view(-1, 1), ys0, torch.full_like(ys0, self.pad_id))
+            self.row_off.copy_(t0 - lens)
         self.ys.fill_(self.pad_id)
         self.ys[:, :t0] = ys0
         self.valid.zero_()
@@ -344,8 +387,9 @@ class KVDecoder:
             self.kc[li][:, :Tp].copy_(qkv[:, :, d:2 * d])
             self.vc[li][:, :Tp].copy_(qkv[:, :, 2 * d:])
         out = self.model.out
-        ops.linear_fwd(y[:, -1].contiguous(), [out.weight], [out.bias], [self.buf["logits"]], out.weight.shape[0])
-        self.pos.fill_(t0 - 1)                                      # "token t0-1 has been consumed"
+        last = y[:, -1] if not self.ragged else y[torch.arange(n, device=y.device), self.off + lens - 1]
+        ops.linear_fwd(last.contiguous(), [out.weight], [out.bias], [self.buf["logits"]], out.weight.shape[0])
+        self.pos.fill_(t0 - 1)                                      # "token t0-1 has been consumed" (row r: t0_r - 1)
         return self.buf["logits"]
 
     # -------------------------------------------------------------------------------------
@@ -356,10 +400,10 @@ class KVDecoder:
         dec, d, n, T, B = self.dec, self.d, self.n, self.T, self.buf
         L = ops._L()
         st = ops._st()
+        row_off = self.row_off if self.ragged and not beam else None        # mixed prefixes: per-row positions
         check(L.gct_decode_advance(self.pos.data_ptr(), st), "gct_decode_advance")   # pos = index of the token consumed now
-        check(L.gct_decode_embed(self.ys.data_ptr(), self.ys.stride(0), self.pos.data_ptr(), self.off,
-                                 dec.embed.embed.weight.data_ptr(), dec.embed.embed.weight.shape[0],
-                                 dec.pe.pe.data_ptr(), B["x"].data_ptr(), n, d, math.sqrt(d), st), "gct_decode_embed")
+        ops.decode_embed(self.ys, self.pos, self.off, dec.embed.embed.weight, dec.pe.pe, B["x"], math.sqrt(d),
+                         row_off=row_off)
         x = B["x"]
         for li, layer in enumerate(dec.layers):
             a1, a2, ff = layer.attn_1, layer.attn_2, layer.ff
@@ -375,7 +419,7 @@ class KVDecoder:
             else:
                 ops.attn_decode(qkv, 3 * d, self.kc[li], self.vc[li], d, T * d, self.valid, T, B["o"], n,
                                 self.H, 0, self.dk, pos=self.pos, cache_off=self.off, knew=qkv[:, d:],
-                                vnew=qkv[:, 2 * d:], ldn=3 * d)
+                                vnew=qkv[:, 2 * d:], ldn=3 * d, row_off=row_off)
             ops.linear_fwd(B["o"], [a1.out.weight], [a1.out.bias], [B["xa"]], d,
                            epi=ops.EPI_DROP_RESID, resid=x, **self.gemm_kw)
             ops.norm_fwd(B["xa"], layer.norm_2.alpha, layer.norm_2.bias, layer.norm_2.eps, out=B["x2"])
@@ -414,7 +458,8 @@ class KVDecoder:
                             parent_i32=self.bparent)
             return
         ops.select_token(self.buf["logits"], self.ys, 0, self.valid, self.done, mode, self.pad_id, self.eos_id,
-                         pos_dev=self.pos, valid_off=self.off, seed_dev=self.seed)
+                         pos_dev=self.pos, valid_off=self.off, seed_dev=self.seed,
+                         row_off=self.row_off if self.ragged else None)
 
     def _advance(self, mode):
         """One step and its selection: the unit a graph captures."""
@@ -423,16 +468,25 @@ class KVDecoder:
 
     # -------------------------------------------------------------------------------------
     @torch.no_grad()
-    def generate(self, ys0, max_strlen=80, algo="greedy", seed=0, check_every=8, use_graphs=False):
+    def generate(self, ys0, max_strlen=80, algo="greedy", seed=0, check_every=8, use_graphs=False, prefix_lens=None):
         """Mirror of Sampling.decode: appends max_strlen-1 tokens to the prefix ys0 [n, t0]
-        (stops early once every sample has produced <eos>, like the reference's break)."""
+        (stops early once every sample has produced <eos>, like the reference's break).
+        prefix_lens (ints [n], 1 <= t0_r <= t0, optional): row r's prefix is ys0[r, :t0_r] (right-padded); it decodes
+        exactly what it would decode alone.  The output is then [n, t0 + G] with row r's G generated tokens at columns
+        t0_r .. t0_r + G - 1 and pad behind them: generated_tokens(ys, prefix_lens) returns them as [n, G].  All lengths
+        equal to t0 (or None): the uniform path."""
         n, t0 = ys0.shape
         steps = max_strlen - 1
+        lens = check_prefix_lens(prefix_lens, n, t0)
+        pe_rows = self.dec.pe.pe.shape[1]
+        if self.off + t0 + steps > pe_rows:
+            raise ValueError(f"prefix {t0} + {steps} steps + {self.off} condition rows exceed the {pe_rows}-row "
+                             "positional table")
         if self.off + t0 + steps > self.T:
             raise ValueError(f"prefix {t0} + {steps} steps exceeds the cache length {self.T - self.off}")
         mode = {"greedy": 0, "multinomial": 1}[algo]
         self.seed.fill_(int(seed) & 0x7FFFFFFFFFFFFFFF)
-        self.prefill(ys0)
+        self.prefill(ys0, lens)
         self._select(mode)                                         # token t0 from the prefill's last position
         last = t0 + steps
         for i in range(1, steps):
@@ -441,7 +495,7 @@ class KVDecoder:
                 last = t0 + i + 1
                 break
         ys = self.ys[:, :last]
-        gen = ys[:, t0:]
+        gen = ys[:, t0:] if lens is None else generated_tokens(ys, lens)
         is_eos = gen == self.eos_id
         if bool(is_eos.any(dim=1).all()):                          # reference break point
             first = torch.where(is_eos, torch.arange(gen.size(1), device=gen.device)[None, :],
@@ -450,11 +504,15 @@ class KVDecoder:
         return ys.clone()
 
     @torch.no_grad()
-    def generate_beam(self, ys0, beam_size, max_strlen=80, alpha=BEAM_ALPHA, check_every=8, use_graphs=False):
+    def generate_beam(self, ys0, beam_size, max_strlen=80, alpha=BEAM_ALPHA, check_every=8, use_graphs=False,
+                      prefix_lens=None):
         """Beam search from the prefix ys0 [n, t0] after start(..., beams=beam_size): up to max_strlen-1 tokens, stops
         early once every beam of every sample has produced <eos> (checked every `check_every` steps).
         Returns (ys [n, k, L] int64, scores [n, k] fp32 sums of log-probabilities, lengths [n, k] int64), beams sorted
-        by score / length**alpha (beam_finalize); pad after each beam's end, L = t0 + the longest beam."""
+        by score / length**alpha (beam_finalize); pad after each beam's end, L = t0 + the longest beam.
+        Mixed prefix lengths are not supported (prefix_lens raises ValueError): decode each length group on its own."""
+        if prefix_lens is not None:
+            raise ValueError("generate_beam: mixed prefix lengths are not supported; run one beam decode per length")
         k = int(beam_size)
         if k != self.beams:
             raise ValueError(f"generate_beam: beam_size {k}, but start() prepared {self.beams} beam(s) per sample")
@@ -489,12 +547,13 @@ class KVDecoder:
         if not use_graphs:
             self._advance(mode)
             return
-        g = self.graphs.get(mode)
+        key = (mode, "mixed") if self.ragged else mode    # a mixed-prefix step passes row_off: a graph of its own
+        g = self.graphs.get(key)
         if g is False:                                  # no usable graph for these buffers (capture failed, or replay is
             self._advance(mode)                         # the slower launch mode on this box): same kernels, eagerly
             return
         if g is None:
-            g = self._capture(mode)
+            g = self._capture(mode, key)
             if g is None:
                 return                                  # _capture ran the step eagerly
         g.replay()
@@ -511,7 +570,7 @@ class KVDecoder:
         return (self.pos, self.ys, self.valid, self.done, self.bscores, self.bfin, self.blen, self.bparent,
                 self.kv_src, self.bdone)
 
-    def _capture(self, mode):
+    def _capture(self, mode, key):
         """Capture step + select into one graph; returns it, or None after running the step eagerly (capture failed, or
         the replay guard found replay slower than eager launches on this box)."""
         # Warm-up run on a side stream (lazy LDS opt-ins, allocator), then capture.  The warm-up really executes a
@@ -539,13 +598,13 @@ class KVDecoder:
             warnings.warn(f"KVDecoder: graph capture failed ({exc}); decoding without graph replay")
             torch.cuda.synchronize()
             self._restore(keep)
-            self.graphs[mode] = False
+            self.graphs[key] = False
             self.graph_replay = False
             self._advance(mode)
             return None
-        self.graphs[mode] = g
+        self.graphs[key] = g
         if REPLAY_GUARD and not self._replay_is_fast(mode, g, keep):
-            self.graphs[mode] = False
+            self.graphs[key] = False
             self.graph_replay = False
             self._advance(mode)
             return None

@@ -902,12 +902,19 @@ def add(a, b, out=None):
 
 
 # ----------------------------------------------------------------------------------- decode
+def _check_row_off(row_off, n):
+    if row_off is not None and (row_off.dtype != torch.int32 or row_off.numel() < n or not row_off.is_contiguous()):
+        raise ValueError("row_off must be a contiguous int32 tensor with one offset per row")
+
+
 def attn_decode(q, ldq, k, v, kv_row, kv_batch, valid_u8, valid_sb, out, n, H, Lc, dk, pos=None, cache_off=0,
-                knew=None, vnew=None, ldn=0, klen=None):
-    """klen (int32 [n], optional, fixed caches only): leading keys to look at per sample (the rest are masked)."""
+                knew=None, vnew=None, ldn=0, klen=None, row_off=None):
+    """klen (int32 [n], optional, fixed caches only): leading keys to look at per sample (the rest are masked).
+    row_off (int32 [n], optional, with pos only): row b sits at position *pos - row_off[b] (mixed prefix lengths)."""
+    _check_row_off(row_off, n)
     check(_L().gct_attn_decode(_p(q), ldq, _p(k), _p(v), kv_row, kv_batch, _p(valid_u8), valid_sb,
                                _p(out), out.stride(0), n, H, Lc, dk, 1.0 / math.sqrt(dk), _p(pos), cache_off,
-                               _p(knew), _p(vnew), ldn, _p(klen), _st()), "gct_attn_decode")
+                               _p(knew), _p(vnew), ldn, _p(klen), _p(row_off), _st()), "gct_attn_decode")
 
 
 def attn_decode_z(q, qoff, z, ckv, nc, valid_u8, out, ooff, n, H, dk, klen=None):
@@ -923,12 +930,22 @@ def attn_decode_z(q, qoff, z, ckv, nc, valid_u8, out, ooff, n, H, dk, klen=None)
 
 
 def select_token(logits2d, ys, pos, valid_u8, done_u8, mode, pad_id, eos_id, seed=0, probs_out=None, pos_dev=None,
-                 valid_off=0, seed_dev=None):
+                 valid_off=0, seed_dev=None, row_off=None):
+    """row_off (int32 [n], optional, with pos_dev only): row r writes at *pos_dev - row_off[r] + 1."""
     n, V = logits2d.shape
+    _check_row_off(row_off, n)
     check(_L().gct_select_token(_p(logits2d), V, _p(ys), ys.stride(0), pos, _p(valid_u8),
                                 valid_u8.stride(0) if valid_u8 is not None else 0, _p(done_u8),
                                 _p(probs_out), n, mode, pad_id, eos_id, seed, _p(pos_dev), valid_off, _p(seed_dev),
-                                _st()), "gct_select_token")
+                                _p(row_off), _st()), "gct_select_token")
+
+
+def decode_embed(ys, pos, pe_off, table, pe, out, scale, row_off=None):
+    """gct_decode_embed: out[b] = table[ys[b, p]] * scale + pe[pe_off + p], p = *pos (- row_off[b])."""
+    n, d = out.shape
+    _check_row_off(row_off, n)
+    check(_L().gct_decode_embed(_p(ys), ys.stride(0), _p(pos), pe_off, _p(table), table.shape[0], _p(pe), _p(out), n, d,
+                                scale, _p(row_off), _st()), "gct_decode_embed")
 
 
 BEAM_MAX_K, BEAM_MAX_VOCAB = 16, 65536          # GCT_BEAM_MAX_K / GCT_BEAM_MAX_VOCAB (include/gctplus_hip.h)

@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 16
+#define GCT_ABI_VERSION 17
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -372,11 +372,16 @@ int gct_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t 
  * serves every step of the loop (gct_decode_embed / gct_select_token read the same counter, gct_decode_advance
  * increments it at the end of the step).  With pos == NULL the first Lc cached keys are used as they are.
  * klen (nullable, only with pos == NULL): per-sample number of leading keys to look at -- for a key-padding mask
- * whose visible keys are a non-empty prefix, the masked rows behind it weigh exactly 0 and are not read. */
+ * whose visible keys are a non-empty prefix, the masked rows behind it weigh exactly 0 and are not read.
+ * row_off (nullable, only with pos): int32 [n], per-row position offset of a batch of prefixes of different lengths
+ * that share one device counter -- row b's position is *pos - row_off[b] (>= 0): the caches of row b hold
+ * cache_off + *pos - row_off[b] keys and this step's key is appended there.  gct_decode_embed and gct_select_token
+ * take the same offsets.  NULL: every row is at *pos (the kernel of ABI 16). */
 int gct_attn_decode(const float* q, int64_t ldq, float* k, float* v, int64_t kv_row,
                     int64_t kv_batch, const uint8_t* valid, int64_t valid_sb, float* o, int64_t ldo,
                     int n, int H, int Lc, int dk, float scale, const int32_t* pos, int cache_off,
-                    const float* knew, const float* vnew, int64_t ldn, const int32_t* klen, void* stream);
+                    const float* knew, const float* vnew, int64_t ldn, const int32_t* klen,
+                    const int32_t* row_off, void* stream);
 /* gct_attn_decode_z: the cross-attention of a decode step (Model/layers.py:73-76 attn_2 over e_outputs = fc_z(z),
  * Model/vaetf.py:75-95) computed over the LATENT rows themselves.  k_{j,h} = G_h z_j + c_h and v_{j,h} = H_h z_j + d_h
  * with G_h = W_k,h W_z, H_h = W_v,h W_z, so score_{j,h} = (G_h^T q_h) . z_j + (a term equal for all keys of the row)
@@ -393,18 +398,22 @@ int gct_attn_decode_z(const float* q, int64_t ldq, int qoff, const float* z, int
                       const float* ckv, int64_t ckv_batch, int64_t ld_ckv, int nc, const uint8_t* valid,
                       int64_t valid_sb, const int32_t* klen, float* out, int64_t ldo, int ooff, int n, int H, int dk,
                       float scale, void* stream);
-/* x[b] = table[ys[b][*pos]] * scale + pe[pe_off + *pos] (Embeddings + PositionalEncoding of one position, eval mode) */
+/* x[b] = table[ys[b][p]] * scale + pe[pe_off + p] with p = *pos - (row_off ? row_off[b] : 0) (Embeddings +
+ * PositionalEncoding of one position, eval mode; row_off as in gct_attn_decode) */
 int gct_decode_embed(const int64_t* ys, int64_t ld_ys, const int32_t* pos, int pe_off, const float* table,
-                     int vocab, const float* pe, float* out, int n, int d, float scale, void* stream);
+                     int vocab, const float* pe, float* out, int n, int d, float scale, const int32_t* row_off,
+                     void* stream);
 int gct_decode_advance(int32_t* pos, void* stream);
 /* softmax(logits[n][V]) then mode 0: argmax (first maximum, torch.max semantics) / mode 1:
  * multinomial (Philox inverse-CDF).  Writes ys[row*ld_ys + pos], valid[row*valid_sb + valid_off + pos] =
  * (token != pad), done[row] |= (token == eos); probs_out (nullable) [n][V].  pos_dev (nullable): pos = *pos_dev + 1;
- * seed_dev (nullable): the multinomial seed is read from device memory (graph replays with a fresh seed). */
+ * seed_dev (nullable): the multinomial seed is read from device memory (graph replays with a fresh seed).
+ * row_off (nullable, only with pos_dev; as in gct_attn_decode): row r writes at pos = *pos_dev - row_off[r] + 1, and
+ * its multinomial draw is keyed by (r, that pos). */
 int gct_select_token(const float* logits, int V, int64_t* ys, int64_t ld_ys, int pos, uint8_t* valid,
                      int64_t valid_sb, uint8_t* done, float* probs_out, int n, int mode,
                      int64_t pad_id, int64_t eos_id, uint64_t seed, const int32_t* pos_dev, int valid_off,
-                     const uint64_t* seed_dev, void* stream);
+                     const uint64_t* seed_dev, const int32_t* row_off, void* stream);
 
 /* Beam search (gct_plus_amd/decode.py beam_step_reference states the rules).  Sample s owns the k rows
  * s*k .. s*k+k-1 of an n*k-row decode.  The self-attention caches, ys and valid are PHYSICAL slots, each written once:

@@ -2,7 +2,12 @@
 """Decoded SMILES/s (BASELINE config 5 shape: pscavaetf-style decode, batch 512, max_strlen 80):
 KV-cached decode (eager and graph replay) vs the reference-style full re-run loop.
 --beam K: beam search of n samples x K beams against greedy decode of the same n*K rows (ms per token step, SMILES/s),
-ids checked against reference_style_beam_decode on the first --ref-n samples."""
+ids checked against reference_style_beam_decode on the first --ref-n samples.
+--scaffolds K [--per-scaffold M]: K scaffold prefixes (<sos> scaffold <sep>, 3..30 tokens) x M rows each, greedy with
+graph replay, decoded SMILES/s of three schedules of the same rows: one batch per scaffold (chunks of <= 512 rows, the
+reference's per-scaffold sampling loop), one batch per prefix length (host-side grouping), and ONE mixed-prefix batch
+(KVDecoder.generate(prefix_lens=)); plus a uniform-prefix batch of the same n at the mean prefix length for scale.  The
+mixed batch's ids are checked against the per-length runs first."""
 import argparse
 import os
 import sys
@@ -22,6 +27,8 @@ ap.add_argument("--ref-n", type=int, default=64, help="batch for the (slow) refe
 ap.add_argument("--ragged", action="store_true", help="latent length 80 with MOSES-like valid lengths N(35,8) (padded "
                 "memory, as Inference/*_sampling.py batches it) instead of 40 fully valid positions")
 ap.add_argument("--beam", type=int, default=0, help="beam search with K beams per sample (see the docstring)")
+ap.add_argument("--scaffolds", type=int, default=0, help="mixed-scaffold schedules over K scaffolds (see the docstring)")
+ap.add_argument("--per-scaffold", type=int, default=64, help="rows per scaffold with --scaffolds")
 a = ap.parse_args()
 mtype = a.model_type
 vs, vt = synthetic.vocab_sizes(mtype)
@@ -47,6 +54,64 @@ def timed(run):
     torch.cuda.synchronize()
     return out, time.perf_counter() - t0
 
+
+if a.scaffolds:
+    from gct_plus_amd.decode import generated_tokens
+    K, M = a.scaffolds, a.per_scaffold
+    n = K * M
+    g = torch.Generator().manual_seed(5)
+    t0s = torch.randint(3, 31, (K,), generator=g)                          # prefix lengths <sos> + scaffold + <sep>
+    pres = [torch.cat([torch.tensor([synthetic.SOS_ID]), torch.randint(5, 30, (int(t) - 2,), generator=g),
+                       torch.tensor([4])]) for t in t0s]
+    lens = t0s.repeat_interleave(M)                                          # rows scaffold-major
+    ys0 = torch.full((n, int(t0s.max())), synthetic.PAD_ID, dtype=torch.long)
+    for r in range(n):
+        ys0[r, :int(lens[r])] = pres[r // M]
+    ys0 = ys0.cuda()
+    z = torch.randn(n, Le, 128, generator=g).cuda()
+    dconds = torch.randn(n, nc, generator=g).cuda() if nc else None
+    src_mask = torch.ones(n, 1, Le, dtype=torch.bool, device="cuda")
+    sub = lambda x, i: None if x is None else x[i]                           # noqa: E731
+    decs = {}
+
+    def run_batches(name, batches):
+        """batches: [(row idx, prefix length)]; one KVDecoder per schedule, greedy, graph replay, all 79 steps."""
+        kd = decs.setdefault(name, KVDecoder(model, synthetic.PAD_ID, synthetic.SOS_ID, eos_id=-1))
+        gen = torch.empty(n, 79, dtype=torch.long, device="cuda")
+        for idx, t0 in batches:
+            kd.start(z[idx], src_mask[idx], sub(dconds, idx), max_total_len=112)
+            ys = kd.generate(ys0[idx, :t0], 80, use_graphs=True, check_every=0)
+            gen[idx] = ys[:, t0:]
+        return gen
+
+    def run_mixed():
+        kd = decs.setdefault("mixed", KVDecoder(model, synthetic.PAD_ID, synthetic.SOS_ID, eos_id=-1))
+        kd.start(z, src_mask, dconds, max_total_len=112)
+        return generated_tokens(kd.generate(ys0, 80, use_graphs=True, check_every=0, prefix_lens=lens), lens)
+
+    rows = torch.arange(n, device="cuda")
+    per_sca = [(rows[s * M + c:s * M + min(c + 512, M)], int(t0s[s])) for s in range(K) for c in range(0, M, 512)]
+    per_len = [(rows[(lens == t).cuda()], int(t)) for t in torch.unique(lens).tolist()]
+    tu = int(round(float(lens.float().mean())))
+    uniform = [(rows, tu)]
+    print(f"{K} scaffolds x {M} rows = {n} rows, prefix lengths {int(t0s.min())}..{int(t0s.max())} "
+          f"(mean {float(lens.float().mean()):.1f}), {len(per_sca)} per-scaffold batches, {len(per_len)} length groups",
+          flush=True)
+    g_len = run_batches("per_length", per_len)
+    g_mix = run_mixed()
+    same = (g_len == g_mix).all(1)
+    print(f"mixed batch ids equal to the per-length runs: {int(same.sum())}/{n} rows", flush=True)
+    res = {}
+    for name, fn in (("per_scaffold", lambda: run_batches("per_scaffold", per_sca)),
+                     ("per_length", lambda: run_batches("per_length", per_len)),
+                     ("mixed", run_mixed),
+                     (f"uniform_t0={tu}", lambda: run_batches("uniform", uniform))):
+        _, dt = timed(fn)
+        res[name] = n / dt
+        print(f"{name:>16}: {dt * 1e3:8.1f} ms -> {n / dt:7.0f} SMILES/s", flush=True)
+    print(f"mixed / uniform {res['mixed'] / res[f'uniform_t0={tu}']:.3f}, mixed / per-scaffold "
+          f"{res['mixed'] / res['per_scaffold']:.2f}x, mixed / per-length {res['mixed'] / res['per_length']:.2f}x")
+    sys.exit(0 if bool(same.all()) else 1)
 
 if a.beam:
     k = a.beam
