@@ -19,10 +19,17 @@ fp32, synthetic MOSES-shaped token batches resident in HBM before the timed regi
 (--model-type scavaetf --gpus 8 is configs[3]: global batch 4096).
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the forward GEMM: the bf16x6
 kernel by default, the fp32-MFMA kernel under GCT_GEMM_MODE=f32) timed live with HIP events on its
-launch stream inside the timed region; `fixed_len_80` is the same step on a batch without padding
-(every sample 80 tokens: the worst case, none of the zero-row shortcuts apply); `decode` is
-BASELINE configs[4]'s metric (KV-cached greedy decode of pscavaetf, decoded SMILES/s, at n = 4096 and n = 512); `cpu_baseline` times the
-CPU oracle (port of the reference step) on the host cores at N=1.
+launch stream inside the timed region.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.
+--full then runs everything else the line can carry, after the timed steps: `fixed_len_80` is the same step
+on a batch without padding (every sample 80 tokens: the worst case, none of the zero-row shortcuts apply),
+`every_decoder_row` the step without the row skipping, `same_step_fp32_mfma_gemms` the step on the fp32
+MFMA pipe, `trainer_loop` and `model_types` the trainer's own loop and the other model types (N=1, or
+--all-legs), `decode` BASELINE configs[4]'s metric (KV-cached greedy decode of pscavaetf, decoded
+SMILES/s, at n = 4096 and n = 512), `multi_rank` the report of an N > 1 run, `box` the device's
+calibration figure, and `cpu_baseline` times the CPU oracle (port of the reference step) on the host
+cores at N=1.  The --no-* switches drop single legs of a --full run.
 
 --selftest-cpu swaps the HIP model for a few-kB plain-torch stand-in on the CPU so that THIS file's
 launcher, rendezvous, sharding, step loop, fences, max-over-ranks timing and JSON line can be
@@ -58,6 +65,9 @@ def parse_args(argv=None):
     ap.add_argument("--fixed-len", action="store_true", help="headline region on unpadded (all 80-token) batches")
     ap.add_argument("--dense-decoder", action="store_true",
                     help="compute every decoder row in the forward pass (the trainer skips the rows of padded targets)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every further leg and check of the line (see the docstring); "
+                         "without it the run measures the headline step only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--all-kernel-timing", action="store_true")
@@ -737,15 +747,16 @@ def worker(a):
         prof, ops.PROFILE = ops.PROFILE, None
     final_loss = float(last.item()) / a.batch
     nxt = a.warmup + a.steps
+    # everything below up to the line itself runs under --full only: a plain run stops at the headline
     multi = None
-    if world > 1:
+    if world > 1 and a.full:
         multi = multi_rank_report(a, dpm, inner, host, ops, dev, world, rank, cpu, step, region, nxt)
         nxt += 8
 
     # the same step on batches WITHOUT padding (every sample 80 tokens): none of the data-dependent
     # shortcuts (zero-gradient query tiles, zero rows of the decoder backward) can apply
     fixed = None
-    if not cpu and not a.no_fixed_len_leg and not a.fixed_len:
+    if a.full and not cpu and not a.no_fixed_len_leg and not a.fixed_len:
         state["pool"] = make_pool(True)
         k2 = max(3, a.steps // 3)
         for i in range(2):
@@ -759,7 +770,7 @@ def worker(a):
     # the same step on the headline batches with EVERY decoder row computed in the forward pass (the reference's
     # forward: logits for padded target positions too, which its ignore_index loss then drops)
     dense = None
-    if not cpu and not a.no_fixed_len_leg and not a.dense_decoder and not a.fixed_len:
+    if a.full and not cpu and not a.no_fixed_len_leg and not a.dense_decoder and not a.fixed_len:
         a.dense_decoder = True                    # fwd_loss reads the switch at every call
         k2 = max(3, a.steps // 3)
         for i in range(2):
@@ -773,7 +784,7 @@ def worker(a):
     # the same step with the GEMMs on the fp32 MFMA pipe (v_mfma_f32_32x32x2_f32), for reference: a short
     # further timed region (every rank runs it, so the collectives stay matched)
     alt = None
-    if not cpu and main_mode == ops.GEMM_BF16X6 and not a.no_alt_mode:
+    if a.full and not cpu and main_mode == ops.GEMM_BF16X6 and not a.no_alt_mode:
         ops.gemm_set_mode(ops.GEMM_F32)
         k2 = max(3, a.steps // 3)
         for i in range(2):
@@ -789,7 +800,7 @@ def worker(a):
     # (Bashscript/train/train_vaetf.sh:10-18, train_scavaetf.sh:10-20), against the bare step of this file on the same
     # batches; and once behind the tokenizer + collate loader on synthetic SMILES strings
     tloop = None
-    side_legs = world == 1 or a.all_legs
+    side_legs = a.full and (world == 1 or a.all_legs)
     if not cpu and not a.no_trainer_loop and not a.tiny and side_legs:
         tloop = trainer_loop_legs(a, inner, opt, state, step, region, fence, reduce_max, make_pool, dev, world, rank, nxt)
         nxt += 4000
@@ -825,7 +836,7 @@ def worker(a):
                           "scavaetf = the per-GPU point of configs[3]")
 
     dec = None
-    if not cpu and not a.no_decode and not a.tiny:
+    if a.full and not cpu and not a.no_decode and not a.tiny:
         dec = decode_block(inner, a, dev, world, fence, reduce_max)
 
     if rank == 0:
@@ -874,18 +885,19 @@ def worker(a):
             }
             if dumped is not None:
                 out["dumped_outputs"] = dumped
-            try:                                       # which box is this: the matrix rate it sustains (diagnostics library)
-                from gct_plus_amd import graphdiag
-                out["box"] = graphdiag.mfma_probe()
-            except Exception as exc:                   # noqa: BLE001 -- calibration only, never a reason to lose the line
-                out["box"] = {"error": repr(exc)}
+            if a.full:
+                try:                                   # which box is this: the matrix rate it sustains (diagnostics library)
+                    from gct_plus_amd import graphdiag
+                    out["box"] = graphdiag.mfma_probe()
+                except Exception as exc:               # noqa: BLE001 -- calibration only, never a reason to lose the line
+                    out["box"] = {"error": repr(exc)}
             if not a.dense_decoder:
                 out["rows_not_computed"] = (
                     "as Train/trainer1.run_epoch runs it: decoder rows whose target is <pad> (ignore_index in the loss) "
                     "and K/V of padded memory / source rows are not computed; loss, every gradient and the updated "
                     "parameters equal the dense step's (tests/test_model_gpu.py::test_full_size_batch_512_skip_ignored_"
-                    "vs_oracle); `every_decoder_row` and `fixed_len_80` are the same step without the shortcut / on "
-                    "batches where none applies")
+                    "vs_oracle); `every_decoder_row` and `fixed_len_80` (with --full) are the same step without the "
+                    "shortcut / on batches where none applies")
             if dense is not None:
                 out["every_decoder_row"] = dense
             if fixed is not None:
@@ -903,7 +915,7 @@ def worker(a):
                 out["trainer_loop"] = tloop
             if dec is not None:
                 out["decode"] = dec
-            if world == 1 and not a.no_cpu_baseline and not a.tiny:
+            if a.full and world == 1 and not a.no_cpu_baseline and not a.tiny:
                 out["cpu_baseline"] = cpu_baseline()
             print(json.dumps(out), flush=True)
     if world > 1:

@@ -27,7 +27,7 @@ def _run(args, timeout=600):
 @pytest.mark.parametrize("mtype", ["vaetf", "scavaetf"])
 def test_plain_gpus2_spawns_two_ranks_cpu(mtype):
     out = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--batch", "8", "--model-type", mtype,
-                "--selftest-cpu"])
+                "--selftest-cpu", "--full"])
     assert out["n_gpus"] == 2 and out["ranks"] == 2 and out["launcher"] == "self-spawn"
     assert out["backend"] == "gloo" and out["steps"] == 4 and out["warmup"] == 1
     assert out["config"]["global_batch"] == 16 and out["config"]["parallelism"] == "dp2"
@@ -46,6 +46,17 @@ def test_plain_gpus2_spawns_two_ranks_cpu(mtype):
     assert ex["exposed_wait_ms_median"] is not None and mr["exposed_wait_ms_max_over_ranks"] >= 0
     assert len(mr["host_ms_per_step"]) == 2 and all(h > 0 for h in mr["host_ms_per_step"])
     assert mr["same_step_overlap_off"]["ms_per_step"] > 0
+
+
+# what the line carries only under --full (every further leg and check after the timed steps)
+FULL_ONLY = {"fixed_len_80", "every_decoder_row", "same_step_fp32_mfma_gemms", "trainer_loop", "model_types", "decode",
+             "multi_rank", "box", "cpu_baseline"}
+
+
+def test_plain_gpus2_carries_the_headline_only_cpu():
+    out = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--selftest-cpu"])
+    assert out["ranks"] == 2 and out["steps"] == 2 and out["ms_per_step"] > 0
+    assert not FULL_ONLY & set(out)
 
 
 def test_single_rank_cpu_selftest_and_world_mismatch():
@@ -106,9 +117,17 @@ def test_dump_outputs_real_model(tmp_path):
 
 
 @pytest.mark.gpu
+def test_plain_run_real_model_carries_the_headline_only():
+    out = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8", "--tiny"], timeout=900)
+    assert out["metric"].startswith("SMILES/sec training step (vaetf") and out["steps"] == 2 and out["ms_per_step"] > 0
+    assert "roofline" in out and "host" in out
+    assert not FULL_ONLY & set(out)
+
+
+@pytest.mark.gpu
 def test_plain_gpus2_real_model_shared_gpu():
     out = _run(["--gpus", "2", "--steps", "3", "--warmup", "2", "--batch", "8", "--model-type", "scavaetf",
-                "--tiny", "--share-gpu", "--no-alt-mode"], timeout=900)
+                "--tiny", "--share-gpu", "--no-alt-mode", "--full"], timeout=900)
     assert out["ranks"] == 2 and out["launcher"] == "self-spawn" and out["n_gpus"] == 2
     assert out["metric"].startswith("SMILES/sec training step (scavaetf")
     assert out["roofline"] is None or "kernel" in out["roofline"]
