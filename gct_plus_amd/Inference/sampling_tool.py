@@ -11,7 +11,11 @@ Deliberate deviations, none in the arithmetic:
     Inference/toklen_sampling.py:19-36, with numpy's Generator instead of the global RNG;
   * decode_algo="beam" (the reference's -decode_algo choice, whose Inference/generate_mols.py code does not run) is
     beam search with frozen finished beams and a length-normalised final ranking (gct_plus_amd.decode): `decode`
-    returns the best beam, `decode_beams` all of them.
+    returns the best beam, `decode_beams` all of them;
+  * `top_k` (the reference's -top_k) takes effect: the reference's per-model-type constructors never forward it, so there
+    the flag is ignored.  Next to it, `top_p` (nucleus) and `temperature`; the rules are decode.sample_filter_reference,
+    applied on the device between the softmax and the draw.  Greedy ignores all three (the top token is always kept);
+    beam search does not take them.
 
 `sample_multiple_smiles` (scaffold models) is the reference's commented-out PscavaetfSampling.sample_multiple_smiles,
 one scaffold per row: the prefixes <sos> scaffold <sep> of different lengths are right-padded into ONE batch and decoded
@@ -28,7 +32,7 @@ import torch
 
 from ..Model.modules import get_src_mask
 from ..data import Vocab, tokenize
-from ..decode import BEAM_ALPHA, KVDecoder, check_beam_size, generated_tokens
+from ..decode import BEAM_ALPHA, KVDecoder, check_beam_size, check_sample_filter, generated_tokens
 
 
 def sample_token_lengths(data: Sequence[int], size: int, rng: np.random.Generator) -> np.ndarray:
@@ -97,9 +101,14 @@ class Sampling:
     def __init__(self, model, SRC: Vocab, TRG: Vocab, latent_dim: int, max_strlen: int = 80,
                  cond_dim: int = 0, decode_algo: str = "greedy", toklen_data: Optional[Sequence[int]] = None,
                  scaler=None, device="cuda", seed: int = 0, use_graphs: bool = False, beam_size: int = 4,
-                 beam_alpha: float = BEAM_ALPHA):
+                 beam_alpha: float = BEAM_ALPHA, top_k: Optional[int] = None, top_p: Optional[float] = None,
+                 temperature: float = 1.0):
+        V = model.out.weight.shape[0]
+        if check_sample_filter(top_k, top_p, temperature, V) and decode_algo == "beam":
+            raise ValueError("top_k / top_p / temperature are not supported with decode_algo='beam'")
         if decode_algo == "beam":
-            check_beam_size(beam_size, model.out.weight.shape[0])
+            check_beam_size(beam_size, V)
+        self.top_k, self.top_p, self.temperature = top_k, top_p, temperature
         self.beam_size, self.beam_alpha = beam_size, float(beam_alpha)
         self.model, self.SRC, self.TRG = model.eval(), SRC, TRG
         self.pad_id, self.sos_id, self.eos_id = SRC.stoi["<pad>"], TRG.stoi["<sos>"], TRG.stoi["<eos>"]
@@ -153,7 +162,8 @@ class Sampling:
     @torch.no_grad()
     def decode(self, zs, ys, src_mask, dconds=None, prefix_lens=None):
         """ids [n, L] (prefix included); with decode_algo="beam" the best beam of each sample.
-        prefix_lens (ints [n], optional): row r's prefix is ys[r, :t0_r] (KVDecoder.generate); not with beam search."""
+        prefix_lens (ints [n], optional): row r's prefix is ys[r, :t0_r] (KVDecoder.generate); not with beam search.
+        The sampler's top_k / top_p / temperature apply to every draw (sample_smiles, sample_multiple_smiles)."""
         if self.decode_algo == "beam":
             if prefix_lens is not None:
                 raise ValueError("decode: beam search takes prefixes of one length (see sample_multiple_smiles)")
@@ -165,7 +175,8 @@ class Sampling:
         # the positional table has 200 rows, of which use_cond2dec spends n_c on the condition tokens
         self.kv.start(zs, src_mask, dconds, max_total_len=min(200 - self.kv.off, total))
         return self.kv.generate(ys, self.max_strlen, algo=self.decode_algo, seed=self.seed,
-                                use_graphs=self.use_graphs, prefix_lens=prefix_lens)
+                                use_graphs=self.use_graphs, prefix_lens=prefix_lens, top_k=self.top_k,
+                                top_p=self.top_p, temperature=self.temperature)
 
     @torch.no_grad()
     def decode_beams(self, zs, ys, src_mask, dconds=None, beam_size=None, alpha=None):

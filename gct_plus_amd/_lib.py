@@ -73,7 +73,7 @@ SIGNATURES = {
     "gct_attn_decode_z": (I32, [P, I64, I32, P, I64, I32, I32, P, I64, I64, I32, P, I64, P, P, I64, I32, I32, I32, I32, F32, P]),
     "gct_decode_embed": (I32, [P, I64, P, I32, P, I32, P, P, I32, I32, F32, P, P]),
     "gct_decode_advance": (I32, [P, P]),
-    "gct_select_token": (I32, [P, I32, P, I64, I32, P, I64, P, P, I32, I32, I64, I64, U64, P, I32, P, P, P]),
+    "gct_select_token": (I32, [P, I32, P, I64, I32, P, I64, P, P, I32, I32, I64, I64, U64, P, I32, P, P, P, P]),
     "gct_attn_decode_beam": (I32, [P, I64, P, P, I64, I64, P, I64, P, I64, I32, I32, I32, I32, F32, P, I32, P, P, I64,
                                    P, I64, P]),
     "gct_beam_select": (I32, [P, I32, I32, I32, P, P, P, P, P, I64, P, I64, I32, P, I64, I32, P, P, I64, I64, P]),
@@ -92,7 +92,7 @@ SIGNATURES = {
     "gct_add": (I32, [P, P, P, I64, P]),
 }
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 _lib = None
 
 

@@ -1,8 +1,9 @@
 // KV-cached autoregressive decode helpers (reference
 // Inference/sampling_tool.py:140-184 re-runs the WHOLE decoder on ys[:, :i+1] every step).
 //   gct_attn_decode  : one query row per (sample, head) against cached keys/values
-//   gct_select_token : softmax over the vocabulary + greedy / multinomial choice, appends the
-//                      token, updates the key-valid flags and the per-sample finished mask
+//   gct_select_token : softmax over the vocabulary + greedy / multinomial choice (optionally through a top-k /
+//                      nucleus / temperature filter), appends the token, updates the key-valid flags and the
+//                      per-sample finished mask
 //   gct_attn_decode_beam / gct_beam_select : the same two for beam search, with the self-attention caches
 //                      shared by ancestry through a per-row map (kv_src) instead of copied
 // Both are tiny and HBM/latency-bound; they exist so a whole decode step is a fixed kernel
@@ -335,6 +336,166 @@ __global__ __launch_bounds__(256) void select_token_kernel(const float* __restri
   }
 }
 
+// ---------------------------------------------------------------------------------------------- filtered sampling
+// The multinomial draw of select_token_kernel with top-k / nucleus / temperature between the softmax and the inverse CDF
+// (semantics: decode.py sample_filter_reference).  Settings come from device memory (*filt), so one captured graph serves
+// any settings.  One wave per row; lane l holds tokens l + 64 t, t < TPL.  Both filters are "count / mass of the tokens
+// with a strictly larger value" per token: TPL == 1 (V <= 64) reads the other tokens with readlane, TPL > 1 stages the
+// row in LDS (broadcast reads).  A row the filter leaves unchanged (no token out of the top k or the nucleus) draws with
+// the plain kernel's arithmetic -- same softmax, same scan, uniform not rescaled -- so at T = 1 it picks the same token.
+template <bool RAGGED, int TPL>
+__global__ __launch_bounds__(256) void select_token_filtered_kernel(
+    const float* __restrict__ logits, int V, int64_t* ys, int64_t ld_ys, int pos_host, uint8_t* valid, int64_t valid_sb,
+    uint8_t* done, float* probs_out, int n, int64_t pad_id, int64_t eos_id, GctRng rng,
+    const int32_t* __restrict__ pos_dev, int valid_off, const uint64_t* __restrict__ seed_dev,
+    const int32_t* __restrict__ row_off, const GctSampleFilter* __restrict__ filt) {
+#pragma clang fp contract(off)
+  __shared__ __attribute__((aligned(16))) float stage[4][TPL > 1 ? TPL * 64 : 4];
+  int pos = pos_dev ? *pos_dev + 1 : pos_host;
+  if (seed_dev) rng = gct_rng_make(*seed_dev, 0xDEC0DEu);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= n) return;
+  if constexpr (RAGGED) pos -= row_off[row];
+  const int top_k = filt->k;
+  const float top_p = filt->top_p, inv_temp = filt->inv_temp;
+  const float* lr = logits + (int64_t)row * V;
+  float x[TPL], w[TPL];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int t = 0; t < TPL; ++t) {
+    const int c = lane + 64 * t;
+    x[t] = c < V ? lr[c] : -INFINITY;
+    mx = fmaxf(mx, x[t]);
+  }
+  mx = gct_wave_max(mx);
+  float se = 0.f;
+#pragma unroll
+  for (int t = 0; t < TPL; ++t) {
+    w[t] = lane + 64 * t < V ? expf((x[t] - mx) * inv_temp) : 0.f;
+    se += w[t];
+  }
+  se = gct_wave_sum(se);
+  const float inv = 1.0f / se;
+#pragma unroll
+  for (int t = 0; t < TPL; ++t) w[t] *= inv;                 // p = softmax(x / T), 0 beyond V
+  bool changed = false;
+  const int Vr = (V + 3) & ~3;                              // LDS reads: float4, padded with values that never count
+  if (top_k < V) {                                          // top-k: in iff fewer than k logits are strictly larger
+    int cnt[TPL];
+#pragma unroll
+    for (int t = 0; t < TPL; ++t) cnt[t] = 0;
+    if constexpr (TPL == 1) {
+      for (int j = 0; j < V; ++j) cnt[0] += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[0]), j)) > x[0];
+    } else {
+#pragma unroll
+      for (int t = 0; t < TPL; ++t) stage[wave][lane + 64 * t] = x[t];
+      __builtin_amdgcn_s_waitcnt(0xC07F);
+      __builtin_amdgcn_wave_barrier();
+      for (int j = 0; j < Vr; j += 4) {
+        const float4 q = *reinterpret_cast<const float4*>(&stage[wave][j]);
+#pragma unroll
+        for (int t = 0; t < TPL; ++t) cnt[t] += (q.x > x[t]) + (q.y > x[t]) + (q.z > x[t]) + (q.w > x[t]);
+      }
+      __builtin_amdgcn_s_waitcnt(0xC07F);
+      __builtin_amdgcn_wave_barrier();
+    }
+#pragma unroll
+    for (int t = 0; t < TPL; ++t)
+      if (lane + 64 * t < V && cnt[t] >= top_k) {
+        w[t] = 1e-6f;                                       // the reference's floor (torch.multinomial renormalises)
+        changed = true;
+      }
+  }
+  if (top_p < 1.f) {                                        // nucleus over s = w / sum w: kept iff the mass of the
+    float sw = 0.f;                                         // tokens with a strictly larger s is < top_p
+#pragma unroll
+    for (int t = 0; t < TPL; ++t) sw += w[t];
+    sw = gct_wave_sum(sw);
+    const float invw = 1.0f / sw;
+    float s[TPL], mass[TPL];
+#pragma unroll
+    for (int t = 0; t < TPL; ++t) {
+      s[t] = w[t] * invw;
+      mass[t] = 0.f;
+    }
+    if constexpr (TPL == 1) {
+      for (int j = 0; j < V; ++j) {
+        const float sj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s[0]), j));
+        mass[0] += sj > s[0] ? sj : 0.f;
+      }
+    } else {
+#pragma unroll
+      for (int t = 0; t < TPL; ++t) stage[wave][lane + 64 * t] = s[t];
+      __builtin_amdgcn_s_waitcnt(0xC07F);
+      __builtin_amdgcn_wave_barrier();
+      for (int j = 0; j < Vr; j += 4) {
+        const float4 q = *reinterpret_cast<const float4*>(&stage[wave][j]);
+#pragma unroll
+        for (int t = 0; t < TPL; ++t) {
+          mass[t] += q.x > s[t] ? q.x : 0.f;
+          mass[t] += q.y > s[t] ? q.y : 0.f;
+          mass[t] += q.z > s[t] ? q.z : 0.f;
+          mass[t] += q.w > s[t] ? q.w : 0.f;
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < TPL; ++t)
+      if (lane + 64 * t < V && !(mass[t] < top_p)) {
+        w[t] = 0.f;
+        changed = true;
+      }
+  }
+  changed = __ballot(changed) != 0ull;                      // wave-uniform from here on
+  const uint4 r = gct_philox(rng, (uint32_t)row, (uint32_t)pos, 0x452821E6u, 0x38D01377u);
+  float u = u01_open(r.x);
+  float pscale = 1.f;
+  int pick = V - 1;
+  if (changed) {                                            // draw c with probability w_c / sum w
+    float sw = 0.f;
+    int last = -1;
+#pragma unroll
+    for (int t = 0; t < TPL; ++t) {
+      sw += w[t];
+      if (w[t] > 0.f) last = lane + 64 * t;
+    }
+    sw = gct_wave_sum(sw);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) last = max(last, __shfl_xor(last, off, 64));
+    u *= sw;
+    pscale = 1.0f / sw;
+    if (last >= 0) pick = last;                             // rounding fallback: the last token of nonzero weight
+  }
+  float cum = 0.f;
+  bool found = false;
+#pragma unroll
+  for (int t = 0; t < TPL; ++t) {
+    if (64 * t >= V) break;
+    const int c = 64 * t + lane;
+    const float p = w[t];
+    if (probs_out && c < V) probs_out[(int64_t)row * V + c] = changed ? p * pscale : p;
+    float incl = p;                                         // inclusive scan over the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const float tt = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += tt;
+    }
+    const bool hit = !found && c < V && (cum + incl) > u && (!changed || p > 0.f);
+    const unsigned long long ball = __ballot(hit);
+    if (ball && !found) {
+      pick = 64 * t + (int)__builtin_ctzll(ball);
+      found = true;
+    }
+    cum += __shfl(incl, 63, 64);
+  }
+  if (lane == 0) {
+    ys[(int64_t)row * ld_ys + pos] = pick;
+    if (valid) valid[(int64_t)row * valid_sb + valid_off + pos] = (pick != pad_id) ? 1 : 0;
+    if (done && pick == eos_id) done[row] = 1;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------- beam search
 // Candidate order of the selection: higher score first, then the lower flat index beam * V + token.
 __device__ __forceinline__ bool beam_better(float av, int ai, float bv, int bi) {
@@ -583,11 +744,28 @@ extern "C" int gct_select_token(const float* logits, int V, int64_t* ys, int64_t
                                 uint8_t* valid, int64_t valid_sb, uint8_t* done, float* probs_out,
                                 int n, int mode, int64_t pad_id, int64_t eos_id, uint64_t seed,
                                 const int32_t* pos_dev, int valid_off, const uint64_t* seed_dev,
-                                const int32_t* row_off, void* stream) {
+                                const int32_t* row_off, const GctSampleFilter* filt, void* stream) {
   GCT_CHECK_ARG(logits && ys && V > 0 && n >= 0 && pos >= 0 && (mode == 0 || mode == 1) && valid_off >= 0,
                 "select_token: bad args");
   GCT_CHECK_ARG(!row_off || pos_dev, "select_token: row_off needs the device position");
+  GCT_CHECK_ARG(!filt || mode == 1, "select_token: the sampling filter is for the multinomial mode");
+  GCT_CHECK_ARG(!filt || V <= GCT_SAMPLE_FILTER_MAX_VOCAB, "select_token: the sampling filter supports up to %d tokens, "
+                "not %d", GCT_SAMPLE_FILTER_MAX_VOCAB, V);
   if (n == 0) return GCT_OK;
+  if (filt) {
+    const dim3 grid((unsigned)((n + 3) / 4)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    const GctRng rng = gct_rng_make(seed, 0xDEC0DEu);
+    if (V <= 64) {
+      if (row_off) hipLaunchKernelGGL((select_token_filtered_kernel<true, 1>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, row_off, filt);
+      else hipLaunchKernelGGL((select_token_filtered_kernel<false, 1>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, nullptr, filt);
+    } else {
+      if (row_off) hipLaunchKernelGGL((select_token_filtered_kernel<true, GCT_SAMPLE_FILTER_MAX_VOCAB / 64>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, row_off, filt);
+      else hipLaunchKernelGGL((select_token_filtered_kernel<false, GCT_SAMPLE_FILTER_MAX_VOCAB / 64>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, nullptr, filt);
+    }
+    GCT_LAUNCH_CHECK("select_token");
+    return GCT_OK;
+  }
   if (row_off)
     hipLaunchKernelGGL(select_token_kernel<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0,
                        (hipStream_t)stream, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out,

@@ -31,10 +31,16 @@ right-padded to t0_max.  The device counter stays shared (the token index of the
 through its offset row_off[r] = t0_max - t0_r (gct_decode_embed / gct_attn_decode / gct_select_token), so each row keeps
 its own token positions, positional rows, cache slots and multinomial keys (row, token position): it decodes exactly
 what it would decode alone.  Row r's generated tokens start at column t0_r of the output (`generated_tokens`).
+
+Top-k / nucleus / temperature sampling (`generate(algo="multinomial", top_k=, top_p=, temperature=)`): the rules are
+stated once, in `sample_filter_reference`; gct_select_token applies them on the device between the softmax and the
+inverse-CDF draw, reading the settings from a device buffer (`self.filt`), so one captured graph serves any settings and
+mixed-prefix rows keep their own draws.
 """
 from __future__ import annotations
 
 import math
+import numbers
 import os
 from typing import Optional
 
@@ -58,6 +64,59 @@ REPLAY_SLOW_FACTOR = 1.3
 # beam search: length penalty exponent of the final ranking score / length**alpha (reference generate_mols.py:182-185)
 BEAM_ALPHA = 0.7
 BEAM = "beam"                                       # selection mode key of the beam step (self.graphs, _advance)
+FILTERED = "filtered"                               # selection mode key of the filtered multinomial draw
+TOP_K_FLOOR = 1e-6                                  # weight of a token outside the top k (the reference's top_k_logits)
+
+
+# ------------------------------------------------------------------------- top-k / nucleus / temperature sampling
+def check_sample_filter(top_k=None, top_p=None, temperature=1.0, vocab=None):
+    """Validate sampling settings: top_k None or an int in [1, vocab]; top_p None or a real in (0, 1]; temperature a
+    finite real > 0 whose fp32 reciprocal is finite.  ValueError otherwise.  Returns True when the settings change the
+    distribution (k < vocab, top_p < 1 or temperature != 1), False when they are neutral."""
+    if top_k is not None:
+        if isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral):
+            raise ValueError(f"top_k must be None or an int, got {top_k!r}")
+        if top_k < 1 or (vocab is not None and top_k > vocab):
+            raise ValueError(f"top_k {top_k} outside [1, {vocab if vocab is not None else 'V'}]")
+    if top_p is not None:
+        if isinstance(top_p, bool) or not isinstance(top_p, numbers.Real) or not 0.0 < float(top_p) <= 1.0:
+            raise ValueError(f"top_p must be None or a real in (0, 1], got {top_p!r}")
+    if isinstance(temperature, bool) or not isinstance(temperature, numbers.Real):
+        raise ValueError(f"temperature must be a real number, got {temperature!r}")
+    t = float(temperature)
+    if not (math.isfinite(t) and t > 0.0 and 1.0 / t < 3.0e38):
+        raise ValueError(f"temperature must be finite and > 0 (with a finite fp32 reciprocal), got {temperature!r}")
+    return ((top_k is not None and (vocab is None or top_k < vocab)) or (top_p is not None and float(top_p) < 1.0)
+            or t != 1.0)
+
+
+def sample_filter_reference(logits, top_k=None, top_p=None, temperature=1.0):
+    """THE statement of the sampling filter (gct_select_token's filtered draw implements it): logits [..., V] -> the
+    normalised distribution [..., V] the multinomial draw uses.
+      1. p = softmax(x / T) in fp32;
+      2. top_k: token c is in when fewer than k tokens have a strictly larger LOGIT (ties at the k-th value stay in, the
+         reference's p_c >= v_k); an out token gets the weight TOP_K_FLOOR = 1e-6, as the reference's top_k_logits gives
+         it before torch.multinomial renormalises; k = V is a no-op;
+      3. top_p (nucleus) on s = w / sum w, w the result of 2: token c is kept when the mass of the tokens with a strictly
+         larger s is < top_p (every token tied at the boundary is kept), otherwise its weight is 0; top_p = 1 is a no-op;
+      4. the draw picks c with probability w_c / sum w (returned).  The top token is always kept, so greedy ignores all
+         three settings."""
+    V = logits.shape[-1]
+    check_sample_filter(top_k, top_p, temperature, V)
+    x = logits.float()
+    w = torch.softmax(x / float(temperature), -1)
+    if top_k is not None and top_k < V:
+        asc = x.sort(-1).values
+        larger = V - torch.searchsorted(asc, x.contiguous(), right=True)           # tokens with a strictly larger logit
+        w = torch.where(larger < top_k, w, torch.full_like(w, TOP_K_FLOOR))
+    if top_p is not None and top_p < 1:
+        s = w / w.sum(-1, keepdim=True)
+        asc = s.sort(-1).values
+        larger = V - torch.searchsorted(asc, s.contiguous(), right=True)           # tokens with a strictly larger s
+        top_mass = asc.flip(-1).double().cumsum(-1)                                  # mass of the j + 1 largest
+        mass = torch.where(larger > 0, top_mass.gather(-1, (larger - 1).clamp(min=0)), torch.zeros_like(top_mass))
+        w = torch.where(mass < float(top_p), w, torch.zeros_like(w))
+    return w / w.sum(-1, keepdim=True)
 
 
 # ------------------------------------------------------------------------------------- beam-search semantics
@@ -252,6 +311,7 @@ class KVDecoder:
             self.row_off = torch.zeros(n, dtype=torch.int32, device=dev)   # mixed prefixes: row r is at pos - row_off[r]
             self.ragged = False                                            # this decode passes row_off to the kernels
             self.seed = torch.zeros(1, dtype=torch.int64, device=dev)      # multinomial seed of this generate()
+            self.filt = torch.zeros(4, dtype=torch.int32, device=dev)      # GctSampleFilter of this generate()
             # beam search state (generate_beam), per row: score, finished, length, parent; the ancestry map; done [n/k]
             self.beams = beams
             self.bscores = torch.zeros(n, device=dev)
@@ -451,15 +511,17 @@ class KVDecoder:
 
     def _select(self, mode):
         """softmax + choice of the next token from buf['logits']; written at ys[:, *pos + 1] (device position).
-        mode BEAM: gct_beam_select (beam state, the kv_src map and bdone in place)."""
+        mode BEAM: gct_beam_select (beam state, the kv_src map and bdone in place).  mode FILTERED: the multinomial draw
+        through the top-k / nucleus / temperature settings in self.filt."""
         if mode == BEAM:
             ops.beam_select(self.buf["logits"], self.beams, self.bscores, self.bfin, self.blen, self.ys, self.valid,
                             self.off, self.kv_src, self.bdone, self.pos, self.pad_id, self.eos_id,
                             parent_i32=self.bparent)
             return
-        ops.select_token(self.buf["logits"], self.ys, 0, self.valid, self.done, mode, self.pad_id, self.eos_id,
-                         pos_dev=self.pos, valid_off=self.off, seed_dev=self.seed,
-                         row_off=self.row_off if self.ragged else None)
+        ops.select_token(self.buf["logits"], self.ys, 0, self.valid, self.done, 1 if mode == FILTERED else mode,
+                         self.pad_id, self.eos_id, pos_dev=self.pos, valid_off=self.off, seed_dev=self.seed,
+                         row_off=self.row_off if self.ragged else None,
+                         filt_dev=self.filt if mode == FILTERED else None)
 
     def _advance(self, mode):
         """One step and its selection: the unit a graph captures."""
@@ -468,13 +530,23 @@ class KVDecoder:
 
     # -------------------------------------------------------------------------------------
     @torch.no_grad()
-    def generate(self, ys0, max_strlen=80, algo="greedy", seed=0, check_every=8, use_graphs=False, prefix_lens=None):
+    def generate(self, ys0, max_strlen=80, algo="greedy", seed=0, check_every=8, use_graphs=False, prefix_lens=None,
+                 top_k=None, top_p=None, temperature=1.0):
         """Mirror of Sampling.decode: appends max_strlen-1 tokens to the prefix ys0 [n, t0]
         (stops early once every sample has produced <eos>, like the reference's break).
         prefix_lens (ints [n], 1 <= t0_r <= t0, optional): row r's prefix is ys0[r, :t0_r] (right-padded); it decodes
         exactly what it would decode alone.  The output is then [n, t0 + G] with row r's G generated tokens at columns
         t0_r .. t0_r + G - 1 and pad behind them: generated_tokens(ys, prefix_lens) returns them as [n, G].  All lengths
-        equal to t0 (or None): the uniform path."""
+        equal to t0 (or None): the uniform path.
+        top_k / top_p / temperature (sample_filter_reference states the rules; validated before any device work, bad
+        values raise ValueError): with algo="multinomial" and a non-neutral setting every draw goes through the filter
+        (a selection mode and graph of its own; vocabularies up to ops.SAMPLE_FILTER_MAX_VOCAB).  Greedy ignores them:
+        the filters always keep the top token."""
+        V = self.model.out.weight.shape[0]
+        filtered = check_sample_filter(top_k, top_p, temperature, V) and algo == "multinomial"
+        if filtered and V > ops.SAMPLE_FILTER_MAX_VOCAB:
+            raise ValueError(f"top-k / nucleus / temperature sampling supports vocabularies up to "
+                             f"{ops.SAMPLE_FILTER_MAX_VOCAB} tokens, not {V}")
         n, t0 = ys0.shape
         steps = max_strlen - 1
         lens = check_prefix_lens(prefix_lens, n, t0)
@@ -486,6 +558,9 @@ class KVDecoder:
             raise ValueError(f"prefix {t0} + {steps} steps exceeds the cache length {self.T - self.off}")
         mode = {"greedy": 0, "multinomial": 1}[algo]
         self.seed.fill_(int(seed) & 0x7FFFFFFFFFFFFFFF)
+        if filtered:
+            mode = FILTERED
+            self.filt.copy_(ops.sample_filter_settings(top_k, top_p, temperature, V))
         self.prefill(ys0, lens)
         self._select(mode)                                         # token t0 from the prefill's last position
         last = t0 + steps

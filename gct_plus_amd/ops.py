@@ -929,15 +929,33 @@ def attn_decode_z(q, qoff, z, ckv, nc, valid_u8, out, ooff, n, H, dk, klen=None)
                                  out.stride(0), ooff, n, H, dk, 1.0 / math.sqrt(dk), _st()), "gct_attn_decode_z")
 
 
+SAMPLE_FILTER_MAX_VOCAB = 1024                  # GCT_SAMPLE_FILTER_MAX_VOCAB (include/gctplus_hip.h)
+
+
+def sample_filter_settings(top_k, top_p, temperature, vocab):
+    """The GctSampleFilter of validated settings (decode.check_sample_filter) as an int32 CPU tensor [4]:
+    {k, top_p, 1/T, 0}, the two floats stored bit for bit (copy it to a device tensor for select_token's filt_dev)."""
+    t = torch.zeros(4, dtype=torch.int32)
+    t[0] = vocab if top_k is None else int(top_k)
+    f = t.view(torch.float32)
+    f[1] = 1.0 if top_p is None else float(top_p)
+    f[2] = 1.0 / float(temperature)
+    return t
+
+
 def select_token(logits2d, ys, pos, valid_u8, done_u8, mode, pad_id, eos_id, seed=0, probs_out=None, pos_dev=None,
-                 valid_off=0, seed_dev=None, row_off=None):
-    """row_off (int32 [n], optional, with pos_dev only): row r writes at *pos_dev - row_off[r] + 1."""
+                 valid_off=0, seed_dev=None, row_off=None, filt_dev=None):
+    """row_off (int32 [n], optional, with pos_dev only): row r writes at *pos_dev - row_off[r] + 1.
+    filt_dev (int32 [4] on the device, optional, mode 1 only): top-k / nucleus / temperature settings
+    (sample_filter_settings), read by the kernel; V <= SAMPLE_FILTER_MAX_VOCAB."""
     n, V = logits2d.shape
     _check_row_off(row_off, n)
+    if filt_dev is not None and (filt_dev.dtype != torch.int32 or filt_dev.numel() != 4 or not filt_dev.is_contiguous()):
+        raise ValueError("filt_dev must be a contiguous int32 tensor of 4 entries (sample_filter_settings)")
     check(_L().gct_select_token(_p(logits2d), V, _p(ys), ys.stride(0), pos, _p(valid_u8),
                                 valid_u8.stride(0) if valid_u8 is not None else 0, _p(done_u8),
                                 _p(probs_out), n, mode, pad_id, eos_id, seed, _p(pos_dev), valid_off, _p(seed_dev),
-                                _p(row_off), _st()), "gct_select_token")
+                                _p(row_off), _p(filt_dev), _st()), "gct_select_token")
 
 
 def decode_embed(ys, pos, pe_off, table, pe, out, scale, row_off=None):

@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 17
+#define GCT_ABI_VERSION 18
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -409,11 +409,28 @@ int gct_decode_advance(int32_t* pos, void* stream);
  * (token != pad), done[row] |= (token == eos); probs_out (nullable) [n][V].  pos_dev (nullable): pos = *pos_dev + 1;
  * seed_dev (nullable): the multinomial seed is read from device memory (graph replays with a fresh seed).
  * row_off (nullable, only with pos_dev; as in gct_attn_decode): row r writes at pos = *pos_dev - row_off[r] + 1, and
- * its multinomial draw is keyed by (r, that pos). */
+ * its multinomial draw is keyed by (r, that pos).
+ * filt (nullable, DEVICE memory, mode 1 only): sampling filter between the softmax and the draw (gct_plus_amd/decode.py
+ * sample_filter_reference states the rules), read by the kernel so that one captured graph serves any settings:
+ *   p = softmax(x * inv_temp) in fp32;
+ *   top-k: token c is in when fewer than k tokens have a strictly larger LOGIT (ties at the k-th value stay in); an out
+ *     token gets the weight 1e-6 (the reference's floor); k >= V: no-op;
+ *   nucleus: with s = w / sum w, token c is kept when the mass of the tokens with a strictly larger s is < top_p,
+ *     otherwise its weight is 0; top_p >= 1: no-op;
+ *   the draw picks c with probability w_c / sum w (the same Philox key); probs_out receives w / sum w.  A row the filter
+ *   leaves unchanged draws exactly as without filt.  The host validates 1 <= k <= V, 0 < top_p <= 1, 0 < T < inf.
+ * V <= GCT_SAMPLE_FILTER_MAX_VOCAB with filt; otherwise (or with mode 0) GCT_ERR_ARG.  NULL: the kernels of ABI 17. */
+typedef struct GctSampleFilter {
+  int32_t k;        /* top-k (>= V: off) */
+  float top_p;      /* nucleus mass (>= 1: off) */
+  float inv_temp;   /* 1 / temperature */
+  int32_t reserved; /* 0 */
+} GctSampleFilter;
+#define GCT_SAMPLE_FILTER_MAX_VOCAB 1024
 int gct_select_token(const float* logits, int V, int64_t* ys, int64_t ld_ys, int pos, uint8_t* valid,
                      int64_t valid_sb, uint8_t* done, float* probs_out, int n, int mode,
                      int64_t pad_id, int64_t eos_id, uint64_t seed, const int32_t* pos_dev, int valid_off,
-                     const uint64_t* seed_dev, const int32_t* row_off, void* stream);
+                     const uint64_t* seed_dev, const int32_t* row_off, const GctSampleFilter* filt, void* stream);
 
 /* Beam search (gct_plus_amd/decode.py beam_step_reference states the rules).  Sample s owns the k rows
  * s*k .. s*k+k-1 of an n*k-row decode.  The self-attention caches, ys and valid are PHYSICAL slots, each written once:

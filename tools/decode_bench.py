@@ -7,7 +7,9 @@ ids checked against reference_style_beam_decode on the first --ref-n samples.
 graph replay, decoded SMILES/s of three schedules of the same rows: one batch per scaffold (chunks of <= 512 rows, the
 reference's per-scaffold sampling loop), one batch per prefix length (host-side grouping), and ONE mixed-prefix batch
 (KVDecoder.generate(prefix_lens=)); plus a uniform-prefix batch of the same n at the mean prefix length for scale.  The
-mixed batch's ids are checked against the per-length runs first."""
+mixed batch's ids are checked against the per-length runs first.
+--top-k K / --top-p P / --temperature T: filtered multinomial sampling against plain multinomial on the same rows (ms per
+token step and SMILES/s, eager and graph replay, all 79 steps)."""
 import argparse
 import os
 import sys
@@ -29,6 +31,9 @@ ap.add_argument("--ragged", action="store_true", help="latent length 80 with MOS
 ap.add_argument("--beam", type=int, default=0, help="beam search with K beams per sample (see the docstring)")
 ap.add_argument("--scaffolds", type=int, default=0, help="mixed-scaffold schedules over K scaffolds (see the docstring)")
 ap.add_argument("--per-scaffold", type=int, default=64, help="rows per scaffold with --scaffolds")
+ap.add_argument("--top-k", type=int, default=None, help="filtered multinomial: top-k (see the docstring)")
+ap.add_argument("--top-p", type=float, default=None, help="filtered multinomial: nucleus mass")
+ap.add_argument("--temperature", type=float, default=1.0, help="filtered multinomial: temperature")
 a = ap.parse_args()
 mtype = a.model_type
 vs, vt = synthetic.vocab_sizes(mtype)
@@ -112,6 +117,22 @@ if a.scaffolds:
     print(f"mixed / uniform {res['mixed'] / res[f'uniform_t0={tu}']:.3f}, mixed / per-scaffold "
           f"{res['mixed'] / res['per_scaffold']:.2f}x, mixed / per-length {res['mixed'] / res['per_length']:.2f}x")
     sys.exit(0 if bool(same.all()) else 1)
+
+if a.top_k is not None or a.top_p is not None or a.temperature != 1.0:
+    filt = dict(top_k=a.top_k, top_p=a.top_p, temperature=a.temperature)
+    kd = KVDecoder(model, synthetic.PAD_ID, synthetic.SOS_ID, eos_id=-1)   # never stop early: worst case
+    for graphs in (False, True):
+        res = {}
+        for name, kw in (("multinomial", {}), ("filtered", filt)):
+            def run():
+                kd.start(z, src_mask, dconds, max_total_len=96)
+                return kd.generate(ys0, 80, algo="multinomial", seed=5, use_graphs=graphs, check_every=0, **kw)
+            ys, dt = timed(run)
+            res[name] = dt
+            print(f"graphs={graphs}: {name:>11} n={n} {dt / 79 * 1e3:.3f} ms/step ({n / dt:.0f} SMILES/s)", flush=True)
+        print(f"graphs={graphs}: filtered / multinomial step {res['filtered'] / res['multinomial']:.3f} "
+              f"({', '.join(f'{k}={v}' for k, v in filt.items())})", flush=True)
+    sys.exit(0)
 
 if a.beam:
     k = a.beam
