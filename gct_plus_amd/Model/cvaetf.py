@@ -9,7 +9,7 @@ from .. import engine, ops
 from ..flat import FlatModelMixin, planes_scope
 from .layers import DecoderLayer, EncoderLayer
 from .modules import Embeddings, Norm, PositionalEncoding, get_clones
-from .vaetf import Linear, _TrunkParams, _row_plan, _row_plan_launch
+from .vaetf import Linear, _DecoderTrunk, _TrunkParams, _row_plan
 
 
 class Encoder(nn.Module, _TrunkParams):
@@ -31,10 +31,11 @@ class Encoder(nn.Module, _TrunkParams):
         self.eps_mode = "device"
         self.eps_override = None
 
-    def forward(self, src, src_mask, econds=None, eps=None, _keys=None):
+    def forward(self, src, src_mask, econds=None, eps=None, _plan=None):
         run = engine.Run(self.p, self.training)
+        plan = engine.RowPlan.launch(engine.ENCODER).finish() if _plan is None else _plan
         outs = engine.EncoderFn.apply(self, run, src.contiguous(), ops.to_mask_u8(src_mask), econds,
-                                      self.get_attn, _keys, *self.trunk_params())
+                                      self.get_attn, plan, *self.trunk_params())
         x = outs[0] if self.get_attn else outs
         if eps is None and self.eps_override is not None:
             eps = self.eps_override.to(x.device)
@@ -48,9 +49,7 @@ class Encoder(nn.Module, _TrunkParams):
         return z, mu, log_var
 
 
-class Decoder(nn.Module, _TrunkParams):
-    _dead_prefixes = ("\0",)
-
+class Decoder(_DecoderTrunk, nn.Module):   # (the mixin first: its forward, not Module's)
     def __init__(self, vocab_size, d_model, N, h, dff, latent_dim, nconds, dropout, use_cond2dec,
                  use_cond2lat, get_attn=False):
         super().__init__()
@@ -65,26 +64,6 @@ class Decoder(nn.Module, _TrunkParams):
         self.fc_z = nn.Linear(latent_dim, d_model)
         self.layers = get_clones(DecoderLayer(h, d_model, dff, dropout, get_attn), N)
         self.norm = Norm(d_model)
-
-    def forward(self, trg, z, src_mask, trg_mask, dconds=None, loss_rows=None, _compact_out=False, _plan=None):
-        """loss_rows: see Model/vaetf.py Decoder.forward (an extension of this build)."""
-        run = engine.Run(self.p, self.training)
-        if loss_rows is not None:
-            loss_rows = loss_rows.to(torch.uint8).contiguous()
-        self._gct_live_out = None
-        outs = engine.DecoderFn.apply(self, run, trg.contiguous(), z, ops.to_mask_u8(src_mask),
-                                      ops.to_mask_u8(trg_mask), dconds, self.get_attn, loss_rows, _plan,
-                                      *self.trunk_params())
-        if self._gct_live_out is not None and not _compact_out:
-            # the trunk ran on the loss rows only and returned them compact [Mc, d]: a caller of the decoder alone gets
-            # every row (zeros where nothing was computed); Vaetf / Cvaetf.forward keep the compact rows through the
-            # vocabulary head and scatter the logits instead
-            live, self._gct_live_out = self._gct_live_out, None
-            outs = engine.ScatterRowsFn.apply(outs, live, trg.size(0), trg.size(1))
-        if self.get_attn:
-            n = self.N
-            return outs[0], list(outs[1:1 + n]), list(outs[1 + n:1 + 2 * n])
-        return outs
 
 
 class Cvaetf(FlatModelMixin, nn.Module):
@@ -121,23 +100,19 @@ class Cvaetf(FlatModelMixin, nn.Module):
 
     def plan_ahead(self, src_mask, trg_mask, loss_rows, trg):
         """As Vaetf.plan_ahead."""
-        return _row_plan_launch(self, src_mask, trg_mask, loss_rows, trg)
+        return _row_plan(self, src_mask, trg_mask, loss_rows, trg)
 
     @planes_scope
     def forward(self, src, trg, src_mask, trg_mask, econds=None, dconds=None, *, loss_rows=None, _plan_ahead=None):
         """Reference signature (Model/cvaetf.py:179) plus the keyword-only loss_rows extension of Vaetf.forward."""
-        if self.get_attn or (self.use_cond2dec and self.nconds > 0):
-            loss_rows = None
-        plan = _plan_ahead.finish() if _plan_ahead is not None else _row_plan(self, src_mask, trg_mask, loss_rows, trg)
-        z, mu, log_var = self.encoder(src, src_mask, econds, _keys=plan.enc_keys)[:3]
-        d_output = self.decoder(trg, z, src_mask, trg_mask, dconds, loss_rows, _compact_out=True, _plan=plan)
+        plan = (_row_plan(self, src_mask, trg_mask, loss_rows, trg) if _plan_ahead is None else _plan_ahead).finish()
+        z, mu, log_var = self.encoder(src, src_mask, econds, _plan=plan)[:3]
+        d_output = self.decoder(trg, z, src_mask, trg_mask, dconds, _plan=plan)
         if self.get_attn:
             d_output = d_output[0]
         output = self.out(d_output)
-        live = self.decoder._gct_live_out
-        if live is not None:            # the decoder ran on the loss rows only: d_output and the logits are compact [Mc, .]
-            self.decoder._gct_live_out = None
-            output = engine.ScatterRowsFn.apply(output, live, trg.size(0), trg.size(1))
+        if plan.live is not None:       # the decoder ran on the loss rows only: d_output and the logits are compact [Mc, .]
+            output = engine.ScatterRowsFn.apply(output, plan.live, trg.size(0), trg.size(1))
         if self.use_cond2dec and self.nconds > 0:
             output_prop = self.prop_fc(output[:, :self.nconds, :])
             output_mol = output[:, self.nconds:, :]

@@ -7,12 +7,8 @@ reference's loss looks at -- `ys = trg[:, 1:] != pad` (Train/trainer1.py:21-22,9
 ignore_index = pad) -- so that it does not compute the others (56 % of the decoder rows at MOSES-like lengths).  Loss
 and every gradient are unchanged; the logits of the ignored rows are not the reference's (nothing reads them).  The
 trainer (Train/trainer1.run_epoch) and bench.py switch it on; a caller that wants every logit leaves it off."""
-import os
-
 from .. import ops
 from .modules import get_src_mask, get_trg_mask
-
-PLAN_AHEAD = os.environ.get("GCT_PLAN_AHEAD", "1") != "0"      # A/B switch of prefetch()
 
 
 def _trg_mask(trg_in, pad_id, use_cond2dec, dconds=None):
@@ -23,53 +19,57 @@ def _trg_mask(trg_in, pad_id, use_cond2dec, dconds=None):
     return get_trg_mask(trg_in, pad_id, use_cond2dec, dconds)
 
 
-def _loss_rows(batch, pad_id, use_cond2dec, skip_ignored):
-    if not skip_ignored or use_cond2dec:
-        return None
-    return batch["trg"][:, 1:] != pad_id
-
-
 def _masks(batch, pad_id, use_cond2dec, skip_ignored, conditioned):
     trg_in = batch["trg"][:, :-1]
-    rows = _loss_rows(batch, pad_id, use_cond2dec, skip_ignored)
+    rows = batch["trg"][:, 1:] != pad_id if skip_ignored else None     # (the model's row planner decides their use)
     if conditioned:
         return (trg_in, get_src_mask(batch["src"], pad_id, batch["econds"]),
                 _trg_mask(trg_in, pad_id, use_cond2dec, batch["dconds"]), rows)
     return trg_in, get_src_mask(batch["src"], pad_id), _trg_mask(trg_in, pad_id, use_cond2dec), rows
 
 
-def _key(batch, pad_id, use_cond2dec, skip_ignored):
-    s, t = batch["src"], batch["trg"]
-    return (s.data_ptr(), t.data_ptr(), tuple(s.shape), tuple(t.shape), s._version, t._version, pad_id,
-            bool(use_cond2dec), bool(skip_ignored))
+def _held(batch, conditioned):
+    return (batch["src"], batch["trg"]) + ((batch["econds"], batch["dconds"]) if conditioned else ())
 
 
 def prefetch(model_type, model, batch, pad_id, use_cond2dec, skip_ignored=False):
     """Queue, NOW, the masks and the row maps of a batch that the NEXT call of forward_propagation[model_type] will get
     (same arguments).  The trainer calls it between a step's forward and its backward: the maps' one device->host
     read-back then completes while that backward runs, and the next step's forward is queued without the host waiting
-    for the device (engine.RowPlan.launch).  Purely an optimisation: a batch that was not announced, or was modified
-    since, is handled exactly as before.  GPU batches and models with plan_ahead only; a no-op otherwise."""
+    for the device (engine.RowPlan).  Purely an optimisation: the announcement holds the batch's tensors, and a forward
+    takes it only for those very tensor objects (`is`) at the versions they had here -- any other batch, a view of
+    these tensors, or a batch modified since is handled exactly as if nothing had been announced.  GPU batches and
+    models with plan_ahead only; a no-op otherwise."""
     inner = getattr(model, "module", model)
-    if not (PLAN_AHEAD and hasattr(inner, "plan_ahead") and batch["src"].is_cuda):
+    if not (hasattr(inner, "plan_ahead") and batch["src"].is_cuda):
         return
     conditioned = forward_propagation[model_type] is _conditioned
+    held = _held(batch, conditioned)
     trg_in, src_mask, trg_mask, rows = _masks(batch, pad_id, use_cond2dec, skip_ignored, conditioned)
-    inner._gct_ahead = (_key(batch, pad_id, use_cond2dec, skip_ignored), src_mask, trg_mask, rows,
-                        inner.plan_ahead(src_mask, trg_mask, rows, trg_in))
+    inner._gct_ahead = (held, tuple(t._version for t in held), (pad_id, bool(use_cond2dec), bool(skip_ignored)),
+                        (src_mask, trg_mask, rows, inner.plan_ahead(src_mask, trg_mask, rows, trg_in)))
 
 
-def _ahead(model, batch, pad_id, use_cond2dec, skip_ignored):
+def forget_announcement(model):
+    """Drop whatever prefetch() announced (run_epoch, at its start)."""
+    getattr(model, "module", model)._gct_ahead = None
+
+
+def _ahead(model, batch, pad_id, use_cond2dec, skip_ignored, conditioned):
     inner = getattr(model, "module", model)
     got = getattr(inner, "_gct_ahead", None)
     if got is None:
         return None
     inner._gct_ahead = None
-    return got[1:] if got[0] == _key(batch, pad_id, use_cond2dec, skip_ignored) else None
+    held, versions, flags, ahead = got
+    now = _held(batch, conditioned)
+    same = (len(now) == len(held) and all(a is b and a._version == v for a, b, v in zip(now, held, versions))
+            and flags == (pad_id, bool(use_cond2dec), bool(skip_ignored)))
+    return ahead if same else None
 
 
 def _call(model, batch, pad_id, use_cond2dec, skip_ignored, conditioned):
-    ahead = _ahead(model, batch, pad_id, use_cond2dec, skip_ignored)
+    ahead = _ahead(model, batch, pad_id, use_cond2dec, skip_ignored, conditioned)
     kw = {}
     if ahead is not None:
         src_mask, trg_mask, rows, kw["_plan_ahead"] = ahead

@@ -45,10 +45,11 @@ class Encoder(nn.Module, _TrunkParams):
         if nconds > 0:
             self.embed_cond2enc = nn.Linear(nconds, d_model * nconds)
 
-    def trunk(self, src, src_mask, econds, _keys=None):
+    def trunk(self, src, src_mask, econds, _plan=None):
         run = engine.Run(self.p, self.training)
+        plan = engine.RowPlan.launch(engine.ENCODER).finish() if _plan is None else _plan
         outs = engine.EncoderFn.apply(self, run, src.contiguous(), ops.to_mask_u8(src_mask), econds,
-                                      self.get_attn, _keys, *self.trunk_params())
+                                      self.get_attn, plan, *self.trunk_params())
         if self.get_attn:
             return outs[0], list(outs[1:])
         return outs, None
@@ -58,9 +59,32 @@ class Encoder(nn.Module, _TrunkParams):
         return (x, attn) if self.get_attn else x
 
 
-class Decoder(nn.Module, _TrunkParams):
+class _DecoderTrunk(_TrunkParams):
+    """The decoder's forward, shared by Vaetf's and Cvaetf's Decoder (which differ in registration order only)."""
     _dead_prefixes = ("\0",)
 
+    def forward(self, trg, z, src_mask, trg_mask, dconds=None, loss_rows=None, _plan=None):
+        """loss_rows (bool / uint8 [B, T], optional -- an extension of this build): the rows whose output reaches the
+        loss; the others are not computed: they come back as zeros, except the (at most 3 per sample) padded rows that
+        share an aligned group of four rows with a live one, which hold arbitrary finite values (engine.decoder_trunk_fwd).
+        _plan (engine.RowPlan, finished): the model forward's; that caller gets the COMPACT rows [Mc, d] when
+        _plan.live is set and scatters them itself.  Without one the decoder plans its own rows and returns every row."""
+        run = engine.Run(self.p, self.training)
+        sm, tm = ops.to_mask_u8(src_mask), ops.to_mask_u8(trg_mask)
+        plan = _plan
+        if plan is None:
+            plan = engine.RowPlan.launch(engine.DECODER, self, sm, tm, loss_rows, *trg.shape, z.shape[1]).finish()
+        outs = engine.DecoderFn.apply(self, run, trg.contiguous(), z, sm, tm, dconds, self.get_attn, plan,
+                                      *self.trunk_params())
+        if plan.live is not None and _plan is None:
+            outs = engine.ScatterRowsFn.apply(outs, plan.live, trg.size(0), trg.size(1))
+        if self.get_attn:
+            n = self.N
+            return outs[0], list(outs[1:1 + n]), list(outs[1 + n:1 + 2 * n])
+        return outs
+
+
+class Decoder(_DecoderTrunk, nn.Module):   # (the mixin first: its forward, not Module's)
     def __init__(self, vocab_size, d_model, N, h, dff, latent_dim, nconds, dropout, use_cond2dec,
                  use_cond2lat, get_attn=False):
         super().__init__()
@@ -76,53 +100,13 @@ class Decoder(nn.Module, _TrunkParams):
         if use_cond2lat and nconds > 0:
             self.embed_cond2lat = nn.Linear(nconds, d_model * nconds)
 
-    def forward(self, trg, z, src_mask, trg_mask, dconds, loss_rows=None, _compact_out=False, _plan=None):
-        """loss_rows (bool / uint8 [B, T], optional -- an extension of this build): the rows whose output reaches the
-        loss; the others are not computed: they come back as zeros, except the (at most 3 per sample) padded rows that
-        share an aligned group of four rows with a live one, which hold arbitrary finite values (engine.decoder_trunk_fwd)."""
-        run = engine.Run(self.p, self.training)
-        if loss_rows is not None:
-            loss_rows = loss_rows.to(torch.uint8).contiguous()
-        self._gct_live_out = None
-        outs = engine.DecoderFn.apply(self, run, trg.contiguous(), z, ops.to_mask_u8(src_mask),
-                                      ops.to_mask_u8(trg_mask), dconds, self.get_attn, loss_rows, _plan,
-                                      *self.trunk_params())
-        if self._gct_live_out is not None and not _compact_out:
-            # the trunk ran on the loss rows only and returned them compact [Mc, d]: a caller of the decoder alone gets
-            # every row (zeros where nothing was computed); Vaetf / Cvaetf.forward keep the compact rows through the
-            # vocabulary head and scatter the logits instead
-            live, self._gct_live_out = self._gct_live_out, None
-            outs = engine.ScatterRowsFn.apply(outs, live, trg.size(0), trg.size(1))
-        if self.get_attn:
-            n = self.N
-            return outs[0], list(outs[1:1 + n]), list(outs[1 + n:1 + 2 * n])
-        return outs
-
 
 def _row_plan(model, src_mask, trg_mask, loss_rows, trg):
-    """engine.RowPlan of a training-style forward: the row maps of both trunks, read back in ONE synchronisation at the
-    start of the step (see engine.RowPlan).  Works on the masks exactly as the caller passed them (Model/modules.py)."""
-    return _row_plan_launch(model, src_mask, trg_mask, loss_rows, trg).finish()
-
-
-def _row_plan_launch(model, src_mask, trg_mask, loss_rows, trg):
-    """The first half of _row_plan (engine.RowPlan.launch): kernels and the read-back are queued, .finish() gives the plan."""
-    if model.get_attn or (model.use_cond2dec and model.nconds > 0):
-        loss_rows = None
-    if model.get_attn or src_mask is None or not src_mask.is_cuda:
-        return engine._PendingPlan(None, None, None, None, 0, 0, 0)
-    dec = model.decoder
-    sm = ops.to_mask_u8(src_mask)
-    B, T = trg.shape
-    if sm.dim() != 3 or sm.shape[0] != B or sm.shape[1] != 1:          # not the reference's [B, 1, L] key-padding mask
-        return engine._PendingPlan(None, None, None, None, 0, 0, 0)
-    Le = sm.shape[2]
-    c2d = dec.use_cond2dec and dec.nconds > 0
-    nc_lat = dec.nconds if (not c2d and dec.use_cond2lat and dec.nconds > 0) else 0
-    lr = None if loss_rows is None else loss_rows.to(torch.uint8).contiguous()
-    tm = None if trg_mask is None else ops.to_mask_u8(trg_mask)
-    return engine.RowPlan.launch(sm.view(B, Le), tm, lr, B, Le, T if not c2d else T + dec.nconds, nc_lat,
-                                 len(model.encoder.layers), len(dec.layers))
+    """engine.RowPlan of a training-style forward (engine.MODEL): the row maps of both trunks, launched with one
+    asynchronous read-back; .finish() gives the plan.  Works on the masks exactly as the caller passed them."""
+    Le = 0 if src_mask is None else src_mask.shape[-1]
+    return engine.RowPlan.launch(engine.MODEL, model.decoder, src_mask, trg_mask, loss_rows, *trg.shape, Le,
+                                 n_enc=len(model.encoder.layers))
 
 
 class Linear(nn.Linear):
@@ -169,7 +153,7 @@ class Vaetf(FlatModelMixin, nn.Module):
     def plan_ahead(self, src_mask, trg_mask, loss_rows, trg):
         """Queue the row maps of a batch that a later forward(..., _plan_ahead=<the returned object>) will use (the
         trainer: the NEXT batch's, between this step's forward and its backward -- Model/forward_propagation1.prefetch)."""
-        return _row_plan_launch(self, src_mask, trg_mask, loss_rows, trg)
+        return _row_plan(self, src_mask, trg_mask, loss_rows, trg)
 
     @planes_scope
     def forward(self, src, trg, src_mask, trg_mask, econds=None, dconds=None, *, loss_rows=None, _plan_ahead=None):
@@ -177,19 +161,15 @@ class Vaetf(FlatModelMixin, nn.Module):
         decoder rows whose logits reach the loss -- the trainer passes `ys != pad` (Model/forward_propagation1.py); the
         other rows are then not computed at all: their logits come back as zeros -- or, for the few padded rows that share an
         aligned group of four with a live row, as arbitrary finite values -- NOT as the reference's values.  Default (None): every row, as the reference."""
-        if self.get_attn or (self.use_cond2dec and self.nconds > 0):
-            loss_rows = None
-        plan = _plan_ahead.finish() if _plan_ahead is not None else _row_plan(self, src_mask, trg_mask, loss_rows, trg)
-        x, enc_attn = self.encoder.trunk(src, src_mask, econds, _keys=plan.enc_keys)
+        plan = (_row_plan(self, src_mask, trg_mask, loss_rows, trg) if _plan_ahead is None else _plan_ahead).finish()
+        x, enc_attn = self.encoder.trunk(src, src_mask, econds, _plan=plan)
         z, mu, log_var = self.sampler(x)
-        d = self.decoder(trg, z, src_mask, trg_mask, dconds, loss_rows, _compact_out=True, _plan=plan)
+        d = self.decoder(trg, z, src_mask, trg_mask, dconds, _plan=plan)
         if self.get_attn:
             d, dec_attn_1, dec_attn_2 = d
         output = self.out(d)
-        live = self.decoder._gct_live_out
-        if live is not None:            # the decoder ran on the loss rows only: d and the logits are compact [Mc, .]
-            self.decoder._gct_live_out = None
-            output = engine.ScatterRowsFn.apply(output, live, trg.size(0), trg.size(1))
+        if plan.live is not None:       # the decoder ran on the loss rows only: d and the logits are compact [Mc, .]
+            output = engine.ScatterRowsFn.apply(output, plan.live, trg.size(0), trg.size(1))
         if self.use_cond2dec:
             output_prop = self.prop_fc(output[:, :self.nconds, :])
             output_mol = output[:, self.nconds:, :]

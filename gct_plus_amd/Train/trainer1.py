@@ -13,7 +13,7 @@ import torch
 import torch.distributed as dist
 
 from .. import engine
-from ..Model.forward_propagation1 import forward_propagation, prefetch
+from ..Model.forward_propagation1 import forget_announcement, forward_propagation, prefetch
 
 
 def KLAnnealer(epoch, KLA_ini_beta, KLA_inc_beta, KLA_beg_epoch):
@@ -59,6 +59,7 @@ def run_epoch(args, model, optimizer, dataloader, current_step, beta, LOG, train
     nprop = len(args.property_list)
     n_batches = len(dataloader)
     pending = []                 # steps whose three loss scalars are on their way to the host
+    forget_announcement(model)   # a look-ahead left behind by an earlier, interrupted epoch is never used
 
     def resolve():
         while pending:
@@ -86,7 +87,7 @@ def run_epoch(args, model, optimizer, dataloader, current_step, beta, LOG, train
         n_onebatch = batch['src'].size(0)
         model_cost_time -= time()
         # skip_ignored: the decoder rows of padded targets never reach this loss (ignore_index below) -- the model does
-        # not compute them (engine.decoder_trunk_fwd; GCT_COMPACT_FWD=0 switches the shortcut off)
+        # not compute them (engine.plan_rows; GCT_COMPACT_FWD=0 switches the shortcut off)
         preds_prop, preds_mol, mu, log_var, _ = forward_propagation[args.model_type](
             model, batch, args.pad_id, args.use_cond2dec, skip_ignored=True)[:5]
         if upcoming is not None:

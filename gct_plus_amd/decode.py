@@ -438,9 +438,10 @@ class KVDecoder:
         self.done.zero_()
         trg_mask = get_trg_mask(ys0, self.pad_id, self.c2d, self.dconds if dec.nconds > 0 else None)
         run = engine.Run(0.0, False)
-        y, saved, _, _ = engine.decoder_trunk_fwd(dec, run, ys0.contiguous(), engine._f32c(self.z),
-                                                  ops.to_mask_u8(self.src_mask_in), ops.to_mask_u8(trg_mask),
-                                                  self.dconds)
+        sm, tm = ops.to_mask_u8(self.src_mask_in), ops.to_mask_u8(trg_mask)
+        plan = engine.RowPlan.launch(engine.PREFILL, dec, sm, tm, None, *ys0.shape, self.z.shape[1]).finish()
+        y, saved, _, _ = engine.decoder_trunk_fwd(dec, run, ys0.contiguous(), engine._f32c(self.z), sm, tm,
+                                                  self.dconds, False, plan)
         Tp = self.off + t0
         for li, sv in enumerate(saved[4]):                          # per layer: (x, m1, r1, sv1, ...); sv1[2] = q|k|v
             qkv = sv[3][2].view(n, Tp, 3 * d)

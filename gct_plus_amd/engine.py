@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 
@@ -30,9 +30,10 @@ _SEED = {"base": None, "ctr": 0}
 # when the compact rows are at most this fraction of all rows (the gathers cost ~1 ms per step).
 COMPACT_BWD = os.environ.get("GCT_COMPACT_BWD", "1") != "0"
 COMPACT_MAX_FRACTION = 0.85
-# Cross-attention over the visible rows of the encoder memory only (decoder_trunk_fwd): GCT_COMPACT_KV=0 disables.
+# The three shortcuts of the row plan (read by RowPlan.launch only, decided by plan_rows):
+# cross-attention over the visible rows of the encoder memory only: GCT_COMPACT_KV=0 disables.
 COMPACT_KV = os.environ.get("GCT_COMPACT_KV", "1") != "0"
-# Decoder FORWARD over the rows that reach the loss only (decoder_trunk_fwd(loss_rows=...)): GCT_COMPACT_FWD=0 disables.
+# decoder FORWARD over the rows that reach the loss only (loss_rows): GCT_COMPACT_FWD=0 disables.
 COMPACT_FWD = os.environ.get("GCT_COMPACT_FWD", "1") != "0"
 # K | V projections of the ENCODER self-attention over the visible rows only (mha_fwd): GCT_COMPACT_ENC_KV=0 disables.
 COMPACT_ENC_KV = os.environ.get("GCT_COMPACT_ENC_KV", "1") != "0"
@@ -55,81 +56,132 @@ def _grads_done(module, G: "GradSink"):
         GRAD_NOTIFY(ps, [G.out.get(p) for p in ps])
 
 
+# Callers of the row planner (plan_rows)
+MODEL = "model"          # the training-style forward, Vaetf / Cvaetf.forward (plan_ahead / prefetch included)
+DECODER = "decoder"      # a Decoder called on its own: model.decode, the samplers
+PREFILL = "prefill"      # decode.KVDecoder.prefill
+ENCODER = "encoder"      # the encoder called on its own: model.encode
+
+
+class RowMaps(NamedTuple):
+    """plan_rows' answer: which maps to build, and the rows each one covers (for the usable_* tests)."""
+    enc_keys: bool = False
+    dec_keys: bool = False
+    live: bool = False
+    nc_lat: int = 0          # visible condition rows in front of the decoder's memory (use_cond2lat)
+    enc_rows: int = 0        # B * Le
+    dec_rows: int = 0        # B * (Le + nc_lat)
+    live_rows: int = 0       # B * T, condition rows of use_cond2dec included
+
+
+def plan_rows(caller, B=0, T=0, Le=0, mask_shape=None, *, loss_rows=False, trg_mask=False, get_attn=False,
+              cond2dec=False, cond2lat=False, nconds=0, n_enc=0, n_dec=0, capturing=False, compact_fwd=False,
+              compact_kv=False, compact_enc_kv=False) -> RowMaps:
+    """Which row maps a caller builds -- the one owner of the three compaction shortcuts:
+      enc_keys  the visible rows of the encoder's key-padding mask  -> encoder self-attention K | V on those rows;
+      dec_keys  the visible rows of the decoder's memory            -> cross-attention K | V on those rows;
+      live      the decoder rows that reach the loss (loss_rows)    -> decoder forward and backward on those rows.
+    Pure: no launch, no environment.  T: target rows (without the condition rows of cond2dec); Le: rows of the encoder
+    memory; mask_shape: shape of the key-padding mask, None when there is none on the device; loss_rows, trg_mask:
+    whether the caller has them; the switches and `capturing` are RowPlan.launch's reads of COMPACT_* and the stream.
+    Each caller keeps the rules it had before the planner:
+      - under stream capture nothing is built (the maps' row counts would be baked into the graph);
+      - the model forward builds nothing with get_attn, and needs the reference's [B, 1, Le] mask;
+      - a decoder on its own (and prefill) compacts the memory keys with get_attn too, and needs B * Le mask elements;
+      - only the model forward maps the encoder's keys; the encoder on its own builds nothing;
+      - the live rows need loss_rows and a target mask, no cond2dec, no get_attn, and every attention of the trunk
+        within the direct kernels' key limit (ops.ATTN_DIRECT_MAX_KEYS: the forward over compact query rows)."""
+    c2d = cond2dec and nconds > 0
+    nc_lat = nconds if (not c2d and cond2lat and nconds > 0) else 0
+    Td, Lk = T + (nconds if c2d else 0), Le + nc_lat
+    none = RowMaps(nc_lat=nc_lat, enc_rows=B * Le, dec_rows=B * Lk, live_rows=B * Td)
+    if caller == ENCODER or capturing:
+        return none
+    if caller == MODEL:
+        if get_attn or mask_shape is None or tuple(mask_shape) != (B, 1, Le):
+            return none
+        mask_ok = True
+    elif caller in (DECODER, PREFILL):
+        mask_ok = mask_shape is not None and math.prod(mask_shape) == B * Le
+    else:
+        raise ValueError(f"plan_rows: unknown caller {caller!r}")
+    return none._replace(
+        enc_keys=bool(caller == MODEL and compact_enc_kv and n_enc > 0),
+        dec_keys=bool(mask_ok and compact_kv and n_dec > 0),
+        live=bool(compact_fwd and loss_rows and trg_mask and not get_attn and not c2d and n_dec > 0
+                  and Td <= ops.ATTN_DIRECT_MAX_KEYS and Lk <= ops.ATTN_DIRECT_MAX_KEYS))
+
+
 class RowPlan:
-    """The row maps of one training step, built and read back TOGETHER at the start of model.forward (one device->host
-    synchronisation per step, taken while the GPU is still finishing the previous step -- the host then runs ahead for the
-    whole step instead of stalling at the decoder's entry):
-      enc_keys  ops.KeyRows of the encoder's key-padding mask  -> K | V of the encoder self-attention on visible rows
-      dec_keys  ops.KeyRows of the decoder's memory mask       -> cross-attention K | V on visible rows
-      live      ops.LiveRows of the rows that reach the loss   -> decoder forward / backward on those rows
-    Each is None when its shortcut does not apply (switch off, mask not a prefix, too little to gain)."""
+    """The row maps of a forward (plan_rows decides which): launched together with ONE asynchronous read-back of their
+    info records, used after finish().  The model forward launches its plan at its start -- or the trainer a step ahead,
+    between a step's forward and its backward (Model/forward_propagation1.prefetch), so that the read-back completes
+    while that backward runs and the next forward never waits for the device.  After finish():
+      enc_keys  ops.KeyRows of the encoder's key-padding mask, or None
+      dec_keys  ops.KeyRows of the decoder's memory mask, or None
+      live      ops.LiveRows of the rows that reach the loss, or None: the decoder returns these rows COMPACT and the
+                caller scatters them (ScatterRowsFn)
+    A map the read-back shows to be unusable (usable_keys / usable_live) is None too."""
 
-    def __init__(self, enc_keys=None, dec_keys=None, live=None):
-        self.enc_keys, self.dec_keys, self.live = enc_keys, dec_keys, live
-
-    @staticmethod
-    def usable_keys(kr, rows):
-        if kr is None:
-            return None
-        h = kr.host()
-        ok = h["nonprefix"] == 0 and h["empty"] == 0 and 0 < h["padded"] <= COMPACT_MAX_FRACTION * rows
-        return kr if ok else None
+    def __init__(self, ek=None, dk=None, lr=None, rows=(0, 0, 0)):
+        self._maps, self._rows = (ek, dk, lr), rows
+        self._pending = ops.PendingReadBack(ek, dk, lr)          # ONE read-back for all three
+        self._usable = None
+        self.enc_keys = self.dec_keys = self.live = None
 
     @staticmethod
-    def usable_live(lr, rows):
-        if lr is None:
-            return None
-        h = lr.host()
-        ok = h["violations"] == 0 and h["nonprefix"] == 0 and 0 < h["padded"] <= COMPACT_MAX_FRACTION * rows
-        return lr if ok else None
+    def usable_keys(h, rows):
+        """A KeyRows map (host info record h, over `rows` rows) pays and is exact: every sample's visible keys are a
+        prefix, none is empty, and some -- not more than COMPACT_MAX_FRACTION -- remain."""
+        return h["nonprefix"] == 0 and h["empty"] == 0 and 0 < h["padded"] <= COMPACT_MAX_FRACTION * rows
+
+    @staticmethod
+    def usable_live(h, rows):
+        """A LiveRows map: no live query sees a dead row, the live rows are a prefix, and the compaction pays."""
+        return h["violations"] == 0 and h["nonprefix"] == 0 and 0 < h["padded"] <= COMPACT_MAX_FRACTION * rows
 
     @classmethod
-    def build(cls, src_mask_u8, trg_mask_u8, loss_rows, B, Le, T, nc_lat, n_layers_enc, n_layers_dec):
-        """src_mask_u8 [B, Le] (encoder keys, condition rows included); the decoder's memory mask is the same with nc_lat
-        visible condition rows in front (use_cond2lat); loss_rows uint8 [B, T] or None."""
-        return cls.launch(src_mask_u8, trg_mask_u8, loss_rows, B, Le, T, nc_lat, n_layers_enc, n_layers_dec).finish()
-
-    @classmethod
-    def launch(cls, src_mask_u8, trg_mask_u8, loss_rows, B, Le, T, nc_lat, n_layers_enc, n_layers_dec):
-        """build() in two halves: the map kernels and ONE asynchronous read-back are queued here, .finish() of the
-        returned object waits for that read-back alone and returns the plan.  Queued a step ahead (between a step's
-        forward and its backward: Model/forward_propagation1.prefetch), the maps of the NEXT batch reach the host while
-        this step's backward runs, and the next forward starts without the host ever waiting for the device."""
-        if torch.cuda.is_current_stream_capturing() or src_mask_u8 is None or src_mask_u8.numel() != B * Le:
-            return _PendingPlan(None, None, None, None, 0, 0, 0)
-        sm = src_mask_u8.view(B, Le)
-        ek = ops.KeyRows(sm, B, Le) if (COMPACT_ENC_KV and n_layers_enc > 0) else None
-        dk = None
-        if COMPACT_KV and n_layers_dec > 0:
-            if nc_lat > 0:
-                ones = torch.ones(B, nc_lat, dtype=torch.uint8, device=sm.device)
-                dk = ops.KeyRows(torch.cat([ones, sm], dim=1).contiguous(), B, Le + nc_lat)
-            elif ek is not None:
-                dk = ek                                  # the same mask: one map serves both trunks
-            else:
-                dk = ops.KeyRows(sm, B, Le)
-        lr = None
-        if (COMPACT_FWD and loss_rows is not None and trg_mask_u8 is not None and T <= ops.ATTN_DIRECT_MAX_KEYS
-                and Le + nc_lat <= ops.ATTN_DIRECT_MAX_KEYS and n_layers_dec > 0):
-            lr = ops.LiveRows.from_rows(loss_rows.reshape(B, T), B, T, trg_mask_u8)
-        return _PendingPlan(ek, dk, lr, ops.PendingReadBack(ek, dk, lr),   # ONE read-back for all three
-                            B * Le, B * (Le + nc_lat), B * T)
-
-
-class _PendingPlan:
-    def __init__(self, ek, dk, lr, pending, rows_e, rows_d, rows_t):
-        self.ek, self.dk, self.lr, self.pending = ek, dk, lr, pending
-        self.rows = (rows_e, rows_d, rows_t)
+    def launch(cls, caller, dec=None, src_mask=None, trg_mask=None, loss_rows=None, B=0, T=0, Le=0, n_enc=0):
+        """Launch what plan_rows(caller, ...) asks for.  dec: the decoder whose flags and layers count; src_mask /
+        trg_mask: the masks as the trunks get them; loss_rows: bool / uint8 [B, T] or None; n_enc: encoder layers."""
+        shape = None if (src_mask is None or not src_mask.is_cuda) else tuple(src_mask.shape)
+        want = plan_rows(caller, B, T, Le, shape, loss_rows=loss_rows is not None, trg_mask=trg_mask is not None,
+                         get_attn=getattr(dec, "get_attn", False), cond2dec=getattr(dec, "use_cond2dec", False),
+                         cond2lat=getattr(dec, "use_cond2lat", False), nconds=getattr(dec, "nconds", 0), n_enc=n_enc,
+                         n_dec=0 if dec is None else len(dec.layers), capturing=torch.cuda.is_current_stream_capturing(),
+                         compact_fwd=COMPACT_FWD, compact_kv=COMPACT_KV, compact_enc_kv=COMPACT_ENC_KV)
+        if not (want.enc_keys or want.dec_keys or want.live):
+            return cls()
+        ek = dk = lr = None
+        if want.enc_keys or want.dec_keys:
+            sm = ops.to_mask_u8(src_mask).view(B, Le)
+            if want.enc_keys:
+                ek = ops.KeyRows(sm, B, Le)
+            if want.dec_keys and want.nc_lat > 0:
+                ones = torch.ones(B, want.nc_lat, dtype=torch.uint8, device=sm.device)
+                dk = ops.KeyRows(torch.cat([ones, sm], dim=1).contiguous(), B, Le + want.nc_lat)
+            elif want.dec_keys:
+                dk = ek if ek is not None else ops.KeyRows(sm, B, Le)   # the same mask: one map serves both trunks
+        if want.live:                                    # (never with cond2dec: T is all the decoder's rows)
+            lr = ops.LiveRows.from_rows(loss_rows.to(torch.uint8).contiguous().reshape(B, T), B, T,
+                                        ops.to_mask_u8(trg_mask))
+        return cls(ek, dk, lr, (want.enc_rows, want.dec_rows, want.live_rows))
 
     def finish(self) -> "RowPlan":
-        if self.pending is None:
-            return RowPlan()
-        self.pending.finish()                            # the step's ONE host synchronisation
-        plan = RowPlan(RowPlan.usable_keys(self.ek, self.rows[0]), RowPlan.usable_keys(self.dk, self.rows[1]),
-                       RowPlan.usable_live(self.lr, self.rows[2]))
-        if plan.live is not None:
-            plan.live.fwd = True
-        return plan
+        """Wait for the read-back (once) and keep the usable maps.  Under stream capture the live map is left out (the
+        decoder then runs on every row) and the key maps are kept."""
+        if self._usable is None:
+            self._pending.finish()                       # the forward's ONE host synchronisation
+            (ek, dk, lr), (re, rd, rt) = self._maps, self._rows
+            self._usable = (ek if ek is not None and self.usable_keys(ek.host(), re) else None,
+                            dk if dk is not None and self.usable_keys(dk.host(), rd) else None,
+                            lr if lr is not None and self.usable_live(lr.host(), rt) else None)
+            if self._usable[2] is not None:
+                self._usable[2].fwd = True
+        self.enc_keys, self.dec_keys, self.live = self._usable
+        if self.live is not None and torch.cuda.is_current_stream_capturing():
+            self.live = None
+        return self
 
 
 def next_seed() -> int:
@@ -431,10 +483,11 @@ def _pe2d(pe_mod, L):
     return pe[0]
 
 
-def encoder_trunk_fwd(enc, run: Run, src, mask_u8, econds, want_probs=False, keys=None):
+def encoder_trunk_fwd(enc, run: Run, src, mask_u8, econds, want_probs, plan: RowPlan):
     """Model/vaetf.py:32-54 (up to the final Norm).  Returns x [B, n_c+S, d] and saved state.
-    keys (ops.KeyRows of the key-padding mask, usable(): checked by the caller): the K | V projections of every layer
-    run on the visible rows only (mha_fwd)."""
+    plan.enc_keys (ops.KeyRows of the key-padding mask): the K | V projections of every layer run on the visible rows
+    only (mha_fwd)."""
+    keys = plan.enc_keys
     B, S = src.shape
     d, nc = enc.d_model, enc.nconds
     cond = None
@@ -478,20 +531,22 @@ def encoder_trunk_bwd(enc, run: Run, saved, dy, G: GradSink):
                              G(enc.embed_cond2enc.bias))
 
 
-def decoder_trunk_fwd(dec, run: Run, trg, z, src_mask_u8, trg_mask_u8, dconds, want_probs=False, loss_rows=None,
-                      plan=None):
-    """Model/vaetf.py:79-114.  z [B, L_e, latent].
-    loss_rows (uint8 [B, T], optional): the decoder rows whose output reaches the loss (the reference's cross-entropy
-    ignores the rows of padded targets, Train/trainer1.py:21-22: 56 % of the rows at MOSES-like lengths).  A row outside
-    the set influences a row inside it only as a KEY of self-attention, so when no live query can see a dead row under
-    THIS call's trg_mask (checked on the device, as for the compacted backward) the whole trunk runs on the quad-
-    compacted live rows: every GEMM, Norm and attention launch sees ~half the rows, every dropout site draws the bits of
-    the original coordinates, the backward finds its activations compact already.  When the shortcut is taken the trunk
-    RETURNS THE COMPACT ROWS [Mc, d] and the map (saved[-1]); whoever scatters them back (ScatterRowsFn: Decoder.forward
-    for a caller of the decoder alone, Vaetf / Cvaetf.forward behind the vocabulary head) produces zeros on the skipped
-    rows -- or, for the few padded rows that share an aligned group of four rows with a live one, finite values without
-    meaning -- not the reference's values (nothing downstream of an ignore_index loss reads them), and reports a
-    gradient that arrives on a skipped row as an error (ops.LiveRows.check_grad)."""
+def decoder_trunk_fwd(dec, run: Run, trg, z, src_mask_u8, trg_mask_u8, dconds, want_probs, plan: RowPlan):
+    """Model/vaetf.py:79-114.  z [B, L_e, latent].  The trunk takes the shortcuts of `plan` (RowPlan, finished):
+      dec_keys  the visible rows of the encoder memory: padded rows are masked keys of every cross-attention, their
+                K / V projections are never used and their dK / dV are zero, so the six K|V GEMMs, their weight
+                gradients and the gradient w.r.t. the memory run on the visible rows only (quad-compacted, ops.KeyRows);
+      live      the decoder rows whose output reaches the loss (the reference's cross-entropy ignores the rows of padded
+                targets, Train/trainer1.py:21-22: 56 % of the rows at MOSES-like lengths).  A row outside the set
+                influences a row inside it only as a KEY of self-attention, and the map was checked on the device
+                against this call's trg_mask (no live query sees a dead row), so the whole trunk runs on the quad-
+                compacted live rows: every GEMM, Norm and attention launch sees ~half the rows, every dropout site draws
+                the bits of the original coordinates, the backward finds its activations compact already.  The trunk
+                then RETURNS THE COMPACT ROWS [Mc, d]; whoever scatters them back (ScatterRowsFn: Decoder.forward for a
+                caller of the decoder alone, Vaetf / Cvaetf.forward behind the vocabulary head) produces zeros on the
+                skipped rows -- or, for the few padded rows that share an aligned group of four rows with a live one,
+                finite values without meaning -- not the reference's values (nothing downstream of an ignore_index loss
+                reads them), and reports a gradient that arrives on a skipped row as an error (ops.LiveRows.check_grad)."""
     B, T0 = trg.shape
     d, nc = dec.d_model, dec.nconds
     Le, lat = z.shape[1], z.shape[2]
@@ -521,33 +576,7 @@ def decoder_trunk_fwd(dec, run: Run, trg, z, src_mask_u8, trg_mask_u8, dconds, w
             ones = torch.ones(B, nc, dtype=torch.uint8, device=src_mask_u8.device)
             src_mask_u8 = torch.cat([ones, src_mask_u8.view(B, Le)], dim=1).contiguous()
     lsv, p1s, p2s = [], [], []
-    capturing = torch.cuda.is_current_stream_capturing()
-    # Row maps.  `plan` (engine.RowPlan, built and read back at the start of model.forward): use what it validated.
-    # Without one (the decoder called on its own, decode prefill) they are built here -- their kernels are queued before
-    # either is read, so both come back in one synchronisation:
-    #   live  the rows that reach the loss (loss_rows): forward and backward of the trunk run on them only;
-    #   keys  the visible rows of the encoder memory: padded rows are masked keys of every cross-attention, their K / V
-    #         projections are never used and their dK / dV are zero, so the six K|V GEMMs, their weight gradients and
-    #         the gradient w.r.t. the memory run on the visible rows only (quad-compacted, ops.KeyRows).
-    live, keys = None, None
-    fwd_ok = (not c2d and not want_probs and T <= ops.ATTN_DIRECT_MAX_KEYS and Lk <= ops.ATTN_DIRECT_MAX_KEYS
-              and len(dec.layers) > 0 and not capturing and trg_mask_u8 is not None)
-    if plan is not None:
-        live = plan.live if fwd_ok else None
-        keys = plan.dec_keys if (src_mask_u8 is not None and src_mask_u8.numel() == B * Lk) else None
-    else:
-        lr = kr = None
-        if COMPACT_FWD and loss_rows is not None and fwd_ok:
-            tm_u8 = trg_mask_u8.u8 if isinstance(trg_mask_u8, ops.MaskBits) else trg_mask_u8
-            lr = ops.LiveRows.from_rows(loss_rows.reshape(B, T), B, T, tm_u8)
-        if (COMPACT_KV and src_mask_u8 is not None and src_mask_u8.numel() == B * Lk and len(dec.layers) > 0
-                and not capturing):
-            kr = ops.KeyRows(src_mask_u8.view(B, Lk), B, Lk)
-        ops.read_back(lr, kr)
-        live = RowPlan.usable_live(lr, B * T)
-        keys = RowPlan.usable_keys(kr, B * Lk)
-        if live is not None:
-            live.fwd = True
+    live, keys = plan.live, plan.dec_keys
     if live is not None:
         x = live.gather(x)
     if keys is not None:
@@ -563,7 +592,7 @@ def decoder_trunk_fwd(dec, run: Run, trg, z, src_mask_u8, trg_mask_u8, dconds, w
     saved = (trg, z2, dconds, site_pe, lsv, x, mean, rstd, B, T, Le, Lk, c2d, c2l,
              trg_mask_u8.u8 if isinstance(trg_mask_u8, ops.MaskBits) else trg_mask_u8, keys, live)
     if live is not None:
-        return y, saved, p1s, p2s        # [Mc, d] COMPACT rows: the caller owns `saved[-1]` (the map) and scatters what it needs
+        return y, saved, p1s, p2s        # [Mc, d] COMPACT rows: the caller holds the plan and scatters what it needs
     return y.view(B, T, d), saved, p1s, p2s
 
 
@@ -579,45 +608,34 @@ def decoder_trunk_bwd(dec, run: Run, saved, dy, G: GradSink, need_dz=True):
     # (csrc/liverows.hip).  When it holds (and pays), the whole decoder backward runs on the QUAD-COMPACTED live
     # rows: every GEMM, norm and dropout backward sees ~half the rows; otherwise the dense path runs, with the
     # weight-gradient GEMMs reducing over the live token tiles (the list names every tile when the check fails).
-    live = None
+    live, lr = live_fwd, None
+    if live_fwd is None:
+        lr = ops.LiveRows(dy.reshape(B * T, d), B, T, trg_mask_u8) if (COMPACT_BWD or (B * T) % 32 == 0) else None
+        if COMPACT_BWD and len(dec.layers) > 0 and not torch.cuda.is_current_stream_capturing():
+            live = lr if RowPlan.usable_live(lr.host(), B * T) else None       # one 32-byte read-back per step
     if live_fwd is not None:
         # the forward ran on these rows only and handed out COMPACT rows: dy arrives compact (ScatterRowsFn gathers the
         # gradient of what it scattered and reports gradient rows that fell on skipped rows)
-        live = live_fwd
-        lr = None
-        g = dy.reshape(live.Mc, d)
+        g = dy.reshape(live.Mc, d).clone()
+    elif live is not None:
+        g = live.gather(dy.reshape(B * T, d))
     else:
-        g = dy.reshape(B * T, d)
-        lr = ops.LiveRows(g, B, T, trg_mask_u8) if (COMPACT_BWD or (B * T) % 32 == 0) else None
-    if live is None and COMPACT_BWD and lr is not None and len(dec.layers) > 0 and not torch.cuda.is_current_stream_capturing():
-        h = lr.host()                                   # one 32-byte read-back per step
-        if h["violations"] == 0 and h["nonprefix"] == 0 and 0 < h["padded"] <= COMPACT_MAX_FRACTION * B * T:
-            live = lr
-    if live is not None:
-        gc = g.clone() if live_fwd is not None else live.gather(g)
-        gdbuf = live.empty(d) if run.p > 0 else None
-        dr = _ffn_drop(run, lsv[-1][-1], gdbuf)
-        ops.norm_bwd(gc, x_last, dec.norm.alpha, mean, rstd, G(dec.norm.alpha), G(dec.norm.bias), out=gc,
-                     eps=dec.norm.eps, live=live, drop=dr)
-        gd = None if dr is None else gdbuf
-        de = new_de()
-        for i in range(len(lsv) - 1, -1, -1):
-            gc, gd = dec_layer_bwd(run, dec.layers[i], lsv[i], gc, de, i == len(lsv) - 1, G, live=live, gd=gd,
-                                   gdbuf=gdbuf, below=lsv[i - 1][-1] if i > 0 else None)
-        g = live.scatter(gc)                            # back to [B*T, d]: zero rows where nothing was live
-    else:
-        g = g.clone()
+        g = dy.reshape(B * T, d).clone()
         run.kt = lr.kt if (lr is not None and (B * T) % 32 == 0) else None
-        gdbuf = torch.empty_like(g) if (run.p > 0 and len(lsv) > 0) else None
-        dr = _ffn_drop(run, lsv[-1][-1] if lsv else None, gdbuf)
-        ops.norm_bwd(g, x_last, dec.norm.alpha, mean, rstd, G(dec.norm.alpha), G(dec.norm.bias), out=g,
-                     eps=dec.norm.eps, drop=dr)
-        gd = None if dr is None else gdbuf
-        de = new_de()
-        for i in range(len(lsv) - 1, -1, -1):
-            g, gd = dec_layer_bwd(run, dec.layers[i], lsv[i], g, de, i == len(lsv) - 1, G, gd=gd, gdbuf=gdbuf,
-                                  below=lsv[i - 1][-1] if i > 0 else None)
-        run.kt = None
+    gdbuf = None
+    if run.p > 0 and len(lsv) > 0:
+        gdbuf = torch.empty_like(g) if live is None else live.empty(d)
+    dr = _ffn_drop(run, lsv[-1][-1] if lsv else None, gdbuf)
+    ops.norm_bwd(g, x_last, dec.norm.alpha, mean, rstd, G(dec.norm.alpha), G(dec.norm.bias), out=g,
+                 eps=dec.norm.eps, live=live, drop=dr)
+    gd = None if dr is None else gdbuf
+    de = new_de()
+    for i in range(len(lsv) - 1, -1, -1):
+        g, gd = dec_layer_bwd(run, dec.layers[i], lsv[i], g, de, i == len(lsv) - 1, G, live=live, gd=gd,
+                              gdbuf=gdbuf, below=lsv[i - 1][-1] if i > 0 else None)
+    run.kt = None
+    if live is not None:
+        g = live.scatter(g)                             # back to [B*T, d]: zero rows where nothing was live
     if len(dec.layers) == 0:
         de.zero_()
     if keys is not None:
@@ -654,8 +672,8 @@ def _f32c(t):
 
 class EncoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, enc, run, src, mask_u8, econds, want_probs, keys, *params):
-        y, saved, probs = encoder_trunk_fwd(enc, run, src, mask_u8, econds, want_probs, keys=keys)
+    def forward(ctx, enc, run, src, mask_u8, econds, want_probs, plan, *params):
+        y, saved, probs = encoder_trunk_fwd(enc, run, src, mask_u8, econds, want_probs, plan)
         ctx.enc, ctx.run, ctx.saved, ctx.params = enc, run, saved, params
         if want_probs:
             for p in probs:
@@ -673,12 +691,10 @@ class EncoderFn(torch.autograd.Function):
 
 class DecoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, dec, run, trg, z, src_mask_u8, trg_mask_u8, dconds, want_probs, loss_rows, plan, *params):
-        y, saved, p1, p2 = decoder_trunk_fwd(dec, run, trg, _f32c(z), src_mask_u8, trg_mask_u8,
-                                             dconds, want_probs, loss_rows=loss_rows, plan=plan)
+    def forward(ctx, dec, run, trg, z, src_mask_u8, trg_mask_u8, dconds, want_probs, plan, *params):
+        y, saved, p1, p2 = decoder_trunk_fwd(dec, run, trg, _f32c(z), src_mask_u8, trg_mask_u8, dconds, want_probs,
+                                             plan)      # plan.live: y holds the COMPACT live rows [Mc, d]
         ctx.dec, ctx.run, ctx.saved, ctx.params = dec, run, saved, params
-        dec._gct_live_out = saved[-1]          # not None: y holds the COMPACT live rows [Mc, d] (Decoder.forward hands
-                                               # the map to its caller, who scatters what it needs: ScatterRowsFn)
         ctx.need_dz = z.requires_grad
         if want_probs:
             for p in p1 + p2:
@@ -691,7 +707,7 @@ class DecoderFn(torch.autograd.Function):
         G = GradSink()
         dz = decoder_trunk_bwd(ctx.dec, ctx.run, ctx.saved, _f32c(dy), G, ctx.need_dz)
         ctx.saved = None
-        return (None, None, None, dz, None, None, None, None, None, None) + G.collect(ctx.params)
+        return (None, None, None, dz, None, None, None, None, None) + G.collect(ctx.params)
 
 
 class ScatterRowsFn(torch.autograd.Function):

@@ -499,7 +499,7 @@ class LiveRows:
 
     def host(self):
         if self._host is None:
-            read_back(self)                                 # ONE read-back (also of the skipped-row gradient counter)
+            PendingReadBack(self).finish()                  # ONE read-back (also of the skipped-row gradient counter)
         return self._host
 
     def scatter_add(self, src2d, dst2d):
@@ -546,30 +546,15 @@ class LiveRows:
         return dst
 
 
-HOST_BLOCKED_S = [0.0]      # host seconds spent waiting in read_back (the one synchronisation of a training step)
-
-
-def read_back(*objs):
-    """host() of several LiveRows / KeyRows with ONE device->host copy (one synchronisation instead of one each)."""
-    objs = [o for o in objs if o is not None and o._host is None]
-    if not objs:
-        return
-    import time
-    t0 = time.perf_counter()
-    v = torch.cat([o.info for o in objs] + [skipped_row_gradients()]).tolist()
-    HOST_BLOCKED_S[0] += time.perf_counter() - t0
-    for i, o in enumerate(objs):
-        o._fill_host(v[8 * i:8 * i + 8])
-    if v[-1] != 0:
-        skipped_row_gradients().zero_()
-        raise _lib.GctError(_SKIPPED_MSG.format(v[-1]))
+HOST_BLOCKED_S = [0.0]      # host seconds spent waiting in PendingReadBack.finish (a training step's one synchronisation)
 
 
 class PendingReadBack:
-    """read_back() in two halves: the constructor queues ONE asynchronous device->host copy of the maps' info records
-    (and of the skipped-row gradient counter) behind the kernels that wrote them and records an event; finish() waits
-    for that event only -- not for whatever was queued on the stream afterwards -- and fills the host side in.  The
-    trainer queues a batch's maps one step ahead (Model/forward_propagation1.prefetch), so finish() finds them done."""
+    """host() of several LiveRows / KeyRows with ONE device->host copy, in two halves: the constructor queues the
+    asynchronous copy of the maps' info records (and of the skipped-row gradient counter) behind the kernels that wrote
+    them and records an event; finish() waits for that event only -- not for whatever was queued on the stream
+    afterwards -- and fills the host side in.  The trainer queues a batch's maps one step ahead
+    (Model/forward_propagation1.prefetch), so finish() finds them done."""
 
     def __init__(self, *objs):
         seen, self.objs = set(), []

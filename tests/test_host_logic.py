@@ -162,3 +162,126 @@ def test_synthetic_layout():
     lens = (ds["src"] != 1).sum(1)
     eos = ds["trg"].gather(1, (lens + 1).unsqueeze(1)).squeeze(1)
     assert (eos == synthetic.EOS_ID).all()
+
+
+def _plan(caller, **kw):
+    """engine.plan_rows with the trainer's case as the default: all switches on, loss rows and a target mask, the
+    reference's [B, 1, Le] key-padding mask, 6 + 6 layers."""
+    from gct_plus_amd import engine
+    B, T, Le = kw.pop("B", 4), kw.pop("T", 60), kw.pop("Le", 70)
+    args = dict(loss_rows=True, trg_mask=True, n_enc=6, n_dec=6, compact_fwd=True, compact_kv=True,
+                compact_enc_kv=True)
+    args.update(kw)
+    shape = args.pop("mask_shape", (B, 1, Le))
+    want = engine.plan_rows(caller, B, T, Le, shape, **args)
+    return (want.enc_keys, want.dec_keys, want.live)
+
+
+def test_row_planner_decision_table():
+    """engine.plan_rows: which of the three row maps (encoder keys, decoder memory keys, loss rows) each caller builds.
+    The callers keep the rules they had when each decided on its own: the model forward builds nothing with get_attn
+    and needs a [B, 1, Le] mask; a decoder on its own (and prefill) still compacts the memory keys with get_attn and
+    needs only B * Le mask elements; nothing under stream capture; the encoder on its own builds nothing."""
+    from gct_plus_amd import engine, ops
+    M, D, P, E = engine.MODEL, engine.DECODER, engine.PREFILL, engine.ENCODER
+    K = ops.ATTN_DIRECT_MAX_KEYS
+    assert K == 96
+    # each caller, the trainer's case
+    assert _plan(M) == (True, True, True)
+    assert _plan(D) == (False, True, True)
+    assert _plan(P, loss_rows=False) == (False, True, False)
+    assert _plan(E) == (False, False, False)
+    # get_attn: the model forward builds nothing, a decoder alone still maps its memory keys
+    assert _plan(M, get_attn=True) == (False, False, False)
+    assert _plan(D, get_attn=True) == (False, True, False)
+    # cond2dec: no live rows (and T counts the condition rows); without conditions the flag is inert
+    assert _plan(M, cond2dec=True, nconds=3) == (True, True, False)
+    assert _plan(D, cond2dec=True, nconds=3) == (False, True, False)
+    assert _plan(M, cond2dec=True, nconds=0) == (True, True, True)
+    w = engine.plan_rows(M, 4, 60, 70, (4, 1, 70), cond2dec=True, cond2lat=True, nconds=3)
+    assert (w.nc_lat, w.live_rows, w.dec_rows) == (0, 4 * 63, 4 * 70)
+    # cond2lat: the decoder's memory has nconds visible rows in front; they count against the key limit
+    w = engine.plan_rows(M, 4, 60, 70, (4, 1, 70), cond2lat=True, nconds=3, compact_kv=True)
+    assert (w.nc_lat, w.enc_rows, w.dec_rows, w.live_rows) == (3, 4 * 70, 4 * 73, 4 * 60)
+    for c in (M, D):
+        assert _plan(c, Le=K - 3, mask_shape=(4, 1, K - 3), cond2lat=True, nconds=3)[2]
+        assert not _plan(c, Le=K - 2, mask_shape=(4, 1, K - 2), cond2lat=True, nconds=3)[2]
+        assert _plan(c, Le=K - 2, mask_shape=(4, 1, K - 2), cond2lat=True, nconds=3)[1]    # keys have no limit
+    # T and Le + nc_lat at the direct kernels' key limit, 96, and one above
+    for c in (M, D):
+        assert _plan(c, T=K)[2] and not _plan(c, T=K + 1)[2]
+        assert _plan(c, Le=K, mask_shape=(4, 1, K))[2] and not _plan(c, Le=K + 1, mask_shape=(4, 1, K + 1))[2]
+        assert _plan(c, T=K - 3, cond2dec=True, nconds=3)[2] is False                 # (cond2dec: never)
+    assert _plan(M, T=K + 1) == (True, True, False) and _plan(D, Le=K + 1, mask_shape=(4, 1, K + 1)) == (False, True, False)
+    # switches off, one at a time
+    assert _plan(M, compact_fwd=False) == (True, True, False)
+    assert _plan(M, compact_kv=False) == (True, False, True)
+    assert _plan(M, compact_enc_kv=False) == (False, True, True)
+    assert _plan(D, compact_kv=False) == (False, False, True)
+    assert _plan(D, compact_enc_kv=False) == (False, True, True)
+    # stream capture: nothing, for every caller
+    for c in (M, D, P, E):
+        assert _plan(c, capturing=True) == (False, False, False)
+    # no target mask / no loss rows: no live rows
+    for c in (M, D):
+        assert not _plan(c, trg_mask=False)[2] and not _plan(c, loss_rows=False)[2]
+    # the key-padding mask: the model forward wants [B, 1, Le]; a decoder alone any shape of B * Le elements
+    assert _plan(M, mask_shape=(4, 70)) == (False, False, False)
+    assert _plan(M, mask_shape=(4, 60, 70)) == (False, False, False)
+    assert _plan(M, mask_shape=None) == (False, False, False)
+    assert _plan(D, mask_shape=(4, 70)) == (False, True, True)
+    assert _plan(D, mask_shape=(4, 1, 70)) == (False, True, True)
+    assert _plan(D, mask_shape=(4, 60, 70)) == (False, False, True)
+    assert _plan(D, mask_shape=None) == (False, False, True)
+    assert _plan(P, mask_shape=(4, 60, 70), loss_rows=False) == (False, False, False)
+    # zero layers
+    assert _plan(M, n_enc=0) == (False, True, True)
+    assert _plan(M, n_dec=0) == (True, False, False)
+    assert _plan(D, n_dec=0) == (False, False, False)
+    with pytest.raises(ValueError):
+        _plan("trainer")
+
+
+def test_row_map_usable_tests():
+    """RowPlan.usable_keys / usable_live, pure functions of a map's host info record: exact (every prefix, no
+    violation, no empty sample for keys) and worth it (0 < compact rows <= COMPACT_MAX_FRACTION of all rows)."""
+    from gct_plus_amd import engine
+    assert engine.COMPACT_MAX_FRACTION == 0.85
+    rows = 1000
+    h = dict(n_live=500, violations=0, nonprefix=0, tiles=20, padded=512, quads=128, empty=0)
+    keys, live = engine.RowPlan.usable_keys, engine.RowPlan.usable_live
+    assert keys(h, rows) and live(h, rows)
+    assert keys(dict(h, padded=850), rows) and live(dict(h, padded=850), rows)              # at the boundary
+    assert not keys(dict(h, padded=852), rows) and not live(dict(h, padded=852), rows)      # above it
+    assert not keys(dict(h, padded=0), rows) and not live(dict(h, padded=0), rows)          # nothing left
+    assert not keys(dict(h, nonprefix=1), rows) and not live(dict(h, nonprefix=1), rows)    # a non-prefix mask
+    assert not live(dict(h, violations=1), rows) and keys(dict(h, violations=1), rows)      # (keys: no such check)
+    assert not keys(dict(h, empty=1), rows) and live(dict(h, empty=1), rows)                # (live: no such check)
+
+
+class _FakeMap:
+    """A row map whose info record is already on the host (no device work in RowPlan / PendingReadBack)."""
+
+    def __init__(self, padded):
+        self._host = dict(n_live=8, violations=0, nonprefix=0, tiles=1, padded=padded, quads=2, empty=0)
+
+    def host(self):
+        return self._host
+
+
+def test_row_plan_finish(monkeypatch):
+    """RowPlan.finish(): keeps the usable maps, can be called more than once, and a plan finished under stream capture
+    keeps its key maps but not its live map (the decoder then runs on every row)."""
+    from gct_plus_amd import engine
+    ek, dk, lr, bad = _FakeMap(8), _FakeMap(8), _FakeMap(8), _FakeMap(0)
+    plan = engine.RowPlan(ek, dk, lr, (16, 16, 16))
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
+    assert plan.finish() is plan
+    assert (plan.enc_keys, plan.dec_keys, plan.live) == (ek, dk, lr) and lr.fwd is True
+    assert plan.finish() is plan and (plan.enc_keys, plan.dec_keys, plan.live) == (ek, dk, lr)
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
+    assert (plan.finish().enc_keys, plan.dec_keys, plan.live) == (ek, dk, None)
+    plan = engine.RowPlan(bad, dk, bad, (16, 16, 16)).finish()
+    assert (plan.enc_keys, plan.dec_keys, plan.live) == (None, dk, None)
+    empty = engine.RowPlan().finish()
+    assert (empty.enc_keys, empty.dec_keys, empty.live) == (None, None, None)

@@ -582,7 +582,7 @@ def test_zero_gradient_rows_with_arbitrary_masks_vs_oracle(case):
                                             ("vaetf", dict(N=2, d_model=512, dff=2048, h=8, latent_dim=128), 48, 80, 0.1)])
 def test_compacted_decoder_backward_matches_dense(mtype, kw, B, S, p, monkeypatch):
     """The decoder backward on quad-compacted live rows (engine.decoder_trunk_bwd, csrc/liverows.hip) and the
-    cross-attention K / V path on the visible rows of the encoder memory only (engine.decoder_trunk_fwd, ops.KeyRows)
+    cross-attention K / V path on the visible rows of the encoder memory only (engine.RowPlan, ops.KeyRows)
     against the dense paths on the same inputs, seeds and dropout masks: loss and every parameter gradient.  The dropout cases prove that
     the mask of a compact quad is regenerated from its ORIGINAL quad (GEMM epilogue, dropout backward, attention)."""
     from gct_plus_amd import engine
@@ -631,7 +631,7 @@ def _fwd_loss_skip(model, mtype, batch, beta, skip):
                                             ("vaetf", dict(N=2, d_model=512, dff=2048, h=8, latent_dim=128), 48, 80, 0.1)])
 def test_decoder_forward_over_loss_rows_matches_dense(mtype, kw, B, S, p, monkeypatch):
     """forward_propagation(..., skip_ignored=True) -- the trainer's mode: the decoder forward AND backward run on the
-    quad-compacted rows whose logits reach the ignore_index loss (engine.decoder_trunk_fwd(loss_rows=...)) -- against
+    quad-compacted rows whose logits reach the ignore_index loss (engine.RowPlan.live) -- against
     the dense model on the same inputs, seeds and dropout masks: the loss, every parameter gradient, the logits of the
     rows the loss reads; the skipped rows come back as zeros (the vocabulary head runs on the compact rows too).  The dropout cases prove that
     every dropout site of the compact forward (GEMM epilogues, attention) draws the bits of the ORIGINAL coordinates."""
@@ -832,10 +832,12 @@ def test_deferred_slab_reductions_give_identical_gradients(mtype, full, batch, m
 
 
 @pytest.mark.parametrize("mtype", ["vaetf", "pscavaetf"])
-def test_announced_batch_gives_the_same_step(mtype):
+def test_announced_batch_gives_the_same_step(mtype, monkeypatch):
     """forward_propagation1.prefetch queues a batch's masks and row maps ahead of the forward that uses them (the
     trainer: between the previous step's forward and its backward).  Same logits, loss and gradients, bit for bit, as the
-    un-announced call; an announcement for ANOTHER batch, or for a batch modified since, is dropped."""
+    un-announced call; an announcement for ANOTHER batch, for a batch modified since, or for a batch dict whose tensors
+    are views of the announced ones (same address, shape and version) is dropped: that forward plans its own rows."""
+    from gct_plus_amd import engine
     from gct_plus_amd.Model import forward_propagation
     from gct_plus_amd.Model.forward_propagation1 import prefetch
     from gct_plus_amd.Train.trainer1 import loss_function
@@ -843,34 +845,46 @@ def test_announced_batch_gives_the_same_step(mtype):
     nc = synthetic.n_conds(mtype)
     b1 = to_dev(synthetic.make_dataset(9, max_len=24, model_type=mtype, seed=11))
     b2 = to_dev(synthetic.make_dataset(9, max_len=24, model_type=mtype, seed=12))
+    plans = []
+    real = engine.plan_rows
+    monkeypatch.setattr(engine, "plan_rows", lambda caller, *a, **k: (plans.append(caller), real(caller, *a, **k))[1])
 
     def step(batch):
         for p in model.parameters():
             p.grad = None
+        n0 = len(plans)
         prop, mol, mu, lv, _ = forward_propagation[mtype](model, batch, PAD, False, skip_ignored=True)
         ys = batch["trg"][:, 1:].contiguous().view(-1)
         ys_cond = batch["dconds"].unsqueeze(2).contiguous().view(-1, nc, 1) if nc else None
         loss = loss_function(0.3, prop, mol, ys_cond, ys, mu, lv, False, PAD)[0]
         loss.backward()
         torch.cuda.synchronize()
+        step.planned = plans[n0:].count(engine.MODEL)           # row plans the forward launched itself
         return mol.detach().clone(), loss.detach().clone(), {n: p.grad.clone() for n, p in model.named_parameters()
                                                               if p.grad is not None}
 
     mu = forward_propagation[mtype](model, b1, PAD, False, skip_ignored=True)[2]
     set_eps(model, torch.randn(mu.shape, generator=torch.Generator().manual_seed(3)).cuda())   # same noise every call
     ref = step(b1)
+    assert step.planned == 1
     prefetch(mtype, model, b1, PAD, False, skip_ignored=True)
-    assert model._gct_ahead is not None
     got = step(b1)                                             # announced: uses the queued maps
-    assert model._gct_ahead is None
+    assert step.planned == 0
+    assert step(b1) and step.planned == 1                      # an announcement is used once
     prefetch(mtype, model, b2, PAD, False, skip_ignored=True)
     other = step(b1)                                           # announced another batch: dropped, built as usual
-    assert model._gct_ahead is None
+    assert step.planned == 1
+    prefetch(mtype, model, b1, PAD, False, skip_ignored=True)
+    views = {k: v.view(v.shape) for k, v in b1.items()}       # same address, shape and version: not the same batch
+    assert all(views[k].data_ptr() == b1[k].data_ptr() and views[k]._version == b1[k]._version for k in b1)
+    viewed = step(views)
+    assert step.planned == 1
     prefetch(mtype, model, b1, PAD, False, skip_ignored=True)
     b1["trg"][0, 3] = b1["trg"][0, 3]                          # an in-place write bumps the version: announcement stale
     stale = step(b1)
+    assert step.planned == 1
     live = (b1["trg"][:, 1:] != PAD)                           # (skipped rows hold no meaningful logits)
-    for out in (got, other, stale):
+    for out in (got, other, viewed, stale):
         assert torch.equal(out[0][live], ref[0][live]) and torch.equal(out[1], ref[1])
         assert out[2].keys() == ref[2].keys()
         for k in ref[2]:
