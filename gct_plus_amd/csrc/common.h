@@ -128,3 +128,11 @@ __device__ __forceinline__ float gct_gelu_grad(float x) {
   const float pdf = 0.39894228040143267794f * __expf(-0.5f * x * x);
   return cdf + x * pdf;
 }
+// gct_gelu(x) and gct_gelu_grad(x) (bit for bit: the same expressions) from one erf
+__device__ __forceinline__ float gct_gelu_with_grad(float x, float& grad) {
+  const float e = gct_erf(x * 0.70710678118654752440f);
+  const float cdf = 0.5f * (1.0f + e);
+  const float pdf = 0.39894228040143267794f * __expf(-0.5f * x * x);
+  grad = cdf + x * pdf;
+  return 0.5f * x * (1.0f + e);
+}

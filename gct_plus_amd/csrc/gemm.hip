@@ -380,6 +380,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GemmArgs g) {
         const int64_t row_base = m0 + wm + i * 32 + 8 * q4 + 4 * h;  // multiple of 4
         uint4 bits = make_uint4(~0u, ~0u, ~0u, ~0u);
         const bool need_rng = g.thr != 0u && (g.epi == GCT_EPI_GELU_DROP ||
+                                              g.epi == GCT_EPI_GELU_DROP_SAVE ||
                                               g.epi == GCT_EPI_DROP_RESID ||
                                               g.epi == EPI_D0 + GCT_DEPI_GELU_BWD);
         if (need_rng) bits = gct_drop_bits(g.rng, drop_quad(g, row_base), (uint32_t)col);
@@ -400,6 +401,12 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GemmArgs g) {
               v = gct_gelu(v);
               v = keep ? v * g.keep_scale : 0.f;
             } break;
+            case GCT_EPI_GELU_DROP_SAVE: {
+              float gd;
+              const float y = gct_gelu_with_grad(v + bias, gd);
+              g.pre[off] = keep ? gd : 0.f;
+              v = keep ? y * g.keep_scale : 0.f;
+            } break;
             case GCT_EPI_DROP_RESID: {
               v += bias;
               v = keep ? v * g.keep_scale : 0.f;
@@ -417,6 +424,16 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GemmArgs g) {
                 u = g.pre_in[off];
               }
               v = keep ? v * gct_gelu_grad(u) * g.keep_scale : 0.f;
+            } break;
+            case EPI_D0 + GCT_DEPI_MUL_SAVED: {
+              float d = 0.f;
+              if (g.pre_rows > 0) {
+                const int64_t er0 = pre_row0(g, row_base);
+                if (er0 >= 0 && er0 + e < g.pre_rows) d = g.pre_in[(er0 + e) * g.ldc + cloc];
+              } else {
+                d = g.pre_in[off];
+              }
+              v = d == 0.f ? 0.f : v * d * g.keep_scale;
             } break;
             default:
               break;  // STORE / SLAB
@@ -459,26 +476,32 @@ __device__ __forceinline__ void epi_store4(float* p, const float (&x)[4]) {
   __builtin_nontemporal_store(f32x4_t{x[0], x[1], x[2], x[3]}, reinterpret_cast<f32x4_t*>(p));
 }
 
-struct FastEpi {
+// SIDE: the epilogues a kernel can be launched with -- 0 any, 1 forward (GCT_EPI_*), 2 dgrad (GCT_DEPI_*), 3 none
+// (slabs only); the others are compiled out of it
+template <int SIDE>
+struct FastEpiT {
+  static constexpr bool FWD = SIDE == 0 || SIDE == 1, BWD = SIDE == 0 || SIDE == 2;
   const GemmArgs& g;
   // number of extra float4 reads per patch row this epilogue needs (resid / accumulate / pre_in)
   __device__ __forceinline__ bool needs_extra() const {
 #ifdef GCT_LAB_NO_EPI_MATH
     return false;
 #endif
-    return g.epi == GCT_EPI_DROP_RESID || g.epi == EPI_D0 + GCT_DEPI_ACCUM ||
-           g.epi == EPI_D0 + GCT_DEPI_GELU_BWD;
+    return (FWD && g.epi == GCT_EPI_DROP_RESID) || (BWD && g.epi == EPI_D0 + GCT_DEPI_ACCUM) || reads_pre();
+  }
+  // the dgrad epilogues that read pre_in (the forward's row space when pre_rows > 0)
+  __device__ __forceinline__ bool reads_pre() const {
+    return BWD && (g.epi == EPI_D0 + GCT_DEPI_GELU_BWD || g.epi == EPI_D0 + GCT_DEPI_MUL_SAVED);
   }
   __device__ __forceinline__ const float* extra_base(const float* cbase) const {
-    return g.epi == GCT_EPI_DROP_RESID ? g.resid
-                                       : (g.epi == EPI_D0 + GCT_DEPI_GELU_BWD ? g.pre_in : cbase);
+    return (FWD && g.epi == GCT_EPI_DROP_RESID) ? g.resid : (reads_pre() ? g.pre_in : cbase);
   }
   // issue the extra reads of one 4x4 patch (latency overlaps the other patches' work)
   __device__ __forceinline__ void prefetch(float4 (&x)[4], int64_t row0, const float* cbase,
                                            int64_t cloc) const {
     const float* eb = extra_base(cbase);
     int64_t er0 = row0, elim = g.M;
-    if (g.epi == EPI_D0 + GCT_DEPI_GELU_BWD && g.pre_rows > 0) {
+    if (reads_pre() && g.pre_rows > 0) {
       er0 = pre_row0(g, row0);
       elim = er0 < 0 ? -1 : g.pre_rows;
     }
@@ -503,8 +526,9 @@ struct FastEpi {
     const int epi = g.epi;
 #endif
     uint4 bits[2];   // one Philox call per 4 rows x 2 columns (col0 % 4 == 0)
-    const bool rng = g.thr != 0u && (epi == GCT_EPI_GELU_DROP || epi == GCT_EPI_DROP_RESID ||
-                                     epi == EPI_D0 + GCT_DEPI_GELU_BWD);
+    const bool rng = g.thr != 0u && ((FWD && (epi == GCT_EPI_GELU_DROP || epi == GCT_EPI_GELU_DROP_SAVE ||
+                                              epi == GCT_EPI_DROP_RESID)) ||
+                                     (BWD && epi == EPI_D0 + GCT_DEPI_GELU_BWD));
     if (rng) {
 #pragma unroll
       for (int cp = 0; cp < 2; ++cp)
@@ -522,42 +546,62 @@ struct FastEpi {
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc) keep[cc] = gct_drop_keep(bits[cc >> 1], rr, (uint32_t)cc, g.thr);
       }
-      if (epi == GCT_EPI_BIAS) {
+      if (FWD && epi == GCT_EPI_BIAS) {
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc) x[cc] += bs[cc];
-      } else if (epi == GCT_EPI_GELU_DROP) {
+      } else if (FWD && epi == GCT_EPI_GELU_DROP) {
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc) x[cc] += bs[cc];
         epi_store4(g.pre + off, x);
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc) x[cc] = keep[cc] ? gct_gelu(x[cc]) * g.keep_scale : 0.f;
-      } else if (epi == GCT_EPI_DROP_RESID) {
+      } else if (FWD && epi == GCT_EPI_GELU_DROP_SAVE) {
+        // the saved factor is the backward's whole elementwise work: gelu'(v) where the element is kept, 0 where it
+        // is dropped (one erf serves both)
+        float d[4];
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) {
+          float gd;
+          const float y = gct_gelu_with_grad(x[cc] + bs[cc], gd);
+          d[cc] = keep[cc] ? gd : 0.f;
+          x[cc] = keep[cc] ? y * g.keep_scale : 0.f;
+        }
+        epi_store4(g.pre + off, d);
+      } else if (FWD && epi == GCT_EPI_DROP_RESID) {
         const float4 r = ex[rr];
         const float rs[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc)
           x[cc] = (keep[cc] ? (x[cc] + bs[cc]) * g.keep_scale : 0.f) + rs[cc];
-      } else if (epi == EPI_D0 + GCT_DEPI_ACCUM) {
+      } else if (BWD && epi == EPI_D0 + GCT_DEPI_ACCUM) {
         const float4 r = ex[rr];
         x[0] += r.x; x[1] += r.y; x[2] += r.z; x[3] += r.w;
-      } else if (epi == EPI_D0 + GCT_DEPI_GELU_BWD) {
+      } else if (BWD && epi == EPI_D0 + GCT_DEPI_GELU_BWD) {
         const float4 u = ex[rr];
         const float us[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc)
           x[cc] = keep[cc] ? x[cc] * gct_gelu_grad(us[cc]) * g.keep_scale : 0.f;
+      } else if (BWD && epi == EPI_D0 + GCT_DEPI_MUL_SAVED) {
+        const float4 u = ex[rr];
+        const float ds[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) x[cc] = ds[cc] == 0.f ? 0.f : x[cc] * ds[cc] * g.keep_scale;
       }
       epi_store4(cbase + off, x);
     }
   }
 };
+using FastEpi = FastEpiT<0>;
 
 
 // Per-wave epilogue shared by the 128x128 fp32-MFMA kernel and the bf16x6 kernels (both leave a
 // 64x64 block per wave in the 32x32 MFMA accumulator layout): transpose through LDS (stg: 64x64
 // floats private to the wave), then every lane finishes 4 patches of 4 rows x 4 columns.
+template <int SIDE>
 __device__ __forceinline__ void wave_epilogue_tail(const GemmArgs& g, float* stg, int lane, int64_t mw,
                                                    int64_t nw, unsigned z);
+template <int SIDE>
 __device__ __forceinline__ void wave_epilogue(const GemmArgs& g, const f32x16 (&acc)[2][2], float* stg,
                                               int lane, int64_t mw, int64_t nw, unsigned z) {
   {
@@ -570,15 +614,16 @@ __device__ __forceinline__ void wave_epilogue(const GemmArgs& g, const f32x16 (&
         for (int r = 0; r < 16; ++r)
           stg[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 64 + j * 32 + c32] = acc[i][j][r];
   }
-  wave_epilogue_tail(g, stg, lane, mw, nw, z);
+  wave_epilogue_tail<SIDE>(g, stg, lane, mw, nw, z);
 }
 
 // second part of the per-wave epilogue: the 64x64 block is in `stg` (row-major, this wave's own LDS writes)
+template <int SIDE>
 __device__ __forceinline__ void wave_epilogue_tail(const GemmArgs& g, float* stg, int lane, int64_t mw,
                                                    int64_t nw, unsigned z) {
   __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's own LDS writes are visible to it
   __builtin_amdgcn_wave_barrier();
-  const FastEpi ep{g};
+  const FastEpiT<SIDE> ep{g};
   // the lane's column chunk is the same for its 4 patches: destination, bias and the
   // segment select are resolved once; the residual / accumulate / pre-activation rows of
   // all 4 patches are requested up front so their latency overlaps
@@ -833,7 +878,7 @@ gemm_f32_fast_kernel(const GemmArgs g) {
 #undef GCT_PIN
 
   // ---- epilogue: per-wave 64x64 transpose through LDS (the tile buffers are free now)
-  wave_epilogue(g, acc, lds + wave * 4096, lane, m0 + wm, n0 + wn, z);
+  wave_epilogue<A_KC && B_KC ? 1 : (A_KC ? 2 : 3)>(g, acc, lds + wave * 4096, lane, m0 + wm, n0 + wn, z);
 #ifdef GCT_STAMPS
   STAMP(6);  // epilogue
   if (g.stamps && (threadIdx.x & 63) == 0 && blockIdx.x < 64) {
@@ -1492,7 +1537,8 @@ static int linear_fwd_impl(const float* x, int64_t ldx, int64_t M, int K, const 
   GCT_CHECK_ARG(nseg < 2 || (w1 && y1), "linear_fwd: missing segment 1");
   GCT_CHECK_ARG(nseg < 3 || (w2 && y2), "linear_fwd: missing segment 2");
   GCT_CHECK_ARG(epi == GCT_EPI_BIAS || nseg == 1, "linear_fwd: fused epilogues need nseg == 1");
-  GCT_CHECK_ARG(epi != GCT_EPI_GELU_DROP || pre, "linear_fwd: GELU epilogue needs pre");
+  GCT_CHECK_ARG(epi >= GCT_EPI_BIAS && epi <= GCT_EPI_GELU_DROP_SAVE, "linear_fwd: unknown epilogue %d", epi);
+  GCT_CHECK_ARG((epi != GCT_EPI_GELU_DROP && epi != GCT_EPI_GELU_DROP_SAVE) || pre, "linear_fwd: GELU epilogue needs pre");
   GCT_CHECK_ARG(epi != GCT_EPI_DROP_RESID || resid, "linear_fwd: residual epilogue needs resid");
   GCT_CHECK_ARG(p >= 0.f && p < 1.f, "linear_fwd: dropout p out of range");
   GemmArgs g = {};
@@ -1604,7 +1650,9 @@ static int linear_dgrad_impl(const float* dy0, const float* dy1, const float* dy
   GCT_CHECK_ARG(!quad_map || M % 4 == 0, "linear_dgrad: compacted rows come in quads");
   GCT_CHECK_ARG(nseg < 2 || (w1 && dy1), "linear_dgrad: missing segment 1");
   GCT_CHECK_ARG(nseg < 3 || (w2 && dy2), "linear_dgrad: missing segment 2");
+  GCT_CHECK_ARG(depi >= GCT_DEPI_STORE && depi <= GCT_DEPI_MUL_SAVED, "linear_dgrad: unknown epilogue %d", depi);
   GCT_CHECK_ARG(depi != GCT_DEPI_GELU_BWD || pre, "linear_dgrad: GELU bwd needs pre");
+  GCT_CHECK_ARG(depi != GCT_DEPI_MUL_SAVED || pre, "linear_dgrad: saved-factor epilogue needs pre");
   GCT_CHECK_ARG(p >= 0.f && p < 1.f, "linear_dgrad: dropout p out of range");
   GemmArgs g = {};
   g.M = M; g.N = K; g.K = (int64_t)nseg * nper;  // reduce over the layer's output features

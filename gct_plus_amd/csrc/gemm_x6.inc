@@ -550,7 +550,7 @@ gemm_x6_kernel(const GemmArgs g) {
 #ifdef GCT_LAB_NO_EPI         // tools/gemm_lab.hip: main loop only
     if (acc[0][0][0] == 123456.789f)
 #endif
-    wave_epilogue_tail(g, stg, lane, m0 + wm, n0 + wn, z);
+    wave_epilogue_tail<MODE == X6_FWD ? 1 : (MODE == X6_DGRAD ? 2 : 3)>(g, stg, lane, m0 + wm, n0 + wn, z);
   }
 #ifdef GCT_STAMPS
   __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0): include the stores' completion
@@ -759,7 +759,7 @@ __global__ __launch_bounds__(512) void gemm_x6s_kernel(const GemmArgs g) {
       for (int r = 0; r < 4; ++r) stg[(16 * i + 4 * fc + r) * 32 + 16 * j + fr] = acc[i][j][r];
   __builtin_amdgcn_s_waitcnt(0xC07F);
   __builtin_amdgcn_wave_barrier();
-  const FastEpi ep{g};
+  const FastEpiT<MODE == X6_FWD ? 1 : 2> ep{g};
   const int rg = lane >> 3, c4 = lane & 7;
   const int64_t row0 = m0 + wm + rg * 4, col0 = n0 + wn + c4 * 4;
   if (row0 < g.M && col0 < g.N) {

@@ -364,11 +364,11 @@ def mha_bwd(run: Run, m, saved, dy, G: GradSink, dxq_out, depi_q, dxkv_out=None,
 def ffn_fwd(run: Run, ff, x, resid, live=None):
     M, d = x.shape
     dff = ff.linear_1.weight.shape[0]
-    pre = _empty(M, dff, x)
+    gelu_d = _empty(M, dff, x)     # the backward's elementwise factor: gelu'(pre-activation) where kept, 0 where dropped
     hdn = _empty(M, dff, x)
     site_h = run.site()
-    ops.linear_fwd(x, [ff.linear_1.weight], [ff.linear_1.bias], [hdn], dff, epi=ops.EPI_GELU_DROP,
-                   pre=pre, p=run.p, seed=run.seed, site=site_h, live=live)
+    ops.linear_fwd(x, [ff.linear_1.weight], [ff.linear_1.bias], [hdn], dff, epi=ops.EPI_GELU_DROP_SAVE,
+                   pre=gelu_d, p=run.p, seed=run.seed, site=site_h, live=live)
     y = _empty(M, d, x)
     site_o = run.site()
     if resid is not None:
@@ -376,18 +376,18 @@ def ffn_fwd(run: Run, ff, x, resid, live=None):
                        epi=ops.EPI_DROP_RESID, resid=resid, p=run.p, seed=run.seed, site=site_o, live=live)
     else:
         ops.linear_fwd(hdn, [ff.linear_2.weight], [ff.linear_2.bias], [y], d)
-    return y, (x, pre, hdn, site_h, site_o, resid is not None)
+    return y, (x, gelu_d, hdn, site_h, site_o, resid is not None)
 
 
 def ffn_bwd(run: Run, ff, saved, dy, G: GradSink, dx_out, depi, live=None, gdrop=None):
-    x, pre, hdn, site_h, site_o, fused = saved
+    x, gelu_d, hdn, site_h, site_o, fused = saved
     M, d = x.shape
-    dff = pre.shape[1]
+    dff = gelu_d.shape[1]
     kt = run.kt
     if live is not None:          # quad-compacted rows: gather what the forward saved
         M, kt = live.Mc, None
-        if not live.fwd:                              # (a compact forward saved compact x / pre / hdn)
-            x, hdn = live.gather(x), live.gather(hdn)     # (pre stays in place: the GELU-backward epilogue reads it
+        if not live.fwd:                              # (a compact forward saved compact x / gelu_d / hdn)
+            x, hdn = live.gather(x), live.gather(hdn)     # (gelu_d stays in place: the dgrad epilogue reads it
                                                           #  through the quad map)
     if gdrop is not None:
         g = gdrop
@@ -395,7 +395,7 @@ def ffn_bwd(run: Run, ff, saved, dy, G: GradSink, dx_out, depi, live=None, gdrop
         g = ops.dropout_bwd(dy, run.p, run.seed, site_o, live=live) if (fused and run.p > 0) else dy
     ops.linear_wgrad([g], d, hdn, [G(ff.linear_2.weight)], [G(ff.linear_2.bias)], kt=kt)
     dpre = _empty(M, dff, dy) if live is None else live.empty(dff)
-    ops.linear_dgrad([g], d, M, [ff.linear_2.weight], dpre, depi=ops.DEPI_GELU_BWD, pre=pre,
+    ops.linear_dgrad([g], d, M, [ff.linear_2.weight], dpre, depi=ops.DEPI_MUL_SAVED, pre=gelu_d,
                      p=run.p, seed=run.seed, site=site_h, live=live, pre_full=live is not None and not live.fwd)
     ops.linear_wgrad([dpre], dff, x, [G(ff.linear_1.weight)], [G(ff.linear_1.bias)], kt=kt)
     ops.linear_dgrad([dpre], dff, M, [ff.linear_1.weight], dx_out, depi=depi)

@@ -17,8 +17,8 @@ import torch
 from . import _lib
 from ._lib import check
 
-EPI_BIAS, EPI_GELU_DROP, EPI_DROP_RESID = 0, 1, 2
-DEPI_STORE, DEPI_ACCUM, DEPI_GELU_BWD = 0, 1, 2
+EPI_BIAS, EPI_GELU_DROP, EPI_DROP_RESID, EPI_GELU_DROP_SAVE = 0, 1, 2, 3
+DEPI_STORE, DEPI_ACCUM, DEPI_GELU_BWD, DEPI_MUL_SAVED = 0, 1, 2, 3
 
 
 def _L():
@@ -379,7 +379,7 @@ def linear_fwd(x2d, ws_: Sequence[torch.Tensor], bs: Sequence[Optional[torch.Ten
     wp, pstride = _plane_ptr(ws_)
     wsb = ws if ws is not None else (workspace(need, x2d.device) if need > 256 else None)
     N = nper * len(ws_)
-    nbytes = 4 * M * K + (6 if wp else 4) * N * K + 4 * N + 4 * M * N * (2 if epi in (EPI_GELU_DROP, EPI_DROP_RESID) else 1)
+    nbytes = 4 * M * K + (6 if wp else 4) * N * K + 4 * N + 4 * M * N * (2 if epi in (EPI_GELU_DROP, EPI_DROP_RESID, EPI_GELU_DROP_SAVE) else 1)
     with _Timed("gemm_fwd", 2.0 * M * K * N, nbytes):
         check(_L().gct_linear_fwd_p(_p(x2d), x2d.stride(0), M, K, w[0], w[1], w[2], ws_[0].stride(0),
                                     wp, pstride, b[0], b[1], b[2], len(ws_), nper, y[0], y[1], y[2],

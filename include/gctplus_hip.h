@@ -86,10 +86,13 @@ int gct_embed_pe_bwd(const float* dout, const int64_t* tok, float* dtable, float
  *   GCT_EPI_BIAS       : plain
  *   GCT_EPI_GELU_DROP  : pre[m][n] = acc+b (saved), y = dropout(gelu_erf(pre))   (FFN-1)
  *   GCT_EPI_DROP_RESID : y = resid[m][n] + dropout(acc+b)                         (out / FFN-2)
+ *   GCT_EPI_GELU_DROP_SAVE : y as GCT_EPI_GELU_DROP; pre[m][n] = keep ? gelu'(acc+b) : 0 (saved: the
+ *                        factor GCT_DEPI_MUL_SAVED needs, keep = the dropout mask of y)   (FFN-1)
  * pre/resid share y's leading dimension and are only valid with nseg == 1. */
 #define GCT_EPI_BIAS 0
 #define GCT_EPI_GELU_DROP 1
 #define GCT_EPI_DROP_RESID 2
+#define GCT_EPI_GELU_DROP_SAVE 3
 int gct_linear_fwd(const float* x, int64_t ldx, int64_t M, int K,
                    const float* w0, const float* w1, const float* w2, int64_t ldw,
                    const float* b0, const float* b1, const float* b2, int nseg, int nper,
@@ -112,10 +115,14 @@ int gct_linear_fwd_ws(const float* x, int64_t ldx, int64_t M, int K,
 
 /* dx[m][k] (op)= sum_s sum_n dy_s[m][n] * w_s[n][k]
  *   GCT_DEPI_STORE / GCT_DEPI_ACCUM (dx += ...) /
- *   GCT_DEPI_GELU_BWD : dx = acc * gelu'(pre[m][k]) * dropmask(site)/(1-p)   (through FFN-1 act.) */
+ *   GCT_DEPI_GELU_BWD : dx = acc * gelu'(pre[m][k]) * dropmask(site)/(1-p)   (through FFN-1 act.)
+ *   GCT_DEPI_MUL_SAVED : dx = pre[m][k] == 0 ? 0 : acc * pre[m][k] / (1-p), pre written by
+ *                        GCT_EPI_GELU_DROP_SAVE (same p): the GCT_DEPI_GELU_BWD result with the
+ *                        same operations in the same order, without Philox / erf / exp */
 #define GCT_DEPI_STORE 0
 #define GCT_DEPI_ACCUM 1
 #define GCT_DEPI_GELU_BWD 2
+#define GCT_DEPI_MUL_SAVED 3
 int gct_linear_dgrad(const float* dy0, const float* dy1, const float* dy2, int64_t lddy,
                      int64_t M, int nseg, int nper,
                      const float* w0, const float* w1, const float* w2, int64_t ldw, int K,
@@ -190,7 +197,8 @@ int gct_linear_dgrad_p(const float* dy0, const float* dy1, const float* dy2, int
                        void* stream);
 /* quad_map (nullable): the M rows are quad-compacted (gct_live_rows); GCT_DEPI_GELU_BWD then regenerates the dropout
  * mask of compact quad q from original quad quad_map[q].  pre_rows == 0: pre is compact like dy / dx; pre_rows > 0:
- * pre keeps the forward's row space (pre_rows rows) and is read through the quad map (no gathered copy needed). */
+ * pre keeps the forward's row space (pre_rows rows) and is read through the quad map (no gathered copy needed) --
+ * for GCT_DEPI_GELU_BWD and GCT_DEPI_MUL_SAVED alike. */
 /* ws of gct_linear_dgrad_p (nullable): >= gct_linear_dgrad_ws_bytes(M, nseg*nper, K).  With a workspace the
  * bf16x6 forward / dgrad launches balance a partial last round of tiles (the tail rows as a second launch: on 64 x 128
  * tiles when the reduction is <= 1024 long, else K-split into slabs + a fix-up kernel) and split a long reduction over

@@ -74,7 +74,8 @@ int main(int argc, char** argv) {
     float* y2 = nseg > 2 ? y + 2 * nper : nullptr;
     const double fl = 2.0 * M * K * N;
     struct Case { const char* nm; int epi; float p; };
-    const Case fc[] = {{"bias", GCT_EPI_BIAS, 0.f}, {"gelu_drop.1", GCT_EPI_GELU_DROP, 0.1f}, {"drop_resid.1", GCT_EPI_DROP_RESID, 0.1f}};
+    const Case fc[] = {{"bias", GCT_EPI_BIAS, 0.f}, {"gelu_drop.1", GCT_EPI_GELU_DROP, 0.1f},
+                       {"gelu_save.1", GCT_EPI_GELU_DROP_SAVE, 0.1f}, {"drop_resid.1", GCT_EPI_DROP_RESID, 0.1f}};
     for (const Case& c : fc) {
       if (c.epi != GCT_EPI_BIAS && nseg > 1) continue;
       const double t = timeit([&] {
@@ -84,7 +85,8 @@ int main(int argc, char** argv) {
       }, reps);
       printf("%-5s fwd   %-13s M=%ld K=%d N=%d: %8.1f us %6.1f TF\n", s.name, c.nm, (long)M, K, N, t, fl / t / 1e6);
     }
-    const Case dc[] = {{"store", GCT_DEPI_STORE, 0.f}, {"gelu_bwd.1", GCT_DEPI_GELU_BWD, 0.1f}};
+    const Case dc[] = {{"store", GCT_DEPI_STORE, 0.f}, {"gelu_bwd.1", GCT_DEPI_GELU_BWD, 0.1f},
+                       {"mul_saved.1", GCT_DEPI_MUL_SAVED, 0.1f}};
     for (const Case& c : dc) {
       if (c.epi != GCT_DEPI_STORE && nseg > 1) continue;
       const double t = timeit([&] {
