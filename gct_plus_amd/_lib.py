@@ -7,97 +7,82 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GCT_LIB_PATH") or os.path.join(_HERE, "libgctplus_hip.so")   # override: A/B builds
 
-P, I64, I32, F32, U64, U32 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_uint32
-
-# name -> (restype, [argtypes])   -- mirrors include/gctplus_hip.h one to one
-SIGNATURES = {
-    "gct_version": (I32, []),
-    "gct_last_error": (C.c_char_p, []),
-    "gct_wgrad_ws_bytes": (I64, [I64, I64, I64]),
-    "gct_rowred_ws_bytes": (I64, [I64, I64]),
-    "gct_embed_ws_bytes": (I64, [I32, I32, I32, I32]),
-    "gct_norm_fwd": (I32, [P, P, P, P, P, P, I64, I32, F32, P]),
-    "gct_norm_bwd": (I32, [P, P, P, P, P, P, P, P, P, P, I64, I32, F32, P, I64, P, F32, U64, U32, P]),
-    "gct_embed_pe_fwd": (I32, [P, P, P, P, P, I32, I32, I32, I32, I32, F32, F32, U64, U32, P]),
-    "gct_embed_pe_bwd": (I32, [P, P, P, P, P, I32, I32, I32, I32, I32, F32, F32, U64, U32, P]),
-    "gct_linear_fwd": (I32, [P, I64, I64, I32, P, P, P, I64, P, P, P, I32, I32, P, P, P, I64,
-                             I32, P, P, F32, U64, U32, P]),
-    "gct_linear_fwd_ws_bytes": (I64, [I64, I32, I32]),
-    "gct_linear_fwd_ws": (I32, [P, I64, I64, I32, P, P, P, I64, P, P, P, I32, I32, P, P, P, I64,
-                                I32, P, P, F32, U64, U32, P, I64, P]),
-    "gct_linear_fwd_p": (I32, [P, I64, I64, I32, P, P, P, I64, P, I64, P, P, P, I32, I32, P, P, P, I64,
-                               I32, P, P, F32, U64, U32, P, I64, P, P]),
-    "gct_linear_dgrad_p": (I32, [P, P, P, I64, I64, I32, I32, P, P, P, I64, P, I64, I32, P, I64, I32, P,
-                                 F32, U64, U32, P, I64, P, I64, P]),
-    "gct_linear_dgrad_ws_bytes": (I64, [I64, I32, I32]),
-    "gct_gemm_set_mode": (I32, [I32]),
-    "gct_gemm_get_mode": (I32, []),
-    "gct_gemm_launch_counts": (I32, [P]),
-    "gct_gemm_x6_kernel_launches": (I64, []),
-    "gct_gemm_x3_launches": (I64, []),
-    "gct_split_planes": (I32, [P, I64, P, I64, P]),
-    "gct_linear_dgrad": (I32, [P, P, P, I64, I64, I32, I32, P, P, P, I64, I32, P, I64, I32, P,
-                               F32, U64, U32, P]),
-    "gct_linear_wgrad": (I32, [P, P, P, I64, I64, I32, I32, P, I64, I32, P, P, P, I64, P, P, P,
-                               P, P]),
-    "gct_dead_rows_nonzero": (I32, [P, I64, I64, I32, P, P, P]),
-    "gct_nonzero_row_tiles": (I32, [P, I64, I64, I32, P, P, P, P]),
-    "gct_live_rows": (I32, [P, I64, I32, I32, I32, P, I64, I64, P, P, P, P, P, P, P, P, P, P]),
-    "gct_gather_quads": (I32, [P, I64, I64, P, I64, I32, P, I64, P]),
-    "gct_scatter_quads": (I32, [P, I64, P, I64, I32, P, I64, I64, P]),
-    "gct_zero_gap_rows": (I32, [P, I64, I32, P, P, I32, I64, P]),
-    "gct_scatter_add_quads": (I32, [P, I64, P, I64, I32, P, I64, I64, P]),
-    "gct_linear_wgrad_kt": (I32, [P, P, P, I64, I64, I32, I32, P, I64, I32, P, P, P, I64, P, P, P,
-                                  P, P, P, P]),
-    "gct_dropout_bwd": (I32, [P, P, I64, I32, F32, U64, U32, P, P]),
-    "gct_attn_fwd": (I32, [P, I64, P, I64, P, I64, P, I64, I64, P, I64, P, P, I32, I32, I32, I32,
-                           I32, F32, F32, U64, U32, P, P, P, I64, I64, P, P, P]),
-    "gct_attn_bwd": (I32, [P, I64, P, I64, P, I64, P, I64, I64, P, P, I64, P, P, I64, P, I64,
-                           P, I64, I32, I32, I32, I32, I32, F32, F32, U64, U32, P, P, I32, P, P, P, I64, I64, P, I64, P]),
-    "gct_attn_bwd_ws_bytes": (I64, [I32, I32, I32, I32]),
-    "gct_key_rows": (I32, [P, I64, I32, I32, P, P, P, P, P, P, P]),
-    "gct_attn_mask_pack": (I32, [P, I64, I64, I32, I32, I32, P, P, P]),
-    "gct_trg_mask_tokens": (I32, [P, I64, I64, I32, I32, P, P]),
-    "gct_reparam_fwd": (I32, [P, P, P, P, P, I64, U64, U32, P]),
-    "gct_reparam_bwd": (I32, [P, P, P, P, P, P, P, I64, P]),
-    "gct_kld_fwd": (I32, [P, P, P, P, I64, P]),
-    "gct_kld_bwd": (I32, [P, P, P, P, P, I64, P]),
-    "gct_ce_fwd": (I32, [P, P, P, P, I64, I32, I64, P]),
-    "gct_ce_bwd": (I32, [P, P, P, P, I64, I32, I64, P]),
-    "gct_attn_decode": (I32, [P, I64, P, P, I64, I64, P, I64, P, I64, I32, I32, I32, I32, F32, P, I32, P, P, I64, P, P,
-                              P]),
-    "gct_attn_decode_z": (I32, [P, I64, I32, P, I64, I32, I32, P, I64, I64, I32, P, I64, P, P, I64, I32, I32, I32, I32, F32, P]),
-    "gct_decode_embed": (I32, [P, I64, P, I32, P, I32, P, P, I32, I32, F32, P, P]),
-    "gct_decode_advance": (I32, [P, P]),
-    "gct_select_token": (I32, [P, I32, P, I64, I32, P, I64, P, P, I32, I32, I64, I64, U64, P, I32, P, P, P, P]),
-    "gct_attn_decode_beam": (I32, [P, I64, P, P, I64, I64, P, I64, P, I64, I32, I32, I32, I32, F32, P, I32, P, P, I64,
-                                   P, I64, P]),
-    "gct_beam_select": (I32, [P, I32, I32, I32, P, P, P, P, P, I64, P, I64, I32, P, I64, I32, P, P, I64, I64, P]),
-    "gct_smiles_tokenize": (I32, [C.c_char_p, I32, P, P, I32]),
-    "gct_smiles_encode_batch": (I32, [P, I32, I32, P, I32, I64, I64, I64, I64, P, I64, P]),
-    "gct_adam_step": (I32, [P, P, P, P, I64, F32, F32, F32, F32, I64, F32, P]),
-    "gct_adam_step_guarded": (I32, [P, P, P, P, I64, F32, F32, F32, F32, I64, F32, P, P]),
-    "gct_copy_rows": (I32, [P, I64, I64, P, I64, I64, I64, I64, I32, I32, P]),
-    "gct_small_linear_fwd": (I32, [P, P, P, P, I32, I32, I32, P]),
-    "gct_small_linear_bwd": (I32, [P, P, P, P, I32, I32, I32, P]),
-    "gct_reduce_slabs": (I32, [P, I32, I64, P, I64, I32, P]),
-    "gct_reduce_defer_begin": (I32, []),
-    "gct_reduce_defer_flush": (I32, [P]),
-    "gct_reduce_defer_end": (I32, [P]),
-    "gct_reduce_defer_pending": (I32, []),
-    "gct_add": (I32, [P, P, P, I64, P]),
-}
-
-ABI_VERSION = 18
-_lib = None
+INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 
 
 class GctError(RuntimeError):
     pass
+
+
+# The headers are the one definition of the boundary: every binding below is parsed from them at import.
+# char* is a C string (bytes in, a string buffer, or a message out); every other pointer, a pointer to pointers or to
+# a struct included, is an address.  A value type that is not listed is an error: nothing is bound by default.
+_VALUE_TYPES = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float,
+                "uint64_t": C.c_uint64, "uint32_t": C.c_uint32}
+_PROTOTYPE = re.compile(r"([A-Za-z_][\w\s\*]*?)\b(\w+)\s*\(([^()]*)\)\s*;")
+
+
+def _ctype(decl: str, proto: str, is_return: bool = False):
+    words = decl.replace("*", " * ").split()
+    if not is_return and len(words) > 1 and words[-1] != "*":
+        words.pop()                                     # the parameter's name
+    base = " ".join(w for w in words if w not in ("const", "*"))
+    stars = words.count("*")
+    if stars == 1 and base == "char":
+        return C.c_char_p
+    if stars and re.fullmatch(r"\w+", base):
+        return C.c_void_p
+    if not stars and base in _VALUE_TYPES:
+        return _VALUE_TYPES[base]
+    raise GctError(f"no ctypes binding for `{decl.strip()}` in `{proto}`")
+
+
+def parse_prototypes(text: str) -> dict:
+    """name -> (restype, [argtypes]) of every `ret name(args);` of a C header's text."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$|extern\s+\"C\"\s*\{|typedef\s+struct\s*\w*\s*\{[^{}]*\}\s*\w+\s*;", " ", text, flags=re.M)
+    out = {}
+    for m in _PROTOTYPE.finditer(text):
+        proto = " ".join(m.group(0).split())
+        args = [] if m.group(3).strip() in ("", "void") else m.group(3).split(",")
+        out[m.group(2)] = (_ctype(m.group(1), proto, is_return=True), [_ctype(a, proto) for a in args])
+    rest = _PROTOTYPE.sub(" ", text).replace("}", " ").split()
+    if rest:
+        raise GctError(f"not a prototype: `{' '.join(rest)[:120]}`")
+    return out
+
+
+def _read_header(name: str) -> str:
+    path = os.path.join(INCLUDE_DIR, name)
+    try:
+        with open(path, encoding="utf-8") as f:
+            return f.read()
+    except OSError as e:
+        raise GctError(f"{path} is missing: it defines the bindings of {LIB_PATH}") from e
+
+
+def _parse_header(name: str) -> dict:
+    sigs = parse_prototypes(_read_header(name))
+    if not sigs:
+        raise GctError(f"no prototype found in {os.path.join(INCLUDE_DIR, name)}")
+    return sigs
+
+
+def _abi_version() -> int:
+    m = re.search(r"^\s*#\s*define\s+GCT_ABI_VERSION\s+(\d+)\b", _read_header("gctplus_hip.h"), flags=re.M)
+    if not m:
+        raise GctError("include/gctplus_hip.h does not define GCT_ABI_VERSION")
+    return int(m.group(1))
+
+
+SIGNATURES = _parse_header("gctplus_hip.h")         # name -> (restype, [argtypes])
+ABI_VERSION = _abi_version()
+_lib = None
 
 
 def load():
@@ -125,13 +110,7 @@ def load():
 
 # ---- the diagnostics library (include/gctplus_diag.h): separate from the operator boundary, optional at run time
 DIAG_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libgctplus_diag.so")
-DIAG_SIGNATURES = {
-    "gct_diag_last_error": (C.c_char_p, []),
-    "gct_graph_probe": (I32, [I32, I32, I32, P, P, P]),
-    "gct_device_facts": (I32, [C.c_char_p, I32]),
-    "gct_graph_census": (I32, [P, P]),
-    "gct_mfma_clock_probe": (I32, [I32, P, P]),
-}
+DIAG_SIGNATURES = _parse_header("gctplus_diag.h")
 _diag = None
 
 

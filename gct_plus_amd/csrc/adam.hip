@@ -46,9 +46,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
 }
 }  // namespace
 
-extern "C" int gct_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr,
-                                     float b1, float b2, float eps, int64_t step, float gscale,
-                                     const int32_t* skip_if_nonzero, void* stream) {
+extern "C" int gct_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr,
+                             float b1, float b2, float eps, int64_t step, float gscale,
+                             const int32_t* skip_if_nonzero, void* stream) {
   GCT_CHECK_ARG(p && g && m && v && n >= 0 && step >= 1, "adam_step: bad args");
   GCT_CHECK_ARG(gct_aligned16(p) && gct_aligned16(g) && gct_aligned16(m) && gct_aligned16(v),
                 "adam_step: buffers must be 16-B aligned");
@@ -64,10 +64,4 @@ extern "C" int gct_adam_step_guarded(float* p, const float* g, float* m, float* 
                      v, n4, n, b1, b2, eps, step_size, inv_bc2_sqrt, gscale, skip_if_nonzero);
   GCT_LAUNCH_CHECK("adam_step");
   return GCT_OK;
-}
-
-extern "C" int gct_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr,
-                             float b1, float b2, float eps, int64_t step, float gscale,
-                             void* stream) {
-  return gct_adam_step_guarded(p, g, m, v, n, lr, b1, b2, eps, step, gscale, nullptr, stream);
 }

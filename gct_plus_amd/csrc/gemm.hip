@@ -1523,13 +1523,13 @@ extern "C" int64_t gct_wgrad_ws_bytes(int64_t M, int64_t Ntot, int64_t K) {
   return (need > cs ? need : cs) * (int64_t)sizeof(float) + 256;
 }
 
-static int linear_fwd_impl(const float* x, int64_t ldx, int64_t M, int K, const float* w0,
-                           const float* w1, const float* w2, int64_t ldw, const float* b0,
-                           const float* b1, const float* b2, int nseg, int nper, float* y0,
-                           float* y1, float* y2, int64_t ldy, int epi, const float* resid,
-                           float* pre, float p, uint64_t seed, uint32_t site, float* ws, int64_t ws_bytes,
-                           void* stream, const uint16_t* wp0 = nullptr, int64_t pstride = 0,
-                           const int32_t* quad_map = nullptr) {
+extern "C" int gct_linear_fwd(const float* x, int64_t ldx, int64_t M, int K, const float* w0,
+                              const float* w1, const float* w2, int64_t ldw, const uint16_t* wp0,
+                              int64_t plane_stride, const float* b0, const float* b1,
+                              const float* b2, int nseg, int nper, float* y0, float* y1, float* y2,
+                              int64_t ldy, int epi, const float* resid, float* pre, float p,
+                              uint64_t seed, uint32_t site, float* ws, int64_t ws_bytes,
+                              const int32_t* quad_map, void* stream) {
   GCT_CHECK_ARG(x && w0 && y0 && M >= 0 && K > 0 && nseg >= 1 && nseg <= 3 && nper > 0,
                 "linear_fwd: bad args");
   GCT_CHECK_ARG(!quad_map || M % 4 == 0, "linear_fwd: compacted rows come in quads");
@@ -1552,41 +1552,11 @@ static int linear_fwd_impl(const float* x, int64_t ldx, int64_t M, int K, const 
   g.bias0 = b0; g.bias_d1 = (b0 && b1) ? b1 - b0 : 0; g.bias_d2 = (b0 && b2) ? b2 - b0 : 0;
   g.resid = resid; g.pre = pre;
   g.thr = gct_drop_threshold(p); g.keep_scale = 1.0f / (1.0f - p); g.rng = gct_rng_make(seed, site);
-  g.bp0 = wp0; g.bp_stride = pstride;
+  g.bp0 = wp0; g.bp_stride = plane_stride;
   g.quad_map = quad_map;          // rows are a quad compaction: the dropout coordinates of the epilogues follow the map
   const bool vec = al16(x) && al16(w0) && al16(w1) && al16(w2) && (ldx % 4 == 0) &&
                    (ldw % 4 == 0) && (K % 4 == 0);
   return launch<true, true>(g, vec, (hipStream_t)stream, ws, ws ? ws_bytes : 0);   // every slab route checks its need against ws_bytes
-}
-
-extern "C" int gct_linear_fwd(const float* x, int64_t ldx, int64_t M, int K, const float* w0,
-                              const float* w1, const float* w2, int64_t ldw, const float* b0,
-                              const float* b1, const float* b2, int nseg, int nper, float* y0,
-                              float* y1, float* y2, int64_t ldy, int epi, const float* resid,
-                              float* pre, float p, uint64_t seed, uint32_t site, void* stream) {
-  return linear_fwd_impl(x, ldx, M, K, w0, w1, w2, ldw, b0, b1, b2, nseg, nper, y0, y1, y2, ldy, epi,
-                         resid, pre, p, seed, site, nullptr, 0, stream);
-}
-
-extern "C" int gct_linear_fwd_ws(const float* x, int64_t ldx, int64_t M, int K, const float* w0,
-                                 const float* w1, const float* w2, int64_t ldw, const float* b0,
-                                 const float* b1, const float* b2, int nseg, int nper, float* y0,
-                                 float* y1, float* y2, int64_t ldy, int epi, const float* resid,
-                                 float* pre, float p, uint64_t seed, uint32_t site, float* ws,
-                                 int64_t ws_bytes, void* stream) {
-  return linear_fwd_impl(x, ldx, M, K, w0, w1, w2, ldw, b0, b1, b2, nseg, nper, y0, y1, y2, ldy, epi,
-                         resid, pre, p, seed, site, ws, ws_bytes, stream);
-}
-
-extern "C" int gct_linear_fwd_p(const float* x, int64_t ldx, int64_t M, int K, const float* w0,
-                                const float* w1, const float* w2, int64_t ldw, const uint16_t* wp0,
-                                int64_t plane_stride, const float* b0, const float* b1,
-                                const float* b2, int nseg, int nper, float* y0, float* y1, float* y2,
-                                int64_t ldy, int epi, const float* resid, float* pre, float p,
-                                uint64_t seed, uint32_t site, float* ws, int64_t ws_bytes,
-                                const int32_t* quad_map, void* stream) {
-  return linear_fwd_impl(x, ldx, M, K, w0, w1, w2, ldw, b0, b1, b2, nseg, nper, y0, y1, y2, ldy, epi,
-                         resid, pre, p, seed, site, ws, ws_bytes, stream, wp0, plane_stride, quad_map);
 }
 
 extern "C" int gct_gemm_set_mode(int mode) {
@@ -1639,12 +1609,14 @@ extern "C" int64_t gct_linear_dgrad_ws_bytes(int64_t M, int Ntot, int K) {
   return (tail > all ? tail : all) + 256;
 }
 
-static int linear_dgrad_impl(const float* dy0, const float* dy1, const float* dy2, int64_t lddy,
-                             int64_t M, int nseg, int nper, const float* w0, const float* w1,
-                             const float* w2, int64_t ldw, int K, float* dx, int64_t lddx,
-                             int depi, const float* pre, float p, uint64_t seed, uint32_t site,
-                             void* stream, const uint16_t* wp0, int64_t pstride, float* ws, int64_t ws_bytes,
-                             const int32_t* quad_map = nullptr, int64_t pre_rows = 0) {
+extern "C" int gct_linear_dgrad(const float* dy0, const float* dy1, const float* dy2, int64_t lddy,
+                                int64_t M, int nseg, int nper, const float* w0, const float* w1,
+                                const float* w2, int64_t ldw, const uint16_t* wp0,
+                                int64_t plane_stride, int K, float* dx, int64_t lddx, int depi,
+                                const float* pre, float p, uint64_t seed, uint32_t site,
+                                float* ws, int64_t ws_bytes, const int32_t* quad_map, int64_t pre_rows,
+                                void* stream) {
+  GCT_CHECK_ARG(ws_bytes >= 0, "linear_dgrad: negative workspace size");
   GCT_CHECK_ARG(dy0 && w0 && dx && M >= 0 && K > 0 && nseg >= 1 && nseg <= 3 && nper > 0,
                 "linear_dgrad: bad args");
   GCT_CHECK_ARG(!quad_map || M % 4 == 0, "linear_dgrad: compacted rows come in quads");
@@ -1662,7 +1634,7 @@ static int linear_dgrad_impl(const float* dy0, const float* dy1, const float* dy
   g.ksplit = g.K; g.nsplit = 1; g.epi = EPI_D0 + depi;
   g.pre_in = pre;
   g.thr = gct_drop_threshold(p); g.keep_scale = 1.0f / (1.0f - p); g.rng = gct_rng_make(seed, site);
-  g.bp0 = wp0; g.bp_stride = pstride;
+  g.bp0 = wp0; g.bp_stride = plane_stride;
   g.quad_map = quad_map;
   g.pre_rows = quad_map ? pre_rows : 0;
   const bool vec = al16(dy0) && al16(dy1) && al16(dy2) && al16(w0) && al16(w1) && al16(w2) &&
@@ -1670,32 +1642,11 @@ static int linear_dgrad_impl(const float* dy0, const float* dy1, const float* dy
   return launch<true, false>(g, vec, (hipStream_t)stream, ws, ws ? ws_bytes : 0);
 }
 
-extern "C" int gct_linear_dgrad(const float* dy0, const float* dy1, const float* dy2, int64_t lddy,
-                                int64_t M, int nseg, int nper, const float* w0, const float* w1,
-                                const float* w2, int64_t ldw, int K, float* dx, int64_t lddx,
-                                int depi, const float* pre, float p, uint64_t seed, uint32_t site,
-                                void* stream) {
-  return linear_dgrad_impl(dy0, dy1, dy2, lddy, M, nseg, nper, w0, w1, w2, ldw, K, dx, lddx, depi, pre,
-                           p, seed, site, stream, nullptr, 0, nullptr, 0);
-}
-
-extern "C" int gct_linear_dgrad_p(const float* dy0, const float* dy1, const float* dy2, int64_t lddy,
-                                  int64_t M, int nseg, int nper, const float* w0, const float* w1,
-                                  const float* w2, int64_t ldw, const uint16_t* wp0,
-                                  int64_t plane_stride, int K, float* dx, int64_t lddx, int depi,
-                                  const float* pre, float p, uint64_t seed, uint32_t site,
-                                  float* ws, int64_t ws_bytes, const int32_t* quad_map, int64_t pre_rows,
-                                  void* stream) {
-  GCT_CHECK_ARG(ws_bytes >= 0, "linear_dgrad: negative workspace size");
-  return linear_dgrad_impl(dy0, dy1, dy2, lddy, M, nseg, nper, w0, w1, w2, ldw, K, dx, lddx, depi, pre,
-                           p, seed, site, stream, wp0, plane_stride, ws, ws_bytes, quad_map, pre_rows);
-}
-
-static int linear_wgrad_impl(const float* dy0, const float* dy1, const float* dy2, int64_t lddy,
-                             int64_t M, int nseg, int nper, const float* x, int64_t ldx, int K,
-                             float* dw0, float* dw1, float* dw2, int64_t lddw, float* db0,
-                             float* db1, float* db2, float* ws, void* stream, const int32_t* kt_list,
-                             const int32_t* kt_count) {
+extern "C" int gct_linear_wgrad(const float* dy0, const float* dy1, const float* dy2, int64_t lddy,
+                                int64_t M, int nseg, int nper, const float* x, int64_t ldx, int K,
+                                float* dw0, float* dw1, float* dw2, int64_t lddw, float* db0,
+                                float* db1, float* db2, float* ws, const int32_t* tile_list,
+                                const int32_t* tile_count, void* stream) {
   GCT_CHECK_ARG(dy0 && x && dw0 && ws && M >= 0 && K > 0 && nseg >= 1 && nseg <= 3 && nper > 0,
                 "linear_wgrad: bad args");
   GCT_CHECK_ARG(nseg < 2 || (dy1 && dw1), "linear_wgrad: missing segment 1");
@@ -1713,7 +1664,7 @@ static int linear_wgrad_impl(const float* dy0, const float* dy1, const float* dy
   g.slab_stride = Ntot * K;
   g.ksplit = BK; g.nsplit = 1; g.epi = EPI_SLAB;
   const bool use_x6 = gemm_mode() != GCT_GEMM_F32 && x6_ok<X6_WGRAD>(g, vec);   // bf16x6 or bf16x3: same route
-  if (use_x6 && kt_list && kt_count) { g.kt_list = kt_list; g.kt_count = kt_count; }   // other kernels reduce over every row
+  if (use_x6 && tile_list && tile_count) { g.kt_list = tile_list; g.kt_count = tile_count; }   // other kernels reduce over every row
   const int splits = wgrad_splits(M, Ntot, K, use_x6);
   int64_t ks = (M + splits - 1) / splits;
   ks = (ks + BK - 1) / BK * BK;
@@ -1741,21 +1692,4 @@ static int linear_wgrad_impl(const float* dy0, const float* dy1, const float* dy
     return gct_reduce_slabs_seg2(ws, g.nsplit, g.slab_stride, dw0, dw1, dw2, (int64_t)nper * K, Ntot * K, bslab, Ntot,
                                  db0, db1, db2, nper, Ntot, st);
   return gct_reduce_slabs_seg(ws, g.nsplit, g.slab_stride, dw0, dw1, dw2, (int64_t)nper * K, Ntot * K, st);
-}
-
-extern "C" int gct_linear_wgrad(const float* dy0, const float* dy1, const float* dy2, int64_t lddy,
-                                int64_t M, int nseg, int nper, const float* x, int64_t ldx, int K,
-                                float* dw0, float* dw1, float* dw2, int64_t lddw, float* db0,
-                                float* db1, float* db2, float* ws, void* stream) {
-  return linear_wgrad_impl(dy0, dy1, dy2, lddy, M, nseg, nper, x, ldx, K, dw0, dw1, dw2, lddw, db0, db1, db2,
-                           ws, stream, nullptr, nullptr);
-}
-
-extern "C" int gct_linear_wgrad_kt(const float* dy0, const float* dy1, const float* dy2, int64_t lddy,
-                                   int64_t M, int nseg, int nper, const float* x, int64_t ldx, int K,
-                                   float* dw0, float* dw1, float* dw2, int64_t lddw, float* db0,
-                                   float* db1, float* db2, float* ws, const int32_t* kt_list,
-                                   const int32_t* kt_count, void* stream) {
-  return linear_wgrad_impl(dy0, dy1, dy2, lddy, M, nseg, nper, x, ldx, K, dw0, dw1, dw2, lddw, db0, db1, db2,
-                           ws, stream, kt_list, kt_count);
 }

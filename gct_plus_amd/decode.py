@@ -443,8 +443,8 @@ class KVDecoder:
         y, saved, _, _ = engine.decoder_trunk_fwd(dec, run, ys0.contiguous(), engine._f32c(self.z), sm, tm,
                                                   self.dconds, False, plan)
         Tp = self.off + t0
-        for li, sv in enumerate(saved[4]):                          # per layer: (x, m1, r1, sv1, ...); sv1[2] = q|k|v
-            qkv = sv[3][2].view(n, Tp, 3 * d)
+        for li, layer in enumerate(saved.layers):                   # the self-attention's q | k | v fills the caches
+            qkv = layer.attn_1.qkv.view(n, Tp, 3 * d)
             self.kc[li][:, :Tp].copy_(qkv[:, :, d:2 * d])
             self.vc[li][:, :Tp].copy_(qkv[:, :, 2 * d:])
         out = self.model.out

@@ -245,6 +245,97 @@ def _empty(rows, cols, like):
     return torch.empty(rows, cols, dtype=torch.float32, device=like.device)
 
 
+# ------------------------------------------------- what a forward saves for its backward
+class MhaSaved(NamedTuple):
+    xq: torch.Tensor                     # query-side input [B*Lq, d] (compact rows under a live forward)
+    xkv: torch.Tensor                    # key-side input: xq itself, the memory, or the gathered visible rows
+    qb: torch.Tensor                     # q [Mq, d], or the fused q | k | v [Mq, 3d] when kvb is None
+    kvb: Optional[torch.Tensor]          # k | v [Mk, 2d]; None: self-attention through the fused buffer
+    o: torch.Tensor                      # attention output, before the output projection
+    lse: torch.Tensor
+    mask_u8: object                      # the mask as the attention kernels got it
+    B: int
+    Lq: int
+    Lk: int
+    site_p: int                          # dropout site of the attention probabilities
+    site_o: int                          # dropout site of the output projection
+    fused: bool                          # the output projection fused resid + dropout(.)
+    keys: object                         # ops.KeyRows the K / V rows were compacted with, or None
+    self_split: bool                     # self-attention whose K | V ran on the visible rows of xq only
+
+    @property
+    def qkv(self) -> torch.Tensor:
+        assert self.kvb is None, "no fused q | k | v buffer: K | V were projected on their own"
+        return self.qb
+
+
+class FfnSaved(NamedTuple):
+    x: torch.Tensor
+    gelu_d: torch.Tensor                 # gelu'(pre-activation) where kept, 0 where dropped
+    hdn: torch.Tensor                    # dropout(gelu(.)), the input of linear_2
+    site_h: int                          # dropout site of the hidden activation
+    site_o: int                          # dropout site of the output
+    fused: bool                          # linear_2 fused resid + dropout(.)
+
+
+class EncLayerSaved(NamedTuple):
+    x_in: torch.Tensor
+    m1: torch.Tensor                     # mean / rstd of norm_1(x_in)
+    r1: torch.Tensor
+    attn: MhaSaved
+    a: torch.Tensor                      # n1 + dropout(attn(n1))
+    m2: torch.Tensor                     # mean / rstd of norm_2(a)
+    r2: torch.Tensor
+    ffn: FfnSaved
+
+
+class DecLayerSaved(NamedTuple):
+    x: torch.Tensor
+    m1: torch.Tensor                     # mean / rstd of norm_1(x)
+    r1: torch.Tensor
+    attn_1: MhaSaved                     # self-attention
+    xa: torch.Tensor                     # x + dropout(attn_1(.))
+    m2: torch.Tensor
+    r2: torch.Tensor
+    attn_2: MhaSaved                     # cross-attention over the encoder memory
+    xb: torch.Tensor                     # xa + dropout(attn_2(.))
+    m3: torch.Tensor
+    r3: torch.Tensor
+    ffn: FfnSaved
+
+
+class EncoderSaved(NamedTuple):
+    src: torch.Tensor
+    econds: Optional[torch.Tensor]
+    site_pe: int                         # dropout site of the embedding
+    layers: List[EncLayerSaved]
+    x_last: torch.Tensor                 # the last layer's output, input of the final Norm
+    mean: torch.Tensor
+    rstd: torch.Tensor
+    B: int
+    L: int
+
+
+class DecoderSaved(NamedTuple):
+    trg: torch.Tensor
+    z2: torch.Tensor                     # z as [B*Le, latent]
+    dconds: Optional[torch.Tensor]
+    site_pe: int
+    layers: List[DecLayerSaved]
+    x_last: torch.Tensor
+    mean: torch.Tensor
+    rstd: torch.Tensor
+    B: int
+    T: int                               # decoder rows per sample, condition rows of cond2dec included
+    Le: int
+    Lk: int                              # memory rows per sample: Le + the condition rows of cond2lat
+    c2d: bool
+    c2l: bool
+    trg_mask_u8: Optional[torch.Tensor]  # unpacked: the backward's ops.LiveRows checks its rows against it
+    keys: object                         # plan.dec_keys of the forward
+    live: object                         # plan.live of the forward: the trunk ran on these compact rows
+
+
 # ------------------------------------------------------------------------------------- MHA
 def mha_fwd(run: Run, m, xq, xkv, B, Lq, Lk, mask_u8, resid, want_probs=False, keys=None, live=None):
     """m: MultiHeadAttention module (q_linear, k_linear, v_linear, out).  xq [B*Lq,d],
@@ -290,12 +381,12 @@ def mha_fwd(run: Run, m, xq, xkv, B, Lq, Lk, mask_u8, resid, want_probs=False, k
                        resid=resid, p=run.p, seed=run.seed, site=site_o, live=live)
     else:
         ops.linear_fwd(o, [m.out.weight], [m.out.bias], [y], d)
-    saved = (xq, xkv, qb, kvb, o, lse, mask_u8, B, Lq, Lk, site_p, site_o, resid is not None,
-             None if (self_attn and live is not None) else keys, self_split)
+    saved = MhaSaved(xq, xkv, qb, kvb, o, lse, mask_u8, B, Lq, Lk, site_p, site_o, resid is not None,
+                     None if (self_attn and live is not None) else keys, self_split)
     return y, saved, probs
 
 
-def mha_bwd(run: Run, m, saved, dy, G: GradSink, dxq_out, depi_q, dxkv_out=None,
+def mha_bwd(run: Run, m, sv: MhaSaved, dy, G: GradSink, dxq_out, depi_q, dxkv_out=None,
             depi_kv=ops.DEPI_STORE, live=None, gdrop=None):
     """dy: gradient w.r.t. the block output (resid + dropout(out(o)) or out(o)); gdrop: dropout_bwd(dy) already
     computed by the producer of dy (ops.norm_bwd(drop=...)).
@@ -303,10 +394,10 @@ def mha_bwd(run: Run, m, saved, dy, G: GradSink, dxq_out, depi_q, dxkv_out=None,
     d(xkv) into dxkv_out (epilogue depi_kv).  The identity path to `resid` is the caller's.
     live (ops.LiveRows): the QUERY-side rows (dy, dxq_out) are quad-compacted; saved forward tensors are
     gathered on the way in, key/value-side gradients of cross-attention stay in the encoder's row space."""
-    xq, xkv, qb, kvb, o, lse, mask_u8, B, Lq, Lk, site_p, site_o, fused, keys, self_split = saved
+    B, Lq, Lk, keys = sv.B, sv.Lq, sv.Lk, sv.keys
     d, H = m.d_model, m.h
     dk = d // H
-    Mq, Mk = B * Lq, xkv.shape[0]
+    Mq, Mk = B * Lq, sv.xkv.shape[0]
     kt = run.kt
     new = lambda cols: _empty(Mq, cols, dy)                                      # noqa: E731
     if live is not None:
@@ -314,22 +405,22 @@ def mha_bwd(run: Run, m, saved, dy, G: GradSink, dxq_out, depi_q, dxkv_out=None,
         # rows of a live quad that belong to no sample's live prefix are never written by the attention kernel
         new = live.empty_zero_gaps
         # (a forward that ran on the compact rows saved compact activations: nothing to gather)
-        o_in, xq_in = (o, xq) if live.fwd else (live.gather(o), live.gather(xq))
+        o_in, xq_in = (sv.o, sv.xq) if live.fwd else (live.gather(sv.o), live.gather(sv.xq))
     else:
-        o_in, xq_in = o, xq
+        o_in, xq_in = sv.o, sv.xq
     if gdrop is not None:
         g = gdrop
     else:
-        g = ops.dropout_bwd(dy, run.p, run.seed, site_o, live=live) if (fused and run.p > 0) else dy
+        g = ops.dropout_bwd(dy, run.p, run.seed, sv.site_o, live=live) if (sv.fused and run.p > 0) else dy
     ops.linear_wgrad([g], d, o_in, [G(m.out.weight)], [G(m.out.bias)], kt=kt)
     do = _empty(Mq, d, dy) if live is None else live.empty(d)
     ops.linear_dgrad([g], d, Mq, [m.out.weight], do)
-    if kvb is None:  # self-attention: fused [q|k|v]
+    if sv.kvb is None:  # self-attention: fused [q|k|v]
         dqkv = new(3 * d)
         fwdc = live is not None and live.fwd             # q | k | v and o are compact too: address K / V like dK / dV
-        ops.attn_bwd(qb, qb[:, d:], qb[:, 2 * d:], 3 * d, 3 * d, 3 * d, mask_u8, o, do, lse, dqkv,
+        ops.attn_bwd(sv.qb, sv.qb[:, d:], sv.qb[:, 2 * d:], 3 * d, 3 * d, 3 * d, sv.mask_u8, sv.o, do, sv.lse, dqkv,
                      dqkv[:, d:], dqkv[:, 2 * d:], 3 * d, 3 * d, 3 * d, B, H, Lq, Lk, dk, run.p,
-                     run.seed, site_p, live=live, kv_compact=live is not None and not fwdc,
+                     run.seed, sv.site_p, live=live, kv_compact=live is not None and not fwdc,
                      keys=live if fwdc else None)
         segs = [dqkv, dqkv[:, d:], dqkv[:, 2 * d:]]
         ops.linear_wgrad(segs, 3 * d, xq_in,
@@ -344,14 +435,14 @@ def mha_bwd(run: Run, m, saved, dy, G: GradSink, dxq_out, depi_q, dxkv_out=None,
             dkv = _empty(Mk, 2 * d, dy)
         else:      # compacted keys: the rows that pad a quad belong to no sample and are never written
             dkv = keys.empty_zero_gaps(2 * d)
-        ops.attn_bwd(qb, kvb, kvb[:, d:], d, 2 * d, 2 * d, mask_u8, o, do, lse, dq, dkv, dkv[:, d:],
-                     d, 2 * d, 2 * d, B, H, Lq, Lk, dk, run.p, run.seed, site_p, live=live, keys=keys)
+        ops.attn_bwd(sv.qb, sv.kvb, sv.kvb[:, d:], d, 2 * d, 2 * d, sv.mask_u8, sv.o, do, sv.lse, dq, dkv, dkv[:, d:],
+                     d, 2 * d, 2 * d, B, H, Lq, Lk, dk, run.p, run.seed, sv.site_p, live=live, keys=keys)
         ops.linear_wgrad([dq], d, xq_in, [G(m.q_linear.weight)], [G(m.q_linear.bias)], kt=kt)   # query rows
-        ops.linear_wgrad([dkv, dkv[:, d:]], 2 * d, xkv,
+        ops.linear_wgrad([dkv, dkv[:, d:]], 2 * d, sv.xkv,
                          [G(m.k_linear.weight), G(m.v_linear.weight)],
                          [G(m.k_linear.bias), G(m.v_linear.bias)])
         ops.linear_dgrad([dq], d, Mq, [m.q_linear.weight], dxq_out, depi=depi_q)
-        if self_split:       # K | V came from the visible rows of xq itself: their input gradient goes back into d(xq)
+        if sv.self_split:    # K | V came from the visible rows of xq itself: their input gradient goes back into d(xq)
             dxk = keys.empty(d)
             ops.linear_dgrad([dkv, dkv[:, d:]], 2 * d, Mk, [m.k_linear.weight, m.v_linear.weight], dxk)
             keys.scatter_add(dxk, dxq_out)
@@ -376,11 +467,11 @@ def ffn_fwd(run: Run, ff, x, resid, live=None):
                        epi=ops.EPI_DROP_RESID, resid=resid, p=run.p, seed=run.seed, site=site_o, live=live)
     else:
         ops.linear_fwd(hdn, [ff.linear_2.weight], [ff.linear_2.bias], [y], d)
-    return y, (x, gelu_d, hdn, site_h, site_o, resid is not None)
+    return y, FfnSaved(x, gelu_d, hdn, site_h, site_o, resid is not None)
 
 
-def ffn_bwd(run: Run, ff, saved, dy, G: GradSink, dx_out, depi, live=None, gdrop=None):
-    x, gelu_d, hdn, site_h, site_o, fused = saved
+def ffn_bwd(run: Run, ff, sv: FfnSaved, dy, G: GradSink, dx_out, depi, live=None, gdrop=None):
+    x, gelu_d, hdn = sv.x, sv.gelu_d, sv.hdn
     M, d = x.shape
     dff = gelu_d.shape[1]
     kt = run.kt
@@ -392,11 +483,11 @@ def ffn_bwd(run: Run, ff, saved, dy, G: GradSink, dx_out, depi, live=None, gdrop
     if gdrop is not None:
         g = gdrop
     else:
-        g = ops.dropout_bwd(dy, run.p, run.seed, site_o, live=live) if (fused and run.p > 0) else dy
+        g = ops.dropout_bwd(dy, run.p, run.seed, sv.site_o, live=live) if (sv.fused and run.p > 0) else dy
     ops.linear_wgrad([g], d, hdn, [G(ff.linear_2.weight)], [G(ff.linear_2.bias)], kt=kt)
     dpre = _empty(M, dff, dy) if live is None else live.empty(dff)
     ops.linear_dgrad([g], d, M, [ff.linear_2.weight], dpre, depi=ops.DEPI_MUL_SAVED, pre=gelu_d,
-                     p=run.p, seed=run.seed, site=site_h, live=live, pre_full=live is not None and not live.fwd)
+                     p=run.p, seed=run.seed, site=sv.site_h, live=live, pre_full=live is not None and not live.fwd)
     ops.linear_wgrad([dpre], dff, x, [G(ff.linear_1.weight)], [G(ff.linear_1.bias)], kt=kt)
     ops.linear_dgrad([dpre], dff, M, [ff.linear_1.weight], dx_out, depi=depi)
 
@@ -407,35 +498,34 @@ def enc_layer_fwd(run: Run, layer, x_in, B, L, mask_u8, want_probs=False, keys=N
     a, sv_a, probs = mha_fwd(run, layer.attn, n1, n1, B, L, L, mask_u8, n1, want_probs, keys=keys)
     n2, m2, r2 = ops.norm_fwd(a, layer.norm_2.alpha, layer.norm_2.bias, layer.norm_2.eps)
     out, sv_f = ffn_fwd(run, layer.ff, n2, n2)
-    return out, (x_in, m1, r1, sv_a, a, m2, r2, sv_f), probs
+    return out, EncLayerSaved(x_in, m1, r1, sv_a, a, m2, r2, sv_f), probs
 
 
-def _mha_drop(run: Run, sv, buf):
+def _mha_drop(run: Run, sv: MhaSaved, buf):
     """ops.norm_bwd(drop=...) request for the attention block saved in sv: the Norm backward that produces the
     gradient of that block's output also writes dropout_bwd of it (the block's own first step) into buf."""
-    return (buf, run.p, run.seed, sv[11]) if (buf is not None and sv[12] and run.p > 0) else None
+    return (buf, run.p, run.seed, sv.site_o) if (buf is not None and sv.fused and run.p > 0) else None
 
 
-def _ffn_drop(run: Run, sv, buf):
-    return (buf, run.p, run.seed, sv[4]) if (buf is not None and sv is not None and sv[5] and run.p > 0) else None
+def _ffn_drop(run: Run, sv: Optional[FfnSaved], buf):
+    return (buf, run.p, run.seed, sv.site_o) if (buf is not None and sv is not None and sv.fused and run.p > 0) else None
 
 
-def enc_layer_bwd(run: Run, layer, saved, g, G: GradSink, gd=None, gdbuf=None, below=None):
+def enc_layer_bwd(run: Run, layer, sv: EncLayerSaved, g, G: GradSink, gd=None, gdbuf=None, below=None):
     """g: mutable [M,d] gradient buffer w.r.t. the layer output; returns d(x_in) in g.
     gd: dropout_bwd(g) for this layer's FFN if the caller's Norm backward already produced it; gdbuf: scratch
     [M,d] for the fused dropout_bwd outputs; below: saved FFN state of the layer underneath (its dropout_bwd is
     written by this layer's last Norm backward) -- returns (g, that buffer or None)."""
-    x_in, m1, r1, sv_a, a, m2, r2, sv_f = saved
     with ops.deferred_reductions():      # the layer's 6 weight / bias / Norm slab reductions: one launch at the end
         # out = n2 + drop(ffn(n2))  =>  d(n2) = g + ffn'(g): the W1 dgrad accumulates into g
-        ffn_bwd(run, layer.ff, sv_f, g, G, g, ops.DEPI_ACCUM, gdrop=gd)
-        dr = _mha_drop(run, sv_a, gdbuf)
-        ops.norm_bwd(g, a, layer.norm_2.alpha, m2, r2, G(layer.norm_2.alpha), G(layer.norm_2.bias),
+        ffn_bwd(run, layer.ff, sv.ffn, g, G, g, ops.DEPI_ACCUM, gdrop=gd)
+        dr = _mha_drop(run, sv.attn, gdbuf)
+        ops.norm_bwd(g, sv.a, layer.norm_2.alpha, sv.m2, sv.r2, G(layer.norm_2.alpha), G(layer.norm_2.bias),
                      out=g, eps=layer.norm_2.eps, drop=dr)
         # a = n1 + drop(attn(n1))
-        mha_bwd(run, layer.attn, sv_a, g, G, g, ops.DEPI_ACCUM, gdrop=None if dr is None else gdbuf)
+        mha_bwd(run, layer.attn, sv.attn, g, G, g, ops.DEPI_ACCUM, gdrop=None if dr is None else gdbuf)
         dr = _ffn_drop(run, below, gdbuf)
-        ops.norm_bwd(g, x_in, layer.norm_1.alpha, m1, r1, G(layer.norm_1.alpha), G(layer.norm_1.bias),
+        ops.norm_bwd(g, sv.x_in, layer.norm_1.alpha, sv.m1, sv.r1, G(layer.norm_1.alpha), G(layer.norm_1.bias),
                      out=g, eps=layer.norm_1.eps, drop=dr)
     _grads_done(layer, G)
     return g, (None if dr is None else gdbuf)
@@ -444,32 +534,32 @@ def enc_layer_bwd(run: Run, layer, saved, g, G: GradSink, gd=None, gdbuf=None, b
 def dec_layer_fwd(run: Run, layer, x, e, B, T, Lk, src_mask_u8, trg_mask_u8, want_probs=False, keys=None, live=None):
     """live (ops.LiveRows with .fwd): x and everything row-wise of this layer hold the compact live rows only."""
     x2, m1, r1 = ops.norm_fwd(x, layer.norm_1.alpha, layer.norm_1.bias, layer.norm_1.eps)
-    xa, sv1, p1 = mha_fwd(run, layer.attn_1, x2, x2, B, T, T, trg_mask_u8, x, want_probs, live=live)
+    xa, sa1, p1 = mha_fwd(run, layer.attn_1, x2, x2, B, T, T, trg_mask_u8, x, want_probs, live=live)
     x2, m2, r2 = ops.norm_fwd(xa, layer.norm_2.alpha, layer.norm_2.bias, layer.norm_2.eps)
-    xb, sv2, p2 = mha_fwd(run, layer.attn_2, x2, e, B, T, Lk, src_mask_u8, xa, want_probs, keys=keys, live=live)
+    xb, sa2, p2 = mha_fwd(run, layer.attn_2, x2, e, B, T, Lk, src_mask_u8, xa, want_probs, keys=keys, live=live)
     x2, m3, r3 = ops.norm_fwd(xb, layer.norm_3.alpha, layer.norm_3.bias, layer.norm_3.eps)
-    xc, svf = ffn_fwd(run, layer.ff, x2, xb, live=live)
-    return xc, (x, m1, r1, sv1, xa, m2, r2, sv2, xb, m3, r3, svf), p1, p2
+    xc, sf = ffn_fwd(run, layer.ff, x2, xb, live=live)
+    return xc, DecLayerSaved(x, m1, r1, sa1, xa, m2, r2, sa2, xb, m3, r3, sf), p1, p2
 
 
-def dec_layer_bwd(run: Run, layer, saved, g, de, first_de, G: GradSink, live=None, gd=None, gdbuf=None, below=None):
+def dec_layer_bwd(run: Run, layer, sv: DecLayerSaved, g, de, first_de, G: GradSink, live=None, gd=None, gdbuf=None,
+                  below=None):
     """live (ops.LiveRows): g and every row-wise gradient of this layer are quad-compacted [live.Mc, d].
     gd / gdbuf / below as in enc_layer_bwd; returns (g, dropout_bwd(g) for the FFN of the layer underneath or None)."""
-    x, m1, r1, sv1, xa, m2, r2, sv2, xb, m3, r3, svf = saved
     t = torch.empty_like(g) if live is None else live.empty(g.shape[1])
     with ops.deferred_reductions():      # the layer's 9 weight / bias / Norm slab reductions: one launch at the end
-        ffn_bwd(run, layer.ff, svf, g, G, t, ops.DEPI_STORE, live=live, gdrop=gd)
-        dr = _mha_drop(run, sv2, gdbuf)
-        ops.norm_bwd(t, xb, layer.norm_3.alpha, m3, r3, G(layer.norm_3.alpha), G(layer.norm_3.bias),
+        ffn_bwd(run, layer.ff, sv.ffn, g, G, t, ops.DEPI_STORE, live=live, gdrop=gd)
+        dr = _mha_drop(run, sv.attn_2, gdbuf)
+        ops.norm_bwd(t, sv.xb, layer.norm_3.alpha, sv.m3, sv.r3, G(layer.norm_3.alpha), G(layer.norm_3.bias),
                      dres=g, out=g, eps=layer.norm_3.eps, live=live, drop=dr)
-        mha_bwd(run, layer.attn_2, sv2, g, G, t, ops.DEPI_STORE, de,
+        mha_bwd(run, layer.attn_2, sv.attn_2, g, G, t, ops.DEPI_STORE, de,
                 ops.DEPI_STORE if first_de else ops.DEPI_ACCUM, live=live, gdrop=None if dr is None else gdbuf)
-        dr = _mha_drop(run, sv1, gdbuf)
-        ops.norm_bwd(t, xa, layer.norm_2.alpha, m2, r2, G(layer.norm_2.alpha), G(layer.norm_2.bias),
+        dr = _mha_drop(run, sv.attn_1, gdbuf)
+        ops.norm_bwd(t, sv.xa, layer.norm_2.alpha, sv.m2, sv.r2, G(layer.norm_2.alpha), G(layer.norm_2.bias),
                      dres=g, out=g, eps=layer.norm_2.eps, live=live, drop=dr)
-        mha_bwd(run, layer.attn_1, sv1, g, G, t, ops.DEPI_STORE, live=live, gdrop=None if dr is None else gdbuf)
+        mha_bwd(run, layer.attn_1, sv.attn_1, g, G, t, ops.DEPI_STORE, live=live, gdrop=None if dr is None else gdbuf)
         dr = _ffn_drop(run, below, gdbuf)
-        ops.norm_bwd(t, x, layer.norm_1.alpha, m1, r1, G(layer.norm_1.alpha), G(layer.norm_1.bias),
+        ops.norm_bwd(t, sv.x, layer.norm_1.alpha, sv.m1, sv.r1, G(layer.norm_1.alpha), G(layer.norm_1.bias),
                      dres=g, out=g, eps=layer.norm_1.eps, live=live, drop=dr)
     _grads_done(layer, G)
     return g, (None if dr is None else gdbuf)
@@ -501,33 +591,33 @@ def encoder_trunk_fwd(enc, run: Run, src, mask_u8, econds, want_probs, plan: Row
     site_pe = run.site()
     x = ops.embed_pe_fwd(src, enc.embed_sentence.embed.weight, cond, _pe2d(enc.pe, L), nc,
                          math.sqrt(d), run.p, run.seed, site_pe)
-    lsv, probs = [], []
+    layers, probs = [], []
     for layer in enc.layers:
         x, sv, pr = enc_layer_fwd(run, layer, x, B, L, mask_u8, want_probs, keys=keys)
-        lsv.append(sv)
+        layers.append(sv)
         probs.append(pr)
     y, mean, rstd = ops.norm_fwd(x, enc.norm.alpha, enc.norm.bias, enc.norm.eps)
-    return y.view(B, L, d), (src, econds, site_pe, lsv, x, mean, rstd, B, L), probs
+    return y.view(B, L, d), EncoderSaved(src, econds, site_pe, layers, x, mean, rstd, B, L), probs
 
 
-def encoder_trunk_bwd(enc, run: Run, saved, dy, G: GradSink):
-    src, econds, site_pe, lsv, x_last, mean, rstd, B, L = saved
+def encoder_trunk_bwd(enc, run: Run, sv: EncoderSaved, dy, G: GradSink):
+    layers, B, L = sv.layers, sv.B, sv.L
     d, nc = enc.d_model, enc.nconds
     g = dy.reshape(B * L, d).clone()
     # every Norm backward also writes dropout_bwd of its result for the sub-layer that consumes it next (gdbuf)
-    gdbuf = torch.empty_like(g) if (run.p > 0 and len(lsv) > 0) else None
-    dr = _ffn_drop(run, lsv[-1][-1] if lsv else None, gdbuf)
-    ops.norm_bwd(g, x_last, enc.norm.alpha, mean, rstd, G(enc.norm.alpha), G(enc.norm.bias), out=g,
+    gdbuf = torch.empty_like(g) if (run.p > 0 and len(layers) > 0) else None
+    dr = _ffn_drop(run, layers[-1].ffn if layers else None, gdbuf)
+    ops.norm_bwd(g, sv.x_last, enc.norm.alpha, sv.mean, sv.rstd, G(enc.norm.alpha), G(enc.norm.bias), out=g,
                  eps=enc.norm.eps, drop=dr)
     gd = None if dr is None else gdbuf
-    for i in range(len(lsv) - 1, -1, -1):
-        g, gd = enc_layer_bwd(run, enc.layers[i], lsv[i], g, G, gd=gd, gdbuf=gdbuf,
-                              below=lsv[i - 1][-1] if i > 0 else None)
+    for i in range(len(layers) - 1, -1, -1):
+        g, gd = enc_layer_bwd(run, enc.layers[i], layers[i], g, G, gd=gd, gdbuf=gdbuf,
+                              below=layers[i - 1].ffn if i > 0 else None)
     dcond = torch.empty(B, nc * d, dtype=torch.float32, device=g.device) if nc > 0 else None
-    ops.embed_pe_bwd(g, src, G(enc.embed_sentence.embed.weight), dcond, nc, math.sqrt(d), run.p,
-                     run.seed, site_pe)
+    ops.embed_pe_bwd(g, sv.src, G(enc.embed_sentence.embed.weight), dcond, nc, math.sqrt(d), run.p,
+                     run.seed, sv.site_pe)
     if nc > 0:
-        ops.small_linear_bwd(dcond, econds.contiguous(), G(enc.embed_cond2enc.weight),
+        ops.small_linear_bwd(dcond, sv.econds.contiguous(), G(enc.embed_cond2enc.weight),
                              G(enc.embed_cond2enc.bias))
 
 
@@ -575,7 +665,7 @@ def decoder_trunk_fwd(dec, run: Run, trg, z, src_mask_u8, trg_mask_u8, dconds, w
         if src_mask_u8 is not None:                                            # vaetf.py:95-98
             ones = torch.ones(B, nc, dtype=torch.uint8, device=src_mask_u8.device)
             src_mask_u8 = torch.cat([ones, src_mask_u8.view(B, Le)], dim=1).contiguous()
-    lsv, p1s, p2s = [], [], []
+    layers, p1s, p2s = [], [], []
     live, keys = plan.live, plan.dec_keys
     if live is not None:
         x = live.gather(x)
@@ -585,19 +675,20 @@ def decoder_trunk_fwd(dec, run: Run, trg, z, src_mask_u8, trg_mask_u8, dconds, w
     trg_m = ops.pack_mask(trg_mask_u8, B, T, T)
     for layer in dec.layers:
         x, sv, p1, p2 = dec_layer_fwd(run, layer, x, e, B, T, Lk, src_m, trg_m, want_probs, keys=keys, live=live)
-        lsv.append(sv)
+        layers.append(sv)
         p1s.append(p1)
         p2s.append(p2)
     y, mean, rstd = ops.norm_fwd(x, dec.norm.alpha, dec.norm.bias, dec.norm.eps)
-    saved = (trg, z2, dconds, site_pe, lsv, x, mean, rstd, B, T, Le, Lk, c2d, c2l,
-             trg_mask_u8.u8 if isinstance(trg_mask_u8, ops.MaskBits) else trg_mask_u8, keys, live)
+    saved = DecoderSaved(trg, z2, dconds, site_pe, layers, x, mean, rstd, B, T, Le, Lk, c2d, c2l,
+                         trg_mask_u8.u8 if isinstance(trg_mask_u8, ops.MaskBits) else trg_mask_u8, keys, live)
     if live is not None:
         return y, saved, p1s, p2s        # [Mc, d] COMPACT rows: the caller holds the plan and scatters what it needs
     return y.view(B, T, d), saved, p1s, p2s
 
 
-def decoder_trunk_bwd(dec, run: Run, saved, dy, G: GradSink, need_dz=True):
-    trg, z2, dconds, site_pe, lsv, x_last, mean, rstd, B, T, Le, Lk, c2d, c2l, trg_mask_u8, keys, live_fwd = saved
+def decoder_trunk_bwd(dec, run: Run, sv: DecoderSaved, dy, G: GradSink, need_dz=True):
+    layers, keys, live_fwd = sv.layers, sv.keys, sv.live
+    B, T, Le, Lk = sv.B, sv.T, sv.Le, sv.Lk
     new_de = (lambda: _empty(B * Lk, d, dy)) if keys is None else (lambda: keys.empty(d))     # d(memory), maybe compact
     d, nc = dec.d_model, dec.nconds
     # A decoder row whose incoming gradient is zero (padded target positions under the ignore_index loss: 56 % of
@@ -610,7 +701,7 @@ def decoder_trunk_bwd(dec, run: Run, saved, dy, G: GradSink, need_dz=True):
     # weight-gradient GEMMs reducing over the live token tiles (the list names every tile when the check fails).
     live, lr = live_fwd, None
     if live_fwd is None:
-        lr = ops.LiveRows(dy.reshape(B * T, d), B, T, trg_mask_u8) if (COMPACT_BWD or (B * T) % 32 == 0) else None
+        lr = ops.LiveRows(dy.reshape(B * T, d), B, T, sv.trg_mask_u8) if (COMPACT_BWD or (B * T) % 32 == 0) else None
         if COMPACT_BWD and len(dec.layers) > 0 and not torch.cuda.is_current_stream_capturing():
             live = lr if RowPlan.usable_live(lr.host(), B * T) else None       # one 32-byte read-back per step
     if live_fwd is not None:
@@ -623,16 +714,16 @@ def decoder_trunk_bwd(dec, run: Run, saved, dy, G: GradSink, need_dz=True):
         g = dy.reshape(B * T, d).clone()
         run.kt = lr.kt if (lr is not None and (B * T) % 32 == 0) else None
     gdbuf = None
-    if run.p > 0 and len(lsv) > 0:
+    if run.p > 0 and len(layers) > 0:
         gdbuf = torch.empty_like(g) if live is None else live.empty(d)
-    dr = _ffn_drop(run, lsv[-1][-1] if lsv else None, gdbuf)
-    ops.norm_bwd(g, x_last, dec.norm.alpha, mean, rstd, G(dec.norm.alpha), G(dec.norm.bias), out=g,
+    dr = _ffn_drop(run, layers[-1].ffn if layers else None, gdbuf)
+    ops.norm_bwd(g, sv.x_last, dec.norm.alpha, sv.mean, sv.rstd, G(dec.norm.alpha), G(dec.norm.bias), out=g,
                  eps=dec.norm.eps, live=live, drop=dr)
     gd = None if dr is None else gdbuf
     de = new_de()
-    for i in range(len(lsv) - 1, -1, -1):
-        g, gd = dec_layer_bwd(run, dec.layers[i], lsv[i], g, de, i == len(lsv) - 1, G, live=live, gd=gd,
-                              gdbuf=gdbuf, below=lsv[i - 1][-1] if i > 0 else None)
+    for i in range(len(layers) - 1, -1, -1):
+        g, gd = dec_layer_bwd(run, dec.layers[i], layers[i], g, de, i == len(layers) - 1, G, live=live, gd=gd,
+                              gdbuf=gdbuf, below=layers[i - 1].ffn if i > 0 else None)
     run.kt = None
     if live is not None:
         g = live.scatter(g)                             # back to [B*T, d]: zero rows where nothing was live
@@ -641,25 +732,25 @@ def decoder_trunk_bwd(dec, run: Run, saved, dy, G: GradSink, need_dz=True):
     if keys is not None:
         de = keys.scatter(de)                            # back to [B*Lk, d]: masked keys get no gradient
     # embedding side
-    dcx = torch.empty(B, nc * d, dtype=torch.float32, device=g.device) if c2d else None
-    ops.embed_pe_bwd(g, trg, G(dec.embed.embed.weight), dcx, nc if c2d else 0, math.sqrt(d), run.p,
-                     run.seed, site_pe)
-    if c2d:
-        ops.small_linear_bwd(dcx, dconds.contiguous(), G(dec.embed_cond2dec.weight),
+    dcx = torch.empty(B, nc * d, dtype=torch.float32, device=g.device) if sv.c2d else None
+    ops.embed_pe_bwd(g, sv.trg, G(dec.embed.embed.weight), dcx, nc if sv.c2d else 0, math.sqrt(d), run.p,
+                     run.seed, sv.site_pe)
+    if sv.c2d:
+        ops.small_linear_bwd(dcx, sv.dconds.contiguous(), G(dec.embed_cond2dec.weight),
                              G(dec.embed_cond2dec.bias))
     # memory side
     dez = de
-    if c2l:
+    if sv.c2l:
         dcl = torch.empty(B, nc * d, dtype=torch.float32, device=g.device)
         ops.copy_rows(de, Lk, 0, dcl, nc, 0, B * nc, nc, d)
-        ops.small_linear_bwd(dcl, dconds.contiguous(), G(dec.embed_cond2lat.weight),
+        ops.small_linear_bwd(dcl, sv.dconds.contiguous(), G(dec.embed_cond2lat.weight),
                              G(dec.embed_cond2lat.bias))
         dez = _empty(B * Le, d, g)
         ops.copy_rows(de, Lk, nc, dez, Le, 0, B * Le, Le, d)
-    ops.linear_wgrad([dez], d, z2, [G(dec.fc_z.weight)], [G(dec.fc_z.bias)])
+    ops.linear_wgrad([dez], d, sv.z2, [G(dec.fc_z.weight)], [G(dec.fc_z.bias)])
     dz = None
     if need_dz:
-        dz = _empty(B * Le, z2.shape[1], g)
+        dz = _empty(B * Le, sv.z2.shape[1], g)
         ops.linear_dgrad([dez], d, B * Le, [dec.fc_z.weight], dz)
         dz = dz.view(B, Le, -1)
     return dz

@@ -6,6 +6,7 @@ forward/backward passes.  PyTorch is used only for device memory and streams.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import threading
@@ -370,23 +371,21 @@ def linear_fwd(x2d, ws_: Sequence[torch.Tensor], bs: Sequence[Optional[torch.Ten
         if t is not None and t.numel() * 4 < need:
             raise _lib.GctError(f"linear_fwd: workspace of {t.numel() * 4} B < {need} B "
                                 f"(gct_linear_fwd_ws_bytes({M}, {K}, {nper * len(ws_)}))")
-    if splitk_ws is not None:      # skinny-M path (decode): split-K through the workspace
-        check(_L().gct_linear_fwd_ws(_p(x2d), x2d.stride(0), M, K, w[0], w[1], w[2], ws_[0].stride(0),
-                                     b[0], b[1], b[2], len(ws_), nper, y[0], y[1], y[2], ldy, epi,
-                                     _p(resid), _p(pre), p, seed, site, _p(splitk_ws), splitk_ws.numel() * 4, _st()),
-              "gct_linear_fwd_ws")
-        return
-    wp, pstride = _plane_ptr(ws_)
-    wsb = ws if ws is not None else (workspace(need, x2d.device) if need > 256 else None)
-    N = nper * len(ws_)
-    nbytes = 4 * M * K + (6 if wp else 4) * N * K + 4 * N + 4 * M * N * (2 if epi in (EPI_GELU_DROP, EPI_DROP_RESID, EPI_GELU_DROP_SAVE) else 1)
-    with _Timed("gemm_fwd", 2.0 * M * K * N, nbytes):
-        check(_L().gct_linear_fwd_p(_p(x2d), x2d.stride(0), M, K, w[0], w[1], w[2], ws_[0].stride(0),
-                                    wp, pstride, b[0], b[1], b[2], len(ws_), nper, y[0], y[1], y[2],
-                                    ldy, epi, _p(resid), _p(pre), p, seed, site, _p(wsb),
-                                    0 if wsb is None else wsb.numel() * 4,
-                                    None if live is None else _p(live.quad_list), _st()),
-              "gct_linear_fwd_p")
+    if splitk_ws is not None:      # skinny-M path (decode): split-K through this workspace; no planes, no quad map
+        wp, pstride, wsb, quad_map, timed = None, 0, splitk_ws, None, contextlib.nullcontext()
+    else:
+        wp, pstride = _plane_ptr(ws_)
+        wsb = ws if ws is not None else (workspace(need, x2d.device) if need > 256 else None)
+        quad_map = None if live is None else _p(live.quad_list)
+        N = nper * len(ws_)
+        nbytes = 4 * M * K + (6 if wp else 4) * N * K + 4 * N + 4 * M * N * (2 if epi in (EPI_GELU_DROP, EPI_DROP_RESID, EPI_GELU_DROP_SAVE) else 1)
+        timed = _Timed("gemm_fwd", 2.0 * M * K * N, nbytes)
+    with timed:
+        check(_L().gct_linear_fwd(_p(x2d), x2d.stride(0), M, K, w[0], w[1], w[2], ws_[0].stride(0),
+                                  wp, pstride, b[0], b[1], b[2], len(ws_), nper, y[0], y[1], y[2],
+                                  ldy, epi, _p(resid), _p(pre), p, seed, site, _p(wsb),
+                                  0 if wsb is None else wsb.numel() * 4, quad_map, _st()),
+              "gct_linear_fwd")
 
 
 def linear_dgrad(dys: Sequence[torch.Tensor], lddy: int, M: int, ws_: Sequence[torch.Tensor], dx,
@@ -399,12 +398,12 @@ def linear_dgrad(dys: Sequence[torch.Tensor], lddy: int, M: int, ws_: Sequence[t
         wp, pstride = _plane_ptr(ws_)
         need = _ws_need("gct_linear_dgrad_ws_bytes", M, nper * len(ws_), K)
         wsb = workspace(need, dx.device) if need > 256 else None
-        check(_L().gct_linear_dgrad_p(d[0], d[1], d[2], lddy, M, len(ws_), nper, w[0], w[1], w[2],
-                                      ws_[0].stride(0), wp, pstride, K, _p(dx), dx.stride(0), depi,
-                                      _p(pre), p, seed, site, _p(wsb), 0 if wsb is None else wsb.numel() * 4,
-                                      None if live is None else _p(live.quad_list),
-                                      pre.shape[0] if (live is not None and pre is not None and pre_full) else 0,
-                                      _st()), "gct_linear_dgrad_p")
+        check(_L().gct_linear_dgrad(d[0], d[1], d[2], lddy, M, len(ws_), nper, w[0], w[1], w[2],
+                                    ws_[0].stride(0), wp, pstride, K, _p(dx), dx.stride(0), depi,
+                                    _p(pre), p, seed, site, _p(wsb), 0 if wsb is None else wsb.numel() * 4,
+                                    None if live is None else _p(live.quad_list),
+                                    pre.shape[0] if (live is not None and pre is not None and pre_full) else 0,
+                                    _st()), "gct_linear_dgrad")
 
 
 def nonzero_row_tiles(x2d: torch.Tensor):
@@ -623,10 +622,10 @@ def linear_wgrad(dys: Sequence[torch.Tensor], lddy: int, x2d, dws: Sequence[torc
     def launch():
         ws = kept_workspace(_ws_need("gct_wgrad_ws_bytes", M, nseg * nper, K), x2d.device)
         with _Timed("gemm_wgrad+bias+reduce", 2.0 * M * K * nper * nseg):
-            check(_L().gct_linear_wgrad_kt(d[0], d[1], d[2], lddy, M, nseg, nper, _p(x2d), x2d.stride(0),
-                                           K, dw[0], dw[1], dw[2], K, db[0], db[1], db[2], _p(ws),
-                                           _p(kt[0]) if kt else None, _p(kt[1]) if kt else None, _st()),
-                  "gct_linear_wgrad_kt")
+            check(_L().gct_linear_wgrad(d[0], d[1], d[2], lddy, M, nseg, nper, _p(x2d), x2d.stride(0),
+                                        K, dw[0], dw[1], dw[2], K, db[0], db[1], db[2], _p(ws),
+                                        _p(kt[0]) if kt else None, _p(kt[1]) if kt else None, _st()),
+                  "gct_linear_wgrad")
 
     if not SIDE_ENABLED or torch.cuda.is_current_stream_capturing():
         launch()
@@ -854,8 +853,8 @@ def ce_bwd(logits2d, target, gout, pad_id):
 def adam_step(p, g, m, v, lr, b1, b2, eps, step, gscale=1.0, guard=True):
     """guard: the update is skipped ON THE DEVICE when a gradient has landed on a decoder row that the forward skipped
     (skipped_row_gradients() != 0): the wrong gradient is never applied, and the next read-back raises."""
-    check(_L().gct_adam_step_guarded(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, b1, b2, eps, step, gscale,
-                                     _p(skipped_row_gradients()) if guard else None, _st()), "gct_adam_step_guarded")
+    check(_L().gct_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, b1, b2, eps, step, gscale,
+                             _p(skipped_row_gradients()) if guard else None, _st()), "gct_adam_step")
 
 
 # ---------------------------------------------------------------------------------- utility

@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 18
+#define GCT_ABI_VERSION 19
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -95,23 +95,23 @@ int gct_embed_pe_bwd(const float* dout, const int64_t* tok, float* dtable, float
 #define GCT_EPI_GELU_DROP_SAVE 3
 int gct_linear_fwd(const float* x, int64_t ldx, int64_t M, int K,
                    const float* w0, const float* w1, const float* w2, int64_t ldw,
-                   const float* b0, const float* b1, const float* b2, int nseg, int nper,
-                   float* y0, float* y1, float* y2, int64_t ldy,
+                   const uint16_t* wp0, int64_t plane_stride,
+                   const float* b0, const float* b1, const float* b2,
+                   int nseg, int nper, float* y0, float* y1, float* y2, int64_t ldy,
                    int epi, const float* resid, float* pre, float p, uint64_t seed, uint32_t site,
-                   void* stream);
-
-/* Same contract with a caller-provided workspace (>= gct_linear_fwd_ws_bytes): lets skinny-M
- * shapes (decode steps, M = batch rows) run split-K with a fused reduce+epilogue pass so all CUs
- * get work; identical results up to fp32 summation order. */
+                   float* ws, int64_t ws_bytes, const int32_t* quad_map, void* stream);
+/* wp0 (nullable): the weights' bf16 planes (gct_split_planes, below): wp0 = plane 0 of w0; the planes of w1, w2 are
+ * addressed as wp0 + (w1 - w0), wp0 + (w2 - w0) (the layout gct_split_planes produces over a common buffer).
+ * wp0 == NULL, or mode GCT_GEMM_F32: the fp32 kernels.
+ * ws (nullable): caller-provided workspace (>= gct_linear_fwd_ws_bytes), ws_bytes its size.  It lets skinny-M shapes
+ * (decode steps, M = batch rows) run split-K with a fused reduce+epilogue pass so all CUs get work, and the bf16x6
+ * launches balance their tail (see gct_linear_dgrad); identical results up to fp32 summation order.  A route that
+ * needs more slabs than ws holds takes fewer K-splits (same result up to the fp32 summation order) or no workspace
+ * route at all; nothing is ever written past ws + ws_bytes.
+ * quad_map (nullable): the M rows are a quad compaction of a larger row space (gct_live_rows); the dropout masks of the
+ * GCT_EPI_GELU_DROP / GCT_EPI_DROP_RESID epilogues are then drawn at the coordinates of original quad quad_map[q] for
+ * compact quad q, i.e. every live row gets exactly the mask it would get in the full row space. */
 int64_t gct_linear_fwd_ws_bytes(int64_t M, int K, int Ntot);
-int gct_linear_fwd_ws(const float* x, int64_t ldx, int64_t M, int K,
-                      const float* w0, const float* w1, const float* w2, int64_t ldw,
-                      const float* b0, const float* b1, const float* b2, int nseg, int nper,
-                      float* y0, float* y1, float* y2, int64_t ldy,
-                      int epi, const float* resid, float* pre, float p, uint64_t seed, uint32_t site,
-                      float* ws, int64_t ws_bytes, void* stream);
-/* ws_bytes: size of ws.  A route that needs more slabs than ws holds takes fewer K-splits (same result up to the
- * fp32 summation order) or no workspace route at all; nothing is ever written past ws + ws_bytes. */
 
 /* dx[m][k] (op)= sum_s sum_n dy_s[m][n] * w_s[n][k]
  *   GCT_DEPI_STORE / GCT_DEPI_ACCUM (dx += ...) /
@@ -125,17 +125,34 @@ int gct_linear_fwd_ws(const float* x, int64_t ldx, int64_t M, int K,
 #define GCT_DEPI_MUL_SAVED 3
 int gct_linear_dgrad(const float* dy0, const float* dy1, const float* dy2, int64_t lddy,
                      int64_t M, int nseg, int nper,
-                     const float* w0, const float* w1, const float* w2, int64_t ldw, int K,
+                     const float* w0, const float* w1, const float* w2, int64_t ldw,
+                     const uint16_t* wp0, int64_t plane_stride, int K,
                      float* dx, int64_t lddx, int depi, const float* pre, float p, uint64_t seed,
-                     uint32_t site, void* stream);
+                     uint32_t site, float* ws, int64_t ws_bytes, const int32_t* quad_map, int64_t pre_rows,
+                     void* stream);
+/* wp0 / plane_stride (nullable): the weights' bf16 planes, as for gct_linear_fwd.
+ * quad_map (nullable): the M rows are quad-compacted (gct_live_rows); GCT_DEPI_GELU_BWD then regenerates the dropout
+ * mask of compact quad q from original quad quad_map[q].  pre_rows == 0: pre is compact like dy / dx; pre_rows > 0:
+ * pre keeps the forward's row space (pre_rows rows) and is read through the quad map (no gathered copy needed) --
+ * for GCT_DEPI_GELU_BWD and GCT_DEPI_MUL_SAVED alike.
+ * ws (nullable): >= gct_linear_dgrad_ws_bytes(M, nseg*nper, K), ws_bytes its size.  With a workspace the
+ * bf16x6 forward / dgrad launches balance a partial last round of tiles (the tail rows as a second launch: on 64 x 128
+ * tiles when the reduction is <= 1024 long, else K-split into slabs + a fix-up kernel) and split a long reduction over
+ * few tiles across the whole chip; gct_linear_fwd_ws_bytes covers the forward (skinny split-K or tail slabs, whichever
+ * the launch would use).  Without one every launch is a single kernel. */
+int64_t gct_linear_dgrad_ws_bytes(int64_t M, int Ntot, int K);
 
 /* dw_s[n][k] = sum_m dy_s[m][n] * x[m][k] ; db_s[n] = sum_m dy_s[m][n]  (overwrite).
  * Split over M into fp32 slabs in ws, reduced deterministically (no atomics).
- * ws >= gct_wgrad_ws_bytes(M, nseg*nper, K). db* nullable. */
+ * ws >= gct_wgrad_ws_bytes(M, nseg*nper, K). db* nullable.
+ * tile_list / tile_count (nullable, together): reduce only over the listed 32-row token tiles (gct_nonzero_row_tiles /
+ * gct_live_rows, below) -- exact whenever every dy row outside them is zero (the skipped terms are 0 * x).  The list
+ * is honoured by the bf16x6 kernel; the fp32 kernels reduce over all rows (same result). */
 int gct_linear_wgrad(const float* dy0, const float* dy1, const float* dy2, int64_t lddy,
                      int64_t M, int nseg, int nper, const float* x, int64_t ldx, int K,
                      float* dw0, float* dw1, float* dw2, int64_t lddw,
-                     float* db0, float* db1, float* db2, float* ws, void* stream);
+                     float* db0, float* db1, float* db2, float* ws,
+                     const int32_t* tile_list, const int32_t* tile_count, void* stream);
 
 /* ---- GEMM arithmetic mode and pre-split weights ------------------------------------------
  * The nn.Linear GEMMs (Model/sublayers.py:54-59,64-66,70,81-88) run in one of two modes with
@@ -175,43 +192,10 @@ int64_t gct_gemm_x3_launches(void);
 int gct_split_planes(const float* src, int64_t numel, uint16_t* planes, int64_t plane_stride,
                      void* stream);
 
-/* gct_linear_fwd_ws / gct_linear_dgrad with the weights' bf16 planes: wp0 = plane 0 of w0; the planes
- * of w1, w2 are addressed as wp0 + (w1 - w0), wp0 + (w2 - w0) (the layout gct_split_planes produces
- * over a common buffer).  wp0 == NULL, or mode GCT_GEMM_F32: identical to the plain entry points. */
-int gct_linear_fwd_p(const float* x, int64_t ldx, int64_t M, int K,
-                     const float* w0, const float* w1, const float* w2, int64_t ldw,
-                     const uint16_t* wp0, int64_t plane_stride,
-                     const float* b0, const float* b1, const float* b2,
-                     int nseg, int nper, float* y0, float* y1, float* y2, int64_t ldy,
-                     int epi, const float* resid, float* pre, float p, uint64_t seed, uint32_t site,
-                     float* ws, int64_t ws_bytes, const int32_t* quad_map, void* stream);
-/* quad_map of gct_linear_fwd_p (nullable): the M rows are a quad compaction of a larger row space (gct_live_rows); the
- * dropout masks of the GCT_EPI_GELU_DROP / GCT_EPI_DROP_RESID epilogues are then drawn at the coordinates of original quad
- * quad_map[q] for compact quad q, i.e. every live row gets exactly the mask it would get in the full row space. */
-int gct_linear_dgrad_p(const float* dy0, const float* dy1, const float* dy2, int64_t lddy,
-                       int64_t M, int nseg, int nper,
-                       const float* w0, const float* w1, const float* w2, int64_t ldw,
-                       const uint16_t* wp0, int64_t plane_stride, int K,
-                       float* dx, int64_t lddx, int depi, const float* pre, float p, uint64_t seed,
-                       uint32_t site, float* ws, int64_t ws_bytes, const int32_t* quad_map, int64_t pre_rows,
-                       void* stream);
-/* quad_map (nullable): the M rows are quad-compacted (gct_live_rows); GCT_DEPI_GELU_BWD then regenerates the dropout
- * mask of compact quad q from original quad quad_map[q].  pre_rows == 0: pre is compact like dy / dx; pre_rows > 0:
- * pre keeps the forward's row space (pre_rows rows) and is read through the quad map (no gathered copy needed) --
- * for GCT_DEPI_GELU_BWD and GCT_DEPI_MUL_SAVED alike. */
-/* ws of gct_linear_dgrad_p (nullable): >= gct_linear_dgrad_ws_bytes(M, nseg*nper, K).  With a workspace the
- * bf16x6 forward / dgrad launches balance a partial last round of tiles (the tail rows as a second launch: on 64 x 128
- * tiles when the reduction is <= 1024 long, else K-split into slabs + a fix-up kernel) and split a long reduction over
- * few tiles across the whole chip; gct_linear_fwd_ws_bytes covers the forward (skinny split-K or tail slabs, whichever
- * the launch would use).  Without one every launch is a single kernel. */
-int64_t gct_linear_dgrad_ws_bytes(int64_t M, int Ntot, int K);
-
 /* Zero-gradient rows.  Under an ignore_index loss the rows of padded target positions carry exactly zero
  * gradients through the whole decoder backward.  gct_nonzero_row_tiles lists, in ascending order, the 32-row
  * tiles of x[rows][cols] that hold a non-zero element (list: >= ceil(rows/32) int32; count: device scalar;
- * flags_ws: >= ceil(rows/32) bytes); gct_linear_wgrad_kt is gct_linear_wgrad reducing only over the listed
- * token tiles -- exact whenever every dy row outside them is zero (the skipped terms are 0 * x).  The list is
- * honoured by the bf16x6 kernel; the fp32 kernels reduce over all rows (same result). */
+ * flags_ws: >= ceil(rows/32) bytes) for gct_linear_wgrad's tile_list / tile_count. */
 /* *counter += number of rows of g[rows][cols] with live[row] == 0 that hold a non-zero element: the check a forward
  * that SKIPPED the dead rows (decoder forward over the rows that reach the loss) owes its backward -- a gradient on a
  * skipped row cannot be honoured.  The caller reads the counter at its next host synchronisation. */
@@ -228,7 +212,7 @@ int gct_nonzero_row_tiles(const float* x, int64_t ld, int64_t rows, int cols, in
  *   info [8] i32: [0] live rows, [1] samples that violate the property, [2] samples whose live rows are not the
  *                 prefix 0..n_b-1, [3] listed token tiles, [4] compact rows (multiple of 128), [5] live quads;
  *   tile_list / tile_count / tile_flags_ws (nullable, together): the 32-row token tiles that hold a live row --
- *   EVERY tile when info[1] != 0, so gct_linear_wgrad_kt stays exact without a host round trip;
+ *   EVERY tile when info[1] != 0, so gct_linear_wgrad stays exact without a host round trip;
  *   cstart [B] / quad_list [ceil(B*T/4)+32] / qrank_ws [ceil(B*T/4)] (nullable, together): the COMPACTION MAP of the
  *   decoder backward.  Rows are compacted in aligned groups of 4 ("quads"), the granularity at which every dropout
  *   site draws its Philox values: compact row 4i+e <-> original row 4*quad_list[i]+e (quad_list ascending, padded
@@ -257,11 +241,6 @@ int gct_zero_gap_rows(float* buf, int64_t ld, int cols, const int32_t* cstart, c
 /* dst rows += the compact rows (gradient of rows that were gathered: the encoder's K | V over its visible rows) */
 int gct_scatter_add_quads(const float* src, int64_t ld, const int32_t* quad_list, int64_t nrows, int cols, float* dst,
                           int64_t ldd, int64_t M, void* stream);
-int gct_linear_wgrad_kt(const float* dy0, const float* dy1, const float* dy2, int64_t lddy,
-                        int64_t M, int nseg, int nper, const float* x, int64_t ldx, int K,
-                        float* dw0, float* dw1, float* dw2, int64_t lddw,
-                        float* db0, float* db1, float* db2, float* ws,
-                        const int32_t* kt_list, const int32_t* kt_count, void* stream);
 
 /* elementwise dropout backward for the GCT_EPI_DROP_RESID sites: dy = dropmask*dout/(1-p); quad_map (nullable):
  * the rows are quad-compacted, the mask of compact quad q is that of original quad quad_map[q] */
@@ -360,14 +339,12 @@ int gct_ce_bwd(const float* logits, const int64_t* target, const float* gout, fl
  * over one flat buffer of n elements; g is multiplied by gscale first (1/W folds the
  * data-parallel mean). `step` is t (1-based, already incremented). */
 int gct_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1,
-                  float b2, float eps, int64_t step, float gscale, void* stream);
-/* The same step behind a device-side guard: when *skip_if_nonzero != 0 at launch time nothing is updated (p, m, v stay
- * as they are).  The trainer passes the device counter of "gradient rows that fell on decoder rows the forward had
- * skipped" (gct_live_rows / gct_scatter_add_quads_check): a wrong gradient is then never applied, without a host
- * synchronisation in front of the update; the host raises at its next read-back.  skip_if_nonzero == NULL: no guard. */
-int gct_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1,
-                          float b2, float eps, int64_t step, float gscale, const int32_t* skip_if_nonzero,
-                          void* stream);
+                  float b2, float eps, int64_t step, float gscale, const int32_t* skip_if_nonzero,
+                  void* stream);
+/* skip_if_nonzero (nullable): a device-side guard: when *skip_if_nonzero != 0 at launch time nothing is updated (p, m,
+ * v stay as they are).  The trainer passes the device counter of "gradient rows that fell on decoder rows the forward
+ * had skipped" (gct_live_rows / gct_scatter_add_quads_check): a wrong gradient is then never applied, without a host
+ * synchronisation in front of the update; the host raises at its next read-back.  NULL: no guard. */
 
 /* --------------------------------------------------------- K11: KV-cached decode */
 /* Inference/sampling_tool.py:140-184 re-runs the whole decoder on ys[:, :i+1] each step; these
@@ -494,7 +471,7 @@ int gct_small_linear_bwd(const float* dy, const float* x, float* dw, float* db, 
 int gct_reduce_slabs(const float* slabs, int nslab, int64_t stride, float* dst, int64_t n,
                      int accumulate, void* stream);
 /* Deferred slab reductions: between gct_reduce_defer_begin and gct_reduce_defer_end every float4-shaped slab reduction
- * that the calling THREAD issues through this library (the tails of gct_linear_wgrad*, gct_norm_bwd's alpha / bias
+ * that the calling THREAD issues through this library (the tails of gct_linear_wgrad, gct_norm_bwd's alpha / bias
  * partials, bias column sums) is recorded instead of launched; gct_reduce_defer_flush launches all recorded ones as ONE
  * kernel on `stream` (same summation order per region: results are bit-identical) and keeps recording, _end flushes and
  * stops, _pending returns the number recorded.  Contract: the caller keeps every recorded call's workspace intact until

@@ -4,6 +4,8 @@ import argparse
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 import torch
@@ -14,23 +16,111 @@ from oracle import gct_oracle as O
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _exported_gct_symbols(path):
+    """The unmangled gct_* names a shared object defines (the C++-mangled helpers shared between translation units
+    start with _Z and do not count)."""
+    out = subprocess.run(["nm", "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
+    return {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("gct_")}
+
+
 def test_library_exports_every_declared_symbol():
-    """include/gctplus_hip.h <-> _lib.SIGNATURES <-> the built .so (no compute call)."""
+    """include/gctplus_hip.h <-> _lib.SIGNATURES (parsed from it) <-> the built .so (no compute call).  The name regex
+    below is independent of _lib's parser: a prototype the parser drops shows up here."""
     hdr = open(os.path.join(ROOT, "include", "gctplus_hip.h")).read()
     declared = set(re.findall(r"\b(gct_[a-z0-9_]+)\s*\(", hdr))
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
     lib = _lib.load()
-    for name in declared:
-        assert hasattr(lib, name), name
-    assert lib.gct_version() == _lib.ABI_VERSION
+    for name, (res, args) in _lib.SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+    header_version = int(re.search(r"^#define GCT_ABI_VERSION (\d+)$", hdr, flags=re.M).group(1))
+    assert header_version == lib.gct_version() == _lib.ABI_VERSION
     assert lib.gct_wgrad_ws_bytes(40960, 512, 512) > 0
     # the diagnostics library has its own header and is NOT part of the operator ABI
     dh = open(os.path.join(ROOT, "include", "gctplus_diag.h")).read()
     ddecl = set(re.findall(r"\b(gct_[a-z0-9_]+)\s*\(", dh))
     assert ddecl == set(_lib.DIAG_SIGNATURES) and not (ddecl & declared), (ddecl, declared & ddecl)
     dl = _lib.load_diag()
-    for name in ddecl:
-        assert hasattr(dl, name), name
+    for name, (res, args) in _lib.DIAG_SIGNATURES.items():
+        fn = getattr(dl, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+    # both directions: the libraries define no gct_* symbol that their header does not declare
+    if shutil.which("nm"):
+        assert _exported_gct_symbols(_lib.LIB_PATH) == declared
+        assert _exported_gct_symbols(_lib.DIAG_PATH) == ddecl
+
+
+def test_header_parser_on_a_literal_header():
+    """_lib.parse_prototypes alone: one prototype per supported type, pointers by the two pointer rules, a prototype over
+    several lines, (void), comments that look like calls, a struct typedef; an unknown value type or text that is no
+    prototype raises and names it -- nothing is bound by default."""
+    C = ctypes
+    text = """
+    /* gct_in_a_comment(int a); is not a prototype */
+    #ifndef X_H
+    #define X_H
+    #define GCT_ABI_VERSION 7   /* gct_define(1) */
+    #ifdef __cplusplus
+    extern "C" {
+    #endif
+    // gct_line_comment(float x);
+    typedef struct GctThing { int32_t k; float p; } GctThing;
+    int gct_version(void);
+    const char* gct_last_error(void);
+    int64_t gct_bytes(int64_t M, int K, int32_t n, float p, uint64_t seed, uint32_t site);
+    int gct_many(const float* x, int64_t ldx,   /* gct_inside(2) */
+                 float* y, const uint16_t* planes, const int64_t* tok,
+                 const int32_t* map, uint8_t* live, void* stream,
+                 const GctThing* thing);
+    int gct_strings(const char* s, char* buf, const char* const* names, const int64_t* const* rows);
+    #ifdef __cplusplus
+    }
+    #endif
+    #endif
+    """
+    P, I, I64 = C.c_void_p, C.c_int, C.c_int64
+    assert _lib.parse_prototypes(text) == {
+        "gct_version": (I, []),
+        "gct_last_error": (C.c_char_p, []),
+        "gct_bytes": (I64, [I64, I, C.c_int32, C.c_float, C.c_uint64, C.c_uint32]),
+        "gct_many": (I, [P, I64, P, P, P, P, P, P, P]),
+        "gct_strings": (I, [C.c_char_p, C.c_char_p, P, P]),
+    }
+    for bad, named in (("int gct_a(double x);", "gct_a"), ("double gct_b(int x);", "gct_b"),
+                       ("int gct_c(unsigned int n);", "gct_c"), ("int gct_d(size_t n);", "gct_d"),
+                       ("int gct_e(int (*cb)(int));", "cb"), ("int gct_f(int a)", "gct_f")):
+        with pytest.raises(_lib.GctError, match=named):
+            _lib.parse_prototypes("int gct_ok(int a);\n" + bad)
+
+
+def test_missing_header_is_a_hard_error(monkeypatch, tmp_path):
+    monkeypatch.setattr(_lib, "INCLUDE_DIR", str(tmp_path))
+    with pytest.raises(_lib.GctError):
+        _lib._parse_header("gctplus_hip.h")
+    (tmp_path / "gctplus_hip.h").write_text("/* nothing declared */\n")
+    with pytest.raises(_lib.GctError):
+        _lib._parse_header("gctplus_hip.h")
+    with pytest.raises(_lib.GctError):
+        _lib._abi_version()
+
+
+def test_saved_state_is_read_by_name():
+    """The records a forward saves for its backward (engine.MhaSaved ... DecoderSaved) have one owner of their layout:
+    nothing in the package indexes them by position."""
+    pat = re.compile(r"saved\[\d|\bsv\[\d|\bsv1\[|\bsv2\[|\bsvf\[|\blsv\b[^\n]*\]\[-1\]")
+    hits = []
+    pkg = os.path.join(ROOT, "gct_plus_amd")
+    for d, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(".py"):
+                for no, line in enumerate(open(os.path.join(d, f), encoding="utf-8"), 1):
+                    if pat.search(line):
+                        hits.append(f"{os.path.relpath(os.path.join(d, f), ROOT)}:{no}: {line.strip()}")
+    assert not hits, hits
+    assert not pat.search("prefix = (sv[:, :-1] >= sv[:, 1:]).all(1)")          # decode.py's mask tensor
+    for line in ("x = saved[4]", "q = sv[3][2]", "s = sv[11]", "a = sv1[2]", "b = sv2[0]", "c = svf[4]",
+                 "below=lsv[i - 1][-1] if i > 0 else None"):
+        assert pat.search(line), line
 
 
 def test_attention_direct_key_limit_has_one_owner():

@@ -779,7 +779,7 @@ def test_dgrad_gelu_bwd_through_quad_map_with_tail_split(ops):
 
 
 def test_wgrad_over_nonzero_row_tiles(ops):
-    """gct_nonzero_row_tiles + gct_linear_wgrad_kt: reducing only over the 32-row token tiles whose gradient rows
+    """gct_nonzero_row_tiles + gct_linear_wgrad (tile_list): reducing only over the 32-row token tiles whose gradient rows
     are not all zero gives the dense result (the skipped terms are exact zeros)."""
     M, K, N = 32 * 260, 512, 1024
     x = rnd(M, K, seed=1).to(DEV)

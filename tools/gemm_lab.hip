@@ -79,8 +79,8 @@ int main(int argc, char** argv) {
     for (const Case& c : fc) {
       if (c.epi != GCT_EPI_BIAS && nseg > 1) continue;
       const double t = timeit([&] {
-        int rc = gct_linear_fwd_p(x, K, M, K, w, w1, w2, K, wp, pstride, b, b1, b2, nseg, nper, y, y1, y2, N, c.epi, resid, pre, c.p,
-                                  3, 1, ws, wsb, nullptr, nullptr);
+        int rc = gct_linear_fwd(x, K, M, K, w, w1, w2, K, wp, pstride, b, b1, b2, nseg, nper, y, y1, y2, N, c.epi, resid, pre, c.p,
+                                3, 1, ws, wsb, nullptr, nullptr);
         if (rc) { printf("fwd failed: %s\n", gct_last_error()); exit(1); }
       }, reps);
       printf("%-5s fwd   %-13s M=%ld K=%d N=%d: %8.1f us %6.1f TF\n", s.name, c.nm, (long)M, K, N, t, fl / t / 1e6);
@@ -90,8 +90,8 @@ int main(int argc, char** argv) {
     for (const Case& c : dc) {
       if (c.epi != GCT_DEPI_STORE && nseg > 1) continue;
       const double t = timeit([&] {
-        int rc = gct_linear_dgrad_p(resid, nseg > 1 ? resid + nper : nullptr, nseg > 2 ? resid + 2 * nper : nullptr, N, M, nseg, nper, w, w1, w2,
-                                    K, wp, pstride, K, dx, K, c.epi, pre, c.p, 3, 1, ws, wsb, nullptr, 0, nullptr);
+        int rc = gct_linear_dgrad(resid, nseg > 1 ? resid + nper : nullptr, nseg > 2 ? resid + 2 * nper : nullptr, N, M, nseg, nper, w, w1, w2,
+                                  K, wp, pstride, K, dx, K, c.epi, pre, c.p, 3, 1, ws, wsb, nullptr, 0, nullptr);
         if (rc) { printf("dgrad failed: %s\n", gct_last_error()); exit(1); }
       }, reps);
       printf("%-5s dgrad %-13s M=%ld K'=%d N'=%d: %8.1f us %6.1f TF\n", s.name, c.nm, (long)M, N, K, t, fl / t / 1e6);
@@ -102,7 +102,7 @@ int main(int argc, char** argv) {
       float* db1 = nseg > 1 ? db + nper : nullptr;
       float* db2 = nseg > 2 ? db + 2 * nper : nullptr;
       const double t = timeit([&] {
-        int rc = gct_linear_wgrad(resid, nseg > 1 ? resid + nper : nullptr, nseg > 2 ? resid + 2 * nper : nullptr, N, M, nseg, nper, x, K, K, dw, dw1, dw2, K, db, db1, db2, ws, nullptr);
+        int rc = gct_linear_wgrad(resid, nseg > 1 ? resid + nper : nullptr, nseg > 2 ? resid + 2 * nper : nullptr, N, M, nseg, nper, x, K, K, dw, dw1, dw2, K, db, db1, db2, ws, nullptr, nullptr, nullptr);
         if (rc) { printf("wgrad failed: %s\n", gct_last_error()); exit(1); }
       }, reps);
       printf("%-5s wgrad (+reduce)       M=%ld: %8.1f us %6.1f TF\n", s.name, (long)M, t, fl / t / 1e6);
