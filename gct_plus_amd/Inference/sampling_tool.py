@@ -22,6 +22,11 @@ one scaffold per row: the prefixes <sos> scaffold <sep> of different lengths are
 with per-row positions (KVDecoder.generate(prefix_lens=)), so each row gives exactly what `sample_smiles` gives for its
 scaffold alone (no left-padding, which would shift the positional encodings).  Beam search has no mixed-length kernels:
 it runs one decode per prefix length and restores the input order.
+
+`stream_rows=R` (optional): greedy / multinomial decodes run with continuous batching (KVDecoder.generate_stream) -- the
+n rows of a call are a pool that R decode rows work through, a row whose molecule reached <eos> taking the next one, so
+`sample_smiles(30000)` is one call that never computes past a molecule's end.  Every decode of such a sampler goes that
+way, also one of fewer than R rows (a single wave): what a molecule decodes then never depends on n or R.
 """
 from __future__ import annotations
 
@@ -32,7 +37,8 @@ import torch
 
 from ..Model.modules import get_src_mask
 from ..data import Vocab, tokenize
-from ..decode import BEAM_ALPHA, KVDecoder, check_beam_size, check_sample_filter, generated_tokens
+from ..decode import (BEAM_ALPHA, KVDecoder, check_beam_size, check_sample_filter, check_stream_model,
+                      check_stream_rows, generated_tokens)
 
 
 def sample_token_lengths(data: Sequence[int], size: int, rng: np.random.Generator) -> np.ndarray:
@@ -102,8 +108,14 @@ class Sampling:
                  cond_dim: int = 0, decode_algo: str = "greedy", toklen_data: Optional[Sequence[int]] = None,
                  scaler=None, device="cuda", seed: int = 0, use_graphs: bool = False, beam_size: int = 4,
                  beam_alpha: float = BEAM_ALPHA, top_k: Optional[int] = None, top_p: Optional[float] = None,
-                 temperature: float = 1.0):
+                 temperature: float = 1.0, stream_rows: Optional[int] = None):
         V = model.out.weight.shape[0]
+        if stream_rows is not None:
+            if decode_algo == "beam":
+                raise ValueError("stream_rows is not supported with decode_algo='beam' (beam search keeps its rows in step)")
+            check_stream_rows(stream_rows)
+            check_stream_model(model, latent_dim)
+        self.stream_rows = stream_rows
         if check_sample_filter(top_k, top_p, temperature, V) and decode_algo == "beam":
             raise ValueError("top_k / top_p / temperature are not supported with decode_algo='beam'")
         if decode_algo == "beam":
@@ -163,7 +175,8 @@ class Sampling:
     def decode(self, zs, ys, src_mask, dconds=None, prefix_lens=None):
         """ids [n, L] (prefix included); with decode_algo="beam" the best beam of each sample.
         prefix_lens (ints [n], optional): row r's prefix is ys[r, :t0_r] (KVDecoder.generate); not with beam search.
-        The sampler's top_k / top_p / temperature apply to every draw (sample_smiles, sample_multiple_smiles)."""
+        The sampler's top_k / top_p / temperature apply to every draw (sample_smiles, sample_multiple_smiles).
+        With stream_rows the n rows are a pool decoded by continuous batching; same layout, input order."""
         if self.decode_algo == "beam":
             if prefix_lens is not None:
                 raise ValueError("decode: beam search takes prefixes of one length (see sample_multiple_smiles)")
@@ -172,6 +185,11 @@ class Sampling:
         zs, ys, src_mask = zs.to(self.device), ys.to(self.device), src_mask.to(self.device)
         dconds = None if dconds is None else dconds.to(self.device)
         total = ys.size(1) + self.max_strlen
+        if self.stream_rows is not None:
+            self.kv.start_stream(zs, src_mask, dconds, rows=self.stream_rows, max_total_len=min(200, total))
+            return self.kv.generate_stream(ys, self.max_strlen, algo=self.decode_algo, seed=self.seed,
+                                           use_graphs=self.use_graphs, prefix_lens=prefix_lens, top_k=self.top_k,
+                                           top_p=self.top_p, temperature=self.temperature)[0]
         # the positional table has 200 rows, of which use_cond2dec spends n_c on the condition tokens
         self.kv.start(zs, src_mask, dconds, max_total_len=min(200 - self.kv.off, total))
         return self.kv.generate(ys, self.max_strlen, algo=self.decode_algo, seed=self.seed,

@@ -4,6 +4,7 @@
 //   gct_select_token : softmax over the vocabulary + greedy / multinomial choice (optionally through a top-k /
 //                      nucleus / temperature filter), appends the token, updates the key-valid flags and the
 //                      per-sample finished mask
+//   gct_stream_refill : continuous batching -- rows that finished hand out their tokens and take the next pool item
 //   gct_attn_decode_beam / gct_beam_select : the same two for beam search, with the self-attention caches
 //                      shared by ancestry through a per-row map (kv_src) instead of copied
 // Both are tiny and HBM/latency-bound; they exist so a whole decode step is a fixed kernel
@@ -262,7 +263,11 @@ __device__ __forceinline__ float u01_open(uint32_t x) { return ((float)(x >> 8) 
 // and valid[.., valid_off + *pos_dev + 1]; seed_dev (nullable) replaces the by-value seed of the multinomial draw.
 // RAGGED (pos_dev required): row r's position is *pos_dev - row_off[r] + 1 (uniform over the wave; the Philox key stays
 // (row, token position))
-template <bool RAGGED>
+// STREAM (continuous batching, RAGGED required): row r decodes pool item item[r].  A parked row (item < 0) writes
+// nothing; while the position is inside the item's prefix the slot keeps the prefix token the refill laid there (ys and
+// valid, done untouched); the Philox key is (item_base + item, token position), so a draw does not depend on the row
+// that makes it, nor on the slice of a larger pool the item came in.
+template <bool RAGGED, bool STREAM>
 __global__ __launch_bounds__(256) void select_token_kernel(const float* __restrict__ logits, int V,
                                                            int64_t* ys, int64_t ld_ys, int pos_host,
                                                            uint8_t* valid, int64_t valid_sb,
@@ -270,13 +275,22 @@ __global__ __launch_bounds__(256) void select_token_kernel(const float* __restri
                                                            int mode, int64_t pad_id, int64_t eos_id,
                                                            GctRng rng, const int32_t* __restrict__ pos_dev,
                                                            int valid_off, const uint64_t* __restrict__ seed_dev,
-                                                           const int32_t* __restrict__ row_off) {
+                                                           const int32_t* __restrict__ row_off,
+                                                           const int32_t* __restrict__ item,
+                                                           const int32_t* __restrict__ prefix_len, int item_base) {
+  static_assert(RAGGED || !STREAM, "streamed rows sit at their own positions");
   int pos = pos_dev ? *pos_dev + 1 : pos_host;
   if (seed_dev) rng = gct_rng_make(*seed_dev, 0xDEC0DEu);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = blockIdx.x * 4 + wave;
   if (row >= n) return;
   if constexpr (RAGGED) pos -= row_off[row];
+  uint32_t key = (uint32_t)row;
+  if constexpr (STREAM) {                                   // uniform over the wave: a whole wave leaves
+    const int it = item[row];
+    if (it < 0 || pos < prefix_len[it] || valid_off + pos >= valid_sb) return;
+    key = (uint32_t)(item_base + it);
+  }
   const float* lr = logits + (int64_t)row * V;
   float mx = -INFINITY;
   for (int c = lane; c < V; c += 64) mx = fmaxf(mx, lr[c]);
@@ -304,7 +318,7 @@ __global__ __launch_bounds__(256) void select_token_kernel(const float* __restri
     best = bi;
   } else {
     // multinomial: inverse CDF with one Philox uniform per (row, position)
-    const uint4 r = gct_philox(rng, (uint32_t)row, (uint32_t)pos, 0x452821E6u, 0x38D01377u);
+    const uint4 r = gct_philox(rng, key, (uint32_t)pos, 0x452821E6u, 0x38D01377u);
     const float u = u01_open(r.x);
     float cum = 0.f;
     int pick = V - 1;
@@ -343,13 +357,16 @@ __global__ __launch_bounds__(256) void select_token_kernel(const float* __restri
 // with a strictly larger value" per token: TPL == 1 (V <= 64) reads the other tokens with readlane, TPL > 1 stages the
 // row in LDS (broadcast reads).  A row the filter leaves unchanged (no token out of the top k or the nucleus) draws with
 // the plain kernel's arithmetic -- same softmax, same scan, uniform not rescaled -- so at T = 1 it picks the same token.
-template <bool RAGGED, int TPL>
+// STREAM: as in select_token_kernel.
+template <bool RAGGED, int TPL, bool STREAM>
 __global__ __launch_bounds__(256) void select_token_filtered_kernel(
     const float* __restrict__ logits, int V, int64_t* ys, int64_t ld_ys, int pos_host, uint8_t* valid, int64_t valid_sb,
     uint8_t* done, float* probs_out, int n, int64_t pad_id, int64_t eos_id, GctRng rng,
     const int32_t* __restrict__ pos_dev, int valid_off, const uint64_t* __restrict__ seed_dev,
-    const int32_t* __restrict__ row_off, const GctSampleFilter* __restrict__ filt) {
+    const int32_t* __restrict__ row_off, const GctSampleFilter* __restrict__ filt, const int32_t* __restrict__ item,
+    const int32_t* __restrict__ prefix_len, int item_base) {
 #pragma clang fp contract(off)
+  static_assert(RAGGED || !STREAM, "streamed rows sit at their own positions");
   __shared__ __attribute__((aligned(16))) float stage[4][TPL > 1 ? TPL * 64 : 4];
   int pos = pos_dev ? *pos_dev + 1 : pos_host;
   if (seed_dev) rng = gct_rng_make(*seed_dev, 0xDEC0DEu);
@@ -357,6 +374,12 @@ __global__ __launch_bounds__(256) void select_token_filtered_kernel(
   const int row = blockIdx.x * 4 + wave;
   if (row >= n) return;
   if constexpr (RAGGED) pos -= row_off[row];
+  uint32_t key = (uint32_t)row;
+  if constexpr (STREAM) {                                   // uniform over the wave: a whole wave leaves
+    const int it = item[row];
+    if (it < 0 || pos < prefix_len[it] || valid_off + pos >= valid_sb) return;
+    key = (uint32_t)(item_base + it);
+  }
   const int top_k = filt->k;
   const float top_p = filt->top_p, inv_temp = filt->inv_temp;
   const float* lr = logits + (int64_t)row * V;
@@ -448,7 +471,7 @@ __global__ __launch_bounds__(256) void select_token_filtered_kernel(
       }
   }
   changed = __ballot(changed) != 0ull;                      // wave-uniform from here on
-  const uint4 r = gct_philox(rng, (uint32_t)row, (uint32_t)pos, 0x452821E6u, 0x38D01377u);
+  const uint4 r = gct_philox(rng, key, (uint32_t)pos, 0x452821E6u, 0x38D01377u);
   float u = u01_open(r.x);
   float pscale = 1.f;
   int pick = V - 1;
@@ -493,6 +516,122 @@ __global__ __launch_bounds__(256) void select_token_filtered_kernel(
     ys[(int64_t)row * ld_ys + pos] = pick;
     if (valid) valid[(int64_t)row * valid_sb + valid_off + pos] = (pick != pad_id) ? 1 : 0;
     if (done && pick == eos_id) done[row] = 1;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- continuous batching
+// gct_stream_refill, kernel 1 of 2 (decode.py stream_schedule_reference states the rule): one workgroup walks the rows
+// in ascending order, 256 at a time.  A row is FINISHED when its item set `done` or produced limit[item] tokens in the
+// step just run (its generated length goes to out_len[item]); a finished or empty row WANTS an item.  The wanting rows
+// take items next_item, next_item + 1, ... in ascending row order (ballot + prefix count: no race decides it); a row
+// that finds the pool empty gets item -1 (parked).  harvest[r] = the item to copy out (-1: none), fresh[r] = the row's
+// slots are to be laid out again; the copies are kernel 2's.  *enable == 0: nothing happens.
+__global__ __launch_bounds__(256) void stream_scan_kernel(GctStreamState s) {
+  if (*s.enable == 0) return;
+  __shared__ int wcnt[4], hcnt[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int R = (int)s.rows, N = (int)s.items;
+  const int p = *s.pos;                                     // index of the token the step just run consumed
+  int next = *s.next_item, harvested = 0;
+  for (int base = 0; base < R; base += 256) {
+    const int r = base + tid;
+    bool want = false, harv = false;
+    int it = -1;
+    if (r < R) {
+      it = s.item[r];
+      if (it < 0 || it >= N) {
+        want = true;
+        it = -1;
+      } else {
+        const int gen = p - s.row_off[r] + 2 - s.prefix_len[it];       // tokens generated so far (<= 0: in the prefix)
+        if (gen > 0 && (s.done[r] != 0 || gen >= s.limit[it])) {
+          want = harv = true;
+          s.out_len[it] = gen;
+        }
+      }
+    }
+    const unsigned long long wb = __ballot(want), hb = __ballot(harv);
+    if (lane == 0) {
+      wcnt[wave] = __popcll(wb);
+      hcnt[wave] = __popcll(hb);
+    }
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      if (w < wave) before += wcnt[w];
+      total += wcnt[w];
+      harvested += hcnt[w];
+    }
+    if (r < R) {
+      s.harvest[r] = harv ? it : -1;
+      s.fresh[r] = want ? 1 : 0;
+      if (want) {
+        const int rank = before + __popcll(wb & ((1ull << lane) - 1ull));
+        const int ni = next + rank < N ? next + rank : -1;
+        s.item[r] = ni;
+        if (ni >= 0) {
+          s.row_of[ni] = r;
+          s.start_step[ni] = p + 1;                         // the shared step that consumes the item's token 0
+        }
+      }
+    }
+    next = next + total < N ? next + total : N;
+    __syncthreads();                                        // wcnt / hcnt are rewritten by the next 256 rows
+  }
+  if (tid == 0) {
+    *s.next_item = next;
+    *s.n_harvested += harvested;
+  }
+}
+
+// gct_stream_refill, kernel 2 of 2: one workgroup per row.  harvest[r] >= 0: the row's tokens go to out_ys[that item].
+// fresh[r]: the row restarts at its own position 0 in the next step (row_off = *pos + 1) -- with a new item its latent
+// rows, memory masks and condition rows come from the pools, ys becomes prefix + pad, valid the prefix's flags and
+// done 0; a parked row (item -1) gets the offset only, every step, so it stays at position 0 and touches nothing but
+// its own slot 0.  Every index is below T (ys, valid), the row's z / mask / condition slots, or the item's pool rows.
+__global__ __launch_bounds__(256) void stream_refill_kernel(GctStreamState s) {
+  if (*s.enable == 0) return;
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const int h = s.harvest[r];
+  const bool fresh = s.fresh[r] != 0;
+  if (h < 0 && !fresh) return;
+  int64_t* yr = s.ys + (int64_t)r * s.ld_ys;
+  const int W = (int)s.width, T = (int)s.T;
+  if (h >= 0) {
+    int64_t* orow = s.out_ys + (int64_t)h * W;
+    for (int j = tid; j < W; j += 256) orow[j] = yr[j];
+  }
+  if (!fresh) return;
+  __syncthreads();                                          // the row's tokens are out before they are overwritten
+  const int it = s.item[r];
+  if (tid == 0) s.row_off[r] = *s.pos + 1;
+  if (it < 0) return;
+  if (tid == 0) {
+    s.done[r] = 0;
+    s.src_klen[r] = s.klen_pool[it];
+  }
+  const int plen = s.prefix_len[it];
+  const int64_t* pr = s.prefix_pool + (int64_t)it * s.t0_max;
+  uint8_t* vr = s.valid + (int64_t)r * s.valid_sb + s.valid_off;
+  for (int j = tid; j < T; j += 256) {
+    const int64_t tok = j < plen ? pr[j] : s.pad_id;
+    yr[j] = tok;
+    vr[j] = tok != s.pad_id ? 1 : 0;
+  }
+  const int Lk = (int)s.Lk;
+  for (int j = tid; j < Lk; j += 256) s.src_valid[(int64_t)r * Lk + j] = s.valid_pool[(int64_t)it * Lk + j];
+  const int z4 = (int)(s.z_row / 4);
+  const float4* zp = reinterpret_cast<const float4*>(s.z_pool + (int64_t)it * s.z_row);
+  float4* zr = reinterpret_cast<float4*>(s.z3 + (int64_t)r * s.z_row);
+  for (int j = tid; j < z4; j += 256) zr[j] = zp[j];
+  const int c4 = (int)(s.ckv_row / 4);
+  if (c4 > 0) {
+    for (int l = 0; l < (int)s.layers; ++l) {
+      const float4* cp = reinterpret_cast<const float4*>(s.ckv_pool[l] + (int64_t)it * s.ckv_row);
+      float4* cr = reinterpret_cast<float4*>(s.ckv[l] + (int64_t)r * s.ckv_row);
+      for (int j = tid; j < c4; j += 256) cr[j] = cp[j];
+    }
   }
 }
 
@@ -744,37 +883,77 @@ extern "C" int gct_select_token(const float* logits, int V, int64_t* ys, int64_t
                                 uint8_t* valid, int64_t valid_sb, uint8_t* done, float* probs_out,
                                 int n, int mode, int64_t pad_id, int64_t eos_id, uint64_t seed,
                                 const int32_t* pos_dev, int valid_off, const uint64_t* seed_dev,
-                                const int32_t* row_off, const GctSampleFilter* filt, void* stream) {
+                                const int32_t* row_off, const GctSampleFilter* filt, const int32_t* item,
+                                const int32_t* prefix_len, int item_base, void* stream) {
   GCT_CHECK_ARG(logits && ys && V > 0 && n >= 0 && pos >= 0 && (mode == 0 || mode == 1) && valid_off >= 0,
                 "select_token: bad args");
   GCT_CHECK_ARG(!row_off || pos_dev, "select_token: row_off needs the device position");
   GCT_CHECK_ARG(!filt || mode == 1, "select_token: the sampling filter is for the multinomial mode");
   GCT_CHECK_ARG(!filt || V <= GCT_SAMPLE_FILTER_MAX_VOCAB, "select_token: the sampling filter supports up to %d tokens, "
                 "not %d", GCT_SAMPLE_FILTER_MAX_VOCAB, V);
+  GCT_CHECK_ARG(!item == !prefix_len && (!item || (row_off && valid && done && item_base >= 0)),
+                "select_token: streamed rows need item, prefix_len, row_off, valid and done");
   if (n == 0) return GCT_OK;
+  const dim3 grid((unsigned)((n + 3) / 4)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const GctRng rng = gct_rng_make(seed, 0xDEC0DEu);
   if (filt) {
-    const dim3 grid((unsigned)((n + 3) / 4)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    const GctRng rng = gct_rng_make(seed, 0xDEC0DEu);
+    constexpr int TPL = GCT_SAMPLE_FILTER_MAX_VOCAB / 64;
     if (V <= 64) {
-      if (row_off) hipLaunchKernelGGL((select_token_filtered_kernel<true, 1>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, row_off, filt);
-      else hipLaunchKernelGGL((select_token_filtered_kernel<false, 1>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, nullptr, filt);
+      if (item) hipLaunchKernelGGL((select_token_filtered_kernel<true, 1, true>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, row_off, filt, item, prefix_len, item_base);
+      else if (row_off) hipLaunchKernelGGL((select_token_filtered_kernel<true, 1, false>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, row_off, filt, nullptr, nullptr, 0);
+      else hipLaunchKernelGGL((select_token_filtered_kernel<false, 1, false>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, nullptr, filt, nullptr, nullptr, 0);
     } else {
-      if (row_off) hipLaunchKernelGGL((select_token_filtered_kernel<true, GCT_SAMPLE_FILTER_MAX_VOCAB / 64>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, row_off, filt);
-      else hipLaunchKernelGGL((select_token_filtered_kernel<false, GCT_SAMPLE_FILTER_MAX_VOCAB / 64>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, nullptr, filt);
+      if (item) hipLaunchKernelGGL((select_token_filtered_kernel<true, TPL, true>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, row_off, filt, item, prefix_len, item_base);
+      else if (row_off) hipLaunchKernelGGL((select_token_filtered_kernel<true, TPL, false>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, row_off, filt, nullptr, nullptr, 0);
+      else hipLaunchKernelGGL((select_token_filtered_kernel<false, TPL, false>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, nullptr, filt, nullptr, nullptr, 0);
     }
     GCT_LAUNCH_CHECK("select_token");
     return GCT_OK;
   }
-  if (row_off)
-    hipLaunchKernelGGL(select_token_kernel<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0,
-                       (hipStream_t)stream, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out,
-                       n, mode, pad_id, eos_id, gct_rng_make(seed, 0xDEC0DEu), pos_dev, valid_off, seed_dev, row_off);
+  if (item)
+    hipLaunchKernelGGL((select_token_kernel<true, true>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb,
+                       done, probs_out, n, mode, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, row_off, item,
+                       prefix_len, item_base);
+  else if (row_off)
+    hipLaunchKernelGGL((select_token_kernel<true, false>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb,
+                       done, probs_out, n, mode, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, row_off, nullptr,
+                       nullptr, 0);
   else
-    hipLaunchKernelGGL(select_token_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0,
-                       (hipStream_t)stream, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out,
-                       n, mode, pad_id, eos_id, gct_rng_make(seed, 0xDEC0DEu), pos_dev, valid_off, seed_dev, nullptr);
+    hipLaunchKernelGGL((select_token_kernel<false, false>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb,
+                       done, probs_out, n, mode, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, nullptr, nullptr,
+                       nullptr, 0);
   GCT_LAUNCH_CHECK("select_token");
+  return GCT_OK;
+}
+
+// Continuous batching: harvest the rows that finished in the step just run and hand them the next pool items.
+extern "C" int gct_stream_refill(const GctStreamState* state, void* stream) {
+  GCT_CHECK_ARG(state, "stream_refill: null state");
+  const GctStreamState& s = *state;
+  GCT_CHECK_ARG(s.ys && s.valid && s.done && s.row_off && s.pos && s.z3 && s.src_valid && s.src_klen && s.item &&
+                    s.harvest && s.fresh && s.z_pool && s.valid_pool && s.klen_pool && s.prefix_pool && s.prefix_len &&
+                    s.limit && s.out_ys && s.out_len && s.row_of && s.start_step && s.next_item && s.n_harvested &&
+                    s.enable,
+                "stream_refill: null pointer");
+  GCT_CHECK_ARG(s.rows >= 1 && s.rows <= GCT_STREAM_MAX_ROWS && s.items >= 0 && s.items <= INT_MAX - 256,
+                "stream_refill: %lld rows (1 .. %d) / %lld items", (long long)s.rows, GCT_STREAM_MAX_ROWS,
+                (long long)s.items);
+  GCT_CHECK_ARG(s.T >= 1 && s.width >= 1 && s.width <= s.T && s.ld_ys >= s.T && s.valid_sb >= s.valid_off + s.T &&
+                    s.valid_off >= 0 && s.t0_max >= 1 && s.t0_max <= s.width,
+                "stream_refill: row width %lld / cache rows %lld / prefix width %lld", (long long)s.width,
+                (long long)s.T, (long long)s.t0_max);
+  GCT_CHECK_ARG(s.z_row >= 0 && s.z_row % 4 == 0 && gct_aligned16(s.z3) && gct_aligned16(s.z_pool) && s.Lk >= 1,
+                "stream_refill: the latent rows must be 16-B aligned");
+  GCT_CHECK_ARG(s.layers >= 0 && s.layers <= GCT_STREAM_MAX_LAYERS && s.ckv_row >= 0 && s.ckv_row % 4 == 0,
+                "stream_refill: %lld layers of condition rows (at most %d)", (long long)s.layers, GCT_STREAM_MAX_LAYERS);
+  for (int l = 0; l < (int)s.layers && s.ckv_row > 0; ++l)
+    GCT_CHECK_ARG(s.ckv[l] && s.ckv_pool[l] && gct_aligned16(s.ckv[l]) && gct_aligned16(s.ckv_pool[l]),
+                  "stream_refill: condition rows of layer %d missing or not 16-B aligned", l);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(stream_scan_kernel, dim3(1), dim3(256), 0, st, s);
+  hipLaunchKernelGGL(stream_refill_kernel, dim3((unsigned)s.rows), dim3(256), 0, st, s);
+  GCT_LAUNCH_CHECK("stream_refill");
   return GCT_OK;
 }
 

@@ -36,9 +36,17 @@ Top-k / nucleus / temperature sampling (`generate(algo="multinomial", top_k=, to
 stated once, in `sample_filter_reference`; gct_select_token applies them on the device between the softmax and the
 inverse-CDF draw, reading the settings from a device buffer (`self.filt`), so one captured graph serves any settings and
 mixed-prefix rows keep their own draws.
+
+Continuous batching (`start_stream` + `generate_stream`): R decode rows work through a pool of N items.  The rule is
+stated once, in `stream_schedule_reference`; gct_stream_refill implements it on the device at the end of every step:
+a row whose item produced <eos> (or reached its cap) hands its tokens out and takes the next item of the pool -- latent
+rows, masks, condition rows, prefix -- with row_off[r] = *pos + 1, so the row restarts at its own position 0 behind the
+same shared counter.  Every item enters that way and consumes its prefix token by token through the step chain (no
+prefill), so what an item decodes depends on nothing but the item; its multinomial key is (item, token position).
 """
 from __future__ import annotations
 
+import heapq
 import math
 import numbers
 import os
@@ -65,6 +73,8 @@ REPLAY_SLOW_FACTOR = 1.3
 BEAM_ALPHA = 0.7
 BEAM = "beam"                                       # selection mode key of the beam step (self.graphs, _advance)
 FILTERED = "filtered"                               # selection mode key of the filtered multinomial draw
+STREAM = "stream"                                   # graph key suffix of the continuous-batching step unit
+STREAM_COND_CHUNK = 256                             # items per GEMM when the pool's condition rows are projected
 TOP_K_FLOOR = 1e-6                                  # weight of a token outside the top k (the reference's top_k_logits)
 
 
@@ -117,6 +127,102 @@ def sample_filter_reference(logits, top_k=None, top_p=None, temperature=1.0):
         mass = torch.where(larger > 0, top_mass.gather(-1, (larger - 1).clamp(min=0)), torch.zeros_like(top_mass))
         w = torch.where(mass < float(top_p), w, torch.zeros_like(w))
     return w / w.sum(-1, keepdim=True)
+
+
+# ------------------------------------------------------------------------------------- continuous batching
+def stream_schedule_reference(steps_needed, rows):
+    """THE statement of the continuous-batching schedule (gct_stream_refill implements it on the device).
+    steps_needed [N] ints >= 1: shared steps item i occupies a row; rows >= 1 decode rows.
+      * shared step 0 starts with items 0 .. min(rows, N) - 1 in the rows of the same index;
+      * after every shared step the rows whose item finished IN that step take the next unstarted items in ascending
+        row order; a row that finds the pool empty is parked for good.
+    Returns (row_of [N] int64, start_step [N] int64, makespan): item i runs in row row_of[i] during the shared steps
+    start_step[i] .. start_step[i] + steps_needed[i] - 1; makespan = the number of shared steps until the last item
+    is done.  An item with a prefix of t0 tokens that generates g tokens needs t0 + g - 1 steps (the step that
+    consumes token j writes token j + 1)."""
+    need = [int(x) for x in torch.as_tensor(steps_needed).view(-1).tolist()]
+    rows = int(rows)
+    if rows < 1:
+        raise ValueError(f"rows must be at least 1, got {rows}")
+    if need and min(need) < 1:
+        raise ValueError("every item needs at least one step")
+    n = len(need)
+    row_of, start = torch.zeros(n, dtype=torch.int64), torch.zeros(n, dtype=torch.int64)
+    first = min(rows, n)
+    row_of[:first] = torch.arange(first)
+    busy = [(need[i], i) for i in range(first)]         # (steps run when the row's item is done, row): a heap pops the
+    heapq.heapify(busy)                                 # rows in the order of the rule -- earlier step, then lower row
+    nxt, makespan = first, 0
+    while busy:
+        end, r = heapq.heappop(busy)
+        makespan = max(makespan, end)
+        if nxt < n:
+            row_of[nxt], start[nxt] = r, end
+            heapq.heappush(busy, (end + need[nxt], r))
+            nxt += 1
+    return row_of, start, makespan
+
+
+def check_stream_rows(rows):
+    """1 <= rows <= ops.STREAM_MAX_ROWS (gct_stream_refill's scan is one workgroup); ValueError otherwise."""
+    if isinstance(rows, bool) or not isinstance(rows, numbers.Integral):
+        raise ValueError(f"rows must be an int, got {rows!r}")
+    if not 1 <= rows <= ops.STREAM_MAX_ROWS:
+        raise ValueError(f"rows {rows} outside [1, {ops.STREAM_MAX_ROWS}]")
+    return int(rows)
+
+
+def zattn_latent_ok(model, lat):
+    """A latent of this width lets a step's cross-attention run over the latent rows themselves (gct_attn_decode_z)."""
+    dec = model.decoder
+    return bool(ZATTN and lat % 4 == 0 and lat <= 128 and dec.layers[0].attn_1.h * lat <= 2 * dec.d_model)
+
+
+def check_stream_model(model, latent_dim=None):
+    """Continuous batching needs a decoder whose condition rows do not live in the self-attention caches (they would
+    come from prefill) and whose cross-attention reads the latent rows: ValueError for use_cond2dec models, for more
+    layers than gct_stream_refill takes and, with latent_dim given, for a latent width gct_attn_decode_z does not take."""
+    dec = model.decoder
+    if latent_dim is not None and not zattn_latent_ok(model, int(latent_dim)):
+        raise ValueError(f"continuous batching needs the cross-attention over the latent rows (gct_attn_decode_z): a "
+                         f"latent of {latent_dim} keeps per-sequence K / V projections")
+    if dec.use_cond2dec and dec.nconds > 0:
+        raise ValueError("continuous batching does not support use_cond2dec models (their condition rows are written "
+                         "into the caches by prefill)")
+    if len(dec.layers) > ops.STREAM_MAX_LAYERS:
+        raise ValueError(f"continuous batching supports up to {ops.STREAM_MAX_LAYERS} decoder layers")
+
+
+def check_max_new_tokens(max_new_tokens, n, steps):
+    """Per-item caps (ints [n], 1 <= cap <= steps) as an int64 CPU tensor; None: every item may generate `steps`
+    tokens.  ValueError otherwise."""
+    if max_new_tokens is None:
+        return torch.full((n,), steps, dtype=torch.int64)
+    cap = torch.as_tensor(max_new_tokens)
+    if cap.dtype.is_floating_point or cap.dtype.is_complex or cap.dtype == torch.bool:
+        raise ValueError(f"max_new_tokens must hold integers, got {cap.dtype}")
+    cap = cap.to("cpu", torch.int64)
+    if cap.dim() != 1 or cap.numel() != n:
+        raise ValueError(f"max_new_tokens must have shape [{n}], got {list(cap.shape)}")
+    if n and (int(cap.min()) < 1 or int(cap.max()) > steps):
+        raise ValueError(f"max_new_tokens must lie in [1, {steps}] (max_strlen - 1), got [{int(cap.min())}, "
+                         f"{int(cap.max())}]")
+    return cap
+
+
+def memory_masks(src_mask, n_cond_rows, Le):
+    """Key flags of the cross-attention memory, sv uint8 [n, Lk] (n_cond_rows always-visible condition rows in front of
+    the Le latent rows), and klen int32 [n]: the rows a step reads.  Visible rows that form a non-empty prefix (the padding
+    masks of Inference/*_sampling.py) hide rows that weigh exactly 0, which gct_attn_decode does not read; any other
+    mask keeps all Lk rows."""
+    n = src_mask.shape[0]
+    sv = ops.to_mask_u8(src_mask).view(n, Le)
+    if n_cond_rows:
+        sv = torch.cat([torch.ones(n, n_cond_rows, dtype=torch.uint8, device=sv.device), sv], dim=1)
+    Lk = sv.shape[1]
+    cnt = sv.sum(1, dtype=torch.int32)
+    prefix = (sv[:, :-1] >= sv[:, 1:]).all(1) if Lk > 1 else torch.ones(n, dtype=torch.bool, device=sv.device)
+    return sv, torch.where(prefix & (cnt > 0), cnt, torch.full_like(cnt, Lk))
 
 
 # ------------------------------------------------------------------------------------- beam-search semantics
@@ -225,6 +331,8 @@ class KVDecoder:
         self.replay_probe = None                          # numbers of the replay guard (after the first capture)
         self._fold_key = None                             # what the cached folded projections were computed from
         self._shape = None
+        self.stream = None                                # continuous batching: pool + StreamState (start_stream)
+        self.streaming = False                            # a generate_stream loop is running (the step unit refills)
 
     # -------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -251,13 +359,13 @@ class KVDecoder:
         nc = dec.nconds
         c2l = (not self.c2d) and dec.use_cond2lat and nc > 0
         self.z, self.src_mask_in, self.dconds = z, src_mask, dconds
-        self.zattn = bool(ZATTN and lat % 4 == 0 and lat <= 128 and Le <= 256 and self.H * lat <= 2 * d)
+        self.zattn = self._zattn_ok(lat, Le)
         z2 = z.reshape(n * Le, lat).float().contiguous()
         Lk, e = Le, None
         if not self.zattn:
             e = ez = torch.empty(n * Le, d, device=dev)
             ops.linear_fwd(z2, [dec.fc_z.weight], [dec.fc_z.bias], [ez], d)
-        sv = ops.to_mask_u8(src_mask).view(n, Le)
+        sv, klen = memory_masks(src_mask, nc if c2l else 0, Le)
         if c2l:
             Lk = Le + nc
             cl = ops.small_linear_fwd(dconds.float().contiguous(), dec.embed_cond2lat.weight,
@@ -266,7 +374,6 @@ class KVDecoder:
                 e = torch.empty(n * Lk, d, device=dev)
                 ops.copy_rows(cl, nc, 0, e, Lk, 0, n * nc, nc, d)
                 ops.copy_rows(ez, Le, 0, e, Lk, nc, n * Le, Le, d)
-            sv = torch.cat([torch.ones(n, nc, dtype=torch.uint8, device=dev), sv], dim=1)
         T = int(max_total_len) + self.off              # cache rows: condition tokens (cond2dec) + tokens
         if T > 256 or Lk > 256:
             raise ValueError("decode lengths above 256 are not supported by gct_attn_decode")
@@ -336,11 +443,7 @@ class KVDecoder:
                             xb=f(n, d), pre=f(n, dff), hdn=f(n, dff), xc=[f(n, d), f(n, d)], y=f(n, d),
                             logits=f(n, V))
         self.src_valid.copy_(sv)
-        # visible memory rows that form a non-empty prefix (the padding masks of Inference/*_sampling.py): the masked rows
-        # behind them weigh exactly 0, gct_attn_decode does not read them; any other mask keeps all Lk rows
-        cnt = sv.sum(1, dtype=torch.int32)
-        prefix = (sv[:, :-1] >= sv[:, 1:]).all(1) if Lk > 1 else torch.ones(n, dtype=torch.bool, device=dev)
-        self.src_klen.copy_(torch.where(prefix & (cnt > 0), cnt, torch.full_like(cnt, Lk)))
+        self.src_klen.copy_(klen)
         if self.zattn:
             self.z3.copy_(z2.view(n, Le, lat))
             self._fold_cross(cl.view(n * nc, d) if c2l else None)
@@ -349,6 +452,10 @@ class KVDecoder:
             kv, a = self.cross_kv[li], layer.attn_2
             ops.linear_fwd(e, [a.k_linear.weight, a.v_linear.weight], [a.k_linear.bias, a.v_linear.bias],
                            [kv, kv[:, d:]], 2 * d)
+
+    def _zattn_ok(self, lat, Le):
+        """The cross-attention of a step runs over the latent rows themselves (gct_attn_decode_z)."""
+        return zattn_latent_ok(self.model, lat) and Le <= 256
 
     def _fold_cross(self, cl):
         """Once per sequence (the n_c condition rows) on top of a weights-only part that is CACHED across start()
@@ -519,15 +626,20 @@ class KVDecoder:
                             self.off, self.kv_src, self.bdone, self.pos, self.pad_id, self.eos_id,
                             parent_i32=self.bparent)
             return
+        st = self.stream if self.streaming else None     # continuous batching: the rows' items and their prefix lengths
         ops.select_token(self.buf["logits"], self.ys, 0, self.valid, self.done, 1 if mode == FILTERED else mode,
                          self.pad_id, self.eos_id, pos_dev=self.pos, valid_off=self.off, seed_dev=self.seed,
                          row_off=self.row_off if self.ragged else None,
-                         filt_dev=self.filt if mode == FILTERED else None)
+                         filt_dev=self.filt if mode == FILTERED else None,
+                         item=st and st["item"], prefix_len=st and st["prefix_len"],
+                         item_base=st["item_base"] if st else 0)
 
     def _advance(self, mode):
-        """One step and its selection: the unit a graph captures."""
+        """One step and its selection: the unit a graph captures.  Continuous batching: then the refill."""
         self.step(beam=mode == BEAM)
         self._select(mode)
+        if self.streaming:
+            self.stream["state"].refill()
 
     # -------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -619,11 +731,209 @@ class KVDecoder:
         return beam_finalize(ys.view(ns, k, last), self.bscores.view(ns, k).clone(),
                              self.blen.view(ns, k).to(torch.int64), t0, alpha)
 
+    # ------------------------------------------------------------------------------------- continuous batching
+    @torch.no_grad()
+    def start_stream(self, z, src_mask, dconds=None, rows=512, max_total_len=208, refold=False, item_base=0):
+        """Prepare `rows` decode rows and a pool of N items for generate_stream: z [N, L_e, latent], src_mask bool
+        [N, 1, L_e], dconds [N, n_c] as start() takes them, N smaller or larger than `rows`.  max_total_len and refold
+        as in start().  item_base: the pool is items item_base .. item_base + N - 1 of a larger one (their multinomial
+        keys; a pool taken in slices decodes exactly what it decodes whole).
+        ValueError before any device work for use_cond2dec models, for a latent geometry whose cross-attention keeps
+        per-sequence K / V projections (gct_attn_decode_z not taken: `GCT_DECODE_ZATTN=0`, latent wider than 128 or
+        than 2 d_model / H) and for rows outside [1, ops.STREAM_MAX_ROWS].
+        HBM: the pool stays on the device until the next start_stream -- N * L_e * latent * 4 B of latent rows,
+        N * (L_e + n_c) B of masks, and with cond2lat the projected condition rows, N * n_c * 2 d_model * 4 B PER
+        LAYER (full-size model, n_c = 3, d_model = 512, 6 layers: 2.4 GB at N = 32 768), plus the prefix and result
+        tables, 2 * N * T * 8 B.  The pool is not sliced internally; a caller short of memory passes slices with
+        item_base.  A pool of the same geometry as the last one (N, rows, latent shape, max_total_len) is copied into
+        the same buffers, so the captured stream graphs live on across start_stream / generate_stream calls, as the
+        plain path's do; a new geometry drops them."""
+        check_stream_model(self.model)
+        R = check_stream_rows(rows)
+        if z.dim() != 3:
+            raise ValueError(f"z must be [N, L_e, latent], got {list(z.shape)}")
+        N, Le, lat = z.shape
+        if not self._zattn_ok(lat, Le):
+            raise ValueError("continuous batching needs the cross-attention over the latent rows (gct_attn_decode_z): "
+                             f"latent {lat} / {Le} rows keep per-sequence K / V projections")
+        dec, d, dev = self.dec, self.d, z.device
+        nc = dec.nconds
+        c2l = bool(dec.use_cond2lat and nc > 0)
+        if c2l and (dconds is None or tuple(dconds.shape) != (N, nc)):
+            raise ValueError(f"a cond2lat model needs dconds [{N}, {nc}]")
+        if tuple(src_mask.shape) != (N, 1, Le):                    # the refill copies L_e flags per item from the pool
+            raise ValueError(f"src_mask must be [{N}, 1, {Le}] (one flag per latent row), got {list(src_mask.shape)}")
+        if N < 1 or int(item_base) < 0 or int(item_base) + N >= 2 ** 31 - 256:
+            raise ValueError(f"a pool of {N} items at item_base {item_base} does not fit")
+        # the rows' buffers, geometry and folded projections: start() on placeholder rows (every row's latent rows, masks
+        # and condition rows are laid out by the refill before the row's first step)
+        self.start(torch.zeros(R, Le, lat, device=dev), torch.ones(R, 1, Le, dtype=torch.bool, device=dev),
+                   torch.zeros(R, nc, device=dev) if c2l else None, max_total_len, refold)
+        sv, klen = memory_masks(src_mask.to(dev), nc if c2l else 0, Le)
+        key = (N, R, self._shape, c2l, self.ys.data_ptr())         # (start() reallocates the rows with a new geometry)
+        st = self.stream
+        if st is None or st["key"] != key:
+            # a new pool geometry: new buffers, a new GctStreamState, and the stream graphs that held the old addresses
+            # go.  The same geometry again (the sampler's next call) is copied into the buffers: its graphs stay
+            T = self.T
+            i32 = lambda *a: torch.zeros(*a, dtype=torch.int32, device=dev)               # noqa: E731
+            st = self.stream = dict(
+                key=key, rows=R, items=N, ckv_row=nc * 2 * d if c2l else 0,
+                z_pool=torch.empty(N, Le * lat, device=dev), valid_pool=torch.empty_like(sv),
+                klen_pool=torch.empty_like(klen),
+                ckv_pool=[torch.empty(N * nc, 2 * d, device=dev) for _ in dec.layers] if c2l else [],
+                prefix_pool=torch.full((N, T), self.pad_id, dtype=torch.int64, device=dev), prefix_len=i32(N),
+                limit=i32(N), out_ys=torch.full((N, T), self.pad_id, dtype=torch.int64, device=dev), out_len=i32(N),
+                row_of=i32(N), start_step=i32(N), item=i32(R), harvest=i32(R),
+                fresh=torch.zeros(R, dtype=torch.uint8, device=dev), next_item=i32(1), n_harvested=i32(1),
+                enable=i32(1))
+            st["state"] = ops.StreamState().set(
+                ys=self.ys, valid=self.valid, done=self.done, row_off=self.row_off, pos=self.pos, z3=self.z3,
+                src_valid=self.src_valid, src_klen=self.src_klen, ckv=[c for c in self.ckv if c is not None],
+                item=st["item"], harvest=st["harvest"], fresh=st["fresh"], z_pool=st["z_pool"],
+                valid_pool=st["valid_pool"], klen_pool=st["klen_pool"], ckv_pool=st["ckv_pool"],
+                prefix_pool=st["prefix_pool"], prefix_len=st["prefix_len"], limit=st["limit"], out_ys=st["out_ys"],
+                out_len=st["out_len"], row_of=st["row_of"], start_step=st["start_step"], next_item=st["next_item"],
+                n_harvested=st["n_harvested"], enable=st["enable"], rows=R, items=N, ld_ys=self.ys.stride(0),
+                valid_sb=self.valid.stride(0), valid_off=0, T=T, width=T, t0_max=T, z_row=self.z3.stride(0), Lk=self.Lk,
+                ckv_row=st["ckv_row"], layers=len(dec.layers) if c2l else 0, pad_id=self.pad_id)
+            self._drop_stream_graphs()
+        st["item_base"] = int(item_base)
+        st["z_pool"].copy_(z.reshape(N, Le * lat))
+        st["valid_pool"].copy_(sv)
+        st["klen_pool"].copy_(klen)
+        if c2l:
+            self._cond_rows_pool(dconds.to(dev), st["ckv_pool"])
+
+    def _cond_rows_pool(self, dconds, pool):
+        """The shifted keys | values of every item's condition rows (what _fold_cross computes per row) into pool, per
+        layer [N * n_c, 2 d].  Projected STREAM_COND_CHUNK items per GEMM, the last chunk padded, so that the GEMM shape --
+        and with it an item's rounding -- does not depend on the size of the pool."""
+        dec, d, nc, dev = self.dec, self.d, self.dec.nconds, dconds.device
+        N, CH = dconds.shape[0], STREAM_COND_CHUNK
+        chunk, kv = torch.zeros(CH, nc, device=dev), torch.empty(CH * nc, 2 * d, device=dev)
+        for lo in range(0, N, CH):
+            m = min(CH, N - lo)
+            chunk.zero_()
+            chunk[:m] = dconds[lo:lo + m].float()
+            cl = ops.small_linear_fwd(chunk, dec.embed_cond2lat.weight, dec.embed_cond2lat.bias).view(CH * nc, d)
+            for li, layer in enumerate(dec.layers):
+                a = layer.attn_2
+                ops.linear_fwd(cl, [a.k_linear.weight, a.v_linear.weight], [a.k_linear.bias, a.v_linear.bias],
+                               [kv, kv[:, d:]], 2 * d)
+                kv.view(-1, 2, d).sub_(self.zcv[li].view(1, 2, d))
+                pool[li][lo * nc:(lo + m) * nc].copy_(kv[:m * nc])
+
+    def _drop_stream_graphs(self):
+        """A captured stream step holds the addresses of the pool's buffers: new buffers, new graphs."""
+        for key in [k for k in self.graphs if isinstance(k, tuple) and k[1] == STREAM]:
+            del self.graphs[key]
+
+    @torch.no_grad()
+    def generate_stream(self, ys0, max_strlen=80, algo="greedy", seed=0, prefix_lens=None, max_new_tokens=None,
+                        top_k=None, top_p=None, temperature=1.0, use_graphs=False, check_every=8):
+        """Decode the pool of start_stream with continuous batching: item i starts from the prefix ys0[i, :t0_i]
+        (ys0 [N, t0_max], prefix_lens ints [N] or None = all t0_max) and generates until <eos> or max_new_tokens[i]
+        tokens (ints [N] in [1, max_strlen - 1]; None: max_strlen - 1); a row that finishes takes the next item
+        (stream_schedule_reference).  algo / seed / top_k / top_p / temperature / use_graphs as in generate(); the
+        multinomial key of a draw is (item_base + i, token position).
+        Returns (ys, record): ys [N, t0_max + G] int64 in ITEM order with generate(prefix_lens=)'s layout -- item i's
+        tokens from column t0_i, pad behind its last one (generated_tokens works on it), cut after the longest item's
+        <eos> when every item produced one -- and record = dict(steps: shared steps until the last item was done,
+        launched: step units issued (the host looks at ONE device word, n_harvested, every check_every steps and
+        nothing else), row_of [N], start_step [N], out_len [N] generated tokens with the <eos>, harvested).
+        ValueError before any device work for beam search, bad prefix_lens / max_new_tokens / sampling settings and
+        lengths beyond the positional table or the cache rows of start_stream."""
+        if algo not in ("greedy", "multinomial"):
+            raise ValueError(f"generate_stream decodes greedy or multinomial, not {algo!r} (beam search keeps its rows "
+                             "in step: generate_beam)")
+        check_stream_model(self.model)
+        V = self.model.out.weight.shape[0]
+        filtered = check_sample_filter(top_k, top_p, temperature, V) and algo == "multinomial"
+        if filtered and V > ops.SAMPLE_FILTER_MAX_VOCAB:
+            raise ValueError(f"top-k / nucleus / temperature sampling supports vocabularies up to "
+                             f"{ops.SAMPLE_FILTER_MAX_VOCAB} tokens, not {V}")
+        if ys0.dim() != 2 or ys0.shape[1] < 1:
+            raise ValueError(f"ys0 must be [N, t0_max >= 1], got {list(ys0.shape)}")
+        N, t0 = ys0.shape
+        steps = int(max_strlen) - 1
+        if N < 1 or steps < 1:
+            raise ValueError("generate_stream: needs at least one item and max_strlen >= 2")
+        if isinstance(check_every, bool) or not isinstance(check_every, numbers.Integral) or check_every < 1:
+            raise ValueError(f"check_every must be an int >= 1, got {check_every!r}")
+        lens = check_prefix_lens(prefix_lens, N, t0)
+        lens = torch.full((N,), t0, dtype=torch.int64) if lens is None else lens
+        cap = check_max_new_tokens(max_new_tokens, N, steps)
+        W = t0 + steps
+        pe_rows = self.dec.pe.pe.shape[1]
+        if W > pe_rows:
+            raise ValueError(f"prefix {t0} + {steps} steps exceed the {pe_rows}-row positional table")
+        st = self.stream
+        if st is None:
+            raise ValueError("generate_stream: no pool (call start_stream first)")
+        if N != st["items"]:
+            raise ValueError(f"generate_stream: {N} prefixes for the {st['items']} items start_stream prepared")
+        if st["key"][2] != self._shape or st["key"][4] != self.ys.data_ptr():      # start() laid the rows out anew since
+            raise ValueError("generate_stream: the decoder's rows are not the ones start_stream prepared (start() was "
+                             "called with another geometry since); call start_stream again")
+        if W > self.T:
+            raise ValueError(f"prefix {t0} + {steps} steps exceeds the cache length {self.T}")
+        dev, R = self.ys.device, st["rows"]
+        cols = torch.arange(t0).view(1, -1)
+        prefix = torch.where(cols < lens.view(-1, 1), ys0.cpu(), torch.full_like(ys0.cpu(), self.pad_id))
+        st["prefix_pool"][:, :t0].copy_(prefix)                    # (columns behind t0 are never read: prefix_len <= t0)
+        st["prefix_len"].copy_(lens)
+        st["limit"].copy_(cap)
+        st["out_ys"].fill_(self.pad_id)
+        for name, v in (("out_len", 0), ("row_of", -1), ("start_step", -1), ("item", -1), ("harvest", -1), ("fresh", 0),
+                        ("next_item", 0), ("n_harvested", 0), ("enable", 1)):
+            st[name].fill_(v)
+        mode = {"greedy": 0, "multinomial": 1}[algo]
+        self.seed.fill_(int(seed) & 0x7FFFFFFFFFFFFFFF)
+        if filtered:
+            mode = FILTERED
+            self.filt.copy_(ops.sample_filter_settings(top_k, top_p, temperature, V))
+        self.ragged = True
+        self.pos.fill_(-1)                                         # the first step consumes every row's token 0
+        self.row_off.zero_()
+        self.ys.fill_(self.pad_id)
+        self.valid.zero_()
+        self.done.zero_()
+        # list scheduling ends within sum / R + max steps (Graham): a loop that runs past it has lost an item
+        most = (N // R + 2) * W + check_every
+        launched = 0
+        self.streaming = True
+        try:
+            st["state"].refill()                                   # the first wave enters like every later item
+            while True:
+                self._run_step(mode, use_graphs)
+                launched += 1
+                if launched % check_every == 0:
+                    if int(st["n_harvested"].item()) >= N:
+                        break
+                    if launched > most:
+                        raise RuntimeError(f"generate_stream: {int(st['n_harvested'].item())} of {N} items after "
+                                           f"{launched} steps")
+        finally:
+            self.streaming = False
+        out_len, start = st["out_len"].cpu().long(), st["start_step"].cpu().long()
+        record = dict(steps=int((start + lens + out_len - 1).max()) if N else 0, launched=launched,
+                      row_of=st["row_of"].cpu().long(), start_step=start, out_len=out_len,
+                      harvested=int(st["n_harvested"].item()))
+        ys = st["out_ys"][:, :W]
+        is_eos = generated_tokens(ys, lens) == self.eos_id
+        if N and bool(is_eos.any(dim=1).all()):                    # generate()'s cut: the longest item's <eos>
+            first = is_eos.int().argmax(dim=1)
+            ys = ys[:, :t0 + int(first.max().item()) + 1]
+        return ys.clone(), record
+
     def _run_step(self, mode, use_graphs):
         if not use_graphs:
             self._advance(mode)
             return
         key = (mode, "mixed") if self.ragged else mode    # a mixed-prefix step passes row_off: a graph of its own
+        if self.streaming:
+            key = (mode, STREAM)                          # step + selection by item + refill
         g = self.graphs.get(key)
         if g is False:                                  # no usable graph for these buffers (capture failed, or replay is
             self._advance(mode)                         # the slower launch mode on this box): same kernels, eagerly
@@ -643,8 +953,20 @@ class KVDecoder:
 
     def _state_tensors(self):
         """Everything a step + selection writes besides the caches' next row (the beam state included)."""
-        return (self.pos, self.ys, self.valid, self.done, self.bscores, self.bfin, self.blen, self.bparent,
+        base = (self.pos, self.ys, self.valid, self.done, self.bscores, self.bfin, self.blen, self.bparent,
                 self.kv_src, self.bdone)
+        if not self.streaming:
+            return base
+        st = self.stream                                  # (the refill is held while a state is kept: _hold_refill)
+        return base + (self.row_off, st["item"], st["next_item"], st["n_harvested"])
+
+    def _hold_refill(self, hold):
+        """Continuous batching: the capture warm-up and the replay guard execute real steps and then restore
+        _state_tensors().  A refill in one of those steps would overwrite a row's latent rows, condition rows and cache
+        slots, which no restore covers -- so they run with the device `enable` word at 0: a row that finishes is held
+        (it decodes on, as a finished row of the plain path does) and the restore puts it back."""
+        if self.streaming:
+            self.stream["enable"].fill_(0 if hold else 1)
 
     def _capture(self, mode, key):
         """Capture step + select into one graph; returns it, or None after running the step eagerly (capture failed, or
@@ -652,6 +974,7 @@ class KVDecoder:
         # Warm-up run on a side stream (lazy LDS opt-ins, allocator), then capture.  The warm-up really executes a
         # step (it advances the device position and writes a token), so the state it touches is restored before
         # the capture; a capture itself executes nothing.
+        self._hold_refill(True)
         keep = self._state()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -676,10 +999,13 @@ class KVDecoder:
             self._restore(keep)
             self.graphs[key] = False
             self.graph_replay = False
+            self._hold_refill(False)
             self._advance(mode)
             return None
         self.graphs[key] = g
-        if REPLAY_GUARD and not self._replay_is_fast(mode, g, keep):
+        fast = not REPLAY_GUARD or self._replay_is_fast(mode, g, keep)
+        self._hold_refill(False)
+        if not fast:
             self.graphs[key] = False
             self.graph_replay = False
             self._advance(mode)
@@ -691,7 +1017,10 @@ class KVDecoder:
         each.  Replay is the faster way to issue the ~70 launches of a step everywhere it behaves; on boxes where it is
         clearly the slower one (round 2: 3-13x) the decoder keeps launching eagerly, says so once, and leaves the
         numbers and the graph's census in `self.replay_probe` for the caller (bench.py prints them)."""
-        room = self.T - self.off - (int(keep[0].item()) + 1) - 1         # steps the caches still have room for
+        ahead = int(keep[0].item())                                      # position of the row that is furthest along
+        if self.streaming:
+            ahead -= int(self.row_off.min().item())
+        room = self.T - self.off - (ahead + 1) - 1                       # steps the caches still have room for
         k = min(4, room)
         if k < 1:
             return True

@@ -928,18 +928,82 @@ def sample_filter_settings(top_k, top_p, temperature, vocab):
 
 
 def select_token(logits2d, ys, pos, valid_u8, done_u8, mode, pad_id, eos_id, seed=0, probs_out=None, pos_dev=None,
-                 valid_off=0, seed_dev=None, row_off=None, filt_dev=None):
+                 valid_off=0, seed_dev=None, row_off=None, filt_dev=None, item=None, prefix_len=None, item_base=0):
     """row_off (int32 [n], optional, with pos_dev only): row r writes at *pos_dev - row_off[r] + 1.
     filt_dev (int32 [4] on the device, optional, mode 1 only): top-k / nucleus / temperature settings
-    (sample_filter_settings), read by the kernel; V <= SAMPLE_FILTER_MAX_VOCAB."""
+    (sample_filter_settings), read by the kernel; V <= SAMPLE_FILTER_MAX_VOCAB.
+    item (int32 [n]) + prefix_len (int32 [items]), with row_off: continuous batching -- row r decodes pool item item[r]
+    (< 0: parked, nothing written), keeps the prefix tokens the refill laid out, and draws with the key
+    (item_base + item, pos)."""
     n, V = logits2d.shape
     _check_row_off(row_off, n)
+    if (item is None) != (prefix_len is None):
+        raise ValueError("item and prefix_len go together")
+    if item is not None:
+        _check_row_off(item, n)
+        if row_off is None or prefix_len.dtype != torch.int32 or not prefix_len.is_contiguous():
+            raise ValueError("streamed rows need row_off and a contiguous int32 prefix_len")
     if filt_dev is not None and (filt_dev.dtype != torch.int32 or filt_dev.numel() != 4 or not filt_dev.is_contiguous()):
         raise ValueError("filt_dev must be a contiguous int32 tensor of 4 entries (sample_filter_settings)")
     check(_L().gct_select_token(_p(logits2d), V, _p(ys), ys.stride(0), pos, _p(valid_u8),
                                 valid_u8.stride(0) if valid_u8 is not None else 0, _p(done_u8),
                                 _p(probs_out), n, mode, pad_id, eos_id, seed, _p(pos_dev), valid_off, _p(seed_dev),
-                                _p(row_off), _p(filt_dev), _st()), "gct_select_token")
+                                _p(row_off), _p(filt_dev), _p(item), _p(prefix_len), item_base, _st()), "gct_select_token")
+
+
+STREAM_MAX_ROWS, STREAM_MAX_LAYERS = 8192, 16   # GCT_STREAM_MAX_ROWS / GCT_STREAM_MAX_LAYERS (include/gctplus_hip.h)
+
+
+def stream_state_fields(header_text=None):
+    """[(field, count)] of GctStreamState in declaration order, parsed from include/gctplus_hip.h (every field is 8
+    bytes wide: a pointer or an int64_t; count > 1: an array)."""
+    import re
+    text = _lib._read_header("gctplus_hip.h") if header_text is None else header_text
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    body = re.search(r"typedef\s+struct\s+GctStreamState\s*\{([^{}]*)\}\s*GctStreamState\s*;", text)
+    if not body:
+        raise _lib.GctError("include/gctplus_hip.h does not define GctStreamState")
+    consts = {k: int(v) for k, v in re.findall(r"^\s*#\s*define\s+(\w+)\s+(\d+)\s*$", text, flags=re.M)}
+    out = []
+    for decl in body.group(1).split(";"):
+        if not decl.strip():
+            continue
+        for part in decl.split(","):
+            m = re.search(r"(\w+)\s*(?:\[\s*(\w+)\s*\])?\s*$", part.strip())
+            dim = m.group(2)
+            out.append((m.group(1), 1 if dim is None else (int(dim) if dim.isdigit() else consts[dim])))
+    return out
+
+
+class StreamState:
+    """Host image of a GctStreamState: `set(name=tensor | int | [tensors])` fills fields, `refill()` enqueues
+    gct_stream_refill on the current stream.  Holds the tensors it points to."""
+
+    def __init__(self):
+        import ctypes
+        self.fields = stream_state_fields()
+        self.slot, n = {}, 0
+        for name, count in self.fields:
+            self.slot[name] = (n, count)
+            n += count
+        self.words = (ctypes.c_int64 * n)()
+        self.keep = {}
+
+    def set(self, **kw):
+        for name, v in kw.items():
+            at, count = self.slot[name]
+            vals = list(v) if isinstance(v, (list, tuple)) else [v]
+            if len(vals) > count:
+                raise ValueError(f"GctStreamState.{name} holds {count} entries, got {len(vals)}")
+            self.keep[name] = vals
+            for i in range(count):
+                x = vals[i] if i < len(vals) else None
+                self.words[at + i] = 0 if x is None else (x.data_ptr() if isinstance(x, torch.Tensor) else int(x))
+        return self
+
+    def refill(self):
+        import ctypes
+        check(_L().gct_stream_refill(ctypes.addressof(self.words), _st()), "gct_stream_refill")
 
 
 def decode_embed(ys, pos, pe_off, table, pe, out, scale, row_off=None):

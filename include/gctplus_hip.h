@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 19
+#define GCT_ABI_VERSION 20
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -404,7 +404,12 @@ int gct_decode_advance(int32_t* pos, void* stream);
  *     otherwise its weight is 0; top_p >= 1: no-op;
  *   the draw picks c with probability w_c / sum w (the same Philox key); probs_out receives w / sum w.  A row the filter
  *   leaves unchanged draws exactly as without filt.  The host validates 1 <= k <= V, 0 < top_p <= 1, 0 < T < inf.
- * V <= GCT_SAMPLE_FILTER_MAX_VOCAB with filt; otherwise (or with mode 0) GCT_ERR_ARG.  NULL: the kernels of ABI 17. */
+ * V <= GCT_SAMPLE_FILTER_MAX_VOCAB with filt; otherwise (or with mode 0) GCT_ERR_ARG.  NULL: the kernels of ABI 17.
+ * item / prefix_len (both or neither; with row_off, valid and done): continuous batching (gct_stream_refill) -- row r
+ * decodes pool item item[r] (int32 [n]; < 0: parked, the row writes nothing).  While pos < prefix_len[item] the slot
+ * already holds the prefix token the refill laid there and is left alone (done untouched); the multinomial draw is
+ * keyed by (item_base + item, pos) instead of (r, pos), in every mode (item_base >= 0: the pool is a slice of a larger
+ * one).  NULL: the kernels of ABI 19. */
 typedef struct GctSampleFilter {
   int32_t k;        /* top-k (>= V: off) */
   float top_p;      /* nucleus mass (>= 1: off) */
@@ -415,7 +420,62 @@ typedef struct GctSampleFilter {
 int gct_select_token(const float* logits, int V, int64_t* ys, int64_t ld_ys, int pos, uint8_t* valid,
                      int64_t valid_sb, uint8_t* done, float* probs_out, int n, int mode,
                      int64_t pad_id, int64_t eos_id, uint64_t seed, const int32_t* pos_dev, int valid_off,
-                     const uint64_t* seed_dev, const int32_t* row_off, const GctSampleFilter* filt, void* stream);
+                     const uint64_t* seed_dev, const int32_t* row_off, const GctSampleFilter* filt,
+                     const int32_t* item, const int32_t* prefix_len, int item_base, void* stream);
+
+/* Continuous batching (gct_plus_amd/decode.py stream_schedule_reference states the schedule).  R decode rows work
+ * through a pool of N items behind the shared counter *pos: the step unit is gct_decode_advance, the RAGGED step
+ * kernels, gct_select_token(item, prefix_len) and then gct_stream_refill, which, when *enable != 0:
+ *   1. finds the rows that FINISHED in the step just run: done[r] set, or the item has produced limit[item] tokens
+ *      (generated so far = *pos - row_off[r] + 2 - prefix_len[item]); copies ys[r][0, width) to out_ys[item] and the
+ *      generated length to out_len[item]; *n_harvested += their number;
+ *   2. gives the finished rows and the empty ones (item[r] < 0) the items *next_item, *next_item + 1, ... in ASCENDING
+ *      ROW ORDER; a row that finds the pool empty gets item -1 (parked).  row_of[item] = r, start_step[item] = *pos + 1;
+ *   3. lays out each such row: row_off[r] = *pos + 1 (the next step consumes the row's token 0); with a new item
+ *      z3 / src_valid / src_klen / ckv rows from the pools, ys[r][0, T) = the item's prefix then pad, valid[r] = the
+ *      prefix's non-pad flags, done[r] = 0.  A parked row gets the offset only, at every call: it stays at position 0.
+ * Every item, the first R included, enters through this call (set item[] = -1, *pos = -1 and call it once before the
+ * first step).  With *enable == 0 nothing is read or written beyond the word itself (capture warm-ups and timing probes
+ * run real steps whose state the host restores).  All fields are 8 bytes wide (pointers and int64_t), in this order. */
+#define GCT_STREAM_MAX_ROWS 8192
+#define GCT_STREAM_MAX_LAYERS 16
+typedef struct GctStreamState {
+  /* the decoder's rows */
+  int64_t* ys;           /* [rows][ld_ys] */
+  uint8_t* valid;        /* [rows][valid_sb], token j at valid_off + j */
+  uint8_t* done;         /* [rows] */
+  int32_t* row_off;      /* [rows] */
+  const int32_t* pos;    /* the shared counter */
+  float* z3;             /* [rows][z_row] latent rows */
+  uint8_t* src_valid;    /* [rows][Lk] */
+  int32_t* src_klen;     /* [rows] */
+  float* ckv[GCT_STREAM_MAX_LAYERS];            /* per layer [rows][ckv_row] condition keys | values (ckv_row > 0) */
+  int32_t* item;         /* [rows] pool item of the row, -1: none */
+  int32_t* harvest;      /* [rows] scratch: item harvested in this call, -1: none */
+  uint8_t* fresh;        /* [rows] scratch: the row is laid out again in this call */
+  /* the pool */
+  const float* z_pool;   /* [items][z_row] */
+  const uint8_t* valid_pool;                    /* [items][Lk] */
+  const int32_t* klen_pool;                     /* [items] */
+  const float* ckv_pool[GCT_STREAM_MAX_LAYERS]; /* per layer [items][ckv_row] */
+  const int64_t* prefix_pool;                   /* [items][t0_max], right-padded */
+  const int32_t* prefix_len;                    /* [items], 1 .. t0_max */
+  const int32_t* limit;                         /* [items] tokens to generate at most, >= 1, prefix_len + limit <= width */
+  /* results */
+  int64_t* out_ys;       /* [items][width] */
+  int32_t* out_len;      /* [items] generated tokens, the <eos> included */
+  int32_t* row_of;       /* [items] */
+  int32_t* start_step;   /* [items] */
+  int32_t* next_item;    /* first item not handed out yet */
+  int32_t* n_harvested;  /* items copied out so far */
+  const int32_t* enable;
+  /* geometry */
+  int64_t rows, items, ld_ys, valid_sb, valid_off, T, width, t0_max, z_row, Lk, ckv_row, layers, pad_id;
+} GctStreamState;
+/* state: HOST memory, read during the call (the kernels get a copy).  1 <= rows <= GCT_STREAM_MAX_ROWS,
+ * width <= T <= ld_ys, valid_off + T <= valid_sb, z_row % 4 == 0, ckv_row % 4 == 0, layers <= GCT_STREAM_MAX_LAYERS;
+ * otherwise GCT_ERR_ARG.  Two launches: a one-workgroup scan over the rows, then one workgroup per row for the copies. */
+int gct_stream_refill(const GctStreamState* state, void* stream);
 
 /* Beam search (gct_plus_amd/decode.py beam_step_reference states the rules).  Sample s owns the k rows
  * s*k .. s*k+k-1 of an n*k-row decode.  The self-attention caches, ys and valid are PHYSICAL slots, each written once:

@@ -9,7 +9,15 @@ reference's per-scaffold sampling loop), one batch per prefix length (host-side 
 (KVDecoder.generate(prefix_lens=)); plus a uniform-prefix batch of the same n at the mean prefix length for scale.  The
 mixed batch's ids are checked against the per-length runs first.
 --top-k K / --top-p P / --temperature T: filtered multinomial sampling against plain multinomial on the same rows (ms per
-token step and SMILES/s, eager and graph replay, all 79 steps)."""
+token step and SMILES/s, eager and graph replay, all 79 steps).
+--stream-rows R --pool N: continuous batching (KVDecoder.generate_stream) of a pool of N items through R rows against
+the plain path on the same items: chunks of R items in pool order through start + generate.  Lengths are imposed
+(eos_id = -1, caps clip(round(N(35, 8)), 15, 78) + 1 from numpy default_rng(0)), so both legs do known work: the stream
+gets them as max_new_tokens, a plain chunk runs max_strlen = its longest cap + 1 (the best its early stop could do).
+The stream's step count must equal stream_schedule_reference's (exit status 1 otherwise).  The two legs alternate three
+times (start / start_stream inside the timing); printed: steps, ms per step of both and of the plain mixed-prefix
+(ragged) step at R rows, SMILES/s, their ratio next to the ratio of the step counts, the replay guard's verdicts.
+--prefix T gives every item a T-token prefix (the scaffold models' <sos> scaffold <sep>)."""
 import argparse
 import os
 import sys
@@ -34,6 +42,10 @@ ap.add_argument("--per-scaffold", type=int, default=64, help="rows per scaffold 
 ap.add_argument("--top-k", type=int, default=None, help="filtered multinomial: top-k (see the docstring)")
 ap.add_argument("--top-p", type=float, default=None, help="filtered multinomial: nucleus mass")
 ap.add_argument("--temperature", type=float, default=1.0, help="filtered multinomial: temperature")
+ap.add_argument("--stream-rows", type=int, default=0, help="continuous batching with R decode rows (see the docstring)")
+ap.add_argument("--pool", type=int, default=8192, help="items of the pool with --stream-rows")
+ap.add_argument("--prefix", type=int, default=1, help="prefix tokens per item with --stream-rows")
+ap.add_argument("--eager", action="store_true", help="--stream-rows: eager launches instead of graph replay")
 a = ap.parse_args()
 mtype = a.model_type
 vs, vt = synthetic.vocab_sizes(mtype)
@@ -41,7 +53,7 @@ nc = synthetic.n_conds(mtype)
 torch.manual_seed(1)
 model = model_dict[mtype](vs, vt, N=6, d_model=512, dff=2048, h=8, latent_dim=128, dropout=0.1, nconds=nc,
                           use_cond2lat=True).cuda().eval()
-n, Le = a.n, (80 if a.ragged else 40) + nc
+n, Le = (a.pool if a.stream_rows else a.n), (80 if a.ragged else 40) + nc
 z = torch.randn(n, Le, 128, device="cuda")
 dconds = torch.randn(n, nc, device="cuda") if nc else None
 src_mask = torch.ones(n, 1, Le, dtype=torch.bool, device="cuda")
@@ -59,6 +71,71 @@ def timed(run):
     torch.cuda.synchronize()
     return out, time.perf_counter() - t0
 
+
+def timed_once(run):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = run()
+    torch.cuda.synchronize()
+    return out, time.perf_counter() - t0
+
+
+if a.stream_rows:
+    import numpy as np
+    from gct_plus_amd.decode import stream_schedule_reference
+    R, N, t0, graphs = a.stream_rows, n, a.prefix, not a.eager
+    caps = torch.from_numpy(np.clip(np.rint(np.random.default_rng(0).normal(35, 8, N)), 15, 78).astype(np.int64) + 1)
+    if t0 > 1:
+        g = torch.Generator().manual_seed(5)
+        pre = torch.cat([torch.tensor([synthetic.SOS_ID]), torch.randint(5, 30, (t0 - 2,), generator=g), torch.tensor([4])])
+        ys0 = pre.view(1, -1).repeat(N, 1).cuda()
+    total = t0 + 79
+    _, _, want = stream_schedule_reference(t0 + caps - 1, R)
+    chunks = [(lo, min(lo + R, N)) for lo in range(0, N, R)]
+    plain_steps = sum(int(caps[lo:hi].max()) for lo, hi in chunks)          # a chunk's prefill counted as one step
+    ks = KVDecoder(model, synthetic.PAD_ID, synthetic.SOS_ID, eos_id=-1)
+    kp = KVDecoder(model, synthetic.PAD_ID, synthetic.SOS_ID, eos_id=-1)
+    kr = KVDecoder(model, synthetic.PAD_ID, synthetic.SOS_ID, eos_id=-1)
+    cut = lambda x, lo, hi: None if x is None else x[lo:hi]                  # noqa: E731
+
+    def stream():
+        ks.start_stream(z, src_mask, dconds, rows=R, max_total_len=total)
+        return ks.generate_stream(ys0, 80, max_new_tokens=caps, use_graphs=graphs)[1]
+
+    def plain():
+        for lo, hi in chunks:
+            kp.start(z[lo:hi], src_mask[lo:hi], cut(dconds, lo, hi), max_total_len=total)
+            kp.generate(ys0[lo:hi], int(caps[lo:hi].max()) + 1, use_graphs=graphs, check_every=0)
+
+    def ragged_step():                                                       # the plain mixed-prefix step at R rows
+        m = min(R, N)
+        y2 = torch.cat([ys0[:m], ys0[:m, -1:]], dim=1)
+        kr.start(z[:m], src_mask[:m], cut(dconds, 0, m), max_total_len=total + 1)
+        kr.generate(y2, 80, use_graphs=graphs, check_every=0, prefix_lens=t0 + torch.arange(m) % 2)
+
+    print(f"pool {N} items, {R} rows, prefix {t0}, caps {int(caps.min())}..{int(caps.max())} (mean "
+          f"{float(caps.float().mean()):.1f}); steps: stream {want} (schedule reference), plain {plain_steps} in "
+          f"{len(chunks)} chunks -> predicted ratio {plain_steps / want:.3f}", flush=True)
+    ts, tp, tr, ok = [], [], [], True
+    stream(); plain(); ragged_step()                                         # warm-up / capture          # noqa: E702
+    for rep in range(3):
+        rec, dt = timed_once(stream)
+        ts.append(dt)
+        ok &= rec["steps"] == want and rec["harvested"] == N and bool((rec["out_len"] == caps).all())
+        _, dt = timed_once(plain)
+        tp.append(dt)
+        _, dt = timed_once(ragged_step)
+        tr.append(dt)
+        print(f"rep {rep}: stream {ts[-1] * 1e3:8.1f} ms ({rec['steps']} steps, {rec['launched']} launched, "
+              f"{ts[-1] / rec['launched'] * 1e3:.3f} ms/step) -> {N / ts[-1]:7.0f} SMILES/s | plain {tp[-1] * 1e3:8.1f} ms "
+              f"({tp[-1] / plain_steps * 1e3:.3f} ms/step) -> {N / tp[-1]:7.0f} SMILES/s | ragged step at {min(R, N)} rows "
+              f"{tr[-1] / 79 * 1e3:.3f} ms", flush=True)
+    bs, bp = min(ts), min(tp)
+    print(f"stream / plain SMILES/s {bp / bs:.3f} (step counts predict {plain_steps / want:.3f}); stream step / ragged step "
+          f"{(bs / rec['launched']) / (min(tr) / 79):.3f}; plain spread {(max(tp) - min(tp)) / min(tp):.3f}; replay: stream "
+          f"{'graph' if graphs and ks.graph_replay else 'eager'}, plain {'graph' if graphs and kp.graph_replay else 'eager'}")
+    print("step count equals the schedule reference:", ok)
+    sys.exit(0 if ok else 1)
 
 if a.scaffolds:
     from gct_plus_amd.decode import generated_tokens
