@@ -20,6 +20,8 @@
 #include <limits.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -617,10 +619,95 @@ __device__ __forceinline__ void wave_epilogue(const GemmArgs& g, const f32x16 (&
   wave_epilogue_tail<SIDE>(g, stg, lane, mw, nw, z);
 }
 
-// second part of the per-wave epilogue: the 64x64 block is in `stg` (row-major, this wave's own LDS writes)
+// What the four patches of a lane share (its 4-column chunk): destination, segment select and bias.  Depends only on
+// the wave's block origin and the lane, so a kernel may resolve it before its main loop.
+struct EpiLane {
+  bool live;        // col0 < N
+  int64_t col0, cloc;
+  float* cbase;
+  float4 bias;
+};
+__device__ __forceinline__ EpiLane epi_lane(const GemmArgs& g, int lane, int64_t nw, unsigned z) {
+  EpiLane el;
+  el.col0 = nw + (lane & 15) * 4;
+  el.live = el.col0 < g.N;
+  el.cloc = 0;
+  el.cbase = g.c0;
+  el.bias = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (el.live) {
+    if (g.epi == EPI_SLAB) {
+      el.cbase = g.c0 + (int64_t)z * g.slab_stride;
+      el.cloc = el.col0;
+    } else {
+      const bool g1 = el.col0 >= g.c_nper, g2 = el.col0 >= 2 * g.c_nper;
+      el.cloc = el.col0 - (g2 ? 2 * g.c_nper : (g1 ? g.c_nper : 0));
+      el.cbase = g.c0 + (g2 ? g.c_d2 : (g1 ? g.c_d1 : 0));
+      if (g.epi < EPI_D0 && g.bias0)
+        el.bias = *reinterpret_cast<const float4*>(g.bias0 + (g2 ? g.bias_d2 : (g1 ? g.bias_d1 : 0)) + el.cloc);
+    }
+  }
+  return el;
+}
+
+// Branch-free request of the extra epilogue operands (needs_extra()) of a lane's four patches, for issue between the
+// MFMAs of a kernel's last K-tile: p[it] is row 0 of patch it's operand rows, `have` bit it says that all four rows
+// exist (inside M, and -- through a quad map -- inside pre_rows and not padding).  The other patches (the ragged last
+// rows of a matrix, padding quads, lanes past N) point at rows 0..3 of the operand, which always exist (epi_ahead_ok
+// asks for that); what is read there is dropped and wave_epilogue_finish loads those patches the ordinary way.
+struct EpiAhead {
+  const float* p[4];
+  unsigned have;
+};
 template <int SIDE>
-__device__ __forceinline__ void wave_epilogue_tail(const GemmArgs& g, float* stg, int lane, int64_t mw,
-                                                   int64_t nw, unsigned z) {
+__device__ __forceinline__ bool epi_ahead_ok(const GemmArgs& g) {
+  const FastEpiT<SIDE> ep{g};
+  return ep.needs_extra() && g.M >= 4 && !(ep.reads_pre() && g.pre_rows > 0 && g.pre_rows < 4);
+}
+// quad-map entries of the lane's four patches (pre_rows > 0: pre_in is read through the map), fetched before the main
+// loop so that the plan below does not wait for them; -1: padding, or no such patch
+template <int SIDE>
+__device__ __forceinline__ void epi_ahead_quads(const GemmArgs& g, int lane, int64_t mw, int64_t nw, int (&qv)[4]) {
+  const FastEpiT<SIDE> ep{g};
+  const bool mapped = ep.reads_pre() && g.pre_rows > 0;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int64_t row0 = mw + (it * 4 + (lane >> 4)) * 4;
+    qv[it] = (int)(row0 >> 2);
+    if (mapped && g.quad_map) qv[it] = (nw + (lane & 15) * 4 < g.N && row0 + 3 < g.M) ? g.quad_map[(row0 + g.row_base) >> 2] : -1;
+  }
+}
+template <int SIDE>
+__device__ __forceinline__ EpiAhead epi_ahead_plan(const GemmArgs& g, const EpiLane& el, int lane, int64_t mw,
+                                                   const int (&qv)[4]) {
+  const FastEpiT<SIDE> ep{g};
+  const float* eb = ep.extra_base(el.cbase) + el.cloc;
+  const bool mapped = ep.reads_pre() && g.pre_rows > 0;
+  const int64_t elim = mapped ? g.pre_rows : g.M;
+  EpiAhead ah;
+  ah.have = 0;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int64_t row0 = mw + (it * 4 + (lane >> 4)) * 4;
+    const int64_t er0 = mapped ? (int64_t)qv[it] * 4 : row0;        // as pre_row0()
+    const bool ok = el.live && row0 + 3 < g.M && er0 >= 0 && er0 + 3 < elim;
+    ah.p[it] = eb + (ok ? er0 * g.ldc : 0);
+    ah.have |= ok ? 1u << it : 0u;
+  }
+  return ah;
+}
+template <int IT0, int IT1>   // patches IT0 .. IT1 - 1
+__device__ __forceinline__ void epi_ahead_issue(const GemmArgs& g, const EpiAhead& ah, float4 (&ex)[4][4]) {
+#pragma unroll
+  for (int it = IT0; it < IT1; ++it)
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) ex[it][rr] = *reinterpret_cast<const float4*>(ah.p[it] + rr * g.ldc);
+}
+
+// second part of the per-wave epilogue: the 64x64 block is in `stg` (row-major, this wave's own LDS writes); ex[it]
+// already holds the extra operands of the patches whose bit is set in `have`
+template <int SIDE>
+__device__ __forceinline__ void wave_epilogue_finish(const GemmArgs& g, float* stg, int lane, int64_t mw,
+                                                     const EpiLane& el, float4 (&ex)[4][4], unsigned have) {
   __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's own LDS writes are visible to it
   __builtin_amdgcn_wave_barrier();
   const FastEpiT<SIDE> ep{g};
@@ -628,27 +715,11 @@ __device__ __forceinline__ void wave_epilogue_tail(const GemmArgs& g, float* stg
   // segment select are resolved once; the residual / accumulate / pre-activation rows of
   // all 4 patches are requested up front so their latency overlaps
   const int c4 = lane & 15;
-  const int64_t col0 = nw + c4 * 4;
-  if (col0 < g.N) {
-    float* cbase;
-    int64_t cloc;
-    float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (g.epi == EPI_SLAB) {
-      cbase = g.c0 + (int64_t)z * g.slab_stride;
-      cloc = col0;
-    } else {
-      const bool g1 = col0 >= g.c_nper, g2 = col0 >= 2 * g.c_nper;
-      cloc = col0 - (g2 ? 2 * g.c_nper : (g1 ? g.c_nper : 0));
-      cbase = g.c0 + (g2 ? g.c_d2 : (g1 ? g.c_d1 : 0));
-      if (g.epi < EPI_D0 && g.bias0)
-        bias = *reinterpret_cast<const float4*>(g.bias0 + (g2 ? g.bias_d2 : (g1 ? g.bias_d1 : 0)) + cloc);
-    }
-    float4 ex[4][4];
-    const bool extra = ep.needs_extra();
-    if (extra) {
+  if (el.live) {
+    if (ep.needs_extra()) {
 #pragma unroll
       for (int it = 0; it < 4; ++it)
-        ep.prefetch(ex[it], mw + (it * 4 + (lane >> 4)) * 4, cbase, cloc);
+        if (!((have >> it) & 1u)) ep.prefetch(ex[it], mw + (it * 4 + (lane >> 4)) * 4, el.cbase, el.cloc);
     }
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
@@ -659,9 +730,16 @@ __device__ __forceinline__ void wave_epilogue_tail(const GemmArgs& g, float* stg
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr)
         v[rr] = *reinterpret_cast<const float4*>(stg + (rg * 4 + rr) * 64 + c4 * 4);
-      ep.apply(v, ex[it], row0, col0, cbase, cloc, bias);
+      ep.apply(v, ex[it], row0, el.col0, el.cbase, el.cloc, el.bias);
     }
   }
+}
+// ... for the kernels that request nothing ahead
+template <int SIDE>
+__device__ __forceinline__ void wave_epilogue_tail(const GemmArgs& g, float* stg, int lane, int64_t mw,
+                                                   int64_t nw, unsigned z) {
+  float4 ex[4][4];
+  wave_epilogue_finish<SIDE>(g, stg, lane, mw, epi_lane(g, lane, nw, z), ex, 0u);
 }
 
 template <bool A_KC, bool B_KC>

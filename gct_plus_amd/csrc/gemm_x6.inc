@@ -414,13 +414,33 @@ gemm_x6_kernel(const GemmArgs g) {
   // split VALU work per K-tile, and its groups are scaled to match (not retuned)
   constexpr int NG = 2 * NP;                              // MFMA / LDS-read groups per fragment-set load
   constexpr int MPW = NP == 3 ? 2 : 1;                    // MFMAs per LDS store (BAL, first half)
+  // ... inside the steady state every index is below nkt: no clamp
+  auto ktile_in = [&](int64_t t) -> int64_t { return kbeg + t * XBK; };
   int64_t k2n = nkt > 0 ? ktile(2) : 0;   // K index of tile t+2, looked up one iteration ahead: the scalar load
                                           // of a tile-list entry never sits in front of the loads that use it
-  for (int64_t kt = 0; kt < nkt; ++kt) {
+  // One K-tile.  TAIL = 0 is the steady state.  The balanced schedule peels its last three K-tiles, so that nothing is
+  // loaded, split, written to LDS or read from it for a tile that does not exist: tile t of nkt stores and reads tile
+  // t+1 (NEXT1), loads B of and splits tile t+2 (NEXT2) and loads A of tile t+3 (NEXT3):
+  //   TAIL 3 (t = nkt-3): no A load            TAIL 2 (t = nkt-2): LDS stores and fragment reads of tile nkt-1 only
+  //   TAIL 1 (t = nkt-1): the MFMAs and the reads of A23 / B23; TAIL 4 is TAIL 1 with the epilogue's own operand reads
+  //   (epi_ahead_issue) in the issue slots that the B loads leave free: one patch in the first half, one in the third
+  //   quarter (B01 fragments dead), two in the last (A01 dead too): any earlier and the 64 operand registers do not fit
+  //   in 256 VGPRs next to the accumulators and the fragments
+  // The issue-order hints are those of the steady state with the groups of the missing work left out.
+  const int64_t mw = m0 + wm, nw = n0 + wn;
+  constexpr int SIDE = MODE == X6_FWD ? 1 : (MODE == X6_DGRAD ? 2 : 3);
+  EpiLane el;
+  EpiAhead ah;
+  float4 ex[4][4];
+  int qv[4];
+  if (BAL) epi_ahead_quads<SIDE>(g, lane, mw, nw, qv);
+  auto ktile_iter = [&](auto tail_c, const int64_t kt) __attribute__((always_inline)) {
+    constexpr int TAIL = decltype(tail_c)::value;
+    constexpr bool NEXT1 = TAIL != 1 && TAIL != 4, NEXT2 = TAIL == 0 || TAIL == 3, NEXT3 = TAIL == 0, AHEAD = TAIL == 4;
     unsigned char* st = xlds + (kt & 1) * X_STAGE;
     unsigned char* stn = xlds + ((kt + 1) & 1) * X_STAGE;
     const int64_t k2 = k2n;
-    k2n = ktile(kt + 3);
+    if (TAIL == 0) k2n = BAL ? ktile_in(kt + 3) : ktile(kt + 3);
     __builtin_amdgcn_sched_barrier(0);
     // ---- first half: phases (A01,B01) (A23,B01) | reads of A23, B23; split + LDS stores of tile t+1
     X6_LD_A(fA23, st, 2)
@@ -430,8 +450,9 @@ gemm_x6_kernel(const GemmArgs g) {
       X6_BSUM(bw)
     }
     if (BAL) {
-      X6_LSTORE_PK(stn);            // tile t+1: A pieces split last iteration, B pieces as loaded
-      X6_GLOAD_B(k2);
+      if (NEXT1) { X6_LSTORE_PK(stn); }   // tile t+1: A pieces split last iteration, B pieces as loaded
+      if (NEXT2) { X6_GLOAD_B(k2); }
+      if (AHEAD) epi_ahead_issue<0, 1>(g, ah, ex);
     } else {
       X6_LSTORE(stn);
     }
@@ -444,12 +465,12 @@ gemm_x6_kernel(const GemmArgs g) {
     }
     if (BAL) {
 #pragma unroll
-      for (int q = 0; q < NWR; ++q) {
+      for (int q = 0; q < (NEXT1 ? NWR : 0); ++q) {
         __builtin_amdgcn_sched_group_barrier(0x008, MPW, 0);
         __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
       }
 #pragma unroll
-      for (int q = 0; q < 2 * NP; ++q) {
+      for (int q = 0; q < (NEXT2 ? 2 * NP : (AHEAD ? 4 : 0)); ++q) {
         __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
@@ -470,27 +491,35 @@ gemm_x6_kernel(const GemmArgs g) {
     __syncthreads();
     STAMP(2);
     // ---- second half: phases (A01,B23) (A23,B23) | reads of B01, A01 of tile t+1; global loads of tile t+2
-    X6_LD_B(fB01, stn, 0)
+    if (NEXT1) { X6_LD_B(fB01, stn, 0) }
     if (BAL) {
-      X6_SPLIT_A()                  // pa holds tile t+2 (loaded one iteration ago)
-      X6_GLOAD_A(k2n);
+      if (NEXT2) { X6_SPLIT_A() }   // pa holds tile t+2 (loaded one iteration ago)
+      if (NEXT3) { X6_GLOAD_A(k2n); }
+      if (AHEAD) epi_ahead_issue<1, 2>(g, ah, ex);
     } else {
       X6_GLOAD(k2);
     }
     X6_MM(fA01, fB23, 0, 2)
 #pragma unroll
-    for (int q = 0; q < NG; ++q) {
+    for (int q = 0; q < (NEXT1 ? NG : 0); ++q) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       __builtin_amdgcn_sched_group_barrier(0x100, RB / NG, 0);
     }
     if (BAL) {
 #pragma unroll
-      for (int q = 0; q < (NP == 3 ? 14 : 6); ++q) {
+      for (int q = 0; q < (NEXT2 ? (NP == 3 ? 14 : 6) : 0); ++q) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x002, NP == 3 ? 3 : 4, 0);
       }
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-      __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+      if (NEXT3) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+      }
+#pragma unroll
+      for (int q = 0; q < (AHEAD ? 4 : 0); ++q) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+      }
     } else {
 #pragma unroll
       for (int q = 0; q < (NP == 3 ? 8 : 4); ++q) {
@@ -499,17 +528,42 @@ gemm_x6_kernel(const GemmArgs g) {
       }
     }
     __builtin_amdgcn_sched_barrier(0);
-    X6_LD_A(fA01, stn, 0)
+    if (NEXT1) { X6_LD_A(fA01, stn, 0) }
+    if (AHEAD) epi_ahead_issue<2, 4>(g, ah, ex);
     X6_MM(fA23, fB23, 2, 2)
 #pragma unroll
-    for (int q = 0; q < NG; ++q) {
+    for (int q = 0; q < (AHEAD ? 8 : 0); ++q) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+    }
+#pragma unroll
+    for (int q = 0; q < (NEXT1 ? NG : 0); ++q) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       __builtin_amdgcn_sched_group_barrier(0x100, RA / NG, 0);
     }
     __builtin_amdgcn_sched_barrier(0);
     STAMP(3);
+    };
+  if (BAL) {
+    int64_t kt = 0;
+    for (; kt < nkt - 3; ++kt) ktile_iter(std::integral_constant<int, 0>{}, kt);
+    // the epilogue's lane mapping depends on the block origin and the lane alone: resolved here, its loads (bias,
+    // quad map) are in flight under the last K-tiles
+    el = epi_lane(g, lane, nw, z);
+    const bool ahead = nkt > 0 && epi_ahead_ok<SIDE>(g);
+    ah.have = 0;
+    if (ahead) ah = epi_ahead_plan<SIDE>(g, el, lane, mw, qv);
+    if (nkt >= 3) ktile_iter(std::integral_constant<int, 3>{}, nkt - 3);
+    if (nkt >= 2) ktile_iter(std::integral_constant<int, 2>{}, nkt - 2);
+    if (ahead) ktile_iter(std::integral_constant<int, 4>{}, nkt - 1);
+    else if (nkt >= 1) ktile_iter(std::integral_constant<int, 1>{}, nkt - 1);
+    // No workgroup barrier here: after the barrier in the middle of the last K-tile no wave reads or writes a stage
+    // (the A23 / B23 reads of that tile are issued before the barrier, which waits for them), so a wave may overwrite
+    // LDS with its staging block as soon as its own MFMAs are done, while slower waves still run theirs.
+  } else {
+    for (int64_t kt = 0; kt < nkt; ++kt) ktile_iter(std::integral_constant<int, 0>{}, kt);
+    __syncthreads();  // speculative fragment reads / stores of the idle stage must finish before LDS is reused
   }
-  __syncthreads();  // speculative fragment reads / stores of the idle stage must finish before LDS is reused
 #undef X6_GLOAD
 #undef X6_GLOAD_A
 #undef X6_GLOAD_B
@@ -550,7 +604,10 @@ gemm_x6_kernel(const GemmArgs g) {
 #ifdef GCT_LAB_NO_EPI         // tools/gemm_lab.hip: main loop only
     if (acc[0][0][0] == 123456.789f)
 #endif
-    wave_epilogue_tail<MODE == X6_FWD ? 1 : (MODE == X6_DGRAD ? 2 : 3)>(g, stg, lane, m0 + wm, n0 + wn, z);
+    {
+      if (BAL) wave_epilogue_finish<SIDE>(g, stg, lane, mw, el, ex, ah.have);
+      else wave_epilogue_tail<SIDE>(g, stg, lane, mw, nw, z);
+    }
   }
 #ifdef GCT_STAMPS
   __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0): include the stores' completion

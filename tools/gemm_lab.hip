@@ -85,7 +85,7 @@ int main(int argc, char** argv) {
       }, reps);
       printf("%-5s fwd   %-13s M=%ld K=%d N=%d: %8.1f us %6.1f TF\n", s.name, c.nm, (long)M, K, N, t, fl / t / 1e6);
     }
-    const Case dc[] = {{"store", GCT_DEPI_STORE, 0.f}, {"gelu_bwd.1", GCT_DEPI_GELU_BWD, 0.1f},
+    const Case dc[] = {{"store", GCT_DEPI_STORE, 0.f}, {"accum", GCT_DEPI_ACCUM, 0.f}, {"gelu_bwd.1", GCT_DEPI_GELU_BWD, 0.1f},
                        {"mul_saved.1", GCT_DEPI_MUL_SAVED, 0.1f}};
     for (const Case& c : dc) {
       if (c.epi != GCT_DEPI_STORE && nseg > 1) continue;
