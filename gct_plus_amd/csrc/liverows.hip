@@ -25,6 +25,8 @@
 //        compact row 4i + e  <->  original row 4 * quad_list[i] + e,
 //        cstart[b]    = compact row of (b, t = 0); the live rows of a sample are contiguous in both spaces, so
 //                       (b, t) sits at compact row cstart[b] + t for t < n_b when the live rows are the prefix 0..n_b-1.
+//                       A sample WITHOUT a live row whose first quad is dead gets the compact row of the next live quad
+//                       (4 * its rank, no offset inside the quad), so cstart never decreases over the samples.
 //     About 8 % more rows than an exact row compaction at MOSES-like lengths (two partial quads per sample).
 #include "common.h"
 
@@ -140,8 +142,13 @@ __global__ __launch_bounds__(1024) void live_quads_kernel(const uint8_t* __restr
   __threadfence_block();
   __syncthreads();
   for (int b = tid; b < B; b += 1024) {
+    // a sample whose first quad is dead has no live prefix row (its row 0 is dead): it gets the compact row of the next
+    // live quad WITHOUT the offset of row 0 inside its quad -- with the offset, cstart[b] could lie past cstart[b + 1],
+    // and the gap [cstart[b - 1] + n_b[b - 1], cstart[b]) of the sample before it would run over live rows behind it
     const int64_t r0 = (int64_t)b * T;
-    cstart[b] = 4 * qrank[r0 >> 2] + (int)(r0 & 3);
+    const int qd = (int)(r0 >> 2), rk = qrank[qd];
+    const bool qlive = rk < total && quad_list[rk] == qd;
+    cstart[b] = 4 * rk + (qlive ? (int)(r0 & 3) : 0);
   }
   if (tid == 0) {
     info[4] = 4 * padded;

@@ -216,7 +216,9 @@ int gct_nonzero_row_tiles(const float* x, int64_t ld, int64_t rows, int cols, in
  *   cstart [B] / quad_list [ceil(B*T/4)+32] / qrank_ws [ceil(B*T/4)] (nullable, together): the COMPACTION MAP of the
  *   decoder backward.  Rows are compacted in aligned groups of 4 ("quads"), the granularity at which every dropout
  *   site draws its Philox values: compact row 4i+e <-> original row 4*quad_list[i]+e (quad_list ascending, padded
- *   with -1 to a multiple of 32 quads); sample b's row t sits at compact row cstart[b]+t.
+ *   with -1 to a multiple of 32 quads); sample b's row t sits at compact row cstart[b]+t for t < n_b[b] (live rows
+ *   that are a prefix).  cstart never decreases over the samples: a sample without a live row gets the compact row
+ *   where the next live row at or behind its own rows starts (4 * live quads, at most, when there is none).
  * gct_gather_quads / gct_scatter_quads move rows between the two spaces (scatter: dst pre-zeroed by the caller). */
 int gct_live_rows(const float* g, int64_t ld, int B, int T, int cols, const uint8_t* mask, int64_t mask_sb,
                   int64_t mask_sq, uint8_t* live, int32_t* n_b, int32_t* info, int32_t* cstart,
@@ -235,7 +237,9 @@ int gct_scatter_quads(const float* src, int64_t ld, const int32_t* quad_list, in
                       int64_t ldd, int64_t M, void* stream);
 /* Zero the rows of a compact [nrows][cols] buffer that belong to no sample: [cstart[b] + n_b[b], cstart[b+1]) for every
  * b and [.., nrows) behind the last one -- what a kernel that writes only rows cstart[b] .. + n_b[b] (attention over
- * compact rows) leaves untouched.  cstart must be ascending (gct_live_rows / gct_key_rows). */
+ * compact rows) leaves untouched; no row of a live prefix is written, whatever the order of the two kernels.  cstart
+ * must be non-decreasing (gct_live_rows / gct_key_rows emit it so, samples without a live row included).  nrows is the
+ * caller's: the compact rows alone, or with the slack rows that follow them in the allocation. */
 int gct_zero_gap_rows(float* buf, int64_t ld, int cols, const int32_t* cstart, const int32_t* n_b, int B, int64_t nrows,
                       void* stream);
 /* dst rows += the compact rows (gradient of rows that were gathered: the encoder's K | V over its visible rows) */
