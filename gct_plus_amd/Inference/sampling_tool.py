@@ -23,6 +23,11 @@ with per-row positions (KVDecoder.generate(prefix_lens=)), so each row gives exa
 scaffold alone (no left-padding, which would shift the positional encodings).  Beam search has no mixed-length kernels:
 it runs one decode per prefix length and restores the input order.
 
+Log-likelihoods: `score` / `score_smiles` give log p(x | z, conditions, scaffold) of molecules the caller holds
+(decode.score_tokens: teacher-forced, one decoder forward), with the token accuracy next to it; `with_logp=True` makes
+`decode`, `sample_smiles` and `sample_multiple_smiles` return the model's log-probability of what they drew as one more
+element (KVDecoder.generate(return_logp=True): no second forward).
+
 `stream_rows=R` (optional): greedy / multinomial decodes run with continuous batching (KVDecoder.generate_stream) -- the
 n rows of a call are a pool that R decode rows work through, a row whose molecule reached <eos> taking the next one, so
 `sample_smiles(30000)` is one call that never computes past a molecule's end.  Every decode of such a sampler goes that
@@ -30,7 +35,7 @@ way, also one of fewer than R rows (a single wave): what a molecule decodes then
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -38,7 +43,17 @@ import torch
 from ..Model.modules import get_src_mask
 from ..data import Vocab, tokenize
 from ..decode import (BEAM_ALPHA, KVDecoder, check_beam_size, check_sample_filter, check_stream_model,
-                      check_stream_rows, generated_tokens)
+                      check_stream_rows, generated_tokens, score_tokens)
+
+
+class Scores(NamedTuple):
+    """What Sampling.score returns, on the CPU: logp [n] fp32 = log p(tokens | z, conditions, prefix), tokens [n] int32
+    scored tokens (the <eos> included), hits [n] int32 of them the model's top choice under teacher forcing,
+    token_logp [n, W] fp32 per column (0 on prefix and pad columns).  decode.score_reference states the rule."""
+    logp: torch.Tensor
+    tokens: torch.Tensor
+    hits: torch.Tensor
+    token_logp: torch.Tensor
 
 
 def sample_token_lengths(data: Sequence[int], size: int, rng: np.random.Generator) -> np.ndarray:
@@ -108,8 +123,12 @@ class Sampling:
                  cond_dim: int = 0, decode_algo: str = "greedy", toklen_data: Optional[Sequence[int]] = None,
                  scaler=None, device="cuda", seed: int = 0, use_graphs: bool = False, beam_size: int = 4,
                  beam_alpha: float = BEAM_ALPHA, top_k: Optional[int] = None, top_p: Optional[float] = None,
-                 temperature: float = 1.0, stream_rows: Optional[int] = None):
+                 temperature: float = 1.0, stream_rows: Optional[int] = None, with_logp: bool = False):
         V = model.out.weight.shape[0]
+        if with_logp and decode_algo == "beam":
+            raise ValueError("with_logp is not supported with decode_algo='beam': decode_beams returns the beams' "
+                             "scores, which are sums of log-probabilities already")
+        self.with_logp = bool(with_logp)
         if stream_rows is not None:
             if decode_algo == "beam":
                 raise ValueError("stream_rows is not supported with decode_algo='beam' (beam search keeps its rows in step)")
@@ -176,7 +195,9 @@ class Sampling:
         """ids [n, L] (prefix included); with decode_algo="beam" the best beam of each sample.
         prefix_lens (ints [n], optional): row r's prefix is ys[r, :t0_r] (KVDecoder.generate); not with beam search.
         The sampler's top_k / top_p / temperature apply to every draw (sample_smiles, sample_multiple_smiles).
-        With stream_rows the n rows are a pool decoded by continuous batching; same layout, input order."""
+        With stream_rows the n rows are a pool decoded by continuous batching; same layout, input order.
+        with_logp (constructor): returns (ids, logp), logp [n] fp32 on the CPU = the model's log-probability of each
+        row's generated tokens up to its <eos> (raw logits at temperature 1, whatever filter the draw went through)."""
         if self.decode_algo == "beam":
             if prefix_lens is not None:
                 raise ValueError("decode: beam search takes prefixes of one length (see sample_multiple_smiles)")
@@ -187,14 +208,51 @@ class Sampling:
         total = ys.size(1) + self.max_strlen
         if self.stream_rows is not None:
             self.kv.start_stream(zs, src_mask, dconds, rows=self.stream_rows, max_total_len=min(200, total))
-            return self.kv.generate_stream(ys, self.max_strlen, algo=self.decode_algo, seed=self.seed,
-                                           use_graphs=self.use_graphs, prefix_lens=prefix_lens, top_k=self.top_k,
-                                           top_p=self.top_p, temperature=self.temperature)[0]
+            out = self.kv.generate_stream(ys, self.max_strlen, algo=self.decode_algo, seed=self.seed,
+                                          use_graphs=self.use_graphs, prefix_lens=prefix_lens, top_k=self.top_k,
+                                          top_p=self.top_p, temperature=self.temperature, return_logp=self.with_logp)
+            return (out[0], out[3].cpu()) if self.with_logp else out[0]
         # the positional table has 200 rows, of which use_cond2dec spends n_c on the condition tokens
         self.kv.start(zs, src_mask, dconds, max_total_len=min(200 - self.kv.off, total))
-        return self.kv.generate(ys, self.max_strlen, algo=self.decode_algo, seed=self.seed,
-                                use_graphs=self.use_graphs, prefix_lens=prefix_lens, top_k=self.top_k,
-                                top_p=self.top_p, temperature=self.temperature)
+        out = self.kv.generate(ys, self.max_strlen, algo=self.decode_algo, seed=self.seed,
+                               use_graphs=self.use_graphs, prefix_lens=prefix_lens, top_k=self.top_k,
+                               top_p=self.top_p, temperature=self.temperature, return_logp=self.with_logp)
+        return (out[0], out[2].cpu()) if self.with_logp else out
+
+    @torch.no_grad()
+    def score(self, zs, ys, src_mask, dconds=None, prefix_lens=None) -> Scores:
+        """Teacher-forced log-likelihood of the full token rows ys [n, W] (prefix, tokens, pad: the layout `decode`
+        returns) under the latents zs, mask and conditions `decode` takes (decode.score_tokens).  Scores on the CPU."""
+        zs, src_mask = zs.to(self.device), src_mask.to(self.device)
+        dconds = None if dconds is None else dconds.to(self.device)
+        logp, tokens, hits, token_logp = score_tokens(self.model, zs, src_mask, dconds, ys, prefix_lens=prefix_lens,
+                                                      pad_id=self.pad_id)
+        return Scores(logp.cpu(), tokens.cpu(), hits.cpu(), token_logp.cpu())
+
+    def _score_targets(self, smiles_list, scaffold_list=None):
+        """<sos> [scaffold <sep>] smiles <eos> per molecule -> (ys [n, W] right-padded, prefix_lens or None, extras:
+        latent rows in front of the molecule's own -- scaffold tokens + 1, or 0)."""
+        smiles_list = list(smiles_list)
+        if scaffold_list is None:
+            rows = [[self.sos_id] + self.smi_to_id(s) + [self.eos_id] for s in smiles_list]
+            return pack_prefixes(rows, self.pad_id)[0], None, [0] * len(rows)
+        scaffold_list = list(scaffold_list)
+        if len(scaffold_list) != len(smiles_list):
+            raise ValueError(f"{len(smiles_list)} molecules for {len(scaffold_list)} scaffolds")
+        sca = [self.smi_to_id(s) for s in scaffold_list]
+        rows = [[self.sos_id] + c + [self.sep_id] + self.smi_to_id(s) + [self.eos_id] for c, s in zip(sca, smiles_list)]
+        return (pack_prefixes(rows, self.pad_id)[0], torch.as_tensor([len(c) + 2 for c in sca], dtype=torch.long),
+                [len(c) + 1 for c in sca])
+
+    def _score_smiles(self, ys, lens, extras, zs, dconds, encode):
+        """zs None: the deterministic reconstruction score -- the latent is the encoder's MEAN of the same molecule
+        (encode() -> (src, src_mask, econds)) and the mask the encoder's.  zs given: latent_setup_rows' mask rule."""
+        if zs is None:
+            src, src_mask, econds = encode()
+            zs = self.model.encode(src=src, src_mask=src_mask, econds=econds)[1]
+        else:
+            zs, _, src_mask = latent_setup_rows(extras, zs, None, self.latent_dim, self.sample_toklen, self.sample_z)
+        return self.score(zs, ys, src_mask, dconds, lens)
 
     @torch.no_grad()
     def decode_beams(self, zs, ys, src_mask, dconds=None, beam_size=None, alpha=None):
@@ -232,7 +290,7 @@ class Sampling:
     @torch.no_grad()
     def _sample_multiple(self, scaffolds, zs, toklen, dconds):
         """One scaffold per row (sample_multiple_smiles): a single mixed-prefix decode, or for beam search one decode
-        per prefix length; (smiles, toklen, toklen_gen) in input order."""
+        per prefix length; (smiles, toklen, toklen_gen) in input order (with_logp: and logp [n])."""
         scaffolds = list(scaffolds)
         if not scaffolds:
             raise ValueError("sample_multiple_smiles: no scaffolds")
@@ -248,14 +306,19 @@ class Sampling:
                     gens[i] = row
         else:
             outs = self.decode(zs, ys0, src_mask, dconds, prefix_lens=lens)
+            outs, logp = outs if self.with_logp else (outs, None)
             gens = list(generated_tokens(outs, lens).cpu())
         smiles = [self.id_to_smi(g.numpy()) for g in gens]
-        return smiles, toklen, [len(tokenize(s, self.add_sep)) for s in smiles]
+        res = smiles, toklen, [len(tokenize(s, self.add_sep)) for s in smiles]
+        return res + (logp,) if self.with_logp else res
 
     def _finish(self, outs, toklen, skip=0):
+        """with_logp: `outs` is decode's (ids, logp) and logp becomes the fourth element."""
+        outs, logp = outs if self.with_logp else (outs, None)
         outs = outs.cpu().numpy()
         smiles = [self.id_to_smi(ids[skip:]) for ids in outs]
-        return smiles, toklen, [len(tokenize(s, self.add_sep)) for s in smiles]
+        res = smiles, toklen, [len(tokenize(s, self.add_sep)) for s in smiles]
+        return res + (logp,) if self.with_logp else res
 
 
 class VaetfSampling(Sampling):
@@ -267,6 +330,15 @@ class VaetfSampling(Sampling):
         zs, toklen, src_mask = self._latent_setup(n, zs, toklen)
         outs = self.decode(zs, self.init_y(n), src_mask)
         return self._finish(outs, toklen)
+
+    def score_smiles(self, smiles_list, zs=None) -> Scores:
+        """log p(<sos> smiles <eos> | z): z = zs [n, L_e, latent], or (None) the encoder's mean of the same molecule."""
+        ys, lens, extras = self._score_targets(smiles_list)
+
+        def encode():
+            src = self.tokenize_smiles(smiles_list).to(self.device)
+            return src, get_src_mask(src, self.pad_id), None
+        return self._score_smiles(ys, lens, extras, zs, None, encode)
 
 
 class CvaetfSampling(Sampling):
@@ -284,6 +356,16 @@ class CvaetfSampling(Sampling):
         outs = self.decode(zs, self.init_y(n), src_mask, dconds)
         return self._finish(outs, toklen)
 
+    def score_smiles(self, smiles_list, conds, zs=None, transform=True) -> Scores:
+        """log p(<sos> smiles <eos> | z, conds); zs None: the encoder's mean of (smiles, conds)."""
+        ys, lens, extras = self._score_targets(smiles_list)
+        conds = self.transform(conds) if transform else torch.as_tensor(conds, dtype=torch.float32)
+
+        def encode():
+            src, econds = self.tokenize_smiles(smiles_list).to(self.device), conds.to(self.device)
+            return src, get_src_mask(src, self.pad_id, econds), econds
+        return self._score_smiles(ys, lens, extras, zs, conds, encode)
+
 
 class ScaVaeSampling(Sampling):
     def encode_smiles(self, smiles_list, scaffold_list):
@@ -295,6 +377,16 @@ class ScaVaeSampling(Sampling):
         zs, toklen, src_mask = self._latent_setup(n, zs, toklen, extra=len(sca_ids) + 1)
         outs = self.decode(zs, self.init_y(n, True, sca_ids, True), src_mask)
         return self._finish(outs, toklen, skip=1 + len(sca_ids) + 1)
+
+    def score_smiles(self, smiles_list, scaffold_list, zs=None) -> Scores:
+        """log p(smiles <eos> | <sos> scaffold <sep>, z), one scaffold per molecule (the prefix is not scored); zs None:
+        the encoder's mean of scaffold <sep> smiles."""
+        ys, lens, extras = self._score_targets(smiles_list, scaffold_list)
+
+        def encode():
+            src = self.tokenize_smiles([b + "<sep>" + a for a, b in zip(smiles_list, scaffold_list)]).to(self.device)
+            return src, get_src_mask(src, self.pad_id), None
+        return self._score_smiles(ys, lens, extras, zs, None, encode)
 
     def sample_multiple_smiles(self, scaffolds, zs=None, toklen=None):
         """One molecule per scaffold, all rows in one batch: row r decodes as sample_smiles(1, scaffolds[r]) with z
@@ -316,6 +408,18 @@ class PscavaetfSampling(Sampling):
         zs, toklen, src_mask = self._latent_setup(n, zs, toklen, extra=len(sca_ids) + 1)
         outs = self.decode(zs, self.init_y(n, True, sca_ids, True), src_mask, dconds)
         return self._finish(outs, toklen, skip=1 + len(sca_ids) + 1)
+
+    def score_smiles(self, smiles_list, scaffold_list, conds, zs=None, transform=True) -> Scores:
+        """log p(smiles <eos> | <sos> scaffold <sep>, z, conds), one scaffold per molecule; zs None: the encoder's mean
+        of (scaffold <sep> smiles, conds)."""
+        ys, lens, extras = self._score_targets(smiles_list, scaffold_list)
+        conds = self.transform(conds) if transform else torch.as_tensor(conds, dtype=torch.float32)
+
+        def encode():
+            src = self.tokenize_smiles([b + "<sep>" + a for a, b in zip(smiles_list, scaffold_list)]).to(self.device)
+            econds = conds.to(self.device)
+            return src, get_src_mask(src, self.pad_id, econds), econds
+        return self._score_smiles(ys, lens, extras, zs, conds, encode)
 
     def sample_multiple_smiles(self, dconds, scaffolds, zs=None, toklen=None, transform=True):
         """The reference's intended sample_multiple_smiles (sampling_tool.py, commented out there): row r has the

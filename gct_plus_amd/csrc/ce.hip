@@ -2,6 +2,9 @@
 // Reference: Train/trainer1.py:21-22  F.cross_entropy(logits.view(-1,V), ys,
 // ignore_index=pad, reduction='sum').  V <= 31 in practice: one wave per row (row = 120 B),
 // wave-level max / sum-exp; per-block partial sums reduced in fixed order.
+// Log-likelihoods (decode.py score_reference states the rule): gct_seq_logp scores given token rows against their
+// teacher-forced logits, gct_chosen_logp the token a decode step has just picked.  Both go through wave_token_logp, the
+// same wave-per-row log-softmax; every output has one writer and a fixed summation order (no atomics).
 #include "common.h"
 
 int gct_final_sum(const float* ws, int n, float scale, float* out, hipStream_t st);
@@ -60,6 +63,99 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
   }
 }
 
+// One wave, one logits row lr[0, V), 0 <= tok < V (uniform over the wave): returns x[tok] - m - log(sum exp(x - m)) on
+// every lane; hit = tok is the FIRST maximum of the row (torch.argmax).
+__device__ __forceinline__ float wave_token_logp(const float* __restrict__ lr, int V, int tok, int lane, bool& hit) {
+  float mx = -INFINITY;
+  for (int c = lane; c < V; c += 64) mx = fmaxf(mx, lr[c]);
+  mx = gct_wave_max(mx);
+  float se = 0.f;
+  int first = 0x7fffffff;                               // lowest index that holds the maximum
+  for (int c = lane; c < V; c += 64) {
+    const float x = lr[c];
+    se += expf(x - mx);
+    if (x == mx && c < first) first = c;
+  }
+  se = gct_wave_sum(se);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
+  hit = first == tok;
+  return (lr[tok] - mx) - logf(se);
+}
+
+constexpr int SEQ_LOGP_MAX_W = 256;
+
+// one workgroup per sequence; wave w takes the token columns w, w + 4, ...  Each column's log-probability and flags
+// go to LDS, and thread 0 adds them up in ascending column order: the sums do not depend on the grid or on which wave
+// took a column.
+__global__ __launch_bounds__(256) void seq_logp_kernel(const float* __restrict__ logits, int64_t ld, int V,
+                                                       int64_t rows_per_seq, int row_shift,
+                                                       const int64_t* __restrict__ ys, int64_t ld_ys,
+                                                       const int32_t* __restrict__ prefix_lens, int64_t pad_id, int W,
+                                                       float* __restrict__ token_logp, int64_t ld_out,
+                                                       float* __restrict__ logp, int32_t* __restrict__ tokens,
+                                                       int32_t* __restrict__ hits) {
+  __shared__ float sh_lp[SEQ_LOGP_MAX_W];
+  __shared__ uint8_t sh_flag[SEQ_LOGP_MAX_W];           // bit 0: scored, bit 1: hit
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t r = blockIdx.x;
+  const int t0 = prefix_lens ? prefix_lens[r] : 1;
+  const int64_t* yr = ys + r * ld_ys;
+  for (int c = wave; c < W; c += 4) {                   // uniform over the wave
+    const int64_t tok = yr[c];
+    const bool scored = c >= t0 && c >= 1 && tok != pad_id && tok >= 0 && tok < V;
+    float lp = 0.f;
+    bool hit = false;
+    if (scored) lp = wave_token_logp(logits + (r * rows_per_seq + row_shift + c - 1) * ld, V, (int)tok, lane, hit);
+    if (lane == 0) {
+      token_logp[r * ld_out + c] = lp;
+      sh_lp[c] = lp;
+      sh_flag[c] = (scored ? 1 : 0) | (hit ? 2 : 0);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float sum = 0.f;
+    int nt = 0, nh = 0;
+    for (int c = 0; c < W; ++c) {
+      const int f = sh_flag[c];
+      if (f & 1) sum += sh_lp[c];
+      nt += f & 1;
+      nh += (f >> 1) & 1;
+    }
+    logp[r] = sum;
+    tokens[r] = nt;
+    hits[r] = nh;
+  }
+}
+
+// one wave per decode row, as select_token_kernel: the column the selection has just written
+__global__ __launch_bounds__(256) void chosen_logp_kernel(const float* __restrict__ logits, int V,
+                                                          const int64_t* __restrict__ ys, int64_t ld_ys,
+                                                          const int32_t* __restrict__ pos,
+                                                          const int32_t* __restrict__ row_off,
+                                                          const int32_t* __restrict__ item,
+                                                          const int32_t* __restrict__ prefix_len, int64_t pad_id,
+                                                          float* __restrict__ out, int64_t ld_out, int out_rows,
+                                                          int n) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= n) return;
+  int p = *pos + 1;
+  if (row_off) p -= row_off[row];
+  int dst = row;
+  if (item) {                                           // uniform over the wave: a whole wave leaves
+    dst = item[row];
+    if (dst < 0 || p < prefix_len[dst]) return;         // parked, or a prefix token: not a generated one
+  }
+  if (p < 0 || p >= ld_out || p >= ld_ys || dst >= out_rows) return;
+  const int64_t tok = ys[(int64_t)row * ld_ys + p];
+  float lp = 0.f;
+  bool hit = false;
+  if (tok != pad_id && tok >= 0 && tok < V) lp = wave_token_logp(logits + (int64_t)row * V, V, (int)tok, lane, hit);
+  if (lane == 0) out[(int64_t)dst * ld_out + p] = lp;
+}
+
 }  // namespace
 
 extern "C" int gct_ce_fwd(const float* logits, const int64_t* target, float* out, float* ws,
@@ -83,5 +179,36 @@ extern "C" int gct_ce_bwd(const float* logits, const int64_t* target, const floa
   hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, logits,
                      target, gout, dlogits, rows, V, pad_id);
   GCT_LAUNCH_CHECK("ce_bwd");
+  return GCT_OK;
+}
+
+extern "C" int gct_seq_logp(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift,
+                            const int64_t* ys, int64_t ld_ys, const int32_t* prefix_lens, int64_t pad_id, int n,
+                            int W, float* token_logp, int64_t ld_out, float* logp, int32_t* tokens, int32_t* hits,
+                            void* stream) {
+  GCT_CHECK_ARG(logits && ys && token_logp && logp && tokens && hits, "seq_logp: null pointer");
+  GCT_CHECK_ARG(n >= 0 && V > 0 && ld >= V, "seq_logp: bad shape (n %d, V %d, ld %lld)", n, V, (long long)ld);
+  GCT_CHECK_ARG(W >= 1 && W <= SEQ_LOGP_MAX_W, "seq_logp: rows of %d tokens (1 .. %d supported)", W, SEQ_LOGP_MAX_W);
+  GCT_CHECK_ARG(ld_ys >= W && ld_out >= W, "seq_logp: ld_ys / ld_out narrower than the %d token columns", W);
+  GCT_CHECK_ARG(row_shift >= 0 && rows_per_seq >= (int64_t)row_shift + W - 1,
+                "seq_logp: %lld logits rows per sequence do not hold %d + %d", (long long)rows_per_seq, row_shift, W - 1);
+  if (n == 0) return GCT_OK;
+  hipLaunchKernelGGL(seq_logp_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, logits, ld, V,
+                     rows_per_seq, row_shift, ys, ld_ys, prefix_lens, pad_id, W, token_logp, ld_out, logp, tokens, hits);
+  GCT_LAUNCH_CHECK("seq_logp");
+  return GCT_OK;
+}
+
+extern "C" int gct_chosen_logp(const float* logits, int V, const int64_t* ys, int64_t ld_ys, const int32_t* pos,
+                               const int32_t* row_off, const int32_t* item, const int32_t* prefix_len, int64_t pad_id,
+                               float* out, int64_t ld_out, int out_rows, int n, void* stream) {
+  GCT_CHECK_ARG(logits && ys && pos && out && n >= 0 && V > 0 && ld_ys > 0 && ld_out > 0 && out_rows >= 0,
+                "chosen_logp: bad args");
+  GCT_CHECK_ARG(!item == !prefix_len && (!item || row_off), "chosen_logp: streamed rows need item, prefix_len and row_off");
+  GCT_CHECK_ARG(item || out_rows >= n, "chosen_logp: %d output rows for %d decode rows", out_rows, n);
+  if (n == 0) return GCT_OK;
+  hipLaunchKernelGGL(chosen_logp_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, V,
+                     ys, ld_ys, pos, row_off, item, prefix_len, pad_id, out, ld_out, out_rows, n);
+  GCT_LAUNCH_CHECK("chosen_logp");
   return GCT_OK;
 }

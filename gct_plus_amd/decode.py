@@ -43,6 +43,11 @@ a row whose item produced <eos> (or reached its cap) hands its tokens out and ta
 rows, masks, condition rows, prefix -- with row_off[r] = *pos + 1, so the row restarts at its own position 0 behind the
 same shared counter.  Every item enters that way and consumes its prefix token by token through the step chain (no
 prefill), so what an item decodes depends on nothing but the item; its multinomial key is (item, token position).
+
+Log-likelihoods: the rule is stated once, in `score_reference`.  `score_tokens` scores given token rows teacher-forced --
+one decoder forward over the rows up to each sequence's last scored token, then gct_seq_logp on the logits; and
+`generate` / `generate_stream(return_logp=True)` return the log-probability of every token they pick: gct_chosen_logp
+reads the step's logits right behind the selection, so a sampling run needs no second forward to know its likelihood.
 """
 from __future__ import annotations
 
@@ -56,6 +61,7 @@ import torch
 
 from . import engine, ops
 from ._lib import check
+from .flat import planes_scope
 
 
 # rows per step below which the step's GEMMs take the skinny fp32 kernels (panel / 64x64 split-K) instead of the general
@@ -74,6 +80,7 @@ BEAM_ALPHA = 0.7
 BEAM = "beam"                                       # selection mode key of the beam step (self.graphs, _advance)
 FILTERED = "filtered"                               # selection mode key of the filtered multinomial draw
 STREAM = "stream"                                   # graph key suffix of the continuous-batching step unit
+LOGP = "logp"                                       # graph key suffix of a step unit that records log-probabilities
 STREAM_COND_CHUNK = 256                             # items per GEMM when the pool's condition rows are projected
 TOP_K_FLOOR = 1e-6                                  # weight of a token outside the top k (the reference's top_k_logits)
 
@@ -127,6 +134,129 @@ def sample_filter_reference(logits, top_k=None, top_p=None, temperature=1.0):
         mass = torch.where(larger > 0, top_mass.gather(-1, (larger - 1).clamp(min=0)), torch.zeros_like(top_mass))
         w = torch.where(mass < float(top_p), w, torch.zeros_like(w))
     return w / w.sum(-1, keepdim=True)
+
+
+# ------------------------------------------------------------------------------------------- log-likelihoods
+def check_score_inputs(ys, prefix_lens, vocab):
+    """Validate the inputs of a scoring call: ys an integer tensor [n, W >= 2] of token ids in [0, vocab); prefix_lens
+    None or integers [n] in [1, W].  ValueError otherwise.  Returns the prefix lengths as an int64 CPU tensor [n] (all 1
+    for None)."""
+    ys = torch.as_tensor(ys)
+    if ys.dim() != 2 or ys.shape[1] < 2:
+        raise ValueError(f"ys must be [n, W >= 2] (full token rows), got {list(ys.shape)}")
+    if ys.dtype.is_floating_point or ys.dtype.is_complex or ys.dtype == torch.bool:
+        raise ValueError(f"ys must hold integer token ids, got {ys.dtype}")
+    n, W = ys.shape
+    if prefix_lens is None:
+        lens = torch.ones(n, dtype=torch.int64)
+    else:
+        lens = torch.as_tensor(prefix_lens)
+        if lens.dtype.is_floating_point or lens.dtype.is_complex or lens.dtype == torch.bool:
+            raise ValueError(f"prefix_lens must hold integers, got {lens.dtype}")
+        lens = lens.to("cpu", torch.int64)
+        if lens.dim() != 1 or lens.numel() != n:
+            raise ValueError(f"prefix_lens must have shape [{n}], got {list(lens.shape)}")
+        if n and (int(lens.min()) < 1 or int(lens.max()) > W):
+            raise ValueError(f"prefix_lens must lie in [1, {W}] (the row width), got [{int(lens.min())}, "
+                             f"{int(lens.max())}]")
+    if n and (int(ys.min()) < 0 or int(ys.max()) >= int(vocab)):
+        raise ValueError(f"token ids must lie in [0, {int(vocab)}), got [{int(ys.min())}, {int(ys.max())}]")
+    return lens
+
+
+def score_reference(logits, ys, prefix_lens, pad_id):
+    """THE statement of the scoring rule (gct_seq_logp implements it on teacher-forced logits, gct_chosen_logp on the
+    logits of a decode step).  ys [n, W] int64: full token rows -- prefix, tokens, pad (generate(prefix_lens=)'s layout);
+    logits [n, W - 1, V]: the teacher-forced logits of the inputs ys[:, :-1], row c - 1 predicts token c; prefix_lens
+    ints [n], 1 <= t0_r <= W (None: 1, only <sos> is given).
+    Column c of row r is SCORED when c >= t0_r and ys[r, c] != pad_id.  Returns, in the dtype of logits (fp32 at least):
+      token_logp [n, W]  x[t] - m - log(sum exp(x - m)) at scored columns (beam_log_softmax's form, m the row maximum),
+                         0 elsewhere;
+      logp [n]           the sum of a row's scored columns in ascending column order;
+      tokens [n] int32   the number of scored columns;
+      hits [n] int32     the scored columns whose target is the FIRST maximum of its logits row (torch.argmax).
+    A row without a scored column gives 0, 0, 0."""
+    ys = torch.as_tensor(ys)
+    lens = check_score_inputs(ys, prefix_lens, logits.shape[-1]).to(ys.device)
+    n, W = ys.shape
+    x = logits if logits.dtype == torch.float64 else logits.float()
+    if tuple(x.shape[:2]) != (n, W - 1):
+        raise ValueError(f"logits must be [{n}, {W - 1}, V], got {list(logits.shape)}")
+    y = x - x.max(-1, keepdim=True).values
+    lsm = y - torch.log(torch.exp(y).sum(-1, keepdim=True))
+    tgt = ys[:, 1:].long()
+    scored = (torch.arange(1, W, device=ys.device).view(1, -1) >= lens.view(-1, 1)) & (tgt != pad_id)
+    zero = torch.zeros((), dtype=x.dtype, device=x.device)
+    picked = torch.where(scored.to(x.device), lsm.gather(-1, tgt.to(x.device).unsqueeze(-1)).squeeze(-1), zero)
+    token_logp = torch.cat([torch.zeros(n, 1, dtype=x.dtype, device=x.device), picked], dim=1)
+    logp = torch.zeros(n, dtype=x.dtype, device=x.device)
+    for c in range(1, W):                                # ascending column order
+        logp = logp + token_logp[:, c]
+    hit = scored.to(x.device) & (x.argmax(-1) == tgt.to(x.device))
+    return token_logp, logp, scored.sum(1).to(torch.int32), hit.sum(1).to(torch.int32)
+
+
+@planes_scope
+def _teacher_forced_logits(model, trg, z, src_mask, trg_mask, dconds, loss_rows):
+    """model.decode with loss_rows: the decoder rows that are not marked are not computed (when the row planner accepts
+    them), under the weight-plane scope model.decode runs in."""
+    x = model.decoder(trg, z, src_mask, trg_mask, dconds, loss_rows=loss_rows)
+    if model.get_attn:
+        x = x[0]
+    return model.out(x)
+
+
+@torch.no_grad()
+def score_tokens(model, z, src_mask, dconds, ys, prefix_lens=None, pad_id=1, chunk=512):
+    """Teacher-forced log-likelihood of the token rows ys [n, W] (score_reference's layout and rule) under
+    model.decode(ys[:, :-1], z, src_mask, ., dconds): z [n, L_e, latent], src_mask bool [n, 1, L_e], dconds [n, n_c] or
+    None, as model.decode takes them.  Returns (logp [n] fp32, tokens [n] int32, hits [n] int32, token_logp [n, W] fp32)
+    on the device.
+    One decoder forward per `chunk` sequences, then gct_seq_logp straight on its logits.  The decoder gets loss_rows =
+    every input row up to the sequence's last scored token (prefix rows included, so that the live rows stay a prefix):
+    the rows behind it are not computed when the row planner accepts the map; a use_cond2dec model runs every row.
+    ValueError before any device work for malformed inputs (check_score_inputs) and for rows beyond the positional
+    table."""
+    from .Model.modules import get_trg_mask
+    dec = model.decoder
+    V = model.out.weight.shape[0]
+    ys = torch.as_tensor(ys)
+    lens = check_score_inputs(ys, prefix_lens, V)
+    if isinstance(chunk, bool) or not isinstance(chunk, numbers.Integral) or chunk < 1:
+        raise ValueError(f"chunk must be an int >= 1, got {chunk!r}")
+    n, W = ys.shape
+    c2d = bool(dec.use_cond2dec and dec.nconds > 0)
+    off = dec.nconds if c2d else 0
+    pe_rows = dec.pe.pe.shape[1]
+    if off + W - 1 > pe_rows or W > 256:
+        raise ValueError(f"{W - 1} input tokens + {off} condition rows exceed the {pe_rows}-row positional table")
+    dev = z.device
+    token_logp = torch.empty(n, W, device=dev)
+    logp = torch.empty(n, device=dev)
+    tokens = torch.empty(n, dtype=torch.int32, device=dev)
+    hits = torch.empty(n, dtype=torch.int32, device=dev)
+    cols = torch.arange(W, device=dev).view(1, -1)
+    for lo in range(0, n, int(chunk)):
+        hi = min(n, lo + int(chunk))
+        y = ys[lo:hi].to(dev, torch.int64).contiguous()
+        t0 = lens[lo:hi].to(dev)
+        out = (token_logp[lo:hi], logp[lo:hi], tokens[lo:hi], hits[lo:hi])
+        scored = (cols >= t0.view(-1, 1)) & (y != pad_id)
+        last = (scored * cols).amax(1)                              # a row's last scored column (0: none)
+        if not bool(last.any()):                                    # nothing to score: no forward
+            for t in out:
+                t.zero_()
+            continue
+        trg = y[:, :-1].contiguous()
+        dc = None if dconds is None else dconds[lo:hi].to(dev)
+        sm = None if src_mask is None else src_mask[lo:hi].to(dev)
+        trg_mask = get_trg_mask(trg, pad_id, c2d, dc if dec.nconds > 0 else None)
+        loss_rows = cols[:, :W - 1] < last.view(-1, 1)              # input row c - 1 predicts token c
+        logits = _teacher_forced_logits(model, trg, z[lo:hi], sm, trg_mask, dc, loss_rows)
+        rows = logits.shape[1]                                      # W - 1 (+ the condition rows of use_cond2dec)
+        ops.seq_logp(logits.reshape((hi - lo) * rows, V), y, None if prefix_lens is None else t0.to(torch.int32),
+                     pad_id, row_shift=off, rows_per_seq=rows, out=out)
+    return logp, tokens, hits, token_logp
 
 
 # ------------------------------------------------------------------------------------- continuous batching
@@ -333,6 +463,7 @@ class KVDecoder:
         self._shape = None
         self.stream = None                                # continuous batching: pool + StreamState (start_stream)
         self.streaming = False                            # a generate_stream loop is running (the step unit refills)
+        self.want_logp = False                            # this generate records the log-probability of every pick
 
     # -------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -412,6 +543,7 @@ class KVDecoder:
             self.valid = torch.zeros(n, T, dtype=torch.uint8, device=dev)
             self.done = torch.zeros(n, dtype=torch.uint8, device=dev)
             self.ys = torch.full((n, T), self.pad_id, dtype=torch.int64, device=dev)
+            self.tok_logp = torch.zeros(n, T, device=dev)                  # return_logp: laid out like ys
             self.src_valid = torch.empty(n, Lk, dtype=torch.uint8, device=dev)
             self.src_klen = torch.empty(n, dtype=torch.int32, device=dev)  # leading memory rows the cross-attention reads
             self.pos = torch.zeros(1, dtype=torch.int32, device=dev)       # token index the next step consumes
@@ -638,13 +770,23 @@ class KVDecoder:
         """One step and its selection: the unit a graph captures.  Continuous batching: then the refill."""
         self.step(beam=mode == BEAM)
         self._select(mode)
+        if self.want_logp and mode != BEAM:
+            self._chosen_logp()                          # before the refill, which reassigns the rows' items
         if self.streaming:
             self.stream["state"].refill()
+
+    def _chosen_logp(self):
+        """The model's log-probability of the token _select has just written (gct_chosen_logp): into tok_logp at the
+        row's own column, or, streamed, into the pool's table at (item, column)."""
+        st = self.stream if self.streaming else None
+        ops.chosen_logp(self.buf["logits"], self.ys, self.pos, st["out_logp"] if st else self.tok_logp, self.pad_id,
+                        row_off=self.row_off if self.ragged else None, item=st and st["item"],
+                        prefix_len=st and st["prefix_len"])
 
     # -------------------------------------------------------------------------------------
     @torch.no_grad()
     def generate(self, ys0, max_strlen=80, algo="greedy", seed=0, check_every=8, use_graphs=False, prefix_lens=None,
-                 top_k=None, top_p=None, temperature=1.0):
+                 top_k=None, top_p=None, temperature=1.0, return_logp=False):
         """Mirror of Sampling.decode: appends max_strlen-1 tokens to the prefix ys0 [n, t0]
         (stops early once every sample has produced <eos>, like the reference's break).
         prefix_lens (ints [n], 1 <= t0_r <= t0, optional): row r's prefix is ys0[r, :t0_r] (right-padded); it decodes
@@ -654,7 +796,11 @@ class KVDecoder:
         top_k / top_p / temperature (sample_filter_reference states the rules; validated before any device work, bad
         values raise ValueError): with algo="multinomial" and a non-neutral setting every draw goes through the filter
         (a selection mode and graph of its own; vocabularies up to ops.SAMPLE_FILTER_MAX_VOCAB).  Greedy ignores them:
-        the filters always keep the top token."""
+        the filters always keep the top token.
+        return_logp=True: returns (ys, token_logp, logp) -- token_logp [n, L] fp32 laid out like ys holds the MODEL's
+        log-probability of every generated token up to the row's first <eos> (raw logits at temperature 1, whatever
+        filter the draw went through; score_reference's rule), 0 on prefix, pad and later columns; logp [n] its row
+        sum.  One small launch per step behind the selection (gct_chosen_logp), no second forward."""
         V = self.model.out.weight.shape[0]
         filtered = check_sample_filter(top_k, top_p, temperature, V) and algo == "multinomial"
         if filtered and V > ops.SAMPLE_FILTER_MAX_VOCAB:
@@ -674,8 +820,13 @@ class KVDecoder:
         if filtered:
             mode = FILTERED
             self.filt.copy_(ops.sample_filter_settings(top_k, top_p, temperature, V))
+        self.want_logp = bool(return_logp)
         self.prefill(ys0, lens)
+        if self.want_logp:
+            self.tok_logp.zero_()
         self._select(mode)                                         # token t0 from the prefill's last position
+        if self.want_logp:
+            self._chosen_logp()
         last = t0 + steps
         for i in range(1, steps):
             self._run_step(mode, use_graphs)                       # consumes token t0+i-1, writes token t0+i
@@ -689,7 +840,16 @@ class KVDecoder:
             first = torch.where(is_eos, torch.arange(gen.size(1), device=gen.device)[None, :],
                                 gen.size(1)).min(dim=1).values
             ys = ys[:, :t0 + int(first.max().item()) + 1]
-        return ys.clone()
+        if not self.want_logp:
+            return ys.clone()
+        # a row's generated span: from its own t0_r to its first <eos> (a finished row decodes on, and the capture
+        # warm-up and the replay guard run real steps past the position they restore): everything else is 0
+        start = torch.full((n,), t0, device=ys.device) if lens is None else lens.to(ys.device)
+        n_gen = torch.where(is_eos.any(dim=1), is_eos.int().argmax(dim=1) + 1, gen.size(1))
+        cols = torch.arange(ys.size(1), device=ys.device).view(1, -1)
+        span = (cols >= start.view(-1, 1)) & (cols < (start + n_gen).view(-1, 1)) & (ys != self.pad_id)
+        token_logp = torch.where(span, self.tok_logp[:, :ys.size(1)], torch.zeros((), device=ys.device))
+        return ys.clone(), token_logp, token_logp.sum(1)
 
     @torch.no_grad()
     def generate_beam(self, ys0, beam_size, max_strlen=80, alpha=BEAM_ALPHA, check_every=8, use_graphs=False,
@@ -713,6 +873,7 @@ class KVDecoder:
         if self.off + t0 + steps > self.T:
             raise ValueError(f"prefix {t0} + {steps} steps exceeds the cache length {self.T - self.off}")
         dev = self.ys.device
+        self.want_logp = False                                     # (the beam scores are log-probabilities already)
         self.prefill(ys0.to(dev).repeat_interleave(k, 0))
         scores, _, _ = beam_init(ns, k, dev)
         self.bscores.copy_(scores.view(-1))
@@ -784,6 +945,7 @@ class KVDecoder:
                 ckv_pool=[torch.empty(N * nc, 2 * d, device=dev) for _ in dec.layers] if c2l else [],
                 prefix_pool=torch.full((N, T), self.pad_id, dtype=torch.int64, device=dev), prefix_len=i32(N),
                 limit=i32(N), out_ys=torch.full((N, T), self.pad_id, dtype=torch.int64, device=dev), out_len=i32(N),
+                out_logp=torch.zeros(N, T, device=dev),           # return_logp: written per (item, column) by the rows
                 row_of=i32(N), start_step=i32(N), item=i32(R), harvest=i32(R),
                 fresh=torch.zeros(R, dtype=torch.uint8, device=dev), next_item=i32(1), n_harvested=i32(1),
                 enable=i32(1))
@@ -831,7 +993,7 @@ class KVDecoder:
 
     @torch.no_grad()
     def generate_stream(self, ys0, max_strlen=80, algo="greedy", seed=0, prefix_lens=None, max_new_tokens=None,
-                        top_k=None, top_p=None, temperature=1.0, use_graphs=False, check_every=8):
+                        top_k=None, top_p=None, temperature=1.0, use_graphs=False, check_every=8, return_logp=False):
         """Decode the pool of start_stream with continuous batching: item i starts from the prefix ys0[i, :t0_i]
         (ys0 [N, t0_max], prefix_lens ints [N] or None = all t0_max) and generates until <eos> or max_new_tokens[i]
         tokens (ints [N] in [1, max_strlen - 1]; None: max_strlen - 1); a row that finishes takes the next item
@@ -842,6 +1004,9 @@ class KVDecoder:
         <eos> when every item produced one -- and record = dict(steps: shared steps until the last item was done,
         launched: step units issued (the host looks at ONE device word, n_harvested, every check_every steps and
         nothing else), row_of [N], start_step [N], out_len [N] generated tokens with the <eos>, harvested).
+        return_logp=True: returns (ys, record, token_logp, logp) in item order -- token_logp [N, L] fp32 laid out like
+        ys, the model's log-probability of item i's generated tokens at columns t0_i .. t0_i + out_len_i - 1 and 0
+        elsewhere, logp [N] its row sum (generate()'s return_logp).
         ValueError before any device work for beam search, bad prefix_lens / max_new_tokens / sampling settings and
         lengths beyond the positional table or the cache rows of start_stream."""
         if algo not in ("greedy", "multinomial"):
@@ -893,6 +1058,9 @@ class KVDecoder:
         if filtered:
             mode = FILTERED
             self.filt.copy_(ops.sample_filter_settings(top_k, top_p, temperature, V))
+        self.want_logp = bool(return_logp)
+        if self.want_logp:
+            st["out_logp"].zero_()
         self.ragged = True
         self.pos.fill_(-1)                                         # the first step consumes every row's token 0
         self.row_off.zero_()
@@ -925,7 +1093,13 @@ class KVDecoder:
         if N and bool(is_eos.any(dim=1).all()):                    # generate()'s cut: the longest item's <eos>
             first = is_eos.int().argmax(dim=1)
             ys = ys[:, :t0 + int(first.max().item()) + 1]
-        return ys.clone(), record
+        if not self.want_logp:
+            return ys.clone(), record
+        # an item's generated span; a held row (capture warm-up, replay guard) decodes past its item's end meanwhile
+        t0_i, cols = lens.to(dev).view(-1, 1), torch.arange(ys.size(1), device=dev).view(1, -1)
+        span = (cols >= t0_i) & (cols < t0_i + out_len.to(dev).view(-1, 1))
+        token_logp = torch.where(span, st["out_logp"][:, :ys.size(1)], torch.zeros((), device=dev))
+        return ys.clone(), record, token_logp, token_logp.sum(1)
 
     def _run_step(self, mode, use_graphs):
         if not use_graphs:
@@ -934,6 +1108,8 @@ class KVDecoder:
         key = (mode, "mixed") if self.ragged else mode    # a mixed-prefix step passes row_off: a graph of its own
         if self.streaming:
             key = (mode, STREAM)                          # step + selection by item + refill
+        if self.want_logp and mode != BEAM:               # the unit holds one more kernel: a graph of its own
+            key = (key if isinstance(key, tuple) else (key, "uniform")) + (LOGP,)
         g = self.graphs.get(key)
         if g is False:                                  # no usable graph for these buffers (capture failed, or replay is
             self._advance(mode)                         # the slower launch mode on this box): same kernels, eagerly

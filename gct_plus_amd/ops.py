@@ -951,6 +951,62 @@ def select_token(logits2d, ys, pos, valid_u8, done_u8, mode, pad_id, eos_id, see
                                 _p(row_off), _p(filt_dev), _p(item), _p(prefix_len), item_base, _st()), "gct_select_token")
 
 
+def seq_logp(logits2d, ys, prefix_lens=None, pad_id=1, row_shift=0, rows_per_seq=None, V=None, out=None):
+    """gct_seq_logp (decode.score_reference states the rule): ys int64 [n, W] full token rows, logits2d fp32
+    [n * rows_per_seq, V] with unit column stride (a strided view is fine: ld = its row stride); the logits row of token
+    column c of sequence r is r * rows_per_seq + row_shift + c - 1 (rows_per_seq defaults to W - 1).  prefix_lens int32
+    [n] on the device or None (every row: 1).  logits2d None (with V given) passes a null pointer: the library refuses.
+    Returns (token_logp [n, W] fp32, logp [n] fp32, tokens [n] int32, hits [n] int32), or fills `out`, a tuple of them."""
+    _chk(ys, "seq_logp.ys", torch.int64)
+    if ys.dim() != 2 or ys.stride(1) != 1:
+        raise ValueError("seq_logp: ys must be [n, W] with unit column stride")
+    n, W = ys.shape
+    R = W - 1 if rows_per_seq is None else int(rows_per_seq)
+    ld = 0
+    if logits2d is not None:
+        _chk(logits2d, "seq_logp.logits")
+        if logits2d.dim() != 2 or logits2d.stride(1) != 1 or logits2d.shape[0] < n * R:
+            raise ValueError(f"seq_logp: logits must be [>= {n * R}, V] with unit column stride, got "
+                             f"{list(logits2d.shape)}")
+        V, ld = logits2d.shape[1], logits2d.stride(0)
+    if prefix_lens is not None:
+        _check_row_off(prefix_lens, n)
+    dev = ys.device
+    if out is None:
+        out = (torch.empty(n, W, device=dev), torch.empty(n, device=dev),
+               torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+    tl, lp, nt, nh = out
+    _chk(tl, "seq_logp.token_logp"), _chk(lp, "seq_logp.logp")
+    _chk(nt, "seq_logp.tokens", torch.int32), _chk(nh, "seq_logp.hits", torch.int32)
+    if tl.shape != (n, W) or tl.stride(1) != 1 or any(t.numel() != n or not t.is_contiguous() for t in (lp, nt, nh)):
+        raise ValueError("seq_logp: out must be (token_logp [n, W], logp [n], tokens [n], hits [n])")
+    check(_L().gct_seq_logp(_p(logits2d), ld, int(V), R, int(row_shift), _p(ys), ys.stride(0), _p(prefix_lens),
+                            int(pad_id), n, W, _p(tl), tl.stride(0), _p(lp), _p(nt), _p(nh), _st()), "gct_seq_logp")
+    return out
+
+
+def chosen_logp(logits2d, ys, pos_dev, out, pad_id, row_off=None, item=None, prefix_len=None):
+    """gct_chosen_logp, after select_token on the same logits [n, V] and device counter: out[dst, p] = the model's
+    log-probability (raw logits, temperature 1) of the token ys[r, p] the selection has just written at
+    p = *pos_dev - row_off[r] + 1, 0 for pad.  item / prefix_len as in select_token: dst = item[r], nothing written for a
+    parked row or a prefix token; otherwise dst = r.  out fp32 [rows, >= width], unit column stride."""
+    n, V = logits2d.shape
+    _chk(logits2d, "chosen_logp.logits"), _chk(out, "chosen_logp.out"), _chk(ys, "chosen_logp.ys", torch.int64)
+    _chk(pos_dev, "chosen_logp.pos", torch.int32)
+    if not logits2d.is_contiguous() or out.dim() != 2 or out.stride(1) != 1 or ys.stride(1) != 1:
+        raise ValueError("chosen_logp: contiguous logits and unit column strides of ys / out")
+    _check_row_off(row_off, n)
+    if (item is None) != (prefix_len is None):
+        raise ValueError("item and prefix_len go together")
+    if item is not None:
+        _check_row_off(item, n)
+        if row_off is None or prefix_len.dtype != torch.int32 or not prefix_len.is_contiguous():
+            raise ValueError("streamed rows need row_off and a contiguous int32 prefix_len")
+    check(_L().gct_chosen_logp(_p(logits2d), V, _p(ys), ys.stride(0), _p(pos_dev), _p(row_off), _p(item),
+                               _p(prefix_len), int(pad_id), _p(out), out.stride(0), out.shape[0], n, _st()),
+          "gct_chosen_logp")
+
+
 STREAM_MAX_ROWS, STREAM_MAX_LAYERS = 8192, 16   # GCT_STREAM_MAX_ROWS / GCT_STREAM_MAX_LAYERS (include/gctplus_hip.h)
 
 

@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 20
+#define GCT_ABI_VERSION 21
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -335,6 +335,32 @@ int gct_ce_fwd(const float* logits, const int64_t* target, float* out, float* ws
 /* dlogits = g*(softmax - onehot) on non-pad rows, 0 on pad rows; g = gout[0] (device). */
 int gct_ce_bwd(const float* logits, const int64_t* target, const float* gout, float* dlogits,
                int64_t rows, int V, int64_t pad_id, void* stream);
+/* Log-likelihoods of token rows (gct_plus_amd/decode.py score_reference states the rule), teacher-forced form.
+ * ys [n][ld_ys] int64 holds full rows of W tokens: prefix, tokens, pad.  The logits row of token column c (c >= 1) of
+ * sequence r is logits + (r * rows_per_seq + row_shift + c - 1) * ld, V floats (ld >= V: strided views; row_shift: the
+ * condition rows a use_cond2dec decoder puts in front).  Column c is SCORED when c >= prefix_lens[r] (int32 [n],
+ * 1 .. W; NULL: 1) and ys[r][c] != pad_id; the host validates 0 <= ys < V (an id outside counts as not scored).
+ *   token_logp [n][ld_out]: x[t] - m - log(sum exp(x - m)) in fp32 at scored columns (m the row maximum), 0 elsewhere;
+ *                           all W columns are written, and the logits rows of columns that are not scored are not read
+ *   logp [n]:   the sum of the scored columns in ascending column order
+ *   tokens [n]: the number of scored columns;  hits [n]: those whose token is the FIRST maximum of its logits row.
+ * One workgroup per sequence, no atomics: bit-reproducible.  1 <= W <= 256, ld_ys >= W, ld_out >= W,
+ * rows_per_seq >= row_shift + W - 1; otherwise GCT_ERR_ARG. */
+int gct_seq_logp(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift, const int64_t* ys,
+                 int64_t ld_ys, const int32_t* prefix_lens, int64_t pad_id, int n, int W, float* token_logp,
+                 int64_t ld_out, float* logp, int32_t* tokens, int32_t* hits, void* stream);
+/* The decode-step form: launched after gct_select_token in the step unit, on the same logits [n][V] and the same
+ * device counter.  Row r looks at column p = *pos - row_off[r] + 1 (row_off nullable), the column the selection has
+ * just written, takes tok = ys[r][p] and writes out[dst][p] = log-softmax(logits[r])[tok], or 0 when tok == pad_id (a
+ * finished row).  The log-probability is always the MODEL's own: it is taken from the raw logits at temperature 1,
+ * whatever top-k / nucleus / temperature filter the draw went through.
+ * item / prefix_len (both or neither, with row_off; continuous batching as in gct_select_token): dst = item[r], and the
+ * row writes nothing when item[r] < 0 (parked) or p < prefix_len[item[r]] (a prefix token is not a generated one) --
+ * so the call goes BEFORE gct_stream_refill, which reassigns item[r].  Without them dst = r.  Nothing is written when
+ * p is outside [0, ld_out) or dst >= out_rows.  out [out_rows][ld_out]. */
+int gct_chosen_logp(const float* logits, int V, const int64_t* ys, int64_t ld_ys, const int32_t* pos,
+                    const int32_t* row_off, const int32_t* item, const int32_t* prefix_len, int64_t pad_id, float* out,
+                    int64_t ld_out, int out_rows, int n, void* stream);
 
 /* -------------------------------------------------------------- K8: Adam step */
 /* torch.optim.Adam semantics (train1.py:116-119; no weight decay, no amsgrad):
