@@ -28,6 +28,11 @@ Log-likelihoods: `score` / `score_smiles` give log p(x | z, conditions, scaffold
 `decode`, `sample_smiles` and `sample_multiple_smiles` return the model's log-probability of what they drew as one more
 element (KVDecoder.generate(return_logp=True): no second forward).
 
+`well_formed=True` (optional): greedy / multinomial decodes are constrained by decode.SmilesGrammar built from the target
+vocabulary -- every returned string has balanced branches, paired ring-closure numbers, no dangling bond, and ended
+with <eos> inside max_strlen.  Syntax only: no valence or aromaticity check.  Not with beam search: the constructor
+refuses decode_algo="beam", and `decode_beams` of such a sampler raises.
+
 `stream_rows=R` (optional): greedy / multinomial decodes run with continuous batching (KVDecoder.generate_stream) -- the
 n rows of a call are a pool that R decode rows work through, a row whose molecule reached <eos> taking the next one, so
 `sample_smiles(30000)` is one call that never computes past a molecule's end.  Every decode of such a sampler goes that
@@ -42,7 +47,7 @@ import torch
 
 from ..Model.modules import get_src_mask
 from ..data import Vocab, tokenize
-from ..decode import (BEAM_ALPHA, KVDecoder, check_beam_size, check_sample_filter, check_stream_model,
+from ..decode import (BEAM_ALPHA, KVDecoder, SmilesGrammar, check_beam_size, check_sample_filter, check_stream_model,
                       check_stream_rows, generated_tokens, score_tokens)
 
 
@@ -123,8 +128,14 @@ class Sampling:
                  cond_dim: int = 0, decode_algo: str = "greedy", toklen_data: Optional[Sequence[int]] = None,
                  scaler=None, device="cuda", seed: int = 0, use_graphs: bool = False, beam_size: int = 4,
                  beam_alpha: float = BEAM_ALPHA, top_k: Optional[int] = None, top_p: Optional[float] = None,
-                 temperature: float = 1.0, stream_rows: Optional[int] = None, with_logp: bool = False):
+                 temperature: float = 1.0, stream_rows: Optional[int] = None, with_logp: bool = False,
+                 well_formed: bool = False):
         V = model.out.weight.shape[0]
+        if well_formed and decode_algo == "beam":
+            raise ValueError("well_formed is not supported with decode_algo='beam' (beam rows keep their history behind "
+                             "the ancestry map)")
+        # constrained decoding: the grammar over the target vocabulary, passed to every decode
+        self.grammar = SmilesGrammar(TRG.itos, TRG.stoi["<pad>"], TRG.stoi["<eos>"]) if well_formed else None
         if with_logp and decode_algo == "beam":
             raise ValueError("with_logp is not supported with decode_algo='beam': decode_beams returns the beams' "
                              "scores, which are sums of log-probabilities already")
@@ -210,13 +221,15 @@ class Sampling:
             self.kv.start_stream(zs, src_mask, dconds, rows=self.stream_rows, max_total_len=min(200, total))
             out = self.kv.generate_stream(ys, self.max_strlen, algo=self.decode_algo, seed=self.seed,
                                           use_graphs=self.use_graphs, prefix_lens=prefix_lens, top_k=self.top_k,
-                                          top_p=self.top_p, temperature=self.temperature, return_logp=self.with_logp)
+                                          top_p=self.top_p, temperature=self.temperature, return_logp=self.with_logp,
+                                          grammar=self.grammar)
             return (out[0], out[3].cpu()) if self.with_logp else out[0]
         # the positional table has 200 rows, of which use_cond2dec spends n_c on the condition tokens
         self.kv.start(zs, src_mask, dconds, max_total_len=min(200 - self.kv.off, total))
         out = self.kv.generate(ys, self.max_strlen, algo=self.decode_algo, seed=self.seed,
                                use_graphs=self.use_graphs, prefix_lens=prefix_lens, top_k=self.top_k,
-                               top_p=self.top_p, temperature=self.temperature, return_logp=self.with_logp)
+                               top_p=self.top_p, temperature=self.temperature, return_logp=self.with_logp,
+                               grammar=self.grammar)
         return (out[0], out[2].cpu()) if self.with_logp else out
 
     @torch.no_grad()
@@ -258,6 +271,8 @@ class Sampling:
     def decode_beams(self, zs, ys, src_mask, dconds=None, beam_size=None, alpha=None):
         """Beam search: (ids [n, k, L], scores [n, k] sums of log-probabilities, lengths [n, k]), beams sorted by
         score / length**alpha (KVDecoder.generate_beam).  beam_size / alpha default to the constructor's."""
+        if self.grammar is not None:
+            raise ValueError("decode_beams: beam search takes no grammar, and this sampler was built with well_formed=True")
         k = self.beam_size if beam_size is None else beam_size
         check_beam_size(k, self.model.out.weight.shape[0])
         zs, ys, src_mask = zs.to(self.device), ys.to(self.device), src_mask.to(self.device)

@@ -4,6 +4,8 @@
 //   gct_select_token : softmax over the vocabulary + greedy / multinomial choice (optionally through a top-k /
 //                      nucleus / temperature filter), appends the token, updates the key-valid flags and the
 //                      per-sample finished mask
+//   gct_grammar_mask : constrained decoding -- a copy of the step's logits with -inf on every token the SMILES grammar
+//                      or the row's length budget forbids, for gct_select_token to choose from
 //   gct_stream_refill : continuous batching -- rows that finished hand out their tokens and take the next pool item
 //   gct_attn_decode_beam / gct_beam_select : the same two for beam search, with the self-attention caches
 //                      shared by ancestry through a per-row map (kv_src) instead of copied
@@ -321,11 +323,12 @@ __global__ __launch_bounds__(256) void select_token_kernel(const float* __restri
     const uint4 r = gct_philox(rng, key, (uint32_t)pos, 0x452821E6u, 0x38D01377u);
     const float u = u01_open(r.x);
     float cum = 0.f;
-    int pick = V - 1;
+    int pick = V - 1, lastnz = -1;
     bool found = false;
     for (int c0 = 0; c0 < V; c0 += 64) {
       const int c = c0 + lane;
       float p = c < V ? expf(lr[c] - mx) * inv : 0.f;
+      if (p > 0.f) lastnz = c;
       if (probs_out && c < V) probs_out[(int64_t)row * V + c] = p;
       float incl = p;                                   // inclusive scan over the wave
 #pragma unroll
@@ -333,13 +336,22 @@ __global__ __launch_bounds__(256) void select_token_kernel(const float* __restri
         const float t = __shfl_up(incl, off, 64);
         if (lane >= off) incl += t;
       }
-      const bool hit = !found && c < V && (cum + incl) > u;
+      // (p > 0: the wave scan is not monotone in fp32 -- a lane of probability exactly 0, a token the grammar mask
+      // forbids, may hold a prefix sum one ulp above its left neighbour's -- so such a lane never takes the hit)
+      const bool hit = !found && c < V && (cum + incl) > u && p > 0.f;
       const unsigned long long ball = __ballot(hit);
       if (ball && !found) {
         pick = c0 + (int)__builtin_ctzll(ball);
         found = true;
       }
       cum += __shfl(incl, 63, 64);
+    }
+    if (!found) {
+      // rounding fallback (the sum stayed below u): the last token of nonzero probability -- V - 1, unless its logit is
+      // -inf (a token the grammar mask forbids) or underflows
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) lastnz = max(lastnz, __shfl_xor(lastnz, off, 64));
+      if (lastnz >= 0) pick = lastnz;
     }
     best = pick;
   }
@@ -425,9 +437,9 @@ __global__ __launch_bounds__(256) void select_token_filtered_kernel(
     }
 #pragma unroll
     for (int t = 0; t < TPL; ++t)
-      if (lane + 64 * t < V && cnt[t] >= top_k) {
-        w[t] = 1e-6f;                                       // the reference's floor (torch.multinomial renormalises)
-        changed = true;
+      if (lane + 64 * t < V && cnt[t] >= top_k && x[t] != -INFINITY) {   // (a -inf logit, a token the grammar mask
+        w[t] = 1e-6f;                                       // forbids, keeps the weight 0: it never gets the floor)
+        changed = true;                                     // the reference's floor (torch.multinomial renormalises)
       }
   }
   if (top_p < 1.f) {                                        // nucleus over s = w / sum w: kept iff the mass of the
@@ -474,21 +486,20 @@ __global__ __launch_bounds__(256) void select_token_filtered_kernel(
   const uint4 r = gct_philox(rng, key, (uint32_t)pos, 0x452821E6u, 0x38D01377u);
   float u = u01_open(r.x);
   float pscale = 1.f;
-  int pick = V - 1;
+  int pick = V - 1, last = -1;
+#pragma unroll
+  for (int t = 0; t < TPL; ++t)
+    if (w[t] > 0.f) last = lane + 64 * t;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) last = max(last, __shfl_xor(last, off, 64));
+  if (last >= 0) pick = last;                               // rounding fallback: the last token of nonzero weight
   if (changed) {                                            // draw c with probability w_c / sum w
     float sw = 0.f;
-    int last = -1;
 #pragma unroll
-    for (int t = 0; t < TPL; ++t) {
-      sw += w[t];
-      if (w[t] > 0.f) last = lane + 64 * t;
-    }
+    for (int t = 0; t < TPL; ++t) sw += w[t];
     sw = gct_wave_sum(sw);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) last = max(last, __shfl_xor(last, off, 64));
     u *= sw;
     pscale = 1.0f / sw;
-    if (last >= 0) pick = last;                             // rounding fallback: the last token of nonzero weight
   }
   float cum = 0.f;
   bool found = false;
@@ -504,7 +515,7 @@ __global__ __launch_bounds__(256) void select_token_filtered_kernel(
       const float tt = __shfl_up(incl, off, 64);
       if (lane >= off) incl += tt;
     }
-    const bool hit = !found && c < V && (cum + incl) > u && (!changed || p > 0.f);
+    const bool hit = !found && c < V && (cum + incl) > u && p > 0.f;   // (a token of weight 0 is never drawn)
     const unsigned long long ball = __ballot(hit);
     if (ball && !found) {
       pick = 64 * t + (int)__builtin_ctzll(ball);
@@ -516,6 +527,162 @@ __global__ __launch_bounds__(256) void select_token_filtered_kernel(
     ys[(int64_t)row * ld_ys + pos] = pick;
     if (valid) valid[(int64_t)row * valid_sb + valid_off + pos] = (pick != pad_id) ? 1 : 0;
     if (done && pick == eos_id) done[row] = 1;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- grammar mask
+// States of the SMILES grammar (decode.py SmilesGrammar is the statement; the classes are GCT_GRAMMAR_*).
+enum { GP_START = 0, GP_ATOM, GP_RING, GP_BOND_A, GP_BOND_B, GP_OPEN, GP_CLOSE, GP_DOT, GP_END };
+
+// May a row in state (prev, depth, open, here) take a token of class cls (ring number r) when `left` slots remain behind
+// it?  The transition must exist and min_finish(state') <= left, with the closed form of min_finish.
+__device__ __forceinline__ bool grammar_allows(int prev, int depth, uint64_t open, uint64_t here, int cls, int r,
+                                               int left) {
+  if (prev == GP_END || left < 0) return cls == GCT_GRAMMAR_PAD;          // finished, or past the budget: pad only
+  const bool ar = prev == GP_ATOM || prev == GP_RING, arc = ar || prev == GP_CLOSE;
+  int np;
+  switch (cls) {
+    case GCT_GRAMMAR_ATOM:
+      np = GP_ATOM;
+      here = 0;
+      break;
+    case GCT_GRAMMAR_BOND:
+      if (ar) np = GP_BOND_A;
+      else if (prev == GP_OPEN || prev == GP_CLOSE) np = GP_BOND_B;
+      else return false;
+      break;
+    case GCT_GRAMMAR_OPEN:
+      if (!arc) return false;
+      np = GP_OPEN;
+      ++depth;
+      break;
+    case GCT_GRAMMAR_CLOSE:
+      if (!arc || depth <= 0) return false;
+      np = GP_CLOSE;
+      --depth;
+      break;
+    case GCT_GRAMMAR_RING: {
+      if (!(ar || prev == GP_BOND_A)) return false;
+      const uint64_t bit = 1ull << (r & 63);
+      if (open & bit) {
+        if (here & bit) return false;                       // a ring does not close on the atom that opened it
+        open ^= bit;
+      } else {
+        open |= bit;
+        here |= bit;
+      }
+      np = GP_RING;
+      break;
+    }
+    case GCT_GRAMMAR_DOT:
+      if (!arc || depth != 0) return false;
+      np = GP_DOT;
+      break;
+    case GCT_GRAMMAR_EOS:
+      return arc && depth == 0 && open == 0;                // min_finish(END) = 0 <= left
+    default:
+      return false;
+  }
+  const bool oh = (open & here) != 0;
+  int a;
+  if (np == GP_BOND_B || np == GP_OPEN || np == GP_DOT) a = 1;
+  else if (np == GP_CLOSE) a = open != 0;
+  else if (np == GP_BOND_A) a = open == 0 || oh;
+  else a = oh;                                              // ATOM, RING
+  return depth + __popcll(open) + 1 + a <= left;
+}
+
+__device__ __forceinline__ uint64_t wave_or64(uint64_t v, bool use_xor) {
+  uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t ol = (uint32_t)__shfl_xor((int)lo, off, 64), oh = (uint32_t)__shfl_xor((int)hi, off, 64);
+    lo = use_xor ? lo ^ ol : lo | ol;
+    hi = use_xor ? hi ^ oh : hi | oh;
+  }
+  return ((uint64_t)hi << 32) | lo;
+}
+
+__device__ __forceinline__ int wave_sum_i32(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// One wave per row, stateless: the row's generated tokens ys[r][t0, p) -- at most 199 under the 200-row positional table,
+// 255 at T = 256; lane l holds tokens l + 64 t, four per lane --
+// are classified through the table and reduced to the grammar state; then lane l masks tokens l, l + 64, ... of the row's
+// logits.  depth = #OPEN - #CLOSE; every RING token toggles its bit, so open = the xor of the ring bits; a ring is in
+// `here` iff it appears behind the last ATOM and is open now (its last toggle there was the opening one: closing it
+// again on the same atom is what the grammar forbids), so here = open & (or of the ring bits behind the last ATOM).
+__global__ __launch_bounds__(256) void grammar_mask_kernel(
+    const float* __restrict__ logits, float* __restrict__ masked, int V, const int32_t* __restrict__ table,
+    const int64_t* __restrict__ ys, int64_t ld_ys, int T, int n, const int32_t* __restrict__ pos_dev,
+    const int32_t* __restrict__ row_off, const int32_t* __restrict__ gram, const int32_t* __restrict__ item,
+    const int32_t* __restrict__ prefix_len, const int32_t* __restrict__ limit) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= n) return;
+  int p = *pos_dev + 1;                                     // the column the selection behind this launch writes
+  const int ro = row_off ? row_off[row] : 0;
+  p -= ro;
+  int t0, G;
+  if (item) {                                               // uniform over the wave: a whole wave leaves
+    const int it = item[row];
+    if (it < 0) return;                                     // parked
+    t0 = prefix_len[it];
+    G = limit[it];
+  } else {
+    G = gram[0];
+    t0 = gram[1] - ro;
+  }
+  const int g = p - t0;                                     // tokens generated so far
+  if (g < 0 || t0 < 0 || p >= T) return;                    // inside the prefix / no such column: 0 <= t0 <= p < T <= 256
+  const int64_t* yr = ys + (int64_t)row * ld_ys + t0;
+  auto entry = [&](int j) -> int {
+    const int64_t tok = yr[j];
+    return tok >= 0 && tok < V ? table[tok] : GCT_GRAMMAR_BANNED;
+  };
+  int e[4];
+  int net = 0, last_atom = -1;
+  uint64_t tog = 0;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int j = lane + 64 * t;
+    e[t] = j < g ? entry(j) : GCT_GRAMMAR_BANNED;
+    const int cls = e[t] & 0xFF;
+    net += (cls == GCT_GRAMMAR_OPEN) - (cls == GCT_GRAMMAR_CLOSE);
+    if (cls == GCT_GRAMMAR_RING) tog ^= 1ull << ((e[t] >> 8) & 63);
+    if (cls == GCT_GRAMMAR_ATOM) last_atom = j;
+  }
+  const int depth = wave_sum_i32(net);
+  const uint64_t open = wave_or64(tog, true);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) last_atom = max(last_atom, __shfl_xor(last_atom, off, 64));
+  uint64_t behind = 0;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+    if ((e[t] & 0xFF) == GCT_GRAMMAR_RING && lane + 64 * t > last_atom) behind |= 1ull << ((e[t] >> 8) & 63);
+  const uint64_t here = open & wave_or64(behind, false);
+  int prev = GP_START;
+  if (g > 0) {
+    const int c1 = entry(g - 1) & 0xFF, c2 = g > 1 ? entry(g - 2) & 0xFF : GCT_GRAMMAR_BANNED;
+    switch (c1) {
+      case GCT_GRAMMAR_ATOM: prev = GP_ATOM; break;
+      case GCT_GRAMMAR_RING: prev = GP_RING; break;
+      case GCT_GRAMMAR_BOND: prev = c2 == GCT_GRAMMAR_ATOM || c2 == GCT_GRAMMAR_RING ? GP_BOND_A : GP_BOND_B; break;
+      case GCT_GRAMMAR_OPEN: prev = GP_OPEN; break;
+      case GCT_GRAMMAR_CLOSE: prev = GP_CLOSE; break;
+      case GCT_GRAMMAR_DOT: prev = GP_DOT; break;
+      default: prev = GP_END; break;                        // <eos>, <pad> behind it (or a token no constrained row wrote)
+    }
+  }
+  const int left = G - g - 1;
+  const float* lr = logits + (int64_t)row * V;
+  float* mr = masked + (int64_t)row * V;
+  for (int c = lane; c < V; c += 64) {
+    const int en = table[c];
+    mr[c] = grammar_allows(prev, depth, open, here, en & 0xFF, (en >> 8) & 63, left) ? lr[c] : -INFINITY;
   }
 }
 
@@ -924,6 +1091,23 @@ extern "C" int gct_select_token(const float* logits, int V, int64_t* ys, int64_t
                        done, probs_out, n, mode, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, nullptr, nullptr,
                        nullptr, 0);
   GCT_LAUNCH_CHECK("select_token");
+  return GCT_OK;
+}
+
+extern "C" int gct_grammar_mask(const float* logits, float* masked, int V, const int32_t* table, const int64_t* ys,
+                                int64_t ld_ys, int T, int n, const int32_t* pos, const int32_t* row_off,
+                                const int32_t* gram, const int32_t* item, const int32_t* prefix_len,
+                                const int32_t* limit, void* stream) {
+  GCT_CHECK_ARG(logits && masked && logits != masked && table && ys && pos && V > 0 && n >= 0, "grammar_mask: bad args");
+  GCT_CHECK_ARG(T >= 1 && T <= 256 && ld_ys >= T, "grammar_mask: %d token columns (1 .. 256) in rows of %lld", T,
+                (long long)ld_ys);
+  GCT_CHECK_ARG(!item == !prefix_len && !item == !limit && (!item || row_off),
+                "grammar_mask: streamed rows need item, prefix_len, limit and row_off");
+  GCT_CHECK_ARG(item || gram, "grammar_mask: no budget (gram, or the stream's limit)");
+  if (n == 0) return GCT_OK;
+  hipLaunchKernelGGL(grammar_mask_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits,
+                     masked, V, table, ys, ld_ys, T, n, pos, row_off, gram, item, prefix_len, limit);
+  GCT_LAUNCH_CHECK("grammar_mask");
   return GCT_OK;
 }
 

@@ -48,6 +48,13 @@ Log-likelihoods: the rule is stated once, in `score_reference`.  `score_tokens` 
 one decoder forward over the rows up to each sequence's last scored token, then gct_seq_logp on the logits; and
 `generate` / `generate_stream(return_logp=True)` return the log-probability of every token they pick: gct_chosen_logp
 reads the step's logits right behind the selection, so a sampling run needs no second forward to know its likelihood.
+
+Grammar-constrained decoding (`generate` / `generate_stream(grammar=SmilesGrammar(...))`): the rules are stated once, in
+`SmilesGrammar` (grammar_step, grammar_min_finish).  gct_grammar_mask runs in front of the selection: one wave per row
+re-derives the row's grammar state from the tokens it has generated (nothing to save for graph capture, nothing to reset
+at a stream refill) and writes a copy of the logits with -inf on every token that has no transition or would leave the
+row unable to reach <eos> inside its length budget, which it reads from device memory.  Every row then ends with <eos>
+and parses.  The guarantee is syntactic only: valence, aromaticity and ring-bond consistency need a chemistry toolkit.
 """
 from __future__ import annotations
 
@@ -81,6 +88,7 @@ BEAM = "beam"                                       # selection mode key of the 
 FILTERED = "filtered"                               # selection mode key of the filtered multinomial draw
 STREAM = "stream"                                   # graph key suffix of the continuous-batching step unit
 LOGP = "logp"                                       # graph key suffix of a step unit that records log-probabilities
+GRAMMAR = "grammar"                                 # graph key suffix of a step unit that masks the logits by a grammar
 STREAM_COND_CHUNK = 256                             # items per GEMM when the pool's condition rows are projected
 TOP_K_FLOOR = 1e-6                                  # weight of a token outside the top k (the reference's top_k_logits)
 
@@ -113,7 +121,8 @@ def sample_filter_reference(logits, top_k=None, top_p=None, temperature=1.0):
       1. p = softmax(x / T) in fp32;
       2. top_k: token c is in when fewer than k tokens have a strictly larger LOGIT (ties at the k-th value stay in, the
          reference's p_c >= v_k); an out token gets the weight TOP_K_FLOOR = 1e-6, as the reference's top_k_logits gives
-         it before torch.multinomial renormalises; k = V is a no-op;
+         it before torch.multinomial renormalises; k = V is a no-op; a token whose logit is -inf (one a grammar mask
+         forbids) has the weight 0 at every stage and never gets the floor;
       3. top_p (nucleus) on s = w / sum w, w the result of 2: token c is kept when the mass of the tokens with a strictly
          larger s is < top_p (every token tied at the boundary is kept), otherwise its weight is 0; top_p = 1 is a no-op;
       4. the draw picks c with probability w_c / sum w (returned).  The top token is always kept, so greedy ignores all
@@ -125,7 +134,7 @@ def sample_filter_reference(logits, top_k=None, top_p=None, temperature=1.0):
     if top_k is not None and top_k < V:
         asc = x.sort(-1).values
         larger = V - torch.searchsorted(asc, x.contiguous(), right=True)           # tokens with a strictly larger logit
-        w = torch.where(larger < top_k, w, torch.full_like(w, TOP_K_FLOOR))
+        w = torch.where((larger < top_k) | (x == -math.inf), w, torch.full_like(w, TOP_K_FLOOR))
     if top_p is not None and top_p < 1:
         s = w / w.sum(-1, keepdim=True)
         asc = s.sort(-1).values
@@ -134,6 +143,211 @@ def sample_filter_reference(logits, top_k=None, top_p=None, temperature=1.0):
         mass = torch.where(larger > 0, top_mass.gather(-1, (larger - 1).clamp(min=0)), torch.zeros_like(top_mass))
         w = torch.where(mass < float(top_p), w, torch.zeros_like(w))
     return w / w.sum(-1, keepdim=True)
+
+
+# ------------------------------------------------------------------------------------- grammar-constrained decoding
+# states `prev` of the grammar: what the last generated token was
+(G_START, G_ATOM, G_RING, G_BOND_A, G_BOND_B, G_OPEN, G_CLOSE, G_DOT, G_END) = range(9)
+GRAMMAR_START = (G_START, 0, 0, 0)                 # (prev, depth, open, here) before the first generated token
+_ATOMS = frozenset("B Br C Cl N O S P F I b c n o s p *".split())
+_BONDS = frozenset("= # - / \\ : ~ $".split())
+
+
+def grammar_class(token):
+    """(class, ring number) of a vocabulary string (ops.GRAMMAR_*): ATOM any [...] token and the organic subset, BOND,
+    OPEN / CLOSE, RING a digit or %NN (ring NN; 64 and above BANNED), DOT; everything else BANNED (<eos> and <pad> are
+    assigned by id, SmilesGrammar)."""
+    t = str(token)
+    if (len(t) >= 3 and t[0] == "[" and t[-1] == "]") or t in _ATOMS:
+        return ops.GRAMMAR_ATOM, 0
+    if t in _BONDS:
+        return ops.GRAMMAR_BOND, 0
+    if t == "(":
+        return ops.GRAMMAR_OPEN, 0
+    if t == ")":
+        return ops.GRAMMAR_CLOSE, 0
+    if t == ".":
+        return ops.GRAMMAR_DOT, 0
+    r = None
+    if len(t) == 1 and t in "0123456789":
+        r = int(t)
+    elif len(t) == 3 and t[0] == "%" and t[1] in "0123456789" and t[2] in "0123456789":
+        r = int(t[1:])
+    if r is not None and r < ops.GRAMMAR_MAX_RINGS:
+        return ops.GRAMMAR_RING, r
+    return ops.GRAMMAR_BANNED, 0
+
+
+def grammar_step(state, cls, ring=0):
+    """The state after a token of class cls (ring number `ring`) in `state` = (prev, depth, open, here), or None when the
+    grammar has no such transition.  THE statement of the transitions (gct_grammar_mask implements them):
+      ATOM   from any state but END; here = {}
+      BOND   from ATOM / RING (-> BOND_A) and from OPEN / CLOSE (-> BOND_B)
+      OPEN   from ATOM / RING / CLOSE; depth + 1          CLOSE  from ATOM / RING / CLOSE when depth > 0; depth - 1
+      RING r from ATOM / RING / BOND_A: r open -> closes it, unless r is in here (a ring does not close on the atom that
+             opened it); otherwise opens it, r joins open and here
+      DOT    from ATOM / RING / CLOSE when depth == 0
+      EOS    from ATOM / RING / CLOSE when depth == 0 and no ring is open -> END;      from END only PAD."""
+    prev, depth, open_, here = state
+    if prev == G_END:
+        return state if cls == ops.GRAMMAR_PAD else None
+    ar = prev in (G_ATOM, G_RING)
+    arc = ar or prev == G_CLOSE
+    if cls == ops.GRAMMAR_ATOM:
+        return G_ATOM, depth, open_, 0
+    if cls == ops.GRAMMAR_BOND:
+        if ar:
+            return G_BOND_A, depth, open_, here
+        return (G_BOND_B, depth, open_, here) if prev in (G_OPEN, G_CLOSE) else None
+    if cls == ops.GRAMMAR_OPEN:
+        return (G_OPEN, depth + 1, open_, here) if arc else None
+    if cls == ops.GRAMMAR_CLOSE:
+        return (G_CLOSE, depth - 1, open_, here) if arc and depth > 0 else None
+    if cls == ops.GRAMMAR_RING:
+        if not (ar or prev == G_BOND_A):
+            return None
+        bit = 1 << int(ring)
+        if open_ & bit:
+            return None if here & bit else (G_RING, depth, open_ ^ bit, here)
+        return G_RING, depth, open_ | bit, here | bit
+    if cls == ops.GRAMMAR_DOT:
+        return (G_DOT, depth, open_, here) if arc and depth == 0 else None
+    if cls == ops.GRAMMAR_EOS:
+        return (G_END, 0, 0, 0) if arc and depth == 0 and open_ == 0 else None
+    return None
+
+
+def grammar_min_finish(state):
+    """Length of the shortest allowed continuation of `state` that ends with <eos> (closed form; the host test checks it
+    against a breadth-first search): 0 at END, otherwise depth + popcount(open) + 1 + a, where a = 1 when an atom has to
+    come first -- after START / BOND_B / OPEN / DOT, after CLOSE with a ring open, after BOND_A with no ring open or one
+    opened on this atom, after ATOM / RING with a ring opened on this atom."""
+    prev, depth, open_, here = state
+    if prev == G_END:
+        return 0
+    if prev in (G_START, G_BOND_B, G_OPEN, G_DOT):
+        a = 1
+    elif prev == G_CLOSE:
+        a = int(open_ != 0)
+    elif prev == G_BOND_A:
+        a = int(open_ == 0 or (open_ & here) != 0)
+    else:
+        a = int((open_ & here) != 0)
+    return depth + bin(open_).count("1") + 1 + a
+
+
+def check_grammar(grammar, vocab, budget):
+    """grammar None, or a SmilesGrammar over `vocab` tokens with a budget (an int, or ints [n]) of at least 2 generated
+    tokens per row -- room for an atom and <eos>; ValueError otherwise."""
+    if grammar is None:
+        return
+    if not isinstance(grammar, SmilesGrammar):
+        raise ValueError(f"grammar must be a SmilesGrammar, got {type(grammar).__name__}")
+    if len(grammar) != int(vocab):
+        raise ValueError(f"the grammar classifies {len(grammar)} tokens, the model's vocabulary has {int(vocab)}")
+    least = int(torch.as_tensor(budget).min())
+    if least < 2:
+        raise ValueError(f"grammar-constrained decoding needs at least 2 generated tokens per row, got {least}")
+
+
+class SmilesGrammar:
+    """SMILES syntax over a target vocabulary, for constrained decoding (KVDecoder.generate / generate_stream(grammar=)).
+    The guarantee is SYNTACTIC: branches balance, ring-closure numbers pair up, bonds have an atom or a ring closure
+    behind them, and the row ends with <eos> inside its length budget.  Chemical validity (valence, aromaticity, a ring
+    bond doubling another, bond orders at the two ends of a ring closure) is not checked.
+    itos: the vocabulary's strings; token pad_id is PAD and token eos_id EOS whatever their strings, every other token is
+    classified by grammar_class, and OPEN is BANNED in a vocabulary without CLOSE.  ValueError for a vocabulary without
+    an ATOM token or without <eos> / <pad> ids inside it.
+    A row may generate G tokens.  Choosing its g-th one (g = len(tokens)), a token is ALLOWED iff its transition exists
+    (grammar_step) and grammar_min_finish(state') <= G - g - 1; a finished row and a row past its budget are allowed
+    <pad> only.  Because min_finish is exact, the allowed set is never empty for G >= 2, and every row reaches <eos>."""
+
+    def __init__(self, itos, pad_id, eos_id):
+        self.itos = [str(t) for t in itos]
+        V = len(self.itos)
+        self.pad_id, self.eos_id = int(pad_id), int(eos_id)
+        if not (0 <= self.eos_id < V and 0 <= self.pad_id < V and self.eos_id != self.pad_id):
+            raise ValueError(f"the vocabulary ({V} tokens) has no <eos> / <pad> at ids {eos_id} / {pad_id}")
+        entries = [grammar_class(t) for t in self.itos]
+        entries[self.pad_id], entries[self.eos_id] = (ops.GRAMMAR_PAD, 0), (ops.GRAMMAR_EOS, 0)
+        if not any(c == ops.GRAMMAR_CLOSE for c, _ in entries):
+            entries = [(ops.GRAMMAR_BANNED, 0) if c == ops.GRAMMAR_OPEN else (c, r) for c, r in entries]
+        if not any(c == ops.GRAMMAR_ATOM for c, _ in entries):
+            raise ValueError("the vocabulary has no atom token: no SMILES can be generated from it")
+        self.classes = [c for c, _ in entries]
+        self.rings = [r for _, r in entries]
+        self.table = torch.tensor([c | (r << 8) for c, r in entries], dtype=torch.int32)    # gct_grammar_mask's layout
+        self._groups = {}                                  # (class, ring) -> the ids that share it
+        for c, e in enumerate(entries):
+            self._groups.setdefault(e, []).append(c)
+        self._device_tables = {}
+
+    def __len__(self):
+        return len(self.itos)
+
+    def device_table(self, device):
+        """The class table on `device` (copied once)."""
+        key = str(torch.device(device))
+        if key not in self._device_tables:
+            self._device_tables[key] = self.table.to(device)
+        return self._device_tables[key]
+
+    def state(self, tokens):
+        """(prev, depth, open, here) after the generated token ids `tokens`; ValueError at a token the grammar forbids."""
+        st = GRAMMAR_START
+        for i, t in enumerate(tokens):
+            nxt = grammar_step(st, self.classes[int(t)], self.rings[int(t)])
+            if nxt is None:
+                raise ValueError(f"token {i} ({self.itos[int(t)]!r}) is not allowed after {[self.itos[int(x)] for x in tokens[:i]]}")
+            st = nxt
+        return st
+
+    def allowed(self, tokens, budget_left):
+        """Sorted ids the row may choose next: tokens = its generated ids so far, budget_left = G - len(tokens), the slots
+        it has left with this one.  THE reference for one row."""
+        st = self.state(list(tokens))
+        if st[0] == G_END or budget_left < 1:
+            return [self.pad_id]
+        out = []
+        for (cls, ring), members in self._groups.items():
+            nxt = grammar_step(st, cls, ring)
+            if nxt is not None and grammar_min_finish(nxt) <= budget_left - 1:
+                out += members
+        return sorted(out)
+
+    def mask_reference(self, logits, ys, starts, pos, G):
+        """THE reference for a batch (gct_grammar_mask implements it): logits [n, V]; row r has generated
+        ys[r, starts[r] : pos[r]] and chooses column pos[r] under the budget G[r] (starts / pos / G: ints or [n]).
+        Returns a copy of logits with -inf on every token that is not allowed; a row with pos[r] < starts[r] (still
+        inside its prefix) is returned as it is."""
+        n = logits.shape[0]
+        def per_row(v):
+            v = [int(x) for x in torch.as_tensor(v).view(-1).tolist()]
+            return v * n if len(v) == 1 else v
+        starts, pos, G = per_row(starts), per_row(pos), per_row(G)
+        out = logits.clone()
+        ys = torch.as_tensor(ys).cpu()
+        for r in range(n):
+            if pos[r] < starts[r]:
+                continue
+            hist = ys[r, starts[r]:pos[r]].tolist()
+            keep = torch.zeros(logits.shape[1], dtype=torch.bool)
+            keep[self.allowed(hist, G[r] - len(hist))] = True
+            out[r, ~keep.to(out.device)] = -math.inf
+        return out
+
+    def well_formed(self, tokens):
+        """The same rules for a whole generated sequence: every token up to the first <eos> has its transition, the
+        <eos> is there and allowed, and only <pad> follows it."""
+        st = GRAMMAR_START
+        for t in tokens:
+            t = int(t)
+            if not 0 <= t < len(self.itos):
+                return False
+            st = grammar_step(st, self.classes[t], self.rings[t])
+            if st is None:
+                return False
+        return st[0] == G_END
 
 
 # ------------------------------------------------------------------------------------------- log-likelihoods
@@ -464,6 +678,7 @@ class KVDecoder:
         self.stream = None                                # continuous batching: pool + StreamState (start_stream)
         self.streaming = False                            # a generate_stream loop is running (the step unit refills)
         self.want_logp = False                            # this generate records the log-probability of every pick
+        self.grammar = None                               # this generate chooses from the grammar-masked logits
 
     # -------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -551,6 +766,7 @@ class KVDecoder:
             self.ragged = False                                            # this decode passes row_off to the kernels
             self.seed = torch.zeros(1, dtype=torch.int64, device=dev)      # multinomial seed of this generate()
             self.filt = torch.zeros(4, dtype=torch.int32, device=dev)      # GctSampleFilter of this generate()
+            self.gram = self.gtable = None                                 # grammar buffers: the first _set_grammar
             # beam search state (generate_beam), per row: score, finished, length, parent; the ancestry map; done [n/k]
             self.beams = beams
             self.bscores = torch.zeros(n, device=dev)
@@ -752,14 +968,21 @@ class KVDecoder:
     def _select(self, mode):
         """softmax + choice of the next token from buf['logits']; written at ys[:, *pos + 1] (device position).
         mode BEAM: gct_beam_select (beam state, the kv_src map and bdone in place).  mode FILTERED: the multinomial draw
-        through the top-k / nucleus / temperature settings in self.filt."""
+        through the top-k / nucleus / temperature settings in self.filt.  With a grammar the choice is made from a masked
+        copy of the logits (gct_grammar_mask, one launch more); buf['logits'] stays raw for _chosen_logp."""
         if mode == BEAM:
             ops.beam_select(self.buf["logits"], self.beams, self.bscores, self.bfin, self.blen, self.ys, self.valid,
                             self.off, self.kv_src, self.bdone, self.pos, self.pad_id, self.eos_id,
                             parent_i32=self.bparent)
             return
         st = self.stream if self.streaming else None     # continuous batching: the rows' items and their prefix lengths
-        ops.select_token(self.buf["logits"], self.ys, 0, self.valid, self.done, 1 if mode == FILTERED else mode,
+        logits = self.buf["logits"]
+        if self.grammar is not None:                     # the selection sees -inf on what the grammar / the budget forbid
+            ops.grammar_mask(logits, self.buf["masked"], self.gtable, self.ys, self.pos, width=self.T - self.off,
+                             row_off=self.row_off if self.ragged else None, gram=self.gram, item=st and st["item"],
+                             prefix_len=st and st["prefix_len"], limit=st and st["limit"])
+            logits = self.buf["masked"]
+        ops.select_token(logits, self.ys, 0, self.valid, self.done, 1 if mode == FILTERED else mode,
                          self.pad_id, self.eos_id, pos_dev=self.pos, valid_off=self.off, seed_dev=self.seed,
                          row_off=self.row_off if self.ragged else None,
                          filt_dev=self.filt if mode == FILTERED else None,
@@ -775,6 +998,20 @@ class KVDecoder:
         if self.streaming:
             self.stream["state"].refill()
 
+    def _set_grammar(self, grammar, budget, t0):
+        """The grammar of this generate (None: unconstrained): its class table, the budget and the prefix width go to
+        the device buffers the captured graphs read -- (budget G, prefix width), the table and the masked copy of the
+        logits, allocated when a decoder's rows first see a grammar."""
+        self.grammar = grammar
+        if grammar is not None:
+            if self.gram is None:                        # first grammar on these rows (they live as long as the rows do,
+                dev, (n, V) = self.ys.device, self.buf["logits"].shape     # like the graphs captured against them)
+                self.gram = torch.zeros(2, dtype=torch.int32, device=dev)
+                self.gtable = torch.zeros(V, dtype=torch.int32, device=dev)
+                self.buf["masked"] = torch.empty(n, V, device=dev)
+            self.gtable.copy_(grammar.device_table(self.gtable.device))
+            self.gram.copy_(torch.tensor([int(budget), int(t0)], dtype=torch.int32))
+
     def _chosen_logp(self):
         """The model's log-probability of the token _select has just written (gct_chosen_logp): into tok_logp at the
         row's own column, or, streamed, into the pool's table at (item, column)."""
@@ -786,7 +1023,7 @@ class KVDecoder:
     # -------------------------------------------------------------------------------------
     @torch.no_grad()
     def generate(self, ys0, max_strlen=80, algo="greedy", seed=0, check_every=8, use_graphs=False, prefix_lens=None,
-                 top_k=None, top_p=None, temperature=1.0, return_logp=False):
+                 top_k=None, top_p=None, temperature=1.0, return_logp=False, grammar=None):
         """Mirror of Sampling.decode: appends max_strlen-1 tokens to the prefix ys0 [n, t0]
         (stops early once every sample has produced <eos>, like the reference's break).
         prefix_lens (ints [n], 1 <= t0_r <= t0, optional): row r's prefix is ys0[r, :t0_r] (right-padded); it decodes
@@ -800,8 +1037,14 @@ class KVDecoder:
         return_logp=True: returns (ys, token_logp, logp) -- token_logp [n, L] fp32 laid out like ys holds the MODEL's
         log-probability of every generated token up to the row's first <eos> (raw logits at temperature 1, whatever
         filter the draw went through; score_reference's rule), 0 on prefix, pad and later columns; logp [n] its row
-        sum.  One small launch per step behind the selection (gct_chosen_logp), no second forward."""
+        sum.  One small launch per step behind the selection (gct_chosen_logp), no second forward.
+        grammar (a SmilesGrammar over the model's vocabulary, optional): constrained decoding -- every mode chooses among
+        the tokens the grammar allows after the row's own generated tokens and that still let the row reach <eos> within
+        its max_strlen - 1 tokens (gct_grammar_mask in front of the selection, one launch more per step; None: no launch).
+        Every row then ends with <eos> and parses; the guarantee is syntactic, not chemical.  return_logp stays the
+        model's own log-probability (raw logits).  ValueError for max_strlen < 3 or a grammar of another vocabulary."""
         V = self.model.out.weight.shape[0]
+        check_grammar(grammar, V, max_strlen - 1)
         filtered = check_sample_filter(top_k, top_p, temperature, V) and algo == "multinomial"
         if filtered and V > ops.SAMPLE_FILTER_MAX_VOCAB:
             raise ValueError(f"top-k / nucleus / temperature sampling supports vocabularies up to "
@@ -821,6 +1064,7 @@ class KVDecoder:
             mode = FILTERED
             self.filt.copy_(ops.sample_filter_settings(top_k, top_p, temperature, V))
         self.want_logp = bool(return_logp)
+        self._set_grammar(grammar, steps, t0)
         self.prefill(ys0, lens)
         if self.want_logp:
             self.tok_logp.zero_()
@@ -874,6 +1118,7 @@ class KVDecoder:
             raise ValueError(f"prefix {t0} + {steps} steps exceeds the cache length {self.T - self.off}")
         dev = self.ys.device
         self.want_logp = False                                     # (the beam scores are log-probabilities already)
+        self.grammar = None                                        # (beam rows keep their history behind kv_src)
         self.prefill(ys0.to(dev).repeat_interleave(k, 0))
         scores, _, _ = beam_init(ns, k, dev)
         self.bscores.copy_(scores.view(-1))
@@ -993,7 +1238,8 @@ class KVDecoder:
 
     @torch.no_grad()
     def generate_stream(self, ys0, max_strlen=80, algo="greedy", seed=0, prefix_lens=None, max_new_tokens=None,
-                        top_k=None, top_p=None, temperature=1.0, use_graphs=False, check_every=8, return_logp=False):
+                        top_k=None, top_p=None, temperature=1.0, use_graphs=False, check_every=8, return_logp=False,
+                        grammar=None):
         """Decode the pool of start_stream with continuous batching: item i starts from the prefix ys0[i, :t0_i]
         (ys0 [N, t0_max], prefix_lens ints [N] or None = all t0_max) and generates until <eos> or max_new_tokens[i]
         tokens (ints [N] in [1, max_strlen - 1]; None: max_strlen - 1); a row that finishes takes the next item
@@ -1007,6 +1253,8 @@ class KVDecoder:
         return_logp=True: returns (ys, record, token_logp, logp) in item order -- token_logp [N, L] fp32 laid out like
         ys, the model's log-probability of item i's generated tokens at columns t0_i .. t0_i + out_len_i - 1 and 0
         elsewhere, logp [N] its row sum (generate()'s return_logp).
+        grammar (a SmilesGrammar, optional): as in generate(), with item i's budget max_new_tokens[i] read from the
+        device: every item ends with <eos> inside its own limit.  ValueError for a limit below 2.
         ValueError before any device work for beam search, bad prefix_lens / max_new_tokens / sampling settings and
         lengths beyond the positional table or the cache rows of start_stream."""
         if algo not in ("greedy", "multinomial"):
@@ -1029,6 +1277,7 @@ class KVDecoder:
         lens = check_prefix_lens(prefix_lens, N, t0)
         lens = torch.full((N,), t0, dtype=torch.int64) if lens is None else lens
         cap = check_max_new_tokens(max_new_tokens, N, steps)
+        check_grammar(grammar, V, cap)
         W = t0 + steps
         pe_rows = self.dec.pe.pe.shape[1]
         if W > pe_rows:
@@ -1059,6 +1308,7 @@ class KVDecoder:
             mode = FILTERED
             self.filt.copy_(ops.sample_filter_settings(top_k, top_p, temperature, V))
         self.want_logp = bool(return_logp)
+        self._set_grammar(grammar, steps, t0)                      # (a streamed row reads limit[item] / prefix_len[item])
         if self.want_logp:
             st["out_logp"].zero_()
         self.ragged = True
@@ -1108,6 +1358,8 @@ class KVDecoder:
         key = (mode, "mixed") if self.ragged else mode    # a mixed-prefix step passes row_off: a graph of its own
         if self.streaming:
             key = (mode, STREAM)                          # step + selection by item + refill
+        if self.grammar is not None and mode != BEAM:     # the unit holds the mask kernel: a graph of its own
+            key = (key if isinstance(key, tuple) else (key, "uniform")) + (GRAMMAR,)
         if self.want_logp and mode != BEAM:               # the unit holds one more kernel: a graph of its own
             key = (key if isinstance(key, tuple) else (key, "uniform")) + (LOGP,)
         g = self.graphs.get(key)
@@ -1236,16 +1488,22 @@ class KVDecoder:
 
 
 @torch.no_grad()
-def reference_style_decode(model, z, src_mask, dconds, ys0, pad_id, eos_id, max_strlen=80):
+def reference_style_decode(model, z, src_mask, dconds, ys0, pad_id, eos_id, max_strlen=80, grammar=None):
     """The reference's loop (sampling_tool.py:140-184, greedy) on the un-cached model.decode --
-    used by tests/benchmarks as the baseline the KV-cached path must match token for token."""
+    used by tests/benchmarks as the baseline the KV-cached path must match token for token.
+    grammar (a SmilesGrammar, optional): the argmax is taken over grammar.mask_reference of the logits."""
     from .Model.modules import get_trg_mask
+    check_grammar(grammar, model.out.weight.shape[0], max_strlen - 1)
     ys = ys0.clone()
+    t0 = ys0.size(1)
     done = torch.zeros(ys.size(0), dtype=torch.bool, device=ys.device)
     for _ in range(max_strlen - 1):
         trg_mask = get_trg_mask(ys, pad_id, False, dconds)
         logits = model.decode(ys, z, src_mask, trg_mask, dconds)
-        nxt = logits[:, -1].argmax(-1)
+        last = logits[:, -1]
+        if grammar is not None:
+            last = grammar.mask_reference(last.float(), ys, t0, ys.size(1), max_strlen - 1)
+        nxt = last.argmax(-1)
         ys = torch.cat([ys, nxt[:, None]], dim=1)
         done |= nxt == eos_id
         if bool(done.all()):

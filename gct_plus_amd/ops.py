@@ -951,6 +951,41 @@ def select_token(logits2d, ys, pos, valid_u8, done_u8, mode, pad_id, eos_id, see
                                 _p(row_off), _p(filt_dev), _p(item), _p(prefix_len), item_base, _st()), "gct_select_token")
 
 
+# token classes of the grammar table, class | ring number << 8 (GCT_GRAMMAR_* of include/gctplus_hip.h)
+(GRAMMAR_ATOM, GRAMMAR_BOND, GRAMMAR_OPEN, GRAMMAR_CLOSE, GRAMMAR_RING, GRAMMAR_DOT, GRAMMAR_EOS, GRAMMAR_PAD,
+ GRAMMAR_BANNED) = range(9)
+GRAMMAR_MAX_RINGS = 64
+
+
+def grammar_mask(logits2d, masked, table, ys, pos_dev, width=None, row_off=None, gram=None, item=None, prefix_len=None,
+                 limit=None):
+    """gct_grammar_mask, in front of select_token on the same device counter: masked [n, V] = logits2d where the grammar
+    (decode.SmilesGrammar; table int32 [V]) and the length budget allow the token as the next one of the row, -inf
+    elsewhere.  gram int32 [2] on the device = (budget G, prefix width t0_max), row r's prefix being t0_max - row_off[r]
+    tokens; or item / prefix_len / limit as in select_token and the stream's state.  width: token columns of ys in use
+    (default all).  Parked rows and rows inside their prefix are not written."""
+    n, V = logits2d.shape
+    _chk(logits2d, "grammar_mask.logits"), _chk(masked, "grammar_mask.masked"), _chk(ys, "grammar_mask.ys", torch.int64)
+    _chk(table, "grammar_mask.table", torch.int32), _chk(pos_dev, "grammar_mask.pos", torch.int32)
+    if not logits2d.is_contiguous() or not masked.is_contiguous() or masked.shape != logits2d.shape:
+        raise ValueError("grammar_mask: logits and masked must be contiguous [n, V] buffers of one shape")
+    if table.numel() != V or not table.is_contiguous() or ys.dim() != 2 or ys.shape[0] < n or ys.stride(1) != 1:
+        raise ValueError("grammar_mask: table int32 [V], ys [n, T] with unit column stride")
+    _check_row_off(row_off, n)
+    stream = [t is not None for t in (item, prefix_len, limit)]
+    if any(stream) != all(stream):
+        raise ValueError("item, prefix_len and limit go together")
+    if item is not None:
+        _check_row_off(item, n)
+        if row_off is None or any(t.dtype != torch.int32 or not t.is_contiguous() for t in (prefix_len, limit)):
+            raise ValueError("streamed rows need row_off and contiguous int32 prefix_len / limit")
+    elif gram is None or gram.dtype != torch.int32 or gram.numel() != 2 or not gram.is_contiguous():
+        raise ValueError("gram must be a contiguous int32 tensor (budget, prefix width)")
+    check(_L().gct_grammar_mask(_p(logits2d), _p(masked), V, _p(table), _p(ys), ys.stride(0),
+                                ys.shape[1] if width is None else int(width), n, _p(pos_dev), _p(row_off), _p(gram),
+                                _p(item), _p(prefix_len), _p(limit), _st()), "gct_grammar_mask")
+
+
 def seq_logp(logits2d, ys, prefix_lens=None, pad_id=1, row_shift=0, rows_per_seq=None, V=None, out=None):
     """gct_seq_logp (decode.score_reference states the rule): ys int64 [n, W] full token rows, logits2d fp32
     [n * rows_per_seq, V] with unit column stride (a strided view is fine: ld = its row stride); the logits row of token

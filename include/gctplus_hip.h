@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 21
+#define GCT_ABI_VERSION 22
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -452,6 +452,33 @@ int gct_select_token(const float* logits, int V, int64_t* ys, int64_t ld_ys, int
                      int64_t pad_id, int64_t eos_id, uint64_t seed, const int32_t* pos_dev, int valid_off,
                      const uint64_t* seed_dev, const int32_t* row_off, const GctSampleFilter* filt,
                      const int32_t* item, const int32_t* prefix_len, int item_base, void* stream);
+
+/* Grammar-constrained decoding (gct_plus_amd/decode.py SmilesGrammar states the grammar and is the reference): launched in
+ * front of gct_select_token in the step unit, on the same device counter.  One wave per row, no state of its own: row r
+ * is about to choose column p = *pos + 1 - row_off[r] (row_off nullable); its generated tokens are ys[r][t0_r, p), with
+ *   t0_r = gram[1] - row_off[r] and the budget G = gram[0]      (gram: int32 [2] in DEVICE memory, so that a captured
+ *                                                                 graph serves any max_strlen and prefix width), or
+ *   t0_r = prefix_len[item[r]] and G = limit[item[r]]           with item / prefix_len / limit (all three or none, with
+ *                                                                 row_off: continuous batching as in gct_select_token).
+ * The wave classifies those g = p - t0_r tokens (at most 255: T <= 256) through table (int32 [V]: class | ring number << 8, GCT_GRAMMAR_*), derives
+ * the state -- depth = #OPEN - #CLOSE, open = xor of the ring bits, here = open & (or of the ring bits behind the last
+ * ATOM), prev from the last two classes -- and writes masked[r][c] = logits[r][c] (bit for bit) when token c is allowed as
+ * the row's g-th token under the budget G, -inf otherwise.  A finished row (prev END) and a row past its budget (g >= G)
+ * allow <pad> only.  Nothing is written for a parked row (item < 0), a row inside its prefix (g < 0) or p >= T.
+ * logits / masked [n][V] contiguous, distinct; ys [n][ld_ys], T <= 256 columns in use; any V >= 1. */
+#define GCT_GRAMMAR_ATOM 0
+#define GCT_GRAMMAR_BOND 1
+#define GCT_GRAMMAR_OPEN 2
+#define GCT_GRAMMAR_CLOSE 3
+#define GCT_GRAMMAR_RING 4
+#define GCT_GRAMMAR_DOT 5
+#define GCT_GRAMMAR_EOS 6
+#define GCT_GRAMMAR_PAD 7
+#define GCT_GRAMMAR_BANNED 8
+#define GCT_GRAMMAR_MAX_RINGS 64
+int gct_grammar_mask(const float* logits, float* masked, int V, const int32_t* table, const int64_t* ys, int64_t ld_ys,
+                     int T, int n, const int32_t* pos, const int32_t* row_off, const int32_t* gram, const int32_t* item,
+                     const int32_t* prefix_len, const int32_t* limit, void* stream);
 
 /* Continuous batching (gct_plus_amd/decode.py stream_schedule_reference states the schedule).  R decode rows work
  * through a pool of N items behind the shared counter *pos: the step unit is gct_decode_advance, the RAGGED step
