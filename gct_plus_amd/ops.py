@@ -236,7 +236,8 @@ def embed_pe_bwd(dout, tok, dtable, dcond, n_c, scale, p, seed, site, d=None):
         vocab, d = dtable.shape
     else:
         vocab = 1
-    ws = workspace(_L().gct_embed_ws_bytes(B, S, d, vocab), dout.device)
+    # kept: the slab reduction that ends it is recorded, not launched, under deferred_reductions()
+    ws = kept_workspace(_L().gct_embed_ws_bytes(B, S, d, vocab), dout.device)
     check(_L().gct_embed_pe_bwd(_p(dout), _p(tok), _p(dtable), _p(dcond), _p(ws), B, S, n_c, d, vocab,
                                 scale, p, seed, site, _st()), "gct_embed_pe_bwd")
 

@@ -71,7 +71,9 @@ int gct_embed_pe_fwd(const int64_t* tok, const float* table, const float* cond, 
                      float* out, int B, int S, int n_c, int d, int vocab, float scale, float p,
                      uint64_t seed, uint32_t site, void* stream);
 /* dtable[vocab][d] overwritten (deterministic two-stage reduction), dcond[B][n_c][d]
- * overwritten (nullable when n_c == 0). ws >= gct_embed_ws_bytes. */
+ * overwritten (nullable when n_c == 0). ws >= gct_embed_ws_bytes.  The reduction that writes dtable is one of the
+ * deferred slab reductions below: while they are being recorded, ws stays intact until the flush.  Token ids outside
+ * [0, vocab) are clamped to rows 0 / vocab - 1 in both directions. */
 int64_t gct_embed_ws_bytes(int B, int S, int d, int vocab);
 int gct_embed_pe_bwd(const float* dout, const int64_t* tok, float* dtable, float* dcond,
                      float* ws, int B, int S, int n_c, int d, int vocab, float scale, float p,
@@ -332,7 +334,9 @@ int gct_kld_bwd(const float* mu, const float* log_var, const float* gout, float*
  * reduction='sum').  out[0] overwritten. ws >= 1024 floats. */
 int gct_ce_fwd(const float* logits, const int64_t* target, float* out, float* ws, int64_t rows,
                int V, int64_t pad_id, void* stream);
-/* dlogits = g*(softmax - onehot) on non-pad rows, 0 on pad rows; g = gout[0] (device). */
+/* dlogits = g*(softmax - onehot) on non-pad rows, 0 on pad rows; g = gout[0] (device).
+ * A target that is neither pad_id nor in [0, V) is not an error: gct_ce_fwd adds nothing for that row and gct_ce_bwd
+ * writes g*softmax (no one-hot term) -- F.cross_entropy raises there. */
 int gct_ce_bwd(const float* logits, const int64_t* target, const float* gout, float* dlogits,
                int64_t rows, int V, int64_t pad_id, void* stream);
 /* Log-likelihoods of token rows (gct_plus_amd/decode.py score_reference states the rule), teacher-forced form.
@@ -589,7 +593,7 @@ int gct_reduce_slabs(const float* slabs, int nslab, int64_t stride, float* dst, 
                      int accumulate, void* stream);
 /* Deferred slab reductions: between gct_reduce_defer_begin and gct_reduce_defer_end every float4-shaped slab reduction
  * that the calling THREAD issues through this library (the tails of gct_linear_wgrad, gct_norm_bwd's alpha / bias
- * partials, bias column sums) is recorded instead of launched; gct_reduce_defer_flush launches all recorded ones as ONE
+ * partials, bias column sums, gct_embed_pe_bwd's dtable) is recorded instead of launched; gct_reduce_defer_flush launches all recorded ones as ONE
  * kernel on `stream` (same summation order per region: results are bit-identical) and keeps recording, _end flushes and
  * stops, _pending returns the number recorded.  Contract: the caller keeps every recorded call's workspace intact until
  * the flush and does not read the destinations before it (a layer's parameter gradients: engine.py flushes at the end of
