@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
   // cross-attention memory are most of it at MOSES-like lengths)
   int Lold;                                                                        // keys already in the cache
   if constexpr (RAGGED) Lold = cache_off + *pos - row_off[b];                      // uniform over the wave
-  else Lold = pos ? cache_off + *pos : (klen ? klen[b] : Lc_host);
+  else Lold = pos ? cache_off + *pos : (klen ? min(klen[b], Lc_host) : Lc_host);   // klen clamped to Lc, as in _z
   const int Lc = pos ? Lold + 1 : Lold;
   const float* qp = q + (int64_t)b * ldq + h * DK;
   float* kp = k + (int64_t)b * kv_batch + h * DK;
@@ -259,7 +259,9 @@ __global__ __launch_bounds__(256) void decode_embed_kernel(const int64_t* __rest
 
 __global__ void decode_advance_kernel(int32_t* pos) { *pos += 1; }
 
-__device__ __forceinline__ float u01_open(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
+// the draw's uniform, in (0, 1]: the fp32 addition rounds to even once x >> 8 >= 2^23, so x >> 8 = 2^24 - 1 gives 1.0
+// and a row whose cumulative sums never exceed u takes the fallback (the last token of nonzero weight)
+__device__ __forceinline__ float u01_draw(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
 // one wave per sample row.  pos_dev (nullable): device-side step counter -- the token is written at ys[.., *pos_dev + 1]
 // and valid[.., valid_off + *pos_dev + 1]; seed_dev (nullable) replaces the by-value seed of the multinomial draw.
@@ -321,7 +323,7 @@ __global__ __launch_bounds__(256) void select_token_kernel(const float* __restri
   } else {
     // multinomial: inverse CDF with one Philox uniform per (row, position)
     const uint4 r = gct_philox(rng, key, (uint32_t)pos, 0x452821E6u, 0x38D01377u);
-    const float u = u01_open(r.x);
+    const float u = u01_draw(r.x);
     float cum = 0.f;
     int pick = V - 1, lastnz = -1;
     bool found = false;
@@ -484,7 +486,7 @@ __global__ __launch_bounds__(256) void select_token_filtered_kernel(
   }
   changed = __ballot(changed) != 0ull;                      // wave-uniform from here on
   const uint4 r = gct_philox(rng, key, (uint32_t)pos, 0x452821E6u, 0x38D01377u);
-  float u = u01_open(r.x);
+  float u = u01_draw(r.x);
   float pscale = 1.f;
   int pick = V - 1, last = -1;
 #pragma unroll

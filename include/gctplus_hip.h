@@ -391,7 +391,8 @@ int gct_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float
  * serves every step of the loop (gct_decode_embed / gct_select_token read the same counter, gct_decode_advance
  * increments it at the end of the step).  With pos == NULL the first Lc cached keys are used as they are.
  * klen (nullable, only with pos == NULL): per-sample number of leading keys to look at -- for a key-padding mask
- * whose visible keys are a non-empty prefix, the masked rows behind it weigh exactly 0 and are not read.
+ * whose visible keys are a non-empty prefix, the masked rows behind it weigh exactly 0 and are not read.  The kernel
+ * looks at min(klen[b], Lc) keys (as gct_attn_decode_z does): a klen above Lc reads nothing behind the Lc rows.
  * row_off (nullable, only with pos): int32 [n], per-row position offset of a batch of prefixes of different lengths
  * that share one device counter -- row b's position is *pos - row_off[b] (>= 0): the caches of row b hold
  * cache_off + *pos - row_off[b] keys and this step's key is appended there.  gct_decode_embed and gct_select_token
@@ -418,7 +419,9 @@ int gct_attn_decode_z(const float* q, int64_t ldq, int qoff, const float* z, int
                       int64_t valid_sb, const int32_t* klen, float* out, int64_t ldo, int ooff, int n, int H, int dk,
                       float scale, void* stream);
 /* x[b] = table[ys[b][p]] * scale + pe[pe_off + p] with p = *pos - (row_off ? row_off[b] : 0) (Embeddings +
- * PositionalEncoding of one position, eval mode; row_off as in gct_attn_decode) */
+ * PositionalEncoding of one position, eval mode; row_off as in gct_attn_decode).  An id outside [0, vocab) is clamped
+ * into it (below 0: row 0, vocab and above: row vocab - 1); one multiply and one add (or one fma) per element; out is
+ * [n][d] contiguous, d % 4 == 0.  gct_decode_advance: *pos += 1. */
 int gct_decode_embed(const int64_t* ys, int64_t ld_ys, const int32_t* pos, int pe_off, const float* table,
                      int vocab, const float* pe, float* out, int n, int d, float scale, const int32_t* row_off,
                      void* stream);
@@ -429,6 +432,14 @@ int gct_decode_advance(int32_t* pos, void* stream);
  * seed_dev (nullable): the multinomial seed is read from device memory (graph replays with a fresh seed).
  * row_off (nullable, only with pos_dev; as in gct_attn_decode): row r writes at pos = *pos_dev - row_off[r] + 1, and
  * its multinomial draw is keyed by (r, that pos).
+ * The multinomial draw of row r at token position pos (plain and filtered alike):
+ *   x = the FIRST word of Philox4x32-10 at the counter (key, pos, 0x452821E6, 0x38D01377), key = r (or item_base + item,
+ *       below), under the key of (seed, site 0xDEC0DE): (seed_lo, seed_hi ^ (0xDEC0DE * 0x9E3779B9 + 0x7F4A7C15));
+ *   u = (float32(x >> 8) + 0.5f) * 2^-24, evaluated in fp32.  The addition rounds to even once x >> 8 >= 2^23, so u lies
+ *       in (0, 1] -- x >> 8 = 2^24 - 1 gives exactly 1.0 -- not in (0, 1);
+ *   the pick is the first token c with w_c > 0 whose inclusive cumulative sum of w / sum w exceeds u (fp32 sums, 64
+ *       tokens per wave scan, carried from chunk to chunk); when no sum exceeds u (rounding, or u = 1), the last token
+ *       of nonzero weight.  A token of weight 0 (a logit of -inf, or one the nucleus dropped) is never picked.
  * filt (nullable, DEVICE memory, mode 1 only): sampling filter between the softmax and the draw (gct_plus_amd/decode.py
  * sample_filter_reference states the rules), read by the kernel so that one captured graph serves any settings:
  *   p = softmax(x * inv_temp) in fp32;

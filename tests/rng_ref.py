@@ -15,6 +15,11 @@ The rules:
   N(0, 1) noise       elements 4 i .. 4 i + 3 from the counter (i, i >> 32, 13198A2E, 03707344): Box-Muller on the pairs
                       (x, y) and (z, w) with u01(v) = ((v >> 8) + 1) / 2^24 in (0, 1]: radius sqrt(-2 ln u01(first)),
                       angle float32(2 pi) * u01(second), outputs (r cos, r sin)
+  multinomial draw    (include/gctplus_hip.h, gct_select_token) site DEC0DE; x = word 0 of the counter
+                      (key, pos, 452821E6, 38D01377), key = the row (or item_base + item), pos = the token position;
+                      u = (float32(x >> 8) + 0.5f) * 2^-24 in float32: the addition rounds to even once
+                      x >> 8 >= 2^23, so u lies in (0, 1] (x >> 8 = 2^24 - 1 gives 1.0); the pick is the first token of
+                      nonzero weight whose normalised inclusive cumulative sum exceeds u, else the last of nonzero weight
 """
 import numpy as np
 
@@ -24,6 +29,8 @@ MASK32 = 0xFFFFFFFF
 DROP_C2, DROP_C3 = 0x243F6A88, 0x85A308D3
 ATTN_C2, ATTN_C3 = 0xA4093822, 0x299F31D0
 NOISE_C2, NOISE_C3 = 0x13198A2E, 0x03707344
+DRAW_C2, DRAW_C3 = 0x452821E6, 0x38D01377
+DRAW_SITE = 0xDEC0DE
 
 
 def _u64(a):
@@ -117,3 +124,44 @@ def reparam_eps(seed, site, n):
         rad, ang = np.sqrt(-2.0 * np.log(_u01(a))), two_pi * _u01(b)
         out[:, 2 * j], out[:, 2 * j + 1] = rad * np.cos(ang), rad * np.sin(ang)
     return out.reshape(-1)[:n]
+
+
+def draw_uniform_of_word(x):
+    """float32 array: u = (float32(x >> 8) + 0.5f) * 2^-24, every operation in float32 (the sum rounds to even once
+    x >> 8 >= 2^23, so the largest words give exactly 1.0)."""
+    hi = (_u64(x) >> _u64(8)).astype(np.float32)                # exact: at most 24 bits
+    return (hi + np.float32(0.5)) * np.float32(2.0 ** -24)
+
+
+def select_uniform(seed, key, pos, word=0):
+    """float32 array: the uniform of the multinomial draw keyed (key, pos) under `seed` (ints or integer arrays).  word: the
+    Philox output word to take -- the draw takes word 0 (x); the others exist for the tests that show a wrong word would
+    be noticed."""
+    words = philox4x32_10((np.asarray(key, dtype=np.int64), np.asarray(pos, dtype=np.int64), DRAW_C2, DRAW_C3),
+                          rng_key(seed, DRAW_SITE))
+    return draw_uniform_of_word(words[word])
+
+
+def draw(weights, u):
+    """weights float64 [n, V] (>= 0, not all 0 in a row), u [n] -> (pick, gap, lo, hi), int64 / float64 [n].
+    pick: the first token c with w_c > 0 whose normalised inclusive cumulative sum exceeds u; when there is none, the last
+    token of nonzero weight.  gap: the distance from u to the nearest cumulative boundary of a nonzero-weight token --
+    lo is that token and hi the next token of nonzero weight behind it (lo itself when it is the last): an evaluation of
+    the sums in another precision or order may move a row whose gap is small from one of the two to the other, and to no
+    third token."""
+    w = np.asarray(weights, dtype=np.float64)
+    u = np.asarray(u, dtype=np.float64).reshape(-1, 1)
+    n, V = w.shape
+    nz = w > 0
+    assert nz.any(1).all() and (w >= 0).all()
+    cum = np.cumsum(w / w.sum(1, keepdims=True), axis=1)
+    idx = np.arange(V)[None, :]
+    last = np.where(nz, idx, -1).max(1)
+    hit = nz & (cum > u)
+    pick = np.where(hit.any(1), hit.argmax(1), last)
+    dist = np.where(nz, np.abs(cum - u), np.inf)
+    lo = dist.argmin(1)
+    gap = dist[np.arange(n), lo]
+    behind = nz & (idx > lo[:, None])
+    hi = np.where(behind.any(1), behind.argmax(1), lo)
+    return pick.astype(np.int64), gap, lo.astype(np.int64), hi.astype(np.int64)

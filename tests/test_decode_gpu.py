@@ -327,6 +327,16 @@ def test_attn_decode_z_equals_attention_over_projected_memory(nc, lat, H, dk, Le
     the reference formulation in fp64: memory = [cond2lat rows ; fc_z(z)], k = W_k mem + b_k, v = W_v mem + b_v,
     softmax(q k^T / sqrt(dk), masked_fill -1e9) v (Model/sublayers.py:29-41).  Masks: full, prefix (with klen), holes, and a
     sample that sees no key (uniform over all keys, like the reference)."""
+    attn_decode_z_case(nc, lat, H, dk, Le)
+
+
+def test_attn_decode_z_klen_inside_the_condition_rows():
+    """klen[b] = 2 with nc = 3: fewer condition rows than nc are visible and no latent row is."""
+    attn_decode_z_case(3, 32, 2, 32, 5, prefix=2)
+
+
+def attn_decode_z_case(nc, lat, H, dk, Le, prefix=None):
+    """prefix: the klen of the visible-prefix samples (default: drawn from nc .. nc + Le)."""
     from gct_plus_amd import ops
     d, n = H * dk, 9
     g = torch.Generator().manual_seed(100 + lat + Le)
@@ -341,7 +351,7 @@ def test_attn_decode_z_equals_attention_over_projected_memory(nc, lat, H, dk, Le
         kind = b % 4
         if kind == 1:                                  # visible prefix: the kernel may stop at klen
             ln = int(torch.randint(nc + (0 if nc else 1), Lk + 1, (1,), generator=g))
-            ln = max(ln, 1)
+            ln = max(ln, 1) if prefix is None else prefix
             valid[b, ln:] = 0
             klen[b] = ln
         elif kind == 2:                                # holes: every row is read
