@@ -1501,6 +1501,19 @@ int launch(int dk, const AttnRoute& r, const AttnArgs& a, hipStream_t st) {
 
 }  // namespace
 
+extern "C" int gct_attn_route(int bwd, int Lq, int Lk, int dk, int64_t npairs, int cus, int64_t* out4) {
+  GCT_CHECK_ARG(out4 && Lq > 0 && Lk > 0 && Lq <= L_MAX && Lk <= L_MAX && (dk == 16 || dk == 32 || dk == 64) &&
+                    npairs >= 0 && npairs <= INT32_MAX,
+                "attn_route: bad args (Lq, Lk in 1..%d, dk 16/32/64)", L_MAX);
+  if (cus <= 0) cus = num_cus();
+  const AttnRoute r = bwd ? plan_attn_bwd(Lq, Lk, dk, npairs, cus) : plan_attn_fwd(Lq, Lk, dk, npairs, cus);
+  out4[0] = r.kind == AttnRoute::DIRECT ? 0 : r.kind == AttnRoute::LDS8 ? 1 : 2;
+  out4[1] = r.grid;
+  out4[2] = r.grid_kv;
+  out4[3] = (int64_t)r.lds;
+  return GCT_OK;
+}
+
 extern "C" int gct_attn_mask_pack(const uint8_t* mask, int64_t mask_sb, int64_t mask_sq, int B, int Lq, int Lk,
                                   uint32_t* bits, uint32_t* tiles, void* stream) {
   GCT_CHECK_ARG(mask && bits && B >= 0 && Lq > 0 && Lk > 0 && Lk <= 32 * MASK_W && gct_aligned16(bits),

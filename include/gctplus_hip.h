@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 22
+#define GCT_ABI_VERSION 23
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -261,7 +261,10 @@ int gct_dropout_bwd(const float* dout, float* dy, int64_t rows, int cols, float 
  * of word k >> 5 set <=> key k visible; row of (b,q) at mbits + b*mb_sb + q*mb_sq (strides in words, multiples of
  * 4; mb_sq == 0 broadcasts a key-padding mask); a cleared bit => score := -1e9 (masked_fill semantics). nullable.
  * Pack once per forward: the same rows serve every layer, every head and the backward pass.
- * o: [B][Lq][H*dk] (heads merged, ready for the out projection); lse: [B][H][Lq].
+ * o: [B][Lq][H*dk] (heads merged, ready for the out projection); lse: [B][H][Lq], the log-sum-exp of the row's scaled
+ * scores over its visible keys (a masked key's exp(-1e9 - max) is exactly 0 in fp32).  A row WITHOUT a visible key
+ * is uniform over its Lk keys; -1e9 + log(Lk) is not representable in fp32, so its lse is log(Lk) and the backward
+ * scores its masked keys as 0 instead of -1e9.
  * probs (nullable): pre-dropout probabilities [B][H][Lq][Lk] (get_attn path).
  * dk in {16, 32, 64}; Lq, Lk <= 208 (the reference's positional table ends at 200: Model/modules.py:117; + 3
  * condition tokens).  Lk <= GCT_ATTN_DIRECT_MAX_KEYS runs the barrier-free kernels (one wave per query / key tile),
@@ -272,7 +275,11 @@ int gct_dropout_bwd(const float* dout, float* dy, int64_t rows, int cols, float 
 /* tiles (nullable): one word per (batch, 16-row query tile) -- [B][1] for a key-padding mask, [B][ceil(Lq/16)]
  * otherwise -- bit t set <=> key tile t must be visited; passed to gct_attn_fwd / gct_attn_bwd as tbits with the
  * strides (tb_sb, tb_su) = (1, 0) resp. (ceil(Lq/16), 1), it lets a wave request its K rows before its mask rows
- * are back.  The kernels compute the same word themselves when tbits is NULL. */
+ * are back.  The kernels compute the same word themselves when tbits is NULL.
+ * The rule, per query tile (rows 16u .. 16u+15 that are below Lq; for a key-padding mask the single row): when every
+ * such row sees at least one key, bit t is set <=> one of them sees a key among keys 16t .. 16t+15 (below Lk);
+ * when one of them sees no key at all, all ceil(Lk/16) bits are set -- that row is uniform over its Lk keys
+ * (masked_fill(-1e9) on the whole row), so every key tile contributes.  Bits at and above ceil(Lk/16) are 0. */
 int gct_attn_mask_pack(const uint8_t* mask, int64_t mask_sb, int64_t mask_sq, int B, int Lq, int Lk,
                        uint32_t* bits, uint32_t* tiles, void* stream);
 /* The decoder's self-attention mask straight from the token ids: the uint8 form of get_trg_mask(target, pad, False)
@@ -311,6 +318,12 @@ int gct_attn_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const
  * Required whenever gct_attn_bwd_ws_bytes > 0: a null, short or misaligned ws is GCT_ERR_ARG.  Longer rows run the
  * single-launch LDS kernel and need none (gct_attn_bwd_ws_bytes == 0, ws may be NULL). */
 int64_t gct_attn_bwd_ws_bytes(int B, int H, int Lq, int Lk);
+/* The route gct_attn_fwd (bwd == 0) / gct_attn_bwd (bwd != 0) take for a shape, from the planner they launch by:
+ * out4 = {kind (0 direct, 1 LDS 8 tiles, 2 LDS 13 tiles), grid, grid_kv, dynamic LDS bytes}.  grid: workgroups of the
+ * launch (direct backward: of the dQ launch, grid_kv of the dK / dV launch; else grid_kv = 0); the LDS kernels are
+ * persistent, so npairs > grid means that workgroups walk several (batch, head) pairs.  cus: compute units to plan
+ * for; cus <= 0: the device's own count.  No launch, no device memory. */
+int gct_attn_route(int bwd, int Lq, int Lk, int dk, int64_t npairs, int cus, int64_t* out4);
 
 /* ------------------------------------------------- K6: reparameterisation + KL */
 /* Model/sublayers.py:14-20 / Model/cvaetf.py:63-69: z = eps*exp(0.5*log_var)+mu.

@@ -209,9 +209,11 @@ def test_attention(ops, B, H, Lq, Lk, dk, mode):
 
 
 def test_attention_many_pairs_per_workgroup(ops):
-    """More (batch, head) pairs than persistent workgroups (2 per CU): every workgroup walks several pairs through
-    the software pipeline (next pair's K / V / Q rows loaded during this pair's MFMAs).  Causal + ragged mask,
-    dropout off; forward and backward against fp64."""
+    """768 (batch, head) pairs at L = 81, causal + ragged mask, dropout off, whole samples without gradient; forward
+    and backward against fp64.  Written for the persistent LDS kernels' pair loop when they ran every length; L <= 96
+    now runs the direct kernels (one wave per (pair, query tile), no pair loop), so this is their large-grid case.  The
+    LDS kernels' walk over several pairs per workgroup is tested in tests/test_attention_dense_gpu.py
+    (test_lds_kernels_walk_several_pairs_per_workgroup), sized from gct_attn_route."""
     B, H, L, dk = 96, 8, 81, 64                      # 768 pairs > 512 workgroups
     d = H * dk
     qkv = rnd(B * L, 3 * d, seed=11)
