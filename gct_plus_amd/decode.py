@@ -18,7 +18,9 @@ same token ids come out of
                key-valid and finished flags on the device.
 The step reads its position from a DEVICE-side counter (csrc/decode.hip), so one captured graph serves every step
 (`use_graphs=True`): no host round trip, no per-position capture.  Work per generated token drops from O(T) decoder
-passes to O(1).
+passes to O(1).  What the unit of step + selection consists of in a given generate call -- the selection, the view of
+the rows its kernels get, grammar mask, log-probabilities -- is one `StepPlan`, built by the call and passed down to the
+step; the decoder keeps no per-call mode.  `StepPlan.key` states which captured graph (`KVDecoder.graphs`) a unit shares.
 
 Beam search (`start(..., beams=k)` + `generate_beam`): sample s owns rows s*k .. s*k+k-1.  The rules are stated once,
 in `beam_step_reference` / `beam_finalize`; gct_beam_select implements the step on the device.  The self-attention
@@ -58,6 +60,8 @@ and parses.  The guarantee is syntactic only: valence, aromaticity and ring-bond
 """
 from __future__ import annotations
 
+import dataclasses
+import functools
 import heapq
 import math
 import numbers
@@ -84,13 +88,51 @@ REPLAY_GUARD = os.environ.get("GCT_DECODE_GRAPH_GUARD", "1") != "0"
 REPLAY_SLOW_FACTOR = 1.3
 # beam search: length penalty exponent of the final ranking score / length**alpha (reference generate_mols.py:182-185)
 BEAM_ALPHA = 0.7
-BEAM = "beam"                                       # selection mode key of the beam step (self.graphs, _advance)
-FILTERED = "filtered"                               # selection mode key of the filtered multinomial draw
-STREAM = "stream"                                   # graph key suffix of the continuous-batching step unit
+BEAM = "beam"                                       # StepPlan.select: the beam step (gct_beam_select)
+FILTERED = "filtered"                               # StepPlan.select: the filtered multinomial draw
+UNIFORM, MIXED, STREAM = "uniform", "mixed", "stream"      # StepPlan.layout
 LOGP = "logp"                                       # graph key suffix of a step unit that records log-probabilities
 GRAMMAR = "grammar"                                 # graph key suffix of a step unit that masks the logits by a grammar
 STREAM_COND_CHUNK = 256                             # items per GEMM when the pool's condition rows are projected
 TOP_K_FLOOR = 1e-6                                  # weight of a token outside the top k (the reference's top_k_logits)
+
+
+@dataclasses.dataclass(frozen=True)
+class StepPlan:
+    """What one step unit is -- the decode step plus the selection, the unit a graph captures.  Each generate call
+    builds one and passes it down; KVDecoder keeps no per-call mode of its own.
+      select   0 greedy, 1 multinomial, FILTERED (the multinomial draw through self.filt) or BEAM (gct_beam_select, the
+               self-attention through the ancestry map kv_src);
+      layout   UNIFORM: every row at the shared position.  MIXED: the kernels get row_off.  STREAM: row_off plus the
+               rows' item and prefix_len, and the unit ends with the refill (KVDecoder._rows is the row view);
+      grammar  gct_grammar_mask runs in front of the selection;
+      logp     gct_chosen_logp runs behind it.
+    ValueError for what the unit cannot do: beam rows keep their history behind kv_src and their scores are
+    log-probabilities already, so BEAM goes with UNIFORM and neither grammar nor logp."""
+    select: object = 0
+    layout: str = UNIFORM
+    grammar: bool = False
+    logp: bool = False
+
+    def __post_init__(self):
+        select, layout, grammar, logp = dataclasses.astuple(self)
+        if select not in (0, 1, FILTERED, BEAM) or layout not in (UNIFORM, MIXED, STREAM):
+            raise ValueError(f"no step unit selects {select!r} over {layout!r} rows")
+        if select == BEAM and (layout != UNIFORM or grammar or logp):
+            raise ValueError("the beam step takes uniform rows, no grammar and no log-probabilities")
+
+    @functools.cached_property
+    def key(self):
+        """THE statement of the graph key (KVDecoder.graphs; bench.py, the tools and the tests read it): "beam"; select
+        alone for plain uniform rows; (select, layout) for another layout; and with a grammar and / or log-probabilities
+        (select, layout[, GRAMMAR][, LOGP]), uniform spelled out.  A stream unit has k[1] == STREAM, logp k[-1] == LOGP."""
+        select, layout, grammar, logp = dataclasses.astuple(self)
+        if select == BEAM:
+            return BEAM
+        tail = (GRAMMAR,) * bool(grammar) + (LOGP,) * bool(logp)
+        if layout == UNIFORM and not tail:
+            return select
+        return (select, layout) + tail
 
 
 # ------------------------------------------------------------------------- top-k / nucleus / temperature sampling
@@ -351,6 +393,20 @@ class SmilesGrammar:
 
 
 # ------------------------------------------------------------------------------------------- log-likelihoods
+def _int_vector(name, values, n, lo, hi, bound):
+    """values as an int64 CPU tensor: integers of shape [n] in [lo, hi] (`bound` says in the message what hi is);
+    ValueError otherwise."""
+    v = torch.as_tensor(values)
+    if v.dtype.is_floating_point or v.dtype.is_complex or v.dtype == torch.bool:
+        raise ValueError(f"{name} must hold integers, got {v.dtype}")
+    v = v.to("cpu", torch.int64)
+    if v.dim() != 1 or v.numel() != n:
+        raise ValueError(f"{name} must have shape [{n}], got {list(v.shape)}")
+    if n and (int(v.min()) < lo or int(v.max()) > hi):
+        raise ValueError(f"{name} must lie in [{lo}, {hi}] ({bound}), got [{int(v.min())}, {int(v.max())}]")
+    return v
+
+
 def check_score_inputs(ys, prefix_lens, vocab):
     """Validate the inputs of a scoring call: ys an integer tensor [n, W >= 2] of token ids in [0, vocab); prefix_lens
     None or integers [n] in [1, W].  ValueError otherwise.  Returns the prefix lengths as an int64 CPU tensor [n] (all 1
@@ -361,18 +417,8 @@ def check_score_inputs(ys, prefix_lens, vocab):
     if ys.dtype.is_floating_point or ys.dtype.is_complex or ys.dtype == torch.bool:
         raise ValueError(f"ys must hold integer token ids, got {ys.dtype}")
     n, W = ys.shape
-    if prefix_lens is None:
-        lens = torch.ones(n, dtype=torch.int64)
-    else:
-        lens = torch.as_tensor(prefix_lens)
-        if lens.dtype.is_floating_point or lens.dtype.is_complex or lens.dtype == torch.bool:
-            raise ValueError(f"prefix_lens must hold integers, got {lens.dtype}")
-        lens = lens.to("cpu", torch.int64)
-        if lens.dim() != 1 or lens.numel() != n:
-            raise ValueError(f"prefix_lens must have shape [{n}], got {list(lens.shape)}")
-        if n and (int(lens.min()) < 1 or int(lens.max()) > W):
-            raise ValueError(f"prefix_lens must lie in [1, {W}] (the row width), got [{int(lens.min())}, "
-                             f"{int(lens.max())}]")
+    lens = torch.ones(n, dtype=torch.int64) if prefix_lens is None else _int_vector(
+        "prefix_lens", prefix_lens, n, 1, W, "the row width")
     if n and (int(ys.min()) < 0 or int(ys.max()) >= int(vocab)):
         raise ValueError(f"token ids must lie in [0, {int(vocab)}), got [{int(ys.min())}, {int(ys.max())}]")
     return lens
@@ -542,16 +588,7 @@ def check_max_new_tokens(max_new_tokens, n, steps):
     tokens.  ValueError otherwise."""
     if max_new_tokens is None:
         return torch.full((n,), steps, dtype=torch.int64)
-    cap = torch.as_tensor(max_new_tokens)
-    if cap.dtype.is_floating_point or cap.dtype.is_complex or cap.dtype == torch.bool:
-        raise ValueError(f"max_new_tokens must hold integers, got {cap.dtype}")
-    cap = cap.to("cpu", torch.int64)
-    if cap.dim() != 1 or cap.numel() != n:
-        raise ValueError(f"max_new_tokens must have shape [{n}], got {list(cap.shape)}")
-    if n and (int(cap.min()) < 1 or int(cap.max()) > steps):
-        raise ValueError(f"max_new_tokens must lie in [1, {steps}] (max_strlen - 1), got [{int(cap.min())}, "
-                         f"{int(cap.max())}]")
-    return cap
+    return _int_vector("max_new_tokens", max_new_tokens, n, 1, steps, "max_strlen - 1")
 
 
 def memory_masks(src_mask, n_cond_rows, Le):
@@ -588,15 +625,7 @@ def check_prefix_lens(prefix_lens, n, width):
     (the uniform path); ValueError otherwise."""
     if prefix_lens is None:
         return None
-    lens = torch.as_tensor(prefix_lens)
-    if lens.dtype.is_floating_point or lens.dtype.is_complex or lens.dtype == torch.bool:
-        raise ValueError(f"prefix_lens must hold integers, got {lens.dtype}")
-    lens = lens.to("cpu", torch.int64)
-    if lens.dim() != 1 or lens.numel() != n:
-        raise ValueError(f"prefix_lens must have shape [{n}], got {list(lens.shape)}")
-    if n and (int(lens.min()) < 1 or int(lens.max()) > width):
-        raise ValueError(f"prefix_lens must lie in [1, {width}] (the prefix width), got [{int(lens.min())}, "
-                         f"{int(lens.max())}]")
+    lens = _int_vector("prefix_lens", prefix_lens, n, 1, width, "the prefix width")
     return None if bool((lens == width).all()) else lens
 
 
@@ -676,9 +705,6 @@ class KVDecoder:
         self._fold_key = None                             # what the cached folded projections were computed from
         self._shape = None
         self.stream = None                                # continuous batching: pool + StreamState (start_stream)
-        self.streaming = False                            # a generate_stream loop is running (the step unit refills)
-        self.want_logp = False                            # this generate records the log-probability of every pick
-        self.grammar = None                               # this generate chooses from the grammar-masked logits
 
     # -------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -763,10 +789,9 @@ class KVDecoder:
             self.src_klen = torch.empty(n, dtype=torch.int32, device=dev)  # leading memory rows the cross-attention reads
             self.pos = torch.zeros(1, dtype=torch.int32, device=dev)       # token index the next step consumes
             self.row_off = torch.zeros(n, dtype=torch.int32, device=dev)   # mixed prefixes: row r is at pos - row_off[r]
-            self.ragged = False                                            # this decode passes row_off to the kernels
             self.seed = torch.zeros(1, dtype=torch.int64, device=dev)      # multinomial seed of this generate()
             self.filt = torch.zeros(4, dtype=torch.int32, device=dev)      # GctSampleFilter of this generate()
-            self.gram = self.gtable = None                                 # grammar buffers: the first _set_grammar
+            self.gram = self.gtable = None                                 # grammar buffers: the first _set_sampling with one
             # beam search state (generate_beam), per row: score, finished, length, parent; the ancestry map; done [n/k]
             self.beams = beams
             self.bscores = torch.zeros(n, device=dev)
@@ -822,11 +847,15 @@ class KVDecoder:
             self._fold_key = key
         off = self.nq - self.nz
         if off:                                                     # condition rows: k - c | v - d
-            for li, layer in enumerate(dec.layers):
-                a, kv = layer.attn_2, self.ckv[li]
-                ops.linear_fwd(cl, [a.k_linear.weight, a.v_linear.weight], [a.k_linear.bias, a.v_linear.bias],
-                               [kv, kv[:, d:]], 2 * d)
-                kv.view(-1, 2, d).sub_(self.zcv[li].view(1, 2, d))
+            for li in range(len(dec.layers)):
+                self._shifted_cond_kv(li, cl, self.ckv[li])
+
+    def _shifted_cond_kv(self, li, cl, kv):
+        """Layer li's keys | values of the condition rows cl [rows, d] into kv [rows, 2 d], shifted by -c | -d."""
+        a, d = self.dec.layers[li].attn_2, self.d
+        ops.linear_fwd(cl, [a.k_linear.weight, a.v_linear.weight], [a.k_linear.bias, a.v_linear.bias],
+                       [kv, kv[:, d:]], 2 * d)
+        kv.view(-1, 2, d).sub_(self.zcv[li].view(1, 2, d))
 
     def _fold_weights(self):
         """The weights-only part of _fold_cross (43 ms of small GEMMs and index fills for six layers: 15 % of a whole
@@ -874,13 +903,12 @@ class KVDecoder:
         forward; fills the caches for positions < off + t0 and returns the logits of the last prefix position.
         prefix_lens (int64 [n], from check_prefix_lens; None = all t0): row r's prefix is ys0[r, :t0_r]; the columns
         behind it become pad (invalid cache slots until generation overwrites them), the returned logits are those of
-        position t0_r - 1, and the steps run with row offsets t0 - t0_r."""
+        position t0_r - 1, and row_off holds the offsets t0 - t0_r a MIXED step unit runs with."""
         from .Model.modules import get_trg_mask
         dec, d, n = self.dec, self.d, self.n
         t0 = ys0.shape[1]
         ys0 = ys0.to(self.ys.device)
-        self.ragged = prefix_lens is not None
-        if self.ragged:
+        if prefix_lens is not None:
             lens = prefix_lens.to(self.ys.device, torch.int64)
             cols = torch.arange(t0, device=ys0.device).view(1, -1)
             ys0 = torch.where(cols < lens.view(-1, 1), ys0, torch.full_like(ys0, self.pad_id))
@@ -903,21 +931,29 @@ class KVDecoder:
             self.kc[li][:, :Tp].copy_(qkv[:, :, d:2 * d])
             self.vc[li][:, :Tp].copy_(qkv[:, :, 2 * d:])
         out = self.model.out
-        last = y[:, -1] if not self.ragged else y[torch.arange(n, device=y.device), self.off + lens - 1]
+        last = y[:, -1] if prefix_lens is None else y[torch.arange(n, device=y.device), self.off + lens - 1]
         ops.linear_fwd(last.contiguous(), [out.weight], [out.bias], [self.buf["logits"]], out.weight.shape[0])
         self.pos.fill_(t0 - 1)                                      # "token t0-1 has been consumed" (row r: t0_r - 1)
         return self.buf["logits"]
 
     # -------------------------------------------------------------------------------------
+    def _rows(self, plan, mask=False):
+        """The row view of a plan, as the keyword arguments the step's kernels take it in: row_off (MIXED and STREAM:
+        row r is at *pos - row_off[r]), item and prefix_len (STREAM: the item a row works on and the items' prefix
+        lengths), None each where the layout has none.  mask=True: what gct_grammar_mask reads besides -- gram, and
+        the items' limit (STREAM)."""
+        st = self.stream if plan.layout == STREAM else {}
+        view = dict(row_off=None if plan.layout == UNIFORM else self.row_off, item=st.get("item"),
+                    prefix_len=st.get("prefix_len"))
+        return dict(view, gram=self.gram, limit=st.get("limit")) if mask else view
+
     @torch.no_grad()
-    def step(self, beam=False):
+    def step(self, plan=StepPlan()):
         """Consume token ys[:, p] with p = *pos + 1 ... see _chain: ONE generated token, position on the device.
-        beam=True: the self-attention reads the caches through the ancestry map kv_src (gct_attn_decode_beam)."""
+        select BEAM: the self-attention reads the caches through the ancestry map kv_src (gct_attn_decode_beam)."""
         dec, d, n, T, B = self.dec, self.d, self.n, self.T, self.buf
-        L = ops._L()
-        st = ops._st()
-        row_off = self.row_off if self.ragged and not beam else None        # mixed prefixes: per-row positions
-        check(L.gct_decode_advance(self.pos.data_ptr(), st), "gct_decode_advance")   # pos = index of the token consumed now
+        beam, row_off = plan.select == BEAM, self._rows(plan)["row_off"]
+        check(ops._L().gct_decode_advance(self.pos.data_ptr(), ops._st()), "gct_decode_advance")   # pos = the token consumed now
         ops.decode_embed(self.ys, self.pos, self.off, dec.embed.embed.weight, dec.pe.pe, B["x"], math.sqrt(d),
                          row_off=row_off)
         x = B["x"]
@@ -965,44 +1001,63 @@ class KVDecoder:
         ops.linear_fwd(B["y"], [out.weight], [out.bias], [B["logits"]], out.weight.shape[0], ws=self.ws)
         return B["logits"]
 
-    def _select(self, mode):
+    def _select(self, plan):
         """softmax + choice of the next token from buf['logits']; written at ys[:, *pos + 1] (device position).
-        mode BEAM: gct_beam_select (beam state, the kv_src map and bdone in place).  mode FILTERED: the multinomial draw
-        through the top-k / nucleus / temperature settings in self.filt.  With a grammar the choice is made from a masked
-        copy of the logits (gct_grammar_mask, one launch more); buf['logits'] stays raw for _chosen_logp."""
-        if mode == BEAM:
+        BEAM: gct_beam_select (beam state, the kv_src map and bdone in place).  FILTERED: the multinomial draw through the
+        top-k / nucleus / temperature settings in self.filt.  With a grammar the choice is made from a masked copy of
+        the logits (gct_grammar_mask, one launch more); buf['logits'] stays raw for _chosen_logp."""
+        if plan.select == BEAM:
             ops.beam_select(self.buf["logits"], self.beams, self.bscores, self.bfin, self.blen, self.ys, self.valid,
                             self.off, self.kv_src, self.bdone, self.pos, self.pad_id, self.eos_id,
                             parent_i32=self.bparent)
             return
-        st = self.stream if self.streaming else None     # continuous batching: the rows' items and their prefix lengths
         logits = self.buf["logits"]
-        if self.grammar is not None:                     # the selection sees -inf on what the grammar / the budget forbid
+        if plan.grammar:                                 # the selection sees -inf on what the grammar / the budget forbid
             ops.grammar_mask(logits, self.buf["masked"], self.gtable, self.ys, self.pos, width=self.T - self.off,
-                             row_off=self.row_off if self.ragged else None, gram=self.gram, item=st and st["item"],
-                             prefix_len=st and st["prefix_len"], limit=st and st["limit"])
+                             **self._rows(plan, mask=True))
             logits = self.buf["masked"]
-        ops.select_token(logits, self.ys, 0, self.valid, self.done, 1 if mode == FILTERED else mode,
+        filtered = plan.select == FILTERED
+        ops.select_token(logits, self.ys, 0, self.valid, self.done, 1 if filtered else plan.select,
                          self.pad_id, self.eos_id, pos_dev=self.pos, valid_off=self.off, seed_dev=self.seed,
-                         row_off=self.row_off if self.ragged else None,
-                         filt_dev=self.filt if mode == FILTERED else None,
-                         item=st and st["item"], prefix_len=st and st["prefix_len"],
-                         item_base=st["item_base"] if st else 0)
+                         filt_dev=self.filt if filtered else None,
+                         item_base=self.stream["item_base"] if plan.layout == STREAM else 0, **self._rows(plan))
 
-    def _advance(self, mode):
+    def _advance(self, plan):
         """One step and its selection: the unit a graph captures.  Continuous batching: then the refill."""
-        self.step(beam=mode == BEAM)
-        self._select(mode)
-        if self.want_logp and mode != BEAM:
-            self._chosen_logp()                          # before the refill, which reassigns the rows' items
-        if self.streaming:
+        self.step(plan)
+        self._select(plan)
+        if plan.logp:
+            self._chosen_logp(plan)                      # before the refill, which reassigns the rows' items
+        if plan.layout == STREAM:
             self.stream["state"].refill()
 
-    def _set_grammar(self, grammar, budget, t0):
-        """The grammar of this generate (None: unconstrained): its class table, the budget and the prefix width go to
-        the device buffers the captured graphs read -- (budget G, prefix width), the table and the masked copy of the
-        logits, allocated when a decoder's rows first see a grammar."""
-        self.grammar = grammar
+    def _chosen_logp(self, plan):
+        """The model's log-probability of the token _select has just written (gct_chosen_logp): into tok_logp at the
+        row's own column, or, streamed, into the pool's table at (item, column)."""
+        out = self.stream["out_logp"] if plan.layout == STREAM else self.tok_logp
+        ops.chosen_logp(self.buf["logits"], self.ys, self.pos, out, self.pad_id, **self._rows(plan))
+
+    # ------------------------------------------------------------- what generate and generate_stream share
+    def _check_sampling(self, algo, top_k, top_p, temperature):
+        """The sampling settings of a generate call, the half that can raise: ValueError for bad values and for a
+        filtered draw over too large a vocabulary.  Returns the GctSampleFilter record (CPU) when the draws go through
+        the filter, None when they do not (neutral settings, or greedy: the filters always keep the top token)."""
+        V = self.model.out.weight.shape[0]
+        filtered = check_sample_filter(top_k, top_p, temperature, V) and algo == "multinomial"
+        if filtered and V > ops.SAMPLE_FILTER_MAX_VOCAB:
+            raise ValueError(f"top-k / nucleus / temperature sampling supports vocabularies up to "
+                             f"{ops.SAMPLE_FILTER_MAX_VOCAB} tokens, not {V}")
+        return ops.sample_filter_settings(top_k, top_p, temperature, V) if filtered else None
+
+    def _set_sampling(self, algo, filt, seed, grammar, budget, t0):
+        """The other half, after every check of the call has passed: seed, filter record and grammar go to the device
+        buffers the captured graphs read -- the grammar as its class table and (budget G, prefix width), allocated with
+        the masked copy of the logits when a decoder's rows first see a grammar.  Returns StepPlan.select."""
+        select = {"greedy": 0, "multinomial": 1}[algo]
+        self.seed.fill_(int(seed) & 0x7FFFFFFFFFFFFFFF)
+        if filt is not None:
+            select = FILTERED
+            self.filt.copy_(filt)
         if grammar is not None:
             if self.gram is None:                        # first grammar on these rows (they live as long as the rows do,
                 dev, (n, V) = self.ys.device, self.buf["logits"].shape     # like the graphs captured against them)
@@ -1011,14 +1066,25 @@ class KVDecoder:
                 self.buf["masked"] = torch.empty(n, V, device=dev)
             self.gtable.copy_(grammar.device_table(self.gtable.device))
             self.gram.copy_(torch.tensor([int(budget), int(t0)], dtype=torch.int32))
+        return select
 
-    def _chosen_logp(self):
-        """The model's log-probability of the token _select has just written (gct_chosen_logp): into tok_logp at the
-        row's own column, or, streamed, into the pool's table at (item, column)."""
-        st = self.stream if self.streaming else None
-        ops.chosen_logp(self.buf["logits"], self.ys, self.pos, st["out_logp"] if st else self.tok_logp, self.pad_id,
-                        row_off=self.row_off if self.ragged else None, item=st and st["item"],
-                        prefix_len=st and st["prefix_len"])
+    def _cut_at_eos(self, ys, lens, t0):
+        """The reference's break point: when every row has produced <eos>, ys [n, t0 + G] (rows' tokens from column
+        lens[r]) is cut after the longest row's first one.  Returns (ys, is_eos [n, G] of the uncut generated part)."""
+        is_eos = generated_tokens(ys, lens) == self.eos_id
+        if ys.size(0) and bool(is_eos.any(dim=1).all()):
+            ys = ys[:, :t0 + int(is_eos.int().argmax(dim=1).max().item()) + 1]
+        return ys, is_eos
+
+    def _span_logp(self, table, ys, lens, n_gen):
+        """(token_logp, logp) of return_logp: table [n, >= L] laid out like ys [n, L], kept on row r's generated span --
+        its columns lens[r] .. lens[r] + n_gen[r] - 1 that are not pad -- and 0 elsewhere: a finished or held row decodes
+        on, and the capture warm-up and the replay guard run real steps past the position they restore."""
+        dev = ys.device
+        start, cols = lens.to(dev).view(-1, 1), torch.arange(ys.size(1), device=dev).view(1, -1)
+        span = (cols >= start) & (cols < start + n_gen.to(dev).view(-1, 1)) & (ys != self.pad_id)
+        token_logp = torch.where(span, table[:, :ys.size(1)], torch.zeros((), device=dev))
+        return token_logp, token_logp.sum(1)
 
     # -------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -1043,12 +1109,8 @@ class KVDecoder:
         its max_strlen - 1 tokens (gct_grammar_mask in front of the selection, one launch more per step; None: no launch).
         Every row then ends with <eos> and parses; the guarantee is syntactic, not chemical.  return_logp stays the
         model's own log-probability (raw logits).  ValueError for max_strlen < 3 or a grammar of another vocabulary."""
-        V = self.model.out.weight.shape[0]
-        check_grammar(grammar, V, max_strlen - 1)
-        filtered = check_sample_filter(top_k, top_p, temperature, V) and algo == "multinomial"
-        if filtered and V > ops.SAMPLE_FILTER_MAX_VOCAB:
-            raise ValueError(f"top-k / nucleus / temperature sampling supports vocabularies up to "
-                             f"{ops.SAMPLE_FILTER_MAX_VOCAB} tokens, not {V}")
+        check_grammar(grammar, self.model.out.weight.shape[0], max_strlen - 1)
+        filt = self._check_sampling(algo, top_k, top_p, temperature)
         n, t0 = ys0.shape
         steps = max_strlen - 1
         lens = check_prefix_lens(prefix_lens, n, t0)
@@ -1058,42 +1120,26 @@ class KVDecoder:
                              "positional table")
         if self.off + t0 + steps > self.T:
             raise ValueError(f"prefix {t0} + {steps} steps exceeds the cache length {self.T - self.off}")
-        mode = {"greedy": 0, "multinomial": 1}[algo]
-        self.seed.fill_(int(seed) & 0x7FFFFFFFFFFFFFFF)
-        if filtered:
-            mode = FILTERED
-            self.filt.copy_(ops.sample_filter_settings(top_k, top_p, temperature, V))
-        self.want_logp = bool(return_logp)
-        self._set_grammar(grammar, steps, t0)
+        plan = StepPlan(self._set_sampling(algo, filt, seed, grammar, steps, t0), UNIFORM if lens is None else MIXED,
+                        grammar is not None, bool(return_logp))
         self.prefill(ys0, lens)
-        if self.want_logp:
+        self._select(plan)                                         # token t0 from the prefill's last position
+        if plan.logp:
             self.tok_logp.zero_()
-        self._select(mode)                                         # token t0 from the prefill's last position
-        if self.want_logp:
-            self._chosen_logp()
+            self._chosen_logp(plan)
         last = t0 + steps
         for i in range(1, steps):
-            self._run_step(mode, use_graphs)                       # consumes token t0+i-1, writes token t0+i
+            self._run_step(plan, use_graphs)                       # consumes token t0+i-1, writes token t0+i
             if check_every and (i + 1) % check_every == 0 and bool(self.done.all()):
                 last = t0 + i + 1
                 break
-        ys = self.ys[:, :last]
-        gen = ys[:, t0:] if lens is None else generated_tokens(ys, lens)
-        is_eos = gen == self.eos_id
-        if bool(is_eos.any(dim=1).all()):                          # reference break point
-            first = torch.where(is_eos, torch.arange(gen.size(1), device=gen.device)[None, :],
-                                gen.size(1)).min(dim=1).values
-            ys = ys[:, :t0 + int(first.max().item()) + 1]
-        if not self.want_logp:
+        lens = torch.full((n,), t0) if lens is None else lens
+        ys, is_eos = self._cut_at_eos(self.ys[:, :last], lens, t0)
+        if not plan.logp:
             return ys.clone()
-        # a row's generated span: from its own t0_r to its first <eos> (a finished row decodes on, and the capture
-        # warm-up and the replay guard run real steps past the position they restore): everything else is 0
-        start = torch.full((n,), t0, device=ys.device) if lens is None else lens.to(ys.device)
-        n_gen = torch.where(is_eos.any(dim=1), is_eos.int().argmax(dim=1) + 1, gen.size(1))
-        cols = torch.arange(ys.size(1), device=ys.device).view(1, -1)
-        span = (cols >= start.view(-1, 1)) & (cols < (start + n_gen).view(-1, 1)) & (ys != self.pad_id)
-        token_logp = torch.where(span, self.tok_logp[:, :ys.size(1)], torch.zeros((), device=ys.device))
-        return ys.clone(), token_logp, token_logp.sum(1)
+        # a row's generated span: from its own t0_r to its first <eos>, or all G columns without one
+        n_gen = torch.where(is_eos.any(dim=1), is_eos.int().argmax(dim=1) + 1, is_eos.size(1))
+        return (ys.clone(),) + self._span_logp(self.tok_logp, ys, lens, n_gen)
 
     @torch.no_grad()
     def generate_beam(self, ys0, beam_size, max_strlen=80, alpha=BEAM_ALPHA, check_every=8, use_graphs=False,
@@ -1116,9 +1162,7 @@ class KVDecoder:
             raise ValueError("generate_beam: max_strlen must be at least 2")
         if self.off + t0 + steps > self.T:
             raise ValueError(f"prefix {t0} + {steps} steps exceeds the cache length {self.T - self.off}")
-        dev = self.ys.device
-        self.want_logp = False                                     # (the beam scores are log-probabilities already)
-        self.grammar = None                                        # (beam rows keep their history behind kv_src)
+        dev, plan = self.ys.device, StepPlan(BEAM)
         self.prefill(ys0.to(dev).repeat_interleave(k, 0))
         scores, _, _ = beam_init(ns, k, dev)
         self.bscores.copy_(scores.view(-1))
@@ -1126,10 +1170,10 @@ class KVDecoder:
         self.blen.zero_()
         self.bdone.zero_()
         self.kv_src.copy_(torch.arange(self.n, dtype=torch.int32, device=dev).view(-1, 1).expand(-1, self.T))
-        self._select(BEAM)                                         # token t0 from the prefill's last position
+        self._select(plan)                                         # token t0 from the prefill's last position
         last = t0 + steps
         for i in range(1, steps):
-            self._run_step(BEAM, use_graphs)                       # consumes token t0+i-1, writes token t0+i
+            self._run_step(plan, use_graphs)                       # consumes token t0+i-1, writes token t0+i
             if check_every and (i + 1) % check_every == 0 and bool(self.bdone.all()):
                 last = t0 + i + 1
                 break
@@ -1194,16 +1238,13 @@ class KVDecoder:
                 row_of=i32(N), start_step=i32(N), item=i32(R), harvest=i32(R),
                 fresh=torch.zeros(R, dtype=torch.uint8, device=dev), next_item=i32(1), n_harvested=i32(1),
                 enable=i32(1))
-            st["state"] = ops.StreamState().set(
+            state = ops.StreamState()                             # the pool's entries under GctStreamState's own names,
+            st["state"] = state.set(                              # then the decoder's rows and the geometry
+                **{name: v for name, v in st.items() if name in state.slot},
                 ys=self.ys, valid=self.valid, done=self.done, row_off=self.row_off, pos=self.pos, z3=self.z3,
                 src_valid=self.src_valid, src_klen=self.src_klen, ckv=[c for c in self.ckv if c is not None],
-                item=st["item"], harvest=st["harvest"], fresh=st["fresh"], z_pool=st["z_pool"],
-                valid_pool=st["valid_pool"], klen_pool=st["klen_pool"], ckv_pool=st["ckv_pool"],
-                prefix_pool=st["prefix_pool"], prefix_len=st["prefix_len"], limit=st["limit"], out_ys=st["out_ys"],
-                out_len=st["out_len"], row_of=st["row_of"], start_step=st["start_step"], next_item=st["next_item"],
-                n_harvested=st["n_harvested"], enable=st["enable"], rows=R, items=N, ld_ys=self.ys.stride(0),
-                valid_sb=self.valid.stride(0), valid_off=0, T=T, width=T, t0_max=T, z_row=self.z3.stride(0), Lk=self.Lk,
-                ckv_row=st["ckv_row"], layers=len(dec.layers) if c2l else 0, pad_id=self.pad_id)
+                ld_ys=self.ys.stride(0), valid_sb=self.valid.stride(0), valid_off=0, T=T, width=T, t0_max=T,
+                z_row=self.z3.stride(0), Lk=self.Lk, layers=len(dec.layers) if c2l else 0, pad_id=self.pad_id)
             self._drop_stream_graphs()
         st["item_base"] = int(item_base)
         st["z_pool"].copy_(z.reshape(N, Le * lat))
@@ -1224,11 +1265,8 @@ class KVDecoder:
             chunk.zero_()
             chunk[:m] = dconds[lo:lo + m].float()
             cl = ops.small_linear_fwd(chunk, dec.embed_cond2lat.weight, dec.embed_cond2lat.bias).view(CH * nc, d)
-            for li, layer in enumerate(dec.layers):
-                a = layer.attn_2
-                ops.linear_fwd(cl, [a.k_linear.weight, a.v_linear.weight], [a.k_linear.bias, a.v_linear.bias],
-                               [kv, kv[:, d:]], 2 * d)
-                kv.view(-1, 2, d).sub_(self.zcv[li].view(1, 2, d))
+            for li in range(len(dec.layers)):
+                self._shifted_cond_kv(li, cl, kv)
                 pool[li][lo * nc:(lo + m) * nc].copy_(kv[:m * nc])
 
     def _drop_stream_graphs(self):
@@ -1261,11 +1299,7 @@ class KVDecoder:
             raise ValueError(f"generate_stream decodes greedy or multinomial, not {algo!r} (beam search keeps its rows "
                              "in step: generate_beam)")
         check_stream_model(self.model)
-        V = self.model.out.weight.shape[0]
-        filtered = check_sample_filter(top_k, top_p, temperature, V) and algo == "multinomial"
-        if filtered and V > ops.SAMPLE_FILTER_MAX_VOCAB:
-            raise ValueError(f"top-k / nucleus / temperature sampling supports vocabularies up to "
-                             f"{ops.SAMPLE_FILTER_MAX_VOCAB} tokens, not {V}")
+        filt = self._check_sampling(algo, top_k, top_p, temperature)
         if ys0.dim() != 2 or ys0.shape[1] < 1:
             raise ValueError(f"ys0 must be [N, t0_max >= 1], got {list(ys0.shape)}")
         N, t0 = ys0.shape
@@ -1277,7 +1311,7 @@ class KVDecoder:
         lens = check_prefix_lens(prefix_lens, N, t0)
         lens = torch.full((N,), t0, dtype=torch.int64) if lens is None else lens
         cap = check_max_new_tokens(max_new_tokens, N, steps)
-        check_grammar(grammar, V, cap)
+        check_grammar(grammar, self.model.out.weight.shape[0], cap)
         W = t0 + steps
         pe_rows = self.dec.pe.pe.shape[1]
         if W > pe_rows:
@@ -1292,7 +1326,7 @@ class KVDecoder:
                              "called with another geometry since); call start_stream again")
         if W > self.T:
             raise ValueError(f"prefix {t0} + {steps} steps exceeds the cache length {self.T}")
-        dev, R = self.ys.device, st["rows"]
+        R = st["rows"]
         cols = torch.arange(t0).view(1, -1)
         prefix = torch.where(cols < lens.view(-1, 1), ys0.cpu(), torch.full_like(ys0.cpu(), self.pad_id))
         st["prefix_pool"][:, :t0].copy_(prefix)                    # (columns behind t0 are never read: prefix_len <= t0)
@@ -1302,16 +1336,11 @@ class KVDecoder:
         for name, v in (("out_len", 0), ("row_of", -1), ("start_step", -1), ("item", -1), ("harvest", -1), ("fresh", 0),
                         ("next_item", 0), ("n_harvested", 0), ("enable", 1)):
             st[name].fill_(v)
-        mode = {"greedy": 0, "multinomial": 1}[algo]
-        self.seed.fill_(int(seed) & 0x7FFFFFFFFFFFFFFF)
-        if filtered:
-            mode = FILTERED
-            self.filt.copy_(ops.sample_filter_settings(top_k, top_p, temperature, V))
-        self.want_logp = bool(return_logp)
-        self._set_grammar(grammar, steps, t0)                      # (a streamed row reads limit[item] / prefix_len[item])
-        if self.want_logp:
+        # (a streamed row reads its budget and prefix length per item: limit[item] / prefix_len[item])
+        plan = StepPlan(self._set_sampling(algo, filt, seed, grammar, steps, t0), STREAM, grammar is not None,
+                        bool(return_logp))
+        if plan.logp:
             st["out_logp"].zero_()
-        self.ragged = True
         self.pos.fill_(-1)                                         # the first step consumes every row's token 0
         self.row_off.zero_()
         self.ys.fill_(self.pad_id)
@@ -1320,94 +1349,69 @@ class KVDecoder:
         # list scheduling ends within sum / R + max steps (Graham): a loop that runs past it has lost an item
         most = (N // R + 2) * W + check_every
         launched = 0
-        self.streaming = True
-        try:
-            st["state"].refill()                                   # the first wave enters like every later item
-            while True:
-                self._run_step(mode, use_graphs)
-                launched += 1
-                if launched % check_every == 0:
-                    if int(st["n_harvested"].item()) >= N:
-                        break
-                    if launched > most:
-                        raise RuntimeError(f"generate_stream: {int(st['n_harvested'].item())} of {N} items after "
-                                           f"{launched} steps")
-        finally:
-            self.streaming = False
+        st["state"].refill()                                       # the first wave enters like every later item
+        while True:
+            self._run_step(plan, use_graphs)
+            launched += 1
+            if launched % check_every == 0:
+                if int(st["n_harvested"].item()) >= N:
+                    break
+                if launched > most:
+                    raise RuntimeError(f"generate_stream: {int(st['n_harvested'].item())} of {N} items after "
+                                       f"{launched} steps")
         out_len, start = st["out_len"].cpu().long(), st["start_step"].cpu().long()
         record = dict(steps=int((start + lens + out_len - 1).max()) if N else 0, launched=launched,
                       row_of=st["row_of"].cpu().long(), start_step=start, out_len=out_len,
                       harvested=int(st["n_harvested"].item()))
-        ys = st["out_ys"][:, :W]
-        is_eos = generated_tokens(ys, lens) == self.eos_id
-        if N and bool(is_eos.any(dim=1).all()):                    # generate()'s cut: the longest item's <eos>
-            first = is_eos.int().argmax(dim=1)
-            ys = ys[:, :t0 + int(first.max().item()) + 1]
-        if not self.want_logp:
+        ys, _ = self._cut_at_eos(st["out_ys"][:, :W], lens, t0)    # generate()'s cut: the longest item's <eos>
+        if not plan.logp:
             return ys.clone(), record
-        # an item's generated span; a held row (capture warm-up, replay guard) decodes past its item's end meanwhile
-        t0_i, cols = lens.to(dev).view(-1, 1), torch.arange(ys.size(1), device=dev).view(1, -1)
-        span = (cols >= t0_i) & (cols < t0_i + out_len.to(dev).view(-1, 1))
-        token_logp = torch.where(span, st["out_logp"][:, :ys.size(1)], torch.zeros((), device=dev))
-        return ys.clone(), record, token_logp, token_logp.sum(1)
+        # an item's generated span: the out_len tokens the refill handed out
+        return (ys.clone(), record) + self._span_logp(st["out_logp"], ys, lens, out_len)
 
-    def _run_step(self, mode, use_graphs):
-        if not use_graphs:
-            self._advance(mode)
-            return
-        key = (mode, "mixed") if self.ragged else mode    # a mixed-prefix step passes row_off: a graph of its own
-        if self.streaming:
-            key = (mode, STREAM)                          # step + selection by item + refill
-        if self.grammar is not None and mode != BEAM:     # the unit holds the mask kernel: a graph of its own
-            key = (key if isinstance(key, tuple) else (key, "uniform")) + (GRAMMAR,)
-        if self.want_logp and mode != BEAM:               # the unit holds one more kernel: a graph of its own
-            key = (key if isinstance(key, tuple) else (key, "uniform")) + (LOGP,)
-        g = self.graphs.get(key)
-        if g is False:                                  # no usable graph for these buffers (capture failed, or replay is
-            self._advance(mode)                         # the slower launch mode on this box): same kernels, eagerly
-            return
+    def _run_step(self, plan, use_graphs):
+        g = self.graphs.get(plan.key) if use_graphs else False
         if g is None:
-            g = self._capture(mode, key)
-            if g is None:
-                return                                  # _capture ran the step eagerly
-        g.replay()
+            self._capture(plan)                         # leaves the graph (or False) in self.graphs and runs this step
+        elif g is False:                                # no usable graph for these buffers (capture failed, or replay is
+            self._advance(plan)                         # the slower launch mode on this box): same kernels, eagerly
+        else:
+            g.replay()
 
-    def _state(self):
-        return tuple(t.clone() for t in self._state_tensors())
-
-    def _restore(self, keep):
-        for t, k in zip(self._state_tensors(), keep):
+    @staticmethod
+    def _restore(keep):
+        for t, k in keep:
             t.copy_(k)
 
-    def _state_tensors(self):
+    def _state_tensors(self, plan):
         """Everything a step + selection writes besides the caches' next row (the beam state included)."""
         base = (self.pos, self.ys, self.valid, self.done, self.bscores, self.bfin, self.blen, self.bparent,
                 self.kv_src, self.bdone)
-        if not self.streaming:
+        if plan.layout != STREAM:
             return base
         st = self.stream                                  # (the refill is held while a state is kept: _hold_refill)
         return base + (self.row_off, st["item"], st["next_item"], st["n_harvested"])
 
-    def _hold_refill(self, hold):
+    def _hold_refill(self, plan, hold):
         """Continuous batching: the capture warm-up and the replay guard execute real steps and then restore
         _state_tensors().  A refill in one of those steps would overwrite a row's latent rows, condition rows and cache
         slots, which no restore covers -- so they run with the device `enable` word at 0: a row that finishes is held
         (it decodes on, as a finished row of the plain path does) and the restore puts it back."""
-        if self.streaming:
+        if plan.layout == STREAM:
             self.stream["enable"].fill_(0 if hold else 1)
 
-    def _capture(self, mode, key):
-        """Capture step + select into one graph; returns it, or None after running the step eagerly (capture failed, or
-        the replay guard found replay slower than eager launches on this box)."""
+    def _capture(self, plan):
+        """Capture step + select into one graph, keep it under plan.key and replay it -- or keep False and run the step
+        eagerly (capture failed, or the replay guard found replay slower than eager launches on this box)."""
         # Warm-up run on a side stream (lazy LDS opt-ins, allocator), then capture.  The warm-up really executes a
         # step (it advances the device position and writes a token), so the state it touches is restored before
         # the capture; a capture itself executes nothing.
-        self._hold_refill(True)
-        keep = self._state()
+        self._hold_refill(plan, True)
+        keep = [(t, t.clone()) for t in self._state_tensors(plan)]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            self._advance(mode)
+            self._advance(plan)
         torch.cuda.current_stream().wait_stream(s)
         # (the key / value row the warm-up appended is rewritten with the same values by the replay below)
         self._restore(keep)
@@ -1419,34 +1423,29 @@ class KVDecoder:
             # thread_local: another thread's runtime calls (the RCCL watchdog of a data-parallel job queries
             # events) must not invalidate this thread's capture
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self._advance(mode)
-        except RuntimeError as exc:                     # no graph for these buffers: same kernels, launched eagerly
+                self._advance(plan)
+        except RuntimeError as exc:
             import warnings
             warnings.warn(f"KVDecoder: graph capture failed ({exc}); decoding without graph replay")
             torch.cuda.synchronize()
             self._restore(keep)
-            self.graphs[key] = False
+            g = None
+        fast = g is not None and (not REPLAY_GUARD or self._replay_is_fast(plan, g, keep))
+        self._hold_refill(plan, False)
+        self.graphs[plan.key] = g if fast else False
+        if fast:
+            g.replay()
+        else:                                           # no graph for these buffers: same kernels, launched eagerly
             self.graph_replay = False
-            self._hold_refill(False)
-            self._advance(mode)
-            return None
-        self.graphs[key] = g
-        fast = not REPLAY_GUARD or self._replay_is_fast(mode, g, keep)
-        self._hold_refill(False)
-        if not fast:
-            self.graphs[key] = False
-            self.graph_replay = False
-            self._advance(mode)
-            return None
-        return g
+            self._advance(plan)
 
-    def _replay_is_fast(self, mode, g, keep):
+    def _replay_is_fast(self, plan, g, keep):
         """Replay guard: a few steps launched eagerly and a few replayed, timed on the device, state restored after
         each.  Replay is the faster way to issue the ~70 launches of a step everywhere it behaves; on boxes where it is
         clearly the slower one (round 2: 3-13x) the decoder keeps launching eagerly, says so once, and leaves the
         numbers and the graph's census in `self.replay_probe` for the caller (bench.py prints them)."""
-        ahead = int(keep[0].item())                                      # position of the row that is furthest along
-        if self.streaming:
+        ahead = int(keep[0][1].item())                                     # position of the row that is furthest along
+        if plan.layout == STREAM:
             ahead -= int(self.row_off.min().item())
         room = self.T - self.off - (ahead + 1) - 1                       # steps the caches still have room for
         k = min(4, room)
@@ -1463,9 +1462,7 @@ class KVDecoder:
             self._restore(keep)
             return e0.elapsed_time(e1) / k
 
-        def eager():
-            self._advance(mode)
-
+        eager = functools.partial(self._advance, plan)
         g.replay()                                                       # first replay (instantiation, upload): untimed
         self._restore(keep)
         t_graph = min(timed(g.replay), timed(g.replay))

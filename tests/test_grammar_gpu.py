@@ -424,3 +424,81 @@ def test_sampler_returns_well_formed_smiles(algo, stream_rows):
         assert parses(toks + ["<eos>"]), s
     free = make_sampler("VaetfSampling", "vaetf", algo, stream_rows).sample_smiles(n, zs=z, toklen=toklen)[0]
     assert not all(parses(tokenize(s) + ["<eos>"]) for s in free)                   # the option did something
+
+
+# ----------------------------------------------------------------- 6. calls on one decoder do not leak into each other
+def _call_sequence(graphs):
+    """[(graph key of the call's step unit, call)]: the six kinds of call, each returning a tuple of tensors.  4 plain rows
+    with prefixes of 3 / 9 / 5 / 3 tokens in ONE start() geometry; a pool of 6 items on 2 stream rows (each row refills);
+    max_strlen 12, max_total_len 40."""
+    rows, pool = make_pool("pscavaetf", [3, 9, 5, 3], 1, 41), make_pool("pscavaetf", [3, 9, 5, 3, 6, 2], 1, 42)
+    lens = rows["lens"]
+    uniform, mixed = rows["ys0"][:, :3].cuda(), rows["ys0"].cuda()               # (every row has >= 3 real tokens)
+
+    def plain(kd, ys0, **kw):
+        kd.start(cu(rows["z"]), cu(rows["src_mask"]), cu(rows["dconds"]), max_total_len=40)
+        out = kd.generate(ys0, 12, use_graphs=graphs, **kw)
+        return out if isinstance(out, tuple) else (out,)
+
+    def stream(kd):
+        kd.start_stream(cu(pool["z"]), cu(pool["src_mask"]), cu(pool["dconds"]), rows=2, max_total_len=40)
+        ys, rec, tl, lp = kd.generate_stream(pool["ys0"].cuda(), 12, prefix_lens=pool["lens"], grammar=GR31,
+                                             return_logp=True, use_graphs=graphs)
+        assert rec["harvested"] == 6 and all(int((rec["row_of"] == r).sum()) >= 2 for r in range(2))
+        return ys, tl, lp, rec["out_len"], rec["row_of"], rec["start_step"]
+
+    return [
+        (0, lambda kd: plain(kd, uniform)),
+        ((1, "mixed", "logp"), lambda kd: plain(kd, mixed, prefix_lens=lens, algo="multinomial", seed=5,
+                                                return_logp=True)),
+        ((0, "mixed", "grammar"), lambda kd: plain(kd, mixed, prefix_lens=lens, grammar=GR31)),
+        ((0, "stream", "grammar", "logp"), stream),
+        (0, lambda kd: plain(kd, uniform)),
+        (("filtered", "mixed"), lambda kd: plain(kd, mixed, prefix_lens=lens, **HOW["filtered"])),
+    ], (rows, uniform)
+
+
+def _same(got, want):
+    """Token ids, lengths and log-probabilities alike: the same kernels on the same shapes, so bit for bit."""
+    return len(got) == len(want) and all(g.dtype == w.dtype and torch.equal(g.cpu(), w.cpu()) and
+                                         (not g.dtype.is_floating_point or same_bits(g, w)) for g, w in zip(got, want))
+
+
+@pytest.mark.parametrize("graphs", [True, False])
+def test_calls_on_one_decoder_do_not_leak_into_each_other(graphs):
+    """Uniform greedy, mixed multinomial with log-probabilities, mixed greedy with a grammar, a stream with grammar and
+    log-probabilities, uniform greedy again, mixed filtered multinomial with neither -- on ONE decoder, each result equal
+    to the same call on a fresh decoder.  Then beam search (k = 2, another geometry) and uniform greedy once more.
+    Graph keys: every call's unit is captured under the key StepPlan.key predicts and none is False.  The dict is
+    checked after every call rather than once at the end, because a captured graph holds the addresses of the rows it
+    was captured against: the three plain calls share the 4-row geometry and their graphs, the 2 stream rows and the
+    beam rows are other buffers, and start() drops the graphs of the rows it replaces."""
+    model = model_of("pscavaetf")
+    calls, (rows, uniform) = _call_sequence(graphs)
+    kd = KVDecoder(model, PAD, SOS, EOS)
+    held = [{0}, {0, (1, "mixed", "logp")}, {0, (1, "mixed", "logp"), (0, "mixed", "grammar")},
+            {(0, "stream", "grammar", "logp")}, {0}, {0, ("filtered", "mixed")}]
+    seen = set()
+    for i, ((key, call), want_keys) in enumerate(zip(calls, held)):
+        got, want = call(kd), call(KVDecoder(model, PAD, SOS, EOS))
+        assert _same(got, want), (graphs, i, key)
+        assert key in want_keys
+        if graphs and kd.graph_replay:                   # (the replay guard may choose eager launches on a box)
+            assert set(kd.graphs) == want_keys, (i, set(kd.graphs))
+            assert all(g is not False for g in kd.graphs.values()), (i, kd.graphs)
+            seen |= set(kd.graphs)
+        elif not graphs:
+            assert kd.graphs == {}
+    if graphs and kd.graph_replay:
+        assert seen == {k for k, _ in calls}
+
+    def beam(d):
+        d.start(cu(rows["z"]), cu(rows["src_mask"]), cu(rows["dconds"]), max_total_len=40, beams=2)
+        return d.generate_beam(uniform, 2, 12, use_graphs=graphs)
+
+    assert _same(beam(kd), beam(KVDecoder(model, PAD, SOS, EOS)))
+    if graphs and kd.graph_replay:
+        assert set(kd.graphs) == {"beam"} and kd.graphs["beam"] is not False
+    assert _same(calls[0][1](kd), calls[0][1](KVDecoder(model, PAD, SOS, EOS)))
+    if graphs and kd.graph_replay:
+        assert set(kd.graphs) == {0} and kd.graphs[0] is not False
