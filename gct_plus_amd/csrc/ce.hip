@@ -6,6 +6,7 @@
 // teacher-forced logits, gct_chosen_logp the token a decode step has just picked.  Both go through wave_token_logp, the
 // same wave-per-row log-softmax; every output has one writer and a fixed summation order (no atomics).
 #include "common.h"
+#include "decode_rows.h"
 
 int gct_final_sum(const float* ws, int n, float scale, float* out, hipStream_t st);
 
@@ -21,12 +22,8 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
     const int64_t t = target[row];
     if (t == pad_id) continue;  // wave-uniform
     const float* lr = logits + row * V;
-    float mx = -INFINITY;
-    for (int c = lane; c < V; c += 64) mx = fmaxf(mx, lr[c]);
-    mx = gct_wave_max(mx);
-    float se = 0.f;
-    for (int c = lane; c < V; c += 64) se += expf(lr[c] - mx);
-    se = gct_wave_sum(se);
+    float mx, se;
+    gct_wave_softmax_stats(lr, V, lane, mx, se);
     if (lane == 0 && t >= 0 && t < V) acc += (mx + logf(se)) - lr[t];
   }
   if (lane == 0) sh[wave] = acc;
@@ -48,12 +45,8 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
       for (int c = lane; c < V; c += 64) dr[c] = 0.f;
       continue;
     }
-    float mx = -INFINITY;
-    for (int c = lane; c < V; c += 64) mx = fmaxf(mx, lr[c]);
-    mx = gct_wave_max(mx);
-    float se = 0.f;
-    for (int c = lane; c < V; c += 64) se += expf(lr[c] - mx);
-    se = gct_wave_sum(se);
+    float mx, se;
+    gct_wave_softmax_stats(lr, V, lane, mx, se);
     const float inv = 1.0f / se;
     for (int c = lane; c < V; c += 64) {
       float pr = expf(lr[c] - mx) * inv;
@@ -129,7 +122,7 @@ __global__ __launch_bounds__(256) void seq_logp_kernel(const float* __restrict__
   }
 }
 
-// one wave per decode row, as select_token_kernel: the column the selection has just written
+// one wave per decode row, as select_token_kernel: the column the selection has just written (gct_row_slot)
 __global__ __launch_bounds__(256) void chosen_logp_kernel(const float* __restrict__ logits, int V,
                                                           const int64_t* __restrict__ ys, int64_t ld_ys,
                                                           const int32_t* __restrict__ pos,
@@ -141,13 +134,9 @@ __global__ __launch_bounds__(256) void chosen_logp_kernel(const float* __restric
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = blockIdx.x * 4 + wave;
   if (row >= n) return;
-  int p = *pos + 1;
-  if (row_off) p -= row_off[row];
-  int dst = row;
-  if (item) {                                           // uniform over the wave: a whole wave leaves
-    dst = item[row];
-    if (dst < 0 || p < prefix_len[dst]) return;         // parked, or a prefix token: not a generated one
-  }
+  const GctRowSlot s = gct_row_slot(*pos + 1, row, row_off != nullptr, row_off, item != nullptr, item, prefix_len);
+  if (!s.acts()) return;                                // parked, or a prefix token: not a generated one (uniform
+  const int p = s.pos, dst = s.item;                    // over the wave: a whole wave leaves)
   if (p < 0 || p >= ld_out || p >= ld_ys || dst >= out_rows) return;
   const int64_t tok = ys[(int64_t)row * ld_ys + p];
   float lp = 0.f;

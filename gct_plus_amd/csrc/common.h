@@ -84,7 +84,8 @@ __device__ __forceinline__ bool gct_drop_keep(uint4 bits, int e, uint32_t col, u
 }
 
 // ---------------------------------------------------------------- wave helpers
-__device__ __forceinline__ float gct_wave_sum(float v) {
+template <typename T>
+__device__ __forceinline__ T gct_wave_sum(T v) {             // float or int
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
@@ -93,6 +94,40 @@ __device__ __forceinline__ float gct_wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
+}
+__device__ __forceinline__ int gct_wave_max_i32(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+// or (use_xor: xor) of the 64 lanes' words
+__device__ __forceinline__ uint64_t gct_wave_or64(uint64_t v, bool use_xor) {
+  uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t ol = (uint32_t)__shfl_xor((int)lo, o, 64), oh = (uint32_t)__shfl_xor((int)hi, o, 64);
+    lo = use_xor ? lo ^ ol : lo | ol;
+    hi = use_xor ? hi ^ oh : hi | oh;
+  }
+  return ((uint64_t)hi << 32) | lo;
+}
+// (value, index) argmax over the wave, on every lane: the larger value, then the lower index
+__device__ __forceinline__ void gct_wave_argmax(float& v, int& i) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(v, o, 64);
+    const int oi = __shfl_xor(i, o, 64);
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+  }
+}
+// softmax statistics of one row lr[0, V) over the wave: mx = max x, se = sum exp(x - mx), on every lane
+__device__ __forceinline__ void gct_wave_softmax_stats(const float* lr, int V, int lane, float& mx, float& se) {
+  mx = -INFINITY;
+  for (int c = lane; c < V; c += 64) mx = fmaxf(mx, lr[c]);
+  mx = gct_wave_max(mx);
+  se = 0.f;
+  for (int c = lane; c < V; c += 64) se += expf(lr[c] - mx);
+  se = gct_wave_sum(se);
 }
 
 // bijective XCD-aware remap of a 1-D block id: blocks that share an XCD (id % 8)

@@ -9,11 +9,15 @@
 //   gct_stream_refill : continuous batching -- rows that finished hand out their tokens and take the next pool item
 //   gct_attn_decode_beam / gct_beam_select : the same two for beam search, with the self-attention caches
 //                      shared by ancestry through a per-row map (kv_src) instead of copied
-// Both are tiny and HBM/latency-bound; they exist so a whole decode step is a fixed kernel
-// chain with no host round trip (graph-capturable).
+//   gct_attn_decode_z / gct_decode_embed / gct_decode_advance : cross-attention over the latent rows, one position's
+//                      embedding, the device counter
+// All are small and HBM/latency-bound; they exist so a whole decode step is a fixed kernel chain with no host round
+// trip (graph-capturable).  Where a row of a step sits is stated once, in decode_rows.h.
 #include <climits>
+#include <type_traits>
 
 #include "common.h"
+#include "decode_rows.h"
 
 namespace {
 
@@ -23,8 +27,8 @@ namespace {
 // (row Lc) and scored from registers, so ONE captured graph serves every step of the decode loop.
 // MAPPED (beam search, pos required): key / value j of row b and the valid flag masking it live in physical row
 // kv_src[b][j] (Lc_host = cache rows, the bound of every map entry's position); the step's own key still goes to row b.
-// RAGGED (pos required, not MAPPED): row b's own position is *pos - row_off[b] (a batch of prefixes of different lengths
-// that share one device counter): Lold = cache_off + *pos - row_off[b], and the step's key is appended at that row.
+// RAGGED (pos required, not MAPPED): row b sits at its own position (gct_row_slot): Lold = cache_off + that position,
+// and the step's key is appended at that row.
 template <int DK, bool MAPPED, bool RAGGED>
 __global__ __launch_bounds__(256) void attn_decode_kernel(
     const float* __restrict__ q, int64_t ldq, float* __restrict__ k, float* __restrict__ v,
@@ -44,7 +48,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
   // least one key, so they weigh exactly 0: their cache rows are never read (the padded latent positions of the
   // cross-attention memory are most of it at MOSES-like lengths)
   int Lold;                                                                        // keys already in the cache
-  if constexpr (RAGGED) Lold = cache_off + *pos - row_off[b];                      // uniform over the wave
+  if constexpr (RAGGED) Lold = gct_row_slot(cache_off + *pos, b, true, row_off).pos;   // uniform over the wave
   else Lold = pos ? cache_off + *pos : (klen ? min(klen[b], Lc_host) : Lc_host);   // klen clamped to Lc, as in _z
   const int Lc = pos ? Lold + 1 : Lold;
   const float* qp = q + (int64_t)b * ldq + h * DK;
@@ -234,20 +238,17 @@ __global__ __launch_bounds__(256) void attn_decode_z_kernel(
 }
 
 // x[b][:] = table[ys[b][*pos]] * scale + pe[pe_off + *pos][:]   (Embeddings + PositionalEncoding of ONE position)
-// RAGGED: row b's position is *pos - row_off[b] (one load per thread; consecutive threads still store consecutive float4)
+// RAGGED: row b at its own position (gct_row_slot; one load per thread, consecutive threads still store float4s in a row)
 template <bool RAGGED>
-__global__ __launch_bounds__(256) void decode_embed_kernel(const int64_t* __restrict__ ys, int64_t ld_ys,
-                                                           const int32_t* __restrict__ pos, int pe_off,
-                                                           const float* __restrict__ table, int vocab,
-                                                           const float* __restrict__ pe, float* __restrict__ out,
-                                                           int n, int d, float scale,
-                                                           const int32_t* __restrict__ row_off) {
+__global__ __launch_bounds__(256) void decode_embed_kernel(
+    const int64_t* __restrict__ ys, int64_t ld_ys, const int32_t* __restrict__ pos, int pe_off,
+    const float* __restrict__ table, int vocab, const float* __restrict__ pe, float* __restrict__ out, int n, int d,
+    float scale, const int32_t* __restrict__ row_off) {
   const int p0 = *pos;
   const int64_t total = (int64_t)n * (d / 4);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int b = (int)(i / (d / 4)), c = (int)(i - (int64_t)b * (d / 4));
-    int p = p0;
-    if constexpr (RAGGED) p -= row_off[b];
+    const int p = gct_row_slot(p0, b, RAGGED, row_off).pos;
     int64_t tok = ys[(int64_t)b * ld_ys + p];
     tok = tok < 0 ? 0 : (tok >= vocab ? vocab - 1 : tok);
     const float4 e = *reinterpret_cast<const float4*>(table + tok * d + c * 4);
@@ -263,45 +264,82 @@ __global__ void decode_advance_kernel(int32_t* pos) { *pos += 1; }
 // and a row whose cumulative sums never exceed u takes the fallback (the last token of nonzero weight)
 __device__ __forceinline__ float u01_draw(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
+// ---------------------------------------------------------------------------------------------- token selection
+// What the two select kernels share.  None of the three helpers holds a multiply that feeds an add, so they compute the
+// same under select_token_filtered_kernel's `fp contract(off)` (the pragma is lexical and does not reach them).
+//
+// The prologue: the row's slot (gct_row_slot at the column *pos_dev + 1, or pos_host), the seed_dev override of the
+// by-value seed, and the Philox key (row | item_base + item, token position) -- a streamed row's draw depends neither on
+// the row that makes it nor on the slice of a larger pool the item came in.  false: the wave leaves -- no such row, a
+// parked row, a position inside the item's prefix (the slot keeps the prefix token the refill laid there: ys and valid, done
+// untouched) or a streamed row without room for its valid flag.  All of it is uniform over the wave.
+template <bool RAGGED, bool STREAM>
+__device__ __forceinline__ bool select_prologue(int row, int n, int pos_host, const int32_t* pos_dev, const int32_t* row_off,
+                                                const int32_t* item, const int32_t* prefix_len, int item_base,
+                                                int valid_off, int64_t valid_sb, const uint64_t* seed_dev, GctRng& rng,
+                                                int& pos, uint32_t& key) {
+  static_assert(RAGGED || !STREAM, "streamed rows sit at their own positions");
+  const int step = pos_dev ? *pos_dev + 1 : pos_host;
+  if (seed_dev) rng = gct_rng_make(*seed_dev, 0xDEC0DEu);
+  if (row >= n) return false;
+  const GctRowSlot s = gct_row_slot(step, row, RAGGED, row_off, STREAM, item, prefix_len);
+  pos = s.pos;
+  key = (uint32_t)(STREAM ? item_base + s.item : row);
+  return !STREAM || (s.acts() && valid_off + pos < valid_sb);
+}
+
+// One 64-token chunk of the inverse-CDF scan: lane l holds the probability p of token c = c0 + l; the first token
+// whose cumulative sum exceeds u takes the hit.  (p > 0: the wave scan is not monotone in fp32 -- a lane of probability
+// exactly 0, a token the grammar mask forbids, may hold a prefix sum one ulp above its left neighbour's -- so such a
+// lane never takes the hit.)
+__device__ __forceinline__ void cdf_scan_chunk(float p, int c0, int V, float u, int lane, float& cum, bool& found,
+                                               int& pick) {
+  float incl = p;                                           // inclusive scan over the wave
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const float t = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += t;
+  }
+  const bool hit = !found && c0 + lane < V && (cum + incl) > u && p > 0.f;
+  const unsigned long long ball = __ballot(hit);
+  if (ball && !found) {
+    pick = c0 + (int)__builtin_ctzll(ball);
+    found = true;
+  }
+  cum += __shfl(incl, 63, 64);
+}
+
+// The commit: the token, its key-valid flag and the sticky finished flag.
+__device__ __forceinline__ void commit_token(int lane, int row, int pos, int tok, int64_t* ys, int64_t ld_ys,
+                                             uint8_t* valid, int64_t valid_sb, int valid_off, uint8_t* done,
+                                             int64_t pad_id, int64_t eos_id) {
+  if (lane != 0) return;
+  ys[(int64_t)row * ld_ys + pos] = tok;
+  if (valid) valid[(int64_t)row * valid_sb + valid_off + pos] = (tok != pad_id) ? 1 : 0;
+  if (done && tok == eos_id) done[row] = 1;
+}
+
 // one wave per sample row.  pos_dev (nullable): device-side step counter -- the token is written at ys[.., *pos_dev + 1]
 // and valid[.., valid_off + *pos_dev + 1]; seed_dev (nullable) replaces the by-value seed of the multinomial draw.
-// RAGGED (pos_dev required): row r's position is *pos_dev - row_off[r] + 1 (uniform over the wave; the Philox key stays
-// (row, token position))
-// STREAM (continuous batching, RAGGED required): row r decodes pool item item[r].  A parked row (item < 0) writes
-// nothing; while the position is inside the item's prefix the slot keeps the prefix token the refill laid there (ys and
-// valid, done untouched); the Philox key is (item_base + item, token position), so a draw does not depend on the row
-// that makes it, nor on the slice of a larger pool the item came in.
+// RAGGED (pos_dev required) / STREAM (continuous batching, RAGGED required): the row sits at its own position and
+// decodes pool item item[r] (select_prologue).  The two select kernels take one parameter list; filt is the other one's.
 template <bool RAGGED, bool STREAM>
-__global__ __launch_bounds__(256) void select_token_kernel(const float* __restrict__ logits, int V,
-                                                           int64_t* ys, int64_t ld_ys, int pos_host,
-                                                           uint8_t* valid, int64_t valid_sb,
-                                                           uint8_t* done, float* probs_out, int n,
-                                                           int mode, int64_t pad_id, int64_t eos_id,
-                                                           GctRng rng, const int32_t* __restrict__ pos_dev,
-                                                           int valid_off, const uint64_t* __restrict__ seed_dev,
-                                                           const int32_t* __restrict__ row_off,
-                                                           const int32_t* __restrict__ item,
-                                                           const int32_t* __restrict__ prefix_len, int item_base) {
-  static_assert(RAGGED || !STREAM, "streamed rows sit at their own positions");
-  int pos = pos_dev ? *pos_dev + 1 : pos_host;
-  if (seed_dev) rng = gct_rng_make(*seed_dev, 0xDEC0DEu);
+__global__ __launch_bounds__(256) void select_token_kernel(
+    const float* __restrict__ logits, int V, int64_t* ys, int64_t ld_ys, int pos_host, uint8_t* valid, int64_t valid_sb,
+    uint8_t* done, float* probs_out, int n, int mode, int64_t pad_id, int64_t eos_id, GctRng rng,
+    const int32_t* __restrict__ pos_dev, int valid_off, const uint64_t* __restrict__ seed_dev,
+    const int32_t* __restrict__ row_off, const GctSampleFilter* __restrict__ /*filt*/, const int32_t* __restrict__ item,
+    const int32_t* __restrict__ prefix_len, int item_base) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = blockIdx.x * 4 + wave;
-  if (row >= n) return;
-  if constexpr (RAGGED) pos -= row_off[row];
-  uint32_t key = (uint32_t)row;
-  if constexpr (STREAM) {                                   // uniform over the wave: a whole wave leaves
-    const int it = item[row];
-    if (it < 0 || pos < prefix_len[it] || valid_off + pos >= valid_sb) return;
-    key = (uint32_t)(item_base + it);
-  }
+  int pos;
+  uint32_t key;
+  if (!select_prologue<RAGGED, STREAM>(row, n, pos_host, pos_dev, row_off, item, prefix_len, item_base, valid_off,
+                                       valid_sb, seed_dev, rng, pos, key))
+    return;
   const float* lr = logits + (int64_t)row * V;
-  float mx = -INFINITY;
-  for (int c = lane; c < V; c += 64) mx = fmaxf(mx, lr[c]);
-  mx = gct_wave_max(mx);
-  float se = 0.f;
-  for (int c = lane; c < V; c += 64) se += expf(lr[c] - mx);
-  se = gct_wave_sum(se);
+  float mx, se;
+  gct_wave_softmax_stats(lr, V, lane, mx, se);
   const float inv = 1.0f / se;
   int best = 0;
   if (mode == 0) {
@@ -313,12 +351,7 @@ __global__ __launch_bounds__(256) void select_token_kernel(const float* __restri
       if (probs_out) probs_out[(int64_t)row * V + c] = p;
       if (p > bp) { bp = p; bi = c; }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float op = __shfl_xor(bp, off, 64);
-      const int oi = __shfl_xor(bi, off, 64);
-      if (op > bp || (op == bp && oi < bi)) { bp = op; bi = oi; }
-    }
+    gct_wave_argmax(bp, bi);
     best = bi;
   } else {
     // multinomial: inverse CDF with one Philox uniform per (row, position)
@@ -332,36 +365,17 @@ __global__ __launch_bounds__(256) void select_token_kernel(const float* __restri
       float p = c < V ? expf(lr[c] - mx) * inv : 0.f;
       if (p > 0.f) lastnz = c;
       if (probs_out && c < V) probs_out[(int64_t)row * V + c] = p;
-      float incl = p;                                   // inclusive scan over the wave
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const float t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-      }
-      // (p > 0: the wave scan is not monotone in fp32 -- a lane of probability exactly 0, a token the grammar mask
-      // forbids, may hold a prefix sum one ulp above its left neighbour's -- so such a lane never takes the hit)
-      const bool hit = !found && c < V && (cum + incl) > u && p > 0.f;
-      const unsigned long long ball = __ballot(hit);
-      if (ball && !found) {
-        pick = c0 + (int)__builtin_ctzll(ball);
-        found = true;
-      }
-      cum += __shfl(incl, 63, 64);
+      cdf_scan_chunk(p, c0, V, u, lane, cum, found, pick);
     }
     if (!found) {
       // rounding fallback (the sum stayed below u): the last token of nonzero probability -- V - 1, unless its logit is
       // -inf (a token the grammar mask forbids) or underflows
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) lastnz = max(lastnz, __shfl_xor(lastnz, off, 64));
+      lastnz = gct_wave_max_i32(lastnz);
       if (lastnz >= 0) pick = lastnz;
     }
     best = pick;
   }
-  if (lane == 0) {
-    ys[(int64_t)row * ld_ys + pos] = best;
-    if (valid) valid[(int64_t)row * valid_sb + valid_off + pos] = (best != pad_id) ? 1 : 0;
-    if (done && best == eos_id) done[row] = 1;
-  }
+  commit_token(lane, row, pos, best, ys, ld_ys, valid, valid_sb, valid_off, done, pad_id, eos_id);
 }
 
 // ---------------------------------------------------------------------------------------------- filtered sampling
@@ -371,29 +385,23 @@ __global__ __launch_bounds__(256) void select_token_kernel(const float* __restri
 // with a strictly larger value" per token: TPL == 1 (V <= 64) reads the other tokens with readlane, TPL > 1 stages the
 // row in LDS (broadcast reads).  A row the filter leaves unchanged (no token out of the top k or the nucleus) draws with
 // the plain kernel's arithmetic -- same softmax, same scan, uniform not rescaled -- so at T = 1 it picks the same token.
-// STREAM: as in select_token_kernel.
+// RAGGED / STREAM and the parameter list: as in select_token_kernel (mode is the other kernel's: always 1 here).
 template <bool RAGGED, int TPL, bool STREAM>
 __global__ __launch_bounds__(256) void select_token_filtered_kernel(
     const float* __restrict__ logits, int V, int64_t* ys, int64_t ld_ys, int pos_host, uint8_t* valid, int64_t valid_sb,
-    uint8_t* done, float* probs_out, int n, int64_t pad_id, int64_t eos_id, GctRng rng,
+    uint8_t* done, float* probs_out, int n, int /*mode*/, int64_t pad_id, int64_t eos_id, GctRng rng,
     const int32_t* __restrict__ pos_dev, int valid_off, const uint64_t* __restrict__ seed_dev,
     const int32_t* __restrict__ row_off, const GctSampleFilter* __restrict__ filt, const int32_t* __restrict__ item,
     const int32_t* __restrict__ prefix_len, int item_base) {
 #pragma clang fp contract(off)
-  static_assert(RAGGED || !STREAM, "streamed rows sit at their own positions");
   __shared__ __attribute__((aligned(16))) float stage[4][TPL > 1 ? TPL * 64 : 4];
-  int pos = pos_dev ? *pos_dev + 1 : pos_host;
-  if (seed_dev) rng = gct_rng_make(*seed_dev, 0xDEC0DEu);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = blockIdx.x * 4 + wave;
-  if (row >= n) return;
-  if constexpr (RAGGED) pos -= row_off[row];
-  uint32_t key = (uint32_t)row;
-  if constexpr (STREAM) {                                   // uniform over the wave: a whole wave leaves
-    const int it = item[row];
-    if (it < 0 || pos < prefix_len[it] || valid_off + pos >= valid_sb) return;
-    key = (uint32_t)(item_base + it);
-  }
+  int pos;
+  uint32_t key;
+  if (!select_prologue<RAGGED, STREAM>(row, n, pos_host, pos_dev, row_off, item, prefix_len, item_base, valid_off,
+                                       valid_sb, seed_dev, rng, pos, key))
+    return;
   const int top_k = filt->k;
   const float top_p = filt->top_p, inv_temp = filt->inv_temp;
   const float* lr = logits + (int64_t)row * V;
@@ -492,8 +500,7 @@ __global__ __launch_bounds__(256) void select_token_filtered_kernel(
 #pragma unroll
   for (int t = 0; t < TPL; ++t)
     if (w[t] > 0.f) last = lane + 64 * t;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) last = max(last, __shfl_xor(last, off, 64));
+  last = gct_wave_max_i32(last);
   if (last >= 0) pick = last;                               // rounding fallback: the last token of nonzero weight
   if (changed) {                                            // draw c with probability w_c / sum w
     float sw = 0.f;
@@ -511,25 +518,9 @@ __global__ __launch_bounds__(256) void select_token_filtered_kernel(
     const int c = 64 * t + lane;
     const float p = w[t];
     if (probs_out && c < V) probs_out[(int64_t)row * V + c] = changed ? p * pscale : p;
-    float incl = p;                                         // inclusive scan over the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const float tt = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += tt;
-    }
-    const bool hit = !found && c < V && (cum + incl) > u && p > 0.f;   // (a token of weight 0 is never drawn)
-    const unsigned long long ball = __ballot(hit);
-    if (ball && !found) {
-      pick = 64 * t + (int)__builtin_ctzll(ball);
-      found = true;
-    }
-    cum += __shfl(incl, 63, 64);
+    cdf_scan_chunk(p, 64 * t, V, u, lane, cum, found, pick);  // (a token of weight 0 is never drawn)
   }
-  if (lane == 0) {
-    ys[(int64_t)row * ld_ys + pos] = pick;
-    if (valid) valid[(int64_t)row * valid_sb + valid_off + pos] = (pick != pad_id) ? 1 : 0;
-    if (done && pick == eos_id) done[row] = 1;
-  }
+  commit_token(lane, row, pos, pick, ys, ld_ys, valid, valid_sb, valid_off, done, pad_id, eos_id);
 }
 
 // ---------------------------------------------------------------------------------------------- grammar mask
@@ -594,23 +585,6 @@ __device__ __forceinline__ bool grammar_allows(int prev, int depth, uint64_t ope
   return depth + __popcll(open) + 1 + a <= left;
 }
 
-__device__ __forceinline__ uint64_t wave_or64(uint64_t v, bool use_xor) {
-  uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const uint32_t ol = (uint32_t)__shfl_xor((int)lo, off, 64), oh = (uint32_t)__shfl_xor((int)hi, off, 64);
-    lo = use_xor ? lo ^ ol : lo | ol;
-    hi = use_xor ? hi ^ oh : hi | oh;
-  }
-  return ((uint64_t)hi << 32) | lo;
-}
-
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // One wave per row, stateless: the row's generated tokens ys[r][t0, p) -- at most 199 under the 200-row positional table,
 // 255 at T = 256; lane l holds tokens l + 64 t, four per lane --
 // are classified through the table and reduced to the grammar state; then lane l masks tokens l, l + 64, ... of the row's
@@ -625,19 +599,12 @@ __global__ __launch_bounds__(256) void grammar_mask_kernel(
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = blockIdx.x * 4 + wave;
   if (row >= n) return;
-  int p = *pos_dev + 1;                                     // the column the selection behind this launch writes
-  const int ro = row_off ? row_off[row] : 0;
-  p -= ro;
-  int t0, G;
-  if (item) {                                               // uniform over the wave: a whole wave leaves
-    const int it = item[row];
-    if (it < 0) return;                                     // parked
-    t0 = prefix_len[it];
-    G = limit[it];
-  } else {
-    G = gram[0];
-    t0 = gram[1] - ro;
-  }
+  const int step = *pos_dev + 1;                            // the column the selection behind this launch writes
+  const GctRowSlot s = gct_row_slot(step, row, row_off != nullptr, row_off, item != nullptr, item, prefix_len);
+  if (s.item < 0) return;                                   // parked (uniform over the wave: a whole wave leaves)
+  const int p = s.pos;
+  const int t0 = item ? s.t0 : gram[1] - (step - p);        // (gram: the shared prefix width, in the row's own columns)
+  const int G = item ? limit[s.item] : gram[0];
   const int g = p - t0;                                     // tokens generated so far
   if (g < 0 || t0 < 0 || p >= T) return;                    // inside the prefix / no such column: 0 <= t0 <= p < T <= 256
   const int64_t* yr = ys + (int64_t)row * ld_ys + t0;
@@ -657,15 +624,14 @@ __global__ __launch_bounds__(256) void grammar_mask_kernel(
     if (cls == GCT_GRAMMAR_RING) tog ^= 1ull << ((e[t] >> 8) & 63);
     if (cls == GCT_GRAMMAR_ATOM) last_atom = j;
   }
-  const int depth = wave_sum_i32(net);
-  const uint64_t open = wave_or64(tog, true);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) last_atom = max(last_atom, __shfl_xor(last_atom, off, 64));
+  const int depth = gct_wave_sum(net);
+  const uint64_t open = gct_wave_or64(tog, true);
+  last_atom = gct_wave_max_i32(last_atom);
   uint64_t behind = 0;
 #pragma unroll
   for (int t = 0; t < 4; ++t)
     if ((e[t] & 0xFF) == GCT_GRAMMAR_RING && lane + 64 * t > last_atom) behind |= 1ull << ((e[t] >> 8) & 63);
-  const uint64_t here = open & wave_or64(behind, false);
+  const uint64_t here = open & gct_wave_or64(behind, false);
   int prev = GP_START;
   if (g > 0) {
     const int c1 = entry(g - 1) & 0xFF, c2 = g > 1 ? entry(g - 2) & 0xFF : GCT_GRAMMAR_BANNED;
@@ -712,7 +678,8 @@ __global__ __launch_bounds__(256) void stream_scan_kernel(GctStreamState s) {
         want = true;
         it = -1;
       } else {
-        const int gen = p - s.row_off[r] + 2 - s.prefix_len[it];       // tokens generated so far (<= 0: in the prefix)
+        // tokens generated so far (<= 0: in the prefix): the row's next column (gct_row_slot) less its prefix
+        const int gen = gct_row_slot(p + 2, r, true, s.row_off).pos - s.prefix_len[it];
         if (gen > 0 && (s.done[r] != 0 || gen >= s.limit[it])) {
           want = harv = true;
           s.out_len[it] = gen;
@@ -861,12 +828,8 @@ __global__ __launch_bounds__(256) void beam_select_kernel(
   for (int b = wave; b < K; b += 4) {                       // log-softmax statistics, one wave per live beam
     if (s_fin[b] || s_score[b] == -INFINITY) continue;
     const float* lr = logits + (row0 + b) * V;
-    float m = -INFINITY;
-    for (int c = lane; c < V; c += 64) m = fmaxf(m, lr[c]);
-    m = gct_wave_max(m);
-    float se = 0.f;
-    for (int c = lane; c < V; c += 64) se += expf(lr[c] - m);
-    se = gct_wave_sum(se);
+    float m, se;
+    gct_wave_softmax_stats(lr, V, lane, m, se);
     if (lane == 0) {
       s_m[b] = m;
       s_ls[b] = logf(se);
@@ -894,12 +857,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(
   for (int r = 0; r < K; ++r) {                             // K rounds: workgroup argmax of the threads' heads
     float bv = cv[0];
     int bi = ci[0];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(bv, off, 64);
-      const int oi = __shfl_xor(bi, off, 64);
-      if (beam_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
+    gct_wave_argmax(bv, bi);                                // beam_better's order
     if (lane == 0) {
       s_wv[r & 1][wave] = bv;
       s_wi[r & 1][wave] = bi;
@@ -957,6 +915,39 @@ __global__ __launch_bounds__(256) void beam_select_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------------- launches
+// Compile-time dispatch on a run-time value: f gets std::integral_constant<int, v> for the first listed value equal
+// to v, the last listed one otherwise.
+template <int A, int... Rest, class F>
+void with_int(int v, F&& f) {
+  if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, A>{});
+  else if (v == A) f(std::integral_constant<int, A>{});
+  else with_int<Rest...>(v, f);
+}
+
+// The one launch of attn_decode_kernel.  The entry points have checked what is theirs and decided which optional
+// pointer is set: klen only without pos, kv_src only when mapped (beam search), row_off only when ragged.
+int launch_attn_decode(const char* who, const float* q, int64_t ldq, float* k, float* v, int64_t kv_row, int64_t kv_batch,
+                       const uint8_t* valid, int64_t valid_sb, float* o, int64_t ldo, int n, int H, int Lc, int dk,
+                       float scale, const int32_t* pos, int cache_off, const float* knew, const float* vnew, int64_t ldn,
+                       const int32_t* klen, const int32_t* kv_src, int64_t ld_src, const int32_t* row_off, void* stream) {
+  GCT_CHECK_ARG(dk == 16 || dk == 32 || dk == 64, "%s: head dim %d unsupported", who, dk);
+  GCT_CHECK_ARG(ldq % 4 == 0 && kv_row % 4 == 0 && kv_batch % 4 == 0 && gct_aligned16(q) && gct_aligned16(k) &&
+                    gct_aligned16(v),
+                "%s: operands must be 16-B aligned", who);
+  if (n == 0) return GCT_OK;
+  const dim3 grid((unsigned)(((int64_t)n * H + 3) / 4));
+  with_int<64, 32, 16>(dk, [&](auto DK) {
+    with_int<2, 1, 0>(kv_src ? 2 : (row_off ? 1 : 0), [&](auto ROWS) {      // 2 mapped, 1 ragged, 0 plain
+      hipLaunchKernelGGL((attn_decode_kernel<DK, ROWS == 2, ROWS == 1>), grid, dim3(256), 0, (hipStream_t)stream, q, ldq,
+                         k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew,
+                         ldn, klen, kv_src, ld_src, row_off);
+    });
+  });
+  GCT_LAUNCH_CHECK(who);
+  return GCT_OK;
+}
+
 }  // namespace
 
 extern "C" int gct_attn_decode(const float* q, int64_t ldq, float* k, float* v,
@@ -971,26 +962,8 @@ extern "C" int gct_attn_decode(const float* q, int64_t ldq, float* k, float* v,
   GCT_CHECK_ARG(pos || Lc > 0, "attn_decode: no keys");
   GCT_CHECK_ARG(!pos || (knew && vnew && ldn % 4 == 0 && gct_aligned16(knew) && gct_aligned16(vnew) && cache_off >= 0),
                 "attn_decode: the device-position form needs this step's key / value rows");
-  GCT_CHECK_ARG(dk == 16 || dk == 32 || dk == 64, "attn_decode: head dim %d unsupported", dk);
-  GCT_CHECK_ARG(ldq % 4 == 0 && kv_row % 4 == 0 && kv_batch % 4 == 0 && gct_aligned16(q) &&
-                    gct_aligned16(k) && gct_aligned16(v),
-                "attn_decode: operands must be 16-B aligned");
-  if (n == 0) return GCT_OK;
-  const int64_t pairs = (int64_t)n * H;
-  dim3 grid((unsigned)((pairs + 3) / 4)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (row_off) {
-    if (dk == 64) hipLaunchKernelGGL((attn_decode_kernel<64, false, true>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, nullptr, nullptr, 0, row_off);
-    else if (dk == 32) hipLaunchKernelGGL((attn_decode_kernel<32, false, true>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, nullptr, nullptr, 0, row_off);
-    else hipLaunchKernelGGL((attn_decode_kernel<16, false, true>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, nullptr, nullptr, 0, row_off);
-    GCT_LAUNCH_CHECK("attn_decode");
-    return GCT_OK;
-  }
-  if (dk == 64) hipLaunchKernelGGL((attn_decode_kernel<64, false, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, klen, nullptr, 0, nullptr);
-  else if (dk == 32) hipLaunchKernelGGL((attn_decode_kernel<32, false, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, klen, nullptr, 0, nullptr);
-  else hipLaunchKernelGGL((attn_decode_kernel<16, false, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, scale, pos, cache_off, knew, vnew, ldn, klen, nullptr, 0, nullptr);
-  GCT_LAUNCH_CHECK("attn_decode");
-  return GCT_OK;
+  return launch_attn_decode("attn_decode", q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, Lc, dk, scale, pos,
+                            cache_off, knew, vnew, ldn, klen, nullptr, 0, row_off, stream);
 }
 
 extern "C" int gct_attn_decode_z(const float* q, int64_t ldq, int qoff, const float* z, int64_t z_batch, int lat, int Le,
@@ -1029,14 +1002,11 @@ extern "C" int gct_decode_embed(const int64_t* ys, int64_t ld_ys, const int32_t*
                     gct_aligned16(table) && gct_aligned16(pe) && gct_aligned16(out),
                 "decode_embed: bad args");
   if (n == 0) return GCT_OK;
-  const int64_t work = (int64_t)n * (d / 4);
-  const dim3 grid((unsigned)((work + 255) / 256));
-  if (row_off)
-    hipLaunchKernelGGL(decode_embed_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, ys, ld_ys, pos, pe_off, table,
-                       vocab, pe, out, n, d, scale, row_off);
-  else
-    hipLaunchKernelGGL(decode_embed_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, ys, ld_ys, pos, pe_off, table,
-                       vocab, pe, out, n, d, scale, nullptr);
+  const dim3 grid((unsigned)(((int64_t)n * (d / 4) + 255) / 256));
+  with_int<1, 0>(row_off != nullptr, [&](auto RAGGED) {
+    hipLaunchKernelGGL(decode_embed_kernel<RAGGED != 0>, grid, dim3(256), 0, (hipStream_t)stream, ys, ld_ys, pos, pe_off,
+                       table, vocab, pe, out, n, d, scale, row_off);
+  });
   GCT_LAUNCH_CHECK("decode_embed");
   return GCT_OK;
 }
@@ -1063,35 +1033,19 @@ extern "C" int gct_select_token(const float* logits, int V, int64_t* ys, int64_t
   GCT_CHECK_ARG(!item == !prefix_len && (!item || (row_off && valid && done && item_base >= 0)),
                 "select_token: streamed rows need item, prefix_len, row_off, valid and done");
   if (n == 0) return GCT_OK;
-  const dim3 grid((unsigned)((n + 3) / 4)), block(256);
-  hipStream_t st = (hipStream_t)stream;
   const GctRng rng = gct_rng_make(seed, 0xDEC0DEu);
-  if (filt) {
-    constexpr int TPL = GCT_SAMPLE_FILTER_MAX_VOCAB / 64;
-    if (V <= 64) {
-      if (item) hipLaunchKernelGGL((select_token_filtered_kernel<true, 1, true>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, row_off, filt, item, prefix_len, item_base);
-      else if (row_off) hipLaunchKernelGGL((select_token_filtered_kernel<true, 1, false>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, row_off, filt, nullptr, nullptr, 0);
-      else hipLaunchKernelGGL((select_token_filtered_kernel<false, 1, false>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, nullptr, filt, nullptr, nullptr, 0);
-    } else {
-      if (item) hipLaunchKernelGGL((select_token_filtered_kernel<true, TPL, true>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, row_off, filt, item, prefix_len, item_base);
-      else if (row_off) hipLaunchKernelGGL((select_token_filtered_kernel<true, TPL, false>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, row_off, filt, nullptr, nullptr, 0);
-      else hipLaunchKernelGGL((select_token_filtered_kernel<false, TPL, false>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb, done, probs_out, n, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, nullptr, filt, nullptr, nullptr, 0);
-    }
-    GCT_LAUNCH_CHECK("select_token");
-    return GCT_OK;
-  }
-  if (item)
-    hipLaunchKernelGGL((select_token_kernel<true, true>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb,
-                       done, probs_out, n, mode, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, row_off, item,
-                       prefix_len, item_base);
-  else if (row_off)
-    hipLaunchKernelGGL((select_token_kernel<true, false>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb,
-                       done, probs_out, n, mode, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, row_off, nullptr,
-                       nullptr, 0);
-  else
-    hipLaunchKernelGGL((select_token_kernel<false, false>), grid, block, 0, st, logits, V, ys, ld_ys, pos, valid, valid_sb,
-                       done, probs_out, n, mode, pad_id, eos_id, rng, pos_dev, valid_off, seed_dev, nullptr, nullptr,
-                       nullptr, 0);
+  constexpr int TPL = GCT_SAMPLE_FILTER_MAX_VOCAB / 64;
+  // streamed rows (item set, hence row_off) are ragged rows; the filter keeps 0 (none: the plain kernel), 1 or TPL
+  // tokens per lane.  Plain rows are keyed by the row alone, whatever item_base says.
+  with_int<2, 1, 0>(item ? 2 : (row_off ? 1 : 0), [&](auto ROWS) {
+    with_int<0, 1, TPL>(!filt ? 0 : (V <= 64 ? 1 : TPL), [&](auto PER_LANE) {
+      auto kernel = select_token_kernel<ROWS != 0, ROWS == 2>;
+      if constexpr (PER_LANE != 0) kernel = select_token_filtered_kernel<ROWS != 0, PER_LANE, ROWS == 2>;
+      hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, V, ys, ld_ys,
+                         pos, valid, valid_sb, done, probs_out, n, mode, pad_id, eos_id, rng, pos_dev, valid_off,
+                         seed_dev, row_off, filt, item, prefix_len, item ? item_base : 0);
+    });
+  });
   GCT_LAUNCH_CHECK("select_token");
   return GCT_OK;
 }
@@ -1153,19 +1107,8 @@ extern "C" int gct_attn_decode_beam(const float* q, int64_t ldq, float* k, float
                 "attn_decode_beam: bad args");
   GCT_CHECK_ARG(knew && vnew && ldn % 4 == 0 && gct_aligned16(knew) && gct_aligned16(vnew),
                 "attn_decode_beam: needs this step's key / value rows");
-  GCT_CHECK_ARG(dk == 16 || dk == 32 || dk == 64, "attn_decode_beam: head dim %d unsupported", dk);
-  GCT_CHECK_ARG(ldq % 4 == 0 && kv_row % 4 == 0 && kv_batch % 4 == 0 && gct_aligned16(q) && gct_aligned16(k) &&
-                    gct_aligned16(v),
-                "attn_decode_beam: operands must be 16-B aligned");
-  if (n == 0) return GCT_OK;
-  const int64_t pairs = (int64_t)n * H;
-  dim3 grid((unsigned)((pairs + 3) / 4)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (dk == 64) hipLaunchKernelGGL((attn_decode_kernel<64, true, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, T, scale, pos, cache_off, knew, vnew, ldn, nullptr, kv_src, ld_src, nullptr);
-  else if (dk == 32) hipLaunchKernelGGL((attn_decode_kernel<32, true, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, T, scale, pos, cache_off, knew, vnew, ldn, nullptr, kv_src, ld_src, nullptr);
-  else hipLaunchKernelGGL((attn_decode_kernel<16, true, false>), grid, block, 0, st, q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, T, scale, pos, cache_off, knew, vnew, ldn, nullptr, kv_src, ld_src, nullptr);
-  GCT_LAUNCH_CHECK("attn_decode_beam");
-  return GCT_OK;
+  return launch_attn_decode("attn_decode_beam", q, ldq, k, v, kv_row, kv_batch, valid, valid_sb, o, ldo, n, H, T, dk, scale,
+                            pos, cache_off, knew, vnew, ldn, nullptr, kv_src, ld_src, nullptr, stream);
 }
 
 extern "C" int gct_beam_select(const float* logits, int V, int n, int k, float* scores, uint8_t* finished,
@@ -1182,10 +1125,11 @@ extern "C" int gct_beam_select(const float* logits, int V, int n, int k, float* 
                 (long long)valid_sb, (long long)ld_ys);
   GCT_CHECK_ARG(pad_id >= 0 && pad_id < V, "beam_select: pad id %lld outside the vocabulary", (long long)pad_id);
   if (n == 0) return GCT_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (k <= 4) hipLaunchKernelGGL(beam_select_kernel<4>, dim3((unsigned)n), dim3(256), 0, st, logits, V, k, scores, finished, lengths, parent, ys, ld_ys, valid, valid_sb, valid_off, kv_src, ld_src, T, done, pos_dev, pad_id, eos_id);
-  else if (k <= 8) hipLaunchKernelGGL(beam_select_kernel<8>, dim3((unsigned)n), dim3(256), 0, st, logits, V, k, scores, finished, lengths, parent, ys, ld_ys, valid, valid_sb, valid_off, kv_src, ld_src, T, done, pos_dev, pad_id, eos_id);
-  else hipLaunchKernelGGL(beam_select_kernel<16>, dim3((unsigned)n), dim3(256), 0, st, logits, V, k, scores, finished, lengths, parent, ys, ld_ys, valid, valid_sb, valid_off, kv_src, ld_src, T, done, pos_dev, pad_id, eos_id);
+  with_int<4, 8, 16>(k <= 4 ? 4 : (k <= 8 ? 8 : 16), [&](auto KM) {
+    hipLaunchKernelGGL(beam_select_kernel<KM>, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, logits, V, k, scores,
+                       finished, lengths, parent, ys, ld_ys, valid, valid_sb, valid_off, kv_src, ld_src, T, done, pos_dev,
+                       pad_id, eos_id);
+  });
   GCT_LAUNCH_CHECK("beam_select");
   return GCT_OK;
 }

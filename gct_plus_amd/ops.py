@@ -892,6 +892,19 @@ def _check_row_off(row_off, n):
         raise ValueError("row_off must be a contiguous int32 tensor with one offset per row")
 
 
+def _check_step_rows(n, row_off, item, **tables):
+    """Rows of a decode step (csrc/decode_rows.h): row_off alone (mixed), or with item and its per-item tables (stream)."""
+    _check_row_off(row_off, n)
+    names = ["item", *tables]
+    if len({t is None for t in (item, *tables.values())}) != 1:
+        raise ValueError(f"{', '.join(names[:-1])} and {names[-1]} go together")
+    if item is not None:
+        _check_row_off(item, n)
+        if row_off is None or any(t.dtype != torch.int32 or not t.is_contiguous() for t in tables.values()):
+            raise ValueError(f"streamed rows need row_off and {'a ' if len(tables) == 1 else ''}contiguous int32 "
+                             f"{' / '.join(tables)}")
+
+
 def attn_decode(q, ldq, k, v, kv_row, kv_batch, valid_u8, valid_sb, out, n, H, Lc, dk, pos=None, cache_off=0,
                 knew=None, vnew=None, ldn=0, klen=None, row_off=None):
     """klen (int32 [n], optional, fixed caches only): leading keys to look at per sample (the rest are masked).
@@ -937,13 +950,7 @@ def select_token(logits2d, ys, pos, valid_u8, done_u8, mode, pad_id, eos_id, see
     (< 0: parked, nothing written), keeps the prefix tokens the refill laid out, and draws with the key
     (item_base + item, pos)."""
     n, V = logits2d.shape
-    _check_row_off(row_off, n)
-    if (item is None) != (prefix_len is None):
-        raise ValueError("item and prefix_len go together")
-    if item is not None:
-        _check_row_off(item, n)
-        if row_off is None or prefix_len.dtype != torch.int32 or not prefix_len.is_contiguous():
-            raise ValueError("streamed rows need row_off and a contiguous int32 prefix_len")
+    _check_step_rows(n, row_off, item, prefix_len=prefix_len)
     if filt_dev is not None and (filt_dev.dtype != torch.int32 or filt_dev.numel() != 4 or not filt_dev.is_contiguous()):
         raise ValueError("filt_dev must be a contiguous int32 tensor of 4 entries (sample_filter_settings)")
     check(_L().gct_select_token(_p(logits2d), V, _p(ys), ys.stride(0), pos, _p(valid_u8),
@@ -972,15 +979,9 @@ def grammar_mask(logits2d, masked, table, ys, pos_dev, width=None, row_off=None,
         raise ValueError("grammar_mask: logits and masked must be contiguous [n, V] buffers of one shape")
     if table.numel() != V or not table.is_contiguous() or ys.dim() != 2 or ys.shape[0] < n or ys.stride(1) != 1:
         raise ValueError("grammar_mask: table int32 [V], ys [n, T] with unit column stride")
-    _check_row_off(row_off, n)
-    stream = [t is not None for t in (item, prefix_len, limit)]
-    if any(stream) != all(stream):
-        raise ValueError("item, prefix_len and limit go together")
-    if item is not None:
-        _check_row_off(item, n)
-        if row_off is None or any(t.dtype != torch.int32 or not t.is_contiguous() for t in (prefix_len, limit)):
-            raise ValueError("streamed rows need row_off and contiguous int32 prefix_len / limit")
-    elif gram is None or gram.dtype != torch.int32 or gram.numel() != 2 or not gram.is_contiguous():
+    _check_step_rows(n, row_off, item, prefix_len=prefix_len, limit=limit)
+    if item is None and (gram is None or gram.dtype != torch.int32 or gram.numel() != 2 or
+                         not gram.is_contiguous()):
         raise ValueError("gram must be a contiguous int32 tensor (budget, prefix width)")
     check(_L().gct_grammar_mask(_p(logits2d), _p(masked), V, _p(table), _p(ys), ys.stride(0),
                                 ys.shape[1] if width is None else int(width), n, _p(pos_dev), _p(row_off), _p(gram),
@@ -1031,13 +1032,7 @@ def chosen_logp(logits2d, ys, pos_dev, out, pad_id, row_off=None, item=None, pre
     _chk(pos_dev, "chosen_logp.pos", torch.int32)
     if not logits2d.is_contiguous() or out.dim() != 2 or out.stride(1) != 1 or ys.stride(1) != 1:
         raise ValueError("chosen_logp: contiguous logits and unit column strides of ys / out")
-    _check_row_off(row_off, n)
-    if (item is None) != (prefix_len is None):
-        raise ValueError("item and prefix_len go together")
-    if item is not None:
-        _check_row_off(item, n)
-        if row_off is None or prefix_len.dtype != torch.int32 or not prefix_len.is_contiguous():
-            raise ValueError("streamed rows need row_off and a contiguous int32 prefix_len")
+    _check_step_rows(n, row_off, item, prefix_len=prefix_len)
     check(_L().gct_chosen_logp(_p(logits2d), V, _p(ys), ys.stride(0), _p(pos_dev), _p(row_off), _p(item),
                                _p(prefix_len), int(pad_id), _p(out), out.stride(0), out.shape[0], n, _st()),
           "gct_chosen_logp")

@@ -409,7 +409,8 @@ int gct_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float
  * row_off (nullable, only with pos): int32 [n], per-row position offset of a batch of prefixes of different lengths
  * that share one device counter -- row b's position is *pos - row_off[b] (>= 0): the caches of row b hold
  * cache_off + *pos - row_off[b] keys and this step's key is appended there.  gct_decode_embed and gct_select_token
- * take the same offsets.  NULL: every row is at *pos (the kernel of ABI 16). */
+ * take the same offsets (csrc/decode_rows.h is the one statement of where a row of a step sits, for every kernel
+ * that takes row_off / item / prefix_len).  NULL: every row is at *pos (the kernel of ABI 16). */
 int gct_attn_decode(const float* q, int64_t ldq, float* k, float* v, int64_t kv_row,
                     int64_t kv_batch, const uint8_t* valid, int64_t valid_sb, float* o, int64_t ldo,
                     int n, int H, int Lc, int dk, float scale, const int32_t* pos, int cache_off,

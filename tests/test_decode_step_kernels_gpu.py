@@ -5,6 +5,7 @@ tests/test_decode_step_ref_host.py):
   gct_decode_embed    clamped ids, positions, row offsets
   gct_select_token    greedy (first maximum, probabilities, side effects) and multinomial, plain and filtered: every draw
                       predicted exactly from the Philox stream, except the rows too close to a cumulative boundary
+                      (row offsets, streamed rows: parked, inside the prefix, without room for the valid flag)
 Every output buffer starts as NaN (a sentinel for integers); whatever a kernel must not touch is compared bit for bit."""
 import math
 
@@ -226,12 +227,12 @@ def test_decode_embed(d, n, pe_off, ragged):
 
 
 # ================================================================================================ gct_select_token
-def run_select(x, mode, pos, W, pad, eos, done0=None, valid_sb=16, valid_off=0, probs=True, **kw):
+def run_select(x, mode, pos, W, pad, eos, done0=None, valid_sb=16, valid_off=0, probs=True, spare_rows=0, **kw):
     """One launch on fresh sentinel buffers -> (ys, valid, done, probs) on the host; valid_sb = 0 / done0 = None pass
-    NULL for valid / done."""
+    NULL for valid / done.  spare_rows: rows of valid allocated (and returned) behind the n of the launch."""
     n, V = x.shape
     ys = torch.full((n, W), YS_FILL, dtype=torch.int64, device="cuda")
-    valid = torch.full((n, valid_sb), VALID_FILL, dtype=torch.uint8, device="cuda") if valid_sb else None
+    valid = torch.full((n + spare_rows, valid_sb), VALID_FILL, dtype=torch.uint8, device="cuda") if valid_sb else None
     done = None if done0 is None else done0.cuda()
     pr = torch.full((n, V), NAN, device="cuda") if probs else None
     ops.select_token(x, ys, pos, valid, done, mode, pad, eos, probs_out=pr, valid_off=valid_off, **kw)
@@ -329,6 +330,30 @@ def test_select_token_greedy_optional_outputs_and_positions():
     assert int(pos_dev) == 4
 
 
+def test_select_token_greedy_stream_rows():
+    """Mode 0 over streamed rows: the rows that act write the first maximum at column *pos_dev + 1 - row_off[r] with the
+    valid / done side effects; parked rows (item < 0) and rows inside their item's prefix keep every sentinel."""
+    V, n = 130, 9
+    x = greedy_rows(V)
+    want, p64 = D.greedy(x)
+    row_off = (torch.arange(n) % 8).to(torch.int32)
+    cols = 10 - row_off.long()                                                     # 10, 9, .., 3, 10
+    item = torch.randperm(n, generator=torch.Generator().manual_seed(9)).to(torch.int32)
+    item[::3] = -1
+    prefix_len = (2 + 3 * (torch.arange(n) % 4)).to(torch.int32)                   # per item: 2, 5, 8, 11
+    behind = cols >= prefix_len[item.clamp(min=0).long()]
+    live = (item >= 0) & behind
+    assert 0.2 * n < int(live.sum()) < 0.8 * n and int(((item >= 0) & ~behind).sum()) > 0
+    pad, eos = int(want[live][0]), int(want[live][-1])                             # both occur among the picks
+    done0 = (torch.arange(n) % 2).to(torch.uint8)
+    ys, valid, done, pr = run_select(x.cuda(), 0, 0, 12, pad, eos, done0=done0, valid_off=2,
+                                     pos_dev=torch.tensor([9], dtype=torch.int32, device="cuda"), row_off=row_off.cuda(),
+                                     item=item.cuda(), prefix_len=prefix_len.cuda(), item_base=1000)
+    tok = side_effects(ys, valid, done, cols, pad, eos, done0, 2, written=live)
+    assert torch.equal(tok[live], want[live]), (tok.tolist(), want.tolist(), live.tolist())
+    assert bool(pr[~live].isnan().all()) and float((pr[live].double() - p64[live]).abs().max()) < 1e-6
+
+
 # ------------------------------------------------------------------------------------------------ exact draws
 PAD, EOS = 0, 2
 
@@ -408,3 +433,27 @@ def test_multinomial_stream_rows_are_keyed_by_their_item(name, item_base):
     tok = side_effects(ys, valid, done, cols, PAD, EOS, done0, 2, written=live)
     keys = (item_base + item.long())[live].numpy()
     D.check_draws(tok[live].numpy(), w[live.numpy()], D.SEEDS[0], keys, cols[live].numpy(), V)
+
+
+@pytest.mark.parametrize("name", ["plain-65", "filt-30"])
+def test_multinomial_stream_rows_without_room_write_nothing(name):
+    """A streamed row whose flag slot valid_off + pos lies at or behind valid_sb writes nothing -- ys (wide enough to
+    hold the column), valid, done -- and the rows with room draw as ever.  A write past the row's flags would land in
+    the next row of valid: the over-long rows are not the last one, and a spare row lies behind the n of the launch."""
+    V = D.CASE[name][1]
+    x, w = D.draw_inputs(name)
+    n, valid_sb, valid_off = D.DRAW_ROWS, 9, 2
+    item = torch.randperm(n, generator=torch.Generator().manual_seed(6)).to(torch.int32)
+    prefix_len = torch.ones(n, dtype=torch.int32)
+    row_off = (torch.arange(n) % 8).to(torch.int32)
+    row_off[-1] = 7                                                                # the last row has room
+    cols = 10 - row_off.long()                                                     # 3 .. 10; flag slots 5 .. 12
+    live = valid_off + cols < valid_sb
+    assert 0.2 * n < int(live.sum()) < 0.8 * n and bool(live[-1]) and int((valid_off + cols).max()) < 2 * valid_sb
+    done0 = (torch.arange(n) % 3 == 0).to(torch.uint8)
+    ys, valid, done, _ = run_select(x.cuda(), 1, 0, 12, PAD, EOS, done0=done0, valid_sb=valid_sb, valid_off=valid_off,
+                                    probs=False, spare_rows=1, seed=D.SEEDS[0],
+                                    pos_dev=torch.tensor([9], dtype=torch.int32, device="cuda"), row_off=row_off.cuda(),
+                                    filt_dev=filt_dev(name), item=item.cuda(), prefix_len=prefix_len.cuda())
+    tok = side_effects(ys, valid, done, cols, PAD, EOS, done0, valid_off, written=live)
+    D.check_draws(tok[live].numpy(), w[live.numpy()], D.SEEDS[0], item.long()[live].numpy(), cols[live].numpy(), V)
