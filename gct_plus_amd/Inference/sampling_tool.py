@@ -28,6 +28,11 @@ Log-likelihoods: `score` / `score_smiles` give log p(x | z, conditions, scaffold
 `decode`, `sample_smiles` and `sample_multiple_smiles` return the model's log-probability of what they drew as one more
 element (KVDecoder.generate(return_logp=True): no second forward).
 
+Fine-tuning on what was sampled: `return_rows=True` on `decode`, `sample_smiles` and `sample_multiple_smiles` appends a
+`DecodedRows` -- the latents, mask, conditions and prefix lengths the decode consumed and the token rows it produced --
+and `logp(*rows)` is `score(*rows)` WITH a gradient (decode.sequence_logp), on the device: the policy term of
+Train/finetune.reinforce_step.  Not with beam search.
+
 `well_formed=True` (optional): greedy / multinomial decodes are constrained by decode.SmilesGrammar built from the target
 vocabulary -- every returned string has balanced branches, paired ring-closure numbers, no dangling bond, and ended
 with <eos> inside max_strlen.  Syntax only: no valence or aromaticity check.  Not with beam search: the constructor
@@ -48,7 +53,7 @@ import torch
 from ..Model.modules import get_src_mask
 from ..data import Vocab, tokenize
 from ..decode import (BEAM_ALPHA, KVDecoder, SmilesGrammar, check_beam_size, check_sample_filter, check_stream_model,
-                      check_stream_rows, generated_tokens, score_tokens)
+                      check_stream_rows, generated_tokens, score_tokens, sequence_logp)
 
 
 class Scores(NamedTuple):
@@ -59,6 +64,24 @@ class Scores(NamedTuple):
     tokens: torch.Tensor
     hits: torch.Tensor
     token_logp: torch.Tensor
+
+
+class DecodedRows(NamedTuple):
+    """What a greedy / multinomial decode consumed and produced (return_rows=True), on the sampler's device; the
+    argument list of Sampling.score and Sampling.logp: zs [n, L_e, latent], ys int64 [n, L] the full token rows --
+    prefix, generated tokens up to the row's first generated <eos>, pad behind it (the decoder goes on writing there and
+    id_to_smi drops it: the rows hold exactly the molecules that were returned) --, src_mask bool [n, 1, L_e], dconds
+    [n, n_c] or None, prefix_lens int64 [n] on the CPU (row r's prefix is ys[r, :prefix_lens[r]]; it is not scored)."""
+    zs: torch.Tensor
+    ys: torch.Tensor
+    src_mask: torch.Tensor
+    dconds: Optional[torch.Tensor]
+    prefix_lens: torch.Tensor
+
+
+def _rows_kw(return_rows):
+    """The keyword of `decode` only when it is asked for: a `decode` with the earlier signature keeps working."""
+    return {"return_rows": True} if return_rows else {}
 
 
 def sample_token_lengths(data: Sequence[int], size: int, rng: np.random.Generator) -> np.ndarray:
@@ -202,13 +225,18 @@ class Sampling:
 
     # ---- decode: KV-cached equivalent of Sampling.decode (sampling_tool.py:140-184) ----------
     @torch.no_grad()
-    def decode(self, zs, ys, src_mask, dconds=None, prefix_lens=None):
+    def decode(self, zs, ys, src_mask, dconds=None, prefix_lens=None, return_rows=False):
         """ids [n, L] (prefix included); with decode_algo="beam" the best beam of each sample.
         prefix_lens (ints [n], optional): row r's prefix is ys[r, :t0_r] (KVDecoder.generate); not with beam search.
         The sampler's top_k / top_p / temperature apply to every draw (sample_smiles, sample_multiple_smiles).
         With stream_rows the n rows are a pool decoded by continuous batching; same layout, input order.
         with_logp (constructor): returns (ids, logp), logp [n] fp32 on the CPU = the model's log-probability of each
-        row's generated tokens up to its <eos> (raw logits at temperature 1, whatever filter the draw went through)."""
+        row's generated tokens up to its <eos> (raw logits at temperature 1, whatever filter the draw went through).
+        return_rows=True appends a DecodedRows (what this decode consumed, and its token rows cut at each row's <eos>):
+        `score(*rows)` / `logp(*rows)` score exactly what was decoded.  ValueError with beam search."""
+        if return_rows and self.decode_algo == "beam":
+            raise ValueError("return_rows is not supported with decode_algo='beam' (a beam row's history lies behind the "
+                             "ancestry map; score the returned beams with score())")
         if self.decode_algo == "beam":
             if prefix_lens is not None:
                 raise ValueError("decode: beam search takes prefixes of one length (see sample_multiple_smiles)")
@@ -223,14 +251,40 @@ class Sampling:
                                           use_graphs=self.use_graphs, prefix_lens=prefix_lens, top_k=self.top_k,
                                           top_p=self.top_p, temperature=self.temperature, return_logp=self.with_logp,
                                           grammar=self.grammar)
-            return (out[0], out[3].cpu()) if self.with_logp else out[0]
+            res = (out[0], out[3].cpu()) if self.with_logp else out[0]
+            return self._with_rows(res, zs, ys, src_mask, dconds, prefix_lens) if return_rows else res
         # the positional table has 200 rows, of which use_cond2dec spends n_c on the condition tokens
         self.kv.start(zs, src_mask, dconds, max_total_len=min(200 - self.kv.off, total))
         out = self.kv.generate(ys, self.max_strlen, algo=self.decode_algo, seed=self.seed,
                                use_graphs=self.use_graphs, prefix_lens=prefix_lens, top_k=self.top_k,
                                top_p=self.top_p, temperature=self.temperature, return_logp=self.with_logp,
                                grammar=self.grammar)
-        return (out[0], out[2].cpu()) if self.with_logp else out
+        res = (out[0], out[2].cpu()) if self.with_logp else out
+        return self._with_rows(res, zs, ys, src_mask, dconds, prefix_lens) if return_rows else res
+
+    def _with_rows(self, res, zs, ys0, src_mask, dconds, prefix_lens):
+        """decode's result with the DecodedRows of the call appended."""
+        ids = res[0] if self.with_logp else res
+        n, L = ids.shape
+        lens = (torch.full((n,), ys0.size(1), dtype=torch.long) if prefix_lens is None
+                else torch.as_tensor(prefix_lens).to("cpu", torch.long).view(-1))
+        cols = torch.arange(L, device=ids.device).view(1, -1)
+        is_eos = (ids == self.eos_id) & (cols >= lens.to(ids.device).view(-1, 1))
+        first = torch.where(is_eos.any(1), is_eos.int().argmax(1), torch.full_like(is_eos[:, 0], L, dtype=torch.long))
+        clean = torch.where(cols <= first.view(-1, 1), ids, torch.full_like(ids, self.pad_id))
+        rows = DecodedRows(zs, clean, src_mask, dconds, lens)
+        return res + (rows,) if self.with_logp else (res, rows)
+
+    def logp(self, zs, ys, src_mask, dconds=None, prefix_lens=None) -> Scores:
+        """`score` with a gradient (decode.sequence_logp): the same arguments -- a DecodedRows unpacks into them -- and
+        the same values, but NOT under no_grad and on the DEVICE: logp [n] and token_logp [n, W] are attached to the
+        graph of the decoder's parameters and model.out (and of zs when it requires grad).  One forward over all n rows,
+        in the model's current train / eval mode."""
+        zs, src_mask = zs.to(self.device), src_mask.to(self.device)
+        dconds = None if dconds is None else dconds.to(self.device)
+        logp, tokens, hits, token_logp = sequence_logp(self.model, zs, src_mask, dconds, ys, prefix_lens=prefix_lens,
+                                                       pad_id=self.pad_id)
+        return Scores(logp, tokens, hits, token_logp)
 
     @torch.no_grad()
     def score(self, zs, ys, src_mask, dconds=None, prefix_lens=None) -> Scores:
@@ -303,9 +357,12 @@ class Sampling:
         return ys0, lens, [len(ids) + 1 for ids in sca]
 
     @torch.no_grad()
-    def _sample_multiple(self, scaffolds, zs, toklen, dconds):
+    def _sample_multiple(self, scaffolds, zs, toklen, dconds, return_rows=False):
         """One scaffold per row (sample_multiple_smiles): a single mixed-prefix decode, or for beam search one decode
-        per prefix length; (smiles, toklen, toklen_gen) in input order (with_logp: and logp [n])."""
+        per prefix length; (smiles, toklen, toklen_gen) in input order (with_logp: and logp [n]; return_rows: and the
+        DecodedRows)."""
+        if return_rows and self.decode_algo == "beam":
+            raise ValueError("return_rows is not supported with decode_algo='beam'")
         scaffolds = list(scaffolds)
         if not scaffolds:
             raise ValueError("sample_multiple_smiles: no scaffolds")
@@ -313,6 +370,7 @@ class Sampling:
         zs, toklen, src_mask = latent_setup_rows(extras, zs, toklen, self.latent_dim, self.sample_toklen,
                                                  self.sample_z)
         n = len(scaffolds)
+        tail = ()
         if self.decode_algo == "beam":
             gens = [None] * n
             for t0, idx in group_by_length(lens):
@@ -320,20 +378,25 @@ class Sampling:
                 for i, row in zip(idx.tolist(), outs[:, t0:].cpu()):
                     gens[i] = row
         else:
-            outs = self.decode(zs, ys0, src_mask, dconds, prefix_lens=lens)
-            outs, logp = outs if self.with_logp else (outs, None)
+            outs = self.decode(zs, ys0, src_mask, dconds, prefix_lens=lens, **_rows_kw(return_rows))
+            outs, tail = self._split(outs, return_rows)
             gens = list(generated_tokens(outs, lens).cpu())
         smiles = [self.id_to_smi(g.numpy()) for g in gens]
-        res = smiles, toklen, [len(tokenize(s, self.add_sep)) for s in smiles]
-        return res + (logp,) if self.with_logp else res
+        return (smiles, toklen, [len(tokenize(s, self.add_sep)) for s in smiles]) + tail
 
-    def _finish(self, outs, toklen, skip=0):
-        """with_logp: `outs` is decode's (ids, logp) and logp becomes the fourth element."""
-        outs, logp = outs if self.with_logp else (outs, None)
+    def _split(self, outs, return_rows):
+        """decode's result -> (ids, what follows them: logp with with_logp, the DecodedRows with return_rows)."""
+        if self.with_logp or return_rows:
+            return outs[0], tuple(outs[1:])
+        return outs, ()
+
+    def _finish(self, outs, toklen, skip=0, return_rows=False):
+        """with_logp: `outs` is decode's (ids, logp) and logp becomes the fourth element; return_rows: the DecodedRows
+        the last one."""
+        outs, tail = self._split(outs, return_rows)
         outs = outs.cpu().numpy()
         smiles = [self.id_to_smi(ids[skip:]) for ids in outs]
-        res = smiles, toklen, [len(tokenize(s, self.add_sep)) for s in smiles]
-        return res + (logp,) if self.with_logp else res
+        return (smiles, toklen, [len(tokenize(s, self.add_sep)) for s in smiles]) + tail
 
 
 class VaetfSampling(Sampling):
@@ -341,10 +404,10 @@ class VaetfSampling(Sampling):
         src = self.tokenize_smiles(smiles_list).to(self.device)
         return self.model.encode(src=src, src_mask=get_src_mask(src, self.pad_id))
 
-    def sample_smiles(self, n, zs=None, toklen=None):
+    def sample_smiles(self, n, zs=None, toklen=None, return_rows=False):
         zs, toklen, src_mask = self._latent_setup(n, zs, toklen)
-        outs = self.decode(zs, self.init_y(n), src_mask)
-        return self._finish(outs, toklen)
+        outs = self.decode(zs, self.init_y(n), src_mask, **_rows_kw(return_rows))
+        return self._finish(outs, toklen, return_rows=return_rows)
 
     def score_smiles(self, smiles_list, zs=None) -> Scores:
         """log p(<sos> smiles <eos> | z): z = zs [n, L_e, latent], or (None) the encoder's mean of the same molecule."""
@@ -362,14 +425,14 @@ class CvaetfSampling(Sampling):
         econds = (self.transform(econds) if transform else torch.as_tensor(econds, dtype=torch.float32)).to(self.device)
         return self.model.encode(src=src, src_mask=get_src_mask(src, self.pad_id, econds), econds=econds)
 
-    def sample_smiles(self, dconds, zs=None, toklen=None, transform=True):
+    def sample_smiles(self, dconds, zs=None, toklen=None, transform=True, return_rows=False):
         n = len(dconds)
         dconds = self.transform(dconds) if transform else torch.as_tensor(dconds, dtype=torch.float32)
         if zs is None and toklen is not None:
             toklen = [t + self.cond_dim for t in toklen]
         zs, toklen, src_mask = self._latent_setup(n, zs, toklen)
-        outs = self.decode(zs, self.init_y(n), src_mask, dconds)
-        return self._finish(outs, toklen)
+        outs = self.decode(zs, self.init_y(n), src_mask, dconds, **_rows_kw(return_rows))
+        return self._finish(outs, toklen, return_rows=return_rows)
 
     def score_smiles(self, smiles_list, conds, zs=None, transform=True) -> Scores:
         """log p(<sos> smiles <eos> | z, conds); zs None: the encoder's mean of (smiles, conds)."""
@@ -387,11 +450,11 @@ class ScaVaeSampling(Sampling):
         src = self.tokenize_smiles([b + "<sep>" + a for a, b in zip(smiles_list, scaffold_list)]).to(self.device)
         return self.model.encode(src=src, src_mask=get_src_mask(src, self.pad_id))
 
-    def sample_smiles(self, n, scaffold, zs=None, toklen=None):
+    def sample_smiles(self, n, scaffold, zs=None, toklen=None, return_rows=False):
         sca_ids = self.smi_to_id(scaffold)
         zs, toklen, src_mask = self._latent_setup(n, zs, toklen, extra=len(sca_ids) + 1)
-        outs = self.decode(zs, self.init_y(n, True, sca_ids, True), src_mask)
-        return self._finish(outs, toklen, skip=1 + len(sca_ids) + 1)
+        outs = self.decode(zs, self.init_y(n, True, sca_ids, True), src_mask, **_rows_kw(return_rows))
+        return self._finish(outs, toklen, skip=1 + len(sca_ids) + 1, return_rows=return_rows)
 
     def score_smiles(self, smiles_list, scaffold_list, zs=None) -> Scores:
         """log p(smiles <eos> | <sos> scaffold <sep>, z), one scaffold per molecule (the prefix is not scored); zs None:
@@ -403,10 +466,10 @@ class ScaVaeSampling(Sampling):
             return src, get_src_mask(src, self.pad_id), None
         return self._score_smiles(ys, lens, extras, zs, None, encode)
 
-    def sample_multiple_smiles(self, scaffolds, zs=None, toklen=None):
+    def sample_multiple_smiles(self, scaffolds, zs=None, toklen=None, return_rows=False):
         """One molecule per scaffold, all rows in one batch: row r decodes as sample_smiles(1, scaffolds[r]) with z
         row zs[r] and token length toklen[r] would (latent rows len(scaffold tokens) + 1 + toklen[r])."""
-        return self._sample_multiple(scaffolds, zs, toklen, None)
+        return self._sample_multiple(scaffolds, zs, toklen, None, return_rows)
 
 
 class PscavaetfSampling(Sampling):
@@ -415,14 +478,14 @@ class PscavaetfSampling(Sampling):
         econds = (self.transform(econds) if transform else torch.as_tensor(econds, dtype=torch.float32)).to(self.device)
         return self.model.encode(src=src, src_mask=get_src_mask(src, self.pad_id, econds), econds=econds)
 
-    def sample_smiles(self, dconds, scaffold, zs=None, toklen=None, transform=True):
+    def sample_smiles(self, dconds, scaffold, zs=None, toklen=None, transform=True, return_rows=False):
         """prefix = <sos> scaffold <sep> (sampling_tool.py:452-498)."""
         n = len(dconds)
         dconds = self.transform(dconds) if transform else torch.as_tensor(dconds, dtype=torch.float32)
         sca_ids = self.smi_to_id(scaffold)
         zs, toklen, src_mask = self._latent_setup(n, zs, toklen, extra=len(sca_ids) + 1)
-        outs = self.decode(zs, self.init_y(n, True, sca_ids, True), src_mask, dconds)
-        return self._finish(outs, toklen, skip=1 + len(sca_ids) + 1)
+        outs = self.decode(zs, self.init_y(n, True, sca_ids, True), src_mask, dconds, **_rows_kw(return_rows))
+        return self._finish(outs, toklen, skip=1 + len(sca_ids) + 1, return_rows=return_rows)
 
     def score_smiles(self, smiles_list, scaffold_list, conds, zs=None, transform=True) -> Scores:
         """log p(smiles <eos> | <sos> scaffold <sep>, z, conds), one scaffold per molecule; zs None: the encoder's mean
@@ -436,14 +499,14 @@ class PscavaetfSampling(Sampling):
             return src, get_src_mask(src, self.pad_id, econds), econds
         return self._score_smiles(ys, lens, extras, zs, conds, encode)
 
-    def sample_multiple_smiles(self, dconds, scaffolds, zs=None, toklen=None, transform=True):
+    def sample_multiple_smiles(self, dconds, scaffolds, zs=None, toklen=None, transform=True, return_rows=False):
         """The reference's intended sample_multiple_smiles (sampling_tool.py, commented out there): row r has the
         properties dconds[r] and the scaffold scaffolds[r]; all rows are one batch and row r decodes as
         sample_smiles(dconds[r:r+1], scaffolds[r]) would."""
         if len(dconds) != len(scaffolds):
             raise ValueError(f"{len(dconds)} property rows for {len(scaffolds)} scaffolds")
         dconds = self.transform(dconds) if transform else torch.as_tensor(dconds, dtype=torch.float32)
-        return self._sample_multiple(scaffolds, zs, toklen, dconds)
+        return self._sample_multiple(scaffolds, zs, toklen, dconds, return_rows)
 
 
 sampling_tool_dict = {

@@ -5,6 +5,8 @@
 // Log-likelihoods (decode.py score_reference states the rule): gct_seq_logp scores given token rows against their
 // teacher-forced logits, gct_chosen_logp the token a decode step has just picked.  Both go through wave_token_logp, the
 // same wave-per-row log-softmax; every output has one writer and a fixed summation order (no atomics).
+// gct_seq_logp_bwd (decode.py seq_logp_grad_reference states the rule) is gct_seq_logp's gradient with respect to the
+// logits: ce_grad_row, the row arithmetic of gct_ce_bwd, with a weight per token column instead of one scalar.
 #include "common.h"
 #include "decode_rows.h"
 
@@ -31,6 +33,19 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
   if (threadIdx.x == 0) ws[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
+// One wave, one logits row lr[0, V): dr[c] = g * (softmax(lr)[c] - [c == t]).  The one place where this arithmetic is
+// written: gct_ce_bwd and gct_seq_logp_bwd give the same bits for the same row, target and weight.
+__device__ __forceinline__ void ce_grad_row(const float* lr, float* dr, int V, int64_t t, float g, int lane) {
+  float mx, se;
+  gct_wave_softmax_stats(lr, V, lane, mx, se);
+  const float inv = 1.0f / se;
+  for (int c = lane; c < V; c += 64) {
+    float pr = expf(lr[c] - mx) * inv;
+    if (c == t) pr -= 1.0f;
+    dr[c] = g * pr;
+  }
+}
+
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ logits,
                                                      const int64_t* __restrict__ target,
                                                      const float* gout, float* dlogits,
@@ -45,14 +60,7 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
       for (int c = lane; c < V; c += 64) dr[c] = 0.f;
       continue;
     }
-    float mx, se;
-    gct_wave_softmax_stats(lr, V, lane, mx, se);
-    const float inv = 1.0f / se;
-    for (int c = lane; c < V; c += 64) {
-      float pr = expf(lr[c] - mx) * inv;
-      if (c == t) pr -= 1.0f;
-      dr[c] = g * pr;
-    }
+    ce_grad_row(lr, dr, V, t, g, lane);
   }
 }
 
@@ -122,6 +130,39 @@ __global__ __launch_bounds__(256) void seq_logp_kernel(const float* __restrict__
   }
 }
 
+// one wave per logits row (r, j), four rows per workgroup, the grid strides over the rest (ce_bwd_kernel's layout).
+// Row j of sequence r predicts token column c = j - row_shift + 1 and is scored under seq_logp_kernel's predicate; its
+// weight is g = g_logp[r] + g_token[r][c] (a null table: 0).  A row that is not scored, or whose weight is 0, gets V
+// exact zeros and its logits are NOT read (the decoder may never have computed them).  Everything a branch depends on
+// is one value per wave.
+__global__ __launch_bounds__(256) void seq_logp_bwd_kernel(const float* __restrict__ logits, int64_t ld, int V,
+                                                           int64_t rows_per_seq, int row_shift,
+                                                           const int64_t* __restrict__ ys, int64_t ld_ys,
+                                                           const int32_t* __restrict__ prefix_lens, int64_t pad_id,
+                                                           int W, const float* __restrict__ g_logp,
+                                                           const float* __restrict__ g_token, int64_t ld_g,
+                                                           float* __restrict__ dlogits, int64_t ld_d, int64_t rows) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
+    const int64_t r = row / rows_per_seq, j = row - r * rows_per_seq;
+    const int64_t c = j - row_shift + 1;
+    float* dr = dlogits + row * ld_d;
+    int64_t tok = 0;
+    float g = 0.f;
+    if (j >= row_shift && c >= 1 && c < W) {
+      const int t0 = prefix_lens ? prefix_lens[r] : 1;
+      tok = ys[r * ld_ys + c];
+      if (c >= t0 && tok != pad_id && tok >= 0 && tok < V)
+        g = (g_logp ? g_logp[r] : 0.f) + (g_token ? g_token[r * ld_g + c] : 0.f);
+    }
+    if (g == 0.f) {                                     // not scored, or a zero weight
+      for (int v = lane; v < V; v += 64) dr[v] = 0.f;
+      continue;
+    }
+    ce_grad_row(logits + row * ld, dr, V, tok, -g, lane);
+  }
+}
+
 // one wave per decode row, as select_token_kernel: the column the selection has just written (gct_row_slot)
 __global__ __launch_bounds__(256) void chosen_logp_kernel(const float* __restrict__ logits, int V,
                                                           const int64_t* __restrict__ ys, int64_t ld_ys,
@@ -185,6 +226,32 @@ extern "C" int gct_seq_logp(const float* logits, int64_t ld, int V, int64_t rows
   hipLaunchKernelGGL(seq_logp_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, logits, ld, V,
                      rows_per_seq, row_shift, ys, ld_ys, prefix_lens, pad_id, W, token_logp, ld_out, logp, tokens, hits);
   GCT_LAUNCH_CHECK("seq_logp");
+  return GCT_OK;
+}
+
+extern "C" int gct_seq_logp_bwd(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift,
+                                const int64_t* ys, int64_t ld_ys, const int32_t* prefix_lens, int64_t pad_id, int n,
+                                int W, const float* g_logp, const float* g_token, int64_t ld_g, float* dlogits,
+                                int64_t ld_d, void* stream) {
+  GCT_CHECK_ARG(logits && ys && dlogits, "seq_logp_bwd: null pointer");
+  GCT_CHECK_ARG(g_logp || g_token, "seq_logp_bwd: both gradients are null (g_logp, g_token)");
+  GCT_CHECK_ARG(n >= 0 && V > 0 && ld >= V && ld_d >= V, "seq_logp_bwd: bad shape (n %d, V %d, ld %lld, ld_d %lld)", n,
+                V, (long long)ld, (long long)ld_d);
+  GCT_CHECK_ARG(W >= 1 && W <= SEQ_LOGP_MAX_W, "seq_logp_bwd: rows of %d tokens (1 .. %d supported)", W,
+                SEQ_LOGP_MAX_W);
+  GCT_CHECK_ARG(ld_ys >= W && (!g_token || ld_g >= W), "seq_logp_bwd: ld_ys / ld_g narrower than the %d token columns",
+                W);
+  GCT_CHECK_ARG(row_shift >= 0 && rows_per_seq >= (int64_t)row_shift + W - 1,
+                "seq_logp_bwd: %lld logits rows per sequence do not hold %d + %d", (long long)rows_per_seq, row_shift,
+                W - 1);
+  const int64_t rows = (int64_t)n * rows_per_seq;
+  if (rows == 0) return GCT_OK;
+  int64_t g = (rows + 3) / 4;
+  g = g > 4096 ? 4096 : g;
+  hipLaunchKernelGGL(seq_logp_bwd_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, logits, ld, V,
+                     rows_per_seq, row_shift, ys, ld_ys, prefix_lens, pad_id, W, g_logp, g_token, ld_g, dlogits, ld_d,
+                     rows);
+  GCT_LAUNCH_CHECK("seq_logp_bwd");
   return GCT_OK;
 }
 

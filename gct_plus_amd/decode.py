@@ -50,6 +50,8 @@ Log-likelihoods: the rule is stated once, in `score_reference`.  `score_tokens` 
 one decoder forward over the rows up to each sequence's last scored token, then gct_seq_logp on the logits; and
 `generate` / `generate_stream(return_logp=True)` return the log-probability of every token they pick: gct_chosen_logp
 reads the step's logits right behind the selection, so a sampling run needs no second forward to know its likelihood.
+`sequence_logp` is score_tokens with a gradient (the backward rule is stated once, in `seq_logp_grad_reference`;
+gct_seq_logp_bwd through engine.SeqLogpFn): the per-molecule policy term of a fine-tuning step (Train/finetune.py).
 
 Grammar-constrained decoding (`generate` / `generate_stream(grammar=SmilesGrammar(...))`): the rules are stated once, in
 `SmilesGrammar` (grammar_step, grammar_min_finish).  gct_grammar_mask runs in front of the selection: one wave per row
@@ -466,6 +468,74 @@ def _teacher_forced_logits(model, trg, z, src_mask, trg_mask, dconds, loss_rows)
     return model.out(x)
 
 
+def seq_logp_grad_reference(logits, ys, prefix_lens, pad_id, g_logp=None, g_token=None):
+    """THE statement of the backward rule of score_reference (gct_seq_logp_bwd implements it): the gradient with respect
+    to the logits [n, W - 1, V] of  sum_r g_logp[r] * logp[r] + sum_{r, c} g_token[r, c] * token_logp[r, c]  (g_logp [n],
+    g_token [n, W]; None: 0).  With g[r, c] = g_logp[r] + g_token[r, c], row c - 1 of sequence r gets
+      g[r, c] * ([v == ys[r, c]] - softmax(logits[r, c - 1])[v])   where column c is scored (score_reference's predicate),
+      exact zeros                                                   where it is not, or where g[r, c] == 0 -- whatever
+    the logits row holds, NaN included: such a row is never looked at.
+    Closed form, in the dtype of logits (fp32 at least), on the device of logits."""
+    ys = torch.as_tensor(ys)
+    lens = check_score_inputs(ys, prefix_lens, logits.shape[-1])
+    n, W = ys.shape
+    x = logits if logits.dtype == torch.float64 else logits.float()
+    if tuple(x.shape[:2]) != (n, W - 1):
+        raise ValueError(f"logits must be [{n}, {W - 1}, V], got {list(logits.shape)}")
+    dev = x.device
+    tgt = ys[:, 1:].long().to(dev)
+    scored = (torch.arange(1, W).view(1, -1) >= lens.view(-1, 1)).to(dev) & (tgt != pad_id)
+    g = torch.zeros(n, W, dtype=x.dtype, device=dev)
+    if g_logp is not None:
+        g = g + torch.as_tensor(g_logp).to(dev, x.dtype).view(n, 1)
+    if g_token is not None:
+        g = g + torch.as_tensor(g_token).to(dev, x.dtype).view(n, W)
+    live = scored & (g[:, 1:] != 0)
+    e = torch.exp(x - x.max(-1, keepdim=True).values)
+    grad = -(e / e.sum(-1, keepdim=True))
+    grad.scatter_add_(-1, tgt.unsqueeze(-1), torch.ones(n, W - 1, 1, dtype=x.dtype, device=dev))
+    return torch.where(live.unsqueeze(-1), g[:, 1:].unsqueeze(-1) * grad, torch.zeros((), dtype=x.dtype, device=dev))
+
+
+def _score_geometry(model, ys, prefix_lens):
+    """What every teacher-forced scoring call validates before any device work: (ys as a tensor, prefix lengths int64
+    [n] on the CPU, use_cond2dec, row_shift = the condition rows in front of a sequence's logits, V).  ValueError for
+    malformed inputs (check_score_inputs) and for rows beyond the positional table."""
+    dec = model.decoder
+    V = model.out.weight.shape[0]
+    ys = torch.as_tensor(ys)
+    lens = check_score_inputs(ys, prefix_lens, V)
+    W = ys.shape[1]
+    c2d = bool(dec.use_cond2dec and dec.nconds > 0)
+    off = dec.nconds if c2d else 0
+    pe_rows = dec.pe.pe.shape[1]
+    if off + W - 1 > pe_rows or W > 256:
+        raise ValueError(f"{W - 1} input tokens + {off} condition rows exceed the {pe_rows}-row positional table")
+    return ys, lens, c2d, off, V
+
+
+def _scoring_logits(model, z, src_mask, dconds, y, t0, pad_id, c2d):
+    """The teacher-forced logits of the token rows y int64 [m, W] (on the device, prefix lengths t0 int64 [m] there too)
+    as gct_seq_logp / gct_seq_logp_bwd take them: (logits [m * rows_per_seq, V], rows_per_seq), or None when no column of
+    the batch is scored (no forward then).  The decoder gets loss_rows = every input row up to the sequence's last
+    scored token (prefix rows included, so that the live rows stay a prefix): the rows behind it are not computed when
+    the row planner accepts the map; a use_cond2dec model runs every row."""
+    from .Model.modules import get_trg_mask
+    dec = model.decoder
+    W = y.shape[1]
+    cols = torch.arange(W, device=y.device).view(1, -1)
+    scored = (cols >= t0.view(-1, 1)) & (y != pad_id)
+    last = (scored * cols).amax(1)                                  # a row's last scored column (0: none)
+    if not bool(last.any()):
+        return None
+    trg = y[:, :-1].contiguous()
+    trg_mask = get_trg_mask(trg, pad_id, c2d, dconds if dec.nconds > 0 else None)
+    loss_rows = cols[:, :W - 1] < last.view(-1, 1)                  # input row c - 1 predicts token c
+    logits = _teacher_forced_logits(model, trg, z, src_mask, trg_mask, dconds, loss_rows)
+    rows = logits.shape[1]                                          # W - 1 (+ the condition rows of use_cond2dec)
+    return logits.reshape(y.shape[0] * rows, logits.shape[-1]), rows
+
+
 @torch.no_grad()
 def score_tokens(model, z, src_mask, dconds, ys, prefix_lens=None, pad_id=1, chunk=512):
     """Teacher-forced log-likelihood of the token rows ys [n, W] (score_reference's layout and rule) under
@@ -476,46 +546,61 @@ def score_tokens(model, z, src_mask, dconds, ys, prefix_lens=None, pad_id=1, chu
     every input row up to the sequence's last scored token (prefix rows included, so that the live rows stay a prefix):
     the rows behind it are not computed when the row planner accepts the map; a use_cond2dec model runs every row.
     ValueError before any device work for malformed inputs (check_score_inputs) and for rows beyond the positional
-    table."""
-    from .Model.modules import get_trg_mask
-    dec = model.decoder
-    V = model.out.weight.shape[0]
-    ys = torch.as_tensor(ys)
-    lens = check_score_inputs(ys, prefix_lens, V)
+    table.  sequence_logp is the same computation with a gradient."""
+    ys, lens, c2d, off, V = _score_geometry(model, ys, prefix_lens)
     if isinstance(chunk, bool) or not isinstance(chunk, numbers.Integral) or chunk < 1:
         raise ValueError(f"chunk must be an int >= 1, got {chunk!r}")
     n, W = ys.shape
-    c2d = bool(dec.use_cond2dec and dec.nconds > 0)
-    off = dec.nconds if c2d else 0
-    pe_rows = dec.pe.pe.shape[1]
-    if off + W - 1 > pe_rows or W > 256:
-        raise ValueError(f"{W - 1} input tokens + {off} condition rows exceed the {pe_rows}-row positional table")
     dev = z.device
     token_logp = torch.empty(n, W, device=dev)
     logp = torch.empty(n, device=dev)
     tokens = torch.empty(n, dtype=torch.int32, device=dev)
     hits = torch.empty(n, dtype=torch.int32, device=dev)
-    cols = torch.arange(W, device=dev).view(1, -1)
     for lo in range(0, n, int(chunk)):
         hi = min(n, lo + int(chunk))
         y = ys[lo:hi].to(dev, torch.int64).contiguous()
         t0 = lens[lo:hi].to(dev)
         out = (token_logp[lo:hi], logp[lo:hi], tokens[lo:hi], hits[lo:hi])
-        scored = (cols >= t0.view(-1, 1)) & (y != pad_id)
-        last = (scored * cols).amax(1)                              # a row's last scored column (0: none)
-        if not bool(last.any()):                                    # nothing to score: no forward
+        dc = None if dconds is None else dconds[lo:hi].to(dev)
+        sm = None if src_mask is None else src_mask[lo:hi].to(dev)
+        got = _scoring_logits(model, z[lo:hi], sm, dc, y, t0, pad_id, c2d)
+        if got is None:                                             # nothing to score: no forward
             for t in out:
                 t.zero_()
             continue
-        trg = y[:, :-1].contiguous()
-        dc = None if dconds is None else dconds[lo:hi].to(dev)
-        sm = None if src_mask is None else src_mask[lo:hi].to(dev)
-        trg_mask = get_trg_mask(trg, pad_id, c2d, dc if dec.nconds > 0 else None)
-        loss_rows = cols[:, :W - 1] < last.view(-1, 1)              # input row c - 1 predicts token c
-        logits = _teacher_forced_logits(model, trg, z[lo:hi], sm, trg_mask, dc, loss_rows)
-        rows = logits.shape[1]                                      # W - 1 (+ the condition rows of use_cond2dec)
-        ops.seq_logp(logits.reshape((hi - lo) * rows, V), y, None if prefix_lens is None else t0.to(torch.int32),
-                     pad_id, row_shift=off, rows_per_seq=rows, out=out)
+        logits2d, rows = got
+        ops.seq_logp(logits2d, y, None if prefix_lens is None else t0.to(torch.int32), pad_id, row_shift=off,
+                     rows_per_seq=rows, out=out)
+    return logp, tokens, hits, token_logp
+
+
+def sequence_logp(model, z, src_mask, dconds, ys, prefix_lens=None, pad_id=1):
+    """score_tokens with a gradient: the same inputs, the same rule, the same values bit for bit, and logp [n] /
+    token_logp [n, W] attached to the autograd graph of the decoder's parameters, of model.out and -- when it requires
+    grad -- of z.  Returns (logp, tokens, hits, token_logp) on the device; tokens / hits are counts and carry no
+    gradient.  A per-molecule objective (REINFORCE, reward-weighted likelihood, the best k of a batch) is any function
+    of logp; Train/finetune.py builds the policy-gradient step on it.
+    ONE decoder forward over all n rows, no chunks -- the caller sizes n -- in the model's current train / eval mode
+    (dropout is live under model.train()).  loss_rows is score_tokens' rule, so the rows behind a sequence's last scored
+    token are computed neither forward nor backward when the row planner accepts the map; the backward
+    (gct_seq_logp_bwd through engine.SeqLogpFn) writes exact zeros on every logits row that is not scored, so no
+    gradient ever falls on a skipped row (ops.assert_no_skipped_row_gradients stays silent).  The encoder is not part of
+    the graph: z is an input.
+    ValueError before any device work for whatever check_score_inputs refuses, for rows beyond the positional table, and
+    for a batch without a single scored column.  A single row with nothing scored is fine: value 0, gradient 0."""
+    ys, lens, c2d, off, V = _score_geometry(model, ys, prefix_lens)
+    n, W = ys.shape
+    host = ys.detach().cpu()
+    if not bool(((torch.arange(W).view(1, -1) >= lens.view(-1, 1)) & (host != pad_id))[:, 1:].any()):
+        raise ValueError("sequence_logp: no column of the batch is scored (every row is prefix or pad)")
+    dev = z.device
+    y = ys.to(dev, torch.int64).contiguous()
+    t0 = lens.to(dev)
+    dc = None if dconds is None else dconds.to(dev)
+    sm = None if src_mask is None else src_mask.to(dev)
+    logits2d, rows = _scoring_logits(model, z, sm, dc, y, t0, pad_id, c2d)
+    logp, token_logp, tokens, hits = engine.SeqLogpFn.apply(
+        logits2d, y, None if prefix_lens is None else t0.to(torch.int32), pad_id, off)
     return logp, tokens, hits, token_logp
 
 

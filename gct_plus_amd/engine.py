@@ -20,6 +20,7 @@ import os
 from typing import List, NamedTuple, Optional
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import ops
 from .flat import HANDED_SLOTS
@@ -920,6 +921,46 @@ class CrossEntropySumFn(torch.autograd.Function):
     def backward(ctx, g):
         l2, t = ctx.saved_tensors
         return ops.ce_bwd(l2, t, _f32c(g), ctx.pad_id).view(ctx.shp), None, None
+
+
+class SeqLogpFn(torch.autograd.Function):
+    """Per-sequence log-likelihoods with a gradient (decode.score_reference / seq_logp_grad_reference state the rules):
+    apply(logits, ys, prefix_lens, pad_id, row_shift) -> (logp [n], token_logp [n, W], tokens [n], hits [n]).
+    logits fp32 [n, R, V] or [n * R, V] (unit column stride; R >= row_shift + W - 1 logits rows per sequence), ys int64
+    [n, W], prefix_lens int32 [n] on the device or None.  tokens / hits are counts: not differentiable.  The backward
+    is gct_seq_logp_bwd: it writes every row of dlogits, exact zeros where nothing is scored or the weight is 0."""
+
+    @staticmethod
+    def forward(ctx, logits, ys, prefix_lens, pad_id, row_shift):
+        n, V = ys.shape[0], logits.shape[-1]
+        if logits.dim() == 3:
+            if logits.shape[0] != n:
+                raise ValueError(f"SeqLogpFn: {logits.shape[0]} logits blocks for {n} token rows")
+            l2 = _f32c(logits).view(-1, V)
+        elif logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1:
+            l2 = logits
+        else:
+            l2 = _f32c(logits).reshape(-1, V)
+        R = l2.shape[0] // n if n else ys.shape[1] - 1 + int(row_shift)
+        ys = ys.contiguous()
+        tl, lp, nt, nh = ops.seq_logp(l2, ys, prefix_lens, int(pad_id), row_shift=int(row_shift), rows_per_seq=R)
+        ctx.save_for_backward(l2, ys, prefix_lens)
+        ctx.geom = (int(pad_id), int(row_shift), R, logits.shape)
+        ctx.set_materialize_grads(False)                 # an output nobody used arrives as None, not as zeros
+        ctx.mark_non_differentiable(nt, nh)
+        return lp, tl, nt, nh
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_logp, g_token, *unused):
+        l2, ys, prefix_lens = ctx.saved_tensors
+        pad_id, row_shift, R, shape = ctx.geom
+        if g_logp is None and g_token is None:
+            return torch.zeros(shape, device=l2.device), None, None, None, None
+        dl = ops.seq_logp_bwd(l2, ys, prefix_lens, pad_id, row_shift=row_shift, rows_per_seq=R,
+                              g_logp=None if g_logp is None else _f32c(g_logp),
+                              g_token=None if g_token is None else _f32c(g_token))
+        return dl.view(shape), None, None, None, None
 
 
 class KldFn(torch.autograd.Function):

@@ -1022,6 +1022,54 @@ def seq_logp(logits2d, ys, prefix_lens=None, pad_id=1, row_shift=0, rows_per_seq
     return out
 
 
+def seq_logp_bwd(logits2d, ys, prefix_lens=None, pad_id=1, row_shift=0, rows_per_seq=None, g_logp=None, g_token=None,
+                 V=None, out=None):
+    """gct_seq_logp_bwd (decode.seq_logp_grad_reference states the rule): the gradient of seq_logp's logp [n] and
+    token_logp [n, W] with respect to the logits, for the geometry seq_logp takes (same checks: ys int64 [n, W], logits2d
+    fp32 [>= n * rows_per_seq, V] with unit column stride, a strided view is fine; prefix_lens int32 [n] or None).
+    g_logp fp32 [n] / g_token fp32 [n, W] with unit column stride: the incoming gradients, either may be None (0), the
+    library refuses both.  logits2d None (with V given) passes a null pointer: the library refuses.
+    Returns dlogits fp32, contiguous, in the shape of logits2d (or fills `out`, [>= n * rows_per_seq, V] with unit column
+    stride): every row is written -- zeros on the rows that are not scored or whose weight is 0, whose logits are not
+    read."""
+    _chk(ys, "seq_logp_bwd.ys", torch.int64)
+    if ys.dim() != 2 or ys.stride(1) != 1:
+        raise ValueError("seq_logp_bwd: ys must be [n, W] with unit column stride")
+    n, W = ys.shape
+    R = W - 1 if rows_per_seq is None else int(rows_per_seq)
+    ld = 0
+    if logits2d is not None:
+        _chk(logits2d, "seq_logp_bwd.logits")
+        if logits2d.dim() != 2 or logits2d.stride(1) != 1 or logits2d.shape[0] < n * R:
+            raise ValueError(f"seq_logp_bwd: logits must be [>= {n * R}, V] with unit column stride, got "
+                             f"{list(logits2d.shape)}")
+        V, ld = logits2d.shape[1], logits2d.stride(0)
+    if prefix_lens is not None:
+        _check_row_off(prefix_lens, n)
+    if g_logp is not None:
+        _chk(g_logp, "seq_logp_bwd.g_logp")
+        if g_logp.numel() != n or not g_logp.is_contiguous():
+            raise ValueError(f"seq_logp_bwd: g_logp must be a contiguous fp32 tensor of {n} entries")
+    if g_token is not None:
+        _chk(g_token, "seq_logp_bwd.g_token")
+        if g_token.shape != (n, W) or g_token.stride(1) != 1:
+            raise ValueError(f"seq_logp_bwd: g_token must be [{n}, {W}] with unit column stride")
+    rows = max(n * R, 0 if logits2d is None else logits2d.shape[0])
+    if out is None:
+        out = torch.empty(rows, int(V), device=ys.device)
+        if rows > n * R:
+            out[n * R:].zero_()                          # rows behind the last sequence belong to nobody
+    _chk(out, "seq_logp_bwd.dlogits")
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < n * R or out.shape[1] != int(V):
+        raise ValueError(f"seq_logp_bwd: out must be [>= {n * R}, {int(V)}] with unit column stride")
+    if n == 0:
+        return out                                       # no sequence: nothing to write (an empty tensor has no address)
+    check(_L().gct_seq_logp_bwd(_p(logits2d), ld, int(V), R, int(row_shift), _p(ys), ys.stride(0), _p(prefix_lens),
+                                int(pad_id), n, W, _p(g_logp), _p(g_token), 0 if g_token is None else g_token.stride(0),
+                                _p(out), out.stride(0), _st()), "gct_seq_logp_bwd")
+    return out
+
+
 def chosen_logp(logits2d, ys, pos_dev, out, pad_id, row_off=None, item=None, prefix_len=None):
     """gct_chosen_logp, after select_token on the same logits [n, V] and device counter: out[dst, p] = the model's
     log-probability (raw logits, temperature 1) of the token ys[r, p] the selection has just written at

@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 23
+#define GCT_ABI_VERSION 24
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -366,6 +366,19 @@ int gct_ce_bwd(const float* logits, const int64_t* target, const float* gout, fl
 int gct_seq_logp(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift, const int64_t* ys,
                  int64_t ld_ys, const int32_t* prefix_lens, int64_t pad_id, int n, int W, float* token_logp,
                  int64_t ld_out, float* logp, int32_t* tokens, int32_t* hits, void* stream);
+/* The gradient of gct_seq_logp with respect to the logits (gct_plus_amd/decode.py seq_logp_grad_reference states the
+ * rule); same geometry.  Logits row j of sequence r (0 <= j < rows_per_seq) predicts token column c = j - row_shift + 1
+ * and is scored exactly when gct_seq_logp scores (r, c): j >= row_shift, 1 <= c < W, c >= prefix_lens[r],
+ * ys[r][c] != pad_id and 0 <= ys[r][c] < V.  With g = g_logp[r] + g_token[r][c] (g_logp fp32 [n], g_token fp32
+ * [n][ld_g]: the gradients of logp and token_logp; either may be NULL and then counts as 0, not both) a scored row gets
+ *   dlogits[v] = (-g) * (softmax(x)[v] - [v == ys[r][c]])
+ * in gct_ce_bwd's arithmetic (the same bits for the same row and weight).  A row that is not scored, or whose g is 0,
+ * gets V exact zeros, and its logits are not read.  All n * rows_per_seq rows of dlogits (row stride ld_d >= V) are
+ * WRITTEN, nothing is accumulated.  One wave per row, no atomics: bit-reproducible.  Shape limits as gct_seq_logp's;
+ * otherwise GCT_ERR_ARG before any launch.  n == 0: nothing to do. */
+int gct_seq_logp_bwd(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift, const int64_t* ys,
+                     int64_t ld_ys, const int32_t* prefix_lens, int64_t pad_id, int n, int W, const float* g_logp,
+                     const float* g_token, int64_t ld_g, float* dlogits, int64_t ld_d, void* stream);
 /* The decode-step form: launched after gct_select_token in the step unit, on the same logits [n][V] and the same
  * device counter.  Row r looks at column p = *pos - row_off[r] + 1 (row_off nullable), the column the selection has
  * just written, takes tok = ys[r][p] and writes out[dst][p] = log-softmax(logits[r])[tok], or 0 when tok == pad_id (a

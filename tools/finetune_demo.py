@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""Policy-gradient fine-tuning end to end on a synthetic-weight pscavaetf (tiny by default, --full: d512 / 6 layers):
+--rounds times  sample --n molecules (multinomial, one scaffold) -> reward -> Train/finetune.reinforce_step.
+The reward is decode.SmilesGrammar.well_formed of the generated tokens (1 or 0), so no chemistry toolkit is needed: a
+randomly initialised model seldom closes its rings and branches and ends with <eos>, and the update teaches it to.
+Prints the well-formed rate of a fixed evaluation batch before and after, the rate of every round, and the time of a
+reinforce_step (forward + backward + optimizer, the sampling not included).
+
+--time-step: no sampling; --n fixed rows of MOSES-like lengths (clip(round(N(35, 8)), 15, 78) tokens + <eos> behind a
+scaffold prefix), --rounds reinforce_steps on them after two warm-up steps: the figure to put next to a bench.py
+training step of the same batch size (recorded in DESIGN 4, not gated)."""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--full", action="store_true", help="the full-size model (N 6, d_model 512, dff 2048, h 8, latent 128)")
+ap.add_argument("--n", type=int, default=512, help="molecules per round")
+ap.add_argument("--rounds", type=int, default=30)
+ap.add_argument("--lr", type=float, default=1e-4)
+ap.add_argument("--max-strlen", type=int, default=40)
+ap.add_argument("--scaffold", default="c1ccccc1")
+ap.add_argument("--seed", type=int, default=1)
+ap.add_argument("--time-step", action="store_true", help="time reinforce_step on fixed rows of MOSES-like lengths")
+a = ap.parse_args()
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from gct_plus_amd import data, synthetic  # noqa: E402
+from gct_plus_amd.decode import SmilesGrammar  # noqa: E402
+from gct_plus_amd.Inference.sampling_tool import DecodedRows, PscavaetfSampling  # noqa: E402
+from gct_plus_amd.Model import model_dict  # noqa: E402
+from gct_plus_amd.optim import FusedAdam  # noqa: E402
+from gct_plus_amd.Train.finetune import reinforce_step  # noqa: E402
+
+mtype = "pscavaetf"
+nc = synthetic.n_conds(mtype)
+dims = (dict(N=6, d_model=512, dff=2048, h=8, latent_dim=128) if a.full
+        else dict(N=2, d_model=64, dff=128, h=4, latent_dim=16))
+TRG = data.Vocab(synthetic.GRAMMAR_VOCAB)
+SRC = data.Vocab([t for t in synthetic.GRAMMAR_VOCAB if t not in ("<sos>", "<eos>")])
+torch.manual_seed(a.seed)
+model = model_dict[mtype](len(SRC), len(TRG), dropout=0.0, nconds=nc, use_cond2lat=True, **dims).cuda()
+sampler = PscavaetfSampling(model, SRC, TRG, latent_dim=dims["latent_dim"], max_strlen=a.max_strlen, cond_dim=nc,
+                            decode_algo="multinomial", seed=a.seed)
+grammar = SmilesGrammar(TRG.itos, sampler.pad_id, sampler.eos_id)
+opt = FusedAdam(model.parameters(), lr=a.lr, betas=(0.9, 0.98), eps=1e-9, model=model)
+gen = torch.Generator().manual_seed(a.seed)
+
+
+def timed_step(rows, reward):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    stats = reinforce_step(sampler, opt, rows, reward)
+    torch.cuda.synchronize()
+    return stats, (time.perf_counter() - t0) * 1e3
+
+
+if a.time_step:
+    n, Le = a.n, 80 + nc
+    sca = sampler.smi_to_id(a.scaffold)
+    t0 = len(sca) + 2
+    ln = np.clip(np.rint(np.random.default_rng(0).normal(35, 8, n)), 15, 78).astype(np.int64)
+    W = t0 + int(ln.max()) + 1
+    ys = torch.randint(5, len(TRG), (n, W), generator=gen)
+    ys[:, :t0] = torch.tensor([sampler.sos_id] + sca + [sampler.sep_id])
+    cols, end = torch.arange(W)[None, :], torch.from_numpy(ln)[:, None] + t0
+    ys[cols == end] = sampler.eos_id
+    ys[cols > end] = sampler.pad_id
+    src_mask = (torch.arange(Le)[None, :] < (torch.from_numpy(ln) + t0 - 1 + nc)[:, None]).unsqueeze(1)
+    rows = DecodedRows(torch.randn(n, Le, dims["latent_dim"], generator=gen).cuda(), ys.cuda(), src_mask.cuda(),
+                       torch.randn(n, nc, generator=gen).cuda(), torch.full((n,), t0))
+    reward = torch.rand(n, generator=gen)
+    for _ in range(2):
+        timed_step(rows, reward)
+    ms = []
+    for i in range(a.rounds):
+        stats, dt = timed_step(rows, reward)
+        ms.append(dt)
+        print(f"step {i}: {dt:8.2f} ms  loss {stats['loss']:.4f}  tokens {stats['tokens']}", flush=True)
+    print(f"reinforce_step on {n} {'full-size' if a.full else 'tiny'} {mtype} rows of {W} columns ({stats['tokens']} scored "
+          f"tokens): median {float(np.median(ms)):.2f} ms, best {min(ms):.2f} ms of {len(ms)}")
+    sys.exit(0)
+
+
+def sample(n, seed):
+    """n molecules of one scaffold -> (DecodedRows, reward [n]: 1 where the generated tokens are a well-formed string)."""
+    sampler.seed = seed
+    g = torch.Generator().manual_seed(seed)
+    toklen = [a.max_strlen // 2] * n
+    zs = torch.randn(n, len(sampler.smi_to_id(a.scaffold)) + 1 + toklen[0], dims["latent_dim"], generator=g)
+    out = sampler.sample_smiles(torch.randn(n, nc, generator=g).numpy(), a.scaffold, zs=zs, toklen=toklen, transform=False,
+                                return_rows=True)
+    rows = out[-1]
+    t0 = int(rows.prefix_lens[0])
+    reward = torch.tensor([float(grammar.well_formed(r)) for r in rows.ys[:, t0:].cpu().tolist()])
+    return rows, reward
+
+
+EVAL_SEED = 10 ** 6
+before = float(sample(a.n, EVAL_SEED)[1].mean())
+print(f"{'full-size' if a.full else 'tiny'} {mtype}, {a.n} molecules per round, lr {a.lr}: well-formed rate of the "
+      f"evaluation batch before fine-tuning {before:.3f}", flush=True)
+ms = []
+for k in range(a.rounds):
+    rows, reward = sample(a.n, a.seed * 1000 + k)
+    stats, dt = timed_step(rows, reward)
+    ms.append(dt)
+    print(f"round {k:3d}: well-formed {stats['mean_reward']:.3f}  mean logp {stats['mean_logp']:8.3f}  loss "
+          f"{stats['loss']:8.4f}  step {dt:7.2f} ms", flush=True)
+after = float(sample(a.n, EVAL_SEED)[1].mean())
+print(f"well-formed rate of the evaluation batch: {before:.3f} before, {after:.3f} after {a.rounds} rounds; "
+      f"reinforce_step median {float(np.median(ms[1:] or ms)):.2f} ms")
