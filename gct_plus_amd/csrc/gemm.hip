@@ -1592,6 +1592,47 @@ static int wgrad_splits(int64_t M, int64_t Ntot, int64_t K, bool x6 = false) {
   return (int)want;
 }
 
+// ---- the route of one gct_linear_wgrad call: the one statement of its vector test, kernel, split and bias rules
+// (gct_linear_wgrad executes it, gct_wgrad_route reports it)
+struct WgradRoute {
+  GemmRoute::Kind kind;   // X6 (bf16 tiles), F32_FAST, F32_VEC or F32
+  bool bias_fused;        // bias slabs written by the GEMM kernel; else gct_colsum (which borrows ws first)
+};
+
+static bool wgrad_vec_shape(int64_t lddy, int64_t ldx, int nper, int K) {
+  return (lddy % 4 == 0) && (ldx % 4 == 0) && (nper % 4 == 0) && (K % 4 == 0);
+}
+
+// the shape half of a wgrad launch: dW[n][k] = sum_m dY[m][n] X[m][k] as slabs at ws (only its alignment is read)
+static GemmArgs wgrad_args(int64_t M, int nseg, int nper, int K, int64_t lddy, int64_t ldx, float* ws) {
+  const int64_t Ntot = (int64_t)nseg * nper;
+  GemmArgs g = {};
+  g.M = Ntot; g.N = K; g.K = M;
+  g.lda = lddy; g.a_nper = nper;
+  g.ldb = ldx; g.b_nper = INT64_MAX / 4;
+  g.c0 = ws; g.ldc = K; g.c_nper = INT64_MAX / 4;
+  g.slab_stride = Ntot * K;
+  g.ksplit = BK; g.nsplit = 1; g.epi = EPI_SLAB;
+  return g;
+}
+
+// Pure: no launch, no device access, no environment.  Sets g.ksplit / g.nsplit: the rows split into `wgrad_splits`
+// ranges of whole 32-row tiles (fewer when they do not all get a tile).
+static WgradRoute plan_wgrad(GemmArgs& g, bool vec, bool want_bias, int mode) {
+  const int64_t M = g.K;
+  g.ksplit = BK; g.nsplit = 1;
+  // bf16x6 or bf16x3: same route.  The kernel choice does not depend on the split (every split is whole K-tiles)
+  const bool use_x6 = plan_gemm<false, false>(g, vec, mode, nullptr, 0).kind == GemmRoute::X6;
+  const int splits = wgrad_splits(M, g.M, g.N, use_x6);
+  int64_t ks = (M + splits - 1) / splits;
+  ks = (ks + BK - 1) / BK * BK;
+  g.ksplit = ks > 0 ? ks : BK;
+  g.nsplit = (int)((M + g.ksplit - 1) / g.ksplit);
+  if (g.nsplit < 1) g.nsplit = 1;
+  const GemmRoute::Kind kind = plan_gemm<false, false>(g, vec, mode, nullptr, 0).kind;   // what launch() will take
+  return {kind, want_bias && (kind == GemmRoute::X6 || kind == GemmRoute::F32_FAST)};
+}
+
 extern "C" int64_t gct_wgrad_ws_bytes(int64_t M, int64_t Ntot, int64_t K) {
   const int s1 = wgrad_splits(M, Ntot, K), s2 = wgrad_splits(M, Ntot, K, true);
   const int s = s1 > s2 ? s1 : s2;
@@ -1732,29 +1773,17 @@ extern "C" int gct_linear_wgrad(const float* dy0, const float* dy1, const float*
   GCT_CHECK_ARG(lddw == K, "linear_wgrad: dW must be dense [nper][K]");
   hipStream_t st = (hipStream_t)stream;
   const int64_t Ntot = (int64_t)nseg * nper;
-  const bool vec = al16(dy0) && al16(dy1) && al16(dy2) && al16(x) && (lddy % 4 == 0) &&
-                   (ldx % 4 == 0) && (nper % 4 == 0) && (K % 4 == 0);
-  GemmArgs g = {};
-  g.M = Ntot; g.N = K; g.K = M;  // dW[n][k] = sum_m dY[m][n] X[m][k]
-  g.a = mkseg(dy0, dy1, dy2); g.lda = lddy; g.a_nper = nper;
-  g.b = mkseg(x, nullptr, nullptr); g.ldb = ldx; g.b_nper = INT64_MAX / 4;
-  g.c0 = ws; g.ldc = K; g.c_nper = INT64_MAX / 4;
-  g.slab_stride = Ntot * K;
-  g.ksplit = BK; g.nsplit = 1; g.epi = EPI_SLAB;
-  const bool use_x6 = gemm_mode() != GCT_GEMM_F32 && x6_ok<X6_WGRAD>(g, vec);   // bf16x6 or bf16x3: same route
-  if (use_x6 && tile_list && tile_count) { g.kt_list = tile_list; g.kt_count = tile_count; }   // other kernels reduce over every row
-  const int splits = wgrad_splits(M, Ntot, K, use_x6);
-  int64_t ks = (M + splits - 1) / splits;
-  ks = (ks + BK - 1) / BK * BK;
-  g.ksplit = ks > 0 ? ks : BK;
-  g.nsplit = (int)((M + g.ksplit - 1) / g.ksplit);
-  if (g.nsplit < 1) g.nsplit = 1;
-  g.epi = EPI_SLAB;
+  const bool vec = al16(dy0) && al16(dy1) && al16(dy2) && al16(x) && wgrad_vec_shape(lddy, ldx, nper, K);
+  GemmArgs g = wgrad_args(M, nseg, nper, K, lddy, ldx, ws);
+  g.a = mkseg(dy0, dy1, dy2);
+  g.b = mkseg(x, nullptr, nullptr);
+  const WgradRoute r = plan_wgrad(g, vec, db0 != nullptr, gemm_mode());   // sets g.ksplit / g.nsplit
+  if (r.kind == GemmRoute::X6 && tile_list && tile_count) { g.kt_list = tile_list; g.kt_count = tile_count; }   // other kernels reduce over every row
   // bias gradients: fused into the GEMM on the fast path (column sums of the A tiles), else a
   // separate column-sum pass that borrows ws before the slabs are written (stream-ordered)
   float* bslab = nullptr;
   if (db0) {
-    if (use_x6 || fast_ok<false, false>(g, vec)) {
+    if (r.bias_fused) {
       int64_t off = (int64_t)g.nsplit * g.slab_stride;
       off = (off + 3) / 4 * 4;
       bslab = ws + off;                     // [nsplit][Ntot] right behind the weight slabs
@@ -1770,4 +1799,23 @@ extern "C" int gct_linear_wgrad(const float* dy0, const float* dy1, const float*
     return gct_reduce_slabs_seg2(ws, g.nsplit, g.slab_stride, dw0, dw1, dw2, (int64_t)nper * K, Ntot * K, bslab, Ntot,
                                  db0, db1, db2, nper, Ntot, st);
   return gct_reduce_slabs_seg(ws, g.nsplit, g.slab_stride, dw0, dw1, dw2, (int64_t)nper * K, Ntot * K, st);
+}
+
+extern "C" int gct_wgrad_route(int64_t M, int nseg, int nper, int K, int64_t lddy, int64_t ldx, int aligned16,
+                               int want_bias, int mode, int64_t* out4) {
+  GCT_CHECK_ARG(out4 && M >= 0 && K > 0 && nseg >= 1 && nseg <= 3 && nper > 0 && lddy >= 0 && ldx >= 0,
+                "wgrad_route: bad args");
+  GCT_CHECK_ARG(mode == GCT_GEMM_F32 || mode == GCT_GEMM_BF16X6 || mode == GCT_GEMM_BF16X3,
+                "wgrad_route: unknown mode %d", mode);
+  // only the alignment of the workspace is read: a stand-in address with the alignment asked about
+  float* const ws = reinterpret_cast<float*>((uintptr_t)(aligned16 ? 16 : 4));
+  GemmArgs g = wgrad_args(M, nseg, nper, K, lddy, ldx, ws);
+  const WgradRoute r = plan_wgrad(g, aligned16 && wgrad_vec_shape(lddy, ldx, nper, K), want_bias != 0, mode);
+  out4[0] = r.kind == GemmRoute::X6 ? GCT_WGRAD_BF16_TILES
+            : r.kind == GemmRoute::F32_FAST ? GCT_WGRAD_F32_FAST
+            : r.kind == GemmRoute::F32_VEC ? GCT_WGRAD_F32_VEC : GCT_WGRAD_F32_SCALAR;
+  out4[1] = g.nsplit;
+  out4[2] = g.ksplit;
+  out4[3] = r.bias_fused ? 1 : 0;
+  return GCT_OK;
 }

@@ -308,6 +308,15 @@ def gemm_launch_counts():
     return int(out[0]), int(out[1])
 
 
+def wgrad_route(M, nseg, nper, K, lddy, ldx, aligned16=True, want_bias=True, mode=None):
+    """(kind, nsplit, rows per split, bias fused) of gct_linear_wgrad for a shape (gct_wgrad_route: no launch)."""
+    import ctypes
+    out = (ctypes.c_int64 * 4)()
+    check(_L().gct_wgrad_route(M, nseg, nper, K, lddy, ldx, int(aligned16), int(want_bias),
+                               gemm_get_mode() if mode is None else int(mode), ctypes.addressof(out)), "gct_wgrad_route")
+    return tuple(int(v) for v in out)
+
+
 def split_planes(flat: torch.Tensor, planes: Optional[torch.Tensor] = None) -> torch.Tensor:
     """flat fp32 [numel] -> int16 [3, numel] holding the hi / mid / lo bf16 pieces of every element
     (exact: hi + mid + lo == x).  numel % 4 == 0."""

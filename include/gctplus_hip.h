@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 24
+#define GCT_ABI_VERSION 25
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -149,12 +149,34 @@ int64_t gct_linear_dgrad_ws_bytes(int64_t M, int Ntot, int K);
  * ws >= gct_wgrad_ws_bytes(M, nseg*nper, K). db* nullable.
  * tile_list / tile_count (nullable, together): reduce only over the listed 32-row token tiles (gct_nonzero_row_tiles /
  * gct_live_rows, below) -- exact whenever every dy row outside them is zero (the skipped terms are 0 * x).  The list
- * is honoured by the bf16x6 kernel; the fp32 kernels reduce over all rows (same result). */
+ * is honoured by the bf16x6 kernel; the fp32 kernels reduce over all rows (same result).
+ * Contract:
+ *   - the list holds ASCENDING indices of 32-row tiles, each below M / 32; M % 32 == 0 on the route that reads it
+ *     (GCT_WGRAD_BF16_TILES is taken only for such M);
+ *   - *tile_count == 0, or M == 0, gives dw = 0 and db = 0 exactly (dy0 and x must still be non-null);
+ *   - the call writes nothing outside dw*, db* and the first gct_wgrad_ws_bytes(M, nseg*nper, K) bytes of ws;
+ *   - what dw*, db* and ws hold on entry does not affect the result. */
 int gct_linear_wgrad(const float* dy0, const float* dy1, const float* dy2, int64_t lddy,
                      int64_t M, int nseg, int nper, const float* x, int64_t ldx, int K,
                      float* dw0, float* dw1, float* dw2, int64_t lddw,
                      float* db0, float* db1, float* db2, float* ws,
                      const int32_t* tile_list, const int32_t* tile_count, void* stream);
+/* The route gct_linear_wgrad takes for a shape (no launch, no device access; the rule the call itself executes):
+ *   out4[0] kernel: GCT_WGRAD_F32_SCALAR (gemm_f32_kernel, scalar loads), GCT_WGRAD_F32_VEC (the same with float4
+ *           loads), GCT_WGRAD_F32_FAST (gemm_f32_fast_kernel) or GCT_WGRAD_BF16_TILES (gemm_x6_kernel, bf16x6 / bf16x3);
+ *   out4[1] nsplit: slabs written, one per range of rows;
+ *   out4[2] rows per split (a multiple of 32; with a tile list split z takes entries [z * per, z * per + per) of the
+ *           list instead, per = ceil(*tile_count / nsplit));
+ *   out4[3] 1: the GEMM kernel writes the bias slabs behind the weight slabs; 0: gct_colsum, which borrows the head
+ *           of ws before the slabs are written (or no bias asked for).
+ * aligned16: dy0..2, x and ws are all 16-byte aligned.  want_bias: db0 != NULL.  mode: a GCT_GEMM_* value (below),
+ * passed in rather than read from the process. */
+#define GCT_WGRAD_F32_SCALAR 0
+#define GCT_WGRAD_F32_VEC 1
+#define GCT_WGRAD_F32_FAST 2
+#define GCT_WGRAD_BF16_TILES 3
+int gct_wgrad_route(int64_t M, int nseg, int nper, int K, int64_t lddy, int64_t ldx, int aligned16, int want_bias,
+                    int mode, int64_t* out4);
 
 /* ---- GEMM arithmetic mode and pre-split weights ------------------------------------------
  * The nn.Linear GEMMs (Model/sublayers.py:54-59,64-66,70,81-88) run in one of two modes with
