@@ -31,7 +31,8 @@ element (KVDecoder.generate(return_logp=True): no second forward).
 Fine-tuning on what was sampled: `return_rows=True` on `decode`, `sample_smiles` and `sample_multiple_smiles` appends a
 `DecodedRows` -- the latents, mask, conditions and prefix lengths the decode consumed and the token rows it produced --
 and `logp(*rows)` is `score(*rows)` WITH a gradient (decode.sequence_logp), on the device: the policy term of
-Train/finetune.reinforce_step.  Not with beam search.
+Train/finetune.reinforce_step.  `policy_terms(*rows, prior=)` adds the policy's entropy and its KL divergence from a
+frozen prior (decode.sequence_policy), the regularisers of that step.  Not with beam search.
 
 `well_formed=True` (optional): greedy / multinomial decodes are constrained by decode.SmilesGrammar built from the target
 vocabulary -- every returned string has balanced branches, paired ring-closure numbers, no dangling bond, and ended
@@ -52,8 +53,9 @@ import torch
 
 from ..Model.modules import get_src_mask
 from ..data import Vocab, tokenize
-from ..decode import (BEAM_ALPHA, KVDecoder, SmilesGrammar, check_beam_size, check_sample_filter, check_stream_model,
-                      check_stream_rows, generated_tokens, score_tokens, sequence_logp)
+from ..decode import (BEAM_ALPHA, KVDecoder, PolicyTerms, SmilesGrammar, check_beam_size, check_sample_filter,
+                      check_stream_model, check_stream_rows, generated_tokens, score_tokens, sequence_logp,
+                      sequence_policy)
 
 
 class Scores(NamedTuple):
@@ -285,6 +287,17 @@ class Sampling:
         logp, tokens, hits, token_logp = sequence_logp(self.model, zs, src_mask, dconds, ys, prefix_lens=prefix_lens,
                                                        pad_id=self.pad_id)
         return Scores(logp, tokens, hits, token_logp)
+
+    def policy_terms(self, zs, ys, src_mask, dconds=None, prefix_lens=None, prior=None) -> PolicyTerms:
+        """`logp` plus the terms of a regularised policy-gradient step, from the same ONE forward
+        (decode.sequence_policy): the entropy of the model's next-token distribution at every scored token and -- with
+        `prior`, a second model of the same architecture (Train/finetune.frozen_prior) -- KL(model || prior) there and
+        the prior's log-likelihood of the same tokens (one forward of the prior, no gradient).  The arguments of `logp`,
+        so `policy_terms(*rows, prior=p)` takes a DecodedRows; PolicyTerms on the device, with gradients."""
+        zs, src_mask = zs.to(self.device), src_mask.to(self.device)
+        dconds = None if dconds is None else dconds.to(self.device)
+        return sequence_policy(self.model, zs, src_mask, dconds, ys, prefix_lens=prefix_lens, pad_id=self.pad_id,
+                               prior=prior)
 
     @torch.no_grad()
     def score(self, zs, ys, src_mask, dconds=None, prefix_lens=None) -> Scores:

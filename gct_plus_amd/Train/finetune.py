@@ -6,9 +6,21 @@ not have.  `reinforce_loss` is the REINFORCE surrogate over differentiable seque
     reward = torch.tensor([score(s) for s in out[0]])           # any per-molecule number
     stats = reinforce_step(sampler, optimizer, out[-1], reward)
 
-Reward-weighted likelihood, hill-climbing on the best k of a batch and any other per-molecule loss are functions of
-`sampler.logp(*rows).logp` in the same way.  Not covered: FlatDataParallel fine-tuning, a prior-KL term (a
-caller composes it from decode.score_tokens on a second, frozen model), importance ratios, beam rows."""
+A reward alone collapses the policy onto the few strings that earn it.  The two standard remedies need the whole
+next-token distribution at every scored token, not logp: an entropy bonus on the policy and a KL penalty that ties it to
+a frozen copy of the pretrained model (decode.sequence_policy -> gct_seq_dist / gct_seq_dist_bwd, from the one forward
+logp takes):
+
+    prior = frozen_prior(sampler.model)                         # before the first update
+    stats = reinforce_step(sampler, optimizer, out[-1], reward, entropy_coef=0.05, kl_coef=0.5, prior=prior)
+
+`regularised_loss` is the loss of that step; REINVENT-style augmented likelihoods are functions of
+`sampler.policy_terms(*rows, prior=prior)`'s logp and prior_logp.  Reward-weighted likelihood, hill-climbing on the best
+k of a batch and any other per-molecule loss are functions of `sampler.logp(*rows).logp` in the same way.  Not covered
+(DESIGN 4): FlatDataParallel fine-tuning, importance ratios / PPO clipping, beam rows, per-step entropy during generate,
+a gradient into the prior."""
+import copy
+
 import torch
 
 
@@ -31,14 +43,52 @@ def reinforce_loss(logp, reward, baseline="mean"):
     return -((reward - b) * logp.view(-1)).sum() / logp.numel()
 
 
-def reinforce_step(sampler, optimizer, rows, reward, baseline="mean"):
+def frozen_prior(model):
+    """A frozen copy of `model` to regularise against (sequence_policy's `prior`): in eval() mode, every parameter with
+    requires_grad=False, sharing no storage with `model` (copy.deepcopy, which FlatModelMixin keeps sound: a flat
+    buffer, planes and hooks of its own), its state_dict equal to model's at the time of the call."""
+    prior = copy.deepcopy(model)
+    prior.eval()
+    for p in prior.parameters():
+        p.requires_grad_(False)
+    return prior
+
+
+def regularised_loss(terms, reward, baseline="mean", entropy_coef=0.0, kl_coef=0.0):
+    """reinforce_loss(terms.logp, reward, baseline) + (kl_coef * terms.kl.sum() - entropy_coef * terms.entropy.sum()) / n
+    over the n sequences of a PolicyTerms (decode.sequence_policy): the REINFORCE surrogate, minus an entropy bonus on
+    the policy's next-token distributions, plus a penalty on their KL divergence from the prior's -- both summed over
+    the scored tokens.  A coefficient of 0 leaves its term out (terms.kl may then be None); kl_coef != 0 needs terms
+    computed with a prior, entropy_coef != 0 terms with the entropy: ValueError otherwise."""
+    loss = reinforce_loss(terms.logp, reward, baseline)
+    n = terms.logp.numel()
+    if kl_coef != 0:
+        if terms.kl is None:
+            raise ValueError("regularised_loss: kl_coef needs terms computed with a prior")
+        loss = loss + kl_coef * terms.kl.sum() / n
+    if entropy_coef != 0:
+        if terms.entropy is None:
+            raise ValueError("regularised_loss: entropy_coef needs terms computed with the entropy")
+        loss = loss - entropy_coef * terms.entropy.sum() / n
+    return loss
+
+
+def reinforce_step(sampler, optimizer, rows, reward, baseline="mean", entropy_coef=0.0, kl_coef=0.0, prior=None):
     """One policy-gradient update of sampler.model on the decoded rows `rows` (a DecodedRows, or any argument tuple of
     Sampling.logp) with one reward per row: model.train(), sampler.logp(*rows), optimizer.zero_grad(set_to_none=True),
     reinforce_loss -> backward -> optimizer.step(), model.eval().  Returns dict(loss, mean_reward, mean_logp, tokens),
     Python numbers read in ONE transfer (tokens: the scored tokens of the batch).
 
+    entropy_coef / kl_coef / prior (a frozen_prior of the pretrained model): with a coefficient that is not 0, or a
+    prior, the step takes sampler.policy_terms(*rows, prior=prior) instead -- the same one forward of the model, one
+    more forward-only pass of the prior -- and minimises regularised_loss.  The result then also holds mean_entropy
+    and, with a prior, mean_kl (both per scored token: the batch sum / tokens) and mean_prior_logp (per sequence), read
+    in the same one transfer.  kl_coef != 0 without a prior: ValueError before any device work.  With the defaults the
+    step is the unregularised one, bit for bit.
+
     The model runs in training mode, so its dropout is live in this forward: the logp of the step is not the eval-mode
-    number `with_logp` reported for the same rows (build the model with dropout 0 where the two must agree).
+    number `with_logp` reported for the same rows (build the model with dropout 0 where the two must agree).  The prior
+    stays in the mode it is in: eval().
 
     What keeps the encoder still: the rows' latents are inputs, so the graph holds the decoder and model.out only and
     the encoder's parameters get NO gradient.  A FRESH optimizer therefore leaves them bit-unchanged (FusedAdam and
@@ -51,17 +101,31 @@ def reinforce_step(sampler, optimizer, rows, reward, baseline="mean"):
     It does NOT follow writes through `p.data` (KVDecoder.start): whoever updates the weights that way calls
     model.invalidate_weight_planes() before the next decode."""
     model = sampler.model
+    if kl_coef != 0 and prior is None:
+        raise ValueError("reinforce_step: kl_coef needs a prior (frozen_prior of the pretrained model)")
     reward = torch.as_tensor(reward, dtype=torch.float32)
+    plain = entropy_coef == 0 and kl_coef == 0 and prior is None
     model.train()
     try:
-        scores = sampler.logp(*rows)
+        scores = sampler.logp(*rows) if plain else sampler.policy_terms(*rows, prior=prior)
         optimizer.zero_grad(set_to_none=True)
-        loss = reinforce_loss(scores.logp, reward, baseline)
+        loss = (reinforce_loss(scores.logp, reward, baseline) if plain else
+                regularised_loss(scores, reward, baseline, entropy_coef, kl_coef))
         loss.backward()
         optimizer.step()
     finally:
         model.eval()
     dev = scores.logp.device
-    stats = torch.stack([loss.detach().float(), reward.to(dev).mean(), scores.logp.detach().mean(),
-                         scores.tokens.sum().float()]).cpu().tolist()
-    return dict(loss=stats[0], mean_reward=stats[1], mean_logp=stats[2], tokens=int(stats[3]))
+    tokens = scores.tokens.sum().float()
+    stats = [loss.detach().float(), reward.to(dev).mean(), scores.logp.detach().mean(), tokens]
+    if not plain:
+        stats.append(scores.entropy.detach().sum() / tokens)
+        if prior is not None:
+            stats += [scores.kl.detach().sum() / tokens, scores.prior_logp.mean()]
+    stats = torch.stack(stats).cpu().tolist()
+    out = dict(loss=stats[0], mean_reward=stats[1], mean_logp=stats[2], tokens=int(stats[3]))
+    if not plain:
+        out["mean_entropy"] = stats[4]
+        if prior is not None:
+            out["mean_kl"], out["mean_prior_logp"] = stats[5], stats[6]
+    return out

@@ -7,6 +7,9 @@
 // same wave-per-row log-softmax; every output has one writer and a fixed summation order (no atomics).
 // gct_seq_logp_bwd (decode.py seq_logp_grad_reference states the rule) is gct_seq_logp's gradient with respect to the
 // logits: ce_grad_row, the row arithmetic of gct_ce_bwd, with a weight per token column instead of one scalar.
+// gct_seq_dist / gct_seq_dist_bwd (decode.py dist_reference / dist_grad_reference state the rules) are the entropy of
+// the next-token distribution and its KL divergence from a second model's, per scored token and per sequence, and their
+// gradient with respect to the first model's logits: the same layouts, around wave_row_dist.
 #include "common.h"
 #include "decode_rows.h"
 
@@ -163,6 +166,142 @@ __global__ __launch_bounds__(256) void seq_logp_bwd_kernel(const float* __restri
   }
 }
 
+// One wave, one logits row lr[0, V) and -- pr non-null -- the prior's row pr[0, V); every lane gets the results.
+//   m = max x, lse = log(sum exp(x - m));  H = lse - sum e_v (x_v - m) / se  with e_v = exp(x_v - m), se = sum e_v;
+//   KL = sum (e_v / se) ((x_v - m - lse) - (y_v - m' - lse'))  (the primed ones: the same of the prior's row).
+// wave_token_logp's numerics: one max pass, one expf pass with a lane-strided V loop, wave sums, logf.  A lane skips
+// its term where e_v == 0 (a -inf logit: p_v log p_v -> 0), so p_v > 0 against q_v == 0 is the only way to +inf.
+struct RowDist {
+  float m, lse, inv, pm, plse, H, KL;
+};
+__device__ __forceinline__ RowDist wave_row_dist(const float* __restrict__ lr, const float* __restrict__ pr, int V,
+                                                 int lane) {
+  RowDist d;
+  float mx = -INFINITY;
+  for (int c = lane; c < V; c += 64) mx = fmaxf(mx, lr[c]);
+  d.m = gct_wave_max(mx);
+  float se = 0.f, sx = 0.f;
+  for (int c = lane; c < V; c += 64) {
+    const float y = lr[c] - d.m, e = expf(y);
+    se += e;
+    if (e != 0.f) sx += e * y;
+  }
+  se = gct_wave_sum(se);
+  sx = gct_wave_sum(sx);
+  d.lse = logf(se);
+  d.inv = 1.0f / se;
+  d.H = d.lse - sx / se;
+  d.pm = d.plse = d.KL = 0.f;
+  if (pr) {                                             // uniform over the wave
+    gct_wave_softmax_stats(pr, V, lane, d.pm, se);
+    d.plse = logf(se);
+    float kl = 0.f;
+    for (int c = lane; c < V; c += 64) {
+      const float y = lr[c] - d.m, e = expf(y);
+      if (e != 0.f) kl += (e * d.inv) * ((y - d.lse) - ((pr[c] - d.pm) - d.plse));
+    }
+    d.KL = gct_wave_sum(kl);
+  }
+  return d;
+}
+
+// seq_logp_kernel's layout: one workgroup per sequence, wave w takes the token columns w, w + 4, ...; each column's
+// entropy and KL go to LDS and thread 0 adds them up in ascending column order.  Neither model's logits row is read
+// at a column that is not scored.
+__global__ __launch_bounds__(256) void seq_dist_kernel(const float* __restrict__ logits, int64_t ld, int V,
+                                                       int64_t rows_per_seq, int row_shift,
+                                                       const float* __restrict__ prior, int64_t ld_prior,
+                                                       const int64_t* __restrict__ ys, int64_t ld_ys,
+                                                       const int32_t* __restrict__ prefix_lens, int64_t pad_id, int W,
+                                                       float* __restrict__ token_entropy, int64_t ld_out,
+                                                       float* __restrict__ entropy, float* __restrict__ token_kl,
+                                                       float* __restrict__ kl) {
+  __shared__ float sh_h[SEQ_LOGP_MAX_W];
+  __shared__ float sh_kl[SEQ_LOGP_MAX_W];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t r = blockIdx.x;
+  const int t0 = prefix_lens ? prefix_lens[r] : 1;
+  const int64_t* yr = ys + r * ld_ys;
+  for (int c = wave; c < W; c += 4) {                   // uniform over the wave
+    const int64_t tok = yr[c];
+    const bool scored = c >= t0 && c >= 1 && tok != pad_id && tok >= 0 && tok < V;
+    float h = 0.f, k = 0.f;
+    if (scored) {
+      const int64_t row = r * rows_per_seq + row_shift + c - 1;
+      const RowDist d = wave_row_dist(logits + row * ld, prior ? prior + row * ld_prior : nullptr, V, lane);
+      h = d.H;
+      k = d.KL;
+    }
+    if (lane == 0) {
+      token_entropy[r * ld_out + c] = h;
+      sh_h[c] = h;
+      if (prior) {
+        token_kl[r * ld_out + c] = k;
+        sh_kl[c] = k;
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float sh = 0.f, sk = 0.f;
+    for (int c = 0; c < W; ++c) sh += sh_h[c];          // a column that is not scored holds 0
+    entropy[r] = sh;
+    if (prior) {
+      for (int c = 0; c < W; ++c) sk += sh_kl[c];
+      kl[r] = sk;
+    }
+  }
+}
+
+// seq_logp_bwd_kernel's layout: one wave per logits row (r, j), four rows per workgroup, the grid strides over the
+// rest.  With a = g_entropy[r] + g_token_entropy[r][c] and b = g_kl[r] + g_token_kl[r][c] (a null table: 0) a scored
+// row gets  a * (-p_v (log p_v + H)) + b * (p_v ((log p_v - log q_v) - KL)),  exact zeros where p_v == 0.  A row that
+// is not scored, or whose a and b are both 0, gets V exact zeros and neither its logits nor the prior's are read.
+// Everything a branch depends on is one value per wave.
+__global__ __launch_bounds__(256) void seq_dist_bwd_kernel(const float* __restrict__ logits, int64_t ld, int V,
+                                                           int64_t rows_per_seq, int row_shift,
+                                                           const float* __restrict__ prior, int64_t ld_prior,
+                                                           const int64_t* __restrict__ ys, int64_t ld_ys,
+                                                           const int32_t* __restrict__ prefix_lens, int64_t pad_id,
+                                                           int W, const float* __restrict__ g_entropy,
+                                                           const float* __restrict__ g_token_entropy, int64_t ld_ge,
+                                                           const float* __restrict__ g_kl,
+                                                           const float* __restrict__ g_token_kl, int64_t ld_gk,
+                                                           float* __restrict__ dlogits, int64_t ld_d, int64_t rows) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
+    const int64_t r = row / rows_per_seq, j = row - r * rows_per_seq;
+    const int64_t c = j - row_shift + 1;
+    float* dr = dlogits + row * ld_d;
+    float a = 0.f, b = 0.f;
+    if (j >= row_shift && c >= 1 && c < W) {
+      const int t0 = prefix_lens ? prefix_lens[r] : 1;
+      const int64_t tok = ys[r * ld_ys + c];
+      if (c >= t0 && tok != pad_id && tok >= 0 && tok < V) {
+        a = (g_entropy ? g_entropy[r] : 0.f) + (g_token_entropy ? g_token_entropy[r * ld_ge + c] : 0.f);
+        b = (g_kl ? g_kl[r] : 0.f) + (g_token_kl ? g_token_kl[r * ld_gk + c] : 0.f);
+      }
+    }
+    if (a == 0.f && b == 0.f) {                         // not scored, or zero weights
+      for (int v = lane; v < V; v += 64) dr[v] = 0.f;
+      continue;
+    }
+    const float* lr = logits + row * ld;
+    const float* pr = b != 0.f ? prior + row * ld_prior : nullptr;   // b != 0 only with a prior (checked by the host)
+    const RowDist d = wave_row_dist(lr, pr, V, lane);
+    for (int v = lane; v < V; v += 64) {
+      const float y = lr[v] - d.m, e = expf(y);
+      float g = 0.f;
+      if (e != 0.f) {
+        const float p = e * d.inv, lp = y - d.lse;
+        g = a * (-p * (lp + d.H));
+        if (pr) g += b * (p * ((lp - ((pr[v] - d.pm) - d.plse)) - d.KL));
+      }
+      dr[v] = g;
+    }
+  }
+}
+
 // one wave per decode row, as select_token_kernel: the column the selection has just written (gct_row_slot)
 __global__ __launch_bounds__(256) void chosen_logp_kernel(const float* __restrict__ logits, int V,
                                                           const int64_t* __restrict__ ys, int64_t ld_ys,
@@ -252,6 +391,58 @@ extern "C" int gct_seq_logp_bwd(const float* logits, int64_t ld, int V, int64_t 
                      rows_per_seq, row_shift, ys, ld_ys, prefix_lens, pad_id, W, g_logp, g_token, ld_g, dlogits, ld_d,
                      rows);
   GCT_LAUNCH_CHECK("seq_logp_bwd");
+  return GCT_OK;
+}
+
+extern "C" int gct_seq_dist(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift,
+                            const float* prior_logits, int64_t ld_prior, const int64_t* ys, int64_t ld_ys,
+                            const int32_t* prefix_lens, int64_t pad_id, int n, int W, float* token_entropy,
+                            int64_t ld_out, float* entropy, float* token_kl, float* kl, void* stream) {
+  GCT_CHECK_ARG(logits && ys && token_entropy && entropy, "seq_dist: null pointer");
+  GCT_CHECK_ARG(prior_logits || (!token_kl && !kl), "seq_dist: kl outputs without prior logits");
+  GCT_CHECK_ARG(!prior_logits || (token_kl && kl), "seq_dist: prior logits without kl outputs (null pointer)");
+  GCT_CHECK_ARG(n >= 0 && V > 0 && ld >= V && (!prior_logits || ld_prior >= V),
+                "seq_dist: bad shape (n %d, V %d, ld %lld, ld_prior %lld)", n, V, (long long)ld, (long long)ld_prior);
+  GCT_CHECK_ARG(W >= 1 && W <= SEQ_LOGP_MAX_W, "seq_dist: rows of %d tokens (1 .. %d supported)", W, SEQ_LOGP_MAX_W);
+  GCT_CHECK_ARG(ld_ys >= W && ld_out >= W, "seq_dist: ld_ys / ld_out narrower than the %d token columns", W);
+  GCT_CHECK_ARG(row_shift >= 0 && rows_per_seq >= (int64_t)row_shift + W - 1,
+                "seq_dist: %lld logits rows per sequence do not hold %d + %d", (long long)rows_per_seq, row_shift,
+                W - 1);
+  if (n == 0) return GCT_OK;
+  hipLaunchKernelGGL(seq_dist_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, logits, ld, V, rows_per_seq,
+                     row_shift, prior_logits, ld_prior, ys, ld_ys, prefix_lens, pad_id, W, token_entropy, ld_out,
+                     entropy, token_kl, kl);
+  GCT_LAUNCH_CHECK("seq_dist");
+  return GCT_OK;
+}
+
+extern "C" int gct_seq_dist_bwd(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift,
+                                const float* prior_logits, int64_t ld_prior, const int64_t* ys, int64_t ld_ys,
+                                const int32_t* prefix_lens, int64_t pad_id, int n, int W, const float* g_entropy,
+                                const float* g_token_entropy, int64_t ld_ge, const float* g_kl,
+                                const float* g_token_kl, int64_t ld_gk, float* dlogits, int64_t ld_d, void* stream) {
+  GCT_CHECK_ARG(logits && ys && dlogits, "seq_dist_bwd: null pointer");
+  GCT_CHECK_ARG(g_entropy || g_token_entropy || g_kl || g_token_kl,
+                "seq_dist_bwd: all four gradients are null (g_entropy, g_token_entropy, g_kl, g_token_kl)");
+  GCT_CHECK_ARG(prior_logits || (!g_kl && !g_token_kl), "seq_dist_bwd: kl gradients without prior logits");
+  GCT_CHECK_ARG(n >= 0 && V > 0 && ld >= V && ld_d >= V && (!prior_logits || ld_prior >= V),
+                "seq_dist_bwd: bad shape (n %d, V %d, ld %lld, ld_prior %lld, ld_d %lld)", n, V, (long long)ld,
+                (long long)ld_prior, (long long)ld_d);
+  GCT_CHECK_ARG(W >= 1 && W <= SEQ_LOGP_MAX_W, "seq_dist_bwd: rows of %d tokens (1 .. %d supported)", W,
+                SEQ_LOGP_MAX_W);
+  GCT_CHECK_ARG(ld_ys >= W && (!g_token_entropy || ld_ge >= W) && (!g_token_kl || ld_gk >= W),
+                "seq_dist_bwd: ld_ys / ld_ge / ld_gk narrower than the %d token columns", W);
+  GCT_CHECK_ARG(row_shift >= 0 && rows_per_seq >= (int64_t)row_shift + W - 1,
+                "seq_dist_bwd: %lld logits rows per sequence do not hold %d + %d", (long long)rows_per_seq, row_shift,
+                W - 1);
+  const int64_t rows = (int64_t)n * rows_per_seq;
+  if (rows == 0) return GCT_OK;
+  int64_t g = (rows + 3) / 4;
+  g = g > 4096 ? 4096 : g;
+  hipLaunchKernelGGL(seq_dist_bwd_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, logits, ld, V,
+                     rows_per_seq, row_shift, prior_logits, ld_prior, ys, ld_ys, prefix_lens, pad_id, W, g_entropy,
+                     g_token_entropy, ld_ge, g_kl, g_token_kl, ld_gk, dlogits, ld_d, rows);
+  GCT_LAUNCH_CHECK("seq_dist_bwd");
   return GCT_OK;
 }
 

@@ -52,6 +52,9 @@ one decoder forward over the rows up to each sequence's last scored token, then 
 reads the step's logits right behind the selection, so a sampling run needs no second forward to know its likelihood.
 `sequence_logp` is score_tokens with a gradient (the backward rule is stated once, in `seq_logp_grad_reference`;
 gct_seq_logp_bwd through engine.SeqLogpFn): the per-molecule policy term of a fine-tuning step (Train/finetune.py).
+`sequence_policy` adds, from the same one forward, the terms that need the whole next-token distribution: the policy's
+entropy and its KL divergence from a frozen prior at every scored token (the rules: `dist_reference` /
+`dist_grad_reference`; gct_seq_dist / gct_seq_dist_bwd through engine.SeqDistFn).
 
 Grammar-constrained decoding (`generate` / `generate_stream(grammar=SmilesGrammar(...))`): the rules are stated once, in
 `SmilesGrammar` (grammar_step, grammar_min_finish).  gct_grammar_mask runs in front of the selection: one wave per row
@@ -68,7 +71,7 @@ import heapq
 import math
 import numbers
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -497,6 +500,115 @@ def seq_logp_grad_reference(logits, ys, prefix_lens, pad_id, g_logp=None, g_toke
     return torch.where(live.unsqueeze(-1), g[:, 1:].unsqueeze(-1) * grad, torch.zeros((), dtype=x.dtype, device=dev))
 
 
+def _dist_rows(logits, prior_logits, ys, prefix_lens):
+    """Shared front of dist_reference / dist_grad_reference: (x, y or None, n, W, prefix lengths on the CPU)."""
+    ys = torch.as_tensor(ys)
+    lens = check_score_inputs(ys, prefix_lens, logits.shape[-1])
+    n, W = ys.shape
+    x = logits if logits.dtype == torch.float64 else logits.float()
+    if tuple(x.shape[:2]) != (n, W - 1):
+        raise ValueError(f"logits must be [{n}, {W - 1}, V], got {list(logits.shape)}")
+    y = None
+    if prior_logits is not None:
+        if prior_logits.shape != logits.shape:
+            raise ValueError(f"prior_logits must have the shape of logits {list(logits.shape)}, got "
+                             f"{list(prior_logits.shape)}")
+        y = prior_logits.to(x.device, x.dtype)
+    return ys, x, y, n, W, lens
+
+
+def _log_softmax_rows(x, live):
+    """log-softmax, in log-sum-exp form, of the rows marked in live [n, W - 1]; a row that is not marked is replaced by
+    zeros BEFORE any arithmetic, so nothing it holds (NaN included) reaches a value or a gradient."""
+    x = torch.where(live.unsqueeze(-1), x, torch.zeros((), dtype=x.dtype, device=x.device))
+    s = x - x.max(-1, keepdim=True).values
+    return s - torch.log(torch.exp(s).sum(-1, keepdim=True))
+
+
+def _p_logp(x, live):
+    """(p, log p) of the marked rows; where p == 0 (a -inf logit) log p is replaced by 0, so that p * log p is exactly
+    0 there, also under autograd."""
+    logp = _log_softmax_rows(x, live)
+    p = torch.exp(logp)
+    return p, torch.where(p > 0, logp, torch.zeros((), dtype=x.dtype, device=x.device))
+
+
+def dist_reference(logits, ys, prefix_lens, pad_id, prior_logits=None):
+    """THE statement of the distribution terms of a policy (gct_seq_dist implements it): the entropy of the next-token
+    distribution and its KL divergence from a second model's (the "prior"), at score_reference's geometry and under its
+    SCORED predicate (ys [n, W] full token rows, logits [n, W - 1, V], row c - 1 predicts token c, column c of row r is
+    scored when c >= t0_r and ys[r, c] != pad_id).  prior_logits: None, or the prior's logits in the shape of logits.
+    At a scored column, with p = softmax(logits[r, c - 1]) and q = softmax(prior_logits[r, c - 1]), both in log-sum-exp
+    form (log p_v = x_v - m - log sum exp(x - m), m the row maximum):
+      token_entropy [n, W]  -sum_v p_v log p_v
+      token_kl [n, W]       sum_v p_v (log p_v - log q_v)        = KL(agent || prior)
+    A term with p_v == 0 (a -inf logit) contributes exactly 0; p_v > 0 where q_v == 0 gives +inf (the prior forbids a
+    token the agent still draws).  Columns that are not scored hold 0 -- whatever their logits rows hold, NaN included:
+    such a row is never looked at.
+      entropy [n], kl [n]   the sums of a row's scored columns in ascending column order; 0 for a row with none.
+    Returns (token_entropy, entropy, token_kl, kl), the last two None without prior_logits, in the dtype of logits (fp32
+    at least) on the device of logits."""
+    ys, x, y, n, W, lens = _dist_rows(logits, prior_logits, ys, prefix_lens)
+    dev = x.device
+    tgt = ys[:, 1:].long().to(dev)
+    scored = (torch.arange(1, W).view(1, -1) >= lens.view(-1, 1)).to(dev) & (tgt != pad_id)
+    zero = torch.zeros((), dtype=x.dtype, device=dev)
+    p, logp = _p_logp(x, scored)
+    first = torch.zeros(n, 1, dtype=x.dtype, device=dev)
+
+    def columns(per_row):                                # [n, W - 1] -> token table [n, W] and its row sums
+        table = torch.cat([first, torch.where(scored, per_row, zero)], dim=1)
+        total = torch.zeros(n, dtype=x.dtype, device=dev)
+        for c in range(1, W):                            # ascending column order
+            total = total + table[:, c]
+        return table, total
+    token_entropy, entropy = columns(-(p * logp).sum(-1))
+    if y is None:
+        return token_entropy, entropy, None, None
+    logq = torch.where(p > 0, _log_softmax_rows(y, scored), zero)   # q_v plays no part where p_v == 0
+    token_kl, kl = columns((p * (logp - logq)).sum(-1))
+    return token_entropy, entropy, token_kl, kl
+
+
+def dist_grad_reference(logits, ys, prefix_lens, pad_id, prior_logits=None, g_entropy=None, g_token_entropy=None,
+                        g_kl=None, g_token_kl=None):
+    """THE statement of the backward rule of dist_reference (gct_seq_dist_bwd implements it): the gradient with respect
+    to the AGENT's logits [n, W - 1, V] of  sum_r g_entropy[r] * entropy[r] + sum_{r, c} g_token_entropy[r, c] *
+    token_entropy[r, c] + sum_r g_kl[r] * kl[r] + sum_{r, c} g_token_kl[r, c] * token_kl[r, c]  (tables [n] and [n, W];
+    None: 0; the kl pair needs prior_logits).  The prior gets no gradient.  With a = g_entropy[r] + g_token_entropy[r, c]
+    and b = g_kl[r] + g_token_kl[r, c], and H, KL the column's token_entropy and token_kl, row c - 1 of sequence r gets
+      a * (-p_v (log p_v + H)) + b * (p_v ((log p_v - log q_v) - KL))   where column c is scored,
+      exact zeros                                                      where it is not, or where a == 0 and b == 0 --
+    whatever the agent's and the prior's logits rows hold, NaN included: such rows are never looked at.  Entries with
+    p_v == 0 get exact zeros.  Closed form, in the dtype of logits (fp32 at least), on the device of logits."""
+    if prior_logits is None and (g_kl is not None or g_token_kl is not None):
+        raise ValueError("dist_grad_reference: g_kl / g_token_kl need prior_logits")
+    ys, x, y, n, W, lens = _dist_rows(logits, prior_logits, ys, prefix_lens)
+    dev = x.device
+    tgt = ys[:, 1:].long().to(dev)
+    scored = (torch.arange(1, W).view(1, -1) >= lens.view(-1, 1)).to(dev) & (tgt != pad_id)
+    zero = torch.zeros((), dtype=x.dtype, device=dev)
+
+    def weight(g_row, g_tab):
+        g = torch.zeros(n, W, dtype=x.dtype, device=dev)
+        if g_row is not None:
+            g = g + torch.as_tensor(g_row).to(dev, x.dtype).view(n, 1)
+        if g_tab is not None:
+            g = g + torch.as_tensor(g_tab).to(dev, x.dtype).view(n, W)
+        return g[:, 1:]
+    a, b = weight(g_entropy, g_token_entropy), weight(g_kl, g_token_kl)
+    live = scored & ((a != 0) | (b != 0))
+    p, logp = _p_logp(x, live)
+    H = -(p * logp).sum(-1, keepdim=True)
+    grad = a.unsqueeze(-1) * (-p * (logp + H))
+    if y is not None:
+        logq = torch.where(p > 0, _log_softmax_rows(y, live & (b != 0)), zero)
+        d = logp - logq
+        KL = (p * d).sum(-1, keepdim=True)
+        grad = grad + torch.where((b != 0).unsqueeze(-1), b.unsqueeze(-1) * (p * (d - KL)), zero)
+    return torch.where(live.unsqueeze(-1) & (p > 0), grad, zero)
+
+
 def _score_geometry(model, ys, prefix_lens):
     """What every teacher-forced scoring call validates before any device work: (ys as a tensor, prefix lengths int64
     [n] on the CPU, use_cond2dec, row_shift = the condition rows in front of a sequence's logits, V).  ValueError for
@@ -602,6 +714,75 @@ def sequence_logp(model, z, src_mask, dconds, ys, prefix_lens=None, pad_id=1):
     logp, token_logp, tokens, hits = engine.SeqLogpFn.apply(
         logits2d, y, None if prefix_lens is None else t0.to(torch.int32), pad_id, off)
     return logp, tokens, hits, token_logp
+
+
+class PolicyTerms(NamedTuple):
+    """What sequence_policy returns, on the device: sequence_logp's four (logp [n], tokens [n] int32, hits [n] int32,
+    token_logp [n, W]); entropy [n] / token_entropy [n, W] of the agent's next-token distributions at the scored columns
+    (None with entropy=False); and with a prior kl [n] / token_kl [n, W] = KL(agent || prior) there and prior_logp [n],
+    the prior's log-likelihood of the same tokens (None without one).  logp, token_logp, entropy, token_entropy, kl and
+    token_kl carry the agent's graph; prior_logp carries none.  dist_reference states the rule of the new terms."""
+    logp: torch.Tensor
+    tokens: torch.Tensor
+    hits: torch.Tensor
+    token_logp: torch.Tensor
+    entropy: Optional[torch.Tensor]
+    token_entropy: Optional[torch.Tensor]
+    kl: Optional[torch.Tensor]
+    token_kl: Optional[torch.Tensor]
+    prior_logp: Optional[torch.Tensor]
+
+
+def _check_prior(model, prior):
+    """A prior scores the agent's rows with the agent's geometry: the same vocabulary, condition count and
+    use_cond2dec.  ValueError otherwise."""
+    for what, a, b in (("vocabulary", model.out.weight.shape[0], prior.out.weight.shape[0]),
+                       ("nconds", model.decoder.nconds, prior.decoder.nconds),
+                       ("use_cond2dec", bool(model.decoder.use_cond2dec), bool(prior.decoder.use_cond2dec))):
+        if a != b:
+            raise ValueError(f"sequence_policy: the prior's {what} ({b}) is not the model's ({a})")
+
+
+def sequence_policy(model, z, src_mask, dconds, ys, prefix_lens=None, pad_id=1, prior=None, entropy=True):
+    """sequence_logp plus the terms that need the whole next-token distribution, from ONE agent forward: the entropy of
+    the policy at every scored token and -- with `prior`, a second model of the same architecture (finetune.frozen_prior)
+    -- KL(agent || prior) there and the prior's log-likelihood of the same tokens.  Returns a PolicyTerms; logp, tokens,
+    hits and token_logp are sequence_logp's bit for bit (same inputs, same train / eval mode).
+    The prior runs ONE forward under torch.no_grad(), in whatever mode it is in (the caller keeps it in eval()), with the
+    agent's loss_rows, so the rows it skips are the agent's; prior_logp is gct_seq_logp on its logits.  entropy=False
+    without a prior launches nothing beyond sequence_logp.  The backward of the new terms is gct_seq_dist_bwd through
+    engine.SeqDistFn: exact zeros on every logits row that is not scored, as SeqLogpFn's, and autograd adds the two.
+    ValueError before any device work for what sequence_logp refuses and for a prior whose vocabulary, nconds or
+    use_cond2dec differ from the model's."""
+    ys, lens, c2d, off, V = _score_geometry(model, ys, prefix_lens)
+    if prior is not None:
+        _check_prior(model, prior)
+    n, W = ys.shape
+    host = ys.detach().cpu()
+    if not bool(((torch.arange(W).view(1, -1) >= lens.view(-1, 1)) & (host != pad_id))[:, 1:].any()):
+        raise ValueError("sequence_policy: no column of the batch is scored (every row is prefix or pad)")
+    dev = z.device
+    y = ys.to(dev, torch.int64).contiguous()
+    t0 = lens.to(dev)
+    dc = None if dconds is None else dconds.to(dev)
+    sm = None if src_mask is None else src_mask.to(dev)
+    t0_dev = None if prefix_lens is None else t0.to(torch.int32)
+    logits2d, rows = _scoring_logits(model, z, sm, dc, y, t0, pad_id, c2d)
+    logp, token_logp, tokens, hits = engine.SeqLogpFn.apply(logits2d, y, t0_dev, pad_id, off)
+    prior2d = prior_logp = None
+    if prior is not None:
+        with torch.no_grad():
+            prior2d, prior_rows = _scoring_logits(prior, z.detach(), sm, dc, y, t0, pad_id, c2d)
+            if prior_rows != rows:
+                raise ValueError(f"sequence_policy: the prior gives {prior_rows} logits rows per sequence, the model "
+                                 f"{rows}")
+            prior_logp = ops.seq_logp(prior2d, y, t0_dev, pad_id, row_shift=off, rows_per_seq=rows)[1]
+    ent = tent = kl = tkl = None
+    if entropy or prior is not None:
+        ent, tent, kl, tkl = engine.SeqDistFn.apply(logits2d, prior2d, y, t0_dev, pad_id, off)
+        if not entropy:
+            ent = tent = None
+    return PolicyTerms(logp, tokens, hits, token_logp, ent, tent, kl, tkl, prior_logp)
 
 
 # ------------------------------------------------------------------------------------- continuous batching

@@ -963,6 +963,51 @@ class SeqLogpFn(torch.autograd.Function):
         return dl.view(shape), None, None, None, None
 
 
+class SeqDistFn(torch.autograd.Function):
+    """Entropy of the next-token distribution and its KL divergence from a frozen prior's, with a gradient into the
+    agent's logits (decode.dist_reference / dist_grad_reference state the rules):
+    apply(logits, prior_logits, ys, prefix_lens, pad_id, row_shift) -> (entropy [n], token_entropy [n, W], kl [n],
+    token_kl [n, W]); kl / token_kl are None when prior_logits is.  logits, ys, prefix_lens as SeqLogpFn takes them;
+    prior_logits fp32 in the shape of logits (or [n * R, V]): no gradient flows into it.  The backward is
+    gct_seq_dist_bwd: it writes every row of dlogits, exact zeros where nothing is scored or the weights are 0, and
+    autograd adds it to SeqLogpFn's on the same logits."""
+
+    @staticmethod
+    def forward(ctx, logits, prior_logits, ys, prefix_lens, pad_id, row_shift):
+        n, V = ys.shape[0], logits.shape[-1]
+
+        def rows2d(t, what):
+            if t.dim() == 3:
+                if t.shape[0] != n:
+                    raise ValueError(f"SeqDistFn: {t.shape[0]} {what} blocks for {n} token rows")
+                return _f32c(t).view(-1, V)
+            if t.dim() == 2 and t.dtype == torch.float32 and t.stride(1) == 1:
+                return t
+            return _f32c(t).reshape(-1, V)
+        l2 = rows2d(logits, "logits")
+        q2 = None if prior_logits is None else rows2d(prior_logits.detach(), "prior logits")
+        R = l2.shape[0] // n if n else ys.shape[1] - 1 + int(row_shift)
+        ys = ys.contiguous()
+        te, en, tk, kl = ops.seq_dist(l2, ys, prefix_lens, int(pad_id), row_shift=int(row_shift), rows_per_seq=R,
+                                      prior_logits2d=q2)
+        ctx.save_for_backward(l2, q2, ys, prefix_lens)
+        ctx.geom = (int(pad_id), int(row_shift), R, logits.shape)
+        ctx.set_materialize_grads(False)                 # an output nobody used arrives as None, not as zeros
+        return en, te, kl, tk
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_entropy, g_token_entropy, g_kl, g_token_kl):
+        l2, q2, ys, prefix_lens = ctx.saved_tensors
+        pad_id, row_shift, R, shape = ctx.geom
+        gs = [None if g is None else _f32c(g) for g in (g_entropy, g_token_entropy, g_kl, g_token_kl)]
+        if all(g is None for g in gs):
+            return torch.zeros(shape, device=l2.device), None, None, None, None, None
+        dl = ops.seq_dist_bwd(l2, ys, prefix_lens, pad_id, row_shift=row_shift, rows_per_seq=R, prior_logits2d=q2,
+                              g_entropy=gs[0], g_token_entropy=gs[1], g_kl=gs[2], g_token_kl=gs[3])
+        return dl.view(shape), None, None, None, None, None
+
+
 class KldFn(torch.autograd.Function):
     """Train/trainer1.py:23."""
 

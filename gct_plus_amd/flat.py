@@ -9,6 +9,7 @@ lets the wgrad kernels write gradients in place (engine.GradSink).
 """
 from __future__ import annotations
 
+import copy
 import functools
 from typing import List
 
@@ -48,6 +49,27 @@ class FlatModelMixin:
                 if hasattr(p, "_gct_gview"):
                     del p._gct_gview
         return out
+
+    def __deepcopy__(self, memo):
+        """copy.deepcopy(model): a second model with buffers of its own.  The default would not survive this class --
+        nn.Parameter's deepcopy clones each parameter out of the flat buffer and drops its gradient view, the copied
+        `_gct_flat` would be a buffer no parameter lives in, and the children's copied plane hooks would still close over
+        the ORIGINAL model.  So: everything but the flat state is copied, the original's hooks are taken off the copy's
+        children, and a copy on the device is flattened again (its own buffers, its own hooks; ops._PLANES is keyed by
+        address range, so the planes of two live models do not meet).  Gradients are not copied."""
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            if k not in ("_gct_flat", "_gct_plane_hooks"):
+                new.__dict__[k] = copy.deepcopy(v, memo)
+        for c in new.children():
+            for key, hook in list(c._forward_pre_hooks.items()):
+                if getattr(hook, "_gct_plane_hook", False):
+                    del c._forward_pre_hooks[key]
+        first = next(new.parameters(), None)
+        if first is not None and first.is_cuda:
+            new.flatten_parameters()
+        return new
 
     def flatten_parameters(self):
         params: List[nn.Parameter] = list(self.parameters())
@@ -136,6 +158,7 @@ class FlatModelMixin:
             if self._gct_depth == 0:
                 self.refresh_weight_planes()
 
+        child_pre._gct_plane_hook = True                # what __deepcopy__ takes off a copy's children
         for c in self.children():
             c.register_forward_pre_hook(child_pre)
 

@@ -1079,6 +1079,100 @@ def seq_logp_bwd(logits2d, ys, prefix_lens=None, pad_id=1, row_shift=0, rows_per
     return out
 
 
+def _seq_geometry(name, logits2d, ys, rows_per_seq, V, prefix_lens, prior2d=None):
+    """The checks seq_logp makes on (ys, logits, prefix_lens), for seq_dist / seq_dist_bwd, with the prior's logits next
+    to the agent's: (n, W, R, V, ld, ld_prior)."""
+    _chk(ys, f"{name}.ys", torch.int64)
+    if ys.dim() != 2 or ys.stride(1) != 1:
+        raise ValueError(f"{name}: ys must be [n, W] with unit column stride")
+    n, W = ys.shape
+    R = W - 1 if rows_per_seq is None else int(rows_per_seq)
+    ld = ld_prior = 0
+    if logits2d is not None:
+        _chk(logits2d, f"{name}.logits")
+        if logits2d.dim() != 2 or logits2d.stride(1) != 1 or logits2d.shape[0] < n * R:
+            raise ValueError(f"{name}: logits must be [>= {n * R}, V] with unit column stride, got "
+                             f"{list(logits2d.shape)}")
+        V, ld = logits2d.shape[1], logits2d.stride(0)
+    if prior2d is not None:
+        _chk(prior2d, f"{name}.prior_logits")
+        if prior2d.dim() != 2 or prior2d.stride(1) != 1 or prior2d.shape[0] < n * R or prior2d.shape[1] != int(V):
+            raise ValueError(f"{name}: prior logits must be [>= {n * R}, {int(V)}] with unit column stride, got "
+                             f"{list(prior2d.shape)}")
+        ld_prior = prior2d.stride(0)
+    if prefix_lens is not None:
+        _check_row_off(prefix_lens, n)
+    return n, W, R, int(V), ld, ld_prior
+
+
+def seq_dist(logits2d, ys, prefix_lens=None, pad_id=1, row_shift=0, rows_per_seq=None, prior_logits2d=None, V=None,
+             out=None):
+    """gct_seq_dist (decode.dist_reference states the rule): the entropy of the next-token distribution and -- with
+    prior_logits2d, a second model's logits in the same row numbering (its own row stride) -- its KL divergence from
+    that model's, for the geometry seq_logp takes (same checks on ys, logits2d, prefix_lens; logits2d None with V given
+    passes a null pointer: the library refuses).
+    Returns (token_entropy [n, W], entropy [n], token_kl [n, W] | None, kl [n] | None) fp32, or fills `out`, a tuple of
+    them (the kl pair None exactly when there is no prior; otherwise the library refuses)."""
+    n, W, R, V, ld, ld_prior = _seq_geometry("seq_dist", logits2d, ys, rows_per_seq, V, prefix_lens, prior_logits2d)
+    dev = ys.device
+    if out is None:
+        out = (torch.empty(n, W, device=dev), torch.empty(n, device=dev))
+        out += (None, None) if prior_logits2d is None else (torch.empty(n, W, device=dev), torch.empty(n, device=dev))
+    te, en, tk, kl = out
+    if (tk is None) != (kl is None):
+        raise ValueError("seq_dist: out needs both token_kl and kl, or neither")
+    for tab, vec, what in ((te, en, "entropy"), (tk, kl, "kl"))[:1 if tk is None else 2]:
+        _chk(tab, f"seq_dist.token_{what}"), _chk(vec, f"seq_dist.{what}")
+        if tab.shape != (n, W) or tab.stride(1) != 1 or vec.numel() != n or not vec.is_contiguous():
+            raise ValueError(f"seq_dist: out must hold token_{what} [n, W] and {what} [n]")
+    if tk is not None and tk.stride(0) != te.stride(0):
+        raise ValueError("seq_dist: token_entropy and token_kl must have one row stride")
+    if n == 0:
+        return out                                       # no sequence: nothing to write (an empty tensor has no address)
+    check(_L().gct_seq_dist(_p(logits2d), ld, V, R, int(row_shift), _p(prior_logits2d), ld_prior, _p(ys), ys.stride(0),
+                            _p(prefix_lens), int(pad_id), n, W, _p(te), te.stride(0), _p(en), _p(tk), _p(kl), _st()),
+          "gct_seq_dist")
+    return out
+
+
+def seq_dist_bwd(logits2d, ys, prefix_lens=None, pad_id=1, row_shift=0, rows_per_seq=None, prior_logits2d=None,
+                 g_entropy=None, g_token_entropy=None, g_kl=None, g_token_kl=None, V=None, out=None):
+    """gct_seq_dist_bwd (decode.dist_grad_reference states the rule): the gradient of seq_dist's four outputs with
+    respect to the AGENT's logits, for the geometry seq_dist takes (same checks).  g_entropy / g_kl fp32 [n],
+    g_token_entropy / g_token_kl fp32 [n, W] with unit column stride: the incoming gradients, each may be None (0); the
+    library refuses all four None, and the kl pair without prior_logits2d.
+    Returns dlogits fp32, contiguous, in the shape of logits2d (or fills `out`, [>= n * rows_per_seq, V] with unit column
+    stride): every row is written -- zeros on the rows that are not scored or whose weights are 0, where neither model's
+    logits are read."""
+    n, W, R, V, ld, ld_prior = _seq_geometry("seq_dist_bwd", logits2d, ys, rows_per_seq, V, prefix_lens, prior_logits2d)
+    for g, what in ((g_entropy, "g_entropy"), (g_kl, "g_kl")):
+        if g is not None:
+            _chk(g, f"seq_dist_bwd.{what}")
+            if g.numel() != n or not g.is_contiguous():
+                raise ValueError(f"seq_dist_bwd: {what} must be a contiguous fp32 tensor of {n} entries")
+    for g, what in ((g_token_entropy, "g_token_entropy"), (g_token_kl, "g_token_kl")):
+        if g is not None:
+            _chk(g, f"seq_dist_bwd.{what}")
+            if g.shape != (n, W) or g.stride(1) != 1:
+                raise ValueError(f"seq_dist_bwd: {what} must be [{n}, {W}] with unit column stride")
+    rows = max(n * R, 0 if logits2d is None else logits2d.shape[0])
+    if out is None:
+        out = torch.empty(rows, V, device=ys.device)
+        if rows > n * R:
+            out[n * R:].zero_()                          # rows behind the last sequence belong to nobody
+    _chk(out, "seq_dist_bwd.dlogits")
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < n * R or out.shape[1] != V:
+        raise ValueError(f"seq_dist_bwd: out must be [>= {n * R}, {V}] with unit column stride")
+    if n == 0:
+        return out                                       # no sequence: nothing to write (an empty tensor has no address)
+    check(_L().gct_seq_dist_bwd(_p(logits2d), ld, V, R, int(row_shift), _p(prior_logits2d), ld_prior, _p(ys),
+                                ys.stride(0), _p(prefix_lens), int(pad_id), n, W, _p(g_entropy), _p(g_token_entropy),
+                                0 if g_token_entropy is None else g_token_entropy.stride(0), _p(g_kl), _p(g_token_kl),
+                                0 if g_token_kl is None else g_token_kl.stride(0), _p(out), out.stride(0), _st()),
+          "gct_seq_dist_bwd")
+    return out
+
+
 def chosen_logp(logits2d, ys, pos_dev, out, pad_id, row_off=None, item=None, prefix_len=None):
     """gct_chosen_logp, after select_token on the same logits [n, V] and device counter: out[dst, p] = the model's
     log-probability (raw logits, temperature 1) of the token ys[r, p] the selection has just written at

@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 25
+#define GCT_ABI_VERSION 26
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -401,6 +401,35 @@ int gct_seq_logp(const float* logits, int64_t ld, int V, int64_t rows_per_seq, i
 int gct_seq_logp_bwd(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift, const int64_t* ys,
                      int64_t ld_ys, const int32_t* prefix_lens, int64_t pad_id, int n, int W, const float* g_logp,
                      const float* g_token, int64_t ld_g, float* dlogits, int64_t ld_d, void* stream);
+/* Entropy of the next-token distribution and its KL divergence from a second ("prior") model's, per scored token and
+ * per sequence (gct_plus_amd/decode.py dist_reference states the rule); gct_seq_logp's geometry and SCORED predicate.
+ * prior_logits (nullable) has the agent's row numbering with its own row stride ld_prior >= V; token_kl and kl are
+ * null exactly when it is.  With e_v = exp(x_v - m), se = sum e_v over a scored column's agent row x (m its maximum)
+ * and m', se' the same of the prior's row y:
+ *   token_entropy [n][ld_out]: log(se) - sum e_v (x_v - m) / se
+ *   token_kl [n][ld_out]:      sum (e_v / se) ((x_v - m - log se) - (y_v - m' - log se'))
+ * in fp32, a term with e_v == 0 (a -inf logit) left out; p_v > 0 where q_v == 0 gives +inf.  Columns that are not
+ * scored hold 0 and NEITHER model's logits row of such a column is read; all W columns are written.
+ *   entropy [n], kl [n]: the sums of the scored columns in ascending column order.
+ * One workgroup per sequence, no atomics: bit-reproducible.  Shape limits as gct_seq_logp's; otherwise, and for kl
+ * outputs without a prior (or a prior without them), GCT_ERR_ARG before any launch.  n == 0: nothing is written. */
+int gct_seq_dist(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift, const float* prior_logits,
+                 int64_t ld_prior, const int64_t* ys, int64_t ld_ys, const int32_t* prefix_lens, int64_t pad_id, int n,
+                 int W, float* token_entropy, int64_t ld_out, float* entropy, float* token_kl, float* kl, void* stream);
+/* The gradient of gct_seq_dist with respect to the AGENT's logits (gct_plus_amd/decode.py dist_grad_reference states
+ * the rule); the prior gets none.  Row numbering and predicate as gct_seq_logp_bwd's.  With
+ * a = g_entropy[r] + g_token_entropy[r][c] and b = g_kl[r] + g_token_kl[r][c] (fp32 [n] and [n][ld_ge] / [n][ld_gk];
+ * each nullable and then 0, not all four; the kl pair only with a prior) a scored row gets
+ *   dlogits[v] = a * (-p_v (log p_v + H)) + b * (p_v ((log p_v - log q_v) - KL)),   exactly 0 where p_v == 0,
+ * H and KL that row's token_entropy and token_kl.  A row that is not scored, or whose a and b are both 0, gets V exact
+ * zeros and neither model's logits row is read.  All n * rows_per_seq rows of dlogits (row stride ld_d >= V) are
+ * WRITTEN, nothing is accumulated.  One wave per row, no atomics: bit-reproducible.  Otherwise GCT_ERR_ARG before any
+ * launch.  n == 0: nothing to do. */
+int gct_seq_dist_bwd(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift,
+                     const float* prior_logits, int64_t ld_prior, const int64_t* ys, int64_t ld_ys,
+                     const int32_t* prefix_lens, int64_t pad_id, int n, int W, const float* g_entropy,
+                     const float* g_token_entropy, int64_t ld_ge, const float* g_kl, const float* g_token_kl,
+                     int64_t ld_gk, float* dlogits, int64_t ld_d, void* stream);
 /* The decode-step form: launched after gct_select_token in the step unit, on the same logits [n][V] and the same
  * device counter.  Row r looks at column p = *pos - row_off[r] + 1 (row_off nullable), the column the selection has
  * just written, takes tok = ys[r][p] and writes out[dst][p] = log-softmax(logits[r])[tok], or 0 when tok == pad_id (a

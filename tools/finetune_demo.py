@@ -3,8 +3,11 @@
 --rounds times  sample --n molecules (multinomial, one scaffold) -> reward -> Train/finetune.reinforce_step.
 The reward is decode.SmilesGrammar.well_formed of the generated tokens (1 or 0), so no chemistry toolkit is needed: a
 randomly initialised model seldom closes its rings and branches and ends with <eos>, and the update teaches it to.
-Prints the well-formed rate of a fixed evaluation batch before and after, the rate of every round, and the time of a
-reinforce_step (forward + backward + optimizer, the sampling not included).
+Prints the well-formed rate of a fixed evaluation batch before and after -- with the number of DISTINCT strings in it and
+the policy's mean entropy per token, which show the collapse a reward alone ends in --, the rate of every round, and the
+time of a reinforce_step (forward + backward + optimizer, the sampling not included).
+--entropy-coef / --kl-coef: the regularised step (an entropy bonus; a KL penalty against Train/finetune.frozen_prior of
+the starting weights, which costs a second, forward-only decoder pass).  No coefficient is prescribed.
 
 --time-step: no sampling; --n fixed rows of MOSES-like lengths (clip(round(N(35, 8)), 15, 78) tokens + <eos> behind a
 scaffold prefix), --rounds reinforce_steps on them after two warm-up steps: the figure to put next to a bench.py
@@ -25,6 +28,9 @@ ap.add_argument("--lr", type=float, default=1e-4)
 ap.add_argument("--max-strlen", type=int, default=40)
 ap.add_argument("--scaffold", default="c1ccccc1")
 ap.add_argument("--seed", type=int, default=1)
+ap.add_argument("--entropy-coef", type=float, default=0.0, help="entropy bonus per scored token (reinforce_step)")
+ap.add_argument("--kl-coef", type=float, default=0.0,
+                help="penalty on KL(policy || frozen starting weights) per scored token")
 ap.add_argument("--time-step", action="store_true", help="time reinforce_step on fixed rows of MOSES-like lengths")
 a = ap.parse_args()
 
@@ -36,7 +42,7 @@ from gct_plus_amd.decode import SmilesGrammar  # noqa: E402
 from gct_plus_amd.Inference.sampling_tool import DecodedRows, PscavaetfSampling  # noqa: E402
 from gct_plus_amd.Model import model_dict  # noqa: E402
 from gct_plus_amd.optim import FusedAdam  # noqa: E402
-from gct_plus_amd.Train.finetune import reinforce_step  # noqa: E402
+from gct_plus_amd.Train.finetune import frozen_prior, reinforce_step  # noqa: E402
 
 mtype = "pscavaetf"
 nc = synthetic.n_conds(mtype)
@@ -51,12 +57,13 @@ sampler = PscavaetfSampling(model, SRC, TRG, latent_dim=dims["latent_dim"], max_
 grammar = SmilesGrammar(TRG.itos, sampler.pad_id, sampler.eos_id)
 opt = FusedAdam(model.parameters(), lr=a.lr, betas=(0.9, 0.98), eps=1e-9, model=model)
 gen = torch.Generator().manual_seed(a.seed)
+prior = frozen_prior(model) if a.kl_coef else None
 
 
 def timed_step(rows, reward):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    stats = reinforce_step(sampler, opt, rows, reward)
+    stats = reinforce_step(sampler, opt, rows, reward, entropy_coef=a.entropy_coef, kl_coef=a.kl_coef, prior=prior)
     torch.cuda.synchronize()
     return stats, (time.perf_counter() - t0) * 1e3
 
@@ -102,17 +109,32 @@ def sample(n, seed):
     return rows, reward
 
 
+def evaluate():
+    """The fixed evaluation batch under the current weights: (well-formed rate, distinct generated strings, mean entropy
+    of the policy per scored token)."""
+    rows, reward = sample(a.n, EVAL_SEED)
+    t0 = int(rows.prefix_lens[0])
+    distinct = len({tuple(t for t in r if t != sampler.pad_id) for r in rows.ys[:, t0:].cpu().tolist()})
+    with torch.no_grad():
+        terms = sampler.policy_terms(*rows)
+    return float(reward.mean()), distinct, float(terms.entropy.sum() / terms.tokens.sum())
+
+
 EVAL_SEED = 10 ** 6
-before = float(sample(a.n, EVAL_SEED)[1].mean())
-print(f"{'full-size' if a.full else 'tiny'} {mtype}, {a.n} molecules per round, lr {a.lr}: well-formed rate of the "
-      f"evaluation batch before fine-tuning {before:.3f}", flush=True)
+before = evaluate()
+reg = f", entropy_coef {a.entropy_coef}, kl_coef {a.kl_coef}" if a.entropy_coef or a.kl_coef else ""
+print(f"{'full-size' if a.full else 'tiny'} {mtype}, {a.n} molecules per round, lr {a.lr}{reg}: evaluation batch before "
+      f"fine-tuning: well-formed {before[0]:.3f}, {before[1]} distinct strings, entropy {before[2]:.3f} per token",
+      flush=True)
 ms = []
 for k in range(a.rounds):
     rows, reward = sample(a.n, a.seed * 1000 + k)
     stats, dt = timed_step(rows, reward)
     ms.append(dt)
+    more = "".join(f"  {key[5:]} {stats[key]:7.4f}" for key in ("mean_entropy", "mean_kl") if key in stats)
     print(f"round {k:3d}: well-formed {stats['mean_reward']:.3f}  mean logp {stats['mean_logp']:8.3f}  loss "
-          f"{stats['loss']:8.4f}  step {dt:7.2f} ms", flush=True)
-after = float(sample(a.n, EVAL_SEED)[1].mean())
-print(f"well-formed rate of the evaluation batch: {before:.3f} before, {after:.3f} after {a.rounds} rounds; "
-      f"reinforce_step median {float(np.median(ms[1:] or ms)):.2f} ms")
+          f"{stats['loss']:8.4f}{more}  step {dt:7.2f} ms", flush=True)
+after = evaluate()
+print(f"evaluation batch of {a.n}: well-formed {before[0]:.3f} -> {after[0]:.3f}, distinct strings {before[1]} -> "
+      f"{after[1]}, entropy per token {before[2]:.3f} -> {after[2]:.3f} after {a.rounds} rounds{reg}; reinforce_step "
+      f"median {float(np.median(ms[1:] or ms)):.2f} ms")
