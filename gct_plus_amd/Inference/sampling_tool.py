@@ -43,6 +43,12 @@ refuses decode_algo="beam", and `decode_beams` of such a sampler raises.
 n rows of a call are a pool that R decode rows work through, a row whose molecule reached <eos> taking the next one, so
 `sample_smiles(30000)` is one call that never computes past a molecule's end.  Every decode of such a sampler goes that
 way, also one of fewer than R rows (a single wave): what a molecule decodes then never depends on n or R.
+
+`interpolate_smiles` (the reference's Inference/mol_interpolation.py, its fifth inference entry point): P pairs of
+molecules x A interior alphas, every cell decoded from latents interpolated between the two endpoints' encodings
+(ops.latent_stats / ops.latent_interp build them on the device) with the reference's retry ladder of rising noise -- the
+tries of every cell are rows of ONE decode per round.  `reconstruct_smiles` is the exact-latent round trip (z = the
+encoder's mean) that interpolation approximates.  Inference/mol_interpolation.py holds the rules and the deviations.
 """
 from __future__ import annotations
 
@@ -51,8 +57,10 @@ from typing import List, NamedTuple, Optional, Sequence
 import numpy as np
 import torch
 
+from .. import ops
 from ..Model.modules import get_src_mask
 from ..data import Vocab, tokenize
+from .mol_interpolation import Interpolation, interior_alphas, interp_plan, lerp, noise_ladder, run_ladder
 from ..decode import (BEAM_ALPHA, KVDecoder, PolicyTerms, SmilesGrammar, check_beam_size, check_sample_filter,
                       check_stream_model, check_stream_rows, generated_tokens, score_tokens, sequence_logp,
                       sequence_policy)
@@ -149,6 +157,8 @@ def latent_setup_rows(extras, zs, toklen, latent_dim, sample_toklen, sample_z):
 
 
 class Sampling:
+    uses_scaffold = uses_props = False          # what the model type's encode_smiles / sample_smiles take
+
     def __init__(self, model, SRC: Vocab, TRG: Vocab, latent_dim: int, max_strlen: int = 80,
                  cond_dim: int = 0, decode_algo: str = "greedy", toklen_data: Optional[Sequence[int]] = None,
                  scaler=None, device="cuda", seed: int = 0, use_graphs: bool = False, beam_size: int = 4,
@@ -187,6 +197,7 @@ class Sampling:
         self.rng = np.random.default_rng(seed)
         self.gen = torch.Generator().manual_seed(seed)
         self.seed = seed
+        self.latent_seed = seed                 # interpolate_smiles' latents: one stream per sampler, not per decode
         self.kv = KVDecoder(model, self.pad_id, self.sos_id, self.eos_id)
 
     # ---- helpers with the reference's names ------------------------------------------------
@@ -349,6 +360,140 @@ class Sampling:
         return self.kv.generate_beam(ys, k, self.max_strlen, alpha=self.beam_alpha if alpha is None else alpha,
                                      use_graphs=self.use_graphs)
 
+    # ---- molecule -> latent -> molecule ------------------------------------------------------
+    def _endpoint_args(self, what, n, scaffolds, props):
+        """The arguments the model type takes, checked: (scaffold list or None, raw property array [n, n_c] or None)."""
+        if (scaffolds is not None) != self.uses_scaffold:
+            raise ValueError(f"{what}: {type(self).__name__} takes {'a scaffold per molecule' if self.uses_scaffold else 'no scaffolds'}")
+        if (props is not None) != self.uses_props:
+            raise ValueError(f"{what}: {type(self).__name__} takes {'a property row per molecule' if self.uses_props else 'no properties'}")
+        if scaffolds is not None:
+            scaffolds = list(scaffolds)
+            if len(scaffolds) != n:
+                raise ValueError(f"{what}: {n} molecules for {len(scaffolds)} scaffolds")
+        if props is not None:
+            props = np.asarray(props, dtype=np.float64)
+            if props.ndim != 2 or props.shape[0] != n:
+                raise ValueError(f"{what}: {n} molecules for a property array of shape {list(props.shape)}")
+        return scaffolds, props
+
+    def _encode_endpoints(self, smiles, scaffolds, props, transform):
+        """One encode_smiles of the molecules -> (mu, log_var [n, L_e, latent], src_mask [n, 1, L_e] the encoder's own
+        mask: condition rows, scaffold, <sep>, tokens)."""
+        args = [smiles] + ([scaffolds] if self.uses_scaffold else []) + ([props] if self.uses_props else [])
+        _, mu, log_var = self.encode_smiles(*args, **({"transform": transform} if self.uses_props else {}))
+        src = self.tokenize_smiles([b + "<sep>" + a for a, b in zip(smiles, scaffolds)] if self.uses_scaffold else smiles)
+        mask = get_src_mask(src, self.pad_id, None if props is None else torch.zeros(len(smiles), props.shape[1]))
+        return mu, log_var, mask
+
+    def _conds(self, props, transform):
+        if props is None:
+            return None
+        return self.transform(props) if transform else torch.as_tensor(props, dtype=torch.float32)
+
+    def interpolate_smiles(self, src0, src1, n_interpolations=8, *, scaffolds0=None, scaffolds1=None, props0=None,
+                           props1=None, ladder=None, chunk=16, accept=None, pair_ids=None, return_rows=False):
+        """The call every type answers (`_interpolate` states it); the types' own front ends below take only what their
+        encode_smiles / sample_smiles take, the property types with `transform` as there."""
+        return self._interpolate(src0, src1, n_interpolations, scaffolds0=scaffolds0, scaffolds1=scaffolds1, props0=props0,
+                                 props1=props1, ladder=ladder, chunk=chunk, accept=accept, pair_ids=pair_ids,
+                                 return_rows=return_rows)
+
+    @torch.no_grad()
+    def _interpolate(self, src0, src1, n_interpolations=8, *, scaffolds0=None, scaffolds1=None, props0=None,
+                     props1=None, ladder=None, chunk=16, accept=None, pair_ids=None, return_rows=False, transform=True):
+        """Interpolate between the molecules src0[p] and src1[p] of P pairs at the A = n_interpolations interior alphas of
+        np.linspace(0, 1, A + 2) (mol_interpolation.py of the reference; the module of that name here states the rules).
+        One encode_smiles of all 2 P endpoints and one ops.latent_stats; then rounds: every unresolved (pair, alpha) cell
+        sends its next `chunk` rungs of `ladder` (noise standard deviations; default noise_ladder()) as rows through one
+        ops.latent_interp and one `decode` -- stream rows, grammar, graphs and filters as the sampler is configured --
+        until every cell has an accepted row or the ladder is exhausted.  Rows of a round: cells in (pair, alpha) order,
+        a cell's rungs ascending; row's latent rows = toklen of its cell (interp_plan), its random streams are keyed by
+        item = (pair_id * A + alpha_index) * len(ladder) + rung, so a cell's latents do not depend on the other pairs of
+        the call, on chunk or on the round (pair_ids: ints [P], default 0 .. P - 1; ValueError when an item does not fit
+        int32) under the sampler's constructor seed.
+        Scaffold types decode behind <sos> scaffolds0[p] <sep>, as the reference does; property types with the
+        transformed lerp of the raw properties.  accept(smiles) -> bool; the default is SmilesGrammar.well_formed on the
+        row's tokens and a non-empty string (syntax only -- a caller with rdkit passes its own).
+        Returns an Interpolation; return_rows=True: (Interpolation, [DecodedRows of each round]).  ValueError with
+        decode_algo="beam"."""
+        if self.decode_algo == "beam":
+            raise ValueError("interpolate_smiles is not supported with decode_algo='beam' (the retry ladder is one mixed "
+                             "batch of greedy / multinomial rows)")
+        src0, src1 = list(src0), list(src1)
+        P = len(src0)
+        if P < 1 or len(src1) != P:
+            raise ValueError(f"interpolate_smiles: {P} first molecules for {len(src1)} second ones")
+        sca0, props0 = self._endpoint_args("interpolate_smiles", P, scaffolds0, props0)
+        sca1, props1 = self._endpoint_args("interpolate_smiles", P, scaffolds1, props1)
+        alphas = interior_alphas(n_interpolations)
+        ladder = noise_ladder() if ladder is None else np.asarray(ladder, dtype=np.float64).reshape(-1)
+        if ladder.size < 1 or not np.all(ladder >= 0):
+            raise ValueError("ladder: at least one noise standard deviation, none negative")
+        A, K = alphas.size, ladder.size
+        mu, log_var, mask = self._encode_endpoints(src0 + src1, None if sca0 is None else sca0 + sca1,
+                                                   None if props0 is None else np.concatenate([props0, props1]),
+                                                   transform)
+        lens = mask.sum(-1).view(-1).cpu().numpy()
+        prefixes = None
+        if self.uses_scaffold:
+            ys0_all, plens_all, extras = self._scaffold_prefixes(sca0)
+            prefixes = (ys0_all, plens_all)
+        toklen = interp_plan(lens[:P], lens[P:], alphas, extras if self.uses_scaffold else None)
+        stats = ops.latent_stats(mu.contiguous(), log_var.contiguous(), lens)
+        if accept is None:
+            grammar = self.grammar or SmilesGrammar(self.TRG.itos, self.pad_id, self.eos_id)
+            verdict = lambda o: bool(o[0]) and grammar.well_formed(o[1])          # noqa: E731
+        else:
+            verdict = lambda o: bool(accept(o[0]))                                # noqa: E731
+        decoded = []
+
+        def decode_round(rnd):
+            p, i = torch.as_tensor(rnd.pair), rnd.alpha
+            tl = toklen[rnd.pair, i]
+            T = int(tl.max())
+            zs = ops.latent_interp(stats, rnd.pair, rnd.pair + P, alphas[i], ladder[rnd.tries], tl, rnd.item, T,
+                                   self.latent_seed)
+            src_mask = torch.arange(T).view(1, 1, T) < torch.as_tensor(tl).view(-1, 1, 1)
+            dconds = None
+            if self.uses_props:
+                dconds = self._conds(lerp(props0[rnd.pair], props1[rnd.pair], alphas[i][:, None]), transform)
+            if prefixes is None:
+                outs = self.decode(zs, self.init_y(len(p)), src_mask, dconds, return_rows=True)
+            else:
+                pl = prefixes[1][p]
+                outs = self.decode(zs, prefixes[0][p][:, :int(pl.max())], src_mask, dconds, prefix_lens=pl,
+                                   return_rows=True)
+            rows = self._split(outs, True)[1][-1]
+            decoded.append(rows)
+            gen = generated_tokens(rows.ys, rows.prefix_lens).cpu().numpy()
+            return [(self.id_to_smi(g), g) for g in gen]
+
+        tries, results, rows_decoded = run_ladder(P, A, K, chunk, pair_ids, decode_round, verdict)
+        smiles = [[None if o is None else o[0] for o in row] for row in results]
+        res = Interpolation(smiles, tries, np.where(tries >= 0, ladder[np.maximum(tries, 0)], np.nan), toklen,
+                            rows_decoded)
+        return (res, decoded) if return_rows else res
+
+    @torch.no_grad()
+    def reconstruct_smiles(self, smiles_list, scaffold_list=None, props=None, transform=True, return_rows=False):
+        """The exact-latent round trip: encode the molecules and decode with z = the encoder's mean under the encoder's
+        own mask (scaffold types behind <sos> scaffold <sep>, property types with the same properties).  Returns
+        (smiles, same): the decoded strings and, per molecule, whether the decoded tokens equal the input's token for
+        token; return_rows=True appends the DecodedRows.  ValueError with decode_algo="beam"."""
+        if self.decode_algo == "beam":
+            raise ValueError("reconstruct_smiles is not supported with decode_algo='beam'")
+        smiles_list = list(smiles_list)
+        sca, props = self._endpoint_args("reconstruct_smiles", len(smiles_list), scaffold_list, props)
+        mu, _, src_mask = self._encode_endpoints(smiles_list, sca, props, transform)
+        ys0, lens = (self.init_y(len(smiles_list)), None) if sca is None else self._scaffold_prefixes(sca)[:2]
+        outs = self.decode(mu, ys0, src_mask, self._conds(props, transform), prefix_lens=lens, return_rows=True)
+        rows = self._split(outs, True)[1][-1]
+        gen = generated_tokens(rows.ys, rows.prefix_lens).cpu().tolist()
+        ids = [g[:g.index(self.eos_id)] if self.eos_id in g else g for g in gen]
+        out = ([self.id_to_smi(g) for g in ids], [g == self.smi_to_id(s) for g, s in zip(ids, smiles_list)])
+        return out + (rows,) if return_rows else out
+
     def _latent_setup(self, n, zs, toklen, extra=0):
         if zs is not None:
             assert n == zs.size(0)
@@ -413,6 +558,10 @@ class Sampling:
 
 
 class VaetfSampling(Sampling):
+    def interpolate_smiles(self, src0, src1, n_interpolations=8, **kw):
+        """Sampling._interpolate of molecules alone."""
+        return self._interpolate(src0, src1, n_interpolations, **kw)
+
     def encode_smiles(self, smiles_list):
         src = self.tokenize_smiles(smiles_list).to(self.device)
         return self.model.encode(src=src, src_mask=get_src_mask(src, self.pad_id))
@@ -433,6 +582,12 @@ class VaetfSampling(Sampling):
 
 
 class CvaetfSampling(Sampling):
+    uses_props = True
+
+    def interpolate_smiles(self, src0, src1, n_interpolations=8, *, props0=None, props1=None, transform=True, **kw):
+        """Sampling._interpolate with a property row per endpoint (raw; transformed like encode_smiles' econds)."""
+        return self._interpolate(src0, src1, n_interpolations, props0=props0, props1=props1, transform=transform, **kw)
+
     def encode_smiles(self, smiles_list, econds, transform=True):
         src = self.tokenize_smiles(smiles_list).to(self.device)
         econds = (self.transform(econds) if transform else torch.as_tensor(econds, dtype=torch.float32)).to(self.device)
@@ -459,6 +614,12 @@ class CvaetfSampling(Sampling):
 
 
 class ScaVaeSampling(Sampling):
+    uses_scaffold = True
+
+    def interpolate_smiles(self, src0, src1, n_interpolations=8, *, scaffolds0=None, scaffolds1=None, **kw):
+        """Sampling._interpolate with a scaffold per endpoint; rows decode behind <sos> scaffolds0[p] <sep>."""
+        return self._interpolate(src0, src1, n_interpolations, scaffolds0=scaffolds0, scaffolds1=scaffolds1, **kw)
+
     def encode_smiles(self, smiles_list, scaffold_list):
         src = self.tokenize_smiles([b + "<sep>" + a for a, b in zip(smiles_list, scaffold_list)]).to(self.device)
         return self.model.encode(src=src, src_mask=get_src_mask(src, self.pad_id))
@@ -486,6 +647,14 @@ class ScaVaeSampling(Sampling):
 
 
 class PscavaetfSampling(Sampling):
+    uses_scaffold = uses_props = True
+
+    def interpolate_smiles(self, src0, src1, n_interpolations=8, *, scaffolds0=None, scaffolds1=None, props0=None,
+                           props1=None, transform=True, **kw):
+        """Sampling._interpolate with a scaffold and a property row per endpoint."""
+        return self._interpolate(src0, src1, n_interpolations, scaffolds0=scaffolds0, scaffolds1=scaffolds1,
+                                 props0=props0, props1=props1, transform=transform, **kw)
+
     def encode_smiles(self, smiles_list, scaffold_list, econds, transform=True):
         src = self.tokenize_smiles([b + "<sep>" + a for a, b in zip(smiles_list, scaffold_list)]).to(self.device)
         econds = (self.transform(econds) if transform else torch.as_tensor(econds, dtype=torch.float32)).to(self.device)

@@ -841,6 +841,69 @@ def kld_bwd(mu, log_var, gout):
     return dmu, dlv
 
 
+LATENT_MAX_DIM = 1024                          # GCT_LATENT_MAX_DIM (include/gctplus_hip.h)
+
+
+def _host_i32(x, name, count=None):
+    """A per-row table the caller holds on the HOST (list, numpy array or CPU tensor) as a contiguous int32 CPU tensor:
+    its range checks are done here, before a launch, because the library never reads device memory."""
+    t = torch.as_tensor(x)
+    if t.numel() == 0:
+        t = t.to(torch.int64)
+    if t.is_cuda or t.is_floating_point() or t.dim() != 1 or (count is not None and t.numel() != count):
+        raise ValueError(f"{name}: expected {'' if count is None else str(count) + ' '}integers on the host, one per row")
+    if t.numel() and (int(t.min()) < -2 ** 31 or int(t.max()) >= 2 ** 31):
+        raise _lib.GctError(f"{name}: does not fit int32")
+    return t.to(torch.int32).contiguous()
+
+
+def latent_stats(mu, log_var, rows):
+    """gct_latent_stats: mu, log_var fp32 [n, Le, D] contiguous on the device, rows [n] host integers (molecule i owns
+    its first rows[i] latent rows, 1 <= rows[i] <= Le; later rows are never read) -> stats fp32 [n, 4, D]: mean and
+    unbiased standard deviation of mu, then of log_var, per dimension (0 where rows[i] == 1)."""
+    _chk(mu, "latent_stats.mu"), _chk(log_var, "latent_stats.log_var")
+    if mu.dim() != 3 or log_var.shape != mu.shape or not mu.is_contiguous() or not log_var.is_contiguous():
+        raise ValueError("latent_stats: mu and log_var must be contiguous [n, Le, D] tensors of one shape")
+    n, Le, D = mu.shape
+    rows = _host_i32(rows, "latent_stats.rows", n)
+    if n and (int(rows.min()) < 1 or int(rows.max()) > Le):
+        raise _lib.GctError(f"latent_stats: rows must lie in [1, {Le}], got {int(rows.min())}..{int(rows.max())}")
+    stats = torch.empty(n, 4, D, dtype=torch.float32, device=mu.device)
+    rows_dev = rows.to(mu.device)                   # held until the launch is enqueued
+    check(_L().gct_latent_stats(_p(mu), _p(log_var), n, Le, D, _p(rows_dev), _p(stats), _st()), "gct_latent_stats")
+    return stats
+
+
+def latent_interp(stats, a, b, alpha, noise_std, lens, items, T, seed):
+    """gct_latent_interp: stats fp32 [n, 4, D] on the device (latent_stats); a, b, lens, items [R] host integers and
+    alpha, noise_std [R] host floats, one per output row -> z fp32 [R, T, D]: row r interpolates molecule a[r] towards
+    b[r] over its first lens[r] tokens (zeros behind them) with the random streams of items[r].  The per-row tables
+    travel to the device as one copy.  GctError before any launch when lens is outside [0, T], a or b outside [0, n),
+    or an item negative."""
+    _chk(stats, "latent_interp.stats")
+    if stats.dim() != 3 or stats.shape[1] != 4 or not stats.is_contiguous():
+        raise ValueError("latent_interp: stats must be a contiguous [n, 4, D] tensor")
+    n, D, T = stats.shape[0], stats.shape[2], int(T)
+    a = _host_i32(a, "latent_interp.a")
+    R = a.numel()
+    b, lens, items = (_host_i32(t, f"latent_interp.{k}", R) for k, t in (("b", b), ("lens", lens), ("items", items)))
+    fl = [torch.as_tensor(t, dtype=torch.float32).reshape(-1).contiguous() for t in (alpha, noise_std)]
+    if any(t.numel() != R or t.is_cuda for t in fl):
+        raise ValueError(f"latent_interp: alpha and noise_std take {R} host floats, one per row")
+    if R:
+        if int(lens.min()) < 0 or int(lens.max()) > T:
+            raise _lib.GctError(f"latent_interp: lens must lie in [0, T = {T}], got {int(lens.min())}..{int(lens.max())}")
+        if min(int(a.min()), int(b.min())) < 0 or max(int(a.max()), int(b.max())) >= n:
+            raise _lib.GctError(f"latent_interp: a and b must lie in [0, n = {n})")
+        if int(items.min()) < 0:
+            raise _lib.GctError("latent_interp: items must be >= 0")
+    tab = torch.stack([a, b, lens, items, fl[0].view(torch.int32), fl[1].view(torch.int32)]).to(stats.device)
+    z = torch.empty(R, max(T, 0), D, dtype=torch.float32, device=stats.device)
+    check(_L().gct_latent_interp(_p(stats), n, D, _p(tab[0]), _p(tab[1]), _p(tab[4]), _p(tab[5]), _p(tab[2]),
+                                 _p(tab[3]), R, T, _p(z), int(seed), _st()), "gct_latent_interp")
+    return z
+
+
 def ce_fwd(logits2d, target, pad_id):
     _chk(target, "ce.target", torch.int64)
     rows, V = logits2d.shape

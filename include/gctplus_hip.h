@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 26
+#define GCT_ABI_VERSION 27
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -363,6 +363,46 @@ int gct_kld_fwd(const float* mu, const float* log_var, float* out, float* ws, in
 /* dmu = g*mu ; dlv = g*0.5*(exp(lv)-1), g read from device scalar gout[0] */
 int gct_kld_bwd(const float* mu, const float* log_var, const float* gout, float* dmu, float* dlv,
                 int64_t n, void* stream);
+
+/* --------------------------------------------- K12: latents for molecule interpolation */
+/* Inference/mol_interpolation.py:124-131 (approximate_z's fit).  mu, log_var fp32 [n][Le][D] contiguous; rows int32 [n]
+ * on the device: the first rows[i] latent rows of molecule i are its own (the prefix get_src_mask marks: condition
+ * rows, scaffold, <sep>, tokens); rows at or beyond rows[i] are never read.  stats fp32 [n][4][D] = per dimension the
+ * mean of mu, the standard deviation of mu, the mean of log_var, the standard deviation of log_var over those rows.
+ * The standard deviation is the unbiased one (torch.std, ddof 1) in two passes, rows in ascending order: the mean
+ * (sum / rows) first, then sqrt(sum of squared deviations / (rows - 1)).  rows[i] == 1 gives 0 (the reference: NaN).
+ * No atomics: bit-reproducible.  Limits: 1 <= D <= GCT_LATENT_MAX_DIM, Le >= 1, 0 <= n <= 65535, else GCT_ERR_ARG before
+ * a launch; 1 <= rows[i] <= Le is the caller's to check (ops.latent_stats does, on the host: the library does not read
+ * device memory), and the kernel clamps rows[i] into that range instead of reading outside the molecule. */
+#define GCT_LATENT_MAX_DIM 1024
+int gct_latent_stats(const float* mu, const float* log_var, int n, int Le, int D, const int32_t* rows, float* stats,
+                     void* stream);
+/* Inference/mol_interpolation.py:124-141, 216-224: output row r interpolates molecule a[r] towards molecule b[r] of
+ * stats (gct_latent_stats, n molecules).  z fp32 [R][T][D]; tokens t >= len[r] are written as exact zeros.  a, b, len,
+ * item int32 [R], alpha, noise_std fp32 [R], all on the device.  For every t < len[r], one wave per (r, t):
+ *   - five vectors of D standard normals n_s, s = 0..4, under the repository's N(0, 1) convention (Philox4x32-10, Box-
+ *     Muller on the word pairs (x, y) and (z, w), u01 of csrc/vae.hip) with the key of (seed, site GCT_LATENT_SITE):
+ *     element d of n_s is element d & 3 of the call with the counter (item[r], 8 * t + s, d >> 2, GCT_LATENT_C3).
+ *     Nothing else enters the counter: a row's latent is a function of (seed, item, a, b, alpha, noise_std, len) and
+ *     not of R, T or its position in the batch.  item[r] >= 0 is the row's identity.
+ *   - per dimension u = mean_mu[a] + std_mu[a] * n_0, v = mean_mu[b] + std_mu[b] * n_1, and p, q likewise from the
+ *     log_var statistics with n_2, n_3.
+ *   - m = slerp(u, v, alpha), l = slerp(p, q, alpha) over the D dimensions of the token: c = u.v / (|u| |v|),
+ *     w = acos(c), result (sin((1 - alpha) w) u + sin(alpha w) v) / sin(w), not renormalised (as the reference).
+ *     Guard: |u| == 0, |v| == 0 or not |c| <= GCT_LATENT_SLERP_MAX_COS (a NaN included) gives the lerp
+ *     (1 - alpha) u + alpha v, evaluated as u + alpha (v - u) so that u == v returns u exactly (the reference divides
+ *     by zero there).
+ *   - z = m + noise_std[r] * n_4 * exp(0.5 * l); noise_std[r] == 0 writes exactly m (and l is not evaluated).
+ * The sums over D run in a fixed lane order, independent of the grid.  Limits: 1 <= D <= GCT_LATENT_MAX_DIM, R >= 0
+ * (R == 0 writes nothing), T >= 1, n >= 1, R * T <= 2^25 (one wave each: 2^31 work-items in the launch), else GCT_ERR_ARG before a launch.  0 <= len[r] <= T and a[r],
+ * b[r] in [0, n) are the caller's to check (ops.latent_interp does, on the host, and raises before a launch); the
+ * kernel reads nothing through a bad index: len[r] > T acts as T, and a row whose a or b is outside [0, n) is zeros. */
+#define GCT_LATENT_SITE 0x1A7E47u
+#define GCT_LATENT_C3 0x082EFA98u
+#define GCT_LATENT_SLERP_MAX_COS 0.99999904632568359375f /* 1 - 2^-20 */
+int gct_latent_interp(const float* stats, int n, int D, const int32_t* a, const int32_t* b, const float* alpha,
+                      const float* noise_std, const int32_t* len, const int32_t* item, int64_t R, int T, float* z,
+                      uint64_t seed, void* stream);
 
 /* ---------------------------------------------------------- K7: cross-entropy */
 /* Train/trainer1.py:21-22  F.cross_entropy(logits.view(-1,V), ys, ignore_index=pad,
