@@ -1557,6 +1557,32 @@ int launch(const GemmArgs& g, bool vec, hipStream_t st, float* ws = nullptr, int
   return GCT_OK;
 }
 
+// gemm_x6_bwd_pair_kernel: the wgrad workgroups of gw (slab form, nsplit row ranges) and the dgrad tiles of gd as one grid
+template <int NP>
+int launch_x6_pair(const GemmArgs& gw, const GemmArgs& gd, hipStream_t st) {
+  const int64_t nw = ((gw.M + XBM - 1) / XBM) * ((gw.N + XBN - 1) / XBN) * gw.nsplit;
+  const int64_t nd = ((gd.M + XBM - 1) / XBM) * ((gd.N + XBN - 1) / XBN);
+  if (nw <= 0 || nd <= 0 || nw + nd > INT_MAX) {
+    gct_set_error("gemm_x6 pair: bad grid (%lld + %lld blocks)", (long long)nw, (long long)nd);
+    return GCT_ERR_ARG;
+  }
+  static bool attr_set = false;   // per instantiation
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute((const void*)gemm_x6_bwd_pair_kernel<NP>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, X_LDS_BYTES);
+    if (e != hipSuccess) {
+      gct_set_error("gemm_x6 pair: cannot reserve %d bytes of LDS: %s", X_LDS_BYTES, hipGetErrorString(e));
+      return GCT_ERR_HIP;
+    }
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((gemm_x6_bwd_pair_kernel<NP>), dim3((unsigned)(nw + nd)), dim3(512), X_LDS_BYTES, st, gw, gd,
+                     (unsigned)nw);
+  ++(NP == 3 ? g_x6_kernel_launches : g_x3_kernel_launches);
+  GCT_LAUNCH_CHECK("gemm_x6 pair");
+  return GCT_OK;
+}
+
 inline bool al16(const void* p) { return p == nullptr || gct_aligned16(p); }
 
 inline Seg3 mkseg(const float* p0, const float* p1, const float* p2) {
@@ -1818,4 +1844,246 @@ extern "C" int gct_wgrad_route(int64_t M, int nseg, int nper, int K, int64_t ldd
   out4[2] = g.ksplit;
   out4[3] = r.bias_fused ? 1 : 0;
   return GCT_OK;
+}
+
+// =====================================================================================
+// One Linear's backward as ONE launch (gemm_x6_bwd_pair_kernel): the dgrad tiles and the weight-gradient workgroups of
+// the same dY share a grid, so neither has to be a whole number of rounds on the 256 CUs alone -- the dgrad needs no
+// tail launch / fix-up and the weight gradient need not be cut into exactly 256 workgroups.
+//
+// The split count comes from a list-scheduling model of that grid (one 144 KB workgroup per CU, blocks dispatched in
+// order: the wgrad workgroups first, each dgrad tile on the CU that frees first).  Unit: the time of one dgrad K-tile
+// (128 x 256 x 32) on its CU.
+//   dgrad tile       o + K'/32 + e(epilogue)         o = 3.3 (x6_tail_plan's prologue + epilogue, s_memtime stamps)
+//   wgrad workgroup  o_w + c_w * rows/(32 s) + st    both operands are split on the fly: a longer K-tile (c_w)
+//   later reduction  r * s * Ntot * K                the slabs are read once more by the deferred reduction
+// =====================================================================================
+namespace {
+constexpr double PAIR_O = 3.3, PAIR_E_RMW = 0.4;          // dgrad: fixed part; epilogues that read a second [M][N] operand
+constexpr double PAIR_OW = 3.3, PAIR_CW = 1.12, PAIR_ST = 0.5;   // wgrad: fixed part, K-tile ratio, 128 KB slab store
+constexpr double PAIR_RED = 1.0 / 2.8e6;                  // K-tile times per slab element reduced later (4 B at ~4 TB/s,
+                                                          // 2.8 us per K-tile)
+constexpr double PAIR_LAUNCH = 1.0;                       // ramp + drain of one more launch on the stream
+// Lab (tools/kernel_bench.py --suite bwdpair, profiles/r08_bwd_pair_lab_every_shape_paired.log and, with the rule
+// below in place, r08_bwd_pair_lab.log; the Linear shapes of a layer at 40 960,
+// 18 016 and 10 432 rows, paired and separate calls alternated): one unit is 2.0-2.3 us both ways, i.e. the model ranks
+// the two ways as the clock does, with one exception.  Where the model finds no partial round to fill -- the dgrad alone
+// is a whole number of rounds (FFN-2 at 40 960 rows: 2 560 tiles) or fits into one round behind a weight gradient that
+// already is one (10 432 rows: 164 tiles) -- all it predicts is the launch saved, and the clock gives that back: the two
+// problems then only share the L2 (measured 0.98-1.03 of the separate calls).  So a pair must save at least this much
+// beyond nothing, i.e. fill a round, not just drop a launch:
+constexpr double PAIR_MIN_GAIN = 2.0;
+
+struct BwdPairPlan {
+  bool paired;
+  int nsplit;          // wgrad row ranges (slabs) of the call, paired or not
+  int64_t ksplit;      // rows per range, a multiple of 32
+  bool bias_fused;
+  int64_t wblocks, dblocks;   // blocks of the pair grid (0 when not paired)
+  double makespan;     // modelled K-tile times of the paired launch (+ its share of the reduction); 0 when not modelled
+  double separate;     // the same model for the two separate calls
+};
+
+// end of the last block when nw blocks of tw and then nd blocks of td are dispatched in order to 256 CUs
+double pair_makespan(int64_t nw, double tw, int64_t nd, double td) {
+  constexpr int64_t CUS = 256;
+  const int64_t q = nw / CUS, nb = nw % CUS, na = CUS - nb;   // nb CUs run q + 1 wgrad blocks, na run q
+  const double fa = (double)q * tw, fb = (double)(q + 1) * tw;
+  double end = nw > 0 ? (nb ? fb : fa) : 0.0;
+  int64_t ka = 0, kb = 0;
+  for (int64_t left = nd; left > 0;) {
+    const double sa = fa + (double)ka * td, sb = fb + (double)kb * td;
+    const bool a = nb == 0 || sa <= sb;
+    const double fin = (a ? sa : sb) + td;
+    if (fin > end) end = fin;
+    left -= a ? na : nb;
+    ++(a ? ka : kb);
+  }
+  return end;
+}
+
+// last round of a dgrad launched alone, in rounds: what x6_tail_plan decides (1.0: an ordinary round)
+double x6_tail_cost(int64_t M, int64_t N, int64_t K, int* launches) {
+  int64_t m1 = 0;
+  const int s = x6_tail_plan(M, N, K, &m1);
+  *launches = 1;
+  if (s == 1) return 1.0;
+  const int64_t tn = (N + XBN - 1) / XBN, rem = (((M + XBM - 1) / XBM) * tn) % 256, nkt = K / XBK;
+  *launches = (nkt <= 32 && x6s_tiles(M - m1, N) <= X6_TAIL_SMALL_MAX) ? 2 : 3;
+  return (double)((rem * s + 255) / 256) * (PAIR_O + (double)nkt / s) / (PAIR_O + nkt) + 0.05;
+}
+
+// Pure (shape only): the wgrad split of the paired launch and the modelled times of both ways.  M rows, dW [Ntot][K],
+// dX [M][K] reduced over Ntot; ws_bytes: the weight-gradient workspace (slabs + bias slabs must fit).
+BwdPairPlan plan_bwd_pair_shape(int64_t M, int64_t Ntot, int64_t K, int depi, bool want_bias, int64_t ws_bytes) {
+  BwdPairPlan r = {false, 1, BK, false, 0, 0, 0.0, 0.0};
+  const int64_t nktm = M / XBK;
+  if (M <= 0 || M % XBK != 0 || Ntot % XBK != 0) return r;
+  const int64_t tw_tiles = ((Ntot + XBM - 1) / XBM) * ((K + XBN - 1) / XBN);
+  const int64_t td_tiles = ((M + XBM - 1) / XBM) * ((K + XBN - 1) / XBN);
+  const double td = PAIR_O + (double)(Ntot / XBK) + (depi == GCT_DEPI_STORE ? 0.0 : PAIR_E_RMW);
+  auto wcost = [&](int64_t ks) { return PAIR_OW + PAIR_CW * (double)(ks / XBK) + PAIR_ST; };
+  auto red = [&](int ns) { return PAIR_RED * (double)ns * (double)Ntot * (double)K; };
+  double best = 0.0;
+  for (int64_t s = 1; s <= 64 && nktm / s >= 4; ++s) {
+    const int64_t ks = (nktm + s - 1) / s * XBK, ns = (M + ks - 1) / ks;
+    if (ns != s) continue;                               // the same ranges as a smaller s
+    const int64_t need = (ns * Ntot * K + 4 + (want_bias ? ns * Ntot : 0)) * (int64_t)sizeof(float);
+    if (need > ws_bytes) break;
+    const double c = pair_makespan(tw_tiles * ns, wcost(ks), td_tiles, td) + red((int)ns) + PAIR_LAUNCH;
+    if (r.makespan == 0.0 || c < best - 1e-9) { best = c; r.makespan = c; r.nsplit = (int)ns; r.ksplit = ks; }
+  }
+  if (r.makespan == 0.0) return r;
+  // the two separate calls: the wgrad in rounds of its own split, the dgrad in rounds with its balanced tail
+  const int ss = wgrad_splits(M, Ntot, K, true);
+  const int64_t kss = ((M + ss - 1) / ss + BK - 1) / BK * BK, nss = (M + kss - 1) / kss;
+  int dl = 1;
+  const double tail = x6_tail_cost(M, K, Ntot, &dl);
+  const double rounds_d = td_tiles <= 256 ? 1.0 : (double)(td_tiles / 256) + (td_tiles % 256 ? tail : 0.0);
+  r.separate = (double)((tw_tiles * nss + 255) / 256) * wcost(kss) + red((int)nss) + rounds_d * td + PAIR_LAUNCH * (1 + dl);
+  r.wblocks = tw_tiles * r.nsplit;
+  r.dblocks = td_tiles;
+  r.paired = r.separate - r.makespan >= PAIR_MIN_GAIN;
+  return r;
+}
+
+struct BwdShape {           // what the routes of a gct_linear_bwd call depend on
+  int64_t M; int nseg, nper, K; int64_t lddy, ldx, ldw, lddx;
+  int depi; bool aligned16, planes, want_bias; int mode;
+};
+
+GemmArgs dgrad_shape_args(const BwdShape& b, float* dx, const uint16_t* wp0, int64_t plane_stride) {
+  GemmArgs g = {};
+  g.M = b.M; g.N = b.K; g.K = (int64_t)b.nseg * b.nper;
+  g.lda = b.lddy; g.a_nper = b.nper; g.ldb = b.ldw; g.b_nper = b.nper;
+  g.c0 = dx; g.ldc = b.lddx; g.c_nper = INT64_MAX / 4;
+  g.ksplit = g.K; g.nsplit = 1; g.epi = EPI_D0 + b.depi;
+  g.bp0 = wp0; g.bp_stride = plane_stride;
+  return g;
+}
+
+// Pure: the plan of a gct_linear_bwd call.  Paired only when BOTH problems would take GemmRoute::X6 on their own and
+// the model says that the pair is the shorter way; gw gets the split of the call either way (plan_wgrad's when not paired).
+BwdPairPlan plan_bwd_pair(const BwdShape& b, GemmArgs& gw, const GemmArgs& gd, int64_t wws_bytes, const float* dws,
+                          int64_t dws_bytes) {
+  const bool vec_w = b.aligned16 && wgrad_vec_shape(b.lddy, b.ldx, b.nper, b.K);
+  const bool vec_d = b.aligned16 && (b.lddy % 4 == 0) && (b.ldw % 4 == 0) && (b.nper % 4 == 0) && (b.K % 4 == 0);
+  const WgradRoute wr = plan_wgrad(gw, vec_w, b.want_bias, b.mode);          // sets gw.ksplit / gw.nsplit
+  BwdPairPlan r = {false, gw.nsplit, gw.ksplit, wr.bias_fused, 0, 0, 0.0, 0.0};
+  if (wr.kind != GemmRoute::X6) return r;
+  if (plan_gemm<true, false>(gd, vec_d, b.mode, dws, dws_bytes).kind != GemmRoute::X6) return r;
+  const BwdPairPlan m = plan_bwd_pair_shape(b.M, (int64_t)b.nseg * b.nper, b.K, b.depi, b.want_bias, wws_bytes);
+  r.makespan = m.makespan; r.separate = m.separate;
+  if (!m.paired) return r;
+  GemmArgs t = gw;
+  t.ksplit = m.ksplit; t.nsplit = m.nsplit;
+  if (plan_gemm<false, false>(t, vec_w, b.mode, nullptr, 0).kind != GemmRoute::X6) return r;
+  gw.ksplit = m.ksplit; gw.nsplit = m.nsplit;
+  r.paired = true; r.nsplit = m.nsplit; r.ksplit = m.ksplit; r.bias_fused = b.want_bias;
+  r.wblocks = m.wblocks; r.dblocks = m.dblocks;
+  return r;
+}
+
+// [lo, hi) of a strided matrix of `rows` x `cols` floats
+inline bool ranges_overlap(const float* a, int64_t arows, int64_t lda, int64_t acols, const float* b, int64_t brows,
+                           int64_t ldb, int64_t bcols) {
+  if (!a || !b || arows <= 0 || brows <= 0) return false;
+  const float* ae = a + (arows - 1) * lda + acols;
+  const float* be = b + (brows - 1) * ldb + bcols;
+  return (uintptr_t)a < (uintptr_t)be && (uintptr_t)b < (uintptr_t)ae;
+}
+}  // namespace
+
+extern "C" int64_t gct_linear_bwd_ws_bytes(int64_t M, int64_t Ntot, int64_t K) { return gct_wgrad_ws_bytes(M, Ntot, K); }
+
+extern "C" int gct_linear_bwd_route(int64_t M, int nseg, int nper, int K, int64_t lddy, int64_t ldx, int64_t ldw,
+                                    int64_t lddx, int depi, int aligned16, int have_planes, int want_bias, int mode,
+                                    int64_t ws_bytes, int64_t* out8) {
+  GCT_CHECK_ARG(out8 && M >= 0 && K > 0 && nseg >= 1 && nseg <= 3 && nper > 0 && lddy >= 0 && ldx >= 0 && ldw >= 0 &&
+                    lddx >= 0 && ws_bytes >= 0, "linear_bwd_route: bad args");
+  GCT_CHECK_ARG(depi >= GCT_DEPI_STORE && depi <= GCT_DEPI_MUL_SAVED, "linear_bwd_route: unknown epilogue %d", depi);
+  GCT_CHECK_ARG(mode == GCT_GEMM_F32 || mode == GCT_GEMM_BF16X6 || mode == GCT_GEMM_BF16X3,
+                "linear_bwd_route: unknown mode %d", mode);
+  // only the alignment of the buffers is read: stand-in addresses with the alignment asked about
+  const uintptr_t al = aligned16 ? 16 : 4;
+  const BwdShape b = {M, nseg, nper, K, lddy, ldx, ldw, lddx, depi, aligned16 != 0, have_planes != 0, want_bias != 0, mode};
+  GemmArgs gw = wgrad_args(M, nseg, nper, K, lddy, ldx, reinterpret_cast<float*>(al));
+  const GemmArgs gd = dgrad_shape_args(b, reinterpret_cast<float*>(al),
+                                       have_planes ? reinterpret_cast<const uint16_t*>((uintptr_t)16) : nullptr, K * (int64_t)nseg * nper);
+  const int64_t dws_bytes = gct_linear_dgrad_ws_bytes(M, nseg * nper, K);
+  const BwdPairPlan r = plan_bwd_pair(b, gw, gd, ws_bytes, reinterpret_cast<const float*>(al), dws_bytes);
+  out8[0] = r.paired ? 1 : 0;
+  out8[1] = r.nsplit;
+  out8[2] = r.ksplit;
+  out8[3] = r.bias_fused ? 1 : 0;
+  out8[4] = r.wblocks;
+  out8[5] = r.dblocks;
+  out8[6] = (int64_t)(r.makespan * 1000.0 + 0.5);
+  out8[7] = (int64_t)(r.separate * 1000.0 + 0.5);
+  return GCT_OK;
+}
+
+extern "C" int gct_linear_bwd(const float* dy0, const float* dy1, const float* dy2, int64_t lddy, int64_t M, int nseg,
+                              int nper, const float* x, int64_t ldx, int K, float* dw0, float* dw1, float* dw2,
+                              int64_t lddw, float* db0, float* db1, float* db2, float* wws, int64_t wws_bytes,
+                              const int32_t* tile_list, const int32_t* tile_count, const float* w0, const float* w1,
+                              const float* w2, int64_t ldw, const uint16_t* wp0, int64_t plane_stride, float* dx,
+                              int64_t lddx, int depi, const float* pre, float p, uint64_t seed, uint32_t site,
+                              float* dws, int64_t dws_bytes, const int32_t* quad_map, int64_t pre_rows, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  bool pair_ok = dy0 && x && dw0 && wws && w0 && dx && M > 0 && K > 0 && nseg >= 1 && nseg <= 3 && nper > 0 &&
+                 lddw == K && wws_bytes > 0 && dws_bytes >= 0 && (nseg < 2 || (dy1 && dw1 && w1)) &&
+                 (nseg < 3 || (dy2 && dw2 && w2)) && depi >= GCT_DEPI_STORE && depi <= GCT_DEPI_MUL_SAVED &&
+                 (!quad_map || M % 4 == 0) && ((depi != GCT_DEPI_GELU_BWD && depi != GCT_DEPI_MUL_SAVED) || pre) &&
+                 p >= 0.f && p < 1.f;
+  if (pair_ok) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;   // a captured graph keeps today's kernels
+    pair_ok = hipStreamIsCapturing(st, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone;
+  }
+  if (pair_ok) {       // the pair runs both problems at once: dX must not overwrite what the weight gradient reads
+    const float* dys[3] = {dy0, dy1, dy2};
+    for (int sgi = 0; sgi < nseg; ++sgi) pair_ok = pair_ok && !ranges_overlap(dx, M, lddx, K, dys[sgi], M, lddy, nper);
+    pair_ok = pair_ok && !ranges_overlap(dx, M, lddx, K, x, M, ldx, K);
+  }
+  if (pair_ok) {
+    const int mode = gemm_mode();
+    const bool al = al16(dy0) && al16(dy1) && al16(dy2) && al16(x) && al16(w0) && al16(w1) && al16(w2);
+    const BwdShape b = {M, nseg, nper, K, lddy, ldx, ldw, lddx, depi, al, wp0 != nullptr, db0 != nullptr, mode};
+    GemmArgs gw = wgrad_args(M, nseg, nper, K, lddy, ldx, wws);
+    gw.a = mkseg(dy0, dy1, dy2);
+    gw.b = mkseg(x, nullptr, nullptr);
+    GemmArgs gd = dgrad_shape_args(b, dx, wp0, plane_stride);
+    gd.a = mkseg(dy0, dy1, dy2);
+    gd.b = mkseg(w0, w1, w2);
+    gd.pre_in = pre;
+    gd.thr = gct_drop_threshold(p); gd.keep_scale = 1.0f / (1.0f - p); gd.rng = gct_rng_make(seed, site);
+    gd.quad_map = quad_map;
+    gd.pre_rows = quad_map ? pre_rows : 0;
+    const BwdPairPlan r = plan_bwd_pair(b, gw, gd, wws_bytes, dws, dws ? dws_bytes : 0);
+    if (r.paired) {
+      if (tile_list && tile_count) { gw.kt_list = tile_list; gw.kt_count = tile_count; }
+      float* bslab = nullptr;
+      if (db0) {
+        int64_t off = (int64_t)gw.nsplit * gw.slab_stride;
+        off = (off + 3) / 4 * 4;
+        bslab = wws + off;                  // [nsplit][Ntot] right behind the weight slabs, as in gct_linear_wgrad
+        gw.bias_slab = bslab;
+      }
+      const bool x3 = mode == GCT_GEMM_BF16X3;
+      const int rc = x3 ? launch_x6_pair<2>(gw, gd, st) : launch_x6_pair<3>(gw, gd, st);
+      if (rc) return rc;
+      if (!x3) g_gemm_launches[1] += 2;     // two GEMM problems, one kernel launch
+      const int64_t Ntot = (int64_t)nseg * nper;
+      if (bslab)
+        return gct_reduce_slabs_seg2(wws, gw.nsplit, gw.slab_stride, dw0, dw1, dw2, (int64_t)nper * K, Ntot * K, bslab,
+                                     Ntot, db0, db1, db2, nper, Ntot, st);
+      return gct_reduce_slabs_seg(wws, gw.nsplit, gw.slab_stride, dw0, dw1, dw2, (int64_t)nper * K, Ntot * K, st);
+    }
+  }
+  // not paired: today's two calls, unchanged (they check their own arguments)
+  int rc = gct_linear_wgrad(dy0, dy1, dy2, lddy, M, nseg, nper, x, ldx, K, dw0, dw1, dw2, lddw, db0, db1, db2, wws,
+                            tile_list, tile_count, stream);
+  if (rc) return rc;
+  return gct_linear_dgrad(dy0, dy1, dy2, lddy, M, nseg, nper, w0, w1, w2, ldw, wp0, plane_stride, K, dx, lddx, depi,
+                          pre, p, seed, site, dws, dws_bytes, quad_map, pre_rows, stream);
 }

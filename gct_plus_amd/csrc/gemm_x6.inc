@@ -139,9 +139,11 @@ typedef float x6_f32x4 __attribute__((ext_vector_type(4)));
 // WGRAD dY [K'][M]  natural, transposed reads     X fp32 [K'][N]    natural, split on the fly, transposed reads
 // NP = pieces per operand element: 3 (bf16x6, six products) or 2 (bf16x3, three products; the LDS layout and the
 // stage size stay those of NP = 3, the third plane slots are left unused)
-template <int MODE, int NP = 3>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void
-gemm_x6_kernel(const GemmArgs g) {
+// The body of one workgroup: block `bid` of a (sub-)grid of `nblk` blocks that covers the problem g.  The XCD remap is
+// applied within that sub-grid, so the blocks that share an operand panel stay on one XCD whether the problem has the
+// launch to itself (gemm_x6_kernel) or shares it (gemm_x6_bwd_pair_kernel).
+template <int MODE, int NP>
+__device__ __forceinline__ void gemm_x6_body(const GemmArgs& g, const unsigned bid, const unsigned nblk) {
   static_assert(NP == 2 || NP == 3, "bf16x3 or bf16x6");
   extern __shared__ __attribute__((aligned(16))) unsigned char xlds[];
   constexpr bool A_TR = MODE == X6_WGRAD, B_TR = MODE != X6_FWD, B_PL = MODE != X6_WGRAD;
@@ -152,7 +154,7 @@ gemm_x6_kernel(const GemmArgs g) {
   const unsigned tiles_n = (unsigned)((g.N + XBN - 1) / XBN);
   const unsigned tiles_m = (unsigned)((g.M + XBM - 1) / XBM);
   const unsigned per_split = tiles_m * tiles_n;
-  const unsigned lid = gct_xcd_remap(blockIdx.x, gridDim.x);
+  const unsigned lid = gct_xcd_remap(bid, nblk);
   const unsigned z = lid / per_split, rest = lid - z * per_split;
   const int64_t m0 = (int64_t)(rest / tiles_n) * XBM, n0 = (int64_t)(rest % tiles_n) * XBN;
   const int64_t kbeg = (int64_t)z * g.ksplit;
@@ -616,6 +618,23 @@ gemm_x6_kernel(const GemmArgs g) {
     for (int i = 0; i < 8; ++i) g.stamps[((size_t)blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + i] = seg[i];
   }
 #endif
+}
+
+template <int MODE, int NP = 3>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void
+gemm_x6_kernel(const GemmArgs g) {
+  gemm_x6_body<MODE, NP>(g, blockIdx.x, gridDim.x);
+}
+
+// One Linear's backward as ONE grid: blocks [0, n_wgrad_blocks) are the weight-gradient workgroups of gw (the longer
+// ones, so they start first; they also pull dY through the L2 before the dgrad tiles read it), the rest the dgrad tiles
+// of gd.  The branch is block-uniform and taken once; each side runs exactly the code of its own kernel (same MFMA and
+// accumulation order), so dX, db and -- at equal split counts -- dW are bit-identical to the separate launches.
+template <int NP = 3>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void
+gemm_x6_bwd_pair_kernel(const GemmArgs gw, const GemmArgs gd, const unsigned n_wgrad_blocks) {
+  if (blockIdx.x < n_wgrad_blocks) gemm_x6_body<X6_WGRAD, NP>(gw, blockIdx.x, n_wgrad_blocks);
+  else gemm_x6_body<X6_DGRAD, NP>(gd, blockIdx.x - n_wgrad_blocks, gridDim.x - n_wgrad_blocks);
 }
 
 // "this launch can take gemm_x6_kernel<MODE>" -- everything else stays on the fp32-MFMA kernels

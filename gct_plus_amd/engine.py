@@ -413,9 +413,8 @@ def mha_bwd(run: Run, m, sv: MhaSaved, dy, G: GradSink, dxq_out, depi_q, dxkv_ou
         g = gdrop
     else:
         g = ops.dropout_bwd(dy, run.p, run.seed, sv.site_o, live=live) if (sv.fused and run.p > 0) else dy
-    ops.linear_wgrad([g], d, o_in, [G(m.out.weight)], [G(m.out.bias)], kt=kt)
     do = _empty(Mq, d, dy) if live is None else live.empty(d)
-    ops.linear_dgrad([g], d, Mq, [m.out.weight], do)
+    ops.linear_bwd([g], d, o_in, [m.out.weight], [G(m.out.weight)], [G(m.out.bias)], do, kt=kt, M=Mq)
     if sv.kvb is None:  # self-attention: fused [q|k|v]
         dqkv = new(3 * d)
         fwdc = live is not None and live.fwd             # q | k | v and o are compact too: address K / V like dK / dV
@@ -424,12 +423,9 @@ def mha_bwd(run: Run, m, sv: MhaSaved, dy, G: GradSink, dxq_out, depi_q, dxkv_ou
                      run.seed, sv.site_p, live=live, kv_compact=live is not None and not fwdc,
                      keys=live if fwdc else None)
         segs = [dqkv, dqkv[:, d:], dqkv[:, 2 * d:]]
-        ops.linear_wgrad(segs, 3 * d, xq_in,
-                         [G(m.q_linear.weight), G(m.k_linear.weight), G(m.v_linear.weight)],
-                         [G(m.q_linear.bias), G(m.k_linear.bias), G(m.v_linear.bias)], kt=kt)
-        ops.linear_dgrad(segs, 3 * d, Mq,
-                         [m.q_linear.weight, m.k_linear.weight, m.v_linear.weight], dxq_out,
-                         depi=depi_q)
+        ops.linear_bwd(segs, 3 * d, xq_in, [m.q_linear.weight, m.k_linear.weight, m.v_linear.weight],
+                       [G(m.q_linear.weight), G(m.k_linear.weight), G(m.v_linear.weight)],
+                       [G(m.q_linear.bias), G(m.k_linear.bias), G(m.v_linear.bias)], dxq_out, depi=depi_q, kt=kt, M=Mq)
     else:
         dq = new(d)
         if keys is None:
@@ -438,18 +434,18 @@ def mha_bwd(run: Run, m, sv: MhaSaved, dy, G: GradSink, dxq_out, depi_q, dxkv_ou
             dkv = keys.empty_zero_gaps(2 * d)
         ops.attn_bwd(sv.qb, sv.kvb, sv.kvb[:, d:], d, 2 * d, 2 * d, sv.mask_u8, sv.o, do, sv.lse, dq, dkv, dkv[:, d:],
                      d, 2 * d, 2 * d, B, H, Lq, Lk, dk, run.p, run.seed, sv.site_p, live=live, keys=keys)
-        ops.linear_wgrad([dq], d, xq_in, [G(m.q_linear.weight)], [G(m.q_linear.bias)], kt=kt)   # query rows
-        ops.linear_wgrad([dkv, dkv[:, d:]], 2 * d, sv.xkv,
-                         [G(m.k_linear.weight), G(m.v_linear.weight)],
-                         [G(m.k_linear.bias), G(m.v_linear.bias)])
-        ops.linear_dgrad([dq], d, Mq, [m.q_linear.weight], dxq_out, depi=depi_q)
+        ops.linear_bwd([dq], d, xq_in, [m.q_linear.weight], [G(m.q_linear.weight)], [G(m.q_linear.bias)], dxq_out,
+                       depi=depi_q, kt=kt, M=Mq)                                          # query rows
+        kv_w = [m.k_linear.weight, m.v_linear.weight]
+        kv_g = ([G(m.k_linear.weight), G(m.v_linear.weight)], [G(m.k_linear.bias), G(m.v_linear.bias)])
         if sv.self_split:    # K | V came from the visible rows of xq itself: their input gradient goes back into d(xq)
             dxk = keys.empty(d)
-            ops.linear_dgrad([dkv, dkv[:, d:]], 2 * d, Mk, [m.k_linear.weight, m.v_linear.weight], dxk)
+            ops.linear_bwd([dkv, dkv[:, d:]], 2 * d, sv.xkv, kv_w, *kv_g, dxk, M=Mk)
             keys.scatter_add(dxk, dxq_out)
         elif dxkv_out is not None:
-            ops.linear_dgrad([dkv, dkv[:, d:]], 2 * d, Mk, [m.k_linear.weight, m.v_linear.weight],
-                             dxkv_out, depi=depi_kv)
+            ops.linear_bwd([dkv, dkv[:, d:]], 2 * d, sv.xkv, kv_w, *kv_g, dxkv_out, depi=depi_kv, M=Mk)
+        else:
+            ops.linear_wgrad([dkv, dkv[:, d:]], 2 * d, sv.xkv, *kv_g)
 
 
 # ------------------------------------------------------------------------------------- FFN
@@ -485,12 +481,12 @@ def ffn_bwd(run: Run, ff, sv: FfnSaved, dy, G: GradSink, dx_out, depi, live=None
         g = gdrop
     else:
         g = ops.dropout_bwd(dy, run.p, run.seed, sv.site_o, live=live) if (sv.fused and run.p > 0) else dy
-    ops.linear_wgrad([g], d, hdn, [G(ff.linear_2.weight)], [G(ff.linear_2.bias)], kt=kt)
     dpre = _empty(M, dff, dy) if live is None else live.empty(dff)
-    ops.linear_dgrad([g], d, M, [ff.linear_2.weight], dpre, depi=ops.DEPI_MUL_SAVED, pre=gelu_d,
-                     p=run.p, seed=run.seed, site=sv.site_h, live=live, pre_full=live is not None and not live.fwd)
-    ops.linear_wgrad([dpre], dff, x, [G(ff.linear_1.weight)], [G(ff.linear_1.bias)], kt=kt)
-    ops.linear_dgrad([dpre], dff, M, [ff.linear_1.weight], dx_out, depi=depi)
+    ops.linear_bwd([g], d, hdn, [ff.linear_2.weight], [G(ff.linear_2.weight)], [G(ff.linear_2.bias)], dpre,
+                   depi=ops.DEPI_MUL_SAVED, pre=gelu_d, p=run.p, seed=run.seed, site=sv.site_h, kt=kt, live=live,
+                   pre_full=live is not None and not live.fwd, M=M)
+    ops.linear_bwd([dpre], dff, x, [ff.linear_1.weight], [G(ff.linear_1.weight)], [G(ff.linear_1.bias)], dx_out,
+                   depi=depi, kt=kt, M=M)
 
 
 # ---------------------------------------------------------------------------------- layers
@@ -896,12 +892,13 @@ class LinearFn(torch.autograd.Function):
         dy2 = _f32c(dy).reshape(-1, N)
         G = GradSink()
         wp, bp = ctx.params
-        ops.linear_wgrad([dy2], N, x2, [G(wp)], [G(bp) if bp is not None else None])
         dx = None
         if ctx.needs_input_grad[0]:
             dx = _empty(x2.shape[0], x2.shape[1], x2)
-            ops.linear_dgrad([dy2], N, x2.shape[0], [w], dx)
+            ops.linear_bwd([dy2], N, x2, [w], [G(wp)], [G(bp) if bp is not None else None], dx)
             dx = dx.view(ctx.shp)
+        else:
+            ops.linear_wgrad([dy2], N, x2, [G(wp)], [G(bp) if bp is not None else None])
         ops.join_side()
         return dx, G.out.get(wp), G.out.get(bp) if bp is not None else None
 

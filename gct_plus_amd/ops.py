@@ -654,6 +654,57 @@ def linear_wgrad(dys: Sequence[torch.Tensor], lddy: int, x2d, dws: Sequence[torc
         _PENDING[t.untyped_storage().data_ptr()] = done
 
 
+# One Linear's backward as one call (gct_linear_bwd): where both problems take the 128 x 256 bf16 tile kernel the library
+# runs them as ONE launch whose weight-gradient split is chosen for the shared grid (csrc/gemm.hip plan_bwd_pair).  Tests
+# flip this attribute to run the same model both ways (and restore it); there is no environment knob.
+PAIR_BWD = True
+
+
+def linear_bwd_route(M, nseg, nper, K, lddy, ldx, ldw, lddx, depi=DEPI_STORE, aligned16=True, have_planes=True,
+                     want_bias=True, mode=None, ws_bytes=None):
+    """(paired, nsplit, rows per split, bias fused, wgrad blocks, dgrad blocks, modelled pair time, modelled time of the
+    two separate calls) of gct_linear_bwd for a shape (gct_linear_bwd_route: no launch; times in dgrad K-tile times)."""
+    import ctypes
+    out = (ctypes.c_int64 * 8)()
+    if ws_bytes is None:
+        ws_bytes = _ws_need("gct_linear_bwd_ws_bytes", M, nseg * nper, K)
+    check(_L().gct_linear_bwd_route(M, nseg, nper, K, lddy, ldx, ldw, lddx, int(depi), int(aligned16), int(have_planes),
+                                    int(want_bias), gemm_get_mode() if mode is None else int(mode), int(ws_bytes),
+                                    ctypes.addressof(out)), "gct_linear_bwd_route")
+    v = [int(t) for t in out]
+    return (v[0], v[1], v[2], v[3], v[4], v[5], v[6] / 1000.0, v[7] / 1000.0)
+
+
+def linear_bwd(dys: Sequence[torch.Tensor], lddy: int, x2d, ws_: Sequence[torch.Tensor], dws: Sequence[torch.Tensor],
+               dbs: Sequence[Optional[torch.Tensor]], dx, depi=DEPI_STORE, pre=None, p=0.0, seed=0, site=0, kt=None,
+               live=None, pre_full=False, M=None):
+    """linear_wgrad(dys, lddy, x2d, dws, dbs, kt) and linear_dgrad(dys, lddy, M, ws_, dx, depi, ...) of the same dY."""
+    M = x2d.shape[0] if M is None else M
+    if not PAIR_BWD or SIDE_ENABLED or M != x2d.shape[0] or torch.cuda.is_current_stream_capturing():
+        linear_wgrad(dys, lddy, x2d, dws, dbs, kt=kt)
+        linear_dgrad(dys, lddy, M, ws_, dx, depi=depi, pre=pre, p=p, seed=seed, site=site, live=live, pre_full=pre_full)
+        return
+    K = x2d.shape[1]
+    nper, nseg = dws[0].shape[0], len(dws)
+    d, dw, db, w = _seg3(dys), _seg3(dws), _seg3(dbs), _seg3(ws_)
+    _wait_pending(dx)
+    wneed = _ws_need("gct_linear_bwd_ws_bytes", M, nseg * nper, K)   # the size the plan is made for (linear_bwd_route's)
+    wws = kept_workspace(wneed, x2d.device)
+    need = _ws_need("gct_linear_dgrad_ws_bytes", M, nper * nseg, K)
+    wsb = workspace(need, dx.device) if need > 256 else None
+    wp, pstride = _plane_ptr(ws_)
+    with _Timed("gemm_bwd", 4.0 * M * K * nper * nseg):
+        check(_L().gct_linear_bwd(d[0], d[1], d[2], lddy, M, nseg, nper, _p(x2d), x2d.stride(0), K,
+                                  dw[0], dw[1], dw[2], K, db[0], db[1], db[2], _p(wws), wneed,
+                                  _p(kt[0]) if kt else None, _p(kt[1]) if kt else None,
+                                  w[0], w[1], w[2], ws_[0].stride(0), wp, pstride,
+                                  _p(dx), dx.stride(0), depi, _p(pre), p, seed, site,
+                                  _p(wsb), 0 if wsb is None else wsb.numel() * 4,
+                                  None if live is None else _p(live.quad_list),
+                                  pre.shape[0] if (live is not None and pre is not None and pre_full) else 0, _st()),
+              "gct_linear_bwd")
+
+
 def dropout_bwd(dout2d, p, seed, site, out=None, live=None):
     rows, cols = dout2d.shape
     if live is not None:

@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 27
+#define GCT_ABI_VERSION 28
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -177,6 +177,38 @@ int gct_linear_wgrad(const float* dy0, const float* dy1, const float* dy2, int64
 #define GCT_WGRAD_BF16_TILES 3
 int gct_wgrad_route(int64_t M, int nseg, int nper, int K, int64_t lddy, int64_t ldx, int aligned16, int want_bias,
                     int mode, int64_t* out4);
+
+/* One nn.Linear's backward: gct_linear_wgrad and gct_linear_dgrad of the same dY in one call (ABI 28).  The arguments are
+ * those of the two calls (dy*, lddy, M, nseg, nper once); wws / wws_bytes is the weight-gradient workspace
+ * (>= gct_linear_bwd_ws_bytes(M, nseg*nper, K)), dws / dws_bytes the dgrad's (nullable, as for gct_linear_dgrad).
+ * When both problems take the 128 x 256 bf16 tile kernel on their own, the stream is not being captured, dx overlaps
+ * neither dy* nor x, and the planner's model of the shared grid is shorter than that of the two launches, both run as
+ * ONE kernel launch (gemm_x6_bwd_pair_kernel: weight-gradient workgroups first, then the dgrad tiles; no dgrad tail
+ * launch, no fix-up).  dx and db* are then bit-identical to the separate calls; dw* too whenever the split
+ * (gct_linear_bwd_route's out8[1], out8[2]) equals gct_wgrad_route's, and otherwise differs by the fp32 summation order
+ * over the slabs only.  In every other case the call IS the two separate calls, in the order wgrad, dgrad.
+ * The slab reduction is issued (or deferred, gct_reduce_defer_begin) exactly as by gct_linear_wgrad. */
+int gct_linear_bwd(const float* dy0, const float* dy1, const float* dy2, int64_t lddy, int64_t M, int nseg, int nper,
+                   const float* x, int64_t ldx, int K,
+                   float* dw0, float* dw1, float* dw2, int64_t lddw, float* db0, float* db1, float* db2,
+                   float* wws, int64_t wws_bytes, const int32_t* tile_list, const int32_t* tile_count,
+                   const float* w0, const float* w1, const float* w2, int64_t ldw,
+                   const uint16_t* wp0, int64_t plane_stride,
+                   float* dx, int64_t lddx, int depi, const float* pre, float p, uint64_t seed, uint32_t site,
+                   float* dws, int64_t dws_bytes, const int32_t* quad_map, int64_t pre_rows, void* stream);
+int64_t gct_linear_bwd_ws_bytes(int64_t M, int64_t Ntot, int64_t K);
+/* The plan of a gct_linear_bwd call for a shape (no launch, no device access; stream capture and overlapping buffers,
+ * which also keep a call from being paired, are not shapes and not reported here):
+ *   out8[0] 1: one paired launch; 0: the two separate calls;
+ *   out8[1] nsplit, out8[2] rows per split (a multiple of 32) of the weight gradient, as in gct_wgrad_route;
+ *   out8[3] bias slabs written by the GEMM kernel;
+ *   out8[4], out8[5] weight-gradient and dgrad blocks of the paired grid (0 when not paired);
+ *   out8[6], out8[7] modelled duration of the paired launch and of the two separate calls, in 1/1000 of the time of
+ *           one 128 x 256 x 32 dgrad K-tile (0: not modelled -- a problem is not on the bf16 tile route).
+ * aligned16: every buffer is 16-byte aligned; have_planes: wp0 != NULL; ws_bytes: wws_bytes of the call. */
+int gct_linear_bwd_route(int64_t M, int nseg, int nper, int K, int64_t lddy, int64_t ldx, int64_t ldw, int64_t lddx,
+                         int depi, int aligned16, int have_planes, int want_bias, int mode, int64_t ws_bytes,
+                         int64_t* out8);
 
 /* ---- GEMM arithmetic mode and pre-split weights ------------------------------------------
  * The nn.Linear GEMMs (Model/sublayers.py:54-59,64-66,70,81-88) run in one of two modes with

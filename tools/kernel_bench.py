@@ -81,6 +81,53 @@ def gemm_suite(reps, only=None, modes=None, rounds=3):
                                                               for m in modes[1:]), flush=True)
 
 
+def bwdpair_suite(reps, rounds=5):
+    """One Linear's backward as gct_linear_bwd's paired launch against the two separate calls (ops.PAIR_BWD off), the two
+    ways alternated call by call in one process: the five Linear shapes of a layer at the headline's dense and compact
+    row counts, with the dgrad epilogues the training step uses.  Also the separate wgrad / dgrad times (the planner's
+    model constants are fitted to them) and the planner's own figures."""
+    dev = "cuda"
+    shapes = [("out", 512, 512, 1, ops.DEPI_STORE), ("qkv", 512, 512, 3, ops.DEPI_ACCUM), ("q", 512, 512, 1, ops.DEPI_ACCUM),
+              ("kv", 512, 512, 2, ops.DEPI_STORE), ("ffn2", 2048, 512, 1, ops.DEPI_MUL_SAVED),
+              ("ffn1", 512, 2048, 1, ops.DEPI_ACCUM)]
+    keep = ops.PAIR_BWD
+    for M in (40960, 18016, 10432):
+        for name, K, nper, nseg, depi in shapes:
+            N = nper * nseg
+            x = torch.randn(M, K, device=dev)
+            wflat = torch.randn(N * K, device=dev) * K ** -0.5
+            ws = [wflat[s * nper * K:(s + 1) * nper * K].view(nper, K) for s in range(nseg)]
+            ops.register_planes(wflat, ops.split_planes(wflat))
+            dy = torch.randn(M, N, device=dev)
+            dys = [dy[:, s * nper:] for s in range(nseg)]
+            dx = torch.zeros(M, K, device=dev)
+            pre = torch.randn(M, K, device=dev) if depi == ops.DEPI_MUL_SAVED else None
+            dws = [torch.empty(nper, K, device=dev) for _ in range(nseg)]
+            dbs = [torch.empty(nper, device=dev) for _ in range(nseg)]
+            kw = dict(depi=depi, pre=pre, p=0.1, seed=3, site=1)
+
+            def both(pair):
+                ops.PAIR_BWD = pair
+                ops.linear_bwd(dys, N, x, ws, dws, dbs, dx, **kw)
+
+            route = ops.linear_bwd_route(M, nseg, nper, K, N, K, K, K, depi)
+            sep_route = ops.wgrad_route(M, nseg, nper, K, N, K)
+            per = {False: [], True: []}
+            for _ in range(rounds):
+                for pair in (False, True):
+                    per[pair].append(timeit(lambda: both(pair), reps)[0])
+            tw = timeit(lambda: ops.linear_wgrad(dys, N, x, dws, dbs), reps)[0]
+            td = timeit(lambda: ops.linear_dgrad(dys, N, M, ws, dx, **kw), reps)[0]
+            ops.PAIR_BWD = keep
+            sep, pr = sorted(per[False]), sorted(per[True])
+            ms, mp = sep[rounds // 2], pr[rounds // 2]
+            print(f"bwdpair {name:5s} M={M} K={K} N={N} depi={depi}: separate {ms*1e6:7.1f} us ({sep[0]*1e6:.1f}..{sep[-1]*1e6:.1f})  "
+                  f"linear_bwd {mp*1e6:7.1f} us ({pr[0]*1e6:.1f}..{pr[-1]*1e6:.1f})  ratio {mp/ms:.3f}  "
+                  f"[wgrad alone {tw*1e6:.1f} us s={sep_route[1]}, dgrad alone {td*1e6:.1f} us]  "
+                  f"plan paired={route[0]} s={route[1]} rows={route[2]} blocks={route[4]}+{route[5]} "
+                  f"model pair {route[6]:.1f} separate {route[7]:.1f} K-tiles", flush=True)
+
+
 def decgemm_suite(reps):
     """Forward GEMMs of a KV-cached decode step (n rows) and of small training batches."""
     dev = "cuda"
@@ -203,6 +250,8 @@ if __name__ == "__main__":
         gemm_suite(a.reps, a.only.split(",") if a.only else None, gmodes or None)
     if "decgemm" in a.suite:
         decgemm_suite(a.reps)
+    if "bwdpair" in a.suite.split(","):
+        bwdpair_suite(a.reps)
     if "epi" in a.suite.split(","):
         epi_suite(a.reps)
     if "attn" in a.suite:
