@@ -32,7 +32,9 @@ Fine-tuning on what was sampled: `return_rows=True` on `decode`, `sample_smiles`
 `DecodedRows` -- the latents, mask, conditions and prefix lengths the decode consumed and the token rows it produced --
 and `logp(*rows)` is `score(*rows)` WITH a gradient (decode.sequence_logp), on the device: the policy term of
 Train/finetune.reinforce_step.  `policy_terms(*rows, prior=)` adds the policy's entropy and its KL divergence from a
-frozen prior (decode.sequence_policy), the regularisers of that step.  Not with beam search.
+frozen prior (decode.sequence_policy), the regularisers of that step.  `ppo_terms(*rows, old_token_logp=, advantage=,
+clip=)` is PPO's clipped surrogate against the log-probabilities the rows were sampled with (decode.sequence_ppo), the
+objective of Train/finetune.ppo_update's several updates per scored batch.  Not with beam search.
 
 `well_formed=True` (optional): greedy / multinomial decodes are constrained by decode.SmilesGrammar built from the target
 vocabulary -- every returned string has balanced branches, paired ring-closure numbers, no dangling bond, and ended
@@ -61,9 +63,9 @@ from .. import ops
 from ..Model.modules import get_src_mask
 from ..data import Vocab, tokenize
 from .mol_interpolation import Interpolation, interior_alphas, interp_plan, lerp, noise_ladder, run_ladder
-from ..decode import (BEAM_ALPHA, KVDecoder, PolicyTerms, SmilesGrammar, check_beam_size, check_sample_filter,
+from ..decode import (BEAM_ALPHA, KVDecoder, PolicyTerms, PpoTerms, SmilesGrammar, check_beam_size, check_sample_filter,
                       check_stream_model, check_stream_rows, generated_tokens, score_tokens, sequence_logp,
-                      sequence_policy)
+                      sequence_policy, sequence_ppo)
 
 
 class Scores(NamedTuple):
@@ -309,6 +311,18 @@ class Sampling:
         dconds = None if dconds is None else dconds.to(self.device)
         return sequence_policy(self.model, zs, src_mask, dconds, ys, prefix_lens=prefix_lens, pad_id=self.pad_id,
                                prior=prior)
+
+    def ppo_terms(self, zs, ys, src_mask, dconds=None, prefix_lens=None, *, old_token_logp, advantage, clip=0.2,
+                  prior=None, entropy=False) -> PpoTerms:
+        """PPO's clipped surrogate of decoded rows (decode.sequence_ppo), from ONE forward: the arguments of `logp` -- so
+        `ppo_terms(*rows, old_token_logp=, advantage=)` takes a DecodedRows -- plus old_token_logp [n, W], the
+        log-probabilities the rows were sampled with (`score(*rows).token_logp`, or `logp(*rows).token_logp` under
+        no_grad, BEFORE the first update), one advantage per row, and clip: a number or (clip_lo, clip_hi).  prior /
+        entropy add policy_terms' terms.  PpoTerms on the device; surrogate and token_surrogate carry the gradient."""
+        zs, src_mask = zs.to(self.device), src_mask.to(self.device)
+        dconds = None if dconds is None else dconds.to(self.device)
+        return sequence_ppo(self.model, zs, src_mask, dconds, ys, old_token_logp, advantage, clip=clip,
+                            prefix_lens=prefix_lens, pad_id=self.pad_id, prior=prior, entropy=entropy)
 
     @torch.no_grad()
     def score(self, zs, ys, src_mask, dconds=None, prefix_lens=None) -> Scores:

@@ -16,12 +16,22 @@ logp takes):
 
 `regularised_loss` is the loss of that step; REINVENT-style augmented likelihoods are functions of
 `sampler.policy_terms(*rows, prior=prior)`'s logp and prior_logp.  Reward-weighted likelihood, hill-climbing on the best
-k of a batch and any other per-molecule loss are functions of `sampler.logp(*rows).logp` in the same way.  Not covered
-(DESIGN 4): FlatDataParallel fine-tuning, importance ratios / PPO clipping, beam rows, per-step entropy during generate,
-a gradient into the prior."""
+k of a batch and any other per-molecule loss are functions of `sampler.logp(*rows).logp` in the same way.
+
+One update per scored batch throws the batch away while the reward is the expensive part.  `ppo_update` takes several
+updates on it -- PPO's clipped surrogate holds each token's probability ratio against the sampling-time policy inside a
+trust region (decode.sequence_ppo -> gct_seq_ppo / gct_seq_ppo_bwd; `advantages` and `ppo_loss` are its pieces):
+
+    history = ppo_update(sampler, optimizer, out[-1], reward, epochs=4, clip=0.2)
+
+Not covered: FlatDataParallel fine-tuning, value networks / GAE (the advantage is per molecule),
+sequence-level ratios (functions of logp and the old logp in torch), beam rows, per-step entropy during generate, a
+gradient into the prior or into old_token_logp."""
 import copy
 
 import torch
+
+from ..decode import clip_pair
 
 
 def reinforce_loss(logp, reward, baseline="mean"):
@@ -88,7 +98,8 @@ def reinforce_step(sampler, optimizer, rows, reward, baseline="mean", entropy_co
 
     The model runs in training mode, so its dropout is live in this forward: the logp of the step is not the eval-mode
     number `with_logp` reported for the same rows (build the model with dropout 0 where the two must agree).  The prior
-    stays in the mode it is in: eval().
+    stays in the mode it is in: eval().  ppo_update, whose objective is a ratio against a deterministic old policy,
+    runs the model in eval() instead (its train_mode flag).
 
     What keeps the encoder still: the rows' latents are inputs, so the graph holds the decoder and model.out only and
     the encoder's parameters get NO gradient.  A FRESH optimizer therefore leaves them bit-unchanged (FusedAdam and
@@ -129,3 +140,131 @@ def reinforce_step(sampler, optimizer, rows, reward, baseline="mean", entropy_co
         if prior is not None:
             out["mean_kl"], out["mean_prior_logp"] = stats[5], stats[6]
     return out
+
+
+def advantages(reward, baseline="mean", normalize=False):
+    """One advantage per sequence: reward - b with reinforce_loss's baseline rule ("mean": the batch mean of the reward,
+    a float or a tensor broadcast against reward: that value, None: 0), fp32 [n] on the device of reward, no graph.
+    normalize=True divides by (the batch standard deviation of the advantage, the population one, + 1e-8)."""
+    reward = torch.as_tensor(reward, dtype=torch.float32).detach().view(-1)
+    if baseline is None:
+        adv = reward.clone()
+    elif isinstance(baseline, str):
+        if baseline != "mean":
+            raise ValueError(f"baseline must be 'mean', a number, a tensor or None, got {baseline!r}")
+        adv = reward - reward.mean()
+    else:
+        b = torch.as_tensor(baseline, dtype=torch.float32).to(reward.device).detach()
+        if b.numel() not in (1, reward.numel()):
+            raise ValueError(f"baseline of shape {list(b.shape)} against {reward.numel()} rewards")
+        adv = reward - b.reshape(-1)
+    if normalize:
+        adv = adv / (adv.std(unbiased=False) + 1e-8)
+    return adv
+
+
+def ppo_loss(terms, entropy_coef=0.0, kl_coef=0.0):
+    """(-terms.surrogate.sum() + kl_coef * terms.kl.sum() - entropy_coef * terms.entropy.sum()) / n over the n sequences
+    of a PpoTerms (decode.sequence_ppo): minus PPO's clipped surrogate, plus regularised_loss's penalty and bonus.  A
+    coefficient of 0 leaves its term out (terms.kl / terms.entropy may then be None); kl_coef != 0 needs terms computed
+    with a prior, entropy_coef != 0 terms with the entropy: ValueError otherwise."""
+    total = -terms.surrogate.sum()
+    if kl_coef != 0:
+        if terms.kl is None:
+            raise ValueError("ppo_loss: kl_coef needs terms computed with a prior")
+        total = total + kl_coef * terms.kl.sum()
+    if entropy_coef != 0:
+        if terms.entropy is None:
+            raise ValueError("ppo_loss: entropy_coef needs terms computed with the entropy")
+        total = total - entropy_coef * terms.entropy.sum()
+    return total / terms.surrogate.numel()
+
+
+def _row_slice(rows, lo, hi):
+    """Rows lo .. hi - 1 of every per-row element of an argument tuple of Sampling.logp (None stays None)."""
+    return tuple(None if a is None else a[lo:hi] for a in rows)
+
+
+def ppo_update(sampler, optimizer, rows, reward, epochs=4, clip=0.2, baseline="mean", normalize=False,
+               old_token_logp=None, minibatch=None, target_kl=None, entropy_coef=0.0, kl_coef=0.0, prior=None,
+               train_mode=False):
+    """Several policy updates of sampler.model on ONE scored batch: `epochs` passes over the decoded rows `rows` (a
+    DecodedRows, or any argument tuple of Sampling.logp) with one reward per row, each pass minimising ppo_loss --
+    PPO's clipped surrogate of every scored token's probability ratio against the sampling-time policy, which holds the
+    later passes inside a trust region around the policy that drew the rows.  The expensive parts of a round, the decode
+    and the reward, are paid once.
+
+    advantage = advantages(reward, baseline, normalize), once.  old_token_logp [n, W]: the log-probabilities the rows
+    were sampled with; None takes them from ONE sampler.logp forward under no_grad before the first update, in the mode
+    the updates run in -- the first update's ratios are then exactly 1 and its step is reinforce_step's.  A caller may
+    pass a table of its own, `sampler.score(*rows).token_logp` for example.  clip: a number e (ratios are held in
+    [1 - e, 1 + e]) or a pair (clip_lo, clip_hi).  minibatch=m splits the rows, in order, into ceil(n / m) updates per
+    epoch, each normalised by its own row count.  target_kl: no further epoch is started once an epoch's approx_kl (as
+    reported below) exceeded it.  entropy_coef / kl_coef / prior as in reinforce_step; kl_coef != 0 without a prior:
+    ValueError before any device work.
+
+    The model runs in eval() unless train_mode=True: with live dropout the ratio against a deterministic old policy is
+    noise around 1 that the clip then cuts at random -- nobody wants that; reinforce_step, which has no ratio, trains in
+    train() (its note on dropout).  train_mode=True is for dropout-0 models and for reproducing reinforce_step.  The
+    model is always left in eval().  reinforce_step's notes on the encoder (no gradient: the latents are inputs), on
+    optimizers with loaded moments and on sampling after an update hold here unchanged.
+
+    Returns a list with one dict per epoch run, Python numbers read in ONE transfer per epoch: loss (the row-weighted
+    mean of the minibatches' losses), mean_surrogate (per sequence), clip_fraction (clipped tokens / scored tokens),
+    approx_kl (the k3 estimate of KL(old || new) per scored token, each minibatch measured at its own forward), tokens;
+    with entropy_coef != 0 mean_entropy, with a prior mean_kl (both per scored token) and mean_prior_logp (per
+    sequence)."""
+    model = sampler.model
+    if kl_coef != 0 and prior is None:
+        raise ValueError("ppo_update: kl_coef needs a prior (frozen_prior of the pretrained model)")
+    if isinstance(epochs, bool) or not isinstance(epochs, int) or epochs < 1:
+        raise ValueError(f"epochs must be an int >= 1, got {epochs!r}")
+    if minibatch is not None and (isinstance(minibatch, bool) or not isinstance(minibatch, int) or minibatch < 1):
+        raise ValueError(f"minibatch must be an int >= 1 or None, got {minibatch!r}")
+    clip = clip_pair(clip)
+    rows = tuple(rows)
+    n = rows[1].shape[0]
+    reward = torch.as_tensor(reward, dtype=torch.float32).view(-1)
+    if reward.numel() != n:
+        raise ValueError(f"{reward.numel()} rewards for {n} sequences")
+    m = n if minibatch is None else min(int(minibatch), n)
+    with_entropy = entropy_coef != 0
+    history = []
+    model.train(bool(train_mode))
+    try:
+        adv = advantages(reward.to(sampler.device), baseline, normalize).cpu()   # the device's arithmetic, as
+        if old_token_logp is None:                                               # reinforce_loss's; checked on the host
+            with torch.no_grad():
+                old_token_logp = sampler.logp(*rows).token_logp
+        for _ in range(epochs):
+            if target_kl is not None and history and history[-1]["approx_kl"] > target_kl:
+                break
+            sums = None
+            for lo in range(0, n, m):
+                hi = min(n, lo + m)
+                terms = sampler.ppo_terms(*_row_slice(rows, lo, hi), old_token_logp=old_token_logp[lo:hi],
+                                          advantage=adv[lo:hi], clip=clip, prior=prior, entropy=with_entropy)
+                optimizer.zero_grad(set_to_none=True)
+                loss = ppo_loss(terms, entropy_coef, kl_coef)
+                loss.backward()
+                optimizer.step()
+                part = [loss.detach().float() * (hi - lo), terms.surrogate.detach().sum(),
+                        terms.clipped.sum().float(), terms.approx_kl.sum(), terms.tokens.sum().float()]
+                if with_entropy:
+                    part.append(terms.entropy.detach().sum())
+                if prior is not None:
+                    part += [terms.kl.detach().sum(), terms.prior_logp.sum()]
+                part = torch.stack(part)
+                sums = part if sums is None else sums + part
+            s = sums.cpu().tolist()
+            tokens = s[4]
+            out = dict(loss=s[0] / n, mean_surrogate=s[1] / n, clip_fraction=s[2] / tokens, approx_kl=s[3] / tokens,
+                       tokens=int(tokens))
+            if with_entropy:
+                out["mean_entropy"] = s[5] / tokens
+            if prior is not None:
+                out["mean_kl"], out["mean_prior_logp"] = s[-2] / tokens, s[-1] / n
+            history.append(out)
+    finally:
+        model.eval()
+    return history

@@ -10,6 +10,10 @@
 // gct_seq_dist / gct_seq_dist_bwd (decode.py dist_reference / dist_grad_reference state the rules) are the entropy of
 // the next-token distribution and its KL divergence from a second model's, per scored token and per sequence, and their
 // gradient with respect to the first model's logits: the same layouts, around wave_row_dist.
+// gct_seq_ppo / gct_seq_ppo_bwd (decode.py ppo_reference / ppo_grad_reference state the rules) are PPO's clipped
+// surrogate of each scored token's probability ratio against the log-probabilities it was sampled with, per token and
+// per sequence, and its gradient with respect to the logits: the same layouts again, wave_token_logp and ce_grad_write
+// around ppo_token.
 #include "common.h"
 #include "decode_rows.h"
 
@@ -36,17 +40,24 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
   if (threadIdx.x == 0) ws[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
-// One wave, one logits row lr[0, V): dr[c] = g * (softmax(lr)[c] - [c == t]).  The one place where this arithmetic is
-// written: gct_ce_bwd and gct_seq_logp_bwd give the same bits for the same row, target and weight.
-__device__ __forceinline__ void ce_grad_row(const float* lr, float* dr, int V, int64_t t, float g, int lane) {
-  float mx, se;
-  gct_wave_softmax_stats(lr, V, lane, mx, se);
+// One wave, one logits row lr[0, V) whose softmax statistics (mx, se) the caller holds:
+// dr[c] = g * (softmax(lr)[c] - [c == t]).  The one place where this arithmetic is written: gct_ce_bwd, gct_seq_logp_bwd
+// and gct_seq_ppo_bwd give the same bits for the same row, target and weight.
+__device__ __forceinline__ void ce_grad_write(const float* lr, float* dr, int V, int64_t t, float g, int lane, float mx,
+                                              float se) {
   const float inv = 1.0f / se;
   for (int c = lane; c < V; c += 64) {
     float pr = expf(lr[c] - mx) * inv;
     if (c == t) pr -= 1.0f;
     dr[c] = g * pr;
   }
+}
+
+// ce_grad_write behind the row's own statistics.
+__device__ __forceinline__ void ce_grad_row(const float* lr, float* dr, int V, int64_t t, float g, int lane) {
+  float mx, se;
+  gct_wave_softmax_stats(lr, V, lane, mx, se);
+  ce_grad_write(lr, dr, V, t, g, lane, mx, se);
 }
 
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ logits,
@@ -163,6 +174,139 @@ __global__ __launch_bounds__(256) void seq_logp_bwd_kernel(const float* __restri
       continue;
     }
     ce_grad_row(logits + row * ld, dr, V, tok, -g, lane);
+  }
+}
+
+// The clipped surrogate of one scored token (decode.py ppo_reference states the rule): lp its log-probability now, old
+// the one it was sampled with, A its sequence's advantage.  rho = exp(lp - old); CLIPPED when A > 0 and rho > 1 +
+// clip_hi, or A < 0 and rho < 1 - clip_lo (strict: rho == 1 never is).  Plain fp32, one value per wave.
+struct PpoToken {
+  float rho, surrogate, k3;
+  bool clipped;
+};
+__device__ __forceinline__ PpoToken ppo_token(float lp, float old, float A, float clip_lo, float clip_hi) {
+  PpoToken t;
+  const float d = lp - old, hi = 1.0f + clip_hi, lo = 1.0f - clip_lo;
+  t.rho = expf(d);
+  const bool up = A > 0.f && t.rho > hi, down = A < 0.f && t.rho < lo;
+  t.clipped = up || down;
+  t.surrogate = up ? A * hi : (down ? A * lo : A * t.rho);
+  t.k3 = (t.rho - 1.0f) - d;                            // the k3 estimator term of KL(old || new)
+  return t;
+}
+
+// seq_logp_kernel's layout: one workgroup per sequence, wave w takes the token columns w, w + 4, ...; each column's
+// log-probability (wave_token_logp: gct_seq_logp's bits), surrogate and KL term go to LDS and thread 0 adds them up in
+// ascending column order.  Neither the logits row nor old_token_logp is read at a column that is not scored.
+__global__ __launch_bounds__(256) void seq_ppo_kernel(const float* __restrict__ logits, int64_t ld, int V,
+                                                      int64_t rows_per_seq, int row_shift,
+                                                      const int64_t* __restrict__ ys, int64_t ld_ys,
+                                                      const int32_t* __restrict__ prefix_lens, int64_t pad_id, int W,
+                                                      const float* __restrict__ old_token_logp, int64_t ld_old,
+                                                      const float* __restrict__ advantage, float clip_lo,
+                                                      float clip_hi, float* __restrict__ token_logp,
+                                                      float* __restrict__ token_surrogate, int64_t ld_out,
+                                                      float* __restrict__ logp, float* __restrict__ surrogate,
+                                                      float* __restrict__ approx_kl, int32_t* __restrict__ tokens,
+                                                      int32_t* __restrict__ hits, int32_t* __restrict__ clipped) {
+  __shared__ float sh_lp[SEQ_LOGP_MAX_W];
+  __shared__ float sh_s[SEQ_LOGP_MAX_W];
+  __shared__ float sh_k[SEQ_LOGP_MAX_W];
+  __shared__ uint8_t sh_flag[SEQ_LOGP_MAX_W];           // bit 0: scored, bit 1: hit, bit 2: clipped
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t r = blockIdx.x;
+  const int t0 = prefix_lens ? prefix_lens[r] : 1;
+  const int64_t* yr = ys + r * ld_ys;
+  const float A = advantage[r];
+  for (int c = wave; c < W; c += 4) {                   // uniform over the wave
+    const int64_t tok = yr[c];
+    const bool scored = c >= t0 && c >= 1 && tok != pad_id && tok >= 0 && tok < V;
+    float lp = 0.f;
+    PpoToken t = {1.f, 0.f, 0.f, false};
+    bool hit = false;
+    if (scored) {
+      lp = wave_token_logp(logits + (r * rows_per_seq + row_shift + c - 1) * ld, V, (int)tok, lane, hit);
+      t = ppo_token(lp, old_token_logp[r * ld_old + c], A, clip_lo, clip_hi);
+    }
+    if (lane == 0) {
+      token_logp[r * ld_out + c] = lp;
+      token_surrogate[r * ld_out + c] = t.surrogate;
+      sh_lp[c] = lp;
+      sh_s[c] = t.surrogate;
+      sh_k[c] = t.k3;
+      sh_flag[c] = (scored ? 1 : 0) | (hit ? 2 : 0) | (t.clipped ? 4 : 0);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float sum = 0.f, ss = 0.f, sk = 0.f;
+    int nt = 0, nh = 0, nc = 0;
+    for (int c = 0; c < W; ++c) {
+      const int f = sh_flag[c];
+      if (f & 1) {
+        sum += sh_lp[c];
+        ss += sh_s[c];
+        sk += sh_k[c];
+      }
+      nt += f & 1;
+      nh += (f >> 1) & 1;
+      nc += (f >> 2) & 1;
+    }
+    logp[r] = sum;
+    surrogate[r] = ss;
+    approx_kl[r] = sk;
+    tokens[r] = nt;
+    hits[r] = nh;
+    clipped[r] = nc;
+  }
+}
+
+// seq_logp_bwd_kernel's layout: one wave per logits row (r, j), four rows per workgroup, the grid strides over the
+// rest.  With A = advantage[r] and g = g_surrogate[r] + g_token_surrogate[r][c] (a null table: 0), a row that is not
+// scored, or whose A or g is 0, gets V exact zeros and its logits are NOT read.  Otherwise the row's softmax statistics
+// are taken once: lp (wave_token_logp's bits), rho and the clip decision follow from them, and the row is V zeros
+// (clipped) or ce_grad_write with the weight -((g * A) * rho): rho == 1 gives gct_seq_logp_bwd's bits for g_logp =
+// g * A.  Everything a branch depends on is one value per wave.
+__global__ __launch_bounds__(256) void seq_ppo_bwd_kernel(const float* __restrict__ logits, int64_t ld, int V,
+                                                          int64_t rows_per_seq, int row_shift,
+                                                          const int64_t* __restrict__ ys, int64_t ld_ys,
+                                                          const int32_t* __restrict__ prefix_lens, int64_t pad_id,
+                                                          int W, const float* __restrict__ old_token_logp,
+                                                          int64_t ld_old, const float* __restrict__ advantage,
+                                                          float clip_lo, float clip_hi,
+                                                          const float* __restrict__ g_surrogate,
+                                                          const float* __restrict__ g_token, int64_t ld_g,
+                                                          float* __restrict__ dlogits, int64_t ld_d, int64_t rows) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
+    const int64_t r = row / rows_per_seq, j = row - r * rows_per_seq;
+    const int64_t c = j - row_shift + 1;
+    float* dr = dlogits + row * ld_d;
+    int64_t tok = 0;
+    float g = 0.f, A = 0.f;
+    if (j >= row_shift && c >= 1 && c < W) {
+      const int t0 = prefix_lens ? prefix_lens[r] : 1;
+      tok = ys[r * ld_ys + c];
+      if (c >= t0 && tok != pad_id && tok >= 0 && tok < V) {
+        g = (g_surrogate ? g_surrogate[r] : 0.f) + (g_token ? g_token[r * ld_g + c] : 0.f);
+        A = advantage[r];
+      }
+    }
+    bool live = g != 0.f && A != 0.f;                   // scored, and both weights count
+    float mx = 0.f, se = 1.f, w = 0.f;
+    const float* lr = logits + row * ld;
+    if (live) {
+      gct_wave_softmax_stats(lr, V, lane, mx, se);
+      const float lp = (lr[tok] - mx) - logf(se);
+      const PpoToken t = ppo_token(lp, old_token_logp[r * ld_old + c], A, clip_lo, clip_hi);
+      live = !t.clipped;
+      w = (g * A) * t.rho;
+    }
+    if (!live) {
+      for (int v = lane; v < V; v += 64) dr[v] = 0.f;
+      continue;
+    }
+    ce_grad_write(lr, dr, V, tok, -w, lane, mx, se);
   }
 }
 
@@ -391,6 +535,64 @@ extern "C" int gct_seq_logp_bwd(const float* logits, int64_t ld, int V, int64_t 
                      rows_per_seq, row_shift, ys, ld_ys, prefix_lens, pad_id, W, g_logp, g_token, ld_g, dlogits, ld_d,
                      rows);
   GCT_LAUNCH_CHECK("seq_logp_bwd");
+  return GCT_OK;
+}
+
+extern "C" int gct_seq_ppo(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift,
+                           const int64_t* ys, int64_t ld_ys, const int32_t* prefix_lens, int64_t pad_id, int n, int W,
+                           const float* old_token_logp, int64_t ld_old, const float* advantage, float clip_lo,
+                           float clip_hi, float* token_logp, float* token_surrogate, int64_t ld_out, float* logp,
+                           float* surrogate, float* approx_kl, int32_t* tokens, int32_t* hits, int32_t* clipped,
+                           void* stream) {
+  GCT_CHECK_ARG(logits && ys && token_logp && token_surrogate && logp && surrogate && approx_kl && tokens && hits &&
+                    clipped,
+                "seq_ppo: null pointer");
+  GCT_CHECK_ARG(old_token_logp && advantage, "seq_ppo: null pointer (old_token_logp, advantage)");
+  GCT_CHECK_ARG(n >= 0 && V > 0 && ld >= V, "seq_ppo: bad shape (n %d, V %d, ld %lld)", n, V, (long long)ld);
+  GCT_CHECK_ARG(W >= 1 && W <= SEQ_LOGP_MAX_W, "seq_ppo: rows of %d tokens (1 .. %d supported)", W, SEQ_LOGP_MAX_W);
+  GCT_CHECK_ARG(ld_ys >= W && ld_out >= W && ld_old >= W,
+                "seq_ppo: ld_ys / ld_out / ld_old narrower than the %d token columns", W);
+  GCT_CHECK_ARG(row_shift >= 0 && rows_per_seq >= (int64_t)row_shift + W - 1,
+                "seq_ppo: %lld logits rows per sequence do not hold %d + %d", (long long)rows_per_seq, row_shift, W - 1);
+  GCT_CHECK_ARG(clip_lo >= 0.f && clip_lo < 1.f && clip_hi >= 0.f,
+                "seq_ppo: clip (%g, %g) outside 0 <= clip_lo < 1, clip_hi >= 0", (double)clip_lo, (double)clip_hi);
+  if (n == 0) return GCT_OK;
+  hipLaunchKernelGGL(seq_ppo_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, logits, ld, V, rows_per_seq,
+                     row_shift, ys, ld_ys, prefix_lens, pad_id, W, old_token_logp, ld_old, advantage, clip_lo, clip_hi,
+                     token_logp, token_surrogate, ld_out, logp, surrogate, approx_kl, tokens, hits, clipped);
+  GCT_LAUNCH_CHECK("seq_ppo");
+  return GCT_OK;
+}
+
+extern "C" int gct_seq_ppo_bwd(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift,
+                               const int64_t* ys, int64_t ld_ys, const int32_t* prefix_lens, int64_t pad_id, int n,
+                               int W, const float* old_token_logp, int64_t ld_old, const float* advantage,
+                               float clip_lo, float clip_hi, const float* g_surrogate,
+                               const float* g_token_surrogate, int64_t ld_g, float* dlogits, int64_t ld_d,
+                               void* stream) {
+  GCT_CHECK_ARG(logits && ys && dlogits, "seq_ppo_bwd: null pointer");
+  GCT_CHECK_ARG(old_token_logp && advantage, "seq_ppo_bwd: null pointer (old_token_logp, advantage)");
+  GCT_CHECK_ARG(g_surrogate || g_token_surrogate,
+                "seq_ppo_bwd: both gradients are null (g_surrogate, g_token_surrogate)");
+  GCT_CHECK_ARG(n >= 0 && V > 0 && ld >= V && ld_d >= V, "seq_ppo_bwd: bad shape (n %d, V %d, ld %lld, ld_d %lld)", n,
+                V, (long long)ld, (long long)ld_d);
+  GCT_CHECK_ARG(W >= 1 && W <= SEQ_LOGP_MAX_W, "seq_ppo_bwd: rows of %d tokens (1 .. %d supported)", W,
+                SEQ_LOGP_MAX_W);
+  GCT_CHECK_ARG(ld_ys >= W && ld_old >= W && (!g_token_surrogate || ld_g >= W),
+                "seq_ppo_bwd: ld_ys / ld_old / ld_g narrower than the %d token columns", W);
+  GCT_CHECK_ARG(row_shift >= 0 && rows_per_seq >= (int64_t)row_shift + W - 1,
+                "seq_ppo_bwd: %lld logits rows per sequence do not hold %d + %d", (long long)rows_per_seq, row_shift,
+                W - 1);
+  GCT_CHECK_ARG(clip_lo >= 0.f && clip_lo < 1.f && clip_hi >= 0.f,
+                "seq_ppo_bwd: clip (%g, %g) outside 0 <= clip_lo < 1, clip_hi >= 0", (double)clip_lo, (double)clip_hi);
+  const int64_t rows = (int64_t)n * rows_per_seq;
+  if (rows == 0) return GCT_OK;
+  int64_t g = (rows + 3) / 4;
+  g = g > 4096 ? 4096 : g;
+  hipLaunchKernelGGL(seq_ppo_bwd_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, logits, ld, V,
+                     rows_per_seq, row_shift, ys, ld_ys, prefix_lens, pad_id, W, old_token_logp, ld_old, advantage,
+                     clip_lo, clip_hi, g_surrogate, g_token_surrogate, ld_g, dlogits, ld_d, rows);
+  GCT_LAUNCH_CHECK("seq_ppo_bwd");
   return GCT_OK;
 }
 

@@ -55,6 +55,9 @@ gct_seq_logp_bwd through engine.SeqLogpFn): the per-molecule policy term of a fi
 `sequence_policy` adds, from the same one forward, the terms that need the whole next-token distribution: the policy's
 entropy and its KL divergence from a frozen prior at every scored token (the rules: `dist_reference` /
 `dist_grad_reference`; gct_seq_dist / gct_seq_dist_bwd through engine.SeqDistFn).
+`sequence_ppo` is the objective of several updates on one scored batch: PPO's clipped surrogate of each scored token's
+probability ratio against the log-probabilities it was sampled with (the rules: `ppo_reference` / `ppo_grad_reference`;
+gct_seq_ppo / gct_seq_ppo_bwd through engine.SeqPpoFn), with sequence_policy's terms beside it when asked for.
 
 Grammar-constrained decoding (`generate` / `generate_stream(grammar=SmilesGrammar(...))`): the rules are stated once, in
 `SmilesGrammar` (grammar_step, grammar_min_finish).  gct_grammar_mask runs in front of the selection: one wave per row
@@ -609,6 +612,141 @@ def dist_grad_reference(logits, ys, prefix_lens, pad_id, prior_logits=None, g_en
     return torch.where(live.unsqueeze(-1) & (p > 0), grad, zero)
 
 
+def clip_pair(clip):
+    """PPO's clip argument as (clip_lo, clip_hi) floats: a number e means (e, e), a pair (lo, hi) itself.  ValueError for
+    anything else; the ranges are check_ppo_inputs' business."""
+    if isinstance(clip, numbers.Real) and not isinstance(clip, bool):
+        return float(clip), float(clip)
+    try:
+        lo, hi = clip
+        if any(isinstance(v, bool) or not isinstance(v, numbers.Real) for v in (lo, hi)):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"clip must be a number or a pair (clip_lo, clip_hi) of numbers, got {clip!r}") from None
+    return float(lo), float(hi)
+
+
+def check_ppo_inputs(old_token_logp, advantage, clip_lo, clip_hi, n, W):
+    """Validate what PPO's surrogate takes beside a scoring call's inputs, for n token rows of W columns: old_token_logp
+    a floating-point tensor [n, W]; advantage [n] finite numbers; 0 <= clip_lo < 1 (the lower bound 1 - clip_lo of the
+    ratio stays positive); clip_hi >= 0.  ValueError otherwise, before any device work of the caller.
+    The VALUES of old_token_logp are not looked at -- the table lives on the device, and a check would wait for it: a
+    non-finite entry on a scored column is not refused, IEEE arithmetic decides the result there (NaN gives a NaN
+    surrogate and gradient row, +inf a ratio of 0, -inf an infinite one).  Returns advantage as a tensor."""
+    if not isinstance(old_token_logp, torch.Tensor) or not old_token_logp.dtype.is_floating_point:
+        raise ValueError("old_token_logp must be a floating-point tensor")
+    if tuple(old_token_logp.shape) != (n, W):
+        raise ValueError(f"old_token_logp must be [{n}, {W}], got {list(old_token_logp.shape)}")
+    adv = torch.as_tensor(advantage)
+    if adv.dtype == torch.bool or adv.dtype.is_complex:
+        raise ValueError(f"advantage must hold real numbers, got {adv.dtype}")
+    if adv.dim() != 1 or adv.numel() != n:
+        raise ValueError(f"advantage must have shape [{n}], got {list(adv.shape)}")
+    if not bool(torch.isfinite(adv.double()).all()):
+        raise ValueError("advantage must be finite")
+    for name, v in (("clip_lo", clip_lo), ("clip_hi", clip_hi)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real):
+            raise ValueError(f"{name} must be a number, got {v!r}")
+    if not 0 <= clip_lo < 1:
+        raise ValueError(f"clip_lo must lie in [0, 1), got {clip_lo!r}")
+    if not clip_hi >= 0:
+        raise ValueError(f"clip_hi must be >= 0, got {clip_hi!r}")
+    return adv
+
+
+def _ppo_rows(logits, ys, prefix_lens, pad_id, old_token_logp, advantage, clip_lo, clip_hi):
+    """Shared front of ppo_reference / ppo_grad_reference: (ys, x, n, W, scored [n, W - 1], targets [n, W - 1], old
+    [n, W - 1], A [n, 1], lo, hi) in the dtype and on the device of x; lo = 1 - clip_lo and hi = 1 + clip_hi are formed
+    in that dtype."""
+    ys = torch.as_tensor(ys)
+    lens = check_score_inputs(ys, prefix_lens, logits.shape[-1])
+    n, W = ys.shape
+    x = logits if logits.dtype == torch.float64 else logits.float()
+    if tuple(x.shape[:2]) != (n, W - 1):
+        raise ValueError(f"logits must be [{n}, {W - 1}, V], got {list(logits.shape)}")
+    adv = check_ppo_inputs(torch.as_tensor(old_token_logp), advantage, clip_lo, clip_hi, n, W)
+    dev = x.device
+    tgt = ys[:, 1:].long().to(dev)
+    scored = (torch.arange(1, W).view(1, -1) >= lens.view(-1, 1)).to(dev) & (tgt != pad_id)
+    old = torch.as_tensor(old_token_logp).to(dev, x.dtype)[:, 1:]
+    A = adv.to(dev, x.dtype).view(n, 1)
+    one = torch.ones((), dtype=x.dtype, device=dev)
+    return ys, x, n, W, scored, tgt, old, A, one - clip_lo, one + clip_hi
+
+
+def ppo_reference(logits, ys, prefix_lens, pad_id, old_token_logp, advantage, clip_lo, clip_hi):
+    """THE statement of PPO's clipped surrogate over the scored tokens (gct_seq_ppo implements it), at score_reference's
+    geometry and under its SCORED predicate (ys [n, W] full token rows, logits [n, W - 1, V], row c - 1 predicts token
+    c).  old_token_logp [n, W]: the log-probabilities the tokens were sampled with (score_reference's token_logp under
+    the sampling-time policy); advantage [n]: one number per sequence; 0 <= clip_lo < 1, clip_hi >= 0
+    (check_ppo_inputs).  At a scored column (r, c), with lp = score_reference's token_logp[r, c], A = advantage[r] and
+      rho = exp(lp - old_token_logp[r, c]):
+    the token is CLIPPED when (A > 0 and rho > 1 + clip_hi) or (A < 0 and rho < 1 - clip_lo) -- strict comparisons, so
+    rho == 1 is never clipped, even with a clip of 0 --, and
+      token_surrogate [n, W]  A * (1 + clip_hi) clipped high, A * (1 - clip_lo) clipped low, A * rho otherwise
+                              (= min(rho A, clamp(rho, 1 - clip_lo, 1 + clip_hi) A) in value);
+      the k3 term             (rho - 1) - (lp - old): an estimator of KL(old || new), >= 0.
+    Columns that are not scored hold 0, whatever their logits rows and old_token_logp hold.  Per sequence, sums of the
+    scored columns in ascending column order: logp [n], surrogate [n], approx_kl [n] (the k3 terms); counts: tokens [n],
+    hits [n], clipped [n] int32.  token_logp, logp, tokens and hits are score_reference's.
+    Returns (token_logp, token_surrogate, logp, surrogate, approx_kl, tokens, hits, clipped), in the dtype of logits
+    (fp32 at least) on the device of logits.  A non-finite old_token_logp on a scored column is not an error: IEEE
+    arithmetic decides."""
+    ys, x, n, W, scored, tgt, old, A, lo, hi = _ppo_rows(logits, ys, prefix_lens, pad_id, old_token_logp, advantage,
+                                                         clip_lo, clip_hi)
+    dev = x.device
+    token_logp, logp, tokens, hits = score_reference(x, ys, prefix_lens, pad_id)
+    zero = torch.zeros((), dtype=x.dtype, device=dev)
+    d = torch.where(scored, token_logp[:, 1:] - old, zero)
+    rho = torch.exp(d)
+    up = scored & (A > 0) & (rho > hi)
+    down = scored & (A < 0) & (rho < lo)
+    first = torch.zeros(n, 1, dtype=x.dtype, device=dev)
+
+    def columns(per_row):                                # [n, W - 1] -> token table [n, W] and its row sums
+        table = torch.cat([first, torch.where(scored, per_row, zero)], dim=1)
+        total = torch.zeros(n, dtype=x.dtype, device=dev)
+        for c in range(1, W):                            # ascending column order
+            total = total + table[:, c]
+        return table, total
+    token_surrogate, surrogate = columns(torch.where(up, A * hi, torch.where(down, A * lo, A * rho)))
+    _, approx_kl = columns((rho - 1) - d)
+    return (token_logp, token_surrogate, logp, surrogate, approx_kl, tokens, hits,
+            (up | down).sum(1).to(torch.int32))
+
+
+def ppo_grad_reference(logits, ys, prefix_lens, pad_id, old_token_logp, advantage, clip_lo, clip_hi, g_surrogate=None,
+                       g_token_surrogate=None):
+    """THE statement of the backward rule of ppo_reference (gct_seq_ppo_bwd implements it): the gradient with respect to
+    the logits [n, W - 1, V] of  sum_r g_surrogate[r] * surrogate[r] + sum_{r, c} g_token_surrogate[r, c] *
+    token_surrogate[r, c]  (g_surrogate [n], g_token_surrogate [n, W]; None: 0).  With g = g_surrogate[r] +
+    g_token_surrogate[r, c], A = advantage[r] and rho as in ppo_reference, row c - 1 of sequence r gets
+      ((g * A) * rho) * ([v == ys[r, c]] - softmax(logits[r, c - 1])[v])   where column c is scored and not clipped,
+      exact zeros   where the column is not scored, the token is clipped, A == 0 or g == 0 -- whatever the logits row
+    holds, NaN included.  For a column that is not scored, or with A == 0 or g == 0, the row is never looked at; a
+    clipped token's row is, to decide that it is clipped.  old_token_logp and advantage get no gradient.
+    Closed form, in the dtype of logits (fp32 at least), on the device of logits."""
+    ys, x, n, W, scored, tgt, old, A, lo, hi = _ppo_rows(logits, ys, prefix_lens, pad_id, old_token_logp, advantage,
+                                                         clip_lo, clip_hi)
+    dev = x.device
+    zero = torch.zeros((), dtype=x.dtype, device=dev)
+    g = torch.zeros(n, W, dtype=x.dtype, device=dev)
+    if g_surrogate is not None:
+        g = g + torch.as_tensor(g_surrogate).to(dev, x.dtype).view(n, 1)
+    if g_token_surrogate is not None:
+        g = g + torch.as_tensor(g_token_surrogate).to(dev, x.dtype).view(n, W)
+    g = g[:, 1:]
+    looked = scored & (g != 0) & (A != 0)
+    lsm = _log_softmax_rows(x, looked)                   # the other rows: zeros before any arithmetic
+    d = torch.where(looked, lsm.gather(-1, tgt.unsqueeze(-1)).squeeze(-1) - old, zero)
+    rho = torch.exp(d)
+    live = looked & ~(((A > 0) & (rho > hi)) | ((A < 0) & (rho < lo)))
+    grad = -torch.exp(lsm)
+    grad.scatter_add_(-1, tgt.unsqueeze(-1), torch.ones(n, W - 1, 1, dtype=x.dtype, device=dev))
+    w = (g * A) * rho
+    return torch.where(live.unsqueeze(-1), w.unsqueeze(-1) * grad, zero)
+
+
 def _score_geometry(model, ys, prefix_lens):
     """What every teacher-forced scoring call validates before any device work: (ys as a tensor, prefix lengths int64
     [n] on the CPU, use_cond2dec, row_shift = the condition rows in front of a sequence's logits, V).  ValueError for
@@ -733,14 +871,70 @@ class PolicyTerms(NamedTuple):
     prior_logp: Optional[torch.Tensor]
 
 
-def _check_prior(model, prior):
+def _check_prior(model, prior, name="sequence_policy"):
     """A prior scores the agent's rows with the agent's geometry: the same vocabulary, condition count and
     use_cond2dec.  ValueError otherwise."""
     for what, a, b in (("vocabulary", model.out.weight.shape[0], prior.out.weight.shape[0]),
                        ("nconds", model.decoder.nconds, prior.decoder.nconds),
                        ("use_cond2dec", bool(model.decoder.use_cond2dec), bool(prior.decoder.use_cond2dec))):
         if a != b:
-            raise ValueError(f"sequence_policy: the prior's {what} ({b}) is not the model's ({a})")
+            raise ValueError(f"{name}: the prior's {what} ({b}) is not the model's ({a})")
+
+
+class _PolicyRows(NamedTuple):
+    """What sequence_policy and sequence_ppo share once the inputs are accepted and the agent's ONE forward has run, on
+    the device: the token rows y, prefix lengths t0 (int64) / t0_dev (int32, None when the caller gave none), mask and
+    conditions, use_cond2dec and the condition rows in front of a sequence's logits, the logits [n * rows, V]."""
+    y: torch.Tensor
+    t0: torch.Tensor
+    t0_dev: Optional[torch.Tensor]
+    sm: Optional[torch.Tensor]
+    dc: Optional[torch.Tensor]
+    c2d: bool
+    off: int
+    logits2d: torch.Tensor
+    rows: int
+
+
+def _policy_rows(name, model, z, src_mask, dconds, ys, prefix_lens, pad_id, prior, check=None):
+    """sequence_policy's validation (ValueError before any device work; `check(n, W)` adds the caller's own), then the
+    agent's one forward through _scoring_logits."""
+    ys, lens, c2d, off, V = _score_geometry(model, ys, prefix_lens)
+    if prior is not None:
+        _check_prior(model, prior, name)
+    n, W = ys.shape
+    if check is not None:
+        check(n, W)
+    host = ys.detach().cpu()
+    if not bool(((torch.arange(W).view(1, -1) >= lens.view(-1, 1)) & (host != pad_id))[:, 1:].any()):
+        raise ValueError(f"{name}: no column of the batch is scored (every row is prefix or pad)")
+    dev = z.device
+    y = ys.to(dev, torch.int64).contiguous()
+    t0 = lens.to(dev)
+    dc = None if dconds is None else dconds.to(dev)
+    sm = None if src_mask is None else src_mask.to(dev)
+    t0_dev = None if prefix_lens is None else t0.to(torch.int32)
+    logits2d, rows = _scoring_logits(model, z, sm, dc, y, t0, pad_id, c2d)
+    return _PolicyRows(y, t0, t0_dev, sm, dc, c2d, off, logits2d, rows)
+
+
+def _dist_terms(name, r, z, pad_id, prior, entropy):
+    """The terms of sequence_policy beyond logp, on the rows r of _policy_rows: the prior's one forward under no_grad and
+    its log-likelihood (gct_seq_logp), then engine.SeqDistFn on the agent's logits.  Returns (entropy, token_entropy, kl,
+    token_kl, prior_logp), each None when not asked for."""
+    prior2d = prior_logp = None
+    if prior is not None:
+        with torch.no_grad():
+            prior2d, prior_rows = _scoring_logits(prior, z.detach(), r.sm, r.dc, r.y, r.t0, pad_id, r.c2d)
+            if prior_rows != r.rows:
+                raise ValueError(f"{name}: the prior gives {prior_rows} logits rows per sequence, the model {r.rows}")
+            prior_logp = ops.seq_logp(prior2d, r.y, r.t0_dev, pad_id, row_shift=r.off, rows_per_seq=r.rows)[1]
+    ent = tent = kl = tkl = None
+    if entropy or prior is not None:
+        ent, tent, kl, tkl = engine.SeqDistFn.apply(r.logits2d, prior2d, r.y, r.t0_dev, pad_id, r.off)
+        if not entropy:
+            ent = tent = None
+    return ent, tent, kl, tkl, prior_logp
 
 
 def sequence_policy(model, z, src_mask, dconds, ys, prefix_lens=None, pad_id=1, prior=None, entropy=True):
@@ -754,35 +948,60 @@ def sequence_policy(model, z, src_mask, dconds, ys, prefix_lens=None, pad_id=1, 
     engine.SeqDistFn: exact zeros on every logits row that is not scored, as SeqLogpFn's, and autograd adds the two.
     ValueError before any device work for what sequence_logp refuses and for a prior whose vocabulary, nconds or
     use_cond2dec differ from the model's."""
-    ys, lens, c2d, off, V = _score_geometry(model, ys, prefix_lens)
-    if prior is not None:
-        _check_prior(model, prior)
-    n, W = ys.shape
-    host = ys.detach().cpu()
-    if not bool(((torch.arange(W).view(1, -1) >= lens.view(-1, 1)) & (host != pad_id))[:, 1:].any()):
-        raise ValueError("sequence_policy: no column of the batch is scored (every row is prefix or pad)")
-    dev = z.device
-    y = ys.to(dev, torch.int64).contiguous()
-    t0 = lens.to(dev)
-    dc = None if dconds is None else dconds.to(dev)
-    sm = None if src_mask is None else src_mask.to(dev)
-    t0_dev = None if prefix_lens is None else t0.to(torch.int32)
-    logits2d, rows = _scoring_logits(model, z, sm, dc, y, t0, pad_id, c2d)
-    logp, token_logp, tokens, hits = engine.SeqLogpFn.apply(logits2d, y, t0_dev, pad_id, off)
-    prior2d = prior_logp = None
-    if prior is not None:
-        with torch.no_grad():
-            prior2d, prior_rows = _scoring_logits(prior, z.detach(), sm, dc, y, t0, pad_id, c2d)
-            if prior_rows != rows:
-                raise ValueError(f"sequence_policy: the prior gives {prior_rows} logits rows per sequence, the model "
-                                 f"{rows}")
-            prior_logp = ops.seq_logp(prior2d, y, t0_dev, pad_id, row_shift=off, rows_per_seq=rows)[1]
-    ent = tent = kl = tkl = None
-    if entropy or prior is not None:
-        ent, tent, kl, tkl = engine.SeqDistFn.apply(logits2d, prior2d, y, t0_dev, pad_id, off)
-        if not entropy:
-            ent = tent = None
+    r = _policy_rows("sequence_policy", model, z, src_mask, dconds, ys, prefix_lens, pad_id, prior)
+    logp, token_logp, tokens, hits = engine.SeqLogpFn.apply(r.logits2d, r.y, r.t0_dev, pad_id, r.off)
+    ent, tent, kl, tkl, prior_logp = _dist_terms("sequence_policy", r, z, pad_id, prior, entropy)
     return PolicyTerms(logp, tokens, hits, token_logp, ent, tent, kl, tkl, prior_logp)
+
+
+class PpoTerms(NamedTuple):
+    """What sequence_ppo returns, on the device: PolicyTerms' nine fields -- logp [n], tokens [n] int32, hits [n] int32,
+    token_logp [n, W] of the CURRENT policy; entropy / token_entropy (None with entropy=False); kl / token_kl /
+    prior_logp (None without a prior) -- and PPO's: surrogate [n] / token_surrogate [n, W], the clipped surrogate of the
+    probability ratios against old_token_logp; approx_kl [n], the k3 estimate of KL(old || new) summed over a row's
+    scored tokens; clipped [n] int32, the row's clipped tokens.  surrogate, token_surrogate, entropy, token_entropy, kl
+    and token_kl carry the agent's graph; logp, token_logp, approx_kl and the counts are reports and carry none (an
+    objective in logp is sequence_logp's business).  ppo_reference states the rule of the new terms."""
+    logp: torch.Tensor
+    tokens: torch.Tensor
+    hits: torch.Tensor
+    token_logp: torch.Tensor
+    entropy: Optional[torch.Tensor]
+    token_entropy: Optional[torch.Tensor]
+    kl: Optional[torch.Tensor]
+    token_kl: Optional[torch.Tensor]
+    prior_logp: Optional[torch.Tensor]
+    surrogate: torch.Tensor
+    token_surrogate: torch.Tensor
+    approx_kl: torch.Tensor
+    clipped: torch.Tensor
+
+
+def sequence_ppo(model, z, src_mask, dconds, ys, old_token_logp, advantage, clip=0.2, prefix_lens=None, pad_id=1,
+                 prior=None, entropy=False):
+    """PPO's clipped surrogate of the token rows ys under the model, against the log-probabilities old_token_logp [n, W]
+    the rows were sampled with (sequence_logp's / Sampling.score's token_logp of the sampling-time policy) and one
+    advantage per row; clip: a number e (the ratio's trust region is [1 - e, 1 + e]) or a pair (clip_lo, clip_hi).
+    Returns a PpoTerms from ONE agent forward: gct_seq_ppo on the teacher-forced logits gives the surrogate and, in the
+    same launch, logp / tokens / hits / token_logp -- sequence_logp's bit for bit, but without a gradient --; with
+    entropy=True or a prior, the entropy / KL terms exactly as sequence_policy computes them (same values bit for bit).
+    old_token_logp and advantage get no gradient.  The backward is gct_seq_ppo_bwd through engine.SeqPpoFn: exact zeros on
+    every logits row that is not scored (ops.assert_no_skipped_row_gradients stays silent) and on the rows of clipped
+    tokens.  The model runs in its current train / eval mode; a ratio against a deterministic old policy wants eval()
+    (Train/finetune.ppo_update).
+    ValueError before any device work for what sequence_policy refuses and for what check_ppo_inputs does."""
+    clip_lo, clip_hi = clip_pair(clip)
+    adv = []
+    r = _policy_rows("sequence_ppo", model, z, src_mask, dconds, ys, prefix_lens, pad_id, prior,
+                     check=lambda n, W: adv.append(check_ppo_inputs(old_token_logp, advantage, clip_lo, clip_hi, n, W)))
+    dev = z.device
+    old = old_token_logp.detach().to(dev, torch.float32)
+    a = adv[0].detach().to(dev, torch.float32)
+    surrogate, token_surrogate, logp, token_logp, approx_kl, tokens, hits, clipped = engine.SeqPpoFn.apply(
+        r.logits2d, r.y, r.t0_dev, pad_id, r.off, old, a, clip_lo, clip_hi)
+    ent, tent, kl, tkl, prior_logp = _dist_terms("sequence_ppo", r, z, pad_id, prior, entropy)
+    return PpoTerms(logp, tokens, hits, token_logp, ent, tent, kl, tkl, prior_logp, surrogate, token_surrogate,
+                    approx_kl, clipped)
 
 
 # ------------------------------------------------------------------------------------- continuous batching

@@ -1005,6 +1005,53 @@ class SeqDistFn(torch.autograd.Function):
         return dl.view(shape), None, None, None, None, None
 
 
+class SeqPpoFn(torch.autograd.Function):
+    """PPO's clipped surrogate of the scored tokens with a gradient into the logits (decode.ppo_reference /
+    ppo_grad_reference state the rules):
+    apply(logits, ys, prefix_lens, pad_id, row_shift, old_token_logp, advantage, clip_lo, clip_hi) -> (surrogate [n],
+    token_surrogate [n, W], logp [n], token_logp [n, W], approx_kl [n], tokens [n], hits [n], clipped [n]).  logits, ys,
+    prefix_lens as SeqLogpFn takes them; old_token_logp fp32 [n, W] and advantage fp32 [n] get no gradient.  Only
+    surrogate and token_surrogate are differentiable (once); the other six are reports.  The backward is
+    gct_seq_ppo_bwd: it writes every row of dlogits, exact zeros where nothing is scored, the token is clipped, or the
+    advantage or the weight is 0."""
+
+    @staticmethod
+    def forward(ctx, logits, ys, prefix_lens, pad_id, row_shift, old_token_logp, advantage, clip_lo, clip_hi):
+        n, V = ys.shape[0], logits.shape[-1]
+        if logits.dim() == 3:
+            if logits.shape[0] != n:
+                raise ValueError(f"SeqPpoFn: {logits.shape[0]} logits blocks for {n} token rows")
+            l2 = _f32c(logits).view(-1, V)
+        elif logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1:
+            l2 = logits
+        else:
+            l2 = _f32c(logits).reshape(-1, V)
+        R = l2.shape[0] // n if n else ys.shape[1] - 1 + int(row_shift)
+        ys = ys.contiguous()
+        old = _f32c(old_token_logp.detach())
+        adv = _f32c(advantage.detach()).view(-1)
+        tl, ts, lp, su, kl, nt, nh, nc = ops.seq_ppo(l2, ys, old, adv, float(clip_lo), float(clip_hi), prefix_lens,
+                                                 int(pad_id), row_shift=int(row_shift), rows_per_seq=R)
+        ctx.save_for_backward(l2, ys, prefix_lens, old, adv)
+        ctx.geom = (int(pad_id), int(row_shift), R, logits.shape, float(clip_lo), float(clip_hi))
+        ctx.set_materialize_grads(False)                 # an output nobody used arrives as None, not as zeros
+        ctx.mark_non_differentiable(lp, tl, kl, nt, nh, nc)
+        return su, ts, lp, tl, kl, nt, nh, nc
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_surrogate, g_token_surrogate, *unused):
+        l2, ys, prefix_lens, old, adv = ctx.saved_tensors
+        pad_id, row_shift, R, shape, clip_lo, clip_hi = ctx.geom
+        none = (None,) * 8
+        if g_surrogate is None and g_token_surrogate is None:
+            return (torch.zeros(shape, device=l2.device),) + none
+        dl = ops.seq_ppo_bwd(l2, ys, old, adv, clip_lo, clip_hi, prefix_lens, pad_id, row_shift=row_shift,
+                             rows_per_seq=R, g_surrogate=None if g_surrogate is None else _f32c(g_surrogate),
+                             g_token_surrogate=None if g_token_surrogate is None else _f32c(g_token_surrogate))
+        return (dl.view(shape),) + none
+
+
 class KldFn(torch.autograd.Function):
     """Train/trainer1.py:23."""
 

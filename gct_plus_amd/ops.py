@@ -1287,6 +1287,89 @@ def seq_dist_bwd(logits2d, ys, prefix_lens=None, pad_id=1, row_shift=0, rows_per
     return out
 
 
+def _ppo_inputs(name, old_token_logp, advantage, n, W):
+    """The checks seq_ppo / seq_ppo_bwd make on the sampling-time table and the advantages (None passes a null pointer:
+    the library refuses): the row stride of old_token_logp."""
+    if old_token_logp is not None:
+        _chk(old_token_logp, f"{name}.old_token_logp")
+        if old_token_logp.shape != (n, W) or old_token_logp.stride(1) != 1:
+            raise ValueError(f"{name}: old_token_logp must be [{n}, {W}] with unit column stride")
+    if advantage is not None:
+        _chk(advantage, f"{name}.advantage")
+        if advantage.numel() != n or not advantage.is_contiguous():
+            raise ValueError(f"{name}: advantage must be a contiguous fp32 tensor of {n} entries")
+    return 0 if old_token_logp is None else old_token_logp.stride(0)
+
+
+def seq_ppo(logits2d, ys, old_token_logp, advantage, clip_lo, clip_hi, prefix_lens=None, pad_id=1, row_shift=0,
+            rows_per_seq=None, V=None, out=None):
+    """gct_seq_ppo (decode.ppo_reference states the rule): PPO's clipped surrogate of the scored tokens, for the geometry
+    seq_logp takes (same checks on ys, logits2d, prefix_lens; logits2d None with V given passes a null pointer: the
+    library refuses).  old_token_logp fp32 [n, W] with unit column stride (its own row stride), advantage fp32 [n],
+    clip_lo in [0, 1), clip_hi >= 0 (the library refuses others).
+    Returns (token_logp [n, W], token_surrogate [n, W], logp [n], surrogate [n], approx_kl [n] fp32, tokens [n],
+    hits [n], clipped [n] int32), or fills `out`, a tuple of them (the two tables with one row stride)."""
+    n, W, R, V, ld, _ = _seq_geometry("seq_ppo", logits2d, ys, rows_per_seq, V, prefix_lens)
+    ld_old = _ppo_inputs("seq_ppo", old_token_logp, advantage, n, W)
+    dev = ys.device
+    if out is None:
+        out = (torch.empty(n, W, device=dev), torch.empty(n, W, device=dev)) + tuple(
+            torch.empty(n, device=dev) for _ in range(3)) + tuple(
+            torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+    tl, ts, lp, su, kl, nt, nh, nc = out
+    for t in (tl, ts, lp, su, kl):
+        _chk(t, "seq_ppo.out")
+    _chk(nt, "seq_ppo.tokens", torch.int32), _chk(nh, "seq_ppo.hits", torch.int32)
+    _chk(nc, "seq_ppo.clipped", torch.int32)
+    if (any(t.shape != (n, W) or t.stride(1) != 1 for t in (tl, ts)) or tl.stride(0) != ts.stride(0) or
+            any(t.numel() != n or not t.is_contiguous() for t in (lp, su, kl, nt, nh, nc))):
+        raise ValueError("seq_ppo: out must be (token_logp [n, W], token_surrogate [n, W] of one row stride, logp [n], "
+                         "surrogate [n], approx_kl [n], tokens [n], hits [n], clipped [n])")
+    if n == 0:
+        return out                                       # no sequence: nothing to write (an empty tensor has no address)
+    check(_L().gct_seq_ppo(_p(logits2d), ld, V, R, int(row_shift), _p(ys), ys.stride(0), _p(prefix_lens), int(pad_id), n,
+                           W, _p(old_token_logp), ld_old, _p(advantage), float(clip_lo), float(clip_hi), _p(tl), _p(ts),
+                           tl.stride(0), _p(lp), _p(su), _p(kl), _p(nt), _p(nh), _p(nc), _st()), "gct_seq_ppo")
+    return out
+
+
+def seq_ppo_bwd(logits2d, ys, old_token_logp, advantage, clip_lo, clip_hi, prefix_lens=None, pad_id=1, row_shift=0,
+                rows_per_seq=None, g_surrogate=None, g_token_surrogate=None, V=None, out=None):
+    """gct_seq_ppo_bwd (decode.ppo_grad_reference states the rule): the gradient of seq_ppo's surrogate [n] and
+    token_surrogate [n, W] with respect to the logits, for the geometry and inputs seq_ppo takes (same checks).
+    g_surrogate fp32 [n] / g_token_surrogate fp32 [n, W] with unit column stride: the incoming gradients, either may be
+    None (0), the library refuses both.
+    Returns dlogits fp32, contiguous, in the shape of logits2d (or fills `out`, [>= n * rows_per_seq, V] with unit column
+    stride): every row is written -- zeros on the rows that are not scored, whose advantage or weight is 0 (their logits
+    are not read), and on the rows of clipped tokens."""
+    n, W, R, V, ld, _ = _seq_geometry("seq_ppo_bwd", logits2d, ys, rows_per_seq, V, prefix_lens)
+    ld_old = _ppo_inputs("seq_ppo_bwd", old_token_logp, advantage, n, W)
+    if g_surrogate is not None:
+        _chk(g_surrogate, "seq_ppo_bwd.g_surrogate")
+        if g_surrogate.numel() != n or not g_surrogate.is_contiguous():
+            raise ValueError(f"seq_ppo_bwd: g_surrogate must be a contiguous fp32 tensor of {n} entries")
+    if g_token_surrogate is not None:
+        _chk(g_token_surrogate, "seq_ppo_bwd.g_token_surrogate")
+        if g_token_surrogate.shape != (n, W) or g_token_surrogate.stride(1) != 1:
+            raise ValueError(f"seq_ppo_bwd: g_token_surrogate must be [{n}, {W}] with unit column stride")
+    rows = max(n * R, 0 if logits2d is None else logits2d.shape[0])
+    if out is None:
+        out = torch.empty(rows, V, device=ys.device)
+        if rows > n * R:
+            out[n * R:].zero_()                          # rows behind the last sequence belong to nobody
+    _chk(out, "seq_ppo_bwd.dlogits")
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < n * R or out.shape[1] != V:
+        raise ValueError(f"seq_ppo_bwd: out must be [>= {n * R}, {V}] with unit column stride")
+    if n == 0:
+        return out                                       # no sequence: nothing to write (an empty tensor has no address)
+    check(_L().gct_seq_ppo_bwd(_p(logits2d), ld, V, R, int(row_shift), _p(ys), ys.stride(0), _p(prefix_lens),
+                               int(pad_id), n, W, _p(old_token_logp), ld_old, _p(advantage), float(clip_lo),
+                               float(clip_hi), _p(g_surrogate), _p(g_token_surrogate),
+                               0 if g_token_surrogate is None else g_token_surrogate.stride(0), _p(out), out.stride(0),
+                               _st()), "gct_seq_ppo_bwd")
+    return out
+
+
 def chosen_logp(logits2d, ys, pos_dev, out, pad_id, row_off=None, item=None, prefix_len=None):
     """gct_chosen_logp, after select_token on the same logits [n, V] and device counter: out[dst, p] = the model's
     log-probability (raw logits, temperature 1) of the token ys[r, p] the selection has just written at

@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 28
+#define GCT_ABI_VERSION 29
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -502,6 +502,42 @@ int gct_seq_dist_bwd(const float* logits, int64_t ld, int V, int64_t rows_per_se
                      const int32_t* prefix_lens, int64_t pad_id, int n, int W, const float* g_entropy,
                      const float* g_token_entropy, int64_t ld_ge, const float* g_kl, const float* g_token_kl,
                      int64_t ld_gk, float* dlogits, int64_t ld_d, void* stream);
+/* PPO's clipped surrogate, per scored token and per sequence (ABI 29; gct_plus_amd/decode.py ppo_reference states the
+ * rule); gct_seq_logp's geometry and SCORED predicate.  old_token_logp fp32 [n][ld_old >= W]: the log-probabilities the
+ * tokens were sampled with; advantage fp32 [n]: one number per sequence; 0 <= clip_lo < 1, clip_hi >= 0.  At a scored
+ * column, with lp = gct_seq_logp's token_logp (the same bits), A = advantage[r], rho = exp(lp - old): the token is
+ * CLIPPED when A > 0 and rho > 1 + clip_hi, or A < 0 and rho < 1 - clip_lo (strict: rho == 1 never is), and
+ *   token_surrogate [n][ld_out]: A * (1 + clip_hi) clipped high, A * (1 - clip_lo) clipped low, A * rho otherwise
+ *                                (= min(rho A, clamp(rho, 1 - clip_lo, 1 + clip_hi) A) in value);
+ *   token_logp [n][ld_out]:      lp.
+ * Columns that are not scored hold 0 in both tables, and neither their logits rows nor their old_token_logp are read;
+ * all W columns are written.  Per sequence, sums over the scored columns in ascending column order:
+ *   logp [n], surrogate [n], approx_kl [n] (the k3 terms (rho - 1) - (lp - old) of KL(old || new)),
+ *   tokens [n], hits [n] and clipped [n] (int32 counts; hits as gct_seq_logp's).  logp, tokens and hits are
+ *   gct_seq_logp's bits.
+ * Non-finite old_token_logp is not an error: IEEE arithmetic decides the result.  One workgroup per sequence, no
+ * atomics: bit-reproducible.  Shape limits as gct_seq_logp's, ld_old >= W; otherwise, for a null old_token_logp or
+ * advantage and for clips outside their ranges, GCT_ERR_ARG before any launch.  n == 0: nothing is written. */
+int gct_seq_ppo(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift, const int64_t* ys,
+                int64_t ld_ys, const int32_t* prefix_lens, int64_t pad_id, int n, int W, const float* old_token_logp,
+                int64_t ld_old, const float* advantage, float clip_lo, float clip_hi, float* token_logp,
+                float* token_surrogate, int64_t ld_out, float* logp, float* surrogate, float* approx_kl,
+                int32_t* tokens, int32_t* hits, int32_t* clipped, void* stream);
+/* The gradient of gct_seq_ppo's surrogate [n] and token_surrogate [n][W] with respect to the logits
+ * (gct_plus_amd/decode.py ppo_grad_reference states the rule); row numbering and predicate as gct_seq_logp_bwd's.  With
+ * g = g_surrogate[r] + g_token_surrogate[r][c] (fp32 [n] and [n][ld_g]; either may be NULL and then counts as 0, not
+ * both) a scored row whose token is not clipped gets
+ *   dlogits[v] = -((g * A) * rho) * (softmax(x)[v] - [v == ys[r][c]])
+ * in gct_ce_bwd's arithmetic, (g * A) a plain fp32 product: with rho == 1 the bits of gct_seq_logp_bwd for g_logp =
+ * g * A.  A row that is not scored, or whose A or g is 0, gets V exact zeros and its logits are not read; a row whose
+ * token is clipped gets V exact zeros (its logits are read to decide).  All n * rows_per_seq rows of dlogits (row stride
+ * ld_d >= V) are WRITTEN, nothing is accumulated.  One wave per row, no atomics: bit-reproducible.  Refusals as
+ * gct_seq_ppo's and gct_seq_logp_bwd's: GCT_ERR_ARG before any launch.  n == 0: nothing to do. */
+int gct_seq_ppo_bwd(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift, const int64_t* ys,
+                    int64_t ld_ys, const int32_t* prefix_lens, int64_t pad_id, int n, int W,
+                    const float* old_token_logp, int64_t ld_old, const float* advantage, float clip_lo, float clip_hi,
+                    const float* g_surrogate, const float* g_token_surrogate, int64_t ld_g, float* dlogits,
+                    int64_t ld_d, void* stream);
 /* The decode-step form: launched after gct_select_token in the step unit, on the same logits [n][V] and the same
  * device counter.  Row r looks at column p = *pos - row_off[r] + 1 (row_off nullable), the column the selection has
  * just written, takes tok = ys[r][p] and writes out[dst][p] = log-softmax(logits[r])[tok], or 0 when tok == pad_id (a

@@ -8,10 +8,14 @@ the policy's mean entropy per token, which show the collapse a reward alone ends
 time of a reinforce_step (forward + backward + optimizer, the sampling not included).
 --entropy-coef / --kl-coef: the regularised step (an entropy bonus; a KL penalty against Train/finetune.frozen_prior of
 the starting weights, which costs a second, forward-only decoder pass).  No coefficient is prescribed.
+--ppo-epochs K [--clip E]: Train/finetune.ppo_update instead -- K updates per sampled batch under PPO's clipped surrogate
+against the log-probabilities the batch was sampled with (one more forward-only pass per batch); the printed time is
+that of the whole update, and per epoch.
 
 --time-step: no sampling; --n fixed rows of MOSES-like lengths (clip(round(N(35, 8)), 15, 78) tokens + <eos> behind a
 scaffold prefix), --rounds reinforce_steps on them after two warm-up steps: the figure to put next to a bench.py
-training step of the same batch size (recorded in DESIGN 4, not gated)."""
+training step of the same batch size (recorded in DESIGN 4, not gated).  With --ppo-epochs it times ONE epoch:
+ppo_update(epochs=1) against a sampling-time table taken once, before the first step, and that pass on its own."""
 import argparse
 import os
 import sys
@@ -31,7 +35,11 @@ ap.add_argument("--seed", type=int, default=1)
 ap.add_argument("--entropy-coef", type=float, default=0.0, help="entropy bonus per scored token (reinforce_step)")
 ap.add_argument("--kl-coef", type=float, default=0.0,
                 help="penalty on KL(policy || frozen starting weights) per scored token")
-ap.add_argument("--time-step", action="store_true", help="time reinforce_step on fixed rows of MOSES-like lengths")
+ap.add_argument("--ppo-epochs", type=int, default=0,
+                help="K > 0: ppo_update with K epochs per sampled batch instead of one reinforce_step")
+ap.add_argument("--clip", type=float, default=0.2, help="PPO's clip: ratios are held in [1 - E, 1 + E]")
+ap.add_argument("--time-step", action="store_true",
+                help="time reinforce_step (one ppo_update epoch with --ppo-epochs) on fixed rows of MOSES-like lengths")
 a = ap.parse_args()
 
 import numpy as np  # noqa: E402
@@ -42,7 +50,7 @@ from gct_plus_amd.decode import SmilesGrammar  # noqa: E402
 from gct_plus_amd.Inference.sampling_tool import DecodedRows, PscavaetfSampling  # noqa: E402
 from gct_plus_amd.Model import model_dict  # noqa: E402
 from gct_plus_amd.optim import FusedAdam  # noqa: E402
-from gct_plus_amd.Train.finetune import frozen_prior, reinforce_step  # noqa: E402
+from gct_plus_amd.Train.finetune import frozen_prior, ppo_update, reinforce_step  # noqa: E402
 
 mtype = "pscavaetf"
 nc = synthetic.n_conds(mtype)
@@ -60,10 +68,15 @@ gen = torch.Generator().manual_seed(a.seed)
 prior = frozen_prior(model) if a.kl_coef else None
 
 
-def timed_step(rows, reward):
+def timed_step(rows, reward, **ppo):
+    """One update, timed: reinforce_step, or with --ppo-epochs ppo_update (its list of per-epoch results)."""
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    stats = reinforce_step(sampler, opt, rows, reward, entropy_coef=a.entropy_coef, kl_coef=a.kl_coef, prior=prior)
+    if a.ppo_epochs:
+        stats = ppo_update(sampler, opt, rows, reward, **dict(dict(epochs=a.ppo_epochs), **ppo), clip=a.clip,
+                           entropy_coef=a.entropy_coef, kl_coef=a.kl_coef, prior=prior)
+    else:
+        stats = reinforce_step(sampler, opt, rows, reward, entropy_coef=a.entropy_coef, kl_coef=a.kl_coef, prior=prior)
     torch.cuda.synchronize()
     return stats, (time.perf_counter() - t0) * 1e3
 
@@ -83,6 +96,28 @@ if a.time_step:
     rows = DecodedRows(torch.randn(n, Le, dims["latent_dim"], generator=gen).cuda(), ys.cuda(), src_mask.cuda(),
                        torch.randn(n, nc, generator=gen).cuda(), torch.full((n,), t0))
     reward = torch.rand(n, generator=gen)
+    if a.ppo_epochs:
+        model.eval()
+        old_ms = []
+        for _ in range(5):                                # the forward-only pass a batch pays once
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            with torch.no_grad():
+                old = sampler.logp(*rows).token_logp
+            torch.cuda.synchronize()
+            old_ms.append((time.perf_counter() - t1) * 1e3)
+        for _ in range(2):
+            timed_step(rows, reward, epochs=1, old_token_logp=old)
+        ms = []
+        for i in range(a.rounds):
+            (stats,), dt = timed_step(rows, reward, epochs=1, old_token_logp=old)
+            ms.append(dt)
+            print(f"epoch {i}: {dt:8.2f} ms  loss {stats['loss']:.4f}  clipped {stats['clip_fraction']:.3f}  approx_kl "
+                  f"{stats['approx_kl']:.5f}  tokens {stats['tokens']}", flush=True)
+        print(f"ppo_update epoch on {n} {'full-size' if a.full else 'tiny'} {mtype} rows of {W} columns ({stats['tokens']} "
+              f"scored tokens), clip {a.clip}: median {float(np.median(ms)):.2f} ms, best {min(ms):.2f} ms of {len(ms)}; "
+              f"the sampling-time table (one forward-only pass per batch): median {float(np.median(old_ms[1:])):.2f} ms")
+        sys.exit(0)
     for _ in range(2):
         timed_step(rows, reward)
     ms = []
@@ -123,6 +158,8 @@ def evaluate():
 EVAL_SEED = 10 ** 6
 before = evaluate()
 reg = f", entropy_coef {a.entropy_coef}, kl_coef {a.kl_coef}" if a.entropy_coef or a.kl_coef else ""
+if a.ppo_epochs:
+    reg += f", {a.ppo_epochs} PPO epochs per round, clip {a.clip}"
 print(f"{'full-size' if a.full else 'tiny'} {mtype}, {a.n} molecules per round, lr {a.lr}{reg}: evaluation batch before "
       f"fine-tuning: well-formed {before[0]:.3f}, {before[1]} distinct strings, entropy {before[2]:.3f} per token",
       flush=True)
@@ -131,10 +168,17 @@ for k in range(a.rounds):
     rows, reward = sample(a.n, a.seed * 1000 + k)
     stats, dt = timed_step(rows, reward)
     ms.append(dt)
+    if a.ppo_epochs:
+        last = stats[-1]
+        more = "".join(f"  {key[5:]} {last[key]:7.4f}" for key in ("mean_entropy", "mean_kl") if key in last)
+        print(f"round {k:3d}: well-formed {float(reward.mean()):.3f}  loss {stats[0]['loss']:8.4f} -> {last['loss']:8.4f}  "
+              f"clipped {last['clip_fraction']:.3f}  approx_kl {last['approx_kl']:.5f}{more}  update {dt:7.2f} ms "
+              f"({dt / len(stats):.2f} per epoch)", flush=True)
+        continue
     more = "".join(f"  {key[5:]} {stats[key]:7.4f}" for key in ("mean_entropy", "mean_kl") if key in stats)
     print(f"round {k:3d}: well-formed {stats['mean_reward']:.3f}  mean logp {stats['mean_logp']:8.3f}  loss "
           f"{stats['loss']:8.4f}{more}  step {dt:7.2f} ms", flush=True)
 after = evaluate()
 print(f"evaluation batch of {a.n}: well-formed {before[0]:.3f} -> {after[0]:.3f}, distinct strings {before[1]} -> "
-      f"{after[1]}, entropy per token {before[2]:.3f} -> {after[2]:.3f} after {a.rounds} rounds{reg}; reinforce_step "
-      f"median {float(np.median(ms[1:] or ms)):.2f} ms")
+      f"{after[1]}, entropy per token {before[2]:.3f} -> {after[2]:.3f} after {a.rounds} rounds{reg}; "
+      f"{'ppo_update' if a.ppo_epochs else 'reinforce_step'} median {float(np.median(ms[1:] or ms)):.2f} ms")
