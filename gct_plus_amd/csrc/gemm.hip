@@ -1368,23 +1368,33 @@ inline bool x6s_shape(const GemmArgs& g) {
 // forward launches alone) -- while they are at most this many tiles
 constexpr int64_t X6_TAIL_SMALL_MAX = 512;
 
-// skinny fp32 forwards: the panel kernel while it has at most this many 32 x 32 (resp. 32 x 64) tiles; 4096: +9 % / +3 %
-// per decode step at n = 1024 / 4096 over 384
-constexpr int64_t PANEL32_MAX_TILES = 4096, PANEL64_MAX_TILES = 768;
+// skinny fp32 forwards: the panel kernel while it has at most this many 32 x 32 tiles; 4096: +9 % / +3 % per decode step
+// at n = 1024 / 4096 over 384
+constexpr int64_t PANEL32_MAX_TILES = 4096;
 
 // ---- slab routes: K split into fp32 slabs at ws, then splitk_epilogue_kernel applies g's epilogue to their sum
 
 // the split-K form of g: raw partial sums of `splits` K ranges (whole 32-wide K-tiles) into dense [M][N] slabs at ws
 static_assert(BK == XBK, "the fp32 and bf16x6 kernels split K at the same granularity");
+// K range of one slab when K is split `splits` ways, and the slabs that makes (fewer than `splits` when the ranges,
+// whole K-tiles each, cover K sooner)
+inline int64_t slab_krange(int64_t K, int splits) { return ((K / BK + splits - 1) / splits) * BK; }
+inline int slab_count(int64_t K, int splits) {
+  const int64_t ks = slab_krange(K, splits);
+  return (int)((K + ks - 1) / ks);
+}
+
 GemmArgs slab_args(const GemmArgs& g, int splits, float* ws) {
-  const int64_t nkt = g.K / BK;
   GemmArgs p = g;
-  p.ksplit = ((nkt + splits - 1) / splits) * BK;
-  p.nsplit = (int)((g.K + p.ksplit - 1) / p.ksplit);
+  p.ksplit = slab_krange(g.K, splits);
+  p.nsplit = slab_count(g.K, splits);
   p.epi = EPI_SLAB; p.c0 = ws; p.ldc = g.N; p.slab_stride = g.M * g.N;
   p.c_d1 = p.c_d2 = 0; p.c_nper = INT64_MAX / 4; p.bias0 = nullptr; p.resid = nullptr; p.pre = nullptr; p.pre_in = nullptr;
   return p;
 }
+
+// bytes of ws the slab launch p writes
+inline int64_t slabs_written(const GemmArgs& p) { return (int64_t)p.nsplit * p.slab_stride * (int64_t)sizeof(float); }
 
 int launch_fixup(const GemmArgs& g, const GemmArgs& slabs, hipStream_t st, const char* name) {
   const int64_t patches = ((g.M + 3) / 4) * (g.N / 4);
@@ -1394,36 +1404,73 @@ int launch_fixup(const GemmArgs& g, const GemmArgs& slabs, hipStream_t st, const
   return GCT_OK;
 }
 
-// executor of the bf16x6 route: plain, or tail-balanced (x6_tail_plan) with the tail rows on the small-tile kernel
-// or K-split into slabs.  Not in the planner: it depends on whether the stream is being captured.  NP: pieces
-// (3: bf16x6, 2: bf16x3).
-template <int MODE, int NP>
-int launch_x6_tail_split(const GemmArgs& g, hipStream_t st, float* ws, int64_t ws_bytes) {
-  if (MODE == X6_WGRAD || g.nsplit != 1 || !ws || !gct_aligned16(ws)) return launch_x6<MODE, NP>(g, st);
-  int64_t m1 = 0;
-  const int best = x6_tail_plan(g.M, g.N, g.K, &m1);
-  const int64_t m2 = g.M - m1, nkt = g.K / XBK;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;   // keep captured graphs to one kernel per GEMM
-  if (best == 1 || slab_bytes(best, m2, g.N) > ws_bytes ||
-      hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
-    return launch_x6<MODE, NP>(g, st);
-  GemmArgs head = g;
-  head.M = m1;
-  int rc = launch_x6<MODE, NP>(head, st);
-  if (rc) return rc;
-  GemmArgs e = g;                                      // the tail rows as their own problem
-  e.M = m2; e.row_base = g.row_base + m1;
+// ---- what a fwd / dgrad call executed, for gct_gemm_last_route (diagnostics: a few stores per call, written where the
+// kernels are launched).  Layout: out8 of gct_linear_fwd_route.
+thread_local int64_t t_last_route[8] = {-1, 1, 0, 0, 1, 0, 0, 0};
+inline void note_route(int kind, int splits, int launches, int64_t ws_written) {
+  const int64_t r[8] = {kind, splits, 0, 0, 1, launches, ws_written, 0};
+  for (int i = 0; i < 8; ++i) t_last_route[i] = r[i];
+}
+
+// the tail of a bf16 tile launch (GemmRoute::X6, forward / dgrad)
+struct X6Tail {
+  enum Kind { NONE = 0, SMALL_TILES = 1, SLABS = 2 } kind;
+  int splits;        // SLABS: K-splits asked of slab_args (it may make fewer slabs: slab_count); 1 otherwise
+  int64_t m1;        // first tail row (a multiple of 128)
+};
+
+// the tail rows [m1, M) of g as their own problem: the dropout coordinates continue through row_base
+GemmArgs x6_tail_args(const GemmArgs& g, int64_t m1) {
+  GemmArgs e = g;
+  e.M = g.M - m1; e.row_base = g.row_base + m1;
   e.a.p0 += m1 * g.lda;                                // FWD / DGRAD: A is [M][K]
   e.c0 += m1 * g.ldc;
   if (e.resid) e.resid += m1 * g.ldc;
   if (e.pre) e.pre += m1 * g.ldc;
   // pre_in read through the quad map keeps the forward's row space: the tail finds its rows through row_base
   if (e.pre_in && !(g.pre_rows > 0 && g.quad_map)) e.pre_in += m1 * g.ldc;
+  return e;
+}
+
+// Pure: whether (and how) the launch of g on the bf16 tile route is tail-balanced (x6_tail_plan): the tail rows on the
+// small-tile kernel, or K-split into slabs at ws + a fix-up.  Only the capture check is left to the executor.
+template <int MODE>
+X6Tail plan_x6_tail(const GemmArgs& g, const float* ws, int64_t ws_bytes) {
+  const X6Tail none = {X6Tail::NONE, 1, 0};
+  if (MODE == X6_WGRAD || g.nsplit != 1 || !ws || !gct_aligned16(ws)) return none;
+  int64_t m1 = 0;
+  const int best = x6_tail_plan(g.M, g.N, g.K, &m1);
+  const int64_t m2 = g.M - m1, nkt = g.K / XBK;
+  if (best == 1 || slab_bytes(best, m2, g.N) > ws_bytes) return none;
   if (nkt <= 32 && x6s_tiles(m2, g.N) <= X6_TAIL_SMALL_MAX) {
-    if (MODE == X6_FWD && x6s_ok(e, true)) return launch_x6s<X6_FWD, NP>(e, st);
-    if (MODE == X6_DGRAD && x6s_dgrad_ok(e, true)) return launch_x6s<X6_DGRAD, NP>(e, st);
+    const GemmArgs e = x6_tail_args(g, m1);
+    if (MODE == X6_FWD ? x6s_ok(e, true) : x6s_dgrad_ok(e, true)) return {X6Tail::SMALL_TILES, 1, m1};
   }
-  const GemmArgs p = slab_args(e, best, ws);
+  return {X6Tail::SLABS, best, m1};
+}
+
+// executor of the bf16x6 route: plain, or tail-balanced as plan_x6_tail says.  A stream that is being captured gets
+// the plain launch: one kernel per GEMM in a captured graph.  NP: pieces (3: bf16x6, 2: bf16x3).
+template <int MODE, int NP>
+int launch_x6_tail_split(const GemmArgs& g, hipStream_t st, float* ws, int64_t ws_bytes) {
+  X6Tail t = plan_x6_tail<MODE>(g, ws, ws_bytes);
+  if (t.kind != X6Tail::NONE) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;   // keep captured graphs to one kernel per GEMM
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) t.kind = X6Tail::NONE;
+  }
+  if (t.kind == X6Tail::NONE) return launch_x6<MODE, NP>(g, st);
+  GemmArgs head = g;
+  head.M = t.m1;
+  int rc = launch_x6<MODE, NP>(head, st);
+  if (rc) return rc;
+  const GemmArgs e = x6_tail_args(g, t.m1);
+  t_last_route[2] = t.kind; t_last_route[3] = t.m1;
+  if (t.kind == X6Tail::SMALL_TILES) {
+    t_last_route[5] = 2;
+    return launch_x6s<MODE == X6_DGRAD ? X6_DGRAD : X6_FWD, NP>(e, st);   // never X6_WGRAD: plan_x6_tail
+  }
+  const GemmArgs p = slab_args(e, t.splits, ws);
+  t_last_route[4] = p.nsplit; t_last_route[5] = 3; t_last_route[6] = slabs_written(p);
   rc = launch_x6<MODE, NP>(p, st);
   if (rc) return rc;
   return launch_fixup(e, p, st, "x6 tail fix-up");
@@ -1436,7 +1483,6 @@ struct GemmRoute {
     X6_SPLITK_ALL,  // gemm_x6_kernel with K split `splits` ways into slabs + fix-up
     PANEL_THIN,     // gemm_f32_panel_kernel<32, RAGGED>: N <= 32
     PANEL32,        // gemm_f32_panel_kernel<32>: the whole reduction in one workgroup per 32 x 32 tile
-    PANEL64,        // gemm_f32_panel_kernel<64>
     F32_SMALL,      // gemm_f32_small_kernel: 64 x 64 fp32 tiles, K split `splits` ways into slabs + fix-up when > 1
     X6,             // gemm_x6_kernel: 128 x 256 bf16x6 tiles, tail-balanced by launch_x6_tail_split
     F32_FAST,       // gemm_f32_fast_kernel
@@ -1445,6 +1491,11 @@ struct GemmRoute {
   } kind;
   int splits;
 };
+static_assert(GemmRoute::X6S == GCT_GEMM_ROUTE_X6S && GemmRoute::X6_SPLITK_ALL == GCT_GEMM_ROUTE_X6_SPLITK_ALL &&
+                  GemmRoute::PANEL_THIN == GCT_GEMM_ROUTE_PANEL_THIN && GemmRoute::PANEL32 == GCT_GEMM_ROUTE_PANEL32 &&
+                  GemmRoute::F32_SMALL == GCT_GEMM_ROUTE_F32_SMALL && GemmRoute::X6 == GCT_GEMM_ROUTE_X6 &&
+                  GemmRoute::F32_FAST == GCT_GEMM_ROUTE_F32_FAST && GemmRoute::F32_VEC == GCT_GEMM_ROUTE_F32_VEC &&
+                  GemmRoute::F32 == GCT_GEMM_ROUTE_F32, "GCT_GEMM_ROUTE_* are the kinds of GemmRoute");
 
 // The first row whose shape condition holds wins.  Pure: no launches, no environment; `mode` is the arithmetic mode
 // (bf16x6 and bf16x3 plan alike: the X6* routes then run the 3- resp. 2-piece kernels), ws / ws_bytes the caller's
@@ -1479,7 +1530,6 @@ GemmRoute plan_gemm(const GemmArgs& g, bool vec, int mode, const float* ws, int6
       const int64_t tm32 = (g.M + 31) / 32;
       if (g.N % 32 == 0 && (g.b_nper >= g.N || g.b_nper % 32 == 0) && tm32 * (g.N / 32) <= PANEL32_MAX_TILES)
         return {GemmRoute::PANEL32, 1};
-      if (g.N % 64 == 0 && tm32 * (g.N / 64) <= PANEL64_MAX_TILES) return {GemmRoute::PANEL64, 1};
     }
     int64_t ns = 1;
     if (ws_ok) {
@@ -1499,7 +1549,10 @@ template <bool A_KC, bool B_KC>
 int launch(const GemmArgs& g, bool vec, hipStream_t st, float* ws = nullptr, int64_t ws_bytes = 0) {
   constexpr int MODE = A_KC ? (B_KC ? X6_FWD : X6_DGRAD) : X6_WGRAD;
   const int64_t tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN) * g.nsplit;
-  if (tiles <= 0) return GCT_OK;
+  if (tiles <= 0) {
+    if (A_KC) note_route(GCT_GEMM_ROUTE_NONE, 1, 0, 0);
+    return GCT_OK;
+  }
   if (tiles > INT_MAX) {
     gct_set_error("gemm: grid too large");
     return GCT_ERR_ARG;
@@ -1507,6 +1560,7 @@ int launch(const GemmArgs& g, bool vec, hipStream_t st, float* ws = nullptr, int
   const int mode = gemm_mode();
   const bool x3 = mode == GCT_GEMM_BF16X3;
   const GemmRoute r = plan_gemm<A_KC, B_KC>(g, vec, mode, ws, ws_bytes);
+  if (A_KC) note_route(r.kind, 1, 1, 0);               // forward / dgrad; the slab routes and the tail add theirs below
   switch (r.kind) {
     case GemmRoute::X6S:
       if (x3) return launch_x6s<B_KC ? X6_FWD : X6_DGRAD, 2>(g, st);
@@ -1514,6 +1568,7 @@ int launch(const GemmArgs& g, bool vec, hipStream_t st, float* ws = nullptr, int
       return launch_x6s<B_KC ? X6_FWD : X6_DGRAD, 3>(g, st);
     case GemmRoute::X6_SPLITK_ALL: {
       const GemmArgs p = slab_args(g, r.splits, ws);
+      if (A_KC) note_route(r.kind, p.nsplit, 2, slabs_written(p));
       int rc = x3 ? launch_x6<MODE, 2>(p, st) : launch_x6<MODE, 3>(p, st);
       if (!rc) rc = launch_fixup(g, p, st, "x6 split-K fix-up");
       if (!rc && !x3) ++g_gemm_launches[1];
@@ -1524,8 +1579,6 @@ int launch(const GemmArgs& g, bool vec, hipStream_t st, float* ws = nullptr, int
       return launch_panel<32, true>(g, st);
     case GemmRoute::PANEL32:
       return launch_panel<32>(g, st);
-    case GemmRoute::PANEL64:
-      return launch_panel<64>(g, st);
     case GemmRoute::F32_SMALL: {
       const int64_t tiles64 = ((g.M + 63) / 64) * ((g.N + 63) / 64);
       if (r.splits == 1) {
@@ -1534,6 +1587,7 @@ int launch(const GemmArgs& g, bool vec, hipStream_t st, float* ws = nullptr, int
         return GCT_OK;
       }
       const GemmArgs p = slab_args(g, r.splits, ws);
+      if (A_KC) note_route(r.kind, p.nsplit, 2, slabs_written(p));
       hipLaunchKernelGGL(gemm_f32_small_kernel, dim3((unsigned)(tiles64 * p.nsplit)), dim3(256), 0, st, p);
       GCT_LAUNCH_CHECK("gemm_f32_small(split-K)");
       return launch_fixup(g, p, st, "splitk_epilogue");
@@ -1668,6 +1722,32 @@ extern "C" int64_t gct_wgrad_ws_bytes(int64_t M, int64_t Ntot, int64_t K) {
   return (need > cs ? need : cs) * (int64_t)sizeof(float) + 256;
 }
 
+// the shape half of a forward / dgrad launch (the calls add their addresses, the route queries stand-ins that carry the
+// alignment and which buffers there are), and the calls' vector tests
+static GemmArgs fwd_args(int64_t M, int K, int nseg, int nper, int64_t ldx, int64_t ldw, int64_t ldy, int epi) {
+  GemmArgs g = {};
+  g.M = M; g.N = (int64_t)nseg * nper; g.K = K;
+  g.lda = ldx; g.a_nper = INT64_MAX / 4;
+  g.ldb = ldw; g.b_nper = nper;
+  g.ldc = ldy; g.c_nper = nper;
+  g.ksplit = K; g.nsplit = 1; g.epi = epi;
+  return g;
+}
+static bool fwd_vec_shape(int K, int64_t ldx, int64_t ldw) { return (ldx % 4 == 0) && (ldw % 4 == 0) && (K % 4 == 0); }
+
+static GemmArgs dgrad_args(int64_t M, int nseg, int nper, int K, int64_t lddy, int64_t ldw, int64_t lddx, int depi) {
+  GemmArgs g = {};
+  g.M = M; g.N = K; g.K = (int64_t)nseg * nper;  // reduce over the layer's output features
+  g.lda = lddy; g.a_nper = nper;
+  g.ldb = ldw; g.b_nper = nper;
+  g.ldc = lddx; g.c_nper = INT64_MAX / 4;
+  g.ksplit = g.K; g.nsplit = 1; g.epi = EPI_D0 + depi;
+  return g;
+}
+static bool dgrad_vec_shape(int nper, int K, int64_t lddy, int64_t ldw) {
+  return (lddy % 4 == 0) && (ldw % 4 == 0) && (nper % 4 == 0) && (K % 4 == 0);
+}
+
 extern "C" int gct_linear_fwd(const float* x, int64_t ldx, int64_t M, int K, const float* w0,
                               const float* w1, const float* w2, int64_t ldw, const uint16_t* wp0,
                               int64_t plane_stride, const float* b0, const float* b1,
@@ -1686,21 +1766,18 @@ extern "C" int gct_linear_fwd(const float* x, int64_t ldx, int64_t M, int K, con
   GCT_CHECK_ARG((epi != GCT_EPI_GELU_DROP && epi != GCT_EPI_GELU_DROP_SAVE) || pre, "linear_fwd: GELU epilogue needs pre");
   GCT_CHECK_ARG(epi != GCT_EPI_DROP_RESID || resid, "linear_fwd: residual epilogue needs resid");
   GCT_CHECK_ARG(p >= 0.f && p < 1.f, "linear_fwd: dropout p out of range");
-  GemmArgs g = {};
-  g.M = M; g.N = (int64_t)nseg * nper; g.K = K;
   GCT_CHECK_ARG(!b0 || nseg < 2 || b1, "linear_fwd: bias of segment 1 missing");
   GCT_CHECK_ARG(!b0 || nseg < 3 || b2, "linear_fwd: bias of segment 2 missing");
-  g.a = mkseg(x, nullptr, nullptr); g.lda = ldx; g.a_nper = INT64_MAX / 4;
-  g.b = mkseg(w0, w1, w2); g.ldb = ldw; g.b_nper = nper;
-  g.c0 = y0; g.c_d1 = y1 ? y1 - y0 : 0; g.c_d2 = y2 ? y2 - y0 : 0; g.ldc = ldy; g.c_nper = nper;
-  g.ksplit = K; g.nsplit = 1; g.epi = epi;
+  GemmArgs g = fwd_args(M, K, nseg, nper, ldx, ldw, ldy, epi);
+  g.a = mkseg(x, nullptr, nullptr);
+  g.b = mkseg(w0, w1, w2);
+  g.c0 = y0; g.c_d1 = y1 ? y1 - y0 : 0; g.c_d2 = y2 ? y2 - y0 : 0;
   g.bias0 = b0; g.bias_d1 = (b0 && b1) ? b1 - b0 : 0; g.bias_d2 = (b0 && b2) ? b2 - b0 : 0;
   g.resid = resid; g.pre = pre;
   g.thr = gct_drop_threshold(p); g.keep_scale = 1.0f / (1.0f - p); g.rng = gct_rng_make(seed, site);
   g.bp0 = wp0; g.bp_stride = plane_stride;
   g.quad_map = quad_map;          // rows are a quad compaction: the dropout coordinates of the epilogues follow the map
-  const bool vec = al16(x) && al16(w0) && al16(w1) && al16(w2) && (ldx % 4 == 0) &&
-                   (ldw % 4 == 0) && (K % 4 == 0);
+  const bool vec = al16(x) && al16(w0) && al16(w1) && al16(w2) && fwd_vec_shape(K, ldx, ldw);
   return launch<true, true>(g, vec, (hipStream_t)stream, ws, ws ? ws_bytes : 0);   // every slab route checks its need against ws_bytes
 }
 
@@ -1771,20 +1848,99 @@ extern "C" int gct_linear_dgrad(const float* dy0, const float* dy1, const float*
   GCT_CHECK_ARG(depi != GCT_DEPI_GELU_BWD || pre, "linear_dgrad: GELU bwd needs pre");
   GCT_CHECK_ARG(depi != GCT_DEPI_MUL_SAVED || pre, "linear_dgrad: saved-factor epilogue needs pre");
   GCT_CHECK_ARG(p >= 0.f && p < 1.f, "linear_dgrad: dropout p out of range");
-  GemmArgs g = {};
-  g.M = M; g.N = K; g.K = (int64_t)nseg * nper;  // reduce over the layer's output features
-  g.a = mkseg(dy0, dy1, dy2); g.lda = lddy; g.a_nper = nper;
-  g.b = mkseg(w0, w1, w2); g.ldb = ldw; g.b_nper = nper;
-  g.c0 = dx; g.ldc = lddx; g.c_nper = INT64_MAX / 4;
-  g.ksplit = g.K; g.nsplit = 1; g.epi = EPI_D0 + depi;
+  GemmArgs g = dgrad_args(M, nseg, nper, K, lddy, ldw, lddx, depi);
+  g.a = mkseg(dy0, dy1, dy2);
+  g.b = mkseg(w0, w1, w2);
+  g.c0 = dx;
   g.pre_in = pre;
   g.thr = gct_drop_threshold(p); g.keep_scale = 1.0f / (1.0f - p); g.rng = gct_rng_make(seed, site);
   g.bp0 = wp0; g.bp_stride = plane_stride;
   g.quad_map = quad_map;
   g.pre_rows = quad_map ? pre_rows : 0;
   const bool vec = al16(dy0) && al16(dy1) && al16(dy2) && al16(w0) && al16(w1) && al16(w2) &&
-                   (lddy % 4 == 0) && (ldw % 4 == 0) && (nper % 4 == 0) && (K % 4 == 0);
+                   dgrad_vec_shape(nper, K, lddy, ldw);
   return launch<true, false>(g, vec, (hipStream_t)stream, ws, ws ? ws_bytes : 0);
+}
+
+// ---- route queries of the forward / dgrad calls: the calls' own GemmArgs helpers, plan_gemm and plan_x6_tail on
+// stand-in addresses (only alignment and presence are read); launch() writes the same eight numbers as it launches
+template <bool B_KC>
+static void report_route(const GemmArgs& g, bool vec, int mode, const float* ws, int64_t ws_bytes, int64_t* out8) {
+  constexpr int MODE = B_KC ? X6_FWD : X6_DGRAD;
+  int64_t r8[8] = {GCT_GEMM_ROUTE_NONE, 1, 0, 0, 1, 0, 0, 0};
+  if (g.M > 0) {
+    const GemmRoute r = plan_gemm<true, B_KC>(g, vec, mode, ws, ws_bytes);
+    r8[0] = r.kind; r8[5] = 1;
+    if (r.kind == GemmRoute::X6_SPLITK_ALL || (r.kind == GemmRoute::F32_SMALL && r.splits > 1)) {
+      const GemmArgs p = slab_args(g, r.splits, nullptr);
+      r8[1] = p.nsplit; r8[5] = 2; r8[6] = slabs_written(p);
+    } else if (r.kind == GemmRoute::X6) {
+      const X6Tail t = plan_x6_tail<MODE>(g, ws, ws_bytes);
+      if (t.kind != X6Tail::NONE) { r8[2] = t.kind; r8[3] = t.m1; r8[5] = 2; }
+      if (t.kind == X6Tail::SLABS) {
+        const GemmArgs p = slab_args(x6_tail_args(g, t.m1), t.splits, nullptr);
+        r8[4] = p.nsplit; r8[5] = 3; r8[6] = slabs_written(p);
+      }
+    }
+  }
+  for (int i = 0; i < 8; ++i) out8[i] = r8[i];
+}
+
+static const float* standin(bool present, bool aligned16) {
+  return present ? reinterpret_cast<const float*>((uintptr_t)(aligned16 ? 16 : 4)) : nullptr;
+}
+
+extern "C" int gct_linear_fwd_route(int64_t M, int K, int nseg, int nper, int64_t ldx, int64_t ldw, int64_t ldy, int epi,
+                                    int aligned16, int have_planes, int have_bias, int mode, int64_t ws_bytes,
+                                    int64_t* out8) {
+  GCT_CHECK_ARG(out8 && M >= 0 && K > 0 && nseg >= 1 && nseg <= 3 && nper > 0 && ldx >= 0 && ldw >= 0 && ldy >= 0 &&
+                    ws_bytes >= 0, "linear_fwd_route: bad args");
+  GCT_CHECK_ARG(epi >= GCT_EPI_BIAS && epi <= GCT_EPI_GELU_DROP_SAVE, "linear_fwd_route: unknown epilogue %d", epi);
+  GCT_CHECK_ARG(epi == GCT_EPI_BIAS || nseg == 1, "linear_fwd_route: fused epilogues need nseg == 1");
+  GCT_CHECK_ARG(mode == GCT_GEMM_F32 || mode == GCT_GEMM_BF16X6 || mode == GCT_GEMM_BF16X3,
+                "linear_fwd_route: unknown mode %d", mode);
+  const bool al = aligned16 != 0;
+  GemmArgs g = fwd_args(M, K, nseg, nper, ldx, ldw, ldy, epi);
+  g.a.p0 = standin(true, al);
+  g.b.p0 = standin(true, al);
+  g.b.d1 = nseg > 1 ? (int64_t)nper * ldw : 0; g.b.d2 = nseg > 2 ? 2 * (int64_t)nper * ldw : 0;
+  g.c0 = const_cast<float*>(standin(true, al));
+  g.c_d1 = nseg > 1 ? nper : 0; g.c_d2 = nseg > 2 ? 2 * (int64_t)nper : 0;
+  g.bias0 = standin(have_bias != 0, al); g.bias_d1 = have_bias ? g.c_d1 : 0; g.bias_d2 = have_bias ? g.c_d2 : 0;
+  g.resid = standin(epi == GCT_EPI_DROP_RESID, al);
+  g.pre = const_cast<float*>(standin(epi == GCT_EPI_GELU_DROP || epi == GCT_EPI_GELU_DROP_SAVE, al));
+  g.bp0 = reinterpret_cast<const uint16_t*>(standin(have_planes != 0, true));
+  g.bp_stride = g.N * g.K;
+  report_route<true>(g, al && fwd_vec_shape(K, ldx, ldw), mode, standin(ws_bytes > 0, al), ws_bytes, out8);
+  return GCT_OK;
+}
+
+extern "C" int gct_linear_dgrad_route(int64_t M, int nseg, int nper, int K, int64_t lddy, int64_t ldw, int64_t lddx,
+                                      int depi, int aligned16, int have_planes, int mode, int64_t ws_bytes,
+                                      int64_t* out8) {
+  GCT_CHECK_ARG(out8 && M >= 0 && K > 0 && nseg >= 1 && nseg <= 3 && nper > 0 && lddy >= 0 && ldw >= 0 && lddx >= 0 &&
+                    ws_bytes >= 0, "linear_dgrad_route: bad args");
+  GCT_CHECK_ARG(depi >= GCT_DEPI_STORE && depi <= GCT_DEPI_MUL_SAVED, "linear_dgrad_route: unknown epilogue %d", depi);
+  GCT_CHECK_ARG(mode == GCT_GEMM_F32 || mode == GCT_GEMM_BF16X6 || mode == GCT_GEMM_BF16X3,
+                "linear_dgrad_route: unknown mode %d", mode);
+  const bool al = aligned16 != 0;
+  GemmArgs g = dgrad_args(M, nseg, nper, K, lddy, ldw, lddx, depi);
+  g.a.p0 = standin(true, al);
+  g.a.d1 = nseg > 1 ? nper : 0; g.a.d2 = nseg > 2 ? 2 * (int64_t)nper : 0;
+  g.b.p0 = standin(true, al);
+  g.b.d1 = nseg > 1 ? (int64_t)nper * ldw : 0; g.b.d2 = nseg > 2 ? 2 * (int64_t)nper * ldw : 0;
+  g.c0 = const_cast<float*>(standin(true, al));
+  g.pre_in = standin(depi == GCT_DEPI_GELU_BWD || depi == GCT_DEPI_MUL_SAVED, al);
+  g.bp0 = reinterpret_cast<const uint16_t*>(standin(have_planes != 0, true));
+  g.bp_stride = g.N * g.K;
+  report_route<false>(g, al && dgrad_vec_shape(nper, K, lddy, ldw), mode, standin(ws_bytes > 0, al), ws_bytes, out8);
+  return GCT_OK;
+}
+
+extern "C" int gct_gemm_last_route(int64_t* out8) {
+  GCT_CHECK_ARG(out8, "gemm_last_route: null");
+  for (int i = 0; i < 8; ++i) out8[i] = t_last_route[i];
+  return GCT_OK;
 }
 
 extern "C" int gct_linear_wgrad(const float* dy0, const float* dy1, const float* dy2, int64_t lddy,
@@ -1953,11 +2109,8 @@ struct BwdShape {           // what the routes of a gct_linear_bwd call depend o
 };
 
 GemmArgs dgrad_shape_args(const BwdShape& b, float* dx, const uint16_t* wp0, int64_t plane_stride) {
-  GemmArgs g = {};
-  g.M = b.M; g.N = b.K; g.K = (int64_t)b.nseg * b.nper;
-  g.lda = b.lddy; g.a_nper = b.nper; g.ldb = b.ldw; g.b_nper = b.nper;
-  g.c0 = dx; g.ldc = b.lddx; g.c_nper = INT64_MAX / 4;
-  g.ksplit = g.K; g.nsplit = 1; g.epi = EPI_D0 + b.depi;
+  GemmArgs g = dgrad_args(b.M, b.nseg, b.nper, b.K, b.lddy, b.ldw, b.lddx, b.depi);
+  g.c0 = dx;
   g.bp0 = wp0; g.bp_stride = plane_stride;
   return g;
 }
@@ -1967,7 +2120,7 @@ GemmArgs dgrad_shape_args(const BwdShape& b, float* dx, const uint16_t* wp0, int
 BwdPairPlan plan_bwd_pair(const BwdShape& b, GemmArgs& gw, const GemmArgs& gd, int64_t wws_bytes, const float* dws,
                           int64_t dws_bytes) {
   const bool vec_w = b.aligned16 && wgrad_vec_shape(b.lddy, b.ldx, b.nper, b.K);
-  const bool vec_d = b.aligned16 && (b.lddy % 4 == 0) && (b.ldw % 4 == 0) && (b.nper % 4 == 0) && (b.K % 4 == 0);
+  const bool vec_d = b.aligned16 && dgrad_vec_shape(b.nper, b.K, b.lddy, b.ldw);
   const WgradRoute wr = plan_wgrad(gw, vec_w, b.want_bias, b.mode);          // sets gw.ksplit / gw.nsplit
   BwdPairPlan r = {false, gw.nsplit, gw.ksplit, wr.bias_fused, 0, 0, 0.0, 0.0};
   if (wr.kind != GemmRoute::X6) return r;

@@ -317,6 +317,43 @@ def wgrad_route(M, nseg, nper, K, lddy, ldx, aligned16=True, want_bias=True, mod
     return tuple(int(v) for v in out)
 
 
+def linear_fwd_route(M, K, nseg, nper, ldx=None, ldw=None, ldy=None, epi=EPI_BIAS, aligned16=True, have_planes=True,
+                     have_bias=True, mode=None, ws_bytes=None):
+    """out8 of gct_linear_fwd_route (no launch): (route kind, slabs, tail, first tail row, tail slabs, launches, bytes of
+    ws written, 0).  ws_bytes None: a workspace of gct_linear_fwd_ws_bytes."""
+    import ctypes
+    out = (ctypes.c_int64 * 8)()
+    if ws_bytes is None:
+        ws_bytes = _L().gct_linear_fwd_ws_bytes(M, K, nseg * nper)
+    check(_L().gct_linear_fwd_route(M, K, nseg, nper, K if ldx is None else ldx, K if ldw is None else ldw,
+                                    nseg * nper if ldy is None else ldy, epi, int(aligned16), int(have_planes),
+                                    int(have_bias), gemm_get_mode() if mode is None else int(mode), int(ws_bytes),
+                                    ctypes.addressof(out)), "gct_linear_fwd_route")
+    return tuple(int(v) for v in out)
+
+
+def linear_dgrad_route(M, nseg, nper, K, lddy=None, ldw=None, lddx=None, depi=DEPI_STORE, aligned16=True,
+                       have_planes=True, mode=None, ws_bytes=None):
+    """out8 of gct_linear_dgrad_route (no launch), as linear_fwd_route."""
+    import ctypes
+    out = (ctypes.c_int64 * 8)()
+    if ws_bytes is None:
+        ws_bytes = _L().gct_linear_dgrad_ws_bytes(M, nseg * nper, K)
+    check(_L().gct_linear_dgrad_route(M, nseg, nper, K, nseg * nper if lddy is None else lddy, K if ldw is None else ldw,
+                                      K if lddx is None else lddx, depi, int(aligned16), int(have_planes),
+                                      gemm_get_mode() if mode is None else int(mode), int(ws_bytes),
+                                      ctypes.addressof(out)), "gct_linear_dgrad_route")
+    return tuple(int(v) for v in out)
+
+
+def gemm_last_route():
+    """out8 of gct_gemm_last_route: what the latest linear_fwd / linear_dgrad of this thread executed."""
+    import ctypes
+    out = (ctypes.c_int64 * 8)()
+    check(_L().gct_gemm_last_route(ctypes.addressof(out)), "gct_gemm_last_route")
+    return tuple(int(v) for v in out)
+
+
 def split_planes(flat: torch.Tensor, planes: Optional[torch.Tensor] = None) -> torch.Tensor:
     """flat fp32 [numel] -> int16 [3, numel] holding the hi / mid / lo bf16 pieces of every element
     (exact: hi + mid + lo == x).  numel % 4 == 0."""

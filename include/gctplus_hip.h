@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 29
+#define GCT_ABI_VERSION 30
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -112,7 +112,8 @@ int gct_linear_fwd(const float* x, int64_t ldx, int64_t M, int K,
  * route at all; nothing is ever written past ws + ws_bytes.
  * quad_map (nullable): the M rows are a quad compaction of a larger row space (gct_live_rows); the dropout masks of the
  * GCT_EPI_GELU_DROP / GCT_EPI_DROP_RESID epilogues are then drawn at the coordinates of original quad quad_map[q] for
- * compact quad q, i.e. every live row gets exactly the mask it would get in the full row space. */
+ * compact quad q, i.e. every live row gets exactly the mask it would get in the full row space.  The map holds M / 4
+ * entries followed by at least 32 readable ones (any value): a tile's rows beyond M look theirs up. */
 int64_t gct_linear_fwd_ws_bytes(int64_t M, int K, int Ntot);
 
 /* dx[m][k] (op)= sum_s sum_n dy_s[m][n] * w_s[n][k]
@@ -143,6 +144,45 @@ int gct_linear_dgrad(const float* dy0, const float* dy1, const float* dy2, int64
  * few tiles across the whole chip; gct_linear_fwd_ws_bytes covers the forward (skinny split-K or tail slabs, whichever
  * the launch would use).  Without one every launch is a single kernel. */
 int64_t gct_linear_dgrad_ws_bytes(int64_t M, int Ntot, int K);
+
+/* The route gct_linear_fwd / gct_linear_dgrad take for a shape (ABI 30; no launch, no device access; the rule the calls
+ * themselves execute, on the calls' own argument builders):
+ *   out8[0] kernel(s), a GCT_GEMM_ROUTE_* value (GCT_GEMM_ROUTE_NONE for M == 0: nothing is launched);
+ *   out8[1] slabs a K-split route writes (GCT_GEMM_ROUTE_X6_SPLITK_ALL, GCT_GEMM_ROUTE_F32_SMALL), 1 otherwise;
+ *   out8[2] tail of a GCT_GEMM_ROUTE_X6 launch: 0 none, 1 the tail rows on 64 x 128 tiles, 2 the tail rows K-split into
+ *           slabs + a fix-up kernel.  Reported for a stream that is not being captured: under capture there is no tail;
+ *   out8[3] first tail row (a multiple of 128; 0 without a tail);
+ *   out8[4] slabs of the tail (1 unless out8[2] == 2);
+ *   out8[5] kernel launches of the call, fix-up kernels included;
+ *   out8[6] bytes of ws the call writes, from ws on (0: ws is not touched; never above the matching *_ws_bytes query);
+ *   out8[7] 0.
+ * A tail on 64 x 128 tiles writes no slabs, yet like the slab tail it is taken only where ws_bytes would hold the
+ * slabs of the tail rows (one rule for both).
+ * aligned16: every buffer of the call (x / dy, w, y / dx, bias, resid, pre, ws) is 16-byte aligned.  Segments are taken
+ * to lie where the model keeps them: the weights stacked in one [nseg * nper][ldw] buffer, outputs / dy* and biases side
+ * by side (segment s at column s * nper of one [M][ld] buffer).  have_planes: wp0 != NULL, 16-byte aligned, with a
+ * plane_stride that is a multiple of 8.  have_bias: b0 != NULL.  resid / pre are present exactly where the epilogue
+ * needs them.  mode: a GCT_GEMM_* value (below), passed in rather than read from the process; bf16x6 and bf16x3 plan
+ * alike.  ws_bytes: that of the call; 0: ws == NULL.
+ * An argument error (unknown mode or epilogue, a negative size, out8 == NULL) returns GCT_ERR_ARG and leaves out8 alone. */
+#define GCT_GEMM_ROUTE_NONE (-1)
+#define GCT_GEMM_ROUTE_X6S 0           /* gemm_x6s_kernel: 64 x 128 bf16 tiles over the whole problem */
+#define GCT_GEMM_ROUTE_X6_SPLITK_ALL 1 /* gemm_x6_kernel, K split into slabs over the whole problem, + fix-up */
+#define GCT_GEMM_ROUTE_PANEL_THIN 2    /* gemm_f32_panel_kernel<32, ragged>: N <= 32 (the vocabulary head) */
+#define GCT_GEMM_ROUTE_PANEL32 3       /* gemm_f32_panel_kernel<32>: the whole reduction in one workgroup per 32 x 32 tile */
+#define GCT_GEMM_ROUTE_F32_SMALL 4     /* gemm_f32_small_kernel: 64 x 64 fp32 tiles; out8[1] > 1: K-split slabs + fix-up */
+#define GCT_GEMM_ROUTE_X6 5            /* gemm_x6_kernel: 128 x 256 bf16 tiles, with the tail of out8[2] */
+#define GCT_GEMM_ROUTE_F32_FAST 6      /* gemm_f32_fast_kernel */
+#define GCT_GEMM_ROUTE_F32_VEC 7       /* gemm_f32_kernel, float4 loads */
+#define GCT_GEMM_ROUTE_F32 8           /* gemm_f32_kernel, scalar loads */
+int gct_linear_fwd_route(int64_t M, int K, int nseg, int nper, int64_t ldx, int64_t ldw, int64_t ldy, int epi,
+                         int aligned16, int have_planes, int have_bias, int mode, int64_t ws_bytes, int64_t* out8);
+int gct_linear_dgrad_route(int64_t M, int nseg, int nper, int K, int64_t lddy, int64_t ldw, int64_t lddx, int depi,
+                           int aligned16, int have_planes, int mode, int64_t ws_bytes, int64_t* out8);
+/* diagnostics: what the most recent gct_linear_fwd / gct_linear_dgrad call on this thread executed, in the layout above,
+ * written by the launcher where it launches (not a second run of the planner); under stream capture out8[2] is 0 and a
+ * GCT_GEMM_ROUTE_X6 call is one launch.  Before the first call: GCT_GEMM_ROUTE_NONE. */
+int gct_gemm_last_route(int64_t* out8);
 
 /* dw_s[n][k] = sum_m dy_s[m][n] * x[m][k] ; db_s[n] = sum_m dy_s[m][n]  (overwrite).
  * Split over M into fp32 slabs in ws, reduced deterministically (no atomics).

@@ -7,6 +7,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import gemm_ref as GR
+from tests import wgrad_ref as WR
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -491,11 +494,11 @@ def test_linear_bf16x6_vs_fp64(ops, M, K, nper, nseg):
     refs = (x.double() @ W.t() + torch.cat(bs).double(), dy.double() @ W, dy.double().t() @ x.double(), dy.double().sum(0))
     assert res[ops.GEMM_F32][4] == 0
     x6_launches = res[ops.GEMM_BF16X6][4]
-    big = -(-M // 128) * -(-N // 128) >= 192           # smaller forward launches take the skinny-M kernel ...
-    small_t, nkt = -(-M // 64) * -(-N // 128), K // 32   # ... or the 64 x 128-tile bf16x6 kernel
-    x6s = (-(-M // 128) * -(-N // 256) <= 160 and 96 <= small_t <= (512 if nkt <= 16 else 256) and nkt <= 32 and
-           (nseg == 1 or nper % 128 == 0))
-    expect = (1 if (x6s or (big and (nseg == 1 or nper % 256 == 0))) else 0) + (1 if N % 32 == 0 else 0) + (1 if M % 32 == 0 else 0)
+    # the three calls that the library's own route queries send to a bf16x6 kernel (skinny forwards, ragged shapes and
+    # segments that are no whole tiles take the fp32 kernels)
+    expect = ((ops.linear_fwd_route(M, K, nseg, nper, mode=ops.GEMM_BF16X6)[0] in GR.BF16_KINDS) +
+              (ops.linear_dgrad_route(M, nseg, nper, K, mode=ops.GEMM_BF16X6)[0] in GR.BF16_KINDS) +
+              (ops.wgrad_route(M, nseg, nper, K, N, K, mode=ops.GEMM_BF16X6)[0] == WR.BF16_TILES))
     assert x6_launches == expect, (x6_launches, expect)
     tols = ((2e-5, 2e-5), (5e-5, 5e-5), (1e-4 * math.sqrt(M / 100 + 1), 1e-4), (1e-4 * math.sqrt(M / 100 + 1), 1e-4))
     for i, what in enumerate(("fwd", "dgrad", "wgrad", "bias grad")):
@@ -631,10 +634,11 @@ def test_linear_bf16x6_epilogues_and_dropout_masks(ops, M, N):
 @pytest.mark.parametrize("M,K,nper,nseg", [(512, 512, 512, 1), (512, 512, 512, 3), (512, 512, 2048, 1),
                                            (512, 2048, 512, 1), (77, 512, 64, 1), (300, 768, 128, 2)])
 def test_linear_panel_kernel_small_problems(ops, M, K, nper, nseg):
-    """The decode-step shapes (few 32 x TN tiles, K a multiple of 256) take gemm_f32_panel_kernel: whole reduction in
-    one workgroup, fused epilogue, no split-K slabs.  Values vs fp64 for the plain, GELU(+pre) and residual
-    epilogues; the same launches with GCT's other skinny route (split-K + fix-up, forced through splitk_ws) agree to
-    fp32 rounding."""
+    """The decode-step shapes (few 32 x 32 tiles, K a multiple of 256) take gemm_f32_panel_kernel<32>: whole reduction in
+    one workgroup, fused epilogue, no split-K slabs -- with or without a workspace (gct_gemm_last_route says so).
+    Values vs fp64 for the plain, GELU(+pre) and residual epilogues.  The other skinny route, gemm_f32_small_kernel
+    with K split into slabs + the fix-up kernel, takes the K = 384 twin of the shape (no multiple of 256) through
+    splitk_ws: asserted by route and compared with fp64."""
     N = nper * nseg
     x = rnd(M, K, seed=1)
     ws = [rnd(nper, K, seed=10 + s, scale=K ** -0.5) for s in range(nseg)]
@@ -646,17 +650,32 @@ def test_linear_panel_kernel_small_problems(ops, M, K, nper, nseg):
     y, pre, y2 = (torch.empty(M, N, device=DEV) for _ in range(3))
     outs = lambda t: [t[:, s * nper:] for s in range(nseg)]                     # noqa: E731
     ops.linear_fwd(xg, wg, bg, outs(y), N)
+    assert ops.gemm_last_route()[0] == GR.PANEL32
     close(y, u, 2e-5, 2e-5, "panel: bias")
     if nseg == 1:
         ops.linear_fwd(xg, wg, bg, [y], N, epi=ops.EPI_GELU_DROP, pre=pre, p=0.0, seed=1, site=1)
+        assert ops.gemm_last_route()[0] == GR.PANEL32
         close(pre, u, 2e-5, 2e-5, "panel: pre")
         close(y, torch.nn.functional.gelu(u), 2e-5, 2e-5, "panel: gelu")
         ops.linear_fwd(xg, wg, bg, [y2], N, epi=ops.EPI_DROP_RESID, resid=rg, p=0.0, seed=1, site=2)
+        assert ops.gemm_last_route()[0] == GR.PANEL32
         close(y2, u + r.double(), 2e-5, 2e-5, "panel: residual")
         wsb = torch.empty(int(ops._L().gct_linear_fwd_ws_bytes(M, K, N)) // 4 + 64, device=DEV)
         y3 = torch.empty(M, N, device=DEV)
         ops.linear_fwd(xg, wg, bg, [y3], N, epi=ops.EPI_DROP_RESID, resid=rg, p=0.0, seed=1, site=2, splitk_ws=wsb)
-        close(y3, y2.double(), 2e-5, 2e-5, "panel vs split-K route")
+        assert ops.gemm_last_route()[0] == GR.PANEL32           # the panel conditions come before the workspace
+        close(y3, y2.double(), 2e-5, 2e-5, "panel with a workspace")
+        # the K = 384 twin: gemm_f32_small_kernel, K split into slabs + fix-up through splitk_ws
+        K2 = 384
+        x2, w2 = rnd(M, K2, seed=31), rnd(nper, K2, seed=32, scale=K2 ** -0.5)
+        x2g, w2g = x2.to(DEV), [w2.to(DEV)]
+        u2 = x2.double() @ w2.double().t() + bs[0].double() + r.double()
+        ws2 = torch.empty(int(ops._L().gct_linear_fwd_ws_bytes(M, K2, N)) // 4 + 64, device=DEV)
+        y4 = torch.empty(M, N, device=DEV)
+        ops.linear_fwd(x2g, w2g, bg, [y4], N, epi=ops.EPI_DROP_RESID, resid=rg, p=0.0, seed=1, site=2, splitk_ws=ws2)
+        route = ops.gemm_last_route()
+        assert route[0] == GR.F32_SMALL and route[1] > 1 and route[5] == 2, route
+        close(y4, u2, 2e-5, 2e-5, "split-K + fix-up vs fp64")
 
 
 @pytest.mark.parametrize("M,K,nper,nseg", [(4096, 512, 512, 1), (2050, 1024, 520, 1), (3000, 512, 512, 2), (5184, 512, 512, 1),
@@ -682,12 +701,15 @@ def test_linear_bf16x6_small_tile_kernel(ops, M, K, nper, nseg):
             k0, c0 = ops._L().gct_gemm_x6_kernel_launches(), ops.gemm_launch_counts()
             y, pre, y1, y2 = (torch.empty(M, N, device=DEV) for _ in range(4))
             ops.linear_fwd(xg, wg, bg, outs(y), N)
+            assert mode != ops.GEMM_BF16X6 or ops.gemm_last_route()[0] == GR.X6S
             n_calls = 1
             if nseg == 1:
                 ops.linear_fwd(xg, wg, bg, [y1], N, epi=ops.EPI_GELU_DROP, pre=pre, p=p, seed=seed, site=2)
+                assert mode != ops.GEMM_BF16X6 or ops.gemm_last_route()[0] == GR.X6S
                 ops.linear_fwd(xg, wg, bg, [y2], N, epi=ops.EPI_DROP_RESID, resid=rg, p=p, seed=seed, site=3)
                 n_calls = 3
             if mode == ops.GEMM_BF16X6:        # one kernel launch per call: no split-K pair, no tail launch
+                assert ops.gemm_last_route()[0] == GR.X6S and ops.gemm_last_route()[5] == 1
                 assert ops._L().gct_gemm_x6_kernel_launches() == k0 + n_calls
                 assert ops.gemm_launch_counts()[1] == c0[1] + n_calls
             res[mode] = [t.cpu() for t in (y, pre, y1, y2)]
@@ -736,8 +758,10 @@ def test_linear_bf16x6_split_k_over_the_whole_problem(ops):
             y1, y2 = torch.empty(M, N, device=DEV), torch.empty(M, N, device=DEV)
             c0, k0 = ops.gemm_launch_counts(), ops._L().gct_gemm_x6_kernel_launches()
             ops.linear_fwd(xg, [wg], [bg], [y1], N, ws=ws)
+            assert mode != ops.GEMM_BF16X6 or ops.gemm_last_route()[:2] == (GR.X6_SPLITK_ALL, 8)
             ops.linear_fwd(xg, [wg], [bg], [y2], N, epi=ops.EPI_DROP_RESID, resid=rg, p=p, seed=seed, site=4, ws=ws)
             if mode == ops.GEMM_BF16X6:            # both calls took the bf16x6 kernel (one split launch each)
+                assert ops.gemm_last_route()[:2] == (GR.X6_SPLITK_ALL, 8) and ops.gemm_last_route()[5] == 2
                 assert ops.gemm_launch_counts()[1] == c0[1] + 2 and ops._L().gct_gemm_x6_kernel_launches() == k0 + 2
             out[mode] = (y1.cpu(), y2.cpu())
     finally:
@@ -848,12 +872,14 @@ def test_tail_rows_on_the_small_tile_kernel_vs_fp64(ops):
         outs = [y[:, s * nper:] for s in range(nseg)]
         k0 = ops._L().gct_gemm_x6_kernel_launches()
         ops.linear_fwd(xd, wv, [b.to(DEV) for b in bs], outs, N)
+        assert ops.gemm_last_route()[:4] == (GR.X6, 1, GR.TAIL_SMALL, 16384), ops.gemm_last_route()
         assert ops._L().gct_gemm_x6_kernel_launches() == k0 + 2
         ref = x.double() @ torch.cat(ws).double().t() + torch.cat(bs).double()
         close(y, ref, 2e-5, 2e-5, "forward (two segments), tail on small tiles")
         y1 = torch.empty(M, nper, device=DEV)                 # fused epilogues take one segment: 155 x 2 tiles
         k0 = ops._L().gct_gemm_x6_kernel_launches()
         ops.linear_fwd(xd, wv[:1], [bs[0].to(DEV)], [y1], nper, epi=ops.EPI_DROP_RESID, resid=resid[:, :nper].contiguous().to(DEV), p=0.0)
+        assert ops.gemm_last_route()[:4] == (GR.X6, 1, GR.TAIL_SMALL, 16384), ops.gemm_last_route()
         assert ops._L().gct_gemm_x6_kernel_launches() == k0 + 2
         close(y1, ref[:, :nper] + resid[:, :nper].double(), 2e-5, 2e-5, "forward (dropout + residual epilogue), tail on small tiles")
         # dgrad: dX[M, K] (+)= dY[M, 2 x 512] @ [W0; W1]  -- N(out) = 512 -> 155 x 2 tiles = 256 + 54
@@ -863,6 +889,7 @@ def test_tail_rows_on_the_small_tile_kernel_vs_fp64(ops):
         dx = base.to(DEV).clone()
         k0 = ops._L().gct_gemm_x6_kernel_launches()
         ops.linear_dgrad(dys, N, M, wv, dx, depi=ops.DEPI_ACCUM)
+        assert ops.gemm_last_route()[:4] == (GR.X6, 1, GR.TAIL_SMALL, 16384), ops.gemm_last_route()
         assert ops._L().gct_gemm_x6_kernel_launches() == k0 + 2
         refd = base.double() + dy.cpu().double() @ torch.cat(ws).double()
         close(dx, refd, 4e-5, 2e-5, "dgrad, tail on small tiles")
@@ -892,6 +919,8 @@ def test_dgrad_routes_for_few_tiles_vs_fp64(ops, M, Kp, N, depi, launches):
         kw = {"store": {}, "gelu": dict(depi=ops.DEPI_GELU_BWD, pre=pre.to(DEV), p=0.0),
               "accum": dict(depi=ops.DEPI_ACCUM)}[depi]
         ops.linear_dgrad(dys, Kp, M, wv, dx, **kw)
+        want = {512: (GR.X6S, 1), 2048: (GR.X6_SPLITK_ALL, 3), 1536: (GR.X6_SPLITK_ALL, 6)}[Kp]
+        assert ops.gemm_last_route()[:2] == want, ops.gemm_last_route()
         assert ops._L().gct_gemm_x6_kernel_launches() == k0 + launches
     finally:
         ops.unregister_planes(flat)
