@@ -2,18 +2,23 @@
 // Reference: Train/trainer1.py:21-22  F.cross_entropy(logits.view(-1,V), ys,
 // ignore_index=pad, reduction='sum').  V <= 31 in practice: one wave per row (row = 120 B),
 // wave-level max / sum-exp; per-block partial sums reduced in fixed order.
-// Log-likelihoods (decode.py score_reference states the rule): gct_seq_logp scores given token rows against their
-// teacher-forced logits, gct_chosen_logp the token a decode step has just picked.  Both go through wave_token_logp, the
-// same wave-per-row log-softmax; every output has one writer and a fixed summation order (no atomics).
-// gct_seq_logp_bwd (decode.py seq_logp_grad_reference states the rule) is gct_seq_logp's gradient with respect to the
-// logits: ce_grad_row, the row arithmetic of gct_ce_bwd, with a weight per token column instead of one scalar.
-// gct_seq_dist / gct_seq_dist_bwd (decode.py dist_reference / dist_grad_reference state the rules) are the entropy of
-// the next-token distribution and its KL divergence from a second model's, per scored token and per sequence, and their
-// gradient with respect to the first model's logits: the same layouts, around wave_row_dist.
-// gct_seq_ppo / gct_seq_ppo_bwd (decode.py ppo_reference / ppo_grad_reference state the rules) are PPO's clipped
-// surrogate of each scored token's probability ratio against the log-probabilities it was sampled with, per token and
-// per sequence, and its gradient with respect to the logits: the same layouts again, wave_token_logp and ce_grad_write
-// around ppo_token.
+//
+// The scored-token family: three forward / backward pairs over one data layout, the token rows ys [n, W] next to their
+// teacher-forced logits (SeqView: the geometry, THE scored predicate, the row address and its inverse).
+//   seq_fwd_kernel<Op>  one workgroup per sequence, a wave per token column; per-token tables, and per-sequence sums
+//                       added up by one thread in ascending column order: one writer per output, no atomics.
+//   seq_bwd_kernel<Op>  one wave per logits row; a row that is not scored, or whose weights are 0, gets V exact zeros
+//                       and its logits are not read.
+// An Op holds what one entry point adds to the view and computes per scored token (decode.py states the rules):
+//   gct_seq_logp / _bwd  score_reference / seq_logp_grad_reference: the log-probability of the given token
+//                        (wave_token_logp) and its gradient, ce_grad_row with a weight per token column;
+//   gct_seq_ppo / _bwd   ppo_reference / ppo_grad_reference: PPO's clipped surrogate of the token's probability ratio
+//                        against the log-probability it was sampled with (ppo_token around wave_token_logp) and its
+//                        gradient (ce_grad_write);
+//   gct_seq_dist / _bwd  dist_reference / dist_grad_reference: the entropy of the next-token distribution and its KL
+//                        divergence from a second model's (wave_row_dist) and their gradient.
+// gct_chosen_logp scores the token a decode step has just picked, through wave_token_logp too.
+#include <algorithm>
 #include "common.h"
 #include "decode_rows.h"
 
@@ -98,85 +103,6 @@ __device__ __forceinline__ float wave_token_logp(const float* __restrict__ lr, i
   return (lr[tok] - mx) - logf(se);
 }
 
-constexpr int SEQ_LOGP_MAX_W = 256;
-
-// one workgroup per sequence; wave w takes the token columns w, w + 4, ...  Each column's log-probability and flags
-// go to LDS, and thread 0 adds them up in ascending column order: the sums do not depend on the grid or on which wave
-// took a column.
-__global__ __launch_bounds__(256) void seq_logp_kernel(const float* __restrict__ logits, int64_t ld, int V,
-                                                       int64_t rows_per_seq, int row_shift,
-                                                       const int64_t* __restrict__ ys, int64_t ld_ys,
-                                                       const int32_t* __restrict__ prefix_lens, int64_t pad_id, int W,
-                                                       float* __restrict__ token_logp, int64_t ld_out,
-                                                       float* __restrict__ logp, int32_t* __restrict__ tokens,
-                                                       int32_t* __restrict__ hits) {
-  __shared__ float sh_lp[SEQ_LOGP_MAX_W];
-  __shared__ uint8_t sh_flag[SEQ_LOGP_MAX_W];           // bit 0: scored, bit 1: hit
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t r = blockIdx.x;
-  const int t0 = prefix_lens ? prefix_lens[r] : 1;
-  const int64_t* yr = ys + r * ld_ys;
-  for (int c = wave; c < W; c += 4) {                   // uniform over the wave
-    const int64_t tok = yr[c];
-    const bool scored = c >= t0 && c >= 1 && tok != pad_id && tok >= 0 && tok < V;
-    float lp = 0.f;
-    bool hit = false;
-    if (scored) lp = wave_token_logp(logits + (r * rows_per_seq + row_shift + c - 1) * ld, V, (int)tok, lane, hit);
-    if (lane == 0) {
-      token_logp[r * ld_out + c] = lp;
-      sh_lp[c] = lp;
-      sh_flag[c] = (scored ? 1 : 0) | (hit ? 2 : 0);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float sum = 0.f;
-    int nt = 0, nh = 0;
-    for (int c = 0; c < W; ++c) {
-      const int f = sh_flag[c];
-      if (f & 1) sum += sh_lp[c];
-      nt += f & 1;
-      nh += (f >> 1) & 1;
-    }
-    logp[r] = sum;
-    tokens[r] = nt;
-    hits[r] = nh;
-  }
-}
-
-// one wave per logits row (r, j), four rows per workgroup, the grid strides over the rest (ce_bwd_kernel's layout).
-// Row j of sequence r predicts token column c = j - row_shift + 1 and is scored under seq_logp_kernel's predicate; its
-// weight is g = g_logp[r] + g_token[r][c] (a null table: 0).  A row that is not scored, or whose weight is 0, gets V
-// exact zeros and its logits are NOT read (the decoder may never have computed them).  Everything a branch depends on
-// is one value per wave.
-__global__ __launch_bounds__(256) void seq_logp_bwd_kernel(const float* __restrict__ logits, int64_t ld, int V,
-                                                           int64_t rows_per_seq, int row_shift,
-                                                           const int64_t* __restrict__ ys, int64_t ld_ys,
-                                                           const int32_t* __restrict__ prefix_lens, int64_t pad_id,
-                                                           int W, const float* __restrict__ g_logp,
-                                                           const float* __restrict__ g_token, int64_t ld_g,
-                                                           float* __restrict__ dlogits, int64_t ld_d, int64_t rows) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
-    const int64_t r = row / rows_per_seq, j = row - r * rows_per_seq;
-    const int64_t c = j - row_shift + 1;
-    float* dr = dlogits + row * ld_d;
-    int64_t tok = 0;
-    float g = 0.f;
-    if (j >= row_shift && c >= 1 && c < W) {
-      const int t0 = prefix_lens ? prefix_lens[r] : 1;
-      tok = ys[r * ld_ys + c];
-      if (c >= t0 && tok != pad_id && tok >= 0 && tok < V)
-        g = (g_logp ? g_logp[r] : 0.f) + (g_token ? g_token[r * ld_g + c] : 0.f);
-    }
-    if (g == 0.f) {                                     // not scored, or a zero weight
-      for (int v = lane; v < V; v += 64) dr[v] = 0.f;
-      continue;
-    }
-    ce_grad_row(logits + row * ld, dr, V, tok, -g, lane);
-  }
-}
-
 // The clipped surrogate of one scored token (decode.py ppo_reference states the rule): lp its log-probability now, old
 // the one it was sampled with, A its sequence's advantage.  rho = exp(lp - old); CLIPPED when A > 0 and rho > 1 +
 // clip_hi, or A < 0 and rho < 1 - clip_lo (strict: rho == 1 never is).  Plain fp32, one value per wave.
@@ -193,121 +119,6 @@ __device__ __forceinline__ PpoToken ppo_token(float lp, float old, float A, floa
   t.surrogate = up ? A * hi : (down ? A * lo : A * t.rho);
   t.k3 = (t.rho - 1.0f) - d;                            // the k3 estimator term of KL(old || new)
   return t;
-}
-
-// seq_logp_kernel's layout: one workgroup per sequence, wave w takes the token columns w, w + 4, ...; each column's
-// log-probability (wave_token_logp: gct_seq_logp's bits), surrogate and KL term go to LDS and thread 0 adds them up in
-// ascending column order.  Neither the logits row nor old_token_logp is read at a column that is not scored.
-__global__ __launch_bounds__(256) void seq_ppo_kernel(const float* __restrict__ logits, int64_t ld, int V,
-                                                      int64_t rows_per_seq, int row_shift,
-                                                      const int64_t* __restrict__ ys, int64_t ld_ys,
-                                                      const int32_t* __restrict__ prefix_lens, int64_t pad_id, int W,
-                                                      const float* __restrict__ old_token_logp, int64_t ld_old,
-                                                      const float* __restrict__ advantage, float clip_lo,
-                                                      float clip_hi, float* __restrict__ token_logp,
-                                                      float* __restrict__ token_surrogate, int64_t ld_out,
-                                                      float* __restrict__ logp, float* __restrict__ surrogate,
-                                                      float* __restrict__ approx_kl, int32_t* __restrict__ tokens,
-                                                      int32_t* __restrict__ hits, int32_t* __restrict__ clipped) {
-  __shared__ float sh_lp[SEQ_LOGP_MAX_W];
-  __shared__ float sh_s[SEQ_LOGP_MAX_W];
-  __shared__ float sh_k[SEQ_LOGP_MAX_W];
-  __shared__ uint8_t sh_flag[SEQ_LOGP_MAX_W];           // bit 0: scored, bit 1: hit, bit 2: clipped
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t r = blockIdx.x;
-  const int t0 = prefix_lens ? prefix_lens[r] : 1;
-  const int64_t* yr = ys + r * ld_ys;
-  const float A = advantage[r];
-  for (int c = wave; c < W; c += 4) {                   // uniform over the wave
-    const int64_t tok = yr[c];
-    const bool scored = c >= t0 && c >= 1 && tok != pad_id && tok >= 0 && tok < V;
-    float lp = 0.f;
-    PpoToken t = {1.f, 0.f, 0.f, false};
-    bool hit = false;
-    if (scored) {
-      lp = wave_token_logp(logits + (r * rows_per_seq + row_shift + c - 1) * ld, V, (int)tok, lane, hit);
-      t = ppo_token(lp, old_token_logp[r * ld_old + c], A, clip_lo, clip_hi);
-    }
-    if (lane == 0) {
-      token_logp[r * ld_out + c] = lp;
-      token_surrogate[r * ld_out + c] = t.surrogate;
-      sh_lp[c] = lp;
-      sh_s[c] = t.surrogate;
-      sh_k[c] = t.k3;
-      sh_flag[c] = (scored ? 1 : 0) | (hit ? 2 : 0) | (t.clipped ? 4 : 0);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float sum = 0.f, ss = 0.f, sk = 0.f;
-    int nt = 0, nh = 0, nc = 0;
-    for (int c = 0; c < W; ++c) {
-      const int f = sh_flag[c];
-      if (f & 1) {
-        sum += sh_lp[c];
-        ss += sh_s[c];
-        sk += sh_k[c];
-      }
-      nt += f & 1;
-      nh += (f >> 1) & 1;
-      nc += (f >> 2) & 1;
-    }
-    logp[r] = sum;
-    surrogate[r] = ss;
-    approx_kl[r] = sk;
-    tokens[r] = nt;
-    hits[r] = nh;
-    clipped[r] = nc;
-  }
-}
-
-// seq_logp_bwd_kernel's layout: one wave per logits row (r, j), four rows per workgroup, the grid strides over the
-// rest.  With A = advantage[r] and g = g_surrogate[r] + g_token_surrogate[r][c] (a null table: 0), a row that is not
-// scored, or whose A or g is 0, gets V exact zeros and its logits are NOT read.  Otherwise the row's softmax statistics
-// are taken once: lp (wave_token_logp's bits), rho and the clip decision follow from them, and the row is V zeros
-// (clipped) or ce_grad_write with the weight -((g * A) * rho): rho == 1 gives gct_seq_logp_bwd's bits for g_logp =
-// g * A.  Everything a branch depends on is one value per wave.
-__global__ __launch_bounds__(256) void seq_ppo_bwd_kernel(const float* __restrict__ logits, int64_t ld, int V,
-                                                          int64_t rows_per_seq, int row_shift,
-                                                          const int64_t* __restrict__ ys, int64_t ld_ys,
-                                                          const int32_t* __restrict__ prefix_lens, int64_t pad_id,
-                                                          int W, const float* __restrict__ old_token_logp,
-                                                          int64_t ld_old, const float* __restrict__ advantage,
-                                                          float clip_lo, float clip_hi,
-                                                          const float* __restrict__ g_surrogate,
-                                                          const float* __restrict__ g_token, int64_t ld_g,
-                                                          float* __restrict__ dlogits, int64_t ld_d, int64_t rows) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
-    const int64_t r = row / rows_per_seq, j = row - r * rows_per_seq;
-    const int64_t c = j - row_shift + 1;
-    float* dr = dlogits + row * ld_d;
-    int64_t tok = 0;
-    float g = 0.f, A = 0.f;
-    if (j >= row_shift && c >= 1 && c < W) {
-      const int t0 = prefix_lens ? prefix_lens[r] : 1;
-      tok = ys[r * ld_ys + c];
-      if (c >= t0 && tok != pad_id && tok >= 0 && tok < V) {
-        g = (g_surrogate ? g_surrogate[r] : 0.f) + (g_token ? g_token[r * ld_g + c] : 0.f);
-        A = advantage[r];
-      }
-    }
-    bool live = g != 0.f && A != 0.f;                   // scored, and both weights count
-    float mx = 0.f, se = 1.f, w = 0.f;
-    const float* lr = logits + row * ld;
-    if (live) {
-      gct_wave_softmax_stats(lr, V, lane, mx, se);
-      const float lp = (lr[tok] - mx) - logf(se);
-      const PpoToken t = ppo_token(lp, old_token_logp[r * ld_old + c], A, clip_lo, clip_hi);
-      live = !t.clipped;
-      w = (g * A) * t.rho;
-    }
-    if (!live) {
-      for (int v = lane; v < V; v += 64) dr[v] = 0.f;
-      continue;
-    }
-    ce_grad_write(lr, dr, V, tok, -w, lane, mx, se);
-  }
 }
 
 // One wave, one logits row lr[0, V) and -- pr non-null -- the prior's row pr[0, V); every lane gets the results.
@@ -349,102 +160,277 @@ __device__ __forceinline__ RowDist wave_row_dist(const float* __restrict__ lr, c
   return d;
 }
 
-// seq_logp_kernel's layout: one workgroup per sequence, wave w takes the token columns w, w + 4, ...; each column's
-// entropy and KL go to LDS and thread 0 adds them up in ascending column order.  Neither model's logits row is read
-// at a column that is not scored.
-__global__ __launch_bounds__(256) void seq_dist_kernel(const float* __restrict__ logits, int64_t ld, int V,
-                                                       int64_t rows_per_seq, int row_shift,
-                                                       const float* __restrict__ prior, int64_t ld_prior,
-                                                       const int64_t* __restrict__ ys, int64_t ld_ys,
-                                                       const int32_t* __restrict__ prefix_lens, int64_t pad_id, int W,
-                                                       float* __restrict__ token_entropy, int64_t ld_out,
-                                                       float* __restrict__ entropy, float* __restrict__ token_kl,
-                                                       float* __restrict__ kl) {
-  __shared__ float sh_h[SEQ_LOGP_MAX_W];
-  __shared__ float sh_kl[SEQ_LOGP_MAX_W];
+// ------------------------------------------------------------------------------------------- the scored-token skeleton
+constexpr int SEQ_LOGP_MAX_W = 256;
+
+// A token id that can be scored at all: not pad, and inside the vocabulary.
+__device__ __forceinline__ bool token_scored(int64_t tok, int64_t pad_id, int V) {
+  return tok != pad_id && tok >= 0 && tok < V;
+}
+
+// The geometry every seq_* entry point takes: token rows ys [n, W] (row stride ld_ys), prefix lengths (null: 1 each),
+// and logits of rows_per_seq rows per sequence (row stride ld), of which row row_shift + c - 1 predicts token column c.
+struct SeqView {
+  const float* logits;
+  int64_t ld;
+  int V;
+  int64_t rows_per_seq;
+  int row_shift;
+  const int64_t* ys;
+  int64_t ld_ys;
+  const int32_t* prefix_lens;
+  int64_t pad_id;
+  int W;
+
+  __device__ __forceinline__ int t0(int64_t r) const { return prefix_lens ? prefix_lens[r] : 1; }
+  // THE predicate: column c < W of sequence r (prefix length t0) is scored; tok = its token either way.
+  __device__ __forceinline__ bool scored(int t0, int64_t r, int64_t c, int64_t& tok) const {
+    tok = ys[r * ld_ys + c];
+    return c >= t0 && c >= 1 && token_scored(tok, pad_id, V);
+  }
+  __device__ __forceinline__ int64_t row_of(int64_t r, int64_t c) const { return r * rows_per_seq + row_shift + c - 1; }
+  __device__ __forceinline__ const float* logits_row(int64_t row) const { return logits + row * ld; }
+  // row_of's inverse: false for a row that predicts no token column (a shift row, or one behind column W - 1)
+  __device__ __forceinline__ bool column_of(int64_t row, int64_t& r, int64_t& c) const {
+    r = row / rows_per_seq;
+    const int64_t j = row - r * rows_per_seq;
+    c = j - row_shift + 1;
+    return j >= row_shift && c >= 1 && c < W;
+  }
+};
+
+// One workgroup per sequence; wave w takes the token columns w, w + 4, ...  At a scored column Op::token fills the
+// column's NSUM values (an unscored column keeps zeros, and no row of it is read) and returns its flag bits above bit 0
+// (scored).  Lane 0 hands the values to Op::store_token and to LDS, and thread 0 adds each of them up in ascending
+// column order and counts each flag for Op::store_seq: the sums do not depend on the grid or on which wave took a
+// column.  Everything a branch depends on is one value per wave.
+template <class Op>
+__global__ __launch_bounds__(256) void seq_fwd_kernel(SeqView v, Op op) {
+  constexpr int NSUM = Op::NSUM, NFLAG = Op::NFLAG;
+  __shared__ float sh[NSUM * SEQ_LOGP_MAX_W + (NFLAG ? SEQ_LOGP_MAX_W / 4 : 0)];
+  uint8_t* sh_flag = reinterpret_cast<uint8_t*>(sh + NSUM * SEQ_LOGP_MAX_W);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t r = blockIdx.x;
-  const int t0 = prefix_lens ? prefix_lens[r] : 1;
-  const int64_t* yr = ys + r * ld_ys;
-  for (int c = wave; c < W; c += 4) {                   // uniform over the wave
-    const int64_t tok = yr[c];
-    const bool scored = c >= t0 && c >= 1 && tok != pad_id && tok >= 0 && tok < V;
-    float h = 0.f, k = 0.f;
-    if (scored) {
-      const int64_t row = r * rows_per_seq + row_shift + c - 1;
-      const RowDist d = wave_row_dist(logits + row * ld, prior ? prior + row * ld_prior : nullptr, V, lane);
-      h = d.H;
-      k = d.KL;
-    }
+  const int t0 = v.t0(r);
+  for (int c = wave; c < v.W; c += 4) {                 // uniform over the wave
+    int64_t tok;
+    const bool scored = v.scored(t0, r, c, tok);
+    float s[NSUM] = {};
+    int flags = scored ? 1 : 0;
+    if (scored) flags |= op.token(v, r, c, (int)tok, lane, s);
     if (lane == 0) {
-      token_entropy[r * ld_out + c] = h;
-      sh_h[c] = h;
-      if (prior) {
-        token_kl[r * ld_out + c] = k;
-        sh_kl[c] = k;
-      }
+      op.store_token(r, c, s);
+#pragma unroll
+      for (int k = 0; k < NSUM; ++k) sh[k * SEQ_LOGP_MAX_W + c] = s[k];
+      if constexpr (NFLAG > 0) sh_flag[c] = (uint8_t)flags;
     }
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    float sh = 0.f, sk = 0.f;
-    for (int c = 0; c < W; ++c) sh += sh_h[c];          // a column that is not scored holds 0
-    entropy[r] = sh;
-    if (prior) {
-      for (int c = 0; c < W; ++c) sk += sh_kl[c];
-      kl[r] = sk;
+    float sum[NSUM] = {};
+    int cnt[NFLAG + 1] = {};
+    for (int c = 0; c < v.W; ++c) {                     // a column that is not scored holds 0
+#pragma unroll
+      for (int k = 0; k < NSUM; ++k) sum[k] += sh[k * SEQ_LOGP_MAX_W + c];
+#pragma unroll
+      for (int b = 0; b < NFLAG; ++b) cnt[b] += (sh_flag[c] >> b) & 1;
     }
+    op.store_seq(r, sum, cnt);
   }
 }
 
-// seq_logp_bwd_kernel's layout: one wave per logits row (r, j), four rows per workgroup, the grid strides over the
-// rest.  With a = g_entropy[r] + g_token_entropy[r][c] and b = g_kl[r] + g_token_kl[r][c] (a null table: 0) a scored
-// row gets  a * (-p_v (log p_v + H)) + b * (p_v ((log p_v - log q_v) - KL)),  exact zeros where p_v == 0.  A row that
-// is not scored, or whose a and b are both 0, gets V exact zeros and neither its logits nor the prior's are read.
-// Everything a branch depends on is one value per wave.
-__global__ __launch_bounds__(256) void seq_dist_bwd_kernel(const float* __restrict__ logits, int64_t ld, int V,
-                                                           int64_t rows_per_seq, int row_shift,
-                                                           const float* __restrict__ prior, int64_t ld_prior,
-                                                           const int64_t* __restrict__ ys, int64_t ld_ys,
-                                                           const int32_t* __restrict__ prefix_lens, int64_t pad_id,
-                                                           int W, const float* __restrict__ g_entropy,
-                                                           const float* __restrict__ g_token_entropy, int64_t ld_ge,
-                                                           const float* __restrict__ g_kl,
-                                                           const float* __restrict__ g_token_kl, int64_t ld_gk,
-                                                           float* __restrict__ dlogits, int64_t ld_d, int64_t rows) {
+// One wave per logits row, four rows per workgroup, the grid strides over the rest (ce_bwd_kernel's layout).  A row
+// that predicts a scored column asks Op::weight for its weights (every other row keeps Weight{}: zeros), and a row
+// whose weights are not Op::dead asks Op::row for the row of dlogits (false: nothing written).  Every other row gets V
+// exact zeros and its logits are NOT read (the decoder may never have computed them).  Everything a branch depends on
+// is one value per wave.  The SGPR budget keeps the widest Op (DistBwd) at 8 waves per SIMD; it costs no spill.
+template <class Op>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(100))) void
+seq_bwd_kernel(SeqView v, Op op, float* __restrict__ dlogits, int64_t ld_d, int64_t rows) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
-    const int64_t r = row / rows_per_seq, j = row - r * rows_per_seq;
-    const int64_t c = j - row_shift + 1;
+    int64_t r, c, tok = 0;
     float* dr = dlogits + row * ld_d;
-    float a = 0.f, b = 0.f;
-    if (j >= row_shift && c >= 1 && c < W) {
-      const int t0 = prefix_lens ? prefix_lens[r] : 1;
-      const int64_t tok = ys[r * ld_ys + c];
-      if (c >= t0 && tok != pad_id && tok >= 0 && tok < V) {
-        a = (g_entropy ? g_entropy[r] : 0.f) + (g_token_entropy ? g_token_entropy[r * ld_ge + c] : 0.f);
-        b = (g_kl ? g_kl[r] : 0.f) + (g_token_kl ? g_token_kl[r * ld_gk + c] : 0.f);
-      }
-    }
-    if (a == 0.f && b == 0.f) {                         // not scored, or zero weights
-      for (int v = lane; v < V; v += 64) dr[v] = 0.f;
-      continue;
-    }
-    const float* lr = logits + row * ld;
-    const float* pr = b != 0.f ? prior + row * ld_prior : nullptr;   // b != 0 only with a prior (checked by the host)
-    const RowDist d = wave_row_dist(lr, pr, V, lane);
-    for (int v = lane; v < V; v += 64) {
-      const float y = lr[v] - d.m, e = expf(y);
+    typename Op::Weight w{};
+    if (v.column_of(row, r, c) && v.scored(v.t0(r), r, c, tok)) w = op.weight(r, c);
+    if (Op::dead(w) || !op.row(v, r, c, row, tok, w, dr, lane))
+      for (int i = lane; i < v.V; i += 64) dr[i] = 0.f;
+  }
+}
+
+// g_row[r] + g_table[r][c], a null pointer counting as 0
+__device__ __forceinline__ float seq_weight(const float* g_row, const float* g_table, int64_t ld_g, int64_t r,
+                                            int64_t c) {
+  return (g_row ? g_row[r] : 0.f) + (g_table ? g_table[r * ld_g + c] : 0.f);
+}
+
+// ---- log-probability of the given token.  Sum: logp; flags: scored, hit.
+struct LogpFwd {
+  static constexpr int NSUM = 1, NFLAG = 2;
+  float* token_logp;
+  int64_t ld_out;
+  float* logp;
+  int32_t *tokens, *hits;
+  __device__ __forceinline__ int token(const SeqView& v, int64_t r, int c, int tok, int lane, float* s) const {
+    bool hit;
+    s[0] = wave_token_logp(v.logits_row(v.row_of(r, c)), v.V, tok, lane, hit);
+    return hit ? 2 : 0;
+  }
+  __device__ __forceinline__ void store_token(int64_t r, int c, const float* s) const {
+    token_logp[r * ld_out + c] = s[0];
+  }
+  __device__ __forceinline__ void store_seq(int64_t r, const float* sum, const int* cnt) const {
+    logp[r] = sum[0];
+    tokens[r] = cnt[0];
+    hits[r] = cnt[1];
+  }
+};
+
+// Weight g = g_logp[r] + g_token[r][c]; the row is ce_grad_row, the row arithmetic of gct_ce_bwd, with -g.
+struct LogpBwd {
+  using Weight = float;
+  const float *g_logp, *g_token;
+  int64_t ld_g;
+  __device__ __forceinline__ float weight(int64_t r, int64_t c) const {
+    return seq_weight(g_logp, g_token, ld_g, r, c);
+  }
+  static __device__ __forceinline__ bool dead(float g) { return g == 0.f; }
+  __device__ __forceinline__ bool row(const SeqView& v, int64_t r, int64_t c, int64_t row, int64_t tok, float g,
+                                      float* dr, int lane) const {
+    ce_grad_row(v.logits_row(row), dr, v.V, tok, -g, lane);
+    return true;
+  }
+};
+
+// ---- PPO.  What both directions read beside the view; old_token_logp is not read at a column that is not scored.
+struct PpoIn {
+  const float* old_token_logp;
+  int64_t ld_old;
+  const float* advantage;
+  float clip_lo, clip_hi;
+  __device__ __forceinline__ PpoToken token(float lp, float A, int64_t r, int64_t c) const {
+    return ppo_token(lp, old_token_logp[r * ld_old + c], A, clip_lo, clip_hi);
+  }
+};
+
+// Sums: logp (wave_token_logp: gct_seq_logp's bits), surrogate, the k3 terms; flags: scored, hit, clipped.
+struct PpoFwd {
+  static constexpr int NSUM = 3, NFLAG = 3;
+  PpoIn in;
+  float *token_logp, *token_surrogate;
+  int64_t ld_out;
+  float *logp, *surrogate, *approx_kl;
+  int32_t *tokens, *hits, *clipped;
+  __device__ __forceinline__ int token(const SeqView& v, int64_t r, int c, int tok, int lane, float* s) const {
+    bool hit;
+    s[0] = wave_token_logp(v.logits_row(v.row_of(r, c)), v.V, tok, lane, hit);
+    const PpoToken t = in.token(s[0], in.advantage[r], r, c);
+    s[1] = t.surrogate;
+    s[2] = t.k3;
+    return (hit ? 2 : 0) | (t.clipped ? 4 : 0);
+  }
+  __device__ __forceinline__ void store_token(int64_t r, int c, const float* s) const {
+    token_logp[r * ld_out + c] = s[0];
+    token_surrogate[r * ld_out + c] = s[1];
+  }
+  __device__ __forceinline__ void store_seq(int64_t r, const float* sum, const int* cnt) const {
+    logp[r] = sum[0];
+    surrogate[r] = sum[1];
+    approx_kl[r] = sum[2];
+    tokens[r] = cnt[0];
+    hits[r] = cnt[1];
+    clipped[r] = cnt[2];
+  }
+};
+
+// Weights g = g_surrogate[r] + g_token[r][c] and A = advantage[r]: both must count.  The row's softmax statistics are
+// taken once: lp (wave_token_logp's bits), rho and the clip decision follow from them, and the row is left to the
+// zeros (clipped) or is ce_grad_write with the weight -((g * A) * rho): rho == 1 gives gct_seq_logp_bwd's bits for
+// g_logp = g * A.
+struct PpoBwd {
+  struct Weight {
+    float g, A;
+  };
+  PpoIn in;
+  const float *g_surrogate, *g_token;
+  int64_t ld_g;
+  __device__ __forceinline__ Weight weight(int64_t r, int64_t c) const {
+    return {seq_weight(g_surrogate, g_token, ld_g, r, c), in.advantage[r]};
+  }
+  static __device__ __forceinline__ bool dead(Weight w) { return w.g == 0.f || w.A == 0.f; }
+  __device__ __forceinline__ bool row(const SeqView& v, int64_t r, int64_t c, int64_t row, int64_t tok, Weight w,
+                                      float* dr, int lane) const {
+    const float* lr = v.logits_row(row);
+    float mx, se;
+    gct_wave_softmax_stats(lr, v.V, lane, mx, se);
+    const float lp = (lr[tok] - mx) - logf(se);
+    const PpoToken t = in.token(lp, w.A, r, c);
+    if (t.clipped) return false;
+    ce_grad_write(lr, dr, v.V, tok, -((w.g * w.A) * t.rho), lane, mx, se);
+    return true;
+  }
+};
+
+// ---- entropy and KL from a prior (null: entropy alone).  Sums: entropy, kl; no flags.
+struct DistFwd {
+  static constexpr int NSUM = 2, NFLAG = 0;
+  const float* prior;
+  int64_t ld_prior;
+  float* token_entropy;
+  int64_t ld_out;
+  float *entropy, *token_kl, *kl;
+  __device__ __forceinline__ int token(const SeqView& v, int64_t r, int c, int tok, int lane, float* s) const {
+    const int64_t row = v.row_of(r, c);
+    const RowDist d = wave_row_dist(v.logits_row(row), prior ? prior + row * ld_prior : nullptr, v.V, lane);
+    s[0] = d.H;
+    s[1] = d.KL;
+    return 0;
+  }
+  __device__ __forceinline__ void store_token(int64_t r, int c, const float* s) const {
+    token_entropy[r * ld_out + c] = s[0];
+    if (prior) token_kl[r * ld_out + c] = s[1];
+  }
+  __device__ __forceinline__ void store_seq(int64_t r, const float* sum, const int*) const {
+    entropy[r] = sum[0];
+    if (prior) kl[r] = sum[1];
+  }
+};
+
+// Weights a = g_entropy[r] + g_token_entropy[r][c] and b = g_kl[r] + g_token_kl[r][c]; the row is
+// a * (-p_v (log p_v + H)) + b * (p_v ((log p_v - log q_v) - KL)),  exact zeros where p_v == 0.  The prior's row is
+// read only where b != 0 (b != 0 only with a prior: checked by the host).
+struct DistBwd {
+  struct Weight {
+    float a, b;
+  };
+  const float* prior;
+  int64_t ld_prior;
+  const float *g_entropy, *g_token_entropy;
+  int64_t ld_ge;
+  const float *g_kl, *g_token_kl;
+  int64_t ld_gk;
+  __device__ __forceinline__ Weight weight(int64_t r, int64_t c) const {
+    return {seq_weight(g_entropy, g_token_entropy, ld_ge, r, c), seq_weight(g_kl, g_token_kl, ld_gk, r, c)};
+  }
+  static __device__ __forceinline__ bool dead(Weight w) { return w.a == 0.f && w.b == 0.f; }
+  __device__ __forceinline__ bool row(const SeqView& v, int64_t r, int64_t c, int64_t row, int64_t tok, Weight w,
+                                      float* dr, int lane) const {
+    const float* lr = v.logits_row(row);
+    const float* pr = w.b != 0.f ? prior + row * ld_prior : nullptr;
+    const RowDist d = wave_row_dist(lr, pr, v.V, lane);
+    for (int i = lane; i < v.V; i += 64) {
+      const float y = lr[i] - d.m, e = expf(y);
       float g = 0.f;
       if (e != 0.f) {
         const float p = e * d.inv, lp = y - d.lse;
-        g = a * (-p * (lp + d.H));
-        if (pr) g += b * (p * ((lp - ((pr[v] - d.pm) - d.plse)) - d.KL));
+        g = w.a * (-p * (lp + d.H));
+        if (pr) g += w.b * (p * ((lp - ((pr[i] - d.pm) - d.plse)) - d.KL));
       }
-      dr[v] = g;
+      dr[i] = g;
     }
+    return true;
   }
-}
+};
 
 // one wave per decode row, as select_token_kernel: the column the selection has just written (gct_row_slot)
 __global__ __launch_bounds__(256) void chosen_logp_kernel(const float* __restrict__ logits, int V,
@@ -465,8 +451,57 @@ __global__ __launch_bounds__(256) void chosen_logp_kernel(const float* __restric
   const int64_t tok = ys[(int64_t)row * ld_ys + p];
   float lp = 0.f;
   bool hit = false;
-  if (tok != pad_id && tok >= 0 && tok < V) lp = wave_token_logp(logits + (int64_t)row * V, V, (int)tok, lane, hit);
+  if (token_scored(tok, pad_id, V)) lp = wave_token_logp(logits + (int64_t)row * V, V, (int)tok, lane, hit);
   if (lane == 0) out[(int64_t)dst * ld_out + p] = lp;
+}
+
+// The checks the six seq_* entry points share, behind their own pointer checks; `name` opens every message.  row_ld:
+// the narrowest of the caller's logits-like row strides (ld, ld_prior, ld_d), table_ld: the narrowest of its [n, W]
+// tables' (ld_out, ld_old, ld_g ...), each counted only where the pointer is there.
+int seq_check_view(const char* name, const SeqView& v, int n, int64_t row_ld, int64_t table_ld) {
+  GCT_CHECK_ARG(v.logits && v.ys, "%s: null pointer (logits, ys)", name);
+  GCT_CHECK_ARG(n >= 0 && v.V > 0 && row_ld >= v.V, "%s: bad shape (n %d, V %d, narrowest row stride %lld)", name, n,
+                v.V, (long long)row_ld);
+  GCT_CHECK_ARG(v.W >= 1 && v.W <= SEQ_LOGP_MAX_W, "%s: rows of %d tokens (1 .. %d supported)", name, v.W,
+                SEQ_LOGP_MAX_W);
+  GCT_CHECK_ARG(v.ld_ys >= v.W && table_ld >= v.W,
+                "%s: a row stride (ys %lld, narrowest table %lld) narrower than the %d token columns", name,
+                (long long)v.ld_ys, (long long)table_ld, v.W);
+  GCT_CHECK_ARG(v.row_shift >= 0 && v.rows_per_seq >= (int64_t)v.row_shift + v.W - 1,
+                "%s: %lld logits rows per sequence do not hold %d + %d", name, (long long)v.rows_per_seq, v.row_shift,
+                v.W - 1);
+  return GCT_OK;
+}
+
+int seq_check_clip(const char* name, float clip_lo, float clip_hi) {
+  GCT_CHECK_ARG(clip_lo >= 0.f && clip_lo < 1.f && clip_hi >= 0.f,
+                "%s: clip (%g, %g) outside 0 <= clip_lo < 1, clip_hi >= 0", name, (double)clip_lo, (double)clip_hi);
+  return GCT_OK;
+}
+
+// the stride of a table that may be null: one that is not there narrows nothing
+int64_t ld_if(const void* table, int64_t ld) { return table ? ld : INT64_MAX; }
+
+template <class Op>
+int seq_launch_fwd(const char* name, const SeqView& v, int n, const Op& op, void* stream) {
+  if (n == 0) return GCT_OK;
+  hipLaunchKernelGGL(seq_fwd_kernel<Op>, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, v, op);
+  GCT_LAUNCH_CHECK(name);
+  return GCT_OK;
+}
+
+// four rows per workgroup, at most 4096 workgroups
+unsigned seq_bwd_grid(int64_t rows) { return (unsigned)std::min<int64_t>((rows + 3) / 4, 4096); }
+
+template <class Op>
+int seq_launch_bwd(const char* name, const SeqView& v, int n, const Op& op, float* dlogits, int64_t ld_d,
+                   void* stream) {
+  const int64_t rows = (int64_t)n * v.rows_per_seq;
+  if (rows == 0) return GCT_OK;
+  hipLaunchKernelGGL(seq_bwd_kernel<Op>, dim3(seq_bwd_grid(rows)), dim3(256), 0, (hipStream_t)stream, v, op, dlogits,
+                     ld_d, rows);
+  GCT_LAUNCH_CHECK(name);
+  return GCT_OK;
 }
 
 }  // namespace
@@ -499,43 +534,21 @@ extern "C" int gct_seq_logp(const float* logits, int64_t ld, int V, int64_t rows
                             const int64_t* ys, int64_t ld_ys, const int32_t* prefix_lens, int64_t pad_id, int n,
                             int W, float* token_logp, int64_t ld_out, float* logp, int32_t* tokens, int32_t* hits,
                             void* stream) {
-  GCT_CHECK_ARG(logits && ys && token_logp && logp && tokens && hits, "seq_logp: null pointer");
-  GCT_CHECK_ARG(n >= 0 && V > 0 && ld >= V, "seq_logp: bad shape (n %d, V %d, ld %lld)", n, V, (long long)ld);
-  GCT_CHECK_ARG(W >= 1 && W <= SEQ_LOGP_MAX_W, "seq_logp: rows of %d tokens (1 .. %d supported)", W, SEQ_LOGP_MAX_W);
-  GCT_CHECK_ARG(ld_ys >= W && ld_out >= W, "seq_logp: ld_ys / ld_out narrower than the %d token columns", W);
-  GCT_CHECK_ARG(row_shift >= 0 && rows_per_seq >= (int64_t)row_shift + W - 1,
-                "seq_logp: %lld logits rows per sequence do not hold %d + %d", (long long)rows_per_seq, row_shift, W - 1);
-  if (n == 0) return GCT_OK;
-  hipLaunchKernelGGL(seq_logp_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, logits, ld, V,
-                     rows_per_seq, row_shift, ys, ld_ys, prefix_lens, pad_id, W, token_logp, ld_out, logp, tokens, hits);
-  GCT_LAUNCH_CHECK("seq_logp");
-  return GCT_OK;
+  const SeqView v{logits, ld, V, rows_per_seq, row_shift, ys, ld_ys, prefix_lens, pad_id, W};
+  GCT_CHECK_ARG(token_logp && logp && tokens && hits, "seq_logp: null pointer (outputs)");
+  if (int rc = seq_check_view("seq_logp", v, n, ld, ld_out)) return rc;
+  return seq_launch_fwd("seq_logp", v, n, LogpFwd{token_logp, ld_out, logp, tokens, hits}, stream);
 }
 
 extern "C" int gct_seq_logp_bwd(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift,
                                 const int64_t* ys, int64_t ld_ys, const int32_t* prefix_lens, int64_t pad_id, int n,
                                 int W, const float* g_logp, const float* g_token, int64_t ld_g, float* dlogits,
                                 int64_t ld_d, void* stream) {
-  GCT_CHECK_ARG(logits && ys && dlogits, "seq_logp_bwd: null pointer");
+  const SeqView v{logits, ld, V, rows_per_seq, row_shift, ys, ld_ys, prefix_lens, pad_id, W};
+  GCT_CHECK_ARG(dlogits, "seq_logp_bwd: null pointer (dlogits)");
   GCT_CHECK_ARG(g_logp || g_token, "seq_logp_bwd: both gradients are null (g_logp, g_token)");
-  GCT_CHECK_ARG(n >= 0 && V > 0 && ld >= V && ld_d >= V, "seq_logp_bwd: bad shape (n %d, V %d, ld %lld, ld_d %lld)", n,
-                V, (long long)ld, (long long)ld_d);
-  GCT_CHECK_ARG(W >= 1 && W <= SEQ_LOGP_MAX_W, "seq_logp_bwd: rows of %d tokens (1 .. %d supported)", W,
-                SEQ_LOGP_MAX_W);
-  GCT_CHECK_ARG(ld_ys >= W && (!g_token || ld_g >= W), "seq_logp_bwd: ld_ys / ld_g narrower than the %d token columns",
-                W);
-  GCT_CHECK_ARG(row_shift >= 0 && rows_per_seq >= (int64_t)row_shift + W - 1,
-                "seq_logp_bwd: %lld logits rows per sequence do not hold %d + %d", (long long)rows_per_seq, row_shift,
-                W - 1);
-  const int64_t rows = (int64_t)n * rows_per_seq;
-  if (rows == 0) return GCT_OK;
-  int64_t g = (rows + 3) / 4;
-  g = g > 4096 ? 4096 : g;
-  hipLaunchKernelGGL(seq_logp_bwd_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, logits, ld, V,
-                     rows_per_seq, row_shift, ys, ld_ys, prefix_lens, pad_id, W, g_logp, g_token, ld_g, dlogits, ld_d,
-                     rows);
-  GCT_LAUNCH_CHECK("seq_logp_bwd");
-  return GCT_OK;
+  if (int rc = seq_check_view("seq_logp_bwd", v, n, std::min(ld, ld_d), ld_if(g_token, ld_g))) return rc;
+  return seq_launch_bwd("seq_logp_bwd", v, n, LogpBwd{g_logp, g_token, ld_g}, dlogits, ld_d, stream);
 }
 
 extern "C" int gct_seq_ppo(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift,
@@ -544,24 +557,15 @@ extern "C" int gct_seq_ppo(const float* logits, int64_t ld, int V, int64_t rows_
                            float clip_hi, float* token_logp, float* token_surrogate, int64_t ld_out, float* logp,
                            float* surrogate, float* approx_kl, int32_t* tokens, int32_t* hits, int32_t* clipped,
                            void* stream) {
-  GCT_CHECK_ARG(logits && ys && token_logp && token_surrogate && logp && surrogate && approx_kl && tokens && hits &&
-                    clipped,
-                "seq_ppo: null pointer");
+  const SeqView v{logits, ld, V, rows_per_seq, row_shift, ys, ld_ys, prefix_lens, pad_id, W};
+  GCT_CHECK_ARG(token_logp && token_surrogate && logp && surrogate && approx_kl && tokens && hits && clipped,
+                "seq_ppo: null pointer (outputs)");
   GCT_CHECK_ARG(old_token_logp && advantage, "seq_ppo: null pointer (old_token_logp, advantage)");
-  GCT_CHECK_ARG(n >= 0 && V > 0 && ld >= V, "seq_ppo: bad shape (n %d, V %d, ld %lld)", n, V, (long long)ld);
-  GCT_CHECK_ARG(W >= 1 && W <= SEQ_LOGP_MAX_W, "seq_ppo: rows of %d tokens (1 .. %d supported)", W, SEQ_LOGP_MAX_W);
-  GCT_CHECK_ARG(ld_ys >= W && ld_out >= W && ld_old >= W,
-                "seq_ppo: ld_ys / ld_out / ld_old narrower than the %d token columns", W);
-  GCT_CHECK_ARG(row_shift >= 0 && rows_per_seq >= (int64_t)row_shift + W - 1,
-                "seq_ppo: %lld logits rows per sequence do not hold %d + %d", (long long)rows_per_seq, row_shift, W - 1);
-  GCT_CHECK_ARG(clip_lo >= 0.f && clip_lo < 1.f && clip_hi >= 0.f,
-                "seq_ppo: clip (%g, %g) outside 0 <= clip_lo < 1, clip_hi >= 0", (double)clip_lo, (double)clip_hi);
-  if (n == 0) return GCT_OK;
-  hipLaunchKernelGGL(seq_ppo_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, logits, ld, V, rows_per_seq,
-                     row_shift, ys, ld_ys, prefix_lens, pad_id, W, old_token_logp, ld_old, advantage, clip_lo, clip_hi,
-                     token_logp, token_surrogate, ld_out, logp, surrogate, approx_kl, tokens, hits, clipped);
-  GCT_LAUNCH_CHECK("seq_ppo");
-  return GCT_OK;
+  if (int rc = seq_check_view("seq_ppo", v, n, ld, std::min(ld_out, ld_old))) return rc;
+  if (int rc = seq_check_clip("seq_ppo", clip_lo, clip_hi)) return rc;
+  const PpoIn in{old_token_logp, ld_old, advantage, clip_lo, clip_hi};
+  return seq_launch_fwd("seq_ppo", v, n, PpoFwd{in, token_logp, token_surrogate, ld_out, logp, surrogate, approx_kl,
+                                                tokens, hits, clipped}, stream);
 }
 
 extern "C" int gct_seq_ppo_bwd(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift,
@@ -570,52 +574,30 @@ extern "C" int gct_seq_ppo_bwd(const float* logits, int64_t ld, int V, int64_t r
                                float clip_lo, float clip_hi, const float* g_surrogate,
                                const float* g_token_surrogate, int64_t ld_g, float* dlogits, int64_t ld_d,
                                void* stream) {
-  GCT_CHECK_ARG(logits && ys && dlogits, "seq_ppo_bwd: null pointer");
+  const SeqView v{logits, ld, V, rows_per_seq, row_shift, ys, ld_ys, prefix_lens, pad_id, W};
+  GCT_CHECK_ARG(dlogits, "seq_ppo_bwd: null pointer (dlogits)");
   GCT_CHECK_ARG(old_token_logp && advantage, "seq_ppo_bwd: null pointer (old_token_logp, advantage)");
   GCT_CHECK_ARG(g_surrogate || g_token_surrogate,
                 "seq_ppo_bwd: both gradients are null (g_surrogate, g_token_surrogate)");
-  GCT_CHECK_ARG(n >= 0 && V > 0 && ld >= V && ld_d >= V, "seq_ppo_bwd: bad shape (n %d, V %d, ld %lld, ld_d %lld)", n,
-                V, (long long)ld, (long long)ld_d);
-  GCT_CHECK_ARG(W >= 1 && W <= SEQ_LOGP_MAX_W, "seq_ppo_bwd: rows of %d tokens (1 .. %d supported)", W,
-                SEQ_LOGP_MAX_W);
-  GCT_CHECK_ARG(ld_ys >= W && ld_old >= W && (!g_token_surrogate || ld_g >= W),
-                "seq_ppo_bwd: ld_ys / ld_old / ld_g narrower than the %d token columns", W);
-  GCT_CHECK_ARG(row_shift >= 0 && rows_per_seq >= (int64_t)row_shift + W - 1,
-                "seq_ppo_bwd: %lld logits rows per sequence do not hold %d + %d", (long long)rows_per_seq, row_shift,
-                W - 1);
-  GCT_CHECK_ARG(clip_lo >= 0.f && clip_lo < 1.f && clip_hi >= 0.f,
-                "seq_ppo_bwd: clip (%g, %g) outside 0 <= clip_lo < 1, clip_hi >= 0", (double)clip_lo, (double)clip_hi);
-  const int64_t rows = (int64_t)n * rows_per_seq;
-  if (rows == 0) return GCT_OK;
-  int64_t g = (rows + 3) / 4;
-  g = g > 4096 ? 4096 : g;
-  hipLaunchKernelGGL(seq_ppo_bwd_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, logits, ld, V,
-                     rows_per_seq, row_shift, ys, ld_ys, prefix_lens, pad_id, W, old_token_logp, ld_old, advantage,
-                     clip_lo, clip_hi, g_surrogate, g_token_surrogate, ld_g, dlogits, ld_d, rows);
-  GCT_LAUNCH_CHECK("seq_ppo_bwd");
-  return GCT_OK;
+  if (int rc = seq_check_view("seq_ppo_bwd", v, n, std::min(ld, ld_d),
+                              std::min(ld_old, ld_if(g_token_surrogate, ld_g))))
+    return rc;
+  if (int rc = seq_check_clip("seq_ppo_bwd", clip_lo, clip_hi)) return rc;
+  const PpoIn in{old_token_logp, ld_old, advantage, clip_lo, clip_hi};
+  return seq_launch_bwd("seq_ppo_bwd", v, n, PpoBwd{in, g_surrogate, g_token_surrogate, ld_g}, dlogits, ld_d, stream);
 }
 
 extern "C" int gct_seq_dist(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift,
                             const float* prior_logits, int64_t ld_prior, const int64_t* ys, int64_t ld_ys,
                             const int32_t* prefix_lens, int64_t pad_id, int n, int W, float* token_entropy,
                             int64_t ld_out, float* entropy, float* token_kl, float* kl, void* stream) {
-  GCT_CHECK_ARG(logits && ys && token_entropy && entropy, "seq_dist: null pointer");
+  const SeqView v{logits, ld, V, rows_per_seq, row_shift, ys, ld_ys, prefix_lens, pad_id, W};
+  GCT_CHECK_ARG(token_entropy && entropy, "seq_dist: null pointer (outputs)");
   GCT_CHECK_ARG(prior_logits || (!token_kl && !kl), "seq_dist: kl outputs without prior logits");
   GCT_CHECK_ARG(!prior_logits || (token_kl && kl), "seq_dist: prior logits without kl outputs (null pointer)");
-  GCT_CHECK_ARG(n >= 0 && V > 0 && ld >= V && (!prior_logits || ld_prior >= V),
-                "seq_dist: bad shape (n %d, V %d, ld %lld, ld_prior %lld)", n, V, (long long)ld, (long long)ld_prior);
-  GCT_CHECK_ARG(W >= 1 && W <= SEQ_LOGP_MAX_W, "seq_dist: rows of %d tokens (1 .. %d supported)", W, SEQ_LOGP_MAX_W);
-  GCT_CHECK_ARG(ld_ys >= W && ld_out >= W, "seq_dist: ld_ys / ld_out narrower than the %d token columns", W);
-  GCT_CHECK_ARG(row_shift >= 0 && rows_per_seq >= (int64_t)row_shift + W - 1,
-                "seq_dist: %lld logits rows per sequence do not hold %d + %d", (long long)rows_per_seq, row_shift,
-                W - 1);
-  if (n == 0) return GCT_OK;
-  hipLaunchKernelGGL(seq_dist_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, logits, ld, V, rows_per_seq,
-                     row_shift, prior_logits, ld_prior, ys, ld_ys, prefix_lens, pad_id, W, token_entropy, ld_out,
-                     entropy, token_kl, kl);
-  GCT_LAUNCH_CHECK("seq_dist");
-  return GCT_OK;
+  if (int rc = seq_check_view("seq_dist", v, n, std::min(ld, ld_if(prior_logits, ld_prior)), ld_out)) return rc;
+  return seq_launch_fwd("seq_dist", v, n,
+                        DistFwd{prior_logits, ld_prior, token_entropy, ld_out, entropy, token_kl, kl}, stream);
 }
 
 extern "C" int gct_seq_dist_bwd(const float* logits, int64_t ld, int V, int64_t rows_per_seq, int row_shift,
@@ -623,29 +605,17 @@ extern "C" int gct_seq_dist_bwd(const float* logits, int64_t ld, int V, int64_t 
                                 const int32_t* prefix_lens, int64_t pad_id, int n, int W, const float* g_entropy,
                                 const float* g_token_entropy, int64_t ld_ge, const float* g_kl,
                                 const float* g_token_kl, int64_t ld_gk, float* dlogits, int64_t ld_d, void* stream) {
-  GCT_CHECK_ARG(logits && ys && dlogits, "seq_dist_bwd: null pointer");
+  const SeqView v{logits, ld, V, rows_per_seq, row_shift, ys, ld_ys, prefix_lens, pad_id, W};
+  GCT_CHECK_ARG(dlogits, "seq_dist_bwd: null pointer (dlogits)");
   GCT_CHECK_ARG(g_entropy || g_token_entropy || g_kl || g_token_kl,
                 "seq_dist_bwd: all four gradients are null (g_entropy, g_token_entropy, g_kl, g_token_kl)");
   GCT_CHECK_ARG(prior_logits || (!g_kl && !g_token_kl), "seq_dist_bwd: kl gradients without prior logits");
-  GCT_CHECK_ARG(n >= 0 && V > 0 && ld >= V && ld_d >= V && (!prior_logits || ld_prior >= V),
-                "seq_dist_bwd: bad shape (n %d, V %d, ld %lld, ld_prior %lld, ld_d %lld)", n, V, (long long)ld,
-                (long long)ld_prior, (long long)ld_d);
-  GCT_CHECK_ARG(W >= 1 && W <= SEQ_LOGP_MAX_W, "seq_dist_bwd: rows of %d tokens (1 .. %d supported)", W,
-                SEQ_LOGP_MAX_W);
-  GCT_CHECK_ARG(ld_ys >= W && (!g_token_entropy || ld_ge >= W) && (!g_token_kl || ld_gk >= W),
-                "seq_dist_bwd: ld_ys / ld_ge / ld_gk narrower than the %d token columns", W);
-  GCT_CHECK_ARG(row_shift >= 0 && rows_per_seq >= (int64_t)row_shift + W - 1,
-                "seq_dist_bwd: %lld logits rows per sequence do not hold %d + %d", (long long)rows_per_seq, row_shift,
-                W - 1);
-  const int64_t rows = (int64_t)n * rows_per_seq;
-  if (rows == 0) return GCT_OK;
-  int64_t g = (rows + 3) / 4;
-  g = g > 4096 ? 4096 : g;
-  hipLaunchKernelGGL(seq_dist_bwd_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, logits, ld, V,
-                     rows_per_seq, row_shift, prior_logits, ld_prior, ys, ld_ys, prefix_lens, pad_id, W, g_entropy,
-                     g_token_entropy, ld_ge, g_kl, g_token_kl, ld_gk, dlogits, ld_d, rows);
-  GCT_LAUNCH_CHECK("seq_dist_bwd");
-  return GCT_OK;
+  if (int rc = seq_check_view("seq_dist_bwd", v, n, std::min({ld, ld_d, ld_if(prior_logits, ld_prior)}),
+                              std::min(ld_if(g_token_entropy, ld_ge), ld_if(g_token_kl, ld_gk))))
+    return rc;
+  return seq_launch_bwd("seq_dist_bwd", v, n,
+                        DistBwd{prior_logits, ld_prior, g_entropy, g_token_entropy, ld_ge, g_kl, g_token_kl, ld_gk},
+                        dlogits, ld_d, stream);
 }
 
 extern "C" int gct_chosen_logp(const float* logits, int V, const int64_t* ys, int64_t ld_ys, const int32_t* pos,

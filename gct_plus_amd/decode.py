@@ -444,24 +444,50 @@ def score_reference(logits, ys, prefix_lens, pad_id):
       tokens [n] int32   the number of scored columns;
       hits [n] int32     the scored columns whose target is the FIRST maximum of its logits row (torch.argmax).
     A row without a scored column gives 0, 0, 0."""
+    ys, x, tgt, scored = _scored_rows(logits, ys, prefix_lens, pad_id)
+    y = x - x.max(-1, keepdim=True).values
+    lsm = y - torch.log(torch.exp(y).sum(-1, keepdim=True))
+    token_logp, logp = _column_sums(scored, lsm.gather(-1, tgt.unsqueeze(-1)).squeeze(-1))
+    hit = scored & (x.argmax(-1) == tgt)
+    return token_logp, logp, scored.sum(1).to(ys.device, torch.int32), hit.sum(1).to(torch.int32)
+
+
+def _scored_rows(logits, ys, prefix_lens, pad_id):
+    """Shared front of the six rules below: check_score_inputs and the shape check, then (ys as a tensor, x = the logits
+    [n, W - 1, V] in fp64 or fp32, the targets ys[:, 1:] int64 [n, W - 1], score_reference's SCORED predicate bool
+    [n, W - 1]), the last two on the device of x."""
     ys = torch.as_tensor(ys)
-    lens = check_score_inputs(ys, prefix_lens, logits.shape[-1]).to(ys.device)
+    lens = check_score_inputs(ys, prefix_lens, logits.shape[-1])
     n, W = ys.shape
     x = logits if logits.dtype == torch.float64 else logits.float()
     if tuple(x.shape[:2]) != (n, W - 1):
         raise ValueError(f"logits must be [{n}, {W - 1}, V], got {list(logits.shape)}")
-    y = x - x.max(-1, keepdim=True).values
-    lsm = y - torch.log(torch.exp(y).sum(-1, keepdim=True))
-    tgt = ys[:, 1:].long()
-    scored = (torch.arange(1, W, device=ys.device).view(1, -1) >= lens.view(-1, 1)) & (tgt != pad_id)
-    zero = torch.zeros((), dtype=x.dtype, device=x.device)
-    picked = torch.where(scored.to(x.device), lsm.gather(-1, tgt.to(x.device).unsqueeze(-1)).squeeze(-1), zero)
-    token_logp = torch.cat([torch.zeros(n, 1, dtype=x.dtype, device=x.device), picked], dim=1)
-    logp = torch.zeros(n, dtype=x.dtype, device=x.device)
+    tgt = ys[:, 1:].long().to(x.device)
+    scored = (torch.arange(1, W).view(1, -1) >= lens.view(-1, 1)).to(x.device) & (tgt != pad_id)
+    return ys, x, tgt, scored
+
+
+def _column_sums(scored, per_row):
+    """per_row [n, W - 1], a value per logits row -> the token table [n, W] (per_row at the scored columns, 0 elsewhere
+    and in column 0) and its row sums [n], added in ascending column order."""
+    n, W = per_row.shape[0], per_row.shape[1] + 1
+    zero = torch.zeros((), dtype=per_row.dtype, device=per_row.device)
+    table = torch.cat([zero.expand(n, 1), torch.where(scored, per_row, zero)], dim=1)
+    total = torch.zeros(n, dtype=per_row.dtype, device=per_row.device)
     for c in range(1, W):                                # ascending column order
-        logp = logp + token_logp[:, c]
-    hit = scored.to(x.device) & (x.argmax(-1) == tgt.to(x.device))
-    return token_logp, logp, scored.sum(1).to(torch.int32), hit.sum(1).to(torch.int32)
+        total = total + table[:, c]
+    return table, total
+
+
+def _grad_weight(g_row, g_table, like, n, W):
+    """The weight of every logits row [n, W - 1] under incoming gradients g_row [n] and g_table [n, W] (None: 0), in the
+    dtype and on the device of `like`: (g_row[r] + g_table[r, c]) for row c - 1."""
+    g = torch.zeros(n, W, dtype=like.dtype, device=like.device)
+    if g_row is not None:
+        g = g + torch.as_tensor(g_row).to(like.device, like.dtype).view(n, 1)
+    if g_table is not None:
+        g = g + torch.as_tensor(g_table).to(like.device, like.dtype).view(n, W)
+    return g[:, 1:]
 
 
 @planes_scope
@@ -482,42 +508,27 @@ def seq_logp_grad_reference(logits, ys, prefix_lens, pad_id, g_logp=None, g_toke
       exact zeros                                                   where it is not, or where g[r, c] == 0 -- whatever
     the logits row holds, NaN included: such a row is never looked at.
     Closed form, in the dtype of logits (fp32 at least), on the device of logits."""
-    ys = torch.as_tensor(ys)
-    lens = check_score_inputs(ys, prefix_lens, logits.shape[-1])
+    ys, x, tgt, scored = _scored_rows(logits, ys, prefix_lens, pad_id)
     n, W = ys.shape
-    x = logits if logits.dtype == torch.float64 else logits.float()
-    if tuple(x.shape[:2]) != (n, W - 1):
-        raise ValueError(f"logits must be [{n}, {W - 1}, V], got {list(logits.shape)}")
-    dev = x.device
-    tgt = ys[:, 1:].long().to(dev)
-    scored = (torch.arange(1, W).view(1, -1) >= lens.view(-1, 1)).to(dev) & (tgt != pad_id)
-    g = torch.zeros(n, W, dtype=x.dtype, device=dev)
-    if g_logp is not None:
-        g = g + torch.as_tensor(g_logp).to(dev, x.dtype).view(n, 1)
-    if g_token is not None:
-        g = g + torch.as_tensor(g_token).to(dev, x.dtype).view(n, W)
-    live = scored & (g[:, 1:] != 0)
+    g = _grad_weight(g_logp, g_token, x, n, W)
+    live = scored & (g != 0)
     e = torch.exp(x - x.max(-1, keepdim=True).values)
     grad = -(e / e.sum(-1, keepdim=True))
-    grad.scatter_add_(-1, tgt.unsqueeze(-1), torch.ones(n, W - 1, 1, dtype=x.dtype, device=dev))
-    return torch.where(live.unsqueeze(-1), g[:, 1:].unsqueeze(-1) * grad, torch.zeros((), dtype=x.dtype, device=dev))
+    grad.scatter_add_(-1, tgt.unsqueeze(-1), torch.ones(n, W - 1, 1, dtype=x.dtype, device=x.device))
+    return torch.where(live.unsqueeze(-1), g.unsqueeze(-1) * grad, torch.zeros((), dtype=x.dtype, device=x.device))
 
 
-def _dist_rows(logits, prior_logits, ys, prefix_lens):
-    """Shared front of dist_reference / dist_grad_reference: (x, y or None, n, W, prefix lengths on the CPU)."""
-    ys = torch.as_tensor(ys)
-    lens = check_score_inputs(ys, prefix_lens, logits.shape[-1])
-    n, W = ys.shape
-    x = logits if logits.dtype == torch.float64 else logits.float()
-    if tuple(x.shape[:2]) != (n, W - 1):
-        raise ValueError(f"logits must be [{n}, {W - 1}, V], got {list(logits.shape)}")
+def _dist_rows(logits, prior_logits, ys, prefix_lens, pad_id):
+    """Shared front of dist_reference / dist_grad_reference: _scored_rows' (ys, x, scored) and the prior's logits in the
+    dtype and on the device of x (None without a prior)."""
+    ys, x, _, scored = _scored_rows(logits, ys, prefix_lens, pad_id)
     y = None
     if prior_logits is not None:
         if prior_logits.shape != logits.shape:
             raise ValueError(f"prior_logits must have the shape of logits {list(logits.shape)}, got "
                              f"{list(prior_logits.shape)}")
         y = prior_logits.to(x.device, x.dtype)
-    return ys, x, y, n, W, lens
+    return ys, x, y, scored
 
 
 def _log_softmax_rows(x, live):
@@ -551,25 +562,14 @@ def dist_reference(logits, ys, prefix_lens, pad_id, prior_logits=None):
       entropy [n], kl [n]   the sums of a row's scored columns in ascending column order; 0 for a row with none.
     Returns (token_entropy, entropy, token_kl, kl), the last two None without prior_logits, in the dtype of logits (fp32
     at least) on the device of logits."""
-    ys, x, y, n, W, lens = _dist_rows(logits, prior_logits, ys, prefix_lens)
-    dev = x.device
-    tgt = ys[:, 1:].long().to(dev)
-    scored = (torch.arange(1, W).view(1, -1) >= lens.view(-1, 1)).to(dev) & (tgt != pad_id)
-    zero = torch.zeros((), dtype=x.dtype, device=dev)
+    ys, x, y, scored = _dist_rows(logits, prior_logits, ys, prefix_lens, pad_id)
+    zero = torch.zeros((), dtype=x.dtype, device=x.device)
     p, logp = _p_logp(x, scored)
-    first = torch.zeros(n, 1, dtype=x.dtype, device=dev)
-
-    def columns(per_row):                                # [n, W - 1] -> token table [n, W] and its row sums
-        table = torch.cat([first, torch.where(scored, per_row, zero)], dim=1)
-        total = torch.zeros(n, dtype=x.dtype, device=dev)
-        for c in range(1, W):                            # ascending column order
-            total = total + table[:, c]
-        return table, total
-    token_entropy, entropy = columns(-(p * logp).sum(-1))
+    token_entropy, entropy = _column_sums(scored, -(p * logp).sum(-1))
     if y is None:
         return token_entropy, entropy, None, None
     logq = torch.where(p > 0, _log_softmax_rows(y, scored), zero)   # q_v plays no part where p_v == 0
-    token_kl, kl = columns((p * (logp - logq)).sum(-1))
+    token_kl, kl = _column_sums(scored, (p * (logp - logq)).sum(-1))
     return token_entropy, entropy, token_kl, kl
 
 
@@ -586,20 +586,9 @@ def dist_grad_reference(logits, ys, prefix_lens, pad_id, prior_logits=None, g_en
     p_v == 0 get exact zeros.  Closed form, in the dtype of logits (fp32 at least), on the device of logits."""
     if prior_logits is None and (g_kl is not None or g_token_kl is not None):
         raise ValueError("dist_grad_reference: g_kl / g_token_kl need prior_logits")
-    ys, x, y, n, W, lens = _dist_rows(logits, prior_logits, ys, prefix_lens)
-    dev = x.device
-    tgt = ys[:, 1:].long().to(dev)
-    scored = (torch.arange(1, W).view(1, -1) >= lens.view(-1, 1)).to(dev) & (tgt != pad_id)
-    zero = torch.zeros((), dtype=x.dtype, device=dev)
-
-    def weight(g_row, g_tab):
-        g = torch.zeros(n, W, dtype=x.dtype, device=dev)
-        if g_row is not None:
-            g = g + torch.as_tensor(g_row).to(dev, x.dtype).view(n, 1)
-        if g_tab is not None:
-            g = g + torch.as_tensor(g_tab).to(dev, x.dtype).view(n, W)
-        return g[:, 1:]
-    a, b = weight(g_entropy, g_token_entropy), weight(g_kl, g_token_kl)
+    ys, x, y, scored = _dist_rows(logits, prior_logits, ys, prefix_lens, pad_id)
+    zero = torch.zeros((), dtype=x.dtype, device=x.device)
+    a, b = _grad_weight(g_entropy, g_token_entropy, x, *ys.shape), _grad_weight(g_kl, g_token_kl, x, *ys.shape)
     live = scored & ((a != 0) | (b != 0))
     p, logp = _p_logp(x, live)
     H = -(p * logp).sum(-1, keepdim=True)
@@ -658,16 +647,10 @@ def _ppo_rows(logits, ys, prefix_lens, pad_id, old_token_logp, advantage, clip_l
     """Shared front of ppo_reference / ppo_grad_reference: (ys, x, n, W, scored [n, W - 1], targets [n, W - 1], old
     [n, W - 1], A [n, 1], lo, hi) in the dtype and on the device of x; lo = 1 - clip_lo and hi = 1 + clip_hi are formed
     in that dtype."""
-    ys = torch.as_tensor(ys)
-    lens = check_score_inputs(ys, prefix_lens, logits.shape[-1])
+    ys, x, tgt, scored = _scored_rows(logits, ys, prefix_lens, pad_id)
     n, W = ys.shape
-    x = logits if logits.dtype == torch.float64 else logits.float()
-    if tuple(x.shape[:2]) != (n, W - 1):
-        raise ValueError(f"logits must be [{n}, {W - 1}, V], got {list(logits.shape)}")
     adv = check_ppo_inputs(torch.as_tensor(old_token_logp), advantage, clip_lo, clip_hi, n, W)
     dev = x.device
-    tgt = ys[:, 1:].long().to(dev)
-    scored = (torch.arange(1, W).view(1, -1) >= lens.view(-1, 1)).to(dev) & (tgt != pad_id)
     old = torch.as_tensor(old_token_logp).to(dev, x.dtype)[:, 1:]
     A = adv.to(dev, x.dtype).view(n, 1)
     one = torch.ones((), dtype=x.dtype, device=dev)
@@ -694,23 +677,13 @@ def ppo_reference(logits, ys, prefix_lens, pad_id, old_token_logp, advantage, cl
     arithmetic decides."""
     ys, x, n, W, scored, tgt, old, A, lo, hi = _ppo_rows(logits, ys, prefix_lens, pad_id, old_token_logp, advantage,
                                                          clip_lo, clip_hi)
-    dev = x.device
     token_logp, logp, tokens, hits = score_reference(x, ys, prefix_lens, pad_id)
-    zero = torch.zeros((), dtype=x.dtype, device=dev)
-    d = torch.where(scored, token_logp[:, 1:] - old, zero)
+    d = torch.where(scored, token_logp[:, 1:] - old, torch.zeros((), dtype=x.dtype, device=x.device))
     rho = torch.exp(d)
     up = scored & (A > 0) & (rho > hi)
     down = scored & (A < 0) & (rho < lo)
-    first = torch.zeros(n, 1, dtype=x.dtype, device=dev)
-
-    def columns(per_row):                                # [n, W - 1] -> token table [n, W] and its row sums
-        table = torch.cat([first, torch.where(scored, per_row, zero)], dim=1)
-        total = torch.zeros(n, dtype=x.dtype, device=dev)
-        for c in range(1, W):                            # ascending column order
-            total = total + table[:, c]
-        return table, total
-    token_surrogate, surrogate = columns(torch.where(up, A * hi, torch.where(down, A * lo, A * rho)))
-    _, approx_kl = columns((rho - 1) - d)
+    token_surrogate, surrogate = _column_sums(scored, torch.where(up, A * hi, torch.where(down, A * lo, A * rho)))
+    _, approx_kl = _column_sums(scored, (rho - 1) - d)
     return (token_logp, token_surrogate, logp, surrogate, approx_kl, tokens, hits,
             (up | down).sum(1).to(torch.int32))
 
@@ -730,12 +703,7 @@ def ppo_grad_reference(logits, ys, prefix_lens, pad_id, old_token_logp, advantag
                                                          clip_lo, clip_hi)
     dev = x.device
     zero = torch.zeros((), dtype=x.dtype, device=dev)
-    g = torch.zeros(n, W, dtype=x.dtype, device=dev)
-    if g_surrogate is not None:
-        g = g + torch.as_tensor(g_surrogate).to(dev, x.dtype).view(n, 1)
-    if g_token_surrogate is not None:
-        g = g + torch.as_tensor(g_token_surrogate).to(dev, x.dtype).view(n, W)
-    g = g[:, 1:]
+    g = _grad_weight(g_surrogate, g_token_surrogate, x, n, W)
     looked = scored & (g != 0) & (A != 0)
     lsm = _log_softmax_rows(x, looked)                   # the other rows: zeros before any arithmetic
     d = torch.where(looked, lsm.gather(-1, tgt.unsqueeze(-1)).squeeze(-1) - old, zero)
@@ -838,19 +806,8 @@ def sequence_logp(model, z, src_mask, dconds, ys, prefix_lens=None, pad_id=1):
     the graph: z is an input.
     ValueError before any device work for whatever check_score_inputs refuses, for rows beyond the positional table, and
     for a batch without a single scored column.  A single row with nothing scored is fine: value 0, gradient 0."""
-    ys, lens, c2d, off, V = _score_geometry(model, ys, prefix_lens)
-    n, W = ys.shape
-    host = ys.detach().cpu()
-    if not bool(((torch.arange(W).view(1, -1) >= lens.view(-1, 1)) & (host != pad_id))[:, 1:].any()):
-        raise ValueError("sequence_logp: no column of the batch is scored (every row is prefix or pad)")
-    dev = z.device
-    y = ys.to(dev, torch.int64).contiguous()
-    t0 = lens.to(dev)
-    dc = None if dconds is None else dconds.to(dev)
-    sm = None if src_mask is None else src_mask.to(dev)
-    logits2d, rows = _scoring_logits(model, z, sm, dc, y, t0, pad_id, c2d)
-    logp, token_logp, tokens, hits = engine.SeqLogpFn.apply(
-        logits2d, y, None if prefix_lens is None else t0.to(torch.int32), pad_id, off)
+    r = _policy_rows("sequence_logp", model, z, src_mask, dconds, ys, prefix_lens, pad_id, prior=None)
+    logp, token_logp, tokens, hits = engine.SeqLogpFn.apply(r.logits2d, r.y, r.t0_dev, pad_id, r.off)
     return logp, tokens, hits, token_logp
 
 

@@ -920,6 +920,30 @@ class CrossEntropySumFn(torch.autograd.Function):
         return ops.ce_bwd(l2, t, _f32c(g), ctx.pad_id).view(ctx.shp), None, None
 
 
+def _seq_rows2d(who, what, t, ys, row_shift):
+    """Logits t [n, R, V] or [n * R, V] for the token rows ys [n, W], as the seq_* kernels take them: (fp32 [n * R, V]
+    with unit column stride -- t itself where it already is one --, R).  `what` names t in the message."""
+    n, V = ys.shape[0], t.shape[-1]
+    if t.dim() == 3:
+        if t.shape[0] != n:
+            raise ValueError(f"{who}: {t.shape[0]} {what} blocks for {n} token rows")
+        t2 = _f32c(t).view(-1, V)
+    elif t.dim() == 2 and t.dtype == torch.float32 and t.stride(1) == 1:
+        t2 = t
+    else:
+        t2 = _f32c(t).reshape(-1, V)
+    return t2, t2.shape[0] // n if n else ys.shape[1] - 1 + int(row_shift)
+
+
+def _seq_backward(shape, l2, grads, inputs, run):
+    """What a seq_* Function's backward returns for its `inputs` inputs: dlogits = run(*grads as fp32 contiguous, None
+    kept) in the shape the forward got -- zeros without a launch when every gradient is None --, then None for the
+    rest."""
+    gs = [None if g is None else _f32c(g) for g in grads]
+    dl = torch.zeros(shape, device=l2.device) if all(g is None for g in gs) else run(*gs).view(shape)
+    return (dl,) + (None,) * (inputs - 1)
+
+
 class SeqLogpFn(torch.autograd.Function):
     """Per-sequence log-likelihoods with a gradient (decode.score_reference / seq_logp_grad_reference state the rules):
     apply(logits, ys, prefix_lens, pad_id, row_shift) -> (logp [n], token_logp [n, W], tokens [n], hits [n]).
@@ -929,16 +953,7 @@ class SeqLogpFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, ys, prefix_lens, pad_id, row_shift):
-        n, V = ys.shape[0], logits.shape[-1]
-        if logits.dim() == 3:
-            if logits.shape[0] != n:
-                raise ValueError(f"SeqLogpFn: {logits.shape[0]} logits blocks for {n} token rows")
-            l2 = _f32c(logits).view(-1, V)
-        elif logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1:
-            l2 = logits
-        else:
-            l2 = _f32c(logits).reshape(-1, V)
-        R = l2.shape[0] // n if n else ys.shape[1] - 1 + int(row_shift)
+        l2, R = _seq_rows2d("SeqLogpFn", "logits", logits, ys, row_shift)
         ys = ys.contiguous()
         tl, lp, nt, nh = ops.seq_logp(l2, ys, prefix_lens, int(pad_id), row_shift=int(row_shift), rows_per_seq=R)
         ctx.save_for_backward(l2, ys, prefix_lens)
@@ -952,12 +967,8 @@ class SeqLogpFn(torch.autograd.Function):
     def backward(ctx, g_logp, g_token, *unused):
         l2, ys, prefix_lens = ctx.saved_tensors
         pad_id, row_shift, R, shape = ctx.geom
-        if g_logp is None and g_token is None:
-            return torch.zeros(shape, device=l2.device), None, None, None, None
-        dl = ops.seq_logp_bwd(l2, ys, prefix_lens, pad_id, row_shift=row_shift, rows_per_seq=R,
-                              g_logp=None if g_logp is None else _f32c(g_logp),
-                              g_token=None if g_token is None else _f32c(g_token))
-        return dl.view(shape), None, None, None, None
+        return _seq_backward(shape, l2, (g_logp, g_token), 5, lambda gl, gt: ops.seq_logp_bwd(
+            l2, ys, prefix_lens, pad_id, row_shift=row_shift, rows_per_seq=R, g_logp=gl, g_token=gt))
 
 
 class SeqDistFn(torch.autograd.Function):
@@ -971,19 +982,9 @@ class SeqDistFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, prior_logits, ys, prefix_lens, pad_id, row_shift):
-        n, V = ys.shape[0], logits.shape[-1]
-
-        def rows2d(t, what):
-            if t.dim() == 3:
-                if t.shape[0] != n:
-                    raise ValueError(f"SeqDistFn: {t.shape[0]} {what} blocks for {n} token rows")
-                return _f32c(t).view(-1, V)
-            if t.dim() == 2 and t.dtype == torch.float32 and t.stride(1) == 1:
-                return t
-            return _f32c(t).reshape(-1, V)
-        l2 = rows2d(logits, "logits")
-        q2 = None if prior_logits is None else rows2d(prior_logits.detach(), "prior logits")
-        R = l2.shape[0] // n if n else ys.shape[1] - 1 + int(row_shift)
+        l2, R = _seq_rows2d("SeqDistFn", "logits", logits, ys, row_shift)
+        q2 = None if prior_logits is None else _seq_rows2d("SeqDistFn", "prior logits", prior_logits.detach(), ys,
+                                                           row_shift)[0]
         ys = ys.contiguous()
         te, en, tk, kl = ops.seq_dist(l2, ys, prefix_lens, int(pad_id), row_shift=int(row_shift), rows_per_seq=R,
                                       prior_logits2d=q2)
@@ -997,12 +998,10 @@ class SeqDistFn(torch.autograd.Function):
     def backward(ctx, g_entropy, g_token_entropy, g_kl, g_token_kl):
         l2, q2, ys, prefix_lens = ctx.saved_tensors
         pad_id, row_shift, R, shape = ctx.geom
-        gs = [None if g is None else _f32c(g) for g in (g_entropy, g_token_entropy, g_kl, g_token_kl)]
-        if all(g is None for g in gs):
-            return torch.zeros(shape, device=l2.device), None, None, None, None, None
-        dl = ops.seq_dist_bwd(l2, ys, prefix_lens, pad_id, row_shift=row_shift, rows_per_seq=R, prior_logits2d=q2,
-                              g_entropy=gs[0], g_token_entropy=gs[1], g_kl=gs[2], g_token_kl=gs[3])
-        return dl.view(shape), None, None, None, None, None
+        return _seq_backward(shape, l2, (g_entropy, g_token_entropy, g_kl, g_token_kl), 6,
+                             lambda ge, gte, gk, gtk: ops.seq_dist_bwd(
+                                 l2, ys, prefix_lens, pad_id, row_shift=row_shift, rows_per_seq=R, prior_logits2d=q2,
+                                 g_entropy=ge, g_token_entropy=gte, g_kl=gk, g_token_kl=gtk))
 
 
 class SeqPpoFn(torch.autograd.Function):
@@ -1017,16 +1016,7 @@ class SeqPpoFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, ys, prefix_lens, pad_id, row_shift, old_token_logp, advantage, clip_lo, clip_hi):
-        n, V = ys.shape[0], logits.shape[-1]
-        if logits.dim() == 3:
-            if logits.shape[0] != n:
-                raise ValueError(f"SeqPpoFn: {logits.shape[0]} logits blocks for {n} token rows")
-            l2 = _f32c(logits).view(-1, V)
-        elif logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1:
-            l2 = logits
-        else:
-            l2 = _f32c(logits).reshape(-1, V)
-        R = l2.shape[0] // n if n else ys.shape[1] - 1 + int(row_shift)
+        l2, R = _seq_rows2d("SeqPpoFn", "logits", logits, ys, row_shift)
         ys = ys.contiguous()
         old = _f32c(old_token_logp.detach())
         adv = _f32c(advantage.detach()).view(-1)
@@ -1043,13 +1033,9 @@ class SeqPpoFn(torch.autograd.Function):
     def backward(ctx, g_surrogate, g_token_surrogate, *unused):
         l2, ys, prefix_lens, old, adv = ctx.saved_tensors
         pad_id, row_shift, R, shape, clip_lo, clip_hi = ctx.geom
-        none = (None,) * 8
-        if g_surrogate is None and g_token_surrogate is None:
-            return (torch.zeros(shape, device=l2.device),) + none
-        dl = ops.seq_ppo_bwd(l2, ys, old, adv, clip_lo, clip_hi, prefix_lens, pad_id, row_shift=row_shift,
-                             rows_per_seq=R, g_surrogate=None if g_surrogate is None else _f32c(g_surrogate),
-                             g_token_surrogate=None if g_token_surrogate is None else _f32c(g_token_surrogate))
-        return (dl.view(shape),) + none
+        return _seq_backward(shape, l2, (g_surrogate, g_token_surrogate), 9, lambda gs, gts: ops.seq_ppo_bwd(
+            l2, ys, old, adv, clip_lo, clip_hi, prefix_lens, pad_id, row_shift=row_shift, rows_per_seq=R,
+            g_surrogate=gs, g_token_surrogate=gts))
 
 
 class KldFn(torch.autograd.Function):

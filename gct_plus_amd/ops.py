@@ -1148,91 +1148,9 @@ def grammar_mask(logits2d, masked, table, ys, pos_dev, width=None, row_off=None,
                                 _p(item), _p(prefix_len), _p(limit), _st()), "gct_grammar_mask")
 
 
-def seq_logp(logits2d, ys, prefix_lens=None, pad_id=1, row_shift=0, rows_per_seq=None, V=None, out=None):
-    """gct_seq_logp (decode.score_reference states the rule): ys int64 [n, W] full token rows, logits2d fp32
-    [n * rows_per_seq, V] with unit column stride (a strided view is fine: ld = its row stride); the logits row of token
-    column c of sequence r is r * rows_per_seq + row_shift + c - 1 (rows_per_seq defaults to W - 1).  prefix_lens int32
-    [n] on the device or None (every row: 1).  logits2d None (with V given) passes a null pointer: the library refuses.
-    Returns (token_logp [n, W] fp32, logp [n] fp32, tokens [n] int32, hits [n] int32), or fills `out`, a tuple of them."""
-    _chk(ys, "seq_logp.ys", torch.int64)
-    if ys.dim() != 2 or ys.stride(1) != 1:
-        raise ValueError("seq_logp: ys must be [n, W] with unit column stride")
-    n, W = ys.shape
-    R = W - 1 if rows_per_seq is None else int(rows_per_seq)
-    ld = 0
-    if logits2d is not None:
-        _chk(logits2d, "seq_logp.logits")
-        if logits2d.dim() != 2 or logits2d.stride(1) != 1 or logits2d.shape[0] < n * R:
-            raise ValueError(f"seq_logp: logits must be [>= {n * R}, V] with unit column stride, got "
-                             f"{list(logits2d.shape)}")
-        V, ld = logits2d.shape[1], logits2d.stride(0)
-    if prefix_lens is not None:
-        _check_row_off(prefix_lens, n)
-    dev = ys.device
-    if out is None:
-        out = (torch.empty(n, W, device=dev), torch.empty(n, device=dev),
-               torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
-    tl, lp, nt, nh = out
-    _chk(tl, "seq_logp.token_logp"), _chk(lp, "seq_logp.logp")
-    _chk(nt, "seq_logp.tokens", torch.int32), _chk(nh, "seq_logp.hits", torch.int32)
-    if tl.shape != (n, W) or tl.stride(1) != 1 or any(t.numel() != n or not t.is_contiguous() for t in (lp, nt, nh)):
-        raise ValueError("seq_logp: out must be (token_logp [n, W], logp [n], tokens [n], hits [n])")
-    check(_L().gct_seq_logp(_p(logits2d), ld, int(V), R, int(row_shift), _p(ys), ys.stride(0), _p(prefix_lens),
-                            int(pad_id), n, W, _p(tl), tl.stride(0), _p(lp), _p(nt), _p(nh), _st()), "gct_seq_logp")
-    return out
-
-
-def seq_logp_bwd(logits2d, ys, prefix_lens=None, pad_id=1, row_shift=0, rows_per_seq=None, g_logp=None, g_token=None,
-                 V=None, out=None):
-    """gct_seq_logp_bwd (decode.seq_logp_grad_reference states the rule): the gradient of seq_logp's logp [n] and
-    token_logp [n, W] with respect to the logits, for the geometry seq_logp takes (same checks: ys int64 [n, W], logits2d
-    fp32 [>= n * rows_per_seq, V] with unit column stride, a strided view is fine; prefix_lens int32 [n] or None).
-    g_logp fp32 [n] / g_token fp32 [n, W] with unit column stride: the incoming gradients, either may be None (0), the
-    library refuses both.  logits2d None (with V given) passes a null pointer: the library refuses.
-    Returns dlogits fp32, contiguous, in the shape of logits2d (or fills `out`, [>= n * rows_per_seq, V] with unit column
-    stride): every row is written -- zeros on the rows that are not scored or whose weight is 0, whose logits are not
-    read."""
-    _chk(ys, "seq_logp_bwd.ys", torch.int64)
-    if ys.dim() != 2 or ys.stride(1) != 1:
-        raise ValueError("seq_logp_bwd: ys must be [n, W] with unit column stride")
-    n, W = ys.shape
-    R = W - 1 if rows_per_seq is None else int(rows_per_seq)
-    ld = 0
-    if logits2d is not None:
-        _chk(logits2d, "seq_logp_bwd.logits")
-        if logits2d.dim() != 2 or logits2d.stride(1) != 1 or logits2d.shape[0] < n * R:
-            raise ValueError(f"seq_logp_bwd: logits must be [>= {n * R}, V] with unit column stride, got "
-                             f"{list(logits2d.shape)}")
-        V, ld = logits2d.shape[1], logits2d.stride(0)
-    if prefix_lens is not None:
-        _check_row_off(prefix_lens, n)
-    if g_logp is not None:
-        _chk(g_logp, "seq_logp_bwd.g_logp")
-        if g_logp.numel() != n or not g_logp.is_contiguous():
-            raise ValueError(f"seq_logp_bwd: g_logp must be a contiguous fp32 tensor of {n} entries")
-    if g_token is not None:
-        _chk(g_token, "seq_logp_bwd.g_token")
-        if g_token.shape != (n, W) or g_token.stride(1) != 1:
-            raise ValueError(f"seq_logp_bwd: g_token must be [{n}, {W}] with unit column stride")
-    rows = max(n * R, 0 if logits2d is None else logits2d.shape[0])
-    if out is None:
-        out = torch.empty(rows, int(V), device=ys.device)
-        if rows > n * R:
-            out[n * R:].zero_()                          # rows behind the last sequence belong to nobody
-    _chk(out, "seq_logp_bwd.dlogits")
-    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < n * R or out.shape[1] != int(V):
-        raise ValueError(f"seq_logp_bwd: out must be [>= {n * R}, {int(V)}] with unit column stride")
-    if n == 0:
-        return out                                       # no sequence: nothing to write (an empty tensor has no address)
-    check(_L().gct_seq_logp_bwd(_p(logits2d), ld, int(V), R, int(row_shift), _p(ys), ys.stride(0), _p(prefix_lens),
-                                int(pad_id), n, W, _p(g_logp), _p(g_token), 0 if g_token is None else g_token.stride(0),
-                                _p(out), out.stride(0), _st()), "gct_seq_logp_bwd")
-    return out
-
-
 def _seq_geometry(name, logits2d, ys, rows_per_seq, V, prefix_lens, prior2d=None):
-    """The checks seq_logp makes on (ys, logits, prefix_lens), for seq_dist / seq_dist_bwd, with the prior's logits next
-    to the agent's: (n, W, R, V, ld, ld_prior)."""
+    """The checks every seq_* wrapper makes on (ys, logits, prefix_lens), with seq_dist's prior logits next to the
+    agent's: (n, W, R, V, ld, ld_prior).  `name` (the caller's) opens every message, here and in the helpers below."""
     _chk(ys, f"{name}.ys", torch.int64)
     if ys.dim() != 2 or ys.stride(1) != 1:
         raise ValueError(f"{name}: ys must be [n, W] with unit column stride")
@@ -1254,6 +1172,82 @@ def _seq_geometry(name, logits2d, ys, rows_per_seq, V, prefix_lens, prior2d=None
     if prefix_lens is not None:
         _check_row_off(prefix_lens, n)
     return n, W, R, int(V), ld, ld_prior
+
+
+def _seq_vector(name, what, t, n):
+    """A per-sequence input (an incoming gradient, PPO's advantage): None, or fp32 [n] contiguous."""
+    if t is not None:
+        _chk(t, f"{name}.{what}")
+        if t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be a contiguous fp32 tensor of {n} entries")
+
+
+def _seq_table(name, what, t, n, W):
+    """A per-token input (an incoming gradient, PPO's old_token_logp): None, or fp32 [n, W] with unit column stride.
+    Returns the row stride to pass (0 for None)."""
+    if t is None:
+        return 0
+    _chk(t, f"{name}.{what}")
+    if t.shape != (n, W) or t.stride(1) != 1:
+        raise ValueError(f"{name}: {what} must be [{n}, {W}] with unit column stride")
+    return t.stride(0)
+
+
+def _seq_dlogits(name, out, logits2d, ys, R, V, launch):
+    """What every backward wrapper does with its result: allocate dlogits in the shape of logits2d (zeros on the rows
+    behind the last sequence: they belong to nobody) or validate the caller's `out`, then `launch(dlogits)` -- unless
+    there is no sequence: nothing to write then (an empty tensor has no address).  Returns dlogits."""
+    n = ys.shape[0]
+    if out is None:
+        rows = max(n * R, 0 if logits2d is None else logits2d.shape[0])
+        out = torch.empty(rows, V, device=ys.device)
+        if rows > n * R:
+            out[n * R:].zero_()
+    _chk(out, f"{name}.dlogits")
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < n * R or out.shape[1] != V:
+        raise ValueError(f"{name}: out must be [>= {n * R}, {V}] with unit column stride")
+    if n:
+        launch(out)
+    return out
+
+
+def seq_logp(logits2d, ys, prefix_lens=None, pad_id=1, row_shift=0, rows_per_seq=None, V=None, out=None):
+    """gct_seq_logp (decode.score_reference states the rule): ys int64 [n, W] full token rows, logits2d fp32
+    [n * rows_per_seq, V] with unit column stride (a strided view is fine: ld = its row stride); the logits row of token
+    column c of sequence r is r * rows_per_seq + row_shift + c - 1 (rows_per_seq defaults to W - 1).  prefix_lens int32
+    [n] on the device or None (every row: 1).  logits2d None (with V given) passes a null pointer: the library refuses.
+    Returns (token_logp [n, W] fp32, logp [n] fp32, tokens [n] int32, hits [n] int32), or fills `out`, a tuple of them."""
+    n, W, R, V, ld, _ = _seq_geometry("seq_logp", logits2d, ys, rows_per_seq, V, prefix_lens)
+    dev = ys.device
+    if out is None:
+        out = (torch.empty(n, W, device=dev), torch.empty(n, device=dev),
+               torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+    tl, lp, nt, nh = out
+    _chk(tl, "seq_logp.token_logp"), _chk(lp, "seq_logp.logp")
+    _chk(nt, "seq_logp.tokens", torch.int32), _chk(nh, "seq_logp.hits", torch.int32)
+    if tl.shape != (n, W) or tl.stride(1) != 1 or any(t.numel() != n or not t.is_contiguous() for t in (lp, nt, nh)):
+        raise ValueError("seq_logp: out must be (token_logp [n, W], logp [n], tokens [n], hits [n])")
+    check(_L().gct_seq_logp(_p(logits2d), ld, V, R, int(row_shift), _p(ys), ys.stride(0), _p(prefix_lens),
+                            int(pad_id), n, W, _p(tl), tl.stride(0), _p(lp), _p(nt), _p(nh), _st()), "gct_seq_logp")
+    return out
+
+
+def seq_logp_bwd(logits2d, ys, prefix_lens=None, pad_id=1, row_shift=0, rows_per_seq=None, g_logp=None, g_token=None,
+                 V=None, out=None):
+    """gct_seq_logp_bwd (decode.seq_logp_grad_reference states the rule): the gradient of seq_logp's logp [n] and
+    token_logp [n, W] with respect to the logits, for the geometry seq_logp takes (same checks: ys int64 [n, W], logits2d
+    fp32 [>= n * rows_per_seq, V] with unit column stride, a strided view is fine; prefix_lens int32 [n] or None).
+    g_logp fp32 [n] / g_token fp32 [n, W] with unit column stride: the incoming gradients, either may be None (0), the
+    library refuses both.  logits2d None (with V given) passes a null pointer: the library refuses.
+    Returns dlogits fp32, contiguous, in the shape of logits2d (or fills `out`, [>= n * rows_per_seq, V] with unit column
+    stride): every row is written -- zeros on the rows that are not scored or whose weight is 0, whose logits are not
+    read."""
+    n, W, R, V, ld, _ = _seq_geometry("seq_logp_bwd", logits2d, ys, rows_per_seq, V, prefix_lens)
+    _seq_vector("seq_logp_bwd", "g_logp", g_logp, n)
+    ld_g = _seq_table("seq_logp_bwd", "g_token", g_token, n, W)
+    return _seq_dlogits("seq_logp_bwd", out, logits2d, ys, R, V, lambda dl: check(_L().gct_seq_logp_bwd(
+        _p(logits2d), ld, V, R, int(row_shift), _p(ys), ys.stride(0), _p(prefix_lens), int(pad_id), n, W, _p(g_logp),
+        _p(g_token), ld_g, _p(dl), dl.stride(0), _st()), "gct_seq_logp_bwd"))
 
 
 def seq_dist(logits2d, ys, prefix_lens=None, pad_id=1, row_shift=0, rows_per_seq=None, prior_logits2d=None, V=None,
@@ -1296,46 +1290,21 @@ def seq_dist_bwd(logits2d, ys, prefix_lens=None, pad_id=1, row_shift=0, rows_per
     stride): every row is written -- zeros on the rows that are not scored or whose weights are 0, where neither model's
     logits are read."""
     n, W, R, V, ld, ld_prior = _seq_geometry("seq_dist_bwd", logits2d, ys, rows_per_seq, V, prefix_lens, prior_logits2d)
-    for g, what in ((g_entropy, "g_entropy"), (g_kl, "g_kl")):
-        if g is not None:
-            _chk(g, f"seq_dist_bwd.{what}")
-            if g.numel() != n or not g.is_contiguous():
-                raise ValueError(f"seq_dist_bwd: {what} must be a contiguous fp32 tensor of {n} entries")
-    for g, what in ((g_token_entropy, "g_token_entropy"), (g_token_kl, "g_token_kl")):
-        if g is not None:
-            _chk(g, f"seq_dist_bwd.{what}")
-            if g.shape != (n, W) or g.stride(1) != 1:
-                raise ValueError(f"seq_dist_bwd: {what} must be [{n}, {W}] with unit column stride")
-    rows = max(n * R, 0 if logits2d is None else logits2d.shape[0])
-    if out is None:
-        out = torch.empty(rows, V, device=ys.device)
-        if rows > n * R:
-            out[n * R:].zero_()                          # rows behind the last sequence belong to nobody
-    _chk(out, "seq_dist_bwd.dlogits")
-    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < n * R or out.shape[1] != V:
-        raise ValueError(f"seq_dist_bwd: out must be [>= {n * R}, {V}] with unit column stride")
-    if n == 0:
-        return out                                       # no sequence: nothing to write (an empty tensor has no address)
-    check(_L().gct_seq_dist_bwd(_p(logits2d), ld, V, R, int(row_shift), _p(prior_logits2d), ld_prior, _p(ys),
-                                ys.stride(0), _p(prefix_lens), int(pad_id), n, W, _p(g_entropy), _p(g_token_entropy),
-                                0 if g_token_entropy is None else g_token_entropy.stride(0), _p(g_kl), _p(g_token_kl),
-                                0 if g_token_kl is None else g_token_kl.stride(0), _p(out), out.stride(0), _st()),
-          "gct_seq_dist_bwd")
-    return out
+    _seq_vector("seq_dist_bwd", "g_entropy", g_entropy, n), _seq_vector("seq_dist_bwd", "g_kl", g_kl, n)
+    ld_ge = _seq_table("seq_dist_bwd", "g_token_entropy", g_token_entropy, n, W)
+    ld_gk = _seq_table("seq_dist_bwd", "g_token_kl", g_token_kl, n, W)
+    return _seq_dlogits("seq_dist_bwd", out, logits2d, ys, R, V, lambda dl: check(_L().gct_seq_dist_bwd(
+        _p(logits2d), ld, V, R, int(row_shift), _p(prior_logits2d), ld_prior, _p(ys), ys.stride(0), _p(prefix_lens),
+        int(pad_id), n, W, _p(g_entropy), _p(g_token_entropy), ld_ge, _p(g_kl), _p(g_token_kl), ld_gk, _p(dl),
+        dl.stride(0), _st()), "gct_seq_dist_bwd"))
 
 
 def _ppo_inputs(name, old_token_logp, advantage, n, W):
     """The checks seq_ppo / seq_ppo_bwd make on the sampling-time table and the advantages (None passes a null pointer:
     the library refuses): the row stride of old_token_logp."""
-    if old_token_logp is not None:
-        _chk(old_token_logp, f"{name}.old_token_logp")
-        if old_token_logp.shape != (n, W) or old_token_logp.stride(1) != 1:
-            raise ValueError(f"{name}: old_token_logp must be [{n}, {W}] with unit column stride")
-    if advantage is not None:
-        _chk(advantage, f"{name}.advantage")
-        if advantage.numel() != n or not advantage.is_contiguous():
-            raise ValueError(f"{name}: advantage must be a contiguous fp32 tensor of {n} entries")
-    return 0 if old_token_logp is None else old_token_logp.stride(0)
+    ld_old = _seq_table(name, "old_token_logp", old_token_logp, n, W)
+    _seq_vector(name, "advantage", advantage, n)
+    return ld_old
 
 
 def seq_ppo(logits2d, ys, old_token_logp, advantage, clip_lo, clip_hi, prefix_lens=None, pad_id=1, row_shift=0,
@@ -1381,30 +1350,12 @@ def seq_ppo_bwd(logits2d, ys, old_token_logp, advantage, clip_lo, clip_hi, prefi
     are not read), and on the rows of clipped tokens."""
     n, W, R, V, ld, _ = _seq_geometry("seq_ppo_bwd", logits2d, ys, rows_per_seq, V, prefix_lens)
     ld_old = _ppo_inputs("seq_ppo_bwd", old_token_logp, advantage, n, W)
-    if g_surrogate is not None:
-        _chk(g_surrogate, "seq_ppo_bwd.g_surrogate")
-        if g_surrogate.numel() != n or not g_surrogate.is_contiguous():
-            raise ValueError(f"seq_ppo_bwd: g_surrogate must be a contiguous fp32 tensor of {n} entries")
-    if g_token_surrogate is not None:
-        _chk(g_token_surrogate, "seq_ppo_bwd.g_token_surrogate")
-        if g_token_surrogate.shape != (n, W) or g_token_surrogate.stride(1) != 1:
-            raise ValueError(f"seq_ppo_bwd: g_token_surrogate must be [{n}, {W}] with unit column stride")
-    rows = max(n * R, 0 if logits2d is None else logits2d.shape[0])
-    if out is None:
-        out = torch.empty(rows, V, device=ys.device)
-        if rows > n * R:
-            out[n * R:].zero_()                          # rows behind the last sequence belong to nobody
-    _chk(out, "seq_ppo_bwd.dlogits")
-    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < n * R or out.shape[1] != V:
-        raise ValueError(f"seq_ppo_bwd: out must be [>= {n * R}, {V}] with unit column stride")
-    if n == 0:
-        return out                                       # no sequence: nothing to write (an empty tensor has no address)
-    check(_L().gct_seq_ppo_bwd(_p(logits2d), ld, V, R, int(row_shift), _p(ys), ys.stride(0), _p(prefix_lens),
-                               int(pad_id), n, W, _p(old_token_logp), ld_old, _p(advantage), float(clip_lo),
-                               float(clip_hi), _p(g_surrogate), _p(g_token_surrogate),
-                               0 if g_token_surrogate is None else g_token_surrogate.stride(0), _p(out), out.stride(0),
-                               _st()), "gct_seq_ppo_bwd")
-    return out
+    _seq_vector("seq_ppo_bwd", "g_surrogate", g_surrogate, n)
+    ld_g = _seq_table("seq_ppo_bwd", "g_token_surrogate", g_token_surrogate, n, W)
+    return _seq_dlogits("seq_ppo_bwd", out, logits2d, ys, R, V, lambda dl: check(_L().gct_seq_ppo_bwd(
+        _p(logits2d), ld, V, R, int(row_shift), _p(ys), ys.stride(0), _p(prefix_lens), int(pad_id), n, W,
+        _p(old_token_logp), ld_old, _p(advantage), float(clip_lo), float(clip_hi), _p(g_surrogate),
+        _p(g_token_surrogate), ld_g, _p(dl), dl.stride(0), _st()), "gct_seq_ppo_bwd"))
 
 
 def chosen_logp(logits2d, ys, pos_dev, out, pad_id, row_off=None, item=None, prefix_len=None):
