@@ -15,7 +15,11 @@ Deliberate deviations, none in the arithmetic:
   * `top_k` (the reference's -top_k) takes effect: the reference's per-model-type constructors never forward it, so there
     the flag is ignored.  Next to it, `top_p` (nucleus) and `temperature`; the rules are decode.sample_filter_reference,
     applied on the device between the softmax and the draw.  Greedy ignores all three (the top token is always kept);
-    beam search does not take them.
+    beam search does not take them;
+  * decode_algo="stochastic_beam" with beam_size=k (no counterpart in the reference) is stochastic beam search (Kool, van
+    Hoof and Welling 2019; decode.sbs_step_reference): `decode_unique` returns k DISTINCT molecules per latent, an exact
+    sample without replacement, with their log-probabilities; `decode` returns the first draw of each, which is
+    distributed exactly as a multinomial sample.  "beam"'s refusals apply; `decode_unique` itself works on any sampler.
 
 `sample_multiple_smiles` (scaffold models) is the reference's commented-out PscavaetfSampling.sample_multiple_smiles,
 one scaffold per row: the prefixes <sos> scaffold <sep> of different lengths are right-padded into ONE batch and decoded
@@ -66,6 +70,9 @@ from .mol_interpolation import Interpolation, interior_alphas, interp_plan, lerp
 from ..decode import (BEAM_ALPHA, KVDecoder, PolicyTerms, PpoTerms, SmilesGrammar, check_beam_size, check_sample_filter,
                       check_stream_model, check_stream_rows, generated_tokens, score_tokens, sequence_logp,
                       sequence_policy, sequence_ppo)
+
+
+BEAM_ALGOS = ("beam", "stochastic_beam")        # decode_algo values that decode k rows per sample in step (kv_src)
 
 
 class Scores(NamedTuple):
@@ -168,24 +175,25 @@ class Sampling:
                  temperature: float = 1.0, stream_rows: Optional[int] = None, with_logp: bool = False,
                  well_formed: bool = False):
         V = model.out.weight.shape[0]
-        if well_formed and decode_algo == "beam":
-            raise ValueError("well_formed is not supported with decode_algo='beam' (beam rows keep their history behind "
-                             "the ancestry map)")
+        if well_formed and decode_algo in BEAM_ALGOS:
+            raise ValueError(f"well_formed is not supported with decode_algo={decode_algo!r} (beam rows keep their history "
+                             "behind the ancestry map)")
         # constrained decoding: the grammar over the target vocabulary, passed to every decode
         self.grammar = SmilesGrammar(TRG.itos, TRG.stoi["<pad>"], TRG.stoi["<eos>"]) if well_formed else None
-        if with_logp and decode_algo == "beam":
-            raise ValueError("with_logp is not supported with decode_algo='beam': decode_beams returns the beams' "
-                             "scores, which are sums of log-probabilities already")
+        if with_logp and decode_algo in BEAM_ALGOS:
+            raise ValueError(f"with_logp is not supported with decode_algo={decode_algo!r}: decode_beams / decode_unique "
+                             "return the beams' scores, which are sums of log-probabilities already")
         self.with_logp = bool(with_logp)
         if stream_rows is not None:
-            if decode_algo == "beam":
-                raise ValueError("stream_rows is not supported with decode_algo='beam' (beam search keeps its rows in step)")
+            if decode_algo in BEAM_ALGOS:
+                raise ValueError(f"stream_rows is not supported with decode_algo={decode_algo!r} (beam search keeps its "
+                                 "rows in step)")
             check_stream_rows(stream_rows)
             check_stream_model(model, latent_dim)
         self.stream_rows = stream_rows
-        if check_sample_filter(top_k, top_p, temperature, V) and decode_algo == "beam":
-            raise ValueError("top_k / top_p / temperature are not supported with decode_algo='beam'")
-        if decode_algo == "beam":
+        if check_sample_filter(top_k, top_p, temperature, V) and decode_algo in BEAM_ALGOS:
+            raise ValueError(f"top_k / top_p / temperature are not supported with decode_algo={decode_algo!r}")
+        if decode_algo in BEAM_ALGOS:
             check_beam_size(beam_size, V)
         self.top_k, self.top_p, self.temperature = top_k, top_p, temperature
         self.beam_size, self.beam_alpha = beam_size, float(beam_alpha)
@@ -252,6 +260,13 @@ class Sampling:
         if return_rows and self.decode_algo == "beam":
             raise ValueError("return_rows is not supported with decode_algo='beam' (a beam row's history lies behind the "
                              "ancestry map; score the returned beams with score())")
+        if self.decode_algo == "stochastic_beam":        # the first draw of each sample: an exact ordinary sample
+            if return_rows:
+                raise ValueError("return_rows is not supported with decode_algo='stochastic_beam': "
+                                 "decode_unique(return_rows=True) returns the rows of all k draws")
+            if prefix_lens is not None:
+                raise ValueError("decode: beam search takes prefixes of one length (see sample_multiple_smiles)")
+            return self.decode_unique(zs, ys, src_mask, dconds).ys[:, 0]
         if self.decode_algo == "beam":
             if prefix_lens is not None:
                 raise ValueError("decode: beam search takes prefixes of one length (see sample_multiple_smiles)")
@@ -279,16 +294,20 @@ class Sampling:
 
     def _with_rows(self, res, zs, ys0, src_mask, dconds, prefix_lens):
         """decode's result with the DecodedRows of the call appended."""
-        ids = res[0] if self.with_logp else res
+        rows = self._decoded_rows(res[0] if self.with_logp else res, zs, ys0.size(1), src_mask, dconds, prefix_lens)
+        return res + (rows,) if self.with_logp else (res, rows)
+
+    def _decoded_rows(self, ids, zs, t0, src_mask, dconds, prefix_lens):
+        """The DecodedRows of decoded ids [n, L] (prefixes of width t0, or prefix_lens): token rows cut at each row's
+        first generated <eos>."""
         n, L = ids.shape
-        lens = (torch.full((n,), ys0.size(1), dtype=torch.long) if prefix_lens is None
+        lens = (torch.full((n,), t0, dtype=torch.long) if prefix_lens is None
                 else torch.as_tensor(prefix_lens).to("cpu", torch.long).view(-1))
         cols = torch.arange(L, device=ids.device).view(1, -1)
         is_eos = (ids == self.eos_id) & (cols >= lens.to(ids.device).view(-1, 1))
         first = torch.where(is_eos.any(1), is_eos.int().argmax(1), torch.full_like(is_eos[:, 0], L, dtype=torch.long))
         clean = torch.where(cols <= first.view(-1, 1), ids, torch.full_like(ids, self.pad_id))
-        rows = DecodedRows(zs, clean, src_mask, dconds, lens)
-        return res + (rows,) if self.with_logp else (res, rows)
+        return DecodedRows(zs, clean, src_mask, dconds, lens)
 
     def logp(self, zs, ys, src_mask, dconds=None, prefix_lens=None) -> Scores:
         """`score` with a gradient (decode.sequence_logp): the same arguments -- a DecodedRows unpacks into them -- and
@@ -374,6 +393,33 @@ class Sampling:
         return self.kv.generate_beam(ys, k, self.max_strlen, alpha=self.beam_alpha if alpha is None else alpha,
                                      use_graphs=self.use_graphs)
 
+    @torch.no_grad()
+    def decode_unique(self, zs, ys, src_mask, dconds=None, k=None, return_rows=False):
+        """Stochastic beam search (KVDecoder.generate_sbs): k DISTINCT molecules per row of zs, an exact sample without
+        replacement from the model's distribution for that latent, conditions and prefix.  Returns decode.SbsSamples
+        (ys [n, k, L], logp [n, k], gumbel [n, k], lengths [n, k]) on the sampler's device, draws in drawing order: the
+        first alone is an ordinary sample, and decode.sbs_importance_weights(logp, gumbel) weights all k into an unbiased
+        estimator.  k defaults to the constructor's beam_size.  Any decode_algo (the sampler's filters and stream_rows do
+        not apply: the draw is from the model's own distribution), but not well_formed=True samplers: ValueError.
+        return_rows=True: (SbsSamples, DecodedRows) -- the n*k rows in sample-major order (row s*k + i: draw i of sample
+        s), zs / src_mask / dconds repeated per draw, token rows cut at each row's <eos> as `decode` cuts them: what
+        `logp(*rows)`, Train/finetune.reinforce_step and ppo_update take.  self.seed advances once per call."""
+        if self.grammar is not None:
+            raise ValueError("decode_unique: beam search takes no grammar, and this sampler was built with well_formed=True")
+        k = self.beam_size if k is None else k
+        check_beam_size(k, self.model.out.weight.shape[0])
+        self.seed += 1
+        zs, ys, src_mask = zs.to(self.device), ys.to(self.device), src_mask.to(self.device)
+        dconds = None if dconds is None else dconds.to(self.device)
+        total = ys.size(1) + self.max_strlen
+        self.kv.start(zs, src_mask, dconds, max_total_len=min(200 - self.kv.off, total), beams=k)
+        out = self.kv.generate_sbs(ys, k, self.max_strlen, seed=self.seed, use_graphs=self.use_graphs)
+        if not return_rows:
+            return out
+        rep = lambda x: None if x is None else x.repeat_interleave(k, 0)       # noqa: E731
+        ids = out.ys.reshape(-1, out.ys.shape[2])
+        return out, self._decoded_rows(ids, rep(zs), ys.size(1), rep(src_mask), rep(dconds), None)
+
     # ---- molecule -> latent -> molecule ------------------------------------------------------
     def _endpoint_args(self, what, n, scaffolds, props):
         """The arguments the model type takes, checked: (scaffold list or None, raw property array [n, n_c] or None)."""
@@ -431,8 +477,8 @@ class Sampling:
         row's tokens and a non-empty string (syntax only -- a caller with rdkit passes its own).
         Returns an Interpolation; return_rows=True: (Interpolation, [DecodedRows of each round]).  ValueError with
         decode_algo="beam"."""
-        if self.decode_algo == "beam":
-            raise ValueError("interpolate_smiles is not supported with decode_algo='beam' (the retry ladder is one mixed "
+        if self.decode_algo in BEAM_ALGOS:
+            raise ValueError(f"interpolate_smiles is not supported with decode_algo={self.decode_algo!r} (the retry ladder is one mixed "
                              "batch of greedy / multinomial rows)")
         src0, src1 = list(src0), list(src1)
         P = len(src0)
@@ -495,8 +541,8 @@ class Sampling:
         own mask (scaffold types behind <sos> scaffold <sep>, property types with the same properties).  Returns
         (smiles, same): the decoded strings and, per molecule, whether the decoded tokens equal the input's token for
         token; return_rows=True appends the DecodedRows.  ValueError with decode_algo="beam"."""
-        if self.decode_algo == "beam":
-            raise ValueError("reconstruct_smiles is not supported with decode_algo='beam'")
+        if self.decode_algo in BEAM_ALGOS:
+            raise ValueError(f"reconstruct_smiles is not supported with decode_algo={self.decode_algo!r}")
         smiles_list = list(smiles_list)
         sca, props = self._endpoint_args("reconstruct_smiles", len(smiles_list), scaffold_list, props)
         mu, _, src_mask = self._encode_endpoints(smiles_list, sca, props, transform)
@@ -533,8 +579,8 @@ class Sampling:
         """One scaffold per row (sample_multiple_smiles): a single mixed-prefix decode, or for beam search one decode
         per prefix length; (smiles, toklen, toklen_gen) in input order (with_logp: and logp [n]; return_rows: and the
         DecodedRows)."""
-        if return_rows and self.decode_algo == "beam":
-            raise ValueError("return_rows is not supported with decode_algo='beam'")
+        if return_rows and self.decode_algo in BEAM_ALGOS:
+            raise ValueError(f"return_rows is not supported with decode_algo={self.decode_algo!r}")
         scaffolds = list(scaffolds)
         if not scaffolds:
             raise ValueError("sample_multiple_smiles: no scaffolds")
@@ -543,7 +589,7 @@ class Sampling:
                                                  self.sample_z)
         n = len(scaffolds)
         tail = ()
-        if self.decode_algo == "beam":
+        if self.decode_algo in BEAM_ALGOS:
             gens = [None] * n
             for t0, idx in group_by_length(lens):
                 outs = self.decode(zs[idx], ys0[idx, :t0], src_mask[idx], None if dconds is None else dconds[idx])

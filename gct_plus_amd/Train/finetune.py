@@ -24,9 +24,17 @@ trust region (decode.sequence_ppo -> gct_seq_ppo / gct_seq_ppo_bwd; `advantages`
 
     history = ppo_update(sampler, optimizer, out[-1], reward, epochs=4, clip=0.2)
 
+A sharpened policy fills a sampled batch with copies of a few strings.  `sampler.decode_unique(..., return_rows=True)`
+draws k DISTINCT molecules per latent instead (stochastic beam search), and decode.sbs_importance_weights turns them into
+an unbiased estimate of the ordinary objective -- a loss weighted that way, every row scored once:
+
+    sbs, rows = sampler.decode_unique(zs, ys0, src_mask, dconds, k=16, return_rows=True)
+    w, _ = sbs_importance_weights(sbs.logp, sbs.gumbel)         # [n, k]; reward [n * k], sample-major like the rows
+    loss = -(w.view(-1) * (reward - reward.mean()) * sampler.logp(*rows).logp).sum() / w.shape[0]
+
 Not covered: FlatDataParallel fine-tuning, value networks / GAE (the advantage is per molecule),
-sequence-level ratios (functions of logp and the old logp in torch), beam rows, per-step entropy during generate, a
-gradient into the prior or into old_token_logp."""
+sequence-level ratios (functions of logp and the old logp in torch), rows of deterministic beam search, per-step entropy
+during generate, a gradient into the prior or into old_token_logp."""
 import copy
 
 import torch

@@ -9,6 +9,8 @@
 //   gct_stream_refill : continuous batching -- rows that finished hand out their tokens and take the next pool item
 //   gct_attn_decode_beam / gct_beam_select : the same two for beam search, with the self-attention caches
 //                      shared by ancestry through a per-row map (kv_src) instead of copied
+//   gct_beam_select_gumbel : stochastic beam search -- the other instantiation of gct_beam_select's kernel template,
+//                      ordering the candidates by Gumbel-perturbed log-probabilities conditioned on their parent's
 //   gct_attn_decode_z / gct_decode_embed / gct_decode_advance : cross-attention over the latent rows, one position's
 //                      embedding, the device counter
 // All are small and HBM/latency-bound; they exist so a whole decode step is a fixed kernel chain with no host round
@@ -777,37 +779,90 @@ __device__ __forceinline__ bool beam_better(float av, int ai, float bv, int bi) 
   return av > bv || (av == bv && ai < bi);
 }
 
-// One thread's KM best candidates, sorted; the new one enters at the tail and bubbles up (constant indices: registers).
-template <int KM>
-__device__ __forceinline__ void beam_insert(float (&cv)[KM], int (&ci)[KM], float v, int i) {
-  if (!beam_better(v, i, cv[KM - 1], ci[KM - 1])) return;
-  cv[KM - 1] = v;
-  ci[KM - 1] = i;
+// One thread's KM best candidates, sorted by their ordering value v; PHI: each carries its score phi beside it.
+template <int KM, bool PHI>
+struct BeamList {
+  float v[KM];
+  int i[KM];
+  float phi[PHI ? KM : 1];
+};
+
+// The new candidate enters at the tail and bubbles up (constant indices: registers).
+template <int KM, bool PHI>
+__device__ __forceinline__ void beam_insert(BeamList<KM, PHI>& L, float v, int i, float phi) {
+  if (!beam_better(v, i, L.v[KM - 1], L.i[KM - 1])) return;
+  L.v[KM - 1] = v;
+  L.i[KM - 1] = i;
+  if constexpr (PHI) L.phi[KM - 1] = phi;
 #pragma unroll
   for (int t = KM - 1; t > 0; --t) {
-    if (beam_better(cv[t], ci[t], cv[t - 1], ci[t - 1])) {
-      const float tv = cv[t]; cv[t] = cv[t - 1]; cv[t - 1] = tv;
-      const int ti = ci[t]; ci[t] = ci[t - 1]; ci[t - 1] = ti;
+    if (beam_better(L.v[t], L.i[t], L.v[t - 1], L.i[t - 1])) {
+      const float tv = L.v[t]; L.v[t] = L.v[t - 1]; L.v[t - 1] = tv;
+      const int ti = L.i[t]; L.i[t] = L.i[t - 1]; L.i[t - 1] = ti;
+      if constexpr (PHI) { const float tp = L.phi[t]; L.phi[t] = L.phi[t - 1]; L.phi[t - 1] = tp; }
     }
   }
 }
 
-// One workgroup per sample s, whose K beams are rows s*K .. s*K+K-1 (semantics: decode.py beam_step_reference).
+// ------------------------------------------------------------------------ stochastic beam search (gct_beam_select_gumbel)
+// What the stochastic instantiation of beam_select_kernel adds (include/gctplus_hip.h states the rules).
+struct BeamGumbel {
+  float* gumbels;             // [n*K] in place
+  GctRng rng;                 // key of (seed, GCT_SBS_SITE)
+  const uint64_t* seed_dev;   // nullable: replaces the by-value seed
+  const float* noise_in;      // nullable [n*K][V]: these variates instead of the draw
+  float* noise_out;           // nullable [n*K][V]: the variates used for live beams
+};
+
+// The standard Gumbel variate of (row, token position p, token c): word c & 3 of the call that serves tokens 4 (c >> 2) ..
+// 4 (c >> 2) + 3; u = (float32(x >> 9) + 0.5f) * 2^-23 is exact in fp32 and lies strictly inside (0, 1).
+__device__ __forceinline__ float sbs_noise(GctRng rng, uint32_t row, uint32_t p, int c, const float* noise_row) {
+  if (noise_row) return noise_row[c];
+  const uint32_t x = gct_pick(gct_philox(rng, row, p, (uint32_t)c >> 2, GCT_SBS_C3), c & 3);
+  const float u = ((float)(x >> 9) + 0.5f) * (1.0f / 8388608.0f);
+  return -logf(-logf(u));
+}
+
+// phi = score_b + logp_b(c) and the perturbed value g = phi + noise: THE one evaluation, used by the pass that finds
+// Z_b = max g and by the pass that conditions every g on it, so that both see the same bits (additions only, and
+// contraction is off in any case: nothing here can be fused differently at the two sites).
+__device__ __forceinline__ float sbs_perturbed(float sb, float x, float m, float ls, float noise, float& phi) {
+#pragma clang fp contract(off)
+  phi = sb + ((x - m) - ls);
+  return phi + noise;
+}
+
+// g~ = -log(exp(-G) - exp(-Z) + exp(-g)) in the stable form of Kool et al. 2019, appendix B.3.  d is clamped: a
+// positive d would make log1mexp a NaN, and a NaN poisons beam_better.
+__device__ __forceinline__ float sbs_child_gumbel(float G, float Z, float g) {
+  const float d = fminf(g - Z, 0.f);
+  const float l = d > -0.69314718f ? logf(-expm1f(d)) : log1pf(-expf(d));      // log(1 - exp(d))
+  const float w = (G - g) + l;
+  return (G - fmaxf(w, 0.f)) - log1pf(expf(-fabsf(w)));
+}
+
+// One workgroup per sample s, whose K beams are rows s*K .. s*K+K-1 (semantics: decode.py beam_step_reference, and
+// sbs_step_reference for GUMBEL).
 //   1. beam state and the group's kv_src rows -> LDS;
 //   2. per live beam (one wave each): m = max logit, ls = log sum exp(x - m); a candidate scores
 //      score_b + ((x - m) - ls); a finished beam offers only (score_b, token pad); beams at -inf offer nothing;
-//   3. each thread keeps its KM best candidates, then K rounds of a workgroup argmax pop the winners in order;
+//      GUMBEL: the same wave then finds Z_b = max g and its first argmax v*_b over the offered tokens;
+//   3. each thread keeps its KM best candidates, then K rounds of a workgroup argmax pop the winners in order; the
+//      ordering value is the score, or with GUMBEL the conditioned Gumbel value g~ (v*_b: G_b itself, by its index; a
+//      finished beam: G_b) with the score carried beside it;
 //   4. child c of parent b: score, finished = fin_b || token == eos, length = len_b + !fin_b, the token at
 //      ys[row][p] / valid[row][valid_off + p], and the parent's kv_src row with entry valid_off + p = the child's row.
 // p = *pos_dev + 1 (device counter, as select_token_kernel): no host round trip, one captured graph for every step.
-template <int KM>
+template <int KM, bool GUMBEL>
 __global__ __launch_bounds__(256) void beam_select_kernel(
     const float* __restrict__ logits, int V, int K, float* __restrict__ scores, uint8_t* __restrict__ finished,
     int32_t* __restrict__ lengths, int32_t* __restrict__ parent_out, int64_t* __restrict__ ys, int64_t ld_ys,
     uint8_t* __restrict__ valid, int64_t valid_sb, int valid_off, int32_t* __restrict__ kv_src, int64_t ld_src, int T,
-    uint8_t* __restrict__ done, const int32_t* __restrict__ pos_dev, int64_t pad_id, int64_t eos_id) {
+    uint8_t* __restrict__ done, const int32_t* __restrict__ pos_dev, int64_t pad_id, int64_t eos_id, BeamGumbel sa) {
+  constexpr int KG = GUMBEL ? KM : 1;
   __shared__ float s_score[KM], s_m[KM], s_ls[KM], s_winv[KM], s_wv[2][4];
-  __shared__ int32_t s_len[KM], s_win[KM], s_par[KM], s_wi[2][4];
+  __shared__ float s_gum[KG], s_z[KG], s_winp[KG];
+  __shared__ int32_t s_len[KM], s_win[KM], s_par[KM], s_wi[2][4], s_vstar[KG];
   __shared__ uint8_t s_fin[KM], s_cfin[KM];
   __shared__ int32_t s_map[KM][256];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -815,10 +870,13 @@ __global__ __launch_bounds__(256) void beam_select_kernel(
   const int slot = valid_off + p;
   if (p < 0 || slot >= T) return;                          // no room (the host sizes the caches)
   const int64_t row0 = (int64_t)blockIdx.x * K;
+  if constexpr (GUMBEL)
+    if (sa.seed_dev) sa.rng = gct_rng_make(*sa.seed_dev, GCT_SBS_SITE);
   if (tid < K) {
     s_score[tid] = scores[row0 + tid];
     s_fin[tid] = finished[row0 + tid];
     s_len[tid] = lengths[row0 + tid];
+    if constexpr (GUMBEL) s_gum[tid] = sa.gumbels[row0 + tid];
   }
   for (int i = tid; i < K * T; i += 256) {
     const int b = i / T, j = i - b * T;
@@ -834,29 +892,60 @@ __global__ __launch_bounds__(256) void beam_select_kernel(
       s_m[b] = m;
       s_ls[b] = logf(se);
     }
+    if constexpr (GUMBEL) {                                 // Z_b and v*_b over the offered tokens (phi > -inf)
+      const float sb = s_score[b], ls = logf(se);           // (se is the same on every lane: the bits of s_ls[b])
+      const float* nr = sa.noise_in ? sa.noise_in + (row0 + b) * V : nullptr;
+      float zv = -INFINITY;
+      int zi = INT_MAX;
+      for (int c = lane; c < V; c += 64) {                  // ascending per lane: > keeps the first
+        const float nz = sbs_noise(sa.rng, (uint32_t)(row0 + b), (uint32_t)p, c, nr);
+        if (sa.noise_out) sa.noise_out[(row0 + b) * V + c] = nz;
+        float phi;
+        const float g = sbs_perturbed(sb, lr[c], m, ls, nz, phi);
+        if (phi > -INFINITY && (g > zv || zi == INT_MAX)) { zv = g; zi = c; }
+      }
+      gct_wave_argmax(zv, zi);
+      if (lane == 0) {
+        s_z[b] = zv;
+        s_vstar[b] = zi;
+      }
+    }
   }
   __syncthreads();
-  float cv[KM];
-  int ci[KM];
+  BeamList<KM, GUMBEL> L;
 #pragma unroll
   for (int t = 0; t < KM; ++t) {
-    cv[t] = -INFINITY;
-    ci[t] = INT_MAX;
+    L.v[t] = -INFINITY;
+    L.i[t] = INT_MAX;
+    if constexpr (GUMBEL) L.phi[t] = -INFINITY;
   }
   for (int b = 0; b < K; ++b) {                             // ascending flat index per thread
     const float sb = s_score[b];
     if (sb == -INFINITY) continue;
     if (s_fin[b]) {
-      if (tid == 0) beam_insert<KM>(cv, ci, sb, b * V + (int)pad_id);
+      if (tid == 0) beam_insert<KM, GUMBEL>(L, GUMBEL ? s_gum[GUMBEL ? b : 0] : sb, b * V + (int)pad_id, sb);
       continue;
     }
     const float m = s_m[b], ls = s_ls[b];
     const float* lr = logits + (row0 + b) * V;
-    for (int c = tid; c < V; c += 256) beam_insert<KM>(cv, ci, sb + ((lr[c] - m) - ls), b * V + c);
+    if constexpr (GUMBEL) {
+      const float G = s_gum[b], Z = s_z[b];
+      const int vs = s_vstar[b];
+      if (vs == INT_MAX) continue;                          // every token at -inf: nothing offered
+      const float* nr = sa.noise_in ? sa.noise_in + (row0 + b) * V : nullptr;
+      for (int c = tid; c < V; c += 256) {
+        float phi;
+        const float g = sbs_perturbed(sb, lr[c], m, ls, sbs_noise(sa.rng, (uint32_t)(row0 + b), (uint32_t)p, c, nr), phi);
+        if (!(phi > -INFINITY)) continue;                   // not offered
+        beam_insert<KM, true>(L, c == vs ? G : sbs_child_gumbel(G, Z, g), b * V + c, phi);
+      }
+    } else {
+      for (int c = tid; c < V; c += 256) beam_insert<KM, false>(L, sb + ((lr[c] - m) - ls), b * V + c, 0.f);
+    }
   }
   for (int r = 0; r < K; ++r) {                             // K rounds: workgroup argmax of the threads' heads
-    float bv = cv[0];
-    int bi = ci[0];
+    float bv = L.v[0];
+    int bi = L.i[0];
     gct_wave_argmax(bv, bi);                                // beam_better's order
     if (lane == 0) {
       s_wv[r & 1][wave] = bv;
@@ -868,14 +957,16 @@ __global__ __launch_bounds__(256) void beam_select_kernel(
 #pragma unroll
     for (int w = 1; w < 4; ++w)
       if (beam_better(s_wv[r & 1][w], s_wi[r & 1][w], wv, wi)) { wv = s_wv[r & 1][w]; wi = s_wi[r & 1][w]; }
-    if (ci[0] == wi && wi != INT_MAX) {                     // the owner pops its head
+    if (L.i[0] == wi && wi != INT_MAX) {                    // the owner pops its head
+      if constexpr (GUMBEL) s_winp[r] = L.phi[0];
 #pragma unroll
       for (int t = 0; t < KM - 1; ++t) {
-        cv[t] = cv[t + 1];
-        ci[t] = ci[t + 1];
+        L.v[t] = L.v[t + 1];
+        L.i[t] = L.i[t + 1];
+        if constexpr (GUMBEL) L.phi[t] = L.phi[t + 1];
       }
-      cv[KM - 1] = -INFINITY;
-      ci[KM - 1] = INT_MAX;
+      L.v[KM - 1] = -INFINITY;
+      L.i[KM - 1] = INT_MAX;
     }
     if (tid == 0) {
       s_win[r] = wi;
@@ -887,14 +978,15 @@ __global__ __launch_bounds__(256) void beam_select_kernel(
     const int f = s_win[tid];
     const int64_t row = row0 + tid;
     int b, tok;
-    float sc;
-    if (f == INT_MAX) {                                     // fewer than K candidates (cannot happen with K <= V)
-      b = tid; tok = (int)pad_id; sc = -INFINITY;
+    float sc, gv;
+    if (f == INT_MAX) {                                     // fewer than K candidates (beam search: cannot happen with K <= V)
+      b = tid; tok = (int)pad_id; sc = gv = -INFINITY;
     } else {
-      b = f / V; tok = f - b * V; sc = s_winv[tid];
+      b = f / V; tok = f - b * V; gv = s_winv[tid]; sc = GUMBEL ? s_winp[GUMBEL ? tid : 0] : gv;
     }
     const bool fin = f == INT_MAX || s_fin[b] || tok == eos_id;
     scores[row] = sc;
+    if constexpr (GUMBEL) sa.gumbels[row] = gv;
     finished[row] = fin ? 1 : 0;
     lengths[row] = s_len[b] + (s_fin[b] ? 0 : 1);
     if (parent_out) parent_out[row] = b;
@@ -1111,25 +1203,48 @@ extern "C" int gct_attn_decode_beam(const float* q, int64_t ldq, float* k, float
                             pos, cache_off, knew, vnew, ldn, nullptr, kv_src, ld_src, nullptr, stream);
 }
 
+// The one launch of beam_select_kernel: gct_beam_select's checks, which gct_beam_select_gumbel shares.
+template <bool GUMBEL>
+static int launch_beam_select(const char* name, const float* logits, int V, int n, int k, float* scores, uint8_t* finished,
+                              int32_t* lengths, int32_t* parent, int64_t* ys, int64_t ld_ys, uint8_t* valid,
+                              int64_t valid_sb, int valid_off, int32_t* kv_src, int64_t ld_src, int T, uint8_t* done,
+                              const int32_t* pos_dev, int64_t pad_id, int64_t eos_id, const BeamGumbel& sa, void* stream) {
+  GCT_CHECK_ARG(logits && scores && finished && lengths && ys && valid && kv_src && done && pos_dev && n >= 0 &&
+                    (!GUMBEL || sa.gumbels),
+                "%s: bad args", name);
+  GCT_CHECK_ARG(k >= 1 && k <= GCT_BEAM_MAX_K && V >= k && V <= GCT_BEAM_MAX_VOCAB,
+                "%s: beam size %d / vocabulary %d unsupported", name, k, V);
+  GCT_CHECK_ARG(T > 0 && T <= 256 && valid_off >= 0 && valid_off < T && ld_src >= T && valid_sb >= T &&
+                    ld_ys >= T - valid_off,
+                "%s: cache rows %d / map %lld / valid %lld / ys %lld", name, T, (long long)ld_src,
+                (long long)valid_sb, (long long)ld_ys);
+  GCT_CHECK_ARG(pad_id >= 0 && pad_id < V, "%s: pad id %lld outside the vocabulary", name, (long long)pad_id);
+  if (n == 0) return GCT_OK;
+  with_int<4, 8, 16>(k <= 4 ? 4 : (k <= 8 ? 8 : 16), [&](auto KM) {
+    hipLaunchKernelGGL((beam_select_kernel<KM, GUMBEL>), dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, logits, V,
+                       k, scores, finished, lengths, parent, ys, ld_ys, valid, valid_sb, valid_off, kv_src, ld_src, T,
+                       done, pos_dev, pad_id, eos_id, sa);
+  });
+  GCT_LAUNCH_CHECK(name);
+  return GCT_OK;
+}
+
 extern "C" int gct_beam_select(const float* logits, int V, int n, int k, float* scores, uint8_t* finished,
                                int32_t* lengths, int32_t* parent, int64_t* ys, int64_t ld_ys, uint8_t* valid,
                                int64_t valid_sb, int valid_off, int32_t* kv_src, int64_t ld_src, int T, uint8_t* done,
                                const int32_t* pos_dev, int64_t pad_id, int64_t eos_id, void* stream) {
-  GCT_CHECK_ARG(logits && scores && finished && lengths && ys && valid && kv_src && done && pos_dev && n >= 0,
-                "beam_select: bad args");
-  GCT_CHECK_ARG(k >= 1 && k <= GCT_BEAM_MAX_K && V >= k && V <= GCT_BEAM_MAX_VOCAB,
-                "beam_select: beam size %d / vocabulary %d unsupported", k, V);
-  GCT_CHECK_ARG(T > 0 && T <= 256 && valid_off >= 0 && valid_off < T && ld_src >= T && valid_sb >= T &&
-                    ld_ys >= T - valid_off,
-                "beam_select: cache rows %d / map %lld / valid %lld / ys %lld", T, (long long)ld_src,
-                (long long)valid_sb, (long long)ld_ys);
-  GCT_CHECK_ARG(pad_id >= 0 && pad_id < V, "beam_select: pad id %lld outside the vocabulary", (long long)pad_id);
-  if (n == 0) return GCT_OK;
-  with_int<4, 8, 16>(k <= 4 ? 4 : (k <= 8 ? 8 : 16), [&](auto KM) {
-    hipLaunchKernelGGL(beam_select_kernel<KM>, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, logits, V, k, scores,
-                       finished, lengths, parent, ys, ld_ys, valid, valid_sb, valid_off, kv_src, ld_src, T, done, pos_dev,
-                       pad_id, eos_id);
-  });
-  GCT_LAUNCH_CHECK("beam_select");
-  return GCT_OK;
+  return launch_beam_select<false>("beam_select", logits, V, n, k, scores, finished, lengths, parent, ys, ld_ys, valid,
+                                   valid_sb, valid_off, kv_src, ld_src, T, done, pos_dev, pad_id, eos_id, BeamGumbel{},
+                                   stream);
+}
+
+extern "C" int gct_beam_select_gumbel(const float* logits, int V, int n, int k, float* scores, uint8_t* finished,
+                                      int32_t* lengths, int32_t* parent, int64_t* ys, int64_t ld_ys, uint8_t* valid,
+                                      int64_t valid_sb, int valid_off, int32_t* kv_src, int64_t ld_src, int T,
+                                      uint8_t* done, const int32_t* pos_dev, int64_t pad_id, int64_t eos_id,
+                                      float* gumbels, uint64_t seed, const uint64_t* seed_dev, const float* noise_in,
+                                      float* noise_out, void* stream) {
+  const BeamGumbel sa{gumbels, gct_rng_make(seed, GCT_SBS_SITE), seed_dev, noise_in, noise_out};
+  return launch_beam_select<true>("beam_select_gumbel", logits, V, n, k, scores, finished, lengths, parent, ys, ld_ys,
+                                  valid, valid_sb, valid_off, kv_src, ld_src, T, done, pos_dev, pad_id, eos_id, sa, stream);
 }

@@ -28,6 +28,12 @@ caches, ys and valid stay PHYSICAL slots, each written once by the row that owns
 says where beam r's logical position j lives (row kv_src[r, j]): a selection copies the parent's map row instead of the
 parent's caches (gct_attn_decode_beam reads through it).  Final ids: token t of beam b is ys[kv_src[b, off + t], t].
 
+Stochastic beam search (`start(..., beams=k)` + `generate_sbs`; Kool, van Hoof and Welling 2019): the same unit with
+another selection, gct_beam_select_gumbel, and one more float per row (`bgumbel`).  The rules are stated once, in
+`sbs_step_reference`: beam search over Gumbel-perturbed log-probabilities, each child's Gumbel value conditioned on its
+parent's.  The k beams are k DISTINCT sequences, an exact sample without replacement from the model's distribution; the
+first is an ordinary sample; `sbs_importance_weights` turns them into an unbiased estimator.
+
 Mixed prefix lengths (`generate(..., prefix_lens=)`, e.g. one batch of many scaffolds): row r's prefix is ys0[r, :t0_r],
 right-padded to t0_max.  The device counter stays shared (the token index of the longest prefix) and row r reads it
 through its offset row_off[r] = t0_max - t0_r (gct_decode_embed / gct_attn_decode / gct_select_token), so each row keeps
@@ -97,6 +103,7 @@ REPLAY_SLOW_FACTOR = 1.3
 # beam search: length penalty exponent of the final ranking score / length**alpha (reference generate_mols.py:182-185)
 BEAM_ALPHA = 0.7
 BEAM = "beam"                                       # StepPlan.select: the beam step (gct_beam_select)
+SBEAM = "sbeam"                                     # StepPlan.select: the stochastic beam step (gct_beam_select_gumbel)
 FILTERED = "filtered"                               # StepPlan.select: the filtered multinomial draw
 UNIFORM, MIXED, STREAM = "uniform", "mixed", "stream"      # StepPlan.layout
 LOGP = "logp"                                       # graph key suffix of a step unit that records log-probabilities
@@ -109,14 +116,14 @@ TOP_K_FLOOR = 1e-6                                  # weight of a token outside 
 class StepPlan:
     """What one step unit is -- the decode step plus the selection, the unit a graph captures.  Each generate call
     builds one and passes it down; KVDecoder keeps no per-call mode of its own.
-      select   0 greedy, 1 multinomial, FILTERED (the multinomial draw through self.filt) or BEAM (gct_beam_select, the
-               self-attention through the ancestry map kv_src);
+      select   0 greedy, 1 multinomial, FILTERED (the multinomial draw through self.filt), BEAM (gct_beam_select, the
+               self-attention through the ancestry map kv_src) or SBEAM (the same unit with gct_beam_select_gumbel);
       layout   UNIFORM: every row at the shared position.  MIXED: the kernels get row_off.  STREAM: row_off plus the
                rows' item and prefix_len, and the unit ends with the refill (KVDecoder._rows is the row view);
       grammar  gct_grammar_mask runs in front of the selection;
       logp     gct_chosen_logp runs behind it.
     ValueError for what the unit cannot do: beam rows keep their history behind kv_src and their scores are
-    log-probabilities already, so BEAM goes with UNIFORM and neither grammar nor logp."""
+    log-probabilities already, so BEAM and SBEAM go with UNIFORM and neither grammar nor logp."""
     select: object = 0
     layout: str = UNIFORM
     grammar: bool = False
@@ -124,15 +131,17 @@ class StepPlan:
 
     def __post_init__(self):
         select, layout, grammar, logp = dataclasses.astuple(self)
-        if select not in (0, 1, FILTERED, BEAM) or layout not in (UNIFORM, MIXED, STREAM):
+        if select not in (0, 1, FILTERED, BEAM, SBEAM) or layout not in (UNIFORM, MIXED, STREAM):
             raise ValueError(f"no step unit selects {select!r} over {layout!r} rows")
         if select == BEAM and (layout != UNIFORM or grammar or logp):
             raise ValueError("the beam step takes uniform rows, no grammar and no log-probabilities")
+        if select == SBEAM and (layout != UNIFORM or grammar or logp):
+            raise ValueError("the stochastic beam step takes uniform rows, no grammar and no log-probabilities")
 
     @functools.cached_property
     def key(self):
-        """THE statement of the graph key (KVDecoder.graphs; bench.py, the tools and the tests read it): "beam"; select
-        alone for plain uniform rows; (select, layout) for another layout; and with a grammar and / or log-probabilities
+        """THE statement of the graph key (KVDecoder.graphs; bench.py, the tools and the tests read it): "beam"; "sbeam"
+        (both are `select` alone: uniform rows are the only layout they have); select alone for plain uniform rows; (select, layout) for another layout; and with a grammar and / or log-probabilities
         (select, layout[, GRAMMAR][, LOGP]), uniform spelled out.  A stream unit has k[1] == STREAM, logp k[-1] == LOGP."""
         select, layout, grammar, logp = dataclasses.astuple(self)
         if select == BEAM:
@@ -1131,6 +1140,120 @@ def beam_finalize(ys, scores, lengths, t0, alpha=BEAM_ALPHA):
     return ys[:, :, :t0 + int(lengths.max())].contiguous(), scores.gather(1, order), lengths
 
 
+# ------------------------------------------------------------------------------ stochastic beam search semantics
+class SbsSamples(NamedTuple):
+    """What a stochastic beam decode returns: ys int64 [n, k, L] (prefix, tokens, pad after each beam's end), logp
+    [n, k] fp32 = log p(beam's tokens | latent, conditions, prefix), gumbel [n, k] fp32 the perturbed log-probabilities
+    the beams were drawn by, lengths [n, k] int64 generated tokens (<eos> included).  The k beams of a sample are
+    distinct and in drawing order (descending gumbel): beam 0 alone is an ordinary sample of the model."""
+    ys: torch.Tensor
+    logp: torch.Tensor
+    gumbel: torch.Tensor
+    lengths: torch.Tensor
+
+
+def sbs_init(n, k, device=None, root=None):
+    """State after the prefill: (scores, gumbels, finished, lengths), scores and gumbels [n, k] = [0, -inf, ...] (the
+    first expansion uses beam 0 only: the root of the tree), the rest as in beam_init.
+    root ([n], optional): the root's Gumbel value, gumbels[:, 0].  WHICH sequences are drawn, and in which order, does
+    not depend on it (the order of an exponential race is independent of its first arrival time), so 0 samples
+    correctly; but every other Gumbel value is conditioned on it, and sbs_importance_weights is unbiased only when the
+    root is a Gumbel(0) variate itself (sbs_root_gumbels; with the root fixed at 0 the toy model of tests/test_sbs_host.py
+    gives E[sum w] = 0.970 instead of 1).  generate_sbs draws it."""
+    scores, finished, lengths = beam_init(n, k, device)
+    gumbels = scores.clone()
+    if root is not None:
+        gumbels[:, 0] = root.to(gumbels)
+    return scores, gumbels, finished, lengths
+
+
+def sbs_root_gumbels(n, seed, device=None):
+    """The root's Gumbel(0) variate of each of n samples under `seed`, fp32 [n]: -log(-log(u)) of torch's CPU generator
+    seeded with seed (u in float64, clamped inside (0, 1)); sample s's value does not depend on n."""
+    u = torch.rand(n, generator=torch.Generator().manual_seed(int(seed) & 0x7FFFFFFFFFFFFFFF), dtype=torch.float64)
+    return (-torch.log(-torch.log(u.clamp(1e-300, 1.0 - 2.0 ** -53)))).float().to(device)
+
+
+def log1mexp(d):
+    """log(1 - exp(d)) for d <= 0: log(-expm1(d)) above -ln 2, log1p(-exp(d)) below (Maechler 2012)."""
+    return torch.where(d > -math.log(2.0), torch.log(-torch.expm1(d)), torch.log1p(-torch.exp(d)))
+
+
+def sbs_candidates(scores, gumbels, finished, logp, noise, k, pad_id):
+    """(value, phi), each [n, k*V] at flat index beam * V + token: the candidate's conditioned Gumbel value g~ (-inf: not
+    offered) and its score; see sbs_step_reference.  Computed in the promoted dtype of the inputs."""
+    n, V = scores.shape[0], logp.shape[-1]
+    dt = functools.reduce(torch.promote_types, (gumbels.dtype, logp.dtype, noise.dtype), scores.dtype)
+    sc, G = scores.to(dt).unsqueeze(-1), gumbels.to(dt).unsqueeze(-1)
+    at = sc > -math.inf                                          # a beam at -inf offers nothing
+    live = at & ~finished.unsqueeze(-1)
+    phi = sc + logp.reshape(n, k, V).to(dt)
+    offered = live & (phi > -math.inf)
+    zero, ninf = torch.zeros((), dtype=dt, device=phi.device), torch.full((), -math.inf, dtype=dt, device=phi.device)
+    g = torch.where(offered, phi + noise.reshape(n, k, V).to(dt), ninf)
+    Z = g.max(-1, keepdim=True).values
+    tok = torch.arange(V, device=phi.device).expand_as(g)
+    vstar = torch.where((g == Z) & offered, tok, V).min(-1, keepdim=True).values       # FIRST argmax; V: nothing offered
+    gs, Zs, Gs = torch.where(offered, g, zero), torch.where(Z > -math.inf, Z, zero), torch.where(at, G, zero)
+    w = Gs - gs + log1mexp((gs - Zs).clamp(max=0.0))
+    val = Gs - w.clamp(min=0.0) - torch.log1p(torch.exp(-w.abs()))
+    val = torch.where(tok == vstar, Gs.expand_as(val), val)      # by index, exactly
+    val = torch.where(offered, val, ninf)
+    frozen = at & finished.unsqueeze(-1) & (tok == pad_id)       # a finished beam: itself, once
+    val = torch.where(frozen, G.expand_as(val), val)
+    phi = torch.where(frozen, sc.expand_as(phi), phi)
+    return val.reshape(n, k * V), phi.reshape(n, k * V)
+
+
+def sbs_step_reference(scores, gumbels, finished, lengths, logp, noise, k, pad_id, eos_id):
+    """One step of stochastic beam search (Kool, van Hoof and Welling 2019), THE statement of the rules
+    (gct_beam_select_gumbel implements them on the device).  scores / gumbels [n, k] (log-probability and Gumbel value
+    of each beam), finished [n, k] bool, lengths [n, k] int, logp [n*k, V] (beam_log_softmax of the step's logits),
+    noise [n*k, V] standard Gumbel variates.
+      * a live beam b with finite scores[b] offers every token v with finite phi_bv = scores[b] + logp_b(v); its
+        perturbed value is g_bv = phi_bv + noise_bv; Z_b = max_v g_bv and v*_b is its first argmax;
+      * the candidate's value is g~_bv = -log(exp(-G_b) - exp(-Z_b) + exp(-g_bv)), G_b = gumbels[b] -- the g_bv
+        conditioned on their maximum being G_b -- evaluated as d = min(g - Z, 0), l = log1mexp(d), w = G - g + l,
+        g~ = G - max(w, 0) - log1p(exp(-|w|)); token v*_b gets g~ = G_b exactly, by its index;
+      * a token with phi = -inf is not offered; a finished beam offers itself once, token pad_id, score and Gumbel value
+        unchanged; a beam at -inf offers nothing;
+      * the k candidates of largest g~ become the children in that order, ties to the lower flat index b*V + token;
+      * child: scores = phi, gumbels = g~, finished and lengths by beam_step_reference's rule.  A slot c that no candidate
+        is left for (fewer than k offered) becomes a finished beam at -inf: parent c, token pad_id.
+    Returns (parent [n, k], token [n, k], scores, gumbels, finished, lengths) of the children, in drawing order."""
+    V = logp.shape[-1]
+    val, phi = sbs_candidates(scores, gumbels, finished, logp, noise, k, pad_id)
+    order = torch.sort(val, dim=1, descending=True, stable=True).indices[:, :k]
+    gum = val.gather(1, order)
+    empty = gum == -math.inf
+    slot = torch.arange(k, device=order.device).expand_as(order)
+    parent = torch.where(empty, slot, order // V)
+    token = torch.where(empty, torch.full_like(order, pad_id), order % V)
+    pfin = finished.gather(1, parent)
+    sc = torch.where(empty, gum, phi.gather(1, order))
+    return (parent, token, sc, gum, pfin | (token == eos_id) | empty, lengths.gather(1, parent) + (~pfin).to(lengths.dtype))
+
+
+def sbs_importance_weights(scores, gumbels):
+    """Importance weights of a stochastic beam sample: scores / gumbels [n, k], sorted by Gumbel value as the decode
+    returns them.  kappa = the k-th (smallest) Gumbel value of the sample; w_i = p_i / q_i(kappa) with p_i = exp(scores_i)
+    and q_i = 1 - exp(-exp(scores_i - kappa)) (through expm1) for the first k - 1 beams, 0 for the last.
+    Returns (w, w_normalised), each [n, k].  The FIRST is the unbiased one: E[sum_i w_i f(y_i)] = E_p[f] exactly; the second,
+    w / sum w per sample, is biased but of lower variance (the paper's normalised estimator).  k = 1 has no estimator
+    (no threshold is left): ValueError."""
+    if scores.dim() != 2 or scores.shape != gumbels.shape:
+        raise ValueError(f"sbs_importance_weights: scores {list(scores.shape)} and gumbels {list(gumbels.shape)} must be "
+                         "the same [n, k]")
+    if scores.shape[1] < 2:
+        raise ValueError("sbs_importance_weights: k = 1 has no estimator (the k-th Gumbel value is the threshold)")
+    kappa = gumbels[:, -1:]
+    ok = scores > -math.inf                                      # (a slot at -inf: the sample ran out of sequences)
+    q = -torch.expm1(-torch.exp(torch.where(ok, scores, torch.zeros_like(scores)) - kappa))
+    w = torch.where(ok, torch.exp(scores) / q, torch.zeros_like(scores))
+    w = torch.cat([w[:, :-1], torch.zeros_like(w[:, -1:])], dim=1)
+    return w, w / w.sum(1, keepdim=True)
+
+
 class KVDecoder:
     def __init__(self, model, pad_id: int, sos_id: int, eos_id: int):
         dec = model.decoder
@@ -1237,6 +1360,7 @@ class KVDecoder:
             # beam search state (generate_beam), per row: score, finished, length, parent; the ancestry map; done [n/k]
             self.beams = beams
             self.bscores = torch.zeros(n, device=dev)
+            self.bgumbel = torch.zeros(n, device=dev)                      # generate_sbs: the rows' Gumbel values
             self.bfin = torch.zeros(n, dtype=torch.uint8, device=dev)
             self.blen = torch.zeros(n, dtype=torch.int32, device=dev)
             self.bparent = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -1392,9 +1516,9 @@ class KVDecoder:
     @torch.no_grad()
     def step(self, plan=StepPlan()):
         """Consume token ys[:, p] with p = *pos + 1 ... see _chain: ONE generated token, position on the device.
-        select BEAM: the self-attention reads the caches through the ancestry map kv_src (gct_attn_decode_beam)."""
+        select BEAM / SBEAM: the self-attention reads the caches through the ancestry map kv_src (gct_attn_decode_beam)."""
         dec, d, n, T, B = self.dec, self.d, self.n, self.T, self.buf
-        beam, row_off = plan.select == BEAM, self._rows(plan)["row_off"]
+        beam, row_off = plan.select in (BEAM, SBEAM), self._rows(plan)["row_off"]
         check(ops._L().gct_decode_advance(self.pos.data_ptr(), ops._st()), "gct_decode_advance")   # pos = the token consumed now
         ops.decode_embed(self.ys, self.pos, self.off, dec.embed.embed.weight, dec.pe.pe, B["x"], math.sqrt(d),
                          row_off=row_off)
@@ -1445,13 +1569,18 @@ class KVDecoder:
 
     def _select(self, plan):
         """softmax + choice of the next token from buf['logits']; written at ys[:, *pos + 1] (device position).
-        BEAM: gct_beam_select (beam state, the kv_src map and bdone in place).  FILTERED: the multinomial draw through the
+        BEAM: gct_beam_select (beam state, the kv_src map and bdone in place); SBEAM: gct_beam_select_gumbel.  FILTERED: the multinomial draw through the
         top-k / nucleus / temperature settings in self.filt.  With a grammar the choice is made from a masked copy of
         the logits (gct_grammar_mask, one launch more); buf['logits'] stays raw for _chosen_logp."""
         if plan.select == BEAM:
             ops.beam_select(self.buf["logits"], self.beams, self.bscores, self.bfin, self.blen, self.ys, self.valid,
                             self.off, self.kv_src, self.bdone, self.pos, self.pad_id, self.eos_id,
                             parent_i32=self.bparent)
+            return
+        if plan.select == SBEAM:                         # the same state plus bgumbel; the draw's seed from self.seed
+            ops.beam_select_gumbel(self.buf["logits"], self.beams, self.bscores, self.bgumbel, self.bfin, self.blen,
+                                   self.ys, self.valid, self.off, self.kv_src, self.bdone, self.pos, self.pad_id,
+                                   self.eos_id, seed_dev=self.seed, parent_i32=self.bparent)
             return
         logits = self.buf["logits"]
         if plan.grammar:                                 # the selection sees -inf on what the grammar / the budget forbid
@@ -1622,6 +1751,52 @@ class KVDecoder:
         ys = torch.gather(self.ys[:, :last], 0, self.kv_src[:, self.off:self.off + last].long())
         return beam_finalize(ys.view(ns, k, last), self.bscores.view(ns, k).clone(),
                              self.blen.view(ns, k).to(torch.int64), t0, alpha)
+
+    @torch.no_grad()
+    def generate_sbs(self, ys0, k, max_strlen=80, seed=0, check_every=8, use_graphs=False, prefix_lens=None):
+        """Stochastic beam search from the prefix ys0 [n, t0] after start(..., beams=k): k DISTINCT token rows per
+        sample, an exact sample without replacement from the model's distribution over sequences of up to max_strlen-1
+        tokens (sbs_step_reference states the step; gct_beam_select_gumbel runs it).  generate_beam's flow: prefill,
+        sbs_init, the first selection from the prefill's logits, the steps with an early stop once every beam of every
+        sample has produced <eos> (checked every `check_every` steps), the gather through kv_src.
+        Returns SbsSamples(ys [n, k, L], logp [n, k], gumbel [n, k], lengths [n, k]), beams in drawing order (descending
+        Gumbel value, the order the kernel leaves them in; no length normalisation), L = t0 + the longest beam.  The
+        root's Gumbel value is drawn too (sbs_root_gumbels(n, seed): sbs_importance_weights needs it).  The same seed
+        gives the same sample.  Mixed prefix lengths raise ValueError, as in generate_beam."""
+        if prefix_lens is not None:
+            raise ValueError("generate_sbs: mixed prefix lengths are not supported; run one decode per length")
+        k = int(k)
+        if k != self.beams:
+            raise ValueError(f"generate_sbs: k = {k}, but start() prepared {self.beams} beam(s) per sample")
+        ns, t0 = ys0.shape
+        if ns * k != self.n:
+            raise ValueError(f"generate_sbs: {ns} prefixes x {k} beams != the {self.n} rows start() prepared")
+        steps = max_strlen - 1
+        if steps < 1:
+            raise ValueError("generate_sbs: max_strlen must be at least 2")
+        if self.off + t0 + steps > self.T:
+            raise ValueError(f"prefix {t0} + {steps} steps exceeds the cache length {self.T - self.off}")
+        dev, plan = self.ys.device, StepPlan(SBEAM)
+        self.seed.fill_(int(seed) & 0x7FFFFFFFFFFFFFFF)
+        self.prefill(ys0.to(dev).repeat_interleave(k, 0))
+        scores, gumbels, _, _ = sbs_init(ns, k, dev, root=sbs_root_gumbels(ns, seed, dev))
+        self.bscores.copy_(scores.view(-1))
+        self.bgumbel.copy_(gumbels.view(-1))
+        self.bfin.zero_()
+        self.blen.zero_()
+        self.bdone.zero_()
+        self.kv_src.copy_(torch.arange(self.n, dtype=torch.int32, device=dev).view(-1, 1).expand(-1, self.T))
+        self._select(plan)                                         # token t0 from the prefill's last position
+        last = t0 + steps
+        for i in range(1, steps):
+            self._run_step(plan, use_graphs)                       # consumes token t0+i-1, writes token t0+i
+            if check_every and (i + 1) % check_every == 0 and bool(self.bdone.all()):
+                last = t0 + i + 1
+                break
+        ys = torch.gather(self.ys[:, :last], 0, self.kv_src[:, self.off:self.off + last].long()).view(ns, k, last)
+        lengths = self.blen.view(ns, k).to(torch.int64)
+        return SbsSamples(ys[:, :, :t0 + int(lengths.max())].contiguous(), self.bscores.view(ns, k).clone(),
+                          self.bgumbel.view(ns, k).clone(), lengths)
 
     # ------------------------------------------------------------------------------------- continuous batching
     @torch.no_grad()
@@ -1827,8 +2002,8 @@ class KVDecoder:
 
     def _state_tensors(self, plan):
         """Everything a step + selection writes besides the caches' next row (the beam state included)."""
-        base = (self.pos, self.ys, self.valid, self.done, self.bscores, self.bfin, self.blen, self.bparent,
-                self.kv_src, self.bdone)
+        base = (self.pos, self.ys, self.valid, self.done, self.bscores, self.bgumbel, self.bfin, self.blen,
+                self.bparent, self.kv_src, self.bdone)
         if plan.layout != STREAM:
             return base
         st = self.stream                                  # (the refill is held while a state is kept: _hold_refill)
@@ -1978,3 +2153,36 @@ def reference_style_beam_decode(model, z, src_mask, dconds, ys0, pad_id, eos_id,
         if bool(finished.all()):
             break
     return beam_finalize(ys.view(n, k, -1), scores, lengths, t0, alpha)
+
+
+@torch.no_grad()
+def reference_style_sbs_decode(model, z, src_mask, dconds, ys0, pad_id, eos_id, k, noise_fn, max_strlen=80, trace=None,
+                               root=None):
+    """Stochastic beam search on the un-cached model.decode over [n*k, t] every step: reference_style_beam_decode's loop
+    with sbs_step_reference as the selection -- the baseline generate_sbs must match.  noise_fn(step) -> [n*k, V] are the
+    standard Gumbel variates of step 0, 1, ... (row s*k + b: beam b of sample s); root [n] the roots' Gumbel values
+    (sbs_init; None: 0).  Returns SbsSamples.
+    trace (a list): receives the k+1 largest candidate values [n, k+1] of every step (near-tie diagnostics)."""
+    from .Model.modules import get_trg_mask
+    dec = model.decoder
+    c2d = bool(dec.use_cond2dec and dec.nconds > 0)
+    nc = dec.nconds if c2d else 0
+    n, t0 = ys0.shape
+    k = int(k)
+    rep = lambda x: None if x is None else x.repeat_interleave(k, 0)       # noqa: E731
+    z, src_mask, dconds, ys = rep(z), rep(src_mask), rep(dconds), rep(ys0)
+    scores, gumbels, finished, lengths = sbs_init(n, k, ys.device, root=root)
+    base = torch.arange(n, device=ys.device).view(n, 1) * k
+    for step in range(max_strlen - 1):
+        logits = model.decode(ys, z, src_mask, get_trg_mask(ys, pad_id, c2d, dconds), dconds)[:, nc:]
+        logp, noise = beam_log_softmax(logits[:, -1]), noise_fn(step).to(ys.device)
+        if trace is not None:
+            val = sbs_candidates(scores, gumbels, finished, logp, noise, k, pad_id)[0]
+            trace.append(val.topk(min(k + 1, val.shape[1]), dim=1).values.cpu())
+        parent, tok, scores, gumbels, finished, lengths = sbs_step_reference(scores, gumbels, finished, lengths, logp,
+                                                                             noise, k, pad_id, eos_id)
+        ys = torch.cat([ys[(base + parent).view(-1)], tok.view(-1, 1)], dim=1)
+        if bool(finished.all()):
+            break
+    ys = ys.view(n, k, -1)
+    return SbsSamples(ys[:, :, :t0 + int(lengths.max())].contiguous(), scores, gumbels, lengths)

@@ -1460,3 +1460,23 @@ def beam_select(logits2d, beam_size, scores, finished_u8, lengths_i32, ys, valid
                                _p(parent_i32), _p(ys), ys.stride(0), _p(valid_u8), valid_u8.stride(0), valid_off,
                                _p(kv_src), kv_src.stride(0), T, _p(done_u8), _p(pos_dev), pad_id, eos_id, _st()),
           "gct_beam_select")
+
+
+def beam_select_gumbel(logits2d, beam_size, scores, gumbels, finished_u8, lengths_i32, ys, valid_u8, valid_off, kv_src,
+                       done_u8, pos_dev, pad_id, eos_id, seed=0, seed_dev=None, noise_in=None, noise_out=None,
+                       parent_i32=None):
+    """gct_beam_select_gumbel over logits [n*k, V]: the stochastic beam step (decode.sbs_step_reference) -- beam_select
+    with the rows' Gumbel values `gumbels` [n*k] fp32 as one more array of state, written in place like the rest.
+    seed_dev (int64 / uint64 [1] on the device) replaces seed; noise_in [n*k, V] fp32 replaces the draw; noise_out
+    [n*k, V] fp32 receives the variates used for live beams."""
+    rows, V = logits2d.shape
+    k = int(beam_size)
+    T = kv_src.shape[1]
+    for name, t in (("noise_in", noise_in), ("noise_out", noise_out)):
+        if t is not None and (t.shape != logits2d.shape or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f"beam_select_gumbel: {name} must be contiguous fp32 {list(logits2d.shape)}")
+    check(_L().gct_beam_select_gumbel(_p(logits2d), V, rows // k, k, _p(scores), _p(finished_u8), _p(lengths_i32),
+                                      _p(parent_i32), _p(ys), ys.stride(0), _p(valid_u8), valid_u8.stride(0), valid_off,
+                                      _p(kv_src), kv_src.stride(0), T, _p(done_u8), _p(pos_dev), pad_id, eos_id,
+                                      _p(gumbels), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(seed_dev), _p(noise_in),
+                                      _p(noise_out), _st()), "gct_beam_select_gumbel")

@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 30
+#define GCT_ABI_VERSION 31
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -800,6 +800,39 @@ int gct_beam_select(const float* logits, int V, int n, int k, float* scores, uin
                     int32_t* parent, int64_t* ys, int64_t ld_ys, uint8_t* valid, int64_t valid_sb, int valid_off,
                     int32_t* kv_src, int64_t ld_src, int T, uint8_t* done, const int32_t* pos_dev, int64_t pad_id,
                     int64_t eos_id, void* stream);
+
+/* Stochastic beam search (ABI 31; Kool, van Hoof and Welling, ICML 2019; gct_plus_amd/decode.py sbs_step_reference
+ * states the rules): beam search over Gumbel-perturbed log-probabilities, whose k beams are a sample WITHOUT replacement
+ * from the sequence distribution.  gct_beam_select_gumbel is gct_beam_select -- the same arguments, limits, error checks
+ * and write-back, one kernel template -- with one more float of state per row, gumbels [n*k] (in place; after the
+ * prefill [0, -inf, ...] like scores), and another ordering value:
+ *   a live beam b (finite scores[b]) offers every token v with finite phi_bv = scores[b] + logp_b(v) (gct_beam_select's
+ *     fp32 log-softmax); g_bv = phi_bv + noise_bv; Z_b = max_v g_bv over the offered tokens, v*_b its first argmax;
+ *   the candidate's value is g~_bv = -log(exp(-G_b) - exp(-Z_b) + exp(-g_bv)), G_b = gumbels[b], evaluated in fp32 as
+ *     d = min(g - Z, 0); l = log(1 - exp(d)) (log(-expm1(d)) for d > -ln 2, log1p(-exp(d)) otherwise); w = G - g + l;
+ *     g~ = G - max(w, 0) - log1p(exp(-|w|));  token v*_b gets g~ = G_b exactly, BY ITS INDEX;
+ *   a token with phi = -inf is not offered; a finished beam offers itself once, token pad_id, score and Gumbel value
+ *     unchanged; a beam at -inf offers nothing;
+ *   the k candidates of largest g~, ties to the lower beam * V + token, become the children in that order: scores = phi,
+ *     gumbels = g~, everything else as gct_beam_select writes it.  A slot c for which no candidate is left (fewer than k
+ *     offered) becomes a finished beam at -inf: parent c, token pad_id, scores = gumbels = -inf.
+ * The draw: noise_bv of the PHYSICAL row r = s*k + b at token position p = *pos_dev + 1 (a child's noise therefore
+ * depends on the slot its parent sits in, which changes no distribution: the variates of distinct (row, p, v) are
+ * independent) is word v & 3 of Philox4x32-10 at the counter (r, p, v >> 2, GCT_SBS_C3) -- one call serves four tokens --
+ * under the key of (seed, site GCT_SBS_SITE): (seed_lo, seed_hi ^ (GCT_SBS_SITE * 0x9E3779B9 + 0x7F4A7C15));
+ *   u = (float32(x >> 9) + 0.5f) * 2^-23: exact in fp32 (23 bits and a half), strictly inside (0, 1);
+ *   noise = -logf(-logf(u)).
+ * seed_dev (nullable, DEVICE memory) replaces seed, so that one captured graph serves every seed (as gct_select_token).
+ * noise_in (nullable, [n*k][V]): these variates are used instead of the draw.  noise_out (nullable, [n*k][V]): receives
+ * the variates used for the rows of live beams (all V of them); rows of other beams are not written.
+ * gumbels NULL, or anything gct_beam_select refuses: GCT_ERR_ARG. */
+#define GCT_SBS_SITE 0x5B5BEAu
+#define GCT_SBS_C3 0xBE5466CFu
+int gct_beam_select_gumbel(const float* logits, int V, int n, int k, float* scores, uint8_t* finished, int32_t* lengths,
+                           int32_t* parent, int64_t* ys, int64_t ld_ys, uint8_t* valid, int64_t valid_sb, int valid_off,
+                           int32_t* kv_src, int64_t ld_src, int T, uint8_t* done, const int32_t* pos_dev, int64_t pad_id,
+                           int64_t eos_id, float* gumbels, uint64_t seed, const uint64_t* seed_dev,
+                           const float* noise_in, float* noise_out, void* stream);
 
 /* ------------------------------------------------ host side: SMILES tokeniser + collate */
 /* Utils/field.py:8-33 moltokenize (the atom-wise regex, findall semantics) as a scanner.
