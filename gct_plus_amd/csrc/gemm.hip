@@ -2240,3 +2240,195 @@ extern "C" int gct_linear_bwd(const float* dy0, const float* dy1, const float* d
   return gct_linear_dgrad(dy0, dy1, dy2, lddy, M, nseg, nper, w0, w1, w2, ldw, wp0, plane_stride, K, dx, lddx, depi,
                           pre, p, seed, site, dws, dws_bytes, quad_map, pre_rows, stream);
 }
+
+// ---- cross-attention K | V straight from the latent (ABI 32) ------------------------------------------------------
+// The decoder memory is e = z W_z^T + b_z and, without cond2lat rows, feeds nothing but the k_linear | v_linear
+// projections of the decoder layers: kvb_l = e W_kv,l^T + b_kv,l = z A_l^T + c_l with A_l = W_kv,l W_z and
+// c_l = W_kv,l b_z + b_kv,l.  The row-sized GEMMs then reduce over the latent width instead of d_model, and the
+// weight-sized products below carry the gradients back to W_kv,l, W_z and b_z.
+namespace {
+
+struct KvFoldTab {
+  const float* w[2 * GCT_KV_FOLD_MAX_LAYERS];      // segment 2 l: k_linear.weight of layer l, 2 l + 1: v_linear.weight
+  const float* b[2 * GCT_KV_FOLD_MAX_LAYERS];
+};
+
+// one wave per weight row r of the stack (4 rows per workgroup, all of one segment: d % 4 == 0):
+// wstack[r][:] = W_seg[r % d][:], c[r] = W_seg[r % d][:] . bz + b_seg[r % d]
+__global__ __launch_bounds__(256) void kv_fold_stack_kernel(const KvFoldTab t, int d, int dm, const float* __restrict__ bz,
+                                                            float* __restrict__ wstack, float* __restrict__ c) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r0 = (int64_t)blockIdx.x * 4;
+  const int seg = (int)(r0 / d);                     // uniform over the workgroup: the table entry is a scalar load
+  const int64_t i = r0 % d + (threadIdx.x >> 6);
+  const float* src = t.w[seg] + i * dm;
+  float* dst = wstack + (r0 + (threadIdx.x >> 6)) * dm;
+  float acc = 0.f;
+  for (int k = lane * 4; k < dm; k += 256) {
+    const float4 v = *reinterpret_cast<const float4*>(src + k);
+    const float4 z = *reinterpret_cast<const float4*>(bz + k);
+    *reinterpret_cast<float4*>(dst + k) = v;
+    acc = fmaf(v.x, z.x, acc); acc = fmaf(v.y, z.y, acc); acc = fmaf(v.z, z.z, acc); acc = fmaf(v.w, z.w, acc);
+  }
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  const float* b = t.b[seg];
+  if (lane == 0) c[r0 + (threadIdx.x >> 6)] = acc + (b ? b[i] : 0.f);
+}
+
+// dW[m][n] = sum_k P[m][k] W_z[n][k] + s[m] b_z[n] for the 2 d rows m of one layer (rows < d to dw0, the others to
+// dw1), db = s: fp32 fma chains over the latent width, 64 x 64 outputs per workgroup, 4 x 4 per thread
+constexpr int KVF_T = 64, KVF_K = 32, KVF_LD = KVF_T + 4;
+__global__ __launch_bounds__(256) void kv_fold_wgrad_kernel(const float* __restrict__ p, const float* __restrict__ s, int d,
+                                                            int lat, const float* __restrict__ wz,
+                                                            const float* __restrict__ bz, int dm, float* __restrict__ dw0,
+                                                            float* __restrict__ dw1, float* __restrict__ db0,
+                                                            float* __restrict__ db1) {
+  __shared__ float as[KVF_K][KVF_LD], bs[KVF_K][KVF_LD];
+  const int tid = threadIdx.x, tm = tid >> 4, tn = tid & 15;
+  const int m0 = blockIdx.x * KVF_T, n0 = blockIdx.y * KVF_T, M = 2 * d;
+  float acc[4][4] = {};
+  // 64 rows x 8 float4 of each operand per K-chunk, two per thread: the next chunk is in flight while this one is used
+  float4 ra[2], rb[2];
+  const float4 zero4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int e = tid + i * 256, row = e >> 3, k = (e & 7) * 4;       // lat % 4 == 0: a float4 is inside or outside
+    ra[i] = (k < lat && m0 + row < M) ? *reinterpret_cast<const float4*>(p + (int64_t)(m0 + row) * lat + k) : zero4;
+    rb[i] = (k < lat && n0 + row < dm) ? *reinterpret_cast<const float4*>(wz + (int64_t)(n0 + row) * lat + k) : zero4;
+  }
+  for (int k0 = 0; k0 < lat; k0 += KVF_K) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {                              // k-major in LDS
+      const int e = tid + i * 256, row = e >> 3, kk = (e & 7) * 4;
+      as[kk][row] = ra[i].x; as[kk + 1][row] = ra[i].y; as[kk + 2][row] = ra[i].z; as[kk + 3][row] = ra[i].w;
+      bs[kk][row] = rb[i].x; bs[kk + 1][row] = rb[i].y; bs[kk + 2][row] = rb[i].z; bs[kk + 3][row] = rb[i].w;
+    }
+    __syncthreads();
+    if (k0 + KVF_K < lat) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int e = tid + i * 256, row = e >> 3, k = k0 + KVF_K + (e & 7) * 4;
+        ra[i] = (k < lat && m0 + row < M) ? *reinterpret_cast<const float4*>(p + (int64_t)(m0 + row) * lat + k) : zero4;
+        rb[i] = (k < lat && n0 + row < dm) ? *reinterpret_cast<const float4*>(wz + (int64_t)(n0 + row) * lat + k) : zero4;
+      }
+    }
+#pragma unroll 8
+    for (int k = 0; k < KVF_K; ++k) {
+      const float4 a = *reinterpret_cast<const float4*>(&as[k][tm * 4]);
+      const float4 b = *reinterpret_cast<const float4*>(&bs[k][tn * 4]);
+      const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(av[i], bv[j], acc[i][j]);
+    }
+    __syncthreads();
+  }
+  const int n = n0 + tn * 4;
+  if (n >= dm) return;                                        // dm % 4 == 0: the four columns are inside together
+  const float4 z = *reinterpret_cast<const float4*>(bz + n);
+  for (int i = 0; i < 4; ++i) {
+    const int m = m0 + tm * 4 + i;
+    if (m >= M) break;
+    const float sm = s[m];
+    float* dst = (m < d ? dw0 + (int64_t)m * dm : dw1 + (int64_t)(m - d) * dm) + n;
+    const float4 o = {fmaf(sm, z.x, acc[i][0]), fmaf(sm, z.y, acc[i][1]), fmaf(sm, z.z, acc[i][2]),
+                      fmaf(sm, z.w, acc[i][3])};
+    *reinterpret_cast<float4*>(dst) = o;
+    if (blockIdx.y == 0 && tn == 0) (m < d ? db0 + m : db1 + (m - d))[0] = sm;
+  }
+}
+
+// db_z[n] = sum_r wstack[r][n] s[r] in two deterministic stages: partial sums of 32 rows, then their sum in a fixed order
+constexpr int KVF_ROWS = 32;
+__global__ __launch_bounds__(256) void kv_fold_dbz_part_kernel(const float* __restrict__ wstack, const float* __restrict__ s,
+                                                               int64_t rows, int dm, float* __restrict__ part) {
+  const int n = blockIdx.y * 256 + threadIdx.x;
+  if (n >= dm) return;
+  const int64_t r0 = (int64_t)blockIdx.x * KVF_ROWS, r1 = r0 + KVF_ROWS < rows ? r0 + KVF_ROWS : rows;
+  float acc = 0.f;
+#pragma unroll 8
+  for (int64_t r = r0; r < r1; ++r) acc = fmaf(wstack[r * dm + n], s[r], acc);
+  part[(int64_t)blockIdx.x * dm + n] = acc;
+}
+__global__ __launch_bounds__(256) void kv_fold_dbz_sum_kernel(const float* __restrict__ part, int nparts, int dm,
+                                                              float* __restrict__ dbz) {
+  __shared__ float sh[8][32];                          // 32 columns per workgroup, the parts dealt to 8 lanes each
+  const int c = threadIdx.x & 31, lane = threadIdx.x >> 5, n = blockIdx.x * 32 + c;
+  float acc = 0.f;
+  if (n < dm)
+    for (int i = lane; i < nparts; i += 8) acc += part[(int64_t)i * dm + n];
+  sh[lane][c] = acc;
+  __syncthreads();
+  if (lane == 0 && n < dm) {
+    float t = sh[0][c];
+    for (int j = 1; j < 8; ++j) t += sh[j][c];
+    dbz[n] = t;
+  }
+}
+
+}  // namespace
+
+extern "C" int64_t gct_kv_fold_ws_bytes(int layers, int d, int dm, int lat) {
+  const int64_t rows = (int64_t)layers * 2 * d;
+  const int64_t g = gct_linear_dgrad_ws_bytes(rows, dm, lat);
+  const int64_t parts = ((rows + KVF_ROWS - 1) / KVF_ROWS) * dm * (int64_t)sizeof(float) + 256;
+  return g > parts ? g : parts;
+}
+
+extern "C" int gct_kv_fold_fwd(int layers, const int64_t* w_addrs, const int64_t* b_addrs, int d, int dm,
+                               const float* wz, const uint16_t* wzp, int64_t wz_plane_stride, const float* bz, int lat,
+                               float* wstack, float* a, float* c, uint16_t* a_planes, int64_t a_plane_stride,
+                               float* ws, int64_t ws_bytes, void* stream) {
+  GCT_CHECK_ARG(layers >= 1 && layers <= GCT_KV_FOLD_MAX_LAYERS && w_addrs && wz && bz && wstack && a && c,
+                "kv_fold_fwd: bad args (1 .. %d layers)", GCT_KV_FOLD_MAX_LAYERS);
+  GCT_CHECK_ARG(d > 0 && d % 4 == 0 && dm > 0 && dm % 4 == 0 && lat > 0 && lat % 4 == 0,
+                "kv_fold_fwd: d, d_model and the latent width must be multiples of 4");
+  GCT_CHECK_ARG(gct_aligned16(wz) && gct_aligned16(bz) && gct_aligned16(wstack) && gct_aligned16(a),
+                "kv_fold_fwd: buffers must be 16-byte aligned");
+  KvFoldTab t = {};
+  for (int i = 0; i < 2 * layers; ++i) {
+    t.w[i] = reinterpret_cast<const float*>((uintptr_t)w_addrs[i]);
+    t.b[i] = b_addrs ? reinterpret_cast<const float*>((uintptr_t)b_addrs[i]) : nullptr;
+    GCT_CHECK_ARG(t.w[i] && gct_aligned16(t.w[i]), "kv_fold_fwd: weight %d missing or not 16-byte aligned", i);
+  }
+  const int64_t rows = (int64_t)layers * 2 * d;
+  hipLaunchKernelGGL(kv_fold_stack_kernel, dim3((unsigned)(rows / 4)), dim3(256), 0, (hipStream_t)stream, t, d, dm, bz,
+                     wstack, c);
+  GCT_LAUNCH_CHECK("kv_fold_stack");
+  // A = wstack W_z: the dgrad form (rows of wstack against the natural [d_model][latent] weight and its planes)
+  int rc = gct_linear_dgrad(wstack, nullptr, nullptr, dm, rows, 1, dm, wz, nullptr, nullptr, lat, wzp, wz_plane_stride,
+                            lat, a, lat, GCT_DEPI_STORE, nullptr, 0.f, 0, 0, ws, ws ? ws_bytes : 0, nullptr, 0, stream);
+  if (rc || !a_planes) return rc;
+  return gct_split_planes(a, rows * lat, a_planes, a_plane_stride, stream);
+}
+
+extern "C" int gct_kv_fold_wgrad(const float* p, const float* s, int d, int lat, const float* wz, const float* bz,
+                                 int dm, float* dw0, float* dw1, float* db0, float* db1, void* stream) {
+  GCT_CHECK_ARG(p && s && wz && bz && dw0 && dw1 && db0 && db1 && d > 0 && lat > 0 && lat % 4 == 0 && dm > 0 &&
+                    dm % 4 == 0,
+                "kv_fold_wgrad: bad args (latent width and d_model must be multiples of 4)");
+  GCT_CHECK_ARG(gct_aligned16(p) && gct_aligned16(wz) && gct_aligned16(bz) && gct_aligned16(dw0) && gct_aligned16(dw1),
+                "kv_fold_wgrad: buffers must be 16-byte aligned");
+  const dim3 grid((unsigned)((2 * d + KVF_T - 1) / KVF_T), (unsigned)((dm + KVF_T - 1) / KVF_T));
+  hipLaunchKernelGGL(kv_fold_wgrad_kernel, grid, dim3(256), 0, (hipStream_t)stream, p, s, d, lat, wz, bz, dm, dw0, dw1,
+                     db0, db1);
+  GCT_LAUNCH_CHECK("kv_fold_wgrad");
+  return GCT_OK;
+}
+
+extern "C" int gct_kv_fold_dbz(const float* wstack, const float* s, int64_t rows, int dm, float* dbz, float* ws,
+                               int64_t ws_bytes, void* stream) {
+  GCT_CHECK_ARG(wstack && s && dbz && ws && rows > 0 && dm > 0, "kv_fold_dbz: bad args");
+  const int64_t parts = (rows + KVF_ROWS - 1) / KVF_ROWS;
+  GCT_CHECK_ARG(parts * dm * (int64_t)sizeof(float) <= ws_bytes && parts <= INT_MAX,
+                "kv_fold_dbz: workspace of %lld B < %lld B", (long long)ws_bytes,
+                (long long)(parts * dm * (int64_t)sizeof(float)));
+  hipLaunchKernelGGL(kv_fold_dbz_part_kernel, dim3((unsigned)parts, (unsigned)((dm + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, wstack, s, rows, dm, ws);
+  GCT_LAUNCH_CHECK("kv_fold_dbz_part");
+  hipLaunchKernelGGL(kv_fold_dbz_sum_kernel, dim3((unsigned)((dm + 31) / 32)), dim3(256), 0, (hipStream_t)stream,
+                     (const float*)ws, (int)parts, dm, dbz);
+  GCT_LAUNCH_CHECK("kv_fold_dbz_sum");
+  return GCT_OK;
+}

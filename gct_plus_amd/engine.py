@@ -38,6 +38,9 @@ COMPACT_KV = os.environ.get("GCT_COMPACT_KV", "1") != "0"
 COMPACT_FWD = os.environ.get("GCT_COMPACT_FWD", "1") != "0"
 # K | V projections of the ENCODER self-attention over the visible rows only (mha_fwd): GCT_COMPACT_ENC_KV=0 disables.
 COMPACT_ENC_KV = os.environ.get("GCT_COMPACT_ENC_KV", "1") != "0"
+# Cross-attention K | V straight from the latent (ops.KvFold; decoder_trunk_fwd takes it when the memory has no cond2lat
+# rows).  Tests flip this attribute to run the same model both ways (and restore it); there is no environment knob.
+KV_FOLD = True
 
 
 # Data parallelism (dp.FlatDataParallel) sets this while a backward pass is running: called as
@@ -335,15 +338,18 @@ class DecoderSaved(NamedTuple):
     trg_mask_u8: Optional[torch.Tensor]  # unpacked: the backward's ops.LiveRows checks its rows against it
     keys: object                         # plan.dec_keys of the forward
     live: object                         # plan.live of the forward: the trunk ran on these compact rows
+    fold: object = None                  # ops.KvFold: the cross-attention K | V came from the rows of z (attn_2.xkv)
 
 
 # ------------------------------------------------------------------------------------- MHA
-def mha_fwd(run: Run, m, xq, xkv, B, Lq, Lk, mask_u8, resid, want_probs=False, keys=None, live=None):
+def mha_fwd(run: Run, m, xq, xkv, B, Lq, Lk, mask_u8, resid, want_probs=False, keys=None, live=None, fold=None):
     """m: MultiHeadAttention module (q_linear, k_linear, v_linear, out).  xq [B*Lq,d],
     xkv [B*Lk,d] (the same tensor object for self-attention).  With `resid` the output
     projection fuses  resid + dropout(.)  (the layer's dropout_k + residual add).
     live (ops.LiveRows with .fwd): xq / resid / the result hold the compact query rows only (and xkv too for
-    self-attention: the live rows of a sample are a prefix, so they are also the only keys a live query can see)."""
+    self-attention: the live rows of a sample are a prefix, so they are also the only keys a live query can see).
+    fold ((ops.KvFold, layer), cross-attention only): xkv holds the rows of the latent z instead of the memory, and
+    K | V are its image under the folded weights of that layer."""
     d, H = m.d_model, m.h
     dk = d // H
     self_attn = xkv is xq
@@ -369,8 +375,11 @@ def mha_fwd(run: Run, m, xq, xkv, B, Lq, Lk, mask_u8, resid, want_probs=False, k
         ops.linear_fwd(xq, [m.q_linear.weight], [m.q_linear.bias], [qb], d)
         # keys (ops.KeyRows): xkv holds the VISIBLE rows of the encoder memory only (quad-compacted)
         kvb = _empty(B * Lk, 2 * d, xkv) if keys is None else keys.empty(2 * d)
-        ops.linear_fwd(xkv, [m.k_linear.weight, m.v_linear.weight],
-                       [m.k_linear.bias, m.v_linear.bias], [kvb, kvb[:, d:]], 2 * d)
+        if fold is not None:
+            fold[0].fwd(fold[1], xkv, [kvb, kvb[:, d:]], 2 * d)
+        else:
+            ops.linear_fwd(xkv, [m.k_linear.weight, m.v_linear.weight],
+                           [m.k_linear.bias, m.v_linear.bias], [kvb, kvb[:, d:]], 2 * d)
         q, k, v, ldq, ldkv = qb, kvb, kvb[:, d:], d, 2 * d
     site_p = run.site()
     o, lse, probs = ops.attn_fwd(q, k, v, ldq, ldkv, ldkv, mask_u8, B, H, Lq, Lk, dk, run.p,
@@ -388,13 +397,15 @@ def mha_fwd(run: Run, m, xq, xkv, B, Lq, Lk, mask_u8, resid, want_probs=False, k
 
 
 def mha_bwd(run: Run, m, sv: MhaSaved, dy, G: GradSink, dxq_out, depi_q, dxkv_out=None,
-            depi_kv=ops.DEPI_STORE, live=None, gdrop=None):
+            depi_kv=ops.DEPI_STORE, live=None, gdrop=None, fold=None):
     """dy: gradient w.r.t. the block output (resid + dropout(out(o)) or out(o)); gdrop: dropout_bwd(dy) already
     computed by the producer of dy (ops.norm_bwd(drop=...)).
     Writes dW/db through G, d(xq) into dxq_out (epilogue depi_q) and, for cross-attention,
     d(xkv) into dxkv_out (epilogue depi_kv).  The identity path to `resid` is the caller's.
     live (ops.LiveRows): the QUERY-side rows (dy, dxq_out) are quad-compacted; saved forward tensors are
-    gathered on the way in, key/value-side gradients of cross-attention stay in the encoder's row space."""
+    gathered on the way in, key/value-side gradients of cross-attention stay in the encoder's row space.
+    fold ((ops.KvFold, layer)): sv.xkv holds rows of the latent z; dxkv_out (nullable) is d(those rows), and the
+    gradients of k_linear / v_linear are the caller's (KvFold.wgrad_layer, after the layer's slab reductions)."""
     B, Lq, Lk, keys = sv.B, sv.Lq, sv.Lk, sv.keys
     d, H = m.d_model, m.h
     dk = d // H
@@ -436,6 +447,9 @@ def mha_bwd(run: Run, m, sv: MhaSaved, dy, G: GradSink, dxq_out, depi_q, dxkv_ou
                      d, 2 * d, 2 * d, B, H, Lq, Lk, dk, run.p, run.seed, sv.site_p, live=live, keys=keys)
         ops.linear_bwd([dq], d, xq_in, [m.q_linear.weight], [G(m.q_linear.weight)], [G(m.q_linear.bias)], dxq_out,
                        depi=depi_q, kt=kt, M=Mq)                                          # query rows
+        if fold is not None:
+            fold[0].bwd(fold[1], [dkv, dkv[:, d:]], 2 * d, sv.xkv, dxkv_out, depi_kv, Mk)
+            return
         kv_w = [m.k_linear.weight, m.v_linear.weight]
         kv_g = ([G(m.k_linear.weight), G(m.v_linear.weight)], [G(m.k_linear.bias), G(m.v_linear.bias)])
         if sv.self_split:    # K | V came from the visible rows of xq itself: their input gradient goes back into d(xq)
@@ -528,20 +542,24 @@ def enc_layer_bwd(run: Run, layer, sv: EncLayerSaved, g, G: GradSink, gd=None, g
     return g, (None if dr is None else gdbuf)
 
 
-def dec_layer_fwd(run: Run, layer, x, e, B, T, Lk, src_mask_u8, trg_mask_u8, want_probs=False, keys=None, live=None):
-    """live (ops.LiveRows with .fwd): x and everything row-wise of this layer hold the compact live rows only."""
+def dec_layer_fwd(run: Run, layer, x, e, B, T, Lk, src_mask_u8, trg_mask_u8, want_probs=False, keys=None, live=None,
+                  fold=None):
+    """live (ops.LiveRows with .fwd): x and everything row-wise of this layer hold the compact live rows only.
+    fold ((ops.KvFold, layer)): e holds the rows of the latent z (mha_fwd)."""
     x2, m1, r1 = ops.norm_fwd(x, layer.norm_1.alpha, layer.norm_1.bias, layer.norm_1.eps)
     xa, sa1, p1 = mha_fwd(run, layer.attn_1, x2, x2, B, T, T, trg_mask_u8, x, want_probs, live=live)
     x2, m2, r2 = ops.norm_fwd(xa, layer.norm_2.alpha, layer.norm_2.bias, layer.norm_2.eps)
-    xb, sa2, p2 = mha_fwd(run, layer.attn_2, x2, e, B, T, Lk, src_mask_u8, xa, want_probs, keys=keys, live=live)
+    xb, sa2, p2 = mha_fwd(run, layer.attn_2, x2, e, B, T, Lk, src_mask_u8, xa, want_probs, keys=keys, live=live,
+                          fold=fold)
     x2, m3, r3 = ops.norm_fwd(xb, layer.norm_3.alpha, layer.norm_3.bias, layer.norm_3.eps)
     xc, sf = ffn_fwd(run, layer.ff, x2, xb, live=live)
     return xc, DecLayerSaved(x, m1, r1, sa1, xa, m2, r2, sa2, xb, m3, r3, sf), p1, p2
 
 
 def dec_layer_bwd(run: Run, layer, sv: DecLayerSaved, g, de, first_de, G: GradSink, live=None, gd=None, gdbuf=None,
-                  below=None):
+                  below=None, fold=None):
     """live (ops.LiveRows): g and every row-wise gradient of this layer are quad-compacted [live.Mc, d].
+    fold ((ops.KvFold, layer)): de (nullable) is the gradient of the rows of z, not of the memory.
     gd / gdbuf / below as in enc_layer_bwd; returns (g, dropout_bwd(g) for the FFN of the layer underneath or None)."""
     t = torch.empty_like(g) if live is None else live.empty(g.shape[1])
     with ops.deferred_reductions():      # the layer's 9 weight / bias / Norm slab reductions: one launch at the end
@@ -550,7 +568,8 @@ def dec_layer_bwd(run: Run, layer, sv: DecLayerSaved, g, de, first_de, G: GradSi
         ops.norm_bwd(t, sv.xb, layer.norm_3.alpha, sv.m3, sv.r3, G(layer.norm_3.alpha), G(layer.norm_3.bias),
                      dres=g, out=g, eps=layer.norm_3.eps, live=live, drop=dr)
         mha_bwd(run, layer.attn_2, sv.attn_2, g, G, t, ops.DEPI_STORE, de,
-                ops.DEPI_STORE if first_de else ops.DEPI_ACCUM, live=live, gdrop=None if dr is None else gdbuf)
+                ops.DEPI_STORE if first_de else ops.DEPI_ACCUM, live=live, gdrop=None if dr is None else gdbuf,
+                fold=fold)
         dr = _mha_drop(run, sv.attn_1, gdbuf)
         ops.norm_bwd(t, sv.xa, layer.norm_2.alpha, sv.m2, sv.r2, G(layer.norm_2.alpha), G(layer.norm_2.bias),
                      dres=g, out=g, eps=layer.norm_2.eps, live=live, drop=dr)
@@ -558,6 +577,10 @@ def dec_layer_bwd(run: Run, layer, sv: DecLayerSaved, g, de, first_de, G: GradSi
         dr = _ffn_drop(run, below, gdbuf)
         ops.norm_bwd(t, sv.x, layer.norm_1.alpha, sv.m1, sv.r1, G(layer.norm_1.alpha), G(layer.norm_1.bias),
                      dres=g, out=g, eps=layer.norm_1.eps, live=live, drop=dr)
+    if fold is not None:                 # P_l and s_l are final now: the gradients of k_linear | v_linear from them
+        a2 = layer.attn_2
+        fold[0].wgrad_layer(fold[1], G(a2.k_linear.weight), G(a2.v_linear.weight), G(a2.k_linear.bias),
+                            G(a2.v_linear.bias))
     _grads_done(layer, G)
     return g, (None if dr is None else gdbuf)
 
@@ -648,10 +671,15 @@ def decoder_trunk_fwd(dec, run: Run, trg, z, src_mask_u8, trg_mask_u8, dconds, w
     site_pe = run.site()
     x = ops.embed_pe_fwd(trg, dec.embed.embed.weight, cond_x, _pe2d(dec.pe, T), nc if c2d else 0,
                          math.sqrt(d), run.p, run.seed, site_pe)
-    ez = _empty(B * Le, d, z2)
-    ops.linear_fwd(z2, [dec.fc_z.weight], [dec.fc_z.bias], [ez], d)
+    # Without cond2lat rows the memory e = fc_z(z) feeds nothing but the K | V projections of the layers: they run on
+    # the rows of z itself, through weights folded once per call (ops.KvFold), and e is never formed
+    kv = [(layer.attn_2.k_linear, layer.attn_2.v_linear) for layer in dec.layers]
+    fold = ops.KvFold(kv, dec.fc_z) if (KV_FOLD and not c2l and ops.KvFold.usable(kv, dec.fc_z)) else None
     Lk = Le
-    e = ez
+    e = z2
+    if fold is None:
+        e = ez = _empty(B * Le, d, z2)
+        ops.linear_fwd(z2, [dec.fc_z.weight], [dec.fc_z.bias], [ez], d)
     if c2l:
         Lk = Le + nc
         cl = ops.small_linear_fwd(dconds.contiguous(), dec.embed_cond2lat.weight,
@@ -670,24 +698,26 @@ def decoder_trunk_fwd(dec, run: Run, trg, z, src_mask_u8, trg_mask_u8, dconds, w
         e = keys.gather(e)
     src_m = ops.pack_mask(src_mask_u8, B, T, Lk)
     trg_m = ops.pack_mask(trg_mask_u8, B, T, T)
-    for layer in dec.layers:
-        x, sv, p1, p2 = dec_layer_fwd(run, layer, x, e, B, T, Lk, src_m, trg_m, want_probs, keys=keys, live=live)
+    for i, layer in enumerate(dec.layers):
+        x, sv, p1, p2 = dec_layer_fwd(run, layer, x, e, B, T, Lk, src_m, trg_m, want_probs, keys=keys, live=live,
+                                      fold=None if fold is None else (fold, i))
         layers.append(sv)
         p1s.append(p1)
         p2s.append(p2)
     y, mean, rstd = ops.norm_fwd(x, dec.norm.alpha, dec.norm.bias, dec.norm.eps)
     saved = DecoderSaved(trg, z2, dconds, site_pe, layers, x, mean, rstd, B, T, Le, Lk, c2d, c2l,
-                         trg_mask_u8.u8 if isinstance(trg_mask_u8, ops.MaskBits) else trg_mask_u8, keys, live)
+                         trg_mask_u8.u8 if isinstance(trg_mask_u8, ops.MaskBits) else trg_mask_u8, keys, live, fold)
     if live is not None:
         return y, saved, p1s, p2s        # [Mc, d] COMPACT rows: the caller holds the plan and scatters what it needs
     return y.view(B, T, d), saved, p1s, p2s
 
 
 def decoder_trunk_bwd(dec, run: Run, sv: DecoderSaved, dy, G: GradSink, need_dz=True):
-    layers, keys, live_fwd = sv.layers, sv.keys, sv.live
+    layers, keys, live_fwd, fold = sv.layers, sv.keys, sv.live, sv.fold
     B, T, Le, Lk = sv.B, sv.T, sv.Le, sv.Lk
-    new_de = (lambda: _empty(B * Lk, d, dy)) if keys is None else (lambda: keys.empty(d))     # d(memory), maybe compact
     d, nc = dec.d_model, dec.nconds
+    dcols = d if fold is None else sv.z2.shape[1]          # d(memory), maybe compact -- with the fold d(rows of z)
+    new_de = (lambda: _empty(B * Lk, dcols, dy)) if keys is None else (lambda: keys.empty(dcols))
     # A decoder row whose incoming gradient is zero (padded target positions under the ignore_index loss: 56 % of
     # the rows at MOSES-like lengths) keeps a zero gradient through every layer below -- norm, linear, GELU and
     # dropout backward map a zero row to a zero row, attention gives zero dQ rows for zero dO rows -- PROVIDED no live
@@ -717,16 +747,17 @@ def decoder_trunk_bwd(dec, run: Run, sv: DecoderSaved, dy, G: GradSink, need_dz=
     ops.norm_bwd(g, sv.x_last, dec.norm.alpha, sv.mean, sv.rstd, G(dec.norm.alpha), G(dec.norm.bias), out=g,
                  eps=dec.norm.eps, live=live, drop=dr)
     gd = None if dr is None else gdbuf
-    de = new_de()
+    de = new_de() if (fold is None or need_dz) else None
     for i in range(len(layers) - 1, -1, -1):
         g, gd = dec_layer_bwd(run, dec.layers[i], layers[i], g, de, i == len(layers) - 1, G, live=live, gd=gd,
-                              gdbuf=gdbuf, below=layers[i - 1].ffn if i > 0 else None)
+                              gdbuf=gdbuf, below=layers[i - 1].ffn if i > 0 else None,
+                              fold=None if fold is None else (fold, i))
     run.kt = None
     if live is not None:
         g = live.scatter(g)                             # back to [B*T, d]: zero rows where nothing was live
     if len(dec.layers) == 0:
         de.zero_()
-    if keys is not None:
+    if keys is not None and de is not None:
         de = keys.scatter(de)                            # back to [B*Lk, d]: masked keys get no gradient
     # embedding side
     dcx = torch.empty(B, nc * d, dtype=torch.float32, device=g.device) if sv.c2d else None
@@ -736,6 +767,9 @@ def decoder_trunk_bwd(dec, run: Run, sv: DecoderSaved, dy, G: GradSink, need_dz=
         ops.small_linear_bwd(dcx, sv.dconds.contiguous(), G(dec.embed_cond2dec.weight),
                              G(dec.embed_cond2dec.bias))
     # memory side
+    if fold is not None:                 # de is d(z) already; fc_z's gradients from the layers' P_l and s_l
+        fold.finish(G(dec.fc_z.weight), G(dec.fc_z.bias))
+        return de.view(B, Le, -1) if need_dz else None
     dez = de
     if sv.c2l:
         dcl = torch.empty(B, nc * d, dtype=torch.float32, device=g.device)

@@ -403,11 +403,12 @@ def _plane_ptr(ws_):
 def linear_fwd(x2d, ws_: Sequence[torch.Tensor], bs: Sequence[Optional[torch.Tensor]],
                outs: Sequence[torch.Tensor], ldy: int, epi=EPI_BIAS, resid=None, pre=None,
                p=0.0, seed=0, site=0, splitk_ws: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
-               live=None):
+               live=None, planes=None):
     """y_s = epi(x @ w_s^T + b_s); outs are (views of) pre-allocated [M, nper] blocks with
     leading dimension ldy.  splitk_ws: force the skinny-M split-K kernel with this workspace; ws: a caller-owned
     workspace (>= gct_linear_fwd_ws_bytes) for the general path (fixed address: graph capture); live (LiveRows): the
-    rows are quad-compacted -- the dropout masks of the fused epilogues are drawn at the original coordinates."""
+    rows are quad-compacted -- the dropout masks of the fused epilogues are drawn at the original coordinates; planes:
+    (address of plane 0 of ws_[0], plane stride) of weights that are not registered (KvFold)."""
     M, K = x2d.shape
     nper = ws_[0].shape[0]
     w = _seg3(ws_)
@@ -421,7 +422,7 @@ def linear_fwd(x2d, ws_: Sequence[torch.Tensor], bs: Sequence[Optional[torch.Ten
     if splitk_ws is not None:      # skinny-M path (decode): split-K through this workspace; no planes, no quad map
         wp, pstride, wsb, quad_map, timed = None, 0, splitk_ws, None, contextlib.nullcontext()
     else:
-        wp, pstride = _plane_ptr(ws_)
+        wp, pstride = _plane_ptr(ws_) if planes is None else planes
         wsb = ws if ws is not None else (workspace(need, x2d.device) if need > 256 else None)
         quad_map = None if live is None else _p(live.quad_list)
         N = nper * len(ws_)
@@ -436,13 +437,13 @@ def linear_fwd(x2d, ws_: Sequence[torch.Tensor], bs: Sequence[Optional[torch.Ten
 
 
 def linear_dgrad(dys: Sequence[torch.Tensor], lddy: int, M: int, ws_: Sequence[torch.Tensor], dx,
-                 depi=DEPI_STORE, pre=None, p=0.0, seed=0, site=0, live=None, pre_full=False):
+                 depi=DEPI_STORE, pre=None, p=0.0, seed=0, site=0, live=None, pre_full=False, planes=None):
     nper, K = ws_[0].shape
     d = _seg3(dys)
     w = _seg3(ws_)
     _wait_pending(dx)
     with _Timed("gemm_dgrad", 2.0 * M * K * nper * len(ws_)):
-        wp, pstride = _plane_ptr(ws_)
+        wp, pstride = _plane_ptr(ws_) if planes is None else planes
         need = _ws_need("gct_linear_dgrad_ws_bytes", M, nper * len(ws_), K)
         wsb = workspace(need, dx.device) if need > 256 else None
         check(_L().gct_linear_dgrad(d[0], d[1], d[2], lddy, M, len(ws_), nper, w[0], w[1], w[2],
@@ -714,12 +715,13 @@ def linear_bwd_route(M, nseg, nper, K, lddy, ldx, ldw, lddx, depi=DEPI_STORE, al
 
 def linear_bwd(dys: Sequence[torch.Tensor], lddy: int, x2d, ws_: Sequence[torch.Tensor], dws: Sequence[torch.Tensor],
                dbs: Sequence[Optional[torch.Tensor]], dx, depi=DEPI_STORE, pre=None, p=0.0, seed=0, site=0, kt=None,
-               live=None, pre_full=False, M=None):
+               live=None, pre_full=False, M=None, planes=None):
     """linear_wgrad(dys, lddy, x2d, dws, dbs, kt) and linear_dgrad(dys, lddy, M, ws_, dx, depi, ...) of the same dY."""
     M = x2d.shape[0] if M is None else M
     if not PAIR_BWD or SIDE_ENABLED or M != x2d.shape[0] or torch.cuda.is_current_stream_capturing():
         linear_wgrad(dys, lddy, x2d, dws, dbs, kt=kt)
-        linear_dgrad(dys, lddy, M, ws_, dx, depi=depi, pre=pre, p=p, seed=seed, site=site, live=live, pre_full=pre_full)
+        linear_dgrad(dys, lddy, M, ws_, dx, depi=depi, pre=pre, p=p, seed=seed, site=site, live=live, pre_full=pre_full,
+                     planes=planes)
         return
     K = x2d.shape[1]
     nper, nseg = dws[0].shape[0], len(dws)
@@ -729,7 +731,7 @@ def linear_bwd(dys: Sequence[torch.Tensor], lddy: int, x2d, ws_: Sequence[torch.
     wws = kept_workspace(wneed, x2d.device)
     need = _ws_need("gct_linear_dgrad_ws_bytes", M, nper * nseg, K)
     wsb = workspace(need, dx.device) if need > 256 else None
-    wp, pstride = _plane_ptr(ws_)
+    wp, pstride = _plane_ptr(ws_) if planes is None else planes
     with _Timed("gemm_bwd", 4.0 * M * K * nper * nseg):
         check(_L().gct_linear_bwd(d[0], d[1], d[2], lddy, M, nseg, nper, _p(x2d), x2d.stride(0), K,
                                   dw[0], dw[1], dw[2], K, db[0], db[1], db[2], _p(wws), wneed,
@@ -740,6 +742,90 @@ def linear_bwd(dys: Sequence[torch.Tensor], lddy: int, x2d, ws_: Sequence[torch.
                                   None if live is None else _p(live.quad_list),
                                   pre.shape[0] if (live is not None and pre is not None and pre_full) else 0, _st()),
               "gct_linear_bwd")
+
+
+KV_FOLD_MAX_LAYERS = 16                        # GCT_KV_FOLD_MAX_LAYERS (include/gctplus_hip.h)
+
+
+class KvFold:
+    """Cross-attention K | V straight from the latent (gct_kv_fold_*): the decoder memory e = z W_z^T + b_z feeds
+    nothing but the k_linear | v_linear projections of the decoder layers, so layer l's K | V are
+    z A_l^T + c_l with A_l = W_kv,l W_z and c_l = W_kv,l b_z + b_kv,l.  One object per decoder forward: it holds A, c
+    and the bf16 planes of A for all layers (written by ONE gct_kv_fold_fwd call) and, for the backward, the stacked
+    weights and the buffers P_l = dkv_l^T z, s_l = colsum(dkv_l) that the layers' weight-gradient GEMMs fill.
+    kv: [(k_linear, v_linear)] of the layers (nn.Linear, weights [d, dm]); fc_z: nn.Linear(lat -> dm)."""
+
+    @staticmethod
+    def usable(kv, fc_z):
+        if not kv or len(kv) > KV_FOLD_MAX_LAYERS or fc_z.bias is None:
+            return False
+        d, dm = kv[0][0].weight.shape
+        al16 = lambda t: t.data_ptr() % 16 == 0 and getattr(t, "_gct_gview", t).data_ptr() % 16 == 0     # noqa: E731
+        return (d % 4 == 0 and dm % 4 == 0 and fc_z.weight.shape[1] % 4 == 0 and fc_z.weight.shape[0] == dm and
+                fc_z.weight.is_contiguous() and al16(fc_z.weight) and al16(fc_z.bias) and
+                all(m.weight.shape == (d, dm) and m.bias is not None and m.weight.is_contiguous() and al16(m.weight)
+                    for pair in kv for m in pair))
+
+    def __init__(self, kv, fc_z):
+        import ctypes
+        self.kv, self.fc_z = kv, fc_z
+        wz, bz = fc_z.weight, fc_z.bias
+        self.L, (self.d, self.dm), self.lat = len(kv), kv[0][0].weight.shape, wz.shape[1]
+        L, d, dm, lat = self.L, self.d, self.dm, self.lat
+        dev, R = wz.device, 2 * L * d
+        _chk(wz, "kv_fold.fc_z.weight")
+        f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)       # noqa: E731
+        self.wstack, self.a, self.c = f32(R, dm), f32(R, lat), f32(R)
+        self.p, self.s = f32(R, lat), f32(R)                                          # the backward's P_l and s_l
+        self.a_planes = torch.empty(3, R * lat, dtype=torch.int16, device=dev)
+        self.planes = (self.a_planes.data_ptr(), self.a_planes.stride(0))
+        mods = [m for pair in kv for m in pair]
+        wa = (ctypes.c_int64 * len(mods))(*[m.weight.data_ptr() for m in mods])
+        ba = (ctypes.c_int64 * len(mods))(*[m.bias.data_ptr() for m in mods])
+        need = int(_L().gct_kv_fold_ws_bytes(L, d, dm, lat))
+        wsb = workspace(need, dev)
+        wzp, wzs = _plane_ptr([wz])
+        check(_L().gct_kv_fold_fwd(L, ctypes.addressof(wa), ctypes.addressof(ba), d, dm, _p(wz), wzp, wzs, _p(bz), lat,
+                                   _p(self.wstack), _p(self.a), _p(self.c), _p(self.a_planes), self.a_planes.stride(0),
+                                   _p(wsb), wsb.numel() * 4, _st()), "gct_kv_fold_fwd")
+
+    def _rows(self, t, layer):
+        d = self.d
+        return [t[2 * layer * d:(2 * layer + 1) * d], t[(2 * layer + 1) * d:(2 * layer + 2) * d]]
+
+    def layer_planes(self, layer):
+        return (self.planes[0] + 2 * (2 * layer * self.d * self.lat), self.planes[1])
+
+    def fwd(self, layer, zc, outs, ldy):
+        """kvb_l = zc A_l^T + c_l into outs (k, v) of leading dimension ldy."""
+        linear_fwd(zc, self._rows(self.a, layer), self._rows(self.c, layer), outs, ldy, planes=self.layer_planes(layer))
+
+    def bwd(self, layer, dys, lddy, zc, dz, depi, M):
+        """P_l, s_l from dkv_l (dys) and the rows zc; dz (nullable) = / += dkv_l A_l."""
+        if dz is None:
+            linear_wgrad(dys, lddy, zc, self._rows(self.p, layer), self._rows(self.s, layer))
+        else:
+            linear_bwd(dys, lddy, zc, self._rows(self.a, layer), self._rows(self.p, layer), self._rows(self.s, layer),
+                       dz, depi=depi, M=M, planes=self.layer_planes(layer))
+
+    def wgrad_layer(self, layer, dwk, dwv, dbk, dbv):
+        """dW_kv,l = P_l W_z^T + s_l (x) b_z and db_kv,l = s_l, once the layer's slab reductions have run."""
+        if SIDE_ENABLED:
+            join_side()
+        d = self.d
+        check(_L().gct_kv_fold_wgrad(_p(self.p[2 * layer * d:]), _p(self.s[2 * layer * d:]), d, self.lat,
+                                     _p(self.fc_z.weight), _p(self.fc_z.bias), self.dm, _p(dwk), _p(dwv), _p(dbk),
+                                     _p(dbv), _st()), "gct_kv_fold_wgrad")
+
+    def finish(self, dwz, dbz):
+        """dW_z = sum_l W_kv,l^T P_l and db_z = sum_l W_kv,l^T s_l, after every layer's backward."""
+        if SIDE_ENABLED:
+            join_side()
+        linear_wgrad([self.wstack], self.dm, self.p, [dwz], [None])
+        need = int(_L().gct_kv_fold_ws_bytes(self.L, self.d, self.dm, self.lat))
+        wsb = workspace(need, dwz.device)
+        check(_L().gct_kv_fold_dbz(_p(self.wstack), _p(self.s), self.wstack.shape[0], self.dm, _p(dbz), _p(wsb),
+                                   wsb.numel() * 4, _st()), "gct_kv_fold_dbz")
 
 
 def dropout_bwd(dout2d, p, seed, site, out=None, live=None):

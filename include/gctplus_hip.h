@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 31
+#define GCT_ABI_VERSION 32
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -287,6 +287,34 @@ int64_t gct_gemm_x3_launches(void);
  * of the buffer starts at element offset o of every plane. */
 int gct_split_planes(const float* src, int64_t numel, uint16_t* planes, int64_t plane_stride,
                      void* stream);
+
+/* ---- cross-attention K | V straight from the latent (ABI 32) ------------------------------
+ * Model/vaetf.py:81: the decoder memory is e = fc_z(z) = z W_z^T + b_z (W_z [dm][lat]).  Where e feeds nothing but the
+ * k_linear | v_linear projections of the decoder layers (no cond2lat rows), layer l's K | V are an affine image of z:
+ *   kvb_l = z A_l^T + c_l,   A_l = W_kv,l W_z  [2d][lat],   c_l = W_kv,l b_z + b_kv,l,
+ * and with P_l = dkv_l^T z, s_l = colsum(dkv_l) (gct_linear_bwd / gct_linear_wgrad over the rows of z against A_l):
+ *   dW_kv,l = P_l W_z^T + s_l (x) b_z,  db_kv,l = s_l,  dW_z = sum_l W_kv,l^T P_l,  db_z = sum_l W_kv,l^T s_l.
+ * gct_kv_fold_fwd, for all layers of a step (w_addrs / b_addrs: HOST arrays of 2 * layers device addresses, k_linear
+ * then v_linear of each layer, weights [d][dm], biases [d]; b_addrs nullable):
+ *   wstack [layers * 2d][dm] = the weights stacked (one copy: the products below then are single launches);
+ *   c      [layers * 2d]     = wstack b_z + biases (the same launch, exact-fp32 dot products);
+ *   a      [layers * 2d][lat] = wstack W_z, as gct_linear_dgrad computes it (bf16x6 with wzp, the planes of W_z);
+ *   a_planes (nullable)      = gct_split_planes(a).
+ * ws >= gct_kv_fold_ws_bytes.  d, dm, lat multiples of 4; every buffer 16-byte aligned.
+ * gct_kv_fold_wgrad, one layer: p [2d][lat] and s [2d] as above -> dw0, dw1 [d][dm] (k_linear, v_linear) and
+ * db0, db1 [d], overwritten; fp32 fma chains over lat (no shorter than the bf16x6 kernels' chains: same error class).
+ * gct_kv_fold_dbz: dbz[dm] = wstack^T s over rows = layers * 2d rows (s: the stacked s_l), overwritten, deterministic.
+ * dW_z is gct_linear_wgrad of dY = wstack against X = the stacked P_l. */
+#define GCT_KV_FOLD_MAX_LAYERS 16
+int64_t gct_kv_fold_ws_bytes(int layers, int d, int dm, int lat);
+int gct_kv_fold_fwd(int layers, const int64_t* w_addrs, const int64_t* b_addrs, int d, int dm,
+                    const float* wz, const uint16_t* wzp, int64_t wz_plane_stride, const float* bz, int lat,
+                    float* wstack, float* a, float* c, uint16_t* a_planes, int64_t a_plane_stride,
+                    float* ws, int64_t ws_bytes, void* stream);
+int gct_kv_fold_wgrad(const float* p, const float* s, int d, int lat, const float* wz, const float* bz, int dm,
+                      float* dw0, float* dw1, float* db0, float* db1, void* stream);
+int gct_kv_fold_dbz(const float* wstack, const float* s, int64_t rows, int dm, float* dbz, float* ws,
+                    int64_t ws_bytes, void* stream);
 
 /* Zero-gradient rows.  Under an ignore_index loss the rows of padded target positions carry exactly zero
  * gradients through the whole decoder backward.  gct_nonzero_row_tiles lists, in ascending order, the 32-row

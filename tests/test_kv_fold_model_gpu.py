@@ -1,0 +1,70 @@
+"""Cross-attention K | V straight from the latent (engine.KV_FOLD) at the model level: the tiny vaetf of
+tests/test_model_gpu.py (2 layers, d_model 64, 4 heads, latent 16), B = 3 with source lengths 5, 9 and 1 of 12 (gaps
+inside a quad, a one-row sample, quads of padding only), flag on against flag off: loss, logits, mu, log_var and every
+parameter gradient at the tolerances test_model_gpu.py states and implements (atol 1e-4 / rtol 1e-4; gradients
+rtol 1e-3 + 1e-5 max|g| with its floor for the analytically zero k_linear.bias gradients; loss rtol 1e-5), on the
+compact row paths and on the dense ones, at dropout 0 and at dropout 0.1 with equal seeds (the masks are drawn at the
+original coordinates, so they match)."""
+import pytest
+import torch
+
+from gct_plus_amd import engine, ops, synthetic
+from tests.test_model_gpu import PAD, assert_close, build, grad_floor, run_fwd_loss, set_eps
+
+pytestmark = pytest.mark.gpu
+LENS, S = (5, 9, 1), 12
+FLAGS = ("COMPACT_BWD", "COMPACT_KV", "COMPACT_FWD", "COMPACT_ENC_KV")
+
+
+def _batch():
+    g = torch.Generator().manual_seed(5)
+    src = torch.full((len(LENS), S), PAD, dtype=torch.int64)
+    trg = torch.full((len(LENS), S + 2), PAD, dtype=torch.int64)
+    for i, n in enumerate(LENS):
+        toks = torch.randint(2, 28, (n,), generator=g)
+        src[i, :n] = toks
+        trg[i, 0], trg[i, 1:n + 1], trg[i, n + 1] = synthetic.SOS_ID, toks + 2, synthetic.EOS_ID
+    return {"src": src, "trg": trg}
+
+
+def _run(fold, dropout, compact):
+    keep = {k: getattr(engine, k) for k in FLAGS + ("KV_FOLD",)}
+    made, init = [], ops.KvFold.__init__
+
+    def counting(self, *a):
+        made.append(self)
+        init(self, *a)
+    try:
+        ops.KvFold.__init__ = counting
+        for k in FLAGS:
+            setattr(engine, k, compact)
+        engine.KV_FOLD = fold
+        model = build("vaetf", dropout=dropout, seed=2).train()
+        set_eps(model, torch.randn(len(LENS), S, 16, generator=torch.Generator().manual_seed(8)))
+        torch.manual_seed(77)
+        engine._SEED["base"] = None                        # the dropout seed counter restarts: every run draws the same masks
+        _, mol, mu, lv, _, loss, _, _ = run_fwd_loss(model, "vaetf", _batch(), 0.1)
+        loss.backward()
+        torch.cuda.synchronize()
+        assert len(made) == (1 if fold else 0)             # the step really took the path under test
+        return dict(loss=loss.detach(), logits=mol.detach(), mu=mu.detach(), log_var=lv.detach(),
+                    grads={n: p.grad.detach().clone() for n, p in model.named_parameters() if p.grad is not None},
+                    names=[n for n, _ in model.named_parameters()])
+    finally:
+        ops.KvFold.__init__ = init
+        for k, v in keep.items():
+            setattr(engine, k, v)
+
+
+@pytest.mark.parametrize("compact", [True, False], ids=["compact", "dense"])
+@pytest.mark.parametrize("dropout", [0.0, 0.1])
+def test_fold_on_against_off(dropout, compact):
+    off, on = _run(False, dropout, compact), _run(True, dropout, compact)
+    assert abs(on["loss"].item() - off["loss"].item()) <= 1e-5 * abs(off["loss"].item())
+    for key in ("logits", "mu", "log_var"):
+        assert_close(on[key], off[key], 1e-4, 1e-4, key)
+    assert on["names"] == off["names"] and set(on["grads"]) == set(off["grads"])
+    assert any(n.endswith("fc_z.weight") for n in on["grads"]) and any(n.endswith("fc_z.bias") for n in on["grads"])
+    floor = grad_floor(off["grads"].values())
+    for name, e in off["grads"].items():
+        assert_close(on["grads"][name], e, 1e-5 * float(e.abs().max()) + floor, 1e-3, "grad " + name)

@@ -128,6 +128,64 @@ def bwdpair_suite(reps, rounds=5):
                   f"model pair {route[6]:.1f} separate {route[7]:.1f} K-tiles", flush=True)
 
 
+def kvfold_suite(reps, rounds=5):
+    """Cross-attention K | V of one decoder layer from the 512-wide memory e (today: forward, dgrad + wgrad pair with
+    K = 512) against the same from the 128-wide latent rows z through A = W_kv W_z (folded: K = 128 forward, a 128-wide
+    dgrad with accumulate, a weight gradient whose X operand is 128 wide), alternated call by call in one process at
+    the headline's and fixed_len_80's memory row counts.  Also the pieces of the folded backward on their own: the
+    dgrad, the weight gradient as it stands and with the roles swapped (P^T = z^T dkv: the 128 side as the tile's 128
+    rows), and what the planner chose for each."""
+    dev = "cuda"
+    d, lat = 512, 128
+    N = 2 * d
+    for M in (18432, 40960):
+        e, z = torch.randn(M, d, device=dev), torch.randn(M, lat, device=dev)
+        wf, af = torch.randn(N * d, device=dev) * d ** -0.5, torch.randn(N * lat, device=dev) * lat ** -0.5
+        ops.register_planes(wf, ops.split_planes(wf))
+        ops.register_planes(af, ops.split_planes(af))
+        W = [wf[s * d * d:(s + 1) * d * d].view(d, d) for s in range(2)]
+        A = [af[s * d * lat:(s + 1) * d * lat].view(d, lat) for s in range(2)]
+        bs = [torch.randn(d, device=dev) for _ in range(2)]
+        kvb = torch.empty(M, N, device=dev)
+        outs = [kvb, kvb[:, d:]]
+        dkv = torch.randn(M, N, device=dev)
+        dys = [dkv, dkv[:, d:]]
+        de, dz = torch.zeros(M, d, device=dev), torch.zeros(M, lat, device=dev)
+        dW, dbs = [torch.empty(d, d, device=dev) for _ in range(2)], [torch.empty(d, device=dev) for _ in range(2)]
+        P = [torch.empty(d, lat, device=dev) for _ in range(2)]
+        PT = torch.empty(lat, N, device=dev)
+        cases = {
+            "fwd": (lambda: ops.linear_fwd(e, W, bs, outs, N), lambda: ops.linear_fwd(z, A, bs, outs, N)),
+            "bwd": (lambda: ops.linear_bwd(dys, N, e, W, dW, dbs, de, depi=ops.DEPI_ACCUM),
+                    lambda: ops.linear_bwd(dys, N, z, A, P, dbs, dz, depi=ops.DEPI_ACCUM)),
+        }
+        tot = [0.0, 0.0]
+        for kind, fns in cases.items():
+            per = ([], [])
+            for _ in range(rounds):
+                for i in (0, 1):
+                    per[i].append(timeit(fns[i], reps)[0])
+            t = [sorted(p) for p in per]
+            m0, m1 = t[0][rounds // 2], t[1][rounds // 2]
+            tot[0] += m0
+            tot[1] += m1
+            print(f"kvfold {kind} Mv={M}: today {m0*1e6:7.1f} us ({t[0][0]*1e6:.1f}..{t[0][-1]*1e6:.1f})  folded {m1*1e6:7.1f} us "
+                  f"({t[1][0]*1e6:.1f}..{t[1][-1]*1e6:.1f})  ratio {m1/m0:.3f}", flush=True)
+        print(f"kvfold trio Mv={M}: today {tot[0]*1e6:7.1f} us  folded {tot[1]*1e6:7.1f} us  saved per layer "
+              f"{(tot[0]-tot[1])*1e6:.1f} us", flush=True)
+        td = timeit(lambda: ops.linear_dgrad(dys, N, M, A, dz, depi=ops.DEPI_ACCUM), reps)[0]
+        rd = ops.gemm_last_route()
+        tw = timeit(lambda: ops.linear_wgrad(dys, N, z, P, dbs), reps)[0]
+        ts = timeit(lambda: ops.linear_wgrad([z], lat, dkv, [PT], [None]), reps)[0]
+        rf = ops.linear_fwd_route(M, lat, 2, d)
+        rp = ops.linear_bwd_route(M, 2, d, lat, N, lat, lat, lat, ops.DEPI_ACCUM)
+        rw, rs = ops.wgrad_route(M, 2, d, lat, N, lat), ops.wgrad_route(M, 1, lat, N, lat, N, want_bias=False)
+        print(f"kvfold pieces Mv={M}: dgrad N=128 {td*1e6:.1f} us route {rd[0]} launches {rd[5]}; wgrad X 128 wide "
+              f"{tw*1e6:.1f} us kind {rw[0]} s={rw[1]}; wgrad roles swapped {ts*1e6:.1f} us kind {rs[0]} s={rs[1]}; "
+              f"fwd K=128 route {rf[0]} tail {rf[2]}; pair plan paired={rp[0]} s={rp[1]} blocks={rp[4]}+{rp[5]} "
+              f"model pair {rp[6]:.1f} separate {rp[7]:.1f} K-tiles", flush=True)
+
+
 def decgemm_suite(reps):
     """Forward GEMMs of a KV-cached decode step (n rows) and of small training batches."""
     dev = "cuda"
@@ -252,6 +310,8 @@ if __name__ == "__main__":
         decgemm_suite(a.reps)
     if "bwdpair" in a.suite.split(","):
         bwdpair_suite(a.reps)
+    if "kvfold" in a.suite.split(","):
+        kvfold_suite(a.reps)
     if "epi" in a.suite.split(","):
         epi_suite(a.reps)
     if "attn" in a.suite:
