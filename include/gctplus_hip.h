@@ -300,10 +300,16 @@ int gct_split_planes(const float* src, int64_t numel, uint16_t* planes, int64_t 
  *   c      [layers * 2d]     = wstack b_z + biases (the same launch, exact-fp32 dot products);
  *   a      [layers * 2d][lat] = wstack W_z, as gct_linear_dgrad computes it (bf16x6 with wzp, the planes of W_z);
  *   a_planes (nullable)      = gct_split_planes(a).
- * ws >= gct_kv_fold_ws_bytes.  d, dm, lat multiples of 4; every buffer 16-byte aligned.
+ * ws >= gct_kv_fold_ws_bytes.  1 .. GCT_KV_FOLD_MAX_LAYERS layers; d, dm, lat multiples of 4; the weights, wz, bz, wstack
+ * and a 16-byte aligned (a_planes: 8, a_plane_stride % 4 == 0 and >= layers * 2d * lat; elements beyond that many of each
+ * plane are not written).
  * gct_kv_fold_wgrad, one layer: p [2d][lat] and s [2d] as above -> dw0, dw1 [d][dm] (k_linear, v_linear) and
  * db0, db1 [d], overwritten; fp32 fma chains over lat (no shorter than the bf16x6 kernels' chains: same error class).
+ * dm and lat multiples of 4, d any positive number (unlike gct_kv_fold_fwd); p, wz, bz, dw0, dw1 16-byte aligned.
  * gct_kv_fold_dbz: dbz[dm] = wstack^T s over rows = layers * 2d rows (s: the stacked s_l), overwritten, deterministic.
+ * Any rows, dm > 0, no alignment asked; ws_bytes >= ceil(rows / 32) * dm * 4 (gct_kv_fold_ws_bytes covers it).
+ * Layer count, widths, alignment, the weight table and the dbz workspace are checked before anything is launched: a call
+ * refused for one of them leaves its outputs untouched (a_planes' own checks are gct_split_planes', made after a is written).
  * dW_z is gct_linear_wgrad of dY = wstack against X = the stacked P_l. */
 #define GCT_KV_FOLD_MAX_LAYERS 16
 int64_t gct_kv_fold_ws_bytes(int layers, int d, int dm, int lat);

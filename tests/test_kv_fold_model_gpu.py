@@ -4,7 +4,9 @@ inside a quad, a one-row sample, quads of padding only), flag on against flag of
 parameter gradient at the tolerances test_model_gpu.py states and implements (atol 1e-4 / rtol 1e-4; gradients
 rtol 1e-3 + 1e-5 max|g| with its floor for the analytically zero k_linear.bias gradients; loss rtol 1e-5), on the
 compact row paths and on the dense ones, at dropout 0 and at dropout 0.1 with equal seeds (the masks are drawn at the
-original coordinates, so they match)."""
+original coordinates, so they match).  The same comparison at d_model 96 with 6 heads, latent 36 and 3 layers -- nothing a
+multiple of the fold kernels' 64-wide tiles or 32-wide K chunk -- in the default GEMM mode and once in fp32 mode; pvaetf
+and pscavaetf, whose memory carries cond2lat rows, construct no fold and equal the flag-off step bit for bit."""
 import pytest
 import torch
 
@@ -27,7 +29,9 @@ def _batch():
     return {"src": src, "trg": trg}
 
 
-def _run(fold, dropout, compact):
+def _run(fold, dropout, compact, mtype="vaetf", batch=None, folds=None, **over):
+    """folds: the KvFold objects the step must construct (default: one with the flag on, none with it off);
+    over: the model's geometry where it is not test_model_gpu.TINY"""
     keep = {k: getattr(engine, k) for k in FLAGS + ("KV_FOLD",)}
     made, init = [], ops.KvFold.__init__
 
@@ -39,14 +43,16 @@ def _run(fold, dropout, compact):
         for k in FLAGS:
             setattr(engine, k, compact)
         engine.KV_FOLD = fold
-        model = build("vaetf", dropout=dropout, seed=2).train()
-        set_eps(model, torch.randn(len(LENS), S, 16, generator=torch.Generator().manual_seed(8)))
+        model = build(mtype, dropout=dropout, seed=2, **over).train()
+        batch = _batch() if batch is None else batch
+        B, rows = batch["src"].shape[0], batch["src"].shape[1] + synthetic.n_conds(mtype)
+        set_eps(model, torch.randn(B, rows, over.get("latent_dim", 16), generator=torch.Generator().manual_seed(8)))
         torch.manual_seed(77)
         engine._SEED["base"] = None                        # the dropout seed counter restarts: every run draws the same masks
-        _, mol, mu, lv, _, loss, _, _ = run_fwd_loss(model, "vaetf", _batch(), 0.1)
+        _, mol, mu, lv, _, loss, _, _ = run_fwd_loss(model, mtype, batch, 0.1)
         loss.backward()
         torch.cuda.synchronize()
-        assert len(made) == (1 if fold else 0)             # the step really took the path under test
+        assert len(made) == ((1 if fold else 0) if folds is None else folds)   # the step really took the path under test
         return dict(loss=loss.detach(), logits=mol.detach(), mu=mu.detach(), log_var=lv.detach(),
                     grads={n: p.grad.detach().clone() for n, p in model.named_parameters() if p.grad is not None},
                     names=[n for n, _ in model.named_parameters()])
@@ -68,3 +74,52 @@ def test_fold_on_against_off(dropout, compact):
     floor = grad_floor(off["grads"].values())
     for name, e in off["grads"].items():
         assert_close(on["grads"][name], e, 1e-5 * float(e.abs().max()) + floor, 1e-3, "grad " + name)
+
+
+# ------------------------------------------------------------------------------------------------ off the 64-multiples
+# d_model 96 with 6 heads (d_k 16), latent 36, 3 layers: 2 d_model = 192 and d_model are no multiples of the 64-wide tile
+# of gct_kv_fold_wgrad, the k_linear | v_linear boundary lies inside a tile, the latent width leaves a ragged second K
+# chunk, and the 576 rows of the stack are 18 parts of gct_kv_fold_dbz (three to two lanes, two to the other six).
+EDGE = dict(N=3, d_model=96, dff=192, h=6, latent_dim=36)
+
+
+def _assert_on_matches_off(on, off):
+    """the comparison of test_fold_on_against_off, at its tolerances"""
+    assert abs(on["loss"].item() - off["loss"].item()) <= 1e-5 * abs(off["loss"].item())
+    for key in ("logits", "mu", "log_var"):
+        assert_close(on[key], off[key], 1e-4, 1e-4, key)
+    assert on["names"] == off["names"] and set(on["grads"]) == set(off["grads"])
+    assert any(n.endswith("fc_z.weight") for n in on["grads"]) and any(n.endswith("fc_z.bias") for n in on["grads"])
+    floor = grad_floor(off["grads"].values())
+    for name, e in off["grads"].items():
+        assert_close(on["grads"][name], e, 1e-5 * float(e.abs().max()) + floor, 1e-3, "grad " + name)
+
+
+@pytest.mark.parametrize("compact", [True, False], ids=["compact", "dense"])
+@pytest.mark.parametrize("dropout", [0.0, 0.1])
+def test_fold_on_against_off_at_the_tile_edges(dropout, compact):
+    _assert_on_matches_off(_run(True, dropout, compact, **EDGE), _run(False, dropout, compact, **EDGE))
+
+
+def test_fold_on_against_off_at_the_tile_edges_in_fp32_mode():
+    keep = ops.gemm_get_mode()
+    try:
+        ops.gemm_set_mode(ops.GEMM_F32)
+        _assert_on_matches_off(_run(True, 0.0, True, **EDGE), _run(False, 0.0, True, **EDGE))
+    finally:
+        ops.gemm_set_mode(keep)
+
+
+@pytest.mark.parametrize("mtype", ["pvaetf", "pscavaetf"])
+def test_models_with_cond2lat_rows_never_fold(mtype):
+    """Their memory carries cond2lat rows, which the fold cannot express: with the flag on no KvFold is constructed and
+    the step is the flag-off step bit for bit."""
+    batch = synthetic.make_dataset(len(LENS), S, mtype, seed=31)
+    on = _run(True, 0.1, True, mtype=mtype, batch=batch, folds=0)
+    off = _run(False, 0.1, True, mtype=mtype, batch=batch, folds=0)
+    assert torch.equal(on["loss"], off["loss"])
+    for key in ("logits", "mu", "log_var"):
+        assert torch.equal(on[key], off[key]), key
+    assert on["names"] == off["names"] and set(on["grads"]) == set(off["grads"]) and on["grads"]
+    for name, e in off["grads"].items():
+        assert torch.equal(on["grads"][name], e), name
