@@ -55,3 +55,19 @@ def train_opts(parser):
     parser.add_argument('-matmul_precision', type=str, default='highest', choices=['highest', 'high'],
                         help="nn.Linear GEMM arithmetic: 'highest' = the process default (bf16x6, fp32-class); "
                              "'high' = opt-in bf16x3, < 3.02 * 2^-16 |a*b| dropped per product, faster")
+    parser.add_argument('-max_grad_norm', type=max_grad_norm_flag, default=0.0,
+                        help="clip the global L2 norm of the gradient to this value on the device "
+                             "(clip_grad_norm_'s rule; a non-finite norm skips the step); 0 = off")
+
+
+def max_grad_norm_flag(text):
+    """A finite float >= 0 (0: clipping off); argparse reports anything else as a usage error."""
+    import argparse
+    import math
+    try:
+        value = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not a number")
+    if not math.isfinite(value) or value < 0:
+        raise argparse.ArgumentTypeError(f"{text!r}: a finite number >= 0 is required (0 = off)")
+    return value

@@ -24,6 +24,10 @@ trust region (decode.sequence_ppo -> gct_seq_ppo / gct_seq_ppo_bwd; `advantages`
 
     history = ppo_update(sampler, optimizer, out[-1], reward, epochs=4, clip=0.2)
 
+Both take max_grad_norm, the bound on the global L2 norm of an update's gradient that PPO and REINFORCE recipes carry:
+a FusedAdam clips on the device (optim.py: no host read, a non-finite norm skips the update), any other optimizer gets
+torch.nn.utils.clip_grad_norm_.
+
 A sharpened policy fills a sampled batch with copies of a few strings.  `sampler.decode_unique(..., return_rows=True)`
 draws k DISTINCT molecules per latent instead (stochastic beam search), and decode.sbs_importance_weights turns them into
 an unbiased estimate of the ordinary objective -- a loss weighted that way, every row scored once:
@@ -40,6 +44,49 @@ import copy
 import torch
 
 from ..decode import clip_pair
+from ..optim import FusedAdam, check_max_grad_norm
+
+
+class _GradClip:
+    """max_grad_norm of reinforce_step / ppo_update.  A FusedAdam clips on the device (its max_grad_norm is set for the
+    duration of the call and put back by restore(); a call that passes None leaves the optimizer's own setting in
+    force); any other optimizer gets torch.nn.utils.clip_grad_norm_ over its parameters between backward() and step().
+    active: whether anything clips.  After a step(), norm_and_clipped() is two device scalars for the caller's one
+    transfer: the pre-clip norm and 1.0 where the update was scaled down (0 < coef < 1; a step skipped for a norm that
+    is not finite reports that norm and 0)."""
+
+    def __init__(self, optimizer, max_grad_norm, what):
+        value = check_max_grad_norm(max_grad_norm, f"{what}: max_grad_norm")
+        self.optimizer, self.fused = optimizer, isinstance(optimizer, FusedAdam)
+        self.saved = optimizer.max_grad_norm if self.fused else None
+        self.value = value if value is not None else check_max_grad_norm(self.saved, f"{what}: optimizer.max_grad_norm")
+        self.active = self.value is not None
+        self._norm = None
+
+    def install(self):
+        if self.fused:
+            self.optimizer.max_grad_norm = self.value
+
+    def restore(self):
+        if self.fused:
+            self.optimizer.max_grad_norm = self.saved
+
+    def step(self):
+        if self.active and not self.fused:
+            params = [p for g in self.optimizer.param_groups for p in g["params"] if p.grad is not None]
+            self._norm = (torch.nn.utils.clip_grad_norm_(params, self.value).detach().float() if params
+                          else torch.zeros(()))                 # no gradient anywhere: norm 0, nothing clipped
+        self.optimizer.step()
+
+    def norm_and_clipped(self):
+        if self.fused and self.optimizer.clip_state is None:    # a generic-path FusedAdam without any gradient
+            return torch.zeros(()), torch.zeros(())
+        if self.fused:
+            norm, coef = self.optimizer.clip_state[0], self.optimizer.clip_state[1]
+        else:
+            norm = self._norm
+            coef = torch.where(torch.isfinite(norm), (self.value / (norm + 1e-6)).clamp(max=1.0), torch.zeros_like(norm))
+        return norm.clone(), ((coef > 0) & (coef < 1)).float()
 
 
 def reinforce_loss(logp, reward, baseline="mean"):
@@ -91,7 +138,8 @@ def regularised_loss(terms, reward, baseline="mean", entropy_coef=0.0, kl_coef=0
     return loss
 
 
-def reinforce_step(sampler, optimizer, rows, reward, baseline="mean", entropy_coef=0.0, kl_coef=0.0, prior=None):
+def reinforce_step(sampler, optimizer, rows, reward, baseline="mean", entropy_coef=0.0, kl_coef=0.0, prior=None,
+                   max_grad_norm=None):
     """One policy-gradient update of sampler.model on the decoded rows `rows` (a DecodedRows, or any argument tuple of
     Sampling.logp) with one reward per row: model.train(), sampler.logp(*rows), optimizer.zero_grad(set_to_none=True),
     reinforce_loss -> backward -> optimizer.step(), model.eval().  Returns dict(loss, mean_reward, mean_logp, tokens),
@@ -103,6 +151,13 @@ def reinforce_step(sampler, optimizer, rows, reward, baseline="mean", entropy_co
     and, with a prior, mean_kl (both per scored token: the batch sum / tokens) and mean_prior_logp (per sequence), read
     in the same one transfer.  kl_coef != 0 without a prior: ValueError before any device work.  With the defaults the
     step is the unregularised one, bit for bit.
+
+    max_grad_norm: a bound on the global L2 norm of the update's gradient (clip_grad_norm_'s rule).  A FusedAdam clips
+    on the device -- the value is set on the optimizer for this call and put back afterwards, an exception included;
+    None leaves an optimizer's own max_grad_norm in force -- and skips the update when the norm is not finite; any
+    other optimizer gets torch.nn.utils.clip_grad_norm_ over its parameters between backward() and step().  Whenever
+    clipping is active the result also holds grad_norm (pre-clip) and clipped (bool: the update was scaled down), read
+    in the same one transfer.  Not a finite number > 0: ValueError before any device work.
 
     The model runs in training mode, so its dropout is live in this forward: the logp of the step is not the eval-mode
     number `with_logp` reported for the same rows (build the model with dropout 0 where the two must agree).  The prior
@@ -122,17 +177,20 @@ def reinforce_step(sampler, optimizer, rows, reward, baseline="mean", entropy_co
     model = sampler.model
     if kl_coef != 0 and prior is None:
         raise ValueError("reinforce_step: kl_coef needs a prior (frozen_prior of the pretrained model)")
+    gclip = _GradClip(optimizer, max_grad_norm, "reinforce_step")
     reward = torch.as_tensor(reward, dtype=torch.float32)
     plain = entropy_coef == 0 and kl_coef == 0 and prior is None
     model.train()
+    gclip.install()
     try:
         scores = sampler.logp(*rows) if plain else sampler.policy_terms(*rows, prior=prior)
         optimizer.zero_grad(set_to_none=True)
         loss = (reinforce_loss(scores.logp, reward, baseline) if plain else
                 regularised_loss(scores, reward, baseline, entropy_coef, kl_coef))
         loss.backward()
-        optimizer.step()
+        gclip.step()
     finally:
+        gclip.restore()
         model.eval()
     dev = scores.logp.device
     tokens = scores.tokens.sum().float()
@@ -141,12 +199,16 @@ def reinforce_step(sampler, optimizer, rows, reward, baseline="mean", entropy_co
         stats.append(scores.entropy.detach().sum() / tokens)
         if prior is not None:
             stats += [scores.kl.detach().sum() / tokens, scores.prior_logp.mean()]
+    if gclip.active:
+        stats += [t.to(dev) for t in gclip.norm_and_clipped()]
     stats = torch.stack(stats).cpu().tolist()
     out = dict(loss=stats[0], mean_reward=stats[1], mean_logp=stats[2], tokens=int(stats[3]))
     if not plain:
         out["mean_entropy"] = stats[4]
         if prior is not None:
             out["mean_kl"], out["mean_prior_logp"] = stats[5], stats[6]
+    if gclip.active:
+        out["grad_norm"], out["clipped"] = stats[-2], bool(stats[-1])
     return out
 
 
@@ -195,7 +257,7 @@ def _row_slice(rows, lo, hi):
 
 def ppo_update(sampler, optimizer, rows, reward, epochs=4, clip=0.2, baseline="mean", normalize=False,
                old_token_logp=None, minibatch=None, target_kl=None, entropy_coef=0.0, kl_coef=0.0, prior=None,
-               train_mode=False):
+               train_mode=False, max_grad_norm=None):
     """Several policy updates of sampler.model on ONE scored batch: `epochs` passes over the decoded rows `rows` (a
     DecodedRows, or any argument tuple of Sampling.logp) with one reward per row, each pass minimising ppo_loss --
     PPO's clipped surrogate of every scored token's probability ratio against the sampling-time policy, which holds the
@@ -221,7 +283,11 @@ def ppo_update(sampler, optimizer, rows, reward, epochs=4, clip=0.2, baseline="m
     mean of the minibatches' losses), mean_surrogate (per sequence), clip_fraction (clipped tokens / scored tokens),
     approx_kl (the k3 estimate of KL(old || new) per scored token, each minibatch measured at its own forward), tokens;
     with entropy_coef != 0 mean_entropy, with a prior mean_kl (both per scored token) and mean_prior_logp (per
-    sequence)."""
+    sequence).
+
+    max_grad_norm as in reinforce_step, applied to every minibatch update; whenever clipping is active each epoch's
+    dict also holds grad_norm (the largest pre-clip norm over the epoch's minibatch updates) and clipped_updates (how
+    many of them were scaled down), read in the same one transfer."""
     model = sampler.model
     if kl_coef != 0 and prior is None:
         raise ValueError("ppo_update: kl_coef needs a prior (frozen_prior of the pretrained model)")
@@ -237,8 +303,10 @@ def ppo_update(sampler, optimizer, rows, reward, epochs=4, clip=0.2, baseline="m
         raise ValueError(f"{reward.numel()} rewards for {n} sequences")
     m = n if minibatch is None else min(int(minibatch), n)
     with_entropy = entropy_coef != 0
+    gclip = _GradClip(optimizer, max_grad_norm, "ppo_update")
     history = []
     model.train(bool(train_mode))
+    gclip.install()
     try:
         adv = advantages(reward.to(sampler.device), baseline, normalize).cpu()   # the device's arithmetic, as
         if old_token_logp is None:                                               # reinforce_loss's; checked on the host
@@ -247,7 +315,7 @@ def ppo_update(sampler, optimizer, rows, reward, epochs=4, clip=0.2, baseline="m
         for _ in range(epochs):
             if target_kl is not None and history and history[-1]["approx_kl"] > target_kl:
                 break
-            sums = None
+            sums = gnorm = None
             for lo in range(0, n, m):
                 hi = min(n, lo + m)
                 terms = sampler.ppo_terms(*_row_slice(rows, lo, hi), old_token_logp=old_token_logp[lo:hi],
@@ -255,16 +323,24 @@ def ppo_update(sampler, optimizer, rows, reward, epochs=4, clip=0.2, baseline="m
                 optimizer.zero_grad(set_to_none=True)
                 loss = ppo_loss(terms, entropy_coef, kl_coef)
                 loss.backward()
-                optimizer.step()
+                gclip.step()
                 part = [loss.detach().float() * (hi - lo), terms.surrogate.detach().sum(),
                         terms.clipped.sum().float(), terms.approx_kl.sum(), terms.tokens.sum().float()]
                 if with_entropy:
                     part.append(terms.entropy.detach().sum())
                 if prior is not None:
                     part += [terms.kl.detach().sum(), terms.prior_logp.sum()]
+                if gclip.active:                       # the clipped-update count rides at the end of the sums
+                    norm, clipped = (t.to(part[0].device) for t in gclip.norm_and_clipped())
+                    gnorm = norm if gnorm is None else torch.maximum(gnorm, norm)
+                    part.append(clipped)
                 part = torch.stack(part)
                 sums = part if sums is None else sums + part
+            if gclip.active:
+                sums = torch.cat([sums, gnorm.view(1)])
             s = sums.cpu().tolist()
+            if gclip.active:
+                s, clip_stats = s[:-2], s[-2:]
             tokens = s[4]
             out = dict(loss=s[0] / n, mean_surrogate=s[1] / n, clip_fraction=s[2] / tokens, approx_kl=s[3] / tokens,
                        tokens=int(tokens))
@@ -272,7 +348,10 @@ def ppo_update(sampler, optimizer, rows, reward, epochs=4, clip=0.2, baseline="m
                 out["mean_entropy"] = s[5] / tokens
             if prior is not None:
                 out["mean_kl"], out["mean_prior_logp"] = s[-2] / tokens, s[-1] / n
+            if gclip.active:
+                out["clipped_updates"], out["grad_norm"] = int(clip_stats[0]), clip_stats[1]
             history.append(out)
     finally:
+        gclip.restore()
         model.eval()
     return history

@@ -134,6 +134,11 @@ def run_epoch(args, model, optimizer, dataloader, current_step, beta, LOG, train
     if train and next(model.parameters()).is_cuda:
         from .. import ops
         ops.assert_no_skipped_row_gradients()     # (every earlier step's counter was read with the next step's row plan)
+    if train and getattr(optimizer, 'max_grad_norm', None) is not None and hasattr(optimizer, 'grad_norm_stats'):
+        clip = optimizer.grad_norm_stats(reset=True)      # one read per epoch, none per step
+        LOG.info(f'GRADCLIP(max_grad_norm {optimizer.max_grad_norm:g})\tsteps: {clip["steps"]}\t'
+                 f'clipped: {clip["clipped_steps"]}\tnon-finite: {clip["nonfinite_steps"]}\t'
+                 f'largest norm: {clip["max_norm"]:.5f}')
     if train:
         return history, current_step
     return history

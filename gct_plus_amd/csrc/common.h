@@ -85,7 +85,7 @@ __device__ __forceinline__ bool gct_drop_keep(uint4 bits, int e, uint32_t col, u
 
 // ---------------------------------------------------------------- wave helpers
 template <typename T>
-__device__ __forceinline__ T gct_wave_sum(T v) {             // float or int
+__device__ __forceinline__ T gct_wave_sum(T v) {             // float, double or int
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;

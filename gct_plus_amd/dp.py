@@ -20,7 +20,15 @@ Replaces torch.nn.parallel.DistributedDataParallel at train1.py:111-112 of the r
   * parameters that receive no gradient (Vaetf's dead encoder.fc_*, learned after the first
     backward) contribute zeros instead of tripping DDP's unused-parameter check.
 state_dict() keys carry the 'module.' prefix exactly like a DDP-wrapped reference model
-(Train/trainer1.py:42 saves from the wrapper; Model/build_model.py:70-71 strips it)."""
+(Train/trainer1.py:42 saves from the wrapper; Model/build_model.py:70-71 strips it).
+
+Gradient-norm clipping (FusedAdam(max_grad_norm=...)) needs no collective of its own.  Every bucket's all-reduce has
+been waited for before the backward returns, so when optimizer.step() runs the flat gradient buffer holds the same
+bytes on every rank: the rank mean (ReduceOp.AVG, or SUM scaled by 1/W here), or the rank sum under an optimizer whose
+grad_scale is 1/W.  Either way ||grad_scale * g|| is the norm of the MEAN gradient, the quantity DDP followed by
+clip_grad_norm_ clips.  Each rank computes it for itself with gct_grad_norm, which has a fixed summation order and no
+atomics: identical bytes give identical state words, so the ranks cannot disagree on coef or on a non-finite skip and
+their parameters stay bit-identical."""
 from __future__ import annotations
 
 import torch

@@ -1097,11 +1097,49 @@ def ce_bwd(logits2d, target, gout, pad_id):
 
 
 # ------------------------------------------------------------------------------- optimiser
-def adam_step(p, g, m, v, lr, b1, b2, eps, step, gscale=1.0, guard=True):
+def adam_step(p, g, m, v, lr, b1, b2, eps, step, gscale=1.0, guard=True, clip_state=None):
     """guard: the update is skipped ON THE DEVICE when a gradient has landed on a decoder row that the forward skipped
-    (skipped_row_gradients() != 0): the wrong gradient is never applied, and the next read-back raises."""
+    (skipped_row_gradients() != 0): the wrong gradient is never applied, and the next read-back raises.
+    clip_state: a state written by grad_norm (with the same gscale): the step consumes (g * gscale) * coef and is
+    skipped on the device when the norm was not finite.  None: the unclipped kernel, as ever."""
+    if clip_state is not None:
+        _chk_clip_state(clip_state, p.device)
     check(_L().gct_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, b1, b2, eps, step, gscale,
-                             _p(skipped_row_gradients()) if guard else None, _st()), "gct_adam_step")
+                             _p(skipped_row_gradients()) if guard else None, _p(clip_state), _st()), "gct_adam_step")
+
+
+GRAD_NORM_MAX_GRID = 2048          # workgroups of 256 lanes, each lane 4 float4 per trip (csrc/adam.hip's header)
+CLIP_STATE_WORDS = 8               # norm, coef, nonfinite, steps, clipped_steps, nonfinite_steps, largest norm, reserved
+
+
+def _chk_clip_state(state, device):
+    if (not isinstance(state, torch.Tensor) or state.dtype != torch.float32 or state.numel() != CLIP_STATE_WORDS
+            or not state.is_contiguous() or state.device != device):
+        raise ValueError(f"clip state: {CLIP_STATE_WORDS} contiguous float32 words on {device} (new_clip_state)")
+
+
+def new_clip_state(device):
+    """A zeroed clipping state (include/gctplus_hip.h: gct_grad_norm); view words 2-5 as int32 to read the counters."""
+    return torch.zeros(CLIP_STATE_WORDS, dtype=torch.float32, device=device)
+
+
+def grad_norm_ws(n, device):
+    """The slab of fp64 partials gct_grad_norm needs for n elements (the caller's, reusable for any smaller n)."""
+    return torch.empty(_L().gct_grad_norm_ws_bytes(int(n)) // 8, dtype=torch.float64, device=device)
+
+
+def grad_norm(g, state, ws, max_norm, gscale=1.0):
+    """state <- norm = |gscale| * ||g||_2, coef = min(1, max_norm / (norm + 1e-6)) and the running counters, on the
+    device, in two launches; g (flat fp32) is only read.  ws: grad_norm_ws(g.numel(), ...).  Nothing is returned and
+    nothing is read by the host."""
+    _chk(g, "grad_norm.g", torch.float32)
+    if not g.is_contiguous():
+        raise ValueError("grad_norm: g must be contiguous (one flat buffer)")
+    _chk_clip_state(state, g.device)
+    if ws.dtype != torch.float64 or ws.device != g.device or ws.numel() * 8 < _L().gct_grad_norm_ws_bytes(g.numel()):
+        raise ValueError("grad_norm: ws must come from grad_norm_ws(n >= g.numel(), g.device)")
+    check(_L().gct_grad_norm(_p(g), g.numel(), float(gscale), float(max_norm), _p(state), _p(ws), _st()),
+          "gct_grad_norm")
 
 
 # ---------------------------------------------------------------------------------- utility

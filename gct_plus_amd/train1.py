@@ -177,7 +177,9 @@ def main(rank, world_size, argv=None):
             kw = dict(allreduce=host_staged_allreduce, broadcast=host_staged_broadcast)
         model = FlatDataParallel(model, **kw)
     optimizer = FusedAdam(inner.parameters(), lr=args.lr, betas=(args.lr_beta1, args.lr_beta2),
-                          eps=args.lr_eps, model=inner)
+                          eps=args.lr_eps, model=inner, max_grad_norm=args.max_grad_norm or None)
+    if args.max_grad_norm:
+        LOG.info("gradient clipping: global L2 norm <= %g, on the device", args.max_grad_norm)
     if args.start_epoch > 1:
         from .Model.build_model import load_checkpoint
         ck = load_checkpoint(args.model_path)

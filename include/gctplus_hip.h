@@ -37,7 +37,7 @@ extern "C" {
 #define GCT_ERR_ARG (-1)  /* bad shape / alignment / null pointer            */
 #define GCT_ERR_HIP (-2)  /* a HIP runtime call failed (launch error)        */
 
-#define GCT_ABI_VERSION 32
+#define GCT_ABI_VERSION 33
 
 int gct_version(void);
 const char* gct_last_error(void);
@@ -633,11 +633,38 @@ int gct_chosen_logp(const float* logits, int V, const int64_t* ys, int64_t ld_ys
  * data-parallel mean). `step` is t (1-based, already incremented). */
 int gct_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1,
                   float b2, float eps, int64_t step, float gscale, const int32_t* skip_if_nonzero,
-                  void* stream);
+                  const float* clip_state, void* stream);
 /* skip_if_nonzero (nullable): a device-side guard: when *skip_if_nonzero != 0 at launch time nothing is updated (p, m,
  * v stay as they are).  The trainer passes the device counter of "gradient rows that fell on decoder rows the forward
  * had skipped" (gct_live_rows / gct_scatter_add_quads_check): a wrong gradient is then never applied, without a host
- * synchronisation in front of the update; the host raises at its next read-back.  NULL: no guard. */
+ * synchronisation in front of the update; the host raises at its next read-back.  NULL: no guard.
+ * clip_state (nullable; new in ABI 33): the 8-word state gct_grad_norm (below) wrote for the same g and gscale.  The
+ * step then consumes (g * gscale) * coef, in that order, with coef = word 1, and updates nothing when word 2 is set.
+ * coef == 1 leaves (g * gscale) exact: a step that did not need to clip is bit-identical to the step without a state.
+ * NULL: no clipping -- the kernel of the earlier versions; one kernel template serves both. */
+
+/* Global gradient-norm clipping, torch.nn.utils.clip_grad_norm_'s rule computed on the device:
+ *   norm = |gscale| * sqrt(sum g[k]^2)     (the L2 norm of the gradient Adam is about to see)
+ *   coef = min(1, max_norm / (norm + 1e-6))
+ * gct_grad_norm reads g [n] once (fp64 from the first product on: the result does not depend on n, on magnitudes or
+ * on the grid), leaves g as it is and writes `state`, 8 32-bit words on the device:
+ *   word 0  float  norm, pre-clip, of the scaled gradient
+ *   word 1  float  coef; 0 when the step is to be skipped
+ *   word 2  int32  nonfinite: 1 when norm is inf or NaN, else 0, for this step
+ *   word 3  int32  steps
+ *   word 4  int32  clipped_steps (finite steps with coef < 1)
+ *   word 5  int32  nonfinite_steps
+ *   word 6  float  the largest finite norm seen
+ *   word 7         reserved, written as 0
+ * Words 3-6 are running totals since the host last zeroed the state (the host zeroes all 8 words before first use).
+ * A norm beyond fp32's range (> 3.4e38) rounds to inf in word 0 and counts as non-finite, as an inf or a NaN in g does.
+ * Unlike torch, a non-finite norm skips the step: gct_adam_step, given the state, leaves p, m and v bit-unchanged.
+ * Two launches: at most 2048 workgroups write one fp64 partial each into ws (>= gct_grad_norm_ws_bytes(n) bytes, the
+ * caller's), one workgroup sums them in a fixed order -- no atomics, so the same bytes give the same state on every
+ * run and on every rank of a data-parallel job.  Nothing is read by the host; both launches can be captured.
+ * g, state, ws 16-B aligned; n >= 0 (n == 0: norm 0, coef 1; g may be NULL); max_norm finite and > 0. */
+int64_t gct_grad_norm_ws_bytes(int64_t n);
+int gct_grad_norm(const float* g, int64_t n, float gscale, float max_norm, float* state, void* ws, void* stream);
 
 /* --------------------------------------------------------- K11: KV-cached decode */
 /* Inference/sampling_tool.py:140-184 re-runs the whole decoder on ys[:, :i+1] each step; these

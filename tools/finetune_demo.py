@@ -11,6 +11,9 @@ the starting weights, which costs a second, forward-only decoder pass).  No coef
 --ppo-epochs K [--clip E]: Train/finetune.ppo_update instead -- K updates per sampled batch under PPO's clipped surrogate
 against the log-probabilities the batch was sampled with (one more forward-only pass per batch); the printed time is
 that of the whole update, and per epoch.
+--max-grad-norm C: every update's gradient is clipped to the global L2 norm C on the device (FusedAdam's max_grad_norm,
+through the max_grad_norm argument of the two functions); the rounds then also print the pre-clip norm.  No value is
+prescribed.
 
 --time-step: no sampling; --n fixed rows of MOSES-like lengths (clip(round(N(35, 8)), 15, 78) tokens + <eos> behind a
 scaffold prefix), --rounds reinforce_steps on them after two warm-up steps: the figure to put next to a bench.py
@@ -38,6 +41,8 @@ ap.add_argument("--kl-coef", type=float, default=0.0,
 ap.add_argument("--ppo-epochs", type=int, default=0,
                 help="K > 0: ppo_update with K epochs per sampled batch instead of one reinforce_step")
 ap.add_argument("--clip", type=float, default=0.2, help="PPO's clip: ratios are held in [1 - E, 1 + E]")
+ap.add_argument("--max-grad-norm", type=float, default=None,
+                help="bound on the global L2 norm of every update's gradient (FusedAdam clips on the device)")
 ap.add_argument("--time-step", action="store_true",
                 help="time reinforce_step (one ppo_update epoch with --ppo-epochs) on fixed rows of MOSES-like lengths")
 a = ap.parse_args()
@@ -74,9 +79,10 @@ def timed_step(rows, reward, **ppo):
     t0 = time.perf_counter()
     if a.ppo_epochs:
         stats = ppo_update(sampler, opt, rows, reward, **dict(dict(epochs=a.ppo_epochs), **ppo), clip=a.clip,
-                           entropy_coef=a.entropy_coef, kl_coef=a.kl_coef, prior=prior)
+                           entropy_coef=a.entropy_coef, kl_coef=a.kl_coef, prior=prior, max_grad_norm=a.max_grad_norm)
     else:
-        stats = reinforce_step(sampler, opt, rows, reward, entropy_coef=a.entropy_coef, kl_coef=a.kl_coef, prior=prior)
+        stats = reinforce_step(sampler, opt, rows, reward, entropy_coef=a.entropy_coef, kl_coef=a.kl_coef, prior=prior,
+                               max_grad_norm=a.max_grad_norm)
     torch.cuda.synchronize()
     return stats, (time.perf_counter() - t0) * 1e3
 
@@ -160,6 +166,8 @@ before = evaluate()
 reg = f", entropy_coef {a.entropy_coef}, kl_coef {a.kl_coef}" if a.entropy_coef or a.kl_coef else ""
 if a.ppo_epochs:
     reg += f", {a.ppo_epochs} PPO epochs per round, clip {a.clip}"
+if a.max_grad_norm is not None:
+    reg += f", max_grad_norm {a.max_grad_norm:g}"
 print(f"{'full-size' if a.full else 'tiny'} {mtype}, {a.n} molecules per round, lr {a.lr}{reg}: evaluation batch before "
       f"fine-tuning: well-formed {before[0]:.3f}, {before[1]} distinct strings, entropy {before[2]:.3f} per token",
       flush=True)
@@ -171,11 +179,16 @@ for k in range(a.rounds):
     if a.ppo_epochs:
         last = stats[-1]
         more = "".join(f"  {key[5:]} {last[key]:7.4f}" for key in ("mean_entropy", "mean_kl") if key in last)
+        if "grad_norm" in last:
+            more += (f"  grad norm {max(s['grad_norm'] for s in stats):8.4f}  clipped updates "
+                     f"{sum(s['clipped_updates'] for s in stats)}")
         print(f"round {k:3d}: well-formed {float(reward.mean()):.3f}  loss {stats[0]['loss']:8.4f} -> {last['loss']:8.4f}  "
               f"clipped {last['clip_fraction']:.3f}  approx_kl {last['approx_kl']:.5f}{more}  update {dt:7.2f} ms "
               f"({dt / len(stats):.2f} per epoch)", flush=True)
         continue
     more = "".join(f"  {key[5:]} {stats[key]:7.4f}" for key in ("mean_entropy", "mean_kl") if key in stats)
+    if "grad_norm" in stats:
+        more += f"  grad norm {stats['grad_norm']:8.4f}{' (clipped)' if stats['clipped'] else ''}"
     print(f"round {k:3d}: well-formed {stats['mean_reward']:.3f}  mean logp {stats['mean_logp']:8.3f}  loss "
           f"{stats['loss']:8.4f}{more}  step {dt:7.2f} ms", flush=True)
 after = evaluate()

@@ -289,6 +289,46 @@ def bw_suite(reps):
     v.abs_()
     med, _ = timeit(lambda: ops.adam_step(p, g, m, v, 1e-4, 0.9, 0.98, 1e-9, 3), reps)
     print(f"adam    : {med*1e6:7.1f} us {28*n/med/1e9:7.0f} GB/s", flush=True)
+    clip_lines(p, g, m, v, reps)
+
+
+def clip_lines(p, g, m, v, reps):
+    """gct_grad_norm (both launches) and the clipped Adam step as FusedAdam(max_grad_norm=...) issues them: in turn,
+    each between its own pair of events, behind an untimed plain Adam launch -- its 1.25 GB push the gradient buffer
+    out of the Infinity Cache, as a training step's backward does, and while it runs the host queues the timed
+    launches, so the events see the device's time and not the host's launch latency."""
+    n = g.numel()
+    state, ws = ops.new_clip_state(g.device), ops.grad_norm_ws(n, g.device)
+    max_norm = 0.5 * float(g.double().norm())
+    tn, ta = [], []
+    for it in range(3 + reps):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ops.adam_step(p, g, m, v, 1e-4, 0.9, 0.98, 1e-9, 3)
+        ev[0].record()
+        ops.grad_norm(g, state, ws, max_norm)
+        ev[1].record()
+        ops.adam_step(p, g, m, v, 1e-4, 0.9, 0.98, 1e-9, 3, clip_state=state)
+        ev[2].record()
+        ev[2].synchronize()
+        if it >= 3:
+            tn.append(ev[0].elapsed_time(ev[1]) * 1e-3)
+            ta.append(ev[1].elapsed_time(ev[2]) * 1e-3)
+    tn.sort()
+    ta.sort()
+    mn, ma = tn[len(tn) // 2], ta[len(ta) // 2]
+    print(f"gradnorm: {mn*1e6:7.1f} us {4*n/mn/1e9:7.0f} GB/s", flush=True)
+    print(f"adamclip: {ma*1e6:7.1f} us {28*n/ma/1e9:7.0f} GB/s", flush=True)
+
+
+def adam_suite(reps):
+    """The three optimizer lines alone, three alternated rounds."""
+    n = 44_514_334
+    p, g, m, v = (torch.randn(n, device="cuda") for _ in range(4))
+    v.abs_()
+    for _ in range(3):
+        med, _ = timeit(lambda: ops.adam_step(p, g, m, v, 1e-4, 0.9, 0.98, 1e-9, 3), reps)
+        print(f"adam    : {med*1e6:7.1f} us {28*n/med/1e9:7.0f} GB/s", flush=True)
+        clip_lines(p, g, m, v, reps)
 
 
 if __name__ == "__main__":
@@ -319,3 +359,5 @@ if __name__ == "__main__":
         attn_suite(a.reps, fixed=True)
     if "bw" in a.suite:
         bw_suite(a.reps)
+    if "adam" in a.suite.split(","):
+        adam_suite(a.reps)
