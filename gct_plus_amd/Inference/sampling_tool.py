@@ -272,25 +272,32 @@ class Sampling:
                 raise ValueError("decode: beam search takes prefixes of one length (see sample_multiple_smiles)")
             return self.decode_beams(zs, ys, src_mask, dconds)[0][:, 0]
         self.seed += 1
+        zs, ys, src_mask, dconds = self._start_rows(zs, ys, src_mask, dconds)
+        kw = dict(algo=self.decode_algo, seed=self.seed, use_graphs=self.use_graphs, prefix_lens=prefix_lens,
+                  top_k=self.top_k, top_p=self.top_p, temperature=self.temperature, return_logp=self.with_logp,
+                  grammar=self.grammar)
+        if self.stream_rows is not None:
+            out = self.kv.generate_stream(ys, self.max_strlen, **kw)
+            res = (out[0], out[3].cpu()) if self.with_logp else out[0]
+        else:
+            out = self.kv.generate(ys, self.max_strlen, **kw)
+            res = (out[0], out[2].cpu()) if self.with_logp else out
+        return self._with_rows(res, zs, ys, src_mask, dconds, prefix_lens) if return_rows else res
+
+    def _start_rows(self, zs, ys, src_mask, dconds, beams=None):
+        """THE way a decode's inputs reach the decoder: the four tensors to the sampler's device (returned), and the
+        decoder's rows started for them -- beams=k: k rows per sample in step (KVDecoder.start(beams=k)); None: the
+        sampler's own rows, the pool of start_stream with stream_rows.  The rows are laid out for the prefix +
+        max_strlen tokens, capped at the rows of the decoder's positional table, of which use_cond2dec spends n_c
+        (KVDecoder.off) on the condition tokens."""
         zs, ys, src_mask = zs.to(self.device), ys.to(self.device), src_mask.to(self.device)
         dconds = None if dconds is None else dconds.to(self.device)
-        total = ys.size(1) + self.max_strlen
-        if self.stream_rows is not None:
-            self.kv.start_stream(zs, src_mask, dconds, rows=self.stream_rows, max_total_len=min(200, total))
-            out = self.kv.generate_stream(ys, self.max_strlen, algo=self.decode_algo, seed=self.seed,
-                                          use_graphs=self.use_graphs, prefix_lens=prefix_lens, top_k=self.top_k,
-                                          top_p=self.top_p, temperature=self.temperature, return_logp=self.with_logp,
-                                          grammar=self.grammar)
-            res = (out[0], out[3].cpu()) if self.with_logp else out[0]
-            return self._with_rows(res, zs, ys, src_mask, dconds, prefix_lens) if return_rows else res
-        # the positional table has 200 rows, of which use_cond2dec spends n_c on the condition tokens
-        self.kv.start(zs, src_mask, dconds, max_total_len=min(200 - self.kv.off, total))
-        out = self.kv.generate(ys, self.max_strlen, algo=self.decode_algo, seed=self.seed,
-                               use_graphs=self.use_graphs, prefix_lens=prefix_lens, top_k=self.top_k,
-                               top_p=self.top_p, temperature=self.temperature, return_logp=self.with_logp,
-                               grammar=self.grammar)
-        res = (out[0], out[2].cpu()) if self.with_logp else out
-        return self._with_rows(res, zs, ys, src_mask, dconds, prefix_lens) if return_rows else res
+        room = min(self.model.decoder.pe.pe.shape[1] - self.kv.off, ys.size(1) + self.max_strlen)
+        if beams is None and self.stream_rows is not None:
+            self.kv.start_stream(zs, src_mask, dconds, rows=self.stream_rows, max_total_len=room)
+        else:
+            self.kv.start(zs, src_mask, dconds, max_total_len=room, beams=beams or 1)
+        return zs, ys, src_mask, dconds
 
     def _with_rows(self, res, zs, ys0, src_mask, dconds, prefix_lens):
         """decode's result with the DecodedRows of the call appended."""
@@ -368,15 +375,16 @@ class Sampling:
         return (pack_prefixes(rows, self.pad_id)[0], torch.as_tensor([len(c) + 2 for c in sca], dtype=torch.long),
                 [len(c) + 1 for c in sca])
 
-    def _score_smiles(self, ys, lens, extras, zs, dconds, encode):
-        """zs None: the deterministic reconstruction score -- the latent is the encoder's MEAN of the same molecule
-        (encode() -> (src, src_mask, econds)) and the mask the encoder's.  zs given: latent_setup_rows' mask rule."""
+    def _score_smiles(self, smiles_list, scaffold_list, conds, zs, transform=True):
+        """What the types' score_smiles share (scaffolds / raw conds: None where the type has none).  zs None: the
+        deterministic reconstruction score -- the latent is the encoder's MEAN of the same molecule and the mask the
+        encoder's (_encode_endpoints).  zs given: latent_setup_rows' mask rule."""
+        ys, lens, extras = self._score_targets(smiles_list, scaffold_list)
         if zs is None:
-            src, src_mask, econds = encode()
-            zs = self.model.encode(src=src, src_mask=src_mask, econds=econds)[1]
+            zs, _, src_mask = self._encode_endpoints(smiles_list, scaffold_list, conds, transform)
         else:
             zs, _, src_mask = latent_setup_rows(extras, zs, None, self.latent_dim, self.sample_toklen, self.sample_z)
-        return self.score(zs, ys, src_mask, dconds, lens)
+        return self.score(zs, ys, src_mask, self._conds(conds, transform), lens)
 
     @torch.no_grad()
     def decode_beams(self, zs, ys, src_mask, dconds=None, beam_size=None, alpha=None):
@@ -386,10 +394,7 @@ class Sampling:
             raise ValueError("decode_beams: beam search takes no grammar, and this sampler was built with well_formed=True")
         k = self.beam_size if beam_size is None else beam_size
         check_beam_size(k, self.model.out.weight.shape[0])
-        zs, ys, src_mask = zs.to(self.device), ys.to(self.device), src_mask.to(self.device)
-        dconds = None if dconds is None else dconds.to(self.device)
-        total = ys.size(1) + self.max_strlen
-        self.kv.start(zs, src_mask, dconds, max_total_len=min(200 - self.kv.off, total), beams=k)
+        ys = self._start_rows(zs, ys, src_mask, dconds, beams=k)[1]
         return self.kv.generate_beam(ys, k, self.max_strlen, alpha=self.beam_alpha if alpha is None else alpha,
                                      use_graphs=self.use_graphs)
 
@@ -409,10 +414,7 @@ class Sampling:
         k = self.beam_size if k is None else k
         check_beam_size(k, self.model.out.weight.shape[0])
         self.seed += 1
-        zs, ys, src_mask = zs.to(self.device), ys.to(self.device), src_mask.to(self.device)
-        dconds = None if dconds is None else dconds.to(self.device)
-        total = ys.size(1) + self.max_strlen
-        self.kv.start(zs, src_mask, dconds, max_total_len=min(200 - self.kv.off, total), beams=k)
+        zs, ys, src_mask, dconds = self._start_rows(zs, ys, src_mask, dconds, beams=k)
         out = self.kv.generate_sbs(ys, k, self.max_strlen, seed=self.seed, use_graphs=self.use_graphs)
         if not return_rows:
             return out
@@ -437,16 +439,25 @@ class Sampling:
                 raise ValueError(f"{what}: {n} molecules for a property array of shape {list(props.shape)}")
         return scaffolds, props
 
+    def _encoder_inputs(self, smiles, scaffolds=None, props=None, transform=True):
+        """THE statement of what the encoder sees for this model type, on the sampler's device: (src, src_mask, econds).
+        src int64 [n, L]: the tokens of scaffold<sep>smiles (uses_scaffold) or of smiles, right-padded; econds [n, n_c]:
+        the raw properties through `_conds` (uses_props), else None; src_mask bool [n, 1, n_c + L]: the condition rows'
+        flags, then the tokens' (get_src_mask).  An argument the type does not use is ignored."""
+        strings = [b + "<sep>" + a for a, b in zip(smiles, scaffolds)] if self.uses_scaffold else smiles
+        src = self.tokenize_smiles(strings).to(self.device)
+        econds = self._conds(props, transform).to(self.device) if self.uses_props else None
+        return src, get_src_mask(src, self.pad_id, econds), econds
+
     def _encode_endpoints(self, smiles, scaffolds, props, transform):
-        """One encode_smiles of the molecules -> (mu, log_var [n, L_e, latent], src_mask [n, 1, L_e] the encoder's own
+        """One encoder forward of the molecules -> (mu, log_var [n, L_e, latent], src_mask [n, 1, L_e] the encoder's own
         mask: condition rows, scaffold, <sep>, tokens)."""
-        args = [smiles] + ([scaffolds] if self.uses_scaffold else []) + ([props] if self.uses_props else [])
-        _, mu, log_var = self.encode_smiles(*args, **({"transform": transform} if self.uses_props else {}))
-        src = self.tokenize_smiles([b + "<sep>" + a for a, b in zip(smiles, scaffolds)] if self.uses_scaffold else smiles)
-        mask = get_src_mask(src, self.pad_id, None if props is None else torch.zeros(len(smiles), props.shape[1]))
-        return mu, log_var, mask
+        src, src_mask, econds = self._encoder_inputs(smiles, scaffolds, props, transform)
+        _, mu, log_var = self.model.encode(src=src, src_mask=src_mask, econds=econds)
+        return mu, log_var, src_mask
 
     def _conds(self, props, transform):
+        """Raw property rows -> the fp32 conditions the model takes (through the scaler with transform); None: None."""
         if props is None:
             return None
         return self.transform(props) if transform else torch.as_tensor(props, dtype=torch.float32)
@@ -623,8 +634,8 @@ class VaetfSampling(Sampling):
         return self._interpolate(src0, src1, n_interpolations, **kw)
 
     def encode_smiles(self, smiles_list):
-        src = self.tokenize_smiles(smiles_list).to(self.device)
-        return self.model.encode(src=src, src_mask=get_src_mask(src, self.pad_id))
+        src, src_mask, econds = self._encoder_inputs(smiles_list)
+        return self.model.encode(src=src, src_mask=src_mask, econds=econds)
 
     def sample_smiles(self, n, zs=None, toklen=None, return_rows=False):
         zs, toklen, src_mask = self._latent_setup(n, zs, toklen)
@@ -633,12 +644,7 @@ class VaetfSampling(Sampling):
 
     def score_smiles(self, smiles_list, zs=None) -> Scores:
         """log p(<sos> smiles <eos> | z): z = zs [n, L_e, latent], or (None) the encoder's mean of the same molecule."""
-        ys, lens, extras = self._score_targets(smiles_list)
-
-        def encode():
-            src = self.tokenize_smiles(smiles_list).to(self.device)
-            return src, get_src_mask(src, self.pad_id), None
-        return self._score_smiles(ys, lens, extras, zs, None, encode)
+        return self._score_smiles(smiles_list, None, None, zs)
 
 
 class CvaetfSampling(Sampling):
@@ -649,13 +655,12 @@ class CvaetfSampling(Sampling):
         return self._interpolate(src0, src1, n_interpolations, props0=props0, props1=props1, transform=transform, **kw)
 
     def encode_smiles(self, smiles_list, econds, transform=True):
-        src = self.tokenize_smiles(smiles_list).to(self.device)
-        econds = (self.transform(econds) if transform else torch.as_tensor(econds, dtype=torch.float32)).to(self.device)
-        return self.model.encode(src=src, src_mask=get_src_mask(src, self.pad_id, econds), econds=econds)
+        src, src_mask, econds = self._encoder_inputs(smiles_list, None, econds, transform)
+        return self.model.encode(src=src, src_mask=src_mask, econds=econds)
 
     def sample_smiles(self, dconds, zs=None, toklen=None, transform=True, return_rows=False):
         n = len(dconds)
-        dconds = self.transform(dconds) if transform else torch.as_tensor(dconds, dtype=torch.float32)
+        dconds = self._conds(dconds, transform)
         if zs is None and toklen is not None:
             toklen = [t + self.cond_dim for t in toklen]
         zs, toklen, src_mask = self._latent_setup(n, zs, toklen)
@@ -664,13 +669,7 @@ class CvaetfSampling(Sampling):
 
     def score_smiles(self, smiles_list, conds, zs=None, transform=True) -> Scores:
         """log p(<sos> smiles <eos> | z, conds); zs None: the encoder's mean of (smiles, conds)."""
-        ys, lens, extras = self._score_targets(smiles_list)
-        conds = self.transform(conds) if transform else torch.as_tensor(conds, dtype=torch.float32)
-
-        def encode():
-            src, econds = self.tokenize_smiles(smiles_list).to(self.device), conds.to(self.device)
-            return src, get_src_mask(src, self.pad_id, econds), econds
-        return self._score_smiles(ys, lens, extras, zs, conds, encode)
+        return self._score_smiles(smiles_list, None, conds, zs, transform)
 
 
 class ScaVaeSampling(Sampling):
@@ -681,8 +680,8 @@ class ScaVaeSampling(Sampling):
         return self._interpolate(src0, src1, n_interpolations, scaffolds0=scaffolds0, scaffolds1=scaffolds1, **kw)
 
     def encode_smiles(self, smiles_list, scaffold_list):
-        src = self.tokenize_smiles([b + "<sep>" + a for a, b in zip(smiles_list, scaffold_list)]).to(self.device)
-        return self.model.encode(src=src, src_mask=get_src_mask(src, self.pad_id))
+        src, src_mask, econds = self._encoder_inputs(smiles_list, scaffold_list)
+        return self.model.encode(src=src, src_mask=src_mask, econds=econds)
 
     def sample_smiles(self, n, scaffold, zs=None, toklen=None, return_rows=False):
         sca_ids = self.smi_to_id(scaffold)
@@ -693,12 +692,7 @@ class ScaVaeSampling(Sampling):
     def score_smiles(self, smiles_list, scaffold_list, zs=None) -> Scores:
         """log p(smiles <eos> | <sos> scaffold <sep>, z), one scaffold per molecule (the prefix is not scored); zs None:
         the encoder's mean of scaffold <sep> smiles."""
-        ys, lens, extras = self._score_targets(smiles_list, scaffold_list)
-
-        def encode():
-            src = self.tokenize_smiles([b + "<sep>" + a for a, b in zip(smiles_list, scaffold_list)]).to(self.device)
-            return src, get_src_mask(src, self.pad_id), None
-        return self._score_smiles(ys, lens, extras, zs, None, encode)
+        return self._score_smiles(smiles_list, scaffold_list, None, zs)
 
     def sample_multiple_smiles(self, scaffolds, zs=None, toklen=None, return_rows=False):
         """One molecule per scaffold, all rows in one batch: row r decodes as sample_smiles(1, scaffolds[r]) with z
@@ -716,14 +710,13 @@ class PscavaetfSampling(Sampling):
                                  props0=props0, props1=props1, transform=transform, **kw)
 
     def encode_smiles(self, smiles_list, scaffold_list, econds, transform=True):
-        src = self.tokenize_smiles([b + "<sep>" + a for a, b in zip(smiles_list, scaffold_list)]).to(self.device)
-        econds = (self.transform(econds) if transform else torch.as_tensor(econds, dtype=torch.float32)).to(self.device)
-        return self.model.encode(src=src, src_mask=get_src_mask(src, self.pad_id, econds), econds=econds)
+        src, src_mask, econds = self._encoder_inputs(smiles_list, scaffold_list, econds, transform)
+        return self.model.encode(src=src, src_mask=src_mask, econds=econds)
 
     def sample_smiles(self, dconds, scaffold, zs=None, toklen=None, transform=True, return_rows=False):
         """prefix = <sos> scaffold <sep> (sampling_tool.py:452-498)."""
         n = len(dconds)
-        dconds = self.transform(dconds) if transform else torch.as_tensor(dconds, dtype=torch.float32)
+        dconds = self._conds(dconds, transform)
         sca_ids = self.smi_to_id(scaffold)
         zs, toklen, src_mask = self._latent_setup(n, zs, toklen, extra=len(sca_ids) + 1)
         outs = self.decode(zs, self.init_y(n, True, sca_ids, True), src_mask, dconds, **_rows_kw(return_rows))
@@ -732,14 +725,7 @@ class PscavaetfSampling(Sampling):
     def score_smiles(self, smiles_list, scaffold_list, conds, zs=None, transform=True) -> Scores:
         """log p(smiles <eos> | <sos> scaffold <sep>, z, conds), one scaffold per molecule; zs None: the encoder's mean
         of (scaffold <sep> smiles, conds)."""
-        ys, lens, extras = self._score_targets(smiles_list, scaffold_list)
-        conds = self.transform(conds) if transform else torch.as_tensor(conds, dtype=torch.float32)
-
-        def encode():
-            src = self.tokenize_smiles([b + "<sep>" + a for a, b in zip(smiles_list, scaffold_list)]).to(self.device)
-            econds = conds.to(self.device)
-            return src, get_src_mask(src, self.pad_id, econds), econds
-        return self._score_smiles(ys, lens, extras, zs, conds, encode)
+        return self._score_smiles(smiles_list, scaffold_list, conds, zs, transform)
 
     def sample_multiple_smiles(self, dconds, scaffolds, zs=None, toklen=None, transform=True, return_rows=False):
         """The reference's intended sample_multiple_smiles (sampling_tool.py, commented out there): row r has the
@@ -747,7 +733,7 @@ class PscavaetfSampling(Sampling):
         sample_smiles(dconds[r:r+1], scaffolds[r]) would."""
         if len(dconds) != len(scaffolds):
             raise ValueError(f"{len(dconds)} property rows for {len(scaffolds)} scaffolds")
-        dconds = self.transform(dconds) if transform else torch.as_tensor(dconds, dtype=torch.float32)
+        dconds = self._conds(dconds, transform)
         return self._sample_multiple(scaffolds, zs, toklen, dconds, return_rows)
 
 

@@ -8,7 +8,7 @@ same token ids come out of
   * `start`:   once per sequence, the cross-attention operands: the key / value projections of the memory fc_z(z) are
                FOLDED into the query / output projections (`_fold_cross`), so a step attends over the latent rows z
                themselves (gct_attn_decode_z) and no per-layer K / V of the memory is built -- or, with a latent wider
-               than 2 d_model / H or `GCT_DECODE_ZATTN=0`, the K/V of all layers projected once;
+               than 2 d_model / H, the K/V of all layers projected once;
   * `prefill`: the prefix (<sos>, or <sos> scaffold <sep>; with use_cond2dec the n_c condition tokens in
                front of it, which see each other and the first token -- Model/modules.py:19-26) through ONE ordinary
                decoder forward, whose per-layer self-attention K/V fill the caches;
@@ -91,11 +91,11 @@ from .flat import planes_scope
 
 # rows per step below which the step's GEMMs take the skinny fp32 kernels (panel / 64x64 split-K) instead of the general
 # path (bf16x6).  Measured on MI355X: n = 1100 / 1536 / 2048 / 3000 take 2.18 / 2.32 / 2.39 / 3.04 ms per token on the
-# general path against 2.27 / 2.46 / 2.58 / 3.74 on the skinny kernels; `GCT_DECODE_SKINNY_BELOW` overrides
-SKINNY_BELOW = int(os.environ.get("GCT_DECODE_SKINNY_BELOW", "1024"))
+# general path against 2.27 / 2.46 / 2.58 / 3.74 on the skinny kernels
+SKINNY_BELOW = 1024
 # cross-attention of a step over the latent rows themselves (gct_attn_decode_z) instead of per-layer K / V projections of
-# the memory; `GCT_DECODE_ZATTN=0` keeps the projected K / V (the A/B switch; also taken when the latent is too wide)
-ZATTN = os.environ.get("GCT_DECODE_ZATTN", "1") != "0"
+# the memory; False keeps the projected K / V (the tests compare the two; also taken when the latent is too wide)
+ZATTN = True
 # replay guard of use_graphs=True (KVDecoder._replay_is_fast): replay must not be slower than REPLAY_SLOW_FACTOR x the
 # eager launches of the same step on this box; `GCT_DECODE_GRAPH_GUARD=0` switches the guard off (always replay)
 REPLAY_GUARD = os.environ.get("GCT_DECODE_GRAPH_GUARD", "1") != "0"
@@ -133,19 +133,17 @@ class StepPlan:
         select, layout, grammar, logp = dataclasses.astuple(self)
         if select not in (0, 1, FILTERED, BEAM, SBEAM) or layout not in (UNIFORM, MIXED, STREAM):
             raise ValueError(f"no step unit selects {select!r} over {layout!r} rows")
-        if select == BEAM and (layout != UNIFORM or grammar or logp):
-            raise ValueError("the beam step takes uniform rows, no grammar and no log-probabilities")
-        if select == SBEAM and (layout != UNIFORM or grammar or logp):
-            raise ValueError("the stochastic beam step takes uniform rows, no grammar and no log-probabilities")
+        if select in (BEAM, SBEAM) and (layout != UNIFORM or grammar or logp):
+            raise ValueError(f"the {'stochastic ' * (select == SBEAM)}beam step takes uniform rows, no grammar and no "
+                             "log-probabilities")
 
     @functools.cached_property
     def key(self):
-        """THE statement of the graph key (KVDecoder.graphs; bench.py, the tools and the tests read it): "beam"; "sbeam"
-        (both are `select` alone: uniform rows are the only layout they have); select alone for plain uniform rows; (select, layout) for another layout; and with a grammar and / or log-probabilities
-        (select, layout[, GRAMMAR][, LOGP]), uniform spelled out.  A stream unit has k[1] == STREAM, logp k[-1] == LOGP."""
+        """THE statement of the graph key (KVDecoder.graphs; bench.py, the tools and the tests read it): `select` alone
+        for plain uniform rows -- the only rows BEAM ("beam") and SBEAM ("sbeam") have; (select, layout) for another
+        layout; and with a grammar and / or log-probabilities (select, layout[, GRAMMAR][, LOGP]), uniform spelled out.
+        A stream unit has k[1] == STREAM, logp k[-1] == LOGP."""
         select, layout, grammar, logp = dataclasses.astuple(self)
-        if select == BEAM:
-            return BEAM
         tail = (GRAMMAR,) * bool(grammar) + (LOGP,) * bool(logp)
         if layout == UNIFORM and not tail:
             return select
@@ -1080,6 +1078,19 @@ def check_prefix_lens(prefix_lens, n, width):
     return None if bool((lens == width).all()) else lens
 
 
+def row_prefix_lens(lens, n, width):
+    """check_prefix_lens' result with the uniform path spelled out: int64 [n] on the CPU, `width` for every row when
+    lens is None."""
+    return torch.full((n,), width, dtype=torch.int64) if lens is None else lens
+
+
+def pad_behind_prefix(ys0, lens, pad_id):
+    """ys0 [n, t0] with pad_id in the columns behind each row's prefix ys0[r, :lens[r]] (lens int64 [n] on the device
+    of ys0): what a mixed-prefix decode reads, whatever the caller left there."""
+    cols = torch.arange(ys0.shape[1], device=ys0.device).view(1, -1)
+    return torch.where(cols < lens.view(-1, 1), ys0, torch.full_like(ys0, pad_id))
+
+
 def generated_tokens(ys, prefix_lens):
     """The generated part of a mixed-prefix output ys [n, t0_max + G]: [n, G], row r = ys[r, t0_r : t0_r + G] (pad
     after the row's last step).  prefix_lens=None: ys[:, t0:] is the caller's slice."""
@@ -1476,8 +1487,7 @@ class KVDecoder:
         ys0 = ys0.to(self.ys.device)
         if prefix_lens is not None:
             lens = prefix_lens.to(self.ys.device, torch.int64)
-            cols = torch.arange(t0, device=ys0.device).view(1, -1)
-            ys0 = torch.where(cols < lens.view(-1, 1), ys0, torch.full_like(ys0, self.pad_id))
+            ys0 = pad_behind_prefix(ys0, lens, self.pad_id)
             self.row_off.copy_(t0 - lens)
         self.ys.fill_(self.pad_id)
         self.ys[:, :t0] = ys0
@@ -1657,6 +1667,67 @@ class KVDecoder:
         token_logp = torch.where(span, table[:, :ys.size(1)], torch.zeros((), device=dev))
         return token_logp, token_logp.sum(1)
 
+    def _check_room(self, who, t0, steps):
+        """A prefix of t0 tokens + `steps` steps (+ the `off` condition rows) fit the positional table, then the cache
+        rows start() laid out; ValueError otherwise.  Before the first start() there are no cache rows to ask about:
+        only the table is checked, and that the rows are missing is the caller's refusal (generate_stream: no pool)."""
+        pe_rows = self.dec.pe.pe.shape[1]
+        if self.off + t0 + steps > pe_rows:
+            raise ValueError(f"{who}: prefix {t0} + {steps} steps + {self.off} condition rows exceed the {pe_rows}-row "
+                             "positional table")
+        if self._shape is not None and self.off + t0 + steps > self.T:
+            raise ValueError(f"{who}: prefix {t0} + {steps} steps exceeds the cache length {self.T - self.off}")
+
+    def _lockstep(self, plan, ys0, lens, steps, done, check_every, use_graphs):
+        """THE driver of the decodes whose rows move in step (generate, generate_beam, generate_sbs): the prefill of
+        the prefix rows ys0 [n, t0] (lens: prefill's prefix_lens), the first selection from the prefill's logits, then
+        steps - 1 units of `plan`.  Every check_every steps (0: never) the host reads the device flags `done` and stops
+        once all are set.  The caller has written the per-call device state the unit reads -- the prefill touches none
+        of it.  Returns last: the decode wrote the token columns ys[:, :last]."""
+        t0 = ys0.shape[1]
+        self.prefill(ys0, lens)
+        self._select(plan)                                         # token t0 from the prefill's last position
+        if plan.logp:
+            self._chosen_logp(plan)
+        for i in range(1, steps):
+            self._run_step(plan, use_graphs)                       # consumes token t0+i-1, writes token t0+i
+            if check_every and (i + 1) % check_every == 0 and bool(done.all()):
+                return t0 + i + 1
+        return t0 + steps
+
+    def _beam_entry(self, who, ys0, k, max_strlen, prefix_lens, root=None):
+        """What generate_beam and generate_sbs (`who`) do before the decode: the refusals (ValueError), then the beam
+        state of start(..., beams=k)'s rows back to sbs_init's -- bscores [0, -inf, ...] per sample, bgumbel the same
+        with the root's Gumbel value `root` [ns] (None: the unit has no bgumbel, it stays), no beam finished, no length,
+        every row its own ancestor.  Returns (ns, k, t0, steps, the prefix rows [ns * k, t0] on the device)."""
+        if prefix_lens is not None:
+            raise ValueError(f"{who}: mixed prefix lengths are not supported; run one decode per length")
+        k = int(k)
+        if k != self.beams:
+            raise ValueError(f"{who}: {k} beams, but start() prepared {self.beams} beam(s) per sample")
+        ns, t0 = ys0.shape
+        if ns * k != self.n:
+            raise ValueError(f"{who}: {ns} prefixes x {k} beams != the {self.n} rows start() prepared")
+        steps = max_strlen - 1
+        if steps < 1:
+            raise ValueError(f"{who}: max_strlen must be at least 2")
+        self._check_room(who, t0, steps)
+        dev = self.ys.device
+        scores, gumbels, _, _ = sbs_init(ns, k, dev, root)
+        self.bscores.copy_(scores.view(-1))
+        if root is not None:
+            self.bgumbel.copy_(gumbels.view(-1))
+        self.bfin.zero_()
+        self.blen.zero_()
+        self.bdone.zero_()
+        self.kv_src.copy_(torch.arange(self.n, dtype=torch.int32, device=dev).view(-1, 1).expand(-1, self.T))
+        return ns, k, t0, steps, ys0.to(dev).repeat_interleave(k, 0)
+
+    def _beam_tokens(self, ns, k, last):
+        """The beams' token rows [ns, k, last]: token t of beam b lies in the row kv_src[b, off + t] that wrote it."""
+        ys = torch.gather(self.ys[:, :last], 0, self.kv_src[:, self.off:self.off + last].long())
+        return ys.view(ns, k, last)
+
     # -------------------------------------------------------------------------------------
     @torch.no_grad()
     def generate(self, ys0, max_strlen=80, algo="greedy", seed=0, check_every=8, use_graphs=False, prefix_lens=None,
@@ -1685,26 +1756,13 @@ class KVDecoder:
         n, t0 = ys0.shape
         steps = max_strlen - 1
         lens = check_prefix_lens(prefix_lens, n, t0)
-        pe_rows = self.dec.pe.pe.shape[1]
-        if self.off + t0 + steps > pe_rows:
-            raise ValueError(f"prefix {t0} + {steps} steps + {self.off} condition rows exceed the {pe_rows}-row "
-                             "positional table")
-        if self.off + t0 + steps > self.T:
-            raise ValueError(f"prefix {t0} + {steps} steps exceeds the cache length {self.T - self.off}")
+        self._check_room("generate", t0, steps)
         plan = StepPlan(self._set_sampling(algo, filt, seed, grammar, steps, t0), UNIFORM if lens is None else MIXED,
                         grammar is not None, bool(return_logp))
-        self.prefill(ys0, lens)
-        self._select(plan)                                         # token t0 from the prefill's last position
         if plan.logp:
             self.tok_logp.zero_()
-            self._chosen_logp(plan)
-        last = t0 + steps
-        for i in range(1, steps):
-            self._run_step(plan, use_graphs)                       # consumes token t0+i-1, writes token t0+i
-            if check_every and (i + 1) % check_every == 0 and bool(self.done.all()):
-                last = t0 + i + 1
-                break
-        lens = torch.full((n,), t0) if lens is None else lens
+        last = self._lockstep(plan, ys0, lens, steps, self.done, check_every, use_graphs)
+        lens = row_prefix_lens(lens, n, t0)
         ys, is_eos = self._cut_at_eos(self.ys[:, :last], lens, t0)
         if not plan.logp:
             return ys.clone()
@@ -1720,36 +1778,9 @@ class KVDecoder:
         Returns (ys [n, k, L] int64, scores [n, k] fp32 sums of log-probabilities, lengths [n, k] int64), beams sorted
         by score / length**alpha (beam_finalize); pad after each beam's end, L = t0 + the longest beam.
         Mixed prefix lengths are not supported (prefix_lens raises ValueError): decode each length group on its own."""
-        if prefix_lens is not None:
-            raise ValueError("generate_beam: mixed prefix lengths are not supported; run one beam decode per length")
-        k = int(beam_size)
-        if k != self.beams:
-            raise ValueError(f"generate_beam: beam_size {k}, but start() prepared {self.beams} beam(s) per sample")
-        ns, t0 = ys0.shape
-        if ns * k != self.n:
-            raise ValueError(f"generate_beam: {ns} prefixes x {k} beams != the {self.n} rows start() prepared")
-        steps = max_strlen - 1
-        if steps < 1:
-            raise ValueError("generate_beam: max_strlen must be at least 2")
-        if self.off + t0 + steps > self.T:
-            raise ValueError(f"prefix {t0} + {steps} steps exceeds the cache length {self.T - self.off}")
-        dev, plan = self.ys.device, StepPlan(BEAM)
-        self.prefill(ys0.to(dev).repeat_interleave(k, 0))
-        scores, _, _ = beam_init(ns, k, dev)
-        self.bscores.copy_(scores.view(-1))
-        self.bfin.zero_()
-        self.blen.zero_()
-        self.bdone.zero_()
-        self.kv_src.copy_(torch.arange(self.n, dtype=torch.int32, device=dev).view(-1, 1).expand(-1, self.T))
-        self._select(plan)                                         # token t0 from the prefill's last position
-        last = t0 + steps
-        for i in range(1, steps):
-            self._run_step(plan, use_graphs)                       # consumes token t0+i-1, writes token t0+i
-            if check_every and (i + 1) % check_every == 0 and bool(self.bdone.all()):
-                last = t0 + i + 1
-                break
-        ys = torch.gather(self.ys[:, :last], 0, self.kv_src[:, self.off:self.off + last].long())
-        return beam_finalize(ys.view(ns, k, last), self.bscores.view(ns, k).clone(),
+        ns, k, t0, steps, rows = self._beam_entry("generate_beam", ys0, beam_size, max_strlen, prefix_lens)
+        last = self._lockstep(StepPlan(BEAM), rows, None, steps, self.bdone, check_every, use_graphs)
+        return beam_finalize(self._beam_tokens(ns, k, last), self.bscores.view(ns, k).clone(),
                              self.blen.view(ns, k).to(torch.int64), t0, alpha)
 
     @torch.no_grad()
@@ -1763,38 +1794,11 @@ class KVDecoder:
         Gumbel value, the order the kernel leaves them in; no length normalisation), L = t0 + the longest beam.  The
         root's Gumbel value is drawn too (sbs_root_gumbels(n, seed): sbs_importance_weights needs it).  The same seed
         gives the same sample.  Mixed prefix lengths raise ValueError, as in generate_beam."""
-        if prefix_lens is not None:
-            raise ValueError("generate_sbs: mixed prefix lengths are not supported; run one decode per length")
-        k = int(k)
-        if k != self.beams:
-            raise ValueError(f"generate_sbs: k = {k}, but start() prepared {self.beams} beam(s) per sample")
-        ns, t0 = ys0.shape
-        if ns * k != self.n:
-            raise ValueError(f"generate_sbs: {ns} prefixes x {k} beams != the {self.n} rows start() prepared")
-        steps = max_strlen - 1
-        if steps < 1:
-            raise ValueError("generate_sbs: max_strlen must be at least 2")
-        if self.off + t0 + steps > self.T:
-            raise ValueError(f"prefix {t0} + {steps} steps exceeds the cache length {self.T - self.off}")
-        dev, plan = self.ys.device, StepPlan(SBEAM)
+        ns, k, t0, steps, rows = self._beam_entry("generate_sbs", ys0, k, max_strlen, prefix_lens,
+                                                  root=sbs_root_gumbels(ys0.shape[0], seed))
         self.seed.fill_(int(seed) & 0x7FFFFFFFFFFFFFFF)
-        self.prefill(ys0.to(dev).repeat_interleave(k, 0))
-        scores, gumbels, _, _ = sbs_init(ns, k, dev, root=sbs_root_gumbels(ns, seed, dev))
-        self.bscores.copy_(scores.view(-1))
-        self.bgumbel.copy_(gumbels.view(-1))
-        self.bfin.zero_()
-        self.blen.zero_()
-        self.bdone.zero_()
-        self.kv_src.copy_(torch.arange(self.n, dtype=torch.int32, device=dev).view(-1, 1).expand(-1, self.T))
-        self._select(plan)                                         # token t0 from the prefill's last position
-        last = t0 + steps
-        for i in range(1, steps):
-            self._run_step(plan, use_graphs)                       # consumes token t0+i-1, writes token t0+i
-            if check_every and (i + 1) % check_every == 0 and bool(self.bdone.all()):
-                last = t0 + i + 1
-                break
-        ys = torch.gather(self.ys[:, :last], 0, self.kv_src[:, self.off:self.off + last].long()).view(ns, k, last)
-        lengths = self.blen.view(ns, k).to(torch.int64)
+        last = self._lockstep(StepPlan(SBEAM), rows, None, steps, self.bdone, check_every, use_graphs)
+        ys, lengths = self._beam_tokens(ns, k, last), self.blen.view(ns, k).to(torch.int64)
         return SbsSamples(ys[:, :, :t0 + int(lengths.max())].contiguous(), self.bscores.view(ns, k).clone(),
                           self.bgumbel.view(ns, k).clone(), lengths)
 
@@ -1806,7 +1810,7 @@ class KVDecoder:
         as in start().  item_base: the pool is items item_base .. item_base + N - 1 of a larger one (their multinomial
         keys; a pool taken in slices decodes exactly what it decodes whole).
         ValueError before any device work for use_cond2dec models, for a latent geometry whose cross-attention keeps
-        per-sequence K / V projections (gct_attn_decode_z not taken: `GCT_DECODE_ZATTN=0`, latent wider than 128 or
+        per-sequence K / V projections (gct_attn_decode_z not taken: latent wider than 128 or
         than 2 d_model / H) and for rows outside [1, ops.STREAM_MAX_ROWS].
         HBM: the pool stays on the device until the next start_stream -- N * L_e * latent * 4 B of latent rows,
         N * (L_e + n_c) B of masks, and with cond2lat the projected condition rows, N * n_c * 2 d_model * 4 B PER
@@ -1925,14 +1929,11 @@ class KVDecoder:
             raise ValueError("generate_stream: needs at least one item and max_strlen >= 2")
         if isinstance(check_every, bool) or not isinstance(check_every, numbers.Integral) or check_every < 1:
             raise ValueError(f"check_every must be an int >= 1, got {check_every!r}")
-        lens = check_prefix_lens(prefix_lens, N, t0)
-        lens = torch.full((N,), t0, dtype=torch.int64) if lens is None else lens
+        lens = row_prefix_lens(check_prefix_lens(prefix_lens, N, t0), N, t0)
         cap = check_max_new_tokens(max_new_tokens, N, steps)
         check_grammar(grammar, self.model.out.weight.shape[0], cap)
         W = t0 + steps
-        pe_rows = self.dec.pe.pe.shape[1]
-        if W > pe_rows:
-            raise ValueError(f"prefix {t0} + {steps} steps exceed the {pe_rows}-row positional table")
+        self._check_room("generate_stream", t0, steps)
         st = self.stream
         if st is None:
             raise ValueError("generate_stream: no pool (call start_stream first)")
@@ -1941,12 +1942,9 @@ class KVDecoder:
         if st["key"][2] != self._shape or st["key"][4] != self.ys.data_ptr():      # start() laid the rows out anew since
             raise ValueError("generate_stream: the decoder's rows are not the ones start_stream prepared (start() was "
                              "called with another geometry since); call start_stream again")
-        if W > self.T:
-            raise ValueError(f"prefix {t0} + {steps} steps exceeds the cache length {self.T}")
         R = st["rows"]
-        cols = torch.arange(t0).view(1, -1)
-        prefix = torch.where(cols < lens.view(-1, 1), ys0.cpu(), torch.full_like(ys0.cpu(), self.pad_id))
-        st["prefix_pool"][:, :t0].copy_(prefix)                    # (columns behind t0 are never read: prefix_len <= t0)
+        # (columns behind t0 are never read: prefix_len <= t0)
+        st["prefix_pool"][:, :t0].copy_(pad_behind_prefix(ys0.cpu(), lens, self.pad_id))
         st["prefix_len"].copy_(lens)
         st["limit"].copy_(cap)
         st["out_ys"].fill_(self.pad_id)
