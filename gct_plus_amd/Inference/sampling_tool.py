@@ -32,6 +32,13 @@ Log-likelihoods: `score` / `score_smiles` give log p(x | z, conditions, scaffold
 `decode`, `sample_smiles` and `sample_multiple_smiles` return the model's log-probability of what they drew as one more
 element (KVDecoder.generate(return_logp=True): no second forward).
 
+Marginal likelihoods: `marginal` / `marginal_smiles` estimate log p(x) itself, the latent integrated out, by the
+importance-weighted bound over K draws of the encoder's posterior (decode.marginal_logp; Burda et al.): one encoder
+forward, the draws and their log p(z) - log q(z | x) from one launch per block (ops.latent_iw), score_tokens on the
+block, and the bound, the ELBO and the effective sample size per molecule (ops.iw_combine).  The number is
+log p(tokens behind the prefix | latent length, scaffold, conditions): the prior is N(0, I) over all of a molecule's own
+latent rows, the latent length stays the encoder's, and no log p(toklen) term is added.
+
 Fine-tuning on what was sampled: `return_rows=True` on `decode`, `sample_smiles` and `sample_multiple_smiles` appends a
 `DecodedRows` -- the latents, mask, conditions and prefix lengths the decode consumed and the token rows it produced --
 and `logp(*rows)` is `score(*rows)` WITH a gradient (decode.sequence_logp), on the device: the policy term of
@@ -67,9 +74,9 @@ from .. import ops
 from ..Model.modules import get_src_mask
 from ..data import Vocab, tokenize
 from .mol_interpolation import Interpolation, interior_alphas, interp_plan, lerp, noise_ladder, run_ladder
-from ..decode import (BEAM_ALPHA, KVDecoder, PolicyTerms, PpoTerms, SmilesGrammar, check_beam_size, check_sample_filter,
-                      check_stream_model, check_stream_rows, generated_tokens, score_tokens, sequence_logp,
-                      sequence_policy, sequence_ppo)
+from ..decode import (BEAM_ALPHA, KVDecoder, Marginal, PolicyTerms, PpoTerms, SmilesGrammar, check_beam_size,
+                      check_sample_filter, check_stream_model, check_stream_rows, generated_tokens, marginal_logp,
+                      score_tokens, sequence_logp, sequence_policy, sequence_ppo)
 
 
 BEAM_ALGOS = ("beam", "stochastic_beam")        # decode_algo values that decode k rows per sample in step (kv_src)
@@ -208,6 +215,7 @@ class Sampling:
         self.gen = torch.Generator().manual_seed(seed)
         self.seed = seed
         self.latent_seed = seed                 # interpolate_smiles' latents: one stream per sampler, not per decode
+        self.marginal_seed = seed               # marginal(seed=None): advanced once per call, so calls draw afresh
         self.kv = KVDecoder(model, self.pad_id, self.sos_id, self.eos_id)
 
     # ---- helpers with the reference's names ------------------------------------------------
@@ -385,6 +393,38 @@ class Sampling:
         else:
             zs, _, src_mask = latent_setup_rows(extras, zs, None, self.latent_dim, self.sample_toklen, self.sample_z)
         return self.score(zs, ys, src_mask, self._conds(conds, transform), lens)
+
+    @torch.no_grad()
+    def marginal(self, mu, log_var, src_mask, ys, dconds=None, prefix_lens=None, K=64, seed=None, chunk=4096,
+                 items=None, return_weights=False) -> Marginal:
+        """Importance-weighted estimate of log p(x) of the full token rows ys [n, W] (`score`'s layout) from K draws of
+        the posterior N(mu, exp(log_var)) -- mu, log_var [n, L_e, latent] and src_mask [n, 1, L_e] as the encoder gives
+        them (decode.marginal_logp; decode.Marginal says what comes back).  Marginal on the CPU.
+        seed None: the sampler's own counter, advanced once per call (two calls draw different latents); an int makes
+        the call repeatable.  The draws of molecule i are keyed by (seed, items[i], k), items default arange(n)."""
+        if seed is None:
+            self.marginal_seed += 1
+            seed = self.marginal_seed
+        mu, log_var, src_mask = mu.to(self.device), log_var.to(self.device), src_mask.to(self.device)
+        dconds = None if dconds is None else dconds.to(self.device)
+        out = marginal_logp(self.model, mu, log_var, src_mask, dconds, ys, prefix_lens=prefix_lens, K=K, seed=seed,
+                            items=items, chunk=chunk, pad_id=self.pad_id, return_weights=return_weights)
+        return Marginal(*(None if t is None else t.cpu() for t in out))
+
+    @torch.no_grad()
+    def _marginal_smiles(self, smiles_list, scaffold_list, conds, transform=True, K=64, seed=None, chunk=4096,
+                         return_weights=False):
+        """What the types' marginal_smiles share: the targets of `score_smiles` (_score_targets), ONE encoder forward
+        of the same molecules for mu, log_var and the encoder's own mask (_encode_endpoints), then `marginal`.
+        The number is log p(tokens behind the prefix | latent length, scaffold, conditions): the prior is N(0, I) over
+        ALL of the molecule's own latent rows (condition rows, scaffold, <sep>, tokens: what sample_z /
+        latent_setup_rows draw from), the latent length is held at the encoder's, and the token-length histogram term
+        log p(toklen) that sample_toklen draws from is NOT added."""
+        smiles_list = list(smiles_list)
+        ys, lens, _ = self._score_targets(smiles_list, scaffold_list)
+        mu, log_var, src_mask = self._encode_endpoints(smiles_list, scaffold_list, conds, transform)
+        return self.marginal(mu, log_var, src_mask, ys, self._conds(conds, transform), lens, K=K, seed=seed, chunk=chunk,
+                             return_weights=return_weights)
 
     @torch.no_grad()
     def decode_beams(self, zs, ys, src_mask, dconds=None, beam_size=None, alpha=None):
@@ -646,6 +686,11 @@ class VaetfSampling(Sampling):
         """log p(<sos> smiles <eos> | z): z = zs [n, L_e, latent], or (None) the encoder's mean of the same molecule."""
         return self._score_smiles(smiles_list, None, None, zs)
 
+    def marginal_smiles(self, smiles_list, K=64, seed=None, chunk=4096, return_weights=False) -> Marginal:
+        """Importance-weighted estimate of log p(<sos> smiles <eos> | latent length) from K posterior draws per molecule
+        (Sampling._marginal_smiles says what the number is; decode.Marginal what comes back)."""
+        return self._marginal_smiles(smiles_list, None, None, True, K, seed, chunk, return_weights)
+
 
 class CvaetfSampling(Sampling):
     uses_props = True
@@ -671,6 +716,12 @@ class CvaetfSampling(Sampling):
         """log p(<sos> smiles <eos> | z, conds); zs None: the encoder's mean of (smiles, conds)."""
         return self._score_smiles(smiles_list, None, conds, zs, transform)
 
+    def marginal_smiles(self, smiles_list, conds, K=64, seed=None, chunk=4096, transform=True,
+                        return_weights=False) -> Marginal:
+        """Importance-weighted estimate of log p(<sos> smiles <eos> | latent length, conds); the encoder sees
+        (smiles, conds), as in score_smiles(zs=None)."""
+        return self._marginal_smiles(smiles_list, None, conds, transform, K, seed, chunk, return_weights)
+
 
 class ScaVaeSampling(Sampling):
     uses_scaffold = True
@@ -693,6 +744,11 @@ class ScaVaeSampling(Sampling):
         """log p(smiles <eos> | <sos> scaffold <sep>, z), one scaffold per molecule (the prefix is not scored); zs None:
         the encoder's mean of scaffold <sep> smiles."""
         return self._score_smiles(smiles_list, scaffold_list, None, zs)
+
+    def marginal_smiles(self, smiles_list, scaffold_list, K=64, seed=None, chunk=4096, return_weights=False) -> Marginal:
+        """Importance-weighted estimate of log p(smiles <eos> | <sos> scaffold <sep>, latent length), one scaffold per
+        molecule (the prefix is not scored); the encoder sees scaffold <sep> smiles."""
+        return self._marginal_smiles(smiles_list, scaffold_list, None, True, K, seed, chunk, return_weights)
 
     def sample_multiple_smiles(self, scaffolds, zs=None, toklen=None, return_rows=False):
         """One molecule per scaffold, all rows in one batch: row r decodes as sample_smiles(1, scaffolds[r]) with z
@@ -726,6 +782,12 @@ class PscavaetfSampling(Sampling):
         """log p(smiles <eos> | <sos> scaffold <sep>, z, conds), one scaffold per molecule; zs None: the encoder's mean
         of (scaffold <sep> smiles, conds)."""
         return self._score_smiles(smiles_list, scaffold_list, conds, zs, transform)
+
+    def marginal_smiles(self, smiles_list, scaffold_list, conds, K=64, seed=None, chunk=4096, transform=True,
+                        return_weights=False) -> Marginal:
+        """Importance-weighted estimate of log p(smiles <eos> | <sos> scaffold <sep>, latent length, conds), one
+        scaffold per molecule; the encoder sees (scaffold <sep> smiles, conds)."""
+        return self._marginal_smiles(smiles_list, scaffold_list, conds, transform, K, seed, chunk, return_weights)
 
     def sample_multiple_smiles(self, dconds, scaffolds, zs=None, toklen=None, transform=True, return_rows=False):
         """The reference's intended sample_multiple_smiles (sampling_tool.py, commented out there): row r has the

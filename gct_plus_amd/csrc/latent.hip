@@ -3,6 +3,9 @@
 // own latent rows (approximate_z's fit).  gct_latent_interp: one wave per (row, token) draws the two endpoints' latents
 // from those fits, slerps them over the D dimensions and adds the retry ladder's noise.  include/gctplus_hip.h states
 // the rules (random streams, guard, limits); nothing here depends on the grid, and there are no atomics.
+// K13: importance-weighted marginal likelihoods.  gct_latent_iw: K posterior draws per molecule, each latent written
+// once together with log p(z) - log q(z | x) of the draw; gct_iw_combine: the bound, the ELBO and the effective sample
+// size of a molecule's K log-weights in fp64, one wave per molecule.
 #include "common.h"
 
 namespace {
@@ -162,7 +165,146 @@ __global__ __launch_bounds__(256) void latent_interp_kernel(const float* stats, 
   }
 }
 
+// K13: one workgroup per output row r = (molecule i, draw k), walking the row's quads q = t * nq + j in steps of 256:
+// consecutive work-items take consecutive quads, so every load and store of a wave is one contiguous run.  A quad
+// costs one Philox call and one Box-Muller; z (and eps) are written once and nothing is read back.  The terms go into a
+// per-work-item fp64 sum in ascending q, then the butterfly and the four waves: the order the header states.
+__global__ __launch_bounds__(256) void latent_iw_kernel(const float* mu, const float* lv, const int32_t* rows,
+                                                        const int32_t* item, int Le, int D, int k0, int Kc,
+                                                        int64_t R, float* z, float* logw, float* eps_out, GctRng rng) {
+  __shared__ double sh[4];
+  const int tid = threadIdx.x, nq = (D + 3) >> 2;
+  const int dt = 256 / nq, dj = 256 % nq;             // one step of 256 quads in (t, j)
+  const bool vec = (D & 3) == 0 && ((((uintptr_t)mu) | ((uintptr_t)lv) | ((uintptr_t)z) | ((uintptr_t)eps_out)) & 15u) == 0;
+  for (int64_t r = blockIdx.x; r < R; r += gridDim.x) {
+    const int i = (int)(r / Kc);
+    const uint32_t c0 = (uint32_t)item[i], c1 = (uint32_t)(k0 + (int)(r - (int64_t)i * Kc));
+    int nr = rows[i];
+    nr = nr < 1 ? 1 : (nr > Le ? Le : nr);            // the wrapper checks 1 <= rows <= Le; never read outside the molecule
+    const float* mi = mu + (int64_t)i * Le * D;
+    const float* li = lv + (int64_t)i * Le * D;
+    float* zr = z + r * Le * D;
+    float* er = eps_out ? eps_out + r * Le * D : nullptr;
+    double acc = 0.0;
+    int t = tid / nq, j = tid - t * nq;
+    while (t < Le) {
+      const int64_t off = (int64_t)t * D + 4 * j;
+      float o[4] = {0.f, 0.f, 0.f, 0.f}, e[4] = {0.f, 0.f, 0.f, 0.f};
+      if (t < nr) {
+        float m[4], l[4];
+        if (vec) {
+          const float4 mv = *reinterpret_cast<const float4*>(mi + off), lq = *reinterpret_cast<const float4*>(li + off);
+          m[0] = mv.x; m[1] = mv.y; m[2] = mv.z; m[3] = mv.w;
+          l[0] = lq.x; l[1] = lq.y; l[2] = lq.z; l[3] = lq.w;
+        } else {
+#pragma unroll
+          for (int x = 0; x < 4; ++x) {
+            const bool in = 4 * j + x < D;
+            m[x] = in ? mi[off + x] : 0.f;
+            l[x] = in ? li[off + x] : 0.f;
+          }
+        }
+        normals4(gct_philox(rng, c0, c1, 256u * (uint32_t)t + (uint32_t)j, GCT_IW_C3), e);
+#pragma unroll
+        for (int x = 0; x < 4; ++x)
+          if (4 * j + x < D) {
+            o[x] = fmaf(e[x], expf(0.5f * l[x]), m[x]);
+            acc += (double)(0.5f * fmaf(e[x] - o[x], e[x] + o[x], l[x]));
+          }
+      }
+      if (vec) {
+        *reinterpret_cast<float4*>(zr + off) = make_float4(o[0], o[1], o[2], o[3]);
+        if (er) *reinterpret_cast<float4*>(er + off) = make_float4(e[0], e[1], e[2], e[3]);
+      } else {
+#pragma unroll
+        for (int x = 0; x < 4; ++x)
+          if (4 * j + x < D) {
+            zr[off + x] = o[x];
+            if (er) er[off + x] = e[x];
+          }
+      }
+      j += dj;
+      t += dt;
+      if (j >= nq) { j -= nq; ++t; }
+    }
+    acc = gct_wave_sum(acc);
+    if ((tid & 63) == 0) sh[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) logw[r] = (float)((sh[0] + sh[1]) + (sh[2] + sh[3]));
+    __syncthreads();                                  // sh is the next row's too
+  }
+}
+
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// one wave per molecule: lane l holds k = l, l + 64, ...; everything in fp64, one rounding per output
+__global__ __launch_bounds__(256) void iw_combine_kernel(const float* logp, const float* logw, int n, int K,
+                                                         float* iwae, float* elbo, float* recon, float* ess) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const float* p = logp + i * K;
+  const float* w = logw + i * K;
+  double m = -INFINITY, sa = 0.0, sp = 0.0;
+  for (int k = lane; k < K; k += 64) {
+    const double a = (double)p[k] + (double)w[k];
+    m = fmax(m, a);
+    sa += a;
+    sp += (double)p[k];
+  }
+  m = wave_max_f64(m);
+  sa = gct_wave_sum(sa);
+  sp = gct_wave_sum(sp);
+  const double shift = m == -INFINITY ? 0.0 : m;      // every weight zero: iwae = -inf, not NaN
+  double s1 = 0.0, s2 = 0.0;
+  for (int k = lane; k < K; k += 64) {
+    const double e = exp(((double)p[k] + (double)w[k]) - shift);
+    s1 += e;
+    s2 += e * e;
+  }
+  s1 = gct_wave_sum(s1);
+  s2 = gct_wave_sum(s2);
+  if (lane == 0) {
+    iwae[i] = (float)(shift + log(s1) - log((double)K));
+    elbo[i] = (float)(sa / (double)K);
+    recon[i] = (float)(sp / (double)K);
+    ess[i] = (float)(s1 * s1 / s2);
+  }
+}
+
 }  // namespace
+
+extern "C" int gct_latent_iw(const float* mu, const float* log_var, int n, int Le, int D, const int32_t* rows,
+                             const int32_t* item, int k0, int Kc, float* z, float* logw, float* eps_out,
+                             uint64_t seed, void* stream) {
+  GCT_CHECK_ARG(D >= 1 && D <= GCT_LATENT_MAX_DIM, "latent_iw: D=%d outside [1, %d]", D, GCT_LATENT_MAX_DIM);
+  GCT_CHECK_ARG(Le >= 1 && Le <= (1 << 24) && n >= 0, "latent_iw: bad Le=%d (1..2^24) or n=%d", Le, n);
+  GCT_CHECK_ARG(k0 >= 0 && Kc >= 0 && (int64_t)k0 + Kc <= 2147483647ll, "latent_iw: bad draw range k0=%d, Kc=%d", k0, Kc);
+  const int64_t R = (int64_t)n * Kc;
+  GCT_CHECK_ARG(R * Le <= ((int64_t)1 << 25), "latent_iw: n * Kc * Le = %lld rows of z exceed 2^25", (long long)(R * Le));
+  if (R == 0) return GCT_OK;
+  GCT_CHECK_ARG(mu && log_var && rows && item && z && logw, "latent_iw: null pointer");
+  const int64_t cap = (int64_t)1 << 20;               // workgroups; a larger batch walks several rows per workgroup
+  hipLaunchKernelGGL(latent_iw_kernel, dim3((unsigned)(R < cap ? R : cap)), dim3(256), 0, (hipStream_t)stream, mu,
+                     log_var, rows, item, Le, D, k0, Kc, R, z, logw, eps_out, gct_rng_make(seed, GCT_IW_SITE));
+  GCT_LAUNCH_CHECK("latent_iw");
+  return GCT_OK;
+}
+
+extern "C" int gct_iw_combine(const float* logp, const float* logw, int n, int K, float* iwae, float* elbo,
+                              float* recon, float* ess, void* stream) {
+  GCT_CHECK_ARG(n >= 0 && K >= 1 && (int64_t)n * K <= 2147483647ll, "iw_combine: bad n=%d or K=%d", n, K);
+  if (n == 0) return GCT_OK;
+  GCT_CHECK_ARG(logp && logw && iwae && elbo && recon && ess, "iw_combine: null pointer");
+  hipLaunchKernelGGL(iw_combine_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logp, logw,
+                     n, K, iwae, elbo, recon, ess);
+  GCT_LAUNCH_CHECK("iw_combine");
+  return GCT_OK;
+}
 
 extern "C" int gct_latent_stats(const float* mu, const float* log_var, int n, int Le, int D, const int32_t* rows,
                                 float* stats, void* stream) {

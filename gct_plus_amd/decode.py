@@ -64,6 +64,9 @@ entropy and its KL divergence from a frozen prior at every scored token (the rul
 `sequence_ppo` is the objective of several updates on one scored batch: PPO's clipped surrogate of each scored token's
 probability ratio against the log-probabilities it was sampled with (the rules: `ppo_reference` / `ppo_grad_reference`;
 gct_seq_ppo / gct_seq_ppo_bwd through engine.SeqPpoFn), with sequence_policy's terms beside it when asked for.
+`marginal_logp` integrates the latent out: the importance-weighted bound of log p(x) over K posterior draws per molecule
+(the rules: `latent_iw_reference` / `marginal_reference`; gct_latent_iw writes each latent once with its
+log p(z) - log q(z | x), score_tokens scores the block, gct_iw_combine forms the bound in fp64).
 
 Grammar-constrained decoding (`generate` / `generate_stream(grammar=SmilesGrammar(...))`): the rules are stated once, in
 `SmilesGrammar` (grammar_step, grammar_min_finish).  gct_grammar_mask runs in front of the selection: one wave per row
@@ -966,6 +969,153 @@ def sequence_ppo(model, z, src_mask, dconds, ys, old_token_logp, advantage, clip
     ent, tent, kl, tkl, prior_logp = _dist_terms("sequence_ppo", r, z, pad_id, prior, entropy)
     return PpoTerms(logp, tokens, hits, token_logp, ent, tent, kl, tkl, prior_logp, surrogate, token_surrogate,
                     approx_kl, clipped)
+
+
+# ------------------------------------------------------------------------ importance-weighted marginal likelihoods
+class Marginal(NamedTuple):
+    """What marginal_logp returns, one entry per molecule: iwae [n] fp32 = logsumexp_k(log w_k) - log K, the
+    importance-weighted lower bound of log p(x) (Burda et al.; the ELBO at K = 1, log p(x) as K grows), with
+    log w_k = log p(x | z_k) + log p(z_k) - log q(z_k | x), z_k ~ q(z | x); elbo [n] = mean_k log w_k, the K-sample
+    estimate of the ELBO; recon [n] = mean_k log p(x | z_k); ess [n] = (sum w)^2 / sum w^2, the effective sample size in
+    [1, K] (near 1: one draw carries the estimate, raise K); tokens [n] int32 the scored tokens (score_tokens').
+    With return_weights: log_w fp64 [n, K] = logp + logw, and its two parts logp [n, K] (the decoder's) and logw [n, K]
+    (gct_latent_iw's log p(z) - log q(z | x)), both fp32."""
+    iwae: torch.Tensor
+    elbo: torch.Tensor
+    recon: torch.Tensor
+    ess: torch.Tensor
+    tokens: Optional[torch.Tensor] = None
+    log_w: Optional[torch.Tensor] = None
+    logp: Optional[torch.Tensor] = None
+    logw: Optional[torch.Tensor] = None
+
+
+def _int_at_least_one(name, v):
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1:
+        raise ValueError(f"{name} must be an int >= 1, got {v!r}")
+    return int(v)
+
+
+def latent_rows(src_mask, n, Le):
+    """The latent rows each molecule owns, int64 [n] on the CPU, from src_mask bool [n, 1, Le] as the encoder and
+    latent_setup_rows build it: the marked rows must be a non-empty prefix (condition rows, scaffold, <sep>, tokens).
+    ValueError otherwise."""
+    m = torch.as_tensor(src_mask)
+    if tuple(m.shape) != (n, 1, Le):
+        raise ValueError(f"src_mask must be [{n}, 1, {Le}], got {list(m.shape)}")
+    m = m[:, 0].to("cpu").bool()
+    rows = m.sum(1)
+    if n and (int(rows.min()) < 1 or not torch.equal(m, torch.arange(Le).view(1, -1) < rows.view(-1, 1))):
+        raise ValueError("src_mask must mark a non-empty prefix of every molecule's latent rows")
+    return rows
+
+
+def check_marginal_inputs(mu, log_var, src_mask, ys, K, chunk):
+    """Validate a marginal-likelihood call: K and chunk ints >= 1; mu, log_var [n, Le, D] of one shape; src_mask
+    [n, 1, Le] marking a non-empty prefix; ys [n, W].  ValueError otherwise.  Returns (K, chunk, rows int64 [n])."""
+    K, chunk = _int_at_least_one("K", K), _int_at_least_one("chunk", chunk)
+    if mu.dim() != 3 or tuple(log_var.shape) != tuple(mu.shape):
+        raise ValueError(f"mu and log_var must be [n, Le, D] of one shape, got {list(mu.shape)} and {list(log_var.shape)}")
+    n, Le, _ = mu.shape
+    ys = torch.as_tensor(ys)
+    if ys.dim() != 2 or ys.shape[0] != n:
+        raise ValueError(f"ys must be [{n}, W], got {list(ys.shape)}")
+    return K, chunk, latent_rows(src_mask, n, Le)
+
+
+def marginal_blocks(n, K, chunk):
+    """The blocks marginal_logp walks the n x K (molecule, draw) rows in, each of at most `chunk` rows:
+    [(i0, i1, k0, k1)] = molecules i0 .. i1 - 1 x draws k0 .. k1 - 1.  Whole molecules x all K draws while K <= chunk;
+    one molecule x ranges of k otherwise."""
+    if K > chunk:
+        return [(i, i + 1, k, min(K, k + chunk)) for i in range(n) for k in range(0, K, chunk)]
+    m = chunk // K
+    return [(i, min(n, i + m), 0, K) for i in range(0, n, m)]
+
+
+def latent_iw_reference(mu, log_var, rows, eps):
+    """THE statement of gct_latent_iw's arithmetic given the draws, in fp64: mu, log_var [n, Le, D], rows ints [n],
+    eps [n, K, Le, D] standard normals -> (z [n, K, Le, D], logw [n, K]).  On a molecule's own rows t < rows[i]:
+    z = mu + eps exp(log_var / 2) and logw = the sum of 0.5 ((eps - z)(eps + z) + log_var) = log N(z; 0, I) -
+    log N(z; mu, exp(log_var)) (the log 2 pi terms cancel); beyond them z = 0 and nothing is added."""
+    mu, lv = torch.as_tensor(mu).double().cpu(), torch.as_tensor(log_var).double().cpu()
+    eps = torch.as_tensor(eps).double().cpu()
+    n, Le, D = mu.shape
+    if eps.dim() != 4 or eps.shape[0] != n or tuple(eps.shape[2:]) != (Le, D) or tuple(lv.shape) != (n, Le, D):
+        raise ValueError(f"eps must be [{n}, K, {Le}, {D}] and log_var [{n}, {Le}, {D}], got {list(eps.shape)}, {list(lv.shape)}")
+    rows = _int_vector("rows", rows, n, 1, Le, "the latent rows")
+    own = (torch.arange(Le).view(1, -1) < rows.view(-1, 1)).view(n, 1, Le, 1)
+    z = mu.unsqueeze(1) + eps * torch.exp(0.5 * lv).unsqueeze(1)
+    term = 0.5 * ((eps - z) * (eps + z) + lv.unsqueeze(1))
+    zero = torch.zeros((), dtype=torch.float64)
+    return torch.where(own, z, zero), torch.where(own, term, zero).sum((2, 3))
+
+
+def marginal_reference(logp, logw=None, mu=None, log_var=None, rows=None, eps=None):
+    """THE statement of the importance-weighted estimate (gct_iw_combine implements it), in fp64 on the CPU.
+    logp [n, K >= 1]: log p(x | z_k) of every draw; logw [n, K]: log p(z_k) - log q(z_k | x) -- or, with logw None,
+    computed from the draws themselves: latent_iw_reference(mu, log_var, rows, eps), eps [n, K, Le, D].
+    Returns Marginal(iwae, elbo, recon, ess, None, log_w) with a = logp + logw, m = max_k a:
+      iwae = m + log(sum_k exp(a_k - m)) - log K      elbo = mean_k a_k      recon = mean_k logp_k
+      ess  = (sum_k exp(a_k - m))^2 / sum_k exp(a_k - m)^2
+    Jensen: elbo <= iwae <= max_k a_k for every molecule.  ValueError for K < 1 and mismatched shapes."""
+    logp = torch.as_tensor(logp).double().cpu()
+    if logp.dim() != 2 or logp.shape[1] < 1:
+        raise ValueError(f"logp must be [n, K >= 1], got {list(logp.shape)}")
+    if logw is None:
+        if mu is None or log_var is None or rows is None or eps is None:
+            raise ValueError("marginal_reference: logw, or (mu, log_var, rows, eps) to compute it from")
+        logw = latent_iw_reference(mu, log_var, rows, eps)[1]
+    logw = torch.as_tensor(logw).double().cpu()
+    if tuple(logw.shape) != tuple(logp.shape):
+        raise ValueError(f"logw must be {list(logp.shape)} like logp, got {list(logw.shape)}")
+    K = logp.shape[1]
+    a = logp + logw
+    m = a.max(1, keepdim=True).values
+    e = torch.exp(a - m)
+    s1, s2 = e.sum(1), (e * e).sum(1)
+    return Marginal(m.squeeze(1) + torch.log(s1) - math.log(K), a.sum(1) / K, logp.sum(1) / K, s1 * s1 / s2, None, a)
+
+
+@torch.no_grad()
+def marginal_logp(model, mu, log_var, src_mask, dconds, ys, prefix_lens=None, K=64, seed=0, items=None, chunk=4096,
+                  pad_id=1, return_weights=False):
+    """Importance-weighted estimate of log p(x) of the token rows ys [n, W] (score_tokens' layout and rule) under the
+    VAE: K draws z_k ~ q(z | x) = N(mu, exp(log_var)) per molecule, mu / log_var [n, L_e, latent] the encoder's and
+    src_mask bool [n, 1, L_e] its mask (a non-empty prefix of every molecule's rows), dconds [n, n_c] or None and
+    prefix_lens as score_tokens takes them.  Returns a Marginal on the device (its docstring says what the numbers are).
+    The number is log p(scored tokens | latent length, prefix, conditions): the prior is N(0, I) over the molecule's own
+    latent rows, whose count is held at the encoder's; no term for the token length is added.
+    The n x K rows are walked in marginal_blocks of at most `chunk` rows: per block ONE gct_latent_iw launch (the
+    latents, written once, with log p(z) - log q(z | x) of each) and score_tokens on the block with the mask, conditions
+    and token rows repeated per draw; at the end one gct_iw_combine.  The draws are keyed by (seed, items[i], k) --
+    items ints [n] >= 0, default arange(n) --: a molecule's latents and logw are bit-identical whatever chunk, n or the
+    order of the molecules.  ValueError before any device work for what check_marginal_inputs and score_tokens refuse."""
+    K, chunk, rows = check_marginal_inputs(mu, log_var, src_mask, ys, K, chunk)
+    ys, lens, _, _, _ = _score_geometry(model, ys, prefix_lens)
+    n = mu.shape[0]
+    items = torch.arange(n) if items is None else _int_vector("items", items, n, 0, 2 ** 31 - 1, "int32")
+    if dconds is not None and dconds.shape[0] != n:
+        raise ValueError(f"dconds must have {n} rows, got {list(dconds.shape)}")
+    dev = mu.device
+    mu, log_var = mu.float().contiguous(), log_var.float().contiguous()
+    src_mask = torch.as_tensor(src_mask).to(dev)
+    logp = torch.empty(n, K, device=dev)
+    logw = torch.empty(n, K, device=dev)
+    tokens = torch.empty(n, dtype=torch.int32, device=dev)
+    for i0, i1, k0, k1 in marginal_blocks(n, K, chunk):
+        Kc = k1 - k0
+        z, lw, _ = ops.latent_iw(mu[i0:i1], log_var[i0:i1], rows[i0:i1], items[i0:i1], k0, Kc, seed)
+        rep = lambda x: None if x is None else x[i0:i1].repeat_interleave(Kc, 0)       # noqa: E731
+        lp, tk, _, _ = score_tokens(model, z, rep(src_mask), rep(dconds), rep(ys),
+                                    None if prefix_lens is None else rep(lens), pad_id=pad_id)
+        logp[i0:i1, k0:k1] = lp.view(-1, Kc)
+        logw[i0:i1, k0:k1] = lw.view(-1, Kc)
+        tokens[i0:i1] = tk.view(-1, Kc)[:, 0]
+    iwae, elbo, recon, ess = ops.iw_combine(logp.view(-1), logw.view(-1), n, K)
+    if not return_weights:
+        return Marginal(iwae, elbo, recon, ess, tokens)
+    return Marginal(iwae, elbo, recon, ess, tokens, logp.double() + logw.double(), logp, logw)
 
 
 # ------------------------------------------------------------------------------------- continuous batching

@@ -1078,6 +1078,56 @@ def latent_interp(stats, a, b, alpha, noise_std, lens, items, T, seed):
     return z
 
 
+def latent_iw(mu, log_var, rows, items, k0, Kc, seed, want_eps=False):
+    """gct_latent_iw: mu, log_var fp32 [n, Le, D] contiguous on the device; rows, items [n] host integers (molecule i
+    owns its first rows[i] latent rows and draws from the streams of items[i]) -> (z fp32 [n * Kc, Le, D], logw fp32
+    [n * Kc], eps or None): the draws k0 .. k0 + Kc - 1 of q(z | x) for every molecule, output row i * Kc + (k - k0),
+    with logw = log p(z) - log q(z | x) of the row; zeros behind a molecule's rows.  want_eps: also the N(0, 1) draws
+    themselves (the tests' handle; z and logw do not depend on it).  ValueError / GctError before any launch for
+    malformed tensors, rows outside [1, Le], a negative item, and whatever the library's limits refuse."""
+    _chk(mu, "latent_iw.mu"), _chk(log_var, "latent_iw.log_var")
+    if mu.dim() != 3 or log_var.shape != mu.shape or not mu.is_contiguous() or not log_var.is_contiguous():
+        raise ValueError("latent_iw: mu and log_var must be contiguous [n, Le, D] tensors of one shape")
+    n, Le, D = mu.shape
+    k0, Kc = int(k0), int(Kc)
+    rows = _host_i32(rows, "latent_iw.rows", n)
+    items = _host_i32(items, "latent_iw.items", n)
+    if n and (int(rows.min()) < 1 or int(rows.max()) > Le):
+        raise _lib.GctError(f"latent_iw: rows must lie in [1, {Le}], got {int(rows.min())}..{int(rows.max())}")
+    if n and int(items.min()) < 0:
+        raise _lib.GctError("latent_iw: items must be >= 0")
+    if not (1 <= D <= LATENT_MAX_DIM and Le >= 1 and k0 >= 0 and Kc >= 0):
+        # the library's own refusals, raised here before any output is allocated with a size it would not accept
+        raise _lib.GctError(f"latent_iw: D={D} outside [1, {LATENT_MAX_DIM}], Le={Le} < 1 or a bad draw range "
+                            f"k0={k0}, Kc={Kc}")
+    tab = torch.stack([rows, items]).to(mu.device)      # one copy; held until the launch is enqueued
+    R = n * Kc
+    z = torch.empty(R, Le, D, dtype=torch.float32, device=mu.device)
+    logw = torch.empty(R, dtype=torch.float32, device=mu.device)
+    eps = torch.empty_like(z) if want_eps else None
+    check(_L().gct_latent_iw(_p(mu), _p(log_var), n, Le, D, _p(tab[0]), _p(tab[1]), k0, Kc, _p(z), _p(logw), _p(eps),
+                             int(seed), _st()), "gct_latent_iw")
+    return z, logw, eps
+
+
+def iw_combine(logp, logw, n, K):
+    """gct_iw_combine: logp, logw fp32 [n * K] contiguous on the device (row i * K + k: the decoder's log p(x | z_k)
+    and latent_iw's log p(z_k) - log q(z_k | x)) -> (iwae, elbo, recon, ess) fp32 [n]: the importance-weighted bound
+    logsumexp_k(logp + logw) - log K, the mean log-weight, the mean logp and the effective sample size, in fp64 with one
+    rounding.  ValueError before any launch for K < 1 or tensors that are not [n * K]."""
+    _chk(logp, "iw_combine.logp"), _chk(logw, "iw_combine.logw")
+    n, K = int(n), int(K)
+    if n < 0 or K < 1:
+        raise ValueError(f"iw_combine: n must be >= 0 and K >= 1, got n={n}, K={K}")
+    for name, t in (("logp", logp), ("logw", logw)):
+        if t.dim() != 1 or t.numel() != n * K or not t.is_contiguous():
+            raise ValueError(f"iw_combine: {name} must be a contiguous [{n * K}] tensor, got {list(t.shape)}")
+    out = torch.empty(4, n, dtype=torch.float32, device=logp.device)
+    check(_L().gct_iw_combine(_p(logp), _p(logw), n, K, _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), _st()),
+          "gct_iw_combine")
+    return out[0], out[1], out[2], out[3]
+
+
 def ce_fwd(logits2d, target, pad_id):
     _chk(target, "ce.target", torch.int64)
     rows, V = logits2d.shape

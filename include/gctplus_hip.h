@@ -510,6 +510,53 @@ int gct_latent_interp(const float* stats, int n, int D, const int32_t* a, const 
                       const float* noise_std, const int32_t* len, const int32_t* item, int64_t R, int T, float* z,
                       uint64_t seed, void* stream);
 
+/* ------------------------------------ K13: importance-weighted marginal likelihoods */
+/* K draws z_k ~ q(z | x) = N(mu, exp(log_var)) per molecule with the prior / posterior part of their log-weights
+ * (Burda et al., IWAE): log w_k = log p(x | z_k) + log p(z_k) - log q(z_k | x); the decoder supplies the first term
+ * (gct_seq_logp), gct_latent_iw the latents and the other two, gct_iw_combine the bound.
+ * mu, log_var fp32 [n][Le][D] contiguous; rows int32 [n] on the device: molecule i owns its first rows[i] latent rows
+ * (gct_latent_stats' rule); item int32 [n] on the device: the molecule's stream id, >= 0.  The call makes the draws
+ * k = k0 .. k0 + Kc - 1 of every molecule; output row r = i * Kc + (k - k0) (sample-major, the order of
+ * decode_unique(return_rows=True)).  z fp32 [n * Kc][Le][D], logw fp32 [n * Kc], eps_out nullable, z's shape.
+ * For every t < rows[i] and every d:
+ *   - eps: a standard normal under the repository's N(0, 1) convention (Philox4x32-10, Box-Muller on the word pairs
+ *     (x, y) and (z, w), u01 of csrc/vae.hip) with the key of (seed, site GCT_IW_SITE): element d & 3 of the call with
+ *     the counter (item[i], k, 256 * t + (d >> 2), GCT_IW_C3).  d >> 2 < 256 because D <= GCT_LATENT_MAX_DIM, and
+ *     256 * t fits because Le <= 2^24.  Nothing else enters: the draw (item, k, t, d) does not depend on n, Le, k0, Kc,
+ *     the order of the molecules or the grid.
+ *   - z = fmaf(eps, expf(0.5f * log_var), mu), gct_reparam_fwd's form.
+ *   - term = 0.5f * fmaf(eps - z, eps + z, log_var) = log N(z; 0, 1) - log N(z; mu, exp(log_var)): the log 2 pi terms
+ *     cancel, and (z - mu)^2 / exp(log_var) is eps^2.
+ * Rows t >= rows[i] of z (and of eps_out) are written as exact zeros and add nothing to logw (gct_latent_interp's
+ * rule; the decoder never reads them through src_mask).
+ * logw[r] = the sum of the row's terms, each widened to fp64 and added in fp64, rounded once to fp32, in a fixed order:
+ * with nq = (D + 3) / 4 the quad (t, d >> 2) has the index q = t * nq + (d >> 2); work-item w of 256 adds the quads
+ * q = w, w + 256, ... in ascending order, the four elements of a quad in ascending d; the 64 work-items of a wave are
+ * summed by a butterfly (xor 32, 16, .. 1), and the four waves as (w0 + w1) + (w2 + w3).  No atomics: bit-reproducible,
+ * and independent of the grid (one workgroup per output row).
+ * mu == 0 and log_var == 0 give z == eps bit for bit and logw == 0 exactly: that is why the term is written with
+ * (eps - z) (eps + z) and not with squares.
+ * Limits: 1 <= D <= GCT_LATENT_MAX_DIM, 1 <= Le <= 2^24, n >= 0, Kc >= 0 (a zero writes nothing), k0 >= 0,
+ * k0 + Kc <= 2^31 - 1, n * Kc * Le <= 2^25, else GCT_ERR_ARG before a launch with the outputs untouched.
+ * 1 <= rows[i] <= Le and item[i] >= 0 are the caller's to check (ops.latent_iw does, on the host); the kernel clamps
+ * rows[i] into [1, Le] instead of reading outside the molecule. */
+#define GCT_IW_SITE 0x1A7E48u
+#define GCT_IW_C3 0x0D95748Fu
+int gct_latent_iw(const float* mu, const float* log_var, int n, int Le, int D, const int32_t* rows,
+                  const int32_t* item, int k0, int Kc, float* z, float* logw, float* eps_out, uint64_t seed,
+                  void* stream);
+/* logp (the decoder's log p(x | z_k), row i * K + k), logw (gct_latent_iw's) fp32 [n * K] -> per molecule, fp32 [n]
+ * each, with a_k = (double)logp + (double)logw, every step in fp64 and one rounding to fp32 at the end:
+ *   iwae  = m + log(sum_k exp(a_k - m)) - log K, m = max_k a_k (two passes: the maximum, then the sum)
+ *   elbo  = (sum_k a_k) / K
+ *   recon = (sum_k logp_k) / K
+ *   ess   = (sum_k w_k)^2 / sum_k w_k^2 with w_k = exp(a_k - m): the effective sample size, in [1, K]
+ * One wave per molecule: lane l holds k = l, l + 64, ... in ascending order, and the lanes are combined by a butterfly
+ * (xor 32, 16, .. 1).  No atomics: bit-reproducible.  K == 1 gives iwae == elbo bit for bit and ess == 1.
+ * Limits: n >= 0 (a zero writes nothing), K >= 1, n * K <= 2^31 - 1, else GCT_ERR_ARG before a launch. */
+int gct_iw_combine(const float* logp, const float* logw, int n, int K, float* iwae, float* elbo, float* recon,
+                   float* ess, void* stream);
+
 /* ---------------------------------------------------------- K7: cross-entropy */
 /* Train/trainer1.py:21-22  F.cross_entropy(logits.view(-1,V), ys, ignore_index=pad,
  * reduction='sum').  out[0] overwritten. ws >= 1024 floats. */
