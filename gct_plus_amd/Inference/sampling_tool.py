@@ -30,7 +30,11 @@ it runs one decode per prefix length and restores the input order.
 Log-likelihoods: `score` / `score_smiles` give log p(x | z, conditions, scaffold) of molecules the caller holds
 (decode.score_tokens: teacher-forced, one decoder forward), with the token accuracy next to it; `with_logp=True` makes
 `decode`, `sample_smiles` and `sample_multiple_smiles` return the model's log-probability of what they drew as one more
-element (KVDecoder.generate(return_logp=True): no second forward).
+element (KVDecoder.generate(return_logp=True): no second forward).  `with_stats=True` adds a decode.StepStats behind it:
+per generated token the model's entropy and, for the BEHAVIOUR distribution the token was really drawn from (top-k /
+nucleus / temperature and the grammar included), its log-probability, entropy and KL divergence from the model's
+(KVDecoder.generate(return_stats=True)) -- Train/finetune.behaviour_weights turns the two log-probabilities into the
+importance weights that correct a policy gradient on filtered or constrained samples.
 
 Marginal likelihoods: `marginal` / `marginal_smiles` estimate log p(x) itself, the latent integrated out, by the
 importance-weighted bound over K draws of the encoder's posterior (decode.marginal_logp; Burda et al.): one encoder
@@ -180,7 +184,7 @@ class Sampling:
                  scaler=None, device="cuda", seed: int = 0, use_graphs: bool = False, beam_size: int = 4,
                  beam_alpha: float = BEAM_ALPHA, top_k: Optional[int] = None, top_p: Optional[float] = None,
                  temperature: float = 1.0, stream_rows: Optional[int] = None, with_logp: bool = False,
-                 well_formed: bool = False):
+                 well_formed: bool = False, with_stats: bool = False):
         V = model.out.weight.shape[0]
         if well_formed and decode_algo in BEAM_ALGOS:
             raise ValueError(f"well_formed is not supported with decode_algo={decode_algo!r} (beam rows keep their history "
@@ -190,7 +194,10 @@ class Sampling:
         if with_logp and decode_algo in BEAM_ALGOS:
             raise ValueError(f"with_logp is not supported with decode_algo={decode_algo!r}: decode_beams / decode_unique "
                              "return the beams' scores, which are sums of log-probabilities already")
-        self.with_logp = bool(with_logp)
+        if with_stats and decode_algo in BEAM_ALGOS:
+            raise ValueError(f"with_stats is not supported with decode_algo={decode_algo!r}: decode_beams / decode_unique "
+                             "return the beams' scores, which are sums of log-probabilities already")
+        self.with_logp, self.with_stats = bool(with_logp), bool(with_stats)
         if stream_rows is not None:
             if decode_algo in BEAM_ALGOS:
                 raise ValueError(f"stream_rows is not supported with decode_algo={decode_algo!r} (beam search keeps its "
@@ -263,6 +270,10 @@ class Sampling:
         With stream_rows the n rows are a pool decoded by continuous batching; same layout, input order.
         with_logp (constructor): returns (ids, logp), logp [n] fp32 on the CPU = the model's log-probability of each
         row's generated tokens up to its <eos> (raw logits at temperature 1, whatever filter the draw went through).
+        with_stats (constructor): a decode.StepStats on the CPU follows (behind logp when both are on) -- per generated
+        token the model's entropy, the log-probability under the distribution the token was really drawn from (filter,
+        temperature and grammar included), that distribution's entropy and its KL divergence from the model's, and
+        behaviour_logp_sum [n] (KVDecoder.generate(return_stats=True)).
         return_rows=True appends a DecodedRows (what this decode consumed, and its token rows cut at each row's <eos>):
         `score(*rows)` / `logp(*rows)` score exactly what was decoded.  ValueError with beam search."""
         if return_rows and self.decode_algo == "beam":
@@ -283,13 +294,18 @@ class Sampling:
         zs, ys, src_mask, dconds = self._start_rows(zs, ys, src_mask, dconds)
         kw = dict(algo=self.decode_algo, seed=self.seed, use_graphs=self.use_graphs, prefix_lens=prefix_lens,
                   top_k=self.top_k, top_p=self.top_p, temperature=self.temperature, return_logp=self.with_logp,
-                  grammar=self.grammar)
+                  grammar=self.grammar, return_stats=self.with_stats)
         if self.stream_rows is not None:
             out = self.kv.generate_stream(ys, self.max_strlen, **kw)
-            res = (out[0], out[3].cpu()) if self.with_logp else out[0]
+            out = (out[0],) + tuple(out[2:])                       # (without the schedule's record)
         else:
             out = self.kv.generate(ys, self.max_strlen, **kw)
-            res = (out[0], out[2].cpu()) if self.with_logp else out
+        if self.with_logp or self.with_stats:                      # (ys, [token_logp, logp], [StepStats])
+            res = (out[0],) + ((out[2].cpu(),) if self.with_logp else ())
+            if self.with_stats:
+                res += (out[-1]._make(t.cpu() for t in out[-1]),)
+        else:
+            res = out[0] if self.stream_rows is not None else out
         return self._with_rows(res, zs, ys, src_mask, dconds, prefix_lens) if return_rows else res
 
     def _start_rows(self, zs, ys, src_mask, dconds, beams=None):
@@ -309,8 +325,9 @@ class Sampling:
 
     def _with_rows(self, res, zs, ys0, src_mask, dconds, prefix_lens):
         """decode's result with the DecodedRows of the call appended."""
-        rows = self._decoded_rows(res[0] if self.with_logp else res, zs, ys0.size(1), src_mask, dconds, prefix_lens)
-        return res + (rows,) if self.with_logp else (res, rows)
+        extras = self.with_logp or self.with_stats
+        rows = self._decoded_rows(res[0] if extras else res, zs, ys0.size(1), src_mask, dconds, prefix_lens)
+        return res + (rows,) if extras else (res, rows)
 
     def _decoded_rows(self, ids, zs, t0, src_mask, dconds, prefix_lens):
         """The DecodedRows of decoded ids [n, L] (prefixes of width t0, or prefix_lens): token rows cut at each row's
@@ -654,14 +671,15 @@ class Sampling:
         return (smiles, toklen, [len(tokenize(s, self.add_sep)) for s in smiles]) + tail
 
     def _split(self, outs, return_rows):
-        """decode's result -> (ids, what follows them: logp with with_logp, the DecodedRows with return_rows)."""
-        if self.with_logp or return_rows:
+        """decode's result -> (ids, what follows them: logp with with_logp, the StepStats with with_stats, the
+        DecodedRows with return_rows)."""
+        if self.with_logp or self.with_stats or return_rows:
             return outs[0], tuple(outs[1:])
         return outs, ()
 
     def _finish(self, outs, toklen, skip=0, return_rows=False):
-        """with_logp: `outs` is decode's (ids, logp) and logp becomes the fourth element; return_rows: the DecodedRows
-        the last one."""
+        """with_logp: `outs` is decode's (ids, logp) and logp becomes the fourth element; with_stats: the StepStats
+        follows; return_rows: the DecodedRows the last one."""
         outs, tail = self._split(outs, return_rows)
         outs = outs.cpu().numpy()
         smiles = [self.id_to_smi(ids[skip:]) for ids in outs]

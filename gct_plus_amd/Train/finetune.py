@@ -36,9 +36,18 @@ an unbiased estimate of the ordinary objective -- a loss weighted that way, ever
     w, _ = sbs_importance_weights(sbs.logp, sbs.gumbel)         # [n, k]; reward [n * k], sample-major like the rows
     loss = -(w.view(-1) * (reward - reward.mean()) * sampler.logp(*rows).logp).sum() / w.shape[0]
 
+Rows drawn through top-k / nucleus / temperature or the grammar come from a behaviour distribution q that is not the
+policy pi, so a policy gradient on them is biased.  A sampler built with with_logp=True, with_stats=True reports both
+log-probabilities of every row, and `behaviour_weights` turns them into the importance weights rho = pi(x) / q(x) that
+both update functions take per molecule:
+
+    smiles, _, _, logp, stats, rows = sampler.sample_smiles(..., return_rows=True)
+    rho = behaviour_weights(logp, stats.behaviour_logp_sum, clip=5.0)
+    stats = reinforce_step(sampler, optimizer, rows, reward, weight=rho)
+
 Not covered: FlatDataParallel fine-tuning, value networks / GAE (the advantage is per molecule),
-sequence-level ratios (functions of logp and the old logp in torch), rows of deterministic beam search, per-step entropy
-during generate, a gradient into the prior or into old_token_logp."""
+sequence-level ratios (functions of logp and the old logp in torch), rows of deterministic beam search, a gradient into
+the prior or into old_token_logp."""
 import copy
 
 import torch
@@ -89,11 +98,44 @@ class _GradClip:
         return norm.clone(), ((coef > 0) & (coef < 1)).float()
 
 
-def reinforce_loss(logp, reward, baseline="mean"):
+def behaviour_weights(model_logp, behaviour_logp, clip=None):
+    """Per-molecule importance weights rho [n] = exp(model_logp - behaviour_logp) of rows sampled from a behaviour
+    distribution that is not the policy (a top-k / nucleus / temperature filter, the grammar): model_logp [n] the
+    policy's log-probability of each row (with_logp), behaviour_logp [n] the one under the distribution it was drawn
+    from (StepStats.behaviour_logp_sum).  clip (a finite number > 0, optional): rho is truncated at that value --
+    truncated importance sampling, a bounded variance for a bias towards the behaviour policy.  fp32, no graph, on the
+    device of model_logp.  ValueError for shapes that do not match, values that are not finite and a bad clip."""
+    lp = torch.as_tensor(model_logp).detach().float()
+    lq = torch.as_tensor(behaviour_logp).detach().float().to(lp.device)
+    if lp.dim() != 1 or lp.shape != lq.shape:
+        raise ValueError(f"behaviour_weights: model_logp {list(lp.shape)} and behaviour_logp {list(lq.shape)} must be "
+                         "vectors of one length")
+    if not (bool(torch.isfinite(lp).all()) and bool(torch.isfinite(lq).all())):
+        raise ValueError("behaviour_weights: the log-probabilities must be finite")
+    if clip is not None:
+        if isinstance(clip, bool) or not isinstance(clip, (int, float)) or not 0.0 < float(clip) < float("inf"):
+            raise ValueError(f"behaviour_weights: clip must be a finite number > 0 or None, got {clip!r}")
+    rho = torch.exp(lp - lq)
+    return rho if clip is None else rho.clamp(max=float(clip))
+
+
+def _check_weight(weight, n, what):
+    """weight [n] of reinforce_step / ppo_update as an fp32 vector without a graph; ValueError for another length or a
+    value that is negative or not finite."""
+    w = torch.as_tensor(weight).detach().float().reshape(-1)
+    if w.numel() != n:
+        raise ValueError(f"{what}: {w.numel()} weights for {n} sequences")
+    if not bool((torch.isfinite(w) & (w >= 0)).all()):
+        raise ValueError(f"{what}: the weights must be finite and >= 0")
+    return w
+
+
+def reinforce_loss(logp, reward, baseline="mean", weight=None):
     """-((reward - b) * logp).sum() / n over the n sequences of a batch: minimising it raises the log-likelihood of the
     sequences whose reward lies above the baseline b and lowers that of the others.  logp [n] (with a graph), reward [n]
     numbers (no gradient flows into them); baseline "mean": the batch mean of the reward, a float or a tensor
-    (broadcast against reward): that value, None: 0."""
+    (broadcast against reward): that value, None: 0.  weight [n] (optional, behaviour_weights): each sequence's
+    advantage reward - b is multiplied by its weight, after the baseline; None: the unweighted loss, bit for bit."""
     reward = torch.as_tensor(reward, dtype=logp.dtype).to(logp.device).detach().view(-1)
     if reward.numel() != logp.numel():
         raise ValueError(f"{reward.numel()} rewards for {logp.numel()} sequences")
@@ -105,7 +147,10 @@ def reinforce_loss(logp, reward, baseline="mean"):
         b = reward.mean()
     else:
         b = torch.as_tensor(baseline, dtype=logp.dtype).to(logp.device).detach()
-    return -((reward - b) * logp.view(-1)).sum() / logp.numel()
+    if weight is None:
+        return -((reward - b) * logp.view(-1)).sum() / logp.numel()
+    weight = _check_weight(weight, logp.numel(), "reinforce_loss").to(logp.device, logp.dtype)
+    return -((weight * (reward - b)) * logp.view(-1)).sum() / logp.numel()
 
 
 def frozen_prior(model):
@@ -119,13 +164,13 @@ def frozen_prior(model):
     return prior
 
 
-def regularised_loss(terms, reward, baseline="mean", entropy_coef=0.0, kl_coef=0.0):
-    """reinforce_loss(terms.logp, reward, baseline) + (kl_coef * terms.kl.sum() - entropy_coef * terms.entropy.sum()) / n
+def regularised_loss(terms, reward, baseline="mean", entropy_coef=0.0, kl_coef=0.0, weight=None):
+    """reinforce_loss(terms.logp, reward, baseline, weight) + (kl_coef * terms.kl.sum() - entropy_coef * terms.entropy.sum()) / n
     over the n sequences of a PolicyTerms (decode.sequence_policy): the REINFORCE surrogate, minus an entropy bonus on
     the policy's next-token distributions, plus a penalty on their KL divergence from the prior's -- both summed over
     the scored tokens.  A coefficient of 0 leaves its term out (terms.kl may then be None); kl_coef != 0 needs terms
     computed with a prior, entropy_coef != 0 terms with the entropy: ValueError otherwise."""
-    loss = reinforce_loss(terms.logp, reward, baseline)
+    loss = reinforce_loss(terms.logp, reward, baseline, weight)
     n = terms.logp.numel()
     if kl_coef != 0:
         if terms.kl is None:
@@ -139,7 +184,7 @@ def regularised_loss(terms, reward, baseline="mean", entropy_coef=0.0, kl_coef=0
 
 
 def reinforce_step(sampler, optimizer, rows, reward, baseline="mean", entropy_coef=0.0, kl_coef=0.0, prior=None,
-                   max_grad_norm=None):
+                   max_grad_norm=None, weight=None):
     """One policy-gradient update of sampler.model on the decoded rows `rows` (a DecodedRows, or any argument tuple of
     Sampling.logp) with one reward per row: model.train(), sampler.logp(*rows), optimizer.zero_grad(set_to_none=True),
     reinforce_loss -> backward -> optimizer.step(), model.eval().  Returns dict(loss, mean_reward, mean_logp, tokens),
@@ -158,6 +203,11 @@ def reinforce_step(sampler, optimizer, rows, reward, baseline="mean", entropy_co
     other optimizer gets torch.nn.utils.clip_grad_norm_ over its parameters between backward() and step().  Whenever
     clipping is active the result also holds grad_norm (pre-clip) and clipped (bool: the update was scaled down), read
     in the same one transfer.  Not a finite number > 0: ValueError before any device work.
+
+    weight [n] (optional; behaviour_weights of rows drawn through a filter or the grammar): every molecule's advantage
+    is multiplied by its weight after the baseline (reinforce_loss).  The result then also holds weight_mean and
+    weight_max, read in the same one transfer.  None: the step as it is without, bit for bit.  A wrong length or a
+    value that is negative or not finite: ValueError before any device work.
 
     The model runs in training mode, so its dropout is live in this forward: the logp of the step is not the eval-mode
     number `with_logp` reported for the same rows (build the model with dropout 0 where the two must agree).  The prior
@@ -179,14 +229,16 @@ def reinforce_step(sampler, optimizer, rows, reward, baseline="mean", entropy_co
         raise ValueError("reinforce_step: kl_coef needs a prior (frozen_prior of the pretrained model)")
     gclip = _GradClip(optimizer, max_grad_norm, "reinforce_step")
     reward = torch.as_tensor(reward, dtype=torch.float32)
+    if weight is not None:
+        weight = _check_weight(weight, reward.numel(), "reinforce_step")
     plain = entropy_coef == 0 and kl_coef == 0 and prior is None
     model.train()
     gclip.install()
     try:
         scores = sampler.logp(*rows) if plain else sampler.policy_terms(*rows, prior=prior)
         optimizer.zero_grad(set_to_none=True)
-        loss = (reinforce_loss(scores.logp, reward, baseline) if plain else
-                regularised_loss(scores, reward, baseline, entropy_coef, kl_coef))
+        loss = (reinforce_loss(scores.logp, reward, baseline, weight) if plain else
+                regularised_loss(scores, reward, baseline, entropy_coef, kl_coef, weight))
         loss.backward()
         gclip.step()
     finally:
@@ -201,7 +253,11 @@ def reinforce_step(sampler, optimizer, rows, reward, baseline="mean", entropy_co
             stats += [scores.kl.detach().sum() / tokens, scores.prior_logp.mean()]
     if gclip.active:
         stats += [t.to(dev) for t in gclip.norm_and_clipped()]
-    stats = torch.stack(stats).cpu().tolist()
+    if weight is not None:                                  # (at the end: the indices in front of them stay)
+        stats += [weight.to(dev).mean(), weight.to(dev).max()]
+        *stats, w_mean, w_max = torch.stack(stats).cpu().tolist()
+    else:
+        stats = torch.stack(stats).cpu().tolist()
     out = dict(loss=stats[0], mean_reward=stats[1], mean_logp=stats[2], tokens=int(stats[3]))
     if not plain:
         out["mean_entropy"] = stats[4]
@@ -209,6 +265,8 @@ def reinforce_step(sampler, optimizer, rows, reward, baseline="mean", entropy_co
             out["mean_kl"], out["mean_prior_logp"] = stats[5], stats[6]
     if gclip.active:
         out["grad_norm"], out["clipped"] = stats[-2], bool(stats[-1])
+    if weight is not None:
+        out["weight_mean"], out["weight_max"] = w_mean, w_max
     return out
 
 
@@ -257,7 +315,7 @@ def _row_slice(rows, lo, hi):
 
 def ppo_update(sampler, optimizer, rows, reward, epochs=4, clip=0.2, baseline="mean", normalize=False,
                old_token_logp=None, minibatch=None, target_kl=None, entropy_coef=0.0, kl_coef=0.0, prior=None,
-               train_mode=False, max_grad_norm=None):
+               train_mode=False, max_grad_norm=None, weight=None):
     """Several policy updates of sampler.model on ONE scored batch: `epochs` passes over the decoded rows `rows` (a
     DecodedRows, or any argument tuple of Sampling.logp) with one reward per row, each pass minimising ppo_loss --
     PPO's clipped surrogate of every scored token's probability ratio against the sampling-time policy, which holds the
@@ -287,7 +345,11 @@ def ppo_update(sampler, optimizer, rows, reward, epochs=4, clip=0.2, baseline="m
 
     max_grad_norm as in reinforce_step, applied to every minibatch update; whenever clipping is active each epoch's
     dict also holds grad_norm (the largest pre-clip norm over the epoch's minibatch updates) and clipped_updates (how
-    many of them were scaled down), read in the same one transfer."""
+    many of them were scaled down), read in the same one transfer.
+
+    weight [n] (optional; behaviour_weights): every molecule's advantage is multiplied by its weight, once, after the
+    baseline and the normalisation; each epoch's dict then also holds weight_mean and weight_max.  None: the update as
+    it is without, bit for bit."""
     model = sampler.model
     if kl_coef != 0 and prior is None:
         raise ValueError("ppo_update: kl_coef needs a prior (frozen_prior of the pretrained model)")
@@ -301,6 +363,8 @@ def ppo_update(sampler, optimizer, rows, reward, epochs=4, clip=0.2, baseline="m
     reward = torch.as_tensor(reward, dtype=torch.float32).view(-1)
     if reward.numel() != n:
         raise ValueError(f"{reward.numel()} rewards for {n} sequences")
+    if weight is not None:
+        weight = _check_weight(weight, n, "ppo_update").cpu()
     m = n if minibatch is None else min(int(minibatch), n)
     with_entropy = entropy_coef != 0
     gclip = _GradClip(optimizer, max_grad_norm, "ppo_update")
@@ -309,6 +373,8 @@ def ppo_update(sampler, optimizer, rows, reward, epochs=4, clip=0.2, baseline="m
     gclip.install()
     try:
         adv = advantages(reward.to(sampler.device), baseline, normalize).cpu()   # the device's arithmetic, as
+        if weight is not None:
+            adv = adv * weight
         if old_token_logp is None:                                               # reinforce_loss's; checked on the host
             with torch.no_grad():
                 old_token_logp = sampler.logp(*rows).token_logp
@@ -350,6 +416,8 @@ def ppo_update(sampler, optimizer, rows, reward, epochs=4, clip=0.2, baseline="m
                 out["mean_kl"], out["mean_prior_logp"] = s[-2] / tokens, s[-1] / n
             if gclip.active:
                 out["clipped_updates"], out["grad_norm"] = int(clip_stats[0]), clip_stats[1]
+            if weight is not None:                     # (on the host already: no transfer)
+                out["weight_mean"], out["weight_max"] = float(weight.mean()), float(weight.max())
             history.append(out)
     finally:
         gclip.restore()

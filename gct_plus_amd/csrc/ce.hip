@@ -86,21 +86,8 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
 // One wave, one logits row lr[0, V), 0 <= tok < V (uniform over the wave): returns x[tok] - m - log(sum exp(x - m)) on
 // every lane; hit = tok is the FIRST maximum of the row (torch.argmax).
 __device__ __forceinline__ float wave_token_logp(const float* __restrict__ lr, int V, int tok, int lane, bool& hit) {
-  float mx = -INFINITY;
-  for (int c = lane; c < V; c += 64) mx = fmaxf(mx, lr[c]);
-  mx = gct_wave_max(mx);
-  float se = 0.f;
-  int first = 0x7fffffff;                               // lowest index that holds the maximum
-  for (int c = lane; c < V; c += 64) {
-    const float x = lr[c];
-    se += expf(x - mx);
-    if (x == mx && c < first) first = c;
-  }
-  se = gct_wave_sum(se);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
-  hit = first == tok;
-  return (lr[tok] - mx) - logf(se);
+  float mx, lse;
+  return gct_wave_token_logp(lr, V, tok, lane, hit, mx, lse);                // (common.h: shared with gct_step_stats)
 }
 
 // The clipped surrogate of one scored token (decode.py ppo_reference states the rule): lp its log-probability now, old
@@ -165,7 +152,7 @@ constexpr int SEQ_LOGP_MAX_W = 256;
 
 // A token id that can be scored at all: not pad, and inside the vocabulary.
 __device__ __forceinline__ bool token_scored(int64_t tok, int64_t pad_id, int V) {
-  return tok != pad_id && tok >= 0 && tok < V;
+  return gct_token_scored(tok, pad_id, V);
 }
 
 // The geometry every seq_* entry point takes: token rows ys [n, W] (row stride ld_ys), prefix lengths (null: 1 each),

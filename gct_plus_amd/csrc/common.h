@@ -130,6 +130,34 @@ __device__ __forceinline__ void gct_wave_softmax_stats(const float* lr, int V, i
   se = gct_wave_sum(se);
 }
 
+// A token id that can be scored at all: not pad, and inside the vocabulary.
+__device__ __forceinline__ bool gct_token_scored(int64_t tok, int64_t pad_id, int V) {
+  return tok != pad_id && tok >= 0 && tok < V;
+}
+// One wave, one logits row lr[0, V), 0 <= tok < V (uniform over the wave): returns x[tok] - m - log(sum exp(x - m)) on
+// every lane, with m and the log of the sum; hit = tok is the FIRST maximum of the row (torch.argmax).  The one place
+// where a token's log-probability is computed: the scored-token kernels (ce.hip) and the decode step's statistics
+// (gct_step_stats) give the same bits for the same row and token.
+__device__ __forceinline__ float gct_wave_token_logp(const float* __restrict__ lr, int V, int tok, int lane, bool& hit,
+                                                     float& mx, float& lse) {
+  mx = -INFINITY;
+  for (int c = lane; c < V; c += 64) mx = fmaxf(mx, lr[c]);
+  mx = gct_wave_max(mx);
+  float se = 0.f;
+  int first = 0x7fffffff;                               // lowest index that holds the maximum
+  for (int c = lane; c < V; c += 64) {
+    const float x = lr[c];
+    se += expf(x - mx);
+    if (x == mx && c < first) first = c;
+  }
+  se = gct_wave_sum(se);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
+  hit = first == tok;
+  lse = logf(se);
+  return (lr[tok] - mx) - lse;
+}
+
 // bijective XCD-aware remap of a 1-D block id: blocks that share an XCD (id % 8)
 // get a contiguous range of logical ids (cdna guide T1).
 __device__ __forceinline__ unsigned gct_xcd_remap(unsigned bid, unsigned nblk) {

@@ -6,6 +6,8 @@
 //                      per-sample finished mask
 //   gct_grammar_mask : constrained decoding -- a copy of the step's logits with -inf on every token the SMILES grammar
 //                      or the row's length budget forbids, for gct_select_token to choose from
+//   gct_step_stats   : behind the selection -- the model's entropy and the log-probability, entropy and KL divergence of
+//                      the distribution the token was really drawn from (gct_select_token's probs_out)
 //   gct_stream_refill : continuous batching -- rows that finished hand out their tokens and take the next pool item
 //   gct_attn_decode_beam / gct_beam_select : the same two for beam search, with the self-attention caches
 //                      shared by ancestry through a per-row map (kv_src) instead of copied
@@ -656,6 +658,70 @@ __global__ __launch_bounds__(256) void grammar_mask_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------------- step statistics
+// Behind the selection (decode.py step_stats_reference states the rules): one wave per row, chosen_logp_kernel's slot
+// and early returns.  pi = softmax of the RAW logits row, through gct_wave_token_logp (gct_chosen_logp's bits); q = the
+// distribution the token was drawn from -- the probs row gct_select_token wrote, pi itself without one, the one-hot at
+// the token under greedy.  Lane l handles tokens l, l + 64, ...: one pass over both rows behind the log-softmax's two
+// (a row is at most a few KB: it comes from HBM once and from the cache after that; the probs row is read once, the
+// chosen token's entry is picked up on the way).  A term with q == 0 (pi == 0) adds exactly 0.
+__global__ __launch_bounds__(256) void step_stats_kernel(
+    const float* __restrict__ logits, const float* __restrict__ probs, int V, const int64_t* __restrict__ ys,
+    int64_t ld_ys, const int32_t* __restrict__ pos, const int32_t* __restrict__ row_off,
+    const int32_t* __restrict__ item, const int32_t* __restrict__ prefix_len, int64_t pad_id, int greedy,
+    float* __restrict__ model_entropy, float* __restrict__ behaviour_logp, float* __restrict__ behaviour_entropy,
+    float* __restrict__ behaviour_kl, int64_t ld_out, int out_rows, int n) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= n) return;
+  const GctRowSlot s = gct_row_slot(*pos + 1, row, row_off != nullptr, row_off, item != nullptr, item, prefix_len);
+  if (!s.acts()) return;                                    // parked, or a prefix token (uniform: a whole wave leaves)
+  const int p = s.pos, dst = s.item;
+  if (p < 0 || p >= ld_out || p >= ld_ys || dst >= out_rows) return;
+  const int64_t tok64 = ys[(int64_t)row * ld_ys + p];
+  float me = 0.f, bl = 0.f, be = 0.f, kl = 0.f;             // pad (a finished row): all four stay 0
+  if (gct_token_scored(tok64, pad_id, V)) {
+    const int tok = (int)tok64;
+    const float* lr = logits + (int64_t)row * V;
+    const float* qr = probs && !greedy ? probs + (int64_t)row * V : nullptr;
+    bool hit;
+    float mx, lse;
+    const float lp = gct_wave_token_logp(lr, V, tok, lane, hit, mx, lse);
+    float s_pi = 0.f, s_q = 0.f, s_kl = 0.f, qt = 0.f;      // sums of pi log pi, q log q, q (log q - log pi)
+    for (int c = lane; c < V; c += 64) {
+      const float lpi = (lr[c] - mx) - lse, pi = expf(lpi);
+      if (pi != 0.f) s_pi += pi * lpi;
+      if (qr) {
+        const float q = qr[c];
+        if (q > 0.f) {
+          const float lq = logf(q);
+          s_q += q * lq;
+          s_kl += q * (lq - lpi);
+        }
+        if (c == tok) qt = q;
+      }
+    }
+    me = 0.f - gct_wave_sum(s_pi);
+    if (greedy) {                                           // one-hot at tok: log q = 0, H(q) = 0, KL = -log pi(tok)
+      kl = 0.f - lp;
+    } else if (!qr) {                                       // q = pi
+      bl = lp;
+      be = me;
+    } else {
+      bl = logf(__shfl(qt, tok & 63, 64));
+      be = 0.f - gct_wave_sum(s_q);
+      kl = gct_wave_sum(s_kl);
+    }
+  }
+  if (lane == 0) {
+    const int64_t o = (int64_t)dst * ld_out + p;
+    if (model_entropy) model_entropy[o] = me;
+    if (behaviour_logp) behaviour_logp[o] = bl;
+    if (behaviour_entropy) behaviour_entropy[o] = be;
+    if (behaviour_kl) behaviour_kl[o] = kl;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------- continuous batching
 // gct_stream_refill, kernel 1 of 2 (decode.py stream_schedule_reference states the rule): one workgroup walks the rows
 // in ascending order, 256 at a time.  A row is FINISHED when its item set `done` or produced limit[item] tokens in the
@@ -1156,6 +1222,25 @@ extern "C" int gct_grammar_mask(const float* logits, float* masked, int V, const
   hipLaunchKernelGGL(grammar_mask_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits,
                      masked, V, table, ys, ld_ys, T, n, pos, row_off, gram, item, prefix_len, limit);
   GCT_LAUNCH_CHECK("grammar_mask");
+  return GCT_OK;
+}
+
+extern "C" int gct_step_stats(const float* logits, const float* probs, int V, const int64_t* ys, int64_t ld_ys,
+                              const int32_t* pos, const int32_t* row_off, const int32_t* item,
+                              const int32_t* prefix_len, int64_t pad_id, int greedy, float* model_entropy,
+                              float* behaviour_logp, float* behaviour_entropy, float* behaviour_kl, int64_t ld_out,
+                              int out_rows, int n, void* stream) {
+  GCT_CHECK_ARG(logits && ys && pos && n >= 0 && V >= 1 && ld_ys > 0 && ld_out > 0 && out_rows >= 0,
+                "step_stats: bad args");
+  GCT_CHECK_ARG(model_entropy || behaviour_logp || behaviour_entropy || behaviour_kl,
+                "step_stats: all four outputs are null");
+  GCT_CHECK_ARG(!item == !prefix_len && (!item || row_off), "step_stats: streamed rows need item, prefix_len and row_off");
+  GCT_CHECK_ARG(item || out_rows >= n, "step_stats: %d output rows for %d decode rows", out_rows, n);
+  if (n == 0) return GCT_OK;
+  hipLaunchKernelGGL(step_stats_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, probs,
+                     V, ys, ld_ys, pos, row_off, item, prefix_len, pad_id, greedy, model_entropy, behaviour_logp,
+                     behaviour_entropy, behaviour_kl, ld_out, out_rows, n);
+  GCT_LAUNCH_CHECK("step_stats");
   return GCT_OK;
 }
 

@@ -74,6 +74,13 @@ re-derives the row's grammar state from the tokens it has generated (nothing to 
 at a stream refill) and writes a copy of the logits with -inf on every token that has no transition or would leave the
 row unable to reach <eos> inside its length budget, which it reads from device memory.  Every row then ends with <eos>
 and parses.  The guarantee is syntactic only: valence, aromaticity and ring-bond consistency need a chemistry toolkit.
+
+Per-step sampling statistics (`generate` / `generate_stream(return_stats=True)`): the rules are stated once, in
+`step_stats_reference`.  return_logp is the MODEL's log-probability of a token; under a filter or the grammar the token
+was drawn from another distribution, the behaviour distribution q.  gct_step_stats runs behind the selection, on the raw
+logits and the normalised weights gct_select_token leaves in buf['probs'], and records per generated token the model's
+entropy, log q(token), q's entropy and KL(q || model) -- the diagnostics of a collapsing policy without a second
+forward, and, summed per row, the denominator of the importance weights Train/finetune.behaviour_weights forms.
 """
 from __future__ import annotations
 
@@ -111,6 +118,7 @@ FILTERED = "filtered"                               # StepPlan.select: the filte
 UNIFORM, MIXED, STREAM = "uniform", "mixed", "stream"      # StepPlan.layout
 LOGP = "logp"                                       # graph key suffix of a step unit that records log-probabilities
 GRAMMAR = "grammar"                                 # graph key suffix of a step unit that masks the logits by a grammar
+STATS = "stats"                                     # graph key suffix of a step unit that records the step statistics
 STREAM_COND_CHUNK = 256                             # items per GEMM when the pool's condition rows are projected
 TOP_K_FLOOR = 1e-6                                  # weight of a token outside the top k (the reference's top_k_logits)
 
@@ -124,30 +132,33 @@ class StepPlan:
       layout   UNIFORM: every row at the shared position.  MIXED: the kernels get row_off.  STREAM: row_off plus the
                rows' item and prefix_len, and the unit ends with the refill (KVDecoder._rows is the row view);
       grammar  gct_grammar_mask runs in front of the selection;
-      logp     gct_chosen_logp runs behind it.
+      logp     gct_chosen_logp runs behind it;
+      stats    gct_step_stats runs behind it too, and a multinomial draw through a filter or a grammar leaves the
+               distribution it drew from in buf['probs'] for it.
     ValueError for what the unit cannot do: beam rows keep their history behind kv_src and their scores are
-    log-probabilities already, so BEAM and SBEAM go with UNIFORM and neither grammar nor logp."""
+    log-probabilities already, so BEAM and SBEAM go with UNIFORM and neither grammar, logp nor stats."""
     select: object = 0
     layout: str = UNIFORM
     grammar: bool = False
     logp: bool = False
+    stats: bool = False
 
     def __post_init__(self):
-        select, layout, grammar, logp = dataclasses.astuple(self)
+        select, layout, grammar, logp, stats = dataclasses.astuple(self)
         if select not in (0, 1, FILTERED, BEAM, SBEAM) or layout not in (UNIFORM, MIXED, STREAM):
             raise ValueError(f"no step unit selects {select!r} over {layout!r} rows")
-        if select in (BEAM, SBEAM) and (layout != UNIFORM or grammar or logp):
-            raise ValueError(f"the {'stochastic ' * (select == SBEAM)}beam step takes uniform rows, no grammar and no "
-                             "log-probabilities")
+        if select in (BEAM, SBEAM) and (layout != UNIFORM or grammar or logp or stats):
+            raise ValueError(f"the {'stochastic ' * (select == SBEAM)}beam step takes uniform rows, no grammar, no "
+                             "log-probabilities and no step statistics")
 
     @functools.cached_property
     def key(self):
         """THE statement of the graph key (KVDecoder.graphs; bench.py, the tools and the tests read it): `select` alone
         for plain uniform rows -- the only rows BEAM ("beam") and SBEAM ("sbeam") have; (select, layout) for another
-        layout; and with a grammar and / or log-probabilities (select, layout[, GRAMMAR][, LOGP]), uniform spelled out.
-        A stream unit has k[1] == STREAM, logp k[-1] == LOGP."""
-        select, layout, grammar, logp = dataclasses.astuple(self)
-        tail = (GRAMMAR,) * bool(grammar) + (LOGP,) * bool(logp)
+        layout; and with a grammar, log-probabilities and / or step statistics (select, layout[, GRAMMAR][, LOGP][,
+        STATS]), uniform spelled out.  A stream unit has k[1] == STREAM; a unit without stats has logp k[-1] == LOGP."""
+        select, layout, grammar, logp, stats = dataclasses.astuple(self)
+        tail = (GRAMMAR,) * bool(grammar) + (LOGP,) * bool(logp) + (STATS,) * bool(stats)
         if layout == UNIFORM and not tail:
             return select
         return (select, layout) + tail
@@ -460,6 +471,61 @@ def score_reference(logits, ys, prefix_lens, pad_id):
     token_logp, logp = _column_sums(scored, lsm.gather(-1, tgt.unsqueeze(-1)).squeeze(-1))
     hit = scored & (x.argmax(-1) == tgt)
     return token_logp, logp, scored.sum(1).to(ys.device, torch.int32), hit.sum(1).to(torch.int32)
+
+
+class StepStats(NamedTuple):
+    """What generate / generate_stream(return_stats=True) return behind their other results (step_stats_reference states
+    the per-step rules): four fp32 tables [n, L] laid out like ys -- kept on a row's generated span up to its first
+    <eos> (return_logp's span), 0 elsewhere -- and behaviour_logp_sum [n], the row sum of behaviour_logp: the
+    log-probability of the row under the distribution it was actually sampled from."""
+    model_entropy: torch.Tensor
+    behaviour_logp: torch.Tensor
+    behaviour_entropy: torch.Tensor
+    behaviour_kl: torch.Tensor
+    behaviour_logp_sum: torch.Tensor
+
+
+def step_stats_reference(logits, probs, tok, pad_id, greedy=False):
+    """THE statement of the per-step sampling statistics (gct_step_stats implements it behind the selection), in fp64
+    on the host.  logits [n, V]: the step's RAW logits; tok [n]: the token each row received; probs [n, V] or None:
+    the normalised weights the draw used (gct_select_token's probs_out), taken as given.
+      pi = softmax(logits) at temperature 1, in log-sum-exp form (score_reference's);
+      q  = the BEHAVIOUR distribution the token was drawn from: probs; pi itself when probs is None; the one-hot at tok
+           when greedy (probs is ignored).
+    Returns fp64 [n] each:
+      model_entropy     -sum pi log pi                       behaviour_logp  log q(tok)
+      behaviour_entropy -sum_{q > 0} q log q                 behaviour_kl    sum_{q > 0} q (log q - log pi)
+    A term with q == 0 (pi == 0) adds exactly 0.  A row whose token is pad_id (a finished row; or no token of the
+    vocabulary) gives four zeros.  With probs None and not greedy log q IS log pi: behaviour_logp is the model's
+    log-probability (score_reference's), behaviour_entropy is model_entropy and behaviour_kl is exactly 0."""
+    x = torch.as_tensor(logits).double()
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise ValueError(f"logits must be [n, V >= 1], got {list(x.shape)}")
+    n, V = x.shape
+    tok = torch.as_tensor(tok).long().reshape(-1)
+    if tok.numel() != n:
+        raise ValueError(f"tok must hold {n} tokens, got {tok.numel()}")
+    live = (tok != pad_id) & (tok >= 0) & (tok < V)
+    at = tok.clamp(0, V - 1).view(n, 1)
+    y = x - x.max(-1, keepdim=True).values
+    lpi = y - torch.log(torch.exp(y).sum(-1, keepdim=True))
+    pi, zero = torch.exp(lpi), torch.zeros((), dtype=torch.float64)
+    if greedy:
+        q = torch.zeros_like(pi).scatter_(1, at, 1.0)
+        lq = torch.zeros_like(pi)
+    elif probs is None:
+        q, lq = pi, lpi
+    else:
+        q = torch.as_tensor(probs).double()
+        if q.shape != x.shape:
+            raise ValueError(f"probs must have the shape of logits {list(x.shape)}, got {list(q.shape)}")
+        lq = torch.log(torch.where(q > 0, q, torch.ones_like(q)))
+    model_entropy = -torch.where(pi > 0, pi * lpi, zero).sum(-1)
+    qt = q.gather(1, at).view(n)
+    behaviour_logp = torch.where(qt > 0, lq.gather(1, at).view(n), torch.full((), -math.inf, dtype=torch.float64))
+    behaviour_entropy = -torch.where(q > 0, q * lq, zero).sum(-1)
+    behaviour_kl = torch.where(q > 0, q * (lq - lpi), zero).sum(-1)
+    return tuple(torch.where(live, v, zero) for v in (model_entropy, behaviour_logp, behaviour_entropy, behaviour_kl))
 
 
 def _scored_rows(logits, ys, prefix_lens, pad_id):
@@ -1518,6 +1584,7 @@ class KVDecoder:
             self.seed = torch.zeros(1, dtype=torch.int64, device=dev)      # multinomial seed of this generate()
             self.filt = torch.zeros(4, dtype=torch.int32, device=dev)      # GctSampleFilter of this generate()
             self.gram = self.gtable = None                                 # grammar buffers: the first _set_sampling with one
+            self.stats_tab = None                                          # return_stats: the first call that asks for them
             # beam search state (generate_beam), per row: score, finished, length, parent; the ancestry map; done [n/k]
             self.beams = beams
             self.bscores = torch.zeros(n, device=dev)
@@ -1731,7 +1798,9 @@ class KVDecoder:
         """softmax + choice of the next token from buf['logits']; written at ys[:, *pos + 1] (device position).
         BEAM: gct_beam_select (beam state, the kv_src map and bdone in place); SBEAM: gct_beam_select_gumbel.  FILTERED: the multinomial draw through the
         top-k / nucleus / temperature settings in self.filt.  With a grammar the choice is made from a masked copy of
-        the logits (gct_grammar_mask, one launch more); buf['logits'] stays raw for _chosen_logp."""
+        the logits (gct_grammar_mask, one launch more); buf['logits'] stays raw for _chosen_logp and _step_stats.  A
+        unit with stats has a multinomial draw through a filter or a grammar write the distribution it drew from to
+        buf['probs'] (_behaviour_probs)."""
         if plan.select == BEAM:
             ops.beam_select(self.buf["logits"], self.beams, self.bscores, self.bfin, self.blen, self.ys, self.valid,
                             self.off, self.kv_src, self.bdone, self.pos, self.pad_id, self.eos_id,
@@ -1750,7 +1819,7 @@ class KVDecoder:
         filtered = plan.select == FILTERED
         ops.select_token(logits, self.ys, 0, self.valid, self.done, 1 if filtered else plan.select,
                          self.pad_id, self.eos_id, pos_dev=self.pos, valid_off=self.off, seed_dev=self.seed,
-                         filt_dev=self.filt if filtered else None,
+                         filt_dev=self.filt if filtered else None, probs_out=self._behaviour_probs(plan),
                          item_base=self.stream["item_base"] if plan.layout == STREAM else 0, **self._rows(plan))
 
     def _advance(self, plan):
@@ -1759,6 +1828,8 @@ class KVDecoder:
         self._select(plan)
         if plan.logp:
             self._chosen_logp(plan)                      # before the refill, which reassigns the rows' items
+        if plan.stats:
+            self._step_stats(plan)
         if plan.layout == STREAM:
             self.stream["state"].refill()
 
@@ -1767,6 +1838,43 @@ class KVDecoder:
         row's own column, or, streamed, into the pool's table at (item, column)."""
         out = self.stream["out_logp"] if plan.layout == STREAM else self.tok_logp
         ops.chosen_logp(self.buf["logits"], self.ys, self.pos, out, self.pad_id, **self._rows(plan))
+
+    def _behaviour_probs(self, plan):
+        """buf['probs'] [n, V] where a unit with stats draws from another distribution than the model's softmax -- a
+        multinomial draw through a filter or a grammar -- and None otherwise (greedy: the one-hot at the token; the
+        plain multinomial draw: the softmax itself).  A function of the plan alone, as a captured graph needs it;
+        allocated with the rows' first such unit, like buf['masked']."""
+        if not plan.stats or plan.select == 0 or not (plan.select == FILTERED or plan.grammar):
+            return None
+        if "probs" not in self.buf:
+            self.buf["probs"] = torch.empty_like(self.buf["logits"])
+        return self.buf["probs"]
+
+    def _stats_tables(self, plan, zero=False):
+        """The four tables gct_step_stats writes, [4, rows, T]: the decoder's own, laid out like ys, or, streamed, the
+        pool's, per (item, column).  Allocated with the first call that asks for statistics."""
+        st = self.stream if plan.layout == STREAM else None
+        tab = self.stats_tab if st is None else st.get("out_stats")
+        if tab is None:
+            tab = torch.zeros(len(ops.STEP_STATS), self.n if st is None else st["items"], self.T, device=self.ys.device)
+            if st is None:
+                self.stats_tab = tab
+            else:
+                st["out_stats"] = tab
+        elif zero:
+            tab.zero_()
+        return tab
+
+    def _step_stats(self, plan):
+        """The statistics of the draw _select has just made (gct_step_stats), at _chosen_logp's (row, column)."""
+        ops.step_stats(self.buf["logits"], self._behaviour_probs(plan), self.ys, self.pos, self.pad_id,
+                       greedy=plan.select == 0, **dict(zip(ops.STEP_STATS, self._stats_tables(plan))),
+                       **self._rows(plan))
+
+    def _span_stats(self, plan, ys, lens, n_gen):
+        """StepStats of return_stats: the four tables through _span_logp, and behaviour_logp's row sum."""
+        kept = [self._span_logp(t, ys, lens, n_gen) for t in self._stats_tables(plan)]
+        return StepStats(*[t for t, _ in kept], kept[ops.STEP_STATS.index("behaviour_logp")][1])
 
     # ------------------------------------------------------------- what generate and generate_stream share
     def _check_sampling(self, algo, top_k, top_p, temperature):
@@ -1839,6 +1947,8 @@ class KVDecoder:
         self._select(plan)                                         # token t0 from the prefill's last position
         if plan.logp:
             self._chosen_logp(plan)
+        if plan.stats:
+            self._step_stats(plan)
         for i in range(1, steps):
             self._run_step(plan, use_graphs)                       # consumes token t0+i-1, writes token t0+i
             if check_every and (i + 1) % check_every == 0 and bool(done.all()):
@@ -1881,7 +1991,7 @@ class KVDecoder:
     # -------------------------------------------------------------------------------------
     @torch.no_grad()
     def generate(self, ys0, max_strlen=80, algo="greedy", seed=0, check_every=8, use_graphs=False, prefix_lens=None,
-                 top_k=None, top_p=None, temperature=1.0, return_logp=False, grammar=None):
+                 top_k=None, top_p=None, temperature=1.0, return_logp=False, grammar=None, return_stats=False):
         """Mirror of Sampling.decode: appends max_strlen-1 tokens to the prefix ys0 [n, t0]
         (stops early once every sample has produced <eos>, like the reference's break).
         prefix_lens (ints [n], 1 <= t0_r <= t0, optional): row r's prefix is ys0[r, :t0_r] (right-padded); it decodes
@@ -1900,7 +2010,12 @@ class KVDecoder:
         the tokens the grammar allows after the row's own generated tokens and that still let the row reach <eos> within
         its max_strlen - 1 tokens (gct_grammar_mask in front of the selection, one launch more per step; None: no launch).
         Every row then ends with <eos> and parses; the guarantee is syntactic, not chemical.  return_logp stays the
-        model's own log-probability (raw logits).  ValueError for max_strlen < 3 or a grammar of another vocabulary."""
+        model's own log-probability (raw logits).  ValueError for max_strlen < 3 or a grammar of another vocabulary.
+        return_stats=True: a StepStats comes last in the result -- per generated token the model's entropy, the
+        log-probability under the BEHAVIOUR distribution the token was really drawn from (through the filter, the
+        temperature and the grammar; the one-hot under greedy), that distribution's entropy and its KL divergence from
+        the model's (step_stats_reference states the rules; gct_step_stats, one small launch per step behind the
+        selection).  Combines with everything above; False: nothing of it runs."""
         check_grammar(grammar, self.model.out.weight.shape[0], max_strlen - 1)
         filt = self._check_sampling(algo, top_k, top_p, temperature)
         n, t0 = ys0.shape
@@ -1908,17 +2023,23 @@ class KVDecoder:
         lens = check_prefix_lens(prefix_lens, n, t0)
         self._check_room("generate", t0, steps)
         plan = StepPlan(self._set_sampling(algo, filt, seed, grammar, steps, t0), UNIFORM if lens is None else MIXED,
-                        grammar is not None, bool(return_logp))
+                        grammar is not None, bool(return_logp), bool(return_stats))
         if plan.logp:
             self.tok_logp.zero_()
+        if plan.stats:                                  # (both buffers exist before a step is run or captured)
+            self._stats_tables(plan, zero=True)
+            self._behaviour_probs(plan)
         last = self._lockstep(plan, ys0, lens, steps, self.done, check_every, use_graphs)
         lens = row_prefix_lens(lens, n, t0)
         ys, is_eos = self._cut_at_eos(self.ys[:, :last], lens, t0)
-        if not plan.logp:
+        if not (plan.logp or plan.stats):
             return ys.clone()
         # a row's generated span: from its own t0_r to its first <eos>, or all G columns without one
         n_gen = torch.where(is_eos.any(dim=1), is_eos.int().argmax(dim=1) + 1, is_eos.size(1))
-        return (ys.clone(),) + self._span_logp(self.tok_logp, ys, lens, n_gen)
+        out = (ys.clone(),)
+        if plan.logp:
+            out += self._span_logp(self.tok_logp, ys, lens, n_gen)
+        return out + (self._span_stats(plan, ys, lens, n_gen),) if plan.stats else out
 
     @torch.no_grad()
     def generate_beam(self, ys0, beam_size, max_strlen=80, alpha=BEAM_ALPHA, check_every=8, use_graphs=False,
@@ -2048,7 +2169,7 @@ class KVDecoder:
     @torch.no_grad()
     def generate_stream(self, ys0, max_strlen=80, algo="greedy", seed=0, prefix_lens=None, max_new_tokens=None,
                         top_k=None, top_p=None, temperature=1.0, use_graphs=False, check_every=8, return_logp=False,
-                        grammar=None):
+                        grammar=None, return_stats=False):
         """Decode the pool of start_stream with continuous batching: item i starts from the prefix ys0[i, :t0_i]
         (ys0 [N, t0_max], prefix_lens ints [N] or None = all t0_max) and generates until <eos> or max_new_tokens[i]
         tokens (ints [N] in [1, max_strlen - 1]; None: max_strlen - 1); a row that finishes takes the next item
@@ -2064,6 +2185,7 @@ class KVDecoder:
         elsewhere, logp [N] its row sum (generate()'s return_logp).
         grammar (a SmilesGrammar, optional): as in generate(), with item i's budget max_new_tokens[i] read from the
         device: every item ends with <eos> inside its own limit.  ValueError for a limit below 2.
+        return_stats=True: a StepStats in item order comes last in the result (generate()'s return_stats).
         ValueError before any device work for beam search, bad prefix_lens / max_new_tokens / sampling settings and
         lengths beyond the positional table or the cache rows of start_stream."""
         if algo not in ("greedy", "multinomial"):
@@ -2103,9 +2225,12 @@ class KVDecoder:
             st[name].fill_(v)
         # (a streamed row reads its budget and prefix length per item: limit[item] / prefix_len[item])
         plan = StepPlan(self._set_sampling(algo, filt, seed, grammar, steps, t0), STREAM, grammar is not None,
-                        bool(return_logp))
+                        bool(return_logp), bool(return_stats))
         if plan.logp:
             st["out_logp"].zero_()
+        if plan.stats:                                  # (both buffers exist before a step is run or captured)
+            self._stats_tables(plan, zero=True)
+            self._behaviour_probs(plan)
         self.pos.fill_(-1)                                         # the first step consumes every row's token 0
         self.row_off.zero_()
         self.ys.fill_(self.pad_id)
@@ -2129,10 +2254,10 @@ class KVDecoder:
                       row_of=st["row_of"].cpu().long(), start_step=start, out_len=out_len,
                       harvested=int(st["n_harvested"].item()))
         ys, _ = self._cut_at_eos(st["out_ys"][:, :W], lens, t0)    # generate()'s cut: the longest item's <eos>
-        if not plan.logp:
-            return ys.clone(), record
-        # an item's generated span: the out_len tokens the refill handed out
-        return (ys.clone(), record) + self._span_logp(st["out_logp"], ys, lens, out_len)
+        out = (ys.clone(), record)
+        if plan.logp:                                   # an item's generated span: the out_len tokens the refill handed out
+            out += self._span_logp(st["out_logp"], ys, lens, out_len)
+        return out + (self._span_stats(plan, ys, lens, out_len),) if plan.stats else out
 
     def _run_step(self, plan, use_graphs):
         g = self.graphs.get(plan.key) if use_graphs else False

@@ -1548,6 +1548,44 @@ def chosen_logp(logits2d, ys, pos_dev, out, pad_id, row_off=None, item=None, pre
           "gct_chosen_logp")
 
 
+STEP_STATS = ("model_entropy", "behaviour_logp", "behaviour_entropy", "behaviour_kl")     # gct_step_stats' tables
+
+
+def step_stats(logits2d, probs, ys, pos_dev, pad_id, greedy=False, row_off=None, item=None, prefix_len=None, **out):
+    """gct_step_stats, after select_token on the same raw logits [n, V] and device counter (decode.step_stats_reference
+    states the rules).  probs [n, V] or None: what select_token wrote to probs_out in this step -- the behaviour
+    distribution q; None: q = the model's own softmax; greedy: q = the one-hot at the chosen token.  **out: the tables
+    to write, any of STEP_STATS, at least one -- fp32 [rows, >= width] of one shape and row stride, unit column
+    stride, written at (dst, p) with chosen_logp's dst and p, 0 for pad.  item / prefix_len / row_off as in chosen_logp."""
+    n, V = logits2d.shape
+    _chk(logits2d, "step_stats.logits"), _chk(ys, "step_stats.ys", torch.int64)
+    _chk(pos_dev, "step_stats.pos", torch.int32)
+    tables = [out.pop(name, None) for name in STEP_STATS]
+    if out:
+        raise ValueError(f"step_stats: no table named {sorted(out)} (the tables are {', '.join(STEP_STATS)})")
+    given = [t for t in tables if t is not None]
+    if not given:
+        raise ValueError(f"step_stats: no table to write ({', '.join(STEP_STATS)})")
+    for name, t in zip(STEP_STATS, tables):
+        if t is not None:
+            _chk(t, f"step_stats.{name}")
+            if t.dim() != 2 or t.stride(1) != 1 or t.shape != given[0].shape or t.stride(0) != given[0].stride(0):
+                raise ValueError("step_stats: the tables are fp32 [rows, width] of one shape and row stride, unit "
+                                 "column stride")
+    if n == 0:                                              # nothing to do (and an empty tensor has no address to pass)
+        return
+    if not logits2d.is_contiguous() or ys.dim() != 2 or ys.shape[0] < n or ys.stride(1) != 1 or pos_dev.numel() < 1:
+        raise ValueError("step_stats: contiguous logits [n, V], ys [>= n, T] with unit column stride, a device counter")
+    if probs is not None:
+        _chk(probs, "step_stats.probs")
+        if probs.shape != logits2d.shape or not probs.is_contiguous():
+            raise ValueError("step_stats: probs must be a contiguous [n, V] buffer of the logits' shape")
+    _check_step_rows(n, row_off, item, prefix_len=prefix_len)
+    check(_L().gct_step_stats(_p(logits2d), _p(probs), V, _p(ys), ys.stride(0), _p(pos_dev), _p(row_off), _p(item),
+                              _p(prefix_len), int(pad_id), int(bool(greedy)), *[_p(t) for t in tables],
+                              given[0].stride(0), given[0].shape[0], n, _st()), "gct_step_stats")
+
+
 STREAM_MAX_ROWS, STREAM_MAX_LAYERS = 8192, 16   # GCT_STREAM_MAX_ROWS / GCT_STREAM_MAX_LAYERS (include/gctplus_hip.h)
 
 

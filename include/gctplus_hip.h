@@ -829,6 +829,24 @@ int gct_grammar_mask(const float* logits, float* masked, int V, const int32_t* t
                      int T, int n, const int32_t* pos, const int32_t* row_off, const int32_t* gram, const int32_t* item,
                      const int32_t* prefix_len, const int32_t* limit, void* stream);
 
+/* Per-step sampling statistics (gct_plus_amd/decode.py step_stats_reference states the rules).  Launched behind
+ * gct_select_token in the step unit, on the same device counter and with gct_chosen_logp's row rule: row r looks at
+ * column p = *pos - row_off[r] + 1, takes tok = ys[r][p] and writes each non-null table at out[dst][p].
+ *   pi  the softmax of the RAW logits row (temperature 1), its log-softmax with gct_chosen_logp's arithmetic;
+ *   q   the BEHAVIOUR distribution the token was drawn from: the probs row [n][V] gct_select_token wrote to probs_out in
+ *       this step, as given; pi itself when probs is null; the one-hot at tok when greedy != 0 (probs is ignored).
+ *   model_entropy = -sum pi log pi           behaviour_logp = log q(tok)
+ *   behaviour_entropy = -sum_{q>0} q log q    behaviour_kl = sum_{q>0} q (log q - log pi)
+ * A term with q == 0 adds exactly 0.  tok == pad_id (a finished row): all four are 0.  probs null and not greedy:
+ * behaviour_logp has gct_chosen_logp's bits, behaviour_entropy model_entropy's, behaviour_kl is exactly 0.
+ * item / prefix_len / row_off, dst and the cases in which nothing is written: as in gct_chosen_logp (so the call goes
+ * BEFORE gct_stream_refill).  The four tables are [out_rows][ld_out], each nullable, at least one given.  One wave per
+ * row; any V >= 1.  n == 0 launches nothing. */
+int gct_step_stats(const float* logits, const float* probs, int V, const int64_t* ys, int64_t ld_ys, const int32_t* pos,
+                   const int32_t* row_off, const int32_t* item, const int32_t* prefix_len, int64_t pad_id, int greedy,
+                   float* model_entropy, float* behaviour_logp, float* behaviour_entropy, float* behaviour_kl,
+                   int64_t ld_out, int out_rows, int n, void* stream);
+
 /* Continuous batching (gct_plus_amd/decode.py stream_schedule_reference states the schedule).  R decode rows work
  * through a pool of N items behind the shared counter *pos: the step unit is gct_decode_advance, the RAGGED step
  * kernels, gct_select_token(item, prefix_len) and then gct_stream_refill, which, when *enable != 0:
