@@ -56,6 +56,12 @@ vocabulary -- every returned string has balanced branches, paired ring-closure n
 with <eos> inside max_strlen.  Syntax only: no valence or aromaticity check.  Not with beam search: the constructor
 refuses decode_algo="beam", and `decode_beams` of such a sampler raises.
 
+`decode_smc` (any sampler, any decode_algo): sequential Monte Carlo under the grammar (KVDecoder.generate_smc) -- k weighted
+well-formed molecules per latent whose weighted distribution converges to the model's own distribution restricted to
+well-formed strings, which a well_formed=True decode's locally renormalised draws do not follow, and an unbiased estimate
+of the probability that an unconstrained sample is well formed.  decode.smc_row_weights turns the weights into the
+`weight=` of Train/finetune.reinforce_step / ppo_update.
+
 `stream_rows=R` (optional): greedy / multinomial decodes run with continuous batching (KVDecoder.generate_stream) -- the
 n rows of a call are a pool that R decode rows work through, a row whose molecule reached <eos> taking the next one, so
 `sample_smiles(30000)` is one call that never computes past a molecule's end.  Every decode of such a sampler goes that
@@ -79,8 +85,9 @@ from ..Model.modules import get_src_mask
 from ..data import Vocab, tokenize
 from .mol_interpolation import Interpolation, interior_alphas, interp_plan, lerp, noise_ladder, run_ladder
 from ..decode import (BEAM_ALPHA, KVDecoder, Marginal, PolicyTerms, PpoTerms, SmilesGrammar, check_beam_size,
-                      check_sample_filter, check_stream_model, check_stream_rows, generated_tokens, marginal_logp,
-                      score_tokens, sequence_logp, sequence_policy, sequence_ppo)
+                      check_ess_threshold, check_grammar, check_particles, check_sample_filter, check_stream_model,
+                      check_stream_rows, generated_tokens, marginal_logp, score_tokens, sequence_logp, sequence_policy,
+                      sequence_ppo)
 
 
 BEAM_ALGOS = ("beam", "stochastic_beam")        # decode_algo values that decode k rows per sample in step (kv_src)
@@ -473,6 +480,33 @@ class Sampling:
         self.seed += 1
         zs, ys, src_mask, dconds = self._start_rows(zs, ys, src_mask, dconds, beams=k)
         out = self.kv.generate_sbs(ys, k, self.max_strlen, seed=self.seed, use_graphs=self.use_graphs)
+        if not return_rows:
+            return out
+        rep = lambda x: None if x is None else x.repeat_interleave(k, 0)       # noqa: E731
+        ids = out.ys.reshape(-1, out.ys.shape[2])
+        return out, self._decoded_rows(ids, rep(zs), ys.size(1), rep(src_mask), rep(dconds), None)
+
+    @torch.no_grad()
+    def decode_smc(self, zs, ys, src_mask, dconds=None, k=None, ess_threshold=0.5, return_rows=False):
+        """Sequential Monte Carlo decoding under the SMILES grammar (KVDecoder.generate_smc): k weighted molecules per row
+        of zs, every one well formed, whose weighted distribution converges to the model's OWN distribution restricted to
+        well-formed strings -- where a well_formed=True decode draws from the locally renormalised one, biased towards
+        what the mask favours -- and, per row, an unbiased estimate exp(log_z) of the probability that an unconstrained
+        sample is well formed.  Returns decode.SmcSamples on the sampler's device.  k defaults to the constructor's
+        beam_size; ess_threshold in [0, 1] is the share of k below which a sample resamples.  Any sampler type and any
+        decode_algo: the grammar is the sampler's, or built from the target vocabulary when it has none (the sampler's
+        filters and stream_rows do not apply).  No mixed prefixes, no streaming, k <= ops.BEAM_MAX_K.
+        return_rows=True: (SmcSamples, DecodedRows) as decode_unique returns them; decode.smc_row_weights(samples) are the
+        rows' weights for Train/finetune.reinforce_step(..., weight=) / ppo_update(..., weight=).  self.seed advances
+        once per call.  ValueError for a bad ess_threshold or k, or max_strlen < 3, before any device work."""
+        check_ess_threshold(ess_threshold)
+        k = check_particles(self.beam_size if k is None else k, "decode_smc")
+        grammar = self.grammar or SmilesGrammar(self.TRG.itos, self.TRG.stoi["<pad>"], self.eos_id)
+        check_grammar(grammar, self.model.out.weight.shape[0], self.max_strlen - 1)
+        self.seed += 1
+        zs, ys, src_mask, dconds = self._start_rows(zs, ys, src_mask, dconds, beams=k)
+        out = self.kv.generate_smc(ys, k, grammar, self.max_strlen, seed=self.seed, ess_threshold=ess_threshold,
+                                   use_graphs=self.use_graphs)
         if not return_rows:
             return out
         rep = lambda x: None if x is None else x.repeat_interleave(k, 0)       # noqa: E731

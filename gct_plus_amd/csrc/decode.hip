@@ -13,6 +13,9 @@
 //                      shared by ancestry through a per-row map (kv_src) instead of copied
 //   gct_beam_select_gumbel : stochastic beam search -- the other instantiation of gct_beam_select's kernel template,
 //                      ordering the candidates by Gumbel-perturbed log-probabilities conditioned on their parent's
+//   gct_grammar_mask_anc / gct_smc_select : sequential Monte Carlo under the grammar on the same beam-shaped rows -- the
+//                      grammar kernel's other instantiation reads a particle's history through kv_src; the selection
+//                      weights the particles by the mass the mask leaves, resamples their ancestors and draws
 //   gct_attn_decode_z / gct_decode_embed / gct_decode_advance : cross-attention over the latent rows, one position's
 //                      embedding, the device counter
 // All are small and HBM/latency-bound; they exist so a whole decode step is a fixed kernel chain with no host round
@@ -313,6 +316,28 @@ __device__ __forceinline__ void cdf_scan_chunk(float p, int c0, int V, float u, 
   cum += __shfl(incl, 63, 64);
 }
 
+// The plain multinomial draw of one row over the wave: p = exp(x - mx) * inv per token (to probs_row when given), the
+// scan chunk by chunk, and the rounding fallback (the sum stayed below u): the last token of nonzero probability -- V - 1,
+// unless its logit is -inf (a token the grammar mask forbids) or underflows.  select_token_kernel's and smc_select_kernel's.
+__device__ __forceinline__ int multinomial_pick(const float* lr, int V, float mx, float inv, float u, int lane,
+                                                float* probs_row) {
+  float cum = 0.f;
+  int pick = V - 1, lastnz = -1;
+  bool found = false;
+  for (int c0 = 0; c0 < V; c0 += 64) {
+    const int c = c0 + lane;
+    float p = c < V ? expf(lr[c] - mx) * inv : 0.f;
+    if (p > 0.f) lastnz = c;
+    if (probs_row && c < V) probs_row[c] = p;
+    cdf_scan_chunk(p, c0, V, u, lane, cum, found, pick);
+  }
+  if (!found) {
+    lastnz = gct_wave_max_i32(lastnz);
+    if (lastnz >= 0) pick = lastnz;
+  }
+  return pick;
+}
+
 // The commit: the token, its key-valid flag and the sticky finished flag.
 __device__ __forceinline__ void commit_token(int lane, int row, int pos, int tok, int64_t* ys, int64_t ld_ys,
                                              uint8_t* valid, int64_t valid_sb, int valid_off, uint8_t* done,
@@ -360,24 +385,7 @@ __global__ __launch_bounds__(256) void select_token_kernel(
   } else {
     // multinomial: inverse CDF with one Philox uniform per (row, position)
     const uint4 r = gct_philox(rng, key, (uint32_t)pos, 0x452821E6u, 0x38D01377u);
-    const float u = u01_draw(r.x);
-    float cum = 0.f;
-    int pick = V - 1, lastnz = -1;
-    bool found = false;
-    for (int c0 = 0; c0 < V; c0 += 64) {
-      const int c = c0 + lane;
-      float p = c < V ? expf(lr[c] - mx) * inv : 0.f;
-      if (p > 0.f) lastnz = c;
-      if (probs_out && c < V) probs_out[(int64_t)row * V + c] = p;
-      cdf_scan_chunk(p, c0, V, u, lane, cum, found, pick);
-    }
-    if (!found) {
-      // rounding fallback (the sum stayed below u): the last token of nonzero probability -- V - 1, unless its logit is
-      // -inf (a token the grammar mask forbids) or underflows
-      lastnz = gct_wave_max_i32(lastnz);
-      if (lastnz >= 0) pick = lastnz;
-    }
-    best = pick;
+    best = multinomial_pick(lr, V, mx, inv, u01_draw(r.x), lane, probs_out ? probs_out + (int64_t)row * V : nullptr);
   }
   commit_token(lane, row, pos, best, ys, ld_ys, valid, valid_sb, valid_off, done, pad_id, eos_id);
 }
@@ -595,11 +603,16 @@ __device__ __forceinline__ bool grammar_allows(int prev, int depth, uint64_t ope
 // logits.  depth = #OPEN - #CLOSE; every RING token toggles its bit, so open = the xor of the ring bits; a ring is in
 // `here` iff it appears behind the last ATOM and is open now (its last toggle there was the opening one: closing it
 // again on the same atom is what the grammar forbids), so here = open & (or of the ring bits behind the last ATOM).
+// ANC (uniform rows of a beam-shaped decode: no row_off, no items): the history view goes through the ancestry map --
+// generated token j of row r lies in the physical row kv_src[r][valid_off + t0 + j] that wrote it (KVDecoder._beam_tokens'
+// rule; entries clamped to [0, n)), column t0 + j as ever.  Everything behind the view is the one code.
+template <bool ANC>
 __global__ __launch_bounds__(256) void grammar_mask_kernel(
     const float* __restrict__ logits, float* __restrict__ masked, int V, const int32_t* __restrict__ table,
     const int64_t* __restrict__ ys, int64_t ld_ys, int T, int n, const int32_t* __restrict__ pos_dev,
     const int32_t* __restrict__ row_off, const int32_t* __restrict__ gram, const int32_t* __restrict__ item,
-    const int32_t* __restrict__ prefix_len, const int32_t* __restrict__ limit) {
+    const int32_t* __restrict__ prefix_len, const int32_t* __restrict__ limit, const int32_t* __restrict__ kv_src,
+    int64_t ld_src, int valid_off) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = blockIdx.x * 4 + wave;
   if (row >= n) return;
@@ -613,7 +626,13 @@ __global__ __launch_bounds__(256) void grammar_mask_kernel(
   if (g < 0 || t0 < 0 || p >= T) return;                    // inside the prefix / no such column: 0 <= t0 <= p < T <= 256
   const int64_t* yr = ys + (int64_t)row * ld_ys + t0;
   auto entry = [&](int j) -> int {
-    const int64_t tok = yr[j];
+    int64_t tok;
+    if constexpr (ANC) {
+      const int r = kv_src[(int64_t)row * ld_src + valid_off + t0 + j];
+      tok = ys[(int64_t)(r < 0 ? 0 : (r >= n ? n - 1 : r)) * ld_ys + t0 + j];
+    } else {
+      tok = yr[j];
+    }
     return tok >= 0 && tok < V ? table[tok] : GCT_GRAMMAR_BANNED;
   };
   int e[4];
@@ -870,6 +889,54 @@ __device__ __forceinline__ void beam_insert(BeamList<KM, PHI>& L, float v, int i
   }
 }
 
+// ------------------------------------------------------------------------ rows that share caches by ancestry
+// What the selections over a group of K rows behind the map kv_src share (beam_select_kernel's two instantiations and
+// smc_select_kernel): the state every one of them keeps per row, and the children's write-back.
+// The load: finished / lengths of the group's rows and their map rows -> LDS (the caller's __syncthreads follows).
+__device__ __forceinline__ void group_load_state(int tid, int K, int T, int64_t row0, const uint8_t* finished,
+                                                 const int32_t* lengths, const int32_t* kv_src, int64_t ld_src,
+                                                 uint8_t* s_fin, int32_t* s_len, int32_t (*s_map)[256]) {
+  if (tid < K) {
+    s_fin[tid] = finished[row0 + tid];
+    s_len[tid] = lengths[row0 + tid];
+  }
+  for (int i = tid; i < K * T; i += 256) {
+    const int b = i / T, j = i - b * T;
+    s_map[b][j] = kv_src[(row0 + b) * ld_src + j];
+  }
+}
+
+// Child tid (< K) of parent b: finished, length, parent, the token at ys[row][p] and its flag at valid[row][slot]; the
+// parent and the flag stay in LDS for group_write_map.
+__device__ __forceinline__ void group_commit_child(int tid, int64_t row, int p, int slot, int b, int tok, bool fin, int len,
+                                                   uint8_t* finished, int32_t* lengths, int32_t* parent_out, int64_t* ys,
+                                                   int64_t ld_ys, uint8_t* valid, int64_t valid_sb, int64_t pad_id,
+                                                   int32_t* s_par, uint8_t* s_cfin) {
+  finished[row] = fin ? 1 : 0;
+  lengths[row] = len;
+  if (parent_out) parent_out[row] = b;
+  ys[row * ld_ys + p] = tok;
+  valid[row * valid_sb + slot] = tok != pad_id ? 1 : 0;
+  s_par[tid] = b;
+  s_cfin[tid] = fin ? 1 : 0;
+}
+
+// Behind the __syncthreads that follows group_commit_child: child row = parent's map row (as loaded), plus its own new
+// slot; done = every child finished.
+__device__ __forceinline__ void group_write_map(int tid, int K, int T, int64_t row0, int slot, int32_t* kv_src,
+                                                int64_t ld_src, const int32_t (*s_map)[256], const int32_t* s_par,
+                                                const uint8_t* s_cfin, uint8_t* done) {
+  for (int i = tid; i < K * T; i += 256) {
+    const int c = i / T, j = i - c * T;
+    kv_src[(row0 + c) * ld_src + j] = j == slot ? (int32_t)(row0 + c) : s_map[s_par[c]][j];
+  }
+  if (tid == 0) {
+    uint8_t all = 1;
+    for (int c = 0; c < K; ++c) all &= s_cfin[c];
+    done[blockIdx.x] = all;
+  }
+}
+
 // ------------------------------------------------------------------------ stochastic beam search (gct_beam_select_gumbel)
 // What the stochastic instantiation of beam_select_kernel adds (include/gctplus_hip.h states the rules).
 struct BeamGumbel {
@@ -940,14 +1007,9 @@ __global__ __launch_bounds__(256) void beam_select_kernel(
     if (sa.seed_dev) sa.rng = gct_rng_make(*sa.seed_dev, GCT_SBS_SITE);
   if (tid < K) {
     s_score[tid] = scores[row0 + tid];
-    s_fin[tid] = finished[row0 + tid];
-    s_len[tid] = lengths[row0 + tid];
     if constexpr (GUMBEL) s_gum[tid] = sa.gumbels[row0 + tid];
   }
-  for (int i = tid; i < K * T; i += 256) {
-    const int b = i / T, j = i - b * T;
-    s_map[b][j] = kv_src[(row0 + b) * ld_src + j];
-  }
+  group_load_state(tid, K, T, row0, finished, lengths, kv_src, ld_src, s_fin, s_len, s_map);
   __syncthreads();
   for (int b = wave; b < K; b += 4) {                       // log-softmax statistics, one wave per live beam
     if (s_fin[b] || s_score[b] == -INFINITY) continue;
@@ -1053,24 +1115,169 @@ __global__ __launch_bounds__(256) void beam_select_kernel(
     const bool fin = f == INT_MAX || s_fin[b] || tok == eos_id;
     scores[row] = sc;
     if constexpr (GUMBEL) sa.gumbels[row] = gv;
-    finished[row] = fin ? 1 : 0;
-    lengths[row] = s_len[b] + (s_fin[b] ? 0 : 1);
-    if (parent_out) parent_out[row] = b;
-    ys[row * ld_ys + p] = tok;
-    valid[row * valid_sb + slot] = tok != pad_id ? 1 : 0;
-    s_par[tid] = b;
-    s_cfin[tid] = fin ? 1 : 0;
+    group_commit_child(tid, row, p, slot, b, tok, fin, s_len[b] + (s_fin[b] ? 0 : 1), finished, lengths, parent_out, ys,
+                       ld_ys, valid, valid_sb, pad_id, s_par, s_cfin);
   }
   __syncthreads();
-  for (int i = tid; i < K * T; i += 256) {                 // child row = parent's map row, plus its own new slot
-    const int c = i / T, j = i - c * T;
-    kv_src[(row0 + c) * ld_src + j] = j == slot ? (int32_t)(row0 + c) : s_map[s_par[c]][j];
+  group_write_map(tid, K, T, row0, slot, kv_src, ld_src, s_map, s_par, s_cfin, done);
+}
+
+// ---------------------------------------------------------------------------------------------- sequential Monte Carlo
+// The K-element arithmetic of one sample, by ONE thread in the stated order (include/gctplus_hip.h, step 2; decode.py
+// smc_step_reference): logw[] are the weights after step 1.  Writes the ancestors par[] and the children's log-weights
+// cw[]; returns true when it resampled (then *lz_add is the term log_z gains) -- all_dead: every weight is -inf.
+// No multiply here may fuse into an add: S2 and the thresholds are compared against a host restatement.
+__device__ __forceinline__ bool smc_resample(int K, const float* logw, float tau, float u, float* w, float* cum,
+                                             int32_t* par, float* cw, double* lz_add, bool* all_dead) {
+#pragma clang fp contract(off)
+  float M = -INFINITY;
+  for (int b = 0; b < K; ++b) M = fmaxf(M, logw[b]);
+  *all_dead = M == -INFINITY;
+  bool res = false;
+  if (!*all_dead) {
+    float S1 = 0.f, S2 = 0.f;
+    for (int b = 0; b < K; ++b) {
+      w[b] = expf(logw[b] - M);
+      S1 += w[b];
+      S2 += w[b] * w[b];
+      cum[b] = S1;
+    }
+    const float ess = (S1 * S1) / S2;
+    res = tau >= 1.f || ess < tau * (float)K;
+    if (res) {
+      const float each = S1 / (float)K;
+      int last = 0;
+      for (int b = 0; b < K; ++b)
+        if (w[b] > 0.f) last = b;
+      for (int c = 0; c < K; ++c) {
+        const float thr = (u + (float)c) * each;
+        int a = last;
+        for (int b = K - 1; b >= 0; --b)
+          if (cum[b] > thr && w[b] > 0.f) a = b;            // the first such b
+        par[c] = a;
+        cw[c] = 0.f;
+      }
+      *lz_add = (double)M + log((double)S1 / (double)K);
+    }
   }
-  if (tid == 0) {
-    uint8_t all = 1;
-    for (int c = 0; c < K; ++c) all &= s_cfin[c];
-    done[blockIdx.x] = all;
+  if (!res)
+    for (int c = 0; c < K; ++c) {
+      par[c] = c;
+      cw[c] = logw[c];
+    }
+  return res;
+}
+
+// One workgroup per sample s, whose K particles are rows s*K .. s*K+K-1 (semantics: include/gctplus_hip.h
+// gct_smc_select; decode.py smc_step_reference).  beam_select_kernel's frame:
+//   1. particle state and the group's kv_src rows -> LDS (group_load_state);
+//   2. per live particle (one wave each): the softmax statistics of its raw and of its masked row -> the weight;
+//   3. thread 0: ESS, the decision, the systematic ancestors, log_z and resamples (smc_resample);
+//   4. per child (one wave each): select_token_kernel's multinomial draw from the parent's masked row;
+//   5. the write-back (group_commit_child, group_write_map).
+template <int KM>
+__global__ __launch_bounds__(256) void smc_select_kernel(
+    const float* __restrict__ logits, const float* __restrict__ masked, int V, int K, float* __restrict__ logw,
+    float* __restrict__ logp, uint8_t* __restrict__ finished, int32_t* __restrict__ lengths,
+    int32_t* __restrict__ parent_out, int64_t* __restrict__ ys, int64_t ld_ys, uint8_t* __restrict__ valid,
+    int64_t valid_sb, int valid_off, int32_t* __restrict__ kv_src, int64_t ld_src, int T, uint8_t* __restrict__ done,
+    const int32_t* __restrict__ pos_dev, int64_t pad_id, int64_t eos_id, double* __restrict__ log_z,
+    int32_t* __restrict__ resamples, const float* __restrict__ tau_dev, GctRng rng, GctRng rng_res,
+    const uint64_t* __restrict__ seed_dev, const float* __restrict__ u_in, float* __restrict__ u_out) {
+  __shared__ float s_logw[KM], s_logp[KM], s_mx[KM], s_lsx[KM], s_my[KM], s_sy[KM], s_w[KM], s_cum[KM], s_cw[KM];
+  __shared__ float s_clogp[KM];
+  __shared__ int32_t s_len[KM], s_par[KM], s_anc[KM], s_tok[KM], s_clen[KM];
+  __shared__ uint8_t s_fin[KM], s_cfin[KM], s_kfin[KM];
+  __shared__ int32_t s_map[KM][256];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int p = *pos_dev + 1;                               // index of the token chosen now
+  const int slot = valid_off + p;
+  if (p < 0 || slot >= T) return;                          // no room (the host sizes the caches)
+  const int s = blockIdx.x;
+  const int64_t row0 = (int64_t)s * K;
+  if (seed_dev) {
+    rng = gct_rng_make(*seed_dev, 0xDEC0DEu);
+    rng_res = gct_rng_make(*seed_dev, GCT_SMC_SITE);
   }
+  if (tid < K) {
+    s_logw[tid] = logw[row0 + tid];
+    s_logp[tid] = logp[row0 + tid];
+  }
+  group_load_state(tid, K, T, row0, finished, lengths, kv_src, ld_src, s_fin, s_len, s_map);
+  __syncthreads();
+  for (int b = wave; b < K; b += 4) {                       // step 1, one wave per live particle
+    if (s_fin[b]) continue;
+    float mx, sx, my, sy;
+    gct_wave_softmax_stats(logits + (row0 + b) * V, V, lane, mx, sx);
+    gct_wave_softmax_stats(masked + (row0 + b) * V, V, lane, my, sy);
+    if (lane == 0) {
+      const float lsx = logf(sx);
+      s_mx[b] = mx;
+      s_lsx[b] = lsx;
+      s_my[b] = my;
+      s_sy[b] = sy;
+      s_logw[b] = my == -INFINITY ? -INFINITY : s_logw[b] + ((my - mx) + (logf(sy) - lsx));
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {                                           // steps 0 and 2
+    bool idle = true;
+    for (int b = 0; b < K; ++b) idle = idle && s_fin[b] != 0;
+    const float u = u_in ? u_in[(int64_t)s * (K + 1) + K]
+                         : u01_draw(gct_philox(rng_res, (uint32_t)s, (uint32_t)p, 0x452821E6u, 0x38D01377u).x);
+    if (u_out) u_out[(int64_t)s * (K + 1) + K] = u;
+    if (idle) {
+      for (int c = 0; c < K; ++c) {
+        s_anc[c] = c;
+        s_cw[c] = s_logw[c];
+      }
+    } else {
+      double add = 0.0;
+      bool all_dead;
+      if (smc_resample(K, s_logw, *tau_dev, u, s_w, s_cum, s_anc, s_cw, &add, &all_dead)) {
+        log_z[s] += add;
+        resamples[s] += 1;
+      }
+      if (all_dead) log_z[s] = -INFINITY;
+    }
+  }
+  __syncthreads();
+  for (int c = wave; c < K; c += 4) {                       // step 3, one wave per child
+    const int a = s_anc[c];
+    const int64_t row = row0 + c;
+    const float u = u_in ? u_in[(int64_t)s * (K + 1) + c]
+                         : u01_draw(gct_philox(rng, (uint32_t)row, (uint32_t)p, 0x452821E6u, 0x38D01377u).x);
+    int tok = (int)pad_id, len = s_len[a];
+    float lp = s_logp[a], cw = s_cw[c];
+    bool fin = true;
+    if (!s_fin[a] && s_logw[a] == -INFINITY) {              // dead: pad, finished from now on
+      cw = -INFINITY;
+    } else if (!s_fin[a]) {
+      const float* xr = logits + (row0 + a) * V;
+      tok = multinomial_pick(masked + (row0 + a) * V, V, s_my[a], 1.0f / s_sy[a], u, lane, nullptr);
+      lp = lp + ((xr[tok] - s_mx[a]) - s_lsx[a]);
+      fin = tok == eos_id;
+      len += 1;
+    }
+    if (lane == 0) {
+      if (u_out) u_out[(int64_t)s * (K + 1) + c] = u;
+      s_tok[c] = tok;
+      s_clogp[c] = lp;
+      s_cw[c] = cw;
+      s_kfin[c] = fin ? 1 : 0;
+      s_clen[c] = len;
+    }
+  }
+  __syncthreads();
+  if (tid < K) {
+    const int64_t row = row0 + tid;
+    logw[row] = s_cw[tid];
+    logp[row] = s_clogp[tid];
+    group_commit_child(tid, row, p, slot, s_anc[tid], s_tok[tid], s_kfin[tid] != 0, s_clen[tid], finished, lengths,
+                       parent_out, ys, ld_ys, valid, valid_sb, pad_id, s_par, s_cfin);
+  }
+  __syncthreads();
+  group_write_map(tid, K, T, row0, slot, kv_src, ld_src, s_map, s_par, s_cfin, done);
 }
 
 // ---------------------------------------------------------------------------------------------- launches
@@ -1219,9 +1426,26 @@ extern "C" int gct_grammar_mask(const float* logits, float* masked, int V, const
                 "grammar_mask: streamed rows need item, prefix_len, limit and row_off");
   GCT_CHECK_ARG(item || gram, "grammar_mask: no budget (gram, or the stream's limit)");
   if (n == 0) return GCT_OK;
-  hipLaunchKernelGGL(grammar_mask_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits,
-                     masked, V, table, ys, ld_ys, T, n, pos, row_off, gram, item, prefix_len, limit);
+  hipLaunchKernelGGL(grammar_mask_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits,
+                     masked, V, table, ys, ld_ys, T, n, pos, row_off, gram, item, prefix_len, limit, nullptr, 0, 0);
   GCT_LAUNCH_CHECK("grammar_mask");
+  return GCT_OK;
+}
+
+extern "C" int gct_grammar_mask_anc(const float* logits, float* masked, int V, const int32_t* table, const int64_t* ys,
+                                    int64_t ld_ys, int T, int n, const int32_t* pos, const int32_t* gram,
+                                    const int32_t* kv_src, int64_t ld_src, int valid_off, void* stream) {
+  GCT_CHECK_ARG(logits && masked && logits != masked && table && ys && pos && gram && kv_src && V > 0 && n >= 0,
+                "grammar_mask_anc: bad args");
+  GCT_CHECK_ARG(T >= 1 && T <= 256 && ld_ys >= T, "grammar_mask_anc: %d token columns (1 .. 256) in rows of %lld", T,
+                (long long)ld_ys);
+  GCT_CHECK_ARG(valid_off >= 0 && ld_src >= (int64_t)valid_off + T, "grammar_mask_anc: map rows of %lld entries for %d + %d",
+                (long long)ld_src, valid_off, T);
+  if (n == 0) return GCT_OK;
+  hipLaunchKernelGGL(grammar_mask_kernel<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits,
+                     masked, V, table, ys, ld_ys, T, n, pos, nullptr, gram, nullptr, nullptr, nullptr, kv_src, ld_src,
+                     valid_off);
+  GCT_LAUNCH_CHECK("grammar_mask_anc");
   return GCT_OK;
 }
 
@@ -1332,4 +1556,32 @@ extern "C" int gct_beam_select_gumbel(const float* logits, int V, int n, int k, 
   const BeamGumbel sa{gumbels, gct_rng_make(seed, GCT_SBS_SITE), seed_dev, noise_in, noise_out};
   return launch_beam_select<true>("beam_select_gumbel", logits, V, n, k, scores, finished, lengths, parent, ys, ld_ys,
                                   valid, valid_sb, valid_off, kv_src, ld_src, T, done, pos_dev, pad_id, eos_id, sa, stream);
+}
+
+// Sequential Monte Carlo under the grammar: gct_beam_select's geometry checks, with the particle state in place of the
+// beam scores (include/gctplus_hip.h states the step).
+extern "C" int gct_smc_select(const float* logits, const float* masked, int V, int n, int k, float* logw, float* logp,
+                              uint8_t* finished, int32_t* lengths, int32_t* parent, int64_t* ys, int64_t ld_ys,
+                              uint8_t* valid, int64_t valid_sb, int valid_off, int32_t* kv_src, int64_t ld_src, int T,
+                              uint8_t* done, const int32_t* pos_dev, int64_t pad_id, int64_t eos_id, double* log_z,
+                              int32_t* resamples, const float* tau_dev, uint64_t seed, const uint64_t* seed_dev,
+                              const float* u_in, float* u_out, void* stream) {
+  GCT_CHECK_ARG(logits && masked && masked != logits && logw && logp && finished && lengths && ys && valid && kv_src &&
+                    done && pos_dev && log_z && resamples && tau_dev && n >= 0,
+                "smc_select: bad args");
+  GCT_CHECK_ARG(k >= 1 && k <= GCT_BEAM_MAX_K && V >= 1, "smc_select: %d particles / vocabulary %d unsupported", k, V);
+  GCT_CHECK_ARG(T > 0 && T <= 256 && valid_off >= 0 && valid_off < T && ld_src >= T && valid_sb >= T &&
+                    ld_ys >= T - valid_off,
+                "smc_select: cache rows %d / map %lld / valid %lld / ys %lld", T, (long long)ld_src, (long long)valid_sb,
+                (long long)ld_ys);
+  GCT_CHECK_ARG(pad_id >= 0 && pad_id < V, "smc_select: pad id %lld outside the vocabulary", (long long)pad_id);
+  if (n == 0) return GCT_OK;
+  const GctRng rng = gct_rng_make(seed, 0xDEC0DEu), rng_res = gct_rng_make(seed, GCT_SMC_SITE);
+  with_int<4, 8, 16>(k <= 4 ? 4 : (k <= 8 ? 8 : 16), [&](auto KM) {
+    hipLaunchKernelGGL(smc_select_kernel<KM>, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, logits, masked, V, k,
+                       logw, logp, finished, lengths, parent, ys, ld_ys, valid, valid_sb, valid_off, kv_src, ld_src, T,
+                       done, pos_dev, pad_id, eos_id, log_z, resamples, tau_dev, rng, rng_res, seed_dev, u_in, u_out);
+  });
+  GCT_LAUNCH_CHECK("smc_select");
+  return GCT_OK;
 }

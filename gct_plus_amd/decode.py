@@ -34,6 +34,14 @@ another selection, gct_beam_select_gumbel, and one more float per row (`bgumbel`
 parent's.  The k beams are k DISTINCT sequences, an exact sample without replacement from the model's distribution; the
 first is an ordinary sample; `sbs_importance_weights` turns them into an unbiased estimator.
 
+Sequential Monte Carlo under the grammar (`start(..., beams=k)` + `generate_smc`; Lew et al. 2023, Loula et al. 2025):
+the same rows and map again, as k weighted PARTICLES per sample.  The rules are stated once, in `smc_step_reference`:
+every step multiplies a particle's weight by the mass A_t the grammar mask leaves of its next-token distribution,
+resamples the ancestors (systematic) when the effective sample size falls below a threshold, and then draws from the
+masked distribution -- gct_grammar_mask_anc reads the particle's history through kv_src, gct_smc_select does the rest.
+The weighted particles converge to the model's own distribution restricted to well-formed strings, which the locally
+renormalised draws of generate(grammar=) do not, and exp(log_z) is an unbiased estimate of that event's probability.
+
 Mixed prefix lengths (`generate(..., prefix_lens=)`, e.g. one batch of many scaffolds): row r's prefix is ys0[r, :t0_r],
 right-padded to t0_max.  The device counter stays shared (the token index of the longest prefix) and row r reads it
 through its offset row_off[r] = t0_max - t0_r (gct_decode_embed / gct_attn_decode / gct_select_token), so each row keeps
@@ -114,6 +122,7 @@ REPLAY_SLOW_FACTOR = 1.3
 BEAM_ALPHA = 0.7
 BEAM = "beam"                                       # StepPlan.select: the beam step (gct_beam_select)
 SBEAM = "sbeam"                                     # StepPlan.select: the stochastic beam step (gct_beam_select_gumbel)
+SMC = "smc"                                         # StepPlan.select: the sequential Monte Carlo step (gct_smc_select)
 FILTERED = "filtered"                               # StepPlan.select: the filtered multinomial draw
 UNIFORM, MIXED, STREAM = "uniform", "mixed", "stream"      # StepPlan.layout
 LOGP = "logp"                                       # graph key suffix of a step unit that records log-probabilities
@@ -128,7 +137,8 @@ class StepPlan:
     """What one step unit is -- the decode step plus the selection, the unit a graph captures.  Each generate call
     builds one and passes it down; KVDecoder keeps no per-call mode of its own.
       select   0 greedy, 1 multinomial, FILTERED (the multinomial draw through self.filt), BEAM (gct_beam_select, the
-               self-attention through the ancestry map kv_src) or SBEAM (the same unit with gct_beam_select_gumbel);
+               self-attention through the ancestry map kv_src), SBEAM (the same unit with gct_beam_select_gumbel) or SMC
+               (the same rows again: gct_grammar_mask_anc through the map, then gct_smc_select);
       layout   UNIFORM: every row at the shared position.  MIXED: the kernels get row_off.  STREAM: row_off plus the
                rows' item and prefix_len, and the unit ends with the refill (KVDecoder._rows is the row view);
       grammar  gct_grammar_mask runs in front of the selection;
@@ -136,7 +146,9 @@ class StepPlan:
       stats    gct_step_stats runs behind it too, and a multinomial draw through a filter or a grammar leaves the
                distribution it drew from in buf['probs'] for it.
     ValueError for what the unit cannot do: beam rows keep their history behind kv_src and their scores are
-    log-probabilities already, so BEAM and SBEAM go with UNIFORM and neither grammar, logp nor stats."""
+    log-probabilities already, so BEAM and SBEAM go with UNIFORM and neither grammar, logp nor stats.  SMC is the unit
+    whose mask reads that history through the map: UNIFORM rows, the grammar always (it is the potential the particles
+    are weighted by), and neither logp nor stats (gct_smc_select accumulates the particles' log-probabilities itself)."""
     select: object = 0
     layout: str = UNIFORM
     grammar: bool = False
@@ -145,11 +157,14 @@ class StepPlan:
 
     def __post_init__(self):
         select, layout, grammar, logp, stats = dataclasses.astuple(self)
-        if select not in (0, 1, FILTERED, BEAM, SBEAM) or layout not in (UNIFORM, MIXED, STREAM):
+        if select not in (0, 1, FILTERED, BEAM, SBEAM, SMC) or layout not in (UNIFORM, MIXED, STREAM):
             raise ValueError(f"no step unit selects {select!r} over {layout!r} rows")
         if select in (BEAM, SBEAM) and (layout != UNIFORM or grammar or logp or stats):
             raise ValueError(f"the {'stochastic ' * (select == SBEAM)}beam step takes uniform rows, no grammar, no "
                              "log-probabilities and no step statistics")
+        if select == SMC and (layout != UNIFORM or not grammar or logp or stats):
+            raise ValueError("the sequential Monte Carlo step takes uniform rows and a grammar, no log-probabilities and "
+                             "no step statistics")
 
     @functools.cached_property
     def key(self):
@@ -1481,6 +1496,178 @@ def sbs_importance_weights(scores, gumbels):
     return w, w / w.sum(1, keepdim=True)
 
 
+# ------------------------------------------------------------------------------ sequential Monte Carlo semantics
+class SmcSamples(NamedTuple):
+    """What a sequential Monte Carlo decode returns, k weighted particles per sample: ys int64 [n, k, L] (prefix, tokens,
+    pad after each particle's end); logw [n, k] fp32 the particles' log-weights, normalised (logsumexp over k is 0);
+    logp [n, k] fp32 = log p(particle's tokens | latent, conditions, prefix) under the model; log_z [n] fp64 = log Z^,
+    the final log mean weight included -- exp(log_z) is an unbiased estimate of P(well formed within the budget);
+    lengths [n, k] int64 generated tokens (<eos> included); ess [n] fp32 the effective sample size of the final weights;
+    resamples [n] int64 how often the sample resampled.  The weighted particles sum_i exp(logw_i) delta(ys_i) converge to
+    the model's own distribution restricted to well-formed strings as k grows; they are NOT distinct."""
+    ys: torch.Tensor
+    logw: torch.Tensor
+    logp: torch.Tensor
+    log_z: torch.Tensor
+    lengths: torch.Tensor
+    ess: torch.Tensor
+    resamples: torch.Tensor
+
+
+def check_ess_threshold(ess_threshold):
+    """A real in [0, 1] (0: never resample, 1: always); ValueError otherwise.  Returns it as a float."""
+    if isinstance(ess_threshold, bool) or not isinstance(ess_threshold, numbers.Real) or \
+            not 0.0 <= float(ess_threshold) <= 1.0:
+        raise ValueError(f"ess_threshold must be a real in [0, 1], got {ess_threshold!r}")
+    return float(ess_threshold)
+
+
+def check_particles(k, who="generate_smc"):
+    """1 <= k <= ops.BEAM_MAX_K particles per sample (gct_smc_select's limit); ValueError otherwise."""
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= int(k) <= ops.BEAM_MAX_K:
+        raise ValueError(f"{who}: k must be an int in [1, {ops.BEAM_MAX_K}] particles per sample, got {k!r}")
+    return int(k)
+
+
+def smc_init(n, k, device=None):
+    """State after the prefill: (logw [n, k] fp32 0, logp [n, k] fp32 0, finished [n, k] False, lengths [n, k] int64 0,
+    log_z [n] fp64 0, resamples [n] int64 0).  Every particle is live from the start -- there is no [0, -inf, ...] root:
+    the k copies of the prefix draw their first tokens independently."""
+    z = lambda *sh, dt: torch.zeros(*sh, dtype=dt, device=device)          # noqa: E731
+    return (z(n, k, dt=torch.float32), z(n, k, dt=torch.float32), z(n, k, dt=torch.bool), z(n, k, dt=torch.int64),
+            z(n, dt=torch.float64), z(n, dt=torch.int64))
+
+
+def _systematic(w, u):
+    """(ancestors [n, k], cum [n, k], thr [n, k], S1 [n]) of systematic_resample_reference."""
+    n, k = w.shape
+    S1, cums = torch.zeros(n, dtype=w.dtype, device=w.device), []
+    for b in range(k):                                           # the fixed order b = 0 .. k-1
+        S1 = S1 + w[:, b]
+        cums.append(S1)
+    cum = torch.stack(cums, 1)
+    idx = torch.arange(k, device=w.device)
+    thr = (u.to(w.dtype).view(n, 1) + idx.to(w.dtype).view(1, k)) * (S1 / k).view(n, 1)
+    pos = w > 0
+    hit = (cum.view(n, 1, k) > thr.view(n, k, 1)) & pos.view(n, 1, k)           # [sample, child, ancestor]
+    last = torch.where(pos, idx.view(1, k), torch.zeros_like(idx).view(1, k)).max(1).values
+    anc = torch.where(hit.any(-1), hit.int().argmax(-1), last.view(n, 1).expand(n, k))
+    return anc, cum, thr, S1
+
+
+def systematic_resample_reference(w, u):
+    """Systematic resampling, THE statement of the rule (gct_smc_select implements it): w [n, k] weights >= 0 (not
+    normalised, at least one positive per sample), u [n] one uniform in (0, 1] per sample.  cum_b = w_0 + .. + w_b summed
+    in the order b = 0 .. k-1; child c takes the first b with cum_b > (u + c) * (S1 / k) and w_b > 0, otherwise the last
+    b with w_b > 0.  Ancestor b gets floor or ceil of k w_b / S1 children, a particle of weight 0 none, and the ancestors
+    come out in ascending order.  Returns ancestors int64 [n, k].  Computed in w's dtype."""
+    return _systematic(w, u)[0]
+
+
+def smc_step_reference(logw, logp, finished, lengths, logits, masked, u, k, pad_id, eos_id, tau, log_z, resamples,
+                       info=None):
+    """One step of sequential Monte Carlo under the grammar, THE statement of the rules (gct_smc_select implements them
+    on the device).  Per sample k particles: logw [n, k] log-weights since the last resampling, logp [n, k]
+    log-probabilities of their tokens under the model, finished [n, k] bool, lengths [n, k] int; logits [n*k, V] the raw
+    rows of the step and masked [n*k, V] the same with -inf where the grammar or the length budget forbids the token;
+    u [n, k + 1] uniforms in (0, 1] -- column c < k child c's draw, column k the resampling; tau the ESS threshold in
+    [0, 1]; log_z [n] fp64 and resamples [n] int the sample's accumulators.
+      0. a sample whose particles are all finished on entry is idle: a_c = c, pad tokens, nothing else changes;
+      1. weight: a live particle b gets logw_b += (my - mx) + (log sy - log sx), (m, s) = (max, sum exp(. - max)) of its
+         raw (x) and masked (y) row -- the log of the model's mass A on the allowed tokens; a finished one keeps logw_b;
+         a masked row with no finite entry gives -inf: the particle is dead -- never an ancestor, it writes pad and is
+         finished from then on;
+      2. resample: M = max_b logw_b.  M = -inf (every particle dead): log_z = -inf, a_c = c.  Otherwise w_b =
+         exp(logw_b - M), S1 = sum w, S2 = sum w^2 (b ascending), ESS = S1^2 / S2, and the sample resamples iff tau >= 1
+         or ESS < tau * k: ancestors a_c by systematic_resample_reference(w, u[:, k]), log_z += M + log(S1 / k), every
+         child's logw = 0, resamples += 1.  Without resampling a_c = c and the child keeps logw_c;
+      3. draw: child c of a live parent a takes the first token v with softmax(y_a)_v > 0 whose inclusive cumulative sum
+         exceeds u[:, c] (none: the last token of nonzero probability) -- gct_select_token's multinomial draw;
+         logp_c = logp_a + ((x_a[v] - mx_a) - log sx_a), finished = v == eos_id, lengths = lengths_a + 1.  A finished or
+         dead parent hands down pad_id and its state (a dead one: logw = -inf, finished).
+    The weight does not depend on the token drawn, so weighting and resampling come before the draw (the fully adapted
+    particle filter): copies of one ancestor diverge at this very step.  With gamma_t(x_<=t) = pi(x_<=t) 1[the prefix
+    can still finish], gamma_t / (gamma_{t-1} q_t) = A_t, hence E[exp(log_z) * mean_b exp(logw_b)] = Z for every k and tau.
+    Computed in the promoted dtype of logw and logits.  info (a dict, optional) receives ess [n], resampled [n],
+    ess_margin [n] = |ESS - tau k|, sys_gap [n] (distance of the nearest systematic position to a cumulative boundary of
+    a positive weight; inf without resampling), probs [n, k, V] the children's draw distributions (0 rows where no draw
+    is made) and drew [n, k].
+    Returns (ancestor [n, k], token [n, k], logw, logp, finished, lengths, log_z, resamples) of the children."""
+    n, V = logw.shape[0], logits.shape[-1]
+    dt, dev = torch.promote_types(logw.dtype, logits.dtype), logits.device
+    ninf, zero = torch.full((), -math.inf, dtype=dt, device=dev), torch.zeros((), dtype=dt, device=dev)
+    x, y = logits.reshape(n, k, V).to(dt), masked.reshape(n, k, V).to(dt)
+    mx, my = x.max(-1).values, y.max(-1).values
+    sx = torch.exp(x - mx.unsqueeze(-1)).sum(-1)
+    some = my > -math.inf                                        # the masked row allows a token
+    mys = torch.where(some, my, zero)
+    sy = torch.where(some, torch.exp(torch.where(some.unsqueeze(-1), y, zero) - mys.unsqueeze(-1)).sum(-1), zero + 1)
+    live = ~finished
+    lw = logw.to(dt)
+    lw = torch.where(live & some, lw + ((mys - mx) + (torch.log(sy) - torch.log(sx))), lw)
+    lw = torch.where(live & ~some, ninf, lw)
+    idle = finished.all(1)
+    M = lw.max(1).values
+    all_dead = (M == -math.inf) & ~idle
+    w = torch.where((M > -math.inf).view(n, 1), torch.exp(lw - torch.where(M > -math.inf, M, zero).view(n, 1)), zero)
+    S2 = torch.zeros(n, dtype=dt, device=dev)
+    for b in range(k):
+        S2 = S2 + w[:, b] * w[:, b]
+    anc_sys, cum, thr, S1 = _systematic(w, u[:, k])
+    weighted = ~idle & ~all_dead
+    ess = torch.where(weighted, S1 * S1 / torch.where(weighted, S2, zero + 1), zero)
+    res = weighted & ((ess < float(tau) * k) | (float(tau) >= 1.0))
+    own = torch.arange(k, device=dev).view(1, k).expand(n, k)
+    anc = torch.where(res.view(n, 1), anc_sys, own)
+    gain = M.double() + torch.log(torch.where(weighted, S1, zero + 1).double() / k)
+    log_z = torch.where(res, log_z.double() + gain, log_z.double())
+    log_z = torch.where(all_dead, torch.full_like(log_z, -math.inf), log_z)
+    resamples = resamples + res.to(resamples.dtype)
+    cw = torch.where(res.view(n, 1), zero, lw)
+    pfin, plw = finished.gather(1, anc), lw.gather(1, anc)
+    dead = ~pfin & (plw == -math.inf)
+    drew = ~pfin & ~dead
+    row = anc.unsqueeze(-1).expand(n, k, V)
+    xa, ya = x.gather(1, row), y.gather(1, row)
+    prob = torch.exp(torch.where(drew.unsqueeze(-1), ya, ninf) - mys.gather(1, anc).unsqueeze(-1)) / \
+        sy.gather(1, anc).unsqueeze(-1)
+    nz = prob > 0
+    tokens = torch.arange(V, device=dev)
+    hit = nz & (prob.cumsum(-1) > u[:, :k].to(dt).unsqueeze(-1))
+    lastnz = torch.where(nz, tokens, torch.zeros_like(tokens)).max(-1).values
+    tok = torch.where(hit.any(-1), hit.int().argmax(-1), lastnz)
+    tok = torch.where(drew, tok, torch.full_like(tok, pad_id))
+    step_lp = (xa.gather(2, tok.unsqueeze(-1)).squeeze(-1) - mx.gather(1, anc)) - torch.log(sx.gather(1, anc))
+    lp = logp.to(dt).gather(1, anc) + torch.where(drew, step_lp, zero)
+    if info is not None:
+        edge = torch.where((w > 0).view(n, 1, k), (cum.view(n, 1, k) - thr.view(n, k, 1)).abs(), zero + math.inf)
+        info.update(ess=ess, resampled=res, ess_margin=(ess - float(tau) * k).abs(), probs=prob, drew=drew,
+                    sys_gap=torch.where(res, edge.reshape(n, -1).min(1).values, zero + math.inf))
+    return (anc, tok, torch.where(dead, ninf, cw), lp, torch.where(drew, tok == eos_id, torch.ones_like(drew)),
+            lengths.gather(1, anc) + drew.to(lengths.dtype), log_z, resamples)
+
+
+def smc_finalize(logw, log_z):
+    """(normalised logw [n, k], log_z [n] fp64 with the final log mean weight, ess [n]) of the weights a decode ends
+    with: logw - logsumexp(logw), log_z + logsumexp(logw) - log k, and (sum w)^2 / sum w^2.  A sample whose particles all
+    died (log_z = -inf) keeps logw = -inf and has ess 0."""
+    k = logw.shape[1]
+    lse = torch.logsumexp(logw.double(), 1)
+    ok = lse > -math.inf
+    norm = torch.where(ok.view(-1, 1), logw.double() - torch.where(ok, lse, torch.zeros_like(lse)).view(-1, 1),
+                       logw.double())
+    ess = torch.where(ok, 1.0 / torch.exp(2.0 * norm).sum(1).clamp(min=1e-300), torch.zeros_like(lse))
+    return norm.to(logw.dtype), log_z.double() + lse - math.log(k), ess.float()
+
+
+def smc_row_weights(samples):
+    """The particles' weights as per-row factors of a policy-gradient step: k * exp(logw) flattened to [n*k] in the
+    sample-major row order of DecodedRows (mean 1 per sample), for Train/finetune.reinforce_step(..., weight=) /
+    ppo_update(..., weight=)."""
+    k = samples.logw.shape[1]
+    return (k * torch.exp(samples.logw.float())).reshape(-1)
+
+
 class KVDecoder:
     def __init__(self, model, pad_id: int, sos_id: int, eos_id: int):
         dec = model.decoder
@@ -1594,7 +1781,13 @@ class KVDecoder:
             self.bparent = torch.zeros(n, dtype=torch.int32, device=dev)
             self.kv_src = torch.zeros(n, T, dtype=torch.int32, device=dev)
             self.bdone = torch.zeros(n // beams, dtype=torch.uint8, device=dev)
-            dff = dec.layers[0].ff.linear_1.weight.shape[0]
+            # generate_smc: bscores holds the particles' log-weights; their log-probabilities, and per sample log Z^,
+            # the resampling count and (one word, read by the kernel) the ESS threshold
+            self.blogp = torch.zeros(n, device=dev)
+            self.blogz = torch.zeros(n // beams, dtype=torch.float64, device=dev)
+            self.bres = torch.zeros(n // beams, dtype=torch.int32, device=dev)
+            self.btau = torch.zeros(1, device=dev)
+            dff =dec.layers[0].ff.linear_1.weight.shape[0]
             V = self.model.out.weight.shape[0]
             need = ops._L().gct_linear_fwd_ws_bytes
             shapes = [(dff, d), (d, 3 * d), (d, dff), (d, d), (d, V)]           # (K, N) of every GEMM of a step
@@ -1743,9 +1936,10 @@ class KVDecoder:
     @torch.no_grad()
     def step(self, plan=StepPlan()):
         """Consume token ys[:, p] with p = *pos + 1 ... see _chain: ONE generated token, position on the device.
-        select BEAM / SBEAM: the self-attention reads the caches through the ancestry map kv_src (gct_attn_decode_beam)."""
+        select BEAM / SBEAM / SMC: the self-attention reads the caches through the ancestry map kv_src
+        (gct_attn_decode_beam)."""
         dec, d, n, T, B = self.dec, self.d, self.n, self.T, self.buf
-        beam, row_off = plan.select in (BEAM, SBEAM), self._rows(plan)["row_off"]
+        beam, row_off = plan.select in (BEAM, SBEAM, SMC), self._rows(plan)["row_off"]
         check(ops._L().gct_decode_advance(self.pos.data_ptr(), ops._st()), "gct_decode_advance")   # pos = the token consumed now
         ops.decode_embed(self.ys, self.pos, self.off, dec.embed.embed.weight, dec.pe.pe, B["x"], math.sqrt(d),
                          row_off=row_off)
@@ -1812,6 +2006,13 @@ class KVDecoder:
                                    self.eos_id, seed_dev=self.seed, parent_i32=self.bparent)
             return
         logits = self.buf["logits"]
+        if plan.select == SMC:                           # the mask through the ancestry, then weight / resample / draw:
+            ops.grammar_mask(logits, self.buf["masked"], self.gtable, self.ys, self.pos, width=self.T - self.off,
+                             gram=self.gram, kv_src=self.kv_src, valid_off=self.off)       # bscores holds the log-weights
+            ops.smc_select(logits, self.buf["masked"], self.beams, self.bscores, self.blogp, self.bfin, self.blen, self.ys,
+                           self.valid, self.off, self.kv_src, self.bdone, self.pos, self.pad_id, self.eos_id, self.blogz,
+                           self.bres, self.btau, seed_dev=self.seed, parent_i32=self.bparent)
+            return
         if plan.grammar:                                 # the selection sees -inf on what the grammar / the budget forbid
             ops.grammar_mask(logits, self.buf["masked"], self.gtable, self.ys, self.pos, width=self.T - self.off,
                              **self._rows(plan, mask=True))
@@ -2073,6 +2274,42 @@ class KVDecoder:
         return SbsSamples(ys[:, :, :t0 + int(lengths.max())].contiguous(), self.bscores.view(ns, k).clone(),
                           self.bgumbel.view(ns, k).clone(), lengths)
 
+    @torch.no_grad()
+    def generate_smc(self, ys0, k, grammar, max_strlen=80, seed=0, ess_threshold=0.5, check_every=8, use_graphs=False,
+                     prefix_lens=None):
+        """Sequential Monte Carlo decoding under `grammar` (a SmilesGrammar over the model's vocabulary) from the prefix
+        ys0 [n, t0] after start(..., beams=k): k weighted particles per sample whose weighted empirical distribution
+        converges to the MODEL's distribution restricted to well-formed strings of up to max_strlen-1 tokens -- not to
+        the locally renormalised one generate(grammar=) draws from -- and an unbiased estimate of that event's
+        probability (smc_step_reference states the step; gct_grammar_mask_anc and gct_smc_select run it).
+        generate_sbs's flow: the prefill, smc_init (every particle live, logw = logp = 0), the first selection from the
+        prefill's logits, the steps with an early stop once every particle of every sample has finished.
+        ess_threshold in [0, 1]: a sample resamples when its effective sample size falls below ess_threshold * k (0:
+        never -- the particles are then the rows generate(algo="multinomial", grammar=) decodes for the latents repeated
+        k times under the same seed, weighted per molecule; 1: at every step).  It lives in device memory: one captured
+        graph serves every threshold and seed.  Returns SmcSamples.  The same seed gives the same result.
+        ValueError, before any device work: a bad ess_threshold, k outside [1, ops.BEAM_MAX_K], no grammar or one of
+        another vocabulary, max_strlen < 3, prefix_lens (mixed prefixes are not supported), then _beam_entry's."""
+        tau = check_ess_threshold(ess_threshold)
+        k = check_particles(k)
+        if grammar is None:
+            raise ValueError("generate_smc: the grammar is the potential the particles are weighted by; it is required")
+        check_grammar(grammar, self.model.out.weight.shape[0], max_strlen - 1)
+        if prefix_lens is not None:
+            raise ValueError("generate_smc: mixed prefix lengths are not supported; run one decode per length")
+        ns, k, t0, steps, rows = self._beam_entry("generate_smc", ys0, k, max_strlen, None)
+        self._set_sampling("multinomial", None, seed, grammar, steps, t0)
+        self.bscores.zero_()                                # log-weights: every particle live from the start
+        self.blogp.zero_()
+        self.blogz.zero_()
+        self.bres.zero_()
+        self.btau.fill_(tau)
+        last = self._lockstep(StepPlan(SMC, UNIFORM, True), rows, None, steps, self.bdone, check_every, use_graphs)
+        ys, lengths = self._beam_tokens(ns, k, last), self.blen.view(ns, k).to(torch.int64)
+        logw, log_z, ess = smc_finalize(self.bscores.view(ns, k), self.blogz)
+        return SmcSamples(ys[:, :, :t0 + int(lengths.max())].contiguous(), logw, self.blogp.view(ns, k).clone(), log_z,
+                          lengths, ess, self.bres.to(torch.int64))
+
     # ------------------------------------------------------------------------------------- continuous batching
     @torch.no_grad()
     def start_stream(self, z, src_mask, dconds=None, rows=512, max_total_len=208, refold=False, item_base=0):
@@ -2277,6 +2514,8 @@ class KVDecoder:
         """Everything a step + selection writes besides the caches' next row (the beam state included)."""
         base = (self.pos, self.ys, self.valid, self.done, self.bscores, self.bgumbel, self.bfin, self.blen,
                 self.bparent, self.kv_src, self.bdone)
+        if plan.select == SMC:
+            base += (self.blogp, self.blogz, self.bres)
         if plan.layout != STREAM:
             return base
         st = self.stream                                  # (the refill is held while a state is kept: _hold_refill)
@@ -2459,3 +2698,38 @@ def reference_style_sbs_decode(model, z, src_mask, dconds, ys0, pad_id, eos_id, 
             break
     ys = ys.view(n, k, -1)
     return SbsSamples(ys[:, :, :t0 + int(lengths.max())].contiguous(), scores, gumbels, lengths)
+
+
+@torch.no_grad()
+def reference_style_smc_decode(model, z, src_mask, dconds, ys0, pad_id, eos_id, k, grammar, u_fn, max_strlen=80,
+                               ess_threshold=0.5, trace=None):
+    """Sequential Monte Carlo on the un-cached model.decode over [n*k, t] every step: reference_style_sbs_decode's loop
+    with grammar.mask_reference and smc_step_reference as the selection -- the baseline generate_smc must match.
+    u_fn(step) -> [n, k + 1] are the uniforms of step 0, 1, ... (smc_step_reference's layout).  Returns SmcSamples.
+    trace (a list): receives every step's `info` of smc_step_reference plus its uniforms (near-tie diagnostics)."""
+    from .Model.modules import get_trg_mask
+    dec = model.decoder
+    c2d = bool(dec.use_cond2dec and dec.nconds > 0)
+    nc = dec.nconds if c2d else 0
+    n, t0 = ys0.shape
+    k, tau = check_particles(k, "reference_style_smc_decode"), check_ess_threshold(ess_threshold)
+    check_grammar(grammar, model.out.weight.shape[0], max_strlen - 1)
+    rep = lambda x: None if x is None else x.repeat_interleave(k, 0)       # noqa: E731
+    z, src_mask, dconds, ys = rep(z), rep(src_mask), rep(dconds), rep(ys0)
+    logw, logp, finished, lengths, log_z, resamples = smc_init(n, k, ys.device)
+    logw, logp = logw.double(), logp.double()
+    base = torch.arange(n, device=ys.device).view(n, 1) * k
+    for step in range(max_strlen - 1):
+        logits = model.decode(ys, z, src_mask, get_trg_mask(ys, pad_id, c2d, dconds), dconds)[:, nc:][:, -1].double()
+        masked = grammar.mask_reference(logits, ys, t0, ys.size(1), max_strlen - 1)
+        u, info = u_fn(step).to(ys.device), {}
+        parent, tok, logw, logp, finished, lengths, log_z, resamples = smc_step_reference(
+            logw, logp, finished, lengths, logits, masked, u, k, pad_id, eos_id, tau, log_z, resamples, info=info)
+        if trace is not None:
+            trace.append(dict(info, u=u, token=tok))
+        ys = torch.cat([ys[(base + parent).view(-1)], tok.view(-1, 1)], dim=1)
+        if bool(finished.all()):
+            break
+    ys = ys.view(n, k, -1)
+    norm, log_z, ess = smc_finalize(logw, log_z)
+    return SmcSamples(ys[:, :, :t0 + int(lengths.max())].contiguous(), norm, logp, log_z, lengths, ess, resamples)

@@ -1300,12 +1300,14 @@ GRAMMAR_MAX_RINGS = 64
 
 
 def grammar_mask(logits2d, masked, table, ys, pos_dev, width=None, row_off=None, gram=None, item=None, prefix_len=None,
-                 limit=None):
+                 limit=None, kv_src=None, valid_off=0):
     """gct_grammar_mask, in front of select_token on the same device counter: masked [n, V] = logits2d where the grammar
     (decode.SmilesGrammar; table int32 [V]) and the length budget allow the token as the next one of the row, -inf
     elsewhere.  gram int32 [2] on the device = (budget G, prefix width t0_max), row r's prefix being t0_max - row_off[r]
     tokens; or item / prefix_len / limit as in select_token and the stream's state.  width: token columns of ys in use
-    (default all).  Parked rows and rows inside their prefix are not written."""
+    (default all).  Parked rows and rows inside their prefix are not written.
+    kv_src (int32 [n, >= valid_off + width], uniform rows only) + valid_off: gct_grammar_mask_anc -- the row's history
+    is read through the ancestry map, token j from row kv_src[r, valid_off + j] (in front of smc_select)."""
     n, V = logits2d.shape
     _chk(logits2d, "grammar_mask.logits"), _chk(masked, "grammar_mask.masked"), _chk(ys, "grammar_mask.ys", torch.int64)
     _chk(table, "grammar_mask.table", torch.int32), _chk(pos_dev, "grammar_mask.pos", torch.int32)
@@ -1317,6 +1319,17 @@ def grammar_mask(logits2d, masked, table, ys, pos_dev, width=None, row_off=None,
     if item is None and (gram is None or gram.dtype != torch.int32 or gram.numel() != 2 or
                          not gram.is_contiguous()):
         raise ValueError("gram must be a contiguous int32 tensor (budget, prefix width)")
+    T = ys.shape[1] if width is None else int(width)
+    if kv_src is not None:
+        if row_off is not None or item is not None:
+            raise ValueError("grammar_mask: rows behind an ancestry map are uniform rows (no row_off, no items)")
+        if (kv_src.dtype != torch.int32 or kv_src.dim() != 2 or kv_src.shape[0] < n or kv_src.stride(1) != 1 or
+                kv_src.shape[1] < int(valid_off) + T or int(valid_off) < 0):
+            raise ValueError("grammar_mask: kv_src int32 [n, >= valid_off + width] with unit column stride")
+        check(_L().gct_grammar_mask_anc(_p(logits2d), _p(masked), V, _p(table), _p(ys), ys.stride(0), T, n, _p(pos_dev),
+                                        _p(gram), _p(kv_src), kv_src.stride(0), int(valid_off), _st()),
+              "gct_grammar_mask_anc")
+        return
     check(_L().gct_grammar_mask(_p(logits2d), _p(masked), V, _p(table), _p(ys), ys.stride(0),
                                 ys.shape[1] if width is None else int(width), n, _p(pos_dev), _p(row_off), _p(gram),
                                 _p(item), _p(prefix_len), _p(limit), _st()), "gct_grammar_mask")
@@ -1692,3 +1705,34 @@ def beam_select_gumbel(logits2d, beam_size, scores, gumbels, finished_u8, length
                                       _p(kv_src), kv_src.stride(0), T, _p(done_u8), _p(pos_dev), pad_id, eos_id,
                                       _p(gumbels), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(seed_dev), _p(noise_in),
                                       _p(noise_out), _st()), "gct_beam_select_gumbel")
+
+
+def smc_select(logits2d, masked, particles, logw, logp, finished_u8, lengths_i32, ys, valid_u8, valid_off, kv_src, done_u8,
+               pos_dev, pad_id, eos_id, log_z, resamples_i32, tau_dev, seed=0, seed_dev=None, u_in=None, u_out=None,
+               parent_i32=None):
+    """gct_smc_select over logits / masked [n*k, V] (raw rows, and the rows grammar_mask(kv_src=) wrote): one step of
+    sequential Monte Carlo under the grammar (decode.smc_step_reference) -- weight, resample, draw -- written in place to
+    the particle state (logw / logp fp32 [n*k], finished, lengths), log_z fp64 [n], resamples int32 [n], ys[:, *pos_dev +
+    1], valid, the kv_src map and done [n].  tau_dev: fp32 [1] on the device, the ESS threshold; seed_dev (int64 [1] on
+    the device) replaces seed; u_in fp32 [n, k + 1] replaces the k draw uniforms and the resampling uniform; u_out fp32
+    [n, k + 1] receives the step's uniforms."""
+    rows, V = logits2d.shape
+    k = int(particles)
+    n = rows // k
+    T = kv_src.shape[1]
+    _chk(logits2d, "smc_select.logits"), _chk(masked, "smc_select.masked"), _chk(logw, "smc_select.logw")
+    _chk(logp, "smc_select.logp"), _chk(log_z, "smc_select.log_z", torch.float64), _chk(tau_dev, "smc_select.tau")
+    _chk(resamples_i32, "smc_select.resamples", torch.int32)
+    if not logits2d.is_contiguous() or not masked.is_contiguous() or masked.shape != logits2d.shape or n * k != rows:
+        raise ValueError("smc_select: logits and masked must be contiguous [n*k, V] buffers of one shape")
+    if min(logw.numel(), logp.numel(), finished_u8.numel(), lengths_i32.numel()) < rows or \
+            min(log_z.numel(), resamples_i32.numel(), done_u8.numel()) < n or tau_dev.numel() < 1:
+        raise ValueError("smc_select: particle state [n*k], sample state [n], tau [1]")
+    for name, t in (("u_in", u_in), ("u_out", u_out)):
+        if t is not None and (tuple(t.shape) != (n, k + 1) or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f"smc_select: {name} must be contiguous fp32 [{n}, {k + 1}]")
+    check(_L().gct_smc_select(_p(logits2d), _p(masked), V, n, k, _p(logw), _p(logp), _p(finished_u8), _p(lengths_i32),
+                              _p(parent_i32), _p(ys), ys.stride(0), _p(valid_u8), valid_u8.stride(0), valid_off,
+                              _p(kv_src), kv_src.stride(0), T, _p(done_u8), _p(pos_dev), pad_id, eos_id, _p(log_z),
+                              _p(resamples_i32), _p(tau_dev), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(seed_dev), _p(u_in),
+                              _p(u_out), _st()), "gct_smc_select")

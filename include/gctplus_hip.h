@@ -960,6 +960,53 @@ int gct_beam_select_gumbel(const float* logits, int V, int n, int k, float* scor
                            int64_t eos_id, float* gumbels, uint64_t seed, const uint64_t* seed_dev,
                            const float* noise_in, float* noise_out, void* stream);
 
+/* Sequential Monte Carlo decoding under the grammar (Lew et al. 2023; Loula et al. 2025; gct_plus_amd/decode.py
+ * smc_step_reference states the rules).  Sample s owns the k PARTICLE rows s*k .. s*k+k-1 of an n*k-row decode, laid out
+ * and written back exactly as the beams of gct_beam_select (physical slots, the ancestry map kv_src).  Why the estimate is
+ * unbiased: with gamma_t(x_<=t) = pi(x_<=t) 1[the prefix can still finish inside the budget] and the proposal q_t = the
+ * masked, renormalised softmax, gamma_t / (gamma_{t-1} q_t) = A_t, the model's mass on the allowed tokens -- a function
+ * of the parent alone, so weighting and resampling come BEFORE the draw (the fully adapted particle filter) and
+ * E[exp(log_z) * mean weight] = Z = P(well formed within the budget) for every k and every threshold.
+ * gct_grammar_mask_anc: gct_grammar_mask for uniform rows (no row_off, no items; one kernel template with it) whose
+ *   history is read through the map: generated token j of row r is ys[kv_src[r][valid_off + t0 + j]][t0 + j], t0 =
+ *   gram[1] (map entries clamped to [0, n)).  ld_src >= valid_off + T.  With the identity map: gct_grammar_mask's bits.
+ * gct_smc_select: one workgroup per sample, p = *pos_dev + 1; logits the RAW rows [n*k][V], masked the rows
+ *   gct_grammar_mask_anc wrote (distinct buffers).  State per row: logw (fp32 log-weight since the last resampling), logp
+ *   (fp32 log-probability of its tokens under the model), finished, lengths; per sample log_z (fp64) and resamples.
+ *   0. every particle finished on entry: nothing but pad tokens and the map's new slot is written (a_c = c).
+ *   1. weight: a live particle b gets logw_b += (my - mx) + (log sy - log sx), (mx, sx) / (my, sy) the row maximum and
+ *      sum exp(. - max) of its raw / masked row (gct_select_token's softmax statistics, twice); a finished one keeps
+ *      logw_b; a masked row without a finite entry gives logw_b = -inf: the particle is DEAD, is never an ancestor, writes
+ *      pad and is finished from then on.
+ *   2. resample: M = max_b logw_b; M = -inf (all dead): log_z = -inf, a_c = c.  Otherwise w_b = expf(logw_b - M), S1 =
+ *      sum w, S2 = sum w * w (fp32, b ascending, no fused multiply-add), ESS = S1 * S1 / S2; resample iff *tau_dev >= 1 or
+ *      ESS < *tau_dev * k.  Systematic, ONE uniform u per (s, p): child c takes the first b whose inclusive fp32 running
+ *      sum of w exceeds (u + c) * (S1 / k) and has w_b > 0, else the last b with w_b > 0; log_z += M + log(S1 / k) in
+ *      fp64, every child's logw = 0, resamples += 1.  Not resampling: a_c = c and the child keeps logw_c.
+ *   3. draw: child c of a live parent a draws from softmax(masked row a) with gct_select_token's multinomial draw, bit
+ *      for bit: the uniform is the FIRST word of Philox at (s*k + c, p, 0x452821E6, 0x38D01377) under (seed, site 0xDEC0DE)
+ *      -- with no resampling the particles are the rows gct_select_token draws for the same masked rows and seed.
+ *      logp_c = logp_a + ((x_a[tok] - mx_a) - log sx_a), finished = tok == eos_id, lengths = lengths_a + 1.  A finished
+ *      (or dead) parent hands down pad and its state.  u of step 2: the first word at (s, p, the same two constants)
+ *      under (seed, site GCT_SMC_SITE), through the same word-to-uniform map.
+ *   4. write-back: gct_beam_select's -- ys[row][p], valid[row][valid_off + p], kv_src[row] = the ancestor's row before
+ *      the call with entry valid_off + p = row, parent (nullable), done[s] = all k children finished.
+ * tau_dev (float) and seed_dev (nullable; replaces seed) live in DEVICE memory: one captured graph serves every threshold
+ * and seed.  u_in (nullable, [n][k + 1]): the k draw uniforms and, last, the resampling uniform, instead of the draws;
+ * u_out (nullable, [n][k + 1]) receives the k + 1 uniforms of the step, used or not.
+ * 1 <= k <= GCT_BEAM_MAX_K, V >= 1 as in gct_select_token, 0 <= pad_id < V, the map / valid / ys bounds of
+ * gct_beam_select; a null state pointer, masked == logits or anything out of range: GCT_ERR_ARG. */
+#define GCT_SMC_SITE 0x53C0DEu
+int gct_grammar_mask_anc(const float* logits, float* masked, int V, const int32_t* table, const int64_t* ys, int64_t ld_ys,
+                         int T, int n, const int32_t* pos, const int32_t* gram, const int32_t* kv_src, int64_t ld_src,
+                         int valid_off, void* stream);
+int gct_smc_select(const float* logits, const float* masked, int V, int n, int k, float* logw, float* logp,
+                   uint8_t* finished, int32_t* lengths, int32_t* parent, int64_t* ys, int64_t ld_ys, uint8_t* valid,
+                   int64_t valid_sb, int valid_off, int32_t* kv_src, int64_t ld_src, int T, uint8_t* done,
+                   const int32_t* pos_dev, int64_t pad_id, int64_t eos_id, double* log_z, int32_t* resamples,
+                   const float* tau_dev, uint64_t seed, const uint64_t* seed_dev, const float* u_in, float* u_out,
+                   void* stream);
+
 /* ------------------------------------------------ host side: SMILES tokeniser + collate */
 /* Utils/field.py:8-33 moltokenize (the atom-wise regex, findall semantics) as a scanner.
  * Returns the number of tokens (may exceed max_tokens: call again with a larger buffer). */
