@@ -58,6 +58,28 @@ def train_opts(parser):
     parser.add_argument('-max_grad_norm', type=max_grad_norm_flag, default=0.0,
                         help="clip the global L2 norm of the gradient to this value on the device "
                              "(clip_grad_norm_'s rule; a non-finite norm skips the step); 0 = off")
+    parser.add_argument('-kl_free_bits', type=kl_free_bits_flag, default=0.0,
+                        help="free bits: a floor, in nats per latent dimension per molecule, under which a dimension's "
+                             "batch KL is neither counted nor given a gradient (sum_j max(floor * B, K_j)); 0 = off")
+    parser.add_argument('-kl_mask_pad', action='store_true',
+                        help="leave padded source positions out of the KL term (they get no KL gradient)")
+    parser.add_argument('-latent_report', action='store_true',
+                        help="after each epoch's validation: per-dimension KL, posterior moments and active units "
+                             "of the validation set, one log line and latent_{epoch}.csv")
+
+
+def kl_free_bits_flag(text):
+    """A finite float >= 0 (0: no floor); argparse reports anything else as a usage error."""
+    import argparse
+    try:
+        value = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not a number")
+    from ..engine import check_kl_controls
+    try:
+        return check_kl_controls(value)[0]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r}: a finite number >= 0 is required (0 = off)")
 
 
 def max_grad_norm_flag(text):

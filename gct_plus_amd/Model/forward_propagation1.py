@@ -28,6 +28,15 @@ def _masks(batch, pad_id, use_cond2dec, skip_ignored, conditioned):
     return trg_in, get_src_mask(batch["src"], pad_id), _trg_mask(trg_in, pad_id, use_cond2dec), rows
 
 
+def latent_live_rows(model_type, batch, pad_id):
+    """bool [B, 1, Le]: the latent rows (mu, log_var [B, Le, D]) that stand for a real source position or a condition
+    -- the encoder's key mask of _masks, the one mask rule.  The KL controls of Train/trainer1 and the latent report
+    count these rows only."""
+    if forward_propagation[model_type] is _conditioned:
+        return get_src_mask(batch["src"], pad_id, batch["econds"])
+    return get_src_mask(batch["src"], pad_id)
+
+
 def _held(batch, conditioned):
     return (batch["src"], batch["trg"]) + ((batch["econds"], batch["dconds"]) if conditioned else ())
 

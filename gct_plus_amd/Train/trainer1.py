@@ -13,25 +13,33 @@ import torch
 import torch.distributed as dist
 
 from .. import engine
-from ..Model.forward_propagation1 import forget_announcement, forward_propagation, prefetch
+from ..Model.forward_propagation1 import forget_announcement, forward_propagation, latent_live_rows, prefetch
 
 
 def KLAnnealer(epoch, KLA_ini_beta, KLA_inc_beta, KLA_beg_epoch):
     return KLA_ini_beta + KLA_inc_beta * ((epoch + 1) - KLA_beg_epoch)
 
 
-def loss_function(beta, preds_prop, preds_mol, ys_cond, ys_mol, mu, log_var, use_cond2dec, pad_id):
+def loss_function(beta, preds_prop, preds_mol, ys_cond, ys_mol, mu, log_var, use_cond2dec, pad_id, *,
+                  free_bits=0.0, latent_live=None):
     """RCE = CE(sum, ignore pad); KLD over every latent element; loss = RCE + beta*KLD
-    (+ MSE_sum(prop) with use_cond2dec).  Returns (loss, RCE_mol, RCE_prop, KLD)."""
+    (+ MSE_sum(prop) with use_cond2dec).  Returns (loss, RCE_mol, RCE_prop, KLD).
+
+    free_bits > 0 (nats per latent dimension per molecule) or latent_live (bool/u8 [B, 1, Le]: the rows that count)
+    replace the KL term by engine.KldFreeBitsFn's objective -- sum_j max(free_bits * B, K_j) over the live rows -- in
+    the loss; the KLD returned is then the plain KL of the live rows, comparable across runs."""
     RCE_mol = engine.CrossEntropySumFn.apply(preds_mol, ys_mol, pad_id)
-    KLD = engine.KldFn.apply(mu, log_var)
+    if free_bits == 0.0 and latent_live is None:
+        KLD = kl_term = engine.KldFn.apply(mu, log_var)
+    else:
+        kl_term, KLD = engine.KldFreeBitsFn.apply(mu, log_var, latent_live, free_bits, mu.shape[0])[:2]
     if use_cond2dec:
         diff = preds_prop - ys_cond          # [B, n_c, 1]: a few hundred floats, host-side glue
         RCE_prop = (diff * diff).sum()
-        loss = RCE_mol + RCE_prop + beta * KLD
+        loss = RCE_mol + RCE_prop + beta * kl_term
     else:
         RCE_prop = torch.zeros(1)
-        loss = RCE_mol + beta * KLD
+        loss = RCE_mol + beta * kl_term
     return loss, RCE_mol, RCE_prop, KLD
 
 
@@ -60,6 +68,8 @@ def run_epoch(args, model, optimizer, dataloader, current_step, beta, LOG, train
     n_batches = len(dataloader)
     pending = []                 # steps whose three loss scalars are on their way to the host
     forget_announcement(model)   # a look-ahead left behind by an earlier, interrupted epoch is never used
+    free_bits, mask_pad = engine.check_kl_controls(getattr(args, 'kl_free_bits', 0.0),
+                                                   getattr(args, 'kl_mask_pad', False))
 
     def resolve():
         while pending:
@@ -101,8 +111,10 @@ def run_epoch(args, model, optimizer, dataloader, current_step, beta, LOG, train
         update_cost_time -= time()
         if train:
             optimizer.zero_grad(set_to_none=True)
+        live = latent_live_rows(args.model_type, batch, args.pad_id) if mask_pad else None
         loss, RCE_mol, RCE_prop, KLD = loss_function(beta, preds_prop, preds_mol, ys_cond, ys_mol,
-                                                     mu, log_var, args.use_cond2dec, args.pad_id)
+                                                     mu, log_var, args.use_cond2dec, args.pad_id,
+                                                     free_bits=free_bits, latent_live=live)
         scal = torch.stack([RCE_mol.detach(), KLD.detach(), loss.detach()])
         host_scal = ev = None
         if scal.is_cuda:
@@ -188,6 +200,11 @@ def train_model(args, model, optimizer, train_loader, valid_loader, rank, world_
                                       train=False)
         LOG.info('Save validation results...')
         pd.DataFrame(valid_history).to_csv(os.path.join(args.model_folder, f'valid_{epoch}{sfx}.csv'))
+        if getattr(args, 'latent_report', False) and rank == 0:
+            from .latent_report import latent_report
+            report = latent_report(args, model, valid_loader)
+            LOG.info(report.line(epoch))
+            report.to_frame().to_csv(os.path.join(args.model_folder, f'latent_{epoch}.csv'))
         if world_size > 1:
             dist.barrier()
         if rank == 0:

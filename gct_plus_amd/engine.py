@@ -1088,6 +1088,82 @@ class KldFn(torch.autograd.Function):
         return dmu, dlv
 
 
+def check_kl_controls(free_bits, mask_pad=False):
+    """(free_bits as a float, mask_pad as a bool) of the trainer's KL controls, or ValueError: free_bits is in nats
+    per latent dimension per molecule, a finite number >= 0 that fits fp32 (0: no floor)."""
+    if isinstance(free_bits, bool) or not isinstance(free_bits, (int, float)):
+        raise ValueError(f"kl_free_bits: expected a number, got {free_bits!r}")
+    value = float(free_bits)
+    if not (math.isfinite(value) and 0.0 <= value <= 3.4028234663852886e38):
+        raise ValueError(f"kl_free_bits: {free_bits!r} is not a finite number >= 0")
+    if not isinstance(mask_pad, (bool, int)) or mask_pad not in (0, 1):
+        raise ValueError(f"kl_mask_pad: expected a bool, got {mask_pad!r}")
+    return value, bool(mask_pad)
+
+
+def _kl_host_rows(mu, log_var, live):
+    """fp32 rows [R, D] of mu and log_var and the live rows as a bool [R], on the host."""
+    m = torch.as_tensor(mu).detach().cpu().to(torch.float32)
+    l = torch.as_tensor(log_var).detach().cpu().to(torch.float32)
+    D = m.shape[-1]
+    m, l = m.reshape(-1, D), l.reshape(-1, D)
+    keep = torch.ones(m.shape[0], dtype=torch.bool) if live is None else (torch.as_tensor(live).cpu() != 0).reshape(-1)
+    if l.shape != m.shape or keep.numel() != m.shape[0]:
+        raise ValueError("kl_dims_reference: mu, log_var [..., D] and live [R] do not fit together")
+    return m, l, keep
+
+
+def kl_dims_reference(mu, log_var, live=None, free_bits=0.0, n_mol=1):
+    """The rule of gct_kld_dims_fwd on the host: t = 1.0f + l - m*m - expf(l) in fp32 operation by operation, as the
+    kernels form it (a kernel may fuse the product into the subtraction, which is inside the kernel tests' bound), then
+    K_j = -0.5 * sum over the live rows of (double) t in fp64, floor = free_bits * n_mol, gate_j = K_j > floor.
+    Returns a dict: objective, raw (floats), kl_dim fp64 [D], gate bool [D], n_floor, live_rows (ints)."""
+    free_bits, _ = check_kl_controls(free_bits)
+    if int(n_mol) < 1:
+        raise ValueError("kl_dims_reference: n_mol must be >= 1")
+    m, l, keep = _kl_host_rows(mu, log_var, live)
+    t = ((1.0 + l) - m * m) - torch.exp(l)                                   # fp32, left to right
+    K = -0.5 * t[keep].to(torch.float64).sum(dim=0)
+    floor = torch.tensor(free_bits, dtype=torch.float32).item() * int(n_mol)      # (double) of the fp32 argument
+    gate = K > floor
+    return {"objective": float(torch.where(gate, K, torch.full_like(K, floor)).sum()), "raw": float(K.sum()),
+            "kl_dim": K, "gate": gate, "n_floor": int((~gate).sum()), "live_rows": int(keep.sum()), "floor": floor}
+
+
+def kl_dims_grad_reference(mu, log_var, live=None, free_bits=0.0, n_mol=1):
+    """d objective / d mu = gate_j * live_r * mu and d objective / d log_var = gate_j * live_r * 0.5 * (exp(lv) - 1),
+    fp64 [R, D] each, with the gate of kl_dims_reference."""
+    gate = kl_dims_reference(mu, log_var, live, free_bits, n_mol)["gate"]
+    m, l, keep = _kl_host_rows(mu, log_var, live)
+    w = (keep[:, None] & gate[None, :]).to(torch.float64)
+    return w * m.to(torch.float64), w * 0.5 * (torch.exp(l.to(torch.float64)) - 1.0)
+
+
+class KldFreeBitsFn(torch.autograd.Function):
+    """The KL term with free bits over the live latent rows (gct_kld_dims_fwd / gct_kld_dims_bwd; the rule:
+    kl_dims_reference): apply(mu, log_var, live, free_bits, n_mol) -> (objective, raw, kl_dim [D], n_floor).
+    live: bool/u8 [B, Le], [B, 1, Le] or [R], or None.  Only objective is differentiable (once); raw is the plain KL
+    of the live rows, kl_dim its split over the dimensions and n_floor how many sit on the floor.  The backward reads
+    the gate the forward wrote."""
+
+    @staticmethod
+    def forward(ctx, mu, log_var, live, free_bits, n_mol):
+        m, l = _f32c(mu), _f32c(log_var)
+        live = None if live is None else ops.to_mask_u8(live)
+        out, kl_dim, gate = ops.kld_dims_fwd(m, l, live, free_bits, n_mol)
+        ctx.save_for_backward(m, l, gate, *(() if live is None else (live,)))
+        objective, raw, n_floor = out[0], out[1], out[2]
+        ctx.mark_non_differentiable(raw, kl_dim, n_floor)
+        return objective, raw, kl_dim, n_floor
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, *unused):
+        m, l, gate, *live = ctx.saved_tensors
+        dmu, dlv = ops.kld_dims_bwd(m, l, live[0] if live else None, gate, _f32c(g))
+        return dmu, dlv, None, None, None
+
+
 class NormFn(torch.autograd.Function):
     """Standalone Norm module call (Model/modules.py:92-95)."""
 

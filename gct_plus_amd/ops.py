@@ -1018,6 +1018,79 @@ def kld_bwd(mu, log_var, gout):
 LATENT_MAX_DIM = 1024                          # GCT_LATENT_MAX_DIM (include/gctplus_hip.h)
 
 
+def _kl_rows(what, mu, log_var, live):
+    """(mu, log_var, live u8 [R] or None, R, D) of the per-dimension KL calls, checked before a launch."""
+    _chk(mu, f"{what}.mu"), _chk(log_var, f"{what}.log_var")
+    if mu.dim() < 1 or mu.shape != log_var.shape:
+        raise _lib.GctError(f"{what}: mu {tuple(mu.shape)} and log_var {tuple(log_var.shape)} must have one shape [..., D]")
+    if not (mu.is_contiguous() and log_var.is_contiguous()):
+        raise _lib.GctError(f"{what}: mu and log_var must be contiguous")
+    D = mu.shape[-1]
+    if D % 4 or not 4 <= D <= LATENT_MAX_DIM:
+        raise _lib.GctError(f"{what}: latent width {D} must be a multiple of 4 in [4, {LATENT_MAX_DIM}]")
+    R = mu.numel() // D
+    if live is not None:
+        if live.dtype not in (torch.bool, torch.uint8) or live.device != mu.device:
+            raise _lib.GctError(f"{what}: live must be a bool or uint8 tensor on mu's device")
+        shapes = [(R,)]
+        if mu.dim() == 3:
+            shapes += [tuple(mu.shape[:2]), (mu.shape[0], 1, mu.shape[1])]
+        if tuple(live.shape) not in shapes:
+            raise _lib.GctError(f"{what}: live {tuple(live.shape)} fits none of {shapes}")
+        live = to_mask_u8(live).view(-1)
+    return mu, log_var, live, R, D
+
+
+def _kld_dims_ws(D, device):
+    return workspace(_L().gct_kld_dims_ws_bytes(D), device)
+
+
+def kld_dims_fwd(mu, log_var, live=None, free_bits=0.0, n_mol=1):
+    """Per-dimension KL with free bits over the live rows (include/gctplus_hip.h: gct_kld_dims_fwd;
+    engine.kl_dims_reference).  mu, log_var fp32 [..., D]; live bool/u8 [B, Le], [B, 1, Le] or [R] (None: every row).
+    Returns (out fp32 [4] = objective, raw, n_floor, live rows; kl_dim fp32 [D]; gate fp32 [D]); nothing is read back."""
+    mu, log_var, live, R, D = _kl_rows("kld_dims_fwd", mu, log_var, live)
+    free_bits, n_mol = float(free_bits), int(n_mol)
+    if not (math.isfinite(free_bits) and free_bits >= 0.0 and abs(free_bits) <= 3.4028234663852886e38):
+        raise _lib.GctError(f"kld_dims_fwd: free_bits {free_bits!r} must be a finite number >= 0")
+    if not 1 <= n_mol < 2 ** 31:
+        raise _lib.GctError(f"kld_dims_fwd: n_mol {n_mol} must be >= 1")
+    out = torch.empty(4, dtype=torch.float32, device=mu.device)
+    kl_dim = torch.empty(D, dtype=torch.float32, device=mu.device)
+    gate = torch.empty(D, dtype=torch.float32, device=mu.device)
+    check(_L().gct_kld_dims_fwd(_p(mu), _p(log_var), _p(live), R, D, free_bits, n_mol, _p(out), _p(kl_dim), _p(gate),
+                                _p(_kld_dims_ws(D, mu.device)), _st()), "gct_kld_dims_fwd")
+    return out, kl_dim, gate
+
+
+def kld_dims_bwd(mu, log_var, live, gate, gout):
+    """(dmu, dlv) of kld_dims_fwd's objective times the device scalar gout: kld_bwd's bits where gate[j] != 0 and the
+    row is live, exact +0.0 elsewhere.  gate: the fp32 [D] the forward wrote."""
+    mu, log_var, live, R, D = _kl_rows("kld_dims_bwd", mu, log_var, live)
+    _chk(gate, "kld_dims_bwd.gate"), _chk(gout, "kld_dims_bwd.gout")
+    if tuple(gate.shape) != (D,) or not gate.is_contiguous() or gout.numel() != 1:
+        raise _lib.GctError(f"kld_dims_bwd: gate must be fp32 [{D}] and gout one fp32 scalar")
+    dmu, dlv = torch.empty_like(mu), torch.empty_like(log_var)
+    check(_L().gct_kld_dims_bwd(_p(mu), _p(log_var), _p(live), _p(gate), _p(gout), _p(dmu), _p(dlv), R, D, _st()),
+          "gct_kld_dims_bwd")
+    return dmu, dlv
+
+
+def latent_moments_state(D, device):
+    """A zeroed running state of latent_moments: fp64 [6, D] (rows: include/gctplus_hip.h, gct_latent_moments)."""
+    return torch.zeros(6, int(D), dtype=torch.float64, device=device)
+
+
+def latent_moments(mu, log_var, live, acc):
+    """Adds one batch's live rows into acc (latent_moments_state): per dimension the sums of mu, mu^2, exp(log_var),
+    log_var and the KL term, and the live-row count.  Two launches; nothing is returned and nothing is read back."""
+    mu, log_var, live, R, D = _kl_rows("latent_moments", mu, log_var, live)
+    if acc.dtype != torch.float64 or tuple(acc.shape) != (6, D) or acc.device != mu.device or not acc.is_contiguous():
+        raise _lib.GctError(f"latent_moments: acc must come from latent_moments_state({D}, mu.device)")
+    check(_L().gct_latent_moments(_p(mu), _p(log_var), _p(live), R, D, _p(acc), _p(_kld_dims_ws(D, mu.device)), _st()),
+          "gct_latent_moments")
+
+
 def _host_i32(x, name, count=None):
     """A per-row table the caller holds on the HOST (list, numpy array or CPU tensor) as a contiguous int32 CPU tensor:
     its range checks are done here, before a launch, because the library never reads device memory."""

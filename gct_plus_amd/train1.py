@@ -180,6 +180,9 @@ def main(rank, world_size, argv=None):
                           eps=args.lr_eps, model=inner, max_grad_norm=args.max_grad_norm or None)
     if args.max_grad_norm:
         LOG.info("gradient clipping: global L2 norm <= %g, on the device", args.max_grad_norm)
+    if args.kl_free_bits or args.kl_mask_pad:
+        LOG.info("KL term: free bits %g nats per dimension per molecule, padded source rows %s",
+                 args.kl_free_bits, "left out" if args.kl_mask_pad else "counted")
     if args.start_epoch > 1:
         from .Model.build_model import load_checkpoint
         ck = load_checkpoint(args.model_path)

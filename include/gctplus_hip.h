@@ -470,6 +470,35 @@ int gct_kld_fwd(const float* mu, const float* log_var, float* out, float* ws, in
 int gct_kld_bwd(const float* mu, const float* log_var, const float* gout, float* dmu, float* dlv,
                 int64_t n, void* stream);
 
+/* Per-dimension KL with free bits and a row mask (Kingma et al. 2016; engine.kl_dims_reference states the rule in
+ * fp64).  mu, log_var fp32 [R][D]; live u8 [R] (nullable: every row counts), nonzero = the row is a real source
+ * position or a condition row.  With t(r, j) = 1.0f + l - m*m - expf(l), gct_kld_fwd's fp32 expression:
+ *   K_j       = -0.5 * sum over live rows r, in ascending order, of (double) t(r, j)
+ *   floor     = (double) free_bits * n_mol           (free_bits: nats per dimension per molecule, batch-averaged form)
+ *   gate_j    = K_j > floor                           (strict, in fp64, before any rounding)
+ *   objective = sum_j max(floor, K_j);  raw = sum_j K_j;  n_floor = #{j : !gate_j}
+ * gct_kld_dims_fwd writes kl_dim[j] = (float) K_j, gate[j] = 1.0f or 0.0f, and out[0..3] = objective, raw, n_floor,
+ * live rows, each rounded to fp32 once.  Two launches, no atomics: workgroups of 256 threads, D / 4 lanes per row
+ * reading float4, write one fp64 partial per (workgroup, dimension) into ws (>= gct_kld_dims_ws_bytes(D) bytes); one
+ * workgroup adds them in a fixed order.  The grid is a function of (R, D) alone (csrc/vae.hip states it), so the same
+ * bytes give the same result on every run.  R == 0: K_j = 0, objective = D * floor, every gate 0 when floor > 0.
+ * gct_kld_dims_bwd, one launch: d objective / d mu = gate_j * live_r * g * mu and d objective / d log_var =
+ * gate_j * live_r * g * 0.5f * (expf(lv) - 1.0f) with g = gout[0] -- gct_kld_bwd's bits where the gate is open and the
+ * row is live, exact +0.0f everywhere else.
+ * gct_latent_moments, the same two launches with more sums: adds this batch's live rows into the caller's running
+ * fp64 state acc [6][D] (zeroed by the caller once): rows 0-5 = sum mu, sum mu^2, sum expf(lv), sum lv, sum -0.5 * t,
+ * live rows (the same count in every column).  Values are converted to double before the first product or sum; the
+ * same batches in the same order give the same bytes.  R == 0 adds nothing.
+ * Limits: D % 4 == 0, 4 <= D <= GCT_LATENT_MAX_DIM, R >= 0, n_mol >= 1, free_bits finite and >= 0; every pointer but
+ * live 16-B aligned (gout: 4-B); else GCT_ERR_ARG before a launch.  gct_kld_dims_ws_bytes: 0 for a D outside the limits. */
+int64_t gct_kld_dims_ws_bytes(int D);
+int gct_kld_dims_fwd(const float* mu, const float* log_var, const uint8_t* live, int64_t R, int D,
+                     float free_bits, int n_mol, float* out, float* kl_dim, float* gate, void* ws, void* stream);
+int gct_kld_dims_bwd(const float* mu, const float* log_var, const uint8_t* live, const float* gate,
+                     const float* gout, float* dmu, float* dlv, int64_t R, int D, void* stream);
+int gct_latent_moments(const float* mu, const float* log_var, const uint8_t* live, int64_t R, int D,
+                       double* acc, void* ws, void* stream);
+
 /* --------------------------------------------- K12: latents for molecule interpolation */
 /* Inference/mol_interpolation.py:124-131 (approximate_z's fit).  mu, log_var fp32 [n][Le][D] contiguous; rows int32 [n]
  * on the device: the first rows[i] latent rows of molecule i are its own (the prefix get_src_mask marks: condition

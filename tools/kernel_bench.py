@@ -331,6 +331,39 @@ def adam_suite(reps):
         clip_lines(p, g, m, v, reps)
 
 
+def kld_suite(reps, rounds=3, batch=20):
+    """The KL term of a training step, R = 512 * 64 latent rows of D = 128 (the bench step's order of size): gct_kld_fwd
+    + gct_kld_bwd against gct_kld_dims_fwd + gct_kld_dims_bwd (free bits 0.25, every fourth row masked out), alternated,
+    next to a device copy that moves the same 24 B per element (the forward reads mu and log_var, the backward reads
+    them again and writes two gradients).  `batch` calls between one pair of events: a call is a few microseconds."""
+    dev = "cuda"
+    B, Le, D = 512, 64, 128
+    n = B * Le * D
+    mu, lv = torch.randn(B, Le, D, device=dev), torch.randn(B, Le, D, device=dev) * 0.1
+    live = (torch.arange(B * Le, device=dev) % 4 != 0).view(B, Le)
+    g = torch.tensor(0.04, device=dev)
+    src, dst = torch.empty(3 * n, device=dev), torch.empty(3 * n, device=dev)
+
+    def plain():
+        ops.kld_fwd(mu, lv)
+        ops.kld_bwd(mu, lv, g)
+
+    def dims(mask):
+        _, _, gate = ops.kld_dims_fwd(mu, lv, mask, 0.25, B)
+        ops.kld_dims_bwd(mu, lv, mask, gate, g)
+
+    variants = (("kld plain        ", plain), ("kld dims         ", lambda: dims(None)),
+                ("kld dims + mask  ", lambda: dims(live)), ("copy, same bytes ", lambda: dst.copy_(src)))
+    for _ in range(rounds):
+        for name, fn in variants:
+            def many():
+                for _ in range(batch):
+                    fn()
+            med, best = timeit(many, reps)
+            print(f"{name}: {med/batch*1e6:7.2f} us (best {best/batch*1e6:7.2f}) {24*n/(med/batch)/1e9:7.0f} GB/s",
+                  flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--suite", default="gemm,attn,bw")
@@ -361,3 +394,5 @@ if __name__ == "__main__":
         bw_suite(a.reps)
     if "adam" in a.suite.split(","):
         adam_suite(a.reps)
+    if "kld" in a.suite.split(","):
+        kld_suite(a.reps)
