@@ -53,8 +53,15 @@ objective of Train/finetune.ppo_update's several updates per scored batch.  Not 
 
 `well_formed=True` (optional): greedy / multinomial decodes are constrained by decode.SmilesGrammar built from the target
 vocabulary -- every returned string has balanced branches, paired ring-closure numbers, no dangling bond, and ended
-with <eos> inside max_strlen.  Syntax only: no valence or aromaticity check.  Not with beam search: the constructor
+with <eos> inside max_strlen.  Syntax only: no valence or aromaticity check (`check_rows` / `is_valid` below check the
+decoded rows for those).  Not with beam search: the constructor
 refuses decode_algo="beam", and `decode_beams` of such a sampler raises.
+
+`check_rows(rows)` (any sampler): decode.SmilesChemistry's check of decoded rows on the device, one launch -- a
+ChemReport(status, position, atoms, ring_bonds) per row: valence caps, ring closures that double a bond or disagree on
+its order, aromatic atoms outside an aromatic ring.  A necessary condition of validity, not a toolkit's verdict.
+Train/finetune.validity_reward turns the report into the reward of reinforce_step / ppo_update; `is_valid(smiles)` is the
+same verdict for one string, usable as accept= of interpolate_smiles.
 
 `decode_smc` (any sampler, any decode_algo): sequential Monte Carlo under the grammar (KVDecoder.generate_smc) -- k weighted
 well-formed molecules per latent whose weighted distribution converges to the model's own distribution restricted to
@@ -84,10 +91,10 @@ from .. import ops
 from ..Model.modules import get_src_mask
 from ..data import Vocab, tokenize
 from .mol_interpolation import Interpolation, interior_alphas, interp_plan, lerp, noise_ladder, run_ladder
-from ..decode import (BEAM_ALPHA, KVDecoder, Marginal, PolicyTerms, PpoTerms, SmilesGrammar, check_beam_size,
-                      check_ess_threshold, check_grammar, check_particles, check_sample_filter, check_stream_model,
-                      check_stream_rows, generated_tokens, marginal_logp, score_tokens, sequence_logp, sequence_policy,
-                      sequence_ppo)
+from ..decode import (BEAM_ALPHA, ChemReport, KVDecoder, Marginal, PolicyTerms, PpoTerms, SmilesChemistry,
+                      SmilesGrammar, check_beam_size, check_ess_threshold, check_grammar, check_particles,
+                      check_sample_filter, check_stream_model, check_stream_rows, generated_tokens, marginal_logp,
+                      score_tokens, sequence_logp, sequence_policy, sequence_ppo)
 
 
 BEAM_ALGOS = ("beam", "stochastic_beam")        # decode_algo values that decode k rows per sample in step (kv_src)
@@ -231,6 +238,33 @@ class Sampling:
         self.latent_seed = seed                 # interpolate_smiles' latents: one stream per sampler, not per decode
         self.marginal_seed = seed               # marginal(seed=None): advanced once per call, so calls draw afresh
         self.kv = KVDecoder(model, self.pad_id, self.sos_id, self.eos_id)
+        self._chemistry = None
+
+    # ---- chemical validity of decoded rows (decode.SmilesChemistry: a check behind the decode, not a constraint on it)
+    @property
+    def chemistry(self) -> SmilesChemistry:
+        """The SmilesChemistry over the target vocabulary, built on first use."""
+        if self._chemistry is None:
+            self._chemistry = SmilesChemistry(self.TRG.itos, self.pad_id, self.eos_id)
+        return self._chemistry
+
+    def check_rows(self, rows, prefix_lens=None) -> ChemReport:
+        """The chemistry check of decoded rows on their device, one launch: `rows` a DecodedRows, or ys int64 [n, L]
+        with prefix_lens ints [n].  ChemReport(status, position, atoms, ring_bonds), int32 [n] each; positions count
+        from the row's first generated token."""
+        if isinstance(rows, DecodedRows):
+            rows, prefix_lens = rows.ys, rows.prefix_lens
+        elif isinstance(rows, tuple) and len(rows) == 2 and prefix_lens is None:
+            rows, prefix_lens = rows
+        if prefix_lens is None:
+            raise ValueError("check_rows: a DecodedRows, or (ys, prefix_lens)")
+        return self.chemistry.check_rows(rows, prefix_lens)
+
+    def is_valid(self, smiles, scaffold=None) -> bool:
+        """True when `smiles` passes the chemistry check (its tokens and <eos>; a token outside the vocabulary is <unk>,
+        which no SMILES holds).  `scaffold` is accepted and ignored, so that the method serves as accept= of
+        interpolate_smiles whatever the model type."""
+        return bool(smiles) and self.chemistry.valid(self.smi_to_id(smiles, add_eos=True))
 
     # ---- helpers with the reference's names ------------------------------------------------
     def init_y(self, n, add_sos=True, sca_ids=None, add_sep=False):

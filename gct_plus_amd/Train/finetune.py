@@ -52,6 +52,7 @@ import copy
 
 import torch
 
+from .. import ops
 from ..decode import clip_pair
 from ..optim import FusedAdam, check_max_grad_norm
 
@@ -117,6 +118,28 @@ def behaviour_weights(model_logp, behaviour_logp, clip=None):
             raise ValueError(f"behaviour_weights: clip must be a finite number > 0 or None, got {clip!r}")
     rho = torch.exp(lp - lq)
     return rho if clip is None else rho.clamp(max=float(clip))
+
+
+def validity_reward(report, shaped=False, lengths=None):
+    """One reward per row from a decode.ChemReport (Sampling.check_rows): fp32 [n] on the report's device, no graph and
+    no synchronisation -- reinforce_step / ppo_update take it as `reward` as it is.  1 where status == ops.CHEM_OK, else
+    0.  shaped=True: a rejected row gets position / length instead, the share of its span that lies in front of the
+    first offence; lengths ints [n] (or one int) are the span lengths W - prefix_lens, all >= 1.  (A SYNTAX row that
+    never reached <eos> has position == length: rows decoded with well_formed=True have none.)  ValueError for
+    shaped=True without lengths, or lengths of another shape."""
+    status = report.status
+    ok = status == ops.CHEM_OK
+    if not shaped:
+        return ok.float()
+    if lengths is None:
+        raise ValueError("validity_reward: shaped=True needs the span lengths")
+    lengths = torch.as_tensor(lengths)
+    if lengths.dtype.is_floating_point or lengths.numel() not in (1, status.numel()) or (
+            not lengths.is_cuda and lengths.numel() and int(lengths.min()) < 1):
+        raise ValueError(f"validity_reward: lengths must be ints >= 1, one or one per row ({status.numel()}), got "
+                         f"{lengths.dtype} {list(lengths.shape)}")
+    share = report.position.float() / lengths.reshape(-1).to(status.device, non_blocking=True).float()
+    return torch.where(ok, torch.ones_like(share), share)
 
 
 def _check_weight(weight, n, what):

@@ -81,7 +81,13 @@ Grammar-constrained decoding (`generate` / `generate_stream(grammar=SmilesGramma
 re-derives the row's grammar state from the tokens it has generated (nothing to save for graph capture, nothing to reset
 at a stream refill) and writes a copy of the logits with -inf on every token that has no transition or would leave the
 row unable to reach <eos> inside its length budget, which it reads from device memory.  Every row then ends with <eos>
-and parses.  The guarantee is syntactic only: valence, aromaticity and ring-bond consistency need a chemistry toolkit.
+and parses.  The guarantee is syntactic only: valence, aromaticity and ring-bond consistency are not part of it.
+
+Chemical validity of FINISHED rows (`SmilesChemistry.check_rows`): the rules are stated once, in `SmilesChemistry.check`
+-- the grammar's verdict with the position of the first offending token, then the molecular graph: valence caps per
+atom, ring closures that double a bond or disagree on its order, aromatic atoms with fewer than two aromatic neighbours.
+gct_smiles_check applies them to a batch of decoded rows in one launch (one wave per row; lane 0 walks the row with its
+stack and per-atom sums in LDS).  A necessary condition, not a chemistry toolkit; it takes no part in the decode loop.
 
 Per-step sampling statistics (`generate` / `generate_stream(return_stats=True)`): the rules are stated once, in
 `step_stats_reference`.  return_logp is the MODEL's log-probability of a token; under a filter or the grammar the token
@@ -98,6 +104,7 @@ import heapq
 import math
 import numbers
 import os
+import re
 from typing import NamedTuple, Optional
 
 import torch
@@ -340,7 +347,8 @@ class SmilesGrammar:
     """SMILES syntax over a target vocabulary, for constrained decoding (KVDecoder.generate / generate_stream(grammar=)).
     The guarantee is SYNTACTIC: branches balance, ring-closure numbers pair up, bonds have an atom or a ring closure
     behind them, and the row ends with <eos> inside its length budget.  Chemical validity (valence, aromaticity, a ring
-    bond doubling another, bond orders at the two ends of a ring closure) is not checked.
+    bond doubling another, bond orders at the two ends of a ring closure) is not checked while decoding: SmilesChemistry
+    checks finished rows for it.
     itos: the vocabulary's strings; token pad_id is PAD and token eos_id EOS whatever their strings, every other token is
     classified by grammar_class, and OPEN is BANNED in a vocabulary without CLOSE.  ValueError for a vocabulary without
     an ATOM token or without <eos> / <pad> ids inside it.
@@ -434,6 +442,200 @@ class SmilesGrammar:
             if st is None:
                 return False
         return st[0] == G_END
+
+
+# ------------------------------------------------------------------------------------------- chemical validity
+_CHEM_CAPS = {"B": 3, "C": 4, "N": 3, "O": 2, "F": 1, "Si": 4, "P": 5, "S": 6, "Cl": 1, "Br": 1, "I": 5}
+_CHEM_ROWS = (("B", "C", "N", "O", "F"), ("Al", "Si", "P", "S", "Cl"))
+_CHEM_BOND_ORDERS = {"-": 1, "=": 2, "#": 3, "$": 4, ":": 1, "/": 1, "\\": 1, "~": 1}
+_CHEM_BRACKET = re.compile(r"\[(\d+)?([A-Z][a-z]?|[a-z][a-z]?|\*)(@{0,2})(H\d?)?(\++|-+|[+-]\d+)?\]")
+
+
+def chem_atom_entry(token):
+    """(cap or None, explicit H count, aromatic, carbon-like) of an ATOM token's string.
+    Organic atoms: caps B 3, C 4, N 3, O 2, F 1, P 5, S 6, Cl 1, Br 1, I 5 (the largest valence of each: implicit
+    hydrogens fill up to the next allowed one, so only the maximum can be exceeded); a lower-case symbol is aromatic;
+    `*` has no cap.  A bracket atom reads [isotope? symbol chirality? H-count? charge?]: aromatic when the symbol is lower
+    case, H the stated count (H alone: 1), and its effective element is the one `charge` places to the LEFT of it in its
+    row B C N O F / Al Si P S Cl (the isoelectronic rule: [N+] is C, cap 4; [O-] is F, cap 1; [n+] is carbon-like); it
+    takes that element's cap (Si 4; Al none) and has none when the shift leaves the row.  An element outside the two rows
+    keeps its own cap at charge 0 and has none otherwise.  A bracket token the pattern does not match is a non-aromatic
+    atom without a cap.  Carbon-like: the effective element is C."""
+    t = str(token)
+    if t.startswith("["):
+        m = _CHEM_BRACKET.fullmatch(t)
+        if not m:
+            return None, 0, False, False
+        sym, h, ch = m.group(2), m.group(4), m.group(5)
+        if sym == "*":
+            return None, (0 if not h else int(h[1:] or 1)), False, False
+        q = 0 if not ch else (int(ch) if len(ch) > 1 and ch[1:].isdigit() else (len(ch) if ch[0] == "+" else -len(ch)))
+        aromatic, el = sym[0].islower(), sym[0].upper() + sym[1:]
+        eff = el if q == 0 else None
+        for row in _CHEM_ROWS:
+            if el in row:
+                i = row.index(el) - q
+                eff = row[i] if 0 <= i < len(row) else None
+        return _CHEM_CAPS.get(eff), (0 if not h else int(h[1:] or 1)), aromatic, eff == "C"
+    if t == "*":
+        return None, 0, False, False
+    el = t[0].upper() + t[1:]
+    return _CHEM_CAPS.get(el), 0, t[0].islower(), el == "C"
+
+
+class ChemReport(NamedTuple):
+    """What SmilesChemistry.check_rows / check_reference return: int32 [n] each -- status (ops.CHEM_*), position of the
+    first finding in the row's span (-1: none), atoms, ring_bonds."""
+    status: torch.Tensor
+    position: torch.Tensor
+    atoms: torch.Tensor
+    ring_bonds: torch.Tensor
+
+
+class SmilesChemistry:
+    """Chemical validity of FINISHED SMILES rows over a target vocabulary: a SmilesGrammar (self.grammar) and a second
+    per-token table (self.chem, gct_smiles_check's layout: cap | H << 4 | aromatic << 8 | carbon-like << 9 |
+    bond order << 12, ops.CHEM_NO_CAP for no cap; chem_atom_entry reads the atoms).  `check` is THE statement of the rules;
+    gct_smiles_check (check_rows) implements it.  It is a check of decoded rows: it takes no part in the decode loop.
+    The check is a NECESSARY condition.  It does not check Kekulé structure or ring membership beyond `anb`.  It does not
+    check stereo marks, or a bracket atom whose valence is below its cap.  An atom without a cap is never flagged for
+    valence.  ValueError for a vocabulary that SmilesGrammar rejects."""
+
+    def __init__(self, itos, pad_id, eos_id):
+        self.grammar = SmilesGrammar(itos, pad_id, eos_id)
+        words = []
+        for t, c in zip(self.grammar.itos, self.grammar.classes):
+            w = ops.CHEM_NO_CAP
+            if c == ops.GRAMMAR_ATOM:
+                cap, h, aromatic, clike = chem_atom_entry(t)
+                w = ((ops.CHEM_NO_CAP if cap is None else cap) | (min(h, 15) << 4) | (int(aromatic) << 8) |
+                     (int(clike) << 9))
+            elif c == ops.GRAMMAR_BOND:
+                w |= _CHEM_BOND_ORDERS[t] << 12
+            words.append(w)
+        self.words = words
+        self.chem = torch.tensor(words, dtype=torch.int32)
+        self._device_tables = {}
+
+    def __len__(self):
+        return len(self.grammar)
+
+    def device_tables(self, device):
+        """(grammar table, chem table) on `device` (copied once)."""
+        key = str(torch.device(device))
+        if key not in self._device_tables:
+            self._device_tables[key] = (self.grammar.device_table(device), self.chem.to(device))
+        return self._device_tables[key]
+
+    def check(self, tokens):
+        """(status, position, atoms, ring_bonds) of a row's generated ids `tokens` -- the <eos> and whatever follows it
+        included, the prefix excluded.  Sequential, on the host.
+        SYNTAX (SmilesGrammar.well_formed is false; ids outside [0, V) and an empty span included): position = the first
+        token without a transition, or len(tokens) when no <eos> was reached; atoms = ring_bonds = 0.
+        Otherwise the graph, atoms numbered in token order: an ATOM bonds to the atom the chain stands at (OPEN pushes
+        that atom, CLOSE pops it, DOT clears it; the first atom has none) with the order of a BOND token directly in
+        front of it, else 1 (- 1, = 2, # 3, $ 4, each of : / \\ ~ 1).  A RING token belongs to the atom it follows; the
+        first occurrence of an open number remembers (atom, order or none), the next one closes it: both ends state an
+        order and the two differ, or the two atoms are bonded already (by the chain or by an earlier closure) ->
+        RING_BOND at the closing token and no bond is added; otherwise a bond of the stated order, 1 when neither end
+        states one.  ring_bonds = closing ring tokens (rejected ones included), atoms = ATOM tokens.
+        Per atom, with sigma the sum of its bond orders, mo the largest, anb its aromatic neighbours, H its explicit
+        hydrogens and used = sigma + H + (1 if it is aromatic and carbon-like and mo < 2): VALENCE at the atom's token
+        when its cap is known and used > cap; otherwise AROMATIC there when it is aromatic and anb < 2.
+        The finding with the smallest position wins; OK has position -1."""
+        g = self.grammar
+        tokens = [int(t) for t in tokens]
+        st = GRAMMAR_START
+        for i, t in enumerate(tokens):
+            st = grammar_step(st, g.classes[t], g.rings[t]) if 0 <= t < len(g) else None
+            if st is None:
+                return ops.CHEM_SYNTAX, i, 0, 0
+        if st[0] != G_END:
+            return ops.CHEM_SYNTAX, len(tokens), 0, 0
+        atoms, bonds, stack, open_rings, findings = [], set(), [], {}, []   # atoms: [token position, word, sigma, mo, anb]
+        cur, pend, ring_bonds = None, None, 0
+
+        def link(a, b, order):
+            bonds.add((a, b))
+            for x, y in ((a, b), (b, a)):
+                atoms[x][2] += order
+                atoms[x][3] = max(atoms[x][3], order)
+                atoms[x][4] += (atoms[y][1] >> 8) & 1
+
+        for i, t in enumerate(tokens):
+            c = g.classes[t]
+            if c == ops.GRAMMAR_ATOM:
+                atoms.append([i, self.words[t], 0, 0, 0])
+                if cur is not None:
+                    link(cur, len(atoms) - 1, pend or 1)
+                cur, pend = len(atoms) - 1, None
+            elif c == ops.GRAMMAR_BOND:
+                pend = (self.words[t] >> 12) & 7
+            elif c == ops.GRAMMAR_OPEN:
+                stack.append(cur)
+            elif c == ops.GRAMMAR_CLOSE:
+                cur, pend = stack.pop(), None
+            elif c == ops.GRAMMAR_DOT:
+                cur, pend = None, None
+            elif c == ops.GRAMMAR_RING:
+                r = g.rings[t]
+                if r in open_rings:
+                    a, order = open_rings.pop(r)
+                    ring_bonds += 1
+                    if (order and pend and order != pend) or (a, cur) in bonds:     # (a < cur: it closes on a later atom)
+                        findings.append((i, ops.CHEM_RING_BOND))
+                    else:
+                        link(a, cur, pend or order or 1)
+                else:
+                    open_rings[r] = (cur, pend)
+                pend = None
+        for pos, w, sigma, mo, anb in atoms:
+            cap, h, aromatic, clike = w & 15, (w >> 4) & 15, (w >> 8) & 1, (w >> 9) & 1
+            used = sigma + h + (1 if aromatic and clike and mo < 2 else 0)
+            if cap != ops.CHEM_NO_CAP and used > cap:
+                findings.append((pos, ops.CHEM_VALENCE))
+            elif aromatic and anb < 2:
+                findings.append((pos, ops.CHEM_AROMATIC))
+        if findings:
+            pos, status = min(findings)
+            return status, pos, len(atoms), ring_bonds
+        return ops.CHEM_OK, -1, len(atoms), ring_bonds
+
+    def valid(self, tokens):
+        return self.check(tokens)[0] == ops.CHEM_OK
+
+    def _starts(self, ys, prefix_lens):
+        """prefix_lens as int64 [n] on the CPU after the checks of a batch call: ys integers [n, W >= 1], prefix_lens in
+        [0, W], no span wider than ops.CHEM_MAX_SPAN columns."""
+        if ys.dim() != 2 or ys.shape[1] < 1:
+            raise ValueError(f"ys must be [n, W >= 1] token rows, got {list(ys.shape)}")
+        if ys.dtype.is_floating_point or ys.dtype.is_complex or ys.dtype == torch.bool:
+            raise ValueError(f"ys must hold integer token ids, got {ys.dtype}")
+        n, W = ys.shape
+        lens = _int_vector("prefix_lens", prefix_lens, n, 0, W, "the row width")
+        if n and W - int(lens.min()) > ops.CHEM_MAX_SPAN:
+            raise ValueError(f"a span of {W - int(lens.min())} columns: the check takes at most {ops.CHEM_MAX_SPAN}")
+        return lens
+
+    def check_reference(self, ys, prefix_lens):
+        """THE batch rule (gct_smiles_check implements it): row r's span is ys[r, prefix_lens[r]:].  A ChemReport on the
+        CPU."""
+        ys = torch.as_tensor(ys)
+        lens = self._starts(ys, prefix_lens).tolist()
+        rows = ys.cpu().tolist()
+        got = [self.check(row[t0:]) for row, t0 in zip(rows, lens)]
+        return ChemReport(*(torch.tensor([g[k] for g in got], dtype=torch.int32) for k in range(4)))
+
+    def check_rows(self, ys, prefix_lens):
+        """The same on the device of ys (int64 [n, W]): one gct_smiles_check launch.  prefix_lens ints [n] (on the CPU, as
+        DecodedRows holds them: no synchronisation).  ValueError for a span wider than 256 columns or prefix_lens outside
+        [0, W]."""
+        lens = self._starts(ys, prefix_lens)
+        table, chem = self.device_tables(ys.device)
+        ys = ys.to(torch.int64)                               # (any integer dtype, as check_reference takes)
+        ys = ys if ys.shape[1] == 1 or ys.stride(1) == 1 else ys.contiguous()
+        out = ops.smiles_check(ys, lens.to(torch.int32).to(ys.device, non_blocking=True), table, chem)
+        return ChemReport(*out.unbind(1))
 
 
 # ------------------------------------------------------------------------------------------- log-likelihoods

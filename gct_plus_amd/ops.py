@@ -1408,6 +1408,40 @@ def grammar_mask(logits2d, masked, table, ys, pos_dev, width=None, row_off=None,
                                 _p(item), _p(prefix_len), _p(limit), _st()), "gct_grammar_mask")
 
 
+# status codes of the chemistry check (GCT_CHEM_* of include/gctplus_hip.h), and its per-token word:
+# cap (bits 0..3, CHEM_NO_CAP: none) | H count << 4 | aromatic << 8 | carbon-like << 9 | bond order << 12
+CHEM_OK, CHEM_SYNTAX, CHEM_VALENCE, CHEM_RING_BOND, CHEM_AROMATIC = range(5)
+CHEM_NO_CAP = 15
+CHEM_MAX_SPAN = 256
+
+
+def smiles_check(ys, start, table, chem, out=None):
+    """gct_smiles_check: out int32 [n, 4] = (status, position, atoms, ring_bonds) of every row's span ys[r, start[r]:]
+    (decode.SmilesChemistry.check is the statement).  ys int64 [n, W] with unit column stride, start int32 [n] on the
+    device with 0 <= start[r] <= W and W - start[r] <= 256 (the caller's to guarantee: a row outside that range is
+    reported as SYNTAX at position 0), table / chem int32 [V] (SmilesChemistry.device_tables).  One launch."""
+    _chk(ys, "smiles_check.ys", torch.int64), _chk(start, "smiles_check.start", torch.int32)
+    _chk(table, "smiles_check.table", torch.int32), _chk(chem, "smiles_check.chem", torch.int32)
+    if ys.dim() != 2 or ys.shape[1] < 1 or (ys.shape[1] > 1 and ys.stride(1) != 1):
+        raise ValueError("smiles_check: ys [n, W >= 1] with unit column stride")
+    n, W = ys.shape
+    if start.dim() != 1 or start.numel() != n or not start.is_contiguous():
+        raise ValueError(f"smiles_check: start must be a contiguous int32 tensor [{n}], got {list(start.shape)}")
+    if (table.dim() != 1 or table.numel() < 1 or chem.shape != table.shape or not table.is_contiguous() or
+            not chem.is_contiguous()):
+        raise ValueError("smiles_check: table and chem int32 [V], contiguous")
+    if out is None:
+        out = torch.empty(n, 4, dtype=torch.int32, device=ys.device)
+    _chk(out, "smiles_check.out", torch.int32)
+    if tuple(out.shape) != (n, 4) or not out.is_contiguous():
+        raise ValueError(f"smiles_check: out must be a contiguous int32 tensor [{n}, 4], got {list(out.shape)}")
+    if n == 0:
+        return out
+    check(_L().gct_smiles_check(_p(ys), max(W, ys.stride(0)), W, n, _p(start), table.numel(),
+                                _p(table), _p(chem), _p(out), _st()), "gct_smiles_check")
+    return out
+
+
 def _seq_geometry(name, logits2d, ys, rows_per_seq, V, prefix_lens, prior2d=None):
     """The checks every seq_* wrapper makes on (ys, logits, prefix_lens), with seq_dist's prior logits next to the
     agent's: (n, W, R, V, ld, ld_prior).  `name` (the caller's) opens every message, here and in the helpers below."""

@@ -25,6 +25,13 @@ N_SYMBOLS = 26
 # strings behind the synthetic ids wherever a grammar is tested or measured.
 GRAMMAR_VOCAB = ["<unk>", "<pad>", "<sos>", "<eos>", "<sep>", "C", "c", "N", "O", "Br", "[nH]", "[C@@H]", "F", "=", "#",
                  "-", "/", "(", ")", "1", "2", "3", "%12", "%70", ".", "@", "+", "S", "n", "Cl", "o"]
+# GRAMMAR_VOCAB, 39 more tokens of every kind (charged, aromatic, isotope and chiral bracket atoms, every bond symbol,
+# ring numbers up to the 64 limit and past it, tokens that are no SMILES), three more bracket atoms -- one of them
+# unreadable -- and ring numbers 13 .. 49, so that a row can hold 40 rings open at once: the chemistry check's vocabulary
+CHEM_VOCAB = GRAMMAR_VOCAB + [
+    "[N+]", "[O-]", "P", "I", "B", "b", "s", "p", "*", "\\", ":", "~", "$", "0", "4", "5", "6", "7", "8", "9", "%01", "%10",
+    "%11", "%63", "%64", "%99", "?", ">", "[Na+]", "[se]", "[Si]", "[2H]", "[13C]", "[S@]", "[P@@]", "[B-]", "[I+]",
+    "[nH+]", "[c-]", "[n+]", "[C@H]", "[C@@@H]"] + [f"%{k}" for k in range(13, 50)]
 
 
 def vocab_sizes(model_type: str):

@@ -858,6 +858,33 @@ int gct_grammar_mask(const float* logits, float* masked, int V, const int32_t* t
                      int T, int n, const int32_t* pos, const int32_t* row_off, const int32_t* gram, const int32_t* item,
                      const int32_t* prefix_len, const int32_t* limit, void* stream);
 
+/* Chemical validity of FINISHED rows (gct_plus_amd/decode.py SmilesChemistry.check states the rules and is the reference):
+ * one wave per row, nothing to do with the decode loop.  Row r's span is ys[r][start[r], W) -- its generated tokens, the
+ * <eos> and whatever follows it included; nothing outside the span is read.  W - start[r] <= 256 and 0 <= start[r] <= W
+ * (a row outside that range is reported as SYNTAX at position 0).  table: the grammar's (int32 [V], as above).
+ * chem: int32 [V], one word per token:
+ *   bits 0..3    the atom's valence cap, GCT_CHEM_NO_CAP (15) for none and for every token that is no atom
+ *   bits 4..7    the atom's explicit hydrogen count
+ *   bit  8       the atom is aromatic          bit 9   the atom is carbon-like (its effective element is C)
+ *   bits 12..14  the order of a BOND token (1 .. 4), 0 for every other token
+ * out [n][4] int32 = (status, position, atoms, ring_bonds), all four written for every row:
+ *   SYNTAX     the span is not well formed (an id outside [0, V) and an empty span included); position = the first token
+ *              without a transition, or the span's length when no <eos> was reached; atoms = ring_bonds = 0
+ *   RING_BOND  a ring closure whose two ends state different orders, or that doubles an existing bond (no bond is added)
+ *   VALENCE    an atom whose bond orders + explicit H (+ 1 for an aromatic carbon-like atom without a double bond) exceed
+ *              its cap;   AROMATIC  an aromatic atom with fewer than two aromatic neighbours
+ *   the finding at the smallest position wins (position = its token's index in the span); OK has position -1.
+ *   atoms = ATOM tokens, ring_bonds = closing ring tokens (rejected ones included).
+ * n = 0 is a no-op.  No global atomics; the walk's stack and the per-atom sums live in LDS. */
+#define GCT_CHEM_OK 0
+#define GCT_CHEM_SYNTAX 1
+#define GCT_CHEM_VALENCE 2
+#define GCT_CHEM_RING_BOND 3
+#define GCT_CHEM_AROMATIC 4
+#define GCT_CHEM_NO_CAP 15
+int gct_smiles_check(const int64_t* ys, int64_t ld_ys, int W, int n, const int32_t* start, int V, const int32_t* table,
+                     const int32_t* chem, int32_t* out, void* stream);
+
 /* Per-step sampling statistics (gct_plus_amd/decode.py step_stats_reference states the rules).  Launched behind
  * gct_select_token in the step unit, on the same device counter and with gct_chosen_logp's row rule: row r looks at
  * column p = *pos - row_off[r] + 1, takes tok = ys[r][p] and writes each non-null table at out[dst][p].

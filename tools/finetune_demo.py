@@ -15,6 +15,11 @@ that of the whole update, and per epoch.
 through the max_grad_norm argument of the two functions); the rounds then also print the pre-clip norm.  No value is
 prescribed.
 
+--reward chemistry: the sampler decodes with well_formed=True (every row is syntactically right already) and the reward is
+Train/finetune.validity_reward of Sampling.check_rows -- decode.SmilesChemistry's valence / ring-bond / aromaticity check,
+one launch on the device instead of the Python loop over the rows; the printed rate is then the VALID share.  The default,
+--reward grammar, is the run described above and prints what it always did.
+
 --time-step: no sampling; --n fixed rows of MOSES-like lengths (clip(round(N(35, 8)), 15, 78) tokens + <eos> behind a
 scaffold prefix), --rounds reinforce_steps on them after two warm-up steps: the figure to put next to a bench.py
 training step of the same batch size (recorded in DESIGN 4, not gated).  With --ppo-epochs it times ONE epoch:
@@ -43,6 +48,10 @@ ap.add_argument("--ppo-epochs", type=int, default=0,
 ap.add_argument("--clip", type=float, default=0.2, help="PPO's clip: ratios are held in [1 - E, 1 + E]")
 ap.add_argument("--max-grad-norm", type=float, default=None,
                 help="bound on the global L2 norm of every update's gradient (FusedAdam clips on the device)")
+ap.add_argument("--reward", choices=("grammar", "chemistry"), default="grammar",
+                help="grammar: 1 for a well-formed string; chemistry: constrained decoding, 1 for a chemically valid one")
+ap.add_argument("--report-valid", action="store_true",
+                help="one more line at the end: the chemically valid share of the evaluation batch before and after")
 ap.add_argument("--time-step", action="store_true",
                 help="time reinforce_step (one ppo_update epoch with --ppo-epochs) on fixed rows of MOSES-like lengths")
 a = ap.parse_args()
@@ -55,7 +64,7 @@ from gct_plus_amd.decode import SmilesGrammar  # noqa: E402
 from gct_plus_amd.Inference.sampling_tool import DecodedRows, PscavaetfSampling  # noqa: E402
 from gct_plus_amd.Model import model_dict  # noqa: E402
 from gct_plus_amd.optim import FusedAdam  # noqa: E402
-from gct_plus_amd.Train.finetune import frozen_prior, ppo_update, reinforce_step  # noqa: E402
+from gct_plus_amd.Train.finetune import frozen_prior, ppo_update, reinforce_step, validity_reward  # noqa: E402
 
 mtype = "pscavaetf"
 nc = synthetic.n_conds(mtype)
@@ -66,8 +75,9 @@ SRC = data.Vocab([t for t in synthetic.GRAMMAR_VOCAB if t not in ("<sos>", "<eos
 torch.manual_seed(a.seed)
 model = model_dict[mtype](len(SRC), len(TRG), dropout=0.0, nconds=nc, use_cond2lat=True, **dims).cuda()
 sampler = PscavaetfSampling(model, SRC, TRG, latent_dim=dims["latent_dim"], max_strlen=a.max_strlen, cond_dim=nc,
-                            decode_algo="multinomial", seed=a.seed)
-grammar = SmilesGrammar(TRG.itos, sampler.pad_id, sampler.eos_id)
+                            decode_algo="multinomial", seed=a.seed, well_formed=a.reward == "chemistry")
+WHAT = "valid" if a.reward == "chemistry" else "well-formed"
+grammar = SmilesGrammar(TRG.itos, sampler.pad_id, sampler.eos_id) if a.reward == "grammar" else None
 opt = FusedAdam(model.parameters(), lr=a.lr, betas=(0.9, 0.98), eps=1e-9, model=model)
 gen = torch.Generator().manual_seed(a.seed)
 prior = frozen_prior(model) if a.kl_coef else None
@@ -145,6 +155,8 @@ def sample(n, seed):
     out = sampler.sample_smiles(torch.randn(n, nc, generator=g).numpy(), a.scaffold, zs=zs, toklen=toklen, transform=False,
                                 return_rows=True)
     rows = out[-1]
+    if a.reward == "chemistry":
+        return rows, validity_reward(sampler.check_rows(rows))
     t0 = int(rows.prefix_lens[0])
     reward = torch.tensor([float(grammar.well_formed(r)) for r in rows.ys[:, t0:].cpu().tolist()])
     return rows, reward
@@ -158,10 +170,13 @@ def evaluate():
     distinct = len({tuple(t for t in r if t != sampler.pad_id) for r in rows.ys[:, t0:].cpu().tolist()})
     with torch.no_grad():
         terms = sampler.policy_terms(*rows)
+    if a.report_valid:
+        VALID_SHARE.append(float(validity_reward(sampler.check_rows(rows)).mean()))
     return float(reward.mean()), distinct, float(terms.entropy.sum() / terms.tokens.sum())
 
 
 EVAL_SEED = 10 ** 6
+VALID_SHARE = []
 before = evaluate()
 reg = f", entropy_coef {a.entropy_coef}, kl_coef {a.kl_coef}" if a.entropy_coef or a.kl_coef else ""
 if a.ppo_epochs:
@@ -169,7 +184,7 @@ if a.ppo_epochs:
 if a.max_grad_norm is not None:
     reg += f", max_grad_norm {a.max_grad_norm:g}"
 print(f"{'full-size' if a.full else 'tiny'} {mtype}, {a.n} molecules per round, lr {a.lr}{reg}: evaluation batch before "
-      f"fine-tuning: well-formed {before[0]:.3f}, {before[1]} distinct strings, entropy {before[2]:.3f} per token",
+      f"fine-tuning: {WHAT} {before[0]:.3f}, {before[1]} distinct strings, entropy {before[2]:.3f} per token",
       flush=True)
 ms = []
 for k in range(a.rounds):
@@ -182,16 +197,19 @@ for k in range(a.rounds):
         if "grad_norm" in last:
             more += (f"  grad norm {max(s['grad_norm'] for s in stats):8.4f}  clipped updates "
                      f"{sum(s['clipped_updates'] for s in stats)}")
-        print(f"round {k:3d}: well-formed {float(reward.mean()):.3f}  loss {stats[0]['loss']:8.4f} -> {last['loss']:8.4f}  "
+        print(f"round {k:3d}: {WHAT} {float(reward.mean()):.3f}  loss {stats[0]['loss']:8.4f} -> {last['loss']:8.4f}  "
               f"clipped {last['clip_fraction']:.3f}  approx_kl {last['approx_kl']:.5f}{more}  update {dt:7.2f} ms "
               f"({dt / len(stats):.2f} per epoch)", flush=True)
         continue
     more = "".join(f"  {key[5:]} {stats[key]:7.4f}" for key in ("mean_entropy", "mean_kl") if key in stats)
     if "grad_norm" in stats:
         more += f"  grad norm {stats['grad_norm']:8.4f}{' (clipped)' if stats['clipped'] else ''}"
-    print(f"round {k:3d}: well-formed {stats['mean_reward']:.3f}  mean logp {stats['mean_logp']:8.3f}  loss "
+    print(f"round {k:3d}: {WHAT} {stats['mean_reward']:.3f}  mean logp {stats['mean_logp']:8.3f}  loss "
           f"{stats['loss']:8.4f}{more}  step {dt:7.2f} ms", flush=True)
 after = evaluate()
-print(f"evaluation batch of {a.n}: well-formed {before[0]:.3f} -> {after[0]:.3f}, distinct strings {before[1]} -> "
+print(f"evaluation batch of {a.n}: {WHAT} {before[0]:.3f} -> {after[0]:.3f}, distinct strings {before[1]} -> "
       f"{after[1]}, entropy per token {before[2]:.3f} -> {after[2]:.3f} after {a.rounds} rounds{reg}; "
       f"{'ppo_update' if a.ppo_epochs else 'reinforce_step'} median {float(np.median(ms[1:] or ms)):.2f} ms")
+if a.report_valid:
+    print(f"chemically valid share of the evaluation batch (decode.SmilesChemistry): {VALID_SHARE[0]:.3f} -> "
+          f"{VALID_SHARE[1]:.3f}")
