@@ -63,6 +63,10 @@ its order, aromatic atoms outside an aromatic ring.  A necessary condition of va
 Train/finetune.validity_reward turns the report into the reward of reinforce_step / ppo_update; `is_valid(smiles)` is the
 same verdict for one string, usable as accept= of interpolate_smiles.
 
+`randomize_smiles(smiles_list, scaffold_list, k, seed)` (any sampler): k random spellings of every given molecule -- the
+same graph written out by a random depth-first traversal (randomize.SmilesRandomizer, one launch, no rdkit), for
+encode_smiles / score_smiles; the reference's randomize_smiles for callers.
+
 `decode_smc` (any sampler, any decode_algo): sequential Monte Carlo under the grammar (KVDecoder.generate_smc) -- k weighted
 well-formed molecules per latent whose weighted distribution converges to the model's own distribution restricted to
 well-formed strings, which a well_formed=True decode's locally renormalised draws do not follow, and an unbiased estimate
@@ -95,6 +99,7 @@ from ..decode import (BEAM_ALPHA, ChemReport, KVDecoder, Marginal, PolicyTerms, 
                       SmilesGrammar, check_beam_size, check_ess_threshold, check_grammar, check_particles,
                       check_sample_filter, check_stream_model, check_stream_rows, generated_tokens, marginal_logp,
                       score_tokens, sequence_logp, sequence_policy, sequence_ppo)
+from ..randomize import SmilesRandomizer
 
 
 BEAM_ALGOS = ("beam", "stochastic_beam")        # decode_algo values that decode k rows per sample in step (kv_src)
@@ -239,6 +244,7 @@ class Sampling:
         self.marginal_seed = seed               # marginal(seed=None): advanced once per call, so calls draw afresh
         self.kv = KVDecoder(model, self.pad_id, self.sos_id, self.eos_id)
         self._chemistry = None
+        self._randomizer = None
 
     # ---- chemical validity of decoded rows (decode.SmilesChemistry: a check behind the decode, not a constraint on it)
     @property
@@ -265,6 +271,54 @@ class Sampling:
         which no SMILES holds).  `scaffold` is accepted and ignored, so that the method serves as accept= of
         interpolate_smiles whatever the model type."""
         return bool(smiles) and self.chemistry.valid(self.smi_to_id(smiles, add_eos=True))
+
+    # ---- random spellings of given molecules (randomize.SmilesRandomizer: the reference's randomize_smiles, no rdkit)
+    @property
+    def randomizer(self) -> SmilesRandomizer:
+        """The SmilesRandomizer over the target vocabulary, built on first use."""
+        if self._randomizer is None:
+            self._randomizer = SmilesRandomizer(self.TRG.itos, self.pad_id, self.eos_id, self.sep_id)
+        return self._randomizer
+
+    def randomize_smiles(self, smiles_list, scaffold_list=None, k=1, seed=0):
+        """k random spellings of every molecule, for encode_smiles / score_smiles: one launch on the sampler's device.
+        Returns (spellings, status): spellings[i] a list of k strings -- of k (scaffold, smiles) pairs with
+        scaffold_list, both parts respelled on their own -- and status int32 [n, k, 2] on the CPU = the ops.RAND_* code
+        of the molecule and of the scaffold (-1 without one).  A part that cannot be randomised (a stereo mark, a dot,
+        a token outside the vocabulary, no room inside 256 tokens) comes back as it was written and its status says
+        why.  Spelling j of molecule i is keyed i | j << 32 under `seed`: it does not depend on k or on the other
+        molecules.  The same graph in another atom order: atoms and bond symbols are carried verbatim."""
+        smiles_list = list(smiles_list)
+        n, k = len(smiles_list), int(k)
+        if k < 1:
+            raise ValueError(f"k must be at least 1, got {k}")
+        if scaffold_list is not None:
+            if not self.add_sep:
+                raise ValueError("scaffold_list needs a scaffold model's vocabulary (no <sep> token here)")
+            scaffold_list = list(scaffold_list)
+            if len(scaffold_list) != n:
+                raise ValueError(f"{len(scaffold_list)} scaffolds for {n} molecules")
+        rows = [self.smi_to_id(s, add_eos=True) for s in smiles_list]
+        if scaffold_list is not None:
+            rows = [self.smi_to_id(c) + [self.sep_id] + r for c, r in zip(scaffold_list, rows)]
+        W = max((len(r) for r in rows), default=1)
+        ys = torch.tensor([r + [self.pad_id] * (W - len(r)) for r in rows], dtype=torch.int64).view(n, W)
+        ys = ys.repeat_interleave(k, 0).to(self.device)
+        key = torch.arange(n, dtype=torch.int64).view(n, 1) | (torch.arange(k, dtype=torch.int64).view(1, k) << 32)
+        got = self.randomizer.randomize_rows(ys, torch.zeros(n * k, dtype=torch.int64), key.reshape(-1), seed, 1.0,
+                                             out_width=max(W, min(W + 32, 256)))
+        out, tokens = [], got.tokens.cpu().tolist()
+        for i in range(n):
+            spell = []
+            for row in tokens[i * k:(i + 1) * k]:
+                ids = row[:row.index(self.eos_id)] if self.eos_id in row else row
+                if scaffold_list is not None and self.sep_id in ids:
+                    c = ids.index(self.sep_id)
+                    spell.append((self.id_to_smi(ids[:c]), self.id_to_smi(ids[c + 1:])))
+                else:
+                    spell.append(self.id_to_smi(ids))
+            out.append(spell)
+        return out, got.info[:, :2].cpu().view(n, k, 2)
 
     # ---- helpers with the reference's names ------------------------------------------------
     def init_y(self, n, add_sos=True, sca_ids=None, add_sep=False):

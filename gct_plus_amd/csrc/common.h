@@ -77,6 +77,14 @@ __device__ __forceinline__ uint32_t gct_pick(uint4 v, int c) {
   return c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w));
 }
 
+// SMILES randomisation (randomize.hip; randomize.py stream() restates it): site GCT_SITE_RANDOMIZE, counter
+// (key low, key high, part, index) -- key the caller's int64 per row, part 0 the molecule and 1 the scaffold.
+//   index 0:                     x the coin (randomise iff p >= 1 or x < floor(float32(p) * 2^32)),
+//                                y the root, floor(y * atoms / 2^32)
+//   index 1 + 2 a + (i - 1) / 4: word (i - 1) % 4 is step i of the Fisher-Yates shuffle of INPUT atom a's bond list,
+//                                j = floor(word * (i + 1) / 2^32), i = deg - 1 .. 1, deg <= 8
+#define GCT_SITE_RANDOMIZE 0x5A11E5u
+
 // e = row & 3; bits = gct_drop_bits(rng, row >> 2, col)
 __device__ __forceinline__ bool gct_drop_keep(uint4 bits, int e, uint32_t col, uint32_t thr) {
   const uint32_t w = gct_pick(bits, e);

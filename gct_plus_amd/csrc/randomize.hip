@@ -1,0 +1,379 @@
+// SMILES randomisation on the device: gct_smiles_randomize against randomize.py SmilesRandomizer (randomize is the
+// statement for one part, randomize_reference the batch rule).  One wave per row, four rows per workgroup, in
+// smiles_check_kernel's shape (decode.hip): lane l stages tokens l + 64 t of the row's span in the wave's own LDS and
+// the wave finds the first <eos> and the first <sep> in front of it; then, part by part (the scaffold, if any, first):
+//   lane 0 parses the part into bonds and per-atom bond lists and tosses the coin;
+//   lane l shuffles the lists of atoms l + 64 t (Philox calls keyed by the INPUT atom: none waits for the walk);
+//   lane 0 runs the depth-first search that tells tree edges from ring bonds, and the emission into the LDS row;
+// and all lanes write the output row, perm and info.  The walks are one lane's because every step depends on the one
+// before; what they leave is indexed dynamically in LDS, never in registers, so nothing spills.  No global atomics.
+// An entry of the LDS row is a literal token id (>= 0: ring numbers, parentheses, <sep>, <eos>) or -(j + 1): the token
+// at position j of the input span (atoms and bond symbols are carried verbatim, whatever their ids).
+#include "common.h"
+
+namespace {
+
+enum { RP_START, RP_ATOM, RP_RING, RP_BOND_A, RP_BOND_B, RP_OPEN, RP_CLOSE, RP_DOT };
+constexpr int kMaxDeg = 8;                                   // randomize.MAX_DEGREE
+constexpr int kNone = 0x7fffffff;
+
+struct RandWave {
+  int32_t e[256];                                            // table word | (the token is <sep>) << 24
+  int32_t out[256];
+  uint32_t ring[GCT_GRAMMAR_MAX_RINGS];                      // open occurrence: atom | order << 8 | (symbol pos + 1) << 12
+  int16_t bsym[256];                                         // bond -> position of its BOND token, -1: none
+  int16_t par[256];                                          // atom -> chain parent (-1: none)
+  uint16_t apos[256], stk[256], stamp[256];                  // (stamp: smiles_check_kernel's "bonded already" rule)
+  uint8_t adj[256][kMaxDeg];                                 // atom -> its bonds, parse order, then shuffled
+  uint8_t ba[256], bb[256];                                  // bond -> its ends, ba < bb
+  uint8_t deg[256], seen[256], pbond[256], left[256];        // per atom; pbond: the bond the search came by (0xFF: root)
+  uint8_t role[256], rnum[256];                              // per bond; role 0 unseen, 1 tree, 2 / 3 ring opened at ba / bb
+  uint8_t perm[256];
+  int32_t res[4];                                            // randomise this part, its atoms, its bonds
+};
+
+__host__ __device__ inline void rand_link(RandWave& w, int a, int b, int sym, int& nb, bool& unsup) {
+  if (w.deg[a] >= kMaxDeg || w.deg[b] >= kMaxDeg) {
+    unsup = true;
+    return;
+  }
+  const int e = nb++;                                        // (a link takes an ATOM or a closing RING token: nb <= 254)
+  w.ba[e] = (uint8_t)a, w.bb[e] = (uint8_t)b;
+  w.bsym[e] = (int16_t)sym;
+  w.adj[a][w.deg[a]++] = (uint8_t)e;
+  w.adj[b][w.deg[b]++] = (uint8_t)e;
+}
+
+// Lane 0: the part e[lo, hi) parsed as SmilesChemistry.check parses it.  Returns false for SYNTAX.  (The two walks are
+// plain C++ over the wave's record, host-callable so that a CPU harness can run them under a sanitizer.)
+__host__ __device__ bool rand_parse(RandWave& w, int lo, int hi, int& atoms, int& bonds, bool& unsup) {
+  int prev = RP_START, depth = 0, cur = -1, pend = 0, pendpos = -1, A = 0, nb = 0, sp = 0;
+  uint64_t open = 0, here = 0;
+  unsup = false;
+  atoms = bonds = 0;
+  for (int i = lo; i < hi; ++i) {
+    const int ent = w.e[i], cls = ent & 0xFF;
+    const bool ar = prev == RP_ATOM || prev == RP_RING, arc = ar || prev == RP_CLOSE;
+    bool ok;
+    if ((ent >> 20) & 1) unsup = true;
+    switch (cls) {
+      case GCT_GRAMMAR_ATOM: {
+        ok = true;
+        prev = RP_ATOM;
+        here = 0;
+        const int a = A++;                                   // (A <= hi - lo <= 255)
+        w.apos[a] = (uint16_t)i;
+        w.deg[a] = 0;
+        w.par[a] = (int16_t)cur;
+        w.stamp[a] = 0;
+        if (cur >= 0) rand_link(w, cur, a, pendpos, nb, unsup);
+        cur = a;
+        pend = 0, pendpos = -1;
+        break;
+      }
+      case GCT_GRAMMAR_BOND:
+        ok = ar || prev == RP_OPEN || prev == RP_CLOSE;
+        prev = ar ? RP_BOND_A : RP_BOND_B;
+        pend = (ent >> 16) & 7, pendpos = i;
+        break;
+      case GCT_GRAMMAR_OPEN:
+        ok = arc;
+        prev = RP_OPEN;
+        ++depth;
+        if (ok) w.stk[sp++] = (uint16_t)cur;                 // (sp <= #OPEN tokens <= 255)
+        break;
+      case GCT_GRAMMAR_CLOSE:
+        ok = arc && depth > 0;
+        prev = RP_CLOSE;
+        --depth;
+        if (ok) cur = w.stk[--sp];
+        pend = 0, pendpos = -1;
+        break;
+      case GCT_GRAMMAR_RING: {
+        ok = ar || prev == RP_BOND_A;
+        const int r = (ent >> 8) & 63;
+        const uint64_t bit = 1ull << r;
+        if (ok && (open & bit)) {
+          if (here & bit) {
+            ok = false;                                      // a ring does not close on the atom that opened it
+          } else {
+            open ^= bit;
+            const uint32_t rec = w.ring[r];
+            const int a = (int)(rec & 0xFFu), o = (int)((rec >> 8) & 7u), osym = (int)(rec >> 12) - 1;
+            if ((o && pend && o != pend) || w.par[cur] == a || w.stamp[a] == cur + 1) {
+              unsup = true;                                  // `check` reports RING_BOND
+            } else {
+              rand_link(w, a, cur, pendpos >= 0 ? pendpos : osym, nb, unsup);
+              w.stamp[a] = (uint16_t)(cur + 1);
+            }
+          }
+        } else if (ok) {
+          open |= bit;
+          here |= bit;
+          w.ring[r] = (uint32_t)cur | ((uint32_t)pend << 8) | ((uint32_t)(pendpos + 1) << 12);
+        }
+        prev = RP_RING;
+        pend = 0, pendpos = -1;
+        break;
+      }
+      case GCT_GRAMMAR_DOT:
+        ok = arc && depth == 0;
+        prev = RP_DOT;
+        unsup = true;
+        cur = -1;
+        pend = 0, pendpos = -1;
+        break;
+      default:                                               // <eos> cannot be here; <pad>, <sep> and banned tokens
+        ok = false;
+        break;
+    }
+    if (!ok) return false;
+  }
+  const bool arc = prev == RP_ATOM || prev == RP_RING || prev == RP_CLOSE;
+  if (!(arc && depth == 0 && open == 0)) return false;       // the <eos> behind the part
+  atoms = A, bonds = nb;
+  return true;
+}
+
+// Lane 0: passes 1 and 2 of the statement for a part of A atoms rooted at `root`, into w.out[opos, opos + room) and
+// w.perm[abase, abase + A).  Returns the length of the new spelling (it may exceed room: nothing is written past it),
+// or -1 when no ring number was free.
+__host__ __device__ int rand_walk(RandWave& w, int A, int root, int opos, int room, int abase,
+                                  const int32_t* __restrict__ ring_ids, int n_rings, int open_id, int close_id) {
+  // pass 1 (seen / left / role were cleared by the lanes)
+  int sp = 0;
+  w.seen[root] = 1;
+  w.pbond[root] = 0xFF;
+  w.stk[sp++] = (uint16_t)root;                              // atom | next list index << 8; sp <= A <= 255
+  while (sp > 0) {
+    const int f = w.stk[sp - 1], u = f & 0xFF, i = f >> 8;
+    if (i == w.deg[u]) {
+      --sp;
+      continue;
+    }
+    w.stk[sp - 1] = (uint16_t)(u | ((i + 1) << 8));
+    const int e = w.adj[u][i];
+    if (e == w.pbond[u] || w.role[e] != 0) continue;
+    const int v = w.ba[e] ^ w.bb[e] ^ u;
+    if (w.seen[v]) {
+      w.role[e] = v == w.ba[e] ? 2 : 3;                      // v is an ancestor: the opening end
+    } else {
+      w.seen[v] = 1;
+      w.pbond[v] = (uint8_t)e;
+      w.role[e] = 1;
+      ++w.left[u];
+      w.stk[sp++] = (uint16_t)v;
+    }
+  }
+  // pass 2
+  uint64_t free_ = (1ull << n_rings) - 1;                    // (n_rings <= 63) bit k: ring_ids[k] is free
+  int k = 0, pk = 0;
+  bool no_ring = false;
+  auto emit = [&](int v) {
+    if (k < room) w.out[opos + k] = v;
+    ++k;
+  };
+  auto emit_atom = [&](int u) {
+    emit(-((int)w.apos[u] + 1));
+    w.perm[abase + pk++] = (uint8_t)(abase + u);             // (every atom is emitted once: pk <= A)
+    uint64_t closed = 0;
+    const int d = w.deg[u];
+    for (int i = 0; i < d; ++i) {
+      const int e = w.adj[u][i], r = w.role[e];
+      if (r < 2) continue;
+      if ((r == 2 ? w.ba[e] : w.bb[e]) == u) {
+        if (w.bsym[e] >= 0) emit(-((int)w.bsym[e] + 1));
+        if (!free_) {
+          no_ring = true;
+          return;
+        }
+        const int idx = __builtin_ctzll(free_);
+        free_ &= free_ - 1;
+        w.rnum[e] = (uint8_t)idx;
+        emit(ring_ids[idx]);
+      } else {
+        const int idx = w.rnum[e];
+        emit(ring_ids[idx]);
+        closed |= 1ull << idx;
+      }
+    }
+    free_ |= closed;                                         // free again from the next atom on
+  };
+  emit_atom(root);
+  sp = 0;
+  w.stk[sp++] = (uint16_t)root;                              // atom | next list index << 8 | inside parentheses << 12
+  while (sp > 0 && !no_ring) {
+    const int f = w.stk[sp - 1], u = f & 0xFF, paren = (f >> 12) & 1, d = w.deg[u];
+    int i = (f >> 8) & 15;
+    while (i < d && !(w.role[w.adj[u][i]] == 1 && w.adj[u][i] != w.pbond[u])) ++i;
+    if (i == d) {
+      --sp;
+      if (paren) emit(close_id);
+      continue;
+    }
+    const int e = w.adj[u][i], v = w.ba[e] ^ w.bb[e] ^ u;
+    w.stk[sp - 1] = (uint16_t)(u | ((i + 1) << 8) | (paren << 12));
+    const int branch = --w.left[u] > 0;
+    if (branch) emit(open_id);
+    if (w.bsym[e] >= 0) emit(-((int)w.bsym[e] + 1));
+    emit_atom(v);
+    w.stk[sp++] = (uint16_t)(v | (branch << 12));
+  }
+  return no_ring ? -1 : k;
+}
+
+__global__ __launch_bounds__(256) void smiles_randomize_kernel(
+    const int64_t* __restrict__ ys, int64_t ld_ys, int W, int n, const int32_t* __restrict__ start,
+    const int64_t* __restrict__ key, int V, const int32_t* __restrict__ table, const int32_t* __restrict__ ring_ids,
+    int n_rings, int open_id, int close_id, int pad_id, int eos_id, int sep_id, GctRng rng, float p,
+    int64_t* __restrict__ out, int32_t* __restrict__ info, int32_t* __restrict__ perm, int out_width) {
+  __shared__ RandWave sh[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int row = blockIdx.x * 4 + wave;
+  const bool live = row < n;
+  RandWave& w = sh[wave];
+  const int t0 = live ? start[row] : W;
+  const bool in_range = live && t0 >= 0 && t0 <= W && W - t0 <= 256;
+  const int g = in_range ? W - t0 : 0;                       // 0 <= g <= 256 tokens in the span
+  const int64_t* yr = ys + (int64_t)row * ld_ys + (in_range ? t0 : 0);   // (read only under j < g, or as the whole row)
+  int E = kNone, sep_at = 0;                                 // first <eos>; bit t: token lane + 64 t is <sep>
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int j = lane + 64 * t;
+    if (j < g) {
+      const int64_t tok = yr[j];
+      int word = tok >= 0 && tok < V ? table[tok] & 0x1FFFFF : GCT_GRAMMAR_BANNED;
+      if (tok == sep_id) word |= 1 << 24, sep_at |= 1 << t;  // (sep_id -1: none)
+      w.e[j] = word;
+      if (tok == eos_id) E = min(E, j);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) E = min(E, __shfl_xor(E, o, 64));
+  int S = kNone;                                             // first <sep> in front of the <eos>
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+    if (((sep_at >> t) & 1) && lane + 64 * t < E) S = min(S, lane + 64 * t);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) S = min(S, __shfl_xor(S, o, 64));
+  const bool row_bad = E == kNone;                           // (a dead wave and a row out of range: g = 0, no <eos>)
+  const bool two = S != kNone;
+  const int total = in_range ? min(out_width - t0, 256) : 0; // columns the new span may take: total >= g > E
+  const int64_t kw = live ? key[row] : 0;
+  const uint32_t klo = (uint32_t)kw, khi = (uint32_t)((uint64_t)kw >> 32);
+  int opos = 0, abase = 0, st_mol = GCT_RAND_SYNTAX, st_sca = -1;   // lane 0's: output columns and atoms so far
+
+  for (int it = 0; it < 2; ++it) {
+    const int which = 1 - it;                                // the scaffold (part 1) first, then the molecule (part 0)
+    const bool active = !row_bad && (which == 0 || two);
+    const int lo = which == 1 ? 0 : (two ? S + 1 : 0), hi = which == 1 ? S : E;
+    int A = 0, nb = 0, status = GCT_RAND_SYNTAX;
+    uint32_t root_word = 0;
+    __syncthreads();                                         // the staged row; the last part's lists are done with
+    if (active && lane == 0) {
+      bool unsup;
+      const bool parsed = rand_parse(w, lo, hi, A, nb, unsup);
+      status = !parsed ? GCT_RAND_SYNTAX : unsup ? GCT_RAND_UNSUPPORTED : GCT_RAND_KEPT;
+      if (status == GCT_RAND_KEPT) {
+        const uint4 c = gct_philox(rng, klo, khi, (uint32_t)which, 0u);
+        root_word = c.y;
+        if (p >= 1.f || c.x < (uint32_t)((double)p * 4294967296.0)) status = GCT_RAND_OK;   // (0 <= p < 1: below 2^32)
+      }
+      w.res[0] = status == GCT_RAND_OK, w.res[1] = A, w.res[2] = nb;
+    } else if (lane == 0) {
+      w.res[0] = 0;
+    }
+    __syncthreads();
+    if (w.res[0]) {
+      const int nA = w.res[1], nB = w.res[2];
+      for (int e = lane; e < nB; e += 64) w.role[e] = 0;
+      for (int a = lane; a < nA; a += 64) {
+        w.seen[a] = 0, w.left[a] = 0;
+        const int d = w.deg[a];
+        if (d < 2) continue;
+        const uint4 c0 = gct_philox(rng, klo, khi, (uint32_t)which, (uint32_t)(1 + 2 * a));
+        uint4 c1 = make_uint4(0, 0, 0, 0);
+        if (d > 5) c1 = gct_philox(rng, klo, khi, (uint32_t)which, (uint32_t)(2 + 2 * a));
+        for (int i = d - 1; i >= 1; --i) {
+          const uint32_t x = i - 1 < 4 ? gct_pick(c0, i - 1) : gct_pick(c1, i - 5);
+          const int j = (int)__umulhi(x, (uint32_t)(i + 1));
+          const uint8_t ti = w.adj[a][i], tj = w.adj[a][j];
+          w.adj[a][i] = tj, w.adj[a][j] = ti;
+        }
+      }
+    }
+    __syncthreads();
+    if (active && lane == 0) {
+      const int len = hi - lo;
+      // room: <eos>, and for the scaffold the <sep> and the molecule's input length, stay inside `total`
+      const int room = total - 1 - (which == 1 ? 1 + (E - S - 1) : opos);
+      int k = len;
+      if (status == GCT_RAND_OK) {
+        k = rand_walk(w, A, (int)__umulhi(root_word, (uint32_t)A), opos, room, abase, ring_ids, n_rings, open_id,
+                      close_id);
+        if (k < 0) status = GCT_RAND_NO_RING;
+        else if (k > room) status = GCT_RAND_TOO_LONG;
+      }
+      if (status != GCT_RAND_OK) {                           // kept: the input tokens, the atoms in their order
+        k = len;                                             // (opos + len < total: the input fitted)
+        for (int i = 0; i < len; ++i) w.out[opos + i] = -(lo + i + 1);
+        for (int a = 0; a < A; ++a) w.perm[abase + a] = (uint8_t)(abase + a);
+      }
+      w.out[opos + k] = which == 1 ? sep_id : eos_id;
+      opos += k + 1;
+      abase += A;                                            // (A = 0 for SYNTAX)
+      if (which == 1) st_sca = status; else st_mol = status;
+    }
+  }
+  if (lane == 0) w.res[0] = opos, w.res[1] = abase;
+  __syncthreads();
+  if (!live) return;
+  const int outlen = w.res[0], atoms = w.res[1];
+  int64_t* orow = out + (int64_t)row * out_width;
+  if (row_bad) {
+    const int64_t* whole = ys + (int64_t)row * ld_ys;
+    for (int c = lane; c < out_width; c += 64) orow[c] = c < W ? whole[c] : (int64_t)pad_id;
+  } else {
+    const int64_t* whole = yr - t0;
+    for (int c = lane; c < out_width; c += 64) {
+      int64_t tok = pad_id;
+      if (c < t0) {
+        tok = whole[c];
+      } else if (c - t0 < outlen) {                          // outlen <= total <= 256
+        const int v = w.out[c - t0];
+        tok = v >= 0 ? (int64_t)v : yr[-v - 1];              // -v - 1 < E < g
+      }
+      orow[c] = tok;
+    }
+  }
+  if (perm) {
+    int32_t* prow = perm + (int64_t)row * out_width;
+    for (int c = lane; c < out_width; c += 64) prow[c] = c < atoms ? (int32_t)w.perm[c] : -1;   // atoms <= 255
+  }
+  if (lane == 0) {
+    int32_t* o4 = info + (int64_t)row * 4;
+    o4[0] = st_mol, o4[1] = row_bad ? -1 : st_sca, o4[2] = row_bad ? g : outlen, o4[3] = atoms;
+  }
+}
+
+}  // namespace
+
+extern "C" int gct_smiles_randomize(const int64_t* ys, int64_t ld_ys, int W, int n, const int32_t* start,
+                                    const int64_t* key, int V, const int32_t* table, const int32_t* ring_ids, int n_rings,
+                                    int open_id, int close_id, int pad_id, int eos_id, int sep_id, uint64_t seed, float p,
+                                    int64_t* out, int32_t* info, int32_t* perm, int out_width, void* stream) {
+  GCT_CHECK_ARG(ys && start && key && table && ring_ids && out && info && n >= 0 && V > 0, "smiles_randomize: bad args");
+  GCT_CHECK_ARG(W >= 0 && ld_ys >= W && out_width >= W, "smiles_randomize: %d token columns in rows of %lld, %d out", W,
+                (long long)ld_ys, out_width);
+  GCT_CHECK_ARG(n_rings >= 0 && n_rings <= 63, "smiles_randomize: %d ring numbers (at most 63)", n_rings);
+  GCT_CHECK_ARG(open_id >= 0 && open_id < V && close_id >= 0 && close_id < V && pad_id >= 0 && pad_id < V &&
+                    eos_id >= 0 && eos_id < V && sep_id >= -1 && sep_id < V,
+                "smiles_randomize: a token id outside the vocabulary of %d", V);
+  GCT_CHECK_ARG(p >= 0.f && p <= 1.f, "smiles_randomize: p = %g is no probability", (double)p);
+  if (n == 0) return GCT_OK;
+  hipLaunchKernelGGL(smiles_randomize_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, ys, ld_ys,
+                     W, n, start, key, V, table, ring_ids, n_rings, open_id, close_id, pad_id, eos_id, sep_id,
+                     gct_rng_make(seed, GCT_SITE_RANDOMIZE), p, out, info, perm, out_width);
+  GCT_LAUNCH_CHECK("smiles_randomize");
+  return GCT_OK;
+}

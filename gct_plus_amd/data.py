@@ -103,10 +103,15 @@ def get_fields(model_type: str, util_folder: str, train_smiles: Optional[Sequenc
 class SmilesLoader:
     """DataLoader + DistributedSampler + collate_fn of the reference in one object: per-rank index
     shard (DistributedSampler semantics), per-batch tokenisation (like SmilesDataset.__getitem__,
-    Utils/dataset.py:269-286) and padding to the batch's longest row (Field.process)."""
+    Utils/dataset.py:269-286) and padding to the batch's longest row (Field.process).
+    randomize_prob > 0 (Utils/dataset.py:263-267): each molecule, and each scaffold of the scaffold models, is rewritten
+    with that probability as a random spelling of itself (randomize.SmilesRandomizer, on the loader's device; on a CPU
+    device, a test rig, the host statement).  The stream of dataset item i in epoch e is keyed i | e << 32 under the
+    loader's seed, and the row may grow to the randomiser's 256 columns whatever the batch holds, so an item's spelling
+    does not depend on batch size, rank count or row order.  `trg` rows longer than 257 columns are a ValueError then."""
 
     def __init__(self, frame, SRC: Vocab, TRG: Vocab, model_type, property_list, batch_size, rank, world,
-                 shuffle, seed, device, use_scaffold=False):
+                 shuffle, seed, device, use_scaffold=False, randomize_prob=0.0):
         self.f, self.SRC, self.TRG = frame, SRC, TRG
         self.props = list(property_list)
         self.add_sep = model_type in ("scavaetf", "pscavaetf")
@@ -118,6 +123,26 @@ class SmilesLoader:
         if self.props:
             self.econds = torch.tensor(frame[[f"src_{p}" for p in self.props]].values, dtype=torch.float32)
             self.dconds = torch.tensor(frame[[f"trg_{p}" for p in self.props]].values, dtype=torch.float32)
+        self.randomize_prob = float(randomize_prob)
+        if not 0.0 <= self.randomize_prob <= 1.0:
+            raise ValueError(f"randomize_prob must be a probability in [0, 1], got {randomize_prob}")
+        self.randomizer = None
+        if self.randomize_prob > 0:
+            from .randomize import SmilesRandomizer
+            self.randomizer = SmilesRandomizer(TRG.itos, TRG.stoi["<pad>"], TRG.stoi["<eos>"],
+                                               TRG.stoi["<sep>"] if self.add_sep else None)
+            # TRG id -> SRC id: the new src row is one gather of the new trg row, its <eos> and <pad> becoming SRC's <pad>
+            to_src, missing = [], []
+            for t in TRG.itos:
+                if t in ("<eos>", "<pad>", "<sos>"):
+                    to_src.append(SRC.stoi["<pad>"])
+                else:
+                    to_src.append(SRC.stoi.get(t, -1))
+                    if t not in SRC.stoi:
+                        missing.append(t)
+            if missing:
+                raise ValueError(f"randomize_prob > 0: the target tokens {missing[:8]} have no id in the source vocabulary")
+            self._to_src = torch.tensor(to_src, dtype=torch.int64, device=device)
 
     def set_epoch(self, epoch):
         self.epoch = epoch
@@ -130,14 +155,32 @@ class SmilesLoader:
             strs = [self.sca_col[i] + "<sep>" + self.src_col[i] for i in idx]
         else:
             strs = [self.src_col[i] for i in idx]
-        src, _ = self.SRC.encode_batch(strs, self.add_sep, sos_eos=False)
         trg, _ = self.TRG.encode_batch(strs, self.add_sep, sos_eos=True)
-        out = {"src": src.to(self.device), "trg": trg.to(self.device)}
+        if self.randomizer is None:
+            src, _ = self.SRC.encode_batch(strs, self.add_sep, sos_eos=False)
+            out = {"src": src.to(self.device), "trg": trg.to(self.device)}
+        else:
+            out = self._randomized(trg.to(self.device), idx)
         if self.props:
             ii = torch.as_tensor(idx)
             out["econds"] = self.econds[ii].to(self.device)
             out["dconds"] = self.dconds[ii].to(self.device)
         return out
+
+    def _randomized(self, trg, idx):
+        """src and trg of a batch whose canonical trg rows are on the device: one randomiser launch behind the <sos>
+        column, one read-back (the longest new row), and src as a gather of the new trg rows."""
+        rz, n = self.randomizer, trg.shape[0]
+        key = torch.as_tensor(list(idx), dtype=torch.int64) | (int(self.epoch) << 32)
+        start = torch.ones(n, dtype=torch.int64)
+        width = 1 + 256                                   # (randomize.py: a span takes at most 256 columns)
+        if trg.shape[1] > width:
+            raise ValueError(f"randomize_prob > 0: a row of {trg.shape[1] - 2} tokens; the randomiser takes at most 255")
+        call = rz.randomize_rows if trg.is_cuda else rz.randomize_reference
+        got = call(trg, start, key, self.seed, self.randomize_prob, out_width=width, return_perm=False)
+        longest = 1 + int(got.info[:, 2].max()) if n else trg.shape[1]
+        new = got.tokens[:, :max(longest, 3)].contiguous()
+        return {"src": self._to_src[new[:, 1:-1]], "trg": new}
 
     def __iter__(self):
         idx = shard_indices(len(self.src_col), self.world, self.rank, self.epoch, self.seed, self.shuffle)

@@ -1442,6 +1442,70 @@ def smiles_check(ys, start, table, chem, out=None):
     return out
 
 
+# status codes of the SMILES randomiser (GCT_RAND_* of include/gctplus_hip.h), the site of its Philox streams
+# (GCT_SITE_RANDOMIZE of csrc/common.h) and its per-token word:
+# class | ring number << 8 | bond order << 16 | unsupported (a / or \ bond, an atom with @) << 20
+RAND_OK, RAND_KEPT, RAND_SYNTAX, RAND_UNSUPPORTED, RAND_NO_RING, RAND_TOO_LONG = range(6)
+RAND_MAX_SPAN = 256
+RANDOMIZE_SITE = 0x5A11E5
+
+
+def smiles_randomize(ys, start, key, table, ring_ids, n_rings, open_id, close_id, pad_id, eos_id, sep_id, seed, p,
+                     out_width=None, return_perm=False, out=None):
+    """gct_smiles_randomize: every row's span ys[r, start[r]:] written out again as a random spelling of the same
+    molecule (randomize.SmilesRandomizer.randomize_reference is the statement).  ys int64 [n, W] with unit column
+    stride, start int32 [n] and key int64 [n] on the device, table int32 [V] and ring_ids int32 [64]
+    (SmilesRandomizer.device_tables), sep_id -1 for none.  Returns (tokens int64 [n, out_width], info int32 [n, 4],
+    perm int32 [n, out_width] or None), freshly allocated or the contiguous tensors of out = (tokens, info, perm or None).
+    One launch."""
+    _chk(ys, "smiles_randomize.ys", torch.int64), _chk(start, "smiles_randomize.start", torch.int32)
+    _chk(key, "smiles_randomize.key", torch.int64), _chk(table, "smiles_randomize.table", torch.int32)
+    _chk(ring_ids, "smiles_randomize.ring_ids", torch.int32)
+    if ys.dim() != 2 or ys.shape[1] < 1 or (ys.shape[1] > 1 and ys.stride(1) != 1):
+        raise ValueError("smiles_randomize: ys [n, W >= 1] with unit column stride")
+    n, W = ys.shape
+    for name, t in (("start", start), ("key", key)):
+        if t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"smiles_randomize: {name} must be a contiguous tensor [{n}], got {list(t.shape)}")
+    if table.dim() != 1 or table.numel() < 1 or not table.is_contiguous():
+        raise ValueError("smiles_randomize: table int32 [V], contiguous")
+    V = table.numel()
+    if ring_ids.dim() != 1 or ring_ids.numel() != 64 or not ring_ids.is_contiguous() or not 0 <= int(n_rings) <= 63:
+        raise ValueError("smiles_randomize: ring_ids int32 [64], contiguous, with at most 63 numbers in use")
+    for name, v in (("open_id", open_id), ("close_id", close_id), ("pad_id", pad_id), ("eos_id", eos_id)):
+        if not 0 <= int(v) < V:
+            raise ValueError(f"smiles_randomize: {name} {v} is outside the vocabulary of {V} tokens")
+    if not -1 <= int(sep_id) < V:
+        raise ValueError(f"smiles_randomize: sep_id {sep_id} is outside the vocabulary of {V} tokens (-1: none)")
+    if not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f"smiles_randomize: p must be a probability in [0, 1], got {p}")
+    out_width = W if out_width is None else int(out_width)
+    if out_width < W:
+        raise ValueError(f"smiles_randomize: out_width {out_width} is narrower than the rows ({W} columns)")
+    if out is None:
+        tokens = torch.empty(n, out_width, dtype=torch.int64, device=ys.device)
+        info = torch.empty(n, 4, dtype=torch.int32, device=ys.device)
+        perm = torch.empty(n, out_width, dtype=torch.int32, device=ys.device) if return_perm else None
+    else:
+        tokens, info, perm = out
+        _chk(tokens, "smiles_randomize.out tokens", torch.int64), _chk(info, "smiles_randomize.out info", torch.int32)
+        wanted = [(tokens, (n, out_width)), (info, (n, 4))]
+        if perm is not None:
+            _chk(perm, "smiles_randomize.out perm", torch.int32)
+            wanted.append((perm, (n, out_width)))
+        for t, shape in wanted:
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"smiles_randomize: out must hold contiguous tensors {[w[1] for w in wanted]}, got "
+                                 f"{list(t.shape)}")
+    if n == 0:
+        return tokens, info, perm
+    check(_L().gct_smiles_randomize(_p(ys), max(W, ys.stride(0)), W, n, _p(start), _p(key), V, _p(table), _p(ring_ids),
+                                    int(n_rings), int(open_id), int(close_id), int(pad_id), int(eos_id), int(sep_id),
+                                    int(seed) & 0xFFFFFFFFFFFFFFFF, float(p), _p(tokens), _p(info), _p(perm), out_width,
+                                    _st()), "gct_smiles_randomize")
+    return tokens, info, perm
+
+
 def _seq_geometry(name, logits2d, ys, rows_per_seq, V, prefix_lens, prior2d=None):
     """The checks every seq_* wrapper makes on (ys, logits, prefix_lens), with seq_dist's prior logits next to the
     agent's: (n, W, R, V, ld, ld_prior).  `name` (the caller's) opens every message, here and in the helpers below."""

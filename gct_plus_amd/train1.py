@@ -12,7 +12,9 @@ environment and none touching the arithmetic:
     of gct_plus_amd.data (replaces torchtext Field pickles; vocabularies are built from the
     training split and stored as {util_folder}/SRC[_sep].json, TRG[_sep].json); `-synthetic N`
     trains on synthetic MOSES-shaped token batches instead (no dataset can be downloaded here).
-    SMILES randomisation (-randomize_prob, needs rdkit) is not available.
+    -randomize_prob P rewrites each training and validation SMILES with probability P as a random spelling of the same
+    molecule, on the device (gct_plus_amd.randomize, no rdkit); it needs SMILES, so it is an error with -synthetic and
+    with pre-tokenised tensors.
 """
 import argparse
 import logging
@@ -98,6 +100,8 @@ def main(rank, world_size, argv=None):
     parser = argparse.ArgumentParser()
     train_opts(parser)
     args = parser.parse_args(argv)
+    if args.randomize_prob > 0 and args.synthetic:
+        raise ValueError("-randomize_prob rewrites SMILES strings: -synthetic token batches are not SMILES")
     local = int(os.environ.get("LOCAL_RANK", rank))
     share_gpu = os.environ.get("GCT_DP_SHARE_GPU", "0") != "0"      # TEST RIG (one-GPU boxes): every rank on cuda:0,
     if share_gpu:                                                   # gradients through host memory over gloo
@@ -143,11 +147,17 @@ def main(rank, world_size, argv=None):
         LOG.info(f"TRG: {TRG.stoi}")
         mk = lambda fr, sh: data.SmilesLoader(fr, SRC, TRG, args.model_type, args.property_list,
                                               args.batch_size, rank, world_size, sh, args.seed, device,
-                                              args.use_scaffold)
+                                              args.use_scaffold, randomize_prob=args.randomize_prob)
         train_loader, valid_loader = mk(ftr, True), mk(fva, False)
         src_vocab, trg_vocab = len(SRC), len(TRG)
         args.sos_id, args.eos_id, args.pad_id = TRG.stoi["<sos>"], TRG.stoi["<eos>"], SRC.stoi["<pad>"]
+        if args.randomize_prob > 0:
+            LOG.info("SMILES randomisation: probability %g per molecule, on the device, keyed by item and epoch",
+                     args.randomize_prob)
     else:
+        if args.randomize_prob > 0:
+            raise ValueError("-randomize_prob rewrites SMILES strings: pre-tokenised tensors are not SMILES "
+                             f"({csv_tr} not found)")
         n_tr = 32 if (args.debug and args.synthetic) else args.synthetic
         n_va = 32 if (args.debug and args.synthetic) else (args.synthetic_valid or max(args.synthetic // 10, 0))
         train = load_tokens(args, "train", n_tr)

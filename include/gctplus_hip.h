@@ -885,6 +885,31 @@ int gct_grammar_mask(const float* logits, float* masked, int V, const int32_t* t
 int gct_smiles_check(const int64_t* ys, int64_t ld_ys, int W, int n, const int32_t* start, int V, const int32_t* table,
                      const int32_t* chem, int32_t* out, void* stream);
 
+/* SMILES randomisation (gct_plus_amd/randomize.py SmilesRandomizer states the rules: `randomize` for one part,
+ * randomize_reference for a batch): row r's span ys[r][start[r], W) written out again as a random depth-first spelling
+ * of the same molecular graph, one wave per row.  The content is what stands in front of the span's first <eos>; with
+ * sep_id >= 0 and a <sep> in it, the scaffold in front of the first <sep> (part 1) and the molecule behind it (part 0)
+ * are handled on their own.  A span without <eos>, W - start[r] > 256 or start[r] outside [0, W]: the row's W columns
+ * are copied, info = (SYNTAX, -1, span length or 0, 0).
+ * table: int32 [V], class | ring number << 8 (as the grammar's) | the order of a BOND token << 16 | unsupported << 20
+ * (a / or \ bond, an atom token with @).  ring_ids: int32 [64], the token ids of the n_rings <= 63 ring numbers the
+ * spelling may use, lowest first.  key: int64 [n], the row's stream; seed, p: by value, 0 <= p <= 1.
+ * out int64 [n][out_width], out_width >= W: columns [0, start) copied, the parts with <sep> between them, <eos>, <pad>.
+ * info int32 [n][4] = (status of the molecule, status of the scaffold or -1, new span length with <eos>, atoms).
+ * perm int32 [n][out_width] or NULL: the input atom index of the k-th output atom, -1 behind them.
+ * A part that is not randomised keeps its tokens; its status says why (OK: it was randomised).
+ * n = 0 is a no-op.  No global atomics, no scratch: the graph, the search stack and the new row live in LDS. */
+#define GCT_RAND_OK 0
+#define GCT_RAND_KEPT 1
+#define GCT_RAND_SYNTAX 2
+#define GCT_RAND_UNSUPPORTED 3
+#define GCT_RAND_NO_RING 4
+#define GCT_RAND_TOO_LONG 5
+int gct_smiles_randomize(const int64_t* ys, int64_t ld_ys, int W, int n, const int32_t* start, const int64_t* key, int V,
+                         const int32_t* table, const int32_t* ring_ids, int n_rings, int open_id, int close_id,
+                         int pad_id, int eos_id, int sep_id, uint64_t seed, float p, int64_t* out, int32_t* info,
+                         int32_t* perm, int out_width, void* stream);
+
 /* Per-step sampling statistics (gct_plus_amd/decode.py step_stats_reference states the rules).  Launched behind
  * gct_select_token in the step unit, on the same device counter and with gct_chosen_logp's row rule: row r looks at
  * column p = *pos - row_off[r] + 1, takes tok = ys[r][p] and writes each non-null table at out[dst][p].
