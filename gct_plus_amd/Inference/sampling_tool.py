@@ -67,6 +67,10 @@ same verdict for one string, usable as accept= of interpolate_smiles.
 same graph written out by a random depth-first traversal (randomize.SmilesRandomizer, one launch, no rdkit), for
 encode_smiles / score_smiles; the reference's randomize_smiles for callers.
 
+`molecule_keys(rows or smiles)` / `basic_metrics(rows, index)` (any sampler): a spelling-independent 64-bit key per
+molecule (molkey.SmilesKeys, one launch) and with it the reference's valid / unique / novel figures on the device --
+`first_occurrence`, `MolKeyIndex` and Train/finetune.uniqueness_reward work on the same keys.
+
 `decode_smc` (any sampler, any decode_algo): sequential Monte Carlo under the grammar (KVDecoder.generate_smc) -- k weighted
 well-formed molecules per latent whose weighted distribution converges to the model's own distribution restricted to
 well-formed strings, which a well_formed=True decode's locally renormalised draws do not follow, and an unbiased estimate
@@ -99,6 +103,7 @@ from ..decode import (BEAM_ALPHA, ChemReport, KVDecoder, Marginal, PolicyTerms, 
                       SmilesGrammar, check_beam_size, check_ess_threshold, check_grammar, check_particles,
                       check_sample_filter, check_stream_model, check_stream_rows, generated_tokens, marginal_logp,
                       score_tokens, sequence_logp, sequence_policy, sequence_ppo)
+from ..molkey import MolKeys, SmilesKeys, basic_metrics
 from ..randomize import SmilesRandomizer
 
 
@@ -245,6 +250,7 @@ class Sampling:
         self.kv = KVDecoder(model, self.pad_id, self.sos_id, self.eos_id)
         self._chemistry = None
         self._randomizer = None
+        self._keys = None
 
     # ---- chemical validity of decoded rows (decode.SmilesChemistry: a check behind the decode, not a constraint on it)
     @property
@@ -319,6 +325,47 @@ class Sampling:
                     spell.append(self.id_to_smi(ids))
             out.append(spell)
         return out, got.info[:, :2].cpu().view(n, k, 2)
+
+    # ---- molecule identity (molkey.SmilesKeys: uniqueness and novelty without moses or rdkit)
+    @property
+    def keys(self) -> SmilesKeys:
+        """The SmilesKeys over the target vocabulary, built on first use."""
+        if self._keys is None:
+            self._keys = SmilesKeys(self.TRG.itos, self.pad_id, self.eos_id, self.sep_id)
+        return self._keys
+
+    def molecule_keys(self, rows, scaffold_list=None) -> MolKeys:
+        """Spelling-independent 64-bit keys on the sampler's device, one launch: `rows` a DecodedRows or
+        (ys, prefix_lens) -- the span behind a row's prefix is keyed, as check_rows reads it -- or SMILES strings, with
+        scaffold_list as `scaffold <sep> molecule` rows whose two parts are keyed on their own.  MolKeys(key int64 [n, 2]
+        = (molecule, scaffold or 0), info int32 [n, 4] = (ops.KEY_* status of the molecule, of the scaffold or -1, atoms,
+        bonds)).  Equal keys: the same molecule as far as molkey's rule can tell; a part with a stereo mark, a dot or bad
+        syntax is the same only as the same string."""
+        if isinstance(rows, DecodedRows):
+            return self.keys.key_rows(rows.ys, rows.prefix_lens)
+        if isinstance(rows, tuple) and len(rows) == 2 and torch.is_tensor(rows[0]):
+            if scaffold_list is not None:
+                raise ValueError("molecule_keys: scaffold_list goes with strings; token rows hold their scaffold")
+            return self.keys.key_rows(*rows)
+        smiles_list = list(rows)
+        n = len(smiles_list)
+        ids = [self.smi_to_id(s, add_eos=True) for s in smiles_list]
+        if scaffold_list is not None:
+            if not self.add_sep:
+                raise ValueError("scaffold_list needs a scaffold model's vocabulary (no <sep> token here)")
+            scaffold_list = list(scaffold_list)
+            if len(scaffold_list) != n:
+                raise ValueError(f"{len(scaffold_list)} scaffolds for {n} molecules")
+            ids = [self.smi_to_id(c) + [self.sep_id] + r for c, r in zip(scaffold_list, ids)]
+        W = max((len(r) for r in ids), default=1)
+        ys = torch.tensor([r + [self.pad_id] * (W - len(r)) for r in ids], dtype=torch.int64).view(n, W)
+        return self.keys.key_rows(ys.to(self.device), torch.zeros(n, dtype=torch.int64))
+
+    def basic_metrics(self, rows, index=None) -> dict:
+        """valid / unique / novel of decoded rows (molkey.basic_metrics, moses' definitions): check_rows, molecule_keys
+        and the counting on the device, one read-back for the dict.  index: a molkey.MolKeyIndex of the training set
+        (without one there is no `novel`)."""
+        return basic_metrics(self.check_rows(rows), self.molecule_keys(rows), index)
 
     # ---- helpers with the reference's names ------------------------------------------------
     def init_y(self, n, add_sos=True, sca_ids=None, add_sep=False):

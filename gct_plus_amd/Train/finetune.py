@@ -54,6 +54,7 @@ import torch
 
 from .. import ops
 from ..decode import clip_pair
+from ..molkey import first_occurrence
 from ..optim import FusedAdam, check_max_grad_norm
 
 
@@ -140,6 +141,18 @@ def validity_reward(report, shaped=False, lengths=None):
                          f"{lengths.dtype} {list(lengths.shape)}")
     share = report.position.float() / lengths.reshape(-1).to(status.device, non_blocking=True).float()
     return torch.where(ok, torch.ones_like(share), share)
+
+
+def uniqueness_reward(keys, index=None, group=None):
+    """One reward per row from molecule keys (Sampling.molecule_keys: a MolKeys, or int64 [n]): fp32 [n] on the keys'
+    device, no graph and no synchronisation -- to multiply into validity_reward.  1 on the first row of the batch that
+    holds a key (per `group`, ints [n], when given: per scaffold or per condition), and with index (a molkey.MolKeyIndex
+    of the training set) only if the index does not hold the key; else 0.  A policy that writes one molecule in five
+    spellings is paid once."""
+    first = first_occurrence(keys, group)
+    if index is not None:
+        first = first & ~index.contains(keys)
+    return first.float()
 
 
 def _check_weight(weight, n, what):

@@ -1,0 +1,217 @@
+// Molecule identity keys on the device: gct_smiles_key against molkey.py SmilesKeys (key is the statement for one part,
+// key_reference the batch rule).  One wave per row, four rows per workgroup, in smiles_randomize_kernel's shape: lane l
+// stages tokens l + 64 t of the row's span -- the table word and the token's 64-bit label -- in the wave's own LDS and the
+// wave finds the first <eos> and the first <sep> in front of it; then, part by part (the scaffold, if any, first):
+//   lane 0 parses the part into bonds and per-atom bond lists (rand_parse of smiles_graph.h);
+//   lane l labels bonds l + 64 t and runs the breadth-first searches of atoms l + 64 t on its own: the visited and the
+//     frontier sets are four 64-bit words each in registers (a part has at most 255 atoms), every word addressed by a
+//     constant, and the bond lists are read from LDS, so no per-lane array is indexed at run time and nothing spills;
+//   GCT_KEY_ROUNDS rounds of refinement, one atom per lane and pass, the colours double-buffered in LDS;
+//   a butterfly over the wave in a fixed order sums the atoms' colours (the sums wrap, so any order gives the same bits;
+//     no atomics).
+// A part without a graph (SYNTAX, UNSUPPORTED) gets lane 0's sequential hash of its tokens' labels instead.
+// LDS: sizeof(KeyWave) = 13 072 bytes per wave (6 656 the parsed graph, 2 048 the labels, 4 096 the two colour buffers,
+// 256 the bond labels, 16 the part's header), 52 288 per workgroup of four rows.
+#include "smiles_graph.h"
+
+namespace {
+
+constexpr int kNone = 0x7fffffff;
+constexpr uint64_t kGold = 0x9E3779B97F4A7C15ull;            // molkey.py: GOLD, STRING_DOMAIN, UNKNOWN_DOMAIN
+constexpr uint64_t kStringDomain = 0xA0761D6478BD642Full;
+constexpr uint64_t kUnknownDomain = 0xE7037ED1A0B428DBull;
+
+struct KeyWave : SmilesGraph {                               // e[i] also carries, from bit 21: the key's bond label of a
+  uint64_t lab[256];                                         //  BOND token (3 bits) or `aromatic` of an ATOM token, and
+  uint64_t col[2][256];                                      //  (the token is <sep>) << 24
+  uint8_t blab[256];                                         // lab: token position -> label; col: atom -> colour;
+  int32_t res[4];                                            // blab: bond -> label; res: graph?, atoms, bonds
+};
+static_assert(sizeof(KeyWave) * 4 <= 64 * 1024, "four rows per workgroup must fit 64 KB of LDS");
+
+__host__ __device__ inline uint64_t key_mix(uint64_t x) {    // splitmix64's finaliser
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+
+// The label of a token the vocabulary does not hold (the part is SYNTAX: it only enters a string key).
+__host__ __device__ inline uint64_t key_unknown_label(int64_t tok) { return key_mix((uint64_t)tok ^ kUnknownDomain); }
+
+// The string key of the tokens at [lo, hi): order-dependent, under its own domain constant.
+__host__ __device__ inline uint64_t key_string(const KeyWave& w, int lo, int hi) {
+  uint64_t h = kStringDomain;
+  for (int i = lo; i < hi; ++i) h = key_mix((h + kGold) ^ w.lab[i]);
+  return key_mix(h + (uint64_t)(hi - lo));
+}
+
+// o(e): the written symbol's label, or without one 5 between two aromatic atom tokens and 1 otherwise.
+__host__ __device__ inline int key_bond_label(const KeyWave& w, int e) {
+  const int s = w.bsym[e];
+  if (s >= 0) return (w.e[s] >> 21) & 7;
+  return ((w.e[w.apos[w.ba[e]]] >> 21) & (w.e[w.apos[w.bb[e]]] >> 21) & 1) ? 5 : 1;
+}
+
+// c0(a): the distance profile of atom a, by a breadth-first search over the bond lists.
+__host__ __device__ inline uint64_t key_profile(const KeyWave& w, int a) {
+  uint64_t v0 = 0, v1 = 0, v2 = 0, v3 = 0, f0, f1, f2, f3, n0, n1, n2, n3, sum = 0, md = 0;
+  auto mark = [&](int v) {                                   // (v < 256: one of the four words takes the bit)
+    const uint64_t bit = 1ull << (v & 63);
+    const int q = v >> 6;
+    n0 |= q == 0 ? bit : 0, n1 |= q == 1 ? bit : 0, n2 |= q == 2 ? bit : 0, n3 |= q == 3 ? bit : 0;
+  };
+  auto level = [&](uint64_t f, int base) {
+    for (; f; f &= f - 1) {
+      const int b = base + __builtin_ctzll(f);               // (a bit is only ever set for an atom of the part)
+      sum += key_mix(w.lab[w.apos[b]] ^ md);
+      const int d = w.deg[b];
+      for (int i = 0; i < d; ++i) {
+        const int e = w.adj[b][i];
+        mark(w.ba[e] ^ w.bb[e] ^ b);
+      }
+    }
+  };
+  n0 = n1 = n2 = n3 = 0;
+  mark(a);
+  f0 = v0 = n0, f1 = v1 = n1, f2 = v2 = n2, f3 = v3 = n3;
+  for (int dist = 1; (f0 | f1 | f2 | f3) != 0; ++dist) {     // (every level takes at least one new atom: <= 255 levels)
+    md = key_mix((uint64_t)dist);
+    n0 = n1 = n2 = n3 = 0;
+    level(f0, 0), level(f1, 64), level(f2, 128), level(f3, 192);
+    f0 = n0 & ~v0, f1 = n1 & ~v1, f2 = n2 & ~v2, f3 = n3 & ~v3;
+    v0 |= f0, v1 |= f1, v2 |= f2, v3 |= f3;
+  }
+  return key_mix(w.lab[w.apos[a]] + sum);
+}
+
+// One round of bond-labelled refinement for atom a over the colours c.
+__host__ __device__ inline uint64_t key_refine(const KeyWave& w, const uint64_t* c, int a) {
+  uint64_t s = 3 * c[a];
+  const int d = w.deg[a];
+  for (int i = 0; i < d; ++i) {
+    const int e = w.adj[a][i];
+    s += key_mix(c[w.ba[e] ^ w.bb[e] ^ a] ^ key_mix((uint64_t)w.blab[e] + 0x100));
+  }
+  return key_mix(s);
+}
+
+__host__ __device__ inline uint64_t key_combine(uint64_t sum, int atoms, int bonds) {
+  return key_mix(sum + (uint64_t)atoms * kGold + (uint64_t)bonds);
+}
+
+__device__ __forceinline__ uint64_t key_wave_sum(uint64_t x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)x, o, 64);
+    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), o, 64);
+    x += (uint64_t)lo | ((uint64_t)hi << 32);
+  }
+  return x;
+}
+
+__global__ __launch_bounds__(256) void smiles_key_kernel(
+    const int64_t* __restrict__ ys, int64_t ld_ys, int W, int n, const int32_t* __restrict__ start, int V,
+    const int32_t* __restrict__ table, const int64_t* __restrict__ label, int eos_id, int sep_id,
+    int64_t* __restrict__ key_out, int32_t* __restrict__ info_out) {
+  __shared__ KeyWave sh[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int row = blockIdx.x * 4 + wave;
+  const bool live = row < n;
+  KeyWave& w = sh[wave];
+  const int t0 = live ? start[row] : W;
+  const bool in_range = live && t0 >= 0 && t0 <= W && W - t0 <= 256;
+  const int g = in_range ? W - t0 : 0;                       // 0 <= g <= 256 tokens in the span
+  const int64_t* yr = ys + (int64_t)row * ld_ys + (in_range ? t0 : 0);   // (read only under j < g)
+  int E = kNone, sep_at = 0;                                 // first <eos>; bit t: token lane + 64 t is <sep>
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int j = lane + 64 * t;
+    if (j < g) {
+      const int64_t tok = yr[j];
+      const bool known = tok >= 0 && tok < V;
+      int word = known ? table[tok] & 0xFFFFFF : GCT_GRAMMAR_BANNED;
+      if (tok == sep_id) word |= 1 << 24, sep_at |= 1 << t;  // (sep_id -1: none)
+      w.e[j] = word;
+      w.lab[j] = known ? (uint64_t)label[tok] : key_unknown_label(tok);
+      if (tok == eos_id) E = min(E, j);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) E = min(E, __shfl_xor(E, o, 64));
+  int S = kNone;                                             // first <sep> in front of the <eos>
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+    if (((sep_at >> t) & 1) && lane + 64 * t < E) S = min(S, lane + 64 * t);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) S = min(S, __shfl_xor(S, o, 64));
+  const bool row_bad = E == kNone;                           // (a dead wave and a row out of range: g = 0, no <eos>)
+  const bool two = S != kNone;
+  uint64_t k_mol = 0, k_sca = 0;                             // lane 0's
+  int st_mol = -1, st_sca = -1, atoms = 0, bonds = 0;
+
+  for (int it = 0; it < 2; ++it) {
+    const int which = 1 - it;                                // the scaffold (part 1) first, then the molecule (part 0)
+    const bool active = !row_bad && (which == 0 || two);
+    const int lo = which == 1 ? 0 : (two ? S + 1 : 0), hi = which == 1 ? S : E;
+    int status = GCT_KEY_STRING_SYNTAX;
+    __syncthreads();                                         // the staged row; the last part's lists are done with
+    if (lane == 0) {
+      int A = 0, nb = 0;
+      if (active) {
+        bool unsup;
+        const bool parsed = rand_parse(w, lo, hi, A, nb, unsup);
+        status = !parsed ? GCT_KEY_STRING_SYNTAX : unsup ? GCT_KEY_STRING_UNSUPPORTED : GCT_KEY_GRAPH;
+      }
+      w.res[0] = active && status == GCT_KEY_GRAPH, w.res[1] = A, w.res[2] = nb;
+    }
+    __syncthreads();
+    const bool graph = w.res[0] != 0;                        // (the same for the whole wave)
+    const int nA = w.res[1], nB = w.res[2];
+    if (graph) {
+      for (int e = lane; e < nB; e += 64) w.blab[e] = (uint8_t)key_bond_label(w, e);
+      for (int a = lane; a < nA; a += 64) w.col[0][a] = key_profile(w, a);
+    }
+    __syncthreads();
+    for (int r = 0; r < GCT_KEY_ROUNDS; ++r) {
+      if (graph)
+        for (int a = lane; a < nA; a += 64) w.col[(r + 1) & 1][a] = key_refine(w, w.col[r & 1], a);
+      __syncthreads();
+    }
+    uint64_t sum = 0;
+    if (graph)
+      for (int a = lane; a < nA; a += 64) sum += key_mix(w.col[GCT_KEY_ROUNDS & 1][a]);
+    sum = key_wave_sum(sum);
+    if (active && lane == 0) {
+      const uint64_t k = graph ? key_combine(sum, nA, nB) : key_string(w, lo, hi);
+      if (which == 1) {
+        k_sca = k, st_sca = status;
+      } else {
+        k_mol = k, st_mol = status, atoms = nA, bonds = nB;
+      }
+    }
+  }
+  if (live && lane == 0) {
+    key_out[(int64_t)row * 2] = (int64_t)k_mol, key_out[(int64_t)row * 2 + 1] = (int64_t)k_sca;
+    int32_t* o4 = info_out + (int64_t)row * 4;
+    o4[0] = st_mol, o4[1] = st_sca, o4[2] = atoms, o4[3] = bonds;
+  }
+}
+
+}  // namespace
+
+extern "C" int gct_smiles_key(const int64_t* ys, int64_t ld_ys, int W, int n, const int32_t* start, int V,
+                              const int32_t* table32, const int64_t* label64, int pad_id, int eos_id, int sep_id,
+                              int64_t* key_out, int32_t* info_out, void* stream) {
+  GCT_CHECK_ARG(ys && start && table32 && label64 && key_out && info_out && n >= 0 && V > 0, "smiles_key: bad args");
+  GCT_CHECK_ARG(W >= 0 && ld_ys >= W, "smiles_key: %d token columns in rows of %lld", W, (long long)ld_ys);
+  GCT_CHECK_ARG(pad_id >= 0 && pad_id < V && eos_id >= 0 && eos_id < V && sep_id >= -1 && sep_id < V,
+                "smiles_key: a token id outside the vocabulary of %d", V);
+  if (n == 0) return GCT_OK;
+  hipLaunchKernelGGL(smiles_key_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, ys, ld_ys, W, n,
+                     start, V, table32, label64, eos_id, sep_id, key_out, info_out);
+  GCT_LAUNCH_CHECK("smiles_key");
+  return GCT_OK;
+}

@@ -1,0 +1,128 @@
+// The labelled graph of one SMILES part as SmilesRandomizer.parse (randomize.py) reads it, stated once for the kernels
+// that work on it: gct_smiles_randomize (randomize.hip) and gct_smiles_key (molkey.hip).  SmilesGraph is the part of a
+// wave's LDS record that the parse fills -- each kernel's record derives from it and adds its own fields -- and
+// rand_parse / rand_link are plain C++ over it, host-callable so that a CPU harness can run them under a sanitizer.
+// An entry e[i] is the token's table word (class | ring number << 8 | bond order << 16 | unsupported << 20; a kernel may
+// keep bits of its own from bit 21 up, the parse does not look at them).
+#pragma once
+#include "common.h"
+
+namespace {
+
+enum { RP_START, RP_ATOM, RP_RING, RP_BOND_A, RP_BOND_B, RP_OPEN, RP_CLOSE, RP_DOT };
+constexpr int kMaxDeg = 8;                                   // randomize.MAX_DEGREE
+
+struct SmilesGraph {
+  int32_t e[256];                                            // table word | the kernel's own bits
+  uint32_t ring[GCT_GRAMMAR_MAX_RINGS];                      // open occurrence: atom | order << 8 | (symbol pos + 1) << 12
+  int16_t bsym[256];                                         // bond -> position of its BOND token, -1: none
+  int16_t par[256];                                          // atom -> chain parent (-1: none)
+  uint16_t apos[256], stk[256], stamp[256];                  // (stamp: smiles_check_kernel's "bonded already" rule)
+  uint8_t adj[256][kMaxDeg];                                 // atom -> its bonds, parse order
+  uint8_t ba[256], bb[256];                                  // bond -> its ends, ba < bb
+  uint8_t deg[256];                                          // per atom
+};
+
+__host__ __device__ inline void rand_link(SmilesGraph& w, int a, int b, int sym, int& nb, bool& unsup) {
+  if (w.deg[a] >= kMaxDeg || w.deg[b] >= kMaxDeg) {
+    unsup = true;
+    return;
+  }
+  const int e = nb++;                                        // (a link takes an ATOM or a closing RING token: nb <= 254)
+  w.ba[e] = (uint8_t)a, w.bb[e] = (uint8_t)b;
+  w.bsym[e] = (int16_t)sym;
+  w.adj[a][w.deg[a]++] = (uint8_t)e;
+  w.adj[b][w.deg[b]++] = (uint8_t)e;
+}
+
+// Lane 0: the part e[lo, hi) parsed as SmilesChemistry.check parses it.  Returns false for SYNTAX.
+__host__ __device__ inline bool rand_parse(SmilesGraph& w, int lo, int hi, int& atoms, int& bonds, bool& unsup) {
+  int prev = RP_START, depth = 0, cur = -1, pend = 0, pendpos = -1, A = 0, nb = 0, sp = 0;
+  uint64_t open = 0, here = 0;
+  unsup = false;
+  atoms = bonds = 0;
+  for (int i = lo; i < hi; ++i) {
+    const int ent = w.e[i], cls = ent & 0xFF;
+    const bool ar = prev == RP_ATOM || prev == RP_RING, arc = ar || prev == RP_CLOSE;
+    bool ok;
+    if ((ent >> 20) & 1) unsup = true;
+    switch (cls) {
+      case GCT_GRAMMAR_ATOM: {
+        ok = true;
+        prev = RP_ATOM;
+        here = 0;
+        const int a = A++;                                   // (A <= hi - lo <= 255)
+        w.apos[a] = (uint16_t)i;
+        w.deg[a] = 0;
+        w.par[a] = (int16_t)cur;
+        w.stamp[a] = 0;
+        if (cur >= 0) rand_link(w, cur, a, pendpos, nb, unsup);
+        cur = a;
+        pend = 0, pendpos = -1;
+        break;
+      }
+      case GCT_GRAMMAR_BOND:
+        ok = ar || prev == RP_OPEN || prev == RP_CLOSE;
+        prev = ar ? RP_BOND_A : RP_BOND_B;
+        pend = (ent >> 16) & 7, pendpos = i;
+        break;
+      case GCT_GRAMMAR_OPEN:
+        ok = arc;
+        prev = RP_OPEN;
+        ++depth;
+        if (ok) w.stk[sp++] = (uint16_t)cur;                 // (sp <= #OPEN tokens <= 255)
+        break;
+      case GCT_GRAMMAR_CLOSE:
+        ok = arc && depth > 0;
+        prev = RP_CLOSE;
+        --depth;
+        if (ok) cur = w.stk[--sp];
+        pend = 0, pendpos = -1;
+        break;
+      case GCT_GRAMMAR_RING: {
+        ok = ar || prev == RP_BOND_A;
+        const int r = (ent >> 8) & 63;
+        const uint64_t bit = 1ull << r;
+        if (ok && (open & bit)) {
+          if (here & bit) {
+            ok = false;                                      // a ring does not close on the atom that opened it
+          } else {
+            open ^= bit;
+            const uint32_t rec = w.ring[r];
+            const int a = (int)(rec & 0xFFu), o = (int)((rec >> 8) & 7u), osym = (int)(rec >> 12) - 1;
+            if ((o && pend && o != pend) || w.par[cur] == a || w.stamp[a] == cur + 1) {
+              unsup = true;                                  // `check` reports RING_BOND
+            } else {
+              rand_link(w, a, cur, pendpos >= 0 ? pendpos : osym, nb, unsup);
+              w.stamp[a] = (uint16_t)(cur + 1);
+            }
+          }
+        } else if (ok) {
+          open |= bit;
+          here |= bit;
+          w.ring[r] = (uint32_t)cur | ((uint32_t)pend << 8) | ((uint32_t)(pendpos + 1) << 12);
+        }
+        prev = RP_RING;
+        pend = 0, pendpos = -1;
+        break;
+      }
+      case GCT_GRAMMAR_DOT:
+        ok = arc && depth == 0;
+        prev = RP_DOT;
+        unsup = true;
+        cur = -1;
+        pend = 0, pendpos = -1;
+        break;
+      default:                                               // <eos> cannot be here; <pad>, <sep> and banned tokens
+        ok = false;
+        break;
+    }
+    if (!ok) return false;
+  }
+  const bool arc = prev == RP_ATOM || prev == RP_RING || prev == RP_CLOSE;
+  if (!(arc && depth == 0 && open == 0)) return false;       // the <eos> behind the part
+  atoms = A, bonds = nb;
+  return true;
+}
+
+}  // namespace

@@ -1506,6 +1506,51 @@ def smiles_randomize(ys, start, key, table, ring_ids, n_rings, open_id, close_id
     return tokens, info, perm
 
 
+# status codes of the molecule keys (GCT_KEY_* of include/gctplus_hip.h) and the rounds of refinement, GCT_KEY_ROUNDS
+KEY_GRAPH, KEY_STRING_SYNTAX, KEY_STRING_UNSUPPORTED = range(3)
+KEY_ROUNDS = 3
+KEY_MAX_SPAN = 256
+
+
+def smiles_key(ys, start, table32, label64, pad_id, eos_id, sep_id, out=None):
+    """gct_smiles_key: a spelling-independent 64-bit key of the molecule in every row's span ys[r, start[r]:], and of the
+    scaffold in front of a <sep> (molkey.SmilesKeys.key_reference is the statement).  ys int64 [n, W] with unit column
+    stride, start int32 [n] on the device, table32 int32 [V] and label64 int64 [V] (SmilesKeys.device_tables), sep_id -1
+    for none.  Returns (key int64 [n, 2], info int32 [n, 4]), freshly allocated or the contiguous tensors of
+    out = (key, info).  One launch."""
+    _chk(ys, "smiles_key.ys", torch.int64), _chk(start, "smiles_key.start", torch.int32)
+    _chk(table32, "smiles_key.table32", torch.int32), _chk(label64, "smiles_key.label64", torch.int64)
+    if ys.dim() != 2 or ys.shape[1] < 1 or (ys.shape[1] > 1 and ys.stride(1) != 1):
+        raise ValueError("smiles_key: ys [n, W >= 1] with unit column stride")
+    n, W = ys.shape
+    if start.dim() != 1 or start.numel() != n or not start.is_contiguous():
+        raise ValueError(f"smiles_key: start must be a contiguous tensor [{n}], got {list(start.shape)}")
+    if (table32.dim() != 1 or table32.numel() < 1 or label64.shape != table32.shape or not table32.is_contiguous() or
+            not label64.is_contiguous()):
+        raise ValueError("smiles_key: table32 int32 [V] and label64 int64 [V], contiguous")
+    V = table32.numel()
+    for name, v in (("pad_id", pad_id), ("eos_id", eos_id)):
+        if not 0 <= int(v) < V:
+            raise ValueError(f"smiles_key: {name} {v} is outside the vocabulary of {V} tokens")
+    if not -1 <= int(sep_id) < V:
+        raise ValueError(f"smiles_key: sep_id {sep_id} is outside the vocabulary of {V} tokens (-1: none)")
+    if out is None:
+        key = torch.empty(n, 2, dtype=torch.int64, device=ys.device)
+        info = torch.empty(n, 4, dtype=torch.int32, device=ys.device)
+    else:
+        key, info = out
+        _chk(key, "smiles_key.out key", torch.int64), _chk(info, "smiles_key.out info", torch.int32)
+        for t, shape in ((key, (n, 2)), (info, (n, 4))):
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"smiles_key: out must hold contiguous tensors [{n}, 2] and [{n}, 4], got "
+                                 f"{list(t.shape)}")
+    if n == 0:
+        return key, info
+    check(_L().gct_smiles_key(_p(ys), max(W, ys.stride(0)), W, n, _p(start), V, _p(table32), _p(label64), int(pad_id),
+                              int(eos_id), int(sep_id), _p(key), _p(info), _st()), "gct_smiles_key")
+    return key, info
+
+
 def _seq_geometry(name, logits2d, ys, rows_per_seq, V, prefix_lens, prior2d=None):
     """The checks every seq_* wrapper makes on (ys, logits, prefix_lens), with seq_dist's prior logits next to the
     agent's: (n, W, R, V, ld, ld_prior).  `name` (the caller's) opens every message, here and in the helpers below."""

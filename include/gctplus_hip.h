@@ -910,6 +910,25 @@ int gct_smiles_randomize(const int64_t* ys, int64_t ld_ys, int W, int n, const i
                          int pad_id, int eos_id, int sep_id, uint64_t seed, float p, int64_t* out, int32_t* info,
                          int32_t* perm, int out_width, void* stream);
 
+/* Molecule identity keys (gct_plus_amd/molkey.py SmilesKeys states the rules: `key` for one part, key_reference for a
+ * batch): a spelling-independent 64-bit key of the labelled graph that gct_smiles_randomize's parse reads from row r's
+ * span ys[r][start[r], W), one wave per row.  Spans, <eos>, <sep> and the two parts: as in gct_smiles_randomize.
+ * table32: int32 [V], gct_smiles_randomize's word | from bit 21 the key's label of a BOND token (- 1, = 2, # 3, $ 4,
+ * : 5, ~ 6) or `aromatic` of an ATOM token.  label64: int64 [V], the FNV-1a hash of every token's string.
+ * A part with a graph (status GRAPH): per atom a distance profile over its breadth-first search, GCT_KEY_ROUNDS rounds
+ * of bond-labelled refinement, a wrapping sum over the atoms.  A part without one -- it does not parse (STRING_SYNTAX) or
+ * the randomiser would report UNSUPPORTED (STRING_UNSUPPORTED) -- gets an order-dependent hash of its tokens' labels.
+ * key_out int64 [n][2] = (the molecule's key, the scaffold's or 0); info_out int32 [n][4] = (status of the molecule,
+ * status of the scaffold or -1, atoms, bonds of the molecule part).  A span without <eos>, W - start[r] > 256 or
+ * start[r] outside [0, W]: keys 0, info (-1, -1, 0, 0).  n = 0 is a no-op.  No global atomics, no scratch. */
+#define GCT_KEY_GRAPH 0
+#define GCT_KEY_STRING_SYNTAX 1
+#define GCT_KEY_STRING_UNSUPPORTED 2
+#define GCT_KEY_ROUNDS 3
+int gct_smiles_key(const int64_t* ys, int64_t ld_ys, int W, int n, const int32_t* start, int V, const int32_t* table32,
+                   const int64_t* label64, int pad_id, int eos_id, int sep_id, int64_t* key_out, int32_t* info_out,
+                   void* stream);
+
 /* Per-step sampling statistics (gct_plus_amd/decode.py step_stats_reference states the rules).  Launched behind
  * gct_select_token in the step unit, on the same device counter and with gct_chosen_logp's row rule: row r looks at
  * column p = *pos - row_off[r] + 1, takes tok = ys[r][p] and writes each non-null table at out[dst][p].

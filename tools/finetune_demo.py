@@ -20,6 +20,10 @@ Train/finetune.validity_reward of Sampling.check_rows -- decode.SmilesChemistry'
 one launch on the device instead of the Python loop over the rows; the printed rate is then the VALID share.  The default,
 --reward grammar, is the run described above and prints what it always did.
 
+--report-unique: one more line at the end: the DISTINCT MOLECULES of the evaluation batch before and after, beside the
+distinct strings -- Sampling.molecule_keys and molkey.first_occurrence, on the device: a policy that writes one molecule
+in five spellings counts once.
+
 --time-step: no sampling; --n fixed rows of MOSES-like lengths (clip(round(N(35, 8)), 15, 78) tokens + <eos> behind a
 scaffold prefix), --rounds reinforce_steps on them after two warm-up steps: the figure to put next to a bench.py
 training step of the same batch size (recorded in DESIGN 4, not gated).  With --ppo-epochs it times ONE epoch:
@@ -52,6 +56,8 @@ ap.add_argument("--reward", choices=("grammar", "chemistry"), default="grammar",
                 help="grammar: 1 for a well-formed string; chemistry: constrained decoding, 1 for a chemically valid one")
 ap.add_argument("--report-valid", action="store_true",
                 help="one more line at the end: the chemically valid share of the evaluation batch before and after")
+ap.add_argument("--report-unique", action="store_true",
+                help="one more line at the end: distinct molecules (molecule keys) beside the distinct strings")
 ap.add_argument("--time-step", action="store_true",
                 help="time reinforce_step (one ppo_update epoch with --ppo-epochs) on fixed rows of MOSES-like lengths")
 a = ap.parse_args()
@@ -63,6 +69,7 @@ from gct_plus_amd import data, synthetic  # noqa: E402
 from gct_plus_amd.decode import SmilesGrammar  # noqa: E402
 from gct_plus_amd.Inference.sampling_tool import DecodedRows, PscavaetfSampling  # noqa: E402
 from gct_plus_amd.Model import model_dict  # noqa: E402
+from gct_plus_amd.molkey import first_occurrence  # noqa: E402
 from gct_plus_amd.optim import FusedAdam  # noqa: E402
 from gct_plus_amd.Train.finetune import frozen_prior, ppo_update, reinforce_step, validity_reward  # noqa: E402
 
@@ -172,11 +179,15 @@ def evaluate():
         terms = sampler.policy_terms(*rows)
     if a.report_valid:
         VALID_SHARE.append(float(validity_reward(sampler.check_rows(rows)).mean()))
+    if a.report_unique:
+        mk = sampler.molecule_keys(rows)
+        MOLECULES.append(int(first_occurrence(mk, valid=mk.info[:, 0] >= 0).sum()))
     return float(reward.mean()), distinct, float(terms.entropy.sum() / terms.tokens.sum())
 
 
 EVAL_SEED = 10 ** 6
 VALID_SHARE = []
+MOLECULES = []
 before = evaluate()
 reg = f", entropy_coef {a.entropy_coef}, kl_coef {a.kl_coef}" if a.entropy_coef or a.kl_coef else ""
 if a.ppo_epochs:
@@ -213,3 +224,7 @@ print(f"evaluation batch of {a.n}: {WHAT} {before[0]:.3f} -> {after[0]:.3f}, dis
 if a.report_valid:
     print(f"chemically valid share of the evaluation batch (decode.SmilesChemistry): {VALID_SHARE[0]:.3f} -> "
           f"{VALID_SHARE[1]:.3f}")
+if a.report_unique:
+    print(f"distinct molecules of the evaluation batch (molkey.SmilesKeys; a row without a graph counts as its string, one without "
+          f"<eos> not at all): "
+          f"{MOLECULES[0]} -> {MOLECULES[1]}, beside distinct strings {before[1]} -> {after[1]}")
