@@ -71,6 +71,11 @@ encode_smiles / score_smiles; the reference's randomize_smiles for callers.
 molecule (molkey.SmilesKeys, one launch) and with it the reference's valid / unique / novel figures on the device --
 `first_occurrence`, `MolKeyIndex` and Train/finetune.uniqueness_reward work on the same keys.
 
+`murcko_scaffolds(rows or smiles)` (any sampler) / `scaffold_report(rows)` (a scaffold model): the Murcko scaffold of
+every molecule -- key, spelling and kept atoms (scaffold.SmilesScaffolds, one launch, no rdkit) -- and, for rows that read
+<sos> scaffold <sep> molecule <eos>, whether the molecule has the scaffold it was given: molkey.scaffold_metrics'
+same_scaffold and Train/finetune.scaffold_reward read that report.
+
 `decode_smc` (any sampler, any decode_algo): sequential Monte Carlo under the grammar (KVDecoder.generate_smc) -- k weighted
 well-formed molecules per latent whose weighted distribution converges to the model's own distribution restricted to
 well-formed strings, which a well_formed=True decode's locally renormalised draws do not follow, and an unbiased estimate
@@ -104,6 +109,7 @@ from ..decode import (BEAM_ALPHA, ChemReport, KVDecoder, Marginal, PolicyTerms, 
                       check_sample_filter, check_stream_model, check_stream_rows, generated_tokens, marginal_logp,
                       score_tokens, sequence_logp, sequence_policy, sequence_ppo)
 from ..molkey import MolKeys, SmilesKeys, basic_metrics
+from ..scaffold import ScaffoldRows, SmilesScaffolds
 from ..randomize import SmilesRandomizer
 
 
@@ -251,6 +257,7 @@ class Sampling:
         self._chemistry = None
         self._randomizer = None
         self._keys = None
+        self._scaffolds = None
 
     # ---- chemical validity of decoded rows (decode.SmilesChemistry: a check behind the decode, not a constraint on it)
     @property
@@ -366,6 +373,42 @@ class Sampling:
         and the counting on the device, one read-back for the dict.  index: a molkey.MolKeyIndex of the training set
         (without one there is no `novel`)."""
         return basic_metrics(self.check_rows(rows), self.molecule_keys(rows), index)
+
+    # ---- Murcko scaffolds (scaffold.SmilesScaffolds: the reference's murcko_scaffold and scaffold filter, no rdkit)
+    @property
+    def scaffolds(self) -> SmilesScaffolds:
+        """The SmilesScaffolds over the target vocabulary, built on first use."""
+        if self._scaffolds is None:
+            self._scaffolds = SmilesScaffolds(self.TRG.itos, self.pad_id, self.eos_id, self.sep_id)
+        return self._scaffolds
+
+    def murcko_scaffolds(self, rows):
+        """The Murcko scaffold of every molecule on the sampler's device, one launch: `rows` a DecodedRows or
+        (ys, prefix_lens) -- the span behind a row's prefix holds the molecule, as check_rows reads it -- or SMILES
+        strings.  Returns (strings, ScaffoldRows): strings[i] the scaffold's spelling, "" for a row without one
+        (info[i, 0] says why: ops.SCA_ACYCLIC, SCA_SYNTAX, SCA_UNSUPPORTED, ...).  One read-back, for the strings."""
+        if isinstance(rows, DecodedRows):
+            got = self.scaffolds.scaffold_rows(rows.ys, rows.prefix_lens)
+        elif isinstance(rows, tuple) and len(rows) == 2 and torch.is_tensor(rows[0]):
+            got = self.scaffolds.scaffold_rows(*rows)
+        else:
+            ids = [self.smi_to_id(s, add_eos=True) for s in rows]
+            n, W = len(ids), max((len(r) for r in ids), default=1)
+            ys = torch.tensor([r + [self.pad_id] * (W - len(r)) for r in ids], dtype=torch.int64).view(n, W)
+            got = self.scaffolds.scaffold_rows(ys.to(self.device), torch.zeros(n, dtype=torch.int64),
+                                               out_width=max(W, min(W + 32, 256)))
+        return [self.id_to_smi(r) for r in got.tokens.cpu().tolist()], got
+
+    def scaffold_report(self, rows) -> ScaffoldRows:
+        """Does every decoded molecule have the scaffold it was asked for?  `rows`: a DecodedRows of a scaffold model, or
+        (ys, prefix_lens), whose rows read <sos> scaffold <sep> molecule <eos> (mixed-scaffold batches are not
+        left-padded: every row begins with <sos>, see the module notes).  One launch on the span behind <sos>, so that
+        the kernel sees both parts: key[:, 0] is the key of the scaffold EXTRACTED from the molecule, key[:, 1] the key of
+        the one given; scaffold.scaffold_match, molkey.scaffold_metrics and finetune.scaffold_reward read the result."""
+        if not self.add_sep:
+            raise ValueError("scaffold_report needs a scaffold model's vocabulary (no <sep> token here)")
+        ys = rows.ys if isinstance(rows, DecodedRows) else rows[0]
+        return self.scaffolds.scaffold_rows(ys, torch.ones(ys.shape[0], dtype=torch.int64))
 
     # ---- helpers with the reference's names ------------------------------------------------
     def init_y(self, n, add_sos=True, sca_ids=None, add_sep=False):

@@ -155,6 +155,15 @@ def uniqueness_reward(keys, index=None, group=None):
     return first.float()
 
 
+def scaffold_reward(sca):
+    """One reward per row from a scaffold.ScaffoldRows of `scaffold <sep> molecule` rows (Sampling.scaffold_report): fp32
+    [n] on the rows' device, no graph and no synchronisation -- to multiply into validity_reward.  1 where the molecule
+    has the scaffold it was given (scaffold.scaffold_match: a scaffold was extracted, the given part has a graph, and
+    the two keys are equal), else 0: a row without a given scaffold is never paid."""
+    from ..scaffold import scaffold_match
+    return scaffold_match(sca).float()
+
+
 def _check_weight(weight, n, what):
     """weight [n] of reinforce_step / ppo_update as an fp32 vector without a graph; ValueError for another length or a
     value that is negative or not finite."""

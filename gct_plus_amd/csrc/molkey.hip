@@ -12,14 +12,12 @@
 // A part without a graph (SYNTAX, UNSUPPORTED) gets lane 0's sequential hash of its tokens' labels instead.
 // LDS: sizeof(KeyWave) = 13 072 bytes per wave (6 656 the parsed graph, 2 048 the labels, 4 096 the two colour buffers,
 // 256 the bond labels, 16 the part's header), 52 288 per workgroup of four rows.
-#include "smiles_graph.h"
+// The per-atom functions (key_profile, key_refine, ...) are smiles_key.h's, shared with gct_smiles_scaffold.
+#include "smiles_key.h"
 
 namespace {
 
 constexpr int kNone = 0x7fffffff;
-constexpr uint64_t kGold = 0x9E3779B97F4A7C15ull;            // molkey.py: GOLD, STRING_DOMAIN, UNKNOWN_DOMAIN
-constexpr uint64_t kStringDomain = 0xA0761D6478BD642Full;
-constexpr uint64_t kUnknownDomain = 0xE7037ED1A0B428DBull;
 
 struct KeyWave : SmilesGraph {                               // e[i] also carries, from bit 21: the key's bond label of a
   uint64_t lab[256];                                         //  BOND token (3 bits) or `aromatic` of an ATOM token, and
@@ -28,89 +26,6 @@ struct KeyWave : SmilesGraph {                               // e[i] also carrie
   int32_t res[4];                                            // blab: bond -> label; res: graph?, atoms, bonds
 };
 static_assert(sizeof(KeyWave) * 4 <= 64 * 1024, "four rows per workgroup must fit 64 KB of LDS");
-
-__host__ __device__ inline uint64_t key_mix(uint64_t x) {    // splitmix64's finaliser
-  x ^= x >> 30;
-  x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27;
-  x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-
-// The label of a token the vocabulary does not hold (the part is SYNTAX: it only enters a string key).
-__host__ __device__ inline uint64_t key_unknown_label(int64_t tok) { return key_mix((uint64_t)tok ^ kUnknownDomain); }
-
-// The string key of the tokens at [lo, hi): order-dependent, under its own domain constant.
-__host__ __device__ inline uint64_t key_string(const KeyWave& w, int lo, int hi) {
-  uint64_t h = kStringDomain;
-  for (int i = lo; i < hi; ++i) h = key_mix((h + kGold) ^ w.lab[i]);
-  return key_mix(h + (uint64_t)(hi - lo));
-}
-
-// o(e): the written symbol's label, or without one 5 between two aromatic atom tokens and 1 otherwise.
-__host__ __device__ inline int key_bond_label(const KeyWave& w, int e) {
-  const int s = w.bsym[e];
-  if (s >= 0) return (w.e[s] >> 21) & 7;
-  return ((w.e[w.apos[w.ba[e]]] >> 21) & (w.e[w.apos[w.bb[e]]] >> 21) & 1) ? 5 : 1;
-}
-
-// c0(a): the distance profile of atom a, by a breadth-first search over the bond lists.
-__host__ __device__ inline uint64_t key_profile(const KeyWave& w, int a) {
-  uint64_t v0 = 0, v1 = 0, v2 = 0, v3 = 0, f0, f1, f2, f3, n0, n1, n2, n3, sum = 0, md = 0;
-  auto mark = [&](int v) {                                   // (v < 256: one of the four words takes the bit)
-    const uint64_t bit = 1ull << (v & 63);
-    const int q = v >> 6;
-    n0 |= q == 0 ? bit : 0, n1 |= q == 1 ? bit : 0, n2 |= q == 2 ? bit : 0, n3 |= q == 3 ? bit : 0;
-  };
-  auto level = [&](uint64_t f, int base) {
-    for (; f; f &= f - 1) {
-      const int b = base + __builtin_ctzll(f);               // (a bit is only ever set for an atom of the part)
-      sum += key_mix(w.lab[w.apos[b]] ^ md);
-      const int d = w.deg[b];
-      for (int i = 0; i < d; ++i) {
-        const int e = w.adj[b][i];
-        mark(w.ba[e] ^ w.bb[e] ^ b);
-      }
-    }
-  };
-  n0 = n1 = n2 = n3 = 0;
-  mark(a);
-  f0 = v0 = n0, f1 = v1 = n1, f2 = v2 = n2, f3 = v3 = n3;
-  for (int dist = 1; (f0 | f1 | f2 | f3) != 0; ++dist) {     // (every level takes at least one new atom: <= 255 levels)
-    md = key_mix((uint64_t)dist);
-    n0 = n1 = n2 = n3 = 0;
-    level(f0, 0), level(f1, 64), level(f2, 128), level(f3, 192);
-    f0 = n0 & ~v0, f1 = n1 & ~v1, f2 = n2 & ~v2, f3 = n3 & ~v3;
-    v0 |= f0, v1 |= f1, v2 |= f2, v3 |= f3;
-  }
-  return key_mix(w.lab[w.apos[a]] + sum);
-}
-
-// One round of bond-labelled refinement for atom a over the colours c.
-__host__ __device__ inline uint64_t key_refine(const KeyWave& w, const uint64_t* c, int a) {
-  uint64_t s = 3 * c[a];
-  const int d = w.deg[a];
-  for (int i = 0; i < d; ++i) {
-    const int e = w.adj[a][i];
-    s += key_mix(c[w.ba[e] ^ w.bb[e] ^ a] ^ key_mix((uint64_t)w.blab[e] + 0x100));
-  }
-  return key_mix(s);
-}
-
-__host__ __device__ inline uint64_t key_combine(uint64_t sum, int atoms, int bonds) {
-  return key_mix(sum + (uint64_t)atoms * kGold + (uint64_t)bonds);
-}
-
-__device__ __forceinline__ uint64_t key_wave_sum(uint64_t x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)x, o, 64);
-    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), o, 64);
-    x += (uint64_t)lo | ((uint64_t)hi << 32);
-  }
-  return x;
-}
 
 __global__ __launch_bounds__(256) void smiles_key_kernel(
     const int64_t* __restrict__ ys, int64_t ld_ys, int W, int n, const int32_t* __restrict__ start, int V,

@@ -9,7 +9,8 @@
 // before; what they leave is indexed dynamically in LDS, never in registers, so nothing spills.  No global atomics.
 // An entry of the LDS row is a literal token id (>= 0: ring numbers, parentheses, <sep>, <eos>) or -(j + 1): the token
 // at position j of the input span (atoms and bond symbols are carried verbatim, whatever their ids).
-#include "smiles_graph.h"
+// rand_walk is smiles_walk.h's, shared with gct_smiles_scaffold.
+#include "smiles_walk.h"
 
 namespace {
 
@@ -22,93 +23,6 @@ struct RandWave : SmilesGraph {                              // (smiles_graph.h:
   uint8_t perm[256];
   int32_t res[4];                                            // randomise this part, its atoms, its bonds
 };
-
-// Lane 0: passes 1 and 2 of the statement for a part of A atoms rooted at `root`, into w.out[opos, opos + room) and
-// w.perm[abase, abase + A).  Returns the length of the new spelling (it may exceed room: nothing is written past it),
-// or -1 when no ring number was free.
-__host__ __device__ int rand_walk(RandWave& w, int A, int root, int opos, int room, int abase,
-                                  const int32_t* __restrict__ ring_ids, int n_rings, int open_id, int close_id) {
-  // pass 1 (seen / left / role were cleared by the lanes)
-  int sp = 0;
-  w.seen[root] = 1;
-  w.pbond[root] = 0xFF;
-  w.stk[sp++] = (uint16_t)root;                              // atom | next list index << 8; sp <= A <= 255
-  while (sp > 0) {
-    const int f = w.stk[sp - 1], u = f & 0xFF, i = f >> 8;
-    if (i == w.deg[u]) {
-      --sp;
-      continue;
-    }
-    w.stk[sp - 1] = (uint16_t)(u | ((i + 1) << 8));
-    const int e = w.adj[u][i];
-    if (e == w.pbond[u] || w.role[e] != 0) continue;
-    const int v = w.ba[e] ^ w.bb[e] ^ u;
-    if (w.seen[v]) {
-      w.role[e] = v == w.ba[e] ? 2 : 3;                      // v is an ancestor: the opening end
-    } else {
-      w.seen[v] = 1;
-      w.pbond[v] = (uint8_t)e;
-      w.role[e] = 1;
-      ++w.left[u];
-      w.stk[sp++] = (uint16_t)v;
-    }
-  }
-  // pass 2
-  uint64_t free_ = (1ull << n_rings) - 1;                    // (n_rings <= 63) bit k: ring_ids[k] is free
-  int k = 0, pk = 0;
-  bool no_ring = false;
-  auto emit = [&](int v) {
-    if (k < room) w.out[opos + k] = v;
-    ++k;
-  };
-  auto emit_atom = [&](int u) {
-    emit(-((int)w.apos[u] + 1));
-    w.perm[abase + pk++] = (uint8_t)(abase + u);             // (every atom is emitted once: pk <= A)
-    uint64_t closed = 0;
-    const int d = w.deg[u];
-    for (int i = 0; i < d; ++i) {
-      const int e = w.adj[u][i], r = w.role[e];
-      if (r < 2) continue;
-      if ((r == 2 ? w.ba[e] : w.bb[e]) == u) {
-        if (w.bsym[e] >= 0) emit(-((int)w.bsym[e] + 1));
-        if (!free_) {
-          no_ring = true;
-          return;
-        }
-        const int idx = __builtin_ctzll(free_);
-        free_ &= free_ - 1;
-        w.rnum[e] = (uint8_t)idx;
-        emit(ring_ids[idx]);
-      } else {
-        const int idx = w.rnum[e];
-        emit(ring_ids[idx]);
-        closed |= 1ull << idx;
-      }
-    }
-    free_ |= closed;                                         // free again from the next atom on
-  };
-  emit_atom(root);
-  sp = 0;
-  w.stk[sp++] = (uint16_t)root;                              // atom | next list index << 8 | inside parentheses << 12
-  while (sp > 0 && !no_ring) {
-    const int f = w.stk[sp - 1], u = f & 0xFF, paren = (f >> 12) & 1, d = w.deg[u];
-    int i = (f >> 8) & 15;
-    while (i < d && !(w.role[w.adj[u][i]] == 1 && w.adj[u][i] != w.pbond[u])) ++i;
-    if (i == d) {
-      --sp;
-      if (paren) emit(close_id);
-      continue;
-    }
-    const int e = w.adj[u][i], v = w.ba[e] ^ w.bb[e] ^ u;
-    w.stk[sp - 1] = (uint16_t)(u | ((i + 1) << 8) | (paren << 12));
-    const int branch = --w.left[u] > 0;
-    if (branch) emit(open_id);
-    if (w.bsym[e] >= 0) emit(-((int)w.bsym[e] + 1));
-    emit_atom(v);
-    w.stk[sp++] = (uint16_t)(v | (branch << 12));
-  }
-  return no_ring ? -1 : k;
-}
 
 __global__ __launch_bounds__(256) void smiles_randomize_kernel(
     const int64_t* __restrict__ ys, int64_t ld_ys, int W, int n, const int32_t* __restrict__ start,

@@ -1,5 +1,6 @@
 // The labelled graph of one SMILES part as SmilesRandomizer.parse (randomize.py) reads it, stated once for the kernels
-// that work on it: gct_smiles_randomize (randomize.hip) and gct_smiles_key (molkey.hip).  SmilesGraph is the part of a
+// that work on it: gct_smiles_randomize (randomize.hip), gct_smiles_key (molkey.hip) and gct_smiles_scaffold
+// (scaffold.hip; smiles_key.h and smiles_walk.h hold what those share beyond the parse).  SmilesGraph is the part of a
 // wave's LDS record that the parse fills -- each kernel's record derives from it and adds its own fields -- and
 // rand_parse / rand_link are plain C++ over it, host-callable so that a CPU harness can run them under a sanitizer.
 // An entry e[i] is the token's table word (class | ring number << 8 | bond order << 16 | unsupported << 20; a kernel may

@@ -1,7 +1,8 @@
 """Molecule identity keys (what the reference's Inference/metrics.py get_basic_metrics takes from moses and rdkit for
 `unique` and `novel`, without either): a spelling-independent 64-bit key of the labelled graph that
 randomize.SmilesRandomizer.parse reads from a token row, and what a batch of such keys is for -- a per-row "first of its
-kind" mask, a sorted index of training-set keys, and the valid / unique / novel figures.
+kind" mask, a sorted index of training-set keys, the valid / unique / novel figures and, over the keys of scaffold.py's
+Murcko scaffolds, scaffold fidelity (scaffold_metrics).
 
 SmilesKeys.key is THE statement for one part, key_reference the batch rule; gct_smiles_key (csrc/molkey.hip,
 SmilesKeys.key_rows) implements them and is compared with them bit for bit.
@@ -372,4 +373,33 @@ def basic_metrics(report: ChemReport, keys, index=None):
     out.update(n=n, n_valid=n_valid, n_unique=n_unique)
     if index is not None:
         out["n_novel"] = counts[2]
+    return out
+
+
+def scaffold_metrics(report: ChemReport, sca, keys=None):
+    """Scaffold fidelity of decoded `scaffold <sep> molecule` rows (what the reference's Plot/sampled_molecules.py reads
+    off `df.scaffold == scaffold`): report a ChemReport, sca a scaffold.ScaffoldRows of the same rows
+    (Sampling.scaffold_report).  same_scaffold = the valid rows whose molecule has the scaffold it was given
+    (scaffold.scaffold_match) / valid rows; n_scaffolds = distinct extracted scaffold keys among the valid rows that have
+    a scaffold; with keys (the rows' molecule keys) unique_on_scaffold = distinct (extracted scaffold, molecule) pairs
+    among the valid rows / valid rows.  0 for an empty denominator.  Also n, n_valid, n_same.  Everything is computed on
+    the rows' device; one read-back."""
+    from .scaffold import scaffold_match
+    k = sca.key[:, 0]
+    ok = (report.status == ops.CHEM_OK).to(k.device)
+    if ok.shape != k.shape:
+        raise ValueError(f"{ok.numel()} report rows for {k.numel()} scaffold rows")
+    counts = [ok.sum(), (scaffold_match(sca) & ok).sum(),
+              first_occurrence(k, valid=ok & (sca.info[:, 0] == ops.SCA_OK)).sum()]
+    if keys is not None:
+        mol = _molecule_column(keys).to(k.device)
+        if mol.shape != k.shape:
+            raise ValueError(f"{mol.numel()} molecule keys for {k.numel()} scaffold rows")
+        counts.append(first_occurrence(mol, group=k, valid=ok).sum())
+    counts = torch.stack(counts).tolist()
+    n, n_valid = k.numel(), counts[0]
+    out = {"same_scaffold": counts[1] / n_valid if n_valid else 0.0, "n_scaffolds": counts[2]}
+    if keys is not None:
+        out["unique_on_scaffold"] = counts[3] / n_valid if n_valid else 0.0
+    out.update(n=n, n_valid=n_valid, n_same=counts[1])
     return out

@@ -1551,6 +1551,66 @@ def smiles_key(ys, start, table32, label64, pad_id, eos_id, sep_id, out=None):
     return key, info
 
 
+# status codes of the Murcko scaffolds (GCT_SCA_* of include/gctplus_hip.h)
+SCA_OK, SCA_ACYCLIC, SCA_SYNTAX, SCA_UNSUPPORTED, SCA_NO_TOKEN, SCA_NO_RING, SCA_TOO_LONG = range(7)
+SCA_MAX_SPAN = 256
+
+
+def smiles_scaffold(ys, start, table32, label64, ring_ids, n_rings, open_id, close_id, pad_id, eos_id, sep_id, n_id,
+                    nh_id, out_width=None, out=None):
+    """gct_smiles_scaffold: the Murcko scaffold of the molecule in every row's span ys[r, start[r]:] -- its key, its
+    spelling and the atoms it keeps -- and the key of the scaffold in front of a <sep>
+    (scaffold.SmilesScaffolds.scaffold_reference is the statement).  ys int64 [n, W] with unit column stride, start int32
+    [n] on the device, table32 int32 [V] and label64 int64 [V] (SmilesKeys.device_tables), ring_ids int32 [64]
+    (SmilesRandomizer.device_tables); sep_id, n_id (the token `n`) and nh_id (`[nH]`) -1 for none.  Returns (tokens int64
+    [n, out_width], key int64 [n, 2], info int32 [n, 4], member int32 [n, W]), freshly allocated or the contiguous
+    tensors of out = (tokens, key, info, member).  One launch."""
+    _chk(ys, "smiles_scaffold.ys", torch.int64), _chk(start, "smiles_scaffold.start", torch.int32)
+    _chk(table32, "smiles_scaffold.table32", torch.int32), _chk(label64, "smiles_scaffold.label64", torch.int64)
+    _chk(ring_ids, "smiles_scaffold.ring_ids", torch.int32)
+    if ys.dim() != 2 or ys.shape[1] < 1 or (ys.shape[1] > 1 and ys.stride(1) != 1):
+        raise ValueError("smiles_scaffold: ys [n, W >= 1] with unit column stride")
+    n, W = ys.shape
+    if start.dim() != 1 or start.numel() != n or not start.is_contiguous():
+        raise ValueError(f"smiles_scaffold: start must be a contiguous tensor [{n}], got {list(start.shape)}")
+    if (table32.dim() != 1 or table32.numel() < 1 or label64.shape != table32.shape or not table32.is_contiguous() or
+            not label64.is_contiguous()):
+        raise ValueError("smiles_scaffold: table32 int32 [V] and label64 int64 [V], contiguous")
+    V = table32.numel()
+    if ring_ids.dim() != 1 or ring_ids.numel() != 64 or not ring_ids.is_contiguous() or not 0 <= int(n_rings) <= 63:
+        raise ValueError("smiles_scaffold: ring_ids int32 [64], contiguous, with at most 63 numbers in use")
+    for name, v in (("open_id", open_id), ("close_id", close_id), ("pad_id", pad_id), ("eos_id", eos_id)):
+        if not 0 <= int(v) < V:
+            raise ValueError(f"smiles_scaffold: {name} {v} is outside the vocabulary of {V} tokens")
+    for name, v in (("sep_id", sep_id), ("n_id", n_id), ("nh_id", nh_id)):
+        if not -1 <= int(v) < V:
+            raise ValueError(f"smiles_scaffold: {name} {v} is outside the vocabulary of {V} tokens (-1: none)")
+    out_width = W if out_width is None else int(out_width)
+    if out_width < 1:
+        raise ValueError(f"smiles_scaffold: out_width {out_width} has no column for <eos>")
+    shapes = ((n, out_width), (n, 2), (n, 4), (n, W))
+    dtypes = (torch.int64, torch.int64, torch.int32, torch.int32)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=ys.device) for s, d in zip(shapes, dtypes))
+    else:
+        out = tuple(out)
+        if len(out) != 4:
+            raise ValueError("smiles_scaffold: out = (tokens, key, info, member)")
+        for name, t, s, d in zip(("tokens", "key", "info", "member"), out, shapes, dtypes):
+            _chk(t, f"smiles_scaffold.out {name}", d)
+            if tuple(t.shape) != s or not t.is_contiguous():
+                raise ValueError(f"smiles_scaffold: out must hold contiguous tensors {[list(x) for x in shapes]}, got "
+                                 f"{list(t.shape)} for {name}")
+    if n == 0:
+        return out
+    tokens, key, info, member = out
+    check(_L().gct_smiles_scaffold(_p(ys), max(W, ys.stride(0)), W, n, _p(start), V, _p(table32), _p(label64),
+                                   _p(ring_ids), int(n_rings), int(open_id), int(close_id), int(pad_id), int(eos_id),
+                                   int(sep_id), int(n_id), int(nh_id), _p(tokens), out_width, _p(key), _p(info),
+                                   _p(member), _st()), "gct_smiles_scaffold")
+    return out
+
+
 def _seq_geometry(name, logits2d, ys, rows_per_seq, V, prefix_lens, prior2d=None):
     """The checks every seq_* wrapper makes on (ys, logits, prefix_lens), with seq_dist's prior logits next to the
     agent's: (n, W, R, V, ld, ld_prior).  `name` (the caller's) opens every message, here and in the helpers below."""

@@ -157,42 +157,11 @@ class SmilesRandomizer:
                 pend = None
         return apos, bonds, lists, unsupported
 
-    def randomize(self, tokens, words, p=1.0, room=None):
-        """THE statement for one part: tokens = its ids (no <eos>, no <sep>), words = the part's stream -- a function
-        index -> 4 words (stream()), or a dict of them (a missing index: four zeros).  p: the coin's probability; room:
-        the columns the new spelling may take (None: any).  Returns (status, new tokens, perm): perm[k] = the input atom
-        of the k-th output atom; with any status but RAND_OK the tokens are the input's and perm is the identity over
-        the atoms (empty for SYNTAX).
-          SYNTAX, then UNSUPPORTED (parse), are decided first; then the coin, call 0 word x: KEPT unless p >= 1 or
-          x < coin_threshold(p).  Root = floor(y * atoms / 2^32), y word 1 of call 0.  The list of atom a (its INPUT
-          index) is shuffled by Fisher-Yates from the back: for i = deg - 1 .. 1, j = floor(w * (i + 1) / 2^32), swap
-          entries i and j, with w = word (i - 1) & 3 of call 1 + 2 a + ((i - 1) >> 2).
-          Pass 1, a depth-first search from the root over the shuffled lists: a bond to an unvisited atom is a tree edge
-          and is followed at once; a bond to a visited atom, other than the edge the search came by, is a ring bond
-          whose OPENING end is that visited atom (an ancestor).
-          Pass 2, emission per atom: its own token; its ring bonds in list order -- an opening writes the bond's symbol,
-          if any, and the lowest free ring number, and takes it (none free: NO_RING); a closing writes the bond's number,
-          which is free again from the NEXT atom on; then its children in list order, each behind its bond's symbol,
-          every child but the last inside `(` `)` with the symbol behind the `(`.
-          TOO_LONG when the new spelling has more than `room` tokens."""
-        get = words if callable(words) else (lambda i: words.get(i, (0, 0, 0, 0)))
-        tokens = [int(t) for t in tokens]
-        parsed = self.parse(tokens)
-        if parsed is None:
-            return ops.RAND_SYNTAX, tokens, []
-        apos, bonds, lists, unsupported = parsed
-        A, same = len(apos), list(range(len(apos)))
-        if unsupported:
-            return ops.RAND_UNSUPPORTED, tokens, same
-        x, y = get(0)[:2]
-        if not (p >= 1 or x < coin_threshold(p)):
-            return ops.RAND_KEPT, tokens, same
-        root = (y * A) >> 32
-        lists = [list(l) for l in lists]
-        for a, l in enumerate(lists):
-            for i in range(len(l) - 1, 0, -1):
-                j = (get(1 + 2 * a + ((i - 1) >> 2))[(i - 1) & 3] * (i + 1)) >> 32
-                l[i], l[j] = l[j], l[i]
+    def write_out(self, tokens, apos, bonds, lists, root):
+        """Passes 1 and 2 of `randomize` on their own: the graph (apos, bonds, lists) of `parse`, one connected component,
+        written out from `root` over the lists as they stand.  Returns (new tokens, perm), or None when no ring number
+        was free.  (SmilesScaffolds spells a scaffold with it.)"""
+        A = len(apos)
         other = lambda e, a: bonds[e][0] ^ bonds[e][1] ^ a
         # pass 1
         parent, opener, visited = {root: None}, {}, {root}     # parent[a]: the bond the search came by; opener[e]: an atom
@@ -238,7 +207,7 @@ class SmilesRandomizer:
             return True
 
         if not atom(root):
-            return ops.RAND_NO_RING, tokens, same
+            return None
         stack = [[root, 0, False]]
         left = {u: sum(1 for e in lists[u] if e not in opener and e != parent[u]) for u in range(A)}
         while stack:
@@ -259,8 +228,50 @@ class SmilesRandomizer:
             if bonds[e][2] is not None:
                 out.append(tokens[bonds[e][2]])
             if not atom(other(e, u)):
-                return ops.RAND_NO_RING, tokens, same
+                return None
             stack.append([other(e, u), 0, branch])
+        return out, perm
+
+    def randomize(self, tokens, words, p=1.0, room=None):
+        """THE statement for one part: tokens = its ids (no <eos>, no <sep>), words = the part's stream -- a function
+        index -> 4 words (stream()), or a dict of them (a missing index: four zeros).  p: the coin's probability; room:
+        the columns the new spelling may take (None: any).  Returns (status, new tokens, perm): perm[k] = the input atom
+        of the k-th output atom; with any status but RAND_OK the tokens are the input's and perm is the identity over
+        the atoms (empty for SYNTAX).
+          SYNTAX, then UNSUPPORTED (parse), are decided first; then the coin, call 0 word x: KEPT unless p >= 1 or
+          x < coin_threshold(p).  Root = floor(y * atoms / 2^32), y word 1 of call 0.  The list of atom a (its INPUT
+          index) is shuffled by Fisher-Yates from the back: for i = deg - 1 .. 1, j = floor(w * (i + 1) / 2^32), swap
+          entries i and j, with w = word (i - 1) & 3 of call 1 + 2 a + ((i - 1) >> 2).
+          Pass 1, a depth-first search from the root over the shuffled lists: a bond to an unvisited atom is a tree edge
+          and is followed at once; a bond to a visited atom, other than the edge the search came by, is a ring bond
+          whose OPENING end is that visited atom (an ancestor).
+          Pass 2, emission per atom: its own token; its ring bonds in list order -- an opening writes the bond's symbol,
+          if any, and the lowest free ring number, and takes it (none free: NO_RING); a closing writes the bond's number,
+          which is free again from the NEXT atom on; then its children in list order, each behind its bond's symbol,
+          every child but the last inside `(` `)` with the symbol behind the `(`.
+          TOO_LONG when the new spelling has more than `room` tokens."""
+        get = words if callable(words) else (lambda i: words.get(i, (0, 0, 0, 0)))
+        tokens = [int(t) for t in tokens]
+        parsed = self.parse(tokens)
+        if parsed is None:
+            return ops.RAND_SYNTAX, tokens, []
+        apos, bonds, lists, unsupported = parsed
+        A, same = len(apos), list(range(len(apos)))
+        if unsupported:
+            return ops.RAND_UNSUPPORTED, tokens, same
+        x, y = get(0)[:2]
+        if not (p >= 1 or x < coin_threshold(p)):
+            return ops.RAND_KEPT, tokens, same
+        root = (y * A) >> 32
+        lists = [list(l) for l in lists]
+        for a, l in enumerate(lists):
+            for i in range(len(l) - 1, 0, -1):
+                j = (get(1 + 2 * a + ((i - 1) >> 2))[(i - 1) & 3] * (i + 1)) >> 32
+                l[i], l[j] = l[j], l[i]
+        written = self.write_out(tokens, apos, bonds, lists, root)
+        if written is None:
+            return ops.RAND_NO_RING, tokens, same
+        out, perm = written
         if room is not None and len(out) > room:
             return ops.RAND_TOO_LONG, tokens, same
         return ops.RAND_OK, out, perm

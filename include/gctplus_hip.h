@@ -929,6 +929,34 @@ int gct_smiles_key(const int64_t* ys, int64_t ld_ys, int W, int n, const int32_t
                    const int64_t* label64, int pad_id, int eos_id, int sep_id, int64_t* key_out, int32_t* info_out,
                    void* stream);
 
+/* Murcko scaffolds (gct_plus_amd/scaffold.py SmilesScaffolds states the rules: `scaffold` for one part,
+ * scaffold_reference for a batch): the ring systems and linkers of the molecule in row r's span ys[r][start[r], W), with
+ * what is double-bonded to them, as a key and as a spelling; one wave per row.  Spans, <eos>, <sep>, table32 and label64:
+ * as in gct_smiles_key; ring_ids, n_rings, open_id, close_id: as in gct_smiles_randomize.  The molecule is the part
+ * behind the first <sep>, or the whole content; the part in front of the <sep> is the scaffold the row was GIVEN and is
+ * keyed by gct_smiles_key's rule.  n_id / nh_id: the ids of the tokens `n` and `[nH]`, -1 for none -- a kept `n` that
+ * loses a neighbour is spelled and keyed as `[nH]` (NO_TOKEN without one).
+ * tokens_out int64 [n][out_width], out_width >= 1: the spelling (the kept atoms and the bonds between them, written out
+ * by the randomiser's walk from the lowest kept atom over the lists in parse order), <eos>, <pad>; a spelling that does
+ * not fit min(out_width, 256) - 1 tokens is TOO_LONG.  key_out int64 [n][2] = (key of the extracted scaffold, key of the
+ * given part or 0).  info_out int32 [n][4] = (status, GCT_KEY_* status of the given part or -1, atoms kept, length of the
+ * spelling).  member_out int32 [n][W]: per atom of the molecule, in order, 0 dropped, 1 core, 2 shell; -1 behind them.
+ * ACYCLIC (no ring), SYNTAX and UNSUPPORTED (as the randomiser's): key 0, empty spelling, 0 atoms kept, and for the
+ * last two no member entry either.  NO_TOKEN: key 0, empty spelling.  NO_RING, TOO_LONG: empty spelling.  A span without
+ * <eos>, W - start[r] > 256 or start[r] outside [0, W]: <pad> tokens, keys 0, info (-1, -1, 0, 0), member -1.
+ * n = 0 is a no-op.  No global atomics, no scratch. */
+#define GCT_SCA_OK 0
+#define GCT_SCA_ACYCLIC 1
+#define GCT_SCA_SYNTAX 2
+#define GCT_SCA_UNSUPPORTED 3
+#define GCT_SCA_NO_TOKEN 4
+#define GCT_SCA_NO_RING 5
+#define GCT_SCA_TOO_LONG 6
+int gct_smiles_scaffold(const int64_t* ys, int64_t ld_ys, int W, int n, const int32_t* start, int V,
+                        const int32_t* table32, const int64_t* label64, const int32_t* ring_ids, int n_rings, int open_id,
+                        int close_id, int pad_id, int eos_id, int sep_id, int n_id, int nh_id, int64_t* tokens_out,
+                        int out_width, int64_t* key_out, int32_t* info_out, int32_t* member_out, void* stream);
+
 /* Per-step sampling statistics (gct_plus_amd/decode.py step_stats_reference states the rules).  Launched behind
  * gct_select_token in the step unit, on the same device counter and with gct_chosen_logp's row rule: row r looks at
  * column p = *pos - row_off[r] + 1, takes tok = ys[r][p] and writes each non-null table at out[dst][p].

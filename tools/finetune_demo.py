@@ -24,6 +24,10 @@ one launch on the device instead of the Python loop over the rows; the printed r
 distinct strings -- Sampling.molecule_keys and molkey.first_occurrence, on the device: a policy that writes one molecule
 in five spellings counts once.
 
+--report-scaffold: one more line at the end: same_scaffold of the evaluation batch before and after -- the share of its
+chemically valid rows whose molecule has the Murcko scaffold the row was given (Sampling.scaffold_report and
+molkey.scaffold_metrics, on the device; Train/finetune.scaffold_reward is the same verdict as a reward).
+
 --time-step: no sampling; --n fixed rows of MOSES-like lengths (clip(round(N(35, 8)), 15, 78) tokens + <eos> behind a
 scaffold prefix), --rounds reinforce_steps on them after two warm-up steps: the figure to put next to a bench.py
 training step of the same batch size (recorded in DESIGN 4, not gated).  With --ppo-epochs it times ONE epoch:
@@ -58,6 +62,8 @@ ap.add_argument("--report-valid", action="store_true",
                 help="one more line at the end: the chemically valid share of the evaluation batch before and after")
 ap.add_argument("--report-unique", action="store_true",
                 help="one more line at the end: distinct molecules (molecule keys) beside the distinct strings")
+ap.add_argument("--report-scaffold", action="store_true",
+                help="one more line at the end: the share of valid rows that have the scaffold they were given")
 ap.add_argument("--time-step", action="store_true",
                 help="time reinforce_step (one ppo_update epoch with --ppo-epochs) on fixed rows of MOSES-like lengths")
 a = ap.parse_args()
@@ -69,7 +75,7 @@ from gct_plus_amd import data, synthetic  # noqa: E402
 from gct_plus_amd.decode import SmilesGrammar  # noqa: E402
 from gct_plus_amd.Inference.sampling_tool import DecodedRows, PscavaetfSampling  # noqa: E402
 from gct_plus_amd.Model import model_dict  # noqa: E402
-from gct_plus_amd.molkey import first_occurrence  # noqa: E402
+from gct_plus_amd.molkey import first_occurrence, scaffold_metrics  # noqa: E402
 from gct_plus_amd.optim import FusedAdam  # noqa: E402
 from gct_plus_amd.Train.finetune import frozen_prior, ppo_update, reinforce_step, validity_reward  # noqa: E402
 
@@ -182,12 +188,15 @@ def evaluate():
     if a.report_unique:
         mk = sampler.molecule_keys(rows)
         MOLECULES.append(int(first_occurrence(mk, valid=mk.info[:, 0] >= 0).sum()))
+    if a.report_scaffold:
+        SAME_SCAFFOLD.append(scaffold_metrics(sampler.check_rows(rows), sampler.scaffold_report(rows)))
     return float(reward.mean()), distinct, float(terms.entropy.sum() / terms.tokens.sum())
 
 
 EVAL_SEED = 10 ** 6
 VALID_SHARE = []
 MOLECULES = []
+SAME_SCAFFOLD = []
 before = evaluate()
 reg = f", entropy_coef {a.entropy_coef}, kl_coef {a.kl_coef}" if a.entropy_coef or a.kl_coef else ""
 if a.ppo_epochs:
@@ -228,3 +237,8 @@ if a.report_unique:
     print(f"distinct molecules of the evaluation batch (molkey.SmilesKeys; a row without a graph counts as its string, one without "
           f"<eos> not at all): "
           f"{MOLECULES[0]} -> {MOLECULES[1]}, beside distinct strings {before[1]} -> {after[1]}")
+if a.report_scaffold:
+    b, c = SAME_SCAFFOLD
+    print(f"same_scaffold of the evaluation batch (scaffold.SmilesScaffolds; valid rows whose Murcko scaffold is {a.scaffold}): "
+          f"{b['same_scaffold']:.3f} -> {c['same_scaffold']:.3f} ({b['n_same']} of {b['n_valid']} -> {c['n_same']} of "
+          f"{c['n_valid']} valid rows), distinct scaffolds among them {b['n_scaffolds']} -> {c['n_scaffolds']}")
