@@ -12,12 +12,11 @@
 // A part without a graph (SYNTAX, UNSUPPORTED) gets lane 0's sequential hash of its tokens' labels instead.
 // LDS: sizeof(KeyWave) = 13 072 bytes per wave (6 656 the parsed graph, 2 048 the labels, 4 096 the two colour buffers,
 // 256 the bond labels, 16 the part's header), 52 288 per workgroup of four rows.
-// The per-atom functions (key_profile, key_refine, ...) are smiles_key.h's, shared with gct_smiles_scaffold.
+// The prelude is smiles_stage_row (smiles_graph.h); key_part and the per-atom functions under it (key_profile,
+// key_refine, ...) are smiles_key.h's, shared with gct_smiles_scaffold.
 #include "smiles_key.h"
 
 namespace {
-
-constexpr int kNone = 0x7fffffff;
 
 struct KeyWave : SmilesGraph {                               // e[i] also carries, from bit 21: the key's bond label of a
   uint64_t lab[256];                                         //  BOND token (3 bits) or `aromatic` of an ATOM token, and
@@ -36,32 +35,12 @@ __global__ __launch_bounds__(256) void smiles_key_kernel(
   const int row = blockIdx.x * 4 + wave;
   const bool live = row < n;
   KeyWave& w = sh[wave];
-  const int t0 = live ? start[row] : W;
-  const bool in_range = live && t0 >= 0 && t0 <= W && W - t0 <= 256;
-  const int g = in_range ? W - t0 : 0;                       // 0 <= g <= 256 tokens in the span
-  const int64_t* yr = ys + (int64_t)row * ld_ys + (in_range ? t0 : 0);   // (read only under j < g)
-  int E = kNone, sep_at = 0;                                 // first <eos>; bit t: token lane + 64 t is <sep>
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int j = lane + 64 * t;
-    if (j < g) {
-      const int64_t tok = yr[j];
-      const bool known = tok >= 0 && tok < V;
-      int word = known ? table[tok] & 0xFFFFFF : GCT_GRAMMAR_BANNED;
-      if (tok == sep_id) word |= 1 << 24, sep_at |= 1 << t;  // (sep_id -1: none)
-      w.e[j] = word;
-      w.lab[j] = known ? (uint64_t)label[tok] : key_unknown_label(tok);
-      if (tok == eos_id) E = min(E, j);
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) E = min(E, __shfl_xor(E, o, 64));
-  int S = kNone;                                             // first <sep> in front of the <eos>
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-    if (((sep_at >> t) & 1) && lane + 64 * t < E) S = min(S, lane + 64 * t);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) S = min(S, __shfl_xor(S, o, 64));
+  const StagedRow sr = smiles_stage_row(w, ys, ld_ys, W, n, row, start, V, table, eos_id, sep_id, lane,
+                                        [&](int j, int64_t tok, bool known, int word) {
+                                          w.lab[j] = known ? (uint64_t)label[tok] : key_unknown_label(tok);
+                                          return word & 0xFFFFFF;
+                                        });
+  const int E = sr.E, S = sr.S;
   const bool row_bad = E == kNone;                           // (a dead wave and a row out of range: g = 0, no <eos>)
   const bool two = S != kNone;
   uint64_t k_mol = 0, k_sca = 0;                             // lane 0's
@@ -71,36 +50,9 @@ __global__ __launch_bounds__(256) void smiles_key_kernel(
     const int which = 1 - it;                                // the scaffold (part 1) first, then the molecule (part 0)
     const bool active = !row_bad && (which == 0 || two);
     const int lo = which == 1 ? 0 : (two ? S + 1 : 0), hi = which == 1 ? S : E;
-    int status = GCT_KEY_STRING_SYNTAX;
-    __syncthreads();                                         // the staged row; the last part's lists are done with
-    if (lane == 0) {
-      int A = 0, nb = 0;
-      if (active) {
-        bool unsup;
-        const bool parsed = rand_parse(w, lo, hi, A, nb, unsup);
-        status = !parsed ? GCT_KEY_STRING_SYNTAX : unsup ? GCT_KEY_STRING_UNSUPPORTED : GCT_KEY_GRAPH;
-      }
-      w.res[0] = active && status == GCT_KEY_GRAPH, w.res[1] = A, w.res[2] = nb;
-    }
-    __syncthreads();
-    const bool graph = w.res[0] != 0;                        // (the same for the whole wave)
-    const int nA = w.res[1], nB = w.res[2];
-    if (graph) {
-      for (int e = lane; e < nB; e += 64) w.blab[e] = (uint8_t)key_bond_label(w, e);
-      for (int a = lane; a < nA; a += 64) w.col[0][a] = key_profile(w, a);
-    }
-    __syncthreads();
-    for (int r = 0; r < GCT_KEY_ROUNDS; ++r) {
-      if (graph)
-        for (int a = lane; a < nA; a += 64) w.col[(r + 1) & 1][a] = key_refine(w, w.col[r & 1], a);
-      __syncthreads();
-    }
-    uint64_t sum = 0;
-    if (graph)
-      for (int a = lane; a < nA; a += 64) sum += key_mix(w.col[GCT_KEY_ROUNDS & 1][a]);
-    sum = key_wave_sum(sum);
+    int status, nA, nB;
+    const uint64_t k = key_part(w, active, lo, hi, lane, status, nA, nB);
     if (active && lane == 0) {
-      const uint64_t k = graph ? key_combine(sum, nA, nB) : key_string(w, lo, hi);
       if (which == 1) {
         k_sca = k, st_sca = status;
       } else {

@@ -1,6 +1,6 @@
 // SMILES randomisation on the device: gct_smiles_randomize against randomize.py SmilesRandomizer (randomize is the
 // statement for one part, randomize_reference the batch rule).  One wave per row, four rows per workgroup, in
-// smiles_check_kernel's shape (decode.hip): lane l stages tokens l + 64 t of the row's span in the wave's own LDS and
+// smiles_check_kernel's shape (chem.hip): lane l stages tokens l + 64 t of the row's span in the wave's own LDS and
 // the wave finds the first <eos> and the first <sep> in front of it; then, part by part (the scaffold, if any, first):
 //   lane 0 parses the part into bonds and per-atom bond lists (rand_parse of smiles_graph.h) and tosses the coin;
 //   lane l shuffles the lists of atoms l + 64 t (Philox calls keyed by the INPUT atom: none waits for the walk);
@@ -9,12 +9,10 @@
 // before; what they leave is indexed dynamically in LDS, never in registers, so nothing spills.  No global atomics.
 // An entry of the LDS row is a literal token id (>= 0: ring numbers, parentheses, <sep>, <eos>) or -(j + 1): the token
 // at position j of the input span (atoms and bond symbols are carried verbatim, whatever their ids).
-// rand_walk is smiles_walk.h's, shared with gct_smiles_scaffold.
+// smiles_stage_row is smiles_graph.h's; rand_shuffle_atom and rand_walk are smiles_walk.h's.
 #include "smiles_walk.h"
 
 namespace {
-
-constexpr int kNone = 0x7fffffff;
 
 struct RandWave : SmilesGraph {                              // (smiles_graph.h: what rand_parse fills; e[i] carries
   int32_t out[256];                                          //  (the token is <sep>) << 24; adj is shuffled in place)
@@ -34,33 +32,13 @@ __global__ __launch_bounds__(256) void smiles_randomize_kernel(
   const int row = blockIdx.x * 4 + wave;
   const bool live = row < n;
   RandWave& w = sh[wave];
-  const int t0 = live ? start[row] : W;
-  const bool in_range = live && t0 >= 0 && t0 <= W && W - t0 <= 256;
-  const int g = in_range ? W - t0 : 0;                       // 0 <= g <= 256 tokens in the span
-  const int64_t* yr = ys + (int64_t)row * ld_ys + (in_range ? t0 : 0);   // (read only under j < g, or as the whole row)
-  int E = kNone, sep_at = 0;                                 // first <eos>; bit t: token lane + 64 t is <sep>
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int j = lane + 64 * t;
-    if (j < g) {
-      const int64_t tok = yr[j];
-      int word = tok >= 0 && tok < V ? table[tok] & 0x1FFFFF : GCT_GRAMMAR_BANNED;
-      if (tok == sep_id) word |= 1 << 24, sep_at |= 1 << t;  // (sep_id -1: none)
-      w.e[j] = word;
-      if (tok == eos_id) E = min(E, j);
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) E = min(E, __shfl_xor(E, o, 64));
-  int S = kNone;                                             // first <sep> in front of the <eos>
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-    if (((sep_at >> t) & 1) && lane + 64 * t < E) S = min(S, lane + 64 * t);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) S = min(S, __shfl_xor(S, o, 64));
+  const StagedRow sr = smiles_stage_row(w, ys, ld_ys, W, n, row, start, V, table, eos_id, sep_id, lane,
+                                        [](int, int64_t, bool, int word) { return word & 0x1FFFFF; });
+  const int t0 = sr.t0, g = sr.g, E = sr.E, S = sr.S;
+  const int64_t* yr = sr.yr;
   const bool row_bad = E == kNone;                           // (a dead wave and a row out of range: g = 0, no <eos>)
   const bool two = S != kNone;
-  const int total = in_range ? min(out_width - t0, 256) : 0; // columns the new span may take: total >= g > E
+  const int total = row_bad ? 0 : min(out_width - t0, 256);  // columns the new span may take: total >= g > E
   const int64_t kw = live ? key[row] : 0;
   const uint32_t klo = (uint32_t)kw, khi = (uint32_t)((uint64_t)kw >> 32);
   int opos = 0, abase = 0, st_mol = GCT_RAND_SYNTAX, st_sca = -1;   // lane 0's: output columns and atoms so far
@@ -96,12 +74,7 @@ __global__ __launch_bounds__(256) void smiles_randomize_kernel(
         const uint4 c0 = gct_philox(rng, klo, khi, (uint32_t)which, (uint32_t)(1 + 2 * a));
         uint4 c1 = make_uint4(0, 0, 0, 0);
         if (d > 5) c1 = gct_philox(rng, klo, khi, (uint32_t)which, (uint32_t)(2 + 2 * a));
-        for (int i = d - 1; i >= 1; --i) {
-          const uint32_t x = i - 1 < 4 ? gct_pick(c0, i - 1) : gct_pick(c1, i - 5);
-          const int j = (int)__umulhi(x, (uint32_t)(i + 1));
-          const uint8_t ti = w.adj[a][i], tj = w.adj[a][j];
-          w.adj[a][i] = tj, w.adj[a][j] = ti;
-        }
+        rand_shuffle_atom(w, a, d, c0, c1);
       }
     }
     __syncthreads();

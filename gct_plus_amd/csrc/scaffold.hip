@@ -24,7 +24,6 @@
 
 namespace {
 
-constexpr int kNone = 0x7fffffff;
 constexpr int kBareN = 1 << 25, kSubst = 1 << 26;            // bits of e[i] beside the table word and <sep> << 24
 
 struct ScaWave : SmilesGraph {                               // e[i]: as KeyWave's | kBareN (the token is `n`) | kSubst
@@ -125,25 +124,6 @@ __host__ __device__ inline void sca_compact(Rec& w, int A, int nb, int& atoms, i
   atoms = nK, bonds = nBk;
 }
 
-// The whole wave: the wrapping sum of the refined colours of a graph of nA atoms and nB bonds, as gct_smiles_key takes it
-// (every wave of the workgroup passes the same barriers, with or without a graph).
-__device__ __forceinline__ uint64_t sca_key_sum(ScaWave& w, bool graph, int nA, int nB, int lane) {
-  if (graph) {
-    for (int e = lane; e < nB; e += 64) w.blab[e] = (uint8_t)key_bond_label(w, e);
-    for (int a = lane; a < nA; a += 64) w.col[0][a] = key_profile(w, a);
-  }
-  __syncthreads();
-  for (int r = 0; r < GCT_KEY_ROUNDS; ++r) {
-    if (graph)
-      for (int a = lane; a < nA; a += 64) w.col[(r + 1) & 1][a] = key_refine(w, w.col[r & 1], a);
-    __syncthreads();
-  }
-  uint64_t sum = 0;
-  if (graph)
-    for (int a = lane; a < nA; a += 64) sum += key_mix(w.col[GCT_KEY_ROUNDS & 1][a]);
-  return key_wave_sum(sum);
-}
-
 __global__ __launch_bounds__(256) void smiles_scaffold_kernel(
     const int64_t* __restrict__ ys, int64_t ld_ys, int W, int n, const int32_t* __restrict__ start, int V,
     const int32_t* __restrict__ table, const int64_t* __restrict__ label, const int32_t* __restrict__ ring_ids,
@@ -189,7 +169,7 @@ __global__ __launch_bounds__(256) void smiles_scaffold_kernel(
   uint64_t k_sca = 0, k_giv = 0;                             // lane 0's
   int st_giv = -1;
 
-  // ---- the given part: gct_smiles_key's path
+  // ---- the given part: gct_smiles_key's path (key_part of smiles_key.h, restated: see smiles_graph.h)
   {
     const bool active = !row_bad && two;
     int status = GCT_KEY_STRING_SYNTAX;
@@ -206,7 +186,7 @@ __global__ __launch_bounds__(256) void smiles_scaffold_kernel(
     __syncthreads();
     const bool graph = w.res[0] != 0;                        // (the same for the whole wave)
     const int nA = w.res[1], nB = w.res[2];
-    const uint64_t sum = sca_key_sum(w, graph, nA, nB, lane);
+    const uint64_t sum = key_graph_sum(w, graph, nA, nB, lane);
     if (active && lane == 0) k_giv = graph ? key_combine(sum, nA, nB) : key_string(w, 0, S), st_giv = status;
   }
 
@@ -251,7 +231,7 @@ __global__ __launch_bounds__(256) void smiles_scaffold_kernel(
   __syncthreads();
   const int nK = has ? w.res[1] : 0, nBk = has ? w.res[2] : 0;
   const bool keyed = has && !no_token;
-  const uint64_t sum = sca_key_sum(w, keyed, nK, nBk, lane);
+  const uint64_t sum = key_graph_sum(w, keyed, nK, nBk, lane);
   __syncthreads();                                           // the colours are done with: the walk's buffers alias them
   if (keyed) {
     for (int e = lane; e < nBk; e += 64) w.role[e] = 0;

@@ -3,8 +3,9 @@
 // is a template over the wave's LDS record Rec, which derives from SmilesGraph (smiles_graph.h) and adds
 //   uint64_t lab[256]   token position -> the token's 64-bit label
 //   uint8_t blab[256]   bond -> its label o(e)
+// (key_graph_sum and key_part also: uint64_t col[2][256], atom -> colour, double-buffered; int32_t res[], three words)
 // and whose e[i] carries, from bit 21, the key's label of a BOND token (3 bits) or `aromatic` of an ATOM token.  Plain
-// C++ but for key_wave_sum, host-callable so that a CPU harness can run it under a sanitizer.
+// C++ but for the whole-wave functions at the end, host-callable so that a CPU harness can run it under a sanitizer.
 #pragma once
 #include "smiles_graph.h"
 
@@ -101,6 +102,52 @@ __device__ __forceinline__ uint64_t key_wave_sum(uint64_t x) {
     x += (uint64_t)lo | ((uint64_t)hi << 32);
   }
   return x;
+}
+
+// The whole wave: the wrapping sum of the refined colours of a graph of nA atoms and nB bonds -- lane l labels bonds
+// l + 64 t and takes the profiles of atoms l + 64 t, then GCT_KEY_ROUNDS rounds of refinement, one atom per lane and
+// pass.  Every wave of the workgroup passes the same 1 + GCT_KEY_ROUNDS barriers, with or without a graph.
+template <class Rec>
+__device__ __forceinline__ uint64_t key_graph_sum(Rec& w, bool graph, int nA, int nB, int lane) {
+  if (graph) {
+    for (int e = lane; e < nB; e += 64) w.blab[e] = (uint8_t)key_bond_label(w, e);
+    for (int a = lane; a < nA; a += 64) w.col[0][a] = key_profile(w, a);
+  }
+  __syncthreads();
+  for (int r = 0; r < GCT_KEY_ROUNDS; ++r) {
+    if (graph)
+      for (int a = lane; a < nA; a += 64) w.col[(r + 1) & 1][a] = key_refine(w, w.col[r & 1], a);
+    __syncthreads();
+  }
+  uint64_t sum = 0;
+  if (graph)
+    for (int a = lane; a < nA; a += 64) sum += key_mix(w.col[GCT_KEY_ROUNDS & 1][a]);
+  return key_wave_sum(sum);
+}
+
+// The whole wave: the key of the part [lo, hi) of the staged row (an inactive wave only passes the barriers, two more
+// than key_graph_sum's): lane 0 parses it, the wave sums a graph's colours, and a part without a graph (SYNTAX,
+// UNSUPPORTED) gets lane 0's sequential hash of its tokens' labels instead.  The key and the status are lane 0's.
+template <class Rec>
+__device__ __forceinline__ uint64_t key_part(Rec& w, bool active, int lo, int hi, int lane, int& status, int& atoms,
+                                             int& bonds) {
+  status = -1;                                               // (no such part)
+  __syncthreads();                                           // the staged row; the last part's lists are done with
+  if (lane == 0) {
+    int A = 0, nb = 0;
+    if (active) {
+      bool unsup;
+      const bool parsed = rand_parse(w, lo, hi, A, nb, unsup);
+      status = !parsed ? GCT_KEY_STRING_SYNTAX : unsup ? GCT_KEY_STRING_UNSUPPORTED : GCT_KEY_GRAPH;
+    }
+    w.res[0] = active && status == GCT_KEY_GRAPH, w.res[1] = A, w.res[2] = nb;
+  }
+  __syncthreads();
+  const bool graph = w.res[0] != 0;                          // (the same for the whole wave)
+  atoms = w.res[1], bonds = w.res[2];
+  const uint64_t sum = key_graph_sum(w, graph, atoms, bonds, lane);
+  if (!active || lane != 0) return 0;
+  return graph ? key_combine(sum, atoms, bonds) : key_string(w, lo, hi);
 }
 
 }  // namespace

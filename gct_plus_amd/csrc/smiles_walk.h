@@ -11,6 +11,21 @@
 
 namespace {
 
+// A lane's atom a: the Fisher-Yates shuffle of its bond list adj[a] of d >= 2 entries, back to front.  Step i swaps
+// entry i with entry floor(x (i + 1) / 2^32), x being word i - 1 of c0 and, from the fifth step on, word i - 5 of c1 (the
+// atom's two Philox results; c1 is not looked at for d <= 5).  The words are picked by constants: no per-lane array.
+template <class Rec>
+__host__ __device__ inline void rand_shuffle_atom(Rec& w, int a, int d, uint4 c0, uint4 c1) {
+  for (int i = d - 1; i >= 1; --i) {
+    const uint4 c = i - 1 < 4 ? c0 : c1;
+    const int k = (i - 1) & 3;
+    const uint32_t x = k == 0 ? c.x : (k == 1 ? c.y : (k == 2 ? c.z : c.w));
+    const int j = (int)(((uint64_t)x * (uint32_t)(i + 1)) >> 32);
+    const uint8_t ti = w.adj[a][i], tj = w.adj[a][j];
+    w.adj[a][i] = tj, w.adj[a][j] = ti;
+  }
+}
+
 // Lane 0: passes 1 and 2 of the statement for a part of A atoms rooted at `root`, into w.out[opos, opos + room) and
 // w.perm[abase, abase + A).  seen / left / role of the part are cleared by the caller.  Returns the length of the new
 // spelling (it may exceed room: nothing is written past it), or -1 when no ring number was free.

@@ -244,6 +244,7 @@ def sample_filter_reference(logits, top_k=None, top_p=None, temperature=1.0):
 GRAMMAR_START = (G_START, 0, 0, 0)                 # (prev, depth, open, here) before the first generated token
 _ATOMS = frozenset("B Br C Cl N O S P F I b c n o s p *".split())
 _BONDS = frozenset("= # - / \\ : ~ $".split())
+_CHEM_BOND_ORDERS = {"-": 1, "=": 2, "#": 3, "$": 4, ":": 1, "/": 1, "\\": 1, "~": 1}
 
 
 def grammar_class(token):
@@ -308,6 +309,64 @@ def grammar_step(state, cls, ring=0):
     if cls == ops.GRAMMAR_EOS:
         return (G_END, 0, 0, 0) if arc and depth == 0 and open_ == 0 else None
     return None
+
+
+def smiles_walk(grammar, tokens, row):
+    """THE walk that reads a token span as a molecule, over a SmilesGrammar (chem_walk of csrc/chem.hip and rand_parse of
+    csrc/smiles_graph.h implement it; SmilesChemistry.check and SmilesRandomizer.parse say what the events mean to them).  row: the span is a whole
+    row -- the <eos> and whatever follows it included; otherwise a part, its <eos> implied behind it.  Atoms are numbered
+    in token order.  An ATOM bonds to the atom the chain stands at (OPEN pushes that atom, CLOSE pops it, DOT clears it;
+    the first atom has none); a BOND token directly in front states the order (- 1, = 2, # 3, $ 4, each of : / \\ ~ 1).
+    A RING token belongs to the atom it follows; the first occurrence of an open number remembers the atom and the BOND
+    token in front, the next one closes it.  Yields, in token order,
+      ("atom", i)                    token i is the next atom
+      ("bond", a, b, order, sym)     a chain bond between atoms a < b; order: the stated one or None; sym: that BOND
+                                     token's position
+      ("ring", a, b, order, sym)     a ring closure's bond: the closing end's order if it states one, else the opening end's
+      ("clash", i)                   the closure at i adds no bond: both ends state an order and the two differ, or the two
+                                     atoms are bonded already (by the chain or by an earlier closure)
+      ("dot", i)
+      ("syntax", i)                  the last event: the first token without a transition (grammar_step; an id outside
+                                     [0, V) has none), or len(tokens) when the span lacks a good end"""
+    g, tokens = grammar, [int(t) for t in tokens]
+    st, atoms, cur, pend = GRAMMAR_START, 0, None, None        # pend: (order, position) of a BOND token that waits
+    stack, open_rings, bonded = [], {}, set()
+    for i, t in enumerate(tokens):
+        st = grammar_step(st, g.classes[t], g.rings[t]) if 0 <= t < len(g) else None
+        if st is None:
+            yield "syntax", i
+            return
+        c = g.classes[t]
+        if c == ops.GRAMMAR_ATOM:
+            yield "atom", i
+            if cur is not None:
+                bonded.add((cur, atoms))
+                yield ("bond", cur, atoms) + (pend or (None, None))
+            cur, atoms = atoms, atoms + 1
+        elif c == ops.GRAMMAR_BOND:
+            pend = (_CHEM_BOND_ORDERS[g.itos[t]], i)
+            continue
+        elif c == ops.GRAMMAR_OPEN:
+            stack.append(cur)
+            continue
+        elif c == ops.GRAMMAR_CLOSE:
+            cur = stack.pop()
+        elif c == ops.GRAMMAR_DOT:
+            yield "dot", i
+            cur = None
+        elif c == ops.GRAMMAR_RING:
+            if g.rings[t] in open_rings:
+                a, first = open_rings.pop(g.rings[t])
+                if (first and pend and first[0] != pend[0]) or (a, cur) in bonded:   # (a < cur: it closes on a later atom)
+                    yield "clash", i
+                else:
+                    bonded.add((a, cur))
+                    yield ("ring", a, cur) + (pend or first or (None, None))
+            else:
+                open_rings[g.rings[t]] = (cur, pend)
+        pend = None
+    if (st[0] != G_END) if row else grammar_step(st, ops.GRAMMAR_EOS) is None:
+        yield "syntax", len(tokens)
 
 
 def grammar_min_finish(state):
@@ -447,7 +506,6 @@ class SmilesGrammar:
 # ------------------------------------------------------------------------------------------- chemical validity
 _CHEM_CAPS = {"B": 3, "C": 4, "N": 3, "O": 2, "F": 1, "Si": 4, "P": 5, "S": 6, "Cl": 1, "Br": 1, "I": 5}
 _CHEM_ROWS = (("B", "C", "N", "O", "F"), ("Al", "Si", "P", "S", "Cl"))
-_CHEM_BOND_ORDERS = {"-": 1, "=": 2, "#": 3, "$": 4, ":": 1, "/": 1, "\\": 1, "~": 1}
 _CHEM_BRACKET = re.compile(r"\[(\d+)?([A-Z][a-z]?|[a-z][a-z]?|\*)(@{0,2})(H\d?)?(\++|-+|[+-]\d+)?\]")
 
 
@@ -543,52 +601,23 @@ class SmilesChemistry:
         hydrogens and used = sigma + H + (1 if it is aromatic and carbon-like and mo < 2): VALENCE at the atom's token
         when its cap is known and used > cap; otherwise AROMATIC there when it is aromatic and anb < 2.
         The finding with the smallest position wins; OK has position -1."""
-        g = self.grammar
         tokens = [int(t) for t in tokens]
-        st = GRAMMAR_START
-        for i, t in enumerate(tokens):
-            st = grammar_step(st, g.classes[t], g.rings[t]) if 0 <= t < len(g) else None
-            if st is None:
-                return ops.CHEM_SYNTAX, i, 0, 0
-        if st[0] != G_END:
-            return ops.CHEM_SYNTAX, len(tokens), 0, 0
-        atoms, bonds, stack, open_rings, findings = [], set(), [], {}, []   # atoms: [token position, word, sigma, mo, anb]
-        cur, pend, ring_bonds = None, None, 0
-
-        def link(a, b, order):
-            bonds.add((a, b))
-            for x, y in ((a, b), (b, a)):
-                atoms[x][2] += order
-                atoms[x][3] = max(atoms[x][3], order)
-                atoms[x][4] += (atoms[y][1] >> 8) & 1
-
-        for i, t in enumerate(tokens):
-            c = g.classes[t]
-            if c == ops.GRAMMAR_ATOM:
-                atoms.append([i, self.words[t], 0, 0, 0])
-                if cur is not None:
-                    link(cur, len(atoms) - 1, pend or 1)
-                cur, pend = len(atoms) - 1, None
-            elif c == ops.GRAMMAR_BOND:
-                pend = (self.words[t] >> 12) & 7
-            elif c == ops.GRAMMAR_OPEN:
-                stack.append(cur)
-            elif c == ops.GRAMMAR_CLOSE:
-                cur, pend = stack.pop(), None
-            elif c == ops.GRAMMAR_DOT:
-                cur, pend = None, None
-            elif c == ops.GRAMMAR_RING:
-                r = g.rings[t]
-                if r in open_rings:
-                    a, order = open_rings.pop(r)
-                    ring_bonds += 1
-                    if (order and pend and order != pend) or (a, cur) in bonds:     # (a < cur: it closes on a later atom)
-                        findings.append((i, ops.CHEM_RING_BOND))
-                    else:
-                        link(a, cur, pend or order or 1)
-                else:
-                    open_rings[r] = (cur, pend)
-                pend = None
+        atoms, findings, ring_bonds = [], [], 0                # atoms: [token position, word, sigma, mo, anb]
+        for ev in smiles_walk(self.grammar, tokens, True):
+            if ev[0] == "syntax":
+                return ops.CHEM_SYNTAX, ev[1], 0, 0
+            if ev[0] == "atom":
+                atoms.append([ev[1], self.words[tokens[ev[1]]], 0, 0, 0])
+            elif ev[0] in ("bond", "ring"):
+                a, b, order = ev[1], ev[2], ev[3] or 1
+                ring_bonds += ev[0] == "ring"
+                for x, y in ((a, b), (b, a)):
+                    atoms[x][2] += order
+                    atoms[x][3] = max(atoms[x][3], order)
+                    atoms[x][4] += (atoms[y][1] >> 8) & 1
+            elif ev[0] == "clash":
+                ring_bonds += 1
+                findings.append((ev[1], ops.CHEM_RING_BOND))
         for pos, w, sigma, mo, anb in atoms:
             cap, h, aromatic, clike = w & 15, (w >> 4) & 15, (w >> 8) & 1, (w >> 9) & 1
             used = sigma + h + (1 if aromatic and clike and mo < 2 else 0)

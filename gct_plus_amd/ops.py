@@ -1415,30 +1415,78 @@ CHEM_NO_CAP = 15
 CHEM_MAX_SPAN = 256
 
 
+def _smiles_rows(name, ys, **vectors):
+    """The checks every smiles_* wrapper makes on its rows: ys int64 [n, W >= 1] with unit column stride and the
+    per-row `vectors` (name -> (tensor, dtype): start, key), contiguous [n].  Returns (n, W, the rows' stride).  `name`
+    (the caller's) opens every message, here and in the helpers below."""
+    _chk(ys, f"{name}.ys", torch.int64)
+    if ys.dim() != 2 or ys.shape[1] < 1 or (ys.shape[1] > 1 and ys.stride(1) != 1):
+        raise ValueError(f"{name}: ys [n, W >= 1] with unit column stride")
+    n, W = ys.shape
+    for what, (t, dtype) in vectors.items():
+        _chk(t, f"{name}.{what}", dtype)
+        if t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be a contiguous tensor [{n}], got {list(t.shape)}")
+    return n, W, max(W, ys.stride(0))
+
+
+def _smiles_tables(name, **tables):
+    """The per-token tables (name -> (tensor, dtype)): contiguous [V >= 1], all of one shape.  Returns V."""
+    V = None
+    for what, (t, dtype) in tables.items():
+        _chk(t, f"{name}.{what}", dtype)
+        if t.dim() != 1 or t.numel() < 1 or not t.is_contiguous() or t.numel() != (V or t.numel()):
+            raise ValueError(f"{name}: {' and '.join(tables)} must be contiguous [V] tensors of one length, got "
+                             f"{list(t.shape)} for {what}")
+        V = t.numel()
+    return V
+
+
+def _smiles_rings(name, ring_ids, n_rings):
+    _chk(ring_ids, f"{name}.ring_ids", torch.int32)
+    if ring_ids.dim() != 1 or ring_ids.numel() != 64 or not ring_ids.is_contiguous() or not 0 <= int(n_rings) <= 63:
+        raise ValueError(f"{name}: ring_ids int32 [64], contiguous, with at most 63 numbers in use")
+
+
+def _smiles_ids(name, V, needed, optional):
+    """Token ids (name -> id): `needed` in [0, V), `optional` in [-1, V) with -1 for none."""
+    for ids, lo, note in ((needed, 0, ""), (optional, -1, " (-1: none)")):
+        for what, v in ids.items():
+            if not lo <= int(v) < V:
+                raise ValueError(f"{name}: {what} {v} is outside the vocabulary of {V} tokens{note}")
+
+
+def _smiles_out(name, given, like, **wanted):
+    """The outputs (name -> (shape, dtype)): freshly allocated on like's device, or the contiguous tensors of the tuple
+    `given`, one per entry.  Returns the tuple."""
+    if given is None:
+        return tuple(torch.empty(shape, dtype=dtype, device=like.device) for shape, dtype in wanted.values())
+    given = tuple(given)
+    if len(given) != len(wanted):
+        raise ValueError(f"{name}: out = ({', '.join(wanted)})")
+    for (what, (shape, dtype)), t in zip(wanted.items(), given):
+        _chk(t, f"{name}.out {what}", dtype)
+        if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise ValueError(f"{name}: out must hold contiguous tensors {[list(w[0]) for w in wanted.values()]}, got "
+                             f"{list(t.shape)} for {what}")
+    return given
+
+
 def smiles_check(ys, start, table, chem, out=None):
     """gct_smiles_check: out int32 [n, 4] = (status, position, atoms, ring_bonds) of every row's span ys[r, start[r]:]
     (decode.SmilesChemistry.check is the statement).  ys int64 [n, W] with unit column stride, start int32 [n] on the
     device with 0 <= start[r] <= W and W - start[r] <= 256 (the caller's to guarantee: a row outside that range is
     reported as SYNTAX at position 0), table / chem int32 [V] (SmilesChemistry.device_tables).  One launch."""
-    _chk(ys, "smiles_check.ys", torch.int64), _chk(start, "smiles_check.start", torch.int32)
-    _chk(table, "smiles_check.table", torch.int32), _chk(chem, "smiles_check.chem", torch.int32)
-    if ys.dim() != 2 or ys.shape[1] < 1 or (ys.shape[1] > 1 and ys.stride(1) != 1):
-        raise ValueError("smiles_check: ys [n, W >= 1] with unit column stride")
-    n, W = ys.shape
-    if start.dim() != 1 or start.numel() != n or not start.is_contiguous():
-        raise ValueError(f"smiles_check: start must be a contiguous int32 tensor [{n}], got {list(start.shape)}")
-    if (table.dim() != 1 or table.numel() < 1 or chem.shape != table.shape or not table.is_contiguous() or
-            not chem.is_contiguous()):
-        raise ValueError("smiles_check: table and chem int32 [V], contiguous")
+    n, W, ld = _smiles_rows("smiles_check", ys, start=(start, torch.int32))
+    V = _smiles_tables("smiles_check", table=(table, torch.int32), chem=(chem, torch.int32))
     if out is None:
         out = torch.empty(n, 4, dtype=torch.int32, device=ys.device)
     _chk(out, "smiles_check.out", torch.int32)
     if tuple(out.shape) != (n, 4) or not out.is_contiguous():
         raise ValueError(f"smiles_check: out must be a contiguous int32 tensor [{n}, 4], got {list(out.shape)}")
-    if n == 0:
-        return out
-    check(_L().gct_smiles_check(_p(ys), max(W, ys.stride(0)), W, n, _p(start), table.numel(),
-                                _p(table), _p(chem), _p(out), _st()), "gct_smiles_check")
+    if n:
+        check(_L().gct_smiles_check(_p(ys), ld, W, n, _p(start), V, _p(table), _p(chem), _p(out), _st()),
+              "gct_smiles_check")
     return out
 
 
@@ -1458,51 +1506,27 @@ def smiles_randomize(ys, start, key, table, ring_ids, n_rings, open_id, close_id
     (SmilesRandomizer.device_tables), sep_id -1 for none.  Returns (tokens int64 [n, out_width], info int32 [n, 4],
     perm int32 [n, out_width] or None), freshly allocated or the contiguous tensors of out = (tokens, info, perm or None).
     One launch."""
-    _chk(ys, "smiles_randomize.ys", torch.int64), _chk(start, "smiles_randomize.start", torch.int32)
-    _chk(key, "smiles_randomize.key", torch.int64), _chk(table, "smiles_randomize.table", torch.int32)
-    _chk(ring_ids, "smiles_randomize.ring_ids", torch.int32)
-    if ys.dim() != 2 or ys.shape[1] < 1 or (ys.shape[1] > 1 and ys.stride(1) != 1):
-        raise ValueError("smiles_randomize: ys [n, W >= 1] with unit column stride")
-    n, W = ys.shape
-    for name, t in (("start", start), ("key", key)):
-        if t.dim() != 1 or t.numel() != n or not t.is_contiguous():
-            raise ValueError(f"smiles_randomize: {name} must be a contiguous tensor [{n}], got {list(t.shape)}")
-    if table.dim() != 1 or table.numel() < 1 or not table.is_contiguous():
-        raise ValueError("smiles_randomize: table int32 [V], contiguous")
-    V = table.numel()
-    if ring_ids.dim() != 1 or ring_ids.numel() != 64 or not ring_ids.is_contiguous() or not 0 <= int(n_rings) <= 63:
-        raise ValueError("smiles_randomize: ring_ids int32 [64], contiguous, with at most 63 numbers in use")
-    for name, v in (("open_id", open_id), ("close_id", close_id), ("pad_id", pad_id), ("eos_id", eos_id)):
-        if not 0 <= int(v) < V:
-            raise ValueError(f"smiles_randomize: {name} {v} is outside the vocabulary of {V} tokens")
-    if not -1 <= int(sep_id) < V:
-        raise ValueError(f"smiles_randomize: sep_id {sep_id} is outside the vocabulary of {V} tokens (-1: none)")
+    name = "smiles_randomize"
+    n, W, ld = _smiles_rows(name, ys, start=(start, torch.int32), key=(key, torch.int64))
+    V = _smiles_tables(name, table=(table, torch.int32))
+    _smiles_rings(name, ring_ids, n_rings)
+    _smiles_ids(name, V, dict(open_id=open_id, close_id=close_id, pad_id=pad_id, eos_id=eos_id), dict(sep_id=sep_id))
     if not 0.0 <= float(p) <= 1.0:
-        raise ValueError(f"smiles_randomize: p must be a probability in [0, 1], got {p}")
+        raise ValueError(f"{name}: p must be a probability in [0, 1], got {p}")
     out_width = W if out_width is None else int(out_width)
     if out_width < W:
-        raise ValueError(f"smiles_randomize: out_width {out_width} is narrower than the rows ({W} columns)")
-    if out is None:
-        tokens = torch.empty(n, out_width, dtype=torch.int64, device=ys.device)
-        info = torch.empty(n, 4, dtype=torch.int32, device=ys.device)
-        perm = torch.empty(n, out_width, dtype=torch.int32, device=ys.device) if return_perm else None
-    else:
-        tokens, info, perm = out
-        _chk(tokens, "smiles_randomize.out tokens", torch.int64), _chk(info, "smiles_randomize.out info", torch.int32)
-        wanted = [(tokens, (n, out_width)), (info, (n, 4))]
-        if perm is not None:
-            _chk(perm, "smiles_randomize.out perm", torch.int32)
-            wanted.append((perm, (n, out_width)))
-        for t, shape in wanted:
-            if tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError(f"smiles_randomize: out must hold contiguous tensors {[w[1] for w in wanted]}, got "
-                                 f"{list(t.shape)}")
-    if n == 0:
-        return tokens, info, perm
-    check(_L().gct_smiles_randomize(_p(ys), max(W, ys.stride(0)), W, n, _p(start), _p(key), V, _p(table), _p(ring_ids),
-                                    int(n_rings), int(open_id), int(close_id), int(pad_id), int(eos_id), int(sep_id),
-                                    int(seed) & 0xFFFFFFFFFFFFFFFF, float(p), _p(tokens), _p(info), _p(perm), out_width,
-                                    _st()), "gct_smiles_randomize")
+        raise ValueError(f"{name}: out_width {out_width} is narrower than the rows ({W} columns)")
+    with_perm = return_perm if out is None else tuple(out)[2:] != (None,)   # (without: the kernel takes a null pointer)
+    wanted = dict(tokens=((n, out_width), torch.int64), info=((n, 4), torch.int32))
+    if with_perm:
+        wanted["perm"] = ((n, out_width), torch.int32)
+    got = _smiles_out(name, out if out is None or with_perm else tuple(out)[:2], ys, **wanted)
+    tokens, info, perm = got if with_perm else got + (None,)
+    if n:
+        check(_L().gct_smiles_randomize(_p(ys), ld, W, n, _p(start), _p(key), V, _p(table), _p(ring_ids), int(n_rings),
+                                        int(open_id), int(close_id), int(pad_id), int(eos_id), int(sep_id),
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, float(p), _p(tokens), _p(info), _p(perm),
+                                        out_width, _st()), "gct_smiles_randomize")
     return tokens, info, perm
 
 
@@ -1518,36 +1542,13 @@ def smiles_key(ys, start, table32, label64, pad_id, eos_id, sep_id, out=None):
     stride, start int32 [n] on the device, table32 int32 [V] and label64 int64 [V] (SmilesKeys.device_tables), sep_id -1
     for none.  Returns (key int64 [n, 2], info int32 [n, 4]), freshly allocated or the contiguous tensors of
     out = (key, info).  One launch."""
-    _chk(ys, "smiles_key.ys", torch.int64), _chk(start, "smiles_key.start", torch.int32)
-    _chk(table32, "smiles_key.table32", torch.int32), _chk(label64, "smiles_key.label64", torch.int64)
-    if ys.dim() != 2 or ys.shape[1] < 1 or (ys.shape[1] > 1 and ys.stride(1) != 1):
-        raise ValueError("smiles_key: ys [n, W >= 1] with unit column stride")
-    n, W = ys.shape
-    if start.dim() != 1 or start.numel() != n or not start.is_contiguous():
-        raise ValueError(f"smiles_key: start must be a contiguous tensor [{n}], got {list(start.shape)}")
-    if (table32.dim() != 1 or table32.numel() < 1 or label64.shape != table32.shape or not table32.is_contiguous() or
-            not label64.is_contiguous()):
-        raise ValueError("smiles_key: table32 int32 [V] and label64 int64 [V], contiguous")
-    V = table32.numel()
-    for name, v in (("pad_id", pad_id), ("eos_id", eos_id)):
-        if not 0 <= int(v) < V:
-            raise ValueError(f"smiles_key: {name} {v} is outside the vocabulary of {V} tokens")
-    if not -1 <= int(sep_id) < V:
-        raise ValueError(f"smiles_key: sep_id {sep_id} is outside the vocabulary of {V} tokens (-1: none)")
-    if out is None:
-        key = torch.empty(n, 2, dtype=torch.int64, device=ys.device)
-        info = torch.empty(n, 4, dtype=torch.int32, device=ys.device)
-    else:
-        key, info = out
-        _chk(key, "smiles_key.out key", torch.int64), _chk(info, "smiles_key.out info", torch.int32)
-        for t, shape in ((key, (n, 2)), (info, (n, 4))):
-            if tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError(f"smiles_key: out must hold contiguous tensors [{n}, 2] and [{n}, 4], got "
-                                 f"{list(t.shape)}")
-    if n == 0:
-        return key, info
-    check(_L().gct_smiles_key(_p(ys), max(W, ys.stride(0)), W, n, _p(start), V, _p(table32), _p(label64), int(pad_id),
-                              int(eos_id), int(sep_id), _p(key), _p(info), _st()), "gct_smiles_key")
+    n, W, ld = _smiles_rows("smiles_key", ys, start=(start, torch.int32))
+    V = _smiles_tables("smiles_key", table32=(table32, torch.int32), label64=(label64, torch.int64))
+    _smiles_ids("smiles_key", V, dict(pad_id=pad_id, eos_id=eos_id), dict(sep_id=sep_id))
+    key, info = _smiles_out("smiles_key", out, ys, key=((n, 2), torch.int64), info=((n, 4), torch.int32))
+    if n:
+        check(_L().gct_smiles_key(_p(ys), ld, W, n, _p(start), V, _p(table32), _p(label64), int(pad_id), int(eos_id),
+                                  int(sep_id), _p(key), _p(info), _st()), "gct_smiles_key")
     return key, info
 
 
@@ -1565,49 +1566,23 @@ def smiles_scaffold(ys, start, table32, label64, ring_ids, n_rings, open_id, clo
     (SmilesRandomizer.device_tables); sep_id, n_id (the token `n`) and nh_id (`[nH]`) -1 for none.  Returns (tokens int64
     [n, out_width], key int64 [n, 2], info int32 [n, 4], member int32 [n, W]), freshly allocated or the contiguous
     tensors of out = (tokens, key, info, member).  One launch."""
-    _chk(ys, "smiles_scaffold.ys", torch.int64), _chk(start, "smiles_scaffold.start", torch.int32)
-    _chk(table32, "smiles_scaffold.table32", torch.int32), _chk(label64, "smiles_scaffold.label64", torch.int64)
-    _chk(ring_ids, "smiles_scaffold.ring_ids", torch.int32)
-    if ys.dim() != 2 or ys.shape[1] < 1 or (ys.shape[1] > 1 and ys.stride(1) != 1):
-        raise ValueError("smiles_scaffold: ys [n, W >= 1] with unit column stride")
-    n, W = ys.shape
-    if start.dim() != 1 or start.numel() != n or not start.is_contiguous():
-        raise ValueError(f"smiles_scaffold: start must be a contiguous tensor [{n}], got {list(start.shape)}")
-    if (table32.dim() != 1 or table32.numel() < 1 or label64.shape != table32.shape or not table32.is_contiguous() or
-            not label64.is_contiguous()):
-        raise ValueError("smiles_scaffold: table32 int32 [V] and label64 int64 [V], contiguous")
-    V = table32.numel()
-    if ring_ids.dim() != 1 or ring_ids.numel() != 64 or not ring_ids.is_contiguous() or not 0 <= int(n_rings) <= 63:
-        raise ValueError("smiles_scaffold: ring_ids int32 [64], contiguous, with at most 63 numbers in use")
-    for name, v in (("open_id", open_id), ("close_id", close_id), ("pad_id", pad_id), ("eos_id", eos_id)):
-        if not 0 <= int(v) < V:
-            raise ValueError(f"smiles_scaffold: {name} {v} is outside the vocabulary of {V} tokens")
-    for name, v in (("sep_id", sep_id), ("n_id", n_id), ("nh_id", nh_id)):
-        if not -1 <= int(v) < V:
-            raise ValueError(f"smiles_scaffold: {name} {v} is outside the vocabulary of {V} tokens (-1: none)")
+    name = "smiles_scaffold"
+    n, W, ld = _smiles_rows(name, ys, start=(start, torch.int32))
+    V = _smiles_tables(name, table32=(table32, torch.int32), label64=(label64, torch.int64))
+    _smiles_rings(name, ring_ids, n_rings)
+    _smiles_ids(name, V, dict(open_id=open_id, close_id=close_id, pad_id=pad_id, eos_id=eos_id),
+                dict(sep_id=sep_id, n_id=n_id, nh_id=nh_id))
     out_width = W if out_width is None else int(out_width)
     if out_width < 1:
-        raise ValueError(f"smiles_scaffold: out_width {out_width} has no column for <eos>")
-    shapes = ((n, out_width), (n, 2), (n, 4), (n, W))
-    dtypes = (torch.int64, torch.int64, torch.int32, torch.int32)
-    if out is None:
-        out = tuple(torch.empty(s, dtype=d, device=ys.device) for s, d in zip(shapes, dtypes))
-    else:
-        out = tuple(out)
-        if len(out) != 4:
-            raise ValueError("smiles_scaffold: out = (tokens, key, info, member)")
-        for name, t, s, d in zip(("tokens", "key", "info", "member"), out, shapes, dtypes):
-            _chk(t, f"smiles_scaffold.out {name}", d)
-            if tuple(t.shape) != s or not t.is_contiguous():
-                raise ValueError(f"smiles_scaffold: out must hold contiguous tensors {[list(x) for x in shapes]}, got "
-                                 f"{list(t.shape)} for {name}")
-    if n == 0:
-        return out
+        raise ValueError(f"{name}: out_width {out_width} has no column for <eos>")
+    out = _smiles_out(name, out, ys, tokens=((n, out_width), torch.int64), key=((n, 2), torch.int64),
+                      info=((n, 4), torch.int32), member=((n, W), torch.int32))
     tokens, key, info, member = out
-    check(_L().gct_smiles_scaffold(_p(ys), max(W, ys.stride(0)), W, n, _p(start), V, _p(table32), _p(label64),
-                                   _p(ring_ids), int(n_rings), int(open_id), int(close_id), int(pad_id), int(eos_id),
-                                   int(sep_id), int(n_id), int(nh_id), _p(tokens), out_width, _p(key), _p(info),
-                                   _p(member), _st()), "gct_smiles_scaffold")
+    if n:
+        check(_L().gct_smiles_scaffold(_p(ys), ld, W, n, _p(start), V, _p(table32), _p(label64), _p(ring_ids),
+                                       int(n_rings), int(open_id), int(close_id), int(pad_id), int(eos_id), int(sep_id),
+                                       int(n_id), int(nh_id), _p(tokens), out_width, _p(key), _p(info), _p(member),
+                                       _st()), "gct_smiles_scaffold")
     return out
 
 

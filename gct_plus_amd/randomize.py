@@ -16,7 +16,7 @@ from typing import NamedTuple
 import torch
 
 from . import ops
-from .decode import (G_END, GRAMMAR_START, SmilesGrammar, _CHEM_BOND_ORDERS, _int_vector, grammar_step)
+from .decode import SmilesGrammar, _CHEM_BOND_ORDERS, _int_vector, smiles_walk
 
 MAX_DEGREE = 8                       # bonds per atom a part may have (more: UNSUPPORTED)
 _M0, _M1, _W0, _W1, _M32 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85, 0xFFFFFFFF
@@ -108,54 +108,22 @@ class SmilesRandomizer:
         parse order.  unsupported: the part holds a DOT, a token the table marks, a ring closure `check` reports as
         RING_BOND (its ends state different orders, or the two atoms are bonded already; no bond is added), or a bond
         that would be some atom's ninth (not added)."""
-        g, V = self.grammar, len(self.grammar)
-        st = GRAMMAR_START
-        for t in list(tokens) + [self.eos_id]:
-            st = grammar_step(st, g.classes[t], g.rings[t]) if 0 <= int(t) < V else None
-            if st is None:
+        apos, bonds, lists, unsupported = [], [], [], False
+        for ev in smiles_walk(self.grammar, tokens, False):
+            if ev[0] == "syntax":
                 return None
-        assert st[0] == G_END
-        apos, bonds, lists, stack, open_rings, bonded = [], [], [], [], {}, set()
-        cur, pend, unsupported = None, None, False           # pend: (position, order) of a BOND token that waits
-
-        def link(a, b, sym):
-            nonlocal unsupported
-            bonded.add((a, b))
-            if len(lists[a]) >= MAX_DEGREE or len(lists[b]) >= MAX_DEGREE:
-                unsupported = True
-                return
-            lists[a].append(len(bonds)), lists[b].append(len(bonds))
-            bonds.append((a, b, sym))
-
-        for i, t in enumerate(tokens):
-            w = self.words[t]
-            c = w & 0xFF
-            unsupported |= bool((w >> 20) & 1) or c == ops.GRAMMAR_DOT
-            if c == ops.GRAMMAR_ATOM:
-                apos.append(i), lists.append([])
-                if cur is not None:
-                    link(cur, len(apos) - 1, pend[0] if pend else None)
-                cur, pend = len(apos) - 1, None
-            elif c == ops.GRAMMAR_BOND:
-                pend = (i, (w >> 16) & 7)
-            elif c == ops.GRAMMAR_OPEN:
-                stack.append(cur)
-            elif c == ops.GRAMMAR_CLOSE:
-                cur, pend = stack.pop(), None
-            elif c == ops.GRAMMAR_DOT:
-                cur, pend = None, None
-            elif c == ops.GRAMMAR_RING:
-                r = (w >> 8) & 63
-                if r in open_rings:
-                    a, first = open_rings.pop(r)
-                    if (first and pend and first[1] != pend[1]) or (a, cur) in bonded:
-                        unsupported = True
-                    else:
-                        link(a, cur, pend[0] if pend else first[0] if first else None)
+            if ev[0] == "atom":
+                apos.append(ev[1]), lists.append([])
+            elif ev[0] in ("bond", "ring"):
+                a, b, sym = ev[1], ev[2], ev[4]
+                if len(lists[a]) >= MAX_DEGREE or len(lists[b]) >= MAX_DEGREE:
+                    unsupported = True
                 else:
-                    open_rings[r] = (cur, pend)
-                pend = None
-        return apos, bonds, lists, unsupported
+                    lists[a].append(len(bonds)), lists[b].append(len(bonds))
+                    bonds.append((a, b, sym))
+            else:                                                # clash, dot
+                unsupported = True
+        return apos, bonds, lists, unsupported or any((self.words[t] >> 20) & 1 for t in tokens)
 
     def write_out(self, tokens, apos, bonds, lists, root):
         """Passes 1 and 2 of `randomize` on their own: the graph (apos, bonds, lists) of `parse`, one connected component,

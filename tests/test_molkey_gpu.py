@@ -106,6 +106,22 @@ def test_edges_of_the_lds_record(ops):
     assert empty.key.shape == (0, 2) and empty.info.shape == (0, 4)
 
 
+def test_sep_and_eos_in_every_slot_of_the_staged_row(ops):
+    """n = 5, W = 256, start 0: the <sep> in a lane's fourth slot (position 200), <sep> <eos> in the last two positions,
+    a <sep> at 255 with no <eos>, two <sep> (the first one counts) and a <sep> behind the <eos> (none counts)."""
+    ks, W, C = KEYS[True], 256, VOCAB.index("C")
+    ys = torch.full((5, W), C)
+    ys[0, 200], ys[0, 253:] = SEP, torch.tensor([EOS, PAD, PAD])
+    ys[1, 254], ys[1, 255] = SEP, EOS
+    ys[2, 255] = SEP
+    ys[3, 70], ys[3, 130], ys[3, 190:] = SEP, SEP, torch.tensor([EOS] + [PAD] * 65)
+    ys[4, 100], ys[4, 200] = EOS, SEP
+    want = ks.key_reference(ys, [0] * 5)
+    G, SY = _ops.KEY_GRAPH, _ops.KEY_STRING_SYNTAX
+    assert want.info.tolist() == [[G, G, 52, 51], [SY, G, 0, 0], [-1, -1, 0, 0], [SY, G, 0, 0], [G, -1, 100, 99]]
+    same(ks.key_rows(ys.cuda(), [0] * 5), want)
+
+
 def test_ids_outside_the_vocabulary(ops):
     """Ids outside [0, V) make a part SYNTAX; its string key tells them apart, as the host statement does."""
     ks, V, C = KEYS[True], len(VOCAB), VOCAB.index("C")
