@@ -979,10 +979,12 @@ int gct_step_stats(const float* logits, const float* probs, int V, const int64_t
  * through a pool of N items behind the shared counter *pos: the step unit is gct_decode_advance, the RAGGED step
  * kernels, gct_select_token(item, prefix_len) and then gct_stream_refill, which, when *enable != 0:
  *   1. finds the rows that FINISHED in the step just run: done[r] set, or the item has produced limit[item] tokens
- *      (generated so far = *pos - row_off[r] + 2 - prefix_len[item]); copies ys[r][0, width) to out_ys[item] and the
- *      generated length to out_len[item]; *n_harvested += their number;
- *   2. gives the finished rows and the empty ones (item[r] < 0) the items *next_item, *next_item + 1, ... in ASCENDING
- *      ROW ORDER; a row that finds the pool empty gets item -1 (parked).  row_of[item] = r, start_step[item] = *pos + 1;
+ *      (generated so far = *pos - row_off[r] + 2 - prefix_len[item]; a row still inside its prefix, generated <= 0, is
+ *      not finished, whatever done[r] says); copies ys[r][0, width) to out_ys[item] and the generated length to
+ *      out_len[item]; *n_harvested += their number;
+ *   2. gives the finished rows and the empty ones (item[r] < 0 or >= items) the items *next_item, *next_item + 1, ...
+ *      in ASCENDING ROW ORDER (*next_item stops at items); a row that finds the pool empty gets item -1 (parked).
+ *      row_of[item] = r, start_step[item] = *pos + 1;
  *   3. lays out each such row: row_off[r] = *pos + 1 (the next step consumes the row's token 0); with a new item
  *      z3 / src_valid / src_klen / ckv rows from the pools, ys[r][0, T) = the item's prefix then pad, valid[r] = the
  *      prefix's non-pad flags, done[r] = 0.  A parked row gets the offset only, at every call: it stays at position 0.
@@ -1035,7 +1037,8 @@ int gct_stream_refill(const GctStreamState* state, void* stream);
  * that token is chosen.  kv_src int32 [n*k][ld_src] maps beam r's logical position j to the physical row kv_src[r][j].
  * gct_attn_decode_beam: the device-position form of gct_attn_decode (pos required, no klen) where key / value j of row
  *   b and valid[.][j] are read from row kv_src[b][j] (clamped to [0, n)); this step's key / value are appended to row b.
- *   T = cache rows (<= 256, <= ld_src).
+ *   T = cache rows (<= 256, <= ld_src).  When the caches are full (cache_off + *pos >= T: no room for this step's key)
+ *   the call writes nothing: o and both caches stay as they are.
  * gct_beam_select: one workgroup per sample; p = *pos_dev + 1.  Candidates: live beam b offers scores[b] + logp_b(v)
  *   for every token v (logp = fp32 log-softmax of logits row b, x - m - log sum exp(x - m)); a finished beam offers
  *   itself once, token pad_id, score unchanged; a beam at -inf offers nothing.  The k best by score, ties to the lower
