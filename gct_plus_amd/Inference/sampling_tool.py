@@ -71,6 +71,11 @@ encode_smiles / score_smiles; the reference's randomize_smiles for callers.
 molecule (molkey.SmilesKeys, one launch) and with it the reference's valid / unique / novel figures on the device --
 `first_occurrence`, `MolKeyIndex` and Train/finetune.uniqueness_reward work on the same keys.
 
+`fingerprints(rows or smiles)` / `snn(rows, ref)` / `basic_metrics(rows, index, int_div=True)` (any sampler): a 1024-bit
+circular fingerprint per molecule (fingerprint.SmilesFingerprints, one launch) and the all-pairs Tanimoto figures over
+them (gct_fp_tanimoto): similarity to the nearest neighbour in a fingerprint.FingerprintIndex, and `intDiv`, which
+completes the reference's get_basic_metrics; Train/finetune.similarity_reward reads the same aggregates.
+
 `murcko_scaffolds(rows or smiles)` (any sampler) / `scaffold_report(rows)` (a scaffold model): the Murcko scaffold of
 every molecule -- key, spelling and kept atoms (scaffold.SmilesScaffolds, one launch, no rdkit) -- and, for rows that read
 <sos> scaffold <sep> molecule <eos>, whether the molecule has the scaffold it was given: molkey.scaffold_metrics'
@@ -108,6 +113,7 @@ from ..decode import (BEAM_ALPHA, ChemReport, KVDecoder, Marginal, PolicyTerms, 
                       SmilesGrammar, check_beam_size, check_ess_threshold, check_grammar, check_particles,
                       check_sample_filter, check_stream_model, check_stream_rows, generated_tokens, marginal_logp,
                       score_tokens, sequence_logp, sequence_policy, sequence_ppo)
+from ..fingerprint import FpRows, SmilesFingerprints, snn as fp_snn
 from ..molkey import MolKeys, SmilesKeys, basic_metrics
 from ..scaffold import ScaffoldRows, SmilesScaffolds
 from ..randomize import SmilesRandomizer
@@ -258,6 +264,7 @@ class Sampling:
         self._randomizer = None
         self._keys = None
         self._scaffolds = None
+        self._fingerprinter = None
 
     # ---- chemical validity of decoded rows (decode.SmilesChemistry: a check behind the decode, not a constraint on it)
     @property
@@ -368,11 +375,42 @@ class Sampling:
         ys = torch.tensor([r + [self.pad_id] * (W - len(r)) for r in ids], dtype=torch.int64).view(n, W)
         return self.keys.key_rows(ys.to(self.device), torch.zeros(n, dtype=torch.int64))
 
-    def basic_metrics(self, rows, index=None) -> dict:
+    def basic_metrics(self, rows, index=None, int_div=False) -> dict:
         """valid / unique / novel of decoded rows (molkey.basic_metrics, moses' definitions): check_rows, molecule_keys
         and the counting on the device, one read-back for the dict.  index: a molkey.MolKeyIndex of the training set
-        (without one there is no `novel`)."""
-        return basic_metrics(self.check_rows(rows), self.molecule_keys(rows), index)
+        (without one there is no `novel`).  int_div=True adds `intDiv`, moses' internal diversity over the valid rows
+        (fingerprint.internal_diversity: one gct_smiles_fp and one gct_fp_tanimoto launch more), and n_fp, the valid
+        rows that have a fingerprint -- the fourth figure of the reference's get_basic_metrics."""
+        return basic_metrics(self.check_rows(rows), self.molecule_keys(rows), index,
+                             self.fingerprints(rows) if int_div else None)
+
+    # ---- fingerprints and Tanimoto figures (fingerprint.SmilesFingerprints: intDiv and SNN without moses or rdkit)
+    @property
+    def fingerprinter(self) -> SmilesFingerprints:
+        """The SmilesFingerprints over the target vocabulary, next to self.keys, built on first use."""
+        if self._fingerprinter is None:
+            self._fingerprinter = SmilesFingerprints(self.TRG.itos, self.pad_id, self.eos_id, self.sep_id, keys=self.keys)
+        return self._fingerprinter
+
+    def fingerprints(self, rows) -> FpRows:
+        """1024-bit circular fingerprints on the sampler's device, one launch: `rows` a DecodedRows or (ys, prefix_lens)
+        -- the span behind a row's prefix is read as molecule_keys reads it, and of `scaffold <sep> molecule` the
+        molecule is fingerprinted -- or SMILES strings.  FpRows(bits int64 [n, 16], info int32 [n, 4] = (ops.FP_* status,
+        bits set, atoms, bonds)); a part with a stereo mark, a dot or bad syntax has no bit."""
+        if isinstance(rows, DecodedRows):
+            return self.fingerprinter.fp_rows(rows.ys, rows.prefix_lens)
+        if isinstance(rows, tuple) and len(rows) == 2 and torch.is_tensor(rows[0]):
+            return self.fingerprinter.fp_rows(*rows)
+        ids = [self.smi_to_id(s, add_eos=True) for s in rows]
+        n, W = len(ids), max((len(r) for r in ids), default=1)
+        ys = torch.tensor([r + [self.pad_id] * (W - len(r)) for r in ids], dtype=torch.int64).view(n, W)
+        return self.fingerprinter.fp_rows(ys.to(self.device), torch.zeros(n, dtype=torch.int64))
+
+    def snn(self, rows, ref) -> float:
+        """Similarity to the nearest neighbour (the reference's get_snn_from_mol): the mean over the rows that have a
+        fingerprint of the largest Tanimoto similarity to `ref`, a fingerprint.FingerprintIndex (of a training set) or
+        an FpRows.  `rows` as `fingerprints` takes them, or an FpRows.  0.0 if either side is empty.  One read-back."""
+        return fp_snn(rows if isinstance(rows, FpRows) else self.fingerprints(rows), ref)
 
     # ---- Murcko scaffolds (scaffold.SmilesScaffolds: the reference's murcko_scaffold and scaffold filter, no rdkit)
     @property

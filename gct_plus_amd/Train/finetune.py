@@ -164,6 +164,20 @@ def scaffold_reward(sca):
     return scaffold_match(sca).float()
 
 
+def similarity_reward(agg_or_best, lo=0.0, hi=1.0):
+    """One reward per row from its largest Tanimoto similarity to a target set (a fingerprint.TanimotoAgg of
+    tanimoto_agg(rows, targets), or its `best`, or FingerprintIndex.nearest's): fp32 [n] on the rows' device, no graph
+    and no synchronisation -- to multiply into validity_reward.  `best` clamped to [lo, hi] and rescaled to [0, 1]: 0 up
+    to lo, 1 from hi on, linear between.  A row without a fingerprint has best 0.  ValueError unless 0 <= lo < hi <= 1."""
+    lo, hi = float(lo), float(hi)
+    if not 0.0 <= lo < hi <= 1.0:
+        raise ValueError(f"similarity_reward: 0 <= lo < hi <= 1, got lo = {lo}, hi = {hi}")
+    best = agg_or_best.best if hasattr(agg_or_best, "best") else torch.as_tensor(agg_or_best)
+    if best.dim() != 1 or not best.dtype.is_floating_point:
+        raise ValueError(f"similarity_reward: best must be a floating-point vector [n], got {best.dtype} {list(best.shape)}")
+    return ((best.detach().float().clamp(lo, hi) - lo) / (hi - lo))
+
+
 def _check_weight(weight, n, what):
     """weight [n] of reinforce_step / ppo_update as an fp32 vector without a graph; ValueError for another length or a
     value that is negative or not finite."""

@@ -352,15 +352,19 @@ class MolKeyIndex:
         return mine[at] == k
 
 
-def basic_metrics(report: ChemReport, keys, index=None):
-    """The reference's get_basic_metrics figures that need no fingerprints, with moses' definitions: valid = the share of
-    rows whose ChemReport status is OK; unique = distinct keys among the valid rows / valid rows; novel (only with an
-    index) = the share of those distinct keys that the index does not hold; 0 for an empty denominator.  Also the
-    counts n, n_valid, n_unique (and n_novel).  Everything is computed on the keys' device; one read-back."""
+def basic_metrics(report: ChemReport, keys, index=None, fps=None):
+    """The reference's get_basic_metrics figures, with moses' definitions: valid = the share of rows whose ChemReport
+    status is OK; unique = distinct keys among the valid rows / valid rows; novel (only with an index) = the share of
+    those distinct keys that the index does not hold; 0 for an empty denominator.  Also the counts n, n_valid, n_unique
+    (and n_novel).  Everything is computed on the keys' device; one read-back.  fps (a fingerprint.FpRows of the same
+    rows) adds intDiv = fingerprint.internal_diversity over the valid rows and n_fp, the valid rows that have a
+    fingerprint, with a read-back of their own; without it the dict is what it was before there were fingerprints."""
     k = _molecule_column(keys)
     ok = (report.status == ops.CHEM_OK).to(k.device)
     if ok.shape != k.shape:
         raise ValueError(f"{ok.numel()} report rows for {k.numel()} keys")
+    if fps is not None and fps.bits.shape[0] != k.numel():
+        raise ValueError(f"{fps.bits.shape[0]} fingerprints for {k.numel()} keys")
     first = first_occurrence(k, valid=ok)
     counts = [ok.sum(), first.sum()]
     if index is not None:
@@ -373,6 +377,11 @@ def basic_metrics(report: ChemReport, keys, index=None):
     out.update(n=n, n_valid=n_valid, n_unique=n_unique)
     if index is not None:
         out["n_novel"] = counts[2]
+    if fps is not None:
+        from .fingerprint import _diversity_terms
+        s, n_fp = _diversity_terms(fps, ok.to(fps.bits.device), 1).tolist()
+        out["intDiv"] = 1.0 - s / n_fp if n_fp else 0.0
+        out["n_fp"] = int(n_fp)
     return out
 
 

@@ -1586,6 +1586,77 @@ def smiles_scaffold(ys, start, table32, label64, ring_ids, n_rings, open_id, clo
     return out
 
 
+# status codes of the circular fingerprints (GCT_FP_* of include/gctplus_hip.h), their radius and their width in bits
+FP_GRAPH, FP_SYNTAX, FP_UNSUPPORTED = range(3)
+FP_RADIUS = 2
+FP_BITS = 1024
+FP_WORDS = FP_BITS // 64
+FP_MAX_SPAN = 256
+
+
+def smiles_fp(ys, start, table32, label64, pad_id, eos_id, sep_id, out=None):
+    """gct_smiles_fp: the FP_BITS-bit circular fingerprint of the molecule in every row's span ys[r, start[r]:] -- behind
+    a <sep> if there is one (fingerprint.SmilesFingerprints.fp_reference is the statement).  ys int64 [n, W] with unit
+    column stride, start int32 [n] on the device, table32 int32 [V] and label64 int64 [V] (SmilesKeys.device_tables),
+    sep_id -1 for none.  Returns (bits int64 [n, 16], info int32 [n, 4] = (status, bits set, atoms, bonds)), freshly
+    allocated or the contiguous tensors of out = (bits, info).  One launch."""
+    n, W, ld = _smiles_rows("smiles_fp", ys, start=(start, torch.int32))
+    V = _smiles_tables("smiles_fp", table32=(table32, torch.int32), label64=(label64, torch.int64))
+    _smiles_ids("smiles_fp", V, dict(pad_id=pad_id, eos_id=eos_id), dict(sep_id=sep_id))
+    bits, info = _smiles_out("smiles_fp", out, ys, bits=((n, FP_WORDS), torch.int64), info=((n, 4), torch.int32))
+    if n:
+        check(_L().gct_smiles_fp(_p(ys), ld, W, n, _p(start), V, _p(table32), _p(label64), int(pad_id), int(eos_id),
+                                 int(sep_id), _p(bits), _p(info), _st()), "gct_smiles_fp")
+    return bits, info
+
+
+def fp_tanimoto_plan(n, m):
+    """(tile_b, splits) of gct_fp_tanimoto for n rows of a against m rows of b: b is walked in tiles of tile_b rows, in
+    `splits` independent parts whose partials a second launch folds.  A function of (n, m) alone, never of the device."""
+    if int(n) < 0 or int(m) < 0:
+        raise ValueError(f"fp_tanimoto_plan: n = {n}, m = {m}")
+    return _L().gct_fp_tanimoto_tile_b(), _L().gct_fp_tanimoto_splits(int(n), int(m))
+
+
+def _fp_rows(name, what, bits, cnt):
+    _chk(bits, f"{name}.{what}", torch.int64)
+    _chk(cnt, f"{name}.cnt_{what}", torch.int32)
+    if bits.dim() != 2 or bits.shape[1] != FP_WORDS or bits.stride(1) != 1 or (bits.shape[0] > 1 and bits.stride(0) < FP_WORDS):
+        raise ValueError(f"{name}: {what} int64 [rows, {FP_WORDS}] with unit column stride and a row stride of at least "
+                         f"{FP_WORDS}, got {list(bits.shape)} with strides {list(bits.stride())}")
+    if cnt.dim() != 1 or cnt.numel() != bits.shape[0] or not cnt.is_contiguous():
+        raise ValueError(f"{name}: cnt_{what} must be a contiguous tensor [{bits.shape[0]}], got {list(cnt.shape)}")
+    if cnt.device != bits.device:
+        raise ValueError(f"{name}: {what} and cnt_{what} are on different devices")
+    return bits.shape[0], max(FP_WORDS, bits.stride(0))
+
+
+def fp_tanimoto(a, cnt_a, b, cnt_b, p=1, out=None):
+    """gct_fp_tanimoto: for every row of a, over the present rows of b (fingerprint.tanimoto_reference is the statement),
+    (best fp32 [n] = the largest Tanimoto similarity, arg int32 [n] = the lowest row of b that attains it, total fp64 [n]
+    = the sum of T^p, p 1 or 2).  a int64 [n, 16], b int64 [m, 16]: smiles_fp's words, unit column stride, any row
+    stride of at least 16; cnt_a, cnt_b int32: their numbers of set bits, 0 for an absent row.  An absent row of a, and
+    every row when no row of b is present: (0, -1, 0).  Freshly allocated or the contiguous tensors of
+    out = (best, arg, total).  One launch, two when fp_tanimoto_plan(n, m) has more than one split."""
+    name = "fp_tanimoto"
+    n, lda = _fp_rows(name, "a", a, cnt_a)
+    m, ldb = _fp_rows(name, "b", b, cnt_b)
+    if b.device != a.device:
+        raise ValueError(f"{name}: a and b are on different devices")
+    if int(p) not in (1, 2):
+        raise ValueError(f"{name}: p must be 1 or 2, got {p}")
+    if m > 1 << 30:
+        raise ValueError(f"{name}: {m} rows of b, at most 2^30")
+    best, arg, total = _smiles_out(name, out, a, best=((n,), torch.float32), arg=((n,), torch.int32),
+                                   total=((n,), torch.float64))
+    if n:
+        nbytes = _L().gct_fp_tanimoto_ws_bytes(n, m)
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=a.device) if nbytes else None
+        check(_L().gct_fp_tanimoto(_p(a), lda, _p(cnt_a), n, _p(b), ldb, _p(cnt_b), m, int(p), _p(ws), nbytes, _p(best),
+                                   _p(arg), _p(total), _st()), "gct_fp_tanimoto")
+    return best, arg, total
+
+
 def _seq_geometry(name, logits2d, ys, rows_per_seq, V, prefix_lens, prior2d=None):
     """The checks every seq_* wrapper makes on (ys, logits, prefix_lens), with seq_dist's prior logits next to the
     agent's: (n, W, R, V, ld, ld_prior).  `name` (the caller's) opens every message, here and in the helpers below."""

@@ -957,6 +957,44 @@ int gct_smiles_scaffold(const int64_t* ys, int64_t ld_ys, int W, int n, const in
                         int close_id, int pad_id, int eos_id, int sep_id, int n_id, int nh_id, int64_t* tokens_out,
                         int out_width, int64_t* key_out, int32_t* info_out, int32_t* member_out, void* stream);
 
+/* Circular fingerprints (gct_plus_amd/fingerprint.py SmilesFingerprints states the rules: `fingerprint` for one part,
+ * fp_reference for a batch): GCT_FP_BITS bits of the labelled graph that gct_smiles_randomize's parse reads from row r's
+ * span ys[r][start[r], W), one wave per row.  Spans, <eos>, <sep>, table32 and label64: as in gct_smiles_key; with a
+ * <sep> the molecule behind it is fingerprinted, the part in front of it is not.
+ * A part with a graph (status GRAPH): id_0(a) = mix(label(a) ^ mix(0x200 + bonds of a)), GCT_FP_RADIUS rounds of
+ * gct_smiles_key's bond-labelled refinement, and for every round 0 .. GCT_FP_RADIUS and atom the bit id mod GCT_FP_BITS.
+ * A part without one -- it does not parse (SYNTAX) or the randomiser would report UNSUPPORTED -- has no bit set.
+ * bits_out int64 [n][GCT_FP_BITS / 64]: word w holds bits 64 w .. 64 w + 63, bit k at 1 << (k & 63).  info_out int32
+ * [n][4] = (status, number of bits set, atoms, bonds).  A span without <eos>, W - start[r] > 256 or start[r] outside
+ * [0, W]: no bit, info (-1, 0, 0, 0).  n = 0 is a no-op.  No global atomics, no scratch. */
+#define GCT_FP_GRAPH 0
+#define GCT_FP_SYNTAX 1
+#define GCT_FP_UNSUPPORTED 2
+#define GCT_FP_RADIUS 2
+#define GCT_FP_BITS 1024
+int gct_smiles_fp(const int64_t* ys, int64_t ld_ys, int W, int n, const int32_t* start, int V, const int32_t* table32,
+                  const int64_t* label64, int pad_id, int eos_id, int sep_id, int64_t* bits_out, int32_t* info_out,
+                  void* stream);
+
+/* Tanimoto aggregates of every row of a against all rows of b (fingerprint.py tanimoto_reference states the rule).
+ * a int64 [n][lda >= 16], b int64 [m][ldb >= 16]: gct_smiles_fp's words; cnt_a int32 [n], cnt_b int32 [m]: their
+ * numbers of set bits (0: the row is absent).  For a pair, c = popcount(a_i & b_j), u = cnt_a[i] + cnt_b[j] - c and
+ * T = (float)c / (float)u, correctly rounded.  Per row i of a, over the present rows j of b:
+ *   best_out float [n]    the largest T, decided by integer cross-multiplication (exact);
+ *   arg_out int32 [n]     the LOWEST j that attains it;
+ *   total_out double [n]  the sum of T (p = 1) or of the fp64 product T * T (p = 2), every term exact in fp64.
+ * An absent row of a, and every row when no row of b is present (m = 0 included): (0, -1, 0).
+ * The grid is (tiles of 256 rows of a) x gct_fp_tanimoto_splits(n, m) splits of b in tiles of gct_fp_tanimoto_tile_b()
+ * rows; with more than one split, ws (8-byte aligned, ws_bytes >= gct_fp_tanimoto_ws_bytes(n, m); otherwise it may be
+ * NULL) takes the partials and a second launch folds them in split order.  The split count is a function of (n, m)
+ * alone, so the bits of total_out do not depend on the device.  m <= 2^30.  n = 0 is a no-op.  No atomics. */
+int gct_fp_tanimoto_tile_b(void);
+int gct_fp_tanimoto_splits(int n, int m);
+int64_t gct_fp_tanimoto_ws_bytes(int n, int m);
+int gct_fp_tanimoto(const int64_t* a, int64_t lda, const int32_t* cnt_a, int n, const int64_t* b, int64_t ldb,
+                    const int32_t* cnt_b, int m, int p, void* ws, int64_t ws_bytes, float* best_out, int32_t* arg_out,
+                    double* total_out, void* stream);
+
 /* Per-step sampling statistics (gct_plus_amd/decode.py step_stats_reference states the rules).  Launched behind
  * gct_select_token in the step unit, on the same device counter and with gct_chosen_logp's row rule: row r looks at
  * column p = *pos - row_off[r] + 1, takes tok = ys[r][p] and writes each non-null table at out[dst][p].

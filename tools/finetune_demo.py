@@ -24,6 +24,10 @@ one launch on the device instead of the Python loop over the rows; the printed r
 distinct strings -- Sampling.molecule_keys and molkey.first_occurrence, on the device: a policy that writes one molecule
 in five spellings counts once.
 
+--report-diversity: one more line at the end: the INTERNAL DIVERSITY (moses' intDiv: 1 - the mean Tanimoto similarity of
+all pairs, self pairs included) of the rows of the evaluation batch that have a fingerprint, before and after --
+Sampling.fingerprints and fingerprint.internal_diversity, on the device: a collapsed policy falls towards 0.
+
 --report-scaffold: one more line at the end: same_scaffold of the evaluation batch before and after -- the share of its
 chemically valid rows whose molecule has the Murcko scaffold the row was given (Sampling.scaffold_report and
 molkey.scaffold_metrics, on the device; Train/finetune.scaffold_reward is the same verdict as a reward).
@@ -62,6 +66,8 @@ ap.add_argument("--report-valid", action="store_true",
                 help="one more line at the end: the chemically valid share of the evaluation batch before and after")
 ap.add_argument("--report-unique", action="store_true",
                 help="one more line at the end: distinct molecules (molecule keys) beside the distinct strings")
+ap.add_argument("--report-diversity", action="store_true",
+                help="one more line at the end: the internal diversity (intDiv) of the evaluation batch before and after")
 ap.add_argument("--report-scaffold", action="store_true",
                 help="one more line at the end: the share of valid rows that have the scaffold they were given")
 ap.add_argument("--time-step", action="store_true",
@@ -73,6 +79,7 @@ import torch  # noqa: E402
 
 from gct_plus_amd import data, synthetic  # noqa: E402
 from gct_plus_amd.decode import SmilesGrammar  # noqa: E402
+from gct_plus_amd.fingerprint import internal_diversity  # noqa: E402
 from gct_plus_amd.Inference.sampling_tool import DecodedRows, PscavaetfSampling  # noqa: E402
 from gct_plus_amd.Model import model_dict  # noqa: E402
 from gct_plus_amd.molkey import first_occurrence, scaffold_metrics  # noqa: E402
@@ -188,6 +195,9 @@ def evaluate():
     if a.report_unique:
         mk = sampler.molecule_keys(rows)
         MOLECULES.append(int(first_occurrence(mk, valid=mk.info[:, 0] >= 0).sum()))
+    if a.report_diversity:
+        fps = sampler.fingerprints(rows)
+        DIVERSITY.append((internal_diversity(fps), int((fps.info[:, 1] > 0).sum())))
     if a.report_scaffold:
         SAME_SCAFFOLD.append(scaffold_metrics(sampler.check_rows(rows), sampler.scaffold_report(rows)))
     return float(reward.mean()), distinct, float(terms.entropy.sum() / terms.tokens.sum())
@@ -197,6 +207,7 @@ EVAL_SEED = 10 ** 6
 VALID_SHARE = []
 MOLECULES = []
 SAME_SCAFFOLD = []
+DIVERSITY = []
 before = evaluate()
 reg = f", entropy_coef {a.entropy_coef}, kl_coef {a.kl_coef}" if a.entropy_coef or a.kl_coef else ""
 if a.ppo_epochs:
@@ -237,6 +248,10 @@ if a.report_unique:
     print(f"distinct molecules of the evaluation batch (molkey.SmilesKeys; a row without a graph counts as its string, one without "
           f"<eos> not at all): "
           f"{MOLECULES[0]} -> {MOLECULES[1]}, beside distinct strings {before[1]} -> {after[1]}")
+if a.report_diversity:
+    (b, nb), (c, nc) = DIVERSITY
+    print(f"internal diversity of the evaluation batch (fingerprint.SmilesFingerprints; intDiv over the rows that have a "
+          f"fingerprint): {b:.4f} -> {c:.4f} ({nb} -> {nc} rows)")
 if a.report_scaffold:
     b, c = SAME_SCAFFOLD
     print(f"same_scaffold of the evaluation batch (scaffold.SmilesScaffolds; valid rows whose Murcko scaffold is {a.scaffold}): "

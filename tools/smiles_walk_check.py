@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""The host-callable parts of gct_smiles_check / _randomize / _key / _scaffold on the CPU under AddressSanitizer and
-UBSan (no GPU needed): builds tools/smiles_walk_host.hip -- a stand-alone program around the parse
-(csrc/smiles_graph.h), the check's walk and verdict (csrc/chem.hip), the list shuffle and the write-out
-(csrc/smiles_walk.h), the key functions (csrc/smiles_key.h) and the peel, marks and compaction of csrc/scaffold.hip, the
-host code sanitised -- into tools/_build/ and runs it once per mode (--modes) over ROWS: molecules, kept rows, rows with
+"""The host-callable parts of gct_smiles_check / _randomize / _key / _scaffold / _fp and gct_fp_tanimoto on the CPU
+under AddressSanitizer and UBSan (no GPU needed): builds tools/smiles_walk_host.hip -- a stand-alone program around the
+parse (csrc/smiles_graph.h), the check's walk and verdict (csrc/chem.hip), the list shuffle and the write-out
+(csrc/smiles_walk.h), the key functions (csrc/smiles_key.h), the peel, marks and compaction of csrc/scaffold.hip and the
+fingerprint and Tanimoto functions (csrc/smiles_fp.h), the host code sanitised -- into tools/_build/ and runs it once per
+mode (--modes) over ROWS: molecules, kept rows, rows with
 scaffolds, shells and [nH] substitutions, and the rows that fill the kernels' LDS records to their ends (chains of 63 ..
 255, a ring of 253 atoms, branch depth 83 with and without a ring at the bottom, 84 branches on one atom, atoms with 8
 and 9 bonds, 40 rings open at once).
@@ -14,6 +15,10 @@ and 9 bonds, 40 rings open at once).
   key        every row and --spellings random spellings of it; against SmilesKeys
   scaffold   the same, every row with an `n` once more without an [nH] token, and every row with too little room;
              against SmilesScaffolds.scaffold
+  fingerprint every row and --spellings random spellings of it; against SmilesFingerprints.fingerprint
+  tanimoto   the pair, tile and fold functions on random fingerprints at three bit densities, with absent rows, rows
+             of all 1024 bits and duplicates, for p = 1 and 2, in tiles and splits of several sizes (a few hundred
+             pairs per case); against tanimoto_reference: best and arg exactly, total within m * 2^-53 * total
 Exit status 1 for a sanitizer report or a line that differs."""
 import argparse
 import collections
@@ -28,11 +33,12 @@ sys.path.insert(0, ROOT)
 
 from gct_plus_amd import ops, synthetic  # noqa: E402
 from gct_plus_amd.decode import SmilesChemistry  # noqa: E402
+from gct_plus_amd.fingerprint import FpRows, SmilesFingerprints, tanimoto_reference  # noqa: E402
 from gct_plus_amd.molkey import as_int64  # noqa: E402
 from gct_plus_amd.randomize import SmilesRandomizer, stream  # noqa: E402
 from gct_plus_amd.scaffold import SmilesScaffolds  # noqa: E402
 
-MODES = ("check", "randomize", "key", "scaffold")
+MODES = ("check", "randomize", "key", "scaffold", "fingerprint", "tanimoto")
 ap = argparse.ArgumentParser()
 ap.add_argument("--modes", nargs="+", choices=MODES, default=list(MODES))
 ap.add_argument("--keys", type=int, default=40)
@@ -164,6 +170,67 @@ def mode_scaffold():
     return cases, lines, want, names
 
 
+def mode_fingerprint():
+    fs = SmilesFingerprints(V, PAD, EOS, keys=ks)
+    cases = [t for s in ROWS for t in spellings(ids(s))]
+
+    def want(toks, got):
+        status, words, atoms, bonds = fs._part(toks)
+        return [int(x) for x in got] == [status, atoms, bonds] + words, status
+    names = {getattr(ops, n): n[3:] for n in ("FP_GRAPH", "FP_SYNTAX", "FP_UNSUPPORTED")}
+    return (cases, lambda toks: [[len(toks)], [ks.words[t] & 0xFFFFFF for t in toks], [ks.labels[t] for t in toks]], want,
+            names)
+
+
+def mode_tanimoto():
+    import struct
+    import torch
+    rng = random.Random(5)
+
+    def rows(n):
+        """n fingerprints as lists of 32 words of 32 bits: densities 1/64, 1/8 and 1/2, row 1 full, row 2 absent, row 3
+        a copy of row 0."""
+        out = []
+        for r in range(n):
+            x = [rng.getrandbits(32) for _ in range(32)]
+            for _ in range((5, 2, 0)[r % 3]):
+                x = [w & rng.getrandbits(32) for w in x]
+            out.append(x)
+        if n >= 4:
+            out[1], out[2], out[3] = [0xFFFFFFFF] * 32, [0] * 32, list(out[0])
+        return out
+
+    def fps(words):
+        bits = torch.tensor([[(r[2 * k] | r[2 * k + 1] << 32) - ((r[2 * k + 1] >> 31) << 64) for k in range(16)] for r in words],
+                            dtype=torch.int64).view(len(words), 16)
+        info = torch.zeros(len(words), 4, dtype=torch.int32)
+        info[:, 1] = torch.tensor([sum(bin(w).count("1") for w in r) for r in words], dtype=torch.int32)
+        return FpRows(bits, info)
+
+    cases = []                                                    # (a, b, p, tile, tiles per split)
+    for na, nb, tile, tps in ((5, 9, 4, 1), (7, 33, 8, 2), (12, 40, 16, 1), (1, 1, 4, 1), (3, 0, 4, 1), (0, 5, 4, 1),
+                              (9, 31, 32, 1), (6, 64, 5, 3), (16, 25, 128, 1), (4, 130, 128, 1)):
+        for p in (1, 2):
+            cases.append((rows(na), rows(nb), p, tile, tps))
+    cases.append((rows(6), [[0] * 32] * 7, 1, 4, 1))              # no row of b is present
+
+    def lines(case):
+        a, b, p, tile, tps = case
+        return [[len(a), len(b), p, tile, tps]] + [[sum(bin(w).count("1") for w in r)] + r for r in a + b]
+
+    def want(case, got):
+        a, b, p, tile, tps = case
+        ref = tanimoto_reference(fps(a), fps(b), p)
+        same = len(got) == 3 * len(a)
+        for i in range(len(a) if same else 0):
+            best = struct.unpack("f", struct.pack("I", int(got[3 * i])))[0]
+            total = struct.unpack("d", struct.pack("Q", int(got[3 * i + 2])))[0]
+            same &= best == ref.best[i].item() and int(got[3 * i + 1]) == ref.arg[i].item()
+            same &= abs(total - ref.total[i].item()) <= len(b) * 2.0 ** -53 * ref.total[i].item()
+        return same, p
+    return cases, lines, want, {1: "p = 1:", 2: "p = 2:"}
+
+
 build = os.path.join(ROOT, "tools", "_build")
 os.makedirs(build, exist_ok=True)
 exe = os.path.join(build, "smiles_walk_host")
@@ -189,6 +256,7 @@ for mode in a.modes:
     bad, seen = 0, collections.Counter()
     for case, line in zip(cases, out):
         same, status = want(case, line.split())
+        same = bool(same)
         seen[status] += 1
         if not same:
             bad += 1

@@ -1,8 +1,9 @@
-// CPU harness of the host-callable parts of the four SMILES kernels (tools/smiles_walk_check.py builds and drives it):
+// CPU harness of the host-callable parts of the SMILES kernels (tools/smiles_walk_check.py builds and drives it):
 // rand_parse of csrc/smiles_graph.h, the check's walk and verdict (csrc/chem.hip), rand_shuffle_atom and
-// rand_walk (csrc/smiles_walk.h), the per-atom key functions (csrc/smiles_key.h) and sca_peel / sca_shell / sca_nh /
-// sca_compact (csrc/scaffold.hip) run on the HOST over one LDS record per case, bond by bond and atom by atom as the
-// kernels' lanes do, so that AddressSanitizer and UBSan see every index they form -- the scaffold's aliased walk buffers
+// rand_walk (csrc/smiles_walk.h), the per-atom key functions (csrc/smiles_key.h), sca_peel / sca_shell / sca_nh /
+// sca_compact (csrc/scaffold.hip) and the fingerprint and Tanimoto functions (csrc/smiles_fp.h) run on the HOST over one
+// LDS record per case, bond by bond and atom by atom as the kernels' lanes do, so that AddressSanitizer and UBSan see
+// every index they form -- the scaffold's aliased walk buffers, the fingerprint's labels in its second identifier buffer
 // and reused parse fields included.  No GPU is touched.  Usage: smiles_walk_host MODE FILE; the file holds the count and
 // then per case, by mode,
 //   check      L / L staged words
@@ -10,17 +11,23 @@
 //   key        L / L table words / L token labels (unsigned 64-bit)
 //   scaffold   L n_rings open_id close_id room nh_id nh_word / nh_label / L table words (| 1 << 25 on `n`) / L token
 //              labels / n_rings ring ids
+//   fingerprint L / L table words / L token labels (unsigned 64-bit)
+//   tanimoto   na nb p tile tiles_per_split / na + nb rows: count and 32 words of 32 bits
 // and one line goes out per case:
 //   check      status position atoms ring_bonds
 //   randomize  status, and for a rewritten part the length, the row's LDS entries | perm
 //   key        status key (unsigned) atoms bonds
 //   scaffold   status key atoms-kept length | the row's entries | member per input atom
+//   fingerprint status atoms bonds and the 16 words (unsigned 64-bit)
+//   tanimoto   per row of a: best (the fp32's bits) arg total (the fp64's bits)
 // (an entry is a literal id, or -(j + 1) for the token at position j).
 #include "../gct_plus_amd/csrc/chem.hip"
 #include "../gct_plus_amd/csrc/randomize.hip"
 #include "../gct_plus_amd/csrc/molkey.hip"
 #include "../gct_plus_amd/csrc/scaffold.hip"
+#include "../gct_plus_amd/csrc/fingerprint.hip"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -186,6 +193,81 @@ static void run_scaffold(ScaWave* w) {
   printf("\n");
 }
 
+static void run_fingerprint(FpWave* w) {                     // smiles_fp_kernel, atom by atom
+  const int L = rd_in(0, 255);
+  fresh(w, L);
+  for (int i = 0; i < L; ++i) w->col[1][i] = rdu();
+  for (int k = 0; k < kFpWords; ++k) w->bits[k] = 0;         // (the kernel clears them in front of the staging)
+  int A, nb;
+  bool unsup;
+  const bool parsed = rand_parse(*w, 0, L, A, nb, unsup);
+  const int status = !parsed ? GCT_FP_SYNTAX : unsup ? GCT_FP_UNSUPPORTED : GCT_FP_GRAPH;
+  if (status == GCT_FP_GRAPH) {
+    for (int e = 0; e < nb; ++e) w->blab[e] = (uint8_t)key_bond_label(*w, e);
+    for (int a = 0; a < A; ++a) {
+      const uint64_t id = fp_id0(*w, a);
+      w->col[0][a] = id;
+      fp_mark(*w, id);
+    }
+    memset((void*)w->col[1], 0xCD, sizeof(w->col[1]));       // every label is read: the first round overwrites them
+    for (int r = 0; r < GCT_FP_RADIUS; ++r)
+      for (int a = 0; a < A; ++a) {
+        const uint64_t id = key_refine(*w, w->col[r & 1], a);
+        w->col[(r + 1) & 1][a] = id;
+        fp_mark(*w, id);
+      }
+  }
+  printf("%d %d %d", status, A, nb);
+  for (int k = 0; k < kFpWords; k += 2)
+    printf(" %llu", (unsigned long long)((uint64_t)w->bits[k] | ((uint64_t)w->bits[k + 1] << 32)));
+  printf("\n");
+}
+
+struct TaniCase {};                                          // (no record: the vectors below are the case's memory)
+
+static void run_tanimoto(TaniCase*) {                        // tani_kernel's walk of one row of a, and tani_fold
+  const int na = rd_in(0, 4096), nb = rd_in(0, 4096), p = rd_in(1, 2), tile = rd_in(1, 4096), tps = rd_in(1, 4096);
+  std::vector<int32_t> ca((size_t)na), cb((size_t)nb);
+  std::vector<uint32_t> wa((size_t)na * kFpWords), wb((size_t)nb * kFpWords);
+  for (int i = 0; i < na; ++i) {
+    ca[i] = rd_in(0, GCT_FP_BITS);
+    for (int k = 0; k < kFpWords; ++k) wa[(size_t)i * kFpWords + k] = (uint32_t)rdu();
+  }
+  for (int j = 0; j < nb; ++j) {
+    cb[j] = rd_in(0, GCT_FP_BITS);
+    for (int k = 0; k < kFpWords; ++k) wb[(size_t)j * kFpWords + k] = (uint32_t)rdu();
+  }
+  const int tiles = (nb + tile - 1) / tile, splits = tiles ? (tiles + tps - 1) / tps : 1;
+  std::vector<int32_t> pc((size_t)splits), pu((size_t)splits), pj((size_t)splits);
+  std::vector<double> pt((size_t)splits);
+  for (int i = 0; i < na; ++i) {
+    for (int s = 0; s < splits; ++s) {
+      TaniBest best = tani_none();
+      double total = 0.0;
+      const int first = s * tps * tile, end = std::min(nb, first + tps * tile);
+      for (int jb = first; jb < end; jb += tile) {           // a tile as the kernel stages it: its own copy, exactly as long
+        const int rows = std::min(tile, end - jb);
+        std::vector<uint32_t> sb(wb.begin() + (size_t)jb * kFpWords, wb.begin() + (size_t)(jb + rows) * kFpWords);
+        std::vector<int32_t> sc(cb.begin() + jb, cb.begin() + jb + rows);
+        if (p == 2)
+          tani_tile<2>(&wa[(size_t)i * kFpWords], ca[i], sb.data(), sc.data(), jb, jb, jb + rows, best, total);
+        else
+          tani_tile<1>(&wa[(size_t)i * kFpWords], ca[i], sb.data(), sc.data(), jb, jb, jb + rows, best, total);
+      }
+      pc[s] = best.c, pu[s] = best.u, pj[s] = best.j, pt[s] = total;
+    }
+    float best;
+    int32_t arg;
+    double total;
+    tani_fold(pc.data(), pu.data(), pj.data(), pt.data(), 1, splits, ca[i], best, arg, total);
+    uint32_t fb;
+    uint64_t tb;
+    memcpy(&fb, &best, 4), memcpy(&tb, &total, 8);
+    printf("%u %d %llu ", fb, (int)arg, (unsigned long long)tb);
+  }
+  printf("\n");
+}
+
 template <class Rec>
 static int run(void (*one)(Rec*)) {
   std::vector<Rec> record(1);                                // on the heap, where ASan guards both ends
@@ -200,5 +282,7 @@ int main(int argc, char** argv) {
   if (!strcmp(mode, "randomize")) return run(run_randomize);
   if (!strcmp(mode, "key")) return run(run_key);
   if (!strcmp(mode, "scaffold")) return run(run_scaffold);
+  if (!strcmp(mode, "fingerprint")) return run(run_fingerprint);
+  if (!strcmp(mode, "tanimoto")) return run(run_tanimoto);
   return 2;
 }
