@@ -76,6 +76,11 @@ circular fingerprint per molecule (fingerprint.SmilesFingerprints, one launch) a
 them (gct_fp_tanimoto): similarity to the nearest neighbour in a fingerprint.FingerprintIndex, and `intDiv`, which
 completes the reference's get_basic_metrics; Train/finetune.similarity_reward reads the same aggregates.
 
+`descriptors(rows or smiles)` / `property_report(rows, targets)` (any sampler): twelve integer descriptors per molecule
+-- atoms, hydrogens, molecular weight, charge, Lipinski's donor and acceptor counts, rotatable bonds, rings, aromatic
+rings, TPSA, ring bonds (descriptor.SmilesDescriptors, one launch, no rdkit) -- and the reference's get_errors of target
+minus computed property over them; Train/finetune.property_reward turns a column into a reward.
+
 `murcko_scaffolds(rows or smiles)` (any sampler) / `scaffold_report(rows)` (a scaffold model): the Murcko scaffold of
 every molecule -- key, spelling and kept atoms (scaffold.SmilesScaffolds, one launch, no rdkit) -- and, for rows that read
 <sos> scaffold <sep> molecule <eos>, whether the molecule has the scaffold it was given: molkey.scaffold_metrics'
@@ -113,6 +118,7 @@ from ..decode import (BEAM_ALPHA, ChemReport, KVDecoder, Marginal, PolicyTerms, 
                       SmilesGrammar, check_beam_size, check_ess_threshold, check_grammar, check_particles,
                       check_sample_filter, check_stream_model, check_stream_rows, generated_tokens, marginal_logp,
                       score_tokens, sequence_logp, sequence_policy, sequence_ppo)
+from ..descriptor import DescRows, SmilesDescriptors, property_errors
 from ..fingerprint import FpRows, SmilesFingerprints, snn as fp_snn
 from ..molkey import MolKeys, SmilesKeys, basic_metrics
 from ..scaffold import ScaffoldRows, SmilesScaffolds
@@ -265,6 +271,7 @@ class Sampling:
         self._keys = None
         self._scaffolds = None
         self._fingerprinter = None
+        self._describer = None
 
     # ---- chemical validity of decoded rows (decode.SmilesChemistry: a check behind the decode, not a constraint on it)
     @property
@@ -411,6 +418,36 @@ class Sampling:
         fingerprint of the largest Tanimoto similarity to `ref`, a fingerprint.FingerprintIndex (of a training set) or
         an FpRows.  `rows` as `fingerprints` takes them, or an FpRows.  0.0 if either side is empty.  One read-back."""
         return fp_snn(rows if isinstance(rows, FpRows) else self.fingerprints(rows), ref)
+
+    # ---- molecular descriptors (descriptor.SmilesDescriptors: MW, Lipinski counts, rings and TPSA without rdkit)
+    @property
+    def describer(self) -> SmilesDescriptors:
+        """The SmilesDescriptors over the target vocabulary, next to self.keys, built on first use."""
+        if self._describer is None:
+            self._describer = SmilesDescriptors(self.TRG.itos, self.pad_id, self.eos_id, self.sep_id, keys=self.keys)
+        return self._describer
+
+    def descriptors(self, rows) -> DescRows:
+        """Integer descriptors on the sampler's device, one launch: `rows` a DecodedRows or (ys, prefix_lens) -- the span
+        behind a row's prefix is read as molecule_keys reads it, and of `scaffold <sep> molecule` the molecule is
+        described -- or SMILES strings.  DescRows(values int32 [n, 12]): the ops.DESC_* columns; a part with a stereo
+        mark, a dot, bad syntax or an atom the rule does not know has a status other than DESC_OK and zeros."""
+        if isinstance(rows, DecodedRows):
+            return self.describer.desc_rows(rows.ys, rows.prefix_lens)
+        if isinstance(rows, tuple) and len(rows) == 2 and torch.is_tensor(rows[0]):
+            return self.describer.desc_rows(*rows)
+        ids = [self.smi_to_id(s, add_eos=True) for s in rows]
+        n, W = len(ids), max((len(r) for r in ids), default=1)
+        ys = torch.tensor([r + [self.pad_id] * (W - len(r)) for r in ids], dtype=torch.int64).view(n, W)
+        return self.describer.desc_rows(ys.to(self.device), torch.zeros(n, dtype=torch.int64))
+
+    def property_report(self, rows, targets, valid_only=True) -> dict:
+        """The reference's get_errors of decoded rows against property targets: targets a dict column name (as
+        DescRows.column takes it: `tpsa`, `mw`, `hbd`, ...) -> a number or one target per row; returns name ->
+        {mae, mse, max, min, aard, amsd, n} (descriptor.property_errors) over the rows that are DESC_OK and, with
+        valid_only, pass check_rows.  `rows` a DecodedRows or (ys, prefix_lens).  One read-back."""
+        mask = (self.check_rows(rows).status == ops.CHEM_OK) if valid_only else None
+        return property_errors(self.descriptors(rows), targets, mask)
 
     # ---- Murcko scaffolds (scaffold.SmilesScaffolds: the reference's murcko_scaffold and scaffold filter, no rdkit)
     @property

@@ -178,6 +178,25 @@ def similarity_reward(agg_or_best, lo=0.0, hi=1.0):
     return ((best.detach().float().clamp(lo, hi) - lo) / (hi - lo))
 
 
+def property_reward(desc, name, target, tol):
+    """One reward per row from a descriptor.DescRows (Sampling.descriptors): fp32 [n] on the rows' device, no graph and
+    no synchronisation -- to multiply into validity_reward.  max(0, 1 - |value - target| / tol) of column `name` (as
+    DescRows.column takes it: `tpsa`, `mw`, `hbd`, ...), computed in fp64 (whose division is correctly rounded on every
+    device: a GPU's reward and the host's agree to the bit) and rounded once to fp32; 0 where the row is not DESC_OK.
+    target: a number, or a tensor with one entry per row, so that a batch of mixed targets works.  ValueError unless
+    tol > 0."""
+    tol = float(tol)
+    if not tol > 0.0:
+        raise ValueError(f"property_reward: tol must be positive, got {tol}")
+    value = desc.column(name, torch.float64).detach()
+    target = torch.as_tensor(target).to(value.device).to(torch.float64)
+    if target.dim() > 1 or (target.dim() == 1 and target.numel() != value.numel()):
+        raise ValueError(f"property_reward: target must be a number or one per row ({value.numel()}), got "
+                         f"{list(target.shape)}")
+    reward = (1.0 - (value - target).abs() / tol).clamp(min=0.0).to(torch.float32)
+    return torch.where(desc.ok, reward, torch.zeros_like(reward))
+
+
 def _check_weight(weight, n, what):
     """weight [n] of reinforce_step / ppo_update as an fp32 vector without a graph; ValueError for another length or a
     value that is negative or not finite."""

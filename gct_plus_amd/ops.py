@@ -1610,6 +1610,30 @@ def smiles_fp(ys, start, table32, label64, pad_id, eos_id, sep_id, out=None):
     return bits, info
 
 
+# status codes of the molecular descriptors (GCT_DESC_* of include/gctplus_hip.h) and the columns of a row
+DESC_OK, DESC_SYNTAX, DESC_UNSUPPORTED, DESC_UNKNOWN_ATOM = range(4)
+(DESC_STATUS, DESC_HEAVY_ATOMS, DESC_HYDROGENS, DESC_MW_MDA, DESC_CHARGE, DESC_HBD, DESC_HBA, DESC_ROTATABLE, DESC_RINGS,
+ DESC_AROMATIC_RINGS, DESC_TPSA_CENTI, DESC_RING_BONDS) = range(12)
+DESC_COLUMNS = 12
+DESC_MAX_SPAN = 256
+
+
+def smiles_desc(ys, start, table32, desc32, pad_id, eos_id, sep_id, out=None):
+    """gct_smiles_desc: the integer descriptors of the molecule in every row's span ys[r, start[r]:] -- behind a <sep> if
+    there is one (descriptor.SmilesDescriptors.desc_reference is the statement).  ys int64 [n, W] with unit column
+    stride, start int32 [n] on the device, table32 int32 [V] (SmilesKeys.device_tables) and desc32 int32 [V]
+    (SmilesDescriptors.device_tables), sep_id -1 for none.  Returns values int32 [n, 12] (the DESC_* columns), freshly
+    allocated or the contiguous tensor `out`.  One launch."""
+    n, W, ld = _smiles_rows("smiles_desc", ys, start=(start, torch.int32))
+    V = _smiles_tables("smiles_desc", table32=(table32, torch.int32), desc32=(desc32, torch.int32))
+    _smiles_ids("smiles_desc", V, dict(pad_id=pad_id, eos_id=eos_id), dict(sep_id=sep_id))
+    values, = _smiles_out("smiles_desc", None if out is None else (out,), ys, values=((n, DESC_COLUMNS), torch.int32))
+    if n:
+        check(_L().gct_smiles_desc(_p(ys), ld, W, n, _p(start), V, _p(table32), _p(desc32), int(pad_id), int(eos_id),
+                                   int(sep_id), _p(values), _st()), "gct_smiles_desc")
+    return values
+
+
 def fp_tanimoto_plan(n, m):
     """(tile_b, splits) of gct_fp_tanimoto for n rows of a against m rows of b: b is walked in tiles of tile_b rows, in
     `splits` independent parts whose partials a second launch folds.  A function of (n, m) alone, never of the device."""

@@ -976,6 +976,33 @@ int gct_smiles_fp(const int64_t* ys, int64_t ld_ys, int W, int n, const int32_t*
                   const int64_t* label64, int pad_id, int eos_id, int sep_id, int64_t* bits_out, int32_t* info_out,
                   void* stream);
 
+/* Molecular descriptors (gct_plus_amd/descriptor.py SmilesDescriptors states the rules: `describe` for one part,
+ * desc_reference for a batch): twelve integers of the labelled graph that gct_smiles_randomize's parse reads from row r's
+ * span ys[r][start[r], W), one wave per row.  Spans, <eos>, <sep> and table32: as in gct_smiles_key (the bond symbol's
+ * label from bit 21); with a <sep> the molecule behind it is described, the part in front of it is not.
+ * desc32: int32 [V], the reading of every ATOM token's string (0 for any other token):
+ *   bits 0..3    element index + 1 over B C N O F Si P S Cl Br I; 0: UNKNOWN (another element, `*`, an element H atom, a
+ *                stated isotope, an unreadable bracket, a charge outside -3 .. 3)
+ *   bit 4        aromatic (a lower-case symbol)
+ *   bit 5        bracket atom: its hydrogens are exactly the stated ones; a bare atom gets implicit hydrogens
+ *   bits 6..9    stated hydrogens (0 .. 9)
+ *   bits 10..12  formal charge + 3
+ * Ring perception: one breadth-first search per bond from one end with the bond excluded gives s(e), the smallest ring
+ * through the bond (0: no ring bond).  A bond without a symbol between two aromatic atoms is AROMATIC only as a ring bond.
+ * values_out int32 [n][GCT_DESC_COLUMNS] = (status, heavy atoms, hydrogens, molecular weight in mDa, formal charge,
+ * N/O atoms with a hydrogen, N and O atoms, rotatable bonds, rings = bonds - atoms + 1, aromatic rings, TPSA in 0.01 A^2
+ * by Ertl's N and O contributions, ring bonds).  Where the status is not OK, columns 2 .. 11 are 0 and column 1 is the
+ * number of atoms of a parsed graph (UNSUPPORTED, UNKNOWN_ATOM), else 0.  A span without <eos>, W - start[r] > 256 or
+ * start[r] outside [0, W]: (-1, 0, ..., 0).  Every row's twelve words are written.  n = 0 is a no-op.  No global
+ * atomics, no scratch. */
+#define GCT_DESC_OK 0
+#define GCT_DESC_SYNTAX 1
+#define GCT_DESC_UNSUPPORTED 2
+#define GCT_DESC_UNKNOWN_ATOM 3
+#define GCT_DESC_COLUMNS 12
+int gct_smiles_desc(const int64_t* ys, int64_t ld_ys, int W, int n, const int32_t* start, int V, const int32_t* table32,
+                    const int32_t* desc32, int pad_id, int eos_id, int sep_id, int32_t* values_out, void* stream);
+
 /* Tanimoto aggregates of every row of a against all rows of b (fingerprint.py tanimoto_reference states the rule).
  * a int64 [n][lda >= 16], b int64 [m][ldb >= 16]: gct_smiles_fp's words; cnt_a int32 [n], cnt_b int32 [m]: their
  * numbers of set bits (0: the row is absent).  For a pair, c = popcount(a_i & b_j), u = cnt_a[i] + cnt_b[j] - c and

@@ -20,6 +20,14 @@ Train/finetune.validity_reward of Sampling.check_rows -- decode.SmilesChemistry'
 one launch on the device instead of the Python loop over the rows; the printed rate is then the VALID share.  The default,
 --reward grammar, is the run described above and prints what it always did.
 
+--reward NAME:T:TOL (NAME a descriptor.DescRows column: tpsa, mw, hbd, hba, rotatable, rings, ...): constrained decoding
+as under --reward chemistry, and the reward is validity_reward x Train/finetune.property_reward(Sampling.descriptors(rows),
+NAME, T, TOL) = max(0, 1 - |value - T| / TOL) -- the policy is paid for valid molecules near the property target; the
+printed rate is then the MEAN REWARD.
+
+--report-descriptors: one more line at the end: the means of mw, tpsa, hbd, hba, rotatable and rings over the rows of the
+evaluation batch that have descriptors (descriptor.SmilesDescriptors, on the device), before and after.
+
 --report-unique: one more line at the end: the DISTINCT MOLECULES of the evaluation batch before and after, beside the
 distinct strings -- Sampling.molecule_keys and molkey.first_occurrence, on the device: a policy that writes one molecule
 in five spellings counts once.
@@ -60,8 +68,25 @@ ap.add_argument("--ppo-epochs", type=int, default=0,
 ap.add_argument("--clip", type=float, default=0.2, help="PPO's clip: ratios are held in [1 - E, 1 + E]")
 ap.add_argument("--max-grad-norm", type=float, default=None,
                 help="bound on the global L2 norm of every update's gradient (FusedAdam clips on the device)")
-ap.add_argument("--reward", choices=("grammar", "chemistry"), default="grammar",
-                help="grammar: 1 for a well-formed string; chemistry: constrained decoding, 1 for a chemically valid one")
+def reward_kind(text):
+    """grammar, chemistry, or NAME:T:TOL -> (NAME, T, TOL)."""
+    if text in ("grammar", "chemistry"):
+        return text
+    parts = text.split(":")
+    try:
+        name, target, tol = parts[0], float(parts[1]), float(parts[2])
+        if len(parts) != 3 or not tol > 0.0:
+            raise ValueError
+    except (IndexError, ValueError):
+        raise argparse.ArgumentTypeError(f"`{text}`: grammar, chemistry or NAME:T:TOL with TOL > 0, such as tpsa:40:20")
+    return name, target, tol
+
+
+ap.add_argument("--reward", type=reward_kind, default="grammar",
+                help="grammar: 1 for a well-formed string; chemistry: constrained decoding, 1 for a chemically valid one; "
+                     "NAME:T:TOL: constrained decoding, validity x max(0, 1 - |descriptor NAME - T| / TOL)")
+ap.add_argument("--report-descriptors", action="store_true",
+                help="one more line at the end: mean mw, tpsa, hbd, hba, rotatable, rings of the evaluation batch")
 ap.add_argument("--report-valid", action="store_true",
                 help="one more line at the end: the chemically valid share of the evaluation batch before and after")
 ap.add_argument("--report-unique", action="store_true",
@@ -84,7 +109,8 @@ from gct_plus_amd.Inference.sampling_tool import DecodedRows, PscavaetfSampling 
 from gct_plus_amd.Model import model_dict  # noqa: E402
 from gct_plus_amd.molkey import first_occurrence, scaffold_metrics  # noqa: E402
 from gct_plus_amd.optim import FusedAdam  # noqa: E402
-from gct_plus_amd.Train.finetune import frozen_prior, ppo_update, reinforce_step, validity_reward  # noqa: E402
+from gct_plus_amd.Train.finetune import (frozen_prior, ppo_update, property_reward, reinforce_step,  # noqa: E402
+                                         validity_reward)
 
 mtype = "pscavaetf"
 nc = synthetic.n_conds(mtype)
@@ -95,8 +121,11 @@ SRC = data.Vocab([t for t in synthetic.GRAMMAR_VOCAB if t not in ("<sos>", "<eos
 torch.manual_seed(a.seed)
 model = model_dict[mtype](len(SRC), len(TRG), dropout=0.0, nconds=nc, use_cond2lat=True, **dims).cuda()
 sampler = PscavaetfSampling(model, SRC, TRG, latent_dim=dims["latent_dim"], max_strlen=a.max_strlen, cond_dim=nc,
-                            decode_algo="multinomial", seed=a.seed, well_formed=a.reward == "chemistry")
-WHAT = "valid" if a.reward == "chemistry" else "well-formed"
+                            decode_algo="multinomial", seed=a.seed, well_formed=a.reward != "grammar")
+PROPERTY = a.reward if isinstance(a.reward, tuple) else None
+WHAT = "valid" if a.reward == "chemistry" else f"reward({PROPERTY[0]})" if PROPERTY else "well-formed"
+if PROPERTY:
+    sampler.descriptors(["C"]).column(PROPERTY[0])             # (an unknown column name ends the run here)
 grammar = SmilesGrammar(TRG.itos, sampler.pad_id, sampler.eos_id) if a.reward == "grammar" else None
 opt = FusedAdam(model.parameters(), lr=a.lr, betas=(0.9, 0.98), eps=1e-9, model=model)
 gen = torch.Generator().manual_seed(a.seed)
@@ -177,6 +206,8 @@ def sample(n, seed):
     rows = out[-1]
     if a.reward == "chemistry":
         return rows, validity_reward(sampler.check_rows(rows))
+    if PROPERTY:
+        return rows, validity_reward(sampler.check_rows(rows)) * property_reward(sampler.descriptors(rows), *PROPERTY)
     t0 = int(rows.prefix_lens[0])
     reward = torch.tensor([float(grammar.well_formed(r)) for r in rows.ys[:, t0:].cpu().tolist()])
     return rows, reward
@@ -198,6 +229,12 @@ def evaluate():
     if a.report_diversity:
         fps = sampler.fingerprints(rows)
         DIVERSITY.append((internal_diversity(fps), int((fps.info[:, 1] > 0).sum())))
+    if a.report_descriptors:
+        d = sampler.descriptors(rows)
+        k = d.ok.sum().clamp(min=1).to(torch.float64)
+        cols = d.columns(DESCRIPTOR_COLUMNS).to(torch.float64)
+        means = torch.where(d.ok[:, None], cols, torch.zeros_like(cols)).sum(0) / k
+        DESCRIPTORS.append((means.tolist(), int(d.ok.sum())))
     if a.report_scaffold:
         SAME_SCAFFOLD.append(scaffold_metrics(sampler.check_rows(rows), sampler.scaffold_report(rows)))
     return float(reward.mean()), distinct, float(terms.entropy.sum() / terms.tokens.sum())
@@ -208,6 +245,8 @@ VALID_SHARE = []
 MOLECULES = []
 SAME_SCAFFOLD = []
 DIVERSITY = []
+DESCRIPTORS = []
+DESCRIPTOR_COLUMNS = ("mw", "tpsa", "hbd", "hba", "rotatable", "rings")
 before = evaluate()
 reg = f", entropy_coef {a.entropy_coef}, kl_coef {a.kl_coef}" if a.entropy_coef or a.kl_coef else ""
 if a.ppo_epochs:
@@ -252,6 +291,10 @@ if a.report_diversity:
     (b, nb), (c, nc) = DIVERSITY
     print(f"internal diversity of the evaluation batch (fingerprint.SmilesFingerprints; intDiv over the rows that have a "
           f"fingerprint): {b:.4f} -> {c:.4f} ({nb} -> {nc} rows)")
+if a.report_descriptors:
+    (b, nb), (c, nc) = DESCRIPTORS
+    print(f"mean descriptors of the evaluation batch (descriptor.SmilesDescriptors; over the rows that have them, {nb} -> "
+          f"{nc}): " + ", ".join(f"{name} {x:.2f} -> {y:.2f}" for name, x, y in zip(DESCRIPTOR_COLUMNS, b, c)))
 if a.report_scaffold:
     b, c = SAME_SCAFFOLD
     print(f"same_scaffold of the evaluation batch (scaffold.SmilesScaffolds; valid rows whose Murcko scaffold is {a.scaffold}): "

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""The host-callable parts of gct_smiles_check / _randomize / _key / _scaffold / _fp and gct_fp_tanimoto on the CPU
+"""The host-callable parts of gct_smiles_check / _randomize / _key / _scaffold / _fp / _desc and gct_fp_tanimoto on the CPU
 under AddressSanitizer and UBSan (no GPU needed): builds tools/smiles_walk_host.hip -- a stand-alone program around the
 parse (csrc/smiles_graph.h), the check's walk and verdict (csrc/chem.hip), the list shuffle and the write-out
-(csrc/smiles_walk.h), the key functions (csrc/smiles_key.h), the peel, marks and compaction of csrc/scaffold.hip and the
-fingerprint and Tanimoto functions (csrc/smiles_fp.h), the host code sanitised -- into tools/_build/ and runs it once per
+(csrc/smiles_walk.h), the key functions (csrc/smiles_key.h), the peel, marks and compaction of csrc/scaffold.hip, the
+fingerprint and Tanimoto functions (csrc/smiles_fp.h) and the ring perception and per-atom descriptor functions
+(csrc/smiles_desc.h), the host code sanitised -- into tools/_build/ and runs it once per
 mode (--modes) over ROWS: molecules, kept rows, rows with
 scaffolds, shells and [nH] substitutions, and the rows that fill the kernels' LDS records to their ends (chains of 63 ..
 255, a ring of 253 atoms, branch depth 83 with and without a ring at the bottom, 84 branches on one atom, atoms with 8
@@ -19,6 +20,8 @@ and 9 bonds, 40 rings open at once).
   tanimoto   the pair, tile and fold functions on random fingerprints at three bit densities, with absent rows, rows
              of all 1024 bits and duplicates, for p = 1 and 2, in tiles and splits of several sizes (a few hundred
              pairs per case); against tanimoto_reference: best and arg exactly, total within m * 2^-53 * total
+  descriptor every row and --spellings random spellings of it, and molecules that reach the TPSA lines, charged and
+             unknown atoms; against SmilesDescriptors.describe
 Exit status 1 for a sanitizer report or a line that differs."""
 import argparse
 import collections
@@ -33,12 +36,13 @@ sys.path.insert(0, ROOT)
 
 from gct_plus_amd import ops, synthetic  # noqa: E402
 from gct_plus_amd.decode import SmilesChemistry  # noqa: E402
+from gct_plus_amd.descriptor import SmilesDescriptors  # noqa: E402
 from gct_plus_amd.fingerprint import FpRows, SmilesFingerprints, tanimoto_reference  # noqa: E402
 from gct_plus_amd.molkey import as_int64  # noqa: E402
 from gct_plus_amd.randomize import SmilesRandomizer, stream  # noqa: E402
 from gct_plus_amd.scaffold import SmilesScaffolds  # noqa: E402
 
-MODES = ("check", "randomize", "key", "scaffold", "fingerprint", "tanimoto")
+MODES = ("check", "randomize", "key", "scaffold", "fingerprint", "tanimoto", "descriptor")
 ap = argparse.ArgumentParser()
 ap.add_argument("--modes", nargs="+", choices=MODES, default=list(MODES))
 ap.add_argument("--keys", type=int, default=40)
@@ -229,6 +233,22 @@ def mode_tanimoto():
             same &= abs(total - ref.total[i].item()) <= len(b) * 2.0 ** -53 * ref.total[i].item()
         return same, p
     return cases, lines, want, {1: "p = 1:", 2: "p = 2:"}
+
+
+def mode_descriptor():
+    ds = SmilesDescriptors(V, PAD, EOS, keys=ks)
+    more = ["CC(=O)Oc1ccccc1C(=O)O", "CC(=O)Nc1ccc(O)cc1", "c1ccccc1[N+](=O)[O-]", "C1CO1", "C1CN1", "CS(C)=O", "CS(=O)(=O)N",
+            "C[N+](C)(C)C", "CC#CC", "c1ccccc1c1ccccc1", "c1ccc2ccccc2c1", "c1ccn2cccc2c1", "O=n1ccccc1", "C[n+]1ccccc1",
+            "c1cc[nH+]cc1", "C[O-]", "c1ccoc1", "CN(=O)=O", "C=N#C", "C$N", "C*C", "C[2H]", "C[Si](C)C", "C[se]C", "FS(F)(F)(F)F",
+            "c1" + "c" * 251 + "n1", "N" + "C" * 252 + "O"]
+    cases = [t for s in ROWS + more for t in spellings(ids(s))]
+
+    def want(toks, got):
+        mine = ds.describe(toks)
+        return [int(x) for x in got] == mine, mine[0]
+    names = {getattr(ops, n): n[5:] for n in ("DESC_OK", "DESC_SYNTAX", "DESC_UNSUPPORTED", "DESC_UNKNOWN_ATOM")}
+    return (cases, lambda toks: [[len(toks)], [ks.words[t] & 0xFFFFFF for t in toks], [ds.desc[t] for t in toks]], want,
+            names)
 
 
 build = os.path.join(ROOT, "tools", "_build")

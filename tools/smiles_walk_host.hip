@@ -1,7 +1,8 @@
 // CPU harness of the host-callable parts of the SMILES kernels (tools/smiles_walk_check.py builds and drives it):
 // rand_parse of csrc/smiles_graph.h, the check's walk and verdict (csrc/chem.hip), rand_shuffle_atom and
 // rand_walk (csrc/smiles_walk.h), the per-atom key functions (csrc/smiles_key.h), sca_peel / sca_shell / sca_nh /
-// sca_compact (csrc/scaffold.hip) and the fingerprint and Tanimoto functions (csrc/smiles_fp.h) run on the HOST over one
+// sca_compact (csrc/scaffold.hip), the fingerprint and Tanimoto functions (csrc/smiles_fp.h) and the ring perception and
+// per-atom descriptor functions (csrc/smiles_desc.h) run on the HOST over one
 // LDS record per case, bond by bond and atom by atom as the kernels' lanes do, so that AddressSanitizer and UBSan see
 // every index they form -- the scaffold's aliased walk buffers, the fingerprint's labels in its second identifier buffer
 // and reused parse fields included.  No GPU is touched.  Usage: smiles_walk_host MODE FILE; the file holds the count and
@@ -13,6 +14,7 @@
 //              labels / n_rings ring ids
 //   fingerprint L / L table words / L token labels (unsigned 64-bit)
 //   tanimoto   na nb p tile tiles_per_split / na + nb rows: count and 32 words of 32 bits
+//   descriptor L / L table words / L desc32 words
 // and one line goes out per case:
 //   check      status position atoms ring_bonds
 //   randomize  status, and for a rewritten part the length, the row's LDS entries | perm
@@ -20,12 +22,14 @@
 //   scaffold   status key atoms-kept length | the row's entries | member per input atom
 //   fingerprint status atoms bonds and the 16 words (unsigned 64-bit)
 //   tanimoto   per row of a: best (the fp32's bits) arg total (the fp64's bits)
+//   descriptor the row's twelve integers
 // (an entry is a literal id, or -(j + 1) for the token at position j).
 #include "../gct_plus_amd/csrc/chem.hip"
 #include "../gct_plus_amd/csrc/randomize.hip"
 #include "../gct_plus_amd/csrc/molkey.hip"
 #include "../gct_plus_amd/csrc/scaffold.hip"
 #include "../gct_plus_amd/csrc/fingerprint.hip"
+#include "../gct_plus_amd/csrc/descriptor.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -268,6 +272,40 @@ static void run_tanimoto(TaniCase*) {                        // tani_kernel's wa
   printf("\n");
 }
 
+static void run_descriptor(DescWave* w) {                    // smiles_desc_kernel, bond by bond and atom by atom
+  const int L = rd_in(0, 255);
+  fresh(w, L);
+  for (int i = 0; i < L; ++i) w->dsc[i] = (uint16_t)rd_in(0, 0xFFFF);
+  int A, nb;
+  bool unsup;
+  const bool parsed = rand_parse(*w, 0, L, A, nb, unsup);
+  if (!parsed || unsup) {
+    printf("%d %d 0 0 0 0 0 0 0 0 0 0\n", parsed ? GCT_DESC_UNSUPPORTED : GCT_DESC_SYNTAX, parsed ? A : 0);
+    return;
+  }
+  int ring_bonds = 0, arom_bonds = 0, rot = 0;
+  for (int e = 0; e < nb; ++e) {
+    const int s = desc_ring_size(*w, e), c = desc_bond_class(*w, e, s);
+    w->rsz[e] = (uint8_t)s, w->bcls[e] = (uint8_t)c;
+    ring_bonds += s != 0, arom_bonds += s != 0 && c == kDescAromatic;
+  }
+  DescAtom t = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int comps = 0;
+  for (int a = 0; a < A; ++a) {
+    const DescAtom r = desc_atom(*w, a);
+    w->aflag[a] = (uint8_t)r.triple;
+    t.unknown += r.unknown, t.hydrogens += r.hydrogens, t.mass += r.mass, t.charge += r.charge, t.hbd += r.hbd;
+    t.hba += r.hba, t.tpsa += r.tpsa, t.touched += r.touched;
+    if (r.touched) comps += desc_component(*w, a) == a;
+  }
+  for (int e = 0; e < nb; ++e) rot += desc_rotatable(*w, e);
+  if (t.unknown)
+    printf("%d %d 0 0 0 0 0 0 0 0 0 0\n", GCT_DESC_UNKNOWN_ATOM, A);
+  else
+    printf("%d %d %d %d %d %d %d %d %d %d %d %d\n", GCT_DESC_OK, A, t.hydrogens, t.mass, t.charge, t.hbd, t.hba, rot,
+           nb - A + 1, arom_bonds - t.touched + comps, t.tpsa, ring_bonds);
+}
+
 template <class Rec>
 static int run(void (*one)(Rec*)) {
   std::vector<Rec> record(1);                                // on the heap, where ASan guards both ends
@@ -284,5 +322,6 @@ int main(int argc, char** argv) {
   if (!strcmp(mode, "scaffold")) return run(run_scaffold);
   if (!strcmp(mode, "fingerprint")) return run(run_fingerprint);
   if (!strcmp(mode, "tanimoto")) return run(run_tanimoto);
+  if (!strcmp(mode, "descriptor")) return run(run_descriptor);
   return 2;
 }
