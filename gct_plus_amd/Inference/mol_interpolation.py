@@ -18,7 +18,7 @@ Deliberate deviations:
     reference divides by zero);
   * the retry ladder is decoded `chunk` rungs at a time; the result is the LOWEST accepted rung of a cell, which is what
     the one-at-a-time loop stops at (the rungs above it are decoded and dropped);
-  * acceptance is syntactic by default (decode.SmilesGrammar.well_formed and a non-empty string) -- rdkit stays outside
+  * acceptance is syntactic by default (smiles.SmilesGrammar.well_formed and a non-empty string) -- rdkit stays outside
     the package; a caller that has it passes `accept=`.  No CSV files, plots or Tanimoto figures.
 """
 from __future__ import annotations

@@ -51,13 +51,13 @@ frozen prior (decode.sequence_policy), the regularisers of that step.  `ppo_term
 clip=)` is PPO's clipped surrogate against the log-probabilities the rows were sampled with (decode.sequence_ppo), the
 objective of Train/finetune.ppo_update's several updates per scored batch.  Not with beam search.
 
-`well_formed=True` (optional): greedy / multinomial decodes are constrained by decode.SmilesGrammar built from the target
+`well_formed=True` (optional): greedy / multinomial decodes are constrained by smiles.SmilesGrammar built from the target
 vocabulary -- every returned string has balanced branches, paired ring-closure numbers, no dangling bond, and ended
 with <eos> inside max_strlen.  Syntax only: no valence or aromaticity check (`check_rows` / `is_valid` below check the
 decoded rows for those).  Not with beam search: the constructor
 refuses decode_algo="beam", and `decode_beams` of such a sampler raises.
 
-`check_rows(rows)` (any sampler): decode.SmilesChemistry's check of decoded rows on the device, one launch -- a
+`check_rows(rows)` (any sampler): smiles.SmilesChemistry's check of decoded rows on the device, one launch -- a
 ChemReport(status, position, atoms, ring_bonds) per row: valence caps, ring closures that double a bond or disagree on
 its order, aromatic atoms outside an aromatic ring.  A necessary condition of validity, not a toolkit's verdict.
 Train/finetune.validity_reward turns the report into the reward of reinforce_step / ppo_update; `is_valid(smiles)` is the
@@ -114,15 +114,15 @@ from .. import ops
 from ..Model.modules import get_src_mask
 from ..data import Vocab, tokenize
 from .mol_interpolation import Interpolation, interior_alphas, interp_plan, lerp, noise_ladder, run_ladder
-from ..decode import (BEAM_ALPHA, ChemReport, KVDecoder, Marginal, PolicyTerms, PpoTerms, SmilesChemistry,
-                      SmilesGrammar, check_beam_size, check_ess_threshold, check_grammar, check_particles,
-                      check_sample_filter, check_stream_model, check_stream_rows, generated_tokens, marginal_logp,
-                      score_tokens, sequence_logp, sequence_policy, sequence_ppo)
+from ..decode import (BEAM_ALPHA, KVDecoder, Marginal, PolicyTerms, PpoTerms, check_beam_size, check_ess_threshold,
+                      check_particles, check_sample_filter, check_stream_model, check_stream_rows, generated_tokens,
+                      marginal_logp, score_tokens, sequence_logp, sequence_policy, sequence_ppo)
 from ..descriptor import DescRows, SmilesDescriptors, property_errors
 from ..fingerprint import FpRows, SmilesFingerprints, snn as fp_snn
 from ..molkey import MolKeys, SmilesKeys, basic_metrics
 from ..scaffold import ScaffoldRows, SmilesScaffolds
 from ..randomize import SmilesRandomizer
+from ..smiles import ChemReport, SmilesChemistry, SmilesGrammar, check_grammar
 
 
 BEAM_ALGOS = ("beam", "stochastic_beam")        # decode_algo values that decode k rows per sample in step (kv_src)
@@ -231,8 +231,10 @@ class Sampling:
         if well_formed and decode_algo in BEAM_ALGOS:
             raise ValueError(f"well_formed is not supported with decode_algo={decode_algo!r} (beam rows keep their history "
                              "behind the ancestry map)")
+        self.TRG = TRG
+        self._vocab_grammar = self._chemistry = self._keys = self._scaffolds = self._fingerprinter = self._describer = None
         # constrained decoding: the grammar over the target vocabulary, passed to every decode
-        self.grammar = SmilesGrammar(TRG.itos, TRG.stoi["<pad>"], TRG.stoi["<eos>"]) if well_formed else None
+        self.grammar = self.vocab_grammar if well_formed else None
         if with_logp and decode_algo in BEAM_ALGOS:
             raise ValueError(f"with_logp is not supported with decode_algo={decode_algo!r}: decode_beams / decode_unique "
                              "return the beams' scores, which are sums of log-probabilities already")
@@ -253,7 +255,7 @@ class Sampling:
             check_beam_size(beam_size, V)
         self.top_k, self.top_p, self.temperature = top_k, top_p, temperature
         self.beam_size, self.beam_alpha = beam_size, float(beam_alpha)
-        self.model, self.SRC, self.TRG = model.eval(), SRC, TRG
+        self.model, self.SRC = model.eval(), SRC
         self.pad_id, self.sos_id, self.eos_id = SRC.stoi["<pad>"], TRG.stoi["<sos>"], TRG.stoi["<eos>"]
         self.sep_id = TRG.stoi.get("<sep>")
         self.add_sep = self.sep_id is not None
@@ -266,19 +268,49 @@ class Sampling:
         self.latent_seed = seed                 # interpolate_smiles' latents: one stream per sampler, not per decode
         self.marginal_seed = seed               # marginal(seed=None): advanced once per call, so calls draw afresh
         self.kv = KVDecoder(model, self.pad_id, self.sos_id, self.eos_id)
-        self._chemistry = None
-        self._randomizer = None
-        self._keys = None
-        self._scaffolds = None
-        self._fingerprinter = None
-        self._describer = None
 
-    # ---- chemical validity of decoded rows (decode.SmilesChemistry: a check behind the decode, not a constraint on it)
+    # ---- one of each SMILES object per vocabulary: the grammar serves well_formed, decode_smc, interpolate_smiles, the
+    # chemistry check and the randomiser; the keys (and their randomiser) serve scaffolds, fingerprints and descriptors
+    @property
+    def vocab_grammar(self) -> SmilesGrammar:
+        """The SmilesGrammar over the target vocabulary, built on first use (self.grammar is it, or None: whether a
+        decode is constrained).  Its <pad> is the TARGET vocabulary's id, also for the chemistry check, the randomiser
+        and the keys, which used to build their grammars with the source vocabulary's: the same id in every vocabulary
+        pair data.py makes."""
+        if self._vocab_grammar is None:
+            self._vocab_grammar = SmilesGrammar(self.TRG.itos, self.TRG.stoi["<pad>"], self.TRG.stoi["<eos>"])
+        return self._vocab_grammar
+
+    def _smiles_rows(self, what, rows, scaffold_list=None, repeat=1):
+        """THE row intake of the SMILES front ends -> (ys, start, W): `rows` a DecodedRows or (ys, prefix_lens), taken as
+        they are (W None; a DecodedRows' scaffold_list is ignored, as it always was), or SMILES strings -- their ids and
+        <eos>, behind `scaffold <sep>` with scaffold_list, <pad> to the widest row W, every row `repeat` times in a row,
+        copied to the sampler's device, with zero starts on the CPU."""
+        if isinstance(rows, DecodedRows):
+            return rows.ys, rows.prefix_lens, None
+        if isinstance(rows, tuple) and len(rows) == 2 and torch.is_tensor(rows[0]):
+            if scaffold_list is not None:
+                raise ValueError(f"{what}: scaffold_list goes with strings; token rows hold their scaffold")
+            return (*rows, None)
+        ids = [self.smi_to_id(s, add_eos=True) for s in rows]
+        n = len(ids)
+        if scaffold_list is not None:
+            if not self.add_sep:
+                raise ValueError("scaffold_list needs a scaffold model's vocabulary (no <sep> token here)")
+            scaffold_list = list(scaffold_list)
+            if len(scaffold_list) != n:
+                raise ValueError(f"{len(scaffold_list)} scaffolds for {n} molecules")
+            ids = [self.smi_to_id(c) + [self.sep_id] + r for c, r in zip(scaffold_list, ids)]
+        W = max((len(r) for r in ids), default=1)
+        ys = torch.tensor([r + [self.pad_id] * (W - len(r)) for r in ids], dtype=torch.int64).view(n, W)
+        return ys.repeat_interleave(repeat, 0).to(self.device), torch.zeros(n * repeat, dtype=torch.int64), W
+
+    # ---- chemical validity of decoded rows (smiles.SmilesChemistry: a check behind the decode, not a constraint on it)
     @property
     def chemistry(self) -> SmilesChemistry:
         """The SmilesChemistry over the target vocabulary, built on first use."""
         if self._chemistry is None:
-            self._chemistry = SmilesChemistry(self.TRG.itos, self.pad_id, self.eos_id)
+            self._chemistry = SmilesChemistry(self.TRG.itos, self.pad_id, self.eos_id, grammar=self.vocab_grammar)
         return self._chemistry
 
     def check_rows(self, rows, prefix_lens=None) -> ChemReport:
@@ -302,10 +334,8 @@ class Sampling:
     # ---- random spellings of given molecules (randomize.SmilesRandomizer: the reference's randomize_smiles, no rdkit)
     @property
     def randomizer(self) -> SmilesRandomizer:
-        """The SmilesRandomizer over the target vocabulary, built on first use."""
-        if self._randomizer is None:
-            self._randomizer = SmilesRandomizer(self.TRG.itos, self.pad_id, self.eos_id, self.sep_id)
-        return self._randomizer
+        """The SmilesRandomizer over the target vocabulary: the keys'."""
+        return self.keys.randomizer
 
     def randomize_smiles(self, smiles_list, scaffold_list=None, k=1, seed=0):
         """k random spellings of every molecule, for encode_smiles / score_smiles: one launch on the sampler's device.
@@ -315,25 +345,13 @@ class Sampling:
         a token outside the vocabulary, no room inside 256 tokens) comes back as it was written and its status says
         why.  Spelling j of molecule i is keyed i | j << 32 under `seed`: it does not depend on k or on the other
         molecules.  The same graph in another atom order: atoms and bond symbols are carried verbatim."""
-        smiles_list = list(smiles_list)
-        n, k = len(smiles_list), int(k)
+        smiles_list, k = list(smiles_list), int(k)
         if k < 1:
             raise ValueError(f"k must be at least 1, got {k}")
-        if scaffold_list is not None:
-            if not self.add_sep:
-                raise ValueError("scaffold_list needs a scaffold model's vocabulary (no <sep> token here)")
-            scaffold_list = list(scaffold_list)
-            if len(scaffold_list) != n:
-                raise ValueError(f"{len(scaffold_list)} scaffolds for {n} molecules")
-        rows = [self.smi_to_id(s, add_eos=True) for s in smiles_list]
-        if scaffold_list is not None:
-            rows = [self.smi_to_id(c) + [self.sep_id] + r for c, r in zip(scaffold_list, rows)]
-        W = max((len(r) for r in rows), default=1)
-        ys = torch.tensor([r + [self.pad_id] * (W - len(r)) for r in rows], dtype=torch.int64).view(n, W)
-        ys = ys.repeat_interleave(k, 0).to(self.device)
+        ys, start, W = self._smiles_rows("randomize_smiles", smiles_list, scaffold_list, repeat=k)
+        n = len(smiles_list)
         key = torch.arange(n, dtype=torch.int64).view(n, 1) | (torch.arange(k, dtype=torch.int64).view(1, k) << 32)
-        got = self.randomizer.randomize_rows(ys, torch.zeros(n * k, dtype=torch.int64), key.reshape(-1), seed, 1.0,
-                                             out_width=max(W, min(W + 32, 256)))
+        got = self.randomizer.randomize_rows(ys, start, key.reshape(-1), seed, 1.0, out_width=max(W, min(W + 32, 256)))
         out, tokens = [], got.tokens.cpu().tolist()
         for i in range(n):
             spell = []
@@ -350,9 +368,10 @@ class Sampling:
     # ---- molecule identity (molkey.SmilesKeys: uniqueness and novelty without moses or rdkit)
     @property
     def keys(self) -> SmilesKeys:
-        """The SmilesKeys over the target vocabulary, built on first use."""
+        """The SmilesKeys over the target vocabulary, built on first use, with its randomiser over self.vocab_grammar."""
         if self._keys is None:
-            self._keys = SmilesKeys(self.TRG.itos, self.pad_id, self.eos_id, self.sep_id)
+            rz = SmilesRandomizer(self.TRG.itos, self.pad_id, self.eos_id, self.sep_id, grammar=self.vocab_grammar)
+            self._keys = SmilesKeys(self.TRG.itos, self.pad_id, self.eos_id, self.sep_id, randomizer=rz)
         return self._keys
 
     def molecule_keys(self, rows, scaffold_list=None) -> MolKeys:
@@ -362,25 +381,7 @@ class Sampling:
         = (molecule, scaffold or 0), info int32 [n, 4] = (ops.KEY_* status of the molecule, of the scaffold or -1, atoms,
         bonds)).  Equal keys: the same molecule as far as molkey's rule can tell; a part with a stereo mark, a dot or bad
         syntax is the same only as the same string."""
-        if isinstance(rows, DecodedRows):
-            return self.keys.key_rows(rows.ys, rows.prefix_lens)
-        if isinstance(rows, tuple) and len(rows) == 2 and torch.is_tensor(rows[0]):
-            if scaffold_list is not None:
-                raise ValueError("molecule_keys: scaffold_list goes with strings; token rows hold their scaffold")
-            return self.keys.key_rows(*rows)
-        smiles_list = list(rows)
-        n = len(smiles_list)
-        ids = [self.smi_to_id(s, add_eos=True) for s in smiles_list]
-        if scaffold_list is not None:
-            if not self.add_sep:
-                raise ValueError("scaffold_list needs a scaffold model's vocabulary (no <sep> token here)")
-            scaffold_list = list(scaffold_list)
-            if len(scaffold_list) != n:
-                raise ValueError(f"{len(scaffold_list)} scaffolds for {n} molecules")
-            ids = [self.smi_to_id(c) + [self.sep_id] + r for c, r in zip(scaffold_list, ids)]
-        W = max((len(r) for r in ids), default=1)
-        ys = torch.tensor([r + [self.pad_id] * (W - len(r)) for r in ids], dtype=torch.int64).view(n, W)
-        return self.keys.key_rows(ys.to(self.device), torch.zeros(n, dtype=torch.int64))
+        return self.keys.key_rows(*self._smiles_rows("molecule_keys", rows, scaffold_list)[:2])
 
     def basic_metrics(self, rows, index=None, int_div=False) -> dict:
         """valid / unique / novel of decoded rows (molkey.basic_metrics, moses' definitions): check_rows, molecule_keys
@@ -404,14 +405,7 @@ class Sampling:
         -- the span behind a row's prefix is read as molecule_keys reads it, and of `scaffold <sep> molecule` the
         molecule is fingerprinted -- or SMILES strings.  FpRows(bits int64 [n, 16], info int32 [n, 4] = (ops.FP_* status,
         bits set, atoms, bonds)); a part with a stereo mark, a dot or bad syntax has no bit."""
-        if isinstance(rows, DecodedRows):
-            return self.fingerprinter.fp_rows(rows.ys, rows.prefix_lens)
-        if isinstance(rows, tuple) and len(rows) == 2 and torch.is_tensor(rows[0]):
-            return self.fingerprinter.fp_rows(*rows)
-        ids = [self.smi_to_id(s, add_eos=True) for s in rows]
-        n, W = len(ids), max((len(r) for r in ids), default=1)
-        ys = torch.tensor([r + [self.pad_id] * (W - len(r)) for r in ids], dtype=torch.int64).view(n, W)
-        return self.fingerprinter.fp_rows(ys.to(self.device), torch.zeros(n, dtype=torch.int64))
+        return self.fingerprinter.fp_rows(*self._smiles_rows("fingerprints", rows)[:2])
 
     def snn(self, rows, ref) -> float:
         """Similarity to the nearest neighbour (the reference's get_snn_from_mol): the mean over the rows that have a
@@ -432,14 +426,7 @@ class Sampling:
         behind a row's prefix is read as molecule_keys reads it, and of `scaffold <sep> molecule` the molecule is
         described -- or SMILES strings.  DescRows(values int32 [n, 12]): the ops.DESC_* columns; a part with a stereo
         mark, a dot, bad syntax or an atom the rule does not know has a status other than DESC_OK and zeros."""
-        if isinstance(rows, DecodedRows):
-            return self.describer.desc_rows(rows.ys, rows.prefix_lens)
-        if isinstance(rows, tuple) and len(rows) == 2 and torch.is_tensor(rows[0]):
-            return self.describer.desc_rows(*rows)
-        ids = [self.smi_to_id(s, add_eos=True) for s in rows]
-        n, W = len(ids), max((len(r) for r in ids), default=1)
-        ys = torch.tensor([r + [self.pad_id] * (W - len(r)) for r in ids], dtype=torch.int64).view(n, W)
-        return self.describer.desc_rows(ys.to(self.device), torch.zeros(n, dtype=torch.int64))
+        return self.describer.desc_rows(*self._smiles_rows("descriptors", rows)[:2])
 
     def property_report(self, rows, targets, valid_only=True) -> dict:
         """The reference's get_errors of decoded rows against property targets: targets a dict column name (as
@@ -452,9 +439,9 @@ class Sampling:
     # ---- Murcko scaffolds (scaffold.SmilesScaffolds: the reference's murcko_scaffold and scaffold filter, no rdkit)
     @property
     def scaffolds(self) -> SmilesScaffolds:
-        """The SmilesScaffolds over the target vocabulary, built on first use."""
+        """The SmilesScaffolds over the target vocabulary, next to self.keys, built on first use."""
         if self._scaffolds is None:
-            self._scaffolds = SmilesScaffolds(self.TRG.itos, self.pad_id, self.eos_id, self.sep_id)
+            self._scaffolds = SmilesScaffolds(self.TRG.itos, self.pad_id, self.eos_id, self.sep_id, keys=self.keys)
         return self._scaffolds
 
     def murcko_scaffolds(self, rows):
@@ -462,16 +449,8 @@ class Sampling:
         (ys, prefix_lens) -- the span behind a row's prefix holds the molecule, as check_rows reads it -- or SMILES
         strings.  Returns (strings, ScaffoldRows): strings[i] the scaffold's spelling, "" for a row without one
         (info[i, 0] says why: ops.SCA_ACYCLIC, SCA_SYNTAX, SCA_UNSUPPORTED, ...).  One read-back, for the strings."""
-        if isinstance(rows, DecodedRows):
-            got = self.scaffolds.scaffold_rows(rows.ys, rows.prefix_lens)
-        elif isinstance(rows, tuple) and len(rows) == 2 and torch.is_tensor(rows[0]):
-            got = self.scaffolds.scaffold_rows(*rows)
-        else:
-            ids = [self.smi_to_id(s, add_eos=True) for s in rows]
-            n, W = len(ids), max((len(r) for r in ids), default=1)
-            ys = torch.tensor([r + [self.pad_id] * (W - len(r)) for r in ids], dtype=torch.int64).view(n, W)
-            got = self.scaffolds.scaffold_rows(ys.to(self.device), torch.zeros(n, dtype=torch.int64),
-                                               out_width=max(W, min(W + 32, 256)))
+        ys, start, W = self._smiles_rows("murcko_scaffolds", rows)
+        got = self.scaffolds.scaffold_rows(ys, start, out_width=None if W is None else max(W, min(W + 32, 256)))
         return [self.id_to_smi(r) for r in got.tokens.cpu().tolist()], got
 
     def scaffold_report(self, rows) -> ScaffoldRows:
@@ -754,7 +733,7 @@ class Sampling:
         once per call.  ValueError for a bad ess_threshold or k, or max_strlen < 3, before any device work."""
         check_ess_threshold(ess_threshold)
         k = check_particles(self.beam_size if k is None else k, "decode_smc")
-        grammar = self.grammar or SmilesGrammar(self.TRG.itos, self.TRG.stoi["<pad>"], self.eos_id)
+        grammar = self.vocab_grammar
         check_grammar(grammar, self.model.out.weight.shape[0], self.max_strlen - 1)
         self.seed += 1
         zs, ys, src_mask, dconds = self._start_rows(zs, ys, src_mask, dconds, beams=k)
@@ -857,7 +836,7 @@ class Sampling:
         toklen = interp_plan(lens[:P], lens[P:], alphas, extras if self.uses_scaffold else None)
         stats = ops.latent_stats(mu.contiguous(), log_var.contiguous(), lens)
         if accept is None:
-            grammar = self.grammar or SmilesGrammar(self.TRG.itos, self.pad_id, self.eos_id)
+            grammar = self.vocab_grammar
             verdict = lambda o: bool(o[0]) and grammar.well_formed(o[1])          # noqa: E731
         else:
             verdict = lambda o: bool(accept(o[0]))                                # noqa: E731

@@ -122,7 +122,7 @@ def behaviour_weights(model_logp, behaviour_logp, clip=None):
 
 
 def validity_reward(report, shaped=False, lengths=None):
-    """One reward per row from a decode.ChemReport (Sampling.check_rows): fp32 [n] on the report's device, no graph and
+    """One reward per row from a smiles.ChemReport (Sampling.check_rows): fp32 [n] on the report's device, no graph and
     no synchronisation -- reinforce_step / ppo_update take it as `reward` as it is.  1 where status == ops.CHEM_OK, else
     0.  shaped=True: a rejected row gets position / length instead, the share of its span that lies in front of the
     first offence; lengths ints [n] (or one int) are the span lengths W - prefix_lens, all >= 1.  (A SYNTAX row that

@@ -11,7 +11,7 @@ The rule.
   Atom entries come from the token STRING (atom_entry; desc32 is the per-token table the kernel reads, its bit layout is
   documented in include/gctplus_hip.h).  Element: B C N O F Si P S Cl Br I, masses in mDa 10810, 12011, 14007, 15999,
   18998, 28086, 30974, 32060, 35450, 79904, 126904; H 1008.  Any other element, `*`, an element H atom, a stated isotope, a
-  bracket decode._CHEM_BRACKET does not read, or a charge outside -3 .. 3 is UNKNOWN: one such atom makes the part
+  bracket smiles._CHEM_BRACKET does not read, or a charge outside -3 .. 3 is UNKNOWN: one such atom makes the part
   DESC_UNKNOWN_ATOM.  Formal charge: as the bracket states it, 0 for a bare atom.  Stated hydrogens: a bracket atom has
   exactly what it states (H alone: 1), a bare atom has 0 stated plus its implicit hydrogens.  Aromatic: a lower-case symbol.
   Ring perception.  Bond e = (a, b) is a ring bond iff b is reachable from a without e; s(e) = 1 + the length of the
@@ -47,8 +47,8 @@ from typing import NamedTuple
 import torch
 
 from . import ops
-from .decode import _CHEM_BRACKET, _int_vector
 from .molkey import SmilesKeys
+from .smiles import _CHEM_BRACKET, launch_rows, on_device, row_mask, row_spans
 
 ELEMENTS = ("B", "C", "N", "O", "F", "Si", "P", "S", "Cl", "Br", "I")
 MASS_MDA = (10810, 12011, 14007, 15999, 18998, 28086, 30974, 32060, 35450, 79904, 126904)
@@ -203,10 +203,8 @@ class SmilesDescriptors:
 
     def device_tables(self, device):
         """(table32 int32 [V] -- the keys' --, desc32 int32 [V]) on `device` (copied once)."""
-        key = str(torch.device(device))
-        if key not in self._device_tables:
-            self._device_tables[key] = (self.keys.device_tables(device)[0], self.desc_table.to(device))
-        return self._device_tables[key]
+        return on_device(self._device_tables, device,
+                         lambda: (self.keys.device_tables(device)[0], self.desc_table.to(device)))
 
     # ------------------------------------------------------------------------------------------------ one part
     @staticmethod
@@ -295,44 +293,24 @@ class SmilesDescriptors:
 
     # --------------------------------------------------------------------------------------------------- batches
     def desc_reference(self, ys, start) -> DescRows:
-        """THE batch rule (gct_smiles_desc implements it), on the CPU.  Spans, the first <eos>, the width limit of 256 and
-        a start outside [0, W] are key_reference's: such a row is (-1, 0, ..., 0).  Otherwise the content is what stands
-        in front of the first <eos>; with sep_id and a <sep> in it, the molecule BEHIND the first <sep> is described."""
-        ys = torch.as_tensor(ys)
-        SmilesKeys._check_batch(ys)
-        n, W = ys.shape
-        starts = [int(s) for s in torch.as_tensor(start).view(-1).tolist()]
-        if len(starts) != n:
-            raise ValueError(f"start must be {n} integers, one per row")
-        out = torch.zeros(n, ops.DESC_COLUMNS, dtype=torch.int32)
-        for r, (row, t0) in enumerate(zip(ys.cpu().tolist(), starts)):
-            span = row[t0:] if 0 <= t0 <= W and W - t0 <= ops.DESC_MAX_SPAN else []
-            if self.eos_id not in span:
+        """THE batch rule (gct_smiles_desc implements it), on the CPU.  Spans, absent rows and the two parts are
+        smiles.row_spans': an absent row is (-1, 0, ..., 0).  Otherwise the molecule is described; of `scaffold <sep>
+        molecule` that is the part BEHIND the first <sep>."""
+        spans = row_spans(ys, start, self.eos_id, self.sep_id)
+        out = torch.zeros(len(spans), ops.DESC_COLUMNS, dtype=torch.int32)
+        for r, sp in enumerate(spans):
+            if sp.molecule is None:
                 out[r, 0] = -1
-                continue
-            content = span[:span.index(self.eos_id)]
-            if self.sep_id is not None and self.sep_id in content:
-                content = content[content.index(self.sep_id) + 1:]
-            out[r] = torch.tensor(self.describe(content), dtype=torch.int32)
+            else:
+                out[r] = torch.tensor(self.describe(sp.molecule), dtype=torch.int32)
         return DescRows(out)
 
     def desc_rows(self, ys, start) -> DescRows:
         """The same on the device of ys: one gct_smiles_desc launch, no synchronisation.  ys integers [n, W]; start ints
         [n] (on the CPU: checked there, as key_rows does) or an int32 tensor on the device (taken as it is: a row
         outside the range has status -1).  ValueError for a span wider than 256 columns or a start outside [0, W]."""
-        SmilesKeys._check_batch(ys)
-        n, W = ys.shape
-        if torch.is_tensor(start) and start.device == ys.device and start.dtype == torch.int32 and ys.is_cuda:
-            st = start
-        else:
-            lens = _int_vector("start", start, n, 0, W, "the row width")
-            if n and W - int(lens.min()) > ops.DESC_MAX_SPAN:
-                raise ValueError(f"a span of {W - int(lens.min())} columns: the descriptors take at most "
-                                 f"{ops.DESC_MAX_SPAN}")
-            st = lens.to(torch.int32).to(ys.device, non_blocking=True)
+        ys, st = launch_rows(ys, start, "the descriptors take")
         table, desc = self.device_tables(ys.device)
-        ys = ys.to(torch.int64)
-        ys = ys if ys.shape[1] == 1 or ys.stride(1) == 1 else ys.contiguous()
         return DescRows(ops.smiles_desc(ys, st, table, desc, self.pad_id, self.eos_id,
                                         -1 if self.sep_id is None else self.sep_id))
 
@@ -363,10 +341,7 @@ def _error_terms(value, target, keep):
 def _mask(mask, n, device):
     if mask is None:
         return torch.ones(n, dtype=torch.bool, device=device)
-    mask = torch.as_tensor(mask).to(device).reshape(-1)
-    if mask.dtype != torch.bool or mask.numel() != n:
-        raise ValueError(f"mask must be {n} booleans, one per row")
-    return mask
+    return row_mask("mask", mask, n, device)
 
 
 def property_errors(values, targets, mask=None):

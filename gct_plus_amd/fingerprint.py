@@ -36,8 +36,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .decode import _int_vector
 from .molkey import SmilesKeys, as_int64, mix
+from .smiles import chunked, launch_rows, on_device, row_mask, row_spans
 
 _M = 0xFFFFFFFFFFFFFFFF
 
@@ -111,28 +111,18 @@ class SmilesFingerprints:
 
     # --------------------------------------------------------------------------------------------------- batches
     def fp_reference(self, ys, start):
-        """THE batch rule (gct_smiles_fp implements it), on the CPU.  Spans, the first <eos>, the width limit of 256 and
-        a start outside [0, W] are key_reference's: such a row has no bit and info (-1, 0, 0, 0).  Otherwise the content
-        is what stands in front of the first <eos>; with sep_id and a <sep> in it, the molecule BEHIND the first <sep> is
-        fingerprinted and the scaffold in front of it is not (a scaffold's fingerprint is fp_rows of the rows that
-        murcko_scaffolds returns)."""
-        ys = torch.as_tensor(ys)
-        SmilesKeys._check_batch(ys)
-        n, W = ys.shape
-        starts = [int(s) for s in torch.as_tensor(start).view(-1).tolist()]
-        if len(starts) != n:
-            raise ValueError(f"start must be {n} integers, one per row")
-        bits = torch.zeros(n, ops.FP_WORDS, dtype=torch.int64)
-        info = torch.zeros(n, 4, dtype=torch.int32)
-        for r, (row, t0) in enumerate(zip(ys.cpu().tolist(), starts)):
-            span = row[t0:] if 0 <= t0 <= W and W - t0 <= ops.FP_MAX_SPAN else []
-            if self.eos_id not in span:
+        """THE batch rule (gct_smiles_fp implements it), on the CPU.  Spans, absent rows and the two parts are
+        smiles.row_spans': an absent row has no bit and info (-1, 0, 0, 0).  Otherwise the molecule is fingerprinted; of
+        `scaffold <sep> molecule` that is the part BEHIND the first <sep>, and the scaffold in front of it is not (a
+        scaffold's fingerprint is fp_rows of the rows that murcko_scaffolds returns)."""
+        spans = row_spans(ys, start, self.eos_id, self.sep_id)
+        bits = torch.zeros(len(spans), ops.FP_WORDS, dtype=torch.int64)
+        info = torch.zeros(len(spans), 4, dtype=torch.int32)
+        for r, sp in enumerate(spans):
+            if sp.molecule is None:
                 info[r, 0] = -1
                 continue
-            content = span[:span.index(self.eos_id)]
-            if self.sep_id is not None and self.sep_id in content:
-                content = content[content.index(self.sep_id) + 1:]
-            status, words, atoms, nbonds = self._part(content)
+            status, words, atoms, nbonds = self._part(sp.molecule)
             bits[r] = torch.tensor([as_int64(w) for w in words])
             info[r] = torch.tensor([status, sum(bin(w).count("1") for w in words), atoms, nbonds])
         return FpRows(bits, info)
@@ -142,19 +132,8 @@ class SmilesFingerprints:
         [n] (on the CPU: checked there, as key_rows does) or an int32 tensor on the device (taken as it is: a row
         outside the range has no fingerprint).  ValueError for a span wider than 256 columns or a start outside
         [0, W]."""
-        SmilesKeys._check_batch(ys)
-        n, W = ys.shape
-        if torch.is_tensor(start) and start.device == ys.device and start.dtype == torch.int32 and ys.is_cuda:
-            st = start
-        else:
-            lens = _int_vector("start", start, n, 0, W, "the row width")
-            if n and W - int(lens.min()) > ops.FP_MAX_SPAN:
-                raise ValueError(f"a span of {W - int(lens.min())} columns: the fingerprints take at most "
-                                 f"{ops.FP_MAX_SPAN}")
-            st = lens.to(torch.int32).to(ys.device, non_blocking=True)
+        ys, st = launch_rows(ys, start, "the fingerprints take")
         table, labels = self.keys.device_tables(ys.device)
-        ys = ys.to(torch.int64)
-        ys = ys if ys.shape[1] == 1 or ys.stride(1) == 1 else ys.contiguous()
         return FpRows(*ops.smiles_fp(ys, st, table, labels, self.pad_id, self.eos_id,
                                      -1 if self.sep_id is None else self.sep_id))
 
@@ -241,10 +220,7 @@ def _agg(a, b, p=1, counts=None):
 def _present(fps, valid=None):
     keep = fps.info[:, 1] > 0
     if valid is not None:
-        valid = torch.as_tensor(valid).to(keep.device).reshape(-1)
-        if valid.dtype != torch.bool or valid.numel() != keep.numel():
-            raise ValueError(f"valid must be {keep.numel()} booleans, one per row")
-        keep = keep & valid
+        keep = keep & row_mask("valid", valid, keep.numel(), keep.device)
     return keep
 
 
@@ -334,17 +310,7 @@ class FingerprintIndex:
     @classmethod
     def from_smiles(cls, sampler, iterable, chunk=65536):
         """From SMILES strings, `chunk` at a time through sampler.fingerprints (one launch per chunk)."""
-        if int(chunk) < 1:
-            raise ValueError(f"chunk must be at least 1, got {chunk}")
-        chunks, batch = [], []
-        for s in iterable:
-            batch.append(s)
-            if len(batch) == int(chunk):
-                chunks.append(cls._kept(sampler.fingerprints(batch)))
-                batch = []
-        if batch:
-            chunks.append(cls._kept(sampler.fingerprints(batch)))
-        return cls._of(chunks)
+        return cls._of([cls._kept(sampler.fingerprints(batch)) for batch in chunked(iterable, chunk)])
 
     def save(self, path):
         torch.save({"bits": self.bits.cpu(), "counts": self.counts.cpu(), "fp_bits": self.shape[0],
@@ -363,12 +329,12 @@ class FingerprintIndex:
 
     def rows_on(self, device):
         """The index as an FpRows on `device` (copied once): info = (FP_GRAPH, count, 0, 0)."""
-        key = str(torch.device(device))
-        if key not in self._on:
+        def make():
             info = torch.zeros(len(self), 4, dtype=torch.int32, device=device)
             info[:, 1] = self.counts.to(device)
-            self._on[key] = FpRows(self.bits.to(device), info)
-        return self._on[key]
+            return FpRows(self.bits.to(device), info)
+
+        return on_device(self._on, device, make)
 
     def nearest(self, fps: FpRows, chunk=1 << 20):
         """(best fp32 [n], arg int32 [n]) of the rows of fps against the index, on their device: the largest T and the

@@ -10,7 +10,7 @@ SmilesKeys.key_rows) implements them and is compared with them bit for bit.
 The rule.  All arithmetic is in uint64 and wraps; every combination over neighbours or atoms is a SUM, so no order can
 leak in.  mix is splitmix64's finaliser.  L(a) is the FNV-1a 64-bit hash of the atom token's STRING (not its id: keys
 compare across vocabularies).  o(e) is the bond's label: the written symbol's (- 1, = 2, # 3, $ 4, : 5, ~ 6), without a
-symbol 5 between two aromatic atom tokens (decode.chem_atom_entry) and 1 otherwise.
+symbol 5 between two aromatic atom tokens (smiles.chem_atom_entry) and 1 otherwise.
   1. distance profile: c_0(a) = mix(L(a) + sum over b reachable from a, a included, of mix(L(b) ^ mix(dist(a, b) + 1)))
   2. ops.KEY_ROUNDS rounds: c_{r+1}(a) = mix(3 c_r(a) + sum over bonds (b, o) of a of mix(c_r(b) ^ mix(o + 0x100)))
   3. key = mix(sum over a of mix(c_R(a)) + atoms * 0x9E3779B97F4A7C15 + bonds)
@@ -30,8 +30,8 @@ from typing import NamedTuple
 import torch
 
 from . import ops
-from .decode import ChemReport, _int_vector, chem_atom_entry
 from .randomize import SmilesRandomizer
+from .smiles import ChemReport, chem_atom_entry, chunked, launch_rows, on_device, row_mask, row_spans
 
 _M = 0xFFFFFFFFFFFFFFFF
 GOLD = 0x9E3779B97F4A7C15
@@ -89,10 +89,11 @@ class SmilesKeys:
     """Identity keys of SMILES token rows over a target vocabulary, next to a SmilesRandomizer (self.randomizer: its
     grammar, its parse and its UNSUPPORTED set).  self.labels: the FNV-1a hash of every token's string; self.words:
     gct_smiles_key's table32, the randomiser's word | from bit 21 the key's label of a BOND token or `aromatic` of an ATOM
-    token.  ValueError for a vocabulary the randomiser rejects."""
+    token.  randomizer: a SmilesRandomizer over the same vocabulary and ids to share instead of building one.  ValueError
+    for a vocabulary the randomiser rejects."""
 
-    def __init__(self, itos, pad_id, eos_id, sep_id=None):
-        self.randomizer = rz = SmilesRandomizer(itos, pad_id, eos_id, sep_id)
+    def __init__(self, itos, pad_id, eos_id, sep_id=None, randomizer=None):
+        self.randomizer = rz = randomizer if randomizer is not None else SmilesRandomizer(itos, pad_id, eos_id, sep_id)
         self.grammar = g = rz.grammar
         self.pad_id, self.eos_id, self.sep_id = rz.pad_id, rz.eos_id, rz.sep_id
         self.labels = [fnv1a64(t) for t in g.itos]
@@ -112,10 +113,7 @@ class SmilesKeys:
 
     def device_tables(self, device):
         """(table32 int32 [V], label64 int64 [V]) on `device` (copied once)."""
-        key = str(torch.device(device))
-        if key not in self._device_tables:
-            self._device_tables[key] = (self.table.to(device), self.label_table.to(device))
-        return self._device_tables[key]
+        return on_device(self._device_tables, device, lambda: (self.table.to(device), self.label_table.to(device)))
 
     # ------------------------------------------------------------------------------------------------ one part
     def label(self, t):
@@ -179,37 +177,20 @@ class SmilesKeys:
         return status, as_int64(k)
 
     # --------------------------------------------------------------------------------------------------- batches
-    @staticmethod
-    def _check_batch(ys):
-        if ys.dim() != 2 or ys.shape[1] < 1:
-            raise ValueError(f"ys must be [n, W >= 1] token rows, got {list(ys.shape)}")
-        if ys.dtype.is_floating_point or ys.dtype.is_complex or ys.dtype == torch.bool:
-            raise ValueError(f"ys must hold integer token ids, got {ys.dtype}")
-
     def key_reference(self, ys, start):
-        """THE batch rule (gct_smiles_key implements it), on the CPU.  Row r's span is ys[r, start_r:]; a span without
-        <eos>, a span wider than 256 columns or a start outside [0, W]: keys 0, info (-1, -1, 0, 0).  Otherwise the
-        content is what stands in front of the first <eos>, and it is one part (the molecule) or, with sep_id and a <sep>
-        in it, the scaffold in front of the first <sep> and the molecule behind it, each through `key` on its own."""
-        ys = torch.as_tensor(ys)
-        self._check_batch(ys)
-        n, W = ys.shape
-        starts = [int(s) for s in torch.as_tensor(start).view(-1).tolist()]
-        if len(starts) != n:
-            raise ValueError(f"start must be {n} integers, one per row")
-        key = torch.zeros(n, 2, dtype=torch.int64)
-        info = torch.zeros(n, 4, dtype=torch.int32)
-        for r, (row, t0) in enumerate(zip(ys.cpu().tolist(), starts)):
-            span = row[t0:] if 0 <= t0 <= W and W - t0 <= ops.KEY_MAX_SPAN else []
-            if self.eos_id not in span:
+        """THE batch rule (gct_smiles_key implements it), on the CPU.  Spans, absent rows and the two parts are
+        smiles.row_spans': an absent row (no <eos> in its span, a span wider than 256 columns, a start outside [0, W]) has
+        keys 0 and info (-1, -1, 0, 0); otherwise the molecule and, where there is one, the scaffold go through `key`,
+        each on its own."""
+        spans = row_spans(ys, start, self.eos_id, self.sep_id)
+        key = torch.zeros(len(spans), 2, dtype=torch.int64)
+        info = torch.zeros(len(spans), 4, dtype=torch.int32)
+        for r, sp in enumerate(spans):
+            if sp.molecule is None:
                 info[r, 0] = info[r, 1] = -1
                 continue
-            content = span[:span.index(self.eos_id)]
-            sca = None
-            if self.sep_id is not None and self.sep_id in content:
-                s = content.index(self.sep_id)
-                sca, content = self._part(content[:s]), content[s + 1:]
-            mol = self._part(content)
+            sca = None if sp.scaffold is None else self._part(sp.scaffold)
+            mol = self._part(sp.molecule)
             key[r, 0] = as_int64(mol[1])
             key[r, 1] = as_int64(sca[1]) if sca else 0
             info[r] = torch.tensor([mol[0], sca[0] if sca else -1, mol[2], mol[3]])
@@ -220,18 +201,8 @@ class SmilesKeys:
         [n] (on the CPU: checked there, as SmilesRandomizer.randomize_rows does) or an int32 tensor on the device (taken
         as it is: a row outside the range has no key).  ValueError for a span wider than 256 columns or a start outside
         [0, W]."""
-        self._check_batch(ys)
-        n, W = ys.shape
-        if torch.is_tensor(start) and start.device == ys.device and start.dtype == torch.int32 and ys.is_cuda:
-            st = start
-        else:
-            lens = _int_vector("start", start, n, 0, W, "the row width")
-            if n and W - int(lens.min()) > ops.KEY_MAX_SPAN:
-                raise ValueError(f"a span of {W - int(lens.min())} columns: the keys take at most {ops.KEY_MAX_SPAN}")
-            st = lens.to(torch.int32).to(ys.device, non_blocking=True)
+        ys, st = launch_rows(ys, start, "the keys take")
         table, labels = self.device_tables(ys.device)
-        ys = ys.to(torch.int64)
-        ys = ys if ys.shape[1] == 1 or ys.stride(1) == 1 else ys.contiguous()
         return MolKeys(*ops.smiles_key(ys, st, table, labels, self.pad_id, self.eos_id,
                                        -1 if self.sep_id is None else self.sep_id))
 
@@ -258,9 +229,7 @@ def first_occurrence(keys, group=None, valid=None):
         k = mix_tensor(k ^ mix_tensor(group.reshape(-1).to(torch.int64)))
     rows = torch.arange(n, device=k.device)
     if valid is not None:
-        valid = torch.as_tensor(valid).to(k.device).reshape(-1)
-        if valid.dtype != torch.bool or valid.numel() != n:
-            raise ValueError(f"valid must be {n} booleans, one per row")
+        valid = row_mask("valid", valid, n, k.device)
         rows = torch.sort((~valid).to(torch.uint8), stable=True).indices      # the valid rows first, each side in row order
     ordered, order = torch.sort(k[rows], stable=True)
     rows = rows[order]
@@ -306,22 +275,11 @@ class MolKeyIndex:
     @classmethod
     def from_smiles(cls, sampler, iterable, chunk=65536, graph_only=True):
         """From SMILES strings, `chunk` at a time through sampler.molecule_keys (one launch per chunk)."""
-        if int(chunk) < 1:
-            raise ValueError(f"chunk must be at least 1, got {chunk}")
-        chunks, batch = [], []
-
-        def flush():
+        chunks = []
+        for batch in chunked(iterable, chunk):
             got = sampler.molecule_keys(batch)
             keep = got.info[:, 0] == ops.KEY_GRAPH if graph_only else got.info[:, 0] >= 0
             chunks.append(torch.unique(got.key[:, 0][keep]))
-            batch.clear()
-
-        for s in iterable:
-            batch.append(s)
-            if len(batch) == int(chunk):
-                flush()
-        if batch:
-            flush()
         if not chunks:
             return cls(torch.zeros(0, dtype=torch.int64))
         return cls(torch.cat(chunks))
@@ -342,10 +300,7 @@ class MolKeyIndex:
         """bool [n] on the keys' device: the key is in the index (torch.searchsorted; the index is copied to a device
         once)."""
         k = _molecule_column(keys)
-        dev = str(k.device)
-        if dev not in self._on:
-            self._on[dev] = self.keys.to(k.device)
-        mine = self._on[dev]
+        mine = on_device(self._on, k.device, lambda: self.keys.to(k.device))
         if mine.numel() == 0:
             return torch.zeros(k.shape, dtype=torch.bool, device=k.device)
         at = torch.searchsorted(mine, k.contiguous()).clamp_(max=mine.numel() - 1)

@@ -1375,7 +1375,7 @@ GRAMMAR_MAX_RINGS = 64
 def grammar_mask(logits2d, masked, table, ys, pos_dev, width=None, row_off=None, gram=None, item=None, prefix_len=None,
                  limit=None, kv_src=None, valid_off=0):
     """gct_grammar_mask, in front of select_token on the same device counter: masked [n, V] = logits2d where the grammar
-    (decode.SmilesGrammar; table int32 [V]) and the length budget allow the token as the next one of the row, -inf
+    (smiles.SmilesGrammar; table int32 [V]) and the length budget allow the token as the next one of the row, -inf
     elsewhere.  gram int32 [2] on the device = (budget G, prefix width t0_max), row r's prefix being t0_max - row_off[r]
     tokens; or item / prefix_len / limit as in select_token and the stream's state.  width: token columns of ys in use
     (default all).  Parked rows and rows inside their prefix are not written.
@@ -1412,7 +1412,8 @@ def grammar_mask(logits2d, masked, table, ys, pos_dev, width=None, row_off=None,
 # cap (bits 0..3, CHEM_NO_CAP: none) | H count << 4 | aromatic << 8 | carbon-like << 9 | bond order << 12
 CHEM_OK, CHEM_SYNTAX, CHEM_VALENCE, CHEM_RING_BOND, CHEM_AROMATIC = range(5)
 CHEM_NO_CAP = 15
-CHEM_MAX_SPAN = 256
+SMILES_MAX_SPAN = 256                               # columns of a row's span that every SMILES kernel stages
+CHEM_MAX_SPAN = SMILES_MAX_SPAN
 
 
 def _smiles_rows(name, ys, **vectors):
@@ -1474,7 +1475,7 @@ def _smiles_out(name, given, like, **wanted):
 
 def smiles_check(ys, start, table, chem, out=None):
     """gct_smiles_check: out int32 [n, 4] = (status, position, atoms, ring_bonds) of every row's span ys[r, start[r]:]
-    (decode.SmilesChemistry.check is the statement).  ys int64 [n, W] with unit column stride, start int32 [n] on the
+    (smiles.SmilesChemistry.check is the statement).  ys int64 [n, W] with unit column stride, start int32 [n] on the
     device with 0 <= start[r] <= W and W - start[r] <= 256 (the caller's to guarantee: a row outside that range is
     reported as SYNTAX at position 0), table / chem int32 [V] (SmilesChemistry.device_tables).  One launch."""
     n, W, ld = _smiles_rows("smiles_check", ys, start=(start, torch.int32))
@@ -1494,7 +1495,7 @@ def smiles_check(ys, start, table, chem, out=None):
 # (GCT_SITE_RANDOMIZE of csrc/common.h) and its per-token word:
 # class | ring number << 8 | bond order << 16 | unsupported (a / or \ bond, an atom with @) << 20
 RAND_OK, RAND_KEPT, RAND_SYNTAX, RAND_UNSUPPORTED, RAND_NO_RING, RAND_TOO_LONG = range(6)
-RAND_MAX_SPAN = 256
+RAND_MAX_SPAN = SMILES_MAX_SPAN
 RANDOMIZE_SITE = 0x5A11E5
 
 
@@ -1533,7 +1534,7 @@ def smiles_randomize(ys, start, key, table, ring_ids, n_rings, open_id, close_id
 # status codes of the molecule keys (GCT_KEY_* of include/gctplus_hip.h) and the rounds of refinement, GCT_KEY_ROUNDS
 KEY_GRAPH, KEY_STRING_SYNTAX, KEY_STRING_UNSUPPORTED = range(3)
 KEY_ROUNDS = 3
-KEY_MAX_SPAN = 256
+KEY_MAX_SPAN = SMILES_MAX_SPAN
 
 
 def smiles_key(ys, start, table32, label64, pad_id, eos_id, sep_id, out=None):
@@ -1554,7 +1555,7 @@ def smiles_key(ys, start, table32, label64, pad_id, eos_id, sep_id, out=None):
 
 # status codes of the Murcko scaffolds (GCT_SCA_* of include/gctplus_hip.h)
 SCA_OK, SCA_ACYCLIC, SCA_SYNTAX, SCA_UNSUPPORTED, SCA_NO_TOKEN, SCA_NO_RING, SCA_TOO_LONG = range(7)
-SCA_MAX_SPAN = 256
+SCA_MAX_SPAN = SMILES_MAX_SPAN
 
 
 def smiles_scaffold(ys, start, table32, label64, ring_ids, n_rings, open_id, close_id, pad_id, eos_id, sep_id, n_id,
@@ -1591,7 +1592,7 @@ FP_GRAPH, FP_SYNTAX, FP_UNSUPPORTED = range(3)
 FP_RADIUS = 2
 FP_BITS = 1024
 FP_WORDS = FP_BITS // 64
-FP_MAX_SPAN = 256
+FP_MAX_SPAN = SMILES_MAX_SPAN
 
 
 def smiles_fp(ys, start, table32, label64, pad_id, eos_id, sep_id, out=None):
@@ -1615,7 +1616,7 @@ DESC_OK, DESC_SYNTAX, DESC_UNSUPPORTED, DESC_UNKNOWN_ATOM = range(4)
 (DESC_STATUS, DESC_HEAVY_ATOMS, DESC_HYDROGENS, DESC_MW_MDA, DESC_CHARGE, DESC_HBD, DESC_HBA, DESC_ROTATABLE, DESC_RINGS,
  DESC_AROMATIC_RINGS, DESC_TPSA_CENTI, DESC_RING_BONDS) = range(12)
 DESC_COLUMNS = 12
-DESC_MAX_SPAN = 256
+DESC_MAX_SPAN = SMILES_MAX_SPAN
 
 
 def smiles_desc(ys, start, table32, desc32, pad_id, eos_id, sep_id, out=None):

@@ -1,6 +1,6 @@
 """SMILES randomisation (the reference's -randomize_prob, Utils/dataset.py:263-267 and Utils/smiles.py:494-502, without
 rdkit): a row's molecule written out again by a random depth-first traversal of the graph that
-decode.SmilesChemistry.check reads from it.  Atom tokens are carried verbatim and every bond keeps the symbol it was
+smiles.SmilesChemistry.check reads from it.  Atom tokens are carried verbatim and every bond keeps the symbol it was
 written with, or none; no stereo perception and no aromaticity model take part.
 
 SmilesRandomizer.randomize is THE statement for one part, randomize_reference the batch rule; gct_smiles_randomize
@@ -16,7 +16,8 @@ from typing import NamedTuple
 import torch
 
 from . import ops
-from .decode import SmilesGrammar, _CHEM_BOND_ORDERS, _int_vector, smiles_walk
+from .smiles import (SmilesGrammar, _CHEM_BOND_ORDERS, check_token_rows, launch_rows, on_device, row_spans,
+                     smiles_walk)
 
 MAX_DEGREE = 8                       # bonds per atom a part may have (more: UNSUPPORTED)
 _M0, _M1, _W0, _W1, _M32 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85, 0xFFFFFFFF
@@ -62,10 +63,11 @@ class SmilesRandomizer:
     `unsupported` on the bonds / and \\ and on an atom token whose string holds @).
     self.ring_ids: the ids of the ring numbers 1 .. 63 that the vocabulary spells, ascending by number, the
     single-character spelling where a number has both.  ValueError for a vocabulary SmilesGrammar rejects, or one without
-    `(` and `)`: no branch could be written."""
+    `(` and `)`: no branch could be written.  grammar: a SmilesGrammar over the same itos, pad_id and eos_id to share
+    instead of building one."""
 
-    def __init__(self, itos, pad_id, eos_id, sep_id=None):
-        self.grammar = g = SmilesGrammar(itos, pad_id, eos_id)
+    def __init__(self, itos, pad_id, eos_id, sep_id=None, grammar=None):
+        self.grammar = g = grammar if grammar is not None else SmilesGrammar(itos, pad_id, eos_id)
         self.pad_id, self.eos_id = g.pad_id, g.eos_id
         self.sep_id = None if sep_id is None else int(sep_id)
         if self.sep_id is not None and not (0 <= self.sep_id < len(g) and self.sep_id not in (g.pad_id, g.eos_id)):
@@ -93,11 +95,11 @@ class SmilesRandomizer:
 
     def device_tables(self, device):
         """(token table int32 [V], ring ids int32 [64], -1 behind the last) on `device` (copied once)."""
-        key = str(torch.device(device))
-        if key not in self._device_tables:
+        def make():
             rid = torch.tensor(self.ring_ids + [-1] * (64 - len(self.ring_ids)), dtype=torch.int32)
-            self._device_tables[key] = (self.table.to(device), rid.to(device))
-        return self._device_tables[key]
+            return self.table.to(device), rid.to(device)
+
+        return on_device(self._device_tables, device, make)
 
     # ------------------------------------------------------------------------------------------------ one part
     def parse(self, tokens):
@@ -245,11 +247,8 @@ class SmilesRandomizer:
         return ops.RAND_OK, out, perm
 
     # --------------------------------------------------------------------------------------------------- batches
-    def _check_batch(self, ys, start, key, p, out_width):
-        if ys.dim() != 2 or ys.shape[1] < 1:
-            raise ValueError(f"ys must be [n, W >= 1] token rows, got {list(ys.shape)}")
-        if ys.dtype.is_floating_point or ys.dtype.is_complex or ys.dtype == torch.bool:
-            raise ValueError(f"ys must hold integer token ids, got {ys.dtype}")
+    def _check_batch(self, ys, key, p, out_width):
+        check_token_rows(ys)
         n, W = ys.shape
         key = torch.as_tensor(key)
         if key.dtype.is_floating_point or key.dim() != 1 or key.numel() != n:
@@ -262,38 +261,29 @@ class SmilesRandomizer:
         return key.to(torch.int64), out_width
 
     def randomize_reference(self, ys, start, key, seed, p=1.0, out_width=None, return_perm=True):
-        """THE batch rule (gct_smiles_randomize implements it), on the CPU.  Row r's span is ys[r, start_r:]; a span
-        without <eos>, a span wider than 256 columns or a start outside [0, W] is a row-level SYNTAX: columns [0, W) are
-        copied and info = (SYNTAX, -1, span length or 0, 0).  Otherwise the content is what stands in front of the first
-        <eos>, whatever follows it is dropped, and the content is one part (part 0, the molecule) or, with sep_id and a
-        <sep> in it, the scaffold (part 1) in front of the first <sep> and the molecule behind it.  Each part goes through
-        `randomize` with stream(seed, key_r, part), the scaffold first.  room: the row may take
+        """THE batch rule (gct_smiles_randomize implements it), on the CPU.  Spans, absent rows and the two parts are
+        smiles.row_spans': an absent row is a row-level SYNTAX: columns [0, W) are copied and info = (SYNTAX, -1, span
+        length or 0, 0).  Otherwise whatever follows the first <eos> is dropped, the molecule is part 0 and the scaffold,
+        where there is one, part 1.  Each part goes through `randomize` with stream(seed, key_r, part), the scaffold
+        first.  room: the row may take
         min(out_width - start_r, 256) columns, less <eos>, less -- for the scaffold -- the <sep> and the molecule's input
         length, less -- for the molecule -- the <sep> and the scaffold's new length.
         Output row: columns [0, start_r) copied, the parts with <sep> between them, <eos>, <pad> up to out_width.
         info[2] = the new span length with <eos>; info[3] = atoms of the parts that are not SYNTAX; perm numbers the atoms
         across those parts in row order."""
         ys = torch.as_tensor(ys)
-        key, out_width = self._check_batch(ys, start, key, p, out_width)
+        key, out_width = self._check_batch(ys, key, p, out_width)
         n, W = ys.shape
-        starts = [int(s) for s in torch.as_tensor(start).view(-1).tolist()]
-        if len(starts) != n:
-            raise ValueError(f"start must be {n} integers, one per row")
+        spans = row_spans(ys, start, self.eos_id, self.sep_id)
         out = torch.full((n, out_width), self.pad_id, dtype=torch.int64)
         info = torch.zeros(n, 4, dtype=torch.int32)
         perm = torch.full((n, out_width), -1, dtype=torch.int32)
-        for r, (row, t0, k) in enumerate(zip(ys.cpu().tolist(), starts, key.tolist())):
-            ok = 0 <= t0 <= W and W - t0 <= ops.RAND_MAX_SPAN
-            span = row[t0:] if ok else []
-            if self.eos_id not in span:
+        for r, ((row, t0, length, scaffold, molecule), k) in enumerate(zip(spans, key.tolist())):
+            if molecule is None:
                 out[r, :W] = torch.tensor(row, dtype=torch.int64)
-                info[r] = torch.tensor([ops.RAND_SYNTAX, -1, len(span), 0])
+                info[r] = torch.tensor([ops.RAND_SYNTAX, -1, length, 0])
                 continue
-            content = span[:span.index(self.eos_id)]
-            parts = [(0, content)]
-            if self.sep_id is not None and self.sep_id in content:
-                s = content.index(self.sep_id)
-                parts = [(1, content[:s]), (0, content[s + 1:])]
+            parts = [(0, molecule)] if scaffold is None else [(1, scaffold), (0, molecule)]
             total = min(out_width - t0, ops.RAND_MAX_SPAN)
             new, atoms, pm, status = [], 0, [], {1: -1}
             for which, toks in parts:
@@ -315,19 +305,9 @@ class SmilesRandomizer:
         start ints [n] (on the CPU: checked there, as SmilesChemistry.check_rows does) or an int32 tensor on the device
         (taken as it is: a row outside the range is a row-level SYNTAX); key integers [n]; seed an int.  ValueError for a
         span wider than 256 columns, a start outside [0, W], p outside [0, 1] or out_width < W."""
-        key, out_width = self._check_batch(ys, start, key, p, out_width)
-        n, W = ys.shape
-        if torch.is_tensor(start) and start.device == ys.device and start.dtype == torch.int32 and ys.is_cuda:
-            st = start
-        else:
-            lens = _int_vector("start", start, n, 0, W, "the row width")
-            if n and W - int(lens.min()) > ops.RAND_MAX_SPAN:
-                raise ValueError(f"a span of {W - int(lens.min())} columns: the randomiser takes at most "
-                                 f"{ops.RAND_MAX_SPAN}")
-            st = lens.to(torch.int32).to(ys.device, non_blocking=True)
+        key, out_width = self._check_batch(ys, key, p, out_width)
+        ys, st = launch_rows(ys, start, "the randomiser takes")
         table, ring_ids = self.device_tables(ys.device)
-        ys = ys.to(torch.int64)
-        ys = ys if ys.shape[1] == 1 or ys.stride(1) == 1 else ys.contiguous()
         tokens, info, perm = ops.smiles_randomize(
             ys, st, key.to(ys.device, non_blocking=True), table, ring_ids, len(self.ring_ids), self.open_id, self.close_id,
             self.pad_id, self.eos_id, -1 if self.sep_id is None else self.sep_id, int(seed), float(p), out_width,

@@ -36,8 +36,8 @@ from typing import NamedTuple
 import torch
 
 from . import ops
-from .decode import _int_vector
 from .molkey import GOLD, SmilesKeys, as_int64, mix
+from .smiles import check_token_rows, launch_rows, row_spans
 
 
 class ScaffoldRows(NamedTuple):
@@ -61,11 +61,11 @@ def scaffold_match(sca: ScaffoldRows) -> torch.Tensor:
 class SmilesScaffolds:
     """Murcko scaffolds of SMILES token rows over a target vocabulary, next to a SmilesKeys (self.keys: its labels and
     table) and its SmilesRandomizer (self.randomizer: the parse, the UNSUPPORTED set and the write-out).  self.n_id /
-    self.nh_id: the ids of the tokens `n` and `[nH]`, None without one.  ValueError for a vocabulary the randomiser
-    rejects."""
+    self.nh_id: the ids of the tokens `n` and `[nH]`, None without one.  keys: a SmilesKeys over the same vocabulary and
+    ids to share instead of building one.  ValueError for a vocabulary the randomiser rejects."""
 
-    def __init__(self, itos, pad_id, eos_id, sep_id=None):
-        self.keys = ks = SmilesKeys(itos, pad_id, eos_id, sep_id)
+    def __init__(self, itos, pad_id, eos_id, sep_id=None, keys=None):
+        self.keys = ks = keys if keys is not None else SmilesKeys(itos, pad_id, eos_id, sep_id)
         self.randomizer = ks.randomizer
         self.pad_id, self.eos_id, self.sep_id = ks.pad_id, ks.eos_id, ks.sep_id
         names = list(ks.grammar.itos)
@@ -137,34 +137,26 @@ class SmilesScaffolds:
         return out_width
 
     def scaffold_reference(self, ys, start, out_width=None):
-        """THE batch rule (gct_smiles_scaffold implements it), on the CPU.  Spans as in SmilesKeys.key_reference: row r's
-        span is ys[r, start_r:]; a span without <eos>, a span wider than 256 columns or a start outside [0, W] is a row
-        without a scaffold (ScaffoldRows says what it gets).  Otherwise the content is what stands in front of the first
-        <eos>: the molecule, or, with sep_id and a <sep> in it, the GIVEN scaffold in front of the first <sep> -- keyed by
-        SmilesKeys' plain rule, whatever its status -- and the molecule behind it.  The molecule goes through `scaffold`
-        with room = min(out_width, 256) - 1: the spelling and its <eos> fit the output row and 256 tokens."""
+        """THE batch rule (gct_smiles_scaffold implements it), on the CPU.  Spans, absent rows and the two parts are
+        smiles.row_spans': an absent row is a row without a scaffold (ScaffoldRows says what it gets).  Otherwise the part
+        in front of the first <sep>, where there is one, is the GIVEN scaffold -- keyed by SmilesKeys' plain rule,
+        whatever its status -- and the molecule goes through `scaffold` with room = min(out_width, 256) - 1: the spelling
+        and its <eos> fit the output row and 256 tokens."""
         ys = torch.as_tensor(ys)
-        SmilesKeys._check_batch(ys)
+        check_token_rows(ys)                                   # (here too: ys is judged before out_width, start after it)
         n, W = ys.shape
         out_width = self._out_width(W, out_width)
-        starts = [int(s) for s in torch.as_tensor(start).view(-1).tolist()]
-        if len(starts) != n:
-            raise ValueError(f"start must be {n} integers, one per row")
+        spans = row_spans(ys, start, self.eos_id, self.sep_id)
         tokens = torch.full((n, out_width), self.pad_id, dtype=torch.int64)
         key = torch.zeros(n, 2, dtype=torch.int64)
         info = torch.zeros(n, 4, dtype=torch.int32)
         member = torch.full((n, W), -1, dtype=torch.int32)
-        for r, (row, t0) in enumerate(zip(ys.cpu().tolist(), starts)):
-            span = row[t0:] if 0 <= t0 <= W and W - t0 <= ops.SCA_MAX_SPAN else []
-            if self.eos_id not in span:
+        for r, sp in enumerate(spans):
+            if sp.molecule is None:
                 info[r, 0] = info[r, 1] = -1
                 continue
-            content = span[:span.index(self.eos_id)]
-            given = None
-            if self.sep_id is not None and self.sep_id in content:
-                s = content.index(self.sep_id)
-                given, content = self.keys._part(content[:s]), content[s + 1:]
-            status, spelt, mem, k = self.scaffold(content, min(out_width, ops.SCA_MAX_SPAN) - 1)
+            given = None if sp.scaffold is None else self.keys._part(sp.scaffold)
+            status, spelt, mem, k = self.scaffold(sp.molecule, min(out_width, ops.SCA_MAX_SPAN) - 1)
             tokens[r, :len(spelt) + 1] = torch.tensor(spelt + [self.eos_id], dtype=torch.int64)
             key[r, 0] = k
             key[r, 1] = as_int64(given[1]) if given else 0
@@ -177,22 +169,12 @@ class SmilesScaffolds:
         ints [n] (on the CPU: checked there, as SmilesKeys.key_rows does) or an int32 tensor on the device (taken as it
         is: a row outside the range has no scaffold).  ValueError for a span wider than 256 columns or a start outside
         [0, W]."""
-        SmilesKeys._check_batch(ys)
-        n, W = ys.shape
-        out_width = self._out_width(W, out_width)
-        if torch.is_tensor(start) and start.device == ys.device and start.dtype == torch.int32 and ys.is_cuda:
-            st = start
-        else:
-            lens = _int_vector("start", start, n, 0, W, "the row width")
-            if n and W - int(lens.min()) > ops.SCA_MAX_SPAN:
-                raise ValueError(f"a span of {W - int(lens.min())} columns: the scaffolds take at most "
-                                 f"{ops.SCA_MAX_SPAN}")
-            st = lens.to(torch.int32).to(ys.device, non_blocking=True)
+        check_token_rows(ys)                                   # (here too: ys is judged before out_width, start after it)
+        out_width = self._out_width(ys.shape[1], out_width)
+        ys, st = launch_rows(ys, start, "the scaffolds take")
         table, labels = self.keys.device_tables(ys.device)
         ring_ids = self.randomizer.device_tables(ys.device)[1]
         rz = self.randomizer
-        ys = ys.to(torch.int64)
-        ys = ys if ys.shape[1] == 1 or ys.stride(1) == 1 else ys.contiguous()
         none = lambda v: -1 if v is None else v
         return ScaffoldRows(*ops.smiles_scaffold(ys, st, table, labels, ring_ids, len(rz.ring_ids), rz.open_id,
                                                  rz.close_id, self.pad_id, self.eos_id, none(self.sep_id),

@@ -21,7 +21,7 @@ PAD_ID, SOS_ID, EOS_ID = 1, 2, 3
 SEP_ID = 4                # <sep> of the TRG_sep field (specials order unk, pad, sos, eos, sep); 2 in SRC_sep
 N_SYMBOLS = 26
 # A hand-made target vocabulary of the scaffold models' size (31 = 5 specials + 26 symbols, ids in the specials order
-# above) with at least one token of every class of decode.SmilesGrammar, two of them banned ring numbers / symbols: the
+# above) with at least one token of every class of smiles.SmilesGrammar, two of them banned ring numbers / symbols: the
 # strings behind the synthetic ids wherever a grammar is tested or measured.
 GRAMMAR_VOCAB = ["<unk>", "<pad>", "<sos>", "<eos>", "<sep>", "C", "c", "N", "O", "Br", "[nH]", "[C@@H]", "F", "=", "#",
                  "-", "/", "(", ")", "1", "2", "3", "%12", "%70", ".", "@", "+", "S", "n", "Cl", "o"]

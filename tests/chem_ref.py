@@ -1,4 +1,4 @@
-"""An independent oracle for decode.SmilesChemistry: it reads token STRINGS (None for an id outside the vocabulary) by
+"""An independent oracle for smiles.SmilesChemistry: it reads token STRINGS (None for an id outside the vocabulary) by
 recursive descent, builds explicit adjacency lists and judges them with its own code.  It shares nothing with
 SmilesChemistry but the rule text of its docstrings: no grammar table, no transition function, no bracket pattern.
 

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from gct_plus_amd import decode as D
+from gct_plus_amd.smiles import SmilesGrammar
 from tests import rng_ref as R
 
 SMC_SITE = 0x53C0DE
@@ -42,7 +43,7 @@ TOY_SCALE = 2.0
 
 class Toy:
     def __init__(self, seed=TOY_SEED):
-        self.gr = D.SmilesGrammar(TOY_VOCAB, TOY_PAD, TOY_EOS)
+        self.gr = SmilesGrammar(TOY_VOCAB, TOY_PAD, TOY_EOS)
         V = len(TOY_VOCAB)
         self.V = V
         g = torch.Generator().manual_seed(seed)

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from gct_plus_amd import data, synthetic
-from gct_plus_amd.decode import SmilesChemistry, SmilesGrammar
+from gct_plus_amd.smiles import SmilesChemistry, SmilesGrammar
 from tests.test_chem_host import (AROMATIC, CHEMV, EOS, INVALID, OK, PAD, RING_BOND, SYNTAX, VALENCE, VALID, VOCAB31,
                                   VOCAB70, ids_of, mixed_set, walk)
 from tests.test_mixed_scaffold_decode_gpu import TINY, mixed_prefixes

@@ -1,4 +1,4 @@
-"""The chemistry check on the host: decode.SmilesChemistry -- hand-written known answers over every status, the atom
+"""The chemistry check on the host: smiles.SmilesChemistry -- hand-written known answers over every status, the atom
 entries of every kind of atom token, `check` against the independent oracle of tests/chem_ref.py on random walks through
 the grammar and on single-token substitutions of valid molecules, validity_reward, and argument validation.  No GPU, no
 native library."""
@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from gct_plus_amd import ops, synthetic
-from gct_plus_amd.decode import ChemReport, SmilesChemistry, SmilesGrammar, chem_atom_entry
+from gct_plus_amd.smiles import ChemReport, SmilesChemistry, SmilesGrammar, chem_atom_entry
 from gct_plus_amd.Train.finetune import validity_reward
 from tests import chem_ref
 from tests.test_grammar_host import EOS, PAD, VOCAB31, VOCAB70

@@ -8,8 +8,9 @@ import pytest
 import torch
 
 from gct_plus_amd import synthetic
-from gct_plus_amd.decode import (GRAMMAR, KVDecoder, SmilesGrammar, generated_tokens, grammar_min_finish,
-                                 reference_style_decode, sample_filter_reference, score_tokens)
+from gct_plus_amd.decode import (GRAMMAR, KVDecoder, generated_tokens, reference_style_decode, sample_filter_reference,
+                                 score_tokens)
+from gct_plus_amd.smiles import SmilesGrammar, grammar_min_finish
 from tests.test_grammar_host import EOS, PAD, SOS, VOCAB31, VOCAB70, parses
 from tests.test_mixed_scaffold_decode_gpu import TINY, mixed_prefixes
 from tests.test_sample_filter_gpu import select

@@ -1,4 +1,4 @@
-"""Grammar-constrained decoding on the host: decode.SmilesGrammar -- the classification of a vocabulary, known answers of
+"""Grammar-constrained decoding on the host: smiles.SmilesGrammar -- the classification of a vocabulary, known answers of
 `allowed`, the closed form of the length budget against a breadth-first search, random walks through `allowed` against an
 independent recursive-descent parser of the token strings, and argument validation.  No GPU, no native library."""
 import random
@@ -7,8 +7,9 @@ import pytest
 import torch
 
 from gct_plus_amd import data, ops, synthetic
-from gct_plus_amd.decode import (G_END, GRAMMAR_START, TOP_K_FLOOR, KVDecoder, SmilesGrammar, check_grammar,
-                                 grammar_class, grammar_min_finish, grammar_step, sample_filter_reference)
+from gct_plus_amd.decode import TOP_K_FLOOR, KVDecoder, sample_filter_reference
+from gct_plus_amd.smiles import (G_END, GRAMMAR_START, SmilesGrammar, check_grammar, grammar_class, grammar_min_finish,
+                                 grammar_step)
 
 PAD, SOS, EOS, SEP = synthetic.PAD_ID, synthetic.SOS_ID, synthetic.EOS_ID, synthetic.SEP_ID
 VOCAB31 = synthetic.GRAMMAR_VOCAB                     # one token of every class, the scaffold models' 31 target tokens

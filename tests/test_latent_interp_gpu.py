@@ -324,7 +324,7 @@ def test_interpolate_smiles_end_to_end(cls_name, mtype):
 @pytest.mark.parametrize("cls_name,mtype", MTYPES)
 @torch.no_grad()
 def test_interpolate_smiles_options(cls_name, mtype):
-    from gct_plus_amd.decode import SmilesGrammar
+    from gct_plus_amd.smiles import SmilesGrammar
     P, A = 3, 3
     sp = make_sampler(cls_name, mtype)
     src0, src1, kw = pairs_for(sp, P)

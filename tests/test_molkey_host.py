@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from gct_plus_amd import ops
-from gct_plus_amd.decode import ChemReport
+from gct_plus_amd.smiles import ChemReport
 from gct_plus_amd.molkey import (MolKeyIndex, MolKeys, SmilesKeys, as_int64, basic_metrics, first_occurrence, mix,
                                  mix_tensor)
 from gct_plus_amd.randomize import SmilesRandomizer, stream

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from gct_plus_amd import data, ops, synthetic
-from gct_plus_amd.decode import SmilesChemistry
+from gct_plus_amd.smiles import SmilesChemistry
 from gct_plus_amd.randomize import SmilesRandomizer, stream
 from tests import randomize_ref as ref
 from tests.test_data_pipeline import SMILES as PIPELINE_SMILES

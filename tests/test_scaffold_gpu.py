@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from gct_plus_amd import data, ops as _ops, synthetic
-from gct_plus_amd.decode import ChemReport
+from gct_plus_amd.smiles import ChemReport
 from gct_plus_amd.molkey import scaffold_metrics
 from gct_plus_amd.scaffold import ScaffoldRows, SmilesScaffolds, scaffold_match
 from gct_plus_amd.Train.finetune import scaffold_reward

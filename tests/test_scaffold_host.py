@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from gct_plus_amd import ops
-from gct_plus_amd.decode import ChemReport
+from gct_plus_amd.smiles import ChemReport
 from gct_plus_amd.molkey import scaffold_metrics
 from gct_plus_amd.randomize import stream
 from gct_plus_amd.scaffold import ScaffoldRows, SmilesScaffolds, scaffold_match

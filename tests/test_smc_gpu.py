@@ -11,8 +11,9 @@ import pytest
 import torch
 
 from gct_plus_amd import ops, synthetic
-from gct_plus_amd.decode import (SMC, KVDecoder, SmcSamples, SmilesGrammar, StepPlan, reference_style_smc_decode,
-                                 score_tokens, smc_row_weights)
+from gct_plus_amd.decode import (SMC, KVDecoder, SmcSamples, StepPlan, reference_style_smc_decode, score_tokens,
+                                 smc_row_weights)
+from gct_plus_amd.smiles import SmilesGrammar
 from tests import rng_ref, smc_ref
 from tests.decode_step_ref import delta, seed_tensor
 from tests.test_beam_decode_gpu import TINY

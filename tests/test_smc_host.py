@@ -7,9 +7,10 @@ import pytest
 import torch
 
 from gct_plus_amd import data
-from gct_plus_amd.decode import (BEAM, GRAMMAR, MIXED, SBEAM, SMC, STREAM, UNIFORM, KVDecoder, SmcSamples, SmilesGrammar,
-                                 StepPlan, smc_finalize, smc_init, smc_row_weights, smc_step_reference,
+from gct_plus_amd.decode import (BEAM, GRAMMAR, MIXED, SBEAM, SMC, STREAM, UNIFORM, KVDecoder, SmcSamples, StepPlan,
+                                 smc_finalize, smc_init, smc_row_weights, smc_step_reference,
                                  systematic_resample_reference)
+from gct_plus_amd.smiles import SmilesGrammar
 from tests import smc_ref
 from tests.test_grammar_host import EOS, PAD, SOS, VOCAB31, VOCAB70, grammar, tiny_model
 

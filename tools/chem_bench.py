@@ -35,7 +35,7 @@ import torch  # noqa: E402
 
 from gct_plus_amd import ops, synthetic  # noqa: E402
 from gct_plus_amd.data import tokenize  # noqa: E402
-from gct_plus_amd.decode import SmilesChemistry  # noqa: E402
+from gct_plus_amd.smiles import SmilesChemistry  # noqa: E402
 
 MOLECULES = ["CCO", "c1ccccc1", "CC(=O)O", "C1CC1", "N#N", "c1cc[nH]c1", "CS(=O)(=O)C", "O=c1cccc[nH]1",
              "CC(=O)Oc1ccccc1C(=O)O", "Cn1cnc2c1c(=O)n(C)c(=O)n2C", "c1ccc2ccccc2c1", "c1ccncc1", "C[N+](C)(C)C",

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Policy-gradient fine-tuning end to end on a synthetic-weight pscavaetf (tiny by default, --full: d512 / 6 layers):
 --rounds times  sample --n molecules (multinomial, one scaffold) -> reward -> Train/finetune.reinforce_step.
-The reward is decode.SmilesGrammar.well_formed of the generated tokens (1 or 0), so no chemistry toolkit is needed: a
+The reward is smiles.SmilesGrammar.well_formed of the generated tokens (1 or 0), so no chemistry toolkit is needed: a
 randomly initialised model seldom closes its rings and branches and ends with <eos>, and the update teaches it to.
 Prints the well-formed rate of a fixed evaluation batch before and after -- with the number of DISTINCT strings in it and
 the policy's mean entropy per token, which show the collapse a reward alone ends in --, the rate of every round, and the
@@ -16,7 +16,7 @@ through the max_grad_norm argument of the two functions); the rounds then also p
 prescribed.
 
 --reward chemistry: the sampler decodes with well_formed=True (every row is syntactically right already) and the reward is
-Train/finetune.validity_reward of Sampling.check_rows -- decode.SmilesChemistry's valence / ring-bond / aromaticity check,
+Train/finetune.validity_reward of Sampling.check_rows -- smiles.SmilesChemistry's valence / ring-bond / aromaticity check,
 one launch on the device instead of the Python loop over the rows; the printed rate is then the VALID share.  The default,
 --reward grammar, is the run described above and prints what it always did.
 
@@ -103,7 +103,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from gct_plus_amd import data, synthetic  # noqa: E402
-from gct_plus_amd.decode import SmilesGrammar  # noqa: E402
+from gct_plus_amd.smiles import SmilesGrammar  # noqa: E402
 from gct_plus_amd.fingerprint import internal_diversity  # noqa: E402
 from gct_plus_amd.Inference.sampling_tool import DecodedRows, PscavaetfSampling  # noqa: E402
 from gct_plus_amd.Model import model_dict  # noqa: E402
@@ -281,7 +281,7 @@ print(f"evaluation batch of {a.n}: {WHAT} {before[0]:.3f} -> {after[0]:.3f}, dis
       f"{after[1]}, entropy per token {before[2]:.3f} -> {after[2]:.3f} after {a.rounds} rounds{reg}; "
       f"{'ppo_update' if a.ppo_epochs else 'reinforce_step'} median {float(np.median(ms[1:] or ms)):.2f} ms")
 if a.report_valid:
-    print(f"chemically valid share of the evaluation batch (decode.SmilesChemistry): {VALID_SHARE[0]:.3f} -> "
+    print(f"chemically valid share of the evaluation batch (smiles.SmilesChemistry): {VALID_SHARE[0]:.3f} -> "
           f"{VALID_SHARE[1]:.3f}")
 if a.report_unique:
     print(f"distinct molecules of the evaluation batch (molkey.SmilesKeys; a row without a graph counts as its string, one without "

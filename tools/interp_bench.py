@@ -48,7 +48,8 @@ from gct_plus_amd import data, ops  # noqa: E402
 from gct_plus_amd.Inference.mol_interpolation import interior_alphas, interp_plan, lerp, noise_ladder  # noqa: E402
 from gct_plus_amd.Inference.sampling_tool import PscavaetfSampling  # noqa: E402
 from gct_plus_amd.Model import model_dict  # noqa: E402
-from gct_plus_amd.decode import SmilesGrammar, generated_tokens  # noqa: E402
+from gct_plus_amd.decode import generated_tokens  # noqa: E402
+from gct_plus_amd.smiles import SmilesGrammar  # noqa: E402
 
 # well-known drug-like molecules (public SMILES), all carrying a benzene ring: the scaffold of every row
 MOLS = ["CC(=O)Oc1ccccc1C(=O)O", "CC(C)Cc1ccc(cc1)C(C)C(=O)O", "CC(=O)Nc1ccc(O)cc1", "CN1CCCC1c1cccnc1",

@@ -40,7 +40,7 @@ import torch  # noqa: E402
 
 from gct_plus_amd import ops, synthetic  # noqa: E402
 from gct_plus_amd.data import tokenize  # noqa: E402
-from gct_plus_amd.decode import ChemReport, SmilesChemistry  # noqa: E402
+from gct_plus_amd.smiles import ChemReport, SmilesChemistry  # noqa: E402
 from gct_plus_amd.molkey import MolKeyIndex, MolKeys, SmilesKeys, basic_metrics  # noqa: E402
 from gct_plus_amd.randomize import stream  # noqa: E402
 

@@ -44,7 +44,7 @@ import torch  # noqa: E402
 
 from gct_plus_amd import data, ops, synthetic  # noqa: E402
 from gct_plus_amd.data import tokenize  # noqa: E402
-from gct_plus_amd.decode import SmilesChemistry  # noqa: E402
+from gct_plus_amd.smiles import SmilesChemistry  # noqa: E402
 from gct_plus_amd.randomize import SmilesRandomizer  # noqa: E402
 
 MOLECULES = ["CCO", "c1ccccc1", "CC(=O)O", "C1CC1", "N#N", "c1cc[nH]c1", "CS(=O)(=O)C", "O=c1cccc[nH]1",

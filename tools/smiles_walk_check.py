@@ -35,7 +35,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from gct_plus_amd import ops, synthetic  # noqa: E402
-from gct_plus_amd.decode import SmilesChemistry  # noqa: E402
+from gct_plus_amd.smiles import SmilesChemistry  # noqa: E402
 from gct_plus_amd.descriptor import SmilesDescriptors  # noqa: E402
 from gct_plus_amd.fingerprint import FpRows, SmilesFingerprints, tanimoto_reference  # noqa: E402
 from gct_plus_amd.molkey import as_int64  # noqa: E402

@@ -36,7 +36,8 @@ import torch  # noqa: E402
 
 from gct_plus_amd import synthetic  # noqa: E402
 from gct_plus_amd.Model import model_dict  # noqa: E402
-from gct_plus_amd.decode import KVDecoder, SmilesGrammar  # noqa: E402
+from gct_plus_amd.decode import KVDecoder  # noqa: E402
+from gct_plus_amd.smiles import SmilesGrammar  # noqa: E402
 
 mtype = "pscavaetf"
 vs, vt = synthetic.vocab_sizes(mtype)
